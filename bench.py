@@ -18,11 +18,21 @@ state are unaffected (`--no-autotune` keeps the heuristic geometry) -- then W wa
 
 Prints ONE JSON line on rank 0.  `roofline` is for the dominant kernel (the dense sweep):
 algorithmic bytes = attempts x N x sizeof(J element) (one coupling-row read per attempt,
-SURVEY.md 8(d)) divided by its HIP-event-timed launch duration.  `cpu_baseline` times the CPU
-oracle (oracle/, a C restatement of the reference's algorithm; OpenMP over replicas) on a
-bounded sample of the same workload on the host cores, replays that sample on the GPU and
-reports the energy gap between the two (`energy_gap_vs_gpu`; 0 = bit-identical).
+SURVEY.md 8(d)) divided by its HIP-event-timed launch duration of the timed steps.
 `--workload c3 | c4 | c5 [--cities N]` run the CSR configurations of BASELINE.json.
+
+A plain run does only what the headline needs: set-up, warm-up, the timed steps, the line.
+`--full` adds everything measured beside it, each with runs of its own: the two bandwidth probes
+(the practical denominators of `roofline`), the storage and cached-local-field `variants`,
+`roofline_beyond_cache`, `cpu_baseline` and the `configs` lines of the other BASELINE configs.
+`cpu_baseline` times the CPU oracle (oracle/, a C restatement of the reference's algorithm; OpenMP
+over replicas) on a bounded sample of the same workload on the host cores, replays that sample on
+the GPU and reports the energy gap between the two (`energy_gap_vs_gpu`; 0 = bit-identical).
+
+`--dump-outputs DIR` writes, after the timed steps, the state those steps left on rank 0 -- what a
+caller of the sweep / exchange path reads back -- as DIR/<name>.npy (float32 / float64, at most
+64 MB; above that, the spins of a fixed seeded sample of replicas).  Inputs and the chain are
+seeded, so two builds can be compared array for array.
 """
 import argparse
 import json
@@ -630,6 +640,37 @@ def config_line(name, a, dev, local_rank, comm_dev, rank=0, world=1, dist=None, 
     return line
 
 
+DUMP_SPINS_BYTES = 48 << 20  # float32 spins written in full up to this size; the other arrays are O(replicas)
+
+
+def dump_outputs(eng, dirpath):
+    """What the timed path computed, as a caller of it receives it (this rank's engine): spins, energies,
+    temperatures, ladder permutation, acceptance counters and the best state.  Spins beyond DUMP_SPINS_BYTES
+    are a fixed seeded sample of whole replicas, their indices in spins_replicas.npy."""
+    os.makedirs(dirpath, exist_ok=True)
+    spins = eng.spins()
+    R, n = spins.shape
+    arrays = {}
+    if R * n * 4 > DUMP_SPINS_BYTES:
+        k = max(1, DUMP_SPINS_BYTES // (4 * n))
+        rows = np.sort(np.random.RandomState(0).choice(R, k, replace=False))
+        arrays["spins_replicas"] = rows.astype(np.float64)
+        spins = spins[rows]
+    arrays["spins"] = spins.astype(np.float32)
+    arrays["energies"] = eng.energies()
+    arrays["temperatures"] = eng.temperatures()
+    if eng.n_ladders > 0:
+        arrays["slot_map"] = eng.slot_map().astype(np.float64)
+    arrays["accepted"] = eng.stats()[0].astype(np.float64)
+    best_e, best_s, best_r = eng.best()
+    arrays["best_energy"] = np.asarray([best_e], np.float64)
+    arrays["best_replica"] = np.asarray([best_r], np.float64)
+    arrays["best_spins"] = best_s.astype(np.float32)
+    for name, arr in arrays.items():
+        np.save(os.path.join(dirpath, name + ".npy"), np.ascontiguousarray(arr))
+    return sorted(arrays)
+
+
 def spawn_ranks(n_ranks):
     """`python bench.py --gpus N` without torchrun: this process has made no GPU call yet; it
     starts N child processes of the same command line, one rank per GPU, with the rendezvous in
@@ -699,14 +740,14 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-variants", action="store_true")
     ap.add_argument("--no-configs", action="store_true",
-                    help="skip the short C3 / C4 / C5 lines that follow the headline in the default run")
+                    help="skip the short C3 / C4 / C5 lines that follow the headline in the --full run")
     ap.add_argument("--configs", default=None,
                     help="comma list of the config lines to run after the headline (c3,c4,c5,c5_1000,c5_1000_csr); "
                          "given explicitly it overrides --no-variants / --no-configs")
     ap.add_argument("--config-replicas", type=int, default=0,
                     help="replicas per rank of the c4 / c5 config lines (tests: a small sharded run against the same "
                          "global replica set on one rank)")
-    ap.add_argument("--no-c5-1000", action="store_true", help="skip the 1000-city lines of configs[4] in the default run")
+    ap.add_argument("--no-c5-1000", action="store_true", help="skip the 1000-city lines of configs[4] in the --full run")
     ap.add_argument("--no-c5-1000-csr", action="store_true",
                     help="skip only the stored-CSR 1000-city line (32 GB of couplings written out: ~15 s of set-up)")
     ap.add_argument("--no-beyond-cache", action="store_true",
@@ -721,7 +762,14 @@ def main():
                     help="keep torch.distributed in the path at --gpus 1: a one-rank process group (RCCL "
                          "with --backend nccl), started as a child process like the ranks of --gpus N; the "
                          "exchange step all-gathers through it.  Results equal the plain run")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, measure everything beside it (bandwidth probes, variants, "
+                         "roofline_beyond_cache, cpu_baseline, the configs lines); a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the state the timed steps left (rank 0) as DIR/<name>.npy, float32 / float64")
     a = ap.parse_args()
+    if a.configs is not None and not a.full:
+        ap.error("--configs selects lines of the --full run: add --full")
 
     if (a.gpus > 1 or a.force_dist) and "WORLD_SIZE" not in os.environ:
         return spawn_ranks(a.gpus)  # before anything here has touched the GPU
@@ -817,7 +865,7 @@ def main():
     # nothing but the steps and the final barrier lies between the warm-up and the end of timing.
     from spin_glass_anneal_rl_amd.engine import probe_read_bandwidth
     copy_gbs = read_gbs = None
-    if os.environ.get("SGA_BENCH_NOPROBE") is None:
+    if a.full and os.environ.get("SGA_BENCH_NOPROBE") is None:
         copy_gbs = measured_copy_bandwidth(dev)
         read_gbs = probe_read_bandwidth(local_rank)  # 4 GiB: beyond the caches
     torch.cuda.synchronize()
@@ -873,6 +921,8 @@ def main():
     best_e, _, _ = eng.best(with_spins=False)
     kernel_inst = eng.last_kernel()  # template arguments of what the timed steps launched (this engine's)
     roof = roofline_block(wl, a.workload, R, avg_launch_s, launches, kernel_inst, copy_gbs, read_gbs)
+    if a.dump_outputs and rank == 0:  # before anything below changes the engine's state
+        dump_outputs(eng, a.dump_outputs)
 
     out = {
         "metric": "spin-flip attempts/s (replicas x spins x sweeps / s)",
@@ -916,7 +966,7 @@ def main():
     # the same workload with the couplings held as int8 / as two bit-planes (what
     # coupling_storage="auto" picks for integer / ternary J; exact arithmetic, identical
     # chain): reported beside the fp32 headline
-    if a.workload == "c2a" and a.storage == "f32" and world == 1 and not a.no_variants:
+    if a.full and a.workload == "c2a" and a.storage == "f32" and world == 1 and not a.no_variants:
         out["variants"] = {}
         for name, st, bytes_per in (("int8_couplings", "i8", float(n)),
                                     ("bit_plane_couplings", "t2", n / 4.0)):
@@ -949,7 +999,7 @@ def main():
     # only when a proposal is ACCEPTED.  A variant with its own byte model -- B = acceptance rate x row
     # bytes per attempt (last sentence) -- reported beside the graded one-row-per-proposal
     # figure, never instead of it.  Storage = what the engine picks by itself for these couplings.
-    if a.workload == "c2a" and world == 1 and not a.no_variants:
+    if a.full and a.workload == "c2a" and world == 1 and not a.no_variants:
         # (sweeps between two exchange rounds go into ONE launch, as ParallelTempering.run / SpinGlassScheduler.anneal
         #  drive the engine: a launch of this variant lasts as long as its hottest replica's chain, and ten sweeps
         #  average that chain's fluctuations; `one_sweep_per_launch` is the figure of rounds 3's line)
@@ -1020,7 +1070,7 @@ def main():
     # C4's couplings are small integers: what the engine picks by itself there is one dword per entry
     # (24-bit column | 8-bit value), half the bytes of a row, the same chain -- a storage variant
     # with its own byte model, reported beside the fp32-value figure
-    if a.workload == "c4" and world == 1 and not a.no_variants:
+    if a.full and a.workload == "c4" and world == 1 and not a.no_variants:
         eng.set_csr_storage("auto")
         pt2 = ShardedTempering(eng, R_local=R, rank=0, world=1, seed=42, slot_temps=ladder,
                                n_ladders=n_ladders, dist=None, device=comm_dev)
@@ -1051,7 +1101,7 @@ def main():
     # fabric-side counters cannot tell from HBM.  The same kernel on a matrix far beyond every
     # cache (n = 32 768: 4.3 GB of fp32 couplings, same 1024 replicas, heuristic geometry) is the
     # genuinely HBM-bound figure: reported beside the headline, PMC passes under profiles/.
-    if a.workload == "c2a" and a.storage == "f32" and world == 1 and not a.no_variants and not a.no_beyond_cache:
+    if a.full and a.workload == "c2a" and a.storage == "f32" and world == 1 and not a.no_variants and not a.no_beyond_cache:
         nb = a.beyond_cache_spins
         Jb = make_sk_instance(nb, 7, dev)
         eng.set_tuning(waves_per_replica=0, sweeps_per_launch=1)
@@ -1081,6 +1131,8 @@ def main():
             "value": float(R) * nb * 2 / dtb, "unit_value": "attempts/s", "geometry": eng.describe(),
             "kernel": "sweep_dense_kernel", "kernel_instantiation": eng.last_kernel(), "cache_served": False}
         eng.set_dense(J, h, storage=a.storage)  # back to the headline instance (cpu_baseline replays on it)
+    if not a.full:
+        a.no_cpu_baseline = True
     substitute = None
     if csr is not None and csr[0] is None and not implicit and rank == 0 and world == 1 and not a.no_cpu_baseline:
         # An instance too large for a host copy (1000 cities: 32 GB of CSR; the CPU port indexes entries
@@ -1111,12 +1163,12 @@ def main():
                                            t_range=(t_hot, t_cold))
     else:
         out["cpu_baseline"] = None
-    # BASELINE configs[2], [3], [4] in the line the driver runs: short runs of the same engine calls as
+    # BASELINE configs[2], [3], [4] in the --full line: short runs of the same engine calls as
     # `--workload c3 | c4 | c5` (5 warm-up + 10 timed sweeps each), each with its own roofline and, at N = 1, a small
     # CPU sample.  With N > 1 ranks: configs[3] and [4] sharded over the ranks as BASELINE states them (every rank
     # takes part; rank 0 prints).
     wanted = None if a.configs is None else [c for c in a.configs.split(",") if c]
-    if a.workload == "c2a" and (wanted is not None or (not a.no_configs and not a.no_variants)):
+    if a.full and a.workload == "c2a" and (wanted is not None or (not a.no_configs and not a.no_variants)):
         eng.close()
         J = None
         wl.clear()

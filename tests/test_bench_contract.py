@@ -1,5 +1,6 @@
 """The bench.py output contract, checked on the committed lines of the last GPU runs
-(profiles/r0N_bench_*.json): the keys and types the driver and the judge read."""
+(profiles/r0N_bench_*.json): the keys and types the driver and the judge read; on the GPU, a plain
+run's line and its --dump-outputs arrays."""
 import glob
 import json
 import os
@@ -225,3 +226,51 @@ def test_round5_one_rank_rccl_line_carries_the_config_lines():
     for name in ("c4", "c5"):
         ex = d["configs"][name]["exchange"]
         assert ex["allgathers_timed"] == ex["rounds_timed"] >= 1 and 0 < ex["allgather_ms_per_round"] < 1.0
+
+
+def _bench(*args, timeout=600):
+    import subprocess
+    import sys
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + list(args), capture_output=True, text=True,
+                       timeout=timeout, env=env)
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = p.stdout.splitlines()
+    assert len(lines) == 1, p.stdout[:500]      # ONE JSON line and nothing else on stdout
+    return json.loads(lines[0])
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_headline_only_and_dumps_what_it_computed(tmp_path):
+    """`bench.py --steps K --warmup W` times the headline and nothing beside it; --dump-outputs writes the state the
+    timed steps left, float32 / float64 within 64 MB, identical from run to run (seeded inputs, seeded chain)."""
+    import numpy as np
+    import torch
+    import bench
+    import oracle
+    n, R, steps = 2000, 64, 12
+    args = ["--gpus", "1", "--steps", str(steps), "--warmup", "2", "--spins", str(n), "--replicas", str(R)]
+    d = _bench(*args, "--dump-outputs", str(tmp_path / "a"))
+    assert d["steps"] == steps and d["metric"].startswith("spin-flip attempts/s") and d["unit"] == "attempts/s"
+    assert d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert d["value"] == pytest.approx(R * n * steps / (d["ms_per_step"] * steps * 1e-3))
+    assert "variants" not in d and "configs" not in d and "roofline_beyond_cache" not in d
+    assert d["cpu_baseline"] is None and "measured_stream_read_GBs" not in d["roofline"]
+    _bench(*args, "--dump-outputs", str(tmp_path / "b"))
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b"))
+    assert {"spins.npy", "energies.npy", "temperatures.npy", "best_energy.npy", "best_spins.npy"} <= set(names)
+    total = 0
+    for f in names:
+        x, y = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert x.dtype in (np.float32, np.float64), f
+        assert np.array_equal(x, y), f
+        total += x.nbytes
+    assert total <= 64 << 20
+    spins, energies = np.load(tmp_path / "a" / "spins.npy"), np.load(tmp_path / "a" / "energies.npy")
+    assert spins.shape == (R, n) and energies.shape == (R,) and set(np.unique(spins)) <= {-1.0, 1.0}
+    # the energies the line's engine tracked belong to the spins it returns (the headline's instance, h = 0)
+    J = bench.make_sk_instance(n, 2, torch.device("cuda", 0)).cpu().numpy()
+    prob = oracle.Problem(J=J, h=np.zeros(n, np.float32))
+    assert np.array_equal(oracle.energy(prob, spins.astype(np.int8)), energies)
+    assert np.load(tmp_path / "a" / "best_energy.npy")[0] <= energies.min()

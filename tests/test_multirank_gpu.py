@@ -62,7 +62,7 @@ def test_bench_multirank_lines_of_configs_3_and_4_equal_the_one_rank_run():
     energies of all replicas, the global best and its replica equal the same global replica set on one rank, bit for bit."""
     two_gpus = torch.cuda.device_count() >= 2
     base = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--spins", "2000",
-            "--replicas", "64", "--no-autotune", "--no-variants", "--no-cpu-baseline", "--configs", "c4,c5"]
+            "--replicas", "64", "--no-autotune", "--no-variants", "--no-cpu-baseline", "--full", "--configs", "c4,c5"]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     runs = {}
     for world, per_rank in ((1, 256), (2, 128)):
@@ -205,7 +205,7 @@ def test_bench_force_dist_runs_the_rccl_path_on_one_gpu():
     and reports that the ranks' couplings agree."""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--force-dist", "--steps", "12",
            "--warmup", "2", "--spins", "2000", "--replicas", "64", "--no-variants", "--no-cpu-baseline",
-           "--configs", "c4,c5", "--config-replicas", "128"]
+           "--full", "--configs", "c4,c5", "--config-replicas", "128"]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env)
     assert p.returncode == 0, p.stderr[-2000:]
