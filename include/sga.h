@@ -117,6 +117,29 @@ int sga_set_csr(sga_engine *e, const int32_t *rowptr, const int32_t *colidx, con
 int sga_set_csr64(sga_engine *e, const int64_t *rowptr, const int32_t *colidx, const float *val,
                   const float *h, int n, int64_t nnz);
 
+/* M independent CSR problems of any sizes in one engine (version >= 600).  n_spins[M] (host); rowptr[sum n + 1] is
+ * ONE concatenated CSR: model m owns rows [row0_m, row0_m + n_m) with row0_m = n_0 + ... + n_{m-1}.  Its columns are
+ * model-local (in [0, n_m)), and its fields are h[row0_m ...].  Host or device pointers, as sga_set_csr.  Replicas are
+ * split evenly, as in sga_set_dense_batch: global replica g belongs to model g / (R_global / M) (R_global % M != 0 is
+ * SGA_ERR_INVALID at sga_init_replicas); with a ladder, pass n_ladders = M (a multiple of M).
+ *   Checks: sga_set_csr's per model (monotone extents, columns in [0, n_m), duplicates add up, unsorted rows allowed):
+ *   SGA_ERR_INVALID naming the model.  A non-zero diagonal or an asymmetric J: SGA_ERR_UNSUPPORTED.  Layouts that
+ *   need 64-bit extents, or a largest model beyond the narrow int8 form (~160 000 spins): SGA_ERR_UNSUPPORTED.
+ *   Spins are [R][sstride(n_max)], zero past n_m: sga_get_spins(r >= 0) / sga_get_best / sga_set_spins move
+ *   n_{model(r)} values, sga_get_spins(r < 0) writes [R_local][n_max] zero-padded, sga_init_replicas' s0 is
+ *   [R_local][n_max] (padding ignored); s0 == NULL draws replica g as a one-model engine of n_{model(g)} spins would.
+ *   Replay arrays and traces are [R][n_sweeps][n_max]: replica r uses the first n_{model(r)} entries of each sweep.
+ *   Everything sga_sweep does (rules, site modes, traces, schedules), sga_exchange (n_ladders = M),
+ *   sga_exchange_pairs (a pair across two models: SGA_ERR_INVALID), energies, sga_local_fields, best tracking,
+ *   stats, export / import, the checksum (n_spins[] included), sga_describe ("csr batch models=M n=min..max ...") and
+ *   the route calls work.  SGA_ERR_UNSUPPORTED: sga_set_field_cache(ON) (AUTO streams), the Wolff rule, sga_flip,
+ *   sga_update, sga_autotune, and any option that would pick a wide, bit-spin, several-updates-per-step or
+ *   cached-field form.  One launch per sweep call: the narrow one-update form, each wave running its own model. */
+int sga_set_csr_batch(sga_engine *e, int n_models, const int32_t *n_spins, const int64_t *rowptr,
+                      const int32_t *colidx, const float *val, const float *h, int64_t nnz);
+/* model m of a ragged batch: its spins and, once replicas exist, its first global replica and replica count */
+int sga_get_batch_model(sga_engine *e, int m, int *n_spins, int *first_replica, int *n_replicas);
+
 /* TSP-structured couplings that are never stored (BASELINE configs[4], examples/tsp_example.py
  * at 1000 cities: 10^6 spins whose CSR is 32 GB).  The problem is the one problems/routing.py:250-328
  * compiles, spin (c, p) = city c at tour position p, index c * n_cities + p, in the convention of
@@ -404,7 +427,7 @@ int sga_get_autotune_table(sga_engine *e, char *buf, int buflen);
 typedef struct sga_route_query {
     int32_t kind;         /* SGA_ROUTE_DENSE | SGA_ROUTE_CSR | SGA_ROUTE_TSP (sga_set_tsp) */
     int32_t n;            /* spins */
-    int32_t n_models;     /* dense batches (sga_set_dense_batch), else 1 */
+    int32_t n_models;     /* dense batches (sga_set_dense_batch), ragged CSR batches (sga_set_csr_batch), else 1 */
     int32_t R_local;      /* replicas on this engine (0: none yet) */
     int32_t cus;          /* compute units of the device (MI355X: 256) */
     int32_t tune_waves;   /* sga_set_tuning waves_per_replica (0 = heuristic) */

@@ -6,7 +6,10 @@ models goes in, one AnnealingResult per model comes out.  The reference loops a 
 over the models in a thread pool (:423-454).  Here models of equal size are stacked into ONE
 engine (`sga_set_dense_batch`): every model gets `replicas_per_model` replicas, a single
 kernel launch sweeps all of them (each replica reads its own model's coupling rows), and with
-more than one replica per model each model is its own temperature ladder.  Simulated
+more than one replica per model each model is its own temperature ladder.  Models with sparse couplings
+(`couplings.is_sparse`, the reference's default) of any sizes go, in input order and `batch_size` at a time, to
+ONE engine kept as CSR (`sga_set_csr_batch`: one launch per sweep call, each replica on its own model's rows);
+a chunk the ragged engine refuses (non-zero diagonal, asymmetric J) takes the stacked path.  Simulated
 annealing semantics per replica are those of GPUAnnealer (schedule, best at sweep ends).
 """
 import time
@@ -19,7 +22,8 @@ import torch
 from .engine import AnnealEngine
 from .exceptions import AnnealingError
 from .gpu_annealer import GPUAnnealerConfig, fresh_seed
-from .ising_model import IsingModel
+from . import _native as N
+from .ising_model import IsingModel, coo_to_csr
 from .result import AnnealingResult
 from .temperature_scheduler import TemperatureScheduler
 
@@ -62,9 +66,26 @@ class BatchProcessor:
         """Anneal every model; results come back in input order."""
         results: List[Optional[AnnealingResult]] = [None] * len(models)
         by_size: Dict[int, List[int]] = {}
+        sparse: List[int] = []
         for i, m in enumerate(models):
-            by_size.setdefault(m.n_spins, []).append(i)
+            if m.couplings.is_sparse:
+                sparse.append(i)
+            else:
+                by_size.setdefault(m.n_spins, []).append(i)
+        bs = self.batch_config.batch_size
+        for lo in range(0, len(sparse), bs):
+            part = sparse[lo:lo + bs]
+            t0 = time.time()
+            out = self._anneal_ragged([models[i] for i in part])
+            if out is None:  # refused by the ragged engine: the stacked path, by size
+                for i in part:
+                    by_size.setdefault(models[i].n_spins, []).append(i)
+                continue
+            for i, r in zip(part, out):
+                results[i] = r
+            self.batch_times.append(time.time() - t0)
         for _, idxs in sorted(by_size.items()):
+            idxs = sorted(idxs)
             for lo in range(0, len(idxs), self.batch_config.batch_size):
                 part = idxs[lo:lo + self.batch_config.batch_size]
                 t0 = time.time()
@@ -100,12 +121,33 @@ class BatchProcessor:
 
     # ------------------------------------------------------------------ one stacked run
     def _anneal_stack(self, models: List[IsingModel]) -> List[AnnealingResult]:
-        cfg, k = self.annealer_config, self.batch_config.replicas_per_model
         M, n = len(models), models[0].n_spins
-        t0 = time.time()
         J = np.stack([m.dense_couplings().detach().cpu().numpy().astype(np.float32) for m in models])
         h = np.stack([m.external_fields.detach().cpu().numpy().astype(np.float32) for m in models])
-        s0 = np.repeat(np.stack([m.spins_int8() for m in models]), k, axis=0)  # [M*k, n]
+        s0 = np.stack([m.spins_int8() for m in models])  # [M, n]
+        return self._run(models, lambda eng: eng.set_dense_batch(J, h, storage=self.annealer_config.coupling_storage), s0)
+
+    # ------------------------------------------------------------------ one ragged run (sparse models, any sizes)
+    def _anneal_ragged(self, models: List[IsingModel]) -> Optional[List[AnnealingResult]]:
+        """None when the ragged engine refuses the chunk (SGA_ERR_UNSUPPORTED: diagonal / asymmetric J)."""
+        problems = [coo_to_csr(m.couplings) + (m.external_fields.detach().cpu().numpy().astype(np.float32),)
+                    for m in models]
+        n_max = max(m.n_spins for m in models)
+        s0 = np.zeros((len(models), n_max), np.int8)  # [M, n_max], zero padded
+        for i, m in enumerate(models):
+            s0[i, :m.n_spins] = m.spins_int8()
+        try:
+            return self._run(models, lambda eng: eng.set_csr_batch(problems), s0)
+        except AnnealingError as err:
+            if (getattr(err, "details", None) or {}).get("code") == N.ERR_UNSUPPORTED:
+                return None
+            raise
+
+    def _run(self, models: List[IsingModel], set_problem, s0_models: np.ndarray) -> List[AnnealingResult]:
+        cfg, k = self.annealer_config, self.batch_config.replicas_per_model
+        M = len(models)
+        t0 = time.time()
+        s0 = np.repeat(s0_models, k, axis=0)  # [M*k, n]
         schedule = TemperatureScheduler.create_schedule(
             cfg.schedule_type, cfg.initial_temp, cfg.final_temp, cfg.n_sweeps, **cfg.schedule_params)
         if cfg.schedule_type.value == "adaptive":
@@ -113,7 +155,7 @@ class BatchProcessor:
         temps = np.maximum(np.asarray([schedule.update(s) for s in range(cfg.n_sweeps)]), 1e-10)
         hist_e = [[] for _ in range(M)]
         with AnnealEngine(self.device_index) as eng:
-            eng.set_dense_batch(J, h, storage=cfg.coupling_storage)
+            set_problem(eng)
             eng.init_replicas(M * k, seed=fresh_seed(cfg.random_seed), s0=s0)
             e0 = eng.energies().reshape(M, k).min(1)
             for m in range(M):

@@ -152,6 +152,22 @@ int recompute_energy_range(sga_engine *e, int r0, int count) {
     }
     const long long batched = e->opt[OPT_BATCHED_ENERGY];  // (one switch for both passes)
     const bool csr_all = batched == 2 || (batched == 1 && e->csr_acc != sga::CSR_ACC_F64_CANON);
+    if (e->ragged) {  // ragged CSR batches: one workgroup per replica over its model's rows
+        sga::EnergyArgs a{};
+        a.rowptr = e->rowptr64;
+        a.cv = e->cv;
+        a.h = e->h;
+        a.spins = e->spins + (long long)r0 * e->sstride;
+        a.energy = e->energy + r0;
+        a.n = e->n;
+        a.sstride = e->sstride;
+        a.R = count;
+        a.reps_per_model = e->Rg / e->n_models;
+        a.replica_base = e->replica0 + r0;
+        a.slices = 1;
+        HIPCHK(sga::launch_energy_csr_ragged(a, e->d_models, e->stream));
+        return SGA_OK;
+    }
     if (e->csr && !e->tsp && count >= 64 && csr_all) {
         // all replicas in one pass over the entries: spins transposed to bits, 32 replicas per lane
         // row groups: enough (group, replica word) threads to fill the chip -- ~4 waves per SIMD -- whatever
@@ -225,7 +241,7 @@ int ensure_packed(sga_engine *e) {
 extern "C" {
 
 const char *sga_last_error(void) { return g_last_error.c_str(); }
-int sga_version(void) { return 500; }  // round 5: + sga_explain_route / sga_get_route_query, sga_get_last_kernel, sga_get_autotune_table, ladder-local sga_exchange
+int sga_version(void) { return 600; }  // + sga_set_csr_batch / sga_get_batch_model (ragged CSR batches)  // round 5: + sga_explain_route / sga_get_route_query, sga_get_last_kernel, sga_get_autotune_table, ladder-local sga_exchange
 
 int sga_create(int device, sga_engine **out) {
     if (!out) return fail(SGA_ERR_INVALID, "out is NULL");
@@ -354,6 +370,8 @@ int sga_set_field_cache(sga_engine *e, int mode) {
     if (!e) return fail(SGA_ERR_INVALID, "engine is NULL");
     if (mode != SGA_FIELD_CACHE_OFF && mode != SGA_FIELD_CACHE_ON && mode != SGA_FIELD_CACHE_AUTO)
         return fail(SGA_ERR_INVALID, "bad field-cache mode");
+    if (mode == SGA_FIELD_CACHE_ON && e->ragged)
+        return fail(SGA_ERR_UNSUPPORTED, "cached local fields are not built for ragged CSR batches (AUTO runs the streaming form)");
     if (mode != e->field_cache) {
         // what an earlier mode learnt about these replicas does not carry over: ON runs every replica on the cached-field
         // kernel (AUTO's per-replica routes would leave some on the row kernels for good), a failed allocation under
@@ -421,7 +439,8 @@ static int init_replicas_body(sga_engine *e, int R_local, int R_global, int repl
         if (rc != SGA_OK) return rc;
         e->sstride = (int)e->ld;
     } else {
-        const sga_route::CsrForm f = sga_route::csr_replica_form(route_query_of(e));
+        const sga_route::CsrForm f = e->ragged ? sga_route::csr_ragged_form(route_query_of(e))
+                                               : sga_route::csr_replica_form(route_query_of(e));
         if (f.error) return fail(SGA_ERR_UNSUPPORTED, f.error);
         e->big = f.bits;
         e->big_form = f.big_form;
@@ -461,7 +480,13 @@ static int init_replicas_body(sga_engine *e, int R_local, int R_global, int repl
         int rc = in.init(e->scratch[1], s0, (size_t)R_local * e->n, e->stream);
         if (rc != SGA_OK) return rc;
         HIPCHK(sga::launch_pad_spins(in.ptr, e->n, e->spins, e->sstride, R_local, e->stream));
+        if (e->ragged)  // [R][n_max]: what lies past a replica's model is padding
+            HIPCHK(sga::launch_mask_spins_ragged(e->spins, e->sstride, R_local, (uint32_t)replica0, e->d_models,
+                                                 R_global / e->n_models, e->stream));
         HIPCHK(hipStreamSynchronize(e->stream));
+    } else if (e->ragged) {
+        HIPCHK(sga::launch_init_spins_ragged(e->spins, e->sstride, R_local, (uint32_t)seed, (uint32_t)(seed >> 32),
+                                             (uint32_t)replica0, e->d_models, R_global / e->n_models, e->stream));
     } else {
         HIPCHK(sga::launch_init_spins(e->spins, e->n, e->sstride, R_local, (uint32_t)seed,
                                       (uint32_t)(seed >> 32), (uint32_t)replica0, e->stream));
@@ -488,6 +513,9 @@ int sga_set_ladder(sga_engine *e, const double *slot_temps, int n_ladders) {
     if (e->R <= 0) return fail(SGA_ERR_INVALID, "no replicas");
     if (n_ladders <= 0 || e->Rg % n_ladders != 0)
         return fail(SGA_ERR_INVALID, "R_global must be a multiple of n_ladders");
+    if (e->ragged && n_ladders % e->n_models != 0)
+        return fail(SGA_ERR_INVALID, "ragged CSR batches: n_ladders must be a multiple of the number of models "
+                                     "(a ladder lies within one model)");
     HIPCHK(hipSetDevice(e->device));
     dev_free(e->slot_temps);
     dev_free(e->slot_to_rep);
@@ -604,6 +632,7 @@ int sga_sweep(sga_engine *e, int n_sweeps, int site_mode, int arith, const doubl
     // (the Wolff rule reports compute_energy() after every sweep as well, spin_dynamics.py:87)
     const bool wolff = e->rule == SGA_RULE_WOLFF;
     if (wolff) {
+        if (e->ragged) return fail(SGA_ERR_UNSUPPORTED, "the Wolff rule is not implemented for ragged CSR batches");
         if (e->tsp) return fail(SGA_ERR_UNSUPPORTED, "the Wolff rule is not implemented for sga_set_tsp problems");
         if (sga::wolff_lds_bytes(n) > 160 * 1024 - 256)
             return fail(SGA_ERR_UNSUPPORTED, "the Wolff rule keeps spins, cluster and queue in LDS: n <= ~31 000");
@@ -844,6 +873,10 @@ int sga_sweep(sga_engine *e, int n_sweeps, int site_mode, int arith, const doubl
         a.no_best = exact_mode ? 1 : 0;
         a.reps_per_model = e->n_models > 1 ? e->Rg / e->n_models : 0;
         a.model_stride_j = (long long)e->n * e->ldj;
+        if (e->ragged) {
+            a.ragged = e->ragged_at;
+            a.reps_per_model = e->Rg / e->n_models;
+        }
         a.seed_lo = (uint32_t)e->seed;
         a.seed_hi = (uint32_t)(e->seed >> 32);
         a.sweep0 = e->sweeps_done + (uint32_t)k0;
@@ -988,6 +1021,8 @@ int sga_set_update_rule(sga_engine *e, int rule) {
         return fail(SGA_ERR_UNSUPPORTED, "update rule not implemented by the engine");
     if (rule == SGA_RULE_WOLFF && e->tsp)
         return fail(SGA_ERR_UNSUPPORTED, "the Wolff rule is not implemented for sga_set_tsp problems");
+    if (rule == SGA_RULE_WOLFF && e->ragged)
+        return fail(SGA_ERR_UNSUPPORTED, "the Wolff rule is not implemented for ragged CSR batches");
     e->rule = rule;
     return SGA_OK;
 }
@@ -1028,8 +1063,12 @@ static int point_op(sga_engine *e, int r, const int32_t *sites, int count, int o
         HIPCHK(hipMemcpy(hs.data(), sites, sizeof(int32_t) * hs.size(), hipMemcpyDeviceToHost));
     else
         std::memcpy(hs.data(), sites, sizeof(int32_t) * hs.size());
+    if (e->ragged && op != 0)
+        return fail(SGA_ERR_UNSUPPORTED, "single-site flip / update are not implemented for ragged CSR batches "
+                                         "(sga_sweep and sga_local_fields are)");
+    const int n_r = spins_of(e, r);
     for (int32_t v : hs)
-        if (v < 0 || v >= e->n) return fail(SGA_ERR_INVALID, "site index out of range");
+        if (v < 0 || v >= n_r) return fail(SGA_ERR_INVALID, "site index out of range");
     if (op == 2 && e->rule == SGA_RULE_WOLFF)
         return fail(SGA_ERR_UNSUPPORTED, "sga_update applies single-site rules; Wolff moves run through sga_sweep");
     if (e->tsp) {  // structured couplings: local fields only (flip / update go through sweeps)
@@ -1060,6 +1099,13 @@ static int point_op(sga_engine *e, int r, const int32_t *sites, int count, int o
         a.cv = e->cv;
         a.h = e->h + model * e->n;
         a.diag = e->diag + model * e->n;
+        if (e->ragged) {  // the model's rows (its columns are model-local)
+            const int row0 = e->model_row0[(size_t)model_of(e, r)];
+            a.model_offset_j = 0;
+            a.rowptr = e->rowptr64 + row0;
+            a.h = e->h + row0;
+            a.diag = e->diag + row0;
+        }
         a.spins = e->spins + (long long)r * e->sstride;
         a.energy = e->energy + r;
         a.n_accepted = e->n_acc + r;
@@ -1067,7 +1113,7 @@ static int point_op(sga_engine *e, int r, const int32_t *sites, int count, int o
         a.out = d_out;
         a.ld = e->ld;
         a.ldj = e->ldj;
-        a.n = e->n;
+        a.n = n_r;
         a.count = count;
         a.op = op;
         a.arith = arith;
@@ -1185,6 +1231,14 @@ int sga_exchange_pairs(sga_engine *e, const double *energies_global, const int32
     if (is_device_ptr(pairs)) return fail(SGA_ERR_INVALID, "pairs must be a host buffer");
     for (int k = 0; k < 2 * count; ++k)
         if (pairs[k] < 0 || pairs[k] >= e->Rg) return fail(SGA_ERR_INVALID, "slot index out of range");
+    if (e->ragged) {  // slots of a ladder hold replicas of its model only: a pair across two models is refused
+        const int reps = e->Rg / e->n_models;
+        for (int k = 0; k < count; ++k)
+            if (pairs[2 * k] / reps != pairs[2 * k + 1] / reps)
+                return fail(SGA_ERR_INVALID, "ragged CSR batch: pair " + std::to_string(k) + " joins slots of models " +
+                                                 std::to_string(pairs[2 * k] / reps) + " and " +
+                                                 std::to_string(pairs[2 * k + 1] / reps));
+    }
     HIPCHK(hipSetDevice(e->device));
     hipStream_t st = e->stream;
     DevIn<double> d_e, d_u;

@@ -133,6 +133,13 @@ struct sga_engine {
     // problem
     int n = 0;
     int n_models = 1;  // dense batches: models stacked row-wise, replicas split evenly
+    // ragged CSR batches (sga_set_csr_batch): n_models CSR problems of any sizes concatenated row-wise, replicas split
+    // evenly; n = the largest model's spins (the replica layout), n_rows = the rows of the concatenation
+    bool ragged = false;
+    int n_rows = 0;
+    std::vector<int> model_n, model_row0;
+    int2 *d_models = nullptr;  // [n_models] {first row, spins}: what the ragged kernels read (inside h's allocation,
+    int ragged_at = 0;         // ragged_at floats in: SweepArgs::ragged)
     bool csr = false;
     bool want_i8 = false, acc64 = false;
     bool acc_canon = false;  // acc64 and the fp64 row sum is not provably exact: canonical summation order
@@ -268,6 +275,12 @@ struct sga_engine {
         dev_free(epart);
         epart_bytes = 0;
         clf_problem = false;
+        d_models = nullptr;  // (part of h)
+        ragged_at = 0;
+        ragged = false;
+        n_rows = 0;
+        model_n.clear();
+        model_row0.clear();
         n = 0;
         ld = 0;
     }
@@ -305,6 +318,12 @@ struct sga_engine {
 };
 
 namespace sga_impl {
+
+// ragged CSR batches: the model of local replica r and its spins (any other engine: model 0 with n spins)
+inline int model_of(const sga_engine *e, int r) {
+    return e->ragged && e->Rg > 0 ? (e->replica0 + r) / (e->Rg / e->n_models) : 0;
+}
+inline int spins_of(const sga_engine *e, int r) { return e->ragged ? e->model_n[(size_t)model_of(e, r)] : e->n; }
 
 inline int elems_per_chunk(bool i8) { return i8 ? 1024 : 256; }
 // Zeroed (column 0, value 0) entries behind the CSR entry array.  The sweep kernels load a row's entries without

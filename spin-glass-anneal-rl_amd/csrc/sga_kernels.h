@@ -92,6 +92,11 @@ struct SweepArgs {
     const int *clf_hq;   // [n] table_scale * h_i as integers (the static part of the local field)
     int clf_row_max;     // entries of the longest row of the layout (slot padding included)
     uint32_t seed_lo, seed_hi, sweep0, replica0;
+    // ragged CSR batches (sga_set_csr_batch): replica r belongs to model (replica0 + r) / reps_per_model, whose
+    // {first row in the concatenated CSR, spins} is entry m of an int2 table that starts `ragged` floats into h
+    // (behind the models' fields, 8-byte aligned).  0: one model | dense batches (the fields above).  (An int, not a
+    // pointer: it fills the struct's tail padding, so no other kernel's argument block changes.)
+    int ragged;
 };
 
 // TSP-structured couplings that are never stored (sweep_tsp.hip): scaled distance tables + penalties
@@ -131,6 +136,8 @@ struct EnergyArgs {
     int slices;
     double *partial;
 };
+// ragged CSR batches: replica r over the rows of model models[(replica_base + r) / reps_per_model] (one slice)
+hipError_t launch_energy_csr_ragged(const EnergyArgs &a, const int2 *models, hipStream_t st);
 hipError_t launch_energy_finish(const double *partial, int slices, double *energy, int R,
                                 hipStream_t st);
 
@@ -234,6 +241,12 @@ hipError_t launch_repack_dense(const float *J, long long ldJ, long long rows, in
 // the lowest set bit (0: no non-zero value): is the fp64 sum of a row exact in any order?
 hipError_t launch_scan_values(const float *v, long long rows, long long cols, long long ld,
                               int *flags, hipStream_t st);
+// ragged CSR batches: replica r as a one-model engine of models[(replica0 + r) / reps].y spins would draw it
+hipError_t launch_init_spins_ragged(int8_t *spins, int sstride, int R, uint32_t seed_lo, uint32_t seed_hi,
+                                    uint32_t replica0, const int2 *models, int reps, hipStream_t st);
+// ... and the padding past each replica's model zeroed (spins handed over as [R][n_max])
+hipError_t launch_mask_spins_ragged(int8_t *spins, int sstride, int R, uint32_t replica0, const int2 *models,
+                                    int reps, hipStream_t st);
 hipError_t launch_pad_spins(const int8_t *src, int n, int8_t *dst, int sstride, int R,
                             hipStream_t st);
 hipError_t launch_unpad_spins(const int8_t *src, int sstride, int8_t *dst, int n, int R,

@@ -1176,4 +1176,101 @@ hipError_t ensure_lds_limit(const void *kernel, size_t lds_bytes) {
     if (e == hipSuccess) have = lds_bytes;
     return e;
 }
+// ---------------------------------------------------------------------------------------
+// ragged CSR batches (sga_set_csr_batch): init / masking / energies per replica model
+// ---------------------------------------------------------------------------------------
+// Ragged CSR batches: energy_csr_kernel<true> (one slice) over the rows of the replica's model -- the model's first
+// row and spins come from `models`, its columns are model-local (the LDS spin slice as it stands).
+__global__ void __launch_bounds__(256) energy_csr_ragged_kernel(const EnergyArgs a, const int2 *models) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int r = blockIdx.x;
+    const int2 model = models[(a.replica_base + r) / a.reps_per_model];
+    const long long *rowptr = a.rowptr + model.x;
+    const float *h = a.h + model.x;
+    int8_t *s = reinterpret_cast<int8_t *>(smem);
+    double *red = reinterpret_cast<double *>(smem + a.sstride);
+    {
+        const int4 *src = reinterpret_cast<const int4 *>(a.spins + (long long)r * a.sstride);
+        int4 *dst = reinterpret_cast<int4 *>(smem);
+        for (int i = tid; i < a.sstride / 16; i += blockDim.x) dst[i] = src[i];
+    }
+    __syncthreads();
+    double e_acc = 0.0, h_acc = 0.0;
+    for (int i = w; i < model.y; i += 4) {
+        double acc = 0.0;
+        for (long long j = rowptr[i] + lane; j < rowptr[i + 1]; j += 64) {
+            const int2 ent = a.cv[j];
+            acc += (double)(__int_as_float(ent.y) * (float)s[ent.x]);
+        }
+        const float mv_i = (float)wave_sum(acc);
+        const double si = (double)s[i];
+        e_acc += (double)mv_i * si;
+        h_acc += (double)h[i] * si;
+    }
+    if (lane == 0) {
+        red[w] = e_acc;
+        red[4 + w] = h_acc;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        const double e = (red[0] + red[1]) + (red[2] + red[3]);
+        const double hs = (red[4] + red[5]) + (red[6] + red[7]);
+        a.energy[r] = -0.5 * (double)(float)e + (-(double)(float)hs);
+    }
+}
+hipError_t launch_energy_csr_ragged(const EnergyArgs &a, const int2 *models, hipStream_t st) {
+    const size_t lds = (size_t)a.sstride + 64;
+    if (!models || a.reps_per_model <= 0 || lds > 160 * 1024 - 256) return hipErrorInvalidValue;
+    hipError_t e = ensure_lds_limit(reinterpret_cast<const void *>(energy_csr_ragged_kernel), lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(energy_csr_ragged_kernel, dim3(a.R), dim3(256), lds, st, a, models);
+    return hipGetLastError();
+}
+
+// ragged CSR batches: init_spins_kernel with the spins of the replica's model (the same Philox words)
+__global__ void init_spins_ragged_kernel(int8_t *spins, int sstride, int R, uint32_t seed_lo, uint32_t seed_hi,
+                                         uint32_t replica0, const int2 *models, int reps) {
+    const int nblk = (sstride + 127) / 128;
+    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (long long)R * nblk) return;
+    const int r = (int)(idx / nblk), blk = (int)(idx - (long long)r * nblk);
+    const int n = models[(replica0 + (uint32_t)r) / (uint32_t)reps].y;
+    const u32x4 w = philox4x32_10((uint32_t)blk, 0u, replica0 + (uint32_t)r, DOMAIN_INIT, seed_lo,
+                                  seed_hi);
+    const uint32_t words[4] = {w.x, w.y, w.z, w.w};
+    int8_t *dst = spins + (long long)r * sstride;
+    for (int q = 0; q < 128; ++q) {
+        const int i = blk * 128 + q;
+        if (i >= sstride) break;
+        const uint32_t bit = (words[q >> 5] >> (q & 31)) & 1u;
+        dst[i] = (i < n) ? (bit ? 1 : -1) : 0;
+    }
+}
+hipError_t launch_init_spins_ragged(int8_t *spins, int sstride, int R, uint32_t seed_lo, uint32_t seed_hi,
+                                    uint32_t replica0, const int2 *models, int reps, hipStream_t st) {
+    if (reps <= 0) return hipErrorInvalidValue;
+    const long long total = (long long)R * ((sstride + 127) / 128);
+    hipLaunchKernelGGL(init_spins_ragged_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st,
+                       spins, sstride, R, seed_lo, seed_hi, replica0, models, reps);
+    return hipGetLastError();
+}
+__global__ void mask_spins_ragged_kernel(int8_t *spins, int sstride, int R, uint32_t replica0, const int2 *models,
+                                         int reps) {
+    const long long total = (long long)R * sstride;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
+         i += (long long)gridDim.x * blockDim.x) {
+        const long long r = i / sstride, c = i - r * sstride;
+        if (c >= models[(replica0 + (uint32_t)r) / (uint32_t)reps].y) spins[i] = 0;
+    }
+}
+
+hipError_t launch_mask_spins_ragged(int8_t *spins, int sstride, int R, uint32_t replica0, const int2 *models,
+                                    int reps, hipStream_t st) {
+    if (reps <= 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(mask_spins_ragged_kernel, dim3(grid_for((long long)R * sstride)), dim3(256), 0, st, spins,
+                       sstride, R, replica0, models, reps);
+    return hipGetLastError();
+}
 }  // namespace sga

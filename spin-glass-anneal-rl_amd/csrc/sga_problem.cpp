@@ -593,4 +593,200 @@ int sga_set_tsp(sga_engine *e, const float *dist, int64_t ld, int n_cities, floa
     return SGA_OK;
 }
 
+// Ragged CSR batches: M independent problems of any sizes in one engine, their rows concatenated (model m owns rows
+// [row0_m, row0_m + n_m), its columns model-local).  Each model gets sga_set_csr's structure checks -- the same scan
+// kernels over the model's rows (extents offset to its first row, columns bounded by its n) -- and its own class;
+// the batch runs the most general accumulation class and the widest accept table any model needs (why every model's
+// chain stays exact: sweep_csr_impl.h, RAGGED).  The layout is the plain (column, value) one: the narrow one-update
+// form is the only one built for ragged batches.
+int sga_set_csr_batch(sga_engine *e, int n_models, const int32_t *n_spins, const int64_t *rowptr,
+                      const int32_t *colidx, const float *val, const float *h, int64_t nnz) {
+    if (!e) return fail(SGA_ERR_INVALID, "engine is NULL");
+    if (n_models <= 0 || !n_spins || !rowptr || !h || nnz < 0 || (nnz > 0 && (!colidx || !val)))
+        return fail(SGA_ERR_INVALID, "bad CSR batch arguments");
+    if (is_device_ptr(n_spins)) return fail(SGA_ERR_INVALID, "n_spins must be a host array");
+    long long total = 0;
+    int n_max = 0;
+    for (int m = 0; m < n_models; ++m) {
+        if (n_spins[m] <= 0) return fail(SGA_ERR_INVALID, "model " + std::to_string(m) + ": n_spins <= 0");
+        total += n_spins[m];
+        n_max = std::max(n_max, (int)n_spins[m]);
+    }
+    if (total >= (long long)INT32_MAX || nnz + CSR_TAIL_PAD >= (int64_t)INT32_MAX)
+        return fail(SGA_ERR_UNSUPPORTED, "CSR batch needs 64-bit row extents (ragged batches run the narrow form, "
+                                         "32-bit extents only)");
+    if (sga::csr_waves_per_block((n_max + 15) / 16 * 16, 0) < 1)
+        return fail(SGA_ERR_UNSUPPORTED, "CSR batch: the largest model (" + std::to_string(n_max) +
+                                             " spins) does not fit the narrow int8 form's LDS slice");
+    const int N = (int)total;
+    HIPCHK(hipSetDevice(e->device));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    e->free_replicas();
+    e->free_problem();
+    e->opt_stale = 0;
+    e->csr = true;
+    e->from_dense = false;
+    e->n = N;  // (rows, while the layout is built; the largest model's spins below)
+    e->n_models = n_models;
+    e->nnz = nnz;
+    const size_t np1 = (size_t)N + 1;
+    auto bail = [&](int code, const std::string &msg) {
+        (void)hipStreamSynchronize(e->stream);
+        dev_free(e->colidx);
+        dev_free(e->val);
+        e->free_problem();
+        return fail(code, msg);
+    };
+    auto check = [&](hipError_t he) -> int {
+        return he == hipSuccess ? SGA_OK : bail(he == hipErrorOutOfMemory ? SGA_ERR_MEMORY : SGA_ERR_DEVICE, hipGetErrorString(he));
+    };
+#define SGA_BATCH_CHK(expr)                  \
+    do {                                     \
+        const int _rc = check(expr);         \
+        if (_rc != SGA_OK) return _rc;       \
+    } while (0)
+    SGA_BATCH_CHK(hipMalloc(&e->rowptr64, sizeof(long long) * np1));
+    SGA_BATCH_CHK(hipMemcpyAsync(e->rowptr64, rowptr, sizeof(long long) * np1, hipMemcpyDefault, e->stream));
+    const size_t nz = (size_t)std::max<int64_t>(nnz, 1);
+    const int32_t *ci = colidx;
+    const float *vv = val;
+    if (nnz > 0 && !is_device_ptr(colidx)) {
+        SGA_BATCH_CHK(hipMalloc(&e->colidx, sizeof(int32_t) * nz));
+        SGA_BATCH_CHK(hipMemcpyAsync(e->colidx, colidx, sizeof(int32_t) * nz, hipMemcpyHostToDevice, e->stream));
+        ci = e->colidx;
+    }
+    if (nnz > 0 && !is_device_ptr(val)) {
+        SGA_BATCH_CHK(hipMalloc(&e->val, sizeof(float) * nz));
+        SGA_BATCH_CHK(hipMemcpyAsync(e->val, val, sizeof(float) * nz, hipMemcpyHostToDevice, e->stream));
+        vv = e->val;
+    }
+    // h, then the model table {first row, spins} 8-byte aligned behind it (SweepArgs::ragged: the sweep kernel finds
+    // it through h)
+    const int h_floats = (N + 1) & ~1;
+    SGA_BATCH_CHK(hipMalloc(&e->h, sizeof(float) * (size_t)h_floats + sizeof(int2) * (size_t)n_models));
+    SGA_BATCH_CHK(hipMemcpyAsync(e->h, h, sizeof(float) * (size_t)N, hipMemcpyDefault, e->stream));
+    e->d_models = reinterpret_cast<int2 *>(e->h + h_floats);
+    SGA_BATCH_CHK(hipMalloc(&e->diag, sizeof(float) * (size_t)N));
+    SGA_BATCH_CHK(hipMemsetAsync(e->diag, 0, sizeof(float) * (size_t)N, e->stream));  // (a diagonal is refused below)
+
+    int flags[sga::CSR_FLAG_COUNT] = {0};
+    auto scan = [&](auto &&launch) -> hipError_t {
+        hipError_t he = hipMemsetAsync(e->d_flags, 0, sizeof(flags), e->stream);
+        if (he == hipSuccess) he = launch();
+        if (he == hipSuccess) he = hipMemcpyAsync(flags, e->d_flags, sizeof(flags), hipMemcpyDeviceToHost, e->stream);
+        return he == hipSuccess ? hipStreamSynchronize(e->stream) : he;
+    };
+    SGA_BATCH_CHK(scan([&] { return sga::launch_csr_check_rowptr(e->rowptr64, N, nnz, e->d_flags, e->stream); }));
+    if (flags[sga::CSR_BAD_ROWPTR])
+        return bail(SGA_ERR_INVALID, "CSR batch rowptr is not monotone or does not span [0, nnz]");
+    std::vector<long long> src(np1);
+    SGA_BATCH_CHK(hipMemcpyAsync(src.data(), e->rowptr64, sizeof(long long) * np1, hipMemcpyDeviceToHost, e->stream));
+    SGA_BATCH_CHK(hipStreamSynchronize(e->stream));
+
+    // per model: the scans of sga_set_csr, then its class; the batch takes the most general class and the widest table
+    int acc_b = sga::CSR_ACC_F32_TABLE, scale_b = 1;
+    bool sorted_b = true;
+    float m_b = 0.0f;
+    std::vector<int> row0((size_t)n_models);
+    std::vector<int2> models((size_t)n_models);
+    for (int m = 0, r0 = 0; m < n_models; r0 += n_spins[m], ++m) {
+        const int nm = n_spins[m];
+        row0[(size_t)m] = r0;
+        models[(size_t)m] = make_int2(r0, nm);
+        const std::string who = "model " + std::to_string(m) + ": ";
+        SGA_BATCH_CHK(scan([&] { return sga::launch_csr_scan(e->rowptr64 + r0, ci, vv, e->h + r0, nm, e->d_flags, e->stream); }));
+        if (flags[sga::CSR_BAD_COLUMN])
+            return bail(SGA_ERR_INVALID, who + "CSR column index out of range [0, " + std::to_string(nm) + ")");
+        if (flags[sga::CSR_DIAGONAL])
+            return bail(SGA_ERR_UNSUPPORTED, who + "non-zero diagonal entry (ragged CSR batches need a zero diagonal)");
+        const bool sorted = !flags[sga::CSR_UNSORTED];
+        sorted_b = sorted_b && sorted;
+        const long long mnnz = src[(size_t)r0 + nm] - src[(size_t)r0];
+        const double avg_deg = (double)mnnz / nm;
+        int sym[sga::CSR_FLAG_COUNT];
+        std::memcpy(sym, flags, sizeof(sym));
+        if (sorted || (double)mnnz * avg_deg <= 4.0e10) {
+            SGA_BATCH_CHK(scan([&] { return sga::launch_csr_symmetry(e->rowptr64 + r0, ci, vv, nm, sorted, e->d_flags, e->stream); }));
+            sym[sga::CSR_ASYMMETRIC] = flags[sga::CSR_ASYMMETRIC];
+        } else {
+            sym[sga::CSR_ASYMMETRIC] = 1;
+        }
+        if (sym[sga::CSR_ASYMMETRIC])
+            return bail(SGA_ERR_UNSUPPORTED, who + "asymmetric J (ragged CSR batches need J[i][j] == J[j][i])");
+        // sga_set_csr's classification of this model alone
+        float mm;
+        std::memcpy(&mm, &sym[sga::CSR_ROW_ABS_MAX], sizeof(mm));
+        int table_m = 0, scale = 1;
+        if (!sym[sga::CSR_NOT_INTEGRAL] && mm >= 1.0f && mm < 16777216.0f) {
+            table_m = 1;
+        } else if ((sym[sga::CSR_NOT_INTEGRAL] & 5) == 0 && mm >= 1.0f && mm < 8388608.0f && e->opt[OPT_HALF_TABLE] != 0) {
+            table_m = 1;
+            scale = 2;
+        }
+        long long max_len = 0;
+        for (int i = r0; i < r0 + nm; ++i) max_len = std::max(max_len, src[(size_t)i + 1] - src[(size_t)i]);
+        int carry = 0;
+        while ((1ll << carry) < std::max<long long>(max_len, 1)) ++carry;
+        const int e_hi = sym[sga::CSR_EXP_HI] - 1024, e_lo = 1024 - sym[sga::CSR_EXP_LO];
+        const bool any = sym[sga::CSR_EXP_HI] != 0;
+        const bool j_int = (sym[sga::CSR_NOT_INTEGRAL] & 1) == 0;
+        int acc;
+        if (j_int && mm < 16777216.0f) acc = table_m > 0 ? sga::CSR_ACC_F32_TABLE : sga::CSR_ACC_F32;
+        else if (!any || (e_hi - e_lo + 1 + carry) <= 52) acc = sga::CSR_ACC_F64;
+        else acc = sga::CSR_ACC_F64_CANON;
+        acc_b = std::max(acc_b, acc);
+        if (acc == sga::CSR_ACC_F32_TABLE) scale_b = std::max(scale_b, scale);
+        m_b = std::max(m_b, mm);
+    }
+    if (e->opt[OPT_FORCE_CSR_ACC] > 0) acc_b = std::max(acc_b, std::min(3, (int)e->opt[OPT_FORCE_CSR_ACC]));
+    e->csr_acc = acc_b;
+    e->table_scale = acc_b == sga::CSR_ACC_F32_TABLE ? scale_b : 1;
+    e->table_m = acc_b == sga::CSR_ACC_F32_TABLE ? (int)std::min((double)e->table_scale * m_b, 2048.0) : 0;
+    e->csr_row_abs_max = m_b;
+    e->csr_sorted = sorted_b;
+    e->consistent_dE = true;
+    e->clf_csr_problem = false;
+    // the plain layout: (column, value) interleaved, CSR_TAIL_PAD zeroed entries behind
+    long long *src_ptr = nullptr;
+    SGA_BATCH_CHK(hipMalloc(&src_ptr, sizeof(long long) * np1));
+    hipError_t he = hipMemcpyAsync(src_ptr, e->rowptr64, sizeof(long long) * np1, hipMemcpyDeviceToDevice, e->stream);
+    int rc = he == hipSuccess ? build_layout(e, src, false) : fail(SGA_ERR_DEVICE, hipGetErrorString(he));
+    if (rc == SGA_OK) {
+        he = hipMalloc(&e->cv, sizeof(int2) * (size_t)(e->layout_entries + CSR_TAIL_PAD));
+        if (he == hipSuccess) he = hipMemsetAsync(e->cv + e->layout_entries, 0, sizeof(int2) * CSR_TAIL_PAD, e->stream);
+        if (he == hipSuccess) he = sga::launch_pack_cv_rows(src_ptr, e->rowptr64, ci, vv, nullptr, e->cv, N, e->stream);
+        if (he == hipSuccess)
+            he = hipMemcpyAsync(e->d_models, models.data(), sizeof(int2) * (size_t)n_models, hipMemcpyHostToDevice, e->stream);
+        if (he == hipSuccess) he = hipStreamSynchronize(e->stream);
+        if (he != hipSuccess) rc = fail(he == hipErrorOutOfMemory ? SGA_ERR_MEMORY : SGA_ERR_DEVICE, hipGetErrorString(he));
+    }
+    dev_free(src_ptr);
+    dev_free(e->colidx);
+    dev_free(e->val);
+    if (rc != SGA_OK) {
+        const std::string msg = g_last_error;
+        e->free_problem();
+        return fail(rc, msg);
+    }
+#undef SGA_BATCH_CHK
+    e->ragged = true;
+    e->ragged_at = h_floats;
+    e->n_rows = N;
+    e->n = n_max;
+    e->model_n.assign(n_spins, n_spins + n_models);
+    e->model_row0 = row0;
+    return SGA_OK;
+}
+
+int sga_get_batch_model(sga_engine *e, int m, int *n_spins, int *first_replica, int *n_replicas) {
+    if (!e) return fail(SGA_ERR_INVALID, "engine is NULL");
+    if (!e->ragged) return fail(SGA_ERR_INVALID, "not a ragged CSR batch (sga_set_csr_batch)");
+    if (m < 0 || m >= e->n_models) return fail(SGA_ERR_INVALID, "model index out of range");
+    if (n_spins) *n_spins = e->model_n[(size_t)m];
+    const int reps = e->Rg > 0 ? e->Rg / e->n_models : 0;
+    if (first_replica) *first_replica = m * reps;
+    if (n_replicas) *n_replicas = reps;
+    return SGA_OK;
+}
+
 }  // extern "C"

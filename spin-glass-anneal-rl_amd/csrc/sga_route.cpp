@@ -155,7 +155,23 @@ int csr_updates_per_step(const Query &q) {
     return v;
 }
 
+CsrForm csr_ragged_form(const Query &q) {
+    CsrForm f;
+    f.table_m = q.table_m;
+    f.sstride = (q.n + 15) / 16 * 16;  // the largest model's spins
+    f.waves = 1;
+    if (sga::csr_waves_per_block(f.sstride, 0) < 1) f.error = "ragged CSR batch: the largest model does not fit the narrow int8 form";
+    else if (q.tune_waves > 1) f.error = "ragged CSR batches run one wave per replica (sga_set_tuning waves_per_replica > 1 picks a wide form)";
+    else if (q.opt[OPT_FORCE_CSR_BITS] != 0) f.error = "ragged CSR batches hold int8 spins (option \"force_csr_bits\" picks a bit-spin form)";
+    else if (q.opt[OPT_CSR_UPDATES_PER_STEP] > 0)
+        f.error = "ragged CSR batches run one update per step (option \"csr_updates_per_step\" > 0 picks another form)";
+    else if (q.storage == SGA_CSR_STORAGE_PACKED) f.error = "ragged CSR batches read (column, value) entries (packed storage refused)";
+    if (sga::csr_waves_per_block(f.sstride, f.table_m) < 1) f.table_m = 0;  // no room for the table: general path
+    return f;
+}
+
 CsrForm csr_replica_form(const Query &q) {
+    if (q.n_models > 1) return csr_ragged_form(q);
     CsrForm f;
     const int R_local = q.R_local;
     f.table_m = q.table_m;
@@ -296,6 +312,8 @@ TspForm tsp_form(int npad, int tune_waves) {
 // fit LDS, and CSR problems with integer J in strictly sorted rows -- any single-site rule.
 const char *clf_refusal(const Query &q) {
     if (q.kind == SGA_ROUTE_TSP) return "cached local fields: stored couplings only";
+    if (q.kind == SGA_ROUTE_CSR && q.n_models > 1)
+        return "cached local fields: not built for ragged CSR batches (sga_set_csr_batch runs the streaming narrow form)";
     if (q.kind == SGA_ROUTE_CSR) {
         // sparse couplings: the dynamic part of the fields as int16 in LDS (sweep_clf_csr.hip)
         const long long ldf = ((long long)q.n + 127) / 128 * 128;
@@ -370,6 +388,15 @@ std::string explain(const Query &q0) {
                       t.waves, t.passes, (long long)q.opt[OPT_TSP_PARALLEL],
                       q.opt[OPT_TSP_PARALLEL] == 0 ? "sweep_tsp_kernel" : "sweep_tsp_par_kernel|sweep_tsp_kernel");
         out = buf;
+    } else if (q.kind == SGA_ROUTE_CSR && q.n_models > 1) {
+        const CsrForm f = csr_ragged_form(q);
+        if (f.error) return std::string("csr error=") + f.error;
+        std::snprintf(buf, sizeof(buf),
+                      "csr form=narrow ragged models=%d spins=int8 waves=1 replicas_per_block=%d updates_per_step=1 slots=0 "
+                      "entries=cv table_m=%d sstride=%d",
+                      q.n_models, sga::csr_waves_per_block(f.sstride, f.table_m), f.table_m, f.sstride);
+        out = buf;
+        q.sstride = f.sstride;
     } else if (q.kind == SGA_ROUTE_CSR) {
         const CsrForm f = csr_replica_form(q);
         if (f.error) return std::string("csr error=") + f.error;

@@ -56,7 +56,7 @@ int sga_get_spins(sga_engine *e, int r, int8_t *out) {
     if (e->R <= 0 || r >= e->R) return fail(SGA_ERR_INVALID, "bad replica index");
     HIPCHK(hipSetDevice(e->device));
     if (r >= 0) {
-        HIPCHK(hipMemcpyAsync(out, e->spins + (long long)r * e->sstride, (size_t)e->n,
+        HIPCHK(hipMemcpyAsync(out, e->spins + (long long)r * e->sstride, (size_t)spins_of(e, r),
                               hipMemcpyDefault, e->stream));
     } else {
         HIPCHK(hipMemcpy2DAsync(out, (size_t)e->n, e->spins, (size_t)e->sstride, (size_t)e->n,
@@ -71,7 +71,7 @@ int sga_set_spins(sga_engine *e, int r, const int8_t *s) {
     if (e->R <= 0 || r < 0 || r >= e->R) return fail(SGA_ERR_INVALID, "bad replica index");
     HIPCHK(hipSetDevice(e->device));
     HIPCHK(hipMemsetAsync(e->spins + (long long)r * e->sstride, 0, (size_t)e->sstride, e->stream));
-    HIPCHK(hipMemcpyAsync(e->spins + (long long)r * e->sstride, s, (size_t)e->n, hipMemcpyDefault,
+    HIPCHK(hipMemcpyAsync(e->spins + (long long)r * e->sstride, s, (size_t)spins_of(e, r), hipMemcpyDefault,
                           e->stream));
     e->fields_valid = false;
     int rc = recompute_energy_range(e, r, 1);
@@ -99,7 +99,7 @@ int sga_get_best(sga_engine *e, int r, double *energy, int8_t *spins, int *r_out
     if (energy) *energy = be[r];
     if (r_out) *r_out = r;
     if (spins) {
-        HIPCHK(hipMemcpyAsync(spins, e->best_spins + (long long)r * e->sstride, (size_t)e->n,
+        HIPCHK(hipMemcpyAsync(spins, e->best_spins + (long long)r * e->sstride, (size_t)spins_of(e, r),
                               hipMemcpyDefault, e->stream));
         HIPCHK(hipStreamSynchronize(e->stream));
     }
@@ -126,7 +126,8 @@ int sga_get_stats(sga_engine *e, int64_t *accepted, int64_t *attempted) {
     }
     if (attempted) {
         if (is_device_ptr(attempted)) return fail(SGA_ERR_INVALID, "attempted must be a host buffer");
-        for (int i = 0; i < e->R; ++i) attempted[i] = e->attempted;
+        for (int i = 0; i < e->R; ++i)  // (ragged batches: e->attempted counts n_max per sweep)
+            attempted[i] = e->ragged ? e->attempted / e->n * spins_of(e, i) : e->attempted;
     }
     return SGA_OK;
 }
@@ -280,6 +281,9 @@ int sga_import_state(sga_engine *e, const void *buf, uint64_t size) {
     for (int8_t *dst : {e->spins, e->best_spins}) {
         HIPCHK(push(stage, sb));
         HIPCHK(sga::launch_pad_spins(stage, e->n, dst, e->sstride, e->R, e->stream));
+        if (e->ragged)  // (past a replica's model: padding, whatever the blob holds)
+            HIPCHK(sga::launch_mask_spins_ragged(dst, e->sstride, e->R, (uint32_t)e->replica0, e->d_models,
+                                                 e->Rg / e->n_models, e->stream));
         HIPCHK(hipStreamSynchronize(e->stream));
     }
     HIPCHK(push(e->energy, R * sizeof(double)));
@@ -339,6 +343,17 @@ int sga_describe(sga_engine *e, char *buf, int buflen) {
                       e->tsp_args.n_cities, e->n, e->R, e->tsp_waves, e->tsp_passes, 4 * e->tsp_args.n_cities,
                       !e->tsp_args.f64 ? "f32-exact" : (e->tsp_exact ? "f64-exact" : "f64"),
                       sga::tsp_lds_bytes(e->tsp_args.n_cities, e->tsp_args.npad));
+    else if (e->ragged)
+        std::snprintf(tmp, sizeof(tmp),
+                      "csr batch models=%d n=%d..%d nnz=%lld R=%d waves_per_replica=1 replicas_per_block=%d sstride=%d "
+                      "path=%s table_m=%d spins=lds-int8 form=narrow-ragged sweep=streaming(no field cache for ragged batches)",
+                      e->n_models, *std::min_element(e->model_n.begin(), e->model_n.end()), e->n, e->nnz, e->R,
+                      sga::csr_waves_per_block(e->sstride, e->table_m), e->sstride,
+                      (e->csr_acc == sga::CSR_ACC_F32_TABLE && e->table_m > 0) ? (e->table_scale == 2 ? "half-integer-fast" : "integer-fast")
+                      : e->csr_acc <= sga::CSR_ACC_F32 ? "general acc=f32-exact"
+                      : e->csr_acc == sga::CSR_ACC_F64 ? "general acc=f64-exact"
+                                                       : "general acc=f64-canonical",
+                      e->table_m);
     else if (e->csr)
         std::snprintf(tmp, sizeof(tmp),
                       "csr n=%d nnz=%lld R=%d waves_per_replica=%d replicas_per_block=%d sstride=%d "
@@ -368,7 +383,7 @@ int sga_describe(sga_engine *e, char *buf, int buflen) {
                                                   e->use_t2 ? e->cpw_t2 : e->cpw,
                                                   e->use_t2 ? e->waves_t2 : e->waves, e->R)
                           : 1);
-    if (e->csr && csr_updates_per_step(e) >= 4 && e->waves <= 1 && (e->big_form == 0 || e->big_form == 2) && e->rowptr)
+    if (e->csr && !e->ragged && csr_updates_per_step(e) >= 4 && e->waves <= 1 && (e->big_form == 0 || e->big_form == 2) && e->rowptr)
         std::snprintf(tmp + std::strlen(tmp), sizeof(tmp) - std::strlen(tmp), " updates_per_step=%d", csr_updates_per_step(e));
     if (e->csr && e->from_dense) std::strncat(tmp, " source=dense-matrix(sparse)", sizeof(tmp) - std::strlen(tmp) - 1);
     if (e->csr && e->slotted)
@@ -379,7 +394,9 @@ int sga_describe(sga_engine *e, char *buf, int buflen) {
     if (e->csr && e->big_form == 1 && e->cvp && e->csr_storage_latched != SGA_CSR_STORAGE_F32)
         std::strncat(tmp, " entries=packed-32bit", sizeof(tmp) - std::strlen(tmp) - 1);
     if (!e->consistent_dE) std::strncat(tmp, " energy=recomputed-per-sweep", sizeof(tmp) - std::strlen(tmp) - 1);
-    if (clf_active(e) && e->csr) {
+    if (e->ragged) {
+        // (one form: nothing below applies)
+    } else if (clf_active(e) && e->csr) {
         if (e->field_cache == SGA_FIELD_CACHE_ON)
             std::snprintf(tmp + std::strlen(tmp), sizeof(tmp) - std::strlen(tmp),
                           " sweep=cached-local-fields(int16 dynamic fields in LDS, row entries read on accept only)");
@@ -418,12 +435,14 @@ int sga_problem_checksum(sga_engine *e, uint64_t *out) {
         HIPCHK(sga::launch_checksum(e->nd4t, bytes, d, e->stream));
     } else if (e->csr) {
         HIPCHK(sga::launch_checksum(e->cv, 8ll * e->layout_entries, d, e->stream));
-        HIPCHK(sga::launch_checksum(e->rowptr64, 8ll * ((long long)e->n + 1), d, e->stream));
+        const long long rows = e->ragged ? e->n_rows : e->n;
+        HIPCHK(sga::launch_checksum(e->rowptr64, 8ll * (rows + 1), d, e->stream));
+        if (e->ragged) HIPCHK(sga::launch_checksum(e->d_models, 8ll * e->n_models, d, e->stream));  // the models' sizes
     } else {
         HIPCHK(sga::launch_checksum(e->J_packed, (long long)e->n_models * e->n * e->ldj * (e->want_i8 ? 1 : 4), d,
                                     e->stream));
     }
-    HIPCHK(sga::launch_checksum(e->h, 4ll * e->n * (e->tsp ? 1 : e->n_models), d + 1, e->stream));
+    HIPCHK(sga::launch_checksum(e->h, e->ragged ? 4ll * e->n_rows : 4ll * e->n * (e->tsp ? 1 : e->n_models), d + 1, e->stream));
     unsigned long long host[2] = {0, 0};
     HIPCHK(hipMemcpyAsync(host, d, sizeof(host), hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));

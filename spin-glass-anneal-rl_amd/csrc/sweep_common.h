@@ -27,12 +27,14 @@ inline bool sweep_args_are_lean(const SweepArgs &a) {
 }
 
 // Everything here is wave-uniform (blockIdx / loop counters / kernel arguments).
+// n = the sites of the replica's model (a.n, except in ragged CSR batches); replay arrays keep the
+// row stride a.n per sweep either way.
 template <bool LEAN>
 __device__ __forceinline__ UpdatePair fetch_pair(const SweepArgs &a, int r, int k, int b,
-                                                 bool valid) {
+                                                 bool valid, int n) {
     UpdatePair o{0, 0, 2.0f, 2.0f};
     if (!valid) return o;
-    const int n = a.n, t0 = 2 * b, t1 = 2 * b + 1;
+    const int t0 = 2 * b, t1 = 2 * b + 1;
     const bool hasB = t1 < n;
     if constexpr (LEAN) {
         const u32x4 w = philox4x32_10((uint32_t)b, a.sweep0 + (uint32_t)k,
@@ -43,7 +45,7 @@ __device__ __forceinline__ UpdatePair fetch_pair(const SweepArgs &a, int r, int 
         o.uB = word_to_u(w.w);
         return o;
     }
-    const long long base = (long long)r * a.replay_stride + (long long)k * n;
+    const long long base = (long long)r * a.replay_stride + (long long)k * a.n;
     if (a.site_mode == SGA_SITE_REPLAY) {
         // recorded stream of the reference: site = torch.randint(0, n, (1,)) at
         // core/spin_dynamics.py:69, u = torch.rand(1) at :146
@@ -75,6 +77,11 @@ __device__ __forceinline__ UpdatePair fetch_pair(const SweepArgs &a, int r, int 
     }
     return o;
 }
+template <bool LEAN>
+__device__ __forceinline__ UpdatePair fetch_pair(const SweepArgs &a, int r, int k, int b,
+                                                 bool valid) {
+    return fetch_pair<LEAN>(a, r, k, b, valid, a.n);
+}
 
 // Supplier of consecutive update pairs (k, b), b = 0, 1, 2, ... within a sweep.
 //
@@ -90,8 +97,13 @@ struct PairSource {
 
     __device__ __forceinline__ UpdatePair get(const SweepArgs &a, int r, int k, int b, bool valid,
                                               int lane) {
+        return get(a, r, k, b, valid, lane, a.n);
+    }
+    // n: the sites of the replica's model (fetch_pair)
+    __device__ __forceinline__ UpdatePair get(const SweepArgs &a, int r, int k, int b, bool valid,
+                                              int lane, int n) {
         if constexpr (!LEAN) {
-            return fetch_pair<false>(a, r, k, b, valid);
+            return fetch_pair<false>(a, r, k, b, valid, n);
         } else {
             UpdatePair o{0, 0, 2.0f, 2.0f};
             if (!valid) return o;
@@ -99,9 +111,9 @@ struct PairSource {
                 const u32x4 w = philox4x32_10((uint32_t)(b + lane), a.sweep0 + (uint32_t)k,
                                               a.replica0 + (uint32_t)r, DOMAIN_SWEEP, a.seed_lo,
                                               a.seed_hi);
-                vsa = word_to_site(w.x, (uint32_t)a.n);
+                vsa = word_to_site(w.x, (uint32_t)n);
                 vua = w.y;
-                vsb = word_to_site(w.z, (uint32_t)a.n);
+                vsb = word_to_site(w.z, (uint32_t)n);
                 vub = w.w;
             }
             const int l = b & 63;

@@ -43,10 +43,20 @@ static hipError_t launch_csr_narrow(const SweepArgs &a, int waves, hipStream_t s
     return launch_csr_kernel(kern, a, false, BIG, waves, st);
 }
 
+static hipError_t launch_csr_ragged(const SweepArgs &a, int waves, hipStream_t st);
+
 // waves_per_replica == 1: several replicas per workgroup (as many as fit LDS), no barriers;
 // > 1: one replica per workgroup, its rows dealt to that many waves (1, 2, 4 or 8: the engine rounds
 // up).  a.big: the bit-spin forms -- 2 = narrow, 1 = one replica per workgroup (1..8 waves).
 hipError_t launch_sweep_csr(const SweepArgs &a0, int waves_per_replica, hipStream_t st) {
+    if (a0.ragged) {  // ragged batches: never the several-updates-per-step, pair look-ahead, bit or wide forms
+        if (waves_per_replica != 1 || a0.big || !a0.rowptr || a0.reps_per_model <= 0) return hipErrorInvalidValue;
+        const int wpb = csr_waves_per_block(a0.sstride, a0.table_m);
+        if (wpb < 1) return hipErrorInvalidValue;
+        SweepArgs a = a0;
+        a.csr_pair_ahead = 0;
+        return launch_csr_ragged(a, wpb, st);
+    }
     // four | eight updates per step (sweep_csr_rows.hip): its own kernel; every other form reads 4 | 8 as "off"
     if (waves_per_replica == 1 && sweep_csr_rows_applies(a0)) {
         const int wpb = a0.big ? csr_bits_waves_per_block(a0.sstride, a0.table_m) : csr_waves_per_block(a0.sstride, a0.table_m);
@@ -74,6 +84,23 @@ hipError_t launch_sweep_csr(const SweepArgs &a0, int waves_per_replica, hipStrea
     const int wpb = csr_waves_per_block(a.sstride, a.table_m);
     if (wpb < 1 || !a.rowptr) return hipErrorInvalidValue;
     return launch_csr_narrow<false>(a, wpb, st);
+}
+
+// ragged CSR batches: the narrow one-update int8 form (accept table, general and LEAN variants)
+static hipError_t launch_csr_ragged(const SweepArgs &a, int waves, hipStream_t st) {
+    const bool lean = csr_args_are_lean(a);
+    void (*kern)(const SweepArgs) = nullptr;
+    switch (csr_effective_acc(a, lean)) {
+        case CSR_ACC_F32_TABLE: kern = sweep_csr_kernel<CSR_ACC_F32_TABLE, true, false, false, 0, 8, false, true>; break;
+        case CSR_ACC_F32: kern = lean ? sweep_csr_kernel<CSR_ACC_F32, true, false, false, 0, 8, false, true> : sweep_csr_kernel<CSR_ACC_F32, false, false, false, 0, 8, false, true>; break;
+        case CSR_ACC_F64: kern = lean ? sweep_csr_kernel<CSR_ACC_F64, true, false, false, 0, 8, false, true> : sweep_csr_kernel<CSR_ACC_F64, false, false, false, 0, 8, false, true>; break;
+        default:
+            kern = lean ? sweep_csr_kernel<CSR_ACC_F64_CANON, true, false, false, 0, 8, false, true> : sweep_csr_kernel<CSR_ACC_F64_CANON, false, false, false, 0, 8, false, true>;
+    }
+    const hipError_t e = launch_csr_kernel(kern, a, false, false, waves, st);
+    note_sweep_kernel("sweep_csr_kernel<acc=%d, %s, ragged> x %d replica(s) per workgroup", csr_effective_acc(a, lean),
+                      lean ? "lean" : "general", waves);
+    return e;
 }
 
 }  // namespace sga

@@ -72,9 +72,22 @@ constexpr int CSR_MAX_WIDE = 8;   // most waves one replica's row is dealt to (1
 // problems with |J| <= 127 and n < 2^24 in the bit-spin wide forms): half the bytes per entry, the row
 // sum accumulated as an integer -- the same value, so the same chain (storage variant with its own byte
 // model, B = deg * 4 + 8).
-template <int ACC, bool LEAN, bool WIDE, bool BIG, int NW = 0, int HD = 8, bool PK = false>
+//
+// RAGGED = many independent models of different sizes in one launch (sga_set_csr_batch), narrow int8 form only:
+// each wave resolves its replica's model at entry -- wave-uniform arithmetic and one scalar load of the model's
+// {first row, spins} -- and from then on sweeps n_m sites, reads rows / h / diag from the model's first row on; its
+// columns are model-local, so the LDS spin slice (sstride of the largest model) serves unchanged.  The accumulation
+// class ACC and the accept table are batch-wide (the most general class any model needs, the largest table_m and
+// table_scale), and every model's chain is still the one-model engine's bit for bit:
+//   * a model of an exact class (fp32 integer sums, fp64 sums exact in any order) gets the exact row sum from any
+//     wider class too -- the canonical fp64 order included -- and both round it to fp32 once;
+//   * the table holds exp(float32(-dE / T)) at dE = 2 q / table_scale: with a larger scale or more entries, the entry
+//     a move looks up stands for the same dE, and a move beyond the table takes the exact expression -- either way
+//     the table decides exactly what metropolis_accept decides.
+template <int ACC, bool LEAN, bool WIDE, bool BIG, int NW = 0, int HD = 8, bool PK = false, bool RAGGED = false>
 __global__ void __launch_bounds__(64 * (WIDE ? CSR_MAX_WIDE : CSR_WAVES_PER_BLOCK))
     sweep_csr_kernel(const SweepArgs a) {
+    static_assert(!RAGGED || (!WIDE && !BIG && !PK), "ragged batches: the narrow int8 form");
     constexpr bool FAST = ACC == CSR_ACC_F32_TABLE || ACC == CSR_ACC_F32;  // fp32 accumulation
     constexpr bool TABLE = ACC == CSR_ACC_F32_TABLE;
     constexpr bool CANON = ACC == CSR_ACC_F64_CANON;
@@ -101,7 +114,17 @@ __global__ void __launch_bounds__(64 * (WIDE ? CSR_MAX_WIDE : CSR_WAVES_PER_BLOC
     const int nw = blockDim.x >> 6;                     // waves in the workgroup
     const int r = WIDE ? (int)blockIdx.x : (int)blockIdx.x * nw + w;
     if (!WIDE && r >= a.R) return;  // wave-uniform; the narrow form has no barriers
-    const int n = a.n;
+    // ragged batches: the replica's model {first row, spins} (wave-uniform, scalar loads); rows, h and diag are read
+    // from its first row on
+    int model_row0 = 0, model_n = 0;
+    if constexpr (RAGGED) {
+        const int m = (int)((a.replica0 + (uint32_t)r) / (uint32_t)a.reps_per_model);
+        const int *md = reinterpret_cast<const int *>(a.h + a.ragged) + 2 * m;
+        model_row0 = *(const __attribute__((address_space(4))) int *)md;
+        model_n = *(const __attribute__((address_space(4))) int *)(md + 1);
+        rowptr += model_row0;
+    }
+    const int n = RAGGED ? model_n : a.n;
     const int slots = WIDE ? 1 : nw;                    // replicas sharing this workgroup's LDS
     const int me = WIDE ? 0 : w;
     const int stride_lanes = WIDE ? 64 * nw : 64;       // entries between a lane's row elements
@@ -241,9 +264,9 @@ __global__ void __launch_bounds__(64 * (WIDE ? CSR_MAX_WIDE : CSR_WAVES_PER_BLOC
             o.end = sload_i(rowptr + us + 1);
             o.zrel = 0;
             o.rem = 0;
-            o.h = sload_f(a.h + us);
+            o.h = sload_f((RAGGED ? a.h + model_row0 : a.h) + us);
         }
-        o.d = arith32 ? sload_f(a.diag + us) : 0.0f;
+        o.d = arith32 ? sload_f((RAGGED ? a.diag + model_row0 : a.diag) + us) : 0.0f;
         return o;
     };
     auto load_head = [&](const Extent &x) {
@@ -551,7 +574,7 @@ __global__ void __launch_bounds__(64 * (WIDE ? CSR_MAX_WIDE : CSR_WAVES_PER_BLOC
             }
             sweep_end(k);
         }
-    } else if (!WIDE && LEAN && TABLE && a.csr_pair_ahead) {
+    } else if (!WIDE && !RAGGED && LEAN && TABLE && a.csr_pair_ahead) {
         // PAIR LOOK-AHEAD (narrow production form, integer problems, rows of <= 64 entries): the two
         // updates of a Philox pair are reduced TOGETHER against the spins as they stand before the first
         // -- two independent gathers, two interleaved wave sums -- and the chain is replayed on scalars:
@@ -687,22 +710,23 @@ __global__ void __launch_bounds__(64 * (WIDE ? CSR_MAX_WIDE : CSR_WAVES_PER_BLOC
         };
         const int nb = (n + 1) >> 1;
         PairState S0, S1;
-        S0.p = rng.get(a, r, 0, 0, a.n_sweeps > 0, lane);
+        S0.p = RAGGED ? rng.get(a, r, 0, 0, a.n_sweeps > 0, lane, n) : rng.get(a, r, 0, 0, a.n_sweeps > 0, lane);
         S0.xA = load_extent(S0.p.sA);
         S0.xB = load_extent(S0.p.sB);
         S0.hA = load_head(S0.xA);
         auto pair = [&](PairState &c, PairState &nx, int k, int b) {
             const bool last = (b + 1 == nb);
             const int kn = last ? k + 1 : k, bn = last ? 0 : b + 1;
-            nx.p = rng.get(a, r, kn, bn, kn < a.n_sweeps, lane);
+            nx.p = RAGGED ? rng.get(a, r, kn, bn, kn < a.n_sweeps, lane, n) : rng.get(a, r, kn, bn, kn < a.n_sweeps, lane);
             const bool hasB = (2 * b + 1) < n;
             nx.xA = load_extent(nx.p.sA);  // a pair ahead
             nx.xB = load_extent(nx.p.sB);
             Head hB{};
             if (hasB) hB = load_head(c.xB);  // in flight while A is reduced
-            update(c.p.sA, c.p.uA, c.p.rA, c.xA, c.hA, (long long)k * n + 2 * b);
+            // (trace index: replay / trace arrays hold a.n updates per sweep -- the largest model's in ragged batches)
+            update(c.p.sA, c.p.uA, c.p.rA, c.xA, c.hA, (long long)k * (RAGGED ? a.n : n) + 2 * b);
             nx.hA = load_head(nx.xA);  // in flight while B is reduced
-            if (hasB) update(c.p.sB, c.p.uB, c.p.rB, c.xB, hB, (long long)k * n + 2 * b + 1);
+            if (hasB) update(c.p.sB, c.p.uB, c.p.rB, c.xB, hB, (long long)k * (RAGGED ? a.n : n) + 2 * b + 1);
         };
         for (int k = 0; k < a.n_sweeps; ++k) {
             sweep_start(k);

@@ -55,6 +55,51 @@ def probe_read_bandwidth(device_index: int = 0, nbytes: int = 1 << 32, reps: int
     return float(out.value)
 
 
+def _host_array(x, dtype, what):
+    if _is_tensor(x):
+        x = x.detach().cpu().numpy()
+    a = np.asarray(x)
+    if a.ndim != 1:
+        raise AnnealingError(f"{what} must be one-dimensional")
+    return np.ascontiguousarray(a, dtype=dtype)
+
+
+def concat_csr_batch(problems):
+    """[(rowptr, colidx, val, h), ...] (numpy or torch, model-local columns) -> the one concatenated CSR of
+    sga_set_csr_batch: (n_spins int32 [M], rowptr int64 [sum n + 1], colidx int32, val float32, h float32).
+    Every argument is checked here, before any device call."""
+    if isinstance(problems, tuple) or not hasattr(problems, "__len__") or len(problems) == 0:
+        raise AnnealingError("problems must be a non-empty list of (rowptr, colidx, val, h)")
+    sizes, rps, cis, vals, hs = [], [], [], [], []
+    base = 0
+    for m, p in enumerate(problems):
+        if len(p) != 4:
+            raise AnnealingError(f"model {m}: expected (rowptr, colidx, val, h)")
+        rp = _host_array(p[0], np.int64, f"model {m}: rowptr")
+        ci = _host_array(p[1], np.int64, f"model {m}: colidx")
+        v = _host_array(p[2], np.float32, f"model {m}: val")
+        h = _host_array(p[3], np.float32, f"model {m}: h")
+        n = rp.size - 1
+        if n <= 0:
+            raise AnnealingError(f"model {m}: rowptr must have n + 1 >= 2 entries")
+        if rp[0] != 0 or np.any(np.diff(rp) < 0) or rp[-1] != ci.size:
+            raise AnnealingError(f"model {m}: rowptr must start at 0, not decrease and end at len(colidx)")
+        if v.size != ci.size:
+            raise AnnealingError(f"model {m}: colidx and val differ in length ({ci.size} vs {v.size})")
+        if h.size != n:
+            raise AnnealingError(f"model {m}: h has {h.size} entries, the model {n} spins")
+        if ci.size and (ci.min() < 0 or ci.max() >= n):
+            raise AnnealingError(f"model {m}: column index outside [0, {n})")
+        sizes.append(n)
+        rps.append(rp[:-1] + base if m + 1 < len(problems) else rp + base)
+        cis.append(ci.astype(np.int32))
+        vals.append(v)
+        hs.append(h)
+        base += int(rp[-1])
+    return (np.asarray(sizes, np.int32), np.concatenate(rps).astype(np.int64), np.concatenate(cis),
+            np.concatenate(vals), np.concatenate(hs))
+
+
 class _SerialisedLib:
     """Calls on one handle must not overlap (include/sga.h); ctypes releases the GIL during a
     call, so the reference's habit of driving sweeps from a thread pool
@@ -89,6 +134,7 @@ class AnnealEngine:
         self.replica0 = 0
         self.n_ladders = 0
         self.n_models = 1
+        self._sizes = None  # ragged CSR batches: spins of every model
 
     # ------------------------------------------------------------------ lifetime
     def close(self):
@@ -214,6 +260,7 @@ class AnnealEngine:
             raise AnnealingError("external fields must have n entries")
         N.check(self._lib.sga_set_dense(self._h, jp, int(ld), hp, int(n), sel), "sga_set_dense")
         del keep
+        self._sizes = None
         self.n, self.R, self.n_models = n, 0, 1
 
     def set_dense_batch(self, J, h, storage: str = "auto"):
@@ -236,6 +283,7 @@ class AnnealEngine:
         N.check(self._lib.sga_set_dense_batch(self._h, jp, int(n), hp, int(n), int(M), sel),
                 "sga_set_dense_batch")
         del keep
+        self._sizes = None
         self.n, self.R, self.n_models = n, 0, M
 
     def set_csr(self, rowptr, colidx, val, h):
@@ -250,7 +298,30 @@ class AnnealEngine:
         nnz = k2.numel() if _is_tensor(k2) else k2.size
         fn, name = (self._lib.sga_set_csr64, "sga_set_csr64") if wide else (self._lib.sga_set_csr, "sga_set_csr")
         N.check(fn(self._h, rp, ci, vp, hp, int(n), int(nnz)), name)
-        self.n, self.R = n, 0
+        self.n, self.R, self.n_models = n, 0, 1
+        self._sizes = None
+
+    def set_csr_batch(self, problems):
+        """Many independent sparse models of any sizes in one engine (sga_set_csr_batch): `problems` is a list of
+        (rowptr, colidx, val, h) with model-local columns.  Replicas are split evenly over the models (R a multiple of
+        the number of models); spins(r) and best(r) return the n of replica r's model."""
+        sizes, rp, ci, v, h = concat_csr_batch(problems)
+        ptr = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+        N.check(self._lib.sga_set_csr_batch(self._h, int(sizes.size), ptr(sizes), ptr(rp), ptr(ci), ptr(v), ptr(h),
+                                            int(ci.size)), "sga_set_csr_batch")
+        self.n, self.R, self.n_models = int(sizes.max()), 0, int(sizes.size)
+        self._sizes = sizes
+
+    def model_sizes(self) -> np.ndarray:
+        """Spins of every model (one entry per model; dense batches and single problems: n each)."""
+        sizes = getattr(self, "_sizes", None)
+        return sizes.copy() if sizes is not None else np.full(self.n_models, self.n, np.int32)
+
+    def _replica_n(self, r: int) -> int:
+        sizes = getattr(self, "_sizes", None)
+        if sizes is None:
+            return self.n
+        return int(sizes[(self.replica0 + int(r)) // (self.R_global // sizes.size)])
 
     def set_tsp(self, dist, city_visit: float, position_fill: float, h):
         """TSP-structured couplings, never stored (see sga_set_tsp): dist [n, n] float32 (numpy or
@@ -275,6 +346,7 @@ class AnnealEngine:
         N.check(self._lib.sga_set_tsp(self._h, dp, int(ld), int(n), float(city_visit), float(position_fill),
                                       hp), "sga_set_tsp")
         del keep
+        self._sizes = None
         self.n, self.R, self.n_models = n * n, 0, 1
 
     # ------------------------------------------------------------------ replicas
@@ -435,15 +507,15 @@ class AnnealEngine:
             N.check(self._lib.sga_get_spins(self._h, -1, out.ctypes.data_as(C.c_void_p)),
                     "sga_get_spins")
             return out
-        out = np.zeros(self.n, np.int8)
+        out = np.zeros(self._replica_n(r), np.int8)
         N.check(self._lib.sga_get_spins(self._h, int(r), out.ctypes.data_as(C.c_void_p)),
                 "sga_get_spins")
         return out
 
     def set_spins(self, r: int, s):
         a = np.ascontiguousarray(s, dtype=np.int8)
-        if a.size != self.n:
-            raise AnnealingError("spins must have n entries")
+        if a.size != self._replica_n(r):
+            raise AnnealingError("spins must have n entries (ragged batches: the replica's model's n)")
         N.check(self._lib.sga_set_spins(self._h, int(r), a.ctypes.data_as(C.c_void_p)),
                 "sga_set_spins")
 
@@ -454,6 +526,8 @@ class AnnealEngine:
         N.check(self._lib.sga_get_best(self._h, -1 if r is None else int(r), C.byref(e),
                                        None if s is None else s.ctypes.data_as(C.c_void_p),
                                        C.byref(idx)), "sga_get_best")
+        if s is not None:
+            s = s[:self._replica_n(idx.value)].copy() if s.size != self._replica_n(idx.value) else s
         return float(e.value), s, int(idx.value)
 
     def reset_best(self):
