@@ -166,7 +166,13 @@ int sga_set_tsp(sga_engine *e, const float *dist, int64_t ld, int n_cities, floa
  * SGA_ERR_INVALID until replicas are initialised again. */
 int sga_init_replicas(sga_engine *e, int R_local, int R_global, int replica0, uint64_t seed,
                       const int8_t *s0);
-/* Temperature of each local replica (used when sga_sweep gets no schedule). */
+/* Temperatures lie in [0, inf].  T = 0 accepts a Metropolis move iff dE <= 0 (a greedy quench: downhill and
+ * flat moves), T = inf accepts every Metropolis proposal; every sweep form gives the same chain at both ends, and
+ * an exchange whose argument is NaN (two T = 0 slots, a T = 0 slot at equal energies) swaps, as
+ * min(1.0, exp(x)) does.  NaN and values with the sign bit set (-0.0 included) are refused with SGA_ERR_INVALID
+ * and a message naming the call, before anything changes -- by sga_set_temperatures, sga_set_ladder and the
+ * sched argument of sga_sweep, for host-memory inputs (device arrays are not read back to be checked).
+ * Temperature of each local replica (used when sga_sweep gets no schedule). */
 int sga_set_temperatures(sga_engine *e, const double *T /* [R_local] */);
 /* Temperature ladder(s) over the GLOBAL replica set: n_ladders ladders of R_global/n_ladders
  * slots, slot_temps[R_global]; slot i initially holds replica i.  Sets local temperatures. */
@@ -175,7 +181,7 @@ int sga_set_ladder(sga_engine *e, const double *slot_temps /* [R_global] */, int
 /* ---- hot path ------------------------------------------------------------------------- */
 /* n_sweeps Metropolis sweeps (n single-spin updates each) of every local replica.
  *   sched: optional temperatures T(k, r) = sched[k*sched_sweep_stride + r*sched_replica_stride]
- *          (k = sweep within this call, r = local replica); NULL = current temperatures.
+ *          (k = sweep within this call, r = local replica), in [0, inf]; NULL = current temperatures.
  *   replay_site [R_local][n_sweeps*n] int32, replay_u [R_local][n_sweeps*n] fp32: SITE_REPLAY
  *          needs both; SITE_SEQUENTIAL takes replay_u if non-NULL (else Philox uniforms).
  *   energy_trace: optional [n_sweeps][R_local] doubles, energy after each sweep.

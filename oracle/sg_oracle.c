@@ -550,7 +550,7 @@ int sgo_pt_exchange_round(int R, const double *slot_temps, const double *rep_ene
         double beta_i = 1.0 / slot_temps[i], beta_j = 1.0 / slot_temps[j];
         double Ei = rep_energy[slot_to_rep[i]], Ej = rep_energy[slot_to_rep[j]];
         double x = (beta_j - beta_i) * (Ej - Ei);
-        double prob = (x >= 0.0) ? 1.0 : sgo_exp(x); /* min(1.0, np.exp(x)), :246 */
+        double prob = !(x < 0.0) ? 1.0 : sgo_exp(x); /* min(1.0, np.exp(x)), :246 -- min(1.0, nan) is 1.0 */
         double uu;
         if (u) {
             uu = u[k];
@@ -584,7 +584,7 @@ int sgo_pt_exchange_pairs(int R, const double *slot_temps, const double *rep_ene
         double beta_i = 1.0 / slot_temps[i], beta_j = 1.0 / slot_temps[j];
         double Ei = rep_energy[slot_to_rep[i]], Ej = rep_energy[slot_to_rep[j]];
         double x = (beta_j - beta_i) * (Ej - Ei);
-        double prob = (x >= 0.0) ? 1.0 : sgo_exp(x);
+        double prob = !(x < 0.0) ? 1.0 : sgo_exp(x);
         double uu;
         if (u) {
             uu = u[k];

@@ -5,6 +5,9 @@
 // sga_route.cpp; shared internals: sga_engine_impl.h)
 #include "sga_engine_impl.h"
 
+#include <cmath>
+#include <cstdio>
+
 namespace sga_impl {
 
 sga_route_query route_query_of(const sga_engine *e) {
@@ -499,9 +502,26 @@ static int init_replicas_body(sga_engine *e, int R_local, int R_global, int repl
     return SGA_OK;
 }
 
+// Temperatures lie in [0, inf] (include/sga.h): NaN and anything with the sign bit set (-0.0 included) are refused,
+// before anything changes.  Host inputs only: a device array is the caller's to check.
+static int check_temperatures(const char *call, const double *T, long long count, long long stride = 1) {
+    if (is_device_ptr(T)) return SGA_OK;
+    for (long long i = 0; i < count; ++i) {
+        const double t = T[i * stride];
+        if (std::isnan(t) || std::signbit(t)) {
+            char msg[160];
+            std::snprintf(msg, sizeof(msg), "%s: temperature %g at index %lld is outside [0, inf]", call, t, i);
+            return fail(SGA_ERR_INVALID, msg);
+        }
+    }
+    return SGA_OK;
+}
+
 int sga_set_temperatures(sga_engine *e, const double *T) {
     if (!e || !T) return fail(SGA_ERR_INVALID, "NULL argument");
     if (e->R <= 0) return fail(SGA_ERR_INVALID, "no replicas");
+    int rc = check_temperatures("sga_set_temperatures", T, e->R);
+    if (rc != SGA_OK) return rc;
     HIPCHK(hipSetDevice(e->device));
     HIPCHK(hipMemcpyAsync(e->rep_temp, T, sizeof(double) * e->R, hipMemcpyDefault, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
@@ -516,6 +536,8 @@ int sga_set_ladder(sga_engine *e, const double *slot_temps, int n_ladders) {
     if (e->ragged && n_ladders % e->n_models != 0)
         return fail(SGA_ERR_INVALID, "ragged CSR batches: n_ladders must be a multiple of the number of models "
                                      "(a ladder lies within one model)");
+    int rc = check_temperatures("sga_set_ladder", slot_temps, e->Rg);
+    if (rc != SGA_OK) return rc;
     HIPCHK(hipSetDevice(e->device));
     dev_free(e->slot_temps);
     dev_free(e->slot_to_rep);
@@ -558,6 +580,14 @@ int sga_sweep(sga_engine *e, int n_sweeps, int site_mode, int arith, const doubl
     if (site_mode == SGA_SITE_REPLAY && (!replay_site || !replay_u))
         return fail(SGA_ERR_INVALID, "SITE_REPLAY needs replay_site and replay_u");
     if (n_sweeps == 0) return SGA_OK;
+    if (sched && !is_device_ptr(sched)) {  // every T(k, r) this call reads, before the first piece runs
+        if (sched_sweep_stride < 0 || sched_replica_stride < 0) return fail(SGA_ERR_INVALID, "negative schedule stride");
+        for (int r = 0; r < e->R; ++r) {
+            int rc = check_temperatures("sga_sweep (sched)", sched + (long long)r * sched_replica_stride, n_sweeps,
+                                        sched_sweep_stride);
+            if (rc != SGA_OK) return rc;
+        }
+    }
     if (e->opt_stale)
         return fail(SGA_ERR_INVALID, std::string("option \"") + (e->opt_stale_key ? e->opt_stale_key : "?") + "\" changed after " +
                                          ((e->opt_stale & 2) ? "the couplings were set (it is read by sga_set_dense / sga_set_csr): set them again"

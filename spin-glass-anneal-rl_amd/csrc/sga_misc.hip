@@ -826,7 +826,7 @@ __global__ void exchange_neighbor_kernel(const ExchangeArgs a) {
         const double beta_i = 1.0 / a.slot_temps[i], beta_j = 1.0 / a.slot_temps[i + 1];
         const int ri = a.slot_to_rep[i], rj = a.slot_to_rep[i + 1];
         const double x = (beta_j - beta_i) * (a.energies[rj - a.energy_base] - a.energies[ri - a.energy_base]);
-        const double prob = (x >= 0.0) ? 1.0 : exp_det(x);
+        const double prob = !(x < 0.0) ? 1.0 : exp_det(x);  // min(1.0, exp(x)): NaN (T = 0 slots) swaps
         double uu;
         if (a.u) {
             uu = a.u[l * half + q];
@@ -874,7 +874,7 @@ __global__ void __launch_bounds__(256) exchange_pairs_kernel(const ExchangeArgs 
             const double beta_i = 1.0 / a.slot_temps[i], beta_j = 1.0 / a.slot_temps[j];
             const int ri = a.slot_to_rep[i], rj = a.slot_to_rep[j];
             const double x = (beta_j - beta_i) * (a.energies[rj] - a.energies[ri]);
-            const double prob = (x >= 0.0) ? 1.0 : exp_det(x);
+            const double prob = !(x < 0.0) ? 1.0 : exp_det(x);  // min(1.0, exp(x)): NaN (T = 0 slots) swaps
             double uu;
             if (a.u) {
                 uu = a.u[k];

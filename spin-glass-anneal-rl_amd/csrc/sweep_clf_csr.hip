@@ -173,7 +173,8 @@ __global__ void __launch_bounds__(64 * CLFS_MAX_WAVES) sweep_clf_csr_kernel(cons
     for (int k = 0; k < a.n_sweeps; ++k) {
         T = a.sched ? a.sched[k * a.sched_ss + r * a.sched_rs] : a.rep_temp[r];
         __syncthreads();
-        for (int q = tid; q <= a.table_m; q += nthreads) ptab[q] = expf_det((float)(-((double)(2 * q) * inv_sc) / T));
+        // (entry 0 = 1 whatever T is: exp(-0 / 0) is NaN)
+        for (int q = tid; q <= a.table_m; q += nthreads) ptab[q] = q == 0 ? 1.0f : expf_det((float)(-((double)(2 * q) * inv_sc) / T));
         __syncthreads();
         for (int t0 = 0; t0 < n; t0 += CLFS_WINDOW * W) {
             const int gA = w * CLFS_WINDOW + 2 * lane, gB = gA + 1;  // positions in the window

@@ -382,8 +382,8 @@ __global__ void __launch_bounds__(64 * CLF_MAX_WAVES) sweep_clf_kernel(const Swe
         T = a.sched ? a.sched[k * a.sched_ss + r * a.sched_rs] : a.rep_temp[r];
         if constexpr (LEAN) {  // exp(float32(-dE/T)) of the moves dE = 2 q / scale, q <= table_m
             __syncthreads();
-            for (int q = tid; q <= a.table_m; q += blockDim.x)
-                ptab[q] = expf_det((float)(-((double)(2 * q) * inv_sc) / T));
+            for (int q = tid; q <= a.table_m; q += blockDim.x)  // (entry 0 = 1 whatever T is: exp(-0 / 0) is NaN)
+                ptab[q] = q == 0 ? 1.0f : expf_det((float)(-((double)(2 * q) * inv_sc) / T));
             __syncthreads();
         }
         const long long base = (long long)r * a.replay_stride + (long long)k * n;

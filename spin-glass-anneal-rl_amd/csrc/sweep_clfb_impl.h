@@ -259,8 +259,9 @@ sweep_clfb_kernel(const SweepArgs a) {
         T = a.sched ? a.sched[k * a.sched_ss + r * a.sched_rs] : a.rep_temp[r];
         [[maybe_unused]] const long long tick_table = CLFB_TICK();
         __syncthreads();
-        for (int q = tid; q <= a.table_m; q += blockDim.x)  // exp(float32(-dE/T)) of the moves dE = 2 q / scale
-            ptab[q] = expf_det((float)(-((double)(2 * q) * inv_sc) / T));
+        // exp(float32(-dE/T)) of the moves dE = 2 q / scale; entry 0 = 1 whatever T is (exp(-0 / 0) is NaN)
+        for (int q = tid; q <= a.table_m; q += blockDim.x)
+            ptab[q] = q == 0 ? 1.0f : expf_det((float)(-((double)(2 * q) * inv_sc) / T));
         if (tid == 0) sums[0] = 0ull, sums[1] = 0ull;
         __syncthreads();
         // The check's filter reads "u >= p(k') is a rejection for every k >= k'": true while the table does not

@@ -488,9 +488,11 @@ __global__ void __launch_bounds__(64 * (WIDE ? CSR_MAX_WIDE : CSR_WAVES_PER_BLOC
             if constexpr (WIDE) __syncthreads();  // nobody still reads last sweep's table
             // as integer thresholds on the uniform's 24 raw bits: u = r 2^-24 < p <=> r < ceil(p 2^24)
             // (p 2^24 is exact, so is its ceiling) -- no int -> float conversion of u per update
+            // (entry 0 is 2^24 whatever T is, as in sweep_csr_rows.hip; the fk <= 0 test serves it here)
             for (int q = first_lane; q <= a.table_m; q += stride_lanes)
-                itab[q] = (unsigned int)__builtin_ceilf(
-                    expf_det((float)(-((double)(2 * q) / (double)a.table_scale) / T)) * 16777216.0f);
+                itab[q] = q == 0 ? 1u << 24
+                                 : (unsigned int)__builtin_ceilf(
+                                       expf_det((float)(-((double)(2 * q) / (double)a.table_scale) / T)) * 16777216.0f);
             if constexpr (WIDE) __syncthreads();
         }
     };

@@ -345,11 +345,13 @@ __global__ void __launch_bounds__(64 * CSR_WAVES_PER_BLOCK) sweep_csr_rows_kerne
     };
     for (int k = 0; k < a.n_sweeps; ++k) {
         T = a.sched ? a.sched[k * a.sched_ss + r * a.sched_rs] : a.rep_temp[r];
-        // exp(float32(-dE / T)) for dE = 2 q / table_scale as integer thresholds on the uniform's raw bits
+        // exp(float32(-dE / T)) for dE = 2 q / table_scale as integer thresholds on the uniform's raw bits; entry 0
+        // (downhill or flat) is 2^24 whatever T is -- at T = 0 the formula would give ceil(NaN)
         if constexpr (!REAL)
             for (int q = lane; q <= a.table_m; q += 64)
-                itab[q] = (unsigned int)__builtin_ceilf(
-                    expf_det((float)(-((double)(2 * q) / (double)a.table_scale) / T)) * 16777216.0f);
+                itab[q] = q == 0 ? 1u << 24
+                                 : (unsigned int)__builtin_ceilf(
+                                       expf_det((float)(-((double)(2 * q) / (double)a.table_scale) / T)) * 16777216.0f);
         int m = 0;
         for (; m + 3 <= steps; m += 3) {
             step3(S0, S1, S2, k, m);
