@@ -380,6 +380,13 @@ int sga_set_field_cache(sga_engine *e, int mode);
  *                           between the accepting sites, the rows applied two at a time (csrc/sweep_clfb_impl.h).  Same
  *                           chain.  2 = while the hottest replica accepts more than ~1 % of its proposals (where the
  *                           form is ahead), 1 = always, 0 = never                               [sweep; SGA_CLF_BATCHED]
+ *   "clf_fixed_point"       0 (default) | 1   cached-field sweep over CSR couplings for real-valued J and wide
+ *                           integer fields: D_i = 2^k sum_j J_ij s_j kept EXACTLY as int32 | int64 in LDS (k from the
+ *                           set-time scan of J's binary exponents; acc class f32 / f64-exact, symmetric J in strictly
+ *                           sorted rows, zero diagonal, any fp32 h), dot = fp32(2^-k D_i) -- the row kernels' value --
+ *                           and the same accept rule: the same chain, any single-site rule, site mode and arithmetic.
+ *                           Problems the int16 form serves keep it.  Refused: f64-canonical J, ragged batches, the
+ *                           implicit TSP form, fields past LDS                                          [set]
  *   "replica_routing"       0 | 1 (default)   SGA_FIELD_CACHE_AUTO routes each replica by its own acceptance (two
  *                           concurrent launches) instead of the whole launch by the hottest replica    [sweep; SGA_NO_REPLICA_ROUTING]
  *   "batched_energy"        0 = one pass over the couplings per replica, 1 (default) = all replicas in one pass where

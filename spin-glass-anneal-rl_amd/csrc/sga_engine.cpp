@@ -33,6 +33,8 @@ sga_route_query route_query_of(const sga_engine *e) {
     q.table_scale = e->table_scale;
     q.clf_bits = e->clf_bits;
     q.clf_scale = e->clf_scale;
+    // option "clf_fixed_point": CSR queries carry the width of the fixed-point fields (32 | 64; 16: the int16 form)
+    if (e->csr && e->opt[OPT_CLF_FIXED_POINT] == 1) q.clf_bits = e->clf_fx_bits ? e->clf_fx_bits : 16;
     q.from_dense = e->from_dense ? 1 : 0;
     q.nnz = e->nnz;
     q.max_row_len = e->max_row_len;
@@ -111,6 +113,8 @@ int fields_pass(sga_engine *e, int r0, int count, double *energy, void *fields) 
 bool clf_possible(const sga_engine *e, const char **why) {
     const sga_route_query q = route_query_of(e);
     const char *reason = sga_route::clf_refusal(q);
+    // (option "clf_fixed_point": the set-time scan knows which condition failed; the query carries only the verdict)
+    if (reason && e->csr && !q.clf_ok && e->clf_fx_why && q.n_models == 1) reason = e->clf_fx_why;
     if (why) *why = reason;
     return reason == nullptr;
 }
@@ -122,10 +126,17 @@ int ensure_fields(sga_engine *e) {
     if (e->fields_valid && e->fields) return SGA_OK;
     if (e->csr) {  // D = J s of every replica (int16), eight replicas per pass over the entries; scale * h once
         e->ldf = ((long long)e->n + 127) / 128 * 128;
-        if (!e->fields && hipMalloc(&e->fields, (size_t)e->R * (size_t)e->ldf * 2) != hipSuccess) {
+        const size_t fbytes = e->clf_fx_bits ? (size_t)(e->clf_fx_bits / 8) : 2;  // (fixed point: D = 2^k J s, int32 | int64)
+        if (!e->fields && hipMalloc(&e->fields, (size_t)e->R * (size_t)e->ldf * fbytes) != hipSuccess) {
             (void)hipGetLastError();
             e->fields = nullptr;
             return fail(SGA_ERR_MEMORY, "no memory for the resident local fields of the cached-field sweep");
+        }
+        if (e->clf_fx_bits) {
+            HIPCHK(sga::launch_csr_fields_seed_fx(e->rowptr64, e->cv, e->spins, e->sstride, e->n, e->R, e->fields, e->ldf,
+                                                  e->clf_fx_bits, e->clf_fx_k, e->stream));
+            e->fields_valid = true;
+            return SGA_OK;
         }
         if (!e->hq) {
             HIPCHK(hipMalloc(&e->hq, sizeof(int) * (size_t)e->n));
@@ -244,7 +255,7 @@ int ensure_packed(sga_engine *e) {
 extern "C" {
 
 const char *sga_last_error(void) { return g_last_error.c_str(); }
-int sga_version(void) { return 600; }  // + sga_set_csr_batch / sga_get_batch_model (ragged CSR batches)  // round 5: + sga_explain_route / sga_get_route_query, sga_get_last_kernel, sga_get_autotune_table, ladder-local sga_exchange
+int sga_version(void) { return 700; }  // + option "clf_fixed_point" (cached fields of real-valued CSR couplings)  // 600: + sga_set_csr_batch / sga_get_batch_model (ragged CSR batches)  // round 5: + sga_explain_route / sga_get_route_query, sga_get_last_kernel, sga_get_autotune_table, ladder-local sga_exchange
 
 int sga_create(int device, sga_engine **out) {
     if (!out) return fail(SGA_ERR_INVALID, "out is NULL");
@@ -948,6 +959,11 @@ int sga_sweep(sga_engine *e, int n_sweeps, int site_mode, int arith, const doubl
             ac.ldf = e->ldf;
             ac.clf_hq = e->hq;
             ac.clf_row_max = (int)std::min<long long>(e->slotted ? (e->max_row_len + 63) / 64 * 64 : e->max_row_len, 1 << 20);
+            if (e->clf_fx_bits) {  // option "clf_fixed_point": D = 2^k J s exactly, any single-site rule / site mode / arithmetic
+                ac.field_bits = e->clf_fx_bits;
+                ac.field_scale = e->clf_fx_k;
+                ac.table_m = 0;
+            }
             const int cw = sga_route::clf_csr_waves(rq);
             if (sga::sweep_clf_csr_applies(ac, cw)) {
                 le = sga::launch_sweep_clf_csr(ac, cw, st);

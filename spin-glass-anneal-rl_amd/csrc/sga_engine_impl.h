@@ -190,6 +190,10 @@ struct sga_engine {
     // ... of CSR problems (sweep_clf_csr.hip): integer J, rows strictly sorted, max_i sum_j |J_ij| < 2^15, the accept
     // table applies, dE of the rule == energy change; the fields are then D = J s as int16, h stays outside
     bool clf_csr_problem = false;
+    // ... or, with option "clf_fixed_point", as exact fixed point: D = 2^k J s as int32 | int64 (any fp32 J whose row
+    // sums are exact, h fp32 beside it): the width (0 = not this form), k, and why the form does not apply (nullptr: it does)
+    int clf_fx_bits = 0, clf_fx_k = 0;
+    const char *clf_fx_why = nullptr;
     float row_j_abs_max = 0.0f;  // max_i sum_j |J_ij|
     float csr_row_abs_max = 0.0f;  // CSR: max_i (sum_j |J_ij| + |h_i|): no |fk| of a move exceeds it
     int *hq = nullptr;           // [n] table_scale * h_i as integers (built with the first cached sweep)
@@ -271,6 +275,9 @@ struct sga_engine {
         dev_free(nd4t);
         dev_free(hq);
         clf_csr_problem = false;
+        clf_fx_bits = 0;
+        clf_fx_k = 0;
+        clf_fx_why = nullptr;
         tsp = false;
         dev_free(epart);
         epart_bytes = 0;

@@ -84,8 +84,8 @@ struct SweepArgs {
     // cached-local-field sweep (sweep_clf_impl.h): resident fields F = field_scale * (J s + h)
     void *fields;        // [R][ldf] int16 | int32
     long long ldf;
-    int field_bits;      // 16 | 32
-    int field_scale;     // 1 | 2 (J integer, h a multiple of 1/2)
+    int field_bits;      // 16 | 32; CSR: 0 = int16 fields, 32 | 64 = fixed-point fields (sweep_clf_csr.hip)
+    int field_scale;     // 1 | 2 (J integer, h a multiple of 1/2); CSR fixed-point fields (sweep_clf_csr.hip): k, D = 2^k J s
     int clf_batched;     // 1: several accepts per round (sweep_clfb_impl.h) where the arguments are the production ones
     int clf_jmax;        // max |J_ij| (integer): the most one flip moves another site's field, in units of 2 scale
     // cached-field sweep of CSR problems (sweep_clf_csr.hip): fields = D [R][ldf] int16, D_i = sum_j J_ij s_j
@@ -162,12 +162,16 @@ hipError_t launch_sweep_clfb(const SweepArgs &a, bool j_is_i8, int waves, hipStr
 bool sweep_clfb_applies(const SweepArgs &a, bool j_is_i8);
 size_t sweep_clfb_lds_bytes(long long ldf, int field_bits, int sstride, int table_m);
 int sweep_clf_batch(long long ldj, bool j_is_i8, int waves);
-// ... and of CSR problems with integer couplings (rows sorted, |sum_j J_ij s_j| < 2^15)
+// ... and of CSR problems with integer couplings (rows sorted, |sum_j J_ij s_j| < 2^15); a.field_bits = 32 | 64: the
+// fixed-point form (option "clf_fixed_point"), D = 2^k J s with k = a.field_scale, no accept table
 hipError_t launch_sweep_clf_csr(const SweepArgs &a, int waves, hipStream_t st);
 bool sweep_clf_csr_applies(const SweepArgs &a, int waves);
-size_t sweep_clf_csr_lds_bytes(long long ldf, int sstride, int table_m);
+size_t sweep_clf_csr_lds_bytes(long long ldf, int sstride, int table_m, int field_bits = 16);
 hipError_t launch_csr_fields_seed(const long long *rowptr, const int2 *cv, const int8_t *spins, int sstride, int n, int R,
                                   short *D, long long ldf, hipStream_t st);
+// D[r][i] = 2^k sum_j J_ij s_rj as int32 | int64 (field_bits), exact
+hipError_t launch_csr_fields_seed_fx(const long long *rowptr, const int2 *cv, const int8_t *spins, int sstride, int n, int R,
+                                     void *D, long long ldf, int field_bits, int k, hipStream_t st);
 hipError_t launch_scaled_fields(const float *h, int n, int scale, int *hq, hipStream_t st);
 size_t sweep_clf_lds_bytes(long long ldf, int field_bits, int sstride, int table_m);
 int sweep_clf_waves(long long ldj, bool j_is_i8, int R, int cus, int forced);

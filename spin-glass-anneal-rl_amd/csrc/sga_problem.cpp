@@ -309,6 +309,32 @@ int set_csr_common(sga_engine *e, const void *rowptr, bool wide_extents, const i
             e->csr_acc = sga::CSR_ACC_F64_CANON;
         if (e->opt[OPT_FORCE_CSR_ACC] > 0)  // parity tests: the slower forms
             e->csr_acc = std::max(e->csr_acc, std::min(3, (int)e->opt[OPT_FORCE_CSR_ACC]));
+        // Option "clf_fixed_point": the cached-field sweep for the problems the int16 form does not take.  Every row
+        // sum is exact (acc classes f32 / f64-exact), and every set bit of every J lies at or above 2^-k, k = minus the
+        // exponent of the lowest set bit: 2^k sum_j J_ij s_j is an integer of at most B = 2^k max_i sum_j |J_ij| (< 2^53
+        // by the class's own bound), kept exactly as int32 (B < 2^31) or int64.  h is never folded in.
+        if (e->opt[OPT_CLF_FIXED_POINT] == 1 && !e->clf_csr_problem) {
+            const int k = any ? flags[sga::CSR_EXP_LO] - 1024 : 0;
+            // (mj is the fp32 rounding of an fp64 sum: < 1 ulp either way)
+            const double bound = std::ldexp((double)e->row_j_abs_max, k) * (1.0 + 0x1.0p-20);
+            if (e->csr_acc == sga::CSR_ACC_F64_CANON)
+                e->clf_fx_why = "cached local fields (fixed point): the couplings need the canonical fp64 summation order "
+                                "(acc class f64-canonical: their binary places span more than 53 bits, so no exact fixed "
+                                "point holds a row sum)";
+            else if (!sorted)
+                e->clf_fx_why = "cached local fields (fixed point): CSR rows must be strictly sorted by column (no duplicate entries)";
+            else if (flags[sga::CSR_DIAGONAL])
+                e->clf_fx_why = "cached local fields (fixed point): J must have a zero diagonal";
+            else if (flags[sga::CSR_ASYMMETRIC])
+                e->clf_fx_why = "cached local fields (fixed point): J must be symmetric";
+            else if (n > (1 << 30) || !(bound < 0x1.0p62))
+                e->clf_fx_why = "cached local fields (fixed point): fields wider than int64";
+            if (!e->clf_fx_why) {
+                e->clf_csr_problem = true;
+                e->clf_fx_bits = bound < 0x1.0p31 ? 32 : 64;
+                e->clf_fx_k = k;
+            }
+        }
     }
     // The layout the kernels read: (column, value) interleaved, one 8-byte load per entry.  Long
     // rows (mean degree >= 192: the problems that run the wide forms) are padded to whole 64-entry

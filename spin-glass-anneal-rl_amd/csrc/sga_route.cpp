@@ -325,6 +325,25 @@ const char *clf_refusal(const Query &q) {
                          "before sga_set_dense"
                        : "cached local fields over CSR couplings need integer-valued symmetric J in strictly sorted rows "
                          "(no duplicates), zero diagonal, max_i sum_j |J_ij| < 2^15 and h in multiples of 1/2";
+        if (q.opt[OPT_CLF_FIXED_POINT] == 1 && (q.clf_bits == 32 || q.clf_bits == 64)) {
+            // option "clf_fixed_point": D = 2^k J s as exact int32 | int64 (sweep_clf_csr.hip), no accept table
+            if (!q.clf_ok)
+                return q.acc == sga::CSR_ACC_F64_CANON
+                           ? "cached local fields (fixed point): acc class f64-canonical -- no exact fixed point holds a row sum"
+                           : "cached local fields (fixed point): need symmetric J in strictly sorted rows (no duplicates) "
+                             "and a zero diagonal";
+            if ((q.slotted ? (q.max_row_len + 63) / 64 * 64 : q.max_row_len) > 4 * 64 * 8)
+                return q.clf_bits == 64 ? "cached local fields (fixed point, int64 fields): a row is longer than 2048 entries"
+                                        : "cached local fields (fixed point, int32 fields): a row is longer than 2048 entries";
+            if (q.R_local > 0 && sga::sweep_clf_csr_lds_bytes(ldf, q.sstride, 0, q.clf_bits) > 160 * 1024)
+                return q.clf_bits == 64 ? "cached local fields (fixed point): int64 fields and spins of a replica do not fit "
+                                          "LDS (160 KiB: n <= ~20 000)"
+                                        : "cached local fields (fixed point): int32 fields and spins of a replica do not fit "
+                                          "LDS (160 KiB: n <= ~40 000)";
+            return nullptr;
+        }
+        if (q.opt[OPT_CLF_FIXED_POINT] == 1 && !q.clf_ok && q.acc == sga::CSR_ACC_F64_CANON)
+            return "cached local fields (fixed point): acc class f64-canonical -- no exact fixed point holds a row sum";
         if (q.R_local > 0 && (sga::sweep_clf_csr_lds_bytes(ldf, q.sstride, q.table_m) > 160 * 1024 ||
                               (q.slotted ? (q.max_row_len + 63) / 64 * 64 : q.max_row_len) > 4 * 64 * 8))
             return "cached local fields: fields and spins of a replica do not fit LDS (or a row is longer than 2048 entries)";
@@ -344,11 +363,22 @@ const char *clf_refusal(const Query &q) {
 // part of the replicas is hot: ~1.5 us per accept (1.15 alone on its CU ... 1.7 with busy neighbours), and per update
 // 0.38 us on bit-planes / 0.58 us on int8 rows at n = 10^4, ~0.3 us on short rows (profiles/r04_routing.py; fp32
 // rows: estimate).
+// Option "clf_fixed_point": the fixed-point cached-field sweep has no accept table -- every proposal of a window takes
+// the exp path -- and moves 4 | 8-byte fields.  The cost per accept in the units of t_upd is set from the measured
+// break-even (profiles/fixed_point_fields.json): C5 at 100 cities (int64), 2.0 against 8.6 ms per sweep at 0.38 %
+// acceptance -- ~1.5 ms of windows plus ~1.5 us per accept: break-even near 6 % --, and a 20 000-spin binary-grid
+// instance (int32), 18.4 against 3.96 ms at 15.9 %: near 3.4 %.
+static double fixed_point_theta(const Query &q, double t_upd) {
+    const double t_acc = q.clf_bits == 64 ? 8.8 : 6.3;
+    return t_upd / t_acc;
+}
 double routing_theta(const Query &q) {
     const double kn = (double)q.n / 1000.0;
     const double t_upd = q.kind == SGA_ROUTE_CSR ? 0.20 + 0.0008 * (double)q.nnz / (double)q.n  // (C4: 0.68, C2b as CSR: 0.36)
                          : q.storage == SGA_J_T2 ? 0.29 + 0.009 * kn
                                                  : (q.storage == SGA_J_I8 ? 0.27 + 0.031 * kn : 0.30 + 0.12 * kn);
+    if (q.kind == SGA_ROUTE_CSR && q.opt[OPT_CLF_FIXED_POINT] == 1 && (q.clf_bits == 32 || q.clf_bits == 64))
+        return fixed_point_theta(q, t_upd);
     return t_upd / 1.5;
 }
 // AUTO, nothing known yet: the run starts on the kernel that loses least if the guess is wrong: the cached-field
@@ -437,7 +467,9 @@ std::string explain(const Query &q0) {
         if (why) {
             out += q.field_cache == SGA_FIELD_CACHE_ON ? " cached=refused" : " cached=unavailable";
         } else if (q.field_cache == SGA_FIELD_CACHE_ON) {
-            if (q.kind == SGA_ROUTE_CSR) std::snprintf(buf, sizeof(buf), " cached=on(waves=%d)", clf_csr_waves(q));
+            if (q.kind == SGA_ROUTE_CSR && q.opt[OPT_CLF_FIXED_POINT] == 1 && (q.clf_bits == 32 || q.clf_bits == 64))
+                std::snprintf(buf, sizeof(buf), " cached=on(waves=%d fields=int%d fixed-point)", clf_csr_waves(q), q.clf_bits);
+            else if (q.kind == SGA_ROUTE_CSR) std::snprintf(buf, sizeof(buf), " cached=on(waves=%d)", clf_csr_waves(q));
             else
                 std::snprintf(buf, sizeof(buf), " cached=on(waves=%d fields=int%d)",
                               sga::sweep_clf_waves(dense_ldj(q), is_i8(q), std::max(q.R_local, 1), q.cus, (int)q.opt[OPT_CLF_WAVES]),

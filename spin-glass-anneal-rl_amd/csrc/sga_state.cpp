@@ -397,9 +397,17 @@ int sga_describe(sga_engine *e, char *buf, int buflen) {
     if (e->ragged) {
         // (one form: nothing below applies)
     } else if (clf_active(e) && e->csr) {
-        if (e->field_cache == SGA_FIELD_CACHE_ON)
+        if (e->field_cache == SGA_FIELD_CACHE_ON && e->clf_fx_bits)
+            std::snprintf(tmp + std::strlen(tmp), sizeof(tmp) - std::strlen(tmp),
+                          " sweep=cached-local-fields(int%d fixed-point dynamic fields, k=%d, in LDS, row entries read on accept only)",
+                          e->clf_fx_bits, e->clf_fx_k);
+        else if (e->field_cache == SGA_FIELD_CACHE_ON)
             std::snprintf(tmp + std::strlen(tmp), sizeof(tmp) - std::strlen(tmp),
                           " sweep=cached-local-fields(int16 dynamic fields in LDS, row entries read on accept only)");
+        else if (e->clf_fx_bits)
+            std::snprintf(tmp + std::strlen(tmp), sizeof(tmp) - std::strlen(tmp),
+                          " sweep=auto(cached local fields, int%d fixed-point, k=%d, while the hottest replica accepts little; now: %s)",
+                          e->clf_fx_bits, e->clf_fx_k, (!e->auto_unavailable && e->n_route_clf > 0) ? "cached" : "one row per proposal");
         else
             std::snprintf(tmp + std::strlen(tmp), sizeof(tmp) - std::strlen(tmp),
                           " sweep=auto(cached local fields while the hottest replica accepts little; now: %s)",

@@ -47,6 +47,8 @@ class GPUAnnealerConfig:
     field_cache: str = "auto"             # "auto" | "on" | "off": resident local fields, a coupling row read
     #                                       only on accept where the problem allows (sga_set_field_cache) --
     #                                       the same chain bit for bit as "off" (one row read per proposal)
+    fixed_point_fields: bool = False      # engine option "clf_fixed_point": the field cache also serves real-valued
+    #                                       sparse couplings (exact int32 | int64 fixed-point fields; same chain)
     device_index: Optional[int] = None
 
     def __post_init__(self):
@@ -102,6 +104,8 @@ class GPUAnnealer:
         n = model.n_spins
         with AnnealEngine(dev_idx) as eng:
             eng.set_field_cache(cfg.field_cache)  # (before the couplings: "on" keeps a sparse matrix dense)
+            if cfg.fixed_point_fields:
+                eng.set_option("clf_fixed_point", 1)  # (read when the couplings are set)
             model.load_into(eng, storage=cfg.coupling_storage)
             eng.set_update_rule(rule)
             eng.init_replicas(1, seed=fresh_seed(cfg.random_seed), s0=model.spins_int8()[None, :])

@@ -48,6 +48,7 @@ class ParallelTemperingConfig:
     # build-specific
     coupling_storage: str = "auto"
     field_cache: str = "auto"             # resident local fields where the problem allows (identical chain)
+    fixed_point_fields: bool = False      # ... real-valued sparse couplings too (option "clf_fixed_point")
     device_index: Optional[int] = None
     autotune: Optional[bool] = None       # measured launch geometry (None: for long runs only)
 
@@ -91,6 +92,8 @@ class ParallelTempering:
         acc_slot, att_slot = np.zeros(R, np.int64), np.zeros(R, np.int64)
         with AnnealEngine(dev_idx) as eng:
             eng.set_field_cache(cfg.field_cache)  # (before the couplings: "on" keeps a sparse matrix dense)
+            if cfg.fixed_point_fields:
+                eng.set_option("clf_fixed_point", 1)  # (read when the couplings are set)
             model.load_into(eng, storage=cfg.coupling_storage)
             eng.set_update_rule(rule)
             eng.init_replicas(R, seed=fresh_seed(cfg.random_seed),

@@ -50,10 +50,13 @@ class SpinGlassScheduler:
                beta_schedule: Union[str, Sequence[float]] = "geometric", beta_min: float = 0.1,
                beta_max: float = 10.0, exchange_interval: int = 10, n_ladders: int = 1,
                coupling_storage: str = "auto", record_interval: int = 10,
-               autotune: Optional[bool] = None, field_cache: str = "auto") -> AnnealingResult:
+               autotune: Optional[bool] = None, field_cache: str = "auto",
+               fixed_point_fields: bool = False) -> AnnealingResult:
         """field_cache: "auto" keeps every replica's local fields resident where the problem allows it
         (dense integer-valued symmetric couplings) so that a coupling row is read only when a proposal is
-        accepted -- the chain, and with it the result, is the one "off" (a row per proposal) gives."""
+        accepted -- the chain, and with it the result, is the one "off" (a row per proposal) gives.
+        fixed_point_fields: the cache also serves real-valued sparse couplings, as exact fixed-point fields
+        (engine option "clf_fixed_point"); the same chain again."""
         if n_replicas < 1 or n_sweeps < 1 or n_replicas % n_ladders:
             raise ConfigurationError("bad replica / sweep / ladder counts")
         t0 = time.time()
@@ -69,6 +72,8 @@ class SpinGlassScheduler:
         e_hist, t_hist = [], []
         with AnnealEngine(dev) as eng:
             eng.set_field_cache(field_cache)  # (before the couplings: "on" keeps a sparse matrix dense)
+            if fixed_point_fields:
+                eng.set_option("clf_fixed_point", 1)  # (read when the couplings are set)
             ising_model.load_into(eng, storage=coupling_storage)
             eng.init_replicas(n_replicas, seed=fresh_seed(self.random_seed))
             eng.set_ladder(temps, n_ladders)
