@@ -220,9 +220,13 @@ int sga_set_wolff_replay(sga_engine *e, const float *u, int64_t capacity);
 /* Recompute every local replica's energy from scratch: -0.5 s.(J s) - h.s.  Batches of replicas share
  * one pass over the couplings (EnergyComputer.compute_batch_energies, core/energy_computer.py:142-158):
  * dense problems with >= 32 replicas on the matrix cores, CSR problems with >= 64 replicas through a
- * transposed spin-bit matrix; fewer replicas take one pass each.  Same values either way (integer
- * problems: exact; real-valued: the fp64 summation order differs, the fp32-rounded energy does not beyond
- * its last bit). */
+ * transposed spin-bit matrix; fewer replicas take one pass each.  E = -1/2 fp32(X) - fp32(Y) with
+ * mv_i the fp32 row sum, X = sum_i mv_i s_i and Y = sum_i h_i s_i in fp64 in one order per replica that
+ * depends on n alone (blocks of rows, four chains per block, block sums in block order).  Under the
+ * default option "batched_energy" = 1 a replica's energy therefore carries the same bits whatever the
+ * replica count, the sharding (R_local), this call, sga_init_replicas or sga_set_spins: the batched passes
+ * are used only where their row sums and X are the per-replica kernels' bits.  Integer and exactly summable
+ * dyadic problems get the exact sums rounded once (mv_i = fp32(S_i), fp32(X), fp32(Y)). */
 int sga_recompute_energies(sga_engine *e);
 
 /* One nearest-neighbour replica-exchange round over the ladder(s)
@@ -391,7 +395,7 @@ int sga_set_field_cache(sga_engine *e, int mode);
  *                           concurrent launches) instead of the whole launch by the hottest replica    [sweep; SGA_NO_REPLICA_ROUTING]
  *   "batched_energy"        0 = one pass over the couplings per replica, 1 (default) = all replicas in one pass where
  *                           that carries the same bits (not for real-valued couplings that need the canonical
- *                           summation order), 2 = always                                                [sweep; SGA_NO_MFMA_ENERGY]
+ *                           summation order; CSR: only where X is exact in fp64), 2 = always           [sweep; SGA_NO_MFMA_ENERGY]
  *   "fields_scratch_mb"     256 (default): cap in MiB of the scratch of the all-replica field / energy pass over dense
  *                           couplings; larger replica sets go through in tiles of 128-replica blocks    [sweep; SGA_FIELDS_SCRATCH_MB]
  *   "csr_updates_per_step"  -1 = by the longest row (default), 0 = one update at a time, 1 | 2 = pair look-ahead,

@@ -11,7 +11,9 @@
 // (n x R / 8 bytes) cache resident.  Thread (g, q) walks the rows i = g, g + G, ... for the replica
 // word q; a row's sum is rounded to fp32 as torch.mv rounds it, multiplied by the row's own spin and
 // accumulated in fp64; the per-group partial sums are added in group order by the finish pass
-// (deterministic), which also forms  E_r = -1/2 fp32(sum_i mv_ri s_ri) - fp32(h . s_r).
+// (deterministic, but a function of the group count: the same bits as the per-replica kernels' only where the sum
+// is exact, sga_engine.cpp), which also forms  E_r = -1/2 fp32(sum_i mv_ri s_ri) - fp32(h . s_r), h . s in the
+// per-replica kernels' order.
 // EXACT32: integer couplings with row sums below 2^24 accumulate in fp32 (exact); otherwise in fp64.
 #include <type_traits>
 
@@ -34,18 +36,16 @@ __global__ void __launch_bounds__(256) transpose_spin_bits_kernel(const int8_t *
     sb[(long long)i * RW + q] = w;
 }
 
-// hs[r] = sum_i h_i s_ri in fp64, fixed order (lane-strided, tree, waves in order)
+// hs[r] = sum_i h_i s_ri in fp64, in the per-replica kernels' order (sga_kernels.h, energy_block_rows)
 __global__ void __launch_bounds__(256) field_dot_kernel(const float *__restrict__ h, const int8_t *__restrict__ spins,
-                                                        int sstride, int n, double *__restrict__ hs) {
-    __shared__ double red[4];
-    const int tid = threadIdx.x, r = blockIdx.x;
+                                                        int sstride, int n, int eblock, double *__restrict__ hs) {
+    __shared__ double ce[4 * ENERGY_MAX_BLOCKS], ch[4 * ENERGY_MAX_BLOCKS];
+    const int r = blockIdx.x;
     const int8_t *s = spins + (long long)r * sstride;
-    double acc = 0.0;
-    for (int i = tid; i < n; i += 256) acc += (double)h[i] * (double)s[i];
-    acc = wave_sum(acc);
-    if ((tid & 63) == 0) red[tid >> 6] = acc;
-    __syncthreads();
-    if (tid == 0) hs[r] = (red[0] + red[1]) + (red[2] + red[3]);
+    double unused, acc;
+    energy_canonical_sums(
+        n, eblock, [](int) { return 0.0; }, [&](int i) { return (double)h[i] * (double)s[i]; }, ce, ch, unused, acc);
+    if (threadIdx.x == 0) hs[r] = acc;
 }
 
 template <bool EXACT32>
@@ -116,7 +116,7 @@ hipError_t launch_energy_csr_all(const long long *rowptr, const int2 *cv, const 
     double *partial = reinterpret_cast<double *>(sb + (((size_t)n * RW + 1) & ~(size_t)1));
     double *hs = partial + (size_t)groups * 32 * RW;
     hipLaunchKernelGGL(transpose_spin_bits_kernel, dim3((n + 255) / 256, RW), dim3(256), 0, st, spins, sstride, n, R, RW, sb);
-    hipLaunchKernelGGL(field_dot_kernel, dim3(R), dim3(256), 0, st, h, spins, sstride, n, hs);
+    hipLaunchKernelGGL(field_dot_kernel, dim3(R), dim3(256), 0, st, h, spins, sstride, n, energy_block_rows(n), hs);
     CsrEnergyArgs a{rowptr, cv, sb, partial, n, R, RW, groups};
     const long long threads = (long long)groups * RW;
     const dim3 grid((unsigned)((threads + 255) / 256));

@@ -229,45 +229,35 @@ hipError_t launch_fields_dense(const FieldsArgs &a, int mode, hipStream_t st) {
 // From the fields to the energies (and to the resident fields of the cached-field sweep):
 //   E_r = -1/2 fp32(sum_i Y_ri s_ri) - fp32(sum_i h_i s_ri)      (core/ising_model.py:161-168)
 //   F_ri = scale * (Y_ri + h_i)   as int16 | int32               (integer problems only)
-// One workgroup per replica; sums in fp64 in a fixed order (lane-strided, tree, waves in order).
+// One workgroup per replica; the energy's sums in fp64 in the per-replica kernels' order (sga_kernels.h,
+// energy_block_rows), each row's Y_ri rounded to fp32 as their row sums are: the same bits as theirs wherever the
+// row sums are exact.
 template <typename YT>
 __global__ void __launch_bounds__(256) fields_finish_kernel(const FieldsArgs a) {
-    __shared__ double red[8];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    __shared__ double ce[4 * ENERGY_MAX_BLOCKS], ch[4 * ENERGY_MAX_BLOCKS];
+    const int tid = threadIdx.x;
     const int r = blockIdx.x;
     const YT *y = reinterpret_cast<const YT *>(a.Y) + (long long)r * a.ldy;
     const int8_t *s = a.spins + (long long)r * a.sstride;
     int16_t *f16 = a.field_bits == 16 ? reinterpret_cast<int16_t *>(a.fields) + (long long)r * a.ldf : nullptr;
     int32_t *f32 = a.field_bits == 32 ? reinterpret_cast<int32_t *>(a.fields) + (long long)r * a.ldf : nullptr;
-    double e = 0.0, hs = 0.0;
-    for (int i = tid; i < a.n; i += 256) {
-        const double yi = (double)y[i], si = (double)s[i];
-        const float hi = a.h[i];
-        e += yi * si;
-        hs += (double)hi * si;
-        if (f16 || f32) {
-            const int v = (int)((float)a.field_scale * ((float)y[i] + hi));  // exact: integers / half-integers < 2^24
+    if (f16 || f32) {
+        for (int i = tid; i < a.n; i += 256) {
+            const int v = (int)((float)a.field_scale * ((float)y[i] + a.h[i]));  // exact: integers / half-integers < 2^24
             if (f16) f16[i] = (int16_t)v;
             else f32[i] = v;
         }
+        for (int i = a.n + tid; i < a.ldf; i += 256) {  // pad entries: never read by a decision
+            if (f16) f16[i] = 0;
+            else f32[i] = 0;
+        }
     }
-    for (int i = a.n + tid; i < a.ldf && (f16 || f32); i += 256) {  // pad entries: never read by a decision
-        if (f16) f16[i] = 0;
-        else f32[i] = 0;
-    }
-    e = wave_sum(e);
-    hs = wave_sum(hs);
-    if (lane == 0) {
-        red[w] = e;
-        red[4 + w] = hs;
-    }
-    __syncthreads();
-    if (tid == 0 && a.energy) {
-        const double et = (red[0] + red[1]) + (red[2] + red[3]);
-        const double ht = (red[4] + red[5]) + (red[6] + red[7]);
-        a.energy[r] = -0.5 * (double)(float)et + (-(double)(float)ht);
-    }
+    if (!a.energy) return;
+    double et, ht;
+    energy_canonical_sums(
+        a.n, a.eblock, [&](int i) { return (double)(float)y[i] * (double)s[i]; },
+        [&](int i) { return (double)a.h[i] * (double)s[i]; }, ce, ch, et, ht);
+    if (tid == 0) a.energy[r] = -0.5 * (double)(float)et + (-(double)(float)ht);
 }
 
 hipError_t launch_fields_finish(const FieldsArgs &a, bool y_is_int, hipStream_t st) {

@@ -184,4 +184,59 @@ __device__ __forceinline__ void wave_sum2(T &a, T &b) {
     b = read_lane(b, 63);
 }
 
+// ---------------------------------------------------------------------------------------
+// The canonical order of a replica's energy sums (sga_kernels.h, energy_block_rows): blocks of rows, four chains
+// per block, block sums added in block order.
+// ---------------------------------------------------------------------------------------
+// End of one block in a kernel of four waves, wave w having formed chain w in (e, h): the block's sums are added
+// to (e_tot, h_tot) (partial == null: this workgroup takes every block) or written to partial[block][2].
+// red: 8 doubles of LDS.  Called by the whole workgroup.
+__device__ inline void energy_block_done(double e, double h, double *red, double *partial, double &e_tot,
+                                         double &h_tot) {
+    const int tid = threadIdx.x;
+    if ((tid & 63) == 0) {
+        red[tid >> 6] = e;
+        red[4 + (tid >> 6)] = h;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        const double eb = (red[0] + red[1]) + (red[2] + red[3]);
+        const double hb = (red[4] + red[5]) + (red[6] + red[7]);
+        if (partial) {
+            partial[0] = eb;
+            partial[1] = hb;
+        } else {
+            e_tot += eb;
+            h_tot += hb;
+        }
+    }
+    __syncthreads();
+}
+// Both sums of one replica by a whole workgroup from per-row terms x(i), y(i): thread t forms chains t,
+// t + blockDim.x, ... (block c / 4, first row c % 4); thread 0 returns the sums.  ce, ch: 4 ENERGY_MAX_BLOCKS
+// doubles of LDS each.
+template <class FX, class FY>
+__device__ inline void energy_canonical_sums(int n, int block_rows, FX x, FY y, double *ce, double *ch, double &X,
+                                             double &Y) {
+    const int nb = (n + block_rows - 1) / block_rows;
+    for (int c = threadIdx.x; c < 4 * nb; c += blockDim.x) {
+        const int b = c >> 2, i1 = min(n, (b + 1) * block_rows);
+        double e = 0.0, h = 0.0;
+        for (int i = b * block_rows + (c & 3); i < i1; i += 4) {
+            e += x(i);
+            h += y(i);
+        }
+        ce[c] = e;
+        ch[c] = h;
+    }
+    __syncthreads();
+    X = 0.0;
+    Y = 0.0;
+    if (threadIdx.x == 0)
+        for (int b = 0; b < nb; ++b) {
+            X += (ce[4 * b] + ce[4 * b + 1]) + (ce[4 * b + 2] + ce[4 * b + 3]);
+            Y += (ch[4 * b] + ch[4 * b + 1]) + (ch[4 * b + 2] + ch[4 * b + 3]);
+        }
+}
+
 }  // namespace sga

@@ -53,9 +53,11 @@ sga_route_query route_query_of(const sga_engine *e) {
 // then energies and / or the resident fields of the cached-field sweep from them.
 bool fields_pass_applies(const sga_engine *e, int count) {
     // option "batched_energy": 0 = off (A/B switch), 1 = where the batched sums carry the same bits as the
-    // per-replica kernels', 2 = always.  Real-valued couplings that need the canonical summation order keep the
-    // per-replica kernels under 1: the matrix-core pass sums a row in k-order, and the fp32-rounded row sum could
-    // differ in its last bit with the number of replicas recomputed together (sga_set_spins: one; a shard: R_local).
+    // per-replica kernels', 2 = always.  The finish pass adds X and Y in the per-replica kernels' order
+    // (energy_block_rows), so the energies agree bit for bit wherever the row sums do.  Real-valued couplings that
+    // need the canonical summation order keep the per-replica kernels under 1: the matrix-core pass sums a row in
+    // k-order, and the fp32-rounded row sum could differ in its last bit with the number of replicas recomputed
+    // together (sga_set_spins: one; a shard: R_local).
     const long long mode = e->opt[OPT_BATCHED_ENERGY];
     if (mode == 0 || (mode == 1 && e->acc_canon)) return false;
     return !e->csr && !e->tsp && e->n_models == 1 && count >= 32 && e->J_packed;
@@ -102,6 +104,7 @@ int fields_pass(sga_engine *e, int r0, int count, double *energy, void *fields) 
         f.sstride = e->sstride;
         f.field_bits = fields ? e->clf_bits : 0;
         f.field_scale = e->clf_scale;
+        f.eblock = sga::energy_block_rows(e->n);
         HIPCHK(sga::launch_fields_dense(f, mode, e->stream));
         HIPCHK(sga::launch_fields_finish(f, mode == 0, e->stream));
     }
@@ -165,7 +168,8 @@ int recompute_energy_range(sga_engine *e, int r0, int count) {
         if (rc != SGA_ERR_MEMORY) return rc;  // (no room for its scratch: the per-replica kernels below need none)
     }
     const long long batched = e->opt[OPT_BATCHED_ENERGY];  // (one switch for both passes)
-    const bool csr_all = batched == 2 || (batched == 1 && e->csr_acc != sga::CSR_ACC_F64_CANON);
+    // (the pass adds X = sum_i mv_i s_i in an order of its own: under 1 only where X is exact in fp64, csr_x_exact)
+    const bool csr_all = batched == 2 || (batched == 1 && e->csr_x_exact);
     if (e->ragged) {  // ragged CSR batches: one workgroup per replica over its model's rows
         sga::EnergyArgs a{};
         a.rowptr = e->rowptr64;
@@ -211,11 +215,19 @@ int recompute_energy_range(sga_engine *e, int r0, int count) {
     a.reps_per_model = e->n_models > 1 ? e->Rg / e->n_models : 0;
     a.replica_base = e->replica0 + r0;
     a.model_stride_j = (long long)e->n * e->ldj;
-    // few replicas: spread each replica's rows over several workgroups (one workgroup reading all
+    // the canonical order of the sums (sga_kernels.h): blocks of rows (TSP: of cities), a function of n alone
+    const int units = e->tsp ? e->tsp_args.n_cities : e->n;
+    a.block_rows = e->tsp ? (units + sga::ENERGY_MAX_BLOCKS - 1) / sga::ENERGY_MAX_BLOCKS : sga::energy_block_rows(units);
+    a.nblocks = (units + a.block_rows - 1) / a.block_rows;
+    // few replicas: spread each replica's blocks over several workgroups (one workgroup reading all
     // of J took 47 ms at n = 10^4 -- longer than the reference's CPU mv)
-    a.slices = count >= 512 ? 1 : std::max(1, std::min({256, (1024 + count - 1) / count, e->n / 8}));
+    // (then as few slices as take the same blocks each, none left without: whole passes of the bit-spin CSR kernel)
+    const int per_pass = e->csr && !e->tsp && sga::energy_csr_bits_form(e->sstride) ? sga::ENERGY_BITS_BLOCKS_PER_PASS : 1;
+    const int want = count >= 512 ? 1 : std::max(1, std::min({a.nblocks, (1024 + count - 1) / count, e->n / 8}));
+    a.blocks_per_slice = ((a.nblocks + want - 1) / want + per_pass - 1) / per_pass * per_pass;
+    a.slices = (a.nblocks + a.blocks_per_slice - 1) / a.blocks_per_slice;
     if (a.slices > 1) {
-        const size_t need = sizeof(double) * 2 * (size_t)count * a.slices;
+        const size_t need = sizeof(double) * 2 * (size_t)count * a.nblocks;
         if (need > e->epart_bytes) {
             dev_free(e->epart);
             HIPCHK(hipMalloc(&e->epart, need));
@@ -226,7 +238,7 @@ int recompute_energy_range(sga_engine *e, int r0, int count) {
     HIPCHK(e->tsp ? sga::launch_energy_tsp(a, e->tsp_args, e->stream)
            : e->csr ? sga::launch_energy_csr(a, e->stream)
                     : sga::launch_energy_dense(a, e->want_i8, e->stream));
-    HIPCHK(sga::launch_energy_finish(a.partial, a.slices, a.energy, count, e->stream));
+    HIPCHK(sga::launch_energy_finish(a.partial, a.nblocks, a.slices, a.energy, count, e->stream));
     return SGA_OK;
 }
 

@@ -221,6 +221,7 @@ struct sga_engine {
     int auto_interval = 4;              // sweeps until the next look (doubles up to 32)
     std::vector<unsigned long long> auto_mark_acc;
     int csr_acc = sga::CSR_ACC_F64_CANON;  // CSR: how the sweep kernels form a row sum (set time)
+    bool csr_x_exact = false;  // CSR: the fp64 sum X = sum_i mv_i s_i of an energy is exact in any order (set time)
 
     // replicas
     int R = 0, Rg = 0, replica0 = 0;

@@ -130,15 +130,30 @@ struct EnergyArgs {
     double *energy;
     long long ld, ldj;
     int n, sstride, R;
-    // few replicas: the rows of one replica are cut into `slices` contiguous ranges, one workgroup
-    // each (grid = R x slices); the (J-part, h-part) sums land in partial[R][slices][2] and
-    // launch_energy_finish adds them up in slice order.  slices == 1: one workgroup per replica.
-    int slices;
+    // The canonical order of X = sum_i mv_i s_i and Y = sum_i h_i s_i (energy_block_rows): `nblocks` blocks of
+    // `block_rows` rows (TSP: of cities).  Few replicas: the blocks of one replica are cut into `slices` contiguous
+    // ranges, one workgroup each (grid = R x slices); each block's (X, Y) sums land in partial[R][nblocks][2] and
+    // launch_energy_finish adds them up in block order.  slices == 1: one workgroup per replica, same additions.
+    int block_rows, nblocks;
+    int slices, blocks_per_slice;  // slice y takes blocks [y bps, (y + 1) bps); every slice has some
     double *partial;
 };
+// Canonical order of a replica's energy sums, a function of n alone (so that its energy carries the same bits
+// whatever the replica count, slicing, tiling or kernel of the launch): rows in blocks of energy_block_rows(n)
+// (at most ENERGY_MAX_BLOCKS blocks); inside a block, chain c = 0..3 adds the terms of rows c, c + 4, ... in row
+// order from 0; a block's sum is (c0 + c1) + (c2 + c3); X and Y add the block sums in block order, from 0.
+constexpr int ENERGY_MAX_BLOCKS = 256;
+__host__ __device__ inline int energy_block_rows(int n) {
+    const int b = (n + ENERGY_MAX_BLOCKS - 1) / ENERGY_MAX_BLOCKS;
+    return b > 8 ? b : 8;
+}
+// The CSR energy kernel with the replica's spins as bits in LDS (problems beyond the int8 LDS capacity) forms
+// ENERGY_BITS_BLOCKS_PER_PASS blocks at a time: its slices take whole multiples of that.
+constexpr int ENERGY_BITS_BLOCKS_PER_PASS = 4;
+bool energy_csr_bits_form(int sstride);
 // ragged CSR batches: replica r over the rows of model models[(replica_base + r) / reps_per_model] (one slice)
 hipError_t launch_energy_csr_ragged(const EnergyArgs &a, const int2 *models, hipStream_t st);
-hipError_t launch_energy_finish(const double *partial, int slices, double *energy, int R,
+hipError_t launch_energy_finish(const double *partial, int nblocks, int slices, double *energy, int R,
                                 hipStream_t st);
 
 // Local fields of all replicas in one pass over the couplings (fields_dense.hip, matrix cores)
@@ -152,6 +167,7 @@ struct FieldsArgs {
     long long ldj, ldy, ldf;
     int n, R, sstride;
     int field_bits, field_scale;
+    int eblock;  // energy_block_rows(n): the energies are summed in the per-replica kernels' order
 };
 // mode 0: int8 J (i8 MFMA) | 1: fp32 J with exact fp32 sums (f32 MFMA) | 2: fp32 J, real valued (f64 MFMA)
 hipError_t launch_fields_dense(const FieldsArgs &a, int mode, hipStream_t st);
@@ -184,6 +200,7 @@ struct CsrEnergyArgs {
     double *partial;         // [groups][32 RW]
     int n, R, RW, groups;
 };
+// (h . s in the canonical order; X in group order, the same bits only where it is exact: sga_engine.cpp)
 size_t csr_energy_scratch_bytes(int n, int R, int groups);
 hipError_t launch_energy_csr_all(const long long *rowptr, const int2 *cv, const float *h, const int8_t *spins, int sstride,
                                  int n, int R, int groups, bool exact32, void *scratch, double *energy, hipStream_t st);

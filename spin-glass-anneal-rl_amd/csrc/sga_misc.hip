@@ -567,34 +567,33 @@ hipError_t launch_copy_best(const double *energy, const int8_t *spins, double *b
 // ---------------------------------------------------------------------------------------
 // Full energy  E = -0.5 * fp32(s.(J s)) - fp32(h.s)   (core/ising_model.py:149-174;
 // operator form annealing/cuda_kernels.py:284-324, fallback :400-413).
-// One workgroup (4 waves) per replica; spins in LDS; each wave takes rows w, w+4, ...,
+// One workgroup (4 waves) per replica or slice of row blocks; spins in LDS; in a block, wave w takes rows w, w+4, ...,
 // streams the row with 16-B loads, DPP-reduces J[i,:].s, rounds it to fp32 as torch.mv does.
 // ---------------------------------------------------------------------------------------
-// E = -1/2 fp32(sum_i mv_i s_i) - fp32(sum_i h_i s_i) (core/ising_model.py:161-168): written
-// directly, or left as this slice's two sums for energy_finish_kernel
+// E = -1/2 fp32(sum_i mv_i s_i) - fp32(sum_i h_i s_i) (core/ising_model.py:161-168), both sums in the canonical
+// order (sga_kernels.h, energy_block_rows): written by the replica's one workgroup, or added up from the block sums
+// by energy_finish_kernel
 __device__ inline void energy_out(const EnergyArgs &a, int r, double e, double hs) {
-    if (a.slices <= 1) {
-        a.energy[r] = -0.5 * (double)(float)e + (-(double)(float)hs);
-    } else {
-        double *p = a.partial + ((long long)r * a.slices + blockIdx.y) * 2;
-        p[0] = e;
-        p[1] = hs;
-    }
+    a.energy[r] = -0.5 * (double)(float)e + (-(double)(float)hs);
 }
-__global__ void energy_finish_kernel(const double *partial, int slices, double *energy, int R) {
+// where a block's sums go: null = into this workgroup's running sums (slices == 1)
+__device__ inline double *energy_partial(const EnergyArgs &a, int r, int b) {
+    return a.slices > 1 ? a.partial + ((long long)r * a.nblocks + b) * 2 : nullptr;
+}
+__global__ void energy_finish_kernel(const double *partial, int nblocks, double *energy, int R) {
     const int r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= R) return;
     double e = 0.0, hs = 0.0;
-    for (int q = 0; q < slices; ++q) {  // fixed order: deterministic
-        e += partial[((long long)r * slices + q) * 2];
-        hs += partial[((long long)r * slices + q) * 2 + 1];
+    for (int b = 0; b < nblocks; ++b) {  // block order: the same additions as a single workgroup's
+        e += partial[((long long)r * nblocks + b) * 2];
+        hs += partial[((long long)r * nblocks + b) * 2 + 1];
     }
     energy[r] = -0.5 * (double)(float)e + (-(double)(float)hs);
 }
-hipError_t launch_energy_finish(const double *partial, int slices, double *energy, int R,
+hipError_t launch_energy_finish(const double *partial, int nblocks, int slices, double *energy, int R,
                                 hipStream_t st) {
     if (slices <= 1) return hipSuccess;
-    hipLaunchKernelGGL(energy_finish_kernel, dim3((R + 255) / 256), dim3(256), 0, st, partial, slices,
+    hipLaunchKernelGGL(energy_finish_kernel, dim3((R + 255) / 256), dim3(256), 0, st, partial, nblocks,
                        energy, R);
     return hipGetLastError();
 }
@@ -608,8 +607,7 @@ __global__ void __launch_bounds__(256) energy_dense_kernel(const EnergyArgs a) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r = blockIdx.x;
-    const int rows_per_slice = (a.n + a.slices - 1) / a.slices;
-    const int row0 = blockIdx.y * rows_per_slice, row1 = min(a.n, row0 + rows_per_slice);
+    const int b0 = blockIdx.y * a.blocks_per_slice, b1 = min(a.nblocks, b0 + a.blocks_per_slice);
     {
         const int4 *src = reinterpret_cast<const int4 *>(a.spins + (long long)r * a.sstride);
         int4 *dst = reinterpret_cast<int4 *>(s);
@@ -619,43 +617,39 @@ __global__ void __launch_bounds__(256) energy_dense_kernel(const EnergyArgs a) {
     const int model = a.reps_per_model > 0 ? (a.replica_base + r) / a.reps_per_model : 0;
     const JT *J = reinterpret_cast<const JT *>(a.J) + model * a.model_stride_j;
     const float *hvec = a.h + (long long)model * a.n;
-    double e_acc = 0.0, h_acc = 0.0;
-    for (int i = row0 + w; i < row1; i += 4) {
-        const JT *row = J + (long long)i * a.ldj;
-        double acc = 0.0;
-        for (long long c = lane * EPL; c < a.ldj; c += EPC) {
-            if constexpr (sizeof(JT) == 4) {
-                const float4 x = *reinterpret_cast<const float4 *>(row + c);
-                const int sw = *reinterpret_cast<const int *>(s + c);
-                acc += (double)(x.x * (float)(int8_t)(sw));
-                acc += (double)(x.y * (float)(int8_t)(sw >> 8));
-                acc += (double)(x.z * (float)(int8_t)(sw >> 16));
-                acc += (double)(x.w * (float)(sw >> 24));
-            } else {
-                const int4 x = *reinterpret_cast<const int4 *>(row + c);
-                const int4 sv = *reinterpret_cast<const int4 *>(s + c);
-                int t = __builtin_amdgcn_sdot4(x.x, sv.x, 0, false);
-                t = __builtin_amdgcn_sdot4(x.y, sv.y, t, false);
-                t = __builtin_amdgcn_sdot4(x.z, sv.z, t, false);
-                t = __builtin_amdgcn_sdot4(x.w, sv.w, t, false);
-                acc += (double)t;
+    double e_tot = 0.0, h_tot = 0.0;
+    for (int b = b0; b < b1; ++b) {
+        const int row1 = min(a.n, (b + 1) * a.block_rows);
+        double e_acc = 0.0, h_acc = 0.0;
+        for (int i = b * a.block_rows + w; i < row1; i += 4) {
+            const JT *row = J + (long long)i * a.ldj;
+            double acc = 0.0;
+            for (long long c = lane * EPL; c < a.ldj; c += EPC) {
+                if constexpr (sizeof(JT) == 4) {
+                    const float4 x = *reinterpret_cast<const float4 *>(row + c);
+                    const int sw = *reinterpret_cast<const int *>(s + c);
+                    acc += (double)(x.x * (float)(int8_t)(sw));
+                    acc += (double)(x.y * (float)(int8_t)(sw >> 8));
+                    acc += (double)(x.z * (float)(int8_t)(sw >> 16));
+                    acc += (double)(x.w * (float)(sw >> 24));
+                } else {
+                    const int4 x = *reinterpret_cast<const int4 *>(row + c);
+                    const int4 sv = *reinterpret_cast<const int4 *>(s + c);
+                    int t = __builtin_amdgcn_sdot4(x.x, sv.x, 0, false);
+                    t = __builtin_amdgcn_sdot4(x.y, sv.y, t, false);
+                    t = __builtin_amdgcn_sdot4(x.z, sv.z, t, false);
+                    t = __builtin_amdgcn_sdot4(x.w, sv.w, t, false);
+                    acc += (double)t;
+                }
             }
+            const float mv_i = (float)wave_sum(acc);  // torch.mv row, fp32
+            const double si = (double)s[i];
+            e_acc += (double)mv_i * si;
+            h_acc += (double)hvec[i] * si;
         }
-        const float mv_i = (float)wave_sum(acc);  // torch.mv row, fp32
-        const double si = (double)s[i];
-        e_acc += (double)mv_i * si;
-        h_acc += (double)hvec[i] * si;
+        energy_block_done(e_acc, h_acc, red, energy_partial(a, r, b), e_tot, h_tot);
     }
-    if (lane == 0) {
-        red[w] = e_acc;
-        red[4 + w] = h_acc;
-    }
-    __syncthreads();
-    if (tid == 0) {
-        const double e = (red[0] + red[1]) + (red[2] + red[3]);
-        const double hs = (red[4] + red[5]) + (red[6] + red[7]);
-        energy_out(a, r, e, hs);
-    }
+    if (tid == 0 && a.slices <= 1) energy_out(a, r, e_tot, h_tot);
 }
 
 hipError_t launch_energy_dense(const EnergyArgs &a, bool j_is_i8, hipStream_t st) {
@@ -691,31 +685,26 @@ __global__ void __launch_bounds__(256) energy_csr_kernel(const EnergyArgs a) {
         s = reinterpret_cast<const int8_t *>(smem);
         __syncthreads();
     }
-    const int rows_per_slice = (a.n + a.slices - 1) / a.slices;
-    const int row0 = blockIdx.y * rows_per_slice, row1 = min(a.n, row0 + rows_per_slice);
-    double e_acc = 0.0, h_acc = 0.0;
-    for (int i = row0 + w; i < row1; i += 4) {
-        double acc = 0.0;
-        for (long long j = a.rowptr[i] + lane; j < a.rowptr[i + 1]; j += 64)
-        {
-            const int2 ent = a.cv[j];
-            acc += (double)(__int_as_float(ent.y) * (float)s[ent.x]);
+    const int b0 = blockIdx.y * a.blocks_per_slice, b1 = min(a.nblocks, b0 + a.blocks_per_slice);
+    double e_tot = 0.0, h_tot = 0.0;
+    for (int b = b0; b < b1; ++b) {
+        const int row1 = min(a.n, (b + 1) * a.block_rows);
+        double e_acc = 0.0, h_acc = 0.0;
+        for (int i = b * a.block_rows + w; i < row1; i += 4) {
+            double acc = 0.0;
+            for (long long j = a.rowptr[i] + lane; j < a.rowptr[i + 1]; j += 64)
+            {
+                const int2 ent = a.cv[j];
+                acc += (double)(__int_as_float(ent.y) * (float)s[ent.x]);
+            }
+            const float mv_i = (float)wave_sum(acc);
+            const double si = (double)s[i];
+            e_acc += (double)mv_i * si;
+            h_acc += (double)a.h[i] * si;
         }
-        const float mv_i = (float)wave_sum(acc);
-        const double si = (double)s[i];
-        e_acc += (double)mv_i * si;
-        h_acc += (double)a.h[i] * si;
+        energy_block_done(e_acc, h_acc, red, energy_partial(a, r, b), e_tot, h_tot);
     }
-    if (lane == 0) {
-        red[w] = e_acc;
-        red[4 + w] = h_acc;
-    }
-    __syncthreads();
-    if (tid == 0) {
-        const double e = (red[0] + red[1]) + (red[2] + red[3]);
-        const double hs = (red[4] + red[5]) + (red[6] + red[7]);
-        energy_out(a, r, e, hs);
-    }
+    if (tid == 0 && a.slices <= 1) energy_out(a, r, e_tot, h_tot);
 }
 
 // Problems beyond the int8 LDS capacity: the replica's spins as bits in LDS (as in the sweep
@@ -733,51 +722,69 @@ __global__ void __launch_bounds__(64 * ENERGY_BIG_WAVES) energy_csr_bits_kernel(
     spins_to_bits(a.spins + (long long)r * a.sstride, bits, a.sstride, tid, blockDim.x);
     __syncthreads();
     auto spin_f = [&](int c) -> float { return ((bits[c >> 5] >> (c & 31)) & 1u) ? -1.0f : 1.0f; };
-    const int rows_per_slice = (a.n + a.slices - 1) / a.slices;
-    const int row0 = blockIdx.y * rows_per_slice, row1 = min(a.n, row0 + rows_per_slice);
-    double e_acc = 0.0, h_acc = 0.0;
-    for (int i = row0 + w; i < row1; i += ENERGY_BIG_WAVES) {
-        const long long beg = a.rowptr[i], end = a.rowptr[i + 1];
-        double acc = 0.0;
-        for (long long j0 = beg + lane; j0 < end; j0 += 64 * ENERGY_BIG_UNROLL) {
-            int c[ENERGY_BIG_UNROLL];
-            float v[ENERGY_BIG_UNROLL];
+    // four blocks at a time: waves 4k .. 4k + 3 form the four chains of block b + k (sga_kernels.h)
+    constexpr int BPR = ENERGY_BIG_WAVES / 4;
+    static_assert(BPR == ENERGY_BITS_BLOCKS_PER_PASS, "slices take whole passes (sga_engine.cpp)");
+    const int b0 = blockIdx.y * a.blocks_per_slice, b1 = min(a.nblocks, b0 + a.blocks_per_slice);
+    double e_tot = 0.0, h_tot = 0.0;
+    for (int bb = b0; bb < b1; bb += BPR) {
+        const int b = bb + (w >> 2);
+        const int row1 = b < b1 ? min(a.n, (b + 1) * a.block_rows) : 0;
+        double e_acc = 0.0, h_acc = 0.0;
+        for (int i = b * a.block_rows + (w & 3); i < row1; i += 4) {
+            const long long beg = a.rowptr[i], end = a.rowptr[i + 1];
+            double acc = 0.0;
+            for (long long j0 = beg + lane; j0 < end; j0 += 64 * ENERGY_BIG_UNROLL) {
+                int c[ENERGY_BIG_UNROLL];
+                float v[ENERGY_BIG_UNROLL];
 #pragma unroll
-            for (int q = 0; q < ENERGY_BIG_UNROLL; ++q) {
-                const long long j = j0 + 64 * q;
-                const bool in = j < end;
-                const int2 ent = in ? a.cv[j] : make_int2(0, 0);
-                c[q] = ent.x;
-                v[q] = __int_as_float(ent.y);
+                for (int q = 0; q < ENERGY_BIG_UNROLL; ++q) {
+                    const long long j = j0 + 64 * q;
+                    const bool in = j < end;
+                    const int2 ent = in ? a.cv[j] : make_int2(0, 0);
+                    c[q] = ent.x;
+                    v[q] = __int_as_float(ent.y);
+                }
+#pragma unroll
+                for (int q = 0; q < ENERGY_BIG_UNROLL; ++q) acc += (double)(v[q] * spin_f(c[q]));
             }
-#pragma unroll
-            for (int q = 0; q < ENERGY_BIG_UNROLL; ++q) acc += (double)(v[q] * spin_f(c[q]));
+            const float mv_i = (float)wave_sum(acc);
+            const double si = (double)spin_f(i);
+            e_acc += (double)mv_i * si;
+            h_acc += (double)a.h[i] * si;
         }
-        const float mv_i = (float)wave_sum(acc);
-        const double si = (double)spin_f(i);
-        e_acc += (double)mv_i * si;
-        h_acc += (double)a.h[i] * si;
-    }
-    if (lane == 0) {
-        red[w] = e_acc;
-        red[ENERGY_BIG_WAVES + w] = h_acc;
-    }
-    __syncthreads();
-    if (tid == 0) {
-        double e = 0.0, hs = 0.0;
-        for (int q = 0; q < ENERGY_BIG_WAVES; ++q) {
-            e += red[q];
-            hs += red[ENERGY_BIG_WAVES + q];
+        if (lane == 0) {
+            red[w] = e_acc;
+            red[ENERGY_BIG_WAVES + w] = h_acc;
         }
-        energy_out(a, r, e, hs);
+        __syncthreads();
+        if (tid == 0)
+            for (int k = 0; k < BPR && bb + k < b1; ++k) {
+                const double *re = red + 4 * k, *rh = red + ENERGY_BIG_WAVES + 4 * k;
+                const double eb = (re[0] + re[1]) + (re[2] + re[3]), hb = (rh[0] + rh[1]) + (rh[2] + rh[3]);
+                double *p = energy_partial(a, r, bb + k);
+                if (p) {
+                    p[0] = eb;
+                    p[1] = hb;
+                } else {
+                    e_tot += eb;
+                    h_tot += hb;
+                }
+            }
+        __syncthreads();
     }
+    if (tid == 0 && a.slices <= 1) energy_out(a, r, e_tot, h_tot);
 }
 
+bool energy_csr_bits_form(int sstride) {
+    const size_t lds = (size_t)sstride + 64, lds_bits = (size_t)sstride / 8 + 2 * ENERGY_BIG_WAVES * sizeof(double);
+    return lds > 160 * 1024 - 256 && sstride % 128 == 0 && lds_bits <= 160 * 1024 - 256;
+}
 hipError_t launch_energy_csr(const EnergyArgs &a, hipStream_t st) {
     const size_t lds = (size_t)a.sstride + 64;
     if (lds > 160 * 1024 - 256) {
         const size_t lds_bits = (size_t)a.sstride / 8 + 2 * ENERGY_BIG_WAVES * sizeof(double);
-        if (a.sstride % 128 == 0 && lds_bits <= 160 * 1024 - 256) {
+        if (energy_csr_bits_form(a.sstride)) {
             hipError_t e = ensure_lds_limit(reinterpret_cast<const void *>(energy_csr_bits_kernel), lds_bits);
             if (e != hipSuccess) return e;
             hipLaunchKernelGGL(energy_csr_bits_kernel, dim3(a.R, a.slices), dim3(64 * ENERGY_BIG_WAVES), lds_bits,

@@ -309,6 +309,12 @@ int set_csr_common(sga_engine *e, const void *rowptr, bool wide_extents, const i
             e->csr_acc = sga::CSR_ACC_F64_CANON;
         if (e->opt[OPT_FORCE_CSR_ACC] > 0)  // parity tests: the slower forms
             e->csr_acc = std::max(e->csr_acc, std::min(3, (int)e->opt[OPT_FORCE_CSR_ACC]));
+        // Is X = sum_i mv_i s_i exact in fp64 in any order?  Every row sum is exact (classes f32 / f64-exact) and a
+        // multiple of 2^e_lo, so is its fp32 rounding mv_i; every partial sum of X is at most n max_i sum_j |J_ij|
+        // (mj: an fp32 rounding, < 1 ulp either way).  Then the all-replica pass's group order gives the bits of the
+        // per-replica kernels' order (recompute_energy_range).
+        e->csr_x_exact = e->csr_acc != sga::CSR_ACC_F64_CANON &&
+                         (!any || std::ldexp((double)n * (double)e->row_j_abs_max * (1.0 + 0x1.0p-20), -e_lo) < 0x1.0p53);
         // Option "clf_fixed_point": the cached-field sweep for the problems the int16 form does not take.  Every row
         // sum is exact (acc classes f32 / f64-exact), and every set bit of every J lies at or above 2^-k, k = minus the
         // exponent of the lowest set bit: 2^k sum_j J_ij s_j is an integer of at most B = 2^k max_i sum_j |J_ij| (< 2^53
@@ -766,6 +772,7 @@ int sga_set_csr_batch(sga_engine *e, int n_models, const int32_t *n_spins, const
     }
     if (e->opt[OPT_FORCE_CSR_ACC] > 0) acc_b = std::max(acc_b, std::min(3, (int)e->opt[OPT_FORCE_CSR_ACC]));
     e->csr_acc = acc_b;
+    e->csr_x_exact = false;  // (no all-replica pass over ragged batches)
     e->table_scale = acc_b == sga::CSR_ACC_F32_TABLE ? scale_b : 1;
     e->table_m = acc_b == sga::CSR_ACC_F32_TABLE ? (int)std::min((double)e->table_scale * m_b, 2048.0) : 0;
     e->csr_row_abs_max = m_b;

@@ -519,7 +519,7 @@ hipError_t launch_sweep_tsp(const SweepArgs &a, const TspArgs &t, int waves, int
 
 // ---------------------------------------------------------------------------------------
 // Full energy on the same structure: -1/2 fp32(sum_i mv_i s_i) - fp32(h . s) with mv_i the fp32
-// row sum (core/ising_model.py:149-174).  Grid (replica, slice of cities); 4 waves, one row each.
+// row sum (core/ising_model.py:149-174).  Grid (replica, slice of city blocks); 4 waves, one row each.
 // ---------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) energy_tsp_kernel(const EnergyArgs a, const TspArgs t) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -531,42 +531,33 @@ __global__ void __launch_bounds__(256) energy_tsp_kernel(const EnergyArgs a, con
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r = blockIdx.x;
     tsp_load_spins(a.spins + (long long)r * a.sstride, bits, sums, n, cw, tid, (int)blockDim.x);
-    const int per = (n + a.slices - 1) / a.slices;
-    const int c0 = blockIdx.y * per, c1 = min(n, c0 + per);
-    double e_acc = 0.0, h_acc = 0.0;
-    for (int c = c0; c < c1; ++c) {
-        const float *rp = t.nd4t + (long long)c * (t.row_bytes >> 2);
-        const float *rn = t.nd4 + (long long)c * (t.row_bytes >> 2);
-        for (int p = w; p < n; p += 4) {
-            const int pm = p == 0 ? n - 1 : p - 1, pn = p == n - 1 ? 0 : p + 1;
-            double acc = 0.0;
-            for (int city0 = 4 * lane; city0 < t.npad; city0 += 256)
-                tsp_accumulate(acc, *reinterpret_cast<const float4 *>(rp + city0),
-                               *reinterpret_cast<const float4 *>(rn + city0), bits, cw, pm, pn, city0);
-            const double dist = wave_sum(acc);
-            const int si = ((bits[p * cw + (c >> 5)] >> (c & 31)) & 1u) ? -1 : 1;
-            const double row = (double)t.a2 * (double)(sums[c] - si) + (double)t.b2 * (double)(sums[n + p] - si) + dist;
-            const float mv = (float)row;
-            e_acc += (double)mv * (double)si;
-            h_acc += (double)a.h[c * n + p] * (double)si;
+    // the canonical order (sga_kernels.h) over blocks of a.block_rows cities: chain w = positions w, w + 4, ... of
+    // every city of the block, city by city
+    const int b0 = blockIdx.y * a.blocks_per_slice, b1 = min(a.nblocks, b0 + a.blocks_per_slice);
+    double e_tot = 0.0, h_tot = 0.0;
+    for (int b = b0; b < b1; ++b) {
+        double e_acc = 0.0, h_acc = 0.0;
+        for (int c = b * a.block_rows; c < min(n, (b + 1) * a.block_rows); ++c) {
+            const float *rp = t.nd4t + (long long)c * (t.row_bytes >> 2);
+            const float *rn = t.nd4 + (long long)c * (t.row_bytes >> 2);
+            for (int p = w; p < n; p += 4) {
+                const int pm = p == 0 ? n - 1 : p - 1, pn = p == n - 1 ? 0 : p + 1;
+                double acc = 0.0;
+                for (int city0 = 4 * lane; city0 < t.npad; city0 += 256)
+                    tsp_accumulate(acc, *reinterpret_cast<const float4 *>(rp + city0),
+                                   *reinterpret_cast<const float4 *>(rn + city0), bits, cw, pm, pn, city0);
+                const double dist = wave_sum(acc);
+                const int si = ((bits[p * cw + (c >> 5)] >> (c & 31)) & 1u) ? -1 : 1;
+                const double row = (double)t.a2 * (double)(sums[c] - si) + (double)t.b2 * (double)(sums[n + p] - si) + dist;
+                const float mv = (float)row;
+                e_acc += (double)mv * (double)si;
+                h_acc += (double)a.h[c * n + p] * (double)si;
+            }
         }
+        energy_block_done(e_acc, h_acc, red, a.slices > 1 ? a.partial + ((long long)r * a.nblocks + b) * 2 : nullptr,
+                          e_tot, h_tot);
     }
-    if (lane == 0) {
-        red[w] = e_acc;
-        red[4 + w] = h_acc;
-    }
-    __syncthreads();
-    if (tid == 0) {
-        const double e = (red[0] + red[1]) + (red[2] + red[3]);
-        const double hs = (red[4] + red[5]) + (red[6] + red[7]);
-        if (a.slices <= 1) {
-            a.energy[r] = -0.5 * (double)(float)e + (-(double)(float)hs);
-        } else {
-            double *o = a.partial + ((long long)r * a.slices + blockIdx.y) * 2;
-            o[0] = e;
-            o[1] = hs;
-        }
-    }
+    if (tid == 0 && a.slices <= 1) a.energy[r] = -0.5 * (double)(float)e_tot + (-(double)(float)h_tot);
 }
 
 hipError_t launch_energy_tsp(const EnergyArgs &a, const TspArgs &t, hipStream_t st) {

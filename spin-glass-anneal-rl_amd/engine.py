@@ -296,6 +296,10 @@ class AnnealEngine:
         hp, k4 = _buf(h, np.float32, "float32")
         n = (k1.numel() if _is_tensor(k1) else k1.size) - 1
         nnz = k2.numel() if _is_tensor(k2) else k2.size
+        if k3 is not None and (k3.numel() if _is_tensor(k3) else k3.size) != nnz:  # (the C call reads nnz values, n fields)
+            raise AnnealingError("CSR values must have one entry per column index")
+        if k4 is not None and (k4.numel() if _is_tensor(k4) else k4.size) != n:
+            raise AnnealingError("external fields must have n entries")
         fn, name = (self._lib.sga_set_csr64, "sga_set_csr64") if wide else (self._lib.sga_set_csr, "sga_set_csr")
         N.check(fn(self._h, rp, ci, vp, hp, int(n), int(nnz)), name)
         self.n, self.R, self.n_models = n, 0, 1
