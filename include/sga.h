@@ -409,6 +409,15 @@ int sga_set_field_cache(sga_engine *e, int mode);
  *   "zero_slot_every"       0 = 2^21 (default), k: an all-zero slot inside the slotted layout after every k slots [set; SGA_ZERO_SLOT_EVERY]
  *   "csr_bits"              0 | 1 (default)   bit spins where they keep more replicas LDS resident      [init; SGA_NO_CSR_BITS]
  *   "force_csr_bits"        0 (default) | 1   CSR sweeps with bit spins whatever the size               [init; SGA_FORCE_CSR_BIG]
+ *   "row_shared"            0 | 1 | 2 (default)   dense integer problems (one model, J and h integer with exact fp32 sums,
+ *                           J symmetric with a zero diagonal, |J| <= 255), production sweeps with the field cache off:
+ *                           "row-shared windows" (csrc/sweep_dense_rs.hip) -- each sweep cut into windows of W updates per
+ *                           replica, each proposed row read ONCE per window and dotted with the window-start spins of every
+ *                           replica that proposes it, the chain then walked per replica with exact corrections for the
+ *                           window's earlier accepts.  Same chain.  0 = never, 1 = wherever it applies (W: option
+ *                           "row_shared_window"), 2 = where sga_autotune measured it ahead of every geometry by more than 1 % [sweep; SGA_ROW_SHARED]
+ *   "row_shared_window"     0 (default) | 256 | 512 | 1024 (other values: rounded down): W under "row_shared" = 1 (0: the
+ *                           autotuner's, else 1024)                                      [sweep; SGA_ROW_SHARED_WINDOW]
  * sga_option_name enumerates the keys (index 0, 1, ... until SGA_ERR_INVALID).
  * (No reference counterpart: the reference has one code path, core/spin_dynamics.py:61-152.) */
 int sga_set_option(sga_engine *e, const char *key, int64_t value);
@@ -424,7 +433,9 @@ int sga_set_tuning(sga_engine *e, int waves_per_replica, int sweeps_per_launch);
  * results are unaffected.  Candidates within 1 % of the fastest are a tie, which goes to the fewest waves / the simpler
  * form (a fixed preference order: other boxes and later profiles see the same pick).  The pick stays as
  * sga_set_tuning / option "csr_updates_per_step" would have set it (readable through sga_get_geometry /
- * sga_get_option).  No-op for sga_set_tsp problems.
+ * sga_get_option).  Dense problems under option "row_shared" = 2 also time the row-shared windows at W = 256, 512 and
+ * 1024 on the winning geometry (table entries "row-shared:W<W>") and keep the fastest where it beats the fastest
+ * geometry by more than 1 %; *best_ms_per_sweep is the fastest GEOMETRY's figure either way.  No-op for sga_set_tsp problems.
  * (No reference counterpart: the reference has no launch geometry.) */
 int sga_autotune(sga_engine *e, double *best_ms_per_sweep);
 /* What the last sga_autotune of this engine measured: "candidate=ms per sweep;..." (dense: "<waves>x<chunks per wave>",

@@ -135,6 +135,7 @@ int sga_autotune(sga_engine *e, double *best_ms_per_sweep) {
     double *en = nullptr, *ben = nullptr;
     unsigned long long *acc = nullptr;
     auto release = [&]() {
+        e->rs_suspend = false;
         dev_free(spins_c);
         dev_free(best_c);
         dev_free(en);
@@ -170,6 +171,8 @@ int sga_autotune(sga_engine *e, double *best_ms_per_sweep) {
     e->tune_table.clear();
     const int user_cache = e->field_cache;  // the geometry belongs to the row-per-proposal kernels
     e->field_cache = SGA_FIELD_CACHE_OFF;
+    e->rs_suspend = true;  // (the geometry trials time the row-per-proposal kernel, whatever option "row_shared" says)
+    e->rs_tuned_w = 0;
 
     // lay the replicas out for `waves` (0 = heuristic) and put the saved state back
     auto layout = [&](int waves) -> int {
@@ -256,6 +259,34 @@ int sga_autotune(sga_engine *e, double *best_ms_per_sweep) {
                 best_w = w;
                 break;
             }
+    // Row-shared windows (sweep_dense_rs.hip, option "row_shared" = 2): W = 256, 512, 1024 timed on the winner's layout
+    // the same way, appended to the table as "row-shared:W<W>"; the form is kept only where it beats the fastest
+    // geometry by more than the same 1 % (ties go to the row-per-proposal kernel).  *best_ms_per_sweep stays the
+    // fastest geometry's figure.
+    e->rs_suspend = false;
+    if (rc == SGA_OK && best_w >= 0 && e->opt[OPT_ROW_SHARED] == 2) {
+        double best_rs = 1e300;
+        int pick = 0;
+        for (int W : {256, 512, 1024}) {
+            e->rs_tuned_w = W;
+            if (row_shared_window(e, true) != W) break;  // (the problem does not admit the form)
+            rc = layout(best_w);
+            if (rc != SGA_OK) break;
+            double t1 = 0.0, t = 0.0;
+            rc = timed(1, t1);
+            if (rc != SGA_OK) break;
+            if (std::strncmp(sga::last_sweep_kernel(), "sweep_dense_rs", 14) != 0) break;  // (its scratch was not to be had)
+            const int k = t1 > 0.0 ? (int)std::min(64.0, std::max(1.0, std::ceil(2.0 / t1))) : 1;
+            rc = timed(k, t);
+            if (rc != SGA_OK) break;
+            char item[64];
+            std::snprintf(item, sizeof(item), ";row-shared:W%d=%.4f", W, t / k);
+            e->tune_table += item;
+            if (t / k < best_rs) best_rs = t / k, pick = W;
+        }
+        e->rs_tuned_w = (rc == SGA_OK && pick > 0 && best_rs < best * 0.99) ? pick : 0;
+        if (!e->rs_tuned_w) e->free_row_shared();
+    }
     // leave with the winner (or the caller's setting if something failed) and the saved state
     e->timing = was_timing;
     e->tune_spl = user_spl;

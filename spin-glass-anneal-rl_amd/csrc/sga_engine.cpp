@@ -113,6 +113,52 @@ int fields_pass(sga_engine *e, int r0, int count, double *energy, void *fields) 
 
 // The cached-local-field sweep serves this problem / these replicas?  why: the reason when it does not
 // (sga_route.cpp, clf_refusal).
+// Row-shared windows (sweep_dense_rs.hip, option "row_shared"): the window W of the form for sweeps whose arguments are
+// the production ones (lean), 0 where today's row-per-proposal kernel runs.  The form needs what the look-ahead form
+// needs -- one dense model, integer J and h with exact fp32 sums (the accept table), Metropolis -- and J symmetric with a
+// zero diagonal (a flip's correction is read from the flipped site's row), |J| <= 255 (bit-planes of |J|).
+// 1 = wherever it applies (W: option "row_shared_window", else the autotuner's, else 1024), 2 = where sga_autotune
+// measured it ahead (default).
+int row_shared_window(const sga_engine *e, bool lean) {
+    const long long o = e->opt[OPT_ROW_SHARED];
+    if (o == 0 || e->rs_suspend || !lean || e->rule != SGA_RULE_METROPOLIS || e->field_cache != SGA_FIELD_CACHE_OFF) return 0;
+    if (e->csr || e->tsp || e->ragged || e->n_models != 1 || e->table_m <= 0 || e->acc64 || !e->consistent_dE) return 0;
+    if (e->opt[OPT_LOOK_AHEAD] == 0 || e->opt[OPT_FORCE_GENERAL] != 0 || !e->J_packed) return 0;
+    if (sga::row_shared_planes(e->j_abs_max) == 0 || (long long)e->R * e->n >= (1ll << 31) || e->R >= (1 << 20)) return 0;
+    if (o == 2) return e->rs_tuned_w;
+    const long long fw = e->opt[OPT_ROW_SHARED_WINDOW];  // (option "row_shared_window": W for option 1)
+    return fw >= 1024 ? 1024 : fw >= 512 ? 512 : fw >= 256 ? 256 : (e->rs_tuned_w > 0 ? e->rs_tuned_w : 1024);
+}
+
+// the form's scratch for W: false (and the row-per-proposal kernel runs) if it cannot be had
+static bool ensure_row_shared(sga_engine *e, int W, hipStream_t st) {
+    if (e->rs.cnt && e->rs.W == W && e->rs_R == e->R && e->rs_n == e->n) return true;
+    e->free_row_shared();
+    const size_t n = (size_t)e->n, R = (size_t)e->R, nwin = (n + (size_t)W - 1) / (size_t)W;
+    const int nw32 = sga::row_shared_nw32(e->n);
+    hipError_t he = hipMalloc(&e->rs.cnt, sizeof(int) * nwin * n);
+    if (he == hipSuccess) he = hipMalloc(&e->rs.off, sizeof(int) * nwin * (n + 1));
+    if (he == hipSuccess) he = hipMalloc(&e->rs.cur, sizeof(int) * nwin * n);
+    if (he == hipSuccess) he = hipMalloc(&e->rs.ent, sizeof(int) * R * n);
+    if (he == hipSuccess) he = hipMalloc(&e->rs.base, sizeof(int) * R * (size_t)W);
+    if (he == hipSuccess) he = hipMalloc(&e->rs.bits, sizeof(uint32_t) * R * (size_t)nw32);
+    if (he == hipSuccess) he = hipMemsetAsync(e->rs.cnt, 0, sizeof(int) * nwin * n, st);
+    if (he != hipSuccess) {
+        (void)hipGetLastError();
+        e->free_row_shared();
+        return false;
+    }
+    int lw = 0;
+    while ((1 << lw) < W) ++lw;
+    e->rs.W = W;
+    e->rs.log_w = lw;
+    e->rs.nw32 = nw32;
+    e->rs.planes = sga::row_shared_planes(e->j_abs_max);
+    e->rs_R = e->R;
+    e->rs_n = e->n;
+    return true;
+}
+
 bool clf_possible(const sga_engine *e, const char **why) {
     const sga_route_query q = route_query_of(e);
     const char *reason = sga_route::clf_refusal(q);
@@ -867,6 +913,13 @@ int sga_sweep(sga_engine *e, int n_sweeps, int site_mode, int arith, const doubl
         e->fields_valid = false;  // the row-per-proposal kernels move the spins only
     }
     e->last_mixed[0] = '\0';
+    // row-shared windows (sweep_dense_rs.hip): one coupling-row read per proposed site and window
+    int rs_w = 0;
+    if (!clf && !wolff && !exact_mode) {
+        const bool lean_call = site_mode == SGA_SITE_RANDOM && arith == SGA_ARITH_F64 && !d_acc.ptr && !d_dE.ptr;
+        rs_w = row_shared_window(e, lean_call);
+        if (rs_w && !ensure_row_shared(e, rs_w, st)) rs_w = 0;
+    }
 
     for (int k0 = 0; k0 < n_sweeps; k0 += spl) {
         const int ks = std::min(spl, n_sweeps - k0);
@@ -1038,6 +1091,8 @@ int sga_sweep(sga_engine *e, int n_sweeps, int site_mode, int arith, const doubl
             le = sga::launch_sweep_tsp(a, e->tsp_args, e->tsp_waves, e->tsp_passes, st);
         } else if (e->csr) {
             le = sga::launch_sweep_csr(a, e->waves, st);
+        } else if (rs_w) {
+            le = sga::launch_sweep_dense_rs(a, e->rs, e->want_i8, st);
         } else {
             le = launch_dense_rows(a, st);
         }

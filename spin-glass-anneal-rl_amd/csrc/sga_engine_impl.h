@@ -220,6 +220,22 @@ struct sga_engine {
     long long auto_mark_attempted = 0;  // per-replica attempts at the last look
     int auto_interval = 4;              // sweeps until the next look (doubles up to 32)
     std::vector<unsigned long long> auto_mark_acc;
+    // row-shared windows (sweep_dense_rs.hip, option "row_shared"): the window the autotuner picked (0: none), the
+    // plan / field scratch and what it was sized for; rs_suspend keeps the form out of the autotuner's geometry trials
+    int rs_tuned_w = 0;
+    bool rs_suspend = false;
+    sga::RowSharedPlan rs{};
+    int rs_R = 0, rs_n = 0;
+    void free_row_shared() {
+        dev_free(rs.cnt);
+        dev_free(rs.off);
+        dev_free(rs.cur);
+        dev_free(rs.ent);
+        dev_free(rs.base);
+        dev_free(rs.bits);
+        rs = sga::RowSharedPlan{};
+        rs_R = rs_n = 0;
+    }
     int csr_acc = sga::CSR_ACC_F64_CANON;  // CSR: how the sweep kernels form a row sum (set time)
     bool csr_x_exact = false;  // CSR: the fp64 sum X = sum_i mv_i s_i of an energy is exact in any order (set time)
 
@@ -291,6 +307,8 @@ struct sga_engine {
         model_row0.clear();
         n = 0;
         ld = 0;
+        free_row_shared();
+        rs_tuned_w = 0;
     }
     void free_replicas() {
         dev_free(spins);
@@ -320,6 +338,8 @@ struct sga_engine {
         auto_mark_attempted = 0;
         auto_interval = 4;
         auto_mark_acc.clear();
+        free_row_shared();
+        rs_tuned_w = 0;
         R = Rg = 0;
         n_ladders = 0;
     }
@@ -351,6 +371,7 @@ bool clf_active(const sga_engine *e);
 int ensure_fields(sga_engine *e);
 int recompute_energy_range(sga_engine *e, int r0, int count);
 int ensure_packed(sga_engine *e);
+int row_shared_window(const sga_engine *e, bool lean);
 // ---- sga_problem.cpp
 bool csr_rows_medium(const sga_engine *e);
 int csr_updates_per_step(const sga_engine *e);

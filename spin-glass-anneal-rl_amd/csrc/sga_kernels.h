@@ -343,6 +343,23 @@ hipError_t launch_check_symmetric(const float *J, long long ldJ, long long rows,
 hipError_t launch_update_best(const double *energy, const int8_t *spins, double *best_energy,
                               int8_t *best_spins, int sstride, int R, hipStream_t st);
 
+// Row-shared windows (sweep_dense_rs.hip): the dense sweep of integer problems with one coupling-row read per
+// proposed site and window of W updates per replica.  Scratch of the window plan and the fields:
+struct RowSharedPlan {
+    int *cnt;        // [n_windows][n] proposals per (window, site); zero between sweeps
+    int *off;        // [n_windows][n + 1] first entry of each (window, site)
+    int *cur;        // [n_windows][n] fill cursors
+    int *ent;        // [R n] (replica << log_w | update in window), grouped by (window, site)
+    int *base;       // [R][W] row sums against the window-start spins
+    uint32_t *bits;  // [R][nw32] window-start spins, 1 = down (the layout of sweep_dense_rs.hip)
+    int W, log_w, nw32, planes;  // planes: magnitude bit-planes of |J| (1 | 3 | 8)
+};
+int row_shared_planes(int j_abs_max);  // 0: |J| beyond 255, the form does not apply
+inline int row_shared_nw32(int n) { return 8 * ((n + 255) / 256); }
+// a.n_sweeps sweeps: spins -> bits, then per sweep the plan, per window fields + chain, best tracking.  Production
+// arguments only (Philox sites, Metropolis with the accept table, fp64 rule, no per-update traces, all replicas).
+hipError_t launch_sweep_dense_rs(const SweepArgs &a, const RowSharedPlan &p, bool j_is_i8, hipStream_t st);
+
 // operator-form PT exchange (cuda_kernels.py:415-443): decide sequentially, then permute rows
 hipError_t launch_op_exchange(float *spins, float *tmp_rows, float *energies, const float *temps,
                               const float *u, int32_t *src_of_pos, int *n_accepted,

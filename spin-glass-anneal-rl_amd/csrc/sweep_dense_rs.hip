@@ -1,0 +1,352 @@
+// sweep_dense_rs.hip -- "row-shared windows": the dense Metropolis sweep of integer problems with ONE read of a
+// coupling row per proposed site and window, instead of one per proposal.
+//
+// The sites and uniforms come from the counter RNG (the stream of fetch_pair / PairSource), so every replica's
+// proposals are known ahead of the chain.  A sweep is cut into windows of W updates per replica; each window runs
+//   * fields: one workgroup per proposed site i reads row i once, turns it on chip into bit-planes (sign of J, and
+//     one plane per binary digit of |J|), and dots it with the window-start spins (bits) of every replica that
+//     proposes i inside the window: base(r, t) = sum_j J_ij s_j -- a full row sum of n terms per proposal;
+//   * chain: one wave per replica holds the W pending fields, one per (lane, block).  Every remaining update is
+//     decided at once against the fields as they stand; the first accepted one is committed (energy, spin), and
+//     the later updates' fields are corrected by -2 J[i_a][i_t] s_a (J symmetric: read from row i_a) and their spins
+//     negated where the site repeats.  Then the next accepted one, and so on.
+// J and h are integer valued with every partial sum below 2^24 (the look-ahead form's proof): the base sums and the
+// corrected fields are exactly the fp32 row sums of the one-update-at-a-time chain, the accept rule is the table
+// form's, and every decision, energy, spin and counter is bit-identical.  No field outlives its window.
+// The window plan -- which (replica, update) proposes which site -- is one counting sort per sweep.
+#include <type_traits>
+
+#include "sweep_common.h"
+
+namespace sga {
+
+// Spin and coupling bits share one layout: element j = 256 g + 4 l + q sits in bit l of 64-bit word 4 g + q (a lane
+// that loads four consecutive elements contributes one bit to each of four ballots).
+__device__ __forceinline__ void rs_bit_of(int j, int &w32, unsigned int &bit) {
+    const int g = j >> 8, e = j & 255, l = e >> 2, q = e & 3;
+    w32 = 2 * (4 * g + q) + (l >> 5);
+    bit = 1u << (l & 31);
+}
+
+// site and uniform bits of update t of sweep k of replica r: fetch_pair's stream
+__device__ __forceinline__ void rs_update(const SweepArgs &a, int r, int k, int t, int &site, uint32_t &ubits) {
+    const u32x4 w = philox4x32_10((uint32_t)(t >> 1), a.sweep0 + (uint32_t)k, a.replica0 + (uint32_t)r, DOMAIN_SWEEP,
+                                  a.seed_lo, a.seed_hi);
+    const bool second = t & 1;
+    site = (int)word_to_site(second ? w.z : w.x, (uint32_t)a.n);
+    ubits = (second ? w.w : w.y) >> 8;
+}
+
+// ---- plan: counting sort of the sweep's (replica, update) pairs by (window, site) --------------------------------
+__global__ void __launch_bounds__(256) rs_count_kernel(const SweepArgs a, RowSharedPlan p, int k) {
+    const int t = blockIdx.y * 256 + threadIdx.x, r = blockIdx.x;
+    if (t >= a.n) return;
+    int site;
+    uint32_t ub;
+    rs_update(a, r, k, t, site, ub);
+    atomicAdd(&p.cnt[(long long)(t >> p.log_w) * a.n + site], 1);
+}
+
+// one workgroup per window: exclusive scan of its n counts, entries of window w start at R w W
+__global__ void __launch_bounds__(1024) rs_scan_kernel(const SweepArgs a, RowSharedPlan p) {
+    __shared__ int sh[1024];
+    const int w = blockIdx.x, tid = threadIdx.x, n = a.n;
+    int *cnt = p.cnt + (long long)w * n, *cur = p.cur + (long long)w * n;
+    int *off = p.off + (long long)w * (n + 1);
+    int carry = a.R * (w << p.log_w);
+    for (int i0 = 0; i0 < n; i0 += 1024) {
+        const int i = i0 + tid;
+        const int v = i < n ? cnt[i] : 0;
+        sh[tid] = v;
+        __syncthreads();
+        for (int d = 1; d < 1024; d <<= 1) {  // inclusive Hillis-Steele scan
+            const int x = tid >= d ? sh[tid - d] : 0;
+            __syncthreads();
+            sh[tid] += x;
+            __syncthreads();
+        }
+        if (i < n) {
+            off[i] = carry + sh[tid] - v;
+            cur[i] = carry + sh[tid] - v;
+            cnt[i] = 0;  // zero again for the next sweep's plan
+        }
+        carry += sh[1023];
+        __syncthreads();
+    }
+    if (tid == 0) off[n] = carry;
+}
+
+__global__ void __launch_bounds__(256) rs_fill_kernel(const SweepArgs a, RowSharedPlan p, int k) {
+    const int t = blockIdx.y * 256 + threadIdx.x, r = blockIdx.x;
+    if (t >= a.n) return;
+    int site;
+    uint32_t ub;
+    rs_update(a, r, k, t, site, ub);
+    const int w = t >> p.log_w;
+    const int pos = atomicAdd(&p.cur[(long long)w * a.n + site], 1);
+    p.ent[pos] = (r << p.log_w) | (t - (w << p.log_w));
+}
+
+// int8 spins -> the bit layout above (1 = spin down); one workgroup per replica
+__global__ void __launch_bounds__(256) rs_pack_kernel(const SweepArgs a, RowSharedPlan p) {
+    const int r = blockIdx.x, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int nseg = (a.n + 255) >> 8;
+    const int8_t *src = a.spins + (long long)r * a.sstride;
+    unsigned long long *dst = reinterpret_cast<unsigned long long *>(p.bits) + (long long)r * (p.nw32 / 2);
+    for (int g = wv; g < nseg; g += 4) {
+        const int e = 256 * g + 4 * lane;
+        const unsigned int v = e < a.n ? *reinterpret_cast<const unsigned int *>(src + e) : 0u;  // (pad spins are 0)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const unsigned long long m = ballot64(((v >> (8 * q + 7)) & 1u) != 0u);
+            if (lane == 0) dst[4 * g + q] = m;
+        }
+    }
+}
+
+// ---- fields: one workgroup (4 waves) per proposed site ----------------------------------------------------------------
+// PL magnitude planes: |J| < 2^PL.  LDS: [PL + 1][4 nseg] 64-bit words (sign plane first).
+template <typename JE, int PL>
+__global__ void __launch_bounds__(256) rs_fields_kernel(const SweepArgs a, RowSharedPlan p, int win) {
+    const int i = blockIdx.x, n = a.n;
+    const int *off = p.off + (long long)win * (n + 1);
+    const int lo = off[i], hi = off[i + 1];
+    if (lo == hi) return;  // nobody proposes this site in this window: the row is not read
+    extern __shared__ unsigned long long planes[];
+    __shared__ int csum[4];
+    const int nseg = (n + 255) >> 8, nw = 4 * nseg;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const JE *row = reinterpret_cast<const JE *>(a.J) + (long long)i * a.ldj;
+    int absum = 0;
+    // four segments per wave in flight, then their ballots
+    for (int g0 = wv; g0 < nseg; g0 += 16) {
+        int v[4][4];
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            const int e = 256 * (g0 + 4 * s) + 4 * lane;  // e < n <= ldj, e % 4 == 0: the 4-element load stays in the row
+            if (g0 + 4 * s < nseg && e < n) {
+                if constexpr (std::is_same<JE, float>::value) {
+                    const float4 x = *reinterpret_cast<const float4 *>(row + e);
+                    v[s][0] = (int)x.x, v[s][1] = (int)x.y, v[s][2] = (int)x.z, v[s][3] = (int)x.w;
+                } else {
+                    const int x = *reinterpret_cast<const int *>(row + e);
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) v[s][q] = (int)(int8_t)(x >> (8 * q));
+                }
+            } else {
+#pragma unroll
+                for (int q = 0; q < 4; ++q) v[s][q] = 0;
+            }
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+                if (e + q >= n) v[s][q] = 0;
+        }
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            const int g = g0 + 4 * s;
+            if (g >= nseg) break;  // wave-uniform
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int m = v[s][q] < 0 ? -v[s][q] : v[s][q];
+                absum += m;
+                const unsigned long long sg = ballot64(v[s][q] < 0);
+                unsigned long long pb[PL];
+#pragma unroll
+                for (int b = 0; b < PL; ++b) pb[b] = ballot64(((m >> b) & 1) != 0);
+                if (lane == 0) {
+                    planes[4 * g + q] = sg;
+#pragma unroll
+                    for (int b = 0; b < PL; ++b) planes[(long long)(1 + b) * nw + 4 * g + q] = pb[b];
+                }
+            }
+        }
+    }
+    absum = wave_sum(absum);
+    if (lane == 0) csum[wv] = absum;
+    __syncthreads();
+    const int C = csum[0] + csum[1] + csum[2] + csum[3];  // sum_j |J_ij|
+    // sum_j J_ij s_j = C - 2 sum_b 2^b popcount(plane_b & (sign ^ spin bits))
+    const unsigned long long *bits = reinterpret_cast<const unsigned long long *>(p.bits);
+    const int wmask = (1 << p.log_w) - 1;
+    for (int x = lo + wv; x < hi; x += 8) {  // two entries per wave at a time (wave-uniform bounds)
+        const bool two = x + 4 < hi;
+        const int e0 = p.ent[x], e1 = two ? p.ent[x + 4] : e0;
+        const unsigned long long *s0 = bits + (long long)(e0 >> p.log_w) * nw;
+        const unsigned long long *s1 = bits + (long long)(e1 >> p.log_w) * nw;
+        int acc0 = 0, acc1 = 0;
+        for (int c = lane; c < nw; c += 64) {
+            const unsigned long long sg = planes[c];
+            const unsigned long long x0 = s0[c] ^ sg, x1 = s1[c] ^ sg;
+#pragma unroll
+            for (int b = 0; b < PL; ++b) {
+                const unsigned long long pb = planes[(long long)(1 + b) * nw + c];
+                acc0 += __popcll(pb & x0) << b;
+                acc1 += __popcll(pb & x1) << b;
+            }
+        }
+        wave_sum2(acc0, acc1);
+        if (lane == 0) {
+            p.base[(long long)(e0 >> p.log_w) * p.W + (e0 & wmask)] = C - 2 * acc0;
+            if (two) p.base[(long long)(e1 >> p.log_w) * p.W + (e1 & wmask)] = C - 2 * acc1;
+        }
+    }
+}
+
+// ---- chain: one wave per replica, W = 64 NB pending fields ---------------------------------------------------------
+// The accept-table rule of the look-ahead form, evaluated per lane: ptab[q] = expf_det((float)(-(double)(2 q) / T)).
+__device__ __forceinline__ bool rs_accept(float fk, float u, double T, int table_m) {
+    if (fk <= 0.0f) return true;
+    if (fk <= (float)table_m) return u < expf_det((float)(-(double)(2 * (int)fk) / T));
+    const double dE = (double)(2.0f * fk);
+    return (dE > T * 104.0) ? false : (u < expf_det((float)(-dE / T)));
+}
+
+template <typename JE, int NB>
+__global__ void __launch_bounds__(64) rs_chain_kernel(const SweepArgs a, RowSharedPlan p, int k, int win) {
+    const int r = blockIdx.x, lane = threadIdx.x, n = a.n;
+    constexpr int W = 64 * NB;
+    const int t0 = win * W, cnt = min(W, n - t0);
+    const double T = a.sched ? a.sched[k * a.sched_ss + r * a.sched_rs] : a.rep_temp[r];
+    int8_t *srow = a.spins + (long long)r * a.sstride;
+    const JE *J = reinterpret_cast<const JE *>(a.J);
+    const int *base = p.base + (long long)r * W;
+    int site[NB], s[NB];
+    float f[NB], hh[NB], u[NB];
+    bool valid[NB], acc[NB];
+#pragma unroll
+    for (int b = 0; b < NB; ++b) {
+        const int tw = 64 * b + lane;
+        valid[b] = tw < cnt;
+        uint32_t ub = 0;
+        site[b] = 0;
+        if (valid[b]) rs_update(a, r, k, t0 + tw, site[b], ub);
+        u[b] = (float)ub * 0x1.0p-24f;
+        f[b] = valid[b] ? (float)base[tw] : 0.0f;
+        hh[b] = a.h[site[b]];
+        s[b] = srow[site[b]];
+    }
+#pragma unroll
+    for (int b = 0; b < NB; ++b) acc[b] = valid[b] && rs_accept((float)s[b] * (f[b] + hh[b]), u[b], T, a.table_m);
+    double E = a.energy[r];
+    unsigned long long nacc = 0;
+    int from = 0;  // updates before `from` are decided
+    for (;;) {
+        // the first update at or after `from` that accepts against the fields as they stand: every one before it
+        // rejects (no accept lies between), so it is the chain's next accept
+        int first = -1;
+#pragma unroll
+        for (int b = 0; b < NB; ++b) {
+            if (first < 0 && 64 * (b + 1) > from) {
+                const unsigned long long m = ballot64(acc[b] && 64 * b + lane >= from);
+                if (m) first = 64 * b + (int)__builtin_ctzll(m);
+            }
+        }
+        if (first < 0) break;
+        const int fb = first >> 6, fl = first & 63;
+        int sa = 0, ss = 0;
+        float fa = 0.0f, ha = 0.0f;
+#pragma unroll
+        for (int b = 0; b < NB; ++b) {
+            if (b == fb) {
+                sa = read_lane(site[b], fl);
+                ss = read_lane(s[b], fl);
+                fa = read_lane(f[b], fl);
+                ha = read_lane(hh[b], fl);
+            }
+        }
+        const float fk = (float)ss * (fa + ha);
+        E += (double)(2.0f * fk);
+        ++nacc;
+        if (lane == 0) {
+            srow[sa] = (int8_t)(-ss);
+            int w32;
+            unsigned int bit;
+            rs_bit_of(sa, w32, bit);
+            atomicXor(&p.bits[(long long)r * p.nw32 + w32], bit);
+        }
+        // the later updates: field -= 2 J[sa][site] s_a (J symmetric), the spin negated where the site repeats
+        const JE *rowa = J + (long long)sa * a.ldj;
+        const float s2 = 2.0f * (float)ss;
+        float x[NB];
+#pragma unroll
+        for (int b = 0; b < NB; ++b)
+            if (b >= fb) x[b] = (float)rowa[site[b]];
+#pragma unroll
+        for (int b = 0; b < NB; ++b) {
+            if (b >= fb) {
+                f[b] -= x[b] * s2;
+                if (site[b] == sa) s[b] = -s[b];
+                acc[b] = valid[b] && rs_accept((float)s[b] * (f[b] + hh[b]), u[b], T, a.table_m);
+            }
+        }
+        from = first + 1;
+    }
+    if (lane == 0) {
+        a.energy[r] = E;
+        a.n_accepted[r] += nacc;
+        if (t0 + cnt == n && a.energy_trace) a.energy_trace[(long long)k * a.R + r] = E;
+    }
+}
+
+template <typename JE, int PL>
+static hipError_t rs_launch_fields(const SweepArgs &a, const RowSharedPlan &p, int win, hipStream_t st) {
+    const size_t lds = (size_t)(PL + 1) * 4 * ((a.n + 255) / 256) * 8;
+    auto kern = rs_fields_kernel<JE, PL>;
+    hipError_t e = ensure_lds_limit(reinterpret_cast<const void *>(kern), lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(kern, dim3(a.n), dim3(256), lds, st, a, p, win);
+    return hipGetLastError();
+}
+
+template <typename JE>
+static hipError_t rs_fields(const SweepArgs &a, const RowSharedPlan &p, int win, hipStream_t st) {
+    switch (p.planes) {
+        case 1: return rs_launch_fields<JE, 1>(a, p, win, st);
+        case 3: return rs_launch_fields<JE, 3>(a, p, win, st);
+        case 8: return rs_launch_fields<JE, 8>(a, p, win, st);
+        default: return hipErrorInvalidValue;
+    }
+}
+
+template <typename JE>
+static hipError_t rs_chain(const SweepArgs &a, const RowSharedPlan &p, int k, int win, hipStream_t st) {
+    switch (p.W) {
+        case 256: hipLaunchKernelGGL((rs_chain_kernel<JE, 4>), dim3(a.R), dim3(64), 0, st, a, p, k, win); break;
+        case 512: hipLaunchKernelGGL((rs_chain_kernel<JE, 8>), dim3(a.R), dim3(64), 0, st, a, p, k, win); break;
+        case 1024: hipLaunchKernelGGL((rs_chain_kernel<JE, 16>), dim3(a.R), dim3(64), 0, st, a, p, k, win); break;
+        default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+int row_shared_planes(int j_abs_max) {
+    return j_abs_max <= 1 ? 1 : j_abs_max <= 7 ? 3 : j_abs_max <= 255 ? 8 : 0;
+}
+
+hipError_t launch_sweep_dense_rs(const SweepArgs &a, const RowSharedPlan &p, bool j_is_i8, hipStream_t st) {
+    if (a.rep_list || a.R <= 0 || a.n <= 0 || (p.W != 256 && p.W != 512 && p.W != 1024) || (1 << p.log_w) != p.W)
+        return hipErrorInvalidValue;
+    const int nwin = (a.n + p.W - 1) / p.W;
+    const dim3 grid(a.R, (a.n + 255) / 256);
+    hipLaunchKernelGGL(rs_pack_kernel, dim3(a.R), dim3(256), 0, st, a, p);
+    hipError_t e = hipGetLastError();
+    for (int k = 0; k < a.n_sweeps && e == hipSuccess; ++k) {
+        hipLaunchKernelGGL(rs_count_kernel, grid, dim3(256), 0, st, a, p, k);
+        hipLaunchKernelGGL(rs_scan_kernel, dim3(nwin), dim3(1024), 0, st, a, p);
+        hipLaunchKernelGGL(rs_fill_kernel, grid, dim3(256), 0, st, a, p, k);
+        e = hipGetLastError();
+        for (int w = 0; w < nwin && e == hipSuccess; ++w) {
+            e = j_is_i8 ? rs_fields<int8_t>(a, p, w, st) : rs_fields<float>(a, p, w, st);
+            if (e == hipSuccess) e = j_is_i8 ? rs_chain<int8_t>(a, p, k, w, st) : rs_chain<float>(a, p, k, w, st);
+        }
+        // sweep boundary: best tracking (annealing/gpu_annealer.py:151-153), the energy is in a.energy
+        if (e == hipSuccess && !a.no_best)
+            e = launch_update_best(a.energy, a.spins, a.best_energy, a.best_spins, a.sstride, a.R, st);
+    }
+    if (e == hipSuccess)
+        note_sweep_kernel("sweep_dense_rs<%s, planes=%d, W=%d> (row-shared windows: plan, fields, chain)",
+                          j_is_i8 ? "int8_t" : "float", p.planes, p.W);
+    return e;
+}
+
+}  // namespace sga

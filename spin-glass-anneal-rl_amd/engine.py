@@ -214,15 +214,17 @@ class AnnealEngine:
         N.check(self._lib.sga_autotune(self._h, C.byref(ms)), "sga_autotune")
         return float(ms.value)
 
-    def autotune_table(self) -> dict:
-        """{candidate: kernel ms per sweep} of the last autotune() (dense: "<waves>x<chunks per wave>")."""
+    def autotune_table(self, forms: bool = False) -> dict:
+        """{candidate: kernel ms per sweep} of the last autotune() (dense: "<waves>x<chunks per wave>").  `forms=True`
+        adds the other sweep forms it timed beside the geometries ("row-shared:W<W>", option "row_shared")."""
         buf = C.create_string_buffer(4096)
         N.check(self._lib.sga_get_autotune_table(self._h, buf, 4096), "sga_get_autotune_table")
         out = {}
         for item in buf.value.decode().split(";"):
             if "=" in item:
                 k, v = item.rsplit("=", 1)
-                out[k] = float(v)
+                if forms or not k.startswith("row-shared:"):
+                    out[k] = float(v)
         return out
 
     def maybe_autotune(self, n_sweeps: int, setting: Optional[bool] = None) -> bool:
