@@ -80,7 +80,7 @@ typedef struct sga_engine sga_engine;
 int sga_create(int device, sga_engine **out);
 void sga_destroy(sga_engine *e);
 const char *sga_last_error(void);
-int sga_version(void);
+int sga_version(void);  /* 800: option "clf_fixed_point" serves dense couplings too */
 /* Run on an existing HIP stream (e.g. torch.cuda.current_stream().cuda_stream); NULL = the
  * engine's own stream (default). */
 int sga_set_stream(sga_engine *e, void *hip_stream);
@@ -390,7 +390,17 @@ int sga_set_field_cache(sga_engine *e, int mode);
  *                           sorted rows, zero diagonal, any fp32 h), dot = fp32(2^-k D_i) -- the row kernels' value --
  *                           and the same accept rule: the same chain, any single-site rule, site mode and arithmetic.
  *                           Problems the int16 form serves keep it.  Refused: f64-canonical J, ragged batches, the
- *                           implicit TSP form, fields past LDS                                          [set]
+ *                           implicit TSP form, fields past LDS.
+ *                           DENSE couplings (sga_set_dense, one model) that the integer cached-field form does not take
+ *                           -- real-valued J, or integer J beside an h that is no multiple of 1/2 --: the same D_i in
+ *                           LDS (csrc/sweep_clf_fx.hip), conditions as above (acc class f32 / f64-exact, symmetric J,
+ *                           zero diagonal, any fp32 h; k = 0 for integer J), int32 while 2^k max_i (sum_j |J_ij| +
+ *                           |h_i|) < 2^31, else int64.  fp32 rows, int8 rows (integer J, k = 0) and bit-plane storage
+ *                           (its int8 rows are read on accept) are served.  Refused, each with its reason
+ *                           (sga_describe / the error of SGA_FIELD_CACHE_ON): f64-canonical J, asymmetric J, a non-zero
+ *                           diagonal, dense batches, fields wider than int64, fields and spins of a replica past LDS
+ *                           (160 KiB: n <= ~39 000 int32, ~20 000 int64).  Problems the integer form serves keep it;
+ *                           option "clf_batched" does not apply (one accept per round)                  [set]
  *   "replica_routing"       0 | 1 (default)   SGA_FIELD_CACHE_AUTO routes each replica by its own acceptance (two
  *                           concurrent launches) instead of the whole launch by the hottest replica    [sweep; SGA_NO_REPLICA_ROUTING]
  *   "batched_energy"        0 = one pass over the couplings per replica, 1 (default) = all replicas in one pass where

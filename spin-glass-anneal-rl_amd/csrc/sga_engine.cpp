@@ -35,6 +35,8 @@ sga_route_query route_query_of(const sga_engine *e) {
     q.clf_scale = e->clf_scale;
     // option "clf_fixed_point": CSR queries carry the width of the fixed-point fields (32 | 64; 16: the int16 form)
     if (e->csr && e->opt[OPT_CLF_FIXED_POINT] == 1) q.clf_bits = e->clf_fx_bits ? e->clf_fx_bits : 16;
+    // ... dense queries whose problem the integer form does not take: 32 | 64, 0 = refused (sga_route.cpp, dense_fixed_point)
+    if (!e->csr && !e->tsp && e->opt[OPT_CLF_FIXED_POINT] == 1 && !e->clf_problem) q.clf_bits = e->clf_fx_bits;
     q.from_dense = e->from_dense ? 1 : 0;
     q.nnz = e->nnz;
     q.max_row_len = e->max_row_len;
@@ -163,7 +165,7 @@ bool clf_possible(const sga_engine *e, const char **why) {
     const sga_route_query q = route_query_of(e);
     const char *reason = sga_route::clf_refusal(q);
     // (option "clf_fixed_point": the set-time scan knows which condition failed; the query carries only the verdict)
-    if (reason && e->csr && !q.clf_ok && e->clf_fx_why && q.n_models == 1) reason = e->clf_fx_why;
+    if (reason && !q.clf_ok && e->clf_fx_why && (!e->csr || q.n_models == 1)) reason = e->clf_fx_why;
     if (why) *why = reason;
     return reason == nullptr;
 }
@@ -197,10 +199,17 @@ int ensure_fields(sga_engine *e) {
         return SGA_OK;
     }
     e->ldf = (e->ldj + 127) / 128 * 128;
-    if (!e->fields && hipMalloc(&e->fields, (size_t)e->R * (size_t)e->ldf * (size_t)(e->clf_bits / 8)) != hipSuccess) {
+    const int fbits = e->clf_fx_bits ? e->clf_fx_bits : e->clf_bits;  // (fixed point: D = 2^k J s, int32 | int64)
+    if (!e->fields && hipMalloc(&e->fields, (size_t)e->R * (size_t)e->ldf * (size_t)(fbits / 8)) != hipSuccess) {
         (void)hipGetLastError();
         e->fields = nullptr;
         return fail(SGA_ERR_MEMORY, "no memory for the resident local fields of the cached-field sweep");
+    }
+    if (e->clf_fx_bits) {  // exact per-replica sums (the matrix-core pass rounds real-valued row sums to fp32)
+        HIPCHK(sga::launch_dense_fields_seed_fx(e->J_packed, e->want_i8, e->ldj, e->spins, e->sstride, e->n, e->R, e->fields,
+                                                e->ldf, e->clf_fx_bits, e->clf_fx_k, e->stream));
+        e->fields_valid = true;
+        return SGA_OK;
     }
     int rc = fields_pass(e, 0, e->R, nullptr, e->fields);  // (any replica count: short tiles are clamped)
     if (rc != SGA_OK) return rc;
@@ -313,7 +322,7 @@ int ensure_packed(sga_engine *e) {
 extern "C" {
 
 const char *sga_last_error(void) { return g_last_error.c_str(); }
-int sga_version(void) { return 700; }  // + option "clf_fixed_point" (cached fields of real-valued CSR couplings)  // 600: + sga_set_csr_batch / sga_get_batch_model (ragged CSR batches)  // round 5: + sga_explain_route / sga_get_route_query, sga_get_last_kernel, sga_get_autotune_table, ladder-local sga_exchange
+int sga_version(void) { return 800; }  // + option "clf_fixed_point" over dense couplings (sweep_clf_fx.hip)  // 700: + option "clf_fixed_point" (cached fields of real-valued CSR couplings)  // 600: + sga_set_csr_batch / sga_get_batch_model (ragged CSR batches)  // round 5: + sga_explain_route / sga_get_route_query, sga_get_last_kernel, sga_get_autotune_table, ladder-local sga_exchange
 
 int sga_create(int device, sga_engine **out) {
     if (!out) return fail(SGA_ERR_INVALID, "out is NULL");
@@ -1039,6 +1048,38 @@ int sga_sweep(sga_engine *e, int n_sweeps, int site_mode, int arith, const doubl
         }
         if (clf_now && e->csr) {
             // (launched above)
+        } else if (clf_now && e->clf_fx_bits) {
+            // dense real-valued couplings, option "clf_fixed_point": D = 2^k J s exactly (sweep_clf_fx.hip); any single-site
+            // rule, site mode and arithmetic, traces included -- the same chain as the row kernels
+            sga::SweepArgs ac = a;
+            ac.fields = e->fields;
+            ac.ldf = e->ldf;
+            ac.field_bits = e->clf_fx_bits;
+            ac.field_scale = e->clf_fx_k;
+            ac.table_m = 0;
+            const int cw = (tail_opt && e->clf_wide)
+                               ? 8
+                               : sga::sweep_clf_waves(e->ldj, e->want_i8, mixed ? n_clf : e->R, e->cus, (int)e->opt[OPT_CLF_WAVES]);
+            if (!mixed) {
+                le = sga::launch_sweep_clf_fx(ac, e->want_i8, cw, st);
+            } else {  // two launches over disjoint replica lists, side by side (as below)
+                ac.rep_list = e->d_rep_lists;
+                ac.rep_count = n_clf;
+                a.rep_list = e->d_rep_lists + R;
+                a.rep_count = R - n_clf;
+                le = hipEventRecord(e->fork_ev, st);
+                if (le == hipSuccess) le = hipStreamWaitEvent(e->aux_stream, e->fork_ev, 0);
+                if (le == hipSuccess) le = sga::launch_sweep_clf_fx(ac, e->want_i8, cw, st);
+                char first[200];
+                std::snprintf(first, sizeof(first), "%s", sga::last_sweep_kernel());
+                if (le == hipSuccess) le = launch_dense_rows(a, e->aux_stream);
+                if (le == hipSuccess) le = hipEventRecord(e->join_ev, e->aux_stream);
+                if (le == hipSuccess) le = hipStreamWaitEvent(st, e->join_ev, 0);
+                if (le != hipSuccess) (void)hipStreamSynchronize(e->aux_stream);
+                std::snprintf(e->last_mixed, sizeof(e->last_mixed), "mixed launch: %d replica(s) on %s || %d on %s", n_clf,
+                              first, R - n_clf, sga::last_sweep_kernel());
+                sga::note_sweep_kernel("%s", e->last_mixed);
+            }
         } else if (clf_now) {
             sga::SweepArgs ac = a;
             if (e->clf_scale == 2)  // half-integer fields: dE = q for q <= 2 M, tabulated at twice the resolution

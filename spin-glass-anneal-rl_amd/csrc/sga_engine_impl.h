@@ -192,6 +192,7 @@ struct sga_engine {
     bool clf_csr_problem = false;
     // ... or, with option "clf_fixed_point", as exact fixed point: D = 2^k J s as int32 | int64 (any fp32 J whose row
     // sums are exact, h fp32 beside it): the width (0 = not this form), k, and why the form does not apply (nullptr: it does)
+    // -- for dense couplings too (sweep_clf_fx.hip: the dense problems clf_problem does not take)
     int clf_fx_bits = 0, clf_fx_k = 0;
     const char *clf_fx_why = nullptr;
     float row_j_abs_max = 0.0f;  // max_i sum_j |J_ij|

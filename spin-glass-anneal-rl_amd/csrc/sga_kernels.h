@@ -189,6 +189,14 @@ hipError_t launch_csr_fields_seed(const long long *rowptr, const int2 *cv, const
 hipError_t launch_csr_fields_seed_fx(const long long *rowptr, const int2 *cv, const int8_t *spins, int sstride, int n, int R,
                                      void *D, long long ldf, int field_bits, int k, hipStream_t st);
 hipError_t launch_scaled_fields(const float *h, int n, int scale, int *hq, hipStream_t st);
+// ... and of dense problems with real-valued J (option "clf_fixed_point", sweep_clf_fx.hip): D = 2^k J s as exact int32 |
+// int64 (a.field_bits), k = a.field_scale, no accept table; fp32 rows, or int8 rows (integer J, k = 0)
+hipError_t launch_sweep_clf_fx(const SweepArgs &a, bool j_is_i8, int waves, hipStream_t st);
+bool sweep_clf_fx_applies(const SweepArgs &a, bool j_is_i8);
+size_t sweep_clf_fx_lds_bytes(long long ldf, int field_bits, int sstride);
+// D[r][i] = 2^k sum_j J_ij s_rj as int32 | int64 (field_bits), exact; J dense [n][ldj] fp32 | int8
+hipError_t launch_dense_fields_seed_fx(const void *J, bool j_is_i8, long long ldj, const int8_t *spins, int sstride, int n,
+                                       int R, void *D, long long ldf, int field_bits, int k, hipStream_t st);
 size_t sweep_clf_lds_bytes(long long ldf, int field_bits, int sstride, int table_m);
 int sweep_clf_waves(long long ldj, bool j_is_i8, int R, int cus, int forced);
 

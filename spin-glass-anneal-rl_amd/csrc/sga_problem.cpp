@@ -515,6 +515,37 @@ int sga_set_dense_batch(sga_engine *e, const float *J, int64_t ldJ, const float 
         if (rcr != SGA_OK || taken) return rcr;
     }
     int rc = pack_dense(e, src, ld_src);
+    // Option "clf_fixed_point": the cached-field sweep for the dense problems the integer form does not take
+    // (sweep_clf_fx.hip).  In the exact accumulation classes -- fp32-exact, f64-exact -- every row sum is exact in any
+    // order; k = minus the exponent of the lowest set bit of any J (0 for integer J) makes every 2^k J an integer, so
+    // D_i = 2^k sum_j J_ij s_j is an integer of at most B = 2^k max_i sum_j |J_ij| (< 2^53 by the class's own bound),
+    // kept exactly as int32 (B < 2^31) or int64.  h is never folded in.  Bit-plane problems are served from their int8
+    // rows.  (After the packing: the diagonal it extracts tells an asymmetric J from a non-zero diagonal.)
+    if (rc == SGA_OK && e->opt[OPT_CLF_FIXED_POINT] == 1 && !e->clf_problem) {
+        const int k = std::max(hflags[5] != 0 ? hflags[6] - 1024 : 0, 0);
+        // (m bounds max_i sum_j |J_ij| from above -- it holds |h_i| too -- and is the fp32 rounding of an fp64 sum: < 1 ulp)
+        const double bound = std::ldexp((double)m, k) * (1.0 + 0x1.0p-20);
+        if (n_models != 1)
+            e->clf_fx_why = "cached local fields (fixed point): not built for dense batches (one model only)";
+        else if (e->acc_canon)
+            e->clf_fx_why = "cached local fields (fixed point): the couplings need the canonical fp64 summation order "
+                            "(acc class f64-canonical: their binary places span more than 53 bits, so no exact fixed "
+                            "point holds a row sum)";
+        else if (!e->consistent_dE) {
+            std::vector<float> dg((size_t)n);
+            HIPCHK(hipMemcpyAsync(dg.data(), e->diag, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, e->stream));
+            HIPCHK(hipStreamSynchronize(e->stream));
+            bool diag = false;
+            for (float v : dg) diag = diag || v != 0.0f;
+            e->clf_fx_why = diag ? "cached local fields (fixed point): J must have a zero diagonal"
+                                 : "cached local fields (fixed point): J must be symmetric";
+        } else if (!(bound < 0x1.0p62))
+            e->clf_fx_why = "cached local fields (fixed point): fields wider than int64";
+        else {
+            e->clf_fx_bits = bound < 0x1.0p31 ? 32 : 64;
+            e->clf_fx_k = k;
+        }
+    }
     if (rc == SGA_OK) rc = ensure_packed(e);
     // the source (the caller's buffer, or the staging copy about to be released) is done with
     HIPCHK(hipStreamSynchronize(e->stream));

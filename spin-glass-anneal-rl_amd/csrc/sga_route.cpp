@@ -308,6 +308,12 @@ TspForm tsp_form(int npad, int tune_waves) {
 }
 
 // ---- cached local fields ----------------------------------------------------------------------------------------------------
+// A dense query under option "clf_fixed_point" = 1 whose problem the integer form does not take (clf_ok = 0) carries the
+// fixed-point form in clf_bits: 32 | 64 = the width of its fields, 0 = the set-time scan refused it (acc = 2: the
+// f64-canonical class).  clf_ok = 1 keeps clf_bits = 16 | 32 of the integer form.
+bool dense_fixed_point(const Query &q) {
+    return q.kind == SGA_ROUTE_DENSE && q.opt[OPT_CLF_FIXED_POINT] == 1 && !q.clf_ok && (q.clf_bits == 32 || q.clf_bits == 64);
+}
 // The cached-local-field sweep serves: dense integer-valued symmetric problems (one model) whose fields and spin bits
 // fit LDS, and CSR problems with integer J in strictly sorted rows -- any single-site rule.
 const char *clf_refusal(const Query &q) {
@@ -349,6 +355,22 @@ const char *clf_refusal(const Query &q) {
             return "cached local fields: fields and spins of a replica do not fit LDS (or a row is longer than 2048 entries)";
         return nullptr;
     }
+    if (!q.clf_ok && dense_fixed_point(q)) {
+        // option "clf_fixed_point": D = 2^k J s as exact int32 | int64 (sweep_clf_fx.hip), no accept table
+        if (q.R_local > 0 && sga::sweep_clf_fx_lds_bytes((dense_ldj(q) + 127) / 128 * 128, q.clf_bits, q.sstride) > 160 * 1024)
+            return q.clf_bits == 64 ? "cached local fields (fixed point): int64 fields and spins of a replica do not fit "
+                                      "LDS (160 KiB: n <= ~20 000)"
+                                    : "cached local fields (fixed point): int32 fields and spins of a replica do not fit "
+                                      "LDS (160 KiB: n <= ~39 000)";
+        return nullptr;
+    }
+    if (!q.clf_ok && q.opt[OPT_CLF_FIXED_POINT] == 1 && q.clf_bits == 0) {
+        // (the set-time scan refused the fixed-point form; the engine reports its own, more precise reason)
+        if (q.n_models > 1) return "cached local fields (fixed point): not built for dense batches (one model only)";
+        if (q.acc == 2)
+            return "cached local fields (fixed point): acc class f64-canonical -- no exact fixed point holds a row sum";
+        return "cached local fields (fixed point): need symmetric J with a zero diagonal and fields within int64";
+    }
     if (!q.clf_ok)
         return "cached local fields need one model with integer-valued symmetric J, zero diagonal, h in "
                "multiples of 1/2 and row sums below 2^24";
@@ -372,6 +394,19 @@ static double fixed_point_theta(const Query &q, double t_upd) {
     const double t_acc = q.clf_bits == 64 ? 8.8 : 6.3;
     return t_upd / t_acc;
 }
+// Dense fixed point (sweep_clf_fx.hip): no accept table either, and an accept scales every entry of its row in fp64
+// before it moves the 4 | 8-byte fields.  The cost per accept, in the units of t_upd below, from
+// profiles/dense_fixed_point.json (binary-grid SK, n = 10^4, int32, 1024 replicas): on a ladder that stays hot (1000 ->
+// 20, hottest replica 92 % acceptance) the launch is that replica's chain, 42.6 ms for 9 213 accepts = 4.6 us per accept,
+// against 54.0 ms / 10^4 = 5.4 us per update on the fp32 row kernel: an accept costs 0.86 updates, t_acc = 0.86 x t_upd
+// (n = 10^4: 1.5) = 1.3 -- a replica at n = 10^4 is never given to the row kernels (theta 1.15; every measured line,
+// 0.2 % to 47 % mean acceptance, is faster cached: 1.1 - 1.3 ms against 54 ms per sweep at 1 %).  int64: not measured at
+// size; 1.5 by the field bytes an accept moves (estimate).
+constexpr double DENSE_FX_T_ACC32 = 1.3, DENSE_FX_T_ACC64 = 1.5;
+static double dense_fixed_point_theta(const Query &q, double t_upd) {
+    const double t_acc = q.clf_bits == 64 ? DENSE_FX_T_ACC64 : DENSE_FX_T_ACC32;
+    return t_upd / t_acc;
+}
 double routing_theta(const Query &q) {
     const double kn = (double)q.n / 1000.0;
     const double t_upd = q.kind == SGA_ROUTE_CSR ? 0.20 + 0.0008 * (double)q.nnz / (double)q.n  // (C4: 0.68, C2b as CSR: 0.36)
@@ -379,6 +414,7 @@ double routing_theta(const Query &q) {
                                                  : (q.storage == SGA_J_I8 ? 0.27 + 0.031 * kn : 0.30 + 0.12 * kn);
     if (q.kind == SGA_ROUTE_CSR && q.opt[OPT_CLF_FIXED_POINT] == 1 && (q.clf_bits == 32 || q.clf_bits == 64))
         return fixed_point_theta(q, t_upd);
+    if (dense_fixed_point(q)) return dense_fixed_point_theta(q, t_upd);
     return t_upd / 1.5;
 }
 // AUTO, nothing known yet: the run starts on the kernel that loses least if the guess is wrong: the cached-field
@@ -475,6 +511,10 @@ std::string explain(const Query &q0) {
         } else if (q.field_cache == SGA_FIELD_CACHE_ON) {
             if (q.kind == SGA_ROUTE_CSR && q.opt[OPT_CLF_FIXED_POINT] == 1 && (q.clf_bits == 32 || q.clf_bits == 64))
                 std::snprintf(buf, sizeof(buf), " cached=on(waves=%d fields=int%d fixed-point)", clf_csr_waves(q), q.clf_bits);
+            else if (dense_fixed_point(q))
+                std::snprintf(buf, sizeof(buf), " cached=on(waves=%d fields=int%d fixed-point)",
+                              sga::sweep_clf_waves(dense_ldj(q), is_i8(q), std::max(q.R_local, 1), q.cus, (int)q.opt[OPT_CLF_WAVES]),
+                              q.clf_bits);
             else if (q.kind == SGA_ROUTE_CSR) std::snprintf(buf, sizeof(buf), " cached=on(waves=%d)", clf_csr_waves(q));
             else
                 std::snprintf(buf, sizeof(buf), " cached=on(waves=%d fields=int%d)",

@@ -124,6 +124,7 @@ TspForm tsp_form(int npad, int tune_waves);
 // ---- cached local fields (sga_set_field_cache) ------------------------------------------------------------------------
 // nullptr when the cached-field sweep can serve q (with q.sstride / q.ldj as laid out), else the reason
 const char *clf_refusal(const Query &q);
+bool dense_fixed_point(const Query &q);     // a dense query served by the fixed-point cached-field form (clf_bits 32 | 64)
 double routing_theta(const Query &q);       // break-even acceptance of one replica between the two kernel families
 bool auto_starts_cached(const Query &q);    // SGA_FIELD_CACHE_AUTO before any acceptance is known
 int clf_csr_waves(const Query &q);          // waves per replica of the cached-field sweep over CSR couplings

@@ -418,6 +418,16 @@ int sga_describe(sga_engine *e, char *buf, int buflen) {
             std::snprintf(tmp + std::strlen(tmp), sizeof(tmp) - std::strlen(tmp),
                           " sweep=auto(cached local fields while the hottest replica accepts little; now: %s)",
                           (!e->auto_unavailable && e->n_route_clf > 0) ? "cached" : "one row per proposal");
+    } else if (clf_active(e) && e->clf_fx_bits) {  // dense couplings, option "clf_fixed_point"
+        if (e->field_cache == SGA_FIELD_CACHE_ON)
+            std::snprintf(tmp + std::strlen(tmp), sizeof(tmp) - std::strlen(tmp),
+                          " sweep=cached-local-fields(int%d fixed-point, k=%d, in LDS, %d wave(s) per replica, row read on accept only)",
+                          e->clf_fx_bits, e->clf_fx_k, sga::sweep_clf_waves(e->ldj, e->want_i8, e->R, e->cus, (int)e->opt[OPT_CLF_WAVES]));
+        else
+            std::snprintf(tmp + std::strlen(tmp), sizeof(tmp) - std::strlen(tmp),
+                          " sweep=auto(cached local fields, int%d fixed-point, k=%d, per replica by its own acceptance; now: %d of "
+                          "%d replica(s) cached, the rest one row per proposal)",
+                          e->clf_fx_bits, e->clf_fx_k, e->auto_unavailable ? 0 : e->n_route_clf, e->R);
     } else if (clf_active(e)) {
         if (e->field_cache == SGA_FIELD_CACHE_ON)
             std::snprintf(tmp + std::strlen(tmp), sizeof(tmp) - std::strlen(tmp),

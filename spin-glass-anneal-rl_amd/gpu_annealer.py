@@ -48,7 +48,7 @@ class GPUAnnealerConfig:
     #                                       only on accept where the problem allows (sga_set_field_cache) --
     #                                       the same chain bit for bit as "off" (one row read per proposal)
     fixed_point_fields: bool = False      # engine option "clf_fixed_point": the field cache also serves real-valued
-    #                                       sparse couplings (exact int32 | int64 fixed-point fields; same chain)
+    #                                       sparse and dense couplings (exact int32 | int64 fixed-point fields; same chain)
     device_index: Optional[int] = None
 
     def __post_init__(self):

@@ -117,7 +117,7 @@ class MultiGPUAnnealer:
     def _make_engine(self, gpu: int, model: IsingModel):
         eng = AnnealEngine(gpu)
         eng.set_field_cache(self.annealer_config.field_cache)
-        if self.annealer_config.fixed_point_fields:
+        if self.annealer_config.fixed_point_fields:  # (real-valued sparse and dense couplings: exact fixed-point fields)
             eng.set_option("clf_fixed_point", 1)  # (read when the couplings are set)
         model.load_into(eng, storage=self.annealer_config.coupling_storage)
         return eng

@@ -48,7 +48,7 @@ class ParallelTemperingConfig:
     # build-specific
     coupling_storage: str = "auto"
     field_cache: str = "auto"             # resident local fields where the problem allows (identical chain)
-    fixed_point_fields: bool = False      # ... real-valued sparse couplings too (option "clf_fixed_point")
+    fixed_point_fields: bool = False      # ... real-valued sparse and dense couplings too (option "clf_fixed_point")
     device_index: Optional[int] = None
     autotune: Optional[bool] = None       # measured launch geometry (None: for long runs only)
 

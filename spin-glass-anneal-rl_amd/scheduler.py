@@ -55,7 +55,7 @@ class SpinGlassScheduler:
         """field_cache: "auto" keeps every replica's local fields resident where the problem allows it
         (dense integer-valued symmetric couplings) so that a coupling row is read only when a proposal is
         accepted -- the chain, and with it the result, is the one "off" (a row per proposal) gives.
-        fixed_point_fields: the cache also serves real-valued sparse couplings, as exact fixed-point fields
+        fixed_point_fields: the cache also serves real-valued sparse and dense couplings, as exact fixed-point fields
         (engine option "clf_fixed_point"); the same chain again."""
         if n_replicas < 1 or n_sweeps < 1 or n_replicas % n_ladders:
             raise ConfigurationError("bad replica / sweep / ladder counts")
