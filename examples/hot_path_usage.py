@@ -52,6 +52,18 @@ def many_replicas():
           f"{1024 * 2048 * 300 / dt:.3g} spin-flip attempts/s")
 
 
+def many_models():
+    """Independent models through one engine; with the field cache on, each replica keeps its local fields resident and
+    reads a coupling row of ITS model on accept only (same results as field_cache="off")."""
+    from spin_glass_anneal_rl_amd import BatchConfig, BatchProcessor
+    models = [random_pm1_model(1024, seed=10 + i) for i in range(8)]
+    cfg = GPUAnnealerConfig(n_sweeps=500, random_seed=3, field_cache="on")
+    t = time.time()
+    results = BatchProcessor(cfg, BatchConfig(replicas_per_model=2)).process_models_batch(models)
+    print(f"batch of {len(models)} models, field cache on: best energies "
+          f"{[round(r.best_energy) for r in results]} in {time.time() - t:.3f} s")
+
+
 def travelling_salesman(n_cities=12):
     rs = np.random.RandomState(0)
     xy = rs.rand(n_cities, 2)
@@ -105,5 +117,6 @@ if __name__ == "__main__":
     simulated_annealing()
     parallel_tempering()
     many_replicas()
+    many_models()
     travelling_salesman()
     travelling_salesman_without_storing_couplings()

@@ -94,7 +94,12 @@ int sga_set_dense(sga_engine *e, const float *J, int64_t ldJ, const float *h, in
  * BatchProcessor workload, annealing/batch_processor.py:231-288): J is the models' matrices
  * stacked row-wise, [n_models*n][ldJ]; h is [n_models][n].  Replicas are split evenly over
  * the models (global replica g belongs to model g / (R_global / n_models)); with a ladder,
- * use n_ladders = n_models so that exchanges stay inside a model. */
+ * use n_ladders = n_models so that exchanges stay inside a model.
+ * sga_set_field_cache(ON / AUTO) serves a batch (version >= 900) whose stacked rows qualify as a whole: every
+ * model's J integer valued and symmetric with a zero diagonal, every h in multiples of 1/2, the largest
+ * sum_j |J_ij| + |h_i| of ANY model below 2^24.  Scale, field width (int16 | int32), accept table and max |J| are
+ * batch-wide; each replica reads its own model's rows, and each model walks its one-model chain.  The fixed-point
+ * form (option "clf_fixed_point"), bit-plane storage and row-shared windows stay one-model only. */
 int sga_set_dense_batch(sga_engine *e, const float *J, int64_t ldJ, const float *h, int n,
                         int n_models, int storage);
 /* CSR couplings (both triangles present), rowptr[n+1], colidx[nnz], val[nnz], h[n]; host or
@@ -343,6 +348,12 @@ int sga_set_csr_storage(sga_engine *e, int storage);
  *     multiples of 1/2, max_i(sum_j |J_ij| + |h_i|) < 2^24 (2^23 with half-integer h), n <= ~75 000 (int16
  *     fields; ~37 000 with int32); fields seeded by one pass over J on the matrix cores; any rule but
  *     SGA_RULE_WOLFF, every site mode and arithmetic;
+ *   dense batches (sga_set_dense_batch, M models of one size; version >= 900): the same conditions over ALL stacked
+ *     rows -- scale, field width and accept table are batch-wide, which keeps every model's fields exact and its
+ *     chain the one-model chain; fields seeded by one launch of exact integer sums, eight replicas per pass over
+ *     a model's rows; "several accepts per round" needs each MODEL's matrix below 4 GiB, not the stack's;
+ *     sga_explain_route / sga_describe name the batch ("models=M").  Ragged CSR batches (sga_set_csr_batch) and
+ *     the fixed-point form over batches stay refused;
  *   CSR couplings (sga_set_csr, or a sparse matrix sga_set_dense kept as CSR): J integer valued and symmetric
  *     in strictly sorted rows (no duplicate entries), zero diagonal, h in multiples of 1/2,
  *     max_i sum_j |J_ij| < 2^15 (only the dynamic part J s of a field is kept, as int16; h is read beside it),

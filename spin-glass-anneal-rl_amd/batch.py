@@ -11,6 +11,13 @@ more than one replica per model each model is its own temperature ladder.  Model
 ONE engine kept as CSR (`sga_set_csr_batch`: one launch per sweep call, each replica on its own model's rows);
 a chunk the ragged engine refuses (non-zero diagonal, asymmetric J) takes the stacked path.  Simulated
 annealing semantics per replica are those of GPUAnnealer (schedule, best at sweep ends).
+
+`GPUAnnealerConfig.field_cache` is handed to the engine before the couplings are set, as GPUAnnealer does.  A stacked
+dense batch whose models all qualify (integer symmetric J, zero diagonal, h in multiples of 1/2) then keeps every
+replica's local fields resident and reads a coupling row on accept only -- the same chain, so every result field
+but `total_time` is the same for "on", "auto" and "off".  On the ragged (sparse) path "auto" and "off" stream; "on"
+is refused by the ragged engine (SGA_ERR_UNSUPPORTED), which sends the chunk to the stacked path like any other
+refusal.
 """
 import time
 from dataclasses import dataclass
@@ -155,6 +162,7 @@ class BatchProcessor:
         temps = np.maximum(np.asarray([schedule.update(s) for s in range(cfg.n_sweeps)]), 1e-10)
         hist_e = [[] for _ in range(M)]
         with AnnealEngine(self.device_index) as eng:
+            eng.set_field_cache(cfg.field_cache)  # (before the couplings, as GPUAnnealer.anneal)
             set_problem(eng)
             eng.init_replicas(M * k, seed=fresh_seed(cfg.random_seed), s0=s0)
             e0 = eng.energies().reshape(M, k).min(1)

@@ -166,6 +166,8 @@ bool clf_possible(const sga_engine *e, const char **why) {
     const char *reason = sga_route::clf_refusal(q);
     // (option "clf_fixed_point": the set-time scan knows which condition failed; the query carries only the verdict)
     if (reason && !q.clf_ok && e->clf_fx_why && (!e->csr || q.n_models == 1)) reason = e->clf_fx_why;
+    // (the integer form over dense couplings, likewise)
+    if (reason && !q.clf_ok && !e->csr && !e->tsp && e->clf_why && e->opt[OPT_CLF_FIXED_POINT] != 1) reason = e->clf_why;
     if (why) *why = reason;
     return reason == nullptr;
 }
@@ -208,6 +210,13 @@ int ensure_fields(sga_engine *e) {
     if (e->clf_fx_bits) {  // exact per-replica sums (the matrix-core pass rounds real-valued row sums to fp32)
         HIPCHK(sga::launch_dense_fields_seed_fx(e->J_packed, e->want_i8, e->ldj, e->spins, e->sstride, e->n, e->R, e->fields,
                                                 e->ldf, e->clf_fx_bits, e->clf_fx_k, e->stream));
+        e->fields_valid = true;
+        return SGA_OK;
+    }
+    if (e->n_models > 1) {  // many-model batches: exact integer sums per model, one launch (sweep_clf.hip)
+        HIPCHK(sga::launch_dense_fields_seed_batch(e->J_packed, e->want_i8, e->ldj, (long long)e->n * e->ldj, e->h, e->spins,
+                                                   e->sstride, e->n, e->R, (uint32_t)e->replica0, e->Rg / e->n_models,
+                                                   e->fields, e->ldf, e->clf_bits, e->clf_scale, e->stream));
         e->fields_valid = true;
         return SGA_OK;
     }
@@ -322,7 +331,7 @@ int ensure_packed(sga_engine *e) {
 extern "C" {
 
 const char *sga_last_error(void) { return g_last_error.c_str(); }
-int sga_version(void) { return 800; }  // + option "clf_fixed_point" over dense couplings (sweep_clf_fx.hip)  // 700: + option "clf_fixed_point" (cached fields of real-valued CSR couplings)  // 600: + sga_set_csr_batch / sga_get_batch_model (ragged CSR batches)  // round 5: + sga_explain_route / sga_get_route_query, sga_get_last_kernel, sga_get_autotune_table, ladder-local sga_exchange
+int sga_version(void) { return 900; }  // + cached local fields for many-model dense batches (sga_set_dense_batch)  // 800: + option "clf_fixed_point" over dense couplings (sweep_clf_fx.hip)  // 700: + option "clf_fixed_point" (cached fields of real-valued CSR couplings)  // 600: + sga_set_csr_batch / sga_get_batch_model (ragged CSR batches)  // round 5: + sga_explain_route / sga_get_route_query, sga_get_last_kernel, sga_get_autotune_table, ladder-local sga_exchange
 
 int sga_create(int device, sga_engine **out) {
     if (!out) return fail(SGA_ERR_INVALID, "out is NULL");

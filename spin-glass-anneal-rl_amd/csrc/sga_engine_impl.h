@@ -184,7 +184,7 @@ struct sga_engine {
     // cached-local-field sweep (sweep_clf_impl.h)
     int field_cache = SGA_FIELD_CACHE_OFF;  // what the caller asked for
     bool from_dense = false;  // CSR problem built from a sparse matrix handed over dense (sga_set_dense, SGA_J_AUTO)
-    bool clf_problem = false;  // dense, one model, J and h integer valued, symmetric, zero diagonal, sums < 2^24
+    bool clf_problem = false;  // dense (one model or a batch, over all stacked rows), J integer valued, h in multiples of 1/2, symmetric, zero diagonal, sums < 2^24
     float row_abs_max = 0.0f;  // max_i(sum_j |J_ij| + |h_i|)
     int j_abs_max = 0;         // ceil(max |J_ij|): the most one flip moves another site's field (several accepts per round: sweep_clfb_impl.h)
     // ... of CSR problems (sweep_clf_csr.hip): integer J, rows strictly sorted, max_i sum_j |J_ij| < 2^15, the accept
@@ -195,6 +195,7 @@ struct sga_engine {
     // -- for dense couplings too (sweep_clf_fx.hip: the dense problems clf_problem does not take)
     int clf_fx_bits = 0, clf_fx_k = 0;
     const char *clf_fx_why = nullptr;
+    const char *clf_why = nullptr;  // dense problems the integer form does not take: which condition failed (set-time scan)
     float row_j_abs_max = 0.0f;  // max_i sum_j |J_ij|
     float csr_row_abs_max = 0.0f;  // CSR: max_i (sum_j |J_ij| + |h_i|): no |fk| of a move exceeds it
     int *hq = nullptr;           // [n] table_scale * h_i as integers (built with the first cached sweep)
@@ -300,6 +301,7 @@ struct sga_engine {
         dev_free(epart);
         epart_bytes = 0;
         clf_problem = false;
+        clf_why = nullptr;
         d_models = nullptr;  // (part of h)
         ragged_at = 0;
         ragged = false;

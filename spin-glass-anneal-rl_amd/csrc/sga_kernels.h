@@ -197,6 +197,12 @@ size_t sweep_clf_fx_lds_bytes(long long ldf, int field_bits, int sstride);
 // D[r][i] = 2^k sum_j J_ij s_rj as int32 | int64 (field_bits), exact; J dense [n][ldj] fp32 | int8
 hipError_t launch_dense_fields_seed_fx(const void *J, bool j_is_i8, long long ldj, const int8_t *spins, int sstride, int n,
                                        int R, void *D, long long ldf, int field_bits, int k, hipStream_t st);
+// F[r][i] = scale (J_m s_r + h_m)[i] as int16 | int32 (field_bits) for the local replicas of a many-model batch, m =
+// (replica0 + r) / reps_per_model: exact integer sums, one launch whatever the number of models (sweep_clf.hip)
+hipError_t launch_dense_fields_seed_batch(const void *J, bool j_is_i8, long long ldj, long long model_stride_j, const float *h,
+                                          const int8_t *spins, int sstride, int n, int R, unsigned int replica0,
+                                          int reps_per_model, void *F, long long ldf, int field_bits, int scale,
+                                          hipStream_t st);
 size_t sweep_clf_lds_bytes(long long ldf, int field_bits, int sstride, int table_m);
 int sweep_clf_waves(long long ldj, bool j_is_i8, int R, int cus, int forced);
 

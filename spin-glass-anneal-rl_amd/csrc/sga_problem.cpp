@@ -493,8 +493,10 @@ int sga_set_dense_batch(sga_engine *e, const float *J, int64_t ldJ, const float 
     }
     // integer problem: tabulate exp(float32(-2k/T)) for the moves k <= min(M, 2048) per sweep
     if (nonint == 0u && m >= 1.0f && m < 16777216.0f) e->table_m = (int)std::min(m, 2048.0f);
-    // cached-local-field sweep: exact integer fields, dE of the rule == energy change, one model
-    // (h a multiple of 1/2 -- the penalty encodings of 0/1 variables -- keeps 2 F an integer: scale 2)
+    // cached-local-field sweep: exact integer fields, dE of the rule == energy change
+    // (h a multiple of 1/2 -- the penalty encodings of 0/1 variables -- keeps 2 F an integer: scale 2).  A many-model
+    // batch qualifies as a whole: the scans above run over all stacked rows, so scale, field width, accept table and
+    // max |J| are batch-wide -- a field kept at scale 2 or as int32 because ANOTHER model needs it is still exact
     e->row_abs_max = m;
     {
         float jm;
@@ -502,7 +504,7 @@ int sga_set_dense_batch(sga_engine *e, const float *J, int64_t ldJ, const float 
         e->j_abs_max = (int)std::min(std::ceil((double)jm), 16777216.0);
     }
     e->clf_scale = (nonint & 2u) ? 2 : 1;
-    e->clf_problem = (nonint & 5u) == 0u && (double)m * e->clf_scale < 16777216.0 && e->consistent_dE && n_models == 1;
+    e->clf_problem = (nonint & 5u) == 0u && (double)m * e->clf_scale < 16777216.0 && e->consistent_dE;
     e->clf_bits = (double)m * e->clf_scale < 32768.0 ? 16 : 32;
     // Sparse matrix?  (route_sparse_dense above.)  Taken when the caller asked for one row read per proposal
     // (field cache OFF), or left the choice (AUTO) on a problem the cached-field sweep cannot serve: where that
@@ -545,6 +547,24 @@ int sga_set_dense_batch(sga_engine *e, const float *J, int64_t ldJ, const float 
             e->clf_fx_bits = bound < 0x1.0p31 ? 32 : 64;
             e->clf_fx_k = k;
         }
+    }
+    // which condition of the integer cached-field form failed (the route query carries only the verdict); a batch is
+    // scanned as a whole, so the reason names what SOME model does
+    if (rc == SGA_OK && !e->clf_problem) {
+        if (nonint & 1u)
+            e->clf_why = "cached local fields: J must be integer valued (a dense batch: in every model)";
+        else if (nonint & 4u)
+            e->clf_why = "cached local fields: h must be in multiples of 1/2 (a dense batch: in every model)";
+        else if (!e->consistent_dE) {
+            std::vector<float> dg((size_t)rows);
+            HIPCHK(hipMemcpyAsync(dg.data(), e->diag, sizeof(float) * (size_t)rows, hipMemcpyDeviceToHost, e->stream));
+            HIPCHK(hipStreamSynchronize(e->stream));
+            bool diag = false;
+            for (float v : dg) diag = diag || v != 0.0f;
+            e->clf_why = diag ? "cached local fields: J must have a zero diagonal (a dense batch: in every model)"
+                              : "cached local fields: J must be symmetric (a dense batch: in every model)";
+        } else
+            e->clf_why = "cached local fields: max_i (sum_j |J_ij| + |h_i|) must stay below 2^24 (2^23 with half-integer h)";
     }
     if (rc == SGA_OK) rc = ensure_packed(e);
     // the source (the caller's buffer, or the staging copy about to be released) is done with

@@ -314,8 +314,8 @@ TspForm tsp_form(int npad, int tune_waves) {
 bool dense_fixed_point(const Query &q) {
     return q.kind == SGA_ROUTE_DENSE && q.opt[OPT_CLF_FIXED_POINT] == 1 && !q.clf_ok && (q.clf_bits == 32 || q.clf_bits == 64);
 }
-// The cached-local-field sweep serves: dense integer-valued symmetric problems (one model) whose fields and spin bits
-// fit LDS, and CSR problems with integer J in strictly sorted rows -- any single-site rule.
+// The cached-local-field sweep serves: dense integer-valued symmetric problems (one model, or a many-model batch that
+// qualifies over all its stacked rows) whose fields and spin bits fit LDS, and CSR problems with integer J in strictly sorted rows -- any single-site rule.
 const char *clf_refusal(const Query &q) {
     if (q.kind == SGA_ROUTE_TSP) return "cached local fields: stored couplings only";
     if (q.kind == SGA_ROUTE_CSR && q.n_models > 1)
@@ -372,8 +372,8 @@ const char *clf_refusal(const Query &q) {
         return "cached local fields (fixed point): need symmetric J with a zero diagonal and fields within int64";
     }
     if (!q.clf_ok)
-        return "cached local fields need one model with integer-valued symmetric J, zero diagonal, h in "
-               "multiples of 1/2 and row sums below 2^24";
+        return "cached local fields need integer-valued symmetric J with a zero diagonal, h in multiples of 1/2 and row "
+               "sums below 2^24 (a dense batch: in every model)";
     if (q.R_local > 0 && sga::sweep_clf_lds_bytes((dense_ldj(q) + 127) / 128 * 128, q.clf_bits, q.sstride,
                                                   q.clf_scale == 2 ? 2048 : q.table_m) > 160 * 1024)
         return "cached local fields: fields and spins of a replica do not fit LDS";
@@ -422,7 +422,16 @@ double routing_theta(const Query &q) {
 // fp32 rows at n = 10^4: the first four sweeps of the bench ladder 55 / 218 ms on the row kernels against 8 / 30 ms
 // cached, and 36 against 56 / 208 ms on a ladder that stays hot), the row-per-proposal kernel otherwise (bit-planes,
 // small n, CSR).
-bool auto_starts_cached(const Query &q) { return q.kind != SGA_ROUTE_CSR && 0.8 * routing_theta(q) >= 0.3; }
+// Many-model dense batches start cached from n = 1024 on: a batch has few replicas per model, the chip is mostly empty
+// and the run is paced by each replica's serial chain, where the cached kernel is ahead from the first sweep -- sweeps
+// 0..10 of the default SA schedule from random spins, 32 models x 1 replica, int8 rows: 0.128 against 0.288 ms per
+// sweep at n = 1024 (11 % acceptance), 0.39 / 1.32 at 4096, 0.93 / 4.94 at 10^4; behind at n = 256 (0.246 / 0.209, 19 %)
+// and n = 128 (0.076 / 0.058, 27 %) -- profiles/batch_cached_fields.json.  The thresholds after the start are the
+// one-model ones.
+bool auto_starts_cached(const Query &q) {
+    if (q.kind == SGA_ROUTE_DENSE && q.n_models > 1) return q.n >= 1024 || 0.8 * routing_theta(q) >= 0.3;
+    return q.kind != SGA_ROUTE_CSR && 0.8 * routing_theta(q) >= 0.3;
+}
 
 int clf_csr_waves(const Query &q) {
     const long long row_max = std::min<long long>(q.slotted ? (q.max_row_len + 63) / 64 * 64 : q.max_row_len, 1 << 20);
@@ -516,14 +525,22 @@ std::string explain(const Query &q0) {
                               sga::sweep_clf_waves(dense_ldj(q), is_i8(q), std::max(q.R_local, 1), q.cus, (int)q.opt[OPT_CLF_WAVES]),
                               q.clf_bits);
             else if (q.kind == SGA_ROUTE_CSR) std::snprintf(buf, sizeof(buf), " cached=on(waves=%d)", clf_csr_waves(q));
+            else if (q.n_models > 1)  // a many-model dense batch: batch-wide field width, each replica on its model's rows
+                std::snprintf(buf, sizeof(buf), " cached=on(waves=%d fields=int%d models=%d)",
+                              sga::sweep_clf_waves(dense_ldj(q), is_i8(q), std::max(q.R_local, 1), q.cus, (int)q.opt[OPT_CLF_WAVES]),
+                              q.clf_bits, q.n_models);
             else
                 std::snprintf(buf, sizeof(buf), " cached=on(waves=%d fields=int%d)",
                               sga::sweep_clf_waves(dense_ldj(q), is_i8(q), std::max(q.R_local, 1), q.cus, (int)q.opt[OPT_CLF_WAVES]),
                               q.clf_bits);
             out += buf;
         } else {
-            std::snprintf(buf, sizeof(buf), " cached=auto(start=%s theta=%.3f)", auto_starts_cached(q) ? "cached" : "rows",
-                          routing_theta(q));
+            if (q.kind == SGA_ROUTE_DENSE && q.n_models > 1)
+                std::snprintf(buf, sizeof(buf), " cached=auto(start=%s theta=%.3f models=%d)", auto_starts_cached(q) ? "cached" : "rows",
+                              routing_theta(q), q.n_models);
+            else
+                std::snprintf(buf, sizeof(buf), " cached=auto(start=%s theta=%.3f)", auto_starts_cached(q) ? "cached" : "rows",
+                              routing_theta(q));
             out += buf;
         }
     }

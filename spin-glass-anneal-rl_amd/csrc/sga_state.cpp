@@ -440,6 +440,9 @@ int sga_describe(sga_engine *e, char *buf, int buflen) {
                           "replica(s) cached%s, the rest one row per proposal)",
                           e->clf_bits, e->auto_unavailable ? 0 : e->n_route_clf, e->R,
                           (!e->auto_unavailable && e->clf_wide) ? " at 8 waves each" : "");
+        if (e->n_models > 1)  // many-model batches: which form ran is visible (batch-wide scale and field width)
+            std::snprintf(tmp + std::strlen(tmp), sizeof(tmp) - std::strlen(tmp), " cached-batch(models=%d scale=%d)", e->n_models,
+                          e->clf_scale);
     }
     std::snprintf(buf, (size_t)buflen, "%s", tmp);
     return SGA_OK;

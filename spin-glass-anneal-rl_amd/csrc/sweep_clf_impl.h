@@ -255,7 +255,11 @@ __global__ void __launch_bounds__(64 * CLF_MAX_WAVES) sweep_clf_kernel(const Swe
     }
     __syncthreads();
 
-    const JT *Jbase = reinterpret_cast<const JT *>(a.J);
+    // many-model batches (sga_set_dense_batch): the replica's model, resolved once and wave-uniform -- every row base
+    // below stays a scalar; offsets inside a row and a model are those of the one-model launch (0: one model)
+    const int model = a.reps_per_model > 0
+                          ? __builtin_amdgcn_readfirstlane((int)((a.replica0 + (uint32_t)r) / (uint32_t)a.reps_per_model)) : 0;
+    const JT *Jbase = reinterpret_cast<const JT *>(a.J) + (long long)model * a.model_stride_j;
     const int n_chunks = (int)((a.ldj + EPC - 1) / EPC);
     double E = a.energy[r], bestE = a.best_energy[r];
     unsigned long long nacc = 0;

@@ -32,7 +32,7 @@
 // one-at-a-time sum has (exact in fp64 in any order).
 //
 // Production arguments only (Philox sites, Metropolis through the accept table, no per-update records), matrices
-// below 4 GiB (32-bit row offsets): the other cases keep sweep_clf_kernel.  Byte model as there: B = acceptance rate
+// below 4 GiB (32-bit row offsets; in a many-model batch: each model's block): the other cases keep sweep_clf_kernel.  Byte model as there: B = acceptance rate
 // x n x sizeof(J element) per attempt.
 #pragma once
 #include "sweep_clf_impl.h"
@@ -100,8 +100,12 @@ sweep_clfb_kernel(const SweepArgs a) {
     }
     __syncthreads();
 
-    const unsigned char *Jbytes = reinterpret_cast<const unsigned char *>(a.J);
-    const JT *Jbase = reinterpret_cast<const JT *>(a.J);
+    // many-model batches: the replica's model, wave-uniform (sweep_clf_impl.h); the 32-bit row offsets of the check are
+    // relative to the model's block, so "below 4 GiB" is asked of one model, not of the stack
+    const int model = a.reps_per_model > 0
+                          ? __builtin_amdgcn_readfirstlane((int)((a.replica0 + (uint32_t)r) / (uint32_t)a.reps_per_model)) : 0;
+    const JT *Jbase = reinterpret_cast<const JT *>(a.J) + (long long)model * a.model_stride_j;
+    const unsigned char *Jbytes = reinterpret_cast<const unsigned char *>(Jbase);
     const int n_chunks = (int)((a.ldj + EPC - 1) / EPC);
     double E = a.energy[r], bestE = a.best_energy[r];
     unsigned long long nacc = 0;
