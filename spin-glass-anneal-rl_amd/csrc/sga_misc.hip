@@ -623,16 +623,33 @@ __global__ void __launch_bounds__(256) energy_dense_kernel(const EnergyArgs a) {
         double e_acc = 0.0, h_acc = 0.0;
         for (int i = b * a.block_rows + w; i < row1; i += 4) {
             const JT *row = J + (long long)i * a.ldj;
-            double acc = 0.0;
-            for (long long c = lane * EPL; c < a.ldj; c += EPC) {
-                if constexpr (sizeof(JT) == 4) {
-                    const float4 x = *reinterpret_cast<const float4 *>(row + c);
-                    const int sw = *reinterpret_cast<const int *>(s + c);
-                    acc += (double)(x.x * (float)(int8_t)(sw));
-                    acc += (double)(x.y * (float)(int8_t)(sw >> 8));
-                    acc += (double)(x.z * (float)(int8_t)(sw >> 16));
-                    acc += (double)(x.w * (float)(sw >> 24));
-                } else {
+            float mv_i;  // torch.mv row, fp32
+            if constexpr (sizeof(JT) == 4) {
+                // canonical order of sweep_dense_impl.h: 1024-element super-chunks; lane l adds its 16
+                // products (chunk q = 0..3, elements 4l .. 4l+3 of each) from +0, one adjacent-pairs tree per
+                // super-chunk, the super-chunk sums added in order.  (Exactly summable J: the same bits in any order.)
+                double t = 0.0;
+                for (long long c0 = 0; c0 < a.ldj; c0 += 4 * EPC) {
+                    double p = 0.0;
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        const long long c = c0 + q * EPC + lane * EPL;
+                        if (c < a.ldj) {
+                            const float4 x = *reinterpret_cast<const float4 *>(row + c);
+                            const int sw = *reinterpret_cast<const int *>(s + c);
+                            p += (double)(x.x * (float)(int8_t)(sw));
+                            p += (double)(x.y * (float)(int8_t)(sw >> 8));
+                            p += (double)(x.z * (float)(int8_t)(sw >> 16));
+                            p += (double)(x.w * (float)(sw >> 24));
+                        }
+                    }
+                    const double cs = wave_sum(p);
+                    t = c0 == 0 ? cs : t + cs;
+                }
+                mv_i = (float)t;
+            } else {
+                double acc = 0.0;
+                for (long long c = lane * EPL; c < a.ldj; c += EPC) {
                     const int4 x = *reinterpret_cast<const int4 *>(row + c);
                     const int4 sv = *reinterpret_cast<const int4 *>(s + c);
                     int t = __builtin_amdgcn_sdot4(x.x, sv.x, 0, false);
@@ -641,8 +658,8 @@ __global__ void __launch_bounds__(256) energy_dense_kernel(const EnergyArgs a) {
                     t = __builtin_amdgcn_sdot4(x.w, sv.w, t, false);
                     acc += (double)t;
                 }
+                mv_i = (float)wave_sum(acc);
             }
-            const float mv_i = (float)wave_sum(acc);  // torch.mv row, fp32
             const double si = (double)s[i];
             e_acc += (double)mv_i * si;
             h_acc += (double)hvec[i] * si;
@@ -669,6 +686,42 @@ hipError_t launch_energy_dense(const EnergyArgs &a, bool j_is_i8, hipStream_t st
     return hipGetLastError();
 }
 
+// fp32 sum of one CSR row [beg, end) formed by ONE wave in the canonical order of sweep_csr.hip: entry e
+// belongs to lane e % 64 of virtual wave (e / 64) % 8, a lane adds its entries in storage order, each virtual wave is
+// folded by the adjacent-pairs tree and the wave sums are added in order.  Eight loads in flight per lane, one
+// accumulator per virtual wave; a slot past the row's end adds a zero product.  spin(c) is the spin of column c.
+template <typename SpinF>
+__device__ __forceinline__ float csr_row_sum_canonical(const int2 *cv, long long beg, long long end, int lane, SpinF spin) {
+    const long long len = end - beg;
+    if (len <= 64) {  // one virtual wave, one entry per lane
+        double acc = 0.0;
+        if (lane < len) {
+            const int2 ent = cv[beg + lane];
+            acc = (double)(__int_as_float(ent.y) * spin(ent.x));
+        }
+        return (float)wave_sum(acc);
+    }
+    double av[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (long long e0 = lane; e0 < len; e0 += 512) {
+        int c[8];
+        float v[8];
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+            const bool in = e0 + 64 * q < len;
+            const int2 ent = in ? cv[beg + e0 + 64 * q] : make_int2(0, 0);
+            c[q] = ent.x;
+            v[q] = __int_as_float(ent.y);
+        }
+#pragma unroll
+        for (int q = 0; q < 8; ++q) av[q] += (double)(v[q] * spin(c[q]));
+    }
+    double tot = wave_sum(av[0]);
+#pragma unroll
+    for (int q = 1; q < 8; ++q)
+        if (64 * q < len) tot += wave_sum(av[q]);  // (uniform: the row's length)
+    return (float)tot;
+}
+
 // LDS_SPINS = false: spins gathered from HBM / L2 (problems beyond the int8 LDS capacity)
 template <bool LDS_SPINS>
 __global__ void __launch_bounds__(256) energy_csr_kernel(const EnergyArgs a) {
@@ -691,13 +744,8 @@ __global__ void __launch_bounds__(256) energy_csr_kernel(const EnergyArgs a) {
         const int row1 = min(a.n, (b + 1) * a.block_rows);
         double e_acc = 0.0, h_acc = 0.0;
         for (int i = b * a.block_rows + w; i < row1; i += 4) {
-            double acc = 0.0;
-            for (long long j = a.rowptr[i] + lane; j < a.rowptr[i + 1]; j += 64)
-            {
-                const int2 ent = a.cv[j];
-                acc += (double)(__int_as_float(ent.y) * (float)s[ent.x]);
-            }
-            const float mv_i = (float)wave_sum(acc);
+            const float mv_i = csr_row_sum_canonical(a.cv, a.rowptr[i], a.rowptr[i + 1], lane,
+                                                     [&](int c) -> float { return (float)s[c]; });
             const double si = (double)s[i];
             e_acc += (double)mv_i * si;
             h_acc += (double)a.h[i] * si;
@@ -711,7 +759,7 @@ __global__ void __launch_bounds__(256) energy_csr_kernel(const EnergyArgs a) {
 // kernel's BIG form), 16 waves per replica, one row per wave with eight (colidx, val) loads in
 // flight per lane.  At the 1000-city TSP instance (4e9 entries, 256 replicas) the HBM-spin
 // form above took 10.7 s for the initial energies.
-constexpr int ENERGY_BIG_WAVES = 16, ENERGY_BIG_UNROLL = 8;
+constexpr int ENERGY_BIG_WAVES = 16;
 __global__ void __launch_bounds__(64 * ENERGY_BIG_WAVES) energy_csr_bits_kernel(const EnergyArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned int *bits = reinterpret_cast<unsigned int *>(smem);
@@ -732,23 +780,7 @@ __global__ void __launch_bounds__(64 * ENERGY_BIG_WAVES) energy_csr_bits_kernel(
         const int row1 = b < b1 ? min(a.n, (b + 1) * a.block_rows) : 0;
         double e_acc = 0.0, h_acc = 0.0;
         for (int i = b * a.block_rows + (w & 3); i < row1; i += 4) {
-            const long long beg = a.rowptr[i], end = a.rowptr[i + 1];
-            double acc = 0.0;
-            for (long long j0 = beg + lane; j0 < end; j0 += 64 * ENERGY_BIG_UNROLL) {
-                int c[ENERGY_BIG_UNROLL];
-                float v[ENERGY_BIG_UNROLL];
-#pragma unroll
-                for (int q = 0; q < ENERGY_BIG_UNROLL; ++q) {
-                    const long long j = j0 + 64 * q;
-                    const bool in = j < end;
-                    const int2 ent = in ? a.cv[j] : make_int2(0, 0);
-                    c[q] = ent.x;
-                    v[q] = __int_as_float(ent.y);
-                }
-#pragma unroll
-                for (int q = 0; q < ENERGY_BIG_UNROLL; ++q) acc += (double)(v[q] * spin_f(c[q]));
-            }
-            const float mv_i = (float)wave_sum(acc);
+            const float mv_i = csr_row_sum_canonical(a.cv, a.rowptr[i], a.rowptr[i + 1], lane, spin_f);
             const double si = (double)spin_f(i);
             e_acc += (double)mv_i * si;
             h_acc += (double)a.h[i] * si;
@@ -1206,12 +1238,8 @@ __global__ void __launch_bounds__(256) energy_csr_ragged_kernel(const EnergyArgs
     __syncthreads();
     double e_acc = 0.0, h_acc = 0.0;
     for (int i = w; i < model.y; i += 4) {
-        double acc = 0.0;
-        for (long long j = rowptr[i] + lane; j < rowptr[i + 1]; j += 64) {
-            const int2 ent = a.cv[j];
-            acc += (double)(__int_as_float(ent.y) * (float)s[ent.x]);
-        }
-        const float mv_i = (float)wave_sum(acc);
+        const float mv_i = csr_row_sum_canonical(a.cv, rowptr[i], rowptr[i + 1], lane,
+                                                 [&](int c) -> float { return (float)s[c]; });
         const double si = (double)s[i];
         e_acc += (double)mv_i * si;
         h_acc += (double)h[i] * si;
