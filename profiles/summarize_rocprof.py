@@ -39,6 +39,10 @@ def main():
     ap.add_argument("--write")
     ap.add_argument("--extra", action="append", default=[],
                     help="further --pmc output dirs; every counter is averaged per launch")
+    ap.add_argument("--sweep-sum", default="",
+                    help="key of a first entry that sums, per sweep, every counter over the kernels named by --sweep-parts")
+    ap.add_argument("--sweep-parts", default="sga::rs_plan_kernel,sga::rs_scan,sga::rs_pack,sga::rs_fields,sga::rs_chain,sga::update_best")
+    ap.add_argument("--sweeps", type=float, default=25.0, help="sweeps of the profiled run (warm-up + timed)")
     ap.add_argument("--tag", required=True)
     ap.add_argument("--note", default="")
     a = ap.parse_args()
@@ -50,6 +54,14 @@ def main():
             csv.writer(f).writerows(keep)
         print(f"wrote {a.tag}_kernel_stats.csv ({len(keep) - 1} engine kernels)")
     pmc = {"note": a.note, "unit": "bytes per launch (average over launches)", "kernels": {}}
+    parts = [x for x in a.sweep_parts.split(",") if x]
+    total, part_names, part_launches = collections.defaultdict(float), set(), collections.defaultdict(int)
+
+    def tally(kernel, key, values, scale=1.0):  # the run's total of one counter over a kernel's launches
+        if a.sweep_sum and any(x in kernel for x in parts):
+            total[key] += sum(values) * scale
+            part_names.add(kernel.split("(")[0].replace("void ", ""))
+            part_launches[kernel] = max(part_launches[kernel], len(values))
     for label, d, scale in (("FETCH_SIZE", a.fetch, 2.0), ("WRITE_SIZE", a.write, 1.0)):
         if not d:
             continue
@@ -64,6 +76,7 @@ def main():
             e[label + "_raw_KiB"] = raw
             e[label.split("_")[0].lower() + "_bytes"] = raw * 1024.0 * scale
             e["launches_" + label] = len(v)
+            tally(k, label.split("_")[0].lower() + "_bytes", v, 1024.0 * scale)
     for d in a.extra:
         src = one(os.path.join(d, "**", "*_counter_collection.csv"))
         agg = collections.defaultdict(list)
@@ -72,6 +85,7 @@ def main():
                 agg[(short(r["Kernel_Name"]), r["Counter_Name"])].append(float(r["Counter_Value"]))
         for (k, c), v in agg.items():
             pmc["kernels"].setdefault(k, {})[c] = sum(v) / len(v)
+            tally(k, c, v)
     for e in pmc["kernels"].values():
         if "TCC_HIT_sum" in e and "TCC_MISS_sum" in e and e["TCC_HIT_sum"] + e["TCC_MISS_sum"] > 0:
             e["l2_hit_rate"] = e["TCC_HIT_sum"] / (e["TCC_HIT_sum"] + e["TCC_MISS_sum"])
@@ -80,6 +94,13 @@ def main():
                               "write_bytes = WRITE_SIZE x 1024")
         for e in pmc["kernels"].values():
             e["hbm_bytes"] = e.get("fetch_bytes", 0.0) + e.get("write_bytes", 0.0)
+    if a.sweep_sum and total:  # first entry: what one sweep of the form costs, its kernels summed
+        e = {k: v / a.sweeps for k, v in total.items()}
+        e["hbm_bytes"] = e.get("fetch_bytes", 0.0) + e.get("write_bytes", 0.0)
+        e["launches_per_sweep"] = sum(part_launches.values()) / a.sweeps
+        e["parts"] = sorted(part_names)
+        pmc["unit"] += "; the first entry: per SWEEP, the named kernels summed"
+        pmc["kernels"] = {a.sweep_sum: e, **pmc["kernels"]}
     if a.fetch or a.write or a.extra:
         with open(os.path.join(HERE, f"{a.tag}_pmc.json"), "w") as f:
             json.dump(pmc, f, indent=1)

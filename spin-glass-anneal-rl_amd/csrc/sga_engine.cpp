@@ -132,19 +132,31 @@ int row_shared_window(const sga_engine *e, bool lean) {
     return fw >= 1024 ? 1024 : fw >= 512 ? 512 : fw >= 256 ? 256 : (e->rs_tuned_w > 0 ? e->rs_tuned_w : 1024);
 }
 
-// the form's scratch for W: false (and the row-per-proposal kernel runs) if it cannot be had
+// the form's scratch for W and, where the problem gets them, its resident bit-planes of J: false (and the
+// row-per-proposal kernel runs) if either cannot be had
 static bool ensure_row_shared(sga_engine *e, int W, hipStream_t st) {
     if (e->rs.cnt && e->rs.W == W && e->rs_R == e->R && e->rs_n == e->n) return true;
     e->free_row_shared();
     const size_t n = (size_t)e->n, R = (size_t)e->R, nwin = (n + (size_t)W - 1) / (size_t)W;
-    const int nw32 = sga::row_shared_nw32(e->n);
-    hipError_t he = hipMalloc(&e->rs.cnt, sizeof(int) * nwin * n);
+    const int nw32 = sga::row_shared_nw32(e->n), planes = sga::row_shared_planes(e->j_abs_max);
+    const int log_rg = sga::row_shared_log_group(e->n, W);
+    const size_t groups = (R + ((size_t)1 << log_rg) - 1) >> log_rg;
+    hipError_t he = hipSuccess;
+    if (!e->rs_jp && sga::row_shared_resident(e->want_i8, planes)) {  // once per problem
+        he = hipMalloc(&e->rs_jp, sga::row_shared_plane_bytes(e->n, planes));
+        if (he == hipSuccess) he = hipMalloc(&e->rs_jabs, sizeof(int) * n);
+        if (he == hipSuccess)
+            he = sga::launch_rs_build_planes(e->J_packed, e->want_i8, e->ldj, e->n, planes, e->rs_jp, e->rs_jabs, st);
+        if (he != hipSuccess) {
+            dev_free(e->rs_jp);
+            dev_free(e->rs_jabs);
+        }
+    }
+    if (he == hipSuccess) he = hipMalloc(&e->rs.cnt, sizeof(int) * nwin * groups * n);
     if (he == hipSuccess) he = hipMalloc(&e->rs.off, sizeof(int) * nwin * (n + 1));
-    if (he == hipSuccess) he = hipMalloc(&e->rs.cur, sizeof(int) * nwin * n);
     if (he == hipSuccess) he = hipMalloc(&e->rs.ent, sizeof(int) * R * n);
     if (he == hipSuccess) he = hipMalloc(&e->rs.base, sizeof(int) * R * (size_t)W);
     if (he == hipSuccess) he = hipMalloc(&e->rs.bits, sizeof(uint32_t) * R * (size_t)nw32);
-    if (he == hipSuccess) he = hipMemsetAsync(e->rs.cnt, 0, sizeof(int) * nwin * n, st);
     if (he != hipSuccess) {
         (void)hipGetLastError();
         e->free_row_shared();
@@ -155,7 +167,11 @@ static bool ensure_row_shared(sga_engine *e, int W, hipStream_t st) {
     e->rs.W = W;
     e->rs.log_w = lw;
     e->rs.nw32 = nw32;
-    e->rs.planes = sga::row_shared_planes(e->j_abs_max);
+    e->rs.planes = planes;
+    e->rs.jp = e->rs_jp;
+    e->rs.jabs = e->rs_jabs;
+    e->rs.log_rg = log_rg;
+    e->rs.n_groups = (int)groups;
     e->rs_R = e->R;
     e->rs_n = e->n;
     return true;

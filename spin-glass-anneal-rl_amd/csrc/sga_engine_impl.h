@@ -223,15 +223,19 @@ struct sga_engine {
     int auto_interval = 4;              // sweeps until the next look (doubles up to 32)
     std::vector<unsigned long long> auto_mark_acc;
     // row-shared windows (sweep_dense_rs.hip, option "row_shared"): the window the autotuner picked (0: none), the
-    // plan / field scratch and what it was sized for; rs_suspend keeps the form out of the autotuner's geometry trials
+    // plan / field scratch and what it was sized for; rs_suspend keeps the form out of the autotuner's geometry trials.
+    // rs_jp / rs_jabs: the resident bit-planes of J_packed and sum_j |J_ij| per row (RowSharedPlan::jp, jabs), built by
+    // the form's first sweep of a problem.  They belong to the problem, not to W or the replicas: free_problem -- the
+    // one place J_packed is replaced -- drops them, window and replica changes keep them.
     int rs_tuned_w = 0;
     bool rs_suspend = false;
     sga::RowSharedPlan rs{};
     int rs_R = 0, rs_n = 0;
+    unsigned long long *rs_jp = nullptr;
+    int *rs_jabs = nullptr;
     void free_row_shared() {
         dev_free(rs.cnt);
         dev_free(rs.off);
-        dev_free(rs.cur);
         dev_free(rs.ent);
         dev_free(rs.base);
         dev_free(rs.bits);
@@ -311,6 +315,8 @@ struct sga_engine {
         n = 0;
         ld = 0;
         free_row_shared();
+        dev_free(rs_jp);
+        dev_free(rs_jabs);
         rs_tuned_w = 0;
     }
     void free_replicas() {

@@ -358,18 +358,41 @@ hipError_t launch_update_best(const double *energy, const int8_t *spins, double 
                               int8_t *best_spins, int sstride, int R, hipStream_t st);
 
 // Row-shared windows (sweep_dense_rs.hip): the dense sweep of integer problems with one coupling-row read per
-// proposed site and window of W updates per replica.  Scratch of the window plan and the fields:
+// proposed site and window of W updates per replica.  Scratch of the window plan and the fields, and the problem's
+// resident bit-planes of J (owned by the engine, made once per problem):
 struct RowSharedPlan {
-    int *cnt;        // [n_windows][n] proposals per (window, site); zero between sweeps
+    int *cnt;        // [n_windows][n_groups][n] proposals per (window, replica group, site); after the scan the first
+                     // entry of each (the fill's cursors)
     int *off;        // [n_windows][n + 1] first entry of each (window, site)
-    int *cur;        // [n_windows][n] fill cursors
     int *ent;        // [R n] (replica << log_w | update in window), grouped by (window, site)
     int *base;       // [R][W] row sums against the window-start spins
     uint32_t *bits;  // [R][nw32] window-start spins, 1 = down (the layout of sweep_dense_rs.hip)
+    const unsigned long long *jp;  // [n][planes + 1][nw32 / 2] sign plane and magnitude planes of every row of J in the
+                                   // spins' bit layout; null: the fields kernel converts the rows of J on chip
+    const int *jabs;               // [n] sum_j |J_ij| (with jp)
     int W, log_w, nw32, planes;  // planes: magnitude bit-planes of |J| (1 | 3 | 8)
+    int log_rg, n_groups;        // replicas per group of the plan (a power of two), groups
 };
 int row_shared_planes(int j_abs_max);  // 0: |J| beyond 255, the form does not apply
 inline int row_shared_nw32(int n) { return 8 * ((n + 255) / 256); }
+// Resident planes exist where they take at most half the bytes of J: fp32 rows always ((planes + 1) / 32 of J), int8
+// rows for 1 and 3 magnitude planes; int8 rows with 8 planes keep the on-chip conversion.
+inline bool row_shared_resident(bool j_is_i8, int planes) { return planes > 0 && (!j_is_i8 || planes <= 3); }
+inline size_t row_shared_plane_bytes(int n, int planes) {
+    return (size_t)n * (size_t)(planes + 1) * (size_t)(row_shared_nw32(n) / 2) * 8;
+}
+// log2 of the replicas per group of the window plan: at least 32, and at least the number of windows, so that a slice
+// (one window, one group: W 2^log_rg entries) holds about as many entries as its histogram has sites and the counts
+// stay within the bytes of the entries
+inline int row_shared_log_group(int n, int W) {
+    const int nwin = (n + W - 1) / W;
+    int l = 5;
+    while ((1 << l) < nwin) ++l;
+    return l;
+}
+// one pass over J: jp and jabs of every row (the first time the form is prepared for a problem)
+hipError_t launch_rs_build_planes(const void *J, bool j_is_i8, long long ldj, int n, int planes, unsigned long long *jp,
+                                  int *jabs, hipStream_t st);
 // a.n_sweeps sweeps: spins -> bits, then per sweep the plan, per window fields + chain, best tracking.  Production
 // arguments only (Philox sites, Metropolis with the accept table, fp64 rule, no per-update traces, all replicas).
 hipError_t launch_sweep_dense_rs(const SweepArgs &a, const RowSharedPlan &p, bool j_is_i8, hipStream_t st);

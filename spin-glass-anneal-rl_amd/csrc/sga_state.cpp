@@ -385,9 +385,15 @@ int sga_describe(sga_engine *e, char *buf, int buflen) {
                           : 1);
     if (!e->csr && !e->tsp && e->field_cache == SGA_FIELD_CACHE_OFF) {  // production sweeps in row-shared windows
         const int rw = row_shared_window(e, true);
-        if (rw > 0)
-            std::snprintf(tmp + std::strlen(tmp), sizeof(tmp) - std::strlen(tmp), " sweep=row-shared(W=%d planes=%d)", rw,
-                          sga::row_shared_planes(e->j_abs_max));
+        if (rw > 0) {
+            const int pl = sga::row_shared_planes(e->j_abs_max);
+            std::snprintf(tmp + std::strlen(tmp), sizeof(tmp) - std::strlen(tmp), " sweep=row-shared(W=%d planes=%d)", rw, pl);
+            if (sga::row_shared_resident(e->want_i8, pl))  // (the bytes the form's first sweep adds, once per problem)
+                std::snprintf(tmp + std::strlen(tmp), sizeof(tmp) - std::strlen(tmp), " rs_fields=resident-planes(%zuB)",
+                              sga::row_shared_plane_bytes(e->n, pl));
+            else
+                std::strncat(tmp, " rs_fields=on-chip-conversion", sizeof(tmp) - std::strlen(tmp) - 1);
+        }
     }
     if (e->csr && !e->ragged && csr_updates_per_step(e) >= 4 && e->waves <= 1 && (e->big_form == 0 || e->big_form == 2) && e->rowptr)
         std::snprintf(tmp + std::strlen(tmp), sizeof(tmp) - std::strlen(tmp), " updates_per_step=%d", csr_updates_per_step(e));

@@ -3,9 +3,12 @@
 //
 // The sites and uniforms come from the counter RNG (the stream of fetch_pair / PairSource), so every replica's
 // proposals are known ahead of the chain.  A sweep is cut into windows of W updates per replica; each window runs
-//   * fields: one workgroup per proposed site i reads row i once, turns it on chip into bit-planes (sign of J, and
-//     one plane per binary digit of |J|), and dots it with the window-start spins (bits) of every replica that
-//     proposes i inside the window: base(r, t) = sum_j J_ij s_j -- a full row sum of n terms per proposal;
+//   * fields: one workgroup per proposed site i takes row i as bit-planes (sign of J, and one plane per binary digit
+//     of |J|) and dots it with the window-start spins (bits) of every replica that proposes i inside the window:
+//     base(r, t) = sum_j J_ij s_j -- a full row sum of n terms per proposal.  The planes of the whole matrix are made
+//     once per problem and stay in HBM (rs_planes_kernel, RowSharedPlan::jp): J does not change between two
+//     sga_set_* calls, and a plane row is (planes + 1) / 32 of the fp32 row.  Only int8 rows with 8 magnitude planes,
+//     whose planes would outweigh J, are converted on chip per window (rs_fields_kernel);
 //   * chain: one wave per replica holds the W pending fields, one per (lane, block).  Every remaining update is
 //     decided at once against the fields as they stand; the first accepted one is committed (energy, spin), and
 //     the later updates' fields are corrected by -2 J[i_a][i_t] s_a (J symmetric: read from row i_a) and their spins
@@ -13,7 +16,8 @@
 // J and h are integer valued with every partial sum below 2^24 (the look-ahead form's proof): the base sums and the
 // corrected fields are exactly the fp32 row sums of the one-update-at-a-time chain, the accept rule is the table
 // form's, and every decision, energy, spin and counter is bit-identical.  No field outlives its window.
-// The window plan -- which (replica, update) proposes which site -- is one counting sort per sweep.
+// The window plan -- which (replica, update) proposes which site -- is one counting sort per sweep, histogrammed in
+// LDS per (window, group of replicas): no atomic of it reaches memory.
 #include <type_traits>
 
 #include "sweep_common.h"
@@ -38,25 +42,59 @@ __device__ __forceinline__ void rs_update(const SweepArgs &a, int r, int k, int 
 }
 
 // ---- plan: counting sort of the sweep's (replica, update) pairs by (window, site) --------------------------------
-__global__ void __launch_bounds__(256) rs_count_kernel(const SweepArgs a, RowSharedPlan p, int k) {
-    const int t = blockIdx.y * 256 + threadIdx.x, r = blockIdx.x;
-    if (t >= a.n) return;
-    int site;
-    uint32_t ub;
-    rs_update(a, r, k, t, site, ub);
-    atomicAdd(&p.cnt[(long long)(t >> p.log_w) * a.n + site], 1);
+// A workgroup owns one slice -- window w, replica group g (2^log_rg replicas) -- and one tile of RS_PLAN_TILE sites:
+// its counters are LDS words (64 KiB at most, so any n is served: n <= 16384 is one tile, beyond that every tile
+// walks the slice's Philox blocks again and keeps the sites that are its own).  count: histogram -> cnt[w][g][site].
+// scan, per window: entries ordered by (site, group) -> off[w][site], and cnt[w][g][site] becomes the first entry of
+// (w, g, site).  fill: the same walk, positions handed out from the LDS copy of the slice's cursors.  The order of
+// the entries inside a (window, site) bucket is whatever the LDS atomics make it; nothing depends on it (each entry
+// names its own base slot).
+constexpr int RS_PLAN_TILE = 16384;
+
+template <bool FILL>
+__global__ void __launch_bounds__(256) rs_plan_kernel(const SweepArgs a, RowSharedPlan p, int k) {
+    extern __shared__ int slot[];  // [min(n, RS_PLAN_TILE)]
+    const int g = blockIdx.x, w = blockIdx.y, s0 = blockIdx.z * RS_PLAN_TILE, n = a.n, tid = threadIdx.x;
+    const int ns = min(RS_PLAN_TILE, n - s0);
+    int *mine = p.cnt + ((long long)w * p.n_groups + g) * n + s0;
+    for (int i = tid; i < ns; i += 256) slot[i] = FILL ? mine[i] : 0;
+    __syncthreads();
+    const int r0 = g << p.log_rg, nr = min(1 << p.log_rg, a.R - r0);
+    const int t0 = w << p.log_w, nt = min(p.W, n - t0);  // t0 is even: one Philox block serves updates 2 b, 2 b + 1
+    const int lhalf = p.log_w - 1, hmask = (1 << lhalf) - 1;
+    for (int x = tid; x < (nr << lhalf); x += 256) {
+        const int r = r0 + (x >> lhalf), b = x & hmask;
+        if (2 * b >= nt) continue;
+        const u32x4 q = philox4x32_10((uint32_t)((t0 >> 1) + b), a.sweep0 + (uint32_t)k, a.replica0 + (uint32_t)r,
+                                      DOMAIN_SWEEP, a.seed_lo, a.seed_hi);
+        const int sA = (int)word_to_site(q.x, (uint32_t)n) - s0, sB = (int)word_to_site(q.z, (uint32_t)n) - s0;
+        const bool inA = (unsigned)sA < (unsigned)ns, inB = 2 * b + 1 < nt && (unsigned)sB < (unsigned)ns;
+        if constexpr (FILL) {
+            if (inA) p.ent[atomicAdd(&slot[sA], 1)] = (r << p.log_w) | (2 * b);
+            if (inB) p.ent[atomicAdd(&slot[sB], 1)] = (r << p.log_w) | (2 * b + 1);
+        } else {
+            if (inA) atomicAdd(&slot[sA], 1);
+            if (inB) atomicAdd(&slot[sB], 1);
+        }
+    }
+    if constexpr (!FILL) {
+        __syncthreads();
+        for (int i = tid; i < ns; i += 256) mine[i] = slot[i];
+    }
 }
 
-// one workgroup per window: exclusive scan of its n counts, entries of window w start at R w W
+// one workgroup per window: exclusive scan of its counts in (site, group) order, entries of window w start at R w W
 __global__ void __launch_bounds__(1024) rs_scan_kernel(const SweepArgs a, RowSharedPlan p) {
     __shared__ int sh[1024];
-    const int w = blockIdx.x, tid = threadIdx.x, n = a.n;
-    int *cnt = p.cnt + (long long)w * n, *cur = p.cur + (long long)w * n;
+    const int w = blockIdx.x, tid = threadIdx.x, n = a.n, G = p.n_groups;
+    int *cnt = p.cnt + (long long)w * G * n;
     int *off = p.off + (long long)w * (n + 1);
     int carry = a.R * (w << p.log_w);
     for (int i0 = 0; i0 < n; i0 += 1024) {
         const int i = i0 + tid;
-        const int v = i < n ? cnt[i] : 0;
+        int v = 0;
+        if (i < n)
+            for (int g = 0; g < G; ++g) v += cnt[(long long)g * n + i];
         sh[tid] = v;
         __syncthreads();
         for (int d = 1; d < 1024; d <<= 1) {  // inclusive Hillis-Steele scan
@@ -66,25 +104,18 @@ __global__ void __launch_bounds__(1024) rs_scan_kernel(const SweepArgs a, RowSha
             __syncthreads();
         }
         if (i < n) {
-            off[i] = carry + sh[tid] - v;
-            cur[i] = carry + sh[tid] - v;
-            cnt[i] = 0;  // zero again for the next sweep's plan
+            int run = carry + sh[tid] - v;
+            off[i] = run;
+            for (int g = 0; g < G; ++g) {
+                const int c = cnt[(long long)g * n + i];
+                cnt[(long long)g * n + i] = run;
+                run += c;
+            }
         }
         carry += sh[1023];
         __syncthreads();
     }
     if (tid == 0) off[n] = carry;
-}
-
-__global__ void __launch_bounds__(256) rs_fill_kernel(const SweepArgs a, RowSharedPlan p, int k) {
-    const int t = blockIdx.y * 256 + threadIdx.x, r = blockIdx.x;
-    if (t >= a.n) return;
-    int site;
-    uint32_t ub;
-    rs_update(a, r, k, t, site, ub);
-    const int w = t >> p.log_w;
-    const int pos = atomicAdd(&p.cur[(long long)w * a.n + site], 1);
-    p.ent[pos] = (r << p.log_w) | (t - (w << p.log_w));
 }
 
 // int8 spins -> the bit layout above (1 = spin down); one workgroup per replica
@@ -104,19 +135,12 @@ __global__ void __launch_bounds__(256) rs_pack_kernel(const SweepArgs a, RowShar
     }
 }
 
-// ---- fields: one workgroup (4 waves) per proposed site ----------------------------------------------------------------
-// PL magnitude planes: |J| < 2^PL.  LDS: [PL + 1][4 nseg] 64-bit words (sign plane first).
+// ---- a row of J as bit-planes ------------------------------------------------------------------------------------
+// PL magnitude planes: |J| < 2^PL.  planes: [PL + 1][nw = 4 nseg] 64-bit words (sign plane first), in LDS or in the
+// resident copy; every word is written.  Called by a workgroup of four waves; returns this lane's share of sum |J_ij|.
 template <typename JE, int PL>
-__global__ void __launch_bounds__(256) rs_fields_kernel(const SweepArgs a, RowSharedPlan p, int win) {
-    const int i = blockIdx.x, n = a.n;
-    const int *off = p.off + (long long)win * (n + 1);
-    const int lo = off[i], hi = off[i + 1];
-    if (lo == hi) return;  // nobody proposes this site in this window: the row is not read
-    extern __shared__ unsigned long long planes[];
-    __shared__ int csum[4];
+__device__ __forceinline__ int rs_row_to_planes(const JE *row, int n, unsigned long long *planes, int lane, int wv) {
     const int nseg = (n + 255) >> 8, nw = 4 * nseg;
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const JE *row = reinterpret_cast<const JE *>(a.J) + (long long)i * a.ldj;
     int absum = 0;
     // four segments per wave in flight, then their ballots
     for (int g0 = wv; g0 < nseg; g0 += 16) {
@@ -161,6 +185,78 @@ __global__ void __launch_bounds__(256) rs_fields_kernel(const SweepArgs a, RowSh
             }
         }
     }
+    return absum;
+}
+
+// the resident copy: one workgroup per row, once per problem
+template <typename JE, int PL>
+__global__ void __launch_bounds__(256) rs_planes_kernel(const JE *J, long long ldj, int n, unsigned long long *jp, int *jabs) {
+    __shared__ int csum[4];
+    const int i = blockIdx.x, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int nw = 4 * ((n + 255) >> 8);
+    int absum = rs_row_to_planes<JE, PL>(J + (long long)i * ldj, n, jp + (long long)i * (PL + 1) * nw, lane, wv);
+    absum = wave_sum(absum);
+    if (lane == 0) csum[wv] = absum;
+    __syncthreads();
+    if (threadIdx.x == 0) jabs[i] = csum[0] + csum[1] + csum[2] + csum[3];
+}
+
+// ---- fields from the resident planes: one workgroup (4 waves) per proposed site ------------------------------------
+// The site's plane row (PL + 1 planes of nw words) goes to LDS as it is; then a quarter wave (16 lanes, one DPP row) per
+// entry: each lane takes two words at a time of the replica's spin bits, and four row-local DPP steps close the sum,
+// so a wave finishes four entries per pass.  sum_j J_ij s_j = C - 2 sum_b 2^b popcount(plane_b & (sign ^ spin bits)).
+template <int PL>
+__global__ void __launch_bounds__(256) rs_fields_planes_kernel(const SweepArgs a, RowSharedPlan p, int win) {
+    const int i = blockIdx.x, n = a.n;
+    const int *off = p.off + (long long)win * (n + 1);
+    const int lo = off[i], hi = off[i + 1];
+    if (lo == hi) return;  // nobody proposes this site in this window: the row is not read
+    extern __shared__ ulonglong2 prow[];  // [PL + 1][nw / 2]
+    const int nw2 = p.nw32 >> 2;           // pairs of 64-bit words per plane (nw is a multiple of 4)
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, sub = lane >> 4, l16 = lane & 15;
+    const ulonglong2 *src = reinterpret_cast<const ulonglong2 *>(p.jp) + (long long)i * (PL + 1) * nw2;
+    for (int c = tid; c < (PL + 1) * nw2; c += 256) prow[c] = src[c];
+    const int C = p.jabs[i];  // sum_j |J_ij|
+    __syncthreads();
+    const ulonglong2 *bits = reinterpret_cast<const ulonglong2 *>(p.bits);
+    const int wmask = (1 << p.log_w) - 1;
+    for (int x0 = lo + 4 * wv; x0 < hi; x0 += 16) {  // wave-uniform bounds: the DPP steps run with every lane on
+        const int x = x0 + sub;
+        const bool live = x < hi;
+        const int e = p.ent[live ? x : lo];
+        const ulonglong2 *s = bits + (long long)(e >> p.log_w) * nw2;
+        int acc = 0;
+        for (int c = l16; c < nw2; c += 16) {
+            const ulonglong2 sv = s[c], sg = prow[c];
+            const unsigned long long x0w = sv.x ^ sg.x, x1w = sv.y ^ sg.y;
+#pragma unroll
+            for (int b = 0; b < PL; ++b) {
+                const ulonglong2 pb = prow[(1 + b) * nw2 + c];
+                acc += (__popcll(pb.x & x0w) + __popcll(pb.y & x1w)) << b;
+            }
+        }
+        acc += dpp_move<DPP_QUAD_XOR1>(acc);
+        acc += dpp_move<DPP_QUAD_XOR2>(acc);
+        acc += dpp_move<DPP_ROW_HALF_MIRROR>(acc);
+        acc += dpp_move<DPP_ROW_MIRROR>(acc);
+        if (live && l16 == 0) p.base[(long long)(e >> p.log_w) * p.W + (e & wmask)] = C - 2 * acc;
+    }
+}
+
+// ---- fields by on-chip conversion (int8 rows with 8 magnitude planes): one workgroup (4 waves) per proposed site -------
+// LDS: [PL + 1][4 nseg] 64-bit words (sign plane first).
+template <typename JE, int PL>
+__global__ void __launch_bounds__(256) rs_fields_kernel(const SweepArgs a, RowSharedPlan p, int win) {
+    const int i = blockIdx.x, n = a.n;
+    const int *off = p.off + (long long)win * (n + 1);
+    const int lo = off[i], hi = off[i + 1];
+    if (lo == hi) return;  // nobody proposes this site in this window: the row is not read
+    extern __shared__ unsigned long long planes[];
+    __shared__ int csum[4];
+    const int nseg = (n + 255) >> 8, nw = 4 * nseg;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const JE *row = reinterpret_cast<const JE *>(a.J) + (long long)i * a.ldj;
+    int absum = rs_row_to_planes<JE, PL>(row, n, planes, lane, wv);
     absum = wave_sum(absum);
     if (lane == 0) csum[wv] = absum;
     __syncthreads();
@@ -201,7 +297,10 @@ __device__ __forceinline__ bool rs_accept(float fk, float u, double T, int table
     return (dE > T * 104.0) ? false : (u < expf_det((float)(-dE / T)));
 }
 
-template <typename JE, int NB>
+// BITS: the correction J[i_a][i_t] is read from the resident planes of row i_a (one magnitude plane: two bits give
+// nonzero ? (sign ? -1 : +1) : 0, the value the row of J holds) -- a 40 KB fp32 row gathered at W sites costs about a
+// cache line per lane, its plane row is 2.5 KB in all.
+template <typename JE, int NB, bool BITS>
 __global__ void __launch_bounds__(64) rs_chain_kernel(const SweepArgs a, RowSharedPlan p, int k, int win) {
     const int r = blockIdx.x, lane = threadIdx.x, n = a.n;
     constexpr int W = 64 * NB;
@@ -265,12 +364,27 @@ __global__ void __launch_bounds__(64) rs_chain_kernel(const SweepArgs a, RowShar
             atomicXor(&p.bits[(long long)r * p.nw32 + w32], bit);
         }
         // the later updates: field -= 2 J[sa][site] s_a (J symmetric), the spin negated where the site repeats
-        const JE *rowa = J + (long long)sa * a.ldj;
         const float s2 = 2.0f * (float)ss;
         float x[NB];
+        if constexpr (BITS) {
+            const uint32_t *sgn = reinterpret_cast<const uint32_t *>(p.jp) + (long long)sa * (2 * p.nw32);
+            const uint32_t *mag = sgn + p.nw32;
 #pragma unroll
-        for (int b = 0; b < NB; ++b)
-            if (b >= fb) x[b] = (float)rowa[site[b]];
+            for (int b = 0; b < NB; ++b) {
+                if (b >= fb) {
+                    int w32;
+                    unsigned int bit;
+                    rs_bit_of(site[b], w32, bit);
+                    const unsigned int sg = sgn[w32], mg = mag[w32];
+                    x[b] = (mg & bit) ? ((sg & bit) ? -1.0f : 1.0f) : 0.0f;
+                }
+            }
+        } else {
+            const JE *rowa = J + (long long)sa * a.ldj;
+#pragma unroll
+            for (int b = 0; b < NB; ++b)
+                if (b >= fb) x[b] = (float)rowa[site[b]];
+        }
 #pragma unroll
         for (int b = 0; b < NB; ++b) {
             if (b >= fb) {
@@ -288,10 +402,8 @@ __global__ void __launch_bounds__(64) rs_chain_kernel(const SweepArgs a, RowShar
     }
 }
 
-template <typename JE, int PL>
-static hipError_t rs_launch_fields(const SweepArgs &a, const RowSharedPlan &p, int win, hipStream_t st) {
-    const size_t lds = (size_t)(PL + 1) * 4 * ((a.n + 255) / 256) * 8;
-    auto kern = rs_fields_kernel<JE, PL>;
+template <typename Kern>
+static hipError_t rs_launch_fields(Kern kern, size_t lds, const SweepArgs &a, const RowSharedPlan &p, int win, hipStream_t st) {
     hipError_t e = ensure_lds_limit(reinterpret_cast<const void *>(kern), lds);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(kern, dim3(a.n), dim3(256), lds, st, a, p, win);
@@ -300,20 +412,29 @@ static hipError_t rs_launch_fields(const SweepArgs &a, const RowSharedPlan &p, i
 
 template <typename JE>
 static hipError_t rs_fields(const SweepArgs &a, const RowSharedPlan &p, int win, hipStream_t st) {
+    const size_t lds = (size_t)(p.planes + 1) * (p.nw32 / 2) * 8;
+    if (p.jp) {
+        switch (p.planes) {
+            case 1: return rs_launch_fields(rs_fields_planes_kernel<1>, lds, a, p, win, st);
+            case 3: return rs_launch_fields(rs_fields_planes_kernel<3>, lds, a, p, win, st);
+            case 8: return rs_launch_fields(rs_fields_planes_kernel<8>, lds, a, p, win, st);
+            default: return hipErrorInvalidValue;
+        }
+    }
     switch (p.planes) {
-        case 1: return rs_launch_fields<JE, 1>(a, p, win, st);
-        case 3: return rs_launch_fields<JE, 3>(a, p, win, st);
-        case 8: return rs_launch_fields<JE, 8>(a, p, win, st);
+        case 1: return rs_launch_fields(rs_fields_kernel<JE, 1>, lds, a, p, win, st);
+        case 3: return rs_launch_fields(rs_fields_kernel<JE, 3>, lds, a, p, win, st);
+        case 8: return rs_launch_fields(rs_fields_kernel<JE, 8>, lds, a, p, win, st);
         default: return hipErrorInvalidValue;
     }
 }
 
-template <typename JE>
+template <typename JE, bool BITS>
 static hipError_t rs_chain(const SweepArgs &a, const RowSharedPlan &p, int k, int win, hipStream_t st) {
     switch (p.W) {
-        case 256: hipLaunchKernelGGL((rs_chain_kernel<JE, 4>), dim3(a.R), dim3(64), 0, st, a, p, k, win); break;
-        case 512: hipLaunchKernelGGL((rs_chain_kernel<JE, 8>), dim3(a.R), dim3(64), 0, st, a, p, k, win); break;
-        case 1024: hipLaunchKernelGGL((rs_chain_kernel<JE, 16>), dim3(a.R), dim3(64), 0, st, a, p, k, win); break;
+        case 256: hipLaunchKernelGGL((rs_chain_kernel<JE, 4, BITS>), dim3(a.R), dim3(64), 0, st, a, p, k, win); break;
+        case 512: hipLaunchKernelGGL((rs_chain_kernel<JE, 8, BITS>), dim3(a.R), dim3(64), 0, st, a, p, k, win); break;
+        case 1024: hipLaunchKernelGGL((rs_chain_kernel<JE, 16, BITS>), dim3(a.R), dim3(64), 0, st, a, p, k, win); break;
         default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
@@ -323,29 +444,56 @@ int row_shared_planes(int j_abs_max) {
     return j_abs_max <= 1 ? 1 : j_abs_max <= 7 ? 3 : j_abs_max <= 255 ? 8 : 0;
 }
 
+template <typename JE>
+static hipError_t rs_build_planes(const void *J, long long ldj, int n, int planes, unsigned long long *jp, int *jabs,
+                                  hipStream_t st) {
+    const JE *Jt = reinterpret_cast<const JE *>(J);
+    switch (planes) {
+        case 1: hipLaunchKernelGGL((rs_planes_kernel<JE, 1>), dim3(n), dim3(256), 0, st, Jt, ldj, n, jp, jabs); break;
+        case 3: hipLaunchKernelGGL((rs_planes_kernel<JE, 3>), dim3(n), dim3(256), 0, st, Jt, ldj, n, jp, jabs); break;
+        case 8: hipLaunchKernelGGL((rs_planes_kernel<JE, 8>), dim3(n), dim3(256), 0, st, Jt, ldj, n, jp, jabs); break;
+        default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_rs_build_planes(const void *J, bool j_is_i8, long long ldj, int n, int planes, unsigned long long *jp,
+                                  int *jabs, hipStream_t st) {
+    if (!J || !jp || !jabs || n <= 0) return hipErrorInvalidValue;
+    return j_is_i8 ? rs_build_planes<int8_t>(J, ldj, n, planes, jp, jabs, st)
+                   : rs_build_planes<float>(J, ldj, n, planes, jp, jabs, st);
+}
+
 hipError_t launch_sweep_dense_rs(const SweepArgs &a, const RowSharedPlan &p, bool j_is_i8, hipStream_t st) {
     if (a.rep_list || a.R <= 0 || a.n <= 0 || (p.W != 256 && p.W != 512 && p.W != 1024) || (1 << p.log_w) != p.W)
         return hipErrorInvalidValue;
+    if (p.log_rg < 0 || p.n_groups != (a.R + (1 << p.log_rg) - 1) >> p.log_rg || (p.jp && !p.jabs)) return hipErrorInvalidValue;
     const int nwin = (a.n + p.W - 1) / p.W;
-    const dim3 grid(a.R, (a.n + 255) / 256);
+    const dim3 pgrid(p.n_groups, nwin, (a.n + RS_PLAN_TILE - 1) / RS_PLAN_TILE);
+    const size_t plds = sizeof(int) * (size_t)(a.n < RS_PLAN_TILE ? a.n : RS_PLAN_TILE);
+    const bool chain_bits = p.jp && p.planes == 1;
     hipLaunchKernelGGL(rs_pack_kernel, dim3(a.R), dim3(256), 0, st, a, p);
     hipError_t e = hipGetLastError();
     for (int k = 0; k < a.n_sweeps && e == hipSuccess; ++k) {
-        hipLaunchKernelGGL(rs_count_kernel, grid, dim3(256), 0, st, a, p, k);
+        hipLaunchKernelGGL(rs_plan_kernel<false>, pgrid, dim3(256), plds, st, a, p, k);
         hipLaunchKernelGGL(rs_scan_kernel, dim3(nwin), dim3(1024), 0, st, a, p);
-        hipLaunchKernelGGL(rs_fill_kernel, grid, dim3(256), 0, st, a, p, k);
+        hipLaunchKernelGGL(rs_plan_kernel<true>, pgrid, dim3(256), plds, st, a, p, k);
         e = hipGetLastError();
         for (int w = 0; w < nwin && e == hipSuccess; ++w) {
             e = j_is_i8 ? rs_fields<int8_t>(a, p, w, st) : rs_fields<float>(a, p, w, st);
-            if (e == hipSuccess) e = j_is_i8 ? rs_chain<int8_t>(a, p, k, w, st) : rs_chain<float>(a, p, k, w, st);
+            if (e != hipSuccess) break;
+            if (chain_bits)
+                e = j_is_i8 ? rs_chain<int8_t, true>(a, p, k, w, st) : rs_chain<float, true>(a, p, k, w, st);
+            else
+                e = j_is_i8 ? rs_chain<int8_t, false>(a, p, k, w, st) : rs_chain<float, false>(a, p, k, w, st);
         }
         // sweep boundary: best tracking (annealing/gpu_annealer.py:151-153), the energy is in a.energy
         if (e == hipSuccess && !a.no_best)
             e = launch_update_best(a.energy, a.spins, a.best_energy, a.best_spins, a.sstride, a.R, st);
     }
     if (e == hipSuccess)
-        note_sweep_kernel("sweep_dense_rs<%s, planes=%d, W=%d> (row-shared windows: plan, fields, chain)",
-                          j_is_i8 ? "int8_t" : "float", p.planes, p.W);
+        note_sweep_kernel("sweep_dense_rs<%s, planes=%d, W=%d> (row-shared windows: plan, fields from %s, chain)",
+                          j_is_i8 ? "int8_t" : "float", p.planes, p.W, p.jp ? "resident bit-planes" : "on-chip conversion");
     return e;
 }
 
