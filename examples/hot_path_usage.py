@@ -81,6 +81,26 @@ def travelling_salesman(n_cities=12):
         print("   tour:", tour)
 
 
+def scheduling_without_storing_couplings(n_tasks=500, n_slots=100, n_replicas=1024, n_sweeps=100):
+    """A scheduling instance whose every coupling comes from a cardinality constraint (one start per task, one task
+    per slot): the engine keeps the groups and their sums instead of J (AnnealEngine.set_groups), bit-identical to
+    the stored-coupling chain -- 0.8 MB of tables instead of 256 MB of CSR at this size."""
+    from spin_glass_anneal_rl_amd import AnnealEngine
+    from spin_glass_anneal_rl_amd.encoders import scheduling_groups
+    n, member_ptr, members, coeff, h, constant = scheduling_groups(
+        np.full(n_tasks, 1.0), 1, float(n_slots), n_slots, objective="total_time",
+        penalty_weights={"assignment": 100.0, "capacity": 50.0})
+    with AnnealEngine(0) as eng:
+        eng.set_groups(n, (member_ptr, members), coeff, h)
+        eng.init_replicas(n_replicas, seed=3)
+        eng.set_ladder(np.geomspace(500.0, 5.0, n_replicas), 1)
+        for _ in range(n_sweeps // 10):
+            eng.sweep(10)
+            eng.exchange(count=False)
+        energy, spins, replica = eng.best()
+        return energy + constant, spins, eng.describe()
+
+
 def travelling_salesman_without_storing_couplings(n_cities=200, n_replicas=512, n_sweeps=200):
     """The same QUBO at a size where the couplings themselves become the cost (200 cities: 40 000
     spins, 32 M couplings; 1000 cities: 10^6 spins, 32 GB): the engine keeps distances + penalty
@@ -120,3 +140,4 @@ if __name__ == "__main__":
     many_models()
     travelling_salesman()
     travelling_salesman_without_storing_couplings()
+    scheduling_without_storing_couplings()

@@ -80,7 +80,7 @@ typedef struct sga_engine sga_engine;
 int sga_create(int device, sga_engine **out);
 void sga_destroy(sga_engine *e);
 const char *sga_last_error(void);
-int sga_version(void);  /* 800: option "clf_fixed_point" serves dense couplings too */
+int sga_version(void);  /* 1000: sga_set_groups (implicit cardinality-group couplings) */
 /* Run on an existing HIP stream (e.g. torch.cuda.current_stream().cuda_stream); NULL = the
  * engine's own stream (default). */
 int sga_set_stream(sga_engine *e, void *hip_stream);
@@ -161,6 +161,33 @@ int sga_get_batch_model(sga_engine *e, int m, int *n_spins, int *first_replica, 
  * form (SGA_ERR_UNSUPPORTED); local fields are. */
 int sga_set_tsp(sga_engine *e, const float *dist, int64_t ld, int n_cities, float city_visit,
                 float position_fill, const float *h);
+
+/* Couplings that are a sum of complete graphs on groups of sites, never stored (version >= 1000): what
+ * encoders.IsingBuilder.add_cardinality_groups builds -- the assignment and scheduling instances, BASELINE
+ * configs[1] / configs[3].  Group g is members[member_ptr[g] .. member_ptr[g + 1]) and adds coeff[g] to J_ij for every
+ * pair i != j of its members:
+ *     J_ij = sum_{g contains i and j} coeff[g]   (i != j),   J_ii = 0
+ *     sum_j J_ij s_j = sum_{g contains i} coeff[g] (S_g - s_i),   S_g = sum_{j in g} s_j.
+ * A replica keeps its spins as bits and the S_g as integers in LDS: a proposal reads the sums of the site's groups, an
+ * accept flips one bit and moves those sums; no coupling is read from HBM.  member_ptr [n_groups + 1], members, coeff
+ * [n_groups], h [n]: host or device arrays, not referenced after the call.  Groups of one member and sites in no
+ * group are legal (no coupling).
+ *   SGA_ERR_INVALID: a member outside [0, n), a site repeated inside one group, extents that are empty, not monotone or
+ *   do not start at 0.
+ *   SGA_ERR_UNSUPPORTED (sga_last_error says which; sga_set_csr on the materialised couplings serves them all):
+ *   - couplings not provably exact in fp32 in any order: every coeff[g] must be an integer multiple of one 2^-k with
+ *     2^k max_i sum_{g contains i} |coeff[g]| (|g| - 1) < 2^24 (the bound on sum_j |J_ij| that also bounds every partial
+ *     sum the kernel forms).  Under it the row sum equals the stored forms' fp32 row sum bit for bit, so the chain is
+ *     sga_set_csr's on the same couplings;
+ *   - a site in more than SGA_GROUPS_MAX_MEMBERSHIPS groups;
+ *   - spin bits and group sums beyond LDS (160 KiB: about 1.3e6 spins).
+ * sga_sweep (every single-site rule, site mode, arithmetic, trace), exchanges, energies, sga_local_fields, best
+ * tracking, export / import, the checksum, sga_describe ("groups ... path=groups acc=f32-exact") and the route calls
+ * work.  SGA_ERR_UNSUPPORTED: sga_flip, sga_update, the Wolff rule, sga_set_field_cache(ON) (AUTO runs the form as it
+ * is), sga_autotune. */
+#define SGA_GROUPS_MAX_MEMBERSHIPS 64
+int sga_set_groups(sga_engine *e, int n, int n_groups, const int64_t *member_ptr, const int32_t *members,
+                   const float *coeff, const float *h);
 
 /* ---- replicas ------------------------------------------------------------------------- */
 /* R_local replicas live on this engine; they are replicas [replica0, replica0+R_local) of a
@@ -472,9 +499,10 @@ int sga_get_autotune_table(sga_engine *e, char *buf, int buflen);
 #define SGA_ROUTE_DENSE 0
 #define SGA_ROUTE_CSR 1
 #define SGA_ROUTE_TSP 2
+#define SGA_ROUTE_GROUPS 3
 #define SGA_ROUTE_MAX_OPTS 32
 typedef struct sga_route_query {
-    int32_t kind;         /* SGA_ROUTE_DENSE | SGA_ROUTE_CSR | SGA_ROUTE_TSP (sga_set_tsp) */
+    int32_t kind;         /* SGA_ROUTE_DENSE | SGA_ROUTE_CSR | SGA_ROUTE_TSP (sga_set_tsp) | SGA_ROUTE_GROUPS (sga_set_groups) */
     int32_t n;            /* spins */
     int32_t n_models;     /* dense batches (sga_set_dense_batch), ragged CSR batches (sga_set_csr_batch), else 1 */
     int32_t R_local;      /* replicas on this engine (0: none yet) */
@@ -504,11 +532,15 @@ typedef struct sga_route_query {
     int32_t reserved_;
     int64_t ldj;          /* dense: row stride of the packed couplings in elements */
     int64_t opt[SGA_ROUTE_MAX_OPTS]; /* option values, index = sga_option_name order */
+    /* sga_set_groups (version >= 1000) */
+    int32_t n_groups;     /* groups */
+    int32_t group_max;    /* members of the largest group */
 } sga_route_query;
 /* zeroes *q and fills the option defaults (the environment is NOT consulted), cus = 256, n_models = 1 */
 int sga_route_query_init(sga_route_query *q);
 /* one line naming every decision for q: "dense storage=... waves=... chunks_per_wave=... kernel=..." |
- * "csr form=rows|narrow|narrow-bits|wide-bits|wide-bytes spins=... waves=... updates_per_step=..." | "tsp waves=... passes=..."
+ * "csr form=rows|narrow|narrow-bits|wide-bits|wide-bytes spins=... waves=... updates_per_step=..." | "tsp waves=... passes=..." |
+ * "groups n_groups=... sums=int16|int32 waves=... kernel=sweep_groups_kernel|sweep_groups_general_kernel"
  * followed by " cached=..." (what sga_set_field_cache would run).  Pure: no device needed. */
 int sga_explain_route(const sga_route_query *q, char *buf, int buflen);
 /* the query the engine itself would pose for its current problem / replicas / options */

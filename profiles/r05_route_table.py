@@ -21,7 +21,8 @@ sys.path.insert(0, ROOT)
 import spin_glass_anneal_rl_amd as sg  # noqa: E402
 from spin_glass_anneal_rl_amd import _native as N  # noqa: E402
 
-FIELDS = [f for f, _ in N.RouteQuery._fields_ if f not in ("opt", "reserved_")]
+# (n_groups / group_max: appended for sga_set_groups queries, 0 for every problem of this table -- dense, CSR, TSP)
+FIELDS = [f for f, _ in N.RouteQuery._fields_ if f not in ("opt", "reserved_", "n_groups", "group_max")]
 
 
 def query_dict(q):

@@ -20,8 +20,9 @@ RULE_METROPOLIS, RULE_GLAUBER, RULE_HEAT_BATH, RULE_WOLFF = 0, 1, 2, 3
 
 _p, _i, _i64, _u64, _u32, _d = C.c_void_p, C.c_int, C.c_int64, C.c_uint64, C.c_uint32, C.c_double
 
-ROUTE_DENSE, ROUTE_CSR, ROUTE_TSP = 0, 1, 2
+ROUTE_DENSE, ROUTE_CSR, ROUTE_TSP, ROUTE_GROUPS = 0, 1, 2, 3
 ROUTE_MAX_OPTS = 32
+GROUPS_MAX_MEMBERSHIPS = 64  # SGA_GROUPS_MAX_MEMBERSHIPS
 
 
 class RouteQuery(C.Structure):
@@ -31,7 +32,8 @@ class RouteQuery(C.Structure):
                                          "acc", "table_m", "table_scale", "clf_ok", "clf_bits", "clf_scale", "from_dense")] + \
                [("nnz", C.c_int64), ("max_row_len", C.c_int64), ("layout_entries", C.c_int64)] + \
                [(k, C.c_int32) for k in ("slotted", "rowptr32", "packed_ok", "n_cities", "sstride", "reserved_")] + \
-               [("ldj", C.c_int64), ("opt", C.c_int64 * ROUTE_MAX_OPTS)]
+               [("ldj", C.c_int64), ("opt", C.c_int64 * ROUTE_MAX_OPTS)] + \
+               [("n_groups", C.c_int32), ("group_max", C.c_int32)]
 
 
 # every symbol include/sga.h declares: (name, restype, argtypes)
@@ -53,6 +55,7 @@ SYMBOLS = [
     ("sga_set_csr_batch", _i, [_p, _i, _p, _p, _p, _p, _p, _i64]),
     ("sga_get_batch_model", _i, [_p, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
     ("sga_set_tsp", _i, [_p, _p, _i64, _i, C.c_float, C.c_float, _p]),
+    ("sga_set_groups", _i, [_p, _i, _i, _p, _p, _p, _p]),
     ("sga_init_replicas", _i, [_p, _i, _i, _i, _u64, _p]),
     ("sga_set_temperatures", _i, [_p, _p]),
     ("sga_set_ladder", _i, [_p, _p, _i]),

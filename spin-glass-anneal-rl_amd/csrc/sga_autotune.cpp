@@ -124,6 +124,8 @@ int sga_autotune(sga_engine *e, double *best_ms_per_sweep) {
     if (e->R <= 0) return fail(SGA_ERR_INVALID, "no replicas (call sga_init_replicas)");
     if (best_ms_per_sweep) *best_ms_per_sweep = 0.0;
     if (e->ragged) return fail(SGA_ERR_UNSUPPORTED, "sga_autotune: ragged CSR batches have one form (nothing to tune)");
+    if (e->groups)
+        return fail(SGA_ERR_UNSUPPORTED, "sga_autotune: sga_set_groups problems run one form (sga_set_tuning picks its waves per replica)");
     if (e->tsp) return SGA_OK;
     if (e->csr) return autotune_csr(e, best_ms_per_sweep);
     HIPCHK(hipSetDevice(e->device));

@@ -13,7 +13,7 @@ namespace sga_impl {
 sga_route_query route_query_of(const sga_engine *e) {
     sga_route_query q;
     (void)sga_route_query_init(&q);
-    q.kind = e->tsp ? SGA_ROUTE_TSP : (e->csr ? SGA_ROUTE_CSR : SGA_ROUTE_DENSE);
+    q.kind = e->groups ? SGA_ROUTE_GROUPS : e->tsp ? SGA_ROUTE_TSP : (e->csr ? SGA_ROUTE_CSR : SGA_ROUTE_DENSE);
     q.n = e->n;
     q.n_models = e->n_models;
     q.R_local = e->R;
@@ -36,7 +36,7 @@ sga_route_query route_query_of(const sga_engine *e) {
     // option "clf_fixed_point": CSR queries carry the width of the fixed-point fields (32 | 64; 16: the int16 form)
     if (e->csr && e->opt[OPT_CLF_FIXED_POINT] == 1) q.clf_bits = e->clf_fx_bits ? e->clf_fx_bits : 16;
     // ... dense queries whose problem the integer form does not take: 32 | 64, 0 = refused (sga_route.cpp, dense_fixed_point)
-    if (!e->csr && !e->tsp && e->opt[OPT_CLF_FIXED_POINT] == 1 && !e->clf_problem) q.clf_bits = e->clf_fx_bits;
+    if (!e->csr && !e->implicit() && e->opt[OPT_CLF_FIXED_POINT] == 1 && !e->clf_problem) q.clf_bits = e->clf_fx_bits;
     q.from_dense = e->from_dense ? 1 : 0;
     q.nnz = e->nnz;
     q.max_row_len = e->max_row_len;
@@ -45,6 +45,8 @@ sga_route_query route_query_of(const sga_engine *e) {
     q.rowptr32 = e->rowptr ? 1 : 0;
     q.packed_ok = e->cvp ? 1 : 0;
     q.n_cities = e->tsp ? e->tsp_args.n_cities : 0;
+    q.n_groups = e->groups ? e->group_args.n_groups : 0;
+    q.group_max = e->groups ? e->g_max_size : 0;
     q.sstride = e->sstride;
     q.ldj = e->ldj;
     for (int i = 0; i < OPT_COUNT; ++i) q.opt[i] = e->opt[i];
@@ -62,7 +64,7 @@ bool fields_pass_applies(const sga_engine *e, int count) {
     // together (sga_set_spins: one; a shard: R_local).
     const long long mode = e->opt[OPT_BATCHED_ENERGY];
     if (mode == 0 || (mode == 1 && e->acc_canon)) return false;
-    return !e->csr && !e->tsp && e->n_models == 1 && count >= 32 && e->J_packed;
+    return !e->csr && !e->implicit() && e->n_models == 1 && count >= 32 && e->J_packed;
 }
 // The pass writes Y = S J^T for the replicas it is given into a scratch buffer ([tile][ldj] int32 | fp32) before
 // the finish kernel reduces it.  The scratch is bounded: replica sets whose Y would exceed the cap go
@@ -124,7 +126,7 @@ int fields_pass(sga_engine *e, int r0, int count, double *energy, void *fields) 
 int row_shared_window(const sga_engine *e, bool lean) {
     const long long o = e->opt[OPT_ROW_SHARED];
     if (o == 0 || e->rs_suspend || !lean || e->rule != SGA_RULE_METROPOLIS || e->field_cache != SGA_FIELD_CACHE_OFF) return 0;
-    if (e->csr || e->tsp || e->ragged || e->n_models != 1 || e->table_m <= 0 || e->acc64 || !e->consistent_dE) return 0;
+    if (e->csr || e->implicit() || e->ragged || e->n_models != 1 || e->table_m <= 0 || e->acc64 || !e->consistent_dE) return 0;
     if (e->opt[OPT_LOOK_AHEAD] == 0 || e->opt[OPT_FORCE_GENERAL] != 0 || !e->J_packed) return 0;
     if (sga::row_shared_planes(e->j_abs_max) == 0 || (long long)e->R * e->n >= (1ll << 31) || e->R >= (1 << 20)) return 0;
     if (o == 2) return e->rs_tuned_w;
@@ -183,7 +185,7 @@ bool clf_possible(const sga_engine *e, const char **why) {
     // (option "clf_fixed_point": the set-time scan knows which condition failed; the query carries only the verdict)
     if (reason && !q.clf_ok && e->clf_fx_why && (!e->csr || q.n_models == 1)) reason = e->clf_fx_why;
     // (the integer form over dense couplings, likewise)
-    if (reason && !q.clf_ok && !e->csr && !e->tsp && e->clf_why && e->opt[OPT_CLF_FIXED_POINT] != 1) reason = e->clf_why;
+    if (reason && !q.clf_ok && !e->csr && !e->implicit() && e->clf_why && e->opt[OPT_CLF_FIXED_POINT] != 1) reason = e->clf_why;
     if (why) *why = reason;
     return reason == nullptr;
 }
@@ -266,7 +268,7 @@ int recompute_energy_range(sga_engine *e, int r0, int count) {
         HIPCHK(sga::launch_energy_csr_ragged(a, e->d_models, e->stream));
         return SGA_OK;
     }
-    if (e->csr && !e->tsp && count >= 64 && csr_all) {
+    if (e->csr && !e->implicit() && count >= 64 && csr_all) {
         // all replicas in one pass over the entries: spins transposed to bits, 32 replicas per lane
         // row groups: enough (group, replica word) threads to fill the chip -- ~4 waves per SIMD -- whatever
         // the replica count (256 replicas = 8 words: 4096 groups left half the SIMDs without a wave)
@@ -279,6 +281,20 @@ int recompute_energy_range(sga_engine *e, int r0, int count) {
             return SGA_OK;
         }
         (void)hipGetLastError();  // no room for the transposed spin bits / partial sums: one pass per replica instead
+    }
+    if (e->groups) {  // group sums from the spin bits, one workgroup per replica (sweep_groups.hip)
+        sga::EnergyArgs a{};
+        a.h = e->h;
+        a.spins = e->spins + (long long)r0 * e->sstride;
+        a.energy = e->energy + r0;
+        a.n = e->n;
+        a.sstride = e->sstride;
+        a.R = count;
+        a.block_rows = sga::energy_block_rows(e->n);
+        a.nblocks = (e->n + a.block_rows - 1) / a.block_rows;
+        a.slices = 1;
+        HIPCHK(sga::launch_energy_groups(a, e->group_args, e->stream));
+        return SGA_OK;
     }
     sga::EnergyArgs a{};
     a.J = e->J_packed;
@@ -302,7 +318,7 @@ int recompute_energy_range(sga_engine *e, int r0, int count) {
     // few replicas: spread each replica's blocks over several workgroups (one workgroup reading all
     // of J took 47 ms at n = 10^4 -- longer than the reference's CPU mv)
     // (then as few slices as take the same blocks each, none left without: whole passes of the bit-spin CSR kernel)
-    const int per_pass = e->csr && !e->tsp && sga::energy_csr_bits_form(e->sstride) ? sga::ENERGY_BITS_BLOCKS_PER_PASS : 1;
+    const int per_pass = e->csr && !e->implicit() && sga::energy_csr_bits_form(e->sstride) ? sga::ENERGY_BITS_BLOCKS_PER_PASS : 1;
     const int want = count >= 512 ? 1 : std::max(1, std::min({a.nblocks, (1024 + count - 1) / count, e->n / 8}));
     a.blocks_per_slice = ((a.nblocks + want - 1) / want + per_pass - 1) / per_pass * per_pass;
     a.slices = (a.nblocks + a.blocks_per_slice - 1) / a.blocks_per_slice;
@@ -325,7 +341,7 @@ int recompute_energy_range(sga_engine *e, int r0, int count) {
 // Launch geometry of the dense kernels for the current replica count / tuning (sga_route.cpp, dense_geometry).  The
 // packed matrices are laid out by n alone (pack_dense, at set time), so a change of geometry never touches them.
 int ensure_packed(sga_engine *e) {
-    if (e->csr || e->tsp) return SGA_OK;
+    if (e->csr || e->implicit()) return SGA_OK;
     if (!e->J_packed) return fail(SGA_ERR_INVALID, "no couplings set");
     const sga_route::DenseGeometry g = sga_route::dense_geometry(route_query_of(e));
     if (e->use_t2 ? (e->ld == g.ld && e->waves_t2 == g.waves_t2 && e->cpw_t2 == g.cpw_t2)
@@ -347,7 +363,7 @@ int ensure_packed(sga_engine *e) {
 extern "C" {
 
 const char *sga_last_error(void) { return g_last_error.c_str(); }
-int sga_version(void) { return 900; }  // + cached local fields for many-model dense batches (sga_set_dense_batch)  // 800: + option "clf_fixed_point" over dense couplings (sweep_clf_fx.hip)  // 700: + option "clf_fixed_point" (cached fields of real-valued CSR couplings)  // 600: + sga_set_csr_batch / sga_get_batch_model (ragged CSR batches)  // round 5: + sga_explain_route / sga_get_route_query, sga_get_last_kernel, sga_get_autotune_table, ladder-local sga_exchange
+int sga_version(void) { return 1000; }  // + sga_set_groups (implicit cardinality-group couplings, sweep_groups.hip)  // 900: + cached local fields for many-model dense batches (sga_set_dense_batch)  // 800: + option "clf_fixed_point" over dense couplings (sweep_clf_fx.hip)  // 700: + option "clf_fixed_point" (cached fields of real-valued CSR couplings)  // 600: + sga_set_csr_batch / sga_get_batch_model (ragged CSR batches)  // round 5: + sga_explain_route / sga_get_route_query, sga_get_last_kernel, sga_get_autotune_table, ladder-local sga_exchange
 
 int sga_create(int device, sga_engine **out) {
     if (!out) return fail(SGA_ERR_INVALID, "out is NULL");
@@ -533,7 +549,13 @@ static int init_replicas_body(sga_engine *e, int R_local, int R_global, int repl
     e->attempted = 0;
     // WHICH form the replicas are laid out for: sga_route.cpp (pure functions of the problem's traits, the replica count,
     // the tuning and the options; tests/test_host_logic.py pins them)
-    if (e->tsp) {
+    if (e->groups) {
+        const sga_route::GroupsForm f = sga_route::groups_form(route_query_of(e));
+        if (f.error) return fail(SGA_ERR_UNSUPPORTED, f.error);
+        e->sstride = f.sstride;
+        e->waves = f.waves;
+        e->cpw = 0;
+    } else if (e->tsp) {
         e->sstride = (e->n + 15) / 16 * 16;
         const sga_route::TspForm t = sga_route::tsp_form(e->tsp_args.npad, e->tune_waves);
         e->tsp_waves = t.waves;
@@ -698,7 +720,7 @@ int sga_sweep(sga_engine *e, int n_sweeps, int site_mode, int arith, const doubl
     HIPCHK(hipSetDevice(e->device));
     int rc = ensure_packed(e);
     if (rc != SGA_OK) return rc;
-    if (!e->csr && !e->tsp && e->sstride != (int)e->ld)
+    if (!e->csr && !e->implicit() && e->sstride != (int)e->ld)
         return fail(SGA_ERR_INVALID, "tuning changed after sga_init_replicas; re-initialise");
     // The cached-field modes pick their kernel form by the acceptance counters, looked at when a call starts: a long
     // production call is walked in pieces of 16 sweeps so that the form follows the run (the chain does not depend on
@@ -767,6 +789,7 @@ int sga_sweep(sga_engine *e, int n_sweeps, int site_mode, int arith, const doubl
     if (wolff) {
         if (e->ragged) return fail(SGA_ERR_UNSUPPORTED, "the Wolff rule is not implemented for ragged CSR batches");
         if (e->tsp) return fail(SGA_ERR_UNSUPPORTED, "the Wolff rule is not implemented for sga_set_tsp problems");
+        if (e->groups) return fail(SGA_ERR_UNSUPPORTED, "the Wolff rule is not implemented for sga_set_groups problems");
         if (sga::wolff_lds_bytes(n) > 160 * 1024 - 256)
             return fail(SGA_ERR_UNSUPPORTED, "the Wolff rule keeps spins, cluster and queue in LDS: n <= ~31 000");
         if (site_mode == SGA_SITE_SEQUENTIAL && !replay_u)
@@ -1152,6 +1175,9 @@ int sga_sweep(sga_engine *e, int n_sweeps, int site_mode, int arith, const doubl
         } else if (wolff) {
             const sga::WolffArgs wa{e->wolff_u, e->wolff_cap, e->wolff_cursor};
             le = sga::launch_sweep_wolff(a, wa, e->csr, e->want_i8, st);
+        } else if (e->groups) {
+            a.table_m = 0;
+            le = sga::launch_sweep_groups(a, e->group_args, e->waves, st);
         } else if (e->tsp) {
             a.table_m = 0;
             le = sga::launch_sweep_tsp(a, e->tsp_args, e->tsp_waves, e->tsp_passes, st);
@@ -1200,6 +1226,8 @@ int sga_set_update_rule(sga_engine *e, int rule) {
         return fail(SGA_ERR_UNSUPPORTED, "update rule not implemented by the engine");
     if (rule == SGA_RULE_WOLFF && e->tsp)
         return fail(SGA_ERR_UNSUPPORTED, "the Wolff rule is not implemented for sga_set_tsp problems");
+    if (rule == SGA_RULE_WOLFF && e->groups)
+        return fail(SGA_ERR_UNSUPPORTED, "the Wolff rule is not implemented for sga_set_groups problems");
     if (rule == SGA_RULE_WOLFF && e->ragged)
         return fail(SGA_ERR_UNSUPPORTED, "the Wolff rule is not implemented for ragged CSR batches");
     e->rule = rule;
@@ -1250,15 +1278,21 @@ static int point_op(sga_engine *e, int r, const int32_t *sites, int count, int o
         if (v < 0 || v >= n_r) return fail(SGA_ERR_INVALID, "site index out of range");
     if (op == 2 && e->rule == SGA_RULE_WOLFF)
         return fail(SGA_ERR_UNSUPPORTED, "sga_update applies single-site rules; Wolff moves run through sga_sweep");
-    if (e->tsp) {  // structured couplings: local fields only (flip / update go through sweeps)
+    if (e->implicit()) {  // structured couplings: local fields only (flip / update go through sweeps)
         if (op != 0)
-            return fail(SGA_ERR_UNSUPPORTED, "single-site flip / update are not implemented for sga_set_tsp problems");
+            return fail(SGA_ERR_UNSUPPORTED, e->groups ? "single-site flip / update are not implemented for sga_set_groups problems"
+                                                       : "single-site flip / update are not implemented for sga_set_tsp problems");
         HIPCHK(e->point_sites.reserve(sizeof(int32_t) * hs.size()));
         HIPCHK(e->point_out.reserve(sizeof(double) * (size_t)out_count));
         HIPCHK(hipMemcpyAsync(e->point_sites.ptr, hs.data(), sizeof(int32_t) * hs.size(), hipMemcpyHostToDevice, st));
-        HIPCHK(sga::launch_fields_tsp(e->tsp_args, e->spins + (long long)r * e->sstride, e->h,
-                                      static_cast<const int32_t *>(e->point_sites.ptr), count,
-                                      static_cast<double *>(e->point_out.ptr), st));
+        if (e->groups)
+            HIPCHK(sga::launch_fields_groups(e->group_args, e->spins + (long long)r * e->sstride, e->h,
+                                             static_cast<const int32_t *>(e->point_sites.ptr), count,
+                                             static_cast<double *>(e->point_out.ptr), st));
+        else
+            HIPCHK(sga::launch_fields_tsp(e->tsp_args, e->spins + (long long)r * e->sstride, e->h,
+                                          static_cast<const int32_t *>(e->point_sites.ptr), count,
+                                          static_cast<double *>(e->point_out.ptr), st));
         HIPCHK(hipMemcpyAsync(out_host, e->point_out.ptr, sizeof(double) * (size_t)out_count, hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
         return SGA_OK;

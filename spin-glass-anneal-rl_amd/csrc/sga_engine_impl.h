@@ -174,6 +174,16 @@ struct sga_engine {
     float *nd4 = nullptr, *nd4t = nullptr;
     sga::TspArgs tsp_args{};
     int tsp_waves = 0, tsp_passes = 0;
+    // couplings as a sum of complete graphs on groups, never stored (sga_set_groups): site -> group table, group -> members
+    bool groups = false;
+    int *g_gptr = nullptr, *g_members = nullptr;
+    int2 *g_gent = nullptr;
+    long long *g_member_ptr = nullptr;
+    float *g_coeff = nullptr;  // [n_groups] as handed over (checksum)
+    long long g_memberships = 0;  // entries of the site -> group table
+    int g_max_size = 0, g_kmax = 0, g_exp = 0;  // largest group, most memberships of one site, k of the 2^-k grid
+    sga::GroupArgs group_args{};
+    bool implicit() const { return tsp || groups; }  // structured couplings, none stored
     double *epart = nullptr;  // per-slice energy sums (few replicas)
     size_t epart_bytes = 0;
     int tune_waves = 0, tune_spl = 0;
@@ -302,6 +312,13 @@ struct sga_engine {
         clf_fx_k = 0;
         clf_fx_why = nullptr;
         tsp = false;
+        dev_free(g_gptr);
+        dev_free(g_members);
+        dev_free(g_gent);
+        dev_free(g_member_ptr);
+        dev_free(g_coeff);
+        groups = false;
+        group_args = sga::GroupArgs{};
         dev_free(epart);
         epart_bytes = 0;
         clf_problem = false;

@@ -111,6 +111,20 @@ struct TspArgs {
 };
 size_t tsp_lds_bytes(int n_cities, int npad);
 
+// Couplings that are a sum of complete graphs on groups of sites, never stored (sweep_groups.hip, sga_set_groups)
+struct GroupArgs {
+    const int *gptr;              // [n + 1] site -> its memberships
+    const int2 *gent;             // [gptr[n]] (group, coefficient bits) interleaved; never empty (one zero entry at least)
+    const long long *member_ptr;  // [n_groups + 1] group -> its members
+    const int *members;
+    int n_groups;                 // >= 1
+    int wide;                     // 0: S_g as int16 in LDS (every group below 2^15 members) | 1: int32
+};
+constexpr int GROUPS_MAX_MEMBERSHIPS = 64;  // groups one site may belong to (include/sga.h)
+size_t groups_lds_bytes(int sstride, int n_groups, int wide);
+size_t groups_energy_lds_bytes(int sstride, int n_groups, int wide);
+hipError_t launch_sweep_groups(const SweepArgs &a, const GroupArgs &g, int waves, hipStream_t st);
+
 // Wolff cluster rule (sweep_wolff.hip): recorded uniforms for the parity tests (null: Philox)
 struct WolffArgs {
     const float *replay_u;   // [R][capacity], consumed in draw order from cursor[r]
@@ -254,6 +268,9 @@ hipError_t launch_sweep_tsp(const SweepArgs &a, const TspArgs &t, int waves, int
 hipError_t launch_energy_tsp(const EnergyArgs &a, const TspArgs &t, hipStream_t st);
 hipError_t launch_fields_tsp(const TspArgs &t, const int8_t *spins, const float *h, const int32_t *sites,
                              int count, double *out, hipStream_t st);
+hipError_t launch_energy_groups(const EnergyArgs &a, const GroupArgs &g, hipStream_t st);
+hipError_t launch_fields_groups(const GroupArgs &g, const int8_t *spins, const float *h, const int32_t *sites, int count,
+                                double *out, hipStream_t st);
 hipError_t launch_tsp_tables(const float *d, long long ldd, int n, int npad, float *nd4, float *nd4t,
                              hipStream_t st);
 int csr_waves_per_block(int sstride, int table_m);  // replicas per workgroup that fit LDS (0: none)

@@ -676,6 +676,139 @@ int sga_set_tsp(sga_engine *e, const float *dist, int64_t ld, int n_cities, floa
     return SGA_OK;
 }
 
+// Couplings as a sum of complete graphs on groups, never stored (sweep_groups.hip).  Everything is checked on the host
+// (the tables are a few bytes per membership): structure, then the proof that a row sum is exact in fp32 in any order.
+int sga_set_groups(sga_engine *e, int n, int n_groups, const int64_t *member_ptr, const int32_t *members, const float *coeff,
+                   const float *h) {
+    if (!e) return fail(SGA_ERR_INVALID, "engine is NULL");
+    if (n <= 0 || !h) return fail(SGA_ERR_INVALID, "bad group problem arguments");
+    if (n_groups <= 0 || !member_ptr || !coeff) return fail(SGA_ERR_INVALID, "sga_set_groups: the extent table is empty (no groups)");
+    HIPCHK(hipSetDevice(e->device));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    e->free_replicas();
+    e->free_problem();
+    e->opt_stale = 0;
+    const size_t G = (size_t)n_groups;
+    std::vector<long long> mp(G + 1);
+    std::vector<float> cf(G), hh((size_t)n);
+    HIPCHK(hipMemcpy(mp.data(), member_ptr, sizeof(long long) * (G + 1), hipMemcpyDefault));
+    HIPCHK(hipMemcpy(cf.data(), coeff, sizeof(float) * G, hipMemcpyDefault));
+    HIPCHK(hipMemcpy(hh.data(), h, sizeof(float) * (size_t)n, hipMemcpyDefault));
+    if (mp[0] != 0) return fail(SGA_ERR_INVALID, "sga_set_groups: member_ptr[0] != 0");
+    for (size_t q = 0; q < G; ++q)
+        if (mp[q + 1] < mp[q]) return fail(SGA_ERR_INVALID, "sga_set_groups: member_ptr is not monotone at group " + std::to_string(q));
+    const long long M = mp[G];
+    if (M >= (long long)INT32_MAX) return fail(SGA_ERR_UNSUPPORTED, "sga_set_groups: 2^31 memberships or more (use sga_set_csr)");
+    if (M > 0 && !members) return fail(SGA_ERR_INVALID, "bad group problem arguments");
+    std::vector<int32_t> mem((size_t)std::max<long long>(M, 1), 0);
+    if (M > 0) HIPCHK(hipMemcpy(mem.data(), members, sizeof(int32_t) * (size_t)M, hipMemcpyDefault));
+    // structure: members in range, no site twice in a group; memberships per site
+    std::vector<int> count((size_t)n + 1, 0), seen((size_t)n, -1);
+    long long max_size = 0;
+    for (size_t q = 0; q < G; ++q) {
+        if (!std::isfinite(cf[q])) return fail(SGA_ERR_INVALID, "sga_set_groups: coefficient of group " + std::to_string(q) + " is not finite");
+        max_size = std::max(max_size, mp[q + 1] - mp[q]);
+        for (long long m = mp[q]; m < mp[q + 1]; ++m) {
+            const int i = mem[(size_t)m];
+            if (i < 0 || i >= n)
+                return fail(SGA_ERR_INVALID, "sga_set_groups: member " + std::to_string(i) + " of group " + std::to_string(q) +
+                                                 " is out of range [0, " + std::to_string(n) + ")");
+            if (seen[(size_t)i] == (int)q)
+                return fail(SGA_ERR_INVALID, "sga_set_groups: site " + std::to_string(i) + " is repeated inside group " + std::to_string(q));
+            seen[(size_t)i] = (int)q;
+            ++count[(size_t)i + 1];
+        }
+    }
+    // the fp32-exact class: every coefficient on one grid 2^-k, 2^k max_i sum_{g contains i} |c_g| (|g| - 1) < 2^24
+    int k = -1000;  // the finest grid any coefficient needs: c = m 2^(ex - 24), lowest set bit at ex - 24 + low
+    for (size_t q = 0; q < G; ++q) {
+        if (cf[q] == 0.0f || mp[q + 1] - mp[q] < 2) continue;  // (contributes no coupling)
+        int ex;
+        const float m = std::frexp(std::fabs(cf[q]), &ex);
+        uint32_t mant = (uint32_t)std::ldexp(m, 24);
+        int low = 0;
+        while (!(mant & 1u)) {
+            mant >>= 1;
+            ++low;
+        }
+        k = std::max(k, -(ex - 24 + low));
+    }
+    if (k == -1000) k = 0;
+    std::vector<double> bound((size_t)n, 0.0);
+    int kmax = 0;
+    for (size_t q = 0; q < G; ++q) {
+        const double term = std::fabs((double)cf[q]) * (double)(mp[q + 1] - mp[q] - 1);
+        for (long long m = mp[q]; m < mp[q + 1]; ++m) bound[(size_t)mem[(size_t)m]] += term;
+    }
+    double worst = 0.0;
+    for (int i = 0; i < n; ++i) {
+        worst = std::max(worst, bound[(size_t)i]);
+        kmax = std::max(kmax, count[(size_t)i + 1]);
+    }
+    if (k > 126 || std::ldexp(worst, k) >= 16777216.0) {
+        char msg[320];
+        std::snprintf(msg, sizeof(msg),
+                      "sga_set_groups: the couplings are not provably exact in fp32: the coefficients lie on the grid 2^%d and "
+                      "max_i sum_j |J_ij| = %.6g of its units is not below 2^24 -- materialise them and use sga_set_csr", -k,
+                      std::ldexp(worst, std::min(k, 126)));
+        return fail(SGA_ERR_UNSUPPORTED, msg);
+    }
+    if (kmax > SGA_GROUPS_MAX_MEMBERSHIPS) {
+        char msg[256];
+        std::snprintf(msg, sizeof(msg), "sga_set_groups: a site belongs to %d groups, more than SGA_GROUPS_MAX_MEMBERSHIPS = %d -- "
+                      "materialise the couplings and use sga_set_csr", kmax, SGA_GROUPS_MAX_MEMBERSHIPS);
+        return fail(SGA_ERR_UNSUPPORTED, msg);
+    }
+    {
+        sga_route_query q;
+        (void)sga_route_query_init(&q);
+        q.kind = SGA_ROUTE_GROUPS;
+        q.n = n;
+        q.n_groups = n_groups;
+        q.group_max = (int32_t)max_size;
+        const sga_route::GroupsForm f = sga_route::groups_form(q);
+        if (f.error) return fail(SGA_ERR_UNSUPPORTED, std::string("sga_set_groups: ") + f.error + " -- use sga_set_csr");
+    }
+    // site -> group table, groups of a site in group order; one zero entry behind (the kernels' padding entry)
+    std::vector<int> gptr((size_t)n + 1, 0);
+    for (int i = 0; i < n; ++i) gptr[(size_t)i + 1] = gptr[(size_t)i] + count[(size_t)i + 1];
+    std::vector<int2> gent((size_t)M + 1, make_int2(0, 0));
+    std::vector<int> cur(gptr.begin(), gptr.end() - 1);
+    for (size_t q = 0; q < G; ++q) {
+        int cbits;
+        std::memcpy(&cbits, &cf[q], sizeof(cbits));
+        for (long long m = mp[q]; m < mp[q + 1]; ++m) gent[(size_t)cur[(size_t)mem[(size_t)m]]++] = make_int2((int)q, cbits);
+    }
+    HIPCHK(hipMalloc(&e->g_gptr, sizeof(int) * ((size_t)n + 1)));
+    HIPCHK(hipMalloc(&e->g_gent, sizeof(int2) * ((size_t)M + 1)));
+    HIPCHK(hipMalloc(&e->g_member_ptr, sizeof(long long) * (G + 1)));
+    HIPCHK(hipMalloc(&e->g_members, sizeof(int) * (size_t)std::max<long long>(M, 1)));
+    HIPCHK(hipMalloc(&e->g_coeff, sizeof(float) * G));
+    HIPCHK(hipMalloc(&e->h, sizeof(float) * (size_t)n));
+    HIPCHK(hipMemcpyAsync(e->g_gptr, gptr.data(), sizeof(int) * ((size_t)n + 1), hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemcpyAsync(e->g_gent, gent.data(), sizeof(int2) * ((size_t)M + 1), hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemcpyAsync(e->g_member_ptr, mp.data(), sizeof(long long) * (G + 1), hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemcpyAsync(e->g_members, mem.data(), sizeof(int) * mem.size(), hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemcpyAsync(e->g_coeff, cf.data(), sizeof(float) * G, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemcpyAsync(e->h, hh.data(), sizeof(float) * (size_t)n, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    e->groups = true;
+    e->csr = false;
+    e->n = n;
+    e->n_models = 1;
+    long long pairs = 0;
+    for (size_t q = 0; q < G; ++q) pairs += (mp[q + 1] - mp[q]) * (mp[q + 1] - mp[q] - 1);
+    e->nnz = pairs;  // entries of the materialised couplings, overlaps counted once per group
+    e->consistent_dE = true;  // symmetric with a zero diagonal by construction
+    e->table_m = 0;
+    e->g_memberships = M;
+    e->g_max_size = (int)max_size;
+    e->g_kmax = kmax;
+    e->g_exp = k;
+    e->group_args = sga::GroupArgs{e->g_gptr, e->g_gent, e->g_member_ptr, e->g_members, n_groups, max_size >= (1 << 15) ? 1 : 0};
+    return SGA_OK;
+}
+
 // Ragged CSR batches: M independent problems of any sizes in one engine, their rows concatenated (model m owns rows
 // [row0_m, row0_m + n_m), its columns model-local).  Each model gets sga_set_csr's structure checks -- the same scan
 // kernels over the model's rows (extents offset to its first row, columns bounded by its n) -- and its own class;

@@ -307,6 +307,27 @@ TspForm tsp_form(int npad, int tune_waves) {
     return t;
 }
 
+// ---- couplings as a sum of complete graphs on groups ---------------------------------------------------------------------
+// One wave decides 128 proposals per round, and a round costs the same whatever the number of waves beside it, so a
+// replica gets as many waves as leave every CU its share of replicas at four waves per SIMD (16 per CU): 1024 replicas
+// on 256 CUs = 4 waves each.  Tuning (sga_set_tuning waves_per_replica = 1 | 2 | 4 | 8) overrides.
+GroupsForm groups_form(const Query &q) {
+    GroupsForm f;
+    f.sstride = (int)(((long long)q.n + 127) / 128 * 128);
+    f.wide = q.group_max >= (1 << 15);
+    f.lds_bytes = std::max(sga::groups_lds_bytes(f.sstride, std::max(q.n_groups, 1), f.wide ? 1 : 0),
+                           sga::groups_energy_lds_bytes(f.sstride, std::max(q.n_groups, 1), f.wide ? 1 : 0));
+    if (f.lds_bytes > 160 * 1024 - 256) f.error = "spin bits and group sums of a replica do not fit LDS (160 KiB)";
+    const long long windows = ((long long)q.n + 127) / 128;  // 128 proposals per wave and round
+    const int per_cu = (std::max(q.R_local, 1) + std::max(q.cus, 1) - 1) / std::max(q.cus, 1);
+    int w = 16 / std::max(per_cu, 1);
+    w = w >= 8 ? 8 : w >= 4 ? 4 : w >= 2 ? 2 : 1;
+    while (w > 1 && w > windows) w >>= 1;
+    if (q.tune_waves == 1 || q.tune_waves == 2 || q.tune_waves == 4 || q.tune_waves == 8) w = q.tune_waves;
+    f.waves = w;
+    return f;
+}
+
 // ---- cached local fields ----------------------------------------------------------------------------------------------------
 // A dense query under option "clf_fixed_point" = 1 whose problem the integer form does not take (clf_ok = 0) carries the
 // fixed-point form in clf_bits: 32 | 64 = the width of its fields, 0 = the set-time scan refused it (acc = 2: the
@@ -318,6 +339,9 @@ bool dense_fixed_point(const Query &q) {
 // qualifies over all its stacked rows) whose fields and spin bits fit LDS, and CSR problems with integer J in strictly sorted rows -- any single-site rule.
 const char *clf_refusal(const Query &q) {
     if (q.kind == SGA_ROUTE_TSP) return "cached local fields: stored couplings only";
+    if (q.kind == SGA_ROUTE_GROUPS)
+        return "cached local fields: stored couplings only (sga_set_groups keeps the group sums resident instead; AUTO runs "
+               "that form as it is)";
     if (q.kind == SGA_ROUTE_CSR && q.n_models > 1)
         return "cached local fields: not built for ragged CSR batches (sga_set_csr_batch runs the streaming narrow form)";
     if (q.kind == SGA_ROUTE_CSR) {
@@ -442,7 +466,8 @@ int clf_csr_waves(const Query &q) {
 int sweeps_per_launch(const Query &q, int n_sweeps, int tune_spl, int npad_tsp) {
     int spl = tune_spl;
     if (spl <= 0) {
-        const double row_bytes = q.kind == SGA_ROUTE_TSP ? 8.0 * npad_tsp
+        const double row_bytes = q.kind == SGA_ROUTE_GROUPS ? 64.0  // (no row: a few table entries per proposal)
+                                 : q.kind == SGA_ROUTE_TSP ? 8.0 * npad_tsp
                                  : q.kind == SGA_ROUTE_CSR ? 264.0 : (double)dense_ldj(q) * (is_i8(q) ? 1 : 4);
         const double per_update = std::max(row_bytes * q.R_local / 4.0e12, 1.0e-6);
         const double per_sweep = per_update * q.n;
@@ -456,7 +481,16 @@ std::string explain(const Query &q0) {
     Query q = q0;
     char buf[640];
     std::string out;
-    if (q.kind == SGA_ROUTE_TSP) {
+    if (q.kind == SGA_ROUTE_GROUPS) {
+        const GroupsForm f = groups_form(q);
+        if (f.error) return std::string("groups error=") + f.error;
+        const bool general = q.opt[OPT_FORCE_GENERAL] != 0;
+        std::snprintf(buf, sizeof(buf), "groups n_groups=%d largest_group=%d sums=%s waves=%d sstride=%d lds_bytes=%zu kernel=%s",
+                      q.n_groups, q.group_max, f.wide ? "int32" : "int16", general ? 1 : f.waves, f.sstride, f.lds_bytes,
+                      general ? "sweep_groups_general_kernel" : "sweep_groups_kernel|sweep_groups_general_kernel");
+        out = buf;
+        q.sstride = f.sstride;
+    } else if (q.kind == SGA_ROUTE_TSP) {
         const int npad = 256 * ((q.n_cities + 255) / 256);
         const TspForm t = tsp_form(npad, q.tune_waves);
         std::snprintf(buf, sizeof(buf), "tsp n_cities=%d waves=%d passes=%d updates_per_step_option=%lld kernel=%s", q.n_cities,
@@ -566,7 +600,8 @@ int sga_route_query_init(sga_route_query *q) {
 
 int sga_explain_route(const sga_route_query *q, char *buf, int buflen) {
     if (!q || !buf || buflen <= 0) return sga_impl::fail(SGA_ERR_INVALID, "bad arguments");
-    if (q->n <= 0 || q->kind < SGA_ROUTE_DENSE || q->kind > SGA_ROUTE_TSP || (q->kind == SGA_ROUTE_TSP && q->n_cities < 3))
+    if (q->n <= 0 || q->kind < SGA_ROUTE_DENSE || q->kind > SGA_ROUTE_GROUPS || (q->kind == SGA_ROUTE_TSP && q->n_cities < 3) ||
+        (q->kind == SGA_ROUTE_GROUPS && q->n_groups < 1))
         return sga_impl::fail(SGA_ERR_INVALID, "route query: kind / n out of range");
     std::snprintf(buf, (size_t)buflen, "%s", sga_route::explain(*q).c_str());
     return SGA_OK;

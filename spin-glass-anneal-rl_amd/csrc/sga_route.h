@@ -121,6 +121,16 @@ struct TspForm {
 };
 TspForm tsp_form(int npad, int tune_waves);
 
+// ---- couplings as a sum of complete graphs on groups (sga_set_groups) ---------------------------------------------
+struct GroupsForm {
+    int waves = 1;            // waves per replica of the production form (the general form runs one)
+    int sstride = 0;
+    bool wide = false;        // group sums as int32 (a group of 2^15 members or more)
+    size_t lds_bytes = 0;
+    const char *error = nullptr;  // spin bits and group sums do not fit LDS
+};
+GroupsForm groups_form(const Query &q);
+
 // ---- cached local fields (sga_set_field_cache) ------------------------------------------------------------------------
 // nullptr when the cached-field sweep can serve q (with q.sstride / q.ldj as laid out), else the reason
 const char *clf_refusal(const Query &q);

@@ -336,7 +336,16 @@ int sga_get_kernel_time(sga_engine *e, int64_t *n_launches, double *total_ms, in
 int sga_describe(sga_engine *e, char *buf, int buflen) {
     if (!e || !buf || buflen <= 0) return fail(SGA_ERR_INVALID, "bad arguments");
     char tmp[512];
-    if (e->tsp)
+    if (e->groups)
+        std::snprintf(tmp, sizeof(tmp),
+                      "groups n=%d n_groups=%d largest_group=%d memberships=%lld max_memberships=%d R=%d waves_per_replica=%d "
+                      "sstride=%d path=groups couplings=implicit (group sums as %s in LDS, 0 coupling bytes per proposal) "
+                      "acc=f32-exact grid=2^%d lds_bytes=%zu",
+                      e->n, e->group_args.n_groups, e->g_max_size, e->g_memberships, e->g_kmax, e->R, e->waves, e->sstride,
+                      e->group_args.wide ? "int32" : "int16", -e->g_exp,
+                      sga::groups_lds_bytes(e->sstride > 0 ? e->sstride : (e->n + 127) / 128 * 128, e->group_args.n_groups,
+                                            e->group_args.wide));
+    else if (e->tsp)
         std::snprintf(tmp, sizeof(tmp),
                       "tsp n_cities=%d n=%d R=%d waves_per_replica=%d passes=%d couplings=implicit "
                       "(2 x %d-byte distance rows per update) acc=%s lds_bytes=%zu",
@@ -383,7 +392,7 @@ int sga_describe(sga_engine *e, char *buf, int buflen) {
                                                   e->use_t2 ? e->cpw_t2 : e->cpw,
                                                   e->use_t2 ? e->waves_t2 : e->waves, e->R)
                           : 1);
-    if (!e->csr && !e->tsp && e->field_cache == SGA_FIELD_CACHE_OFF) {  // production sweeps in row-shared windows
+    if (!e->csr && !e->implicit() && e->field_cache == SGA_FIELD_CACHE_OFF) {  // production sweeps in row-shared windows
         const int rw = row_shared_window(e, true);
         if (rw > 0) {
             const int pl = sga::row_shared_planes(e->j_abs_max);
@@ -462,7 +471,12 @@ int sga_problem_checksum(sga_engine *e, uint64_t *out) {
     unsigned long long *d = static_cast<unsigned long long *>(e->point_out.ptr);
     HIPCHK(hipMemsetAsync(d, 0, 2 * sizeof(unsigned long long), e->stream));
     // what the sweep kernels read: the packed matrix | the entry layout | the distance tables; then h
-    if (e->tsp) {
+    if (e->groups) {  // extents, members, coefficients (h below)
+        const int G = e->group_args.n_groups;
+        HIPCHK(sga::launch_checksum(e->g_member_ptr, 8ll * (G + 1), d, e->stream));
+        if (e->g_memberships > 0) HIPCHK(sga::launch_checksum(e->g_members, 4ll * e->g_memberships, d, e->stream));
+        HIPCHK(sga::launch_checksum(e->g_coeff, 4ll * G, d, e->stream));
+    } else if (e->tsp) {
         const long long bytes = 4ll * e->tsp_args.n_cities * e->tsp_args.npad;
         HIPCHK(sga::launch_checksum(e->nd4, bytes, d, e->stream));
         HIPCHK(sga::launch_checksum(e->nd4t, bytes, d, e->stream));
@@ -475,7 +489,7 @@ int sga_problem_checksum(sga_engine *e, uint64_t *out) {
         HIPCHK(sga::launch_checksum(e->J_packed, (long long)e->n_models * e->n * e->ldj * (e->want_i8 ? 1 : 4), d,
                                     e->stream));
     }
-    HIPCHK(sga::launch_checksum(e->h, e->ragged ? 4ll * e->n_rows : 4ll * e->n * (e->tsp ? 1 : e->n_models), d + 1, e->stream));
+    HIPCHK(sga::launch_checksum(e->h, e->ragged ? 4ll * e->n_rows : 4ll * e->n * (e->implicit() ? 1 : e->n_models), d + 1, e->stream));
     unsigned long long host[2] = {0, 0};
     HIPCHK(hipMemcpyAsync(host, d, sizeof(host), hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
@@ -485,8 +499,8 @@ int sga_problem_checksum(sga_engine *e, uint64_t *out) {
 
 int sga_get_geometry(sga_engine *e, int *waves_per_replica, int *chunks_per_wave) {
     if (!e) return fail(SGA_ERR_INVALID, "engine is NULL");
-    if (waves_per_replica) *waves_per_replica = (!e->csr && !e->tsp && e->use_t2) ? e->waves_t2 : e->waves;
-    if (chunks_per_wave) *chunks_per_wave = (!e->csr && !e->tsp && e->use_t2) ? e->cpw_t2 : e->cpw;
+    if (waves_per_replica) *waves_per_replica = (!e->csr && !e->implicit() && e->use_t2) ? e->waves_t2 : e->waves;
+    if (chunks_per_wave) *chunks_per_wave = (!e->csr && !e->implicit() && e->use_t2) ? e->cpw_t2 : e->cpw;
     return SGA_OK;
 }
 

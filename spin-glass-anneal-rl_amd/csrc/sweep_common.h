@@ -128,6 +128,12 @@ struct PairSource {
     }
 };
 
+// Philox block b of sweep k of local replica r, the coordinates of every sweep form (fetch_pair): words (site A, u A,
+// site B, u B) of updates 2 b and 2 b + 1.  For forms whose lanes each hold a block of their own.
+__device__ __forceinline__ u32x4 sweep_block(const SweepArgs &a, int r, int k, uint32_t b) {
+    return philox4x32_10(b, a.sweep0 + (uint32_t)k, a.replica0 + (uint32_t)r, DOMAIN_SWEEP, a.seed_lo, a.seed_hi);
+}
+
 // The accept rule.  dot = fp32 coupling dot product J[site,:].s (already rounded to fp32),
 // si = s[site] (+-1).  Returns true if the spin flips; dE receives the energy change of the
 // flip.

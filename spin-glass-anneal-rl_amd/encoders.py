@@ -34,6 +34,8 @@ class IsingBuilder:
         self.h = np.zeros(self.n, np.float64)
         self.constant = 0.0
         self._rows, self._cols, self._vals = [], [], []
+        self._groups, self._group_coeff = [], []  # what add_cardinality_groups added, group by group
+        self._group_blocks = 0                    # ... and how many of the coupling blocks are theirs
 
     # ------------------------------------------------------------------ raw terms
     def add_field(self, idx, coeff) -> None:
@@ -91,6 +93,9 @@ class IsingBuilder:
             self.add_field(g.ravel(), np.full(g.size, 2.0 * w * target))
             self.add_coupling(g[:, a].ravel(), g[:, b].ravel(), -2.0 * w)
             self.constant += G * w * (m + target * target)
+        self._groups.extend(np.ascontiguousarray(g))
+        self._group_coeff.extend([(2.0 if self.convention == "reference" else -2.0) * w] * G)
+        self._group_blocks += 1
 
     def add_qubo_pair(self, a, b, q) -> None:
         """Objective term q * x_a x_b with x = (1+s)/2 (physical convention only)."""
@@ -143,6 +148,21 @@ class IsingBuilder:
         full.sort_indices()
         return (full.indptr.astype(np.int32), full.indices.astype(np.int32),
                 full.data.astype(np.float32))
+
+    def group_structure(self):
+        """(member_ptr int64 [G + 1], members int32, coeff fp32 [G], h fp32 [n], constant): the couplings as a sum of
+        complete graphs on groups -- J_ij = sum of coeff[g] over the groups holding i and j, here coeff = -weight / 2 --
+        for `AnnealEngine.set_groups`, which sweeps them without storing J.  Raises if any coupling of the builder did
+        not come from `add_cardinality_groups` (add_coupling, add_qubo_pair, add_equality / add_cardinality), or in the
+        reference / overwrite convention (whose couplings are not this sum)."""
+        if self.convention != "physical" or self.overwrite:
+            raise ValueError("group_structure is defined for the physical convention without overwrite")
+        if len(self._rows) != self._group_blocks:
+            raise ValueError("the builder holds couplings that did not come from add_cardinality_groups")
+        sizes = np.array([g.size for g in self._groups], np.int64)
+        member_ptr = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+        members = (np.concatenate(self._groups) if self._groups else np.zeros(0)).astype(np.int32)
+        return member_ptr, members, np.asarray(self._group_coeff, np.float32), self.fields(), self.constant
 
     def to_dense(self) -> np.ndarray:
         r, c, v = self._triples()
@@ -384,6 +404,27 @@ def assignment_ising(n_agents: int, n_tasks: int, weight: float = 100.0, costs=N
         else:
             b.add_qubo_linear(np.arange(c.size), c)
     return b
+
+
+def assignment_groups(n_agents: int, n_tasks: int, weight: float = 100.0, costs=None):
+    """`assignment_ising(...)` as groups: (n, member_ptr, members, coeff, h, constant) for `AnnealEngine.set_groups`."""
+    b = assignment_ising(n_agents, n_tasks, weight, costs)
+    return (b.n,) + b.group_structure()
+
+
+def scheduling_groups(durations: Sequence[float], n_agents: int, time_horizon: int, time_discretization: int,
+                      due_dates: Optional[Sequence[float]] = None, priorities: Optional[Sequence[float]] = None,
+                      objective: str = "makespan", penalty_weights: Optional[Dict[str, float]] = None):
+    """`scheduling_ising(...)` without precedence terms as groups: (n, member_ptr, members, coeff, h, constant).
+    `penalty_weights` defaults to assignment 100, capacity 50 (and time_window 60 where due dates are given); a
+    "precedence" weight is refused -- those couplings are no cardinality groups."""
+    if penalty_weights is None:
+        penalty_weights = {"assignment": 100.0, "capacity": 50.0, "time_window": 60.0}
+    if "precedence" in penalty_weights:
+        raise ValueError("scheduling_groups serves instances without precedence terms")
+    b = scheduling_ising(durations, n_agents, time_horizon, time_discretization, due_dates, priorities, objective,
+                         penalty_weights)
+    return (b.n,) + b.group_structure()
 
 
 def evaluate_penalties(spins, terms: Iterable[Tuple[str, tuple]]) -> float:

@@ -355,6 +355,32 @@ class AnnealEngine:
         self._sizes = None
         self.n, self.R, self.n_models = n * n, 0, 1
 
+    def set_groups(self, n: int, groups, coeff, h):
+        """Couplings that are a sum of complete graphs on groups of sites, never stored (see sga_set_groups):
+        J_ij = sum of coeff[g] over the groups that hold both i and j.  `groups` is a list of index arrays or a
+        tuple (member_ptr int64 [G + 1], members int32); `coeff` [G] and `h` [n] float32; numpy or torch device
+        tensors (`encoders.assignment_groups` / `scheduling_groups` / `IsingBuilder.group_structure` return them)."""
+        if isinstance(groups, tuple) and len(groups) == 2:  # (a LIST of two index arrays is two groups)
+            member_ptr, members = groups
+        else:
+            rows = [np.asarray(g, np.int32).ravel() for g in groups]
+            member_ptr = np.concatenate([[0], np.cumsum([r.size for r in rows])]).astype(np.int64)
+            members = np.concatenate(rows).astype(np.int32) if rows else np.zeros(0, np.int32)
+        mp, k1 = _buf(member_ptr, np.int64, "int64")
+        mm, k2 = _buf(members, np.int32, "int32")
+        cp, k3 = _buf(coeff, np.float32, "float32")
+        hp, k4 = _buf(h, np.float32, "float32")
+        size = lambda k: 0 if k is None else (k.numel() if _is_tensor(k) else k.size)  # noqa: E731
+        G = size(k1) - 1
+        if size(k3) != G:
+            raise AnnealingError("one coefficient per group")
+        if size(k4) != int(n):
+            raise AnnealingError("external fields must have n entries")
+        N.check(self._lib.sga_set_groups(self._h, int(n), int(G), mp, mm, cp, hp), "sga_set_groups")
+        del k1, k2, k3, k4
+        self._sizes = None
+        self.n, self.R, self.n_models = int(n), 0, 1
+
     # ------------------------------------------------------------------ replicas
     def init_replicas(self, R: int, seed: int = 0, s0=None, R_global: Optional[int] = None,
                       replica0: int = 0):
