@@ -80,7 +80,7 @@ typedef struct sga_engine sga_engine;
 int sga_create(int device, sga_engine **out);
 void sga_destroy(sga_engine *e);
 const char *sga_last_error(void);
-int sga_version(void);  /* 1000: sga_set_groups (implicit cardinality-group couplings) */
+int sga_version(void);  /* 1100: option "ragged_field_cache" (cached local fields for ragged CSR batches); 1000: sga_set_groups */
 /* Run on an existing HIP stream (e.g. torch.cuda.current_stream().cuda_stream); NULL = the
  * engine's own stream (default). */
 int sga_set_stream(sga_engine *e, void *hip_stream);
@@ -137,9 +137,18 @@ int sga_set_csr64(sga_engine *e, const int64_t *rowptr, const int32_t *colidx, c
  *   Everything sga_sweep does (rules, site modes, traces, schedules), sga_exchange (n_ladders = M),
  *   sga_exchange_pairs (a pair across two models: SGA_ERR_INVALID), energies, sga_local_fields, best tracking,
  *   stats, export / import, the checksum (n_spins[] included), sga_describe ("csr batch models=M n=min..max ...") and
- *   the route calls work.  SGA_ERR_UNSUPPORTED: sga_set_field_cache(ON) (AUTO streams), the Wolff rule, sga_flip,
- *   sga_update, sga_autotune, and any option that would pick a wide, bit-spin, several-updates-per-step or
- *   cached-field form.  One launch per sweep call: the narrow one-update form, each wave running its own model. */
+ *   the route calls work.  SGA_ERR_UNSUPPORTED: sga_set_field_cache(ON) (AUTO streams) unless option
+ *   "ragged_field_cache" is set, the Wolff rule, sga_flip, sga_update, sga_autotune, and any option that would pick a
+ *   wide, bit-spin, several-updates-per-step or fixed-point cached-field form.  One launch per sweep call: the narrow
+ *   one-update form, each wave running its own model.
+ *   Option "ragged_field_cache" = 1 (version >= 1100, set before this call): the batch is also scanned for the int16
+ *   cached-field form of sga_set_csr -- in EVERY model J integer valued in strictly sorted rows without duplicates,
+ *   h in multiples of 1/2, max_i sum_j |J_ij| < 2^15, rows of <= 2048 entries, the largest model within LDS -- and
+ *   sga_set_field_cache(ON / AUTO) then acts as on a one-model CSR engine: one workgroup of 4 | 8 waves per replica,
+ *   its model's fields D = J s resident in LDS, a row read on accept only.  Accept table, its scale and the launch
+ *   geometry are batch-wide (the largest table, scale 2 as soon as one model has a half-integer h), which leaves
+ *   every model on its one-model chain.  ON over a batch that does not qualify: sga_sweep fails with
+ *   SGA_ERR_UNSUPPORTED naming the first offending model; AUTO streams there. */
 int sga_set_csr_batch(sga_engine *e, int n_models, const int32_t *n_spins, const int64_t *rowptr,
                       const int32_t *colidx, const float *val, const float *h, int64_t nnz);
 /* model m of a ragged batch: its spins and, once replicas exist, its first global replica and replica count */
@@ -379,8 +388,11 @@ int sga_set_csr_storage(sga_engine *e, int storage);
  *     rows -- scale, field width and accept table are batch-wide, which keeps every model's fields exact and its
  *     chain the one-model chain; fields seeded by one launch of exact integer sums, eight replicas per pass over
  *     a model's rows; "several accepts per round" needs each MODEL's matrix below 4 GiB, not the stack's;
- *     sga_explain_route / sga_describe name the batch ("models=M").  Ragged CSR batches (sga_set_csr_batch) and
- *     the fixed-point form over batches stay refused;
+ *     sga_explain_route / sga_describe name the batch ("models=M").  The fixed-point form over batches stays
+ *     refused;
+ *   ragged CSR batches (sga_set_csr_batch; version >= 1100) under option "ragged_field_cache" = 1: the CSR
+ *     conditions below in every model, production sweeps, one launch under AUTO decided by the hottest replica.
+ *     With the option at 0 (default) ON is refused (SGA_ERR_UNSUPPORTED) and AUTO streams;
  *   CSR couplings (sga_set_csr, or a sparse matrix sga_set_dense kept as CSR): J integer valued and symmetric
  *     in strictly sorted rows (no duplicate entries), zero diagonal, h in multiples of 1/2,
  *     max_i sum_j |J_ij| < 2^15 (only the dynamic part J s of a field is kept, as int16; h is read beside it),
@@ -466,6 +478,10 @@ int sga_set_field_cache(sga_engine *e, int mode);
  *                           "row_shared_window"), 2 = where sga_autotune measured it ahead of every geometry by more than 1 % [sweep; SGA_ROW_SHARED]
  *   "row_shared_window"     0 (default) | 256 | 512 | 1024 (other values: rounded down): W under "row_shared" = 1 (0: the
  *                           autotuner's, else 1024)                                      [sweep; SGA_ROW_SHARED_WINDOW]
+ *   "ragged_field_cache"    0 (default) | 1   ragged CSR batches (sga_set_csr_batch): the int16 cached-field sweep of
+ *                           sga_set_csr over the batch (csrc/sweep_clf_csr.hip, ragged build): sga_set_field_cache(ON)
+ *                           is accepted, sga_set_csr_batch scans every model for the form's conditions, ON / AUTO act
+ *                           as on a one-model CSR engine.  0: ON is refused, AUTO streams.  Same chain       [set]
  * sga_option_name enumerates the keys (index 0, 1, ... until SGA_ERR_INVALID).
  * (No reference counterpart: the reference has one code path, core/spin_dynamics.py:61-152.) */
 int sga_set_option(sga_engine *e, const char *key, int64_t value);

@@ -18,6 +18,13 @@ replica's local fields resident and reads a coupling row on accept only -- the s
 but `total_time` is the same for "on", "auto" and "off".  On the ragged (sparse) path "auto" and "off" stream; "on"
 is refused by the ragged engine (SGA_ERR_UNSUPPORTED), which sends the chunk to the stacked path like any other
 refusal.
+
+`BatchConfig.ragged_field_cache=True` (build-specific, default False) sets the engine option "ragged_field_cache"
+before the couplings: the ragged engine then serves `field_cache` "on" / "auto" itself -- every replica's local fields
+of ITS model resident, one workgroup of 4 or 8 waves per replica, a row read on accept only; the same chain, so again
+every result field but `total_time` is unchanged.  A chunk that does not qualify (a model with real-valued J, row sums
+of 2^15 or more, duplicate entries, h off the half-integers) is refused under "on" and takes the stacked path; under
+"auto" it streams on the ragged engine.
 """
 import time
 from dataclasses import dataclass
@@ -46,6 +53,7 @@ class BatchConfig:
     streaming_mode: bool = False
     checkpoint_interval: int = 100
     replicas_per_model: int = 1  # build-specific: independent restarts per model, best is kept
+    ragged_field_cache: bool = False  # build-specific: sparse chunks serve field_cache "on" / "auto" on the ragged engine
 
     def __post_init__(self):
         if self.batch_size <= 0:
@@ -143,8 +151,13 @@ class BatchProcessor:
         s0 = np.zeros((len(models), n_max), np.int8)  # [M, n_max], zero padded
         for i, m in enumerate(models):
             s0[i, :m.n_spins] = m.spins_int8()
+        def set_problem(eng):
+            if self.batch_config.ragged_field_cache:  # (a [set] option: before the couplings)
+                eng.set_option("ragged_field_cache", 1)
+            eng.set_csr_batch(problems)
+
         try:
-            return self._run(models, lambda eng: eng.set_csr_batch(problems), s0)
+            return self._run(models, set_problem, s0)
         except AnnealingError as err:
             if (getattr(err, "details", None) or {}).get("code") == N.ERR_UNSUPPORTED:
                 return None

@@ -186,6 +186,8 @@ bool clf_possible(const sga_engine *e, const char **why) {
     if (reason && !q.clf_ok && e->clf_fx_why && (!e->csr || q.n_models == 1)) reason = e->clf_fx_why;
     // (the integer form over dense couplings, likewise)
     if (reason && !q.clf_ok && !e->csr && !e->implicit() && e->clf_why && e->opt[OPT_CLF_FIXED_POINT] != 1) reason = e->clf_why;
+    // (ragged CSR batches under option "ragged_field_cache": the first offending model and the condition it fails)
+    if (reason && !q.clf_ok && e->ragged && !e->clf_ragged_why.empty()) reason = e->clf_ragged_why.c_str();
     if (why) *why = reason;
     return reason == nullptr;
 }
@@ -195,6 +197,23 @@ bool clf_active(const sga_engine *e) {
 // resident fields of every replica, from the all-replica pass (the tracked energies are left alone)
 int ensure_fields(sga_engine *e) {
     if (e->fields_valid && e->fields) return SGA_OK;
+    if (e->ragged) {  // D = J_m s of every replica over its model's rows, up to eight replicas of a model per pass
+        e->ldf = ((long long)e->n + 127) / 128 * 128;  // (the largest model's)
+        if (!e->fields && hipMalloc(&e->fields, (size_t)e->R * (size_t)e->ldf * 2) != hipSuccess) {
+            (void)hipGetLastError();
+            e->fields = nullptr;
+            return fail(SGA_ERR_MEMORY, "no memory for the resident local fields of the cached-field sweep");
+        }
+        if (!e->hq) {  // scale * h of every row of the concatenation, at the batch-wide scale
+            HIPCHK(hipMalloc(&e->hq, sizeof(int) * (size_t)e->n_rows));
+            HIPCHK(sga::launch_scaled_fields(e->h, e->n_rows, e->table_scale, e->hq, e->stream));
+        }
+        HIPCHK(sga::launch_csr_fields_seed_ragged(e->rowptr64, e->cv, e->spins, e->sstride, e->n, e->R, (unsigned int)e->replica0,
+                                                  e->Rg / e->n_models, e->d_models, static_cast<short *>(e->fields), e->ldf,
+                                                  e->stream));
+        e->fields_valid = true;
+        return SGA_OK;
+    }
     if (e->csr) {  // D = J s of every replica (int16), eight replicas per pass over the entries; scale * h once
         e->ldf = ((long long)e->n + 127) / 128 * 128;
         const size_t fbytes = e->clf_fx_bits ? (size_t)(e->clf_fx_bits / 8) : 2;  // (fixed point: D = 2^k J s, int32 | int64)
@@ -363,7 +382,7 @@ int ensure_packed(sga_engine *e) {
 extern "C" {
 
 const char *sga_last_error(void) { return g_last_error.c_str(); }
-int sga_version(void) { return 1000; }  // + sga_set_groups (implicit cardinality-group couplings, sweep_groups.hip)  // 900: + cached local fields for many-model dense batches (sga_set_dense_batch)  // 800: + option "clf_fixed_point" over dense couplings (sweep_clf_fx.hip)  // 700: + option "clf_fixed_point" (cached fields of real-valued CSR couplings)  // 600: + sga_set_csr_batch / sga_get_batch_model (ragged CSR batches)  // round 5: + sga_explain_route / sga_get_route_query, sga_get_last_kernel, sga_get_autotune_table, ladder-local sga_exchange
+int sga_version(void) { return 1100; }  // + option "ragged_field_cache" (cached local fields for ragged CSR batches, sweep_clf_csr.hip)  // 1000: + sga_set_groups (implicit cardinality-group couplings, sweep_groups.hip)  // 900: + cached local fields for many-model dense batches (sga_set_dense_batch)  // 800: + option "clf_fixed_point" over dense couplings (sweep_clf_fx.hip)  // 700: + option "clf_fixed_point" (cached fields of real-valued CSR couplings)  // 600: + sga_set_csr_batch / sga_get_batch_model (ragged CSR batches)  // round 5: + sga_explain_route / sga_get_route_query, sga_get_last_kernel, sga_get_autotune_table, ladder-local sga_exchange
 
 int sga_create(int device, sga_engine **out) {
     if (!out) return fail(SGA_ERR_INVALID, "out is NULL");
@@ -492,7 +511,7 @@ int sga_set_field_cache(sga_engine *e, int mode) {
     if (!e) return fail(SGA_ERR_INVALID, "engine is NULL");
     if (mode != SGA_FIELD_CACHE_OFF && mode != SGA_FIELD_CACHE_ON && mode != SGA_FIELD_CACHE_AUTO)
         return fail(SGA_ERR_INVALID, "bad field-cache mode");
-    if (mode == SGA_FIELD_CACHE_ON && e->ragged)
+    if (mode == SGA_FIELD_CACHE_ON && e->ragged && e->opt[OPT_RAGGED_FIELD_CACHE] == 0)
         return fail(SGA_ERR_UNSUPPORTED, "cached local fields are not built for ragged CSR batches (AUTO runs the streaming form)");
     if (mode != e->field_cache) {
         // what an earlier mode learnt about these replicas does not carry over: ON runs every replica on the cached-field
@@ -880,9 +899,11 @@ int sga_sweep(sga_engine *e, int n_sweeps, int site_mode, int arith, const doubl
                                 else if (rt == 1 && acc < enter) rt = 0, back = true;
                             }
                         } else {
-                            unsigned long long top = 0;
-                            for (int r2 = 0; r2 < e->R; ++r2) top = std::max(top, now[(size_t)r2] - e->auto_mark_acc[(size_t)r2]);
-                            const double hottest = (double)top / (double)since;
+                            // (ragged batches: `since` counts n_max attempts per sweep, replica r2 made n_m of them)
+                            double hottest = 0.0;
+                            for (int r2 = 0; r2 < e->R; ++r2)
+                                hottest = std::max(hottest, (double)(now[(size_t)r2] - e->auto_mark_acc[(size_t)r2]) /
+                                                                ((double)since * (double)spins_of(e, r2) / (double)n));
                             const bool was = e->n_route_clf > 0;
                             const bool use = was ? hottest < leave : hottest < enter;
                             back = use && !was;
@@ -1081,6 +1102,7 @@ int sga_sweep(sga_engine *e, int n_sweeps, int site_mode, int arith, const doubl
             ac.ldf = e->ldf;
             ac.clf_hq = e->hq;
             ac.clf_row_max = (int)std::min<long long>(e->slotted ? (e->max_row_len + 63) / 64 * 64 : e->max_row_len, 1 << 20);
+            // (ragged batches: the batch's longest row and largest model choose the waves; a.ragged picks the build)
             if (e->clf_fx_bits) {  // option "clf_fixed_point": D = 2^k J s exactly, any single-site rule / site mode / arithmetic
                 ac.field_bits = e->clf_fx_bits;
                 ac.field_scale = e->clf_fx_k;

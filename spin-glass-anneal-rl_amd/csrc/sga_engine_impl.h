@@ -200,6 +200,9 @@ struct sga_engine {
     // ... of CSR problems (sweep_clf_csr.hip): integer J, rows strictly sorted, max_i sum_j |J_ij| < 2^15, the accept
     // table applies, dE of the rule == energy change; the fields are then D = J s as int16, h stays outside
     bool clf_csr_problem = false;
+    // ... of ragged CSR batches under option "ragged_field_cache": the first model that keeps the batch off the int16
+    // form and why (empty: the batch qualifies, or the option is off)
+    std::string clf_ragged_why;
     // ... or, with option "clf_fixed_point", as exact fixed point: D = 2^k J s as int32 | int64 (any fp32 J whose row
     // sums are exact, h fp32 beside it): the width (0 = not this form), k, and why the form does not apply (nullptr: it does)
     // -- for dense couplings too (sweep_clf_fx.hip: the dense problems clf_problem does not take)
@@ -308,6 +311,7 @@ struct sga_engine {
         dev_free(nd4t);
         dev_free(hq);
         clf_csr_problem = false;
+        clf_ragged_why.clear();
         clf_fx_bits = 0;
         clf_fx_k = 0;
         clf_fx_why = nullptr;

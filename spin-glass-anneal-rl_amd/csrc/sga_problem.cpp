@@ -902,7 +902,11 @@ int sga_set_csr_batch(sga_engine *e, int n_models, const int32_t *n_spins, const
     // per model: the scans of sga_set_csr, then its class; the batch takes the most general class and the widest table
     int acc_b = sga::CSR_ACC_F32_TABLE, scale_b = 1;
     bool sorted_b = true;
-    float m_b = 0.0f;
+    float m_b = 0.0f, mj_b = 0.0f;
+    // option "ragged_field_cache": sga_set_csr's eligibility for the int16 cached-field sweep, over every model; the
+    // first model that fails one of the conditions and which (sga_sweep under SGA_FIELD_CACHE_ON reports it)
+    const bool want_clf = e->opt[OPT_RAGGED_FIELD_CACHE] == 1;
+    std::string clf_why;
     std::vector<int> row0((size_t)n_models);
     std::vector<int2> models((size_t)n_models);
     for (int m = 0, r0 = 0; m < n_models; r0 += n_spins[m], ++m) {
@@ -953,6 +957,21 @@ int sga_set_csr_batch(sga_engine *e, int n_models, const int32_t *n_spins, const
         acc_b = std::max(acc_b, acc);
         if (acc == sga::CSR_ACC_F32_TABLE) scale_b = std::max(scale_b, scale);
         m_b = std::max(m_b, mm);
+        float mj;
+        std::memcpy(&mj, &sym[sga::CSR_ROW_J_ABS_MAX], sizeof(mj));
+        mj_b = std::max(mj_b, mj);
+        if (want_clf && clf_why.empty()) {
+            const char *bad = nullptr;
+            if (sym[sga::CSR_NOT_INTEGRAL] & 1) bad = "J is not integer valued";
+            else if (sym[sga::CSR_NOT_INTEGRAL] & 4) bad = "h is not a multiple of 1/2";
+            else if (!sorted) bad = "rows are not strictly sorted by column (unsorted or duplicate entries)";
+            else if (!(mj < 32768.0f)) bad = "max_i sum_j |J_ij| is not below 2^15 (int16 fields)";
+            else if (max_len > 4 * 64 * 8) bad = "a row is longer than 2048 entries";
+            else if (acc != sga::CSR_ACC_F32_TABLE)
+                bad = "the accept table does not apply (max_i (sum_j |J_ij| + |h_i|) outside [1, 2^24), or half-integer h with "
+                      "option \"half_integer_table\" = 0)";
+            if (bad) clf_why = "cached local fields over ragged CSR batches: " + who + bad;
+        }
     }
     if (e->opt[OPT_FORCE_CSR_ACC] > 0) acc_b = std::max(acc_b, std::min(3, (int)e->opt[OPT_FORCE_CSR_ACC]));
     e->csr_acc = acc_b;
@@ -962,7 +981,11 @@ int sga_set_csr_batch(sga_engine *e, int n_models, const int32_t *n_spins, const
     e->csr_row_abs_max = m_b;
     e->csr_sorted = sorted_b;
     e->consistent_dE = true;
-    e->clf_csr_problem = false;
+    e->row_j_abs_max = mj_b;
+    if (want_clf && clf_why.empty() && (acc_b != sga::CSR_ACC_F32_TABLE || e->table_m <= 0))
+        clf_why = "cached local fields over ragged CSR batches: the batch runs without an accept table (option \"force_csr_acc\")";
+    e->clf_csr_problem = want_clf && clf_why.empty();
+    e->clf_ragged_why = want_clf ? clf_why : std::string();
     // the plain layout: (column, value) interleaved, CSR_TAIL_PAD zeroed entries behind
     long long *src_ptr = nullptr;
     SGA_BATCH_CHK(hipMalloc(&src_ptr, sizeof(long long) * np1));

@@ -342,8 +342,21 @@ const char *clf_refusal(const Query &q) {
     if (q.kind == SGA_ROUTE_GROUPS)
         return "cached local fields: stored couplings only (sga_set_groups keeps the group sums resident instead; AUTO runs "
                "that form as it is)";
-    if (q.kind == SGA_ROUTE_CSR && q.n_models > 1)
+    if (q.kind == SGA_ROUTE_CSR && q.n_models > 1 && q.opt[OPT_RAGGED_FIELD_CACHE] == 0)
         return "cached local fields: not built for ragged CSR batches (sga_set_csr_batch runs the streaming narrow form)";
+    if (q.kind == SGA_ROUTE_CSR && q.n_models > 1) {
+        // option "ragged_field_cache": the int16 form of sweep_clf_csr.hip, each replica on its own model's rows; LDS is
+        // laid out for the largest model (q.n), the table and the longest row are the batch's
+        const long long ldf = ((long long)q.n + 127) / 128 * 128;
+        if (!q.clf_ok)
+            return "cached local fields over ragged CSR batches need, in every model, integer-valued J in strictly sorted rows "
+                   "(no duplicates), h in multiples of 1/2, max_i sum_j |J_ij| < 2^15 and the accept table";
+        if (q.max_row_len > 4 * 64 * 8) return "cached local fields over ragged CSR batches: a row is longer than 2048 entries";
+        if (q.R_local > 0 && (q.table_m <= 0 || sga::sweep_clf_csr_lds_bytes(ldf, q.sstride, q.table_m) > 160 * 1024))
+            return "cached local fields over ragged CSR batches: fields, spins and accept table of the largest model do not "
+                   "fit LDS (160 KiB)";
+        return nullptr;
+    }
     if (q.kind == SGA_ROUTE_CSR) {
         // sparse couplings: the dynamic part of the fields as int16 in LDS (sweep_clf_csr.hip)
         const long long ldf = ((long long)q.n + 127) / 128 * 128;
@@ -433,7 +446,10 @@ static double dense_fixed_point_theta(const Query &q, double t_upd) {
 }
 double routing_theta(const Query &q) {
     const double kn = (double)q.n / 1000.0;
-    const double t_upd = q.kind == SGA_ROUTE_CSR ? 0.20 + 0.0008 * (double)q.nnz / (double)q.n  // (C4: 0.68, C2b as CSR: 0.36)
+    // (ragged batches: q.n is the largest model, so nnz / n overstates the mean row; no row is longer than the longest)
+    const double deg = (q.kind == SGA_ROUTE_CSR && q.n_models > 1) ? std::min((double)q.nnz / (double)q.n, (double)q.max_row_len)
+                                                                     : (double)q.nnz / (double)q.n;
+    const double t_upd = q.kind == SGA_ROUTE_CSR ? 0.20 + 0.0008 * deg  // (C4: 0.68, C2b as CSR: 0.36)
                          : q.storage == SGA_J_T2 ? 0.29 + 0.009 * kn
                                                  : (q.storage == SGA_J_I8 ? 0.27 + 0.031 * kn : 0.30 + 0.12 * kn);
     if (q.kind == SGA_ROUTE_CSR && q.opt[OPT_CLF_FIXED_POINT] == 1 && (q.clf_bits == 32 || q.clf_bits == 64))
@@ -558,6 +574,8 @@ std::string explain(const Query &q0) {
                 std::snprintf(buf, sizeof(buf), " cached=on(waves=%d fields=int%d fixed-point)",
                               sga::sweep_clf_waves(dense_ldj(q), is_i8(q), std::max(q.R_local, 1), q.cus, (int)q.opt[OPT_CLF_WAVES]),
                               q.clf_bits);
+            else if (q.kind == SGA_ROUTE_CSR && q.n_models > 1)  // a ragged batch: waves by its longest row and largest model
+                std::snprintf(buf, sizeof(buf), " cached=on(waves=%d models=%d)", clf_csr_waves(q), q.n_models);
             else if (q.kind == SGA_ROUTE_CSR) std::snprintf(buf, sizeof(buf), " cached=on(waves=%d)", clf_csr_waves(q));
             else if (q.n_models > 1)  // a many-model dense batch: batch-wide field width, each replica on its model's rows
                 std::snprintf(buf, sizeof(buf), " cached=on(waves=%d fields=int%d models=%d)",
@@ -569,7 +587,7 @@ std::string explain(const Query &q0) {
                               q.clf_bits);
             out += buf;
         } else {
-            if (q.kind == SGA_ROUTE_DENSE && q.n_models > 1)
+            if (q.n_models > 1)  // (CSR: a ragged batch under option "ragged_field_cache")
                 std::snprintf(buf, sizeof(buf), " cached=auto(start=%s theta=%.3f models=%d)", auto_starts_cached(q) ? "cached" : "rows",
                               routing_theta(q), q.n_models);
             else

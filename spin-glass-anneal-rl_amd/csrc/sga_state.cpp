@@ -355,14 +355,17 @@ int sga_describe(sga_engine *e, char *buf, int buflen) {
     else if (e->ragged)
         std::snprintf(tmp, sizeof(tmp),
                       "csr batch models=%d n=%d..%d nnz=%lld R=%d waves_per_replica=1 replicas_per_block=%d sstride=%d "
-                      "path=%s table_m=%d spins=lds-int8 form=narrow-ragged sweep=streaming(no field cache for ragged batches)",
+                      "path=%s table_m=%d spins=lds-int8 form=narrow-ragged%s",
                       e->n_models, *std::min_element(e->model_n.begin(), e->model_n.end()), e->n, e->nnz, e->R,
                       sga::csr_waves_per_block(e->sstride, e->table_m), e->sstride,
                       (e->csr_acc == sga::CSR_ACC_F32_TABLE && e->table_m > 0) ? (e->table_scale == 2 ? "half-integer-fast" : "integer-fast")
                       : e->csr_acc <= sga::CSR_ACC_F32 ? "general acc=f32-exact"
                       : e->csr_acc == sga::CSR_ACC_F64 ? "general acc=f64-exact"
                                                        : "general acc=f64-canonical",
-                      e->table_m);
+                      e->table_m,
+                      // (option "ragged_field_cache" with the cache requested: the sweep form is named below)
+                      (e->opt[OPT_RAGGED_FIELD_CACHE] == 1 && e->field_cache != SGA_FIELD_CACHE_OFF)
+                          ? "" : " sweep=streaming(no field cache for ragged batches)");
     else if (e->csr)
         std::snprintf(tmp, sizeof(tmp),
                       "csr n=%d nnz=%lld R=%d waves_per_replica=%d replicas_per_block=%d sstride=%d "
@@ -416,7 +419,21 @@ int sga_describe(sga_engine *e, char *buf, int buflen) {
         std::strncat(tmp, " entries=packed-32bit", sizeof(tmp) - std::strlen(tmp) - 1);
     if (!e->consistent_dE) std::strncat(tmp, " energy=recomputed-per-sweep", sizeof(tmp) - std::strlen(tmp) - 1);
     if (e->ragged) {
-        // (one form: nothing below applies)
+        // option "ragged_field_cache": the int16 cached-field form over the batch, or why it streams
+        if (e->opt[OPT_RAGGED_FIELD_CACHE] == 1 && e->field_cache != SGA_FIELD_CACHE_OFF) {
+            const sga_route_query rq = route_query_of(e);
+            if (!clf_active(e))
+                std::strncat(tmp, " sweep=streaming(the batch does not qualify for cached local fields)", sizeof(tmp) - std::strlen(tmp) - 1);
+            else if (e->field_cache == SGA_FIELD_CACHE_ON)
+                std::snprintf(tmp + std::strlen(tmp), sizeof(tmp) - std::strlen(tmp),
+                              " sweep=cached-local-fields(ragged: int16 dynamic fields of each replica's model in LDS, %d waves per "
+                              "replica, scale=%d, row entries read on accept only)",
+                              sga_route::clf_csr_waves(rq), e->table_scale);
+            else
+                std::snprintf(tmp + std::strlen(tmp), sizeof(tmp) - std::strlen(tmp),
+                              " sweep=auto(ragged cached local fields while the hottest replica accepts little; now: %s)",
+                              (!e->auto_unavailable && e->n_route_clf > 0) ? "cached" : "one row per proposal");
+        }
     } else if (clf_active(e) && e->csr) {
         if (e->field_cache == SGA_FIELD_CACHE_ON && e->clf_fx_bits)
             std::snprintf(tmp + std::strlen(tmp), sizeof(tmp) - std::strlen(tmp),

@@ -31,6 +31,14 @@
 // metropolis_accept on the arguments the row kernels pass (h fp32, never folded into D): the chain is theirs bit for
 // bit, for every rule, site mode and arithmetic.  No accept table: uphill moves take the exp path.  An accept moves
 // D[column] by -2 s_i 2^k J (the entry's fp32 value scaled in the kernel: no second copy of J) with a no-return LDS add.
+//
+// Ragged batches (sga_set_csr_batch under option "ragged_field_cache", RAGGED): the int16 form with one workgroup per
+// replica of ANY model.  The workgroup looks its model {first row, n_m} up at entry (SweepArgs::ragged, as
+// sweep_csr_impl.h) and everything that depends on the problem size uses n_m: the sites word_to_site(x, n_m), the
+// window loop, the bit-to-spin write-backs (which leave the rows' padding past n_m zero).  Row extents and hq are read
+// from the model's first row on; columns are model-local, so D[column] is the replica's own slice.  LDS is laid out for
+// the largest model (a.ldf, a.sstride), the accept table and its scale are batch-wide: entry q stands for dE = 2 q /
+// scale whatever the model, so k = s_i (scale D_i + scale h_i) decides as it would on a one-model engine.
 #include "sweep_common.h"
 
 namespace sga {
@@ -103,6 +111,74 @@ hipError_t launch_csr_fields_seed(const long long *rowptr, const int2 *cv, const
     const int slices = std::max(1, std::min(64, 2048 / std::max(blocks, 1)));
     hipLaunchKernelGGL(csr_fields_seed_kernel, dim3(blocks, slices), dim3(256), lds, st, rowptr, cv, spins, sstride, n, R,
                        slices, D, ldf);
+    return hipGetLastError();
+}
+// ragged batches: blockIdx.x = (model among those this engine's replicas touch, group of up to eight of ITS replicas) --
+// replicas per model need not divide eight, and a shard may start inside a model: a block never straddles two models
+__global__ void __launch_bounds__(256) csr_fields_seed_ragged_kernel(const long long *__restrict__ rowptr, const int2 *__restrict__ cv,
+                                                                     const int8_t *__restrict__ spins, int sstride, int R,
+                                                                     unsigned int replica0, int reps, int groups_per_model,
+                                                                     const int2 *__restrict__ models, int slices,
+                                                                     short *__restrict__ D, long long ldf) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    unsigned int *sb = reinterpret_cast<unsigned int *>(smem);  // [8][words]: bit = spin down
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int m = (int)(replica0 / (unsigned int)reps) + (int)blockIdx.x / groups_per_model;
+    const int g = (int)blockIdx.x % groups_per_model;
+    // the model's replicas on this engine, as local indices [lo, hi)
+    const long long first = (long long)m * reps - (long long)replica0;
+    const int lo = (int)max(first, 0ll) + CLFS_SEED_REPS * g, hi = (int)min(first + reps, (long long)R);
+    if (lo >= hi) return;  // (block-uniform: a shard that holds part of the model)
+    const int count = min(CLFS_SEED_REPS, hi - lo);
+    const int2 md = models[m];
+    const int n = md.y, words = (n + 31) / 32;
+    rowptr += md.x;
+    for (int q = tid; q < CLFS_SEED_REPS * words; q += 256) {
+        const int rep = q / words, wd = q % words;
+        unsigned int b = 0;
+        if (rep < count)
+            for (int t = 0; t < 32; ++t) {
+                const int i = 32 * wd + t;
+                if (i < n && spins[(long long)(lo + rep) * sstride + i] < 0) b |= 1u << t;
+            }
+        sb[q] = b;
+    }
+    __syncthreads();
+    const int per = (n + slices - 1) / slices;
+    const int i0 = min(n, (int)blockIdx.y * per), i1 = min(n, i0 + per);
+    for (int i = i0 + w; i < i1; i += 4) {
+        const long long beg = rowptr[i], end = rowptr[i + 1];
+        int acc[CLFS_SEED_REPS];
+#pragma unroll
+        for (int rep = 0; rep < CLFS_SEED_REPS; ++rep) acc[rep] = 0;
+        for (long long e = beg + lane; e < end; e += 64) {
+            const int2 ent = cv[e];
+            const int J = (int)__int_as_float(ent.y);  // integer valued (engine: eligibility)
+            const int wd = ent.x >> 5, bit = ent.x & 31;  // (model-local column: below n)
+#pragma unroll
+            for (int rep = 0; rep < CLFS_SEED_REPS; ++rep) acc[rep] += ((sb[rep * words + wd] >> bit) & 1u) ? -J : J;
+        }
+#pragma unroll
+        for (int rep = 0; rep < CLFS_SEED_REPS; ++rep) {
+            const int tot = wave_sum(acc[rep]);
+            if (lane == 0 && rep < count) D[(long long)(lo + rep) * ldf + i] = (short)tot;
+        }
+    }
+}
+hipError_t launch_csr_fields_seed_ragged(const long long *rowptr, const int2 *cv, const int8_t *spins, int sstride, int n_max,
+                                         int R, unsigned int replica0, int reps_per_model, const int2 *models, short *D,
+                                         long long ldf, hipStream_t st) {
+    const size_t lds = (size_t)CLFS_SEED_REPS * (size_t)((n_max + 31) / 32) * 4;
+    if (lds > 160 * 1024 || R <= 0 || reps_per_model <= 0) return hipErrorInvalidValue;
+    hipError_t e = ensure_lds_limit(reinterpret_cast<const void *>(csr_fields_seed_ragged_kernel), lds);
+    if (e != hipSuccess) return e;
+    const int groups_per_model = (reps_per_model + CLFS_SEED_REPS - 1) / CLFS_SEED_REPS;
+    const int n_touched = (int)((replica0 + (unsigned int)R - 1) / (unsigned int)reps_per_model - replica0 / (unsigned int)reps_per_model) + 1;
+    const long long blocks = (long long)n_touched * groups_per_model;
+    if (blocks > 0x7fffffffll) return hipErrorInvalidValue;
+    const int slices = (int)std::max(1ll, std::min(64ll, 2048 / blocks));
+    hipLaunchKernelGGL(csr_fields_seed_ragged_kernel, dim3((unsigned int)blocks, slices), dim3(256), lds, st, rowptr, cv, spins,
+                       sstride, R, replica0, reps_per_model, groups_per_model, models, slices, D, ldf);
     return hipGetLastError();
 }
 // fixed point: D[r][i] = 2^k sum_j J_ij s_rj as FT (int | long long).  Every term and partial sum is an integer below
@@ -179,9 +255,11 @@ hipError_t launch_scaled_fields(const float *h, int n, int scale, int *hq, hipSt
 // ---- the sweep ------------------------------------------------------------------------------------------------
 // EPT: entries of a row per thread (the longest row <= EPT x threads of the workgroup).  FT: the field type (short;
 // int | long long with FX, the fixed-point fields: a.field_scale = k, a.table_m = 0).
-template <int EPT, typename FT, bool FX>
+// RAGGED: a ragged batch -- the replica's model is looked up at entry, n is its n_m (int16 form only).
+template <int EPT, typename FT, bool FX, bool RAGGED = false>
 __global__ void __launch_bounds__(64 * CLFS_MAX_WAVES) sweep_clf_csr_kernel(const SweepArgs a) {
     static_assert(FX == (sizeof(FT) != 2), "int16 fields: integer form; int32 | int64: fixed point");
+    static_assert(!RAGGED || !FX, "ragged batches: the int16 form");
     constexpr int SLOT_INTS = FX ? CLFS_SLOT_INTS_FX : CLFS_SLOT_INTS;
     constexpr int FB = (int)sizeof(FT);
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -194,17 +272,31 @@ __global__ void __launch_bounds__(64 * CLFS_MAX_WAVES) sweep_clf_csr_kernel(cons
     const int tid = threadIdx.x, lane = tid & 63;
     const int W = (int)(blockDim.x >> 6), nthreads = (int)blockDim.x;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int r = a.rep_list ? __builtin_amdgcn_readfirstlane(a.rep_list[blockIdx.x]) : (int)blockIdx.x, n = a.n;
+    const int r = a.rep_list ? __builtin_amdgcn_readfirstlane(a.rep_list[blockIdx.x]) : (int)blockIdx.x;
     const int sc = a.table_scale;            // 1 | 2: k and the table are in units of 1 / scale
     const double inv_sc = 1.0 / (double)sc;  // exact
     const int *hq = a.clf_hq;
     const long long *rp = a.rowptr64;
+    // ragged batches: the replica's model {first row, spins} by its GLOBAL index (wave-uniform, scalar loads); row
+    // extents and hq are read from the model's first row on
+    int model_n = 0;
+    if constexpr (RAGGED) {
+        const int m = (int)((a.replica0 + (uint32_t)r) / (uint32_t)a.reps_per_model);
+        const int *md = reinterpret_cast<const int *>(a.h + a.ragged) + 2 * m;
+        const int model_row0 = *(const __attribute__((address_space(4))) int *)md;
+        model_n = *(const __attribute__((address_space(4))) int *)(md + 1);
+        hq += model_row0;
+        rp += model_row0;
+    }
+    const int n = RAGGED ? model_n : a.n;
+    // 16-byte pieces of the field slice that hold fields (ragged: the model's own n_m; what lies past is never a field)
+    const int field_vecs = RAGGED ? (n * FB + 15) / 16 : (int)(a.ldf * FB / 16);
     constexpr int NONE = 1 << 30;
 
     {   // resident state -> LDS
         const int4 *src = reinterpret_cast<const int4 *>(reinterpret_cast<const FT *>(a.fields) + (long long)r * a.ldf);
         int4 *dst = reinterpret_cast<int4 *>(D);
-        for (int i = tid; i < (int)(a.ldf * FB / 16); i += nthreads) dst[i] = src[i];
+        for (int i = tid; i < field_vecs; i += nthreads) dst[i] = src[i];
         const int8_t *srow = a.spins + (long long)r * a.sstride;
         spins_to_bits(srow, bits, a.sstride, tid, nthreads);
         if ((a.sstride & 31) && tid == 0) {  // (int8 layouts are padded to 16: the last half word)
@@ -419,7 +511,7 @@ __global__ void __launch_bounds__(64 * CLFS_MAX_WAVES) sweep_clf_csr_kernel(cons
     {
         int4 *dst = reinterpret_cast<int4 *>(reinterpret_cast<FT *>(a.fields) + (long long)r * a.ldf);
         const int4 *src = reinterpret_cast<const int4 *>(D);
-        for (int i = tid; i < (int)(a.ldf * FB / 16); i += nthreads) dst[i] = src[i];
+        for (int i = tid; i < field_vecs; i += nthreads) dst[i] = src[i];
         bits_to_spins(bits, a.spins + (long long)r * a.sstride, a.sstride, n, tid, nthreads);
     }
     if (tid == 0) {
@@ -434,6 +526,7 @@ __global__ void __launch_bounds__(64 * CLFS_MAX_WAVES) sweep_clf_csr_kernel(cons
 // Fixed-point fields (a.field_bits = 32 | 64): every single-site rule, site mode and arithmetic; per-update records take
 // the row-per-proposal kernels.
 bool sweep_clf_csr_applies(const SweepArgs &a, int waves) {
+    if (a.ragged && (a.field_bits != 0 || a.rep_list || a.reps_per_model <= 0)) return false;  // ragged batches: int16, all replicas
     if (a.field_bits == 32 || a.field_bits == 64)
         return !a.accept_trace && !a.dE_trace && a.rule != SGA_RULE_WOLFF && a.table_m == 0 && a.fields && a.rowptr64 &&
                a.clf_row_max <= 4 * 64 * waves && a.ldf % 8 == 0 && a.sstride % 16 == 0 &&
@@ -453,6 +546,9 @@ hipError_t launch_sweep_clf_csr(const SweepArgs &a, int waves, hipStream_t st) {
     else if (a.field_bits == 32)
         kern = ept <= 1 ? sweep_clf_csr_kernel<1, int, true> : ept <= 2 ? sweep_clf_csr_kernel<2, int, true>
                                                                         : sweep_clf_csr_kernel<4, int, true>;
+    else if (a.ragged)
+        kern = ept <= 1 ? sweep_clf_csr_kernel<1, short, false, true> : ept <= 2 ? sweep_clf_csr_kernel<2, short, false, true>
+                                                                                 : sweep_clf_csr_kernel<4, short, false, true>;
     else
         kern = ept <= 1 ? sweep_clf_csr_kernel<1, short, false> : ept <= 2 ? sweep_clf_csr_kernel<2, short, false>
                                                                            : sweep_clf_csr_kernel<4, short, false>;
@@ -464,6 +560,10 @@ hipError_t launch_sweep_clf_csr(const SweepArgs &a, int waves, hipStream_t st) {
         note_sweep_kernel("sweep_clf_csr_kernel<%d entries per thread> x %d wave(s) (int%d fixed-point fields in LDS, k=%d, "
                           "row read on accept only)",
                           ept <= 1 ? 1 : ept <= 2 ? 2 : 4, waves, a.field_bits, a.field_scale);
+    else if (a.ragged)
+        note_sweep_kernel("sweep_clf_csr_kernel<%d entries per thread, ragged> x %d wave(s) (int16 fields in LDS, row read on accept "
+                          "only; each replica on its own model's rows)",
+                          ept <= 1 ? 1 : ept <= 2 ? 2 : 4, waves);
     else
         note_sweep_kernel("sweep_clf_csr_kernel<%d entries per thread> x %d wave(s) (int16 fields in LDS, row read on accept only)",
                           ept <= 1 ? 1 : ept <= 2 ? 2 : 4, waves);
