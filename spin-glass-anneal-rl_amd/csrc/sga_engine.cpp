@@ -115,8 +115,6 @@ int fields_pass(sga_engine *e, int r0, int count, double *energy, void *fields) 
     return SGA_OK;
 }
 
-// The cached-local-field sweep serves this problem / these replicas?  why: the reason when it does not
-// (sga_route.cpp, clf_refusal).
 // Row-shared windows (sweep_dense_rs.hip, option "row_shared"): the window W of the form for sweeps whose arguments are
 // the production ones (lean), 0 where today's row-per-proposal kernel runs.  The form needs what the look-ahead form
 // needs -- one dense model, integer J and h with exact fp32 sums (the accept table), Metropolis -- and J symmetric with a
@@ -179,6 +177,8 @@ static bool ensure_row_shared(sga_engine *e, int W, hipStream_t st) {
     return true;
 }
 
+// The cached-local-field sweep serves this problem / these replicas?  why: the reason when it does not
+// (sga_route.cpp, clf_refusal).
 bool clf_possible(const sga_engine *e, const char **why) {
     const sga_route_query q = route_query_of(e);
     const char *reason = sga_route::clf_refusal(q);
@@ -517,15 +517,7 @@ int sga_set_field_cache(sga_engine *e, int mode) {
         // what an earlier mode learnt about these replicas does not carry over: ON runs every replica on the cached-field
         // kernel (AUTO's per-replica routes would leave some on the row kernels for good), a failed allocation under
         // AUTO is retried, the fields are seeded anew
-        e->route.clear();
-        e->auto_mark_acc.clear();
-        e->n_route_clf = 0;
-        e->clf_wide = false;
-        e->clf_hot = true;
-        e->auto_unavailable = false;
-        e->auto_mark_attempted = 0;
-        e->auto_interval = 4;
-        e->route_dirty = true;
+        e->routing.reset();
         e->fields_valid = false;
     }
     e->field_cache = mode;
@@ -709,6 +701,392 @@ int sga_set_ladder(sga_engine *e, const double *slot_temps, int n_ladders) {
     return SGA_OK;
 }
 
+// ---- the stages of sga_sweep (below): staging, the plan, launch arguments, dispatch, the launches ------------------------
+namespace {
+
+// One sga_sweep call as its stages see it: the scalar arguments, and the schedule / replay inputs and trace outputs on
+// the device -- borrowed where they live there, staged otherwise.
+struct SweepCall {
+    int n_sweeps, site_mode, arith;
+    int64_t sched_ss, sched_rs;
+    DevIn<double> sched;
+    DevIn<int32_t> site;
+    DevIn<float> u;
+    DevOut<double> etrace, dE;
+    DevOut<uint8_t> acc;
+    int stage(sga_engine *e, const double *sched_, const int32_t *replay_site, const float *replay_u, double *energy_trace,
+              uint8_t *accept_trace, double *dE_trace) {
+        const size_t R = (size_t)e->R, per = (size_t)n_sweeps * (size_t)e->n;
+        hipStream_t st = e->stream;
+        int rc = SGA_OK;
+        if (sched_)  // the table's extent, from the strides
+            rc = sched.init(e->scratch[0], sched_, (size_t)((n_sweeps - 1) * sched_ss + (e->R - 1) * sched_rs + 1), st);
+        if (rc == SGA_OK && site_mode == SGA_SITE_REPLAY) rc = site.init(e->scratch[1], replay_site, R * per, st);
+        if (rc == SGA_OK && site_mode != SGA_SITE_RANDOM && replay_u) rc = u.init(e->scratch[2], replay_u, R * per, st);
+        if (rc == SGA_OK) rc = etrace.init(e->scratch[3], energy_trace, (size_t)n_sweeps * R, st);
+        if (rc == SGA_OK) rc = acc.init(e->scratch[4], accept_trace, R * per, st);
+        if (rc == SGA_OK) rc = dE.init(e->scratch[5], dE_trace, R * per, st);
+        return rc;
+    }
+    int finish(hipStream_t st) {
+        int rc = etrace.flush(st);
+        if (rc == SGA_OK) rc = acc.flush(st);
+        if (rc == SGA_OK) rc = dE.flush(st);
+        // host-side outputs must be complete, and staged host inputs consumed, before returning
+        if (rc == SGA_OK && (sched.staged || site.staged || u.staged || etrace.ptr || acc.ptr || dE.ptr)) HIPCHK(hipStreamSynchronize(st));
+        return rc;
+    }
+};
+
+enum class Cached { NONE, CSR, FIXED_POINT, INTEGER, INTEGER_BATCHED };
+struct SweepPlan {  // what holds for every launch of a call
+    sga_route_query rq;
+    sga_route::ClfLooks looks;
+    int spl = 1;                // sweeps per launch
+    bool exact_mode = false;    // every sweep its own launch, energies from scratch after it
+    Cached cached = Cached::NONE;  // the cached-field kernel of the call (NONE: the row-per-proposal kernels for all)
+    int cw = 0;                 // ... its waves per replica,
+    int n_clf = 0;              // ... the replicas on it,
+    bool mixed = false;         // ... and the others beside them on the row kernels, second stream
+    int rs_w = 0;               // row-shared window (0: not this form)
+};
+
+// The policy's look at the acceptance counters (sga_route.cpp, look): one read-back and synchronise when a look is due,
+// none otherwise.
+int look_at_counters(sga_engine *e, const SweepPlan &p) {
+    sga_route::LookInput in;
+    in.n = e->n;
+    in.R = e->R;
+    in.attempted = e->attempted;
+    in.theta = sga_route::routing_theta(p.rq);
+    in.start_cached = !p.looks.is_auto || sga_route::auto_starts_cached(p.rq);
+    in.looks = p.looks;
+    in.per_replica = e->opt[OPT_REPLICA_ROUTING] != 0 && !e->csr;  // (the CSR row kernels take no replica lists)
+    std::vector<int> model_spins;
+    if (e->ragged) {
+        for (int r = 0; r < e->R; ++r) model_spins.push_back(spins_of(e, r));
+        in.spins = model_spins.data();
+    }
+    std::vector<unsigned long long> now;
+    hipError_t he = hipSuccess;
+    const bool reseed = sga_route::look(e->routing, in, [&]() -> const unsigned long long * {
+        now.resize((size_t)e->R);
+        he = hipMemcpyAsync(now.data(), e->n_acc, sizeof(unsigned long long) * e->R, hipMemcpyDeviceToHost, e->stream);
+        if (he == hipSuccess) he = hipStreamSynchronize(e->stream);
+        return he == hipSuccess ? now.data() : nullptr;
+    });
+    HIPCHK(he);
+    if (reseed) e->fields_valid = false;  // somebody returns from the row kernels: fields are seeded anew
+    return SGA_OK;
+}
+
+// replica lists on the device ([0, n_clf): cached-field kernel, [R, R + R - n_clf): row kernels), the second
+// stream and the two events that fork / join it
+int prepare_mixed(sga_engine *e) {
+    const int R = e->R;
+    if (!e->d_rep_lists) HIPCHK(hipMalloc(&e->d_rep_lists, sizeof(int) * 2 * (size_t)R));
+    if (e->routing.dirty) {
+        std::vector<int> lists(2 * (size_t)R, 0);
+        int ia = 0, ib = 0;
+        for (int r = 0; r < R; ++r) {
+            if (e->routing.route[(size_t)r] == 0) lists[(size_t)ia++] = r;
+            else lists[(size_t)R + (size_t)ib++] = r;
+        }
+        HIPCHK(hipMemcpyAsync(e->d_rep_lists, lists.data(), sizeof(int) * lists.size(), hipMemcpyHostToDevice, e->stream));
+        HIPCHK(hipStreamSynchronize(e->stream));
+        e->routing.dirty = false;
+    }
+    if (!e->aux_stream) HIPCHK(hipStreamCreateWithFlags(&e->aux_stream, hipStreamNonBlocking));
+    if (!e->fork_ev) HIPCHK(hipEventCreateWithFlags(&e->fork_ev, hipEventDisableTiming));
+    if (!e->join_ev) HIPCHK(hipEventCreateWithFlags(&e->join_ev, hipEventDisableTiming));
+    return SGA_OK;
+}
+
+// The arguments of the launch that starts at sweep k0 of the call, as the row-per-proposal kernels take them.
+sga::SweepArgs base_args(const sga_engine *e, const SweepCall &c, const SweepPlan &p, int k0) {
+    sga::SweepArgs a{};
+    a.J = e->J_packed;
+    a.rowptr = e->rowptr;
+    a.rowptr64 = e->rowptr64;
+    a.rowinfo = e->rowinfo;
+    a.cvp = (e->big_form == 1 && e->csr_storage_latched != SGA_CSR_STORAGE_F32) ? e->cvp : nullptr;
+    a.csr_acc = e->csr_acc;  // (the table form needs its table: set below once table_m is final)
+    // head slots per wave that the longest row needs (the wide bit forms are built per count)
+    const long long slots = (e->max_row_len + 63) / 64;
+    const long long head = (slots + std::max(e->waves, 1) - 1) / std::max(e->waves, 1);
+    a.csr_head = (int)std::min<long long>(std::max<long long>(head, 1), 10);
+    a.big = e->big_form;
+    // (a slotted layout's row extents include the padding to whole 64-entry slots)
+    a.csr_row_cap = (e->csr && e->max_row_len <= 256)
+                        ? (int)std::max<long long>(e->slotted ? (e->max_row_len + 63) / 64 * 64 : e->max_row_len, 1) : 0;
+    a.csr_pair_ahead = csr_updates_per_step(e);
+    // (option "look_ahead" = 0: A/B switch and the parity tests' cross-check)
+    a.look_ahead = e->opt[OPT_LOOK_AHEAD] != 0 ? 1 : 0;
+    a.force_general = e->opt[OPT_FORCE_GENERAL] != 0 ? 1 : 0;
+    a.tsp_parallel = (int)e->opt[OPT_TSP_PARALLEL];
+    a.cv = e->cv;
+    a.h = e->h;
+    a.diag = e->diag;
+    a.spins = e->spins;
+    a.energy = e->energy;
+    a.best_energy = e->best_energy;
+    a.best_spins = e->best_spins;
+    a.n_accepted = e->n_acc;
+    a.rep_temp = e->rep_temp;
+    a.sched = c.sched.ptr ? c.sched.ptr + (long long)k0 * c.sched_ss : nullptr;
+    a.sched_ss = c.sched_ss;
+    a.sched_rs = c.sched_rs;
+    const long long off = (long long)k0 * e->n;
+    a.replay_site = c.site.ptr ? c.site.ptr + off : nullptr;
+    a.replay_u = c.u.ptr ? c.u.ptr + off : nullptr;
+    a.replay_stride = (long long)c.n_sweeps * e->n;
+    a.energy_trace = (c.etrace.ptr && !p.exact_mode) ? c.etrace.ptr + (long long)k0 * e->R : nullptr;
+    a.accept_trace = c.acc.ptr ? c.acc.ptr + off : nullptr;
+    a.dE_trace = c.dE.ptr ? c.dE.ptr + off : nullptr;
+    a.ld = e->ld;
+    a.ldj = e->ldj;
+    a.n = e->n;
+    a.sstride = e->sstride;
+    a.R = e->R;
+    a.n_sweeps = std::min(p.spl, c.n_sweeps - k0);
+    a.site_mode = c.site_mode;
+    a.arith = c.arith;
+    a.rule = e->rule;
+    a.table_m = p.exact_mode ? 0 : e->table_m;
+    a.table_scale = e->csr ? e->table_scale : 1;
+    a.table_covers = (e->csr && a.table_m > 0 && (double)e->table_scale * (double)e->csr_row_abs_max <= (double)a.table_m) ? 1 : 0;
+    if (a.csr_acc == sga::CSR_ACC_F32_TABLE && a.table_m == 0) a.csr_acc = sga::CSR_ACC_F32;
+    a.no_best = p.exact_mode ? 1 : 0;
+    a.reps_per_model = (e->n_models > 1 || e->ragged) ? e->Rg / e->n_models : 0;
+    a.model_stride_j = (long long)e->n * e->ldj;
+    if (e->ragged) a.ragged = e->ragged_at;
+    a.seed_lo = (uint32_t)e->seed;
+    a.seed_hi = (uint32_t)(e->seed >> 32);
+    a.sweep0 = e->sweeps_done + (uint32_t)k0;
+    a.replica0 = (uint32_t)e->replica0;
+    return a;
+}
+
+// ... and as the plan's cached-field form takes them: the resident fields, their width and scale.
+sga::SweepArgs cached_args(const sga_engine *e, const SweepPlan &p, sga::SweepArgs a) {
+    a.fields = e->fields;
+    a.ldf = e->ldf;
+    if (p.cached == Cached::CSR) {
+        // sparse couplings: D = J s as int16 in LDS, the row's entries read on accept (sweep_clf_csr.hip)
+        // (ragged batches: the batch's longest row and largest model choose the waves; a.ragged picks the build)
+        a.clf_hq = e->hq;
+        a.clf_row_max = (int)std::min<long long>(e->slotted ? (e->max_row_len + 63) / 64 * 64 : e->max_row_len, 1 << 20);
+    }
+    if (e->clf_fx_bits) {
+        // option "clf_fixed_point": D = 2^k J s exactly (CSR: sweep_clf_csr.hip, dense real-valued couplings:
+        // sweep_clf_fx.hip); any single-site rule, site mode and arithmetic -- the same chain as the row kernels
+        a.field_bits = e->clf_fx_bits;
+        a.field_scale = e->clf_fx_k;
+        a.table_m = 0;
+    } else if (p.cached != Cached::CSR) {
+        if (e->clf_scale == 2)  // half-integer fields: dE = q for q <= 2 M, tabulated at twice the resolution
+            a.table_m = (int)std::min(2.0 * (double)e->row_abs_max, 2048.0);
+        a.field_bits = e->clf_bits;
+        a.field_scale = e->clf_scale;
+        a.clf_jmax = e->j_abs_max;
+        // option "clf_batched": production arguments commit several accepts per round -- every decision of a
+        // super-window guessed at once, the guess checked against the few couplings between the accepting sites
+        // (sweep_clfb_impl.h); the same chain.  Ahead while the hottest replica accepts more than ~1 % (first sweeps
+        // from random spins 2.19 -> 1.72 ms, sweeps 5-25 0.272 -> 0.245), behind after 100 sweeps (0.105 -> 0.112):
+        // 2 = by the hottest replica's acceptance (default), 1 = always, 0 = never (profiles/r04_experiments.md 9)
+        a.clf_batched = (e->opt[OPT_CLF_BATCHED] == 1 || (p.looks.adaptive && e->routing.hot)) ? 1 : 0;
+    }
+    return a;
+}
+
+// Everything about the call that its launches share.  May refuse the call (Wolff, cached fields ON where they cannot
+// be had); under AUTO a failed allocation of the fields leaves the call on the row-per-proposal kernels.
+int plan_sweep(sga_engine *e, const SweepCall &c, SweepPlan &p) {
+    const int R = e->R;
+    p.rq = route_query_of(e);
+    // sweeps per launch: aim for ~50 ms of estimated work per launch (sga_route.cpp)
+    p.spl = sga_route::sweeps_per_launch(p.rq, c.n_sweeps, e->tune_spl, e->tsp ? e->tsp_args.npad : 0);
+    const bool wolff = e->rule == SGA_RULE_WOLFF;
+    if (wolff) {
+        if (e->ragged) return fail(SGA_ERR_UNSUPPORTED, "the Wolff rule is not implemented for ragged CSR batches");
+        if (e->tsp) return fail(SGA_ERR_UNSUPPORTED, "the Wolff rule is not implemented for sga_set_tsp problems");
+        if (e->groups) return fail(SGA_ERR_UNSUPPORTED, "the Wolff rule is not implemented for sga_set_groups problems");
+        if (sga::wolff_lds_bytes(e->n) > 160 * 1024 - 256)
+            return fail(SGA_ERR_UNSUPPORTED, "the Wolff rule keeps spins, cluster and queue in LDS: n <= ~31 000");
+        if (c.site_mode == SGA_SITE_SEQUENTIAL && !c.u.ptr)
+            return fail(SGA_ERR_INVALID, "sequential Wolff sweeps need replay_u (unused values are fine)");
+        // the cluster growth treats every stored entry as one bond: duplicate columns of a row (which the
+        // other rules add up) would be drawn twice and could overrun the cluster queue
+        if (e->csr && !e->csr_sorted)
+            return fail(SGA_ERR_UNSUPPORTED, "the Wolff rule over CSR couplings needs rows strictly sorted by "
+                                             "column (no duplicate entries)");
+    }
+    // Asymmetric J or a non-zero diagonal: the rule's dE (row i only, as the reference computes
+    // it) is not the energy change, so E += dE would drift from compute_energy().  Then every
+    // sweep is its own launch, followed by a from-scratch energy evaluation and the best update
+    // (exactly the reference's sequence, core/spin_dynamics.py:87, gpu_annealer.py:151-153).
+    // (the Wolff rule reports compute_energy() after every sweep as well, spin_dynamics.py:87)
+    p.exact_mode = !e->consistent_dE || wolff;
+    if (p.exact_mode) p.spl = 1;
+    // cached local fields (sga_set_field_cache): a row is read only when a proposal is accepted
+    bool clf = false;
+    if (e->field_cache != SGA_FIELD_CACHE_OFF && !wolff) {
+        const char *why = nullptr;
+        clf = clf_possible(e, &why);
+        if (!clf && e->field_cache == SGA_FIELD_CACHE_ON) return fail(SGA_ERR_UNSUPPORTED, why);
+    }
+    p.n_clf = clf ? R : 0;
+    if (clf) p.looks = sga_route::clf_looks(p.rq);
+    if (p.looks.any()) {  // (unavailable, below, is only ever set under AUTO)
+        int rc = e->routing.unavailable ? SGA_OK : look_at_counters(e, p);
+        if (rc != SGA_OK) return rc;
+        p.n_clf = e->routing.unavailable ? 0 : e->routing.n_cached;
+        clf = p.n_clf > 0;
+    }
+    if (clf) {
+        int rc = ensure_fields(e);
+        if (rc == SGA_ERR_MEMORY && e->field_cache == SGA_FIELD_CACHE_AUTO) {
+            // AUTO promises a faster form where it is available, not a failure where the row-per-proposal kernels
+            // (which need none of this memory) would have run: the cache is "not available" for these replicas
+            e->routing.unavailable = true;
+            dev_free(e->fields);
+            clf = false;
+            p.n_clf = 0;
+        } else if (rc != SGA_OK) {
+            return rc;
+        }
+    }
+    p.mixed = clf && p.n_clf < R;  // some replicas of this call on the row-per-proposal kernels beside the cached ones
+    if (p.mixed) {
+        int rc = prepare_mixed(e);
+        if (rc != SGA_OK) return rc;
+    }
+    if (!clf) e->fields_valid = false;  // the row-per-proposal kernels move the spins only
+    if (clf) {
+        // no row streaming to bound the launch by: many sweeps per launch (a sweep is 0.1 ... 10 ms here:
+        // at most 256 of them, so that a launch stays well under a few seconds)
+        if (!p.mixed && e->tune_spl <= 0) p.spl = std::min(c.n_sweeps, 256);
+        p.cached = e->csr ? Cached::CSR : e->clf_fx_bits ? Cached::FIXED_POINT : Cached::INTEGER;
+        p.cw = e->csr ? sga_route::clf_csr_waves(p.rq)
+               : (p.looks.tail && e->routing.wide)
+                   ? 8
+                   : sga::sweep_clf_waves(e->ldj, e->want_i8, p.mixed ? p.n_clf : R, e->cus, (int)e->opt[OPT_CLF_WAVES]);
+        // Whether the batched / the CSR form applies is asked once, of the first launch's arguments: it depends on which
+        // pointers are set, the modes and the sizes, and those are the same for every launch of a call.
+        const sga::SweepArgs ac = cached_args(e, p, base_args(e, c, p, 0));
+        if (p.cached == Cached::INTEGER && sga::sweep_clfb_applies(ac, e->want_i8)) p.cached = Cached::INTEGER_BATCHED;
+        // CSR: production arguments only -- traced / replayed / sequential sweeps take the row-per-proposal kernels
+        // (the same chain) and the fields are seeded anew afterwards
+        if (p.cached == Cached::CSR && !sga::sweep_clf_csr_applies(ac, p.cw)) {
+            p.cached = Cached::NONE;
+            e->fields_valid = false;
+        }
+    }
+    // row-shared windows (sweep_dense_rs.hip): one coupling-row read per proposed site and window
+    if (!clf && !p.exact_mode) {  // (exact_mode: the Wolff rule too)
+        const bool lean_call = c.site_mode == SGA_SITE_RANDOM && c.arith == SGA_ARITH_F64 && !c.acc.ptr && !c.dE.ptr;
+        p.rs_w = row_shared_window(e, lean_call);
+        if (p.rs_w && !ensure_row_shared(e, p.rs_w, e->stream)) p.rs_w = 0;
+    }
+    return SGA_OK;
+}
+
+// the row-per-proposal kernel of a dense problem (all replicas, or the list in a.rep_list)
+hipError_t launch_dense_rows(const sga_engine *e, sga::SweepArgs a, hipStream_t st) {
+    const bool lean = !a.force_general && a.site_mode == SGA_SITE_RANDOM && a.arith == SGA_ARITH_F64 &&
+                      e->rule == SGA_RULE_METROPOLIS && !a.accept_trace && !a.dE_trace;
+    if (e->use_t2 && lean) {  // production sweeps read the two bit-planes
+        a.J = e->J_bits;
+        a.J_aux = e->J_packed;
+        a.plane_row_bytes = t2_row_bits(e->n) / 8;
+        a.plane_bytes = (long long)e->n * a.plane_row_bytes;
+        a.diag = e->row_nnz;
+        return sga::launch_sweep_dense_t2(a, e->waves_t2, e->cpw_t2 > sga::T2_MAX_CPW ? 0 : e->cpw_t2, st);
+    }
+    return sga::launch_sweep_dense(a, e->want_i8, e->acc64 ? (e->acc_canon ? 2 : 1) : 0, e->waves,
+                                   e->cpw > sga::MAX_CPW ? 0 : e->cpw, st);
+}
+
+hipError_t launch_cached(const sga_engine *e, const SweepPlan &p, const sga::SweepArgs &ac, hipStream_t st) {
+    if (p.cached == Cached::CSR) return sga::launch_sweep_clf_csr(ac, p.cw, st);
+    if (p.cached == Cached::FIXED_POINT) return sga::launch_sweep_clf_fx(ac, e->want_i8, p.cw, st);
+    if (p.cached == Cached::INTEGER_BATCHED) return sga::launch_sweep_clfb(ac, e->want_i8, p.cw, st);
+    return sga::launch_sweep_clf(ac, e->want_i8, p.cw, st);
+}
+
+// Two launches over disjoint replica lists, side by side: the cached-field kernel on the engine's stream, the
+// row-per-proposal kernel on the second one, forked and joined by events.
+hipError_t launch_mixed(sga_engine *e, const SweepPlan &p, sga::SweepArgs ac, sga::SweepArgs a, hipStream_t st) {
+    ac.rep_list = e->d_rep_lists;
+    ac.rep_count = p.n_clf;
+    a.rep_list = e->d_rep_lists + e->R;
+    a.rep_count = e->R - p.n_clf;
+    hipError_t le = hipEventRecord(e->fork_ev, st);
+    if (le == hipSuccess) le = hipStreamWaitEvent(e->aux_stream, e->fork_ev, 0);
+    if (le == hipSuccess) le = launch_cached(e, p, ac, st);
+    char first[200], both[448];
+    std::snprintf(first, sizeof(first), "%s", sga::last_sweep_kernel());
+    if (le == hipSuccess) le = launch_dense_rows(e, a, e->aux_stream);
+    if (le == hipSuccess) le = hipEventRecord(e->join_ev, e->aux_stream);
+    if (le == hipSuccess) le = hipStreamWaitEvent(st, e->join_ev, 0);
+    if (le != hipSuccess) (void)hipStreamSynchronize(e->aux_stream);
+    std::snprintf(both, sizeof(both), "mixed launch: %d replica(s) on %s || %d on %s", p.n_clf, first, e->R - p.n_clf,
+                  sga::last_sweep_kernel());
+    sga::note_sweep_kernel("%s", both);
+    return le;
+}
+
+// One launch of the plan's form: cached fields, else the rule's / the problem's own kernel.
+hipError_t launch_sweep(sga_engine *e, const SweepPlan &p, sga::SweepArgs a, hipStream_t st) {
+    if (p.cached != Cached::NONE) {
+        const sga::SweepArgs ac = cached_args(e, p, a);
+        return p.mixed ? launch_mixed(e, p, ac, a, st) : launch_cached(e, p, ac, st);
+    }
+    if (e->rule == SGA_RULE_WOLFF) return sga::launch_sweep_wolff(a, sga::WolffArgs{e->wolff_u, e->wolff_cap, e->wolff_cursor}, e->csr, e->want_i8, st);
+    if (e->implicit()) a.table_m = 0;
+    if (e->groups) return sga::launch_sweep_groups(a, e->group_args, e->waves, st);
+    if (e->tsp) return sga::launch_sweep_tsp(a, e->tsp_args, e->tsp_waves, e->tsp_passes, st);
+    if (e->csr) return sga::launch_sweep_csr(a, e->waves, st);
+    if (p.rs_w) return sga::launch_sweep_dense_rs(a, e->rs, e->want_i8, st);
+    return launch_dense_rows(e, a, st);
+}
+
+// The call's launches, spl sweeps each; exact_mode: energies from scratch and the best update after every one.
+int run_launches(sga_engine *e, const SweepCall &c, const SweepPlan &p) {
+    const int R = e->R;
+    hipStream_t st = e->stream;
+    for (int k0 = 0; k0 < c.n_sweeps; k0 += p.spl) {
+        hipEvent_t ev0 = nullptr, ev1 = nullptr;
+        if (e->timing) {
+            HIPCHK(hipEventCreate(&ev0));
+            const hipError_t ce = hipEventCreate(&ev1);
+            if (ce != hipSuccess) {
+                (void)hipEventDestroy(ev0);
+                HIPCHK(ce);
+            }
+            HIPCHK(hipEventRecord(ev0, st));
+        }
+        const hipError_t le = launch_sweep(e, p, base_args(e, c, p, k0), st);
+        if (e->timing) {
+            (void)hipEventRecord(ev1, st);
+            e->events.emplace_back(ev0, ev1);
+        }
+        if (le != hipSuccess) (void)hipStreamSynchronize(st);  // staged inputs / scratch slots are reusable again
+        HIPCHK(le);
+        std::snprintf(e->last_kernel, sizeof(e->last_kernel), "%s", sga::last_sweep_kernel());  // (this thread just launched it)
+        if (p.exact_mode) {
+            int rc = recompute_energy_range(e, 0, R);
+            if (rc != SGA_OK) return rc;
+            HIPCHK(sga::launch_update_best(e->energy, e->spins, e->best_energy, e->best_spins, e->sstride, R, st));
+            if (c.etrace.ptr)
+                HIPCHK(hipMemcpyAsync(c.etrace.ptr + (long long)k0 * R, e->energy, sizeof(double) * R, hipMemcpyDeviceToDevice, st));
+        }
+    }
+    return SGA_OK;
+}
+
+}  // namespace
+
 int sga_sweep(sga_engine *e, int n_sweeps, int site_mode, int arith, const double *sched,
               int64_t sched_sweep_stride, int64_t sched_replica_stride,
               const int32_t *replay_site, const float *replay_u, double *energy_trace,
@@ -724,8 +1102,8 @@ int sga_sweep(sga_engine *e, int n_sweeps, int site_mode, int arith, const doubl
     if (site_mode == SGA_SITE_REPLAY && (!replay_site || !replay_u))
         return fail(SGA_ERR_INVALID, "SITE_REPLAY needs replay_site and replay_u");
     if (n_sweeps == 0) return SGA_OK;
+    if (sched && (sched_sweep_stride < 0 || sched_replica_stride < 0)) return fail(SGA_ERR_INVALID, "negative schedule stride");
     if (sched && !is_device_ptr(sched)) {  // every T(k, r) this call reads, before the first piece runs
-        if (sched_sweep_stride < 0 || sched_replica_stride < 0) return fail(SGA_ERR_INVALID, "negative schedule stride");
         for (int r = 0; r < e->R; ++r) {
             int rc = check_temperatures("sga_sweep (sched)", sched + (long long)r * sched_replica_stride, n_sweeps,
                                         sched_sweep_stride);
@@ -743,503 +1121,28 @@ int sga_sweep(sga_engine *e, int n_sweeps, int site_mode, int arith, const doubl
         return fail(SGA_ERR_INVALID, "tuning changed after sga_init_replicas; re-initialise");
     // The cached-field modes pick their kernel form by the acceptance counters, looked at when a call starts: a long
     // production call is walked in pieces of 16 sweeps so that the form follows the run (the chain does not depend on
-    // how a run is cut into calls).
+    // how a run is cut into calls).  Only where the counters ARE looked at: AUTO, and ON over dense couplings with the
+    // tail / batched forms enabled -- ON over CSR couplings has one form: its call stays one piece, launches of up to
+    // 256 sweeps.
     constexpr int PIECE = 16;
     if (n_sweeps > PIECE && e->field_cache != SGA_FIELD_CACHE_OFF && e->rule != SGA_RULE_WOLFF && site_mode == SGA_SITE_RANDOM &&
-        !replay_site && !replay_u && !accept_trace && !dE_trace) {
-        const char *why = nullptr;
-        // (only where the counters ARE looked at: AUTO, and ON over dense couplings with the tail / batched forms
-        //  enabled -- ON over CSR couplings has one form: its call stays one piece, launches of up to 256 sweeps)
-        const bool looks = e->field_cache == SGA_FIELD_CACHE_AUTO ||
-                           (!e->csr && ((e->opt[OPT_CLF_TAIL_WAVES] != 0 && e->opt[OPT_CLF_WAVES] == 0) || e->opt[OPT_CLF_BATCHED] == 2));
-        if (looks && clf_possible(e, &why)) {
-            for (int k = 0; k < n_sweeps; k += PIECE) {
-                rc = sga_sweep(e, std::min(PIECE, n_sweeps - k), site_mode, arith, sched ? sched + (long long)k * sched_sweep_stride : nullptr,
-                               sched_sweep_stride, sched_replica_stride, nullptr, nullptr,
-                               energy_trace ? energy_trace + (size_t)k * (size_t)e->R : nullptr, nullptr, nullptr);
-                if (rc != SGA_OK) return rc;
-            }
-            return SGA_OK;
-        }
+        !replay_site && !replay_u && !accept_trace && !dE_trace &&
+        sga_route::clf_looks(route_query_of(e), false).any() && clf_possible(e, nullptr)) {
+        for (int k = 0; k < n_sweeps && rc == SGA_OK; k += PIECE)
+            rc = sga_sweep(e, std::min(PIECE, n_sweeps - k), site_mode, arith, sched ? sched + (long long)k * sched_sweep_stride : nullptr,
+                           sched_sweep_stride, sched_replica_stride, nullptr, nullptr,
+                           energy_trace ? energy_trace + (size_t)k * (size_t)e->R : nullptr, nullptr, nullptr);
+        return rc;
     }
-
-    const int n = e->n, R = e->R;
-    const long long per = (long long)n_sweeps * n;
-    hipStream_t st = e->stream;
-
-    // schedule table: find its extent from the strides
-    DevIn<double> d_sched;
-    if (sched) {
-        if (sched_sweep_stride < 0 || sched_replica_stride < 0)
-            return fail(SGA_ERR_INVALID, "negative schedule stride");
-        const size_t extent =
-            (size_t)((n_sweeps - 1) * sched_sweep_stride + (R - 1) * sched_replica_stride + 1);
-        rc = d_sched.init(e->scratch[0], sched, extent, st);
-        if (rc != SGA_OK) return rc;
-    }
-    DevIn<int32_t> d_site;
-    DevIn<float> d_u;
-    if (site_mode == SGA_SITE_REPLAY) {
-        rc = d_site.init(e->scratch[1], replay_site, (size_t)R * per, st);
-        if (rc != SGA_OK) return rc;
-    }
-    if (site_mode != SGA_SITE_RANDOM && replay_u) {
-        rc = d_u.init(e->scratch[2], replay_u, (size_t)R * per, st);
-        if (rc != SGA_OK) return rc;
-    }
-    DevOut<double> d_etrace, d_dE;
-    DevOut<uint8_t> d_acc;
-    rc = d_etrace.init(e->scratch[3], energy_trace, (size_t)n_sweeps * R, st);
+    SweepCall c{n_sweeps, site_mode, arith, sched_sweep_stride, sched_replica_stride};
+    rc = c.stage(e, sched, replay_site, replay_u, energy_trace, accept_trace, dE_trace);
+    SweepPlan p;
+    if (rc == SGA_OK) rc = plan_sweep(e, c, p);
+    if (rc == SGA_OK) rc = run_launches(e, c, p);
     if (rc != SGA_OK) return rc;
-    rc = d_acc.init(e->scratch[4], accept_trace, (size_t)R * per, st);
-    if (rc != SGA_OK) return rc;
-    rc = d_dE.init(e->scratch[5], dE_trace, (size_t)R * per, st);
-    if (rc != SGA_OK) return rc;
-
-    // sweeps per launch: aim for ~50 ms of estimated work per launch (sga_route.cpp)
-    const sga_route_query rq = route_query_of(e);
-    int spl = sga_route::sweeps_per_launch(rq, n_sweeps, e->tune_spl, e->tsp ? e->tsp_args.npad : 0);
-    // Asymmetric J or a non-zero diagonal: the rule's dE (row i only, as the reference computes
-    // it) is not the energy change, so E += dE would drift from compute_energy().  Then every
-    // sweep is its own launch, followed by a from-scratch energy evaluation and the best update
-    // (exactly the reference's sequence, core/spin_dynamics.py:87, gpu_annealer.py:151-153).
-    // (the Wolff rule reports compute_energy() after every sweep as well, spin_dynamics.py:87)
-    const bool wolff = e->rule == SGA_RULE_WOLFF;
-    if (wolff) {
-        if (e->ragged) return fail(SGA_ERR_UNSUPPORTED, "the Wolff rule is not implemented for ragged CSR batches");
-        if (e->tsp) return fail(SGA_ERR_UNSUPPORTED, "the Wolff rule is not implemented for sga_set_tsp problems");
-        if (e->groups) return fail(SGA_ERR_UNSUPPORTED, "the Wolff rule is not implemented for sga_set_groups problems");
-        if (sga::wolff_lds_bytes(n) > 160 * 1024 - 256)
-            return fail(SGA_ERR_UNSUPPORTED, "the Wolff rule keeps spins, cluster and queue in LDS: n <= ~31 000");
-        if (site_mode == SGA_SITE_SEQUENTIAL && !replay_u)
-            return fail(SGA_ERR_INVALID, "sequential Wolff sweeps need replay_u (unused values are fine)");
-        // the cluster growth treats every stored entry as one bond: duplicate columns of a row (which the
-        // other rules add up) would be drawn twice and could overrun the cluster queue
-        if (e->csr && !e->csr_sorted)
-            return fail(SGA_ERR_UNSUPPORTED, "the Wolff rule over CSR couplings needs rows strictly sorted by "
-                                             "column (no duplicate entries)");
-    }
-    const bool exact_mode = !e->consistent_dE || wolff;
-    if (exact_mode) spl = 1;
-    // cached local fields (sga_set_field_cache): a row is read only when a proposal is accepted
-    bool clf = false;
-    if (e->field_cache != SGA_FIELD_CACHE_OFF && !wolff) {
-        const char *why = nullptr;
-        clf = clf_possible(e, &why);
-        if (!clf && e->field_cache == SGA_FIELD_CACHE_ON) return fail(SGA_ERR_UNSUPPORTED, why);
-    }
-    // AUTO routes every replica by ITS OWN acceptance: the cached-field kernel costs a replica ~1.1 - 1.7 us of its
-    // serial chain per ACCEPTED proposal and next to nothing per rejected one, the row-per-proposal kernels cost
-    // every replica the same per update whatever happens (~0.4 us on bit-planes, ~1.3 us on int8 rows, ~5 us on
-    // fp32 rows at n = 10^4) -- so a replica belongs on the row kernels only while its acceptance exceeds the ratio
-    // of the two (profiles/r04_experiments.md 2), and a ladder with a hot end runs as TWO concurrent launches (two
-    // streams) over disjoint replica lists.  The chain of a replica does not depend on the kernel that walks it.
-    // The run starts on the kernel that loses least if the guess is wrong (below); the per-replica counters are read back every
-    // 4 ... 16 sweeps.  Option "replica_routing" = 0: one launch, decided by the hottest replica (round 3).
-    // Both cached-field modes (ON and AUTO) look at the per-replica acceptance now and then.  A launch of the cached-field
-    // kernel ends with its hottest replica's serial chain; once most replicas accept next to nothing -- their workgroups
-    // are gone early and the chip idles behind that one chain -- EVERY replica gets eight waves (option "clf_tail_waves"):
-    // the workgroups then run as two rounds, which costs where the replicas are busy (sweeps 5-25 of the 10 000-spin ladder:
-    // 0.42 against 0.27 ms per sweep) and pays in the tail (after 100 sweeps 0.098 against 0.106;
-    // profiles/r04_experiments.md 9).  Giving only the hottest replicas eight waves in a launch of their own did not:
-    // beside the four-wave workgroups of the others their rounds took 1.6 us instead of 0.9.
-    int n_clf = clf ? R : 0;  // replicas on the cached-field kernel in this call
-    const bool is_auto = e->field_cache == SGA_FIELD_CACHE_AUTO;
-    const int clf_waves_std = (clf && !e->csr) ? sga::sweep_clf_waves(e->ldj, e->want_i8, e->R, e->cus, (int)e->opt[OPT_CLF_WAVES]) : 0;
-    const bool tail_opt = clf && !e->csr && e->opt[OPT_CLF_TAIL_WAVES] != 0 && e->opt[OPT_CLF_WAVES] == 0 &&
-                         clf_waves_std < 8 && e->ldj >= 6 * (e->want_i8 ? 1024 : 256) && e->R >= 16;
-    // Option "clf_batched" = 2 (default): the form that commits several accepts per round (sweep_clfb_impl.h) while the
-    // hottest replica accepts more than ~1 % of its proposals -- 16 % ahead on the first sweeps from random spins, 10 %
-    // at sweeps 5-25 of the 10 000-spin ladder -- and one accept per round below (7 % ahead after 100 sweeps).
-    const bool adaptive = clf && !e->csr && e->opt[OPT_CLF_BATCHED] == 2;
-    // break-even acceptance of one replica between the two kernel families: sga_route.cpp
-    auto routing_theta = [&]() -> double { return sga_route::routing_theta(rq); };
-    if (clf && (is_auto || tail_opt || adaptive)) {
-        if (is_auto && e->auto_unavailable) {
-            n_clf = 0;
-        } else {
-            if ((long long)e->auto_mark_acc.size() != e->R) {
-                e->auto_mark_acc.assign((size_t)e->R, 0ull);
-                // ON: 0 = cached-field kernel.  AUTO: nothing is known yet -- the run starts on the kernel that loses least
-                // if the guess is wrong: the cached-field kernel where a replica would have to accept more than ~30 % of
-                // its proposals for the row kernels to win (int8 and fp32 rows at n = 10^4: the first four sweeps of the
-                // bench ladder 55 / 218 ms on the row kernels against 8 / 30 ms cached, and 36 against 56 / 208 ms on a
-                // ladder that stays hot), the row-per-proposal kernel otherwise (bit-planes, small n).
-                const bool start_cached = !is_auto || sga_route::auto_starts_cached(rq);
-                e->route.assign((size_t)e->R, start_cached ? 0 : 1);
-                e->n_route_clf = start_cached ? e->R : 0;
-                e->clf_wide = false;
-                e->clf_hot = true;   // (nothing known yet: a run starts hot)
-                e->auto_mark_attempted = 0;
-                e->auto_interval = 4;
-            }
-            const long long since = e->attempted - e->auto_mark_attempted;
-            if (since >= (long long)e->auto_interval * n || since < 0) {
-                std::vector<unsigned long long> now((size_t)e->R);
-                HIPCHK(hipMemcpyAsync(now.data(), e->n_acc, sizeof(unsigned long long) * e->R, hipMemcpyDeviceToHost, st));
-                HIPCHK(hipStreamSynchronize(st));
-                if (since > 0) {
-                    bool back = false;
-                    const bool was_wide = e->clf_wide;
-                    if (is_auto) {
-                        // (enter, leave): acceptance below which a replica is taken onto the cached-field kernel, above
-                        // which it is given back (hysteresis)
-                        // Break-even acceptance of ONE replica = (what an update costs its chain on the row kernel) / (what
-                        // an accept costs it on the cached-field kernel).  Both kernels are paced by a replica's serial
-                        // chain, not by the chip, whenever only part of the replicas is hot: ~1.5 us per accept (1.15 alone
-                        // on its CU ... 1.7 with busy neighbours), and per update 0.38 us on bit-planes / 0.58 us on int8
-                        // rows at n = 10^4, ~0.3 us on short rows (profiles/r04_routing.py; fp32 rows: estimate).
-                        const double theta = routing_theta();
-                        const double enter = 0.8 * theta, leave = 1.2 * theta;
-                        if (e->opt[OPT_REPLICA_ROUTING] != 0 && !e->csr) {  // (the CSR row kernels take no replica lists)
-                            for (int r2 = 0; r2 < e->R; ++r2) {
-                                const double acc = (double)(now[(size_t)r2] - e->auto_mark_acc[(size_t)r2]) / (double)since;
-                                int &rt = e->route[(size_t)r2];
-                                if (rt == 0 && acc > leave) rt = 1;
-                                else if (rt == 1 && acc < enter) rt = 0, back = true;
-                            }
-                        } else {
-                            // (ragged batches: `since` counts n_max attempts per sweep, replica r2 made n_m of them)
-                            double hottest = 0.0;
-                            for (int r2 = 0; r2 < e->R; ++r2)
-                                hottest = std::max(hottest, (double)(now[(size_t)r2] - e->auto_mark_acc[(size_t)r2]) /
-                                                                ((double)since * (double)spins_of(e, r2) / (double)n));
-                            const bool was = e->n_route_clf > 0;
-                            const bool use = was ? hottest < leave : hottest < enter;
-                            back = use && !was;
-                            e->route.assign((size_t)e->R, use ? 0 : 1);
-                        }
-                    }
-                    int cnt = 0;
-                    for (int v : e->route) cnt += v == 0;
-                    e->n_route_clf = cnt;
-                    e->clf_wide = false;
-                    if (adaptive && cnt > 0) {  // (hysteresis: in above 1.5 % of the hottest replica's proposals, out below 1 %)
-                        unsigned long long top = 0;
-                        for (int r2 = 0; r2 < e->R; ++r2)
-                            if (e->route[(size_t)r2] == 0) top = std::max(top, now[(size_t)r2] - e->auto_mark_acc[(size_t)r2]);
-                        const double hottest = (double)top / (double)since;
-                        e->clf_hot = hottest > (e->clf_hot ? 0.010 : 0.015);
-                    }
-                    if (tail_opt && cnt > 0 && !(adaptive && e->clf_hot)) {
-                        // accepts per sweep of the replicas on the cached-field kernel: the hottest one's, and the mean
-                        const double per_sweep = (double)n / (double)since;  // counter difference -> accepts per sweep
-                        double amax = 0.0, asum = 0.0;
-                        for (int r2 = 0; r2 < e->R; ++r2) {
-                            if (e->route[(size_t)r2] != 0) continue;
-                            const double ar = (double)(now[(size_t)r2] - e->auto_mark_acc[(size_t)r2]) * per_sweep;
-                            amax = std::max(amax, ar);
-                            asum += ar;
-                        }
-                        // (mean / hottest ~ the share of the launch during which the chip is busy: measured ahead at 0.21,
-                        //  behind at 0.38 -- in below 0.28, out above 0.36; a chain of two dozen accepts per sweep is the
-                        //  least that matters against the windows of a sweep)
-                        const double ratio = asum / (double)cnt / std::max(amax, 1.0);
-                        e->clf_wide = amax >= 24.0 && ratio < (was_wide ? 0.36 : 0.28);
-                    }
-                    if (back) e->fields_valid = false;  // somebody returns from the row kernels: fields are seeded anew
-                    e->auto_interval = std::min(16, e->auto_interval * 2);
-                    e->route_dirty = true;
-                }
-                e->auto_mark_acc.swap(now);
-                e->auto_mark_attempted = e->attempted;
-            }
-            n_clf = e->n_route_clf;
-        }
-        clf = n_clf > 0;
-    }
-    if (clf) {
-        rc = ensure_fields(e);
-        if (rc == SGA_ERR_MEMORY && e->field_cache == SGA_FIELD_CACHE_AUTO) {
-            // AUTO promises a faster form where it is available, not a failure where the row-per-proposal kernels
-            // (which need none of this memory) would have run: the cache is "not available" for these replicas
-            e->auto_unavailable = true;
-            dev_free(e->fields);
-            e->fields_valid = false;
-            clf = false;
-            n_clf = 0;
-        } else if (rc != SGA_OK) {
-            return rc;
-        }
-    }
-    const int n_rows = clf ? R - n_clf : 0;  // replicas of this call on the row-per-proposal kernels beside the cached ones
-    const bool mixed = clf && n_rows > 0;
-    if (mixed) {
-        // replica lists on the device ([0, n_clf): cached-field kernel, [R, R + R - n_clf): row kernels), the second
-        // stream and the two events that fork / join it
-        if (!e->d_rep_lists) HIPCHK(hipMalloc(&e->d_rep_lists, sizeof(int) * 2 * (size_t)R));
-        if (e->route_dirty) {
-            std::vector<int> lists(2 * (size_t)R, 0);
-            int ia = 0, ib = 0;
-            for (int r2 = 0; r2 < R; ++r2) {
-                if (e->route[(size_t)r2] == 0) lists[(size_t)ia++] = r2;
-                else lists[(size_t)R + (size_t)ib++] = r2;
-            }
-            HIPCHK(hipMemcpyAsync(e->d_rep_lists, lists.data(), sizeof(int) * lists.size(), hipMemcpyHostToDevice, st));
-            HIPCHK(hipStreamSynchronize(st));
-            e->route_dirty = false;
-        }
-        if (!e->aux_stream) HIPCHK(hipStreamCreateWithFlags(&e->aux_stream, hipStreamNonBlocking));
-        if (!e->fork_ev) HIPCHK(hipEventCreateWithFlags(&e->fork_ev, hipEventDisableTiming));
-        if (!e->join_ev) HIPCHK(hipEventCreateWithFlags(&e->join_ev, hipEventDisableTiming));
-    }
-    if (clf && n_rows == 0) {
-        // no row streaming to bound the launch by: many sweeps per launch (a sweep is 0.1 ... 10 ms here:
-        // at most 256 of them, so that a launch stays well under a few seconds)
-        if (e->tune_spl <= 0) spl = std::min(n_sweeps, 256);
-    } else if (!clf) {
-        e->fields_valid = false;  // the row-per-proposal kernels move the spins only
-    }
-    e->last_mixed[0] = '\0';
-    // row-shared windows (sweep_dense_rs.hip): one coupling-row read per proposed site and window
-    int rs_w = 0;
-    if (!clf && !wolff && !exact_mode) {
-        const bool lean_call = site_mode == SGA_SITE_RANDOM && arith == SGA_ARITH_F64 && !d_acc.ptr && !d_dE.ptr;
-        rs_w = row_shared_window(e, lean_call);
-        if (rs_w && !ensure_row_shared(e, rs_w, st)) rs_w = 0;
-    }
-
-    for (int k0 = 0; k0 < n_sweeps; k0 += spl) {
-        const int ks = std::min(spl, n_sweeps - k0);
-        sga::SweepArgs a{};
-        a.J = e->J_packed;
-        a.rowptr = e->rowptr;
-        a.rowptr64 = e->rowptr64;
-        a.rowinfo = e->rowinfo;
-        a.cvp = (e->big_form == 1 && e->csr_storage_latched != SGA_CSR_STORAGE_F32) ? e->cvp : nullptr;
-        a.csr_acc = e->csr_acc;  // (the table form needs its table: set below once table_m is final)
-        {   // head slots per wave that the longest row needs (the wide bit forms are built per count)
-            const long long slots = (e->max_row_len + 63) / 64;
-            const long long need = (slots + std::max(e->waves, 1) - 1) / std::max(e->waves, 1);
-            a.csr_head = (int)std::min<long long>(std::max<long long>(need, 1), 10);
-        }
-        a.big = e->big_form;
-        // (a slotted layout's row extents include the padding to whole 64-entry slots)
-        a.csr_row_cap = (e->csr && e->max_row_len <= 256)
-                            ? (int)std::max<long long>(e->slotted ? (e->max_row_len + 63) / 64 * 64 : e->max_row_len, 1) : 0;
-        a.csr_pair_ahead = csr_updates_per_step(e);
-        // (option "look_ahead" = 0: A/B switch and the parity tests' cross-check)
-        a.look_ahead = e->opt[OPT_LOOK_AHEAD] != 0 ? 1 : 0;
-        a.force_general = e->opt[OPT_FORCE_GENERAL] != 0 ? 1 : 0;
-        a.tsp_parallel = (int)e->opt[OPT_TSP_PARALLEL];
-        a.cv = e->cv;
-        a.h = e->h;
-        a.diag = e->diag;
-        a.spins = e->spins;
-        a.energy = e->energy;
-        a.best_energy = e->best_energy;
-        a.best_spins = e->best_spins;
-        a.n_accepted = e->n_acc;
-        a.rep_temp = e->rep_temp;
-        a.sched = d_sched.ptr ? d_sched.ptr + (long long)k0 * sched_sweep_stride : nullptr;
-        a.sched_ss = sched_sweep_stride;
-        a.sched_rs = sched_replica_stride;
-        const long long off = (long long)k0 * n;
-        a.replay_site = d_site.ptr ? d_site.ptr + off : nullptr;
-        a.replay_u = d_u.ptr ? d_u.ptr + off : nullptr;
-        a.replay_stride = per;
-        a.energy_trace = (d_etrace.ptr && !exact_mode) ? d_etrace.ptr + (long long)k0 * R : nullptr;
-        a.accept_trace = d_acc.ptr ? d_acc.ptr + off : nullptr;
-        a.dE_trace = d_dE.ptr ? d_dE.ptr + off : nullptr;
-        a.ld = e->ld;
-        a.ldj = e->ldj;
-        a.n = n;
-        a.sstride = e->sstride;
-        a.R = R;
-        a.n_sweeps = ks;
-        a.site_mode = site_mode;
-        a.arith = arith;
-        a.rule = e->rule;
-        a.table_m = exact_mode ? 0 : e->table_m;
-        a.table_scale = e->csr ? e->table_scale : 1;
-        a.table_covers = (e->csr && a.table_m > 0 && (double)e->table_scale * (double)e->csr_row_abs_max <= (double)a.table_m) ? 1 : 0;
-        if (a.csr_acc == sga::CSR_ACC_F32_TABLE && a.table_m == 0) a.csr_acc = sga::CSR_ACC_F32;
-        a.no_best = exact_mode ? 1 : 0;
-        a.reps_per_model = e->n_models > 1 ? e->Rg / e->n_models : 0;
-        a.model_stride_j = (long long)e->n * e->ldj;
-        if (e->ragged) {
-            a.ragged = e->ragged_at;
-            a.reps_per_model = e->Rg / e->n_models;
-        }
-        a.seed_lo = (uint32_t)e->seed;
-        a.seed_hi = (uint32_t)(e->seed >> 32);
-        a.sweep0 = e->sweeps_done + (uint32_t)k0;
-        a.replica0 = (uint32_t)e->replica0;
-
-        hipEvent_t ev0 = nullptr, ev1 = nullptr;
-        if (e->timing) {
-            HIPCHK(hipEventCreate(&ev0));
-            const hipError_t ce = hipEventCreate(&ev1);
-            if (ce != hipSuccess) {
-                (void)hipEventDestroy(ev0);
-                HIPCHK(ce);
-            }
-            HIPCHK(hipEventRecord(ev0, st));
-        }
-        const bool lean = !a.force_general && site_mode == SGA_SITE_RANDOM && arith == SGA_ARITH_F64 &&
-                          e->rule == SGA_RULE_METROPOLIS && !a.accept_trace && !a.dE_trace;
-        // the row-per-proposal kernel of a dense problem (all replicas, or the list in aa.rep_list)
-        auto launch_dense_rows = [&](sga::SweepArgs aa, hipStream_t s2) -> hipError_t {
-            if (e->use_t2 && lean) {  // production sweeps read the two bit-planes
-                aa.J = e->J_bits;
-                aa.J_aux = e->J_packed;
-                aa.plane_row_bytes = t2_row_bits(e->n) / 8;
-                aa.plane_bytes = (long long)e->n * aa.plane_row_bytes;
-                aa.diag = e->row_nnz;
-                return sga::launch_sweep_dense_t2(aa, e->waves_t2, e->cpw_t2 > sga::T2_MAX_CPW ? 0 : e->cpw_t2, s2);
-            }
-            return sga::launch_sweep_dense(aa, e->want_i8, e->acc64 ? (e->acc_canon ? 2 : 1) : 0, e->waves,
-                                           e->cpw > sga::MAX_CPW ? 0 : e->cpw, s2);
-        };
-        hipError_t le;
-        bool clf_now = clf;
-        if (clf && e->csr) {
-            // sparse couplings: D = J s as int16 in LDS, the row's entries read on accept (sweep_clf_csr.hip);
-            // production arguments only -- traced / replayed / sequential sweeps take the row-per-proposal kernels
-            // (the same chain) and the fields are seeded anew afterwards
-            sga::SweepArgs ac = a;
-            ac.fields = e->fields;
-            ac.ldf = e->ldf;
-            ac.clf_hq = e->hq;
-            ac.clf_row_max = (int)std::min<long long>(e->slotted ? (e->max_row_len + 63) / 64 * 64 : e->max_row_len, 1 << 20);
-            // (ragged batches: the batch's longest row and largest model choose the waves; a.ragged picks the build)
-            if (e->clf_fx_bits) {  // option "clf_fixed_point": D = 2^k J s exactly, any single-site rule / site mode / arithmetic
-                ac.field_bits = e->clf_fx_bits;
-                ac.field_scale = e->clf_fx_k;
-                ac.table_m = 0;
-            }
-            const int cw = sga_route::clf_csr_waves(rq);
-            if (sga::sweep_clf_csr_applies(ac, cw)) {
-                le = sga::launch_sweep_clf_csr(ac, cw, st);
-            } else {
-                clf_now = false;
-                e->fields_valid = false;
-            }
-        }
-        if (clf_now && e->csr) {
-            // (launched above)
-        } else if (clf_now && e->clf_fx_bits) {
-            // dense real-valued couplings, option "clf_fixed_point": D = 2^k J s exactly (sweep_clf_fx.hip); any single-site
-            // rule, site mode and arithmetic, traces included -- the same chain as the row kernels
-            sga::SweepArgs ac = a;
-            ac.fields = e->fields;
-            ac.ldf = e->ldf;
-            ac.field_bits = e->clf_fx_bits;
-            ac.field_scale = e->clf_fx_k;
-            ac.table_m = 0;
-            const int cw = (tail_opt && e->clf_wide)
-                               ? 8
-                               : sga::sweep_clf_waves(e->ldj, e->want_i8, mixed ? n_clf : e->R, e->cus, (int)e->opt[OPT_CLF_WAVES]);
-            if (!mixed) {
-                le = sga::launch_sweep_clf_fx(ac, e->want_i8, cw, st);
-            } else {  // two launches over disjoint replica lists, side by side (as below)
-                ac.rep_list = e->d_rep_lists;
-                ac.rep_count = n_clf;
-                a.rep_list = e->d_rep_lists + R;
-                a.rep_count = R - n_clf;
-                le = hipEventRecord(e->fork_ev, st);
-                if (le == hipSuccess) le = hipStreamWaitEvent(e->aux_stream, e->fork_ev, 0);
-                if (le == hipSuccess) le = sga::launch_sweep_clf_fx(ac, e->want_i8, cw, st);
-                char first[200];
-                std::snprintf(first, sizeof(first), "%s", sga::last_sweep_kernel());
-                if (le == hipSuccess) le = launch_dense_rows(a, e->aux_stream);
-                if (le == hipSuccess) le = hipEventRecord(e->join_ev, e->aux_stream);
-                if (le == hipSuccess) le = hipStreamWaitEvent(st, e->join_ev, 0);
-                if (le != hipSuccess) (void)hipStreamSynchronize(e->aux_stream);
-                std::snprintf(e->last_mixed, sizeof(e->last_mixed), "mixed launch: %d replica(s) on %s || %d on %s", n_clf,
-                              first, R - n_clf, sga::last_sweep_kernel());
-                sga::note_sweep_kernel("%s", e->last_mixed);
-            }
-        } else if (clf_now) {
-            sga::SweepArgs ac = a;
-            if (e->clf_scale == 2)  // half-integer fields: dE = q for q <= 2 M, tabulated at twice the resolution
-                ac.table_m = (int)std::min(2.0 * (double)e->row_abs_max, 2048.0);
-            ac.fields = e->fields;
-            ac.ldf = e->ldf;
-            ac.field_bits = e->clf_bits;
-            ac.field_scale = e->clf_scale;
-            ac.clf_jmax = e->j_abs_max;
-            const int cw = (tail_opt && e->clf_wide)
-                               ? 8
-                               : sga::sweep_clf_waves(e->ldj, e->want_i8, mixed ? n_clf : e->R, e->cus, (int)e->opt[OPT_CLF_WAVES]);
-            // option "clf_batched": production arguments commit several accepts per round -- every decision of a
-            // super-window guessed at once, the guess checked against the few couplings between the accepting sites
-            // (sweep_clfb_impl.h); the same chain.  Ahead while the hottest replica accepts more than ~1 % (first sweeps
-            // from random spins 2.19 -> 1.72 ms, sweeps 5-25 0.272 -> 0.245), behind after 100 sweeps (0.105 -> 0.112):
-            // 2 = by the hottest replica's acceptance (default), 1 = always, 0 = never (profiles/r04_experiments.md 9)
-            ac.clf_batched = (e->opt[OPT_CLF_BATCHED] == 1 || (adaptive && e->clf_hot)) ? 1 : 0;
-            const bool batched = sga::sweep_clfb_applies(ac, e->want_i8);
-            auto launch_cached = [&](const sga::SweepArgs &aa, hipStream_t s2) -> hipError_t {
-                return batched ? sga::launch_sweep_clfb(aa, e->want_i8, cw, s2) : sga::launch_sweep_clf(aa, e->want_i8, cw, s2);
-            };
-            if (!mixed) {
-                le = launch_cached(ac, st);
-            } else {
-                // two launches over disjoint replica lists, side by side: the cached-field kernel on the engine's
-                // stream, the row-per-proposal kernel on the second one, forked and joined by events
-                ac.rep_list = e->d_rep_lists;
-                ac.rep_count = n_clf;
-                a.rep_list = e->d_rep_lists + R;
-                a.rep_count = R - n_clf;
-                le = hipEventRecord(e->fork_ev, st);
-                if (le == hipSuccess) le = hipStreamWaitEvent(e->aux_stream, e->fork_ev, 0);
-                if (le == hipSuccess) le = launch_cached(ac, st);
-                char first[200];
-                std::snprintf(first, sizeof(first), "%s", sga::last_sweep_kernel());
-                if (le == hipSuccess) le = launch_dense_rows(a, e->aux_stream);
-                if (le == hipSuccess) le = hipEventRecord(e->join_ev, e->aux_stream);
-                if (le == hipSuccess) le = hipStreamWaitEvent(st, e->join_ev, 0);
-                if (le != hipSuccess) (void)hipStreamSynchronize(e->aux_stream);
-                std::snprintf(e->last_mixed, sizeof(e->last_mixed), "mixed launch: %d replica(s) on %s || %d on %s", n_clf,
-                              first, R - n_clf, sga::last_sweep_kernel());
-                sga::note_sweep_kernel("%s", e->last_mixed);
-            }
-        } else if (wolff) {
-            const sga::WolffArgs wa{e->wolff_u, e->wolff_cap, e->wolff_cursor};
-            le = sga::launch_sweep_wolff(a, wa, e->csr, e->want_i8, st);
-        } else if (e->groups) {
-            a.table_m = 0;
-            le = sga::launch_sweep_groups(a, e->group_args, e->waves, st);
-        } else if (e->tsp) {
-            a.table_m = 0;
-            le = sga::launch_sweep_tsp(a, e->tsp_args, e->tsp_waves, e->tsp_passes, st);
-        } else if (e->csr) {
-            le = sga::launch_sweep_csr(a, e->waves, st);
-        } else if (rs_w) {
-            le = sga::launch_sweep_dense_rs(a, e->rs, e->want_i8, st);
-        } else {
-            le = launch_dense_rows(a, st);
-        }
-        if (e->timing) {
-            (void)hipEventRecord(ev1, st);
-            e->events.emplace_back(ev0, ev1);
-        }
-        if (le != hipSuccess) (void)hipStreamSynchronize(st);  // staged inputs / scratch slots are reusable again
-        HIPCHK(le);
-        std::snprintf(e->last_kernel, sizeof(e->last_kernel), "%s", sga::last_sweep_kernel());  // (this thread just launched it)
-        if (exact_mode) {
-            int rc2 = recompute_energy_range(e, 0, R);
-            if (rc2 != SGA_OK) return rc2;
-            HIPCHK(sga::launch_update_best(e->energy, e->spins, e->best_energy, e->best_spins,
-                                           e->sstride, R, st));
-            if (d_etrace.ptr)
-                HIPCHK(hipMemcpyAsync(d_etrace.ptr + (long long)k0 * R, e->energy, sizeof(double) * R,
-                                      hipMemcpyDeviceToDevice, st));
-        }
-    }
     e->sweeps_done += (uint32_t)n_sweeps;
-    e->attempted += per;
-
-    rc = d_etrace.flush(st);
-    if (rc != SGA_OK) return rc;
-    rc = d_acc.flush(st);
-    if (rc != SGA_OK) return rc;
-    rc = d_dE.flush(st);
-    if (rc != SGA_OK) return rc;
-    // host-side outputs must be complete, and staged host inputs consumed, before returning
-    if (d_sched.staged || d_site.staged || d_u.staged || d_etrace.ptr || d_acc.ptr || d_dE.ptr)
-        HIPCHK(hipStreamSynchronize(st));
-    return SGA_OK;
+    e->attempted += (long long)n_sweeps * e->n;
+    return c.finish(e->stream);
 }
 
 int sga_set_update_rule(sga_engine *e, int rule) {

@@ -4,7 +4,8 @@
 //   sga_problem.cpp   sga_set_dense / sga_set_csr / sga_set_tsp: scans, packing, CSR layouts
 //   sga_autotune.cpp  sga_autotune (measured launch geometry / sweep form)
 //   sga_state.cpp     state access, checkpoint / resume, timing, sga_describe, checksum
-//   sga_route.cpp     WHICH form runs: pure functions of the problem's traits and the options (no HIP calls)
+//   sga_route.cpp     WHICH form runs: pure functions of the problem's traits and the options, and the cached-field
+//                     modes' sweep-time policy over the acceptance counters (no HIP calls)
 #ifndef SGA_ENGINE_IMPL_H
 #define SGA_ENGINE_IMPL_H
 #include <hip/hip_runtime.h>
@@ -218,23 +219,13 @@ struct sga_engine {
     bool fields_valid = false;
     void *ybuf = nullptr;      // [count][ldj] int32 | float: scratch of the all-replica field pass
     size_t ybuf_bytes = 0;
-    // SGA_FIELD_CACHE_AUTO looks at the acceptance of the last sweeps now and then (host read-back of the
-    // per-replica counters): an accept costs ~2 us of its replica's chain, so the cached-field sweep only
-    // pays while the HOTTEST replica accepts little
-    bool auto_unavailable = false;      // the fields could not be allocated: AUTO stays on the row-per-proposal kernels
-    std::vector<int> route;             // per local replica: 0 = cached-field kernel, 1 = row-per-proposal kernel (AUTO)
-    int n_route_clf = 0;                // replicas routed to the cached-field kernel
-    bool clf_wide = false;              // the cached-field launch runs at eight waves per replica (option "clf_tail_waves")
-    bool clf_hot = true;                // its hottest replica accepts > ~1 %: several accepts per round (option "clf_batched" = 2)
-    bool route_dirty = true;            // the device copy of the replica lists is stale
+    // The cached-field modes look at the acceptance of the last sweeps now and then (host read-back of the per-replica
+    // counters): which replicas run on which kernel family, and in which form of the cached one (sga_route.cpp, look)
+    sga_route::ReplicaRouting routing;
     int *d_rep_lists = nullptr;         // [2][R]: the cached-field kernel's replicas, then the row kernels'
     hipStream_t aux_stream = nullptr;   // the second launch of a mixed sweep
     hipEvent_t fork_ev = nullptr, join_ev = nullptr;
-    char last_mixed[448] = {0};
     char last_kernel[512] = {0};        // the instantiation this engine's last sweep launch ran (sga_get_last_kernel)
-    long long auto_mark_attempted = 0;  // per-replica attempts at the last look
-    int auto_interval = 4;              // sweeps until the next look (doubles up to 32)
-    std::vector<unsigned long long> auto_mark_acc;
     // row-shared windows (sweep_dense_rs.hip, option "row_shared"): the window the autotuner picked (0: none), the
     // plan / field scratch and what it was sized for; rs_suspend keeps the form out of the autotuner's geometry trials.
     // rs_jp / rs_jabs: the resident bit-planes of J_packed and sum_j |J_ij| per row (RowSharedPlan::jp, jabs), built by
@@ -358,16 +349,8 @@ struct sga_engine {
         fields_valid = false;
         dev_free(ybuf);
         ybuf_bytes = 0;
-        auto_unavailable = false;
-        route.clear();
-        n_route_clf = 0;
-        clf_wide = false;
-        clf_hot = true;
-        route_dirty = true;
+        routing.reset();
         dev_free(d_rep_lists);
-        auto_mark_attempted = 0;
-        auto_interval = 4;
-        auto_mark_acc.clear();
         free_row_shared();
         rs_tuned_w = 0;
         R = Rg = 0;

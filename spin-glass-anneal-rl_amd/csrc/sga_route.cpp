@@ -492,6 +492,107 @@ int sweeps_per_launch(const Query &q, int n_sweeps, int tune_spl, int npad_tsp) 
     return std::max(1, std::min(spl, n_sweeps));
 }
 
+// ---- the cached-field modes' look at the acceptance counters -------------------------------------------------------------
+// AUTO routes every replica by ITS OWN acceptance: the cached-field kernel costs a replica ~1.1 - 1.7 us of its
+// serial chain per ACCEPTED proposal and next to nothing per rejected one, the row-per-proposal kernels cost
+// every replica the same per update whatever happens (~0.4 us on bit-planes, ~1.3 us on int8 rows, ~5 us on
+// fp32 rows at n = 10^4) -- so a replica belongs on the row kernels only while its acceptance exceeds the ratio
+// of the two (profiles/r04_experiments.md 2), and a ladder with a hot end runs as TWO concurrent launches (two
+// streams) over disjoint replica lists.  The chain of a replica does not depend on the kernel that walks it.
+// The per-replica counters are read back every 4 ... 16 sweeps.  Without per-replica routing (option
+// "replica_routing" = 0; CSR couplings, whose row kernels take no replica lists): one launch, decided by the hottest
+// replica.
+// Both cached-field modes (ON and AUTO) look at the per-replica acceptance now and then.  A launch of the cached-field
+// kernel ends with its hottest replica's serial chain; once most replicas accept next to nothing -- their workgroups
+// are gone early and the chip idles behind that one chain -- EVERY replica gets eight waves (option "clf_tail_waves"):
+// the workgroups then run as two rounds, which costs where the replicas are busy (sweeps 5-25 of the 10 000-spin ladder:
+// 0.42 against 0.27 ms per sweep) and pays in the tail (after 100 sweeps 0.098 against 0.106;
+// profiles/r04_experiments.md 9).  Giving only the hottest replicas eight waves in a launch of their own did not:
+// beside the four-wave workgroups of the others their rounds took 1.6 us instead of 0.9.
+// Option "clf_batched" = 2 (default): the form that commits several accepts per round (sweep_clfb_impl.h) while the
+// hottest replica accepts more than ~1 % of its proposals -- 16 % ahead on the first sweeps from random spins, 10 %
+// at sweeps 5-25 of the 10 000-spin ladder -- and one accept per round below (7 % ahead after 100 sweeps).
+ClfLooks clf_looks(const Query &q, bool sized) {
+    ClfLooks l;
+    const bool dense = q.kind != SGA_ROUTE_CSR;
+    l.is_auto = q.field_cache == SGA_FIELD_CACHE_AUTO;
+    l.tail = dense && q.opt[OPT_CLF_TAIL_WAVES] != 0 && q.opt[OPT_CLF_WAVES] == 0 &&
+             (!sized || (sga::sweep_clf_waves(q.ldj, is_i8(q), q.R_local, q.cus, (int)q.opt[OPT_CLF_WAVES]) < 8 &&
+                         q.ldj >= 6 * elems_per_chunk(is_i8(q)) && q.R_local >= 16));
+    l.adaptive = dense && q.opt[OPT_CLF_BATCHED] == 2;
+    return l;
+}
+
+bool look(ReplicaRouting &s, const LookInput &in, const std::function<const unsigned long long *()> &read_counters) {
+    const size_t R = (size_t)in.R;
+    if (s.mark_acc.size() != R) {  // nothing known yet: a run starts hot, four sweeps to the first look
+        s.reset();
+        s.mark_acc.assign(R, 0ull);
+        s.route.assign(R, in.start_cached ? 0 : 1);
+        s.n_cached = in.start_cached ? in.R : 0;
+    }
+    const long long since = in.attempted - s.mark_attempted;
+    if (since >= 0 && since < (long long)s.interval * in.n) return false;
+    const unsigned long long *now = read_counters();
+    if (!now) return false;
+    bool back = false;
+    auto accepts = [&](size_t r) { return now[r] - s.mark_acc[r]; };
+    if (since > 0) {
+        if (in.looks.is_auto) {
+            // (enter, leave): acceptance below which a replica is taken onto the cached-field kernel, above which it is
+            // given back (hysteresis).  Break-even acceptance of ONE replica (theta: routing_theta) = (what an update
+            // costs its chain on the row kernel) / (what an accept costs it on the cached-field kernel).  Both kernels
+            // are paced by a replica's serial chain, not by the chip, whenever only part of the replicas is hot: ~1.5 us
+            // per accept (1.15 alone on its CU ... 1.7 with busy neighbours), and per update 0.38 us on bit-planes /
+            // 0.58 us on int8 rows at n = 10^4, ~0.3 us on short rows (profiles/r04_routing.py; fp32 rows: estimate).
+            const double enter = 0.8 * in.theta, leave = 1.2 * in.theta;
+            if (in.per_replica) {
+                for (size_t r = 0; r < R; ++r) {
+                    const double acc = (double)accepts(r) / (double)since;
+                    int &rt = s.route[r];
+                    if (rt == 0 && acc > leave) rt = 1;
+                    else if (rt == 1 && acc < enter) rt = 0, back = true;
+                }
+            } else {
+                // (ragged batches: `since` counts n_max attempts per sweep, replica r made n_m of them)
+                double hottest = 0.0;
+                for (size_t r = 0; r < R; ++r)
+                    hottest = std::max(hottest, (double)accepts(r) / ((double)since * (double)(in.spins ? in.spins[r] : in.n) /
+                                                                     (double)in.n));
+                const bool was = s.n_cached > 0;
+                const bool use = was ? hottest < leave : hottest < enter;
+                back = use && !was;
+                s.route.assign(R, use ? 0 : 1);
+            }
+        }
+        // the replicas on the cached-field kernel: how many, the hottest one's accepts, and the sum in accepts per sweep
+        const double per_sweep = (double)in.n / (double)since;  // counter difference -> accepts per sweep
+        unsigned long long top = 0;
+        double asum = 0.0;
+        int cnt = 0;
+        for (size_t r = 0; r < R; ++r) {
+            if (s.route[r] != 0) continue;
+            ++cnt;
+            top = std::max(top, accepts(r));
+            asum += (double)accepts(r) * per_sweep;
+        }
+        s.n_cached = cnt;
+        // (hysteresis: in above 1.5 % of the hottest replica's proposals, out below 1 %)
+        if (in.looks.adaptive && cnt > 0) s.hot = (double)top / (double)since > (s.hot ? 0.010 : 0.015);
+        // (mean / hottest ~ the share of the launch during which the chip is busy: measured ahead at 0.21,
+        //  behind at 0.38 -- in below 0.28, out above 0.36; a chain of two dozen accepts per sweep is the
+        //  least that matters against the windows of a sweep)
+        const double amax = (double)top * per_sweep;
+        s.wide = in.looks.tail && cnt > 0 && !(in.looks.adaptive && s.hot) && amax >= 24.0 &&
+                 asum / (double)cnt / std::max(amax, 1.0) < (s.wide ? 0.36 : 0.28);
+        s.interval = std::min(16, s.interval * 2);
+        s.dirty = true;
+    }
+    s.mark_acc.assign(now, now + R);
+    s.mark_attempted = in.attempted;
+    return back;
+}
+
 // ---- the whole chain of decisions as one line ----------------------------------------------------------------------------
 std::string explain(const Query &q0) {
     Query q = q0;

@@ -2,11 +2,14 @@
 // traits as the set-time scans found them, replica count, tuning, options).  No device call anywhere in sga_route.cpp;
 // the LDS-footprint helpers it uses (sga_kernels.h) are plain arithmetic on the kernels' layouts.  The engine asks
 // these functions at the stage where each decision is latched (set / replicas / sweep); sga_explain_route strings the
-// same calls together for tests.
+// same calls together for tests.  The one decision that has a memory -- the cached-field modes' look at the acceptance
+// counters -- is a transition on a plain struct (ReplicaRouting) from counters the engine hands in.
 #ifndef SGA_ROUTE_H
 #define SGA_ROUTE_H
 #include <cstring>
+#include <functional>
 #include <string>
+#include <vector>
 
 #include "sga.h"
 
@@ -141,6 +144,48 @@ bool auto_starts_cached(const Query &q);    // SGA_FIELD_CACHE_AUTO before any a
 int clf_csr_waves(const Query &q);          // waves per replica of the cached-field sweep over CSR couplings
 // ---- sweep time ------------------------------------------------------------------------------------------------------
 int sweeps_per_launch(const Query &q, int n_sweeps, int tune_spl, int npad_tsp);
+
+// Which looks at the per-replica acceptance counters a cached-field sweep of q takes when a call starts (meaningful
+// where clf_refusal(q) == nullptr).
+struct ClfLooks {
+    bool is_auto = false;     // SGA_FIELD_CACHE_AUTO: replicas move between the two kernel families
+    bool tail = false;        // option "clf_tail_waves" on, "clf_waves" left to the library, dense couplings -- and, with
+                              // `sized`, a launch large enough for eight waves per replica to matter
+    bool adaptive = false;    // option "clf_batched" = 2: several accepts per round while the hottest replica is hot
+    bool any() const { return is_auto || tail || adaptive; }
+};
+// sized = false is what the walk of a long call in 16-sweep pieces asks (so that the form follows the run): that test
+// has never applied the size conditions of the tail look (it predates them) -- a call with the look enabled but too
+// small for it is still cut, which changes how the run divides into launches, not the chain.  Kept as it is.
+ClfLooks clf_looks(const Query &q, bool sized = true);
+
+// What the policy knows about the replicas of an engine between calls.
+struct ReplicaRouting {
+    std::vector<int> route;          // per local replica: 0 = cached-field kernel, 1 = row-per-proposal kernel (AUTO)
+    int n_cached = 0;                // replicas routed to the cached-field kernel
+    bool wide = false;               // the cached-field launch runs at eight waves per replica (option "clf_tail_waves")
+    bool hot = true;                 // its hottest replica accepts > ~1 %: several accepts per round (option "clf_batched" = 2)
+    bool dirty = true;               // the device copy of the replica lists is stale
+    bool unavailable = false;        // the fields could not be allocated: AUTO stays on the row-per-proposal kernels
+    std::vector<unsigned long long> mark_acc;  // per-replica acceptance counters at the last look
+    long long mark_attempted = 0;    // per-replica attempts at the last look
+    int interval = 4;                // sweeps until the next look (doubles up to 16)
+    void reset() { *this = ReplicaRouting{}; }
+};
+struct LookInput {
+    int n = 0, R = 0;                // spins (ragged batches: the largest model's), local replicas
+    long long attempted = 0;         // per-replica attempts so far
+    const int *spins = nullptr;      // [R] spins of each replica's model (ragged batches), nullptr: n each
+    double theta = 0.0;              // routing_theta(q)
+    bool start_cached = true;        // the routes before anything is known: all cached (ON; AUTO: auto_starts_cached(q))
+    ClfLooks looks;
+    bool per_replica = true;         // option "replica_routing" != 0 and dense couplings
+};
+// The policy's step when a call starts.  New replica count: the initial routes.  A look is due after `interval` sweeps
+// of attempts (or when the attempts counter went backwards); only then read_counters is called, once, for the [R]
+// acceptance counters now (nullptr: the read failed, nothing moves), and the routes, hot / wide, the marks and the
+// interval move.  True: somebody returns from the row kernels, the resident fields are to be seeded anew.
+bool look(ReplicaRouting &s, const LookInput &in, const std::function<const unsigned long long *()> &read_counters);
 
 std::string explain(const Query &q);
 

@@ -421,18 +421,17 @@ int sga_describe(sga_engine *e, char *buf, int buflen) {
     if (e->ragged) {
         // option "ragged_field_cache": the int16 cached-field form over the batch, or why it streams
         if (e->opt[OPT_RAGGED_FIELD_CACHE] == 1 && e->field_cache != SGA_FIELD_CACHE_OFF) {
-            const sga_route_query rq = route_query_of(e);
             if (!clf_active(e))
                 std::strncat(tmp, " sweep=streaming(the batch does not qualify for cached local fields)", sizeof(tmp) - std::strlen(tmp) - 1);
             else if (e->field_cache == SGA_FIELD_CACHE_ON)
                 std::snprintf(tmp + std::strlen(tmp), sizeof(tmp) - std::strlen(tmp),
                               " sweep=cached-local-fields(ragged: int16 dynamic fields of each replica's model in LDS, %d waves per "
                               "replica, scale=%d, row entries read on accept only)",
-                              sga_route::clf_csr_waves(rq), e->table_scale);
+                              sga_route::clf_csr_waves(route_query_of(e)), e->table_scale);
             else
                 std::snprintf(tmp + std::strlen(tmp), sizeof(tmp) - std::strlen(tmp),
                               " sweep=auto(ragged cached local fields while the hottest replica accepts little; now: %s)",
-                              (!e->auto_unavailable && e->n_route_clf > 0) ? "cached" : "one row per proposal");
+                              (!e->routing.unavailable && e->routing.n_cached > 0) ? "cached" : "one row per proposal");
         }
     } else if (clf_active(e) && e->csr) {
         if (e->field_cache == SGA_FIELD_CACHE_ON && e->clf_fx_bits)
@@ -445,11 +444,11 @@ int sga_describe(sga_engine *e, char *buf, int buflen) {
         else if (e->clf_fx_bits)
             std::snprintf(tmp + std::strlen(tmp), sizeof(tmp) - std::strlen(tmp),
                           " sweep=auto(cached local fields, int%d fixed-point, k=%d, while the hottest replica accepts little; now: %s)",
-                          e->clf_fx_bits, e->clf_fx_k, (!e->auto_unavailable && e->n_route_clf > 0) ? "cached" : "one row per proposal");
+                          e->clf_fx_bits, e->clf_fx_k, (!e->routing.unavailable && e->routing.n_cached > 0) ? "cached" : "one row per proposal");
         else
             std::snprintf(tmp + std::strlen(tmp), sizeof(tmp) - std::strlen(tmp),
                           " sweep=auto(cached local fields while the hottest replica accepts little; now: %s)",
-                          (!e->auto_unavailable && e->n_route_clf > 0) ? "cached" : "one row per proposal");
+                          (!e->routing.unavailable && e->routing.n_cached > 0) ? "cached" : "one row per proposal");
     } else if (clf_active(e) && e->clf_fx_bits) {  // dense couplings, option "clf_fixed_point"
         if (e->field_cache == SGA_FIELD_CACHE_ON)
             std::snprintf(tmp + std::strlen(tmp), sizeof(tmp) - std::strlen(tmp),
@@ -459,19 +458,19 @@ int sga_describe(sga_engine *e, char *buf, int buflen) {
             std::snprintf(tmp + std::strlen(tmp), sizeof(tmp) - std::strlen(tmp),
                           " sweep=auto(cached local fields, int%d fixed-point, k=%d, per replica by its own acceptance; now: %d of "
                           "%d replica(s) cached, the rest one row per proposal)",
-                          e->clf_fx_bits, e->clf_fx_k, e->auto_unavailable ? 0 : e->n_route_clf, e->R);
+                          e->clf_fx_bits, e->clf_fx_k, e->routing.unavailable ? 0 : e->routing.n_cached, e->R);
     } else if (clf_active(e)) {
         if (e->field_cache == SGA_FIELD_CACHE_ON)
             std::snprintf(tmp + std::strlen(tmp), sizeof(tmp) - std::strlen(tmp),
                           " sweep=cached-local-fields(int%d in LDS, %d wave(s) per replica%s, row read on accept only)",
                           e->clf_bits, sga::sweep_clf_waves(e->ldj, e->want_i8, e->R, e->cus, (int)e->opt[OPT_CLF_WAVES]),
-                          e->clf_wide ? " -- now 8: the launch is its hottest replica's chain" : "");
+                          e->routing.wide ? " -- now 8: the launch is its hottest replica's chain" : "");
         else
             std::snprintf(tmp + std::strlen(tmp), sizeof(tmp) - std::strlen(tmp),
                           " sweep=auto(cached local fields, int%d in LDS, per replica by its own acceptance; now: %d of %d "
                           "replica(s) cached%s, the rest one row per proposal)",
-                          e->clf_bits, e->auto_unavailable ? 0 : e->n_route_clf, e->R,
-                          (!e->auto_unavailable && e->clf_wide) ? " at 8 waves each" : "");
+                          e->clf_bits, e->routing.unavailable ? 0 : e->routing.n_cached, e->R,
+                          (!e->routing.unavailable && e->routing.wide) ? " at 8 waves each" : "");
         if (e->n_models > 1)  // many-model batches: which form ran is visible (batch-wide scale and field width)
             std::snprintf(tmp + std::strlen(tmp), sizeof(tmp) - std::strlen(tmp), " cached-batch(models=%d scale=%d)", e->n_models,
                           e->clf_scale);

@@ -4,6 +4,8 @@ the product fails loudly instead of falling back)."""
 import ctypes
 import os
 import re
+import shutil
+import subprocess
 
 import numpy as np
 import pytest
@@ -356,3 +358,96 @@ def test_integration_md_route_snippet_runs_as_written_without_a_gpu(capsys):
     finally:
         os.chdir(cwd)
     assert capsys.readouterr().out.startswith("csr form=rows spins=int8 waves=1 replicas_per_block=4 updates_per_step=4 ")
+
+
+def _look_line(at, due, reseed, route, hot, wide, interval, mark, dirty):
+    return (f"at={at} due={due} reseed={reseed} route={route} cached={route.count('0')} hot={hot} wide={wide} "
+            f"interval={interval} mark={mark} dirty={dirty}")
+
+
+# The cached-field modes' sweep-time policy (csrc/sga_route.cpp: clf_looks, look), n = 100, R = 4, theta = 0.125 -- so
+# enter = 0.8 theta = 0.1, leave = 1.2 theta = 0.15.  Written from the thresholds in the code: a look after 4, 8, 16,
+# 16 sweeps of attempts; a cached replica leaves ABOVE leave, a row replica returns BELOW enter; one launch for all:
+# the hottest replica keeps the launch cached BELOW leave and takes it BELOW enter; hot above 1.5 %, cold at or below
+# 1 %; eight waves from 24 accepts per sweep and mean / hottest below 0.28, given up at or above 0.36.
+LOOK_EXPECTED = {
+    # which looks a call takes (clf_looks): the tail look needs option "clf_tail_waves" with "clf_waves" left alone, dense
+    # rows of six chunks (1024 int8 | 256 fp32) or more that do not get eight waves anyway, and 16 replicas; hot / cold
+    # needs "clf_batched" = 2 and dense rows.  A call is cut into pieces with the tail look merely armed.
+    "clf_looks": [
+        "int8 6144 x 16: auto=1 tail=1 adaptive=1 any=1 pieces=1",
+        "15 replicas: auto=1 tail=0 adaptive=1 any=1 pieces=1",
+        "rows of 6016: auto=1 tail=0 adaptive=1 any=1 pieces=1",
+        "rows of 13312: auto=1 tail=0 adaptive=1 any=1 pieces=1",
+        "fp32 rows of 1536: auto=1 tail=1 adaptive=1 any=1 pieces=1",
+        "fp32 rows of 1408: auto=1 tail=0 adaptive=1 any=1 pieces=1",
+        "clf_waves=4: auto=1 tail=0 adaptive=1 any=1 pieces=1",
+        "clf_batched=1: auto=1 tail=1 adaptive=0 any=1 pieces=1",
+        "CSR: auto=1 tail=0 adaptive=0 any=1 pieces=1",
+        "CSR ON: auto=0 tail=0 adaptive=0 any=0 pieces=0",
+        "ON, no look enabled: auto=0 tail=0 adaptive=0 any=0 pieces=0",
+        "ON, 15 replicas, clf_batched=0: auto=0 tail=0 adaptive=0 any=0 pieces=1"],
+    "per-replica AUTO": [
+        _look_line(400, 1, 0, "0110", 1, 0, 8, 400, 1),
+        _look_line(1200, 1, 0, "0110", 1, 0, 16, 1200, 1),
+        _look_line(2800, 1, 1, "0010", 1, 0, 16, 2800, 1)],
+    "whole-launch AUTO": [
+        _look_line(400, 1, 0, "1111", 1, 0, 8, 400, 1),
+        _look_line(1200, 1, 1, "0000", 1, 0, 16, 1200, 1),
+        _look_line(2800, 1, 0, "0000", 1, 0, 16, 2800, 1),
+        _look_line(4400, 1, 0, "1111", 1, 0, 16, 4400, 1)],
+    "whole-launch AUTO, ragged shares 1.0 0.5 1.0 0.5": [
+        _look_line(400, 1, 0, "1111", 1, 0, 8, 400, 1),
+        _look_line(1200, 1, 1, "0000", 1, 0, 16, 1200, 1)],
+    "adaptive hot / cold (ON)": [
+        _look_line(10000, 1, 0, "0000", 1, 0, 8, 10000, 1),
+        _look_line(20000, 1, 0, "0000", 0, 0, 16, 20000, 1),
+        _look_line(30000, 1, 0, "0000", 0, 0, 16, 30000, 1),
+        _look_line(40000, 1, 0, "0000", 1, 0, 16, 40000, 1)],
+    "adaptive, a replica on the rows is not counted (AUTO)": [
+        _look_line(10000, 1, 0, "0100", 0, 0, 8, 10000, 1),
+        _look_line(20000, 1, 0, "0100", 0, 0, 16, 20000, 1)],
+    "tail (ON)": [
+        _look_line(400, 1, 0, "0000", 1, 0, 8, 400, 1),
+        _look_line(1200, 1, 0, "0000", 1, 1, 16, 1200, 1),
+        _look_line(2800, 1, 0, "0000", 1, 1, 16, 2800, 1),
+        _look_line(4400, 1, 0, "0000", 1, 0, 16, 4400, 1)],
+    "tail, 23 accepts per sweep (ON)": [
+        _look_line(400, 1, 0, "0000", 1, 0, 8, 400, 1)],
+    "tail while adaptive and hot (ON)": [
+        _look_line(400, 1, 0, "0000", 1, 0, 8, 400, 1)],
+    "cadence": [
+        _look_line(0, 0, 0, "0000", 1, 0, 4, 0, 1),
+        _look_line(399, 0, 0, "0000", 1, 0, 4, 0, 0),
+        _look_line(400, 1, 0, "0000", 1, 0, 8, 400, 1),
+        _look_line(1199, 0, 0, "0000", 1, 0, 8, 400, 1),
+        _look_line(1200, 1, 0, "0000", 1, 0, 16, 1200, 1),
+        _look_line(2799, 0, 0, "0000", 1, 0, 16, 1200, 1),
+        _look_line(2800, 1, 0, "0000", 1, 0, 16, 2800, 1),
+        _look_line(4399, 0, 0, "0000", 1, 0, 16, 2800, 1),
+        _look_line(4400, 1, 0, "0000", 1, 0, 16, 4400, 1),
+        _look_line(100, 1, 0, "0000", 1, 0, 16, 100, 0),     # attempts went backwards: the marks move, nothing else
+        _look_line(200, 0, 0, "111", 1, 0, 4, 0, 1)],        # three replicas now: from the start (AUTO starting on rows)
+}
+
+
+@pytest.mark.skipif(shutil.which("g++") is None, reason="needs g++")
+def test_sweep_time_routing_policy_over_scripted_counters(tmp_path):
+    """tests/c_abi/route_look.cpp drives sga_route::clf_looks and look (plain C++, no device call) through counter
+    sequences that sit on and beside every threshold; its print is compared with LOOK_EXPECTED."""
+    csrc = os.path.join(ROOT, "spin-glass-anneal-rl_amd", "csrc")
+    exe = str(tmp_path / "route_look")
+    subprocess.run(["g++", "-std=c++17", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), "-I", csrc,
+                    os.path.join(ROOT, "tests", "c_abi", "route_look.cpp"), "-o", exe, "-L", csrc, "-lsga",
+                    "-Wl,-rpath," + csrc, "-Wl,-rpath,/opt/rocm/lib"], check=True, capture_output=True)
+    out = subprocess.run([exe], check=True, capture_output=True, text=True).stdout
+    got, name = {}, None
+    for line in out.splitlines():
+        if line.startswith("# "):
+            name = line[2:]
+            got[name] = []
+        else:
+            got[name].append(line)
+    assert list(got) == list(LOOK_EXPECTED)
+    for name, lines in LOOK_EXPECTED.items():
+        assert got[name] == lines, name
