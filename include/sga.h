@@ -80,7 +80,7 @@ typedef struct sga_engine sga_engine;
 int sga_create(int device, sga_engine **out);
 void sga_destroy(sga_engine *e);
 const char *sga_last_error(void);
-int sga_version(void);  /* 1100: option "ragged_field_cache" (cached local fields for ragged CSR batches); 1000: sga_set_groups */
+int sga_version(void);  /* 1200: sga_set_groups_csr (group couplings plus a stored sparse remainder); 1100: option "ragged_field_cache" (cached local fields for ragged CSR batches); 1000: sga_set_groups */
 /* Run on an existing HIP stream (e.g. torch.cuda.current_stream().cuda_stream); NULL = the
  * engine's own stream (default). */
 int sga_set_stream(sga_engine *e, void *hip_stream);
@@ -197,6 +197,33 @@ int sga_set_tsp(sga_engine *e, const float *dist, int64_t ld, int n_cities, floa
 #define SGA_GROUPS_MAX_MEMBERSHIPS 64
 int sga_set_groups(sga_engine *e, int n, int n_groups, const int64_t *member_ptr, const int32_t *members,
                    const float *coeff, const float *h);
+
+/* Group couplings plus a stored sparse remainder (version >= 1200): cardinality constraints as groups, the
+ * comparatively few explicit pair couplings of the objective (precedence, edge conflicts, flow terms) as a CSR matrix R:
+ *     J_ij = sum_{g contains i and j} coeff[g] + R_ij   (i != j),   J_ii = 0
+ *     sum_j J_ij s_j = sum_{g contains i} coeff[g] (S_g - s_i) + sum_j R_ij s_j.
+ * The constraint part costs no coupling bytes, as in sga_set_groups; R stays in HBM as rptr [n + 1] int32 and (column,
+ * value) entries of 8 bytes.  A candidate's remainder row is walked by one lane, once per window; every accept then
+ * costs each undecided candidate one binary search (<= 8 probes) in its own row.  rowptr [n + 1], colidx / val [nnz]:
+ * host or device arrays, not referenced after the call.  n_groups = 0 with nnz > 0 is legal; nnz = 0 IS sga_set_groups
+ * (same kernels, same chain, same sga_describe line).  The group checks are sga_set_groups's.  For R:
+ *   SGA_ERR_INVALID: extents that are not monotone or do not span [0, nnz), a column outside [0, n), a value that is
+ *   not finite.
+ *   SGA_ERR_UNSUPPORTED (sga_last_error names the reason; sga_set_csr on the materialised couplings serves them all):
+ *   - a non-zero diagonal entry; R not symmetric; a row not strictly sorted by column (duplicates included);
+ *   - a row of more than SGA_GROUPS_MAX_REST_ROW entries (a declared limit of the form: one lane walks a row);
+ *   - nnz >= 2^31;
+ *   - couplings not provably exact in fp32 in any order: every coeff[g] and every val must be an integer multiple of
+ *     one 2^-k with 2^k max_i (sum_{g contains i} |coeff[g]| (|g| - 1) + sum_j |R_ij|) < 2^24.  Under it every partial
+ *     sum is exact, the materialised J_ij is itself exact in fp32 and the stored forms' fp32 row sum is the same number:
+ *     the chain is sga_set_csr's bit for bit.  A remainder that alone breaks the bound is refused, and so is an
+ *     off-grid value (0.1 beside other couplings).
+ * Works and is refused as for sga_set_groups; the checksum covers rptr, columns and values; sga_describe reads
+ * "groups ... rest_nnz=... rest_max_row=... path=groups acc=f32-exact". */
+#define SGA_GROUPS_MAX_REST_ROW 256
+int sga_set_groups_csr(sga_engine *e, int n, int n_groups, const int64_t *member_ptr, const int32_t *members,
+                       const float *coeff, const int32_t *rowptr, const int32_t *colidx, const float *val,
+                       int64_t nnz, const float *h);
 
 /* ---- replicas ------------------------------------------------------------------------- */
 /* R_local replicas live on this engine; they are replicas [replica0, replica0+R_local) of a
@@ -551,12 +578,17 @@ typedef struct sga_route_query {
     /* sga_set_groups (version >= 1000) */
     int32_t n_groups;     /* groups */
     int32_t group_max;    /* members of the largest group */
+    /* sga_set_groups_csr (version >= 1200): the stored remainder, 0 = none */
+    int64_t rest_nnz;     /* entries */
+    int32_t rest_max_row; /* entries of the longest row */
+    int32_t reserved2_;
 } sga_route_query;
 /* zeroes *q and fills the option defaults (the environment is NOT consulted), cus = 256, n_models = 1 */
 int sga_route_query_init(sga_route_query *q);
 /* one line naming every decision for q: "dense storage=... waves=... chunks_per_wave=... kernel=..." |
  * "csr form=rows|narrow|narrow-bits|wide-bits|wide-bytes spins=... waves=... updates_per_step=..." | "tsp waves=... passes=..." |
  * "groups n_groups=... sums=int16|int32 waves=... kernel=sweep_groups_kernel|sweep_groups_general_kernel"
+ * (with a stored remainder, rest_nnz > 0: " rest_nnz=... rest_max_row=..." behind it)
  * followed by " cached=..." (what sga_set_field_cache would run).  Pure: no device needed. */
 int sga_explain_route(const sga_route_query *q, char *buf, int buflen);
 /* the query the engine itself would pose for its current problem / replicas / options */

@@ -21,8 +21,10 @@ sys.path.insert(0, ROOT)
 import spin_glass_anneal_rl_amd as sg  # noqa: E402
 from spin_glass_anneal_rl_amd import _native as N  # noqa: E402
 
-# (n_groups / group_max: appended for sga_set_groups queries, 0 for every problem of this table -- dense, CSR, TSP)
-FIELDS = [f for f, _ in N.RouteQuery._fields_ if f not in ("opt", "reserved_", "n_groups", "group_max")]
+# (n_groups / group_max, rest_nnz / rest_max_row: appended for sga_set_groups / sga_set_groups_csr queries, 0 for every
+# problem of this table -- dense, CSR, TSP)
+FIELDS = [f for f, _ in N.RouteQuery._fields_
+          if f not in ("opt", "reserved_", "n_groups", "group_max", "rest_nnz", "rest_max_row", "reserved2_")]
 
 
 def query_dict(q):

@@ -23,6 +23,7 @@ _p, _i, _i64, _u64, _u32, _d = C.c_void_p, C.c_int, C.c_int64, C.c_uint64, C.c_u
 ROUTE_DENSE, ROUTE_CSR, ROUTE_TSP, ROUTE_GROUPS = 0, 1, 2, 3
 ROUTE_MAX_OPTS = 32
 GROUPS_MAX_MEMBERSHIPS = 64  # SGA_GROUPS_MAX_MEMBERSHIPS
+GROUPS_MAX_REST_ROW = 256    # SGA_GROUPS_MAX_REST_ROW
 
 
 class RouteQuery(C.Structure):
@@ -33,7 +34,8 @@ class RouteQuery(C.Structure):
                [("nnz", C.c_int64), ("max_row_len", C.c_int64), ("layout_entries", C.c_int64)] + \
                [(k, C.c_int32) for k in ("slotted", "rowptr32", "packed_ok", "n_cities", "sstride", "reserved_")] + \
                [("ldj", C.c_int64), ("opt", C.c_int64 * ROUTE_MAX_OPTS)] + \
-               [("n_groups", C.c_int32), ("group_max", C.c_int32)]
+               [("n_groups", C.c_int32), ("group_max", C.c_int32)] + \
+               [("rest_nnz", C.c_int64), ("rest_max_row", C.c_int32), ("reserved2_", C.c_int32)]
 
 
 # every symbol include/sga.h declares: (name, restype, argtypes)
@@ -56,6 +58,7 @@ SYMBOLS = [
     ("sga_get_batch_model", _i, [_p, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
     ("sga_set_tsp", _i, [_p, _p, _i64, _i, C.c_float, C.c_float, _p]),
     ("sga_set_groups", _i, [_p, _i, _i, _p, _p, _p, _p]),
+    ("sga_set_groups_csr", _i, [_p, _i, _i, _p, _p, _p, _p, _p, _p, _i64, _p]),
     ("sga_init_replicas", _i, [_p, _i, _i, _i, _u64, _p]),
     ("sga_set_temperatures", _i, [_p, _p]),
     ("sga_set_ladder", _i, [_p, _p, _i]),

@@ -181,6 +181,8 @@ struct sga_engine {
     int2 *g_gent = nullptr;
     long long *g_member_ptr = nullptr;
     float *g_coeff = nullptr;  // [n_groups] as handed over (checksum)
+    int *g_rptr = nullptr;     // the stored remainder of sga_set_groups_csr (null: none): extents [n + 1] ...
+    int2 *g_rent = nullptr;    // ... and (column, value bits) entries; counts in group_args.rest
     long long g_memberships = 0;  // entries of the site -> group table
     int g_max_size = 0, g_kmax = 0, g_exp = 0;  // largest group, most memberships of one site, k of the 2^-k grid
     sga::GroupArgs group_args{};
@@ -312,6 +314,8 @@ struct sga_engine {
         dev_free(g_gent);
         dev_free(g_member_ptr);
         dev_free(g_coeff);
+        dev_free(g_rptr);
+        dev_free(g_rent);
         groups = false;
         group_args = sga::GroupArgs{};
         dev_free(epart);

@@ -117,10 +117,21 @@ struct GroupArgs {
     const int2 *gent;             // [gptr[n]] (group, coefficient bits) interleaved; never empty (one zero entry at least)
     const long long *member_ptr;  // [n_groups + 1] group -> its members
     const int *members;
-    int n_groups;                 // >= 1
+    int n_groups;                 // >= 1 (0 only with a remainder)
     int wide;                     // 0: S_g as int16 in LDS (every group below 2^15 members) | 1: int32
+    // the stored sparse remainder R of sga_set_groups_csr (J_ij = sum_g c_g + R_ij): symmetric, zero diagonal, rows
+    // strictly sorted by column and at most GROUPS_MAX_REST_ROW long.  nnz == 0: no remainder, the REST = false kernels
+    struct Rest {
+        const int *rptr;   // [n + 1]
+        const int2 *rent;  // [nnz] (column, value bits) interleaved
+        long long nnz;
+        int max_row;       // entries of the longest row
+    } rest;
 };
 constexpr int GROUPS_MAX_MEMBERSHIPS = 64;  // groups one site may belong to (include/sga.h)
+constexpr int GROUPS_MAX_REST_ROW = 256;    // entries of one remainder row (include/sga.h)
+// per-row sum_j |R_ij| of a remainder (set-time bound of sga_set_groups_csr), one wave per row
+hipError_t launch_groups_rest_row_abs(const long long *rowptr, const float *val, int n, double *out, hipStream_t st);
 size_t groups_lds_bytes(int sstride, int n_groups, int wide);
 size_t groups_energy_lds_bytes(int sstride, int n_groups, int wide);
 hipError_t launch_sweep_groups(const SweepArgs &a, const GroupArgs &g, int waves, hipStream_t st);

@@ -676,29 +676,59 @@ int sga_set_tsp(sga_engine *e, const float *dist, int64_t ld, int n_cities, floa
     return SGA_OK;
 }
 
-// Couplings as a sum of complete graphs on groups, never stored (sweep_groups.hip).  Everything is checked on the host
-// (the tables are a few bytes per membership): structure, then the proof that a row sum is exact in fp32 in any order.
-int sga_set_groups(sga_engine *e, int n, int n_groups, const int64_t *member_ptr, const int32_t *members, const float *coeff,
-                   const float *h) {
+}  // extern "C"
+
+namespace {
+
+// what the remainder of sga_set_groups_csr leaves on the device while it is checked; released on every way out
+struct RestStage {
+    long long *rowptr64 = nullptr;
+    int32_t *rowptr32 = nullptr, *colidx = nullptr;
+    float *val = nullptr, *h = nullptr;
+    double *row_abs = nullptr;
+    int *rptr = nullptr;
+    int2 *rent = nullptr;
+    ~RestStage() {
+        dev_free(rowptr64), dev_free(rowptr32), dev_free(colidx), dev_free(val), dev_free(h), dev_free(row_abs);
+        dev_free(rptr), dev_free(rent);
+    }
+};
+
+// Couplings as a sum of complete graphs on groups, never stored (sweep_groups.hip), plus -- sga_set_groups_csr, nnz > 0 --
+// a stored sparse remainder.  The group tables are checked on the host (a few bytes per membership); the remainder is
+// scanned where it lies, by the CSR scan kernels of sga_set_csr (extents, columns, diagonal, ordering, symmetry, grid)
+// and one pass for sum_j |R_ij| per row.  Then the proof that a combined row sum is exact in fp32 in any order.
+// `who`: the call the messages name.
+int set_groups_common(sga_engine *e, const char *who_, int n, int n_groups, const int64_t *member_ptr, const int32_t *members,
+                      const float *coeff, const int32_t *rowptr, const int32_t *colidx, const float *val, int64_t nnz,
+                      const float *h) {
+    const std::string who = who_;
+    const bool rest = nnz > 0;
     if (!e) return fail(SGA_ERR_INVALID, "engine is NULL");
     if (n <= 0 || !h) return fail(SGA_ERR_INVALID, "bad group problem arguments");
-    if (n_groups <= 0 || !member_ptr || !coeff) return fail(SGA_ERR_INVALID, "sga_set_groups: the extent table is empty (no groups)");
+    if (nnz < 0 || (rest && (!rowptr || !colidx || !val))) return fail(SGA_ERR_INVALID, who + ": bad remainder arguments");
+    if (n_groups < 0 || (n_groups == 0 && !rest) || (n_groups > 0 && (!member_ptr || !coeff)))
+        return fail(SGA_ERR_INVALID, who + ": the extent table is empty (no groups)");
+    if (nnz >= (int64_t)INT32_MAX)
+        return fail(SGA_ERR_UNSUPPORTED, who + ": the remainder has 2^31 entries or more -- materialise the couplings and use sga_set_csr");
     HIPCHK(hipSetDevice(e->device));
     HIPCHK(hipStreamSynchronize(e->stream));
     e->free_replicas();
     e->free_problem();
     e->opt_stale = 0;
     const size_t G = (size_t)n_groups;
-    std::vector<long long> mp(G + 1);
+    std::vector<long long> mp(G + 1, 0);
     std::vector<float> cf(G), hh((size_t)n);
-    HIPCHK(hipMemcpy(mp.data(), member_ptr, sizeof(long long) * (G + 1), hipMemcpyDefault));
-    HIPCHK(hipMemcpy(cf.data(), coeff, sizeof(float) * G, hipMemcpyDefault));
+    if (G > 0) {
+        HIPCHK(hipMemcpy(mp.data(), member_ptr, sizeof(long long) * (G + 1), hipMemcpyDefault));
+        HIPCHK(hipMemcpy(cf.data(), coeff, sizeof(float) * G, hipMemcpyDefault));
+    }
     HIPCHK(hipMemcpy(hh.data(), h, sizeof(float) * (size_t)n, hipMemcpyDefault));
-    if (mp[0] != 0) return fail(SGA_ERR_INVALID, "sga_set_groups: member_ptr[0] != 0");
+    if (mp[0] != 0) return fail(SGA_ERR_INVALID, who + ": member_ptr[0] != 0");
     for (size_t q = 0; q < G; ++q)
-        if (mp[q + 1] < mp[q]) return fail(SGA_ERR_INVALID, "sga_set_groups: member_ptr is not monotone at group " + std::to_string(q));
+        if (mp[q + 1] < mp[q]) return fail(SGA_ERR_INVALID, who + ": member_ptr is not monotone at group " + std::to_string(q));
     const long long M = mp[G];
-    if (M >= (long long)INT32_MAX) return fail(SGA_ERR_UNSUPPORTED, "sga_set_groups: 2^31 memberships or more (use sga_set_csr)");
+    if (M >= (long long)INT32_MAX) return fail(SGA_ERR_UNSUPPORTED, who + ": 2^31 memberships or more (use sga_set_csr)");
     if (M > 0 && !members) return fail(SGA_ERR_INVALID, "bad group problem arguments");
     std::vector<int32_t> mem((size_t)std::max<long long>(M, 1), 0);
     if (M > 0) HIPCHK(hipMemcpy(mem.data(), members, sizeof(int32_t) * (size_t)M, hipMemcpyDefault));
@@ -706,15 +736,15 @@ int sga_set_groups(sga_engine *e, int n, int n_groups, const int64_t *member_ptr
     std::vector<int> count((size_t)n + 1, 0), seen((size_t)n, -1);
     long long max_size = 0;
     for (size_t q = 0; q < G; ++q) {
-        if (!std::isfinite(cf[q])) return fail(SGA_ERR_INVALID, "sga_set_groups: coefficient of group " + std::to_string(q) + " is not finite");
+        if (!std::isfinite(cf[q])) return fail(SGA_ERR_INVALID, who + ": coefficient of group " + std::to_string(q) + " is not finite");
         max_size = std::max(max_size, mp[q + 1] - mp[q]);
         for (long long m = mp[q]; m < mp[q + 1]; ++m) {
             const int i = mem[(size_t)m];
             if (i < 0 || i >= n)
-                return fail(SGA_ERR_INVALID, "sga_set_groups: member " + std::to_string(i) + " of group " + std::to_string(q) +
+                return fail(SGA_ERR_INVALID, who + ": member " + std::to_string(i) + " of group " + std::to_string(q) +
                                                  " is out of range [0, " + std::to_string(n) + ")");
             if (seen[(size_t)i] == (int)q)
-                return fail(SGA_ERR_INVALID, "sga_set_groups: site " + std::to_string(i) + " is repeated inside group " + std::to_string(q));
+                return fail(SGA_ERR_INVALID, who + ": site " + std::to_string(i) + " is repeated inside group " + std::to_string(q));
             seen[(size_t)i] = (int)q;
             ++count[(size_t)i + 1];
         }
@@ -733,9 +763,77 @@ int sga_set_groups(sga_engine *e, int n, int n_groups, const int64_t *member_ptr
         }
         k = std::max(k, -(ex - 24 + low));
     }
-    if (k == -1000) k = 0;
     std::vector<double> bound((size_t)n, 0.0);
     int kmax = 0;
+    // the remainder: structure scans on the device (sga_set_csr's kernels), then its grid and sum_j |R_ij| per row
+    RestStage rs;
+    int rest_max_row = 0;
+    if (rest) {
+        const size_t np1 = (size_t)n + 1, nz = (size_t)nnz;
+        std::vector<int32_t> rp(np1);
+        HIPCHK(hipMemcpy(rp.data(), rowptr, sizeof(int32_t) * np1, hipMemcpyDefault));
+        HIPCHK(hipMalloc(&rs.rowptr32, sizeof(int32_t) * np1));
+        HIPCHK(hipMalloc(&rs.rowptr64, sizeof(long long) * np1));
+        HIPCHK(hipMemcpyAsync(rs.rowptr32, rp.data(), sizeof(int32_t) * np1, hipMemcpyHostToDevice, e->stream));
+        HIPCHK(sga::launch_widen_rowptr(rs.rowptr32, rs.rowptr64, (long long)np1, e->stream));
+        const int32_t *ci = colidx;
+        const float *vv = val;
+        if (!is_device_ptr(colidx)) {
+            HIPCHK(hipMalloc(&rs.colidx, sizeof(int32_t) * nz));
+            HIPCHK(hipMemcpyAsync(rs.colidx, colidx, sizeof(int32_t) * nz, hipMemcpyHostToDevice, e->stream));
+            ci = rs.colidx;
+        }
+        if (!is_device_ptr(val)) {
+            HIPCHK(hipMalloc(&rs.val, sizeof(float) * nz));
+            HIPCHK(hipMemcpyAsync(rs.val, val, sizeof(float) * nz, hipMemcpyHostToDevice, e->stream));
+            vv = rs.val;
+        }
+        HIPCHK(hipMalloc(&rs.h, sizeof(float) * (size_t)n));
+        HIPCHK(hipMemcpyAsync(rs.h, hh.data(), sizeof(float) * (size_t)n, hipMemcpyHostToDevice, e->stream));
+        int *d_flags = e->d_flags;
+        int flags[sga::CSR_FLAG_COUNT] = {0};
+        auto read_flags = [&]() -> hipError_t {
+            hipError_t he = hipMemcpyAsync(flags, d_flags, sizeof(flags), hipMemcpyDeviceToHost, e->stream);
+            return he == hipSuccess ? hipStreamSynchronize(e->stream) : he;
+        };
+        HIPCHK(hipMemsetAsync(d_flags, 0, sizeof(flags), e->stream));
+        HIPCHK(sga::launch_csr_check_rowptr(rs.rowptr64, n, nnz, d_flags, e->stream));
+        HIPCHK(read_flags());
+        if (flags[sga::CSR_BAD_ROWPTR])
+            return fail(SGA_ERR_INVALID, who + ": the remainder's rowptr is not monotone or does not span [0, nnz]");
+        HIPCHK(sga::launch_csr_scan(rs.rowptr64, ci, vv, rs.h, n, d_flags, e->stream));
+        HIPCHK(read_flags());
+        if (flags[sga::CSR_BAD_COLUMN])
+            return fail(SGA_ERR_INVALID, who + ": a remainder column index is out of range [0, " + std::to_string(n) + ")");
+        const std::string way_out = " -- materialise the couplings and use sga_set_csr";
+        if (flags[sga::CSR_DIAGONAL])
+            return fail(SGA_ERR_UNSUPPORTED, who + ": the remainder has a non-zero diagonal entry" + way_out);
+        if (flags[sga::CSR_UNSORTED])
+            return fail(SGA_ERR_UNSUPPORTED, who + ": a remainder row is not strictly sorted by column (unsorted or duplicate "
+                                                   "entries)" + way_out);
+        HIPCHK(sga::launch_csr_symmetry(rs.rowptr64, ci, vv, n, true, d_flags, e->stream));
+        HIPCHK(read_flags());
+        if (flags[sga::CSR_ASYMMETRIC]) return fail(SGA_ERR_UNSUPPORTED, who + ": the remainder is not symmetric" + way_out);
+        for (int i = 0; i < n; ++i) rest_max_row = std::max(rest_max_row, rp[(size_t)i + 1] - rp[(size_t)i]);
+        if (rest_max_row > SGA_GROUPS_MAX_REST_ROW) {
+            char msg[256];
+            std::snprintf(msg, sizeof(msg), "%s: a remainder row has %d entries, more than SGA_GROUPS_MAX_REST_ROW = %d%s", who_,
+                          rest_max_row, SGA_GROUPS_MAX_REST_ROW, way_out.c_str());
+            return fail(SGA_ERR_UNSUPPORTED, msg);
+        }
+        if (flags[sga::CSR_EXP_LO]) k = std::max(k, flags[sga::CSR_EXP_LO] - 1024);  // the finest grid any R_ij needs
+        HIPCHK(hipMalloc(&rs.row_abs, sizeof(double) * (size_t)n));
+        HIPCHK(sga::launch_groups_rest_row_abs(rs.rowptr64, vv, n, rs.row_abs, e->stream));
+        HIPCHK(hipMemcpyAsync(bound.data(), rs.row_abs, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, e->stream));
+        // the layout the kernels read: 32-bit extents, (column, value bits) interleaved
+        HIPCHK(hipMalloc(&rs.rent, sizeof(int2) * nz));
+        HIPCHK(sga::launch_pack_cv_rows(rs.rowptr64, rs.rowptr64, ci, vv, nullptr, rs.rent, n, e->stream));
+        HIPCHK(hipStreamSynchronize(e->stream));
+        for (int i = 0; i < n; ++i)
+            if (!std::isfinite(bound[(size_t)i]))
+                return fail(SGA_ERR_INVALID, who + ": remainder row " + std::to_string(i) + " holds a value that is not finite");
+    }
+    if (k == -1000) k = 0;
     for (size_t q = 0; q < G; ++q) {
         const double term = std::fabs((double)cf[q]) * (double)(mp[q + 1] - mp[q] - 1);
         for (long long m = mp[q]; m < mp[q + 1]; ++m) bound[(size_t)mem[(size_t)m]] += term;
@@ -748,15 +846,15 @@ int sga_set_groups(sga_engine *e, int n, int n_groups, const int64_t *member_ptr
     if (k > 126 || std::ldexp(worst, k) >= 16777216.0) {
         char msg[320];
         std::snprintf(msg, sizeof(msg),
-                      "sga_set_groups: the couplings are not provably exact in fp32: the coefficients lie on the grid 2^%d and "
-                      "max_i sum_j |J_ij| = %.6g of its units is not below 2^24 -- materialise them and use sga_set_csr", -k,
-                      std::ldexp(worst, std::min(k, 126)));
+                      "%s: the couplings are not provably exact in fp32: the coefficients%s lie on the grid 2^%d and "
+                      "max_i sum_j |J_ij| = %.6g of its units is not below 2^24 -- materialise them and use sga_set_csr", who_,
+                      rest ? " and remainder values" : "", -k, std::ldexp(worst, std::min(k, 126)));
         return fail(SGA_ERR_UNSUPPORTED, msg);
     }
     if (kmax > SGA_GROUPS_MAX_MEMBERSHIPS) {
         char msg[256];
-        std::snprintf(msg, sizeof(msg), "sga_set_groups: a site belongs to %d groups, more than SGA_GROUPS_MAX_MEMBERSHIPS = %d -- "
-                      "materialise the couplings and use sga_set_csr", kmax, SGA_GROUPS_MAX_MEMBERSHIPS);
+        std::snprintf(msg, sizeof(msg), "%s: a site belongs to %d groups, more than SGA_GROUPS_MAX_MEMBERSHIPS = %d -- "
+                      "materialise the couplings and use sga_set_csr", who_, kmax, SGA_GROUPS_MAX_MEMBERSHIPS);
         return fail(SGA_ERR_UNSUPPORTED, msg);
     }
     {
@@ -767,7 +865,7 @@ int sga_set_groups(sga_engine *e, int n, int n_groups, const int64_t *member_ptr
         q.n_groups = n_groups;
         q.group_max = (int32_t)max_size;
         const sga_route::GroupsForm f = sga_route::groups_form(q);
-        if (f.error) return fail(SGA_ERR_UNSUPPORTED, std::string("sga_set_groups: ") + f.error + " -- use sga_set_csr");
+        if (f.error) return fail(SGA_ERR_UNSUPPORTED, who + ": " + f.error + " -- use sga_set_csr");
     }
     // site -> group table, groups of a site in group order; one zero entry behind (the kernels' padding entry)
     std::vector<int> gptr((size_t)n + 1, 0);
@@ -783,13 +881,13 @@ int sga_set_groups(sga_engine *e, int n, int n_groups, const int64_t *member_ptr
     HIPCHK(hipMalloc(&e->g_gent, sizeof(int2) * ((size_t)M + 1)));
     HIPCHK(hipMalloc(&e->g_member_ptr, sizeof(long long) * (G + 1)));
     HIPCHK(hipMalloc(&e->g_members, sizeof(int) * (size_t)std::max<long long>(M, 1)));
-    HIPCHK(hipMalloc(&e->g_coeff, sizeof(float) * G));
+    HIPCHK(hipMalloc(&e->g_coeff, sizeof(float) * std::max<size_t>(G, 1)));
     HIPCHK(hipMalloc(&e->h, sizeof(float) * (size_t)n));
     HIPCHK(hipMemcpyAsync(e->g_gptr, gptr.data(), sizeof(int) * ((size_t)n + 1), hipMemcpyHostToDevice, e->stream));
     HIPCHK(hipMemcpyAsync(e->g_gent, gent.data(), sizeof(int2) * ((size_t)M + 1), hipMemcpyHostToDevice, e->stream));
     HIPCHK(hipMemcpyAsync(e->g_member_ptr, mp.data(), sizeof(long long) * (G + 1), hipMemcpyHostToDevice, e->stream));
     HIPCHK(hipMemcpyAsync(e->g_members, mem.data(), sizeof(int) * mem.size(), hipMemcpyHostToDevice, e->stream));
-    HIPCHK(hipMemcpyAsync(e->g_coeff, cf.data(), sizeof(float) * G, hipMemcpyHostToDevice, e->stream));
+    if (G > 0) HIPCHK(hipMemcpyAsync(e->g_coeff, cf.data(), sizeof(float) * G, hipMemcpyHostToDevice, e->stream));
     HIPCHK(hipMemcpyAsync(e->h, hh.data(), sizeof(float) * (size_t)n, hipMemcpyHostToDevice, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
     e->groups = true;
@@ -798,15 +896,42 @@ int sga_set_groups(sga_engine *e, int n, int n_groups, const int64_t *member_ptr
     e->n_models = 1;
     long long pairs = 0;
     for (size_t q = 0; q < G; ++q) pairs += (mp[q + 1] - mp[q]) * (mp[q + 1] - mp[q] - 1);
-    e->nnz = pairs;  // entries of the materialised couplings, overlaps counted once per group
+    e->nnz = pairs + nnz;  // entries of the materialised couplings, overlaps counted once per group (and per remainder entry)
     e->consistent_dE = true;  // symmetric with a zero diagonal by construction
     e->table_m = 0;
     e->g_memberships = M;
     e->g_max_size = (int)max_size;
     e->g_kmax = kmax;
     e->g_exp = k;
-    e->group_args = sga::GroupArgs{e->g_gptr, e->g_gent, e->g_member_ptr, e->g_members, n_groups, max_size >= (1 << 15) ? 1 : 0};
+    e->group_args = sga::GroupArgs{e->g_gptr, e->g_gent, e->g_member_ptr, e->g_members, n_groups, max_size >= (1 << 15) ? 1 : 0,
+                                   {nullptr, nullptr, 0, 0}};
+    if (rest) {  // the staged layout becomes the engine's
+        e->g_rptr = reinterpret_cast<int *>(rs.rowptr32);
+        e->g_rent = rs.rent;
+        rs.rowptr32 = nullptr;
+        rs.rent = nullptr;
+        e->group_args.rest = sga::GroupArgs::Rest{e->g_rptr, e->g_rent, (long long)nnz, rest_max_row};
+    }
     return SGA_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sga_set_groups(sga_engine *e, int n, int n_groups, const int64_t *member_ptr, const int32_t *members, const float *coeff,
+                   const float *h) {
+    if (n_groups <= 0 || !member_ptr || !coeff) {
+        if (!e) return fail(SGA_ERR_INVALID, "engine is NULL");
+        if (n <= 0 || !h) return fail(SGA_ERR_INVALID, "bad group problem arguments");
+        return fail(SGA_ERR_INVALID, "sga_set_groups: the extent table is empty (no groups)");
+    }
+    return set_groups_common(e, "sga_set_groups", n, n_groups, member_ptr, members, coeff, nullptr, nullptr, nullptr, 0, h);
+}
+
+int sga_set_groups_csr(sga_engine *e, int n, int n_groups, const int64_t *member_ptr, const int32_t *members, const float *coeff,
+                       const int32_t *rowptr, const int32_t *colidx, const float *val, int64_t nnz, const float *h) {
+    return set_groups_common(e, "sga_set_groups_csr", n, n_groups, member_ptr, members, coeff, rowptr, colidx, val, nnz, h);
 }
 
 // Ragged CSR batches: M independent problems of any sizes in one engine, their rows concatenated (model m owns rows

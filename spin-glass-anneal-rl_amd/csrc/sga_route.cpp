@@ -606,6 +606,10 @@ std::string explain(const Query &q0) {
                       q.n_groups, q.group_max, f.wide ? "int32" : "int16", general ? 1 : f.waves, f.sstride, f.lds_bytes,
                       general ? "sweep_groups_general_kernel" : "sweep_groups_kernel|sweep_groups_general_kernel");
         out = buf;
+        if (q.rest_nnz > 0) {  // sga_set_groups_csr: the stored remainder
+            std::snprintf(buf, sizeof(buf), " rest_nnz=%lld rest_max_row=%d", (long long)q.rest_nnz, q.rest_max_row);
+            out += buf;
+        }
         q.sstride = f.sstride;
     } else if (q.kind == SGA_ROUTE_TSP) {
         const int npad = 256 * ((q.n_cities + 255) / 256);
@@ -720,7 +724,7 @@ int sga_route_query_init(sga_route_query *q) {
 int sga_explain_route(const sga_route_query *q, char *buf, int buflen) {
     if (!q || !buf || buflen <= 0) return sga_impl::fail(SGA_ERR_INVALID, "bad arguments");
     if (q->n <= 0 || q->kind < SGA_ROUTE_DENSE || q->kind > SGA_ROUTE_GROUPS || (q->kind == SGA_ROUTE_TSP && q->n_cities < 3) ||
-        (q->kind == SGA_ROUTE_GROUPS && q->n_groups < 1))
+        (q->kind == SGA_ROUTE_GROUPS && (q->n_groups < 0 || (q->n_groups < 1 && q->rest_nnz < 1))))
         return sga_impl::fail(SGA_ERR_INVALID, "route query: kind / n out of range");
     std::snprintf(buf, (size_t)buflen, "%s", sga_route::explain(*q).c_str());
     return SGA_OK;

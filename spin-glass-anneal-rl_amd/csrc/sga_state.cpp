@@ -335,14 +335,19 @@ int sga_get_kernel_time(sga_engine *e, int64_t *n_launches, double *total_ms, in
 
 int sga_describe(sga_engine *e, char *buf, int buflen) {
     if (!e || !buf || buflen <= 0) return fail(SGA_ERR_INVALID, "bad arguments");
-    char tmp[512];
+    char tmp[640];
+    char rest[96] = "";  // sga_set_groups_csr: the stored remainder
+    if (e->groups && e->group_args.rest.nnz > 0)
+        std::snprintf(rest, sizeof(rest), " rest_nnz=%lld rest_max_row=%d", e->group_args.rest.nnz, e->group_args.rest.max_row);
     if (e->groups)
         std::snprintf(tmp, sizeof(tmp),
-                      "groups n=%d n_groups=%d largest_group=%d memberships=%lld max_memberships=%d R=%d waves_per_replica=%d "
-                      "sstride=%d path=groups couplings=implicit (group sums as %s in LDS, 0 coupling bytes per proposal) "
+                      "groups n=%d n_groups=%d largest_group=%d memberships=%lld max_memberships=%d%s R=%d waves_per_replica=%d "
+                      "sstride=%d path=groups couplings=implicit (group sums as %s in LDS, 0 coupling bytes per proposal%s) "
                       "acc=f32-exact grid=2^%d lds_bytes=%zu",
-                      e->n, e->group_args.n_groups, e->g_max_size, e->g_memberships, e->g_kmax, e->R, e->waves, e->sstride,
-                      e->group_args.wide ? "int32" : "int16", -e->g_exp,
+                      e->n, e->group_args.n_groups, e->g_max_size, e->g_memberships, e->g_kmax, rest, e->R, e->waves, e->sstride,
+                      e->group_args.wide ? "int32" : "int16",
+                      e->group_args.rest.nnz > 0 ? " for the groups; stored remainder rows walked once per candidate and window" : "",
+                      -e->g_exp,
                       sga::groups_lds_bytes(e->sstride > 0 ? e->sstride : (e->n + 127) / 128 * 128, e->group_args.n_groups,
                                             e->group_args.wide));
     else if (e->tsp)
@@ -491,7 +496,11 @@ int sga_problem_checksum(sga_engine *e, uint64_t *out) {
         const int G = e->group_args.n_groups;
         HIPCHK(sga::launch_checksum(e->g_member_ptr, 8ll * (G + 1), d, e->stream));
         if (e->g_memberships > 0) HIPCHK(sga::launch_checksum(e->g_members, 4ll * e->g_memberships, d, e->stream));
-        HIPCHK(sga::launch_checksum(e->g_coeff, 4ll * G, d, e->stream));
+        if (G > 0) HIPCHK(sga::launch_checksum(e->g_coeff, 4ll * G, d, e->stream));
+        if (e->group_args.rest.nnz > 0) {  // the stored remainder: extents, then (column, value) entries
+            HIPCHK(sga::launch_checksum(e->g_rptr, 4ll * (e->n + 1), d, e->stream));
+            HIPCHK(sga::launch_checksum(e->g_rent, 8ll * e->group_args.rest.nnz, d, e->stream));
+        }
     } else if (e->tsp) {
         const long long bytes = 4ll * e->tsp_args.n_cities * e->tsp_args.npad;
         HIPCHK(sga::launch_checksum(e->nd4, bytes, d, e->stream));

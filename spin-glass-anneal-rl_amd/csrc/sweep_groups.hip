@@ -21,6 +21,15 @@
 // evaluated again.  A super-window costs (accepts + 1) rounds whatever the number of proposals.
 // General form: one wave, one update at a time: sequential / replayed sites, Glauber / heat bath, fp32 operator
 // arithmetic, per-update traces.
+//
+// Stored remainder (sga_set_groups_csr, template flag REST): J_ij = sum_g c_g + R_ij with R a CSR matrix in HBM
+// (rptr[n + 1], (column, value bits) entries, rows strictly sorted, symmetric, zero diagonal, at most
+// GROUPS_MAX_REST_ROW entries per row).  The set-time bound covers both parts -- every c_g and R_ij a multiple of one
+// 2^-k, 2^k max_i (sum_g |c_g| (|g| - 1) + sum_j |R_ij|) < 2^24 -- so the combined row sum is exact in any order too.
+// The general, energy and field kernels add a walk of the site's remainder row against the spin bits.  The production
+// form walks a candidate's row ONCE per super-window (rd = sum_j R_ij s_j, in request()); an accept at site a is
+// published with its old spin, and every still-undecided candidate looks a up in its own sorted row (<= 8 probes)
+// and moves rd by -2 R_ia s_a: rounds stay (accepts + 1), not (accepts + 1) x row length.
 #include "sweep_common.h"
 
 namespace sga {
@@ -74,17 +83,40 @@ __device__ __forceinline__ void groups_apply(const GroupArgs &g, unsigned int *b
     }
 }
 
+// sum_j R_ij s_j of one site (one lane walks the row; exact under the set-time bound)
+__device__ __forceinline__ float groups_rest_row_sum(const GroupArgs &g, const unsigned int *bits, int site) {
+    float acc = 0.0f;
+    for (int m = g.rest.rptr[site]; m < g.rest.rptr[site + 1]; ++m) {
+        const int2 ent = g.rest.rent[m];
+        acc += ((bits[ent.x >> 5] >> (ent.x & 31)) & 1u) ? -__int_as_float(ent.y) : __int_as_float(ent.y);
+    }
+    return acc;
+}
+
+// R_ia of a strictly sorted remainder row [beg, beg + cnt): 0 when the row has no column a
+__device__ __forceinline__ float groups_rest_find(const GroupArgs &g, int beg, int cnt, int a) {
+    int lo = 0, hi = cnt;  // first entry with column >= a
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (g.rest.rent[beg + mid].x < a) lo = mid + 1;
+        else hi = mid;
+    }
+    if (lo >= cnt) return 0.0f;
+    const int2 ent = g.rest.rent[beg + lo];
+    return ent.x == a ? __int_as_float(ent.y) : 0.0f;
+}
+
 // ---------------------------------------------------------------------------------------
 // Production form
 // ---------------------------------------------------------------------------------------
-template <bool WIDE>
+template <bool WIDE, bool REST>
 __global__ void __launch_bounds__(64 * GROUPS_MAX_WAVES) sweep_groups_kernel(const SweepArgs a, const GroupArgs g) {
     using sum_t = typename GroupSums<WIDE>::type;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned int *bits = reinterpret_cast<unsigned int *>(smem);
     sum_t *sums = reinterpret_cast<sum_t *>(smem + a.sstride / 8);
     int *dec = reinterpret_cast<int *>(smem + a.sstride / 8 + (((size_t)g.n_groups * sizeof(sum_t) + 15) & ~(size_t)15));
-    int *won = dec + 2 * GROUPS_MAX_WAVES;  // [2][4]: dE of the applied update
+    int *won = dec + 2 * GROUPS_MAX_WAVES;  // [2][4]: dE of the applied update (REST: its site and old spin behind)
     const int tid = threadIdx.x, lane = tid & 63;
     const int W = (int)(blockDim.x >> 6);
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -107,6 +139,8 @@ __global__ void __launch_bounds__(64 * GROUPS_MAX_WAVES) sweep_groups_kernel(con
         int site, beg, cnt, live;
         float u, h;
         int2 ent[KR];
+        int rbeg, rcnt;  // REST: the site's remainder row ...
+        float rd;        // ... and sum_j R_ij s_j against the state as it stands (moved by every accept)
     };
     auto request = [&](Cand &c) {  // what the candidate's decisions need, fetched once per window
         c.beg = g.gptr[c.site];
@@ -115,6 +149,11 @@ __global__ void __launch_bounds__(64 * GROUPS_MAX_WAVES) sweep_groups_kernel(con
 #pragma unroll
         for (int q = 0; q < KR; ++q)  // past the site's memberships: group 0 with coefficient 0 adds an exact zero
             c.ent[q] = q < c.cnt ? g.gent[c.beg + q] : make_int2(0, 0);
+        if constexpr (REST) {  // the applies of the previous super-window are behind barrier (B)
+            c.rbeg = g.rest.rptr[c.site];
+            c.rcnt = g.rest.rptr[c.site + 1] - c.rbeg;
+            c.rd = c.live ? groups_rest_row_sum(g, bits, c.site) : 0.0f;
+        }
     };
     auto decide = [&](const Cand &c, int &si, double &dE) -> bool {
         si = ((bits[c.site >> 5] >> (c.site & 31)) & 1u) ? -1 : 1;
@@ -125,6 +164,7 @@ __global__ void __launch_bounds__(64 * GROUPS_MAX_WAVES) sweep_groups_kernel(con
             const int2 ent = g.gent[c.beg + q];
             acc += __int_as_float(ent.y) * (float)((int)sums[ent.x] - si);
         }
+        if constexpr (REST) acc += c.rd;
         return metropolis_accept(SGA_RULE_METROPOLIS, SGA_ARITH_F64, acc, si, c.h, 0.0f, T, c.u, dE);
     };
 
@@ -177,12 +217,22 @@ __global__ void __launch_bounds__(64 * GROUPS_MAX_WAVES) sweep_groups_kernel(con
                     const long long db = __double_as_longlong(second ? d1 : d0);
                     rec[0] = (int)(unsigned int)db;
                     rec[1] = (int)(db >> 32);
+                    if constexpr (REST) {
+                        rec[2] = site;
+                        rec[3] = si;
+                    }
                 }
                 __syncthreads();  // (B) the new state and the record are visible
                 E += __longlong_as_double((long long)(((unsigned long long)(unsigned int)rec[1] << 32) | (unsigned int)rec[0]));
                 ++nacc;
                 // waves before the accepting one are done, it goes on behind the accept, later ones start over
                 start = w < first_w ? 128 : (w == first_w ? first_i + 1 : 0);
+                if constexpr (REST) {  // the undecided candidates' remainder sums follow the flip of site a (diagonal 0)
+                    const int sa = rec[2];
+                    const float two_s = (float)(2 * rec[3]);
+                    if (c0.live && 2 * lane >= start && c0.rcnt > 0) c0.rd -= two_s * groups_rest_find(g, c0.rbeg, c0.rcnt, sa);
+                    if (c1.live && 2 * lane + 1 >= start && c1.rcnt > 0) c1.rd -= two_s * groups_rest_find(g, c1.rbeg, c1.rcnt, sa);
+                }
             }
         }
         if (tid == 0 && a.energy_trace) a.energy_trace[(long long)k * a.R + r] = E;
@@ -204,7 +254,7 @@ __global__ void __launch_bounds__(64 * GROUPS_MAX_WAVES) sweep_groups_kernel(con
 // ---------------------------------------------------------------------------------------
 // General form: one wave per replica, one update at a time; every lane walks the same chain
 // ---------------------------------------------------------------------------------------
-template <bool WIDE>
+template <bool WIDE, bool REST>
 __global__ void __launch_bounds__(64) sweep_groups_general_kernel(const SweepArgs a, const GroupArgs g) {
     using sum_t = typename GroupSums<WIDE>::type;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -229,7 +279,8 @@ __global__ void __launch_bounds__(64) sweep_groups_general_kernel(const SweepArg
             const int site = (t & 1) ? pr.sB : pr.sA;
             const float u = (t & 1) ? pr.uB : pr.uA;
             int si;
-            const float dot = groups_row_sum(g, bits, sums, site, si);
+            float dot = groups_row_sum(g, bits, sums, site, si);
+            if constexpr (REST) dot += groups_rest_row_sum(g, bits, site);
             double dE;
             const bool flip = metropolis_accept(rule, arith, dot, si, a.h[site], 0.0f, T, u, dE);
             __syncthreads();  // every lane has read the old state
@@ -262,22 +313,33 @@ __global__ void __launch_bounds__(64) sweep_groups_general_kernel(const SweepArg
 }
 
 hipError_t launch_sweep_groups(const SweepArgs &a, const GroupArgs &g, int waves, hipStream_t st) {
-    if (waves < 1 || waves > GROUPS_MAX_WAVES || a.sstride % 128 != 0 || g.n_groups < 1) return hipErrorInvalidValue;
+    const bool rest = g.rest.nnz > 0;
+    if (waves < 1 || waves > GROUPS_MAX_WAVES || a.sstride % 128 != 0 || (g.n_groups < 1 && !rest)) return hipErrorInvalidValue;
     const size_t lds = groups_lds_bytes(a.sstride, g.n_groups, g.wide);
     const int blocks = a.rep_list ? a.rep_count : a.R;
     const bool production = sweep_args_are_lean(a) && a.rule == SGA_RULE_METROPOLIS && !a.rep_list;
     void (*kern)(const SweepArgs, const GroupArgs) =
-        production ? (g.wide ? sweep_groups_kernel<true> : sweep_groups_kernel<false>)
-                   : (g.wide ? sweep_groups_general_kernel<true> : sweep_groups_general_kernel<false>);
+        production ? (rest ? (g.wide ? sweep_groups_kernel<true, true> : sweep_groups_kernel<false, true>)
+                           : (g.wide ? sweep_groups_kernel<true, false> : sweep_groups_kernel<false, false>))
+                   : (rest ? (g.wide ? sweep_groups_general_kernel<true, true> : sweep_groups_general_kernel<false, true>)
+                           : (g.wide ? sweep_groups_general_kernel<true, false> : sweep_groups_general_kernel<false, false>));
     hipError_t e = ensure_lds_limit(reinterpret_cast<const void *>(kern), lds);
     if (e != hipSuccess) return e;
     if (production) {
         hipLaunchKernelGGL(kern, dim3(blocks), dim3(64 * waves), lds, st, a, g);
-        note_sweep_kernel("sweep_groups_kernel<%s sums> x %d wave(s), windows of 128 updates per wave", g.wide ? "int32" : "int16",
-                          waves);
+        if (rest)
+            note_sweep_kernel("sweep_groups_kernel<%s sums, stored remainder> x %d wave(s), windows of 128 updates per wave",
+                              g.wide ? "int32" : "int16", waves);
+        else
+            note_sweep_kernel("sweep_groups_kernel<%s sums> x %d wave(s), windows of 128 updates per wave", g.wide ? "int32" : "int16",
+                              waves);
     } else {
         hipLaunchKernelGGL(kern, dim3(blocks), dim3(64), lds, st, a, g);
-        note_sweep_kernel("sweep_groups_general_kernel<%s sums> x 1 wave, one update at a time", g.wide ? "int32" : "int16");
+        if (rest)
+            note_sweep_kernel("sweep_groups_general_kernel<%s sums, stored remainder> x 1 wave, one update at a time",
+                              g.wide ? "int32" : "int16");
+        else
+            note_sweep_kernel("sweep_groups_general_kernel<%s sums> x 1 wave, one update at a time", g.wide ? "int32" : "int16");
     }
     return hipGetLastError();
 }
@@ -286,7 +348,7 @@ hipError_t launch_sweep_groups(const SweepArgs &a, const GroupArgs &g, int waves
 // Full energy: -1/2 fp32(sum_i mv_i s_i) - fp32(h . s), mv_i the fp32 row sum (core/ising_model.py:149-174); X and
 // Y in the canonical per-replica order (sga_kernels.h, energy_block_rows).  One workgroup per replica.
 // ---------------------------------------------------------------------------------------
-template <bool WIDE>
+template <bool WIDE, bool REST>
 __global__ void __launch_bounds__(256) energy_groups_kernel(const EnergyArgs a, const GroupArgs g) {
     using sum_t = typename GroupSums<WIDE>::type;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -304,7 +366,8 @@ __global__ void __launch_bounds__(256) energy_groups_kernel(const EnergyArgs a, 
         a.n, a.block_rows,
         [&](int i) {
             int si;
-            const float mv = groups_row_sum(g, bits, sums, i, si);
+            float mv = groups_row_sum(g, bits, sums, i, si);
+            if constexpr (REST) mv += groups_rest_row_sum(g, bits, i);
             return (double)mv * (double)si;
         },
         [&](int i) { return (double)a.h[i] * (((bits[i >> 5] >> (i & 31)) & 1u) ? -1.0 : 1.0); }, ce, ch, X, Y);
@@ -318,7 +381,9 @@ size_t groups_energy_lds_bytes(int sstride, int n_groups, int wide) {
 
 hipError_t launch_energy_groups(const EnergyArgs &a, const GroupArgs &g, hipStream_t st) {
     const size_t lds = groups_energy_lds_bytes(a.sstride, g.n_groups, g.wide);
-    void (*kern)(const EnergyArgs, const GroupArgs) = g.wide ? energy_groups_kernel<true> : energy_groups_kernel<false>;
+    void (*kern)(const EnergyArgs, const GroupArgs) =
+        g.rest.nnz > 0 ? (g.wide ? energy_groups_kernel<true, true> : energy_groups_kernel<false, true>)
+                       : (g.wide ? energy_groups_kernel<true, false> : energy_groups_kernel<false, false>);
     hipError_t e = ensure_lds_limit(reinterpret_cast<const void *>(kern), lds);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(kern, dim3(a.R), dim3(256), lds, st, a, g);
@@ -329,6 +394,7 @@ hipError_t launch_energy_groups(const EnergyArgs &a, const GroupArgs &g, hipStre
 // Local fields of single sites (IsingModel.get_local_field, core/ising_model.py:176-185), spins read from HBM: one
 // wave per requested site, the site's groups one after the other, a group's members across the lanes.
 // ---------------------------------------------------------------------------------------
+template <bool REST>
 __global__ void __launch_bounds__(64) fields_groups_kernel(const GroupArgs g, const int8_t *spins, const float *h,
                                                            const int32_t *sites, double *out) {
     const int lane = threadIdx.x;
@@ -342,13 +408,43 @@ __global__ void __launch_bounds__(64) fields_groups_kernel(const GroupArgs g, co
         s = wave_sum(s);
         acc += __int_as_float(ent.y) * (float)(s - si);
     }
+    if constexpr (REST) {  // the site's remainder row across the lanes
+        float part = 0.0f;
+        for (int m = g.rest.rptr[site] + lane; m < g.rest.rptr[site + 1]; m += 64) {
+            const int2 ent = g.rest.rent[m];
+            part += __int_as_float(ent.y) * (float)spins[ent.x];
+        }
+        acc += wave_sum(part);
+    }
     if (lane == 0) out[blockIdx.x] = (double)acc + (double)h[site];
 }
 
 hipError_t launch_fields_groups(const GroupArgs &g, const int8_t *spins, const float *h, const int32_t *sites, int count,
                                 double *out, hipStream_t st) {
     if (count <= 0) return hipSuccess;
-    hipLaunchKernelGGL(fields_groups_kernel, dim3(count), dim3(64), 0, st, g, spins, h, sites, out);
+    if (g.rest.nnz > 0)
+        hipLaunchKernelGGL(fields_groups_kernel<true>, dim3(count), dim3(64), 0, st, g, spins, h, sites, out);
+    else
+        hipLaunchKernelGGL(fields_groups_kernel<false>, dim3(count), dim3(64), 0, st, g, spins, h, sites, out);
+    return hipGetLastError();
+}
+
+// sum_j |R_ij| per remainder row, in fp64 (the set-time bound adds it to the row's group part on the host)
+__global__ void __launch_bounds__(256) groups_rest_row_abs_kernel(const long long *rowptr, const float *val, int n, double *out) {
+    const int lane = threadIdx.x & 63;
+    const int wave = (int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
+    const int n_waves = (int)((gridDim.x * blockDim.x) >> 6);
+    for (int i = wave; i < n; i += n_waves) {
+        double acc = 0.0;
+        for (long long j = rowptr[i] + lane; j < rowptr[i + 1]; j += 64) acc += (double)fabsf(val[j]);
+        acc = wave_sum(acc);
+        if (lane == 0) out[i] = acc;
+    }
+}
+
+hipError_t launch_groups_rest_row_abs(const long long *rowptr, const float *val, int n, double *out, hipStream_t st) {
+    const int blocks = (int)std::min<long long>(((long long)n + 3) / 4, 256 * 32);
+    hipLaunchKernelGGL(groups_rest_row_abs_kernel, dim3(blocks), dim3(256), 0, st, rowptr, val, n, out);
     return hipGetLastError();
 }
 

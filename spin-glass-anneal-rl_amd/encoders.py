@@ -36,6 +36,7 @@ class IsingBuilder:
         self._rows, self._cols, self._vals = [], [], []
         self._groups, self._group_coeff = [], []  # what add_cardinality_groups added, group by group
         self._group_blocks = 0                    # ... and how many of the coupling blocks are theirs
+        self._group_block_ids = []                # ... and which (indices into _rows)
 
     # ------------------------------------------------------------------ raw terms
     def add_field(self, idx, coeff) -> None:
@@ -96,6 +97,7 @@ class IsingBuilder:
         self._groups.extend(np.ascontiguousarray(g))
         self._group_coeff.extend([(2.0 if self.convention == "reference" else -2.0) * w] * G)
         self._group_blocks += 1
+        self._group_block_ids.append(len(self._rows) - 1)
 
     def add_qubo_pair(self, a, b, q) -> None:
         """Objective term q * x_a x_b with x = (1+s)/2 (physical convention only)."""
@@ -163,6 +165,31 @@ class IsingBuilder:
         member_ptr = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
         members = (np.concatenate(self._groups) if self._groups else np.zeros(0)).astype(np.int32)
         return member_ptr, members, np.asarray(self._group_coeff, np.float32), self.fields(), self.constant
+
+    def group_rest_structure(self):
+        """(member_ptr, members, coeff, (rowptr int32 [n + 1], colidx int32, val fp32), h, constant): the couplings as
+        groups plus a stored remainder, for `AnnealEngine.set_groups(..., rest=...)`.  The groups are what
+        `add_cardinality_groups` added; the remainder is every other coupling block (add_coupling, add_qubo_pair,
+        add_equality / add_cardinality) summed, both triangles, rows sorted, exact zeros dropped.  Physical convention
+        without overwrite only."""
+        import scipy.sparse as sp
+        if self.convention != "physical" or self.overwrite:
+            raise ValueError("group_rest_structure is defined for the physical convention without overwrite")
+        sizes = np.array([g.size for g in self._groups], np.int64)
+        member_ptr = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+        members = (np.concatenate(self._groups) if self._groups else np.zeros(0)).astype(np.int32)
+        theirs = set(self._group_block_ids)
+        others = [q for q in range(len(self._rows)) if q not in theirs]
+        z = np.zeros(0, np.int64)
+        r = np.concatenate([self._rows[q] for q in others]) if others else z
+        c = np.concatenate([self._cols[q] for q in others]) if others else z
+        v = np.concatenate([self._vals[q] for q in others]) if others else np.zeros(0)
+        up = sp.coo_matrix((v, (r, c)), shape=(self.n, self.n)).tocsr()  # (duplicates summed)
+        full = (up + sp.triu(up, 1).T).tocsr()
+        full.eliminate_zeros()
+        full.sort_indices()
+        rest = (full.indptr.astype(np.int32), full.indices.astype(np.int32), full.data.astype(np.float32))
+        return member_ptr, members, np.asarray(self._group_coeff, np.float32), rest, self.fields(), self.constant
 
     def to_dense(self) -> np.ndarray:
         r, c, v = self._triples()
@@ -320,11 +347,13 @@ def scheduling_ising(durations: Sequence[float], n_agents: int, time_horizon: fl
                      time_discretization: int, due_dates: Optional[Sequence[float]] = None,
                      priorities: Optional[Sequence[float]] = None, objective: str = "makespan",
                      penalty_weights: Optional[Dict[str, float]] = None,
-                     convention: str = "physical", overwrite: bool = False) -> IsingBuilder:
+                     convention: str = "physical", overwrite: bool = False,
+                     precedence_pairs: Optional[Sequence] = None) -> IsingBuilder:
     """Multi-agent scheduling, spin (task, agent, slot) -> (task*A + agent)*S + slot
     (reference problems/scheduling.py:67-285): completion-time objective on the fields,
     one-hot assignment per task, at-most-one task per (agent, slot), precedence i<j,
-    due-date penalties."""
+    due-date penalties.  `precedence_pairs`: None = every pair i < j (the reference); a list of (i, j) restricts the
+    precedence terms to those pairs (a task DAG)."""
     dur = np.asarray(durations, np.float64)
     T, A, S = dur.size, int(n_agents), int(time_discretization)
     if penalty_weights is None:  # scheduling.py:86-92
@@ -365,7 +394,13 @@ def scheduling_ising(durations: Sequence[float], n_agents: int, time_horizon: fl
             b.add_cardinality_groups(groups, 1, penalty_weights["capacity"])
     if "precedence" in penalty_weights:              # :247-268: i < j, start_j <= start_i
         w = penalty_weights["precedence"]
-        ti, tj = np.triu_indices(T, 1)
+        if precedence_pairs is None:
+            ti, tj = np.triu_indices(T, 1)
+        else:
+            pp = np.asarray(list(precedence_pairs), np.int64).reshape(-1, 2)
+            if pp.size and (pp.min() < 0 or pp.max() >= T or np.any(pp[:, 0] == pp[:, 1])):
+                raise ValueError("precedence_pairs must name pairs of distinct tasks")
+            ti, tj = pp[:, 0], pp[:, 1]
         si, sj = np.nonzero(np.arange(S)[None, :] <= np.arange(S)[:, None])  # sj <= si
         for i, j in zip(ti, tj):
             a_idx = idx[i][:, si]                    # [A, P]
@@ -443,3 +478,16 @@ def evaluate_penalties(spins, terms: Iterable[Tuple[str, tuple]]) -> float:
             val = float(np.dot(np.asarray(c, np.float64), s[np.asarray(idx)]))
             total += w * (max(0.0, val - t) ** 2 if kind == "inequality" else (val - t) ** 2)
     return total
+
+
+def scheduling_groups_rest(durations: Sequence[float], n_agents: int, time_horizon: int, time_discretization: int,
+                           penalty_weights: Optional[Dict[str, float]] = None, due_dates: Optional[Sequence[float]] = None,
+                           priorities: Optional[Sequence[float]] = None, objective: str = "makespan",
+                           precedence_pairs: Optional[Sequence] = None):
+    """`scheduling_ising(...)` as groups plus a stored remainder: (n, member_ptr, members, coeff, rest, h, constant)
+    for `AnnealEngine.set_groups(n, (member_ptr, members), coeff, h, rest=rest)`.  The assignment and capacity
+    constraints are the groups, the precedence terms (a "precedence" weight; `precedence_pairs` as in
+    `scheduling_ising`) the remainder `rest = (rowptr, colidx, val)`."""
+    b = scheduling_ising(durations, n_agents, time_horizon, time_discretization, due_dates, priorities, objective,
+                         penalty_weights, precedence_pairs=precedence_pairs)
+    return (b.n,) + b.group_rest_structure()

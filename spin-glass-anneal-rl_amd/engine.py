@@ -355,17 +355,25 @@ class AnnealEngine:
         self._sizes = None
         self.n, self.R, self.n_models = n * n, 0, 1
 
-    def set_groups(self, n: int, groups, coeff, h):
+    def set_groups(self, n: int, groups, coeff, h, rest=None):
         """Couplings that are a sum of complete graphs on groups of sites, never stored (see sga_set_groups):
         J_ij = sum of coeff[g] over the groups that hold both i and j.  `groups` is a list of index arrays or a
         tuple (member_ptr int64 [G + 1], members int32); `coeff` [G] and `h` [n] float32; numpy or torch device
-        tensors (`encoders.assignment_groups` / `scheduling_groups` / `IsingBuilder.group_structure` return them)."""
+        tensors (`encoders.assignment_groups` / `scheduling_groups` / `IsingBuilder.group_structure` return them).
+        `rest`: a stored sparse remainder R added to those couplings (see sga_set_groups_csr) -- (rowptr int32 [n + 1],
+        colidx int32, val float32) or a scipy sparse matrix; symmetric, zero diagonal, rows strictly sorted and at most
+        256 entries long (`IsingBuilder.group_rest_structure` / `encoders.scheduling_groups_rest` return it)."""
         if isinstance(groups, tuple) and len(groups) == 2:  # (a LIST of two index arrays is two groups)
             member_ptr, members = groups
         else:
             rows = [np.asarray(g, np.int32).ravel() for g in groups]
             member_ptr = np.concatenate([[0], np.cumsum([r.size for r in rows])]).astype(np.int64)
             members = np.concatenate(rows).astype(np.int32) if rows else np.zeros(0, np.int32)
+        if rest is not None and hasattr(rest, "tocsr"):
+            m = rest.tocsr()
+            m.sum_duplicates()
+            m.sort_indices()
+            rest = (np.asarray(m.indptr, np.int32), np.asarray(m.indices, np.int32), np.asarray(m.data, np.float32))
         mp, k1 = _buf(member_ptr, np.int64, "int64")
         mm, k2 = _buf(members, np.int32, "int32")
         cp, k3 = _buf(coeff, np.float32, "float32")
@@ -376,7 +384,20 @@ class AnnealEngine:
             raise AnnealingError("one coefficient per group")
         if size(k4) != int(n):
             raise AnnealingError("external fields must have n entries")
-        N.check(self._lib.sga_set_groups(self._h, int(n), int(G), mp, mm, cp, hp), "sga_set_groups")
+        if rest is None:
+            N.check(self._lib.sga_set_groups(self._h, int(n), int(G), mp, mm, cp, hp), "sga_set_groups")
+        else:
+            rowptr, colidx, val = rest
+            rp, k5 = _buf(rowptr, np.int32, "int32")
+            ci, k6 = _buf(colidx, np.int32, "int32")
+            vp, k7 = _buf(val, np.float32, "float32")
+            if size(k5) != int(n) + 1:
+                raise AnnealingError("the remainder's rowptr must have n + 1 entries")
+            if size(k6) != size(k7):
+                raise AnnealingError("the remainder needs one value per column index")
+            N.check(self._lib.sga_set_groups_csr(self._h, int(n), int(G), mp, mm, cp, rp, ci, vp, int(size(k7)), hp),
+                    "sga_set_groups_csr")
+            del k5, k6, k7
         del k1, k2, k3, k4
         self._sizes = None
         self.n, self.R, self.n_models = int(n), 0, 1
