@@ -80,7 +80,7 @@ typedef struct sga_engine sga_engine;
 int sga_create(int device, sga_engine **out);
 void sga_destroy(sga_engine *e);
 const char *sga_last_error(void);
-int sga_version(void);  /* 1200: sga_set_groups_csr (group couplings plus a stored sparse remainder); 1100: option "ragged_field_cache" (cached local fields for ragged CSR batches); 1000: sga_set_groups */
+int sga_version(void);  /* 1300: options "ragged_field_cache" and "clf_fixed_point" together (fixed-point cached local fields for ragged CSR batches); 1200: sga_set_groups_csr (group couplings plus a stored sparse remainder); 1100: option "ragged_field_cache" (cached local fields for ragged CSR batches); 1000: sga_set_groups */
 /* Run on an existing HIP stream (e.g. torch.cuda.current_stream().cuda_stream); NULL = the
  * engine's own stream (default). */
 int sga_set_stream(sga_engine *e, void *hip_stream);
@@ -139,8 +139,8 @@ int sga_set_csr64(sga_engine *e, const int64_t *rowptr, const int32_t *colidx, c
  *   stats, export / import, the checksum (n_spins[] included), sga_describe ("csr batch models=M n=min..max ...") and
  *   the route calls work.  SGA_ERR_UNSUPPORTED: sga_set_field_cache(ON) (AUTO streams) unless option
  *   "ragged_field_cache" is set, the Wolff rule, sga_flip, sga_update, sga_autotune, and any option that would pick a
- *   wide, bit-spin, several-updates-per-step or fixed-point cached-field form.  One launch per sweep call: the narrow
- *   one-update form, each wave running its own model.
+ *   wide, bit-spin or several-updates-per-step form.  One launch per sweep call: the narrow one-update form, each
+ *   wave running its own model.
  *   Option "ragged_field_cache" = 1 (version >= 1100, set before this call): the batch is also scanned for the int16
  *   cached-field form of sga_set_csr -- in EVERY model J integer valued in strictly sorted rows without duplicates,
  *   h in multiples of 1/2, max_i sum_j |J_ij| < 2^15, rows of <= 2048 entries, the largest model within LDS -- and
@@ -148,7 +148,18 @@ int sga_set_csr64(sga_engine *e, const int64_t *rowptr, const int32_t *colidx, c
  *   its model's fields D = J s resident in LDS, a row read on accept only.  Accept table, its scale and the launch
  *   geometry are batch-wide (the largest table, scale 2 as soon as one model has a half-integer h), which leaves
  *   every model on its one-model chain.  ON over a batch that does not qualify: sga_sweep fails with
- *   SGA_ERR_UNSUPPORTED naming the first offending model; AUTO streams there. */
+ *   SGA_ERR_UNSUPPORTED naming the first offending model; AUTO streams there.
+ *   Options "ragged_field_cache" = 1 and "clf_fixed_point" = 1 together (version >= 1300, both set before this call): a
+ *   batch the int16 form does not take -- a model with real-valued J, an h that is no multiple of 1/2, integer fields
+ *   of 2^15 or more -- is scanned for the fixed-point form of sga_set_csr: in EVERY model acc class f32 / f64-exact,
+ *   strictly sorted rows without duplicates, rows of <= 2048 entries; any fp32 h (never folded into the fields).  k is
+ *   batch-wide: the finest grid 2^-k any model's J needs, so every 2^k J of every model is an integer; the fields
+ *   D = 2^k J_m s are int32 while 2^k max_i sum_j |J_ij| < 2^31 over all rows of the batch, else int64, and the batch
+ *   is refused from 2^53 on.  dot = fp32(2^-k D_i) is one rounding of the exact row sum: every model walks its
+ *   one-model chain.  A batch the int16 form takes keeps it.  Served by the cached kernel: SGA_SITE_RANDOM, both
+ *   arithmetics, Metropolis / Glauber / heat bath, no per-update records; other calls take the streaming kernel and
+ *   the fields are seeded anew.  sga_describe names "models=M", the width and k; refusals name the first offending
+ *   model (f64-canonical J, unsorted or duplicate rows, a row too long, fields wider than the bound). */
 int sga_set_csr_batch(sga_engine *e, int n_models, const int32_t *n_spins, const int64_t *rowptr,
                       const int32_t *colidx, const float *val, const float *h, int64_t nnz);
 /* model m of a ragged batch: its spins and, once replicas exist, its first global replica and replica count */
@@ -419,7 +430,11 @@ int sga_set_csr_storage(sga_engine *e, int storage);
  *     refused;
  *   ragged CSR batches (sga_set_csr_batch; version >= 1100) under option "ragged_field_cache" = 1: the CSR
  *     conditions below in every model, production sweeps, one launch under AUTO decided by the hottest replica.
- *     With the option at 0 (default) ON is refused (SGA_ERR_UNSUPPORTED) and AUTO streams;
+ *     With the option at 0 (default) ON is refused (SGA_ERR_UNSUPPORTED) and AUTO streams.  With option
+ *     "clf_fixed_point" = 1 as well (version >= 1300) a batch that fails those conditions is served by the fixed-point
+ *     form -- one k and one field width (int32 | int64) for the batch, any fp32 h, any single-site rule and
+ *     arithmetic on Philox sites; AUTO by the hottest replica against the one-model fixed-point break-even (~6 % int64,
+ *     ~3.4 % int32; not measured for ragged batches);
  *   CSR couplings (sga_set_csr, or a sparse matrix sga_set_dense kept as CSR): J integer valued and symmetric
  *     in strictly sorted rows (no duplicate entries), zero diagonal, h in multiples of 1/2,
  *     max_i sum_j |J_ij| < 2^15 (only the dynamic part J s of a field is kept, as int16; h is read beside it),
@@ -466,8 +481,9 @@ int sga_set_field_cache(sga_engine *e, int mode);
  *                           set-time scan of J's binary exponents; acc class f32 / f64-exact, symmetric J in strictly
  *                           sorted rows, zero diagonal, any fp32 h), dot = fp32(2^-k D_i) -- the row kernels' value --
  *                           and the same accept rule: the same chain, any single-site rule, site mode and arithmetic.
- *                           Problems the int16 form serves keep it.  Refused: f64-canonical J, ragged batches, the
- *                           implicit TSP form, fields past LDS.
+ *                           Problems the int16 form serves keep it.  Refused: f64-canonical J, the implicit TSP form,
+ *                           fields past LDS.  Ragged batches (sga_set_csr_batch): refused unless option
+ *                           "ragged_field_cache" = 1 is set too -- then one k and one width for the batch, see there.
  *                           DENSE couplings (sga_set_dense, one model) that the integer cached-field form does not take
  *                           -- real-valued J, or integer J beside an h that is no multiple of 1/2 --: the same D_i in
  *                           LDS (csrc/sweep_clf_fx.hip), conditions as above (acc class f32 / f64-exact, symmetric J,
@@ -508,7 +524,9 @@ int sga_set_field_cache(sga_engine *e, int mode);
  *   "ragged_field_cache"    0 (default) | 1   ragged CSR batches (sga_set_csr_batch): the int16 cached-field sweep of
  *                           sga_set_csr over the batch (csrc/sweep_clf_csr.hip, ragged build): sga_set_field_cache(ON)
  *                           is accepted, sga_set_csr_batch scans every model for the form's conditions, ON / AUTO act
- *                           as on a one-model CSR engine.  0: ON is refused, AUTO streams.  Same chain       [set]
+ *                           as on a one-model CSR engine.  0: ON is refused, AUTO streams.  Same chain.  Together with
+ *                           option "clf_fixed_point" = 1 (version >= 1300): a batch the int16 form does not take runs
+ *                           the fixed-point form over the batch (int32 | int64 fields at one batch-wide k)  [set]
  * sga_option_name enumerates the keys (index 0, 1, ... until SGA_ERR_INVALID).
  * (No reference counterpart: the reference has one code path, core/spin_dynamics.py:61-152.) */
 int sga_set_option(sga_engine *e, const char *key, int64_t value);

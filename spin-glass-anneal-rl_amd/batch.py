@@ -25,6 +25,11 @@ of ITS model resident, one workgroup of 4 or 8 waves per replica, a row read on 
 every result field but `total_time` is unchanged.  A chunk that does not qualify (a model with real-valued J, row sums
 of 2^15 or more, duplicate entries, h off the half-integers) is refused under "on" and takes the stacked path; under
 "auto" it streams on the ragged engine.
+
+`annealer_config.fixed_point_fields=True` beside it sets the engine option "clf_fixed_point" as well: a chunk the
+int16 form does not take (real-valued J such as distances, h off the half-integers, integer fields of 2^15 or more)
+then runs the fixed-point form on the ragged engine -- D = 2^k J s as exact int32 | int64 at one batch-wide k; the
+same chain once more.  Without `ragged_field_cache` the flag does nothing on the ragged path.
 """
 import time
 from dataclasses import dataclass
@@ -154,6 +159,8 @@ class BatchProcessor:
         def set_problem(eng):
             if self.batch_config.ragged_field_cache:  # (a [set] option: before the couplings)
                 eng.set_option("ragged_field_cache", 1)
+                if self.annealer_config.fixed_point_fields:  # ([set] too: real-valued / wide chunks)
+                    eng.set_option("clf_fixed_point", 1)
             eng.set_csr_batch(problems)
 
         try:

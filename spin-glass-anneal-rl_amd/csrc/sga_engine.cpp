@@ -201,10 +201,18 @@ int ensure_fields(sga_engine *e) {
     if (e->fields_valid && e->fields) return SGA_OK;
     if (e->ragged) {  // D = J_m s of every replica over its model's rows, up to eight replicas of a model per pass
         e->ldf = ((long long)e->n + 127) / 128 * 128;  // (the largest model's)
-        if (!e->fields && hipMalloc(&e->fields, (size_t)e->R * (size_t)e->ldf * 2) != hipSuccess) {
+        const size_t fbytes = e->clf_fx_bits ? (size_t)(e->clf_fx_bits / 8) : 2;  // (fixed point: D = 2^k J_m s, int32 | int64)
+        if (!e->fields && hipMalloc(&e->fields, (size_t)e->R * (size_t)e->ldf * fbytes) != hipSuccess) {
             (void)hipGetLastError();
             e->fields = nullptr;
             return fail(SGA_ERR_MEMORY, "no memory for the resident local fields of the cached-field sweep");
+        }
+        if (e->clf_fx_bits) {  // options "ragged_field_cache" and "clf_fixed_point": exact sums at the batch-wide k, h not folded in
+            HIPCHK(sga::launch_csr_fields_seed_ragged_fx(e->rowptr64, e->cv, e->spins, e->sstride, e->n, e->R,
+                                                         (unsigned int)e->replica0, e->Rg / e->n_models, e->d_models, e->fields,
+                                                         e->ldf, e->clf_fx_bits, e->clf_fx_k, e->stream));
+            e->fields_valid = true;
+            return SGA_OK;
         }
         if (!e->hq) {  // scale * h of every row of the concatenation, at the batch-wide scale
             HIPCHK(hipMalloc(&e->hq, sizeof(int) * (size_t)e->n_rows));
@@ -384,7 +392,7 @@ int ensure_packed(sga_engine *e) {
 extern "C" {
 
 const char *sga_last_error(void) { return g_last_error.c_str(); }
-int sga_version(void) { return 1200; }  // + sga_set_groups_csr (group couplings plus a stored sparse remainder, sweep_groups.hip)  // 1100: + option "ragged_field_cache" (cached local fields for ragged CSR batches, sweep_clf_csr.hip)  // 1000: + sga_set_groups (implicit cardinality-group couplings, sweep_groups.hip)  // 900: + cached local fields for many-model dense batches (sga_set_dense_batch)  // 800: + option "clf_fixed_point" over dense couplings (sweep_clf_fx.hip)  // 700: + option "clf_fixed_point" (cached fields of real-valued CSR couplings)  // 600: + sga_set_csr_batch / sga_get_batch_model (ragged CSR batches)  // round 5: + sga_explain_route / sga_get_route_query, sga_get_last_kernel, sga_get_autotune_table, ladder-local sga_exchange
+int sga_version(void) { return 1300; }  // + options "ragged_field_cache" and "clf_fixed_point" together: fixed-point cached local fields for ragged CSR batches (sweep_clf_csr.hip)  // 1200: + sga_set_groups_csr (group couplings plus a stored sparse remainder, sweep_groups.hip)  // 1100: + option "ragged_field_cache" (cached local fields for ragged CSR batches, sweep_clf_csr.hip)  // 1000: + sga_set_groups (implicit cardinality-group couplings, sweep_groups.hip)  // 900: + cached local fields for many-model dense batches (sga_set_dense_batch)  // 800: + option "clf_fixed_point" over dense couplings (sweep_clf_fx.hip)  // 700: + option "clf_fixed_point" (cached fields of real-valued CSR couplings)  // 600: + sga_set_csr_batch / sga_get_batch_model (ragged CSR batches)  // round 5: + sga_explain_route / sga_get_route_query, sga_get_last_kernel, sga_get_autotune_table, ladder-local sga_exchange
 
 int sga_create(int device, sga_engine **out) {
     if (!out) return fail(SGA_ERR_INVALID, "out is NULL");

@@ -219,6 +219,11 @@ hipError_t launch_scaled_fields(const float *h, int n, int scale, int *hq, hipSt
 hipError_t launch_csr_fields_seed_ragged(const long long *rowptr, const int2 *cv, const int8_t *spins, int sstride, int n_max,
                                          int R, unsigned int replica0, int reps_per_model, const int2 *models, short *D,
                                          long long ldf, hipStream_t st);
+// ... with fixed-point fields (options "ragged_field_cache" and "clf_fixed_point" together): D = 2^k J_m s as int32 | int64,
+// one k and one width for the batch
+hipError_t launch_csr_fields_seed_ragged_fx(const long long *rowptr, const int2 *cv, const int8_t *spins, int sstride, int n_max,
+                                            int R, unsigned int replica0, int reps_per_model, const int2 *models, void *D,
+                                            long long ldf, int field_bits, int k, hipStream_t st);
 // ... and of dense problems with real-valued J (option "clf_fixed_point", sweep_clf_fx.hip): D = 2^k J s as exact int32 |
 // int64 (a.field_bits), k = a.field_scale, no accept table; fp32 rows, or int8 rows (integer J, k = 0)
 hipError_t launch_sweep_clf_fx(const SweepArgs &a, bool j_is_i8, int waves, hipStream_t st);

@@ -1032,6 +1032,13 @@ int sga_set_csr_batch(sga_engine *e, int n_models, const int32_t *n_spins, const
     // first model that fails one of the conditions and which (sga_sweep under SGA_FIELD_CACHE_ON reports it)
     const bool want_clf = e->opt[OPT_RAGGED_FIELD_CACHE] == 1;
     std::string clf_why;
+    // ... with option "clf_fixed_point" too: a batch the int16 form refuses is scanned for the fixed-point form (DESIGN
+    // 4.1l).  Per model: the class of its row sums, sorted rows, rows of <= 2048 entries; batch-wide: k = the finest grid
+    // any model needs, and 2^k max_i sum_j |J_ij| over all rows, which picks the width.  fx_why: the first offending model.
+    const bool want_fx = want_clf && e->opt[OPT_CLF_FIXED_POINT] == 1;
+    std::string fx_why;
+    int fx_k = INT32_MIN;
+    std::vector<float> fx_mj((size_t)n_models, 0.0f);
     std::vector<int> row0((size_t)n_models);
     std::vector<int2> models((size_t)n_models);
     for (int m = 0, r0 = 0; m < n_models; r0 += n_spins[m], ++m) {
@@ -1097,6 +1104,17 @@ int sga_set_csr_batch(sga_engine *e, int n_models, const int32_t *n_spins, const
                       "option \"half_integer_table\" = 0)";
             if (bad) clf_why = "cached local fields over ragged CSR batches: " + who + bad;
         }
+        if (want_fx) {
+            fx_mj[(size_t)m] = mj;
+            if (any) fx_k = std::max(fx_k, sym[sga::CSR_EXP_LO] - 1024);  // k_m: minus the exponent of J's lowest set bit
+            const char *bad = nullptr;
+            if (acc == sga::CSR_ACC_F64_CANON)
+                bad = "the couplings need the canonical fp64 summation order (acc class f64-canonical: their binary places span "
+                      "more than 53 bits, so no exact fixed point holds a row sum)";
+            else if (!sorted) bad = "rows are not strictly sorted by column (unsorted or duplicate entries)";
+            else if (max_len > 4 * 64 * 8) bad = "a row is longer than 2048 entries";
+            if (bad && fx_why.empty()) fx_why = "cached local fields over ragged CSR batches (fixed point): " + who + bad;
+        }
     }
     if (e->opt[OPT_FORCE_CSR_ACC] > 0) acc_b = std::max(acc_b, std::min(3, (int)e->opt[OPT_FORCE_CSR_ACC]));
     e->csr_acc = acc_b;
@@ -1111,6 +1129,34 @@ int sga_set_csr_batch(sga_engine *e, int n_models, const int32_t *n_spins, const
         clf_why = "cached local fields over ragged CSR batches: the batch runs without an accept table (option \"force_csr_acc\")";
     e->clf_csr_problem = want_clf && clf_why.empty();
     e->clf_ragged_why = want_clf ? clf_why : std::string();
+    if (want_fx && !clf_why.empty()) {  // the int16 form does not take the batch: the fixed-point form
+        const int k = fx_k == INT32_MIN ? 0 : fx_k;
+        // D_i = 2^k sum_j J_ij s_j of any row of the batch must stay below 2^53: then the fp64 sums of the seed kernel, the
+        // int64 -> fp64 conversion of a proposal and the scaled entries of an accept are all exact (the one-model condition
+        // over the concatenation; mj is the fp32 rounding of an fp64 sum: < 1 ulp either way)
+        double bound = 0.0;
+        for (int m = 0; m < n_models; ++m) {
+            const double bm = std::ldexp((double)fx_mj[(size_t)m], k) * (1.0 + 0x1.0p-20);
+            bound = std::max(bound, bm);
+            if (fx_why.empty() && !(bm < 0x1.0p53)) {
+                char msg[256];
+                std::snprintf(msg, sizeof(msg), "cached local fields over ragged CSR batches (fixed point): model %d: fields wider "
+                              "than the bound: 2^k max_i sum_j |J_ij| is not below 2^53 at the batch-wide k = %d", m, k);
+                fx_why = msg;
+            }
+        }
+        if (fx_why.empty() && acc_b == sga::CSR_ACC_F64_CANON)
+            fx_why = "cached local fields over ragged CSR batches (fixed point): the batch runs the canonical fp64 summation order "
+                     "(option \"force_csr_acc\")";
+        if (fx_why.empty()) {
+            e->clf_csr_problem = true;
+            e->clf_fx_bits = bound < 0x1.0p31 ? 32 : 64;
+            e->clf_fx_k = k;
+            e->clf_ragged_why.clear();
+        } else {
+            e->clf_ragged_why = fx_why;
+        }
+    }
     // the plain layout: (column, value) interleaved, CSR_TAIL_PAD zeroed entries behind
     long long *src_ptr = nullptr;
     SGA_BATCH_CHK(hipMalloc(&src_ptr, sizeof(long long) * np1));

@@ -348,6 +348,21 @@ const char *clf_refusal(const Query &q) {
         // option "ragged_field_cache": the int16 form of sweep_clf_csr.hip, each replica on its own model's rows; LDS is
         // laid out for the largest model (q.n), the table and the longest row are the batch's
         const long long ldf = ((long long)q.n + 127) / 128 * 128;
+        if (q.opt[OPT_CLF_FIXED_POINT] == 1 && (q.clf_bits == 32 || q.clf_bits == 64)) {
+            // ... with option "clf_fixed_point": a batch the int16 form does not take, D = 2^k J_m s as exact int32 | int64
+            // with one k and one width for the batch, no accept table
+            if (!q.clf_ok || q.acc == sga::CSR_ACC_F64_CANON)
+                return "cached local fields over ragged CSR batches (fixed point) need, in every model, acc class f32 / f64-exact, "
+                       "strictly sorted rows (no duplicates), and 2^k max_i sum_j |J_ij| < 2^53 at the batch-wide k";
+            if (q.max_row_len > 4 * 64 * 8)
+                return "cached local fields over ragged CSR batches (fixed point): a row is longer than 2048 entries";
+            if (q.R_local > 0 && sga::sweep_clf_csr_lds_bytes(ldf, q.sstride, 0, q.clf_bits) > 160 * 1024)
+                return q.clf_bits == 64 ? "cached local fields over ragged CSR batches (fixed point): int64 fields and spins of the "
+                                          "largest model do not fit LDS (160 KiB: n_max <= ~20 000)"
+                                        : "cached local fields over ragged CSR batches (fixed point): int32 fields and spins of the "
+                                          "largest model do not fit LDS (160 KiB: n_max <= ~39 000)";
+            return nullptr;
+        }
         if (!q.clf_ok)
             return "cached local fields over ragged CSR batches need, in every model, integer-valued J in strictly sorted rows "
                    "(no duplicates), h in multiples of 1/2, max_i sum_j |J_ij| < 2^15 and the accept table";
@@ -427,6 +442,9 @@ const char *clf_refusal(const Query &q) {
 // break-even (profiles/fixed_point_fields.json): C5 at 100 cities (int64), 2.0 against 8.6 ms per sweep at 0.38 %
 // acceptance -- ~1.5 ms of windows plus ~1.5 us per accept: break-even near 6 % --, and a 20 000-spin binary-grid
 // instance (int32), 18.4 against 3.96 ms at 15.9 %: near 3.4 %.
+// Ragged batches under "ragged_field_cache" too: the same two costs per accept, against the hottest replica's acceptance
+// over its own n_m -- NOT measured for ragged batches as a break-even (profiles/ragged_fixed_point.json reports whole
+// windows of an SA run).
 static double fixed_point_theta(const Query &q, double t_upd) {
     const double t_acc = q.clf_bits == 64 ? 8.8 : 6.3;
     return t_upd / t_acc;
@@ -673,7 +691,10 @@ std::string explain(const Query &q0) {
         if (why) {
             out += q.field_cache == SGA_FIELD_CACHE_ON ? " cached=refused" : " cached=unavailable";
         } else if (q.field_cache == SGA_FIELD_CACHE_ON) {
-            if (q.kind == SGA_ROUTE_CSR && q.opt[OPT_CLF_FIXED_POINT] == 1 && (q.clf_bits == 32 || q.clf_bits == 64))
+            if (q.kind == SGA_ROUTE_CSR && q.n_models > 1 && q.opt[OPT_CLF_FIXED_POINT] == 1 && (q.clf_bits == 32 || q.clf_bits == 64))
+                std::snprintf(buf, sizeof(buf), " cached=on(waves=%d fields=int%d fixed-point models=%d)", clf_csr_waves(q), q.clf_bits,
+                              q.n_models);
+            else if (q.kind == SGA_ROUTE_CSR && q.opt[OPT_CLF_FIXED_POINT] == 1 && (q.clf_bits == 32 || q.clf_bits == 64))
                 std::snprintf(buf, sizeof(buf), " cached=on(waves=%d fields=int%d fixed-point)", clf_csr_waves(q), q.clf_bits);
             else if (dense_fixed_point(q))
                 std::snprintf(buf, sizeof(buf), " cached=on(waves=%d fields=int%d fixed-point)",

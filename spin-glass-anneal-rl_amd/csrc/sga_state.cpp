@@ -428,6 +428,17 @@ int sga_describe(sga_engine *e, char *buf, int buflen) {
         if (e->opt[OPT_RAGGED_FIELD_CACHE] == 1 && e->field_cache != SGA_FIELD_CACHE_OFF) {
             if (!clf_active(e))
                 std::strncat(tmp, " sweep=streaming(the batch does not qualify for cached local fields)", sizeof(tmp) - std::strlen(tmp) - 1);
+            else if (e->field_cache == SGA_FIELD_CACHE_ON && e->clf_fx_bits)
+                std::snprintf(tmp + std::strlen(tmp), sizeof(tmp) - std::strlen(tmp),
+                              " sweep=cached-local-fields(ragged models=%d: int%d fixed-point dynamic fields, k=%d, of each replica's "
+                              "model in LDS, %d waves per replica, row entries read on accept only)",
+                              e->n_models, e->clf_fx_bits, e->clf_fx_k, sga_route::clf_csr_waves(route_query_of(e)));
+            else if (e->clf_fx_bits)
+                std::snprintf(tmp + std::strlen(tmp), sizeof(tmp) - std::strlen(tmp),
+                              " sweep=auto(ragged cached local fields models=%d, int%d fixed-point, k=%d, while the hottest replica "
+                              "accepts little; now: %s)",
+                              e->n_models, e->clf_fx_bits, e->clf_fx_k,
+                              (!e->routing.unavailable && e->routing.n_cached > 0) ? "cached" : "one row per proposal");
             else if (e->field_cache == SGA_FIELD_CACHE_ON)
                 std::snprintf(tmp + std::strlen(tmp), sizeof(tmp) - std::strlen(tmp),
                               " sweep=cached-local-fields(ragged: int16 dynamic fields of each replica's model in LDS, %d waves per "

@@ -39,6 +39,13 @@
 // from the model's first row on; columns are model-local, so D[column] is the replica's own slice.  LDS is laid out for
 // the largest model (a.ldf, a.sstride), the accept table and its scale are batch-wide: entry q stands for dE = 2 q /
 // scale whatever the model, so k = s_i (scale D_i + scale h_i) decides as it would on a one-model engine.
+//
+// Ragged batches with fixed-point fields (options "ragged_field_cache" and "clf_fixed_point" together, RAGGED and FX):
+// batches the int16 form refuses -- a model with real-valued J, an h off the half-integers, integer fields past 2^15.
+// One k for the whole batch (the finest grid any model needs: every 2^k J of every model is an integer), one field
+// width (int32 | int64 by 2^k max_i sum_j |J_ij| over all rows of the batch, below 2^53), h read as fp32 from the
+// model's first row on.  dot = fp32(2^-k D_i) is one rounding of the exact row sum whatever k is, so each model walks
+// its one-model chain.  Philox sites only; other site modes take the streaming ragged kernel.
 #include "sweep_common.h"
 
 namespace sga {
@@ -114,12 +121,17 @@ hipError_t launch_csr_fields_seed(const long long *rowptr, const int2 *cv, const
     return hipGetLastError();
 }
 // ragged batches: blockIdx.x = (model among those this engine's replicas touch, group of up to eight of ITS replicas) --
-// replicas per model need not divide eight, and a shard may start inside a model: a block never straddles two models
+// replicas per model need not divide eight, and a shard may start inside a model: a block never straddles two models.
+// FT = short: integer J summed as int (the int16 form); FT = int | long long: the fixed point D = 2^kx J s, exact fp64
+// sums of integer terms below 2^53 as csr_fields_seed_fx_kernel (options "ragged_field_cache" and "clf_fixed_point").
+template <typename FT>
 __global__ void __launch_bounds__(256) csr_fields_seed_ragged_kernel(const long long *__restrict__ rowptr, const int2 *__restrict__ cv,
                                                                      const int8_t *__restrict__ spins, int sstride, int R,
                                                                      unsigned int replica0, int reps, int groups_per_model,
                                                                      const int2 *__restrict__ models, int slices,
-                                                                     short *__restrict__ D, long long ldf) {
+                                                                     FT *__restrict__ D, long long ldf, int kx) {
+    constexpr bool FX = sizeof(FT) != 2;
+    using AT = std::conditional_t<FX, double, int>;  // what a term and a row sum are held in
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned int *sb = reinterpret_cast<unsigned int *>(smem);  // [8][words]: bit = spin down
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -148,38 +160,56 @@ __global__ void __launch_bounds__(256) csr_fields_seed_ragged_kernel(const long 
     const int i0 = min(n, (int)blockIdx.y * per), i1 = min(n, i0 + per);
     for (int i = i0 + w; i < i1; i += 4) {
         const long long beg = rowptr[i], end = rowptr[i + 1];
-        int acc[CLFS_SEED_REPS];
+        AT acc[CLFS_SEED_REPS];
 #pragma unroll
         for (int rep = 0; rep < CLFS_SEED_REPS; ++rep) acc[rep] = 0;
         for (long long e = beg + lane; e < end; e += 64) {
             const int2 ent = cv[e];
-            const int J = (int)__int_as_float(ent.y);  // integer valued (engine: eligibility)
+            AT J;  // an integer (engine: eligibility)
+            if constexpr (FX) J = ldexp((double)__int_as_float(ent.y), kx);
+            else J = (int)__int_as_float(ent.y);
             const int wd = ent.x >> 5, bit = ent.x & 31;  // (model-local column: below n)
 #pragma unroll
             for (int rep = 0; rep < CLFS_SEED_REPS; ++rep) acc[rep] += ((sb[rep * words + wd] >> bit) & 1u) ? -J : J;
         }
 #pragma unroll
         for (int rep = 0; rep < CLFS_SEED_REPS; ++rep) {
-            const int tot = wave_sum(acc[rep]);
-            if (lane == 0 && rep < count) D[(long long)(lo + rep) * ldf + i] = (short)tot;
+            const AT tot = wave_sum(acc[rep]);
+            if (lane == 0 && rep < count) D[(long long)(lo + rep) * ldf + i] = FX ? (FT)(long long)tot : (FT)tot;
         }
     }
 }
-hipError_t launch_csr_fields_seed_ragged(const long long *rowptr, const int2 *cv, const int8_t *spins, int sstride, int n_max,
-                                         int R, unsigned int replica0, int reps_per_model, const int2 *models, short *D,
-                                         long long ldf, hipStream_t st) {
+template <typename FT>
+static hipError_t launch_seed_ragged(const long long *rowptr, const int2 *cv, const int8_t *spins, int sstride, int n_max, int R,
+                                     unsigned int replica0, int reps_per_model, const int2 *models, FT *D, long long ldf, int k,
+                                     hipStream_t st) {
     const size_t lds = (size_t)CLFS_SEED_REPS * (size_t)((n_max + 31) / 32) * 4;
     if (lds > 160 * 1024 || R <= 0 || reps_per_model <= 0) return hipErrorInvalidValue;
-    hipError_t e = ensure_lds_limit(reinterpret_cast<const void *>(csr_fields_seed_ragged_kernel), lds);
+    hipError_t e = ensure_lds_limit(reinterpret_cast<const void *>(csr_fields_seed_ragged_kernel<FT>), lds);
     if (e != hipSuccess) return e;
     const int groups_per_model = (reps_per_model + CLFS_SEED_REPS - 1) / CLFS_SEED_REPS;
     const int n_touched = (int)((replica0 + (unsigned int)R - 1) / (unsigned int)reps_per_model - replica0 / (unsigned int)reps_per_model) + 1;
     const long long blocks = (long long)n_touched * groups_per_model;
     if (blocks > 0x7fffffffll) return hipErrorInvalidValue;
     const int slices = (int)std::max(1ll, std::min(64ll, 2048 / blocks));
-    hipLaunchKernelGGL(csr_fields_seed_ragged_kernel, dim3((unsigned int)blocks, slices), dim3(256), lds, st, rowptr, cv, spins,
-                       sstride, R, replica0, reps_per_model, groups_per_model, models, slices, D, ldf);
+    hipLaunchKernelGGL(csr_fields_seed_ragged_kernel<FT>, dim3((unsigned int)blocks, slices), dim3(256), lds, st, rowptr, cv, spins,
+                       sstride, R, replica0, reps_per_model, groups_per_model, models, slices, D, ldf, k);
     return hipGetLastError();
+}
+hipError_t launch_csr_fields_seed_ragged(const long long *rowptr, const int2 *cv, const int8_t *spins, int sstride, int n_max,
+                                         int R, unsigned int replica0, int reps_per_model, const int2 *models, short *D,
+                                         long long ldf, hipStream_t st) {
+    return launch_seed_ragged<short>(rowptr, cv, spins, sstride, n_max, R, replica0, reps_per_model, models, D, ldf, 0, st);
+}
+hipError_t launch_csr_fields_seed_ragged_fx(const long long *rowptr, const int2 *cv, const int8_t *spins, int sstride, int n_max,
+                                            int R, unsigned int replica0, int reps_per_model, const int2 *models, void *D,
+                                            long long ldf, int field_bits, int k, hipStream_t st) {
+    if (field_bits == 64)
+        return launch_seed_ragged<long long>(rowptr, cv, spins, sstride, n_max, R, replica0, reps_per_model, models,
+                                             static_cast<long long *>(D), ldf, k, st);
+    if (field_bits != 32) return hipErrorInvalidValue;
+    return launch_seed_ragged<int>(rowptr, cv, spins, sstride, n_max, R, replica0, reps_per_model, models, static_cast<int *>(D), ldf,
+                                   k, st);
 }
 // fixed point: D[r][i] = 2^k sum_j J_ij s_rj as FT (int | long long).  Every term and partial sum is an integer below
 // 2^53 (set-time scan): the fp64 sums are exact in any order.
@@ -255,11 +285,11 @@ hipError_t launch_scaled_fields(const float *h, int n, int scale, int *hq, hipSt
 // ---- the sweep ------------------------------------------------------------------------------------------------
 // EPT: entries of a row per thread (the longest row <= EPT x threads of the workgroup).  FT: the field type (short;
 // int | long long with FX, the fixed-point fields: a.field_scale = k, a.table_m = 0).
-// RAGGED: a ragged batch -- the replica's model is looked up at entry, n is its n_m (int16 form only).
+// RAGGED: a ragged batch -- the replica's model is looked up at entry, n is its n_m (int16, or with FX the batch-wide
+// fixed point: one k and one width for every model).
 template <int EPT, typename FT, bool FX, bool RAGGED = false>
 __global__ void __launch_bounds__(64 * CLFS_MAX_WAVES) sweep_clf_csr_kernel(const SweepArgs a) {
     static_assert(FX == (sizeof(FT) != 2), "int16 fields: integer form; int32 | int64: fixed point");
-    static_assert(!RAGGED || !FX, "ragged batches: the int16 form");
     constexpr int SLOT_INTS = FX ? CLFS_SLOT_INTS_FX : CLFS_SLOT_INTS;
     constexpr int FB = (int)sizeof(FT);
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -277,15 +307,17 @@ __global__ void __launch_bounds__(64 * CLFS_MAX_WAVES) sweep_clf_csr_kernel(cons
     const double inv_sc = 1.0 / (double)sc;  // exact
     const int *hq = a.clf_hq;
     const long long *rp = a.rowptr64;
+    const float *hf = a.h;  // (FX: h as it is)
     // ragged batches: the replica's model {first row, spins} by its GLOBAL index (wave-uniform, scalar loads); row
-    // extents and hq are read from the model's first row on
+    // extents and hq | h are read from the model's first row on
     int model_n = 0;
     if constexpr (RAGGED) {
         const int m = (int)((a.replica0 + (uint32_t)r) / (uint32_t)a.reps_per_model);
         const int *md = reinterpret_cast<const int *>(a.h + a.ragged) + 2 * m;
         const int model_row0 = *(const __attribute__((address_space(4))) int *)md;
         model_n = *(const __attribute__((address_space(4))) int *)(md + 1);
-        hq += model_row0;
+        if constexpr (FX) hf += model_row0;
+        else hq += model_row0;
         rp += model_row0;
     }
     const int n = RAGGED ? model_n : a.n;
@@ -359,7 +391,7 @@ __global__ void __launch_bounds__(64 * CLFS_MAX_WAVES) sweep_clf_csr_kernel(cons
             const bool vA = tA < n, vB = tB < n;
             int sA, sB;
             float uA, uB;
-            if constexpr (FX) {  // any site mode: the general supplier, one pair per lane
+            if constexpr (FX) {  // any site mode: the general supplier, one pair per lane (ragged: sites of the model's n)
                 const UpdatePair pr = fetch_pair<false>(a, r, k, tA >> 1, vA, n);
                 sA = pr.sA, sB = pr.sB, uA = pr.uA, uB = pr.uB;
             } else {
@@ -372,7 +404,7 @@ __global__ void __launch_bounds__(64 * CLFS_MAX_WAVES) sweep_clf_csr_kernel(cons
             }
             // what does not change during the window: the sites' static fields and row extents
             const int hA = FX ? 0 : hq[sA], hB = FX ? 0 : hq[sB];
-            const float hfA = FX ? a.h[sA] : 0.0f, hfB = FX ? a.h[sB] : 0.0f;
+            const float hfA = FX ? hf[sA] : 0.0f, hfB = FX ? hf[sB] : 0.0f;
             const long long begA = rp[sA], begB = rp[sB];
             const int lenA = (int)(rp[sA + 1] - begA), lenB = (int)(rp[sB + 1] - begB);
             int pos = 0;
@@ -526,7 +558,9 @@ __global__ void __launch_bounds__(64 * CLFS_MAX_WAVES) sweep_clf_csr_kernel(cons
 // Fixed-point fields (a.field_bits = 32 | 64): every single-site rule, site mode and arithmetic; per-update records take
 // the row-per-proposal kernels.
 bool sweep_clf_csr_applies(const SweepArgs &a, int waves) {
-    if (a.ragged && (a.field_bits != 0 || a.rep_list || a.reps_per_model <= 0)) return false;  // ragged batches: int16, all replicas
+    if (a.ragged && (a.rep_list || a.reps_per_model <= 0)) return false;  // ragged batches: all replicas
+    // ... with fixed-point fields: Philox sites (sequential and replayed calls take the streaming ragged kernel)
+    if (a.ragged && a.field_bits != 0 && (a.site_mode != SGA_SITE_RANDOM || a.replay_site || a.replay_u)) return false;
     if (a.field_bits == 32 || a.field_bits == 64)
         return !a.accept_trace && !a.dE_trace && a.rule != SGA_RULE_WOLFF && a.table_m == 0 && a.fields && a.rowptr64 &&
                a.clf_row_max <= 4 * 64 * waves && a.ldf % 8 == 0 && a.sstride % 16 == 0 &&
@@ -540,7 +574,14 @@ hipError_t launch_sweep_clf_csr(const SweepArgs &a, int waves, hipStream_t st) {
     if (waves < 1 || waves > CLFS_MAX_WAVES || !sweep_clf_csr_applies(a, waves)) return hipErrorInvalidValue;
     const int ept = (a.clf_row_max + 64 * waves - 1) / (64 * waves);
     void (*kern)(const SweepArgs);
-    if (a.field_bits == 64)
+    if (a.field_bits == 64 && a.ragged)
+        kern = ept <= 1   ? sweep_clf_csr_kernel<1, long long, true, true>
+               : ept <= 2 ? sweep_clf_csr_kernel<2, long long, true, true>
+                          : sweep_clf_csr_kernel<4, long long, true, true>;
+    else if (a.field_bits == 32 && a.ragged)
+        kern = ept <= 1 ? sweep_clf_csr_kernel<1, int, true, true> : ept <= 2 ? sweep_clf_csr_kernel<2, int, true, true>
+                                                                              : sweep_clf_csr_kernel<4, int, true, true>;
+    else if (a.field_bits == 64)
         kern = ept <= 1 ? sweep_clf_csr_kernel<1, long long, true> : ept <= 2 ? sweep_clf_csr_kernel<2, long long, true>
                                                                               : sweep_clf_csr_kernel<4, long long, true>;
     else if (a.field_bits == 32)
@@ -556,7 +597,11 @@ hipError_t launch_sweep_clf_csr(const SweepArgs &a, int waves, hipStream_t st) {
     hipError_t e = ensure_lds_limit(reinterpret_cast<const void *>(kern), lds);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(kern, dim3(a.rep_list ? a.rep_count : a.R), dim3(64 * waves), lds, st, a);
-    if (a.field_bits)
+    if (a.field_bits && a.ragged)
+        note_sweep_kernel("sweep_clf_csr_kernel<%d entries per thread, ragged> x %d wave(s) (int%d fixed-point fields in LDS, k=%d, "
+                          "row read on accept only; each replica on its own model's rows)",
+                          ept <= 1 ? 1 : ept <= 2 ? 2 : 4, waves, a.field_bits, a.field_scale);
+    else if (a.field_bits)
         note_sweep_kernel("sweep_clf_csr_kernel<%d entries per thread> x %d wave(s) (int%d fixed-point fields in LDS, k=%d, "
                           "row read on accept only)",
                           ept <= 1 ? 1 : ept <= 2 ? 2 : 4, waves, a.field_bits, a.field_scale);
