@@ -6,6 +6,8 @@
 //   sga_state.cpp     state access, checkpoint / resume, timing, sga_describe, checksum
 //   sga_route.cpp     WHICH form runs: pure functions of the problem's traits and the options, and the cached-field
 //                     modes' sweep-time policy over the acceptance counters (no HIP calls)
+//   sga_classify.cpp  WHICH arithmetic a problem admits: accumulation class, accept table, cached-field eligibility and
+//                     the refusal reasons, pure functions of the set-time scan summaries (no HIP calls)
 #ifndef SGA_ENGINE_IMPL_H
 #define SGA_ENGINE_IMPL_H
 #include <hip/hip_runtime.h>

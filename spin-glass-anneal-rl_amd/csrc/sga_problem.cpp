@@ -1,9 +1,28 @@
 // sga_problem.cpp -- the problem side of the C ABI (include/sga.h): sga_set_dense / sga_set_dense_batch, sga_set_csr /
 // sga_set_csr64, sga_set_tsp.  Value and structure scans on the device, the packed layouts the kernels read, CSR row
-// layouts (plain / 64-entry slots / packed entries).  Which form a problem then runs in: sga_route.cpp.
+// layouts (plain / 64-entry slots / packed entries).  Which arithmetic a problem admits: sga_classify.cpp; which form it
+// then runs in: sga_route.cpp.
+#include "sga_classify.h"
 #include "sga_engine_impl.h"
 
 namespace {
+
+static_assert(sga_classify::ACC_F32_TABLE == sga::CSR_ACC_F32_TABLE && sga_classify::ACC_F32 == sga::CSR_ACC_F32 &&
+              sga_classify::ACC_F64 == sga::CSR_ACC_F64 && sga_classify::ACC_F64_CANON == sga::CSR_ACC_F64_CANON, "acc classes");
+
+// the CSR scans' flag words as sga_classify reads them
+sga_classify::CsrScan csr_scan_of(const int *flags) {
+    sga_classify::CsrScan s;
+    s.not_integral = flags[sga::CSR_NOT_INTEGRAL];
+    s.unsorted = flags[sga::CSR_UNSORTED] != 0;
+    s.diagonal = flags[sga::CSR_DIAGONAL] != 0;
+    s.asymmetric = flags[sga::CSR_ASYMMETRIC] != 0;
+    std::memcpy(&s.row_abs_max, &flags[sga::CSR_ROW_ABS_MAX], sizeof(float));
+    std::memcpy(&s.row_j_abs_max, &flags[sga::CSR_ROW_J_ABS_MAX], sizeof(float));
+    s.exp_hi_word = flags[sga::CSR_EXP_HI];
+    s.exp_lo_word = flags[sga::CSR_EXP_LO];
+    return s;
+}
 
 // Pack the caller's fp32 matrix (device pointer `src`, row stride ld_src) into the engine's
 // layout(s): rows packed to 128 bytes, not padded to the kernel's whole chunks (2.4 % fewer bytes
@@ -261,85 +280,30 @@ int set_csr_common(sga_engine *e, const void *rowptr, bool wide_extents, const i
     } else {
         flags[sga::CSR_ASYMMETRIC] = 1;
     }
-    e->consistent_dE = !flags[sga::CSR_ASYMMETRIC] && !flags[sga::CSR_DIAGONAL];
-    // integer-valued problem?  then dE takes at most M = max_i(sum_j |J_ij| + |h_i|) even values
-    float m;
-    std::memcpy(&m, &flags[sga::CSR_ROW_ABS_MAX], sizeof(m));
-    // (J integer, h a multiple of 1/2 -- penalty encodings of 0/1 variables: dE takes integer values,
-    // tabulated at twice the resolution)
-    e->table_m = 0;
-    e->table_scale = 1;
-    e->csr_row_abs_max = m;
-    if (!flags[sga::CSR_NOT_INTEGRAL] && m >= 1.0f && m < 16777216.0f) {
-        e->table_m = (int)std::min(m, 2048.0f);
-    } else if ((flags[sga::CSR_NOT_INTEGRAL] & 5) == 0 && m >= 1.0f && m < 8388608.0f &&
-               e->opt[OPT_HALF_TABLE] != 0) {
-        e->table_m = (int)std::min(2.0f * m, 2048.0f);
-        e->table_scale = 2;
-    }
-    {
-        float mj;
-        std::memcpy(&mj, &flags[sga::CSR_ROW_J_ABS_MAX], sizeof(mj));
-        e->row_j_abs_max = mj;
-        // cached-field sweep over CSR: exact int16 dynamic fields, table arithmetic, every entry its own column
-        e->clf_csr_problem = (flags[sga::CSR_NOT_INTEGRAL] & 5) == 0 && e->table_m > 0 && e->consistent_dE && sorted &&
-                             mj < 32768.0f && n <= (1 << 30);
-    }
     HIPCHK(sga::launch_gather_diag_csr(e->rowptr64, ci, vv, n, e->diag, e->stream));
     std::vector<long long> src(np1);
     HIPCHK(hipMemcpyAsync(src.data(), e->rowptr64, sizeof(long long) * np1, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
     {
-        // How exact is a row sum?  Integer J with sum |J| < 2^24: fp32 accumulation is exact.  Else,
-        // if every J's set bits lie within 53 binary places of each other once the carries of
-        // the longest row are counted, the fp64 sum of the (exact) fp32 products is exact in any
-        // order.  Only couplings of a wider dynamic range need the canonical summation order.
+        // the class of the problem (sga_classify.cpp), once the longest row is known
         long long max_len = 0;
         for (int i = 0; i < n; ++i) max_len = std::max(max_len, src[(size_t)i + 1] - src[(size_t)i]);
-        int carry = 0;
-        while ((1ll << carry) < std::max<long long>(max_len, 1)) ++carry;
-        const int e_hi = flags[sga::CSR_EXP_HI] - 1024, e_lo = 1024 - flags[sga::CSR_EXP_LO];
-        const bool any = flags[sga::CSR_EXP_HI] != 0;
-        const bool j_int = (flags[sga::CSR_NOT_INTEGRAL] & 1) == 0;
-        if (j_int && m < 16777216.0f)
-            e->csr_acc = e->table_m > 0 ? sga::CSR_ACC_F32_TABLE : sga::CSR_ACC_F32;
-        else if (!any || (e_hi - e_lo + 1 + carry) <= 52)
-            e->csr_acc = sga::CSR_ACC_F64;
-        else
-            e->csr_acc = sga::CSR_ACC_F64_CANON;
-        if (e->opt[OPT_FORCE_CSR_ACC] > 0)  // parity tests: the slower forms
-            e->csr_acc = std::max(e->csr_acc, std::min(3, (int)e->opt[OPT_FORCE_CSR_ACC]));
-        // Is X = sum_i mv_i s_i exact in fp64 in any order?  Every row sum is exact (classes f32 / f64-exact) and a
-        // multiple of 2^e_lo, so is its fp32 rounding mv_i; every partial sum of X is at most n max_i sum_j |J_ij|
-        // (mj: an fp32 rounding, < 1 ulp either way).  Then the all-replica pass's group order gives the bits of the
-        // per-replica kernels' order (recompute_energy_range).
-        e->csr_x_exact = e->csr_acc != sga::CSR_ACC_F64_CANON &&
-                         (!any || std::ldexp((double)n * (double)e->row_j_abs_max * (1.0 + 0x1.0p-20), -e_lo) < 0x1.0p53);
-        // Option "clf_fixed_point": the cached-field sweep for the problems the int16 form does not take.  Every row
-        // sum is exact (acc classes f32 / f64-exact), and every set bit of every J lies at or above 2^-k, k = minus the
-        // exponent of the lowest set bit: 2^k sum_j J_ij s_j is an integer of at most B = 2^k max_i sum_j |J_ij| (< 2^53
-        // by the class's own bound), kept exactly as int32 (B < 2^31) or int64.  h is never folded in.
-        if (e->opt[OPT_CLF_FIXED_POINT] == 1 && !e->clf_csr_problem) {
-            const int k = any ? flags[sga::CSR_EXP_LO] - 1024 : 0;
-            // (mj is the fp32 rounding of an fp64 sum: < 1 ulp either way)
-            const double bound = std::ldexp((double)e->row_j_abs_max, k) * (1.0 + 0x1.0p-20);
-            if (e->csr_acc == sga::CSR_ACC_F64_CANON)
-                e->clf_fx_why = "cached local fields (fixed point): the couplings need the canonical fp64 summation order "
-                                "(acc class f64-canonical: their binary places span more than 53 bits, so no exact fixed "
-                                "point holds a row sum)";
-            else if (!sorted)
-                e->clf_fx_why = "cached local fields (fixed point): CSR rows must be strictly sorted by column (no duplicate entries)";
-            else if (flags[sga::CSR_DIAGONAL])
-                e->clf_fx_why = "cached local fields (fixed point): J must have a zero diagonal";
-            else if (flags[sga::CSR_ASYMMETRIC])
-                e->clf_fx_why = "cached local fields (fixed point): J must be symmetric";
-            else if (n > (1 << 30) || !(bound < 0x1.0p62))
-                e->clf_fx_why = "cached local fields (fixed point): fields wider than int64";
-            if (!e->clf_fx_why) {
-                e->clf_csr_problem = true;
-                e->clf_fx_bits = bound < 0x1.0p31 ? 32 : 64;
-                e->clf_fx_k = k;
-            }
+        const sga_classify::CsrClass c = sga_classify::classify_csr(
+            csr_scan_of(flags), max_len, n, {e->opt[OPT_HALF_TABLE] != 0, (int)e->opt[OPT_FORCE_CSR_ACC]});
+        e->consistent_dE = c.consistent_dE;
+        e->table_m = c.table_m;
+        e->table_scale = c.table_scale;
+        e->csr_row_abs_max = c.row_abs_max;
+        e->row_j_abs_max = c.row_j_abs_max;
+        e->clf_csr_problem = c.clf_int16;
+        e->csr_acc = c.acc;
+        e->csr_x_exact = c.x_exact;
+        if (e->opt[OPT_CLF_FIXED_POINT] == 1 && !e->clf_csr_problem) {  // the problems the int16 form does not take
+            const sga_classify::FxVerdict v = sga_classify::csr_fixed_point(c, n);
+            e->clf_fx_why = v.why;
+            e->clf_fx_bits = v.bits;
+            e->clf_fx_k = v.k;
+            e->clf_csr_problem = !v.why;
         }
     }
     // The layout the kernels read: (column, value) interleaved, one 8-byte load per entry.  Long
@@ -362,6 +326,16 @@ int set_csr_common(sga_engine *e, const void *rowptr, bool wide_extents, const i
     dev_free(e->val);
     if (rc != SGA_OK) e->free_problem();
     return rc;
+}
+
+// does the diagonal pack_dense extracted hold a non-zero?  (*out: 0 | 1)
+int diag_nonzero(sga_engine *e, long long rows, int *out) {
+    std::vector<float> dg((size_t)rows);
+    HIPCHK(hipMemcpyAsync(dg.data(), e->diag, sizeof(float) * (size_t)rows, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    *out = 0;
+    for (float v : dg) *out = *out || v != 0.0f;
+    return SGA_OK;
 }
 
 // Sparse couplings handed over as a dense matrix (the reference's IsingModel is dense by default; its assignment
@@ -464,107 +438,52 @@ int sga_set_dense_batch(sga_engine *e, const float *J, int64_t ldJ, const float 
     HIPCHK(sga::launch_check_symmetric(src, ld_src, rows, n, flags + 4, e->stream));
     HIPCHK(hipMemcpyAsync(hflags, flags, sizeof(hflags), hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
-    e->consistent_dE = hflags[4] == 0;
-    const bool fits_i8 = hflags[0] == 0;
-    if (storage == SGA_J_I8 && !fits_i8)
+    const sga_classify::DenseClass c = sga_classify::classify_dense(hflags, n, n_models, storage, e->opt[OPT_FORCE_DENSE_CANON] != 0);
+    e->consistent_dE = c.consistent_dE;
+    if (storage == SGA_J_I8 && !c.fits_i8)
         return fail(SGA_ERR_INVALID, "int8 storage requested but J is not integer in [-127,127]");
-    const bool ternary = hflags[1] == 0 && n_models == 1;
-    if (storage == SGA_J_T2 && !ternary)
+    if (storage == SGA_J_T2 && !c.ternary)
         return fail(SGA_ERR_INVALID, "bit-plane storage needs one model with J in {-1, 0, +1}");
-    e->use_t2 = storage == SGA_J_T2 || (storage == SGA_J_AUTO && ternary && n >= 4096);
-    e->want_i8 = e->use_t2 || (storage == SGA_J_I8) || (storage == SGA_J_AUTO && fits_i8);
-    float m;
-    std::memcpy(&m, &hflags[2], sizeof(float));
-    const unsigned nonint = (unsigned)hflags[3];  // bit 0: some J, bit 1: some h not an integer
-    // fp32 partial sums are exact (any order) when J is integer valued and no row's sum of
-    // |J| reaches 2^24; otherwise the row sum is accumulated in fp64
-    e->acc64 = !e->want_i8 && !((nonint & 1u) == 0u && m < 16777216.0f);
-    {
-        // ... and the fp64 sum of a row's (exact) fp32 products is exact in ANY order when the set bits
-        // of all J lie within 53 binary places of each other, the row's carries included; only
-        // couplings of a wider dynamic range (e.g. Gaussian J: tiny values next to large ones) need the
-        // canonical summation order and its one tree per 256-element chunk
-        int carry = 0;
-        while ((1ll << carry) < n) ++carry;
-        const bool any = hflags[5] != 0;
-        const int span = (hflags[5] - 1024) - (1024 - hflags[6]) + 1;
-        e->acc_canon = e->acc64 && any && span + carry > 52;
-        if (e->opt[OPT_FORCE_DENSE_CANON]) e->acc_canon = e->acc64;  // parity tests
-    }
-    // integer problem: tabulate exp(float32(-2k/T)) for the moves k <= min(M, 2048) per sweep
-    if (nonint == 0u && m >= 1.0f && m < 16777216.0f) e->table_m = (int)std::min(m, 2048.0f);
-    // cached-local-field sweep: exact integer fields, dE of the rule == energy change
-    // (h a multiple of 1/2 -- the penalty encodings of 0/1 variables -- keeps 2 F an integer: scale 2).  A many-model
-    // batch qualifies as a whole: the scans above run over all stacked rows, so scale, field width, accept table and
-    // max |J| are batch-wide -- a field kept at scale 2 or as int32 because ANOTHER model needs it is still exact
-    e->row_abs_max = m;
-    {
-        float jm;
-        std::memcpy(&jm, &hflags[7], sizeof(float));
-        e->j_abs_max = (int)std::min(std::ceil((double)jm), 16777216.0);
-    }
-    e->clf_scale = (nonint & 2u) ? 2 : 1;
-    e->clf_problem = (nonint & 5u) == 0u && (double)m * e->clf_scale < 16777216.0 && e->consistent_dE;
-    e->clf_bits = (double)m * e->clf_scale < 32768.0 ? 16 : 32;
+    e->use_t2 = c.use_t2;
+    e->want_i8 = c.want_i8;
+    e->acc64 = c.acc64;
+    e->acc_canon = c.acc_canon;
+    e->table_m = c.table_m;
+    e->row_abs_max = c.row_abs_max;
+    e->j_abs_max = c.j_abs_max;
+    e->clf_scale = c.clf_scale;
+    e->clf_problem = c.clf_problem;
+    e->clf_bits = c.clf_bits;
     // Sparse matrix?  (route_sparse_dense above.)  Taken when the caller asked for one row read per proposal
     // (field cache OFF), or left the choice (AUTO) on a problem the cached-field sweep cannot serve: where that
     // sweep applies it is the better form while few proposals are accepted (C2b, 1024 replicas, acceptance 2 %:
     // dense int8 rows 7.7e8, as CSR four updates per step 4.3e9, cached fields 1.06e10 attempts/s).
-    if (sga_route::sparse_route_wanted(storage, n_models, n, (nonint & 1u) == 0u, e->field_cache, e->clf_problem,
+    if (sga_route::sparse_route_wanted(storage, n_models, n, (c.nonint & 1u) == 0u, e->field_cache, e->clf_problem,
                                        e->opt[OPT_SPARSE_ROUTE])) {
         bool taken = false;
         const int rcr = route_sparse_dense(e, src, ld_src, h, n, &taken);  // (h: the caller's pointer)
         if (rcr != SGA_OK || taken) return rcr;
     }
     int rc = pack_dense(e, src, ld_src);
-    // Option "clf_fixed_point": the cached-field sweep for the dense problems the integer form does not take
-    // (sweep_clf_fx.hip).  In the exact accumulation classes -- fp32-exact, f64-exact -- every row sum is exact in any
-    // order; k = minus the exponent of the lowest set bit of any J (0 for integer J) makes every 2^k J an integer, so
-    // D_i = 2^k sum_j J_ij s_j is an integer of at most B = 2^k max_i sum_j |J_ij| (< 2^53 by the class's own bound),
-    // kept exactly as int32 (B < 2^31) or int64.  h is never folded in.  Bit-plane problems are served from their int8
-    // rows.  (After the packing: the diagonal it extracts tells an asymmetric J from a non-zero diagonal.)
-    if (rc == SGA_OK && e->opt[OPT_CLF_FIXED_POINT] == 1 && !e->clf_problem) {
-        const int k = std::max(hflags[5] != 0 ? hflags[6] - 1024 : 0, 0);
-        // (m bounds max_i sum_j |J_ij| from above -- it holds |h_i| too -- and is the fp32 rounding of an fp64 sum: < 1 ulp)
-        const double bound = std::ldexp((double)m, k) * (1.0 + 0x1.0p-20);
-        if (n_models != 1)
-            e->clf_fx_why = "cached local fields (fixed point): not built for dense batches (one model only)";
-        else if (e->acc_canon)
-            e->clf_fx_why = "cached local fields (fixed point): the couplings need the canonical fp64 summation order "
-                            "(acc class f64-canonical: their binary places span more than 53 bits, so no exact fixed "
-                            "point holds a row sum)";
-        else if (!e->consistent_dE) {
-            std::vector<float> dg((size_t)n);
-            HIPCHK(hipMemcpyAsync(dg.data(), e->diag, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, e->stream));
-            HIPCHK(hipStreamSynchronize(e->stream));
-            bool diag = false;
-            for (float v : dg) diag = diag || v != 0.0f;
-            e->clf_fx_why = diag ? "cached local fields (fixed point): J must have a zero diagonal"
-                                 : "cached local fields (fixed point): J must be symmetric";
-        } else if (!(bound < 0x1.0p62))
-            e->clf_fx_why = "cached local fields (fixed point): fields wider than int64";
-        else {
-            e->clf_fx_bits = bound < 0x1.0p31 ? 32 : 64;
-            e->clf_fx_k = k;
-        }
-    }
-    // which condition of the integer cached-field form failed (the route query carries only the verdict); a batch is
-    // scanned as a whole, so the reason names what SOME model does
+    // The problems the integer cached-field form does not take: which of its conditions failed, and with option
+    // "clf_fixed_point" the fixed-point form's verdict (sga_classify.cpp).  After the packing: the diagonal it extracts
+    // tells an asymmetric J from a non-zero diagonal -- read back at most once, and only when dE is not consistent.
     if (rc == SGA_OK && !e->clf_problem) {
-        if (nonint & 1u)
-            e->clf_why = "cached local fields: J must be integer valued (a dense batch: in every model)";
-        else if (nonint & 4u)
-            e->clf_why = "cached local fields: h must be in multiples of 1/2 (a dense batch: in every model)";
-        else if (!e->consistent_dE) {
-            std::vector<float> dg((size_t)rows);
-            HIPCHK(hipMemcpyAsync(dg.data(), e->diag, sizeof(float) * (size_t)rows, hipMemcpyDeviceToHost, e->stream));
-            HIPCHK(hipStreamSynchronize(e->stream));
-            bool diag = false;
-            for (float v : dg) diag = diag || v != 0.0f;
-            e->clf_why = diag ? "cached local fields: J must have a zero diagonal (a dense batch: in every model)"
-                              : "cached local fields: J must be symmetric (a dense batch: in every model)";
-        } else
-            e->clf_why = "cached local fields: max_i (sum_j |J_ij| + |h_i|) must stay below 2^24 (2^23 with half-integer h)";
+        int diag_rc = SGA_OK, diag = -1;
+        const auto diagonal = [&] {
+            if (diag < 0) diag_rc = diag_nonzero(e, rows, &diag);
+            return diag == 1;
+        };
+        if (e->opt[OPT_CLF_FIXED_POINT] == 1) {
+            const sga_classify::FxVerdict v = sga_classify::dense_fixed_point(c, n_models, diagonal);
+            if (diag_rc != SGA_OK) return diag_rc;
+            e->clf_fx_why = v.why;
+            e->clf_fx_bits = v.bits;
+            e->clf_fx_k = v.k;
+        }
+        const char *why = sga_classify::dense_clf_why(c, diagonal);
+        if (diag_rc != SGA_OK) return diag_rc;
+        e->clf_why = why;
     }
     if (rc == SGA_OK) rc = ensure_packed(e);
     // the source (the caller's buffer, or the staging copy about to be released) is done with
@@ -604,22 +523,9 @@ int sga_set_tsp(sga_engine *e, const float *dist, int64_t ld, int n_cities, floa
     HIPCHK(hipMemcpy(hh.data(), h, sizeof(float) * (size_t)N, hipMemcpyDefault));
     const float a2 = -(city_visit / 2.0f), b2 = -(position_fill / 2.0f);
     bool integral = a2 == std::rint(a2) && b2 == std::rint(b2);
-    int e_hi = -10000, e_lo = 10000;
-    auto span = [&](float v) {  // binary exponents of the highest and the lowest set bit
-        if (v == 0.0f || !std::isfinite(v)) return;
-        int ex;
-        const float m = std::frexp(std::fabs(v), &ex);  // v = m 2^ex, m in [0.5, 1)
-        uint32_t mant = (uint32_t)std::ldexp(m, 24);    // 24-bit integer mantissa
-        int low = 0;
-        while (!(mant & 1u)) {
-            mant >>= 1;
-            ++low;
-        }
-        e_hi = std::max(e_hi, ex - 1);
-        e_lo = std::min(e_lo, ex - 24 + low);
-    };
-    span(a2);
-    span(b2);
+    sga_classify::BitSpan bits;  // binary exponents of the highest and the lowest set bit of any coupling
+    sga_classify::span_add(bits, a2);
+    sga_classify::span_add(bits, b2);
     double worst_row = 0.0;
     for (int c = 0; c < n; ++c) {
         double row = 0.0;
@@ -628,17 +534,16 @@ int sga_set_tsp(sga_engine *e, const float *dist, int64_t ld, int n_cities, floa
             const float v1 = dh[(size_t)c * n + q] / 4.0f, v2 = dh[(size_t)q * n + c] / 4.0f;
             if (!std::isfinite(v1)) return fail(SGA_ERR_INVALID, "distance matrix holds a non-finite value");
             integral = integral && v1 == std::rint(v1);
-            span(v1);
+            sga_classify::span_add(bits, v1);
             row += std::fabs((double)v1) + std::fabs((double)v2);
         }
         worst_row = std::max(worst_row, row);
     }
     for (long long i = 0; i < N && integral; ++i) integral = hh[(size_t)i] == std::rint(hh[(size_t)i]);
     worst_row += (double)(n - 1) * (std::fabs((double)a2) + std::fabs((double)b2));
-    int carry = 0;
-    while ((1ll << carry) < 4ll * n) ++carry;
-    const bool exact32 = integral && worst_row < 16777216.0;
-    e->tsp_exact = exact32 || e_hi < e_lo || (e_hi - e_lo + 1 + carry) <= 52;
+    const sga_classify::TspClass tc = sga_classify::classify_tsp(bits, integral, worst_row, n);
+    const bool exact32 = tc.exact32;
+    e->tsp_exact = tc.tsp_exact;
     // site / n by multiply-shift, verified for every site
     const unsigned int magic = (unsigned int)((0x100000000ull + (unsigned long long)n - 1) / (unsigned long long)n);
     for (long long sidx = 0; sidx < N; ++sidx)
@@ -750,24 +655,13 @@ int set_groups_common(sga_engine *e, const char *who_, int n, int n_groups, cons
         }
     }
     // the fp32-exact class: every coefficient on one grid 2^-k, 2^k max_i sum_{g contains i} |c_g| (|g| - 1) < 2^24
-    int k = -1000;  // the finest grid any coefficient needs: c = m 2^(ex - 24), lowest set bit at ex - 24 + low
-    for (size_t q = 0; q < G; ++q) {
-        if (cf[q] == 0.0f || mp[q + 1] - mp[q] < 2) continue;  // (contributes no coupling)
-        int ex;
-        const float m = std::frexp(std::fabs(cf[q]), &ex);
-        uint32_t mant = (uint32_t)std::ldexp(m, 24);
-        int low = 0;
-        while (!(mant & 1u)) {
-            mant >>= 1;
-            ++low;
-        }
-        k = std::max(k, -(ex - 24 + low));
-    }
+    sga_classify::BitSpan grid;  // the finest grid any coefficient needs: the lowest set bit of any that contributes a coupling
+    for (size_t q = 0; q < G; ++q) sga_classify::groups_span_add(grid, cf[q], mp[q + 1] - mp[q]);
     std::vector<double> bound((size_t)n, 0.0);
     int kmax = 0;
     // the remainder: structure scans on the device (sga_set_csr's kernels), then its grid and sum_j |R_ij| per row
     RestStage rs;
-    int rest_max_row = 0;
+    int rest_max_row = 0, rest_exp_lo = 0;
     if (rest) {
         const size_t np1 = (size_t)n + 1, nz = (size_t)nnz;
         std::vector<int32_t> rp(np1);
@@ -821,7 +715,7 @@ int set_groups_common(sga_engine *e, const char *who_, int n, int n_groups, cons
                           rest_max_row, SGA_GROUPS_MAX_REST_ROW, way_out.c_str());
             return fail(SGA_ERR_UNSUPPORTED, msg);
         }
-        if (flags[sga::CSR_EXP_LO]) k = std::max(k, flags[sga::CSR_EXP_LO] - 1024);  // the finest grid any R_ij needs
+        rest_exp_lo = flags[sga::CSR_EXP_LO];  // the finest grid any R_ij needs
         HIPCHK(hipMalloc(&rs.row_abs, sizeof(double) * (size_t)n));
         HIPCHK(sga::launch_groups_rest_row_abs(rs.rowptr64, vv, n, rs.row_abs, e->stream));
         HIPCHK(hipMemcpyAsync(bound.data(), rs.row_abs, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, e->stream));
@@ -833,7 +727,6 @@ int set_groups_common(sga_engine *e, const char *who_, int n, int n_groups, cons
             if (!std::isfinite(bound[(size_t)i]))
                 return fail(SGA_ERR_INVALID, who + ": remainder row " + std::to_string(i) + " holds a value that is not finite");
     }
-    if (k == -1000) k = 0;
     for (size_t q = 0; q < G; ++q) {
         const double term = std::fabs((double)cf[q]) * (double)(mp[q + 1] - mp[q] - 1);
         for (long long m = mp[q]; m < mp[q + 1]; ++m) bound[(size_t)mem[(size_t)m]] += term;
@@ -843,7 +736,9 @@ int set_groups_common(sga_engine *e, const char *who_, int n, int n_groups, cons
         worst = std::max(worst, bound[(size_t)i]);
         kmax = std::max(kmax, count[(size_t)i + 1]);
     }
-    if (k > 126 || std::ldexp(worst, k) >= 16777216.0) {
+    const sga_classify::GroupsClass gc = sga_classify::classify_groups(grid, rest_exp_lo, worst);
+    const int k = gc.k;
+    if (!gc.exact) {
         char msg[320];
         std::snprintf(msg, sizeof(msg),
                       "%s: the couplings are not provably exact in fp32: the coefficients%s lie on the grid 2^%d and "
@@ -1024,21 +919,10 @@ int sga_set_csr_batch(sga_engine *e, int n_models, const int32_t *n_spins, const
     SGA_BATCH_CHK(hipMemcpyAsync(src.data(), e->rowptr64, sizeof(long long) * np1, hipMemcpyDeviceToHost, e->stream));
     SGA_BATCH_CHK(hipStreamSynchronize(e->stream));
 
-    // per model: the scans of sga_set_csr, then its class; the batch takes the most general class and the widest table
-    int acc_b = sga::CSR_ACC_F32_TABLE, scale_b = 1;
-    bool sorted_b = true;
-    float m_b = 0.0f, mj_b = 0.0f;
-    // option "ragged_field_cache": sga_set_csr's eligibility for the int16 cached-field sweep, over every model; the
-    // first model that fails one of the conditions and which (sga_sweep under SGA_FIELD_CACHE_ON reports it)
-    const bool want_clf = e->opt[OPT_RAGGED_FIELD_CACHE] == 1;
-    std::string clf_why;
-    // ... with option "clf_fixed_point" too: a batch the int16 form refuses is scanned for the fixed-point form (DESIGN
-    // 4.1l).  Per model: the class of its row sums, sorted rows, rows of <= 2048 entries; batch-wide: k = the finest grid
-    // any model needs, and 2^k max_i sum_j |J_ij| over all rows, which picks the width.  fx_why: the first offending model.
-    const bool want_fx = want_clf && e->opt[OPT_CLF_FIXED_POINT] == 1;
-    std::string fx_why;
-    int fx_k = INT32_MIN;
-    std::vector<float> fx_mj((size_t)n_models, 0.0f);
+    // per model: the scans of sga_set_csr, then its class (force_csr_acc applies to the batch); sga_classify::fold_ragged
+    // takes the most general class and the widest table, and names the first model that keeps the batch off the
+    // cached-field forms (options "ragged_field_cache", "clf_fixed_point"; sga_sweep under SGA_FIELD_CACHE_ON reports it)
+    std::vector<sga_classify::CsrClass> classes((size_t)n_models);
     std::vector<int> row0((size_t)n_models);
     std::vector<int2> models((size_t)n_models);
     for (int m = 0, r0 = 0; m < n_models; r0 += n_spins[m], ++m) {
@@ -1052,7 +936,6 @@ int sga_set_csr_batch(sga_engine *e, int n_models, const int32_t *n_spins, const
         if (flags[sga::CSR_DIAGONAL])
             return bail(SGA_ERR_UNSUPPORTED, who + "non-zero diagonal entry (ragged CSR batches need a zero diagonal)");
         const bool sorted = !flags[sga::CSR_UNSORTED];
-        sorted_b = sorted_b && sorted;
         const long long mnnz = src[(size_t)r0 + nm] - src[(size_t)r0];
         const double avg_deg = (double)mnnz / nm;
         int sym[sga::CSR_FLAG_COUNT];
@@ -1065,98 +948,25 @@ int sga_set_csr_batch(sga_engine *e, int n_models, const int32_t *n_spins, const
         }
         if (sym[sga::CSR_ASYMMETRIC])
             return bail(SGA_ERR_UNSUPPORTED, who + "asymmetric J (ragged CSR batches need J[i][j] == J[j][i])");
-        // sga_set_csr's classification of this model alone
-        float mm;
-        std::memcpy(&mm, &sym[sga::CSR_ROW_ABS_MAX], sizeof(mm));
-        int table_m = 0, scale = 1;
-        if (!sym[sga::CSR_NOT_INTEGRAL] && mm >= 1.0f && mm < 16777216.0f) {
-            table_m = 1;
-        } else if ((sym[sga::CSR_NOT_INTEGRAL] & 5) == 0 && mm >= 1.0f && mm < 8388608.0f && e->opt[OPT_HALF_TABLE] != 0) {
-            table_m = 1;
-            scale = 2;
-        }
         long long max_len = 0;
         for (int i = r0; i < r0 + nm; ++i) max_len = std::max(max_len, src[(size_t)i + 1] - src[(size_t)i]);
-        int carry = 0;
-        while ((1ll << carry) < std::max<long long>(max_len, 1)) ++carry;
-        const int e_hi = sym[sga::CSR_EXP_HI] - 1024, e_lo = 1024 - sym[sga::CSR_EXP_LO];
-        const bool any = sym[sga::CSR_EXP_HI] != 0;
-        const bool j_int = (sym[sga::CSR_NOT_INTEGRAL] & 1) == 0;
-        int acc;
-        if (j_int && mm < 16777216.0f) acc = table_m > 0 ? sga::CSR_ACC_F32_TABLE : sga::CSR_ACC_F32;
-        else if (!any || (e_hi - e_lo + 1 + carry) <= 52) acc = sga::CSR_ACC_F64;
-        else acc = sga::CSR_ACC_F64_CANON;
-        acc_b = std::max(acc_b, acc);
-        if (acc == sga::CSR_ACC_F32_TABLE) scale_b = std::max(scale_b, scale);
-        m_b = std::max(m_b, mm);
-        float mj;
-        std::memcpy(&mj, &sym[sga::CSR_ROW_J_ABS_MAX], sizeof(mj));
-        mj_b = std::max(mj_b, mj);
-        if (want_clf && clf_why.empty()) {
-            const char *bad = nullptr;
-            if (sym[sga::CSR_NOT_INTEGRAL] & 1) bad = "J is not integer valued";
-            else if (sym[sga::CSR_NOT_INTEGRAL] & 4) bad = "h is not a multiple of 1/2";
-            else if (!sorted) bad = "rows are not strictly sorted by column (unsorted or duplicate entries)";
-            else if (!(mj < 32768.0f)) bad = "max_i sum_j |J_ij| is not below 2^15 (int16 fields)";
-            else if (max_len > 4 * 64 * 8) bad = "a row is longer than 2048 entries";
-            else if (acc != sga::CSR_ACC_F32_TABLE)
-                bad = "the accept table does not apply (max_i (sum_j |J_ij| + |h_i|) outside [1, 2^24), or half-integer h with "
-                      "option \"half_integer_table\" = 0)";
-            if (bad) clf_why = "cached local fields over ragged CSR batches: " + who + bad;
-        }
-        if (want_fx) {
-            fx_mj[(size_t)m] = mj;
-            if (any) fx_k = std::max(fx_k, sym[sga::CSR_EXP_LO] - 1024);  // k_m: minus the exponent of J's lowest set bit
-            const char *bad = nullptr;
-            if (acc == sga::CSR_ACC_F64_CANON)
-                bad = "the couplings need the canonical fp64 summation order (acc class f64-canonical: their binary places span "
-                      "more than 53 bits, so no exact fixed point holds a row sum)";
-            else if (!sorted) bad = "rows are not strictly sorted by column (unsorted or duplicate entries)";
-            else if (max_len > 4 * 64 * 8) bad = "a row is longer than 2048 entries";
-            if (bad && fx_why.empty()) fx_why = "cached local fields over ragged CSR batches (fixed point): " + who + bad;
-        }
+        classes[(size_t)m] = sga_classify::classify_csr(csr_scan_of(sym), max_len, nm, {e->opt[OPT_HALF_TABLE] != 0, 0});
     }
-    if (e->opt[OPT_FORCE_CSR_ACC] > 0) acc_b = std::max(acc_b, std::min(3, (int)e->opt[OPT_FORCE_CSR_ACC]));
-    e->csr_acc = acc_b;
+    const bool want_clf = e->opt[OPT_RAGGED_FIELD_CACHE] == 1;
+    const sga_classify::RaggedClass b = sga_classify::fold_ragged(
+        classes, {(int)e->opt[OPT_FORCE_CSR_ACC], want_clf, want_clf && e->opt[OPT_CLF_FIXED_POINT] == 1});
+    e->csr_acc = b.acc;
     e->csr_x_exact = false;  // (no all-replica pass over ragged batches)
-    e->table_scale = acc_b == sga::CSR_ACC_F32_TABLE ? scale_b : 1;
-    e->table_m = acc_b == sga::CSR_ACC_F32_TABLE ? (int)std::min((double)e->table_scale * m_b, 2048.0) : 0;
-    e->csr_row_abs_max = m_b;
-    e->csr_sorted = sorted_b;
+    e->table_scale = b.table_scale;
+    e->table_m = b.table_m;
+    e->csr_row_abs_max = b.row_abs_max;
+    e->csr_sorted = b.sorted;
     e->consistent_dE = true;
-    e->row_j_abs_max = mj_b;
-    if (want_clf && clf_why.empty() && (acc_b != sga::CSR_ACC_F32_TABLE || e->table_m <= 0))
-        clf_why = "cached local fields over ragged CSR batches: the batch runs without an accept table (option \"force_csr_acc\")";
-    e->clf_csr_problem = want_clf && clf_why.empty();
-    e->clf_ragged_why = want_clf ? clf_why : std::string();
-    if (want_fx && !clf_why.empty()) {  // the int16 form does not take the batch: the fixed-point form
-        const int k = fx_k == INT32_MIN ? 0 : fx_k;
-        // D_i = 2^k sum_j J_ij s_j of any row of the batch must stay below 2^53: then the fp64 sums of the seed kernel, the
-        // int64 -> fp64 conversion of a proposal and the scaled entries of an accept are all exact (the one-model condition
-        // over the concatenation; mj is the fp32 rounding of an fp64 sum: < 1 ulp either way)
-        double bound = 0.0;
-        for (int m = 0; m < n_models; ++m) {
-            const double bm = std::ldexp((double)fx_mj[(size_t)m], k) * (1.0 + 0x1.0p-20);
-            bound = std::max(bound, bm);
-            if (fx_why.empty() && !(bm < 0x1.0p53)) {
-                char msg[256];
-                std::snprintf(msg, sizeof(msg), "cached local fields over ragged CSR batches (fixed point): model %d: fields wider "
-                              "than the bound: 2^k max_i sum_j |J_ij| is not below 2^53 at the batch-wide k = %d", m, k);
-                fx_why = msg;
-            }
-        }
-        if (fx_why.empty() && acc_b == sga::CSR_ACC_F64_CANON)
-            fx_why = "cached local fields over ragged CSR batches (fixed point): the batch runs the canonical fp64 summation order "
-                     "(option \"force_csr_acc\")";
-        if (fx_why.empty()) {
-            e->clf_csr_problem = true;
-            e->clf_fx_bits = bound < 0x1.0p31 ? 32 : 64;
-            e->clf_fx_k = k;
-            e->clf_ragged_why.clear();
-        } else {
-            e->clf_ragged_why = fx_why;
-        }
-    }
+    e->row_j_abs_max = b.row_j_abs_max;
+    e->clf_csr_problem = b.clf_problem;
+    e->clf_ragged_why = b.clf_why;
+    e->clf_fx_bits = b.fx_bits;
+    e->clf_fx_k = b.fx_k;
     // the plain layout: (column, value) interleaved, CSR_TAIL_PAD zeroed entries behind
     long long *src_ptr = nullptr;
     SGA_BATCH_CHK(hipMalloc(&src_ptr, sizeof(long long) * np1));
