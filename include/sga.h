@@ -80,7 +80,7 @@ typedef struct sga_engine sga_engine;
 int sga_create(int device, sga_engine **out);
 void sga_destroy(sga_engine *e);
 const char *sga_last_error(void);
-int sga_version(void);  /* 1300: options "ragged_field_cache" and "clf_fixed_point" together (fixed-point cached local fields for ragged CSR batches); 1200: sga_set_groups_csr (group couplings plus a stored sparse remainder); 1100: option "ragged_field_cache" (cached local fields for ragged CSR batches); 1000: sga_set_groups */
+int sga_version(void);  /* 1400: option "batch_fixed_point" (fixed-point cached local fields for many-model dense batches); 1300: options "ragged_field_cache" and "clf_fixed_point" together (fixed-point cached local fields for ragged CSR batches); 1200: sga_set_groups_csr (group couplings plus a stored sparse remainder); 1100: option "ragged_field_cache" (cached local fields for ragged CSR batches); 1000: sga_set_groups */
 /* Run on an existing HIP stream (e.g. torch.cuda.current_stream().cuda_stream); NULL = the
  * engine's own stream (default). */
 int sga_set_stream(sga_engine *e, void *hip_stream);
@@ -99,7 +99,15 @@ int sga_set_dense(sga_engine *e, const float *J, int64_t ldJ, const float *h, in
  * model's J integer valued and symmetric with a zero diagonal, every h in multiples of 1/2, the largest
  * sum_j |J_ij| + |h_i| of ANY model below 2^24.  Scale, field width (int16 | int32), accept table and max |J| are
  * batch-wide; each replica reads its own model's rows, and each model walks its one-model chain.  The fixed-point
- * form (option "clf_fixed_point"), bit-plane storage and row-shared windows stay one-model only. */
+ * form (option "clf_fixed_point"), bit-plane storage and row-shared windows stay one-model only -- the fixed-point form
+ * unless option "batch_fixed_point" = 1 is set too (version >= 1400, both set before this call): a batch the integer
+ * form does not take (real-valued J, an h off the half-integers) is then scanned as a whole for the fixed-point form.
+ * k is batch-wide -- the finest grid 2^-k any model's J needs (0 for integer J), so every 2^k J of every model is an
+ * integer --, the fields D = 2^k J_m s are int32 while 2^k max (sum_j |J_ij| + |h_i|) over ALL stacked rows < 2^31, else
+ * int64.  dot = fp32(2^-k D_i) is the one rounding of the exact row sum: every model walks its one-model chain,
+ * whatever k or width it would get alone.  Refused (SGA_ERR_UNSUPPORTED under SGA_FIELD_CACHE_ON, each naming "a dense
+ * batch: in every model"): f64-canonical J over the stack, an asymmetric J or a non-zero diagonal in any model, fields
+ * wider than int64.  A batch the integer form takes keeps it. */
 int sga_set_dense_batch(sga_engine *e, const float *J, int64_t ldJ, const float *h, int n,
                         int n_models, int storage);
 /* CSR couplings (both triangles present), rowptr[n+1], colidx[nnz], val[nnz], h[n]; host or
@@ -427,7 +435,11 @@ int sga_set_csr_storage(sga_engine *e, int storage);
  *     chain the one-model chain; fields seeded by one launch of exact integer sums, eight replicas per pass over
  *     a model's rows; "several accepts per round" needs each MODEL's matrix below 4 GiB, not the stack's;
  *     sga_explain_route / sga_describe name the batch ("models=M").  The fixed-point form over batches stays
- *     refused;
+ *     refused unless option "batch_fixed_point" = 1 is set beside "clf_fixed_point" = 1 (version >= 1400): then the
+ *     conditions of the one-model fixed-point form over all stacked rows, one k and one width (int32 | int64) for the
+ *     batch, fields seeded by one launch of exact fp64 sums (eight replicas of one model per pass), any single-site
+ *     rule, site mode and arithmetic, one accept per round; AUTO routes each replica by its own acceptance against
+ *     the one-model dense fixed-point break-even (not measured for batches);
  *   ragged CSR batches (sga_set_csr_batch; version >= 1100) under option "ragged_field_cache" = 1: the CSR
  *     conditions below in every model, production sweeps, one launch under AUTO decided by the hottest replica.
  *     With the option at 0 (default) ON is refused (SGA_ERR_UNSUPPORTED) and AUTO streams.  With option
@@ -527,6 +539,14 @@ int sga_set_field_cache(sga_engine *e, int mode);
  *                           as on a one-model CSR engine.  0: ON is refused, AUTO streams.  Same chain.  Together with
  *                           option "clf_fixed_point" = 1 (version >= 1300): a batch the int16 form does not take runs
  *                           the fixed-point form over the batch (int32 | int64 fields at one batch-wide k)  [set]
+ *   "batch_fixed_point"     0 (default) | 1   many-model dense batches (sga_set_dense_batch) under option "clf_fixed_point"
+ *                           = 1, both set before the couplings: a batch the integer cached-field form does not take runs
+ *                           the dense fixed-point form (csrc/sweep_clf_fx.hip, batch build) -- one k (the finest grid any
+ *                           model's J needs) and one field width (int32 | int64) for the batch, each replica on its own
+ *                           model's rows and h, every model on its one-model chain.  0, or "clf_fixed_point" = 0: as
+ *                           before -- ON over such a batch is refused ("not built for dense batches"), AUTO runs the
+ *                           row kernels.  Bit-plane storage, row-shared windows and "clf_batched" do not apply to
+ *                           batches in fixed point                                         [set; SGA_BATCH_FIXED_POINT]
  * sga_option_name enumerates the keys (index 0, 1, ... until SGA_ERR_INVALID).
  * (No reference counterpart: the reference has one code path, core/spin_dynamics.py:61-152.) */
 int sga_set_option(sga_engine *e, const char *key, int64_t value);

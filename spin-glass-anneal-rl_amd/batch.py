@@ -30,6 +30,15 @@ of 2^15 or more, duplicate entries, h off the half-integers) is refused under "o
 int16 form does not take (real-valued J such as distances, h off the half-integers, integer fields of 2^15 or more)
 then runs the fixed-point form on the ragged engine -- D = 2^k J s as exact int32 | int64 at one batch-wide k; the
 same chain once more.  Without `ragged_field_cache` the flag does nothing on the ragged path.
+
+`BatchConfig.stacked_fixed_point=True` (build-specific, default False) together with
+`annealer_config.fixed_point_fields=True` sets the engine options "clf_fixed_point" and "batch_fixed_point" before the
+couplings of a STACKED batch: `field_cache` "on" / "auto" then also act on stacked batches the integer form does not
+take -- real-valued J (half- and quarter-valued physical-convention encodings, binary-grid couplings, distances) or an
+h off the half-integers.  The fields are D = 2^k J_m s as exact int32 | int64 at one batch-wide k, each replica on its
+own model's rows; the same chain, so every result field but `total_time` equals the "off" result.  A batch that does
+not qualify (f64-canonical J, an asymmetric J or a non-zero diagonal in some model) fails under "on" and runs the row
+kernels under "auto".  With either flag unset the stacked path is what it was.
 """
 import time
 from dataclasses import dataclass
@@ -59,6 +68,7 @@ class BatchConfig:
     checkpoint_interval: int = 100
     replicas_per_model: int = 1  # build-specific: independent restarts per model, best is kept
     ragged_field_cache: bool = False  # build-specific: sparse chunks serve field_cache "on" / "auto" on the ragged engine
+    stacked_fixed_point: bool = False  # build-specific: stacked real-valued batches serve field_cache "on" / "auto" (fixed point)
 
     def __post_init__(self):
         if self.batch_size <= 0:
@@ -69,6 +79,8 @@ class BatchConfig:
             raise ValueError("Memory optimization level must be 0, 1, or 2")
         if self.replicas_per_model <= 0:
             raise ValueError("replicas_per_model must be positive")
+        if not isinstance(self.stacked_fixed_point, bool):
+            raise ValueError("stacked_fixed_point must be a bool")
 
 
 class BatchProcessor:
@@ -145,7 +157,13 @@ class BatchProcessor:
         J = np.stack([m.dense_couplings().detach().cpu().numpy().astype(np.float32) for m in models])
         h = np.stack([m.external_fields.detach().cpu().numpy().astype(np.float32) for m in models])
         s0 = np.stack([m.spins_int8() for m in models])  # [M, n]
-        return self._run(models, lambda eng: eng.set_dense_batch(J, h, storage=self.annealer_config.coupling_storage), s0)
+        def set_problem(eng):
+            if self.batch_config.stacked_fixed_point and self.annealer_config.fixed_point_fields:
+                eng.set_option("clf_fixed_point", 1)  # ([set] options: before the couplings)
+                eng.set_option("batch_fixed_point", 1)
+            eng.set_dense_batch(J, h, storage=self.annealer_config.coupling_storage)
+
+        return self._run(models, set_problem, s0)
 
     # ------------------------------------------------------------------ one ragged run (sparse models, any sizes)
     def _anneal_ragged(self, models: List[IsingModel]) -> Optional[List[AnnealingResult]]:

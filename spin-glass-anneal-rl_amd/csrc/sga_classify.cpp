@@ -59,16 +59,23 @@ FxVerdict fixed_point_verdict(const FxQuery &q, const std::function<bool()> &dia
     if (q.batch)
         v.why = "cached local fields (fixed point): not built for dense batches (one model only)";
     else if (q.canonical)
-        v.why = "cached local fields (fixed point): the couplings need the canonical fp64 summation order "
-                "(acc class f64-canonical: their binary places span more than 53 bits, so no exact fixed "
-                "point holds a row sum)";
+        v.why = q.stacked ? "cached local fields (fixed point): the couplings need the canonical fp64 summation order "
+                            "(acc class f64-canonical: their binary places span more than 53 bits over the stack, so no "
+                            "exact fixed point at one k holds a row sum; a dense batch: in every model)"
+                          : "cached local fields (fixed point): the couplings need the canonical fp64 summation order "
+                            "(acc class f64-canonical: their binary places span more than 53 bits, so no exact fixed "
+                            "point holds a row sum)";
     else if (q.unsorted)
         v.why = "cached local fields (fixed point): CSR rows must be strictly sorted by column (no duplicate entries)";
     else if (!q.consistent_dE)
-        v.why = diagonal() ? "cached local fields (fixed point): J must have a zero diagonal"
-                           : "cached local fields (fixed point): J must be symmetric";
+        v.why = diagonal() ? (q.stacked ? "cached local fields (fixed point): J must have a zero diagonal (a dense batch: in every model)"
+                                        : "cached local fields (fixed point): J must have a zero diagonal")
+                           : (q.stacked ? "cached local fields (fixed point): J must be symmetric (a dense batch: in every model)"
+                                        : "cached local fields (fixed point): J must be symmetric");
     else if (q.n_too_large || !(bound < FX_LIMIT_ONE))
-        v.why = "cached local fields (fixed point): fields wider than int64";
+        v.why = q.stacked ? "cached local fields (fixed point): fields wider than int64 (a dense batch: in every model, at the "
+                            "batch-wide k)"
+                          : "cached local fields (fixed point): fields wider than int64";
     else
         v.bits = fx_bits(bound), v.k = k;
     return v;
@@ -233,12 +240,18 @@ const char *dense_clf_why(const DenseClass &c, const std::function<bool()> &diag
 }
 
 // (sweep_clf_fx.hip; bit-plane problems are served from their int8 rows)
-FxVerdict dense_fixed_point(const DenseClass &c, int n_models, const std::function<bool()> &diagonal) {
+// Many-model batches (batch_allowed: option "batch_fixed_point"): the one-model verdict over the STACKED scan.  The span
+// is over every model's J, so k is the finest grid any model needs and every model's 2^k J is an integer; the class
+// (fp32-exact / f64-exact) and the field bound hold over all stacked rows, so every row sum of every model is exact
+// and dot = fp32(2^-k D_i) is the one rounding of that exact sum -- the value the row kernels form for that model
+// alone, whatever class, k or width the model would get on its own.  Every model walks its one-model chain.
+FxVerdict dense_fixed_point(const DenseClass &c, int n_models, const std::function<bool()> &diagonal, bool batch_allowed) {
     FxQuery q;
     q.span = c.span;
     q.clamp_k = true;              // kept as found: dense k is clamped at 0 (CSR: not)
     q.field_max = c.row_abs_max;   // kept as found: max_i (sum_j |J_ij| + |h_i|) bounds max_i sum_j |J_ij| from above (CSR: without h)
-    q.batch = n_models != 1;
+    q.batch = n_models != 1 && !batch_allowed;
+    q.stacked = n_models != 1 && batch_allowed;
     q.canonical = c.acc_canon;
     q.consistent_dE = c.consistent_dE;
     return fixed_point_verdict(q, diagonal);

@@ -35,6 +35,7 @@ struct FxQuery {
     bool clamp_k = false;       // k >= 0
     double field_max = 0.0;     // the maximum that bounds the fields
     bool batch = false, canonical = false, unsorted = false, consistent_dE = true, n_too_large = false;
+    bool stacked = false;       // a dense batch scanned as a whole: the reasons name what SOME model does
 };
 double fx_bound(double field_max, int k);  // 2^k field_max, the fp32 rounding of field_max allowed for
 inline int fx_bits(double bound) { return bound < 0x1.0p31 ? 32 : 64; }
@@ -91,7 +92,8 @@ struct DenseClass {
 DenseClass classify_dense(const int hflags[8], int n, int n_models, int storage, bool force_dense_canonical);
 // a problem with !clf_problem: which condition of the integer cached-field form failed, and the fixed-point verdict
 const char *dense_clf_why(const DenseClass &c, const std::function<bool()> &diagonal);
-FxVerdict dense_fixed_point(const DenseClass &c, int n_models, const std::function<bool()> &diagonal);
+// batch_allowed (option "batch_fixed_point"): a many-model batch gets the one-model verdict over its stacked scan
+FxVerdict dense_fixed_point(const DenseClass &c, int n_models, const std::function<bool()> &diagonal, bool batch_allowed = false);
 
 // ---- implicit couplings --------------------------------------------------------------------------------------------------
 struct TspClass {

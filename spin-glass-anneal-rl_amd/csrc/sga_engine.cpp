@@ -254,6 +254,13 @@ int ensure_fields(sga_engine *e) {
         e->fields = nullptr;
         return fail(SGA_ERR_MEMORY, "no memory for the resident local fields of the cached-field sweep");
     }
+    if (e->clf_fx_bits && e->n_models > 1) {  // option "batch_fixed_point": each replica over its own model's rows
+        HIPCHK(sga::launch_dense_fields_seed_fx_batch(e->J_packed, e->want_i8, e->ldj, (long long)e->n * e->ldj, e->spins,
+                                                      e->sstride, e->n, e->R, (uint32_t)e->replica0, e->Rg / e->n_models,
+                                                      e->fields, e->ldf, e->clf_fx_bits, e->clf_fx_k, e->stream));
+        e->fields_valid = true;
+        return SGA_OK;
+    }
     if (e->clf_fx_bits) {  // exact per-replica sums (the matrix-core pass rounds real-valued row sums to fp32)
         HIPCHK(sga::launch_dense_fields_seed_fx(e->J_packed, e->want_i8, e->ldj, e->spins, e->sstride, e->n, e->R, e->fields,
                                                 e->ldf, e->clf_fx_bits, e->clf_fx_k, e->stream));
@@ -392,7 +399,7 @@ int ensure_packed(sga_engine *e) {
 extern "C" {
 
 const char *sga_last_error(void) { return g_last_error.c_str(); }
-int sga_version(void) { return 1300; }  // + options "ragged_field_cache" and "clf_fixed_point" together: fixed-point cached local fields for ragged CSR batches (sweep_clf_csr.hip)  // 1200: + sga_set_groups_csr (group couplings plus a stored sparse remainder, sweep_groups.hip)  // 1100: + option "ragged_field_cache" (cached local fields for ragged CSR batches, sweep_clf_csr.hip)  // 1000: + sga_set_groups (implicit cardinality-group couplings, sweep_groups.hip)  // 900: + cached local fields for many-model dense batches (sga_set_dense_batch)  // 800: + option "clf_fixed_point" over dense couplings (sweep_clf_fx.hip)  // 700: + option "clf_fixed_point" (cached fields of real-valued CSR couplings)  // 600: + sga_set_csr_batch / sga_get_batch_model (ragged CSR batches)  // round 5: + sga_explain_route / sga_get_route_query, sga_get_last_kernel, sga_get_autotune_table, ladder-local sga_exchange
+int sga_version(void) { return 1400; }  // + option "batch_fixed_point": fixed-point cached local fields for many-model dense batches (sweep_clf_fx.hip, MODELS)  // 1300: + options "ragged_field_cache" and "clf_fixed_point" together: fixed-point cached local fields for ragged CSR batches (sweep_clf_csr.hip)  // 1200: + sga_set_groups_csr (group couplings plus a stored sparse remainder, sweep_groups.hip)  // 1100: + option "ragged_field_cache" (cached local fields for ragged CSR batches, sweep_clf_csr.hip)  // 1000: + sga_set_groups (implicit cardinality-group couplings, sweep_groups.hip)  // 900: + cached local fields for many-model dense batches (sga_set_dense_batch)  // 800: + option "clf_fixed_point" over dense couplings (sweep_clf_fx.hip)  // 700: + option "clf_fixed_point" (cached fields of real-valued CSR couplings)  // 600: + sga_set_csr_batch / sga_get_batch_model (ragged CSR batches)  // round 5: + sga_explain_route / sga_get_route_query, sga_get_last_kernel, sga_get_autotune_table, ladder-local sga_exchange
 
 int sga_create(int device, sga_engine **out) {
     if (!out) return fail(SGA_ERR_INVALID, "out is NULL");
@@ -1019,7 +1026,7 @@ hipError_t launch_dense_rows(const sga_engine *e, sga::SweepArgs a, hipStream_t 
 
 hipError_t launch_cached(const sga_engine *e, const SweepPlan &p, const sga::SweepArgs &ac, hipStream_t st) {
     if (p.cached == Cached::CSR) return sga::launch_sweep_clf_csr(ac, p.cw, st);
-    if (p.cached == Cached::FIXED_POINT) return sga::launch_sweep_clf_fx(ac, e->want_i8, p.cw, st);
+    if (p.cached == Cached::FIXED_POINT) return sga::launch_sweep_clf_fx(ac, e->want_i8, p.cw, st, e->n_models);
     if (p.cached == Cached::INTEGER_BATCHED) return sga::launch_sweep_clfb(ac, e->want_i8, p.cw, st);
     return sga::launch_sweep_clf(ac, e->want_i8, p.cw, st);
 }

@@ -226,7 +226,14 @@ hipError_t launch_csr_fields_seed_ragged_fx(const long long *rowptr, const int2 
                                             long long ldf, int field_bits, int k, hipStream_t st);
 // ... and of dense problems with real-valued J (option "clf_fixed_point", sweep_clf_fx.hip): D = 2^k J s as exact int32 |
 // int64 (a.field_bits), k = a.field_scale, no accept table; fp32 rows, or int8 rows (integer J, k = 0)
-hipError_t launch_sweep_clf_fx(const SweepArgs &a, bool j_is_i8, int waves, hipStream_t st);
+// (a.reps_per_model > 0: the build for many-model batches, option "batch_fixed_point" -- n_models names the batch in the
+//  kernel note)
+hipError_t launch_sweep_clf_fx(const SweepArgs &a, bool j_is_i8, int waves, hipStream_t st, int n_models = 1);
+// ... the seed of a many-model batch: local replica r over the rows of model (replica0 + r) / reps_per_model, exact fp64
+// sums at the batch-wide k, one launch whatever the number of models
+hipError_t launch_dense_fields_seed_fx_batch(const void *J, bool j_is_i8, long long ldj, long long model_stride_j,
+                                             const int8_t *spins, int sstride, int n, int R, unsigned int replica0,
+                                             int reps_per_model, void *D, long long ldf, int field_bits, int k, hipStream_t st);
 bool sweep_clf_fx_applies(const SweepArgs &a, bool j_is_i8);
 size_t sweep_clf_fx_lds_bytes(long long ldf, int field_bits, int sstride);
 // D[r][i] = 2^k sum_j J_ij s_rj as int32 | int64 (field_bits), exact; J dense [n][ldj] fp32 | int8

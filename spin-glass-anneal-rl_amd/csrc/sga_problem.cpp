@@ -475,7 +475,9 @@ int sga_set_dense_batch(sga_engine *e, const float *J, int64_t ldJ, const float 
             return diag == 1;
         };
         if (e->opt[OPT_CLF_FIXED_POINT] == 1) {
-            const sga_classify::FxVerdict v = sga_classify::dense_fixed_point(c, n_models, diagonal);
+            // (option "batch_fixed_point": a many-model batch gets the verdict over its stacked scan -- one k, one width)
+            const sga_classify::FxVerdict v =
+                sga_classify::dense_fixed_point(c, n_models, diagonal, e->opt[OPT_BATCH_FIXED_POINT] == 1);
             if (diag_rc != SGA_OK) return diag_rc;
             e->clf_fx_why = v.why;
             e->clf_fx_bits = v.bits;

@@ -418,7 +418,9 @@ const char *clf_refusal(const Query &q) {
     }
     if (!q.clf_ok && q.opt[OPT_CLF_FIXED_POINT] == 1 && q.clf_bits == 0) {
         // (the set-time scan refused the fixed-point form; the engine reports its own, more precise reason)
-        if (q.n_models > 1) return "cached local fields (fixed point): not built for dense batches (one model only)";
+        // (many-model batches: only under option "batch_fixed_point", set with "clf_fixed_point" before sga_set_dense_batch)
+        if (q.n_models > 1 && q.opt[OPT_BATCH_FIXED_POINT] == 0)
+            return "cached local fields (fixed point): not built for dense batches (one model only)";
         if (q.acc == 2)
             return "cached local fields (fixed point): acc class f64-canonical -- no exact fixed point holds a row sum";
         return "cached local fields (fixed point): need symmetric J with a zero diagonal and fields within int64";
@@ -457,6 +459,8 @@ static double fixed_point_theta(const Query &q, double t_upd) {
 // (n = 10^4: 1.5) = 1.3 -- a replica at n = 10^4 is never given to the row kernels (theta 1.15; every measured line,
 // 0.2 % to 47 % mean acceptance, is faster cached: 1.1 - 1.3 ms against 54 ms per sweep at 1 %).  int64: not measured at
 // size; 1.5 by the field bytes an accept moves (estimate).
+// Many-model batches (option "batch_fixed_point"): the same two figures -- NOT measured for batches as a break-even (a
+// batch has few replicas per model and a mostly empty chip; profiles/batch_fixed_point.json reports whole runs).
 constexpr double DENSE_FX_T_ACC32 = 1.3, DENSE_FX_T_ACC64 = 1.5;
 static double dense_fixed_point_theta(const Query &q, double t_upd) {
     const double t_acc = q.clf_bits == 64 ? DENSE_FX_T_ACC64 : DENSE_FX_T_ACC32;
@@ -696,6 +700,12 @@ std::string explain(const Query &q0) {
                               q.n_models);
             else if (q.kind == SGA_ROUTE_CSR && q.opt[OPT_CLF_FIXED_POINT] == 1 && (q.clf_bits == 32 || q.clf_bits == 64))
                 std::snprintf(buf, sizeof(buf), " cached=on(waves=%d fields=int%d fixed-point)", clf_csr_waves(q), q.clf_bits);
+            else if (dense_fixed_point(q) && q.n_models > 1 && q.opt[OPT_BATCH_FIXED_POINT] == 1)
+                // a many-model dense batch under option "batch_fixed_point": batch-wide k and field width, each replica on
+                // its model's rows (sweep_clf_fx.hip, MODELS)
+                std::snprintf(buf, sizeof(buf), " cached=on(waves=%d fields=int%d fixed-point models=%d)",
+                              sga::sweep_clf_waves(dense_ldj(q), is_i8(q), std::max(q.R_local, 1), q.cus, (int)q.opt[OPT_CLF_WAVES]),
+                              q.clf_bits, q.n_models);
             else if (dense_fixed_point(q))
                 std::snprintf(buf, sizeof(buf), " cached=on(waves=%d fields=int%d fixed-point)",
                               sga::sweep_clf_waves(dense_ldj(q), is_i8(q), std::max(q.R_local, 1), q.cus, (int)q.opt[OPT_CLF_WAVES]),

@@ -475,6 +475,9 @@ int sga_describe(sga_engine *e, char *buf, int buflen) {
                           " sweep=auto(cached local fields, int%d fixed-point, k=%d, per replica by its own acceptance; now: %d of "
                           "%d replica(s) cached, the rest one row per proposal)",
                           e->clf_fx_bits, e->clf_fx_k, e->routing.unavailable ? 0 : e->routing.n_cached, e->R);
+        if (e->n_models > 1)  // option "batch_fixed_point": the batch, its width and its one k
+            std::snprintf(tmp + std::strlen(tmp), sizeof(tmp) - std::strlen(tmp), " cached-batch(models=%d fields=int%d k=%d)",
+                          e->n_models, e->clf_fx_bits, e->clf_fx_k);
     } else if (clf_active(e)) {
         if (e->field_cache == SGA_FIELD_CACHE_ON)
             std::snprintf(tmp + std::strlen(tmp), sizeof(tmp) - std::strlen(tmp),

@@ -133,10 +133,127 @@ hipError_t launch_dense_fields_seed_fx(const void *J, bool j_is_i8, long long ld
     return field_bits == 64 ? go(float{}, (long long)0) : go(float{}, int{});
 }
 
+// ---- seeding a many-model batch (sga_set_dense_batch under option "batch_fixed_point") -------------------------------
+// D[r][i] = 2^k sum_j J_m[i][j] s_rj for every local replica r, m = (replica0 + r) / reps_per_model, in ONE launch whatever
+// the number of models, grouped as dense_fields_seed_batch_kernel (sweep_clf.hip) groups them: a workgroup takes a GROUP
+// of up to eight replicas of one model (groups never straddle a model; a shard's cut inside a group leaves the other
+// side's replicas out) and a slice of that model's rows.  The sums are those of dense_fields_seed_fx_kernel: k is
+// batch-wide and the class bound holds over all stacked rows, so in EVERY model each term and partial sum is a multiple
+// of 2^-k below 2^(53 - k) -- fp64 sums exact in any order, and so is their scaling by 2^k.  A lane holds 16 bytes of a
+// row per step (rows are padded with zeros to ldj, a multiple of 16 bytes; the spin bits past n are zero).
+template <typename JT, typename FT>
+__global__ void __launch_bounds__(256) dense_fields_seed_fx_batch_kernel(const JT *__restrict__ J, long long ldj, long long model_stride_j,
+                                                                         const int8_t *__restrict__ spins, int sstride, int n, int R,
+                                                                         unsigned int replica0, int reps_per_model, int group0,
+                                                                         int slices, FT *__restrict__ D, long long ldf, int kx) {
+    constexpr int EPL = 16 / (int)sizeof(JT);  // couplings per lane and step: 16 | 4
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    unsigned int *sb = reinterpret_cast<unsigned int *>(smem);  // [8][words]: bit = spin down; zero past n
+    const int words = (int)((ldj + 31) / 32);
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int gpm = (reps_per_model + CLFX_SEED_REPS - 1) / CLFX_SEED_REPS;  // groups per model
+    const int G = group0 + (int)blockIdx.x, model = G / gpm;                // (workgroup-uniform: no divergence on the model)
+    const long long g0 = (long long)model * reps_per_model + (long long)(G - model * gpm) * CLFX_SEED_REPS;  // first global replica
+    const int count = (int)min((long long)CLFX_SEED_REPS, (long long)(model + 1) * reps_per_model - g0);
+    // local replica of slot `rep`, -1: not in this engine's shard
+    auto local = [&](int rep) -> long long {
+        const long long r = g0 + rep - (long long)replica0;
+        return (rep < count && r >= 0 && r < R) ? r : -1;
+    };
+    for (int q = tid; q < CLFX_SEED_REPS * words; q += 256) {
+        const int rep = q / words, wd = q % words;
+        const long long r = local(rep);
+        unsigned int b = 0;
+        if (r >= 0)
+            for (int t = 0; t < 32; ++t) {
+                const int i = 32 * wd + t;
+                if (i < n && spins[r * sstride + i] < 0) b |= 1u << t;
+            }
+        sb[q] = b;
+    }
+    __syncthreads();
+    const JT *Jm = J + (long long)model * model_stride_j;
+    const int per = (n + slices - 1) / slices;
+    const int i0 = blockIdx.y * per, i1 = min(n, i0 + per);
+    using vec_t = typename std::conditional<sizeof(JT) == 4, float4, int4>::type;
+    for (int i = i0 + w; i < i1; i += 4) {
+        const JT *row = Jm + (long long)i * ldj;
+        double acc[CLFX_SEED_REPS];
+#pragma unroll
+        for (int rep = 0; rep < CLFX_SEED_REPS; ++rep) acc[rep] = 0.0;
+        for (long long j0 = (long long)lane * EPL; j0 < ldj; j0 += 64 * EPL) {
+            const int wd = (int)(j0 >> 5), sh = (int)(j0 & 31);
+            const vec_t v = *reinterpret_cast<const vec_t *>(row + j0);
+            JT e[EPL];
+            __builtin_memcpy(e, &v, sizeof(e));
+            double x[EPL];
+#pragma unroll
+            for (int d = 0; d < EPL; ++d) x[d] = (double)e[d];
+#pragma unroll
+            for (int rep = 0; rep < CLFX_SEED_REPS; ++rep) {
+                if (rep >= count) break;  // wave-uniform
+                const unsigned int dn = sb[rep * words + wd] >> sh;
+#pragma unroll
+                for (int d = 0; d < EPL; ++d) acc[rep] += ((dn >> d) & 1u) ? -x[d] : x[d];
+            }
+        }
+#pragma unroll
+        for (int rep = 0; rep < CLFX_SEED_REPS; ++rep) {
+            if (rep >= count) break;
+            const double tot = wave_sum(acc[rep]);
+            const long long r = local(rep);
+            if (lane == 0 && r >= 0) D[r * ldf + i] = (FT)(long long)ldexp(tot, kx);
+        }
+    }
+    // (the padding [n, ldf) of a field row: zero, as the one-model seed leaves it)
+    if (blockIdx.y == 0)
+        for (int q = tid; q < CLFX_SEED_REPS * (int)(ldf - n); q += 256) {
+            const int rep = q / (int)(ldf - n), i = n + q % (int)(ldf - n);
+            const long long r = local(rep);
+            if (r >= 0) D[r * ldf + i] = (FT)0;
+        }
+}
+
+hipError_t launch_dense_fields_seed_fx_batch(const void *J, bool j_is_i8, long long ldj, long long model_stride_j,
+                                             const int8_t *spins, int sstride, int n, int R, unsigned int replica0,
+                                             int reps_per_model, void *D, long long ldf, int field_bits, int k, hipStream_t st) {
+    const size_t lds = (size_t)CLFX_SEED_REPS * (size_t)((ldj + 31) / 32) * 4;
+    if (lds > 160 * 1024 || (field_bits != 32 && field_bits != 64) || ldf < n || ldj < n || sstride < n || R <= 0 ||
+        reps_per_model <= 0 || (ldj * (j_is_i8 ? 1 : 4)) % 16 != 0 || model_stride_j < (long long)n * ldj || (j_is_i8 && k != 0))
+        return hipErrorInvalidValue;
+    // global groups [group0, group1] hold the local replicas [replica0, replica0 + R)
+    const int gpm = (reps_per_model + CLFX_SEED_REPS - 1) / CLFX_SEED_REPS;
+    auto group_of = [&](long long g) -> long long {
+        const long long m = g / reps_per_model;
+        return m * gpm + (g - m * reps_per_model) / CLFX_SEED_REPS;
+    };
+    const long long group0 = group_of((long long)replica0), group1 = group_of((long long)replica0 + R - 1);
+    if (group1 >= (1ll << 30)) return hipErrorInvalidValue;
+    const int blocks = (int)(group1 - group0 + 1);
+    const int slices = std::max(1, std::min({64, 2048 / blocks, n}));
+    auto go = [&](auto jt, auto ft) -> hipError_t {
+        using JT = decltype(jt);
+        using FT = decltype(ft);
+        auto kern = dense_fields_seed_fx_batch_kernel<JT, FT>;
+        hipError_t e = ensure_lds_limit(reinterpret_cast<const void *>(kern), lds);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(kern, dim3(blocks, slices), dim3(256), lds, st, static_cast<const JT *>(J), ldj, model_stride_j, spins,
+                           sstride, n, R, replica0, reps_per_model, (int)group0, slices, static_cast<FT *>(D), ldf, k);
+        return hipGetLastError();
+    };
+    if (j_is_i8) return field_bits == 64 ? go(int8_t{}, (long long)0) : go(int8_t{}, int{});
+    return field_bits == 64 ? go(float{}, (long long)0) : go(float{}, int{});
+}
+
 // ---- the sweep ------------------------------------------------------------------------------------------------
 // JT: the stored row (float | int8_t), FT: the field (int | long long), BATCH: row chunks a wave requests together.
 // a.field_scale = k, a.fields = D [R][ldf] FT.
-template <typename JT, typename FT, int BATCH>
+// MODELS: the build for many-model batches (sga_set_dense_batch under option "batch_fixed_point"): the
+// replica's model (replica0 + r) / reps_per_model is resolved once, wave-uniform, and gives the base of its rows and of
+// its h -- every row base stays a scalar; offsets inside a row and a model, the LDS layout, windows, traces and best
+// tracking are those of the one-model launch.  A template flag, not a run-time test: the one-model instantiations hold
+// no trace of it (their code is the code they had before the flag).
+template <typename JT, typename FT, int BATCH, bool MODELS>
 __global__ void __launch_bounds__(64 * CLF_MAX_WAVES) sweep_clf_fx_kernel(const SweepArgs a) {
     constexpr int EPL = 16 / (int)sizeof(JT), EPC = 64 * EPL;  // elements per lane / per 1-KiB chunk
     constexpr int FB = (int)sizeof(FT);
@@ -162,6 +279,12 @@ __global__ void __launch_bounds__(64 * CLF_MAX_WAVES) sweep_clf_fx_kernel(const 
     __syncthreads();
 
     const JT *Jbase = reinterpret_cast<const JT *>(a.J);
+    const float *hbase = a.h;
+    if constexpr (MODELS) {
+        const int model = __builtin_amdgcn_readfirstlane((int)((a.replica0 + (uint32_t)r) / (uint32_t)a.reps_per_model));
+        Jbase += (long long)model * a.model_stride_j;
+        hbase += (long long)model * n;
+    }
     const int n_chunks = (int)((a.ldj + EPC - 1) / EPC);
     double E = a.energy[r], bestE = a.best_energy[r];
     unsigned long long nacc = 0;
@@ -224,7 +347,7 @@ __global__ void __launch_bounds__(64 * CLF_MAX_WAVES) sweep_clf_fx_kernel(const 
             const UpdatePair pr = fetch_pair<false>(a, r, k, tA >> 1, vA, n);
             const int sA = pr.sA, sB = pr.sB;
             const float uA = pr.uA, uB = pr.uB;
-            const float hA = a.h[sA], hB = a.h[sB];  // (static during the window)
+            const float hA = hbase[sA], hB = hbase[sB];  // (static during the window)
             int pos = 0;  // super-window positions below pos are decided
             RowRegs buf0 = row_request(0), buf1 = buf0;
             int held_pos = -1;  // super-window position whose row the buffer `held` of the coming round holds (-1: none)
@@ -339,30 +462,44 @@ __global__ void __launch_bounds__(64 * CLF_MAX_WAVES) sweep_clf_fx_kernel(const 
 bool sweep_clf_fx_applies(const SweepArgs &a, bool j_is_i8) {
     return a.rule != SGA_RULE_WOLFF && a.fields && (a.field_bits == 32 || a.field_bits == 64) && a.ldf >= a.ldj &&
            a.ldf % 128 == 0 && a.sstride % 32 == 0 && a.sstride >= a.n && a.table_m == 0 && !(j_is_i8 && a.field_scale != 0) &&
+           a.reps_per_model >= 0 && (a.reps_per_model == 0 || a.model_stride_j >= (long long)a.n * a.ldj) &&
            sweep_clf_fx_lds_bytes(a.ldf, a.field_bits, a.sstride) <= 160 * 1024;
 }
 
-template <typename JT, typename FT>
-static hipError_t launch_clf_fx(const SweepArgs &a, int waves, hipStream_t st) {
+template <typename JT, typename FT, bool MODELS>
+static hipError_t launch_clf_fx(const SweepArgs &a, int waves, int n_models, hipStream_t st) {
     const size_t lds = sweep_clf_fx_lds_bytes(a.ldf, a.field_bits, a.sstride);
     const int batch = sweep_clf_batch(a.ldj, sizeof(JT) == 1, waves);
     // (int8 rows: three chunks per request -- five hold 2 x 80 bytes of row per lane and spill)
     void (*kern)(const SweepArgs) =
-        (batch == 3 || sizeof(JT) == 1) ? sweep_clf_fx_kernel<JT, FT, 3> : sweep_clf_fx_kernel<JT, FT, CLF_BATCH_MAX>;
+        (batch == 3 || sizeof(JT) == 1) ? sweep_clf_fx_kernel<JT, FT, 3, MODELS> : sweep_clf_fx_kernel<JT, FT, CLF_BATCH_MAX, MODELS>;
     hipError_t e = ensure_lds_limit(reinterpret_cast<const void *>(kern), lds);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(kern, dim3(a.rep_list ? a.rep_count : a.R), dim3(64 * waves), lds, st, a);
-    note_sweep_kernel("sweep_clf_fx_kernel<%s, BATCH=%d> x %d wave(s) (int%d fixed-point fields in LDS, k=%d, row read on "
-                      "accept only)",
-                      sizeof(JT) == 4 ? "float" : "int8_t", batch, waves, a.field_bits, a.field_scale);
+    if constexpr (MODELS)
+        note_sweep_kernel("sweep_clf_fx_kernel<%s, BATCH=%d, MODELS> x %d wave(s) (int%d fixed-point fields in LDS, k=%d, "
+                          "models=%d, row read on accept only)",
+                          sizeof(JT) == 4 ? "float" : "int8_t", batch, waves, a.field_bits, a.field_scale, n_models);
+    else
+        note_sweep_kernel("sweep_clf_fx_kernel<%s, BATCH=%d> x %d wave(s) (int%d fixed-point fields in LDS, k=%d, row read on "
+                          "accept only)",
+                          sizeof(JT) == 4 ? "float" : "int8_t", batch, waves, a.field_bits, a.field_scale);
     return hipGetLastError();
 }
 
-hipError_t launch_sweep_clf_fx(const SweepArgs &a, bool j_is_i8, int waves, hipStream_t st) {
+hipError_t launch_sweep_clf_fx(const SweepArgs &a, bool j_is_i8, int waves, hipStream_t st, int n_models) {
     if (waves < 1 || waves > CLF_MAX_WAVES || !sweep_clf_fx_applies(a, j_is_i8)) return hipErrorInvalidValue;
+    if ((a.reps_per_model > 0) != (n_models > 1)) return hipErrorInvalidValue;
+    if (a.reps_per_model > 0) {  // a many-model batch: each replica on its own model's rows
+        if (j_is_i8)
+            return a.field_bits == 64 ? launch_clf_fx<int8_t, long long, true>(a, waves, n_models, st)
+                                      : launch_clf_fx<int8_t, int, true>(a, waves, n_models, st);
+        return a.field_bits == 64 ? launch_clf_fx<float, long long, true>(a, waves, n_models, st) : launch_clf_fx<float, int, true>(a, waves, n_models, st);
+    }
     if (j_is_i8)
-        return a.field_bits == 64 ? launch_clf_fx<int8_t, long long>(a, waves, st) : launch_clf_fx<int8_t, int>(a, waves, st);
-    return a.field_bits == 64 ? launch_clf_fx<float, long long>(a, waves, st) : launch_clf_fx<float, int>(a, waves, st);
+        return a.field_bits == 64 ? launch_clf_fx<int8_t, long long, false>(a, waves, n_models, st)
+                                  : launch_clf_fx<int8_t, int, false>(a, waves, n_models, st);
+    return a.field_bits == 64 ? launch_clf_fx<float, long long, false>(a, waves, n_models, st) : launch_clf_fx<float, int, false>(a, waves, n_models, st);
 }
 
 }  // namespace sga
