@@ -156,6 +156,7 @@ static bool ensure_row_shared(sga_engine *e, int W, hipStream_t st) {
     }
     if (he == hipSuccess) he = hipMalloc(&e->rs.cnt, sizeof(int) * nwin * groups * n);
     if (he == hipSuccess) he = hipMalloc(&e->rs.off, sizeof(int) * nwin * (n + 1));
+    if (he == hipSuccess) he = hipMalloc(&e->rs.tot, sizeof(int) * nwin * (size_t)sga::row_shared_scan_chunks(e->n));
     if (he == hipSuccess) he = hipMalloc(&e->rs.ent, sizeof(int) * R * n);
     if (he == hipSuccess) he = hipMalloc(&e->rs.base, sizeof(int) * R * (size_t)W);
     if (he == hipSuccess) he = hipMalloc(&e->rs.bits, sizeof(uint32_t) * R * (size_t)nw32);

@@ -244,6 +244,7 @@ struct sga_engine {
     void free_row_shared() {
         dev_free(rs.cnt);
         dev_free(rs.off);
+        dev_free(rs.tot);
         dev_free(rs.ent);
         dev_free(rs.base);
         dev_free(rs.bits);

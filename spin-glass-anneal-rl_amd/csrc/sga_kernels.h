@@ -409,6 +409,7 @@ struct RowSharedPlan {
     int *cnt;        // [n_windows][n_groups][n] proposals per (window, replica group, site); after the scan the first
                      // entry of each (the fill's cursors)
     int *off;        // [n_windows][n + 1] first entry of each (window, site)
+    int *tot;        // [n_windows][row_shared_scan_chunks(n)] proposals per (window, chunk of 1024 sites): the scan's carries
     int *ent;        // [R n] (replica << log_w | update in window), grouped by (window, site)
     int *base;       // [R][W] row sums against the window-start spins
     uint32_t *bits;  // [R][nw32] window-start spins, 1 = down (the layout of sweep_dense_rs.hip)
@@ -420,6 +421,7 @@ struct RowSharedPlan {
 };
 int row_shared_planes(int j_abs_max);  // 0: |J| beyond 255, the form does not apply
 inline int row_shared_nw32(int n) { return 8 * ((n + 255) / 256); }
+inline int row_shared_scan_chunks(int n) { return (n + 1023) / 1024; }  // workgroups of the scan per window
 // Resident planes exist where they take at most half the bytes of J: fp32 rows always ((planes + 1) / 32 of J), int8
 // rows for 1 and 3 magnitude planes; int8 rows with 8 planes keep the on-chip conversion.
 inline bool row_shared_resident(bool j_is_i8, int planes) { return planes > 0 && (!j_is_i8 || planes <= 3); }

@@ -9,10 +9,12 @@
 //     once per problem and stay in HBM (rs_planes_kernel, RowSharedPlan::jp): J does not change between two
 //     sga_set_* calls, and a plane row is (planes + 1) / 32 of the fp32 row.  Only int8 rows with 8 magnitude planes,
 //     whose planes would outweigh J, are converted on chip per window (rs_fields_kernel);
-//   * chain: one wave per replica holds the W pending fields, one per (lane, block).  Every remaining update is
-//     decided at once against the fields as they stand; the first accepted one is committed (energy, spin), and
-//     the later updates' fields are corrected by -2 J[i_a][i_t] s_a (J symmetric: read from row i_a) and their spins
-//     negated where the site repeats.  Then the next accepted one, and so on.
+//   * chain: one wave per replica holds the W pending fields, one per (lane, block of 64 updates), and walks the
+//     blocks in order.  A block first takes the corrections -2 J[i_a][i_t] s_a (J symmetric: read from row i_a) of
+//     every accept the window has made so far, its spins negated where the site repeats; then its 64 updates are
+//     decided at once against the fields as they stand, the couplings of the first few accepting ones to the block
+//     are fetched together, and accepts are committed (energy, spin, the block's fields) from registers for as long
+//     as the first accepting update is one of those fetched: a memory round trip per batch, not per accept.
 // J and h are integer valued with every partial sum below 2^24 (the look-ahead form's proof): the base sums and the
 // corrected fields are exactly the fp32 row sums of the one-update-at-a-time chain, the accept rule is the table
 // form's, and every decision, energy, spin and counter is bit-identical.  No field outlives its window.
@@ -83,39 +85,59 @@ __global__ void __launch_bounds__(256) rs_plan_kernel(const SweepArgs a, RowShar
     }
 }
 
-// one workgroup per window: exclusive scan of its counts in (site, group) order, entries of window w start at R w W
-__global__ void __launch_bounds__(1024) rs_scan_kernel(const SweepArgs a, RowSharedPlan p) {
-    __shared__ int sh[1024];
-    const int w = blockIdx.x, tid = threadIdx.x, n = a.n, G = p.n_groups;
+// The scan, per window: exclusive scan of its counts in (site, group) order, entries of window w start at R w W.  One
+// workgroup per (window, chunk of RS_SCAN_CHUNK sites).  totals: the chunk's count over every group -> tot[w][chunk].
+constexpr int RS_SCAN_CHUNK = 1024;
+
+__global__ void __launch_bounds__(RS_SCAN_CHUNK) rs_scan_totals_kernel(const SweepArgs a, RowSharedPlan p) {
+    __shared__ int part[RS_SCAN_CHUNK / 64];
+    const int c = blockIdx.x, w = blockIdx.y, tid = threadIdx.x, n = a.n, G = p.n_groups;
+    const int *cnt = p.cnt + (long long)w * G * n;
+    const int i = c * RS_SCAN_CHUNK + tid;
+    int v = 0;
+    if (i < n)
+        for (int g = 0; g < G; ++g) v += cnt[(long long)g * n + i];
+    v = wave_sum(v);
+    if ((tid & 63) == 0) part[tid >> 6] = v;
+    __syncthreads();
+    if (tid == 0) {
+        int t = 0;
+        for (int x = 0; x < RS_SCAN_CHUNK / 64; ++x) t += part[x];
+        p.tot[(long long)w * gridDim.x + c] = t;
+    }
+}
+
+// the scan proper: the chunk's carry is the prefix of the chunk totals (at most ceil(n / RS_SCAN_CHUNK) values)
+__global__ void __launch_bounds__(RS_SCAN_CHUNK) rs_scan_kernel(const SweepArgs a, RowSharedPlan p) {
+    __shared__ int sh[RS_SCAN_CHUNK];
+    const int c = blockIdx.x, w = blockIdx.y, tid = threadIdx.x, n = a.n, G = p.n_groups;
     int *cnt = p.cnt + (long long)w * G * n;
     int *off = p.off + (long long)w * (n + 1);
+    const int *tot = p.tot + (long long)w * gridDim.x;
     int carry = a.R * (w << p.log_w);
-    for (int i0 = 0; i0 < n; i0 += 1024) {
-        const int i = i0 + tid;
-        int v = 0;
-        if (i < n)
-            for (int g = 0; g < G; ++g) v += cnt[(long long)g * n + i];
-        sh[tid] = v;
+    for (int x = 0; x < c; ++x) carry += tot[x];
+    const int i = c * RS_SCAN_CHUNK + tid;
+    int v = 0;
+    if (i < n)
+        for (int g = 0; g < G; ++g) v += cnt[(long long)g * n + i];
+    sh[tid] = v;
+    __syncthreads();
+    for (int d = 1; d < RS_SCAN_CHUNK; d <<= 1) {  // inclusive Hillis-Steele scan
+        const int x = tid >= d ? sh[tid - d] : 0;
         __syncthreads();
-        for (int d = 1; d < 1024; d <<= 1) {  // inclusive Hillis-Steele scan
-            const int x = tid >= d ? sh[tid - d] : 0;
-            __syncthreads();
-            sh[tid] += x;
-            __syncthreads();
-        }
-        if (i < n) {
-            int run = carry + sh[tid] - v;
-            off[i] = run;
-            for (int g = 0; g < G; ++g) {
-                const int c = cnt[(long long)g * n + i];
-                cnt[(long long)g * n + i] = run;
-                run += c;
-            }
-        }
-        carry += sh[1023];
+        sh[tid] += x;
         __syncthreads();
     }
-    if (tid == 0) off[n] = carry;
+    if (i < n) {
+        int run = carry + sh[tid] - v;
+        off[i] = run;
+        for (int g = 0; g < G; ++g) {
+            const int cc = cnt[(long long)g * n + i];
+            cnt[(long long)g * n + i] = run;
+            run += cc;
+        }
+    }
+    if (c == (int)gridDim.x - 1 && tid == 0) off[n] = carry + sh[RS_SCAN_CHUNK - 1];
 }
 
 // int8 spins -> the bit layout above (1 = spin down); one workgroup per replica
@@ -297,107 +319,154 @@ __device__ __forceinline__ bool rs_accept(float fk, float u, double T, int table
     return (dE > T * 104.0) ? false : (u < expf_det((float)(-dE / T)));
 }
 
-// BITS: the correction J[i_a][i_t] is read from the resident planes of row i_a (one magnitude plane: two bits give
-// nonzero ? (sign ? -1 : +1) : 0, the value the row of J holds) -- a 40 KB fp32 row gathered at W sites costs about a
-// cache line per lane, its plane row is 2.5 KB in all.
+// J[sa][site], sa wave-uniform, in two steps, so that several gathers are in flight before the first is looked at:
+// rs_coupling_load issues the loads and rs_coupling decodes the float the row of J holds.  BITS: from the resident
+// planes of row sa (one magnitude plane: two bits give nonzero ? (sign ? -1 : +1) : 0), (w32, bit) = rs_bit_of(site)
+// -- a 40 KB fp32 row gathered at W sites costs about a cache line per lane, its plane row is 2.5 KB in all.
+template <typename JE, bool BITS>
+struct RsRaw {
+    typename std::conditional<BITS, uint2, JE>::type v;
+};
+// voff: the lane's byte offset in the row (BITS: of the 32-bit word of rs_bit_of(site) in a plane; else of J[.][site]),
+// unsigned and 32 bits wide beside a wave-uniform row address
+template <typename JE, bool BITS>
+__device__ __forceinline__ void rs_coupling_load(RsRaw<JE, BITS> &raw, const SweepArgs &a, const RowSharedPlan &p, int sa,
+                                                 unsigned int voff) {
+    if constexpr (BITS) {
+        const char *sgn = reinterpret_cast<const char *>(p.jp) + (long long)sa * (8ll * p.nw32);
+        const char *mag = sgn + 4ll * p.nw32;
+        raw.v = make_uint2(*reinterpret_cast<const uint32_t *>(sgn + voff), *reinterpret_cast<const uint32_t *>(mag + voff));
+    } else {
+        const char *row = reinterpret_cast<const char *>(a.J) + (long long)sa * a.ldj * (long long)sizeof(JE);
+        raw.v = *reinterpret_cast<const JE *>(row + voff);
+    }
+}
+template <typename JE, bool BITS>
+__device__ __forceinline__ float rs_coupling(const RsRaw<JE, BITS> &raw, unsigned int bit) {
+    if constexpr (BITS) return (raw.v.y & bit) ? ((raw.v.x & bit) ? -1.0f : 1.0f) : 0.0f;
+    else return (float)raw.v;
+}
+
+constexpr int RS_CHAIN_K = 4;  // candidates fetched per round (measured among 4, 8, 16)
+constexpr int RS_CHAIN_U = 8;  // earlier accepts applied to a block per wait
+
+// The blocks of the window (64 updates, one per lane) are walked in order.  A block is touched when it becomes
+// current: first it takes the corrections of every accept made so far in the window -- field -= 2 J[i_a][site] s_a
+// (J symmetric: read from row i_a), spin negated where the site repeats -- from the accept list in LDS, RS_CHAIN_U
+// independent gathers per wait.  Then it is decided in rounds: the first RS_CHAIN_K accepting lanes are candidates,
+// their couplings to the block are fetched together (a coupling depends on the two sites only, so it stays good
+// whatever is committed meanwhile), and accepts are committed from registers for as long as the first accepting
+// lane -- the chain's next accept: every lane before it rejects against fields that hold every earlier accept -- is
+// the next candidate.  A candidate that stopped accepting is skipped; a lane that was not fetched and accepts first
+// starts a new round.  One memory round trip per round, not per accept; the sums are integers below 2^24, so the
+// order of the corrections does not matter.
 template <typename JE, int NB, bool BITS>
 __global__ void __launch_bounds__(64) rs_chain_kernel(const SweepArgs a, RowSharedPlan p, int k, int win) {
+    constexpr int W = 64 * NB, K = RS_CHAIN_K, U = RS_CHAIN_U;
+    __shared__ uint32_t alist[W + U];  // the window's accepts in chain order: site | (spin before the flip < 0) << 31
     const int r = blockIdx.x, lane = threadIdx.x, n = a.n;
-    constexpr int W = 64 * NB;
     const int t0 = win * W, cnt = min(W, n - t0);
     const double T = a.sched ? a.sched[k * a.sched_ss + r * a.sched_rs] : a.rep_temp[r];
     int8_t *srow = a.spins + (long long)r * a.sstride;
-    const JE *J = reinterpret_cast<const JE *>(a.J);
     const int *base = p.base + (long long)r * W;
     int site[NB], s[NB];
     float f[NB], hh[NB], u[NB];
-    bool valid[NB], acc[NB];
 #pragma unroll
     for (int b = 0; b < NB; ++b) {
         const int tw = 64 * b + lane;
-        valid[b] = tw < cnt;
+        const bool valid = tw < cnt;
         uint32_t ub = 0;
         site[b] = 0;
-        if (valid[b]) rs_update(a, r, k, t0 + tw, site[b], ub);
+        if (valid) rs_update(a, r, k, t0 + tw, site[b], ub);
         u[b] = (float)ub * 0x1.0p-24f;
-        f[b] = valid[b] ? (float)base[tw] : 0.0f;
+        f[b] = valid ? (float)base[tw] : 0.0f;
         hh[b] = a.h[site[b]];
         s[b] = srow[site[b]];
     }
-#pragma unroll
-    for (int b = 0; b < NB; ++b) acc[b] = valid[b] && rs_accept((float)s[b] * (f[b] + hh[b]), u[b], T, a.table_m);
     double E = a.energy[r];
-    unsigned long long nacc = 0;
-    int from = 0;  // updates before `from` are decided
-    for (;;) {
-        // the first update at or after `from` that accepts against the fields as they stand: every one before it
-        // rejects (no accept lies between), so it is the chain's next accept
-        int first = -1;
+    int nA = 0;  // accepts of this window so far
+    const int nblk = (cnt + 63) >> 6;
+    for (int cb = 0; cb < nblk; ++cb) {
+        int csite = 0, cs = 0;
+        float cf = 0.0f, chh = 0.0f, cu = 0.0f;
 #pragma unroll
-        for (int b = 0; b < NB; ++b) {
-            if (first < 0 && 64 * (b + 1) > from) {
-                const unsigned long long m = ballot64(acc[b] && 64 * b + lane >= from);
-                if (m) first = 64 * b + (int)__builtin_ctzll(m);
-            }
-        }
-        if (first < 0) break;
-        const int fb = first >> 6, fl = first & 63;
-        int sa = 0, ss = 0;
-        float fa = 0.0f, ha = 0.0f;
-#pragma unroll
-        for (int b = 0; b < NB; ++b) {
-            if (b == fb) {
-                sa = read_lane(site[b], fl);
-                ss = read_lane(s[b], fl);
-                fa = read_lane(f[b], fl);
-                ha = read_lane(hh[b], fl);
-            }
-        }
-        const float fk = (float)ss * (fa + ha);
-        E += (double)(2.0f * fk);
-        ++nacc;
-        if (lane == 0) {
-            srow[sa] = (int8_t)(-ss);
-            int w32;
-            unsigned int bit;
-            rs_bit_of(sa, w32, bit);
-            atomicXor(&p.bits[(long long)r * p.nw32 + w32], bit);
-        }
-        // the later updates: field -= 2 J[sa][site] s_a (J symmetric), the spin negated where the site repeats
-        const float s2 = 2.0f * (float)ss;
-        float x[NB];
+        for (int b = 0; b < NB; ++b)
+            if (b == cb) csite = site[b], cs = s[b], cf = f[b], chh = hh[b], cu = u[b];
+        const bool cvalid = 64 * cb + lane < cnt;
+        unsigned int voff = (unsigned int)csite * (unsigned int)sizeof(JE), bit = 0;
         if constexpr (BITS) {
-            const uint32_t *sgn = reinterpret_cast<const uint32_t *>(p.jp) + (long long)sa * (2 * p.nw32);
-            const uint32_t *mag = sgn + p.nw32;
+            int w32;
+            rs_bit_of(csite, w32, bit);
+            voff = 4u * (unsigned int)w32;
+        }
+        // The fence of the accept list: the workgroup is one wave, so no barrier is executed, but neither the compiler
+        // nor the LDS queue may move the reads below ahead of lane 0's stores to alist (wave-uniform control flow).
+        __syncthreads();
+        for (int k0 = 0; k0 < nA; k0 += U) {
+            uint32_t e[U];
+            RsRaw<JE, BITS> x[U];
 #pragma unroll
-            for (int b = 0; b < NB; ++b) {
-                if (b >= fb) {
-                    int w32;
-                    unsigned int bit;
-                    rs_bit_of(site[b], w32, bit);
-                    const unsigned int sg = sgn[w32], mg = mag[w32];
-                    x[b] = (mg & bit) ? ((sg & bit) ? -1.0f : 1.0f) : 0.0f;
+            for (int j = 0; j < U; ++j) e[j] = alist[k0 + j];  // (past nA: in the array, unused)
+#pragma unroll
+            for (int j = 0; j < U; ++j) {
+                x[j] = RsRaw<JE, BITS>{};
+                if (k0 + j < nA) {  // wave-uniform, here and below
+                    e[j] = (uint32_t)__builtin_amdgcn_readfirstlane((int)e[j]);
+                    rs_coupling_load<JE, BITS>(x[j], a, p, (int)(e[j] & 0x7fffffffu), voff);
                 }
             }
-        } else {
-            const JE *rowa = J + (long long)sa * a.ldj;
 #pragma unroll
-            for (int b = 0; b < NB; ++b)
-                if (b >= fb) x[b] = (float)rowa[site[b]];
-        }
-#pragma unroll
-        for (int b = 0; b < NB; ++b) {
-            if (b >= fb) {
-                f[b] -= x[b] * s2;
-                if (site[b] == sa) s[b] = -s[b];
-                acc[b] = valid[b] && rs_accept((float)s[b] * (f[b] + hh[b]), u[b], T, a.table_m);
+            for (int j = 0; j < U; ++j) {
+                if (k0 + j < nA) {
+                    cf -= rs_coupling<JE, BITS>(x[j], bit) * ((e[j] >> 31) ? -2.0f : 2.0f);
+                    if (csite == (int)(e[j] & 0x7fffffffu)) cs = -cs;
+                }
             }
         }
-        from = first + 1;
+        bool acc = cvalid && rs_accept((float)cs * (cf + chh), cu, T, a.table_m);
+        unsigned long long m = ballot64(acc);  // accepting lanes among the undecided ones
+        while (m) {
+            int cl[K];
+            RsRaw<JE, BITS> x[K];
+            unsigned long long rest = m;
+#pragma unroll
+            for (int j = 0; j < K; ++j) {
+                cl[j] = rest ? (int)__builtin_ctzll(rest) : 64;
+                rest &= rest - 1;
+            }
+#pragma unroll
+            for (int j = 0; j < K; ++j) {
+                x[j] = RsRaw<JE, BITS>{};
+                if (cl[j] < 64) rs_coupling_load<JE, BITS>(x[j], a, p, read_lane(csite, cl[j]), voff);  // wave-uniform
+            }
+#pragma unroll
+            for (int j = 0; j < K; ++j) {
+                if (!m) break;
+                const int fl = (int)__builtin_ctzll(m);
+                if (fl < cl[j]) break;      // not fetched (or the candidates are used up): the next round
+                if (fl > cl[j]) continue;   // candidate j accepts no longer
+                const int sa = read_lane(csite, fl), ss = read_lane(cs, fl);
+                const float fk = (float)ss * (read_lane(cf, fl) + read_lane(chh, fl));
+                E += (double)(2.0f * fk);
+                if (lane == 0) {
+                    srow[sa] = (int8_t)(-ss);
+                    int aw;
+                    unsigned int ab;
+                    rs_bit_of(sa, aw, ab);
+                    atomicXor(&p.bits[(long long)r * p.nw32 + aw], ab);
+                    alist[nA] = (uint32_t)sa | (ss < 0 ? 0x80000000u : 0u);
+                }
+                ++nA;
+                cf -= rs_coupling<JE, BITS>(x[j], bit) * (2.0f * (float)ss);
+                if (csite == sa) cs = -cs;
+                acc = cvalid && rs_accept((float)cs * (cf + chh), cu, T, a.table_m);
+                m = ballot64(acc) & (~1ull << fl);
+            }
+        }
     }
     if (lane == 0) {
         a.energy[r] = E;
-        a.n_accepted[r] += nacc;
+        a.n_accepted[r] += (unsigned long long)nA;
         if (t0 + cnt == n && a.energy_trace) a.energy_trace[(long long)k * a.R + r] = E;
     }
 }
@@ -467,16 +536,19 @@ hipError_t launch_rs_build_planes(const void *J, bool j_is_i8, long long ldj, in
 hipError_t launch_sweep_dense_rs(const SweepArgs &a, const RowSharedPlan &p, bool j_is_i8, hipStream_t st) {
     if (a.rep_list || a.R <= 0 || a.n <= 0 || (p.W != 256 && p.W != 512 && p.W != 1024) || (1 << p.log_w) != p.W)
         return hipErrorInvalidValue;
-    if (p.log_rg < 0 || p.n_groups != (a.R + (1 << p.log_rg) - 1) >> p.log_rg || (p.jp && !p.jabs)) return hipErrorInvalidValue;
+    if (p.log_rg < 0 || p.n_groups != (a.R + (1 << p.log_rg) - 1) >> p.log_rg || (p.jp && !p.jabs) || !p.tot)
+        return hipErrorInvalidValue;
     const int nwin = (a.n + p.W - 1) / p.W;
     const dim3 pgrid(p.n_groups, nwin, (a.n + RS_PLAN_TILE - 1) / RS_PLAN_TILE);
     const size_t plds = sizeof(int) * (size_t)(a.n < RS_PLAN_TILE ? a.n : RS_PLAN_TILE);
+    const dim3 sgrid(row_shared_scan_chunks(a.n), nwin);
     const bool chain_bits = p.jp && p.planes == 1;
     hipLaunchKernelGGL(rs_pack_kernel, dim3(a.R), dim3(256), 0, st, a, p);
     hipError_t e = hipGetLastError();
     for (int k = 0; k < a.n_sweeps && e == hipSuccess; ++k) {
         hipLaunchKernelGGL(rs_plan_kernel<false>, pgrid, dim3(256), plds, st, a, p, k);
-        hipLaunchKernelGGL(rs_scan_kernel, dim3(nwin), dim3(1024), 0, st, a, p);
+        hipLaunchKernelGGL(rs_scan_totals_kernel, sgrid, dim3(RS_SCAN_CHUNK), 0, st, a, p);
+        hipLaunchKernelGGL(rs_scan_kernel, sgrid, dim3(RS_SCAN_CHUNK), 0, st, a, p);
         hipLaunchKernelGGL(rs_plan_kernel<true>, pgrid, dim3(256), plds, st, a, p, k);
         e = hipGetLastError();
         for (int w = 0; w < nwin && e == hipSuccess; ++w) {
