@@ -80,7 +80,7 @@ typedef struct sga_engine sga_engine;
 int sga_create(int device, sga_engine **out);
 void sga_destroy(sga_engine *e);
 const char *sga_last_error(void);
-int sga_version(void);  /* 1400: option "batch_fixed_point" (fixed-point cached local fields for many-model dense batches); 1300: options "ragged_field_cache" and "clf_fixed_point" together (fixed-point cached local fields for ragged CSR batches); 1200: sga_set_groups_csr (group couplings plus a stored sparse remainder); 1100: option "ragged_field_cache" (cached local fields for ragged CSR batches); 1000: sga_set_groups */
+int sga_version(void);  /* 1500: sga_get_scan_summary, and sga_set_dense / sga_set_dense_batch / sga_set_csr / sga_set_csr64 / sga_set_csr_batch refuse a NaN or +-Inf in J or h (SGA_ERR_INVALID, "non-finite"); 1400: option "batch_fixed_point" (fixed-point cached local fields for many-model dense batches); 1300: options "ragged_field_cache" and "clf_fixed_point" together (fixed-point cached local fields for ragged CSR batches); 1200: sga_set_groups_csr (group couplings plus a stored sparse remainder); 1100: option "ragged_field_cache" (cached local fields for ragged CSR batches); 1000: sga_set_groups */
 /* Run on an existing HIP stream (e.g. torch.cuda.current_stream().cuda_stream); NULL = the
  * engine's own stream (default). */
 int sga_set_stream(sga_engine *e, void *hip_stream);
@@ -631,6 +631,28 @@ int sga_route_query_init(sga_route_query *q);
 int sga_explain_route(const sga_route_query *q, char *buf, int buflen);
 /* the query the engine itself would pose for its current problem / replicas / options */
 int sga_get_route_query(sga_engine *e, sga_route_query *out);
+/* The raw words the set-time scans wrote for the problem as it is held (version >= 1500).  No device call: the setter
+ * keeps what it read back.  words may be NULL (then only *kind and *count are filled); else capacity >= *count.
+ * *kind = SGA_ROUTE_DENSE: 8 words; a dense batch is scanned stacked (every word is over all models' rows): model must be 0.
+ *   [0] 1: some J_ij is not an integer in [-127, 127] (0: J fits int8)
+ *   [1] 1: some J_ij is outside {-1, 0, +1}
+ *   [2] float bits of max_i (sum_j |J_ij| + |h_i|): the fp32 rounding of the fp64 sum
+ *   [3] bit 0: some J_ij is not an integer; bit 1: some h_i is not an integer; bit 2: some h_i is not a multiple of 1/2
+ *       (bit 3, non-finite input, is never seen here: such a problem is refused)
+ *   [4] 1: some model's J is not symmetric or has a non-zero diagonal entry
+ *   [5] 1024 + e_hi, [6] 1024 - e_lo: the binary exponents of the highest and the lowest set bit of any non-zero J_ij
+ *       (subnormals by their true bits: 3 x 2^-149 has e_hi = -148, e_lo = -149); both 0 when J is all zero
+ *   [7] float bits of max |J_ij|
+ * *kind = SGA_ROUTE_CSR: 11 words per model (ragged batches: model = 0 .. n_models - 1), the stored entries only:
+ *   [0] bad rowptr and [1] bad column (0: either is refused)
+ *   [2] the bits of dense word [3]
+ *   [3] 1: some row is not strictly ascending by column (unsorted, or a column twice)
+ *   [4] 1: a non-zero diagonal entry        [5] 1: J_ij != J_ji for some stored entry (duplicates summed)
+ *   [6] float bits of max_i (sum_j |J_ij| + |h_i|)   [7] 1024 + e_hi   [8] 1024 - e_lo   (as dense [5], [6])
+ *   [9] float bits of max_i sum_j |J_ij|    [10] entries of the longest row
+ * A dense matrix kept as CSR (sga_get_route_query: from_dense) reports the CSR words.
+ * sga_set_tsp / sga_set_groups*: SGA_ERR_UNSUPPORTED (scanned on the host, no words kept). */
+int sga_get_scan_summary(sga_engine *e, int model, int32_t *kind, int32_t *words, int capacity, int *count);
 /* the instantiation this ENGINE's last sweep launch ran (sga_last_kernel: this thread's last launch of any engine) */
 int sga_get_last_kernel(sga_engine *e, char *buf, int buflen);
 

@@ -43,6 +43,7 @@ SYMBOLS = [
     ("sga_route_query_init", _i, [C.POINTER(RouteQuery)]),
     ("sga_explain_route", _i, [C.POINTER(RouteQuery), C.c_char_p, _i]),
     ("sga_get_route_query", _i, [_p, C.POINTER(RouteQuery)]),
+    ("sga_get_scan_summary", _i, [_p, _i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _i, C.POINTER(_i)]),
     ("sga_get_last_kernel", _i, [_p, C.c_char_p, _i]),
     ("sga_get_autotune_table", _i, [_p, C.c_char_p, _i]),
     ("sga_create", _i, [_i, C.POINTER(_p)]),

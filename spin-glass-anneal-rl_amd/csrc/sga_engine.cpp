@@ -400,7 +400,7 @@ int ensure_packed(sga_engine *e) {
 extern "C" {
 
 const char *sga_last_error(void) { return g_last_error.c_str(); }
-int sga_version(void) { return 1400; }  // + option "batch_fixed_point": fixed-point cached local fields for many-model dense batches (sweep_clf_fx.hip, MODELS)  // 1300: + options "ragged_field_cache" and "clf_fixed_point" together: fixed-point cached local fields for ragged CSR batches (sweep_clf_csr.hip)  // 1200: + sga_set_groups_csr (group couplings plus a stored sparse remainder, sweep_groups.hip)  // 1100: + option "ragged_field_cache" (cached local fields for ragged CSR batches, sweep_clf_csr.hip)  // 1000: + sga_set_groups (implicit cardinality-group couplings, sweep_groups.hip)  // 900: + cached local fields for many-model dense batches (sga_set_dense_batch)  // 800: + option "clf_fixed_point" over dense couplings (sweep_clf_fx.hip)  // 700: + option "clf_fixed_point" (cached fields of real-valued CSR couplings)  // 600: + sga_set_csr_batch / sga_get_batch_model (ragged CSR batches)  // round 5: + sga_explain_route / sga_get_route_query, sga_get_last_kernel, sga_get_autotune_table, ladder-local sga_exchange
+int sga_version(void) { return 1500; }  // + sga_get_scan_summary; the dense and CSR setters refuse non-finite J / h  // 1400: + option "batch_fixed_point": fixed-point cached local fields for many-model dense batches (sweep_clf_fx.hip, MODELS)  // 1300: + options "ragged_field_cache" and "clf_fixed_point" together: fixed-point cached local fields for ragged CSR batches (sweep_clf_csr.hip)  // 1200: + sga_set_groups_csr (group couplings plus a stored sparse remainder, sweep_groups.hip)  // 1100: + option "ragged_field_cache" (cached local fields for ragged CSR batches, sweep_clf_csr.hip)  // 1000: + sga_set_groups (implicit cardinality-group couplings, sweep_groups.hip)  // 900: + cached local fields for many-model dense batches (sga_set_dense_batch)  // 800: + option "clf_fixed_point" over dense couplings (sweep_clf_fx.hip)  // 700: + option "clf_fixed_point" (cached fields of real-valued CSR couplings)  // 600: + sga_set_csr_batch / sga_get_batch_model (ragged CSR batches)  // round 5: + sga_explain_route / sga_get_route_query, sga_get_last_kernel, sga_get_autotune_table, ladder-local sga_exchange
 
 int sga_create(int device, sga_engine **out) {
     if (!out) return fail(SGA_ERR_INVALID, "out is NULL");

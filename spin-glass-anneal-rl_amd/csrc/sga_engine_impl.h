@@ -252,6 +252,10 @@ struct sga_engine {
         rs_R = rs_n = 0;
     }
     int csr_acc = sga::CSR_ACC_F64_CANON;  // CSR: how the sweep kernels form a row sum (set time)
+    // what the set-time scans wrote, as read back by the setter (sga_get_scan_summary): dense the eight words of
+    // classify_dense, CSR the CSR_* words and the longest row per model; empty: none kept (implicit couplings)
+    std::vector<int32_t> scan_words;
+    int scan_per_model = 0;  // words per model (dense: the one stacked scan)
     bool csr_x_exact = false;  // CSR: the fp64 sum X = sum_i mv_i s_i of an energy is exact in any order (set time)
 
     // replicas
@@ -331,6 +335,8 @@ struct sga_engine {
         n_rows = 0;
         model_n.clear();
         model_row0.clear();
+        scan_words.clear();
+        scan_per_model = 0;
         n = 0;
         ld = 0;
         free_row_shared();

@@ -345,13 +345,17 @@ hipError_t launch_widen_rowptr(const int32_t *src, long long *dst, long long cou
 hipError_t launch_rowinfo_fields(int4 *rowinfo, const float *h, int n, hipStream_t st);
 hipError_t launch_pack_entries(const int2 *cv, uint32_t *cvp, long long count, int *bad, hipStream_t st);
 hipError_t launch_narrow_rowptr(const long long *src, int32_t *dst, long long count, hipStream_t st);
-// CSR structure checks on the device.  flags (int[8], zeroed by the caller):
+// CSR structure checks on the device.  flags (int[CSR_FLAG_COUNT] = int[10], zeroed by the caller):
 //  [0] rowptr not monotone / not spanning [0, nnz]   [1] column out of range
-//  [2] some J or h not an integer                     [3] rows not strictly sorted by column
+//  [2] value bits (below)                             [3] rows not strictly sorted by column
 //  [4] non-zero diagonal entry                        [5] J[i][j] != J[j][i]
 //  [6] bits of max_i(sum_j |J_ij| + |h_i|) as float
-//  [7] 1024 + highest binary exponent of a non-zero J   [8] 1024 - exponent of the lowest set bit
-//  ([2]: bit 0 = some J, bit 1 = some h not an integer)
+//  [7] 1024 + exponent of the highest set bit of any non-zero J (subnormals: their true top bit)
+//  [8] 1024 - exponent of the lowest set bit          [9] bits of max_i sum_j |J_ij| as float
+//  ([2]: bit 0 = some J not an integer, bit 1 = some h not an integer, bit 2 = some h not a multiple of 1/2,
+//   bit 3 = SCAN_NON_FINITE: some J or h is NaN or +-Inf -- the setters refuse the problem; [6] to [9] then mean nothing)
+// The dense scans (launch_scan_values / launch_dense_row_abs_max) keep the same four bits in their word [3].
+enum { SCAN_NON_FINITE = 8 };
 enum { CSR_BAD_ROWPTR = 0, CSR_BAD_COLUMN, CSR_NOT_INTEGRAL, CSR_UNSORTED, CSR_DIAGONAL,
        CSR_ASYMMETRIC, CSR_ROW_ABS_MAX, CSR_EXP_HI, CSR_EXP_LO, CSR_ROW_J_ABS_MAX, CSR_FLAG_COUNT = 10 };
 // how the CSR sweep kernels form a row sum

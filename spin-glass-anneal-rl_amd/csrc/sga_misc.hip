@@ -61,7 +61,8 @@ __global__ void scan_values_kernel(const float *__restrict__ v, long long rows, 
             const unsigned int bits = __float_as_uint(x);
             const int ef = (int)((bits >> 23) & 255u);
             const unsigned int mant = (bits & 0x7FFFFFu) | (ef ? 0x800000u : 0u);
-            exp_hi = max(exp_hi, (ef ? ef - 127 : -127) + 1024);
+            // (a subnormal's top bit is its mantissa's: 2^-149 has hi = lo = -149, as sga_classify::span_add counts it)
+            exp_hi = max(exp_hi, (ef ? ef - 127 : -118 - __builtin_clz(mant ? mant : 1u)) + 1024);
             exp_lo = max(exp_lo, 1024 - ((ef ? ef - 127 : -126) - 23 + __builtin_ctz(mant ? mant : 1u)));
         }
     }
@@ -89,19 +90,21 @@ __global__ void __launch_bounds__(256) dense_row_abs_max_kernel(const float *__r
     __shared__ int bad[4];
     const int i = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     double acc = 0.0;
-    int nonint = 0;
+    int nonint = 0;  // bit 0: some J of this thread's is not an integer, SCAN_NON_FINITE: some is NaN or +-Inf
     float big = 0.0f;
     for (int j = tid; j < n; j += 256) {
         const float x = J[(long long)i * ldJ + j];
         acc += (double)__builtin_fabsf(x);
         nonint |= (x != __builtin_rintf(x));
+        // exponent field 255: fmaxf drops a NaN and +-Inf == rintf(+-Inf), so neither shows in the words below
+        if ((__float_as_uint(x) & 0x7F800000u) == 0x7F800000u) nonint |= SCAN_NON_FINITE;
         big = __builtin_fmaxf(big, __builtin_fabsf(x));
     }
     // out[5]: max |J_ij| over the matrix (non-negative floats: bit order = value order; one atomic per wave)
     for (int sft = 32; sft >= 1; sft >>= 1) big = __builtin_fmaxf(big, __shfl_xor(big, sft));
     if (lane == 0 && big > 0.0f) atomicMax(&out[5], __builtin_bit_cast(unsigned int, big));
     const double ws = wave_sum(acc);
-    const int wb = wave_sum(nonint);
+    const int wb = (__ballot(nonint & 1) ? 1 : 0) | (__ballot(nonint & SCAN_NON_FINITE) ? SCAN_NON_FINITE : 0);
     if (lane == 0) {
         red[w] = ws;
         bad[w] = wb;
@@ -111,7 +114,10 @@ __global__ void __launch_bounds__(256) dense_row_abs_max_kernel(const float *__r
         const float hi = h[i];
         const float row = (float)((red[0] + red[1]) + (red[2] + red[3]) + (double)__builtin_fabsf(hi));
         atomicMax(&out[0], __builtin_bit_cast(unsigned int, row));  // non-negative: bit order = value order
-        if (bad[0] | bad[1] | bad[2] | bad[3]) atomicOr(&out[1], 1u);  // some J not an integer
+        const int jbits = bad[0] | bad[1] | bad[2] | bad[3];
+        if (jbits & 1) atomicOr(&out[1], 1u);  // some J not an integer
+        if ((jbits & SCAN_NON_FINITE) || (__float_as_uint(hi) & 0x7F800000u) == 0x7F800000u)
+            atomicOr(&out[1], (unsigned int)SCAN_NON_FINITE);           // some J or h is NaN or +-Inf
         if (hi != __builtin_rintf(hi)) atomicOr(&out[1], 2u);           // some h not an integer
         if (2.0f * hi != __builtin_rintf(2.0f * hi)) atomicOr(&out[1], 4u);  // ... not even a multiple of 1/2
     }
@@ -399,11 +405,13 @@ __global__ void __launch_bounds__(256) csr_scan_kernel(const long long *rowptr, 
             const float v = val[j];
             if (c < 0 || c >= n) bad_col = 1;
             if (v != rintf(v)) non_int |= 1;
+            if ((__float_as_uint(v) & 0x7F800000u) == 0x7F800000u) non_int |= SCAN_NON_FINITE;  // NaN, +-Inf
             if (v != 0.0f) {  // binary exponents of the value's highest and lowest set bits
                 const unsigned int bits = __float_as_uint(v);
                 const int ef = (int)((bits >> 23) & 255u);
                 const unsigned int mant = (bits & 0x7FFFFFu) | (ef ? 0x800000u : 0u);
-                const int e_hi = ef ? ef - 127 : -127;
+                // (a subnormal's top bit is its mantissa's, as sga_classify::span_add counts it)
+                const int e_hi = ef ? ef - 127 : -118 - __builtin_clz(mant ? mant : 1u);
                 const int e_lo = (ef ? ef - 127 : -126) - 23 + __builtin_ctz(mant ? mant : 1u);
                 exp_hi = max(exp_hi, e_hi + 1024);
                 exp_lo = max(exp_lo, 1024 - e_lo);
@@ -415,6 +423,7 @@ __global__ void __launch_bounds__(256) csr_scan_kernel(const long long *rowptr, 
         const float hi = h[i];
         if (hi != rintf(hi)) non_int |= 2;
         if (2.0f * hi != rintf(2.0f * hi)) non_int |= 4;
+        if ((__float_as_uint(hi) & 0x7F800000u) == 0x7F800000u) non_int |= SCAN_NON_FINITE;
         // an upper bound is all the table needs; fp32 rounds it up or down by < 1 ulp
         const double jsum = wave_sum(acc);
         const float tot = (float)(jsum + (double)fabsf(hi));
@@ -422,7 +431,7 @@ __global__ void __launch_bounds__(256) csr_scan_kernel(const long long *rowptr, 
         row_j_max = fmaxf(row_j_max, (float)jsum);  // sum_j |J_ij| alone: the range of the dynamic part of a field
     }
     if (bad_col) flags[CSR_BAD_COLUMN] = 1;
-    if (non_int) atomicOr(&flags[CSR_NOT_INTEGRAL], non_int);  // bit 0: some J, bit 1: some h, bit 2: some 2 h
+    if (non_int) atomicOr(&flags[CSR_NOT_INTEGRAL], non_int);  // bit 0: some J, bit 1: some h, bit 2: some 2 h, bit 3: non-finite
     if (exp_hi) atomicMax(&flags[CSR_EXP_HI], exp_hi);
     if (exp_lo) atomicMax(&flags[CSR_EXP_LO], exp_lo);
     if (unsorted) flags[CSR_UNSORTED] = 1;

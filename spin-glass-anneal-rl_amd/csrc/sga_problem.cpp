@@ -24,6 +24,15 @@ sga_classify::CsrScan csr_scan_of(const int *flags) {
     return s;
 }
 
+// a model's CSR words as sga_get_scan_summary hands them out: the CSR_* words in enum order, then the longest row
+void keep_csr_scan(sga_engine *e, const int *flags, long long longest_row) {
+    e->scan_per_model = sga::CSR_FLAG_COUNT + 1;
+    e->scan_words.insert(e->scan_words.end(), flags, flags + sga::CSR_FLAG_COUNT);
+    e->scan_words.push_back((int32_t)std::min<long long>(longest_row, INT32_MAX));
+}
+
+const char *const NON_FINITE_MSG = "non-finite value (NaN or +-Inf) in J or h";
+
 // Pack the caller's fp32 matrix (device pointer `src`, row stride ld_src) into the engine's
 // layout(s): rows packed to 128 bytes, not padded to the kernel's whole chunks (2.4 % fewer bytes
 // per attempt at n = 10^4); lanes past a row's end re-read its first granule.
@@ -267,6 +276,7 @@ int set_csr_common(sga_engine *e, const void *rowptr, bool wide_extents, const i
     if (he == hipSuccess) he = read_flags();
     if (he != hipSuccess) return bail(SGA_ERR_DEVICE, hipGetErrorString(he));
     if (flags[sga::CSR_BAD_COLUMN]) return bail(SGA_ERR_INVALID, "CSR column index out of range");
+    if (flags[sga::CSR_NOT_INTEGRAL] & sga::SCAN_NON_FINITE) return bail(SGA_ERR_INVALID, NON_FINITE_MSG);
     // symmetric with zero diagonal?  Sorted rows: one binary search per entry; unsorted rows are
     // compared by linear scans while that stays cheap, else treated as asymmetric (exact-energy
     // mode: slower, never wrong)
@@ -290,6 +300,7 @@ int set_csr_common(sga_engine *e, const void *rowptr, bool wide_extents, const i
         for (int i = 0; i < n; ++i) max_len = std::max(max_len, src[(size_t)i + 1] - src[(size_t)i]);
         const sga_classify::CsrClass c = sga_classify::classify_csr(
             csr_scan_of(flags), max_len, n, {e->opt[OPT_HALF_TABLE] != 0, (int)e->opt[OPT_FORCE_CSR_ACC]});
+        keep_csr_scan(e, flags, max_len);
         e->consistent_dE = c.consistent_dE;
         e->table_m = c.table_m;
         e->table_scale = c.table_scale;
@@ -438,6 +449,12 @@ int sga_set_dense_batch(sga_engine *e, const float *J, int64_t ldJ, const float 
     HIPCHK(sga::launch_check_symmetric(src, ld_src, rows, n, flags + 4, e->stream));
     HIPCHK(hipMemcpyAsync(hflags, flags, sizeof(hflags), hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
+    if (hflags[3] & sga::SCAN_NON_FINITE) {
+        e->free_problem();
+        return fail(SGA_ERR_INVALID, NON_FINITE_MSG);
+    }
+    e->scan_words.assign(hflags, hflags + 8);
+    e->scan_per_model = 8;
     const sga_classify::DenseClass c = sga_classify::classify_dense(hflags, n, n_models, storage, e->opt[OPT_FORCE_DENSE_CANON] != 0);
     e->consistent_dE = c.consistent_dE;
     if (storage == SGA_J_I8 && !c.fits_i8)
@@ -935,6 +952,7 @@ int sga_set_csr_batch(sga_engine *e, int n_models, const int32_t *n_spins, const
         SGA_BATCH_CHK(scan([&] { return sga::launch_csr_scan(e->rowptr64 + r0, ci, vv, e->h + r0, nm, e->d_flags, e->stream); }));
         if (flags[sga::CSR_BAD_COLUMN])
             return bail(SGA_ERR_INVALID, who + "CSR column index out of range [0, " + std::to_string(nm) + ")");
+        if (flags[sga::CSR_NOT_INTEGRAL] & sga::SCAN_NON_FINITE) return bail(SGA_ERR_INVALID, who + NON_FINITE_MSG);
         if (flags[sga::CSR_DIAGONAL])
             return bail(SGA_ERR_UNSUPPORTED, who + "non-zero diagonal entry (ragged CSR batches need a zero diagonal)");
         const bool sorted = !flags[sga::CSR_UNSORTED];
@@ -953,6 +971,7 @@ int sga_set_csr_batch(sga_engine *e, int n_models, const int32_t *n_spins, const
         long long max_len = 0;
         for (int i = r0; i < r0 + nm; ++i) max_len = std::max(max_len, src[(size_t)i + 1] - src[(size_t)i]);
         classes[(size_t)m] = sga_classify::classify_csr(csr_scan_of(sym), max_len, nm, {e->opt[OPT_HALF_TABLE] != 0, 0});
+        keep_csr_scan(e, sym, max_len);
     }
     const bool want_clf = e->opt[OPT_RAGGED_FIELD_CACHE] == 1;
     const sga_classify::RaggedClass b = sga_classify::fold_ragged(
@@ -998,6 +1017,24 @@ int sga_set_csr_batch(sga_engine *e, int n_models, const int32_t *n_spins, const
     e->n = n_max;
     e->model_n.assign(n_spins, n_spins + n_models);
     e->model_row0 = row0;
+    return SGA_OK;
+}
+
+int sga_get_scan_summary(sga_engine *e, int model, int32_t *kind, int32_t *words, int capacity, int *count) {
+    if (!e) return fail(SGA_ERR_INVALID, "engine is NULL");
+    if (e->n <= 0) return fail(SGA_ERR_INVALID, "no problem set");
+    if (e->implicit() || e->scan_words.empty() || e->scan_per_model <= 0)
+        return fail(SGA_ERR_UNSUPPORTED, "sga_get_scan_summary: implicit couplings (sga_set_tsp, sga_set_groups*) are scanned on "
+                                         "the host and keep no scan words");
+    const int models = (int)(e->scan_words.size() / (size_t)e->scan_per_model);
+    if (model < 0 || model >= models)
+        return fail(SGA_ERR_INVALID, e->csr ? "model index out of range" : "a dense batch is scanned stacked: model must be 0");
+    if (count) *count = e->scan_per_model;
+    if (kind) *kind = e->csr ? SGA_ROUTE_CSR : SGA_ROUTE_DENSE;
+    if (words) {
+        if (capacity < e->scan_per_model) return fail(SGA_ERR_INVALID, "sga_get_scan_summary: capacity below the word count");
+        std::memcpy(words, e->scan_words.data() + (size_t)model * e->scan_per_model, sizeof(int32_t) * (size_t)e->scan_per_model);
+    }
     return SGA_OK;
 }
 

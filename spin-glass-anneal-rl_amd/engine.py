@@ -612,6 +612,16 @@ class AnnealEngine:
         N.check(self._lib.sga_get_route_query(self._h, C.byref(q)), "sga_get_route_query")
         return q
 
+    def scan_summary(self, model: int = 0):
+        """(kind, words) the set-time scans wrote for the problem as held (sga_get_scan_summary; layout in include/sga.h):
+        kind N.ROUTE_DENSE with 8 words -- a dense batch is scanned stacked, model must be 0 -- or N.ROUTE_CSR with the
+        CSR words and the longest row, per model of a ragged batch."""
+        kind, count = C.c_int32(-1), C.c_int(0)
+        words = (C.c_int32 * 16)()
+        N.check(self._lib.sga_get_scan_summary(self._h, int(model), C.byref(kind), words, 16, C.byref(count)),
+                "sga_get_scan_summary")
+        return int(kind.value), [int(w) for w in words[:count.value]]
+
     def explain_route(self) -> str:
         """What csrc/sga_route.cpp answers for this engine's problem, replicas and options."""
         return N.explain_route(self.route_query())

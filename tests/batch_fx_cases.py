@@ -5,6 +5,7 @@ no test lives here."""
 import numpy as np
 
 import oracle
+from scan_reference import scan_words  # noqa: F401  (the stacked scan's eight words: callers reach it through this module)
 
 INF = float("inf")
 FX_OPTIONS = {"clf_fixed_point": 1, "batch_fixed_point": 1}
@@ -75,29 +76,6 @@ def case_e():
     Js = np.stack([grid_sk(n, 110 + m) for m in range(M)])
     hs = np.stack([(np.random.RandomState(120 + m).randn(n) * 0.7).astype(np.float32) for m in range(M)])
     return Js, hs
-
-
-def scan_words(Js, hs):
-    """What the set-time scans hand to classify_dense for the stacked batch: (hflags[8] as ints) -- int8 / ternary flags,
-    max_i (sum_j |J_ij| + |h_i|) as float bits, the non-integer bits, symmetry, the exponent words of J's highest and
-    lowest set bit, max |J_ij| as float bits."""
-    J = Js.reshape(-1, Js.shape[-1]).astype(np.float32)
-    h = hs.reshape(-1).astype(np.float32)
-    integer = bool(np.all(J == np.rint(J)))
-    nz = J[J != 0].astype(np.float64)
-    mant, ex = np.frexp(np.abs(nz))
-    im = np.rint(np.ldexp(mant, 24)).astype(np.int64)
-    low = np.zeros_like(im)
-    for b in range(24):  # trailing zeros of the 24-bit mantissa
-        low += ((im & ((1 << (b + 1)) - 1)) == 0).astype(np.int64)
-    hi, lo = int((ex - 1).max()), int((ex - 24 + low).min())
-    row = np.float32((np.abs(J.astype(np.float64)).sum(1) + np.abs(h.astype(np.float64))).max())
-    nonint = (0 if integer else 1) | (0 if np.all(h == np.rint(h)) else 2) | (0 if np.all(2 * h == np.rint(2 * h)) else 4)
-    symmetric = all(np.array_equal(Jm, Jm.T) and not np.any(np.diag(Jm)) for Jm in Js)
-    fits_i8 = integer and float(np.abs(J).max()) <= 127
-    ternary = integer and float(np.abs(J).max()) <= 1
-    return [0 if fits_i8 else 1, 0 if ternary else 1, int(row.view(np.int32)), nonint, 0 if symmetric else 1, 1024 + hi,
-            1024 - lo, int(np.float32(np.abs(J).max()).view(np.int32))]
 
 
 # ----------------------------------------------------------------------------- truth: the oracle, one run per model
