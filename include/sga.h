@@ -562,7 +562,10 @@ int sga_set_tuning(sga_engine *e, int waves_per_replica, int sweeps_per_launch);
  * results are unaffected.  Candidates within 1 % of the fastest are a tie, which goes to the fewest waves / the simpler
  * form (a fixed preference order: other boxes and later profiles see the same pick).  The pick stays as
  * sga_set_tuning / option "csr_updates_per_step" would have set it (readable through sga_get_geometry /
- * sga_get_option).  Dense problems under option "row_shared" = 2 also time the row-shared windows at W = 256, 512 and
+ * sga_get_option) for as long as THIS problem is held, another sga_init_replicas included.  It ends with the problem
+ * it was measured on: the next sga_set_* call returns to the caller's own values -- what the caller last passed to
+ * sga_set_tuning and sga_set_option("csr_updates_per_step"), or the defaults -- sga_get_option reads the caller's value
+ * again and the table of sga_get_autotune_table is empty.  Dense problems under option "row_shared" = 2 also time the row-shared windows at W = 256, 512 and
  * 1024 on the winning geometry (table entries "row-shared:W<W>") and keep the fastest where it beats the fastest
  * geometry by more than 1 %; *best_ms_per_sweep is the fastest GEOMETRY's figure either way.  No-op for sga_set_tsp problems.
  * (No reference counterpart: the reference has no launch geometry.) */

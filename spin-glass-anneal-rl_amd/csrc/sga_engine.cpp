@@ -422,6 +422,7 @@ int sga_create(int device, sga_engine **out) {
         const char *v = d.env ? std::getenv(d.env) : nullptr;
         if (v) eng->opt[i] = d.env_presence ? d.env_value : std::max(d.lo, std::min(d.hi, (long long)std::atoll(v)));
     }
+    eng->caller_csr_ups = eng->opt[OPT_CSR_UPDATES_PER_STEP];
     {
         int cus = 0;
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cus > 0)
@@ -490,6 +491,7 @@ int sga_set_option(sga_engine *e, const char *key, int64_t value) {
         if (d.stage == 1 && e->R > 0) e->opt_stale |= 1, e->opt_stale_key = d.key;
     }
     e->opt[i] = (long long)value;
+    if (i == OPT_CSR_UPDATES_PER_STEP) e->caller_csr_ups = (long long)value;  // (the caller's, as opposed to sga_autotune's pick)
     return SGA_OK;
 }
 
@@ -520,7 +522,7 @@ int sga_set_tuning(sga_engine *e, int waves_per_replica, int sweeps_per_launch) 
     if (!e) return fail(SGA_ERR_INVALID, "engine is NULL");
     if (waves_per_replica < 0 || waves_per_replica > sga::MAX_WAVES || sweeps_per_launch < 0)
         return fail(SGA_ERR_INVALID, "bad tuning values");
-    e->tune_waves = waves_per_replica;
+    e->tune_waves = e->caller_tune_waves = waves_per_replica;
     e->tune_spl = sweeps_per_launch;
     return SGA_OK;
 }

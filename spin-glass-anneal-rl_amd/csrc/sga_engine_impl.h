@@ -130,6 +130,10 @@ struct sga_engine {
     // instead of silently running the form the old value chose
     int opt_stale = 0;
     const char *opt_stale_key = nullptr;
+    // The caller's own sga_set_tuning waves and option "csr_updates_per_step".  sga_autotune writes its pick into tune_waves
+    // and opt[] for the problem it measured; free_problem() -- every setter -- goes back to these.
+    int caller_tune_waves = 0;
+    long long caller_csr_ups = -1;
     hipStream_t own_stream = nullptr;
     hipStream_t stream = nullptr;
 
@@ -343,6 +347,44 @@ struct sga_engine {
         dev_free(rs_jp);
         dev_free(rs_jabs);
         rs_tuned_w = 0;
+        // every other problem-scoped member back to its declared default: what one problem's setter computed is never
+        // the next problem's, whichever setter that is and whether or not it assigns the member itself
+        // (tests/test_engine_reuse_host.py holds the struct's "// problem" section against this function)
+        n_models = 1;
+        csr = false;
+        want_i8 = acc64 = acc_canon = false;
+        waves_t2 = cpw_t2 = 0;
+        ldj = 0;
+        waves = cpw = 0;
+        csr_sorted = false;
+        csr_storage_latched = SGA_CSR_STORAGE_AUTO;
+        table_scale = 1;
+        layout_entries = 0;
+        max_row_len = 0;
+        big = false;
+        big_form = 0;
+        nnz = 0;
+        tsp_exact = true;
+        tsp_args = sga::TspArgs{};
+        tsp_waves = tsp_passes = 0;
+        g_memberships = 0;
+        g_max_size = g_kmax = g_exp = 0;
+        consistent_dE = true;
+        table_m = 0;
+        from_dense = false;
+        row_abs_max = 0.0f;
+        j_abs_max = 0;
+        row_j_abs_max = 0.0f;
+        csr_row_abs_max = 0.0f;
+        clf_scale = 1;
+        clf_bits = 16;
+        ldf = 0;
+        csr_acc = sga::CSR_ACC_F64_CANON;
+        csr_x_exact = false;
+        // sga_autotune's pick ends with the problem it was measured on (include/sga.h)
+        tune_waves = caller_tune_waves;
+        opt[OPT_CSR_UPDATES_PER_STEP] = caller_csr_ups;
+        tune_table.clear();
     }
     void free_replicas() {
         dev_free(spins);

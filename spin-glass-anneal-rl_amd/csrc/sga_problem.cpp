@@ -385,10 +385,17 @@ int route_sparse_dense(sga_engine *e, const float *src, long long ld_src, const 
     HIPCHK(hipMemcpyAsync(g.b, rp.data(), sizeof(int) * ((size_t)n + 1), hipMemcpyHostToDevice, e->stream));
     HIPCHK(sga::launch_dense_to_csr(src, ld_src, n, g.b, g.c, g.v, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
+    // (set_csr_common starts from free_problem()'s defaults; what sga_set_dense's scan found stays with the problem)
+    const bool want_i8 = e->want_i8, acc64 = e->acc64, acc_canon = e->acc_canon;
+    const float row_abs_max = e->row_abs_max;
+    const int j_abs_max = e->j_abs_max, clf_scale = e->clf_scale, clf_bits = e->clf_bits;
     const int rc = set_csr_common(e, g.b, false, g.c, g.v, h, n, total);
     if (rc == SGA_OK) {
         *taken = true;
         e->from_dense = true;
+        e->want_i8 = want_i8, e->acc64 = acc64, e->acc_canon = acc_canon;
+        e->row_abs_max = row_abs_max;
+        e->j_abs_max = j_abs_max, e->clf_scale = clf_scale, e->clf_bits = clf_bits;
     }
     return rc;
 }
@@ -457,10 +464,11 @@ int sga_set_dense_batch(sga_engine *e, const float *J, int64_t ldJ, const float 
     e->scan_per_model = 8;
     const sga_classify::DenseClass c = sga_classify::classify_dense(hflags, n, n_models, storage, e->opt[OPT_FORCE_DENSE_CANON] != 0);
     e->consistent_dE = c.consistent_dE;
-    if (storage == SGA_J_I8 && !c.fits_i8)
-        return fail(SGA_ERR_INVALID, "int8 storage requested but J is not integer in [-127,127]");
-    if (storage == SGA_J_T2 && !c.ternary)
-        return fail(SGA_ERR_INVALID, "bit-plane storage needs one model with J in {-1, 0, +1}");
+    if ((storage == SGA_J_I8 && !c.fits_i8) || (storage == SGA_J_T2 && !c.ternary)) {
+        e->free_problem();  // (no half-set problem: n, h and the scan words are this call's already)
+        return fail(SGA_ERR_INVALID, storage == SGA_J_I8 ? "int8 storage requested but J is not integer in [-127,127]"
+                                                         : "bit-plane storage needs one model with J in {-1, 0, +1}");
+    }
     e->use_t2 = c.use_t2;
     e->want_i8 = c.want_i8;
     e->acc64 = c.acc64;

@@ -66,9 +66,9 @@ def _fields(n, seed, lo=-1, hi=1, div=1.0):
     return (np.random.RandomState(seed).randint(lo, hi + 1, n) / div).astype(np.float32)
 
 
-def dense_streaming(storage, look):
+def dense_streaming(storage, look, n=256):
     def build():
-        te, n = _te(), 256
+        te = _te()
         J, h = te.pm1(n, 3), _fields(n, 4)
 
         def setup(e):
