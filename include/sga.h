@@ -80,7 +80,7 @@ typedef struct sga_engine sga_engine;
 int sga_create(int device, sga_engine **out);
 void sga_destroy(sga_engine *e);
 const char *sga_last_error(void);
-int sga_version(void);  /* 1500: sga_get_scan_summary, and sga_set_dense / sga_set_dense_batch / sga_set_csr / sga_set_csr64 / sga_set_csr_batch refuse a NaN or +-Inf in J or h (SGA_ERR_INVALID, "non-finite"); 1400: option "batch_fixed_point" (fixed-point cached local fields for many-model dense batches); 1300: options "ragged_field_cache" and "clf_fixed_point" together (fixed-point cached local fields for ragged CSR batches); 1200: sga_set_groups_csr (group couplings plus a stored sparse remainder); 1100: option "ragged_field_cache" (cached local fields for ragged CSR batches); 1000: sga_set_groups */
+int sga_version(void);  /* 1600: sga_set_dense_shared (one coupling matrix, many field vectors; row-shared windows, bit-planes and the matrix-core pass for such batches), sga_route_query.shared_j; 1500: sga_get_scan_summary, and sga_set_dense / sga_set_dense_batch / sga_set_csr / sga_set_csr64 / sga_set_csr_batch refuse a NaN or +-Inf in J or h (SGA_ERR_INVALID, "non-finite"); 1400: option "batch_fixed_point" (fixed-point cached local fields for many-model dense batches); 1300: options "ragged_field_cache" and "clf_fixed_point" together (fixed-point cached local fields for ragged CSR batches); 1200: sga_set_groups_csr (group couplings plus a stored sparse remainder); 1100: option "ragged_field_cache" (cached local fields for ragged CSR batches); 1000: sga_set_groups */
 /* Run on an existing HIP stream (e.g. torch.cuda.current_stream().cuda_stream); NULL = the
  * engine's own stream (default). */
 int sga_set_stream(sga_engine *e, void *hip_stream);
@@ -110,6 +110,29 @@ int sga_set_dense(sga_engine *e, const float *J, int64_t ldJ, const float *h, in
  * wider than int64.  A batch the integer form takes keeps it. */
 int sga_set_dense_batch(sga_engine *e, const float *J, int64_t ldJ, const float *h, int n,
                         int n_models, int storage);
+/* A batch with ONE coupling matrix and n_models field vectors (version >= 1600): J[n][ldJ] as in sga_set_dense, H is
+ * [n_models][n] (the same graph under many bias vectors, clamped sub-problems, a field scan).  In every call of this
+ * header the engine behaves exactly as after sga_set_dense_batch on J tiled n_models times with the same H -- the
+ * replica -> model map g / (R_global / n_models), R_global % n_models != 0 refused, n_ladders = n_models,
+ * sga_exchange_pairs (a pair across models is taken as there), spins, energies, bests, stats, export / import, the single-site operators,
+ * sharding through replica0, every refusal and its wording, the eight words of sga_get_scan_summary -- and each model
+ * walks the chain of a one-model engine holding (J, h_m) started at replica0 = m * (R_global / n_models), bit for bit,
+ * in whatever form runs.  Four things differ:
+ *   1. J is packed once: coupling memory is sga_set_dense's (bit-planes of the row-shared form included), not
+ *      n_models times it.
+ *   2. sga_problem_checksum covers J once and all of H.
+ *   3. sga_describe / sga_explain_route name the kind: "shared-J models=M".
+ *   4. The forms that need the ROWS to be the same for every replica open up: bit-plane storage (SGA_J_AUTO resolves
+ *      as for one model -- bit-planes for ternary J from n = 4096, else int8, else fp32 -- and SGA_J_T2 is served),
+ *      row-shared windows (option "row_shared"; integer J and EVERY h with exact fp32 sums -- one accept table for
+ *      the batch --, symmetric J with a zero diagonal, |J| <= 255, Metropolis, production arguments, field cache
+ *      OFF: a proposed row is read once for every replica of every model that proposes it) and the matrix-core
+ *      energy / field pass (J leaves HBM once for all replicas).  Cached fields ON / AUTO behave as on the stacked
+ *      batch: batch-wide scale, field width and table; the fixed-point form behind "clf_fixed_point" +
+ *      "batch_fixed_point".  AUTO's break-evens are the stacked batch's (not measured for shared batches).
+ * A NaN or +-Inf in J or H: SGA_ERR_INVALID ("non-finite"), as the other setters. */
+int sga_set_dense_shared(sga_engine *e, const float *J, int64_t ldJ, const float *H /* [n_models][n] */, int n,
+                         int n_models, int storage);
 /* CSR couplings (both triangles present), rowptr[n+1], colidx[nnz], val[nnz], h[n]; host or
  * device pointers.  The structure is checked on the device (SGA_ERR_INVALID for extents that are
  * not monotone / do not span [0, nnz], or a column outside [0, n)); rows need not be sorted and
@@ -524,7 +547,7 @@ int sga_set_field_cache(sga_engine *e, int mode);
  *   "zero_slot_every"       0 = 2^21 (default), k: an all-zero slot inside the slotted layout after every k slots [set; SGA_ZERO_SLOT_EVERY]
  *   "csr_bits"              0 | 1 (default)   bit spins where they keep more replicas LDS resident      [init; SGA_NO_CSR_BITS]
  *   "force_csr_bits"        0 (default) | 1   CSR sweeps with bit spins whatever the size               [init; SGA_FORCE_CSR_BIG]
- *   "row_shared"            0 | 1 | 2 (default)   dense integer problems (one model, J and h integer with exact fp32 sums,
+ *   "row_shared"            0 | 1 | 2 (default)   dense integer problems (one model, or the models of sga_set_dense_shared; J and h integer with exact fp32 sums,
  *                           J symmetric with a zero diagonal, |J| <= 255), production sweeps with the field cache off:
  *                           "row-shared windows" (csrc/sweep_dense_rs.hip) -- each sweep cut into windows of W updates per
  *                           replica, each proposed row read ONCE per window and dotted with the window-start spins of every
@@ -613,7 +636,7 @@ typedef struct sga_route_query {
     int32_t n_cities;     /* TSP */
     /* as laid out (0 = derive from the rest) */
     int32_t sstride;      /* spin stride of the replicas */
-    int32_t reserved_;
+    int32_t shared_j;     /* dense batches: 1 = one coupling matrix for every model (sga_set_dense_shared; version >= 1600) */
     int64_t ldj;          /* dense: row stride of the packed couplings in elements */
     int64_t opt[SGA_ROUTE_MAX_OPTS]; /* option values, index = sga_option_name order */
     /* sga_set_groups (version >= 1000) */

@@ -32,7 +32,7 @@ class RouteQuery(C.Structure):
     _fields_ = [(k, C.c_int32) for k in ("kind", "n", "n_models", "R_local", "cus", "tune_waves", "field_cache", "storage",
                                          "acc", "table_m", "table_scale", "clf_ok", "clf_bits", "clf_scale", "from_dense")] + \
                [("nnz", C.c_int64), ("max_row_len", C.c_int64), ("layout_entries", C.c_int64)] + \
-               [(k, C.c_int32) for k in ("slotted", "rowptr32", "packed_ok", "n_cities", "sstride", "reserved_")] + \
+               [(k, C.c_int32) for k in ("slotted", "rowptr32", "packed_ok", "n_cities", "sstride", "shared_j")] + \
                [("ldj", C.c_int64), ("opt", C.c_int64 * ROUTE_MAX_OPTS)] + \
                [("n_groups", C.c_int32), ("group_max", C.c_int32)] + \
                [("rest_nnz", C.c_int64), ("rest_max_row", C.c_int32), ("reserved2_", C.c_int32)]
@@ -53,6 +53,7 @@ SYMBOLS = [
     ("sga_set_stream", _i, [_p, _p]),
     ("sga_set_dense", _i, [_p, _p, _i64, _p, _i, _i]),
     ("sga_set_dense_batch", _i, [_p, _p, _i64, _p, _i, _i, _i]),
+    ("sga_set_dense_shared", _i, [_p, _p, _i64, _p, _i, _i, _i]),
     ("sga_set_csr", _i, [_p, _p, _p, _p, _p, _i, _i64]),
     ("sga_set_csr64", _i, [_p, _p, _p, _p, _p, _i, _i64]),
     ("sga_set_csr_batch", _i, [_p, _i, _p, _p, _p, _p, _p, _i64]),

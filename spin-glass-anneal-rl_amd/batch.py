@@ -39,6 +39,15 @@ h off the half-integers.  The fields are D = 2^k J_m s as exact int32 | int64 at
 own model's rows; the same chain, so every result field but `total_time` equals the "off" result.  A batch that does
 not qualify (f64-canonical J, an asymmetric J or a non-zero diagonal in some model) fails under "on" and runs the row
 kernels under "auto".  With either flag unset the stacked path is what it was.
+
+`BatchConfig.shared_couplings=True` (build-specific, default False): inside a chunk of dense models of one size, a run of
+two or more CONSECUTIVE models that hold the same couplings (`shared_coupling_runs`: the same tensor object, the same
+storage, or equal values) goes to ONE engine through `set_dense_shared` -- the matrix is handed over, packed and kept
+once, each model contributes its field vector alone; what lies between two runs is stacked as before.  Such a run is
+the same graph under many bias vectors: a policy's proposals, sub-problems with clamped variables, a field scan.  Every
+segment is annealed as `process_models_batch` would anneal it on its own (replicas numbered from the segment's first
+model), so a chunk that is one run gives the default path's results field for field but `total_time`.  All engine
+options above act on a shared run as on a stacked batch.
 """
 import time
 from dataclasses import dataclass
@@ -69,6 +78,7 @@ class BatchConfig:
     replicas_per_model: int = 1  # build-specific: independent restarts per model, best is kept
     ragged_field_cache: bool = False  # build-specific: sparse chunks serve field_cache "on" / "auto" on the ragged engine
     stacked_fixed_point: bool = False  # build-specific: stacked real-valued batches serve field_cache "on" / "auto" (fixed point)
+    shared_couplings: bool = False  # build-specific: runs of dense models with one coupling matrix go through set_dense_shared
 
     def __post_init__(self):
         if self.batch_size <= 0:
@@ -81,6 +91,38 @@ class BatchConfig:
             raise ValueError("replicas_per_model must be positive")
         if not isinstance(self.stacked_fixed_point, bool):
             raise ValueError("stacked_fixed_point must be a bool")
+        if not isinstance(self.shared_couplings, bool):
+            raise ValueError("shared_couplings must be a bool")
+
+
+def _same_couplings(a: torch.Tensor, b: torch.Tensor) -> bool:
+    if a is b:
+        return True
+    if a.is_sparse or b.is_sparse or a.shape != b.shape:
+        return False
+    if a.dtype == b.dtype and a.device == b.device and a.data_ptr() == b.data_ptr() and a.stride() == b.stride():
+        return True  # two views of one storage
+    if a.device != b.device:
+        a, b = a.detach().cpu(), b.detach().cpu()
+    return a.dtype == b.dtype and bool(torch.equal(a, b))
+
+
+def shared_coupling_runs(models) -> List[tuple]:
+    """[(start, stop), ...]: the maximal runs models[start:stop] of two or more CONSECUTIVE dense models that share
+    their couplings -- the same tensor object, or the same storage pointer, shape and strides, or else equal values
+    (`torch.equal`).  A sparse model or a differing matrix ends a run; a run of one is not shared.  Pure: no engine,
+    no GPU needed."""
+    runs, start = [], 0
+    while start < len(models):
+        stop = start + 1
+        first = models[start].couplings
+        if not first.is_sparse:
+            while stop < len(models) and _same_couplings(first, models[stop].couplings):
+                stop += 1
+        if stop - start >= 2:
+            runs.append((start, stop))
+        start = stop
+    return runs
 
 
 class BatchProcessor:
@@ -92,6 +134,7 @@ class BatchProcessor:
         self.processed_models = 0
         self.total_processing_time = 0.0
         self.batch_times: List[float] = []
+        self.last_description: Optional[str] = None  # sga_describe of the last shared-coupling engine (shared_couplings)
 
     # ------------------------------------------------------------------ public API
     def process_models_batch(self, models: List[IsingModel]) -> List[AnnealingResult]:
@@ -121,7 +164,7 @@ class BatchProcessor:
             for lo in range(0, len(idxs), self.batch_config.batch_size):
                 part = idxs[lo:lo + self.batch_config.batch_size]
                 t0 = time.time()
-                for i, r in zip(part, self._anneal_stack([models[i] for i in part])):
+                for i, r in zip(part, self._anneal_dense([models[i] for i in part])):
                     results[i] = r
                 self.batch_times.append(time.time() - t0)
         self.processed_models += len(models)
@@ -150,6 +193,36 @@ class BatchProcessor:
 
     def reset(self) -> None:
         self.processed_models, self.total_processing_time, self.batch_times = 0, 0.0, []
+
+    # ------------------------------------------------------------------ a chunk of dense models of one size
+    def _anneal_dense(self, models: List[IsingModel]) -> List[AnnealingResult]:
+        if not self.batch_config.shared_couplings:
+            return self._anneal_stack(models)
+        out: List[AnnealingResult] = []
+        at = 0
+        for start, stop in shared_coupling_runs(models) + [(len(models), len(models))]:
+            if start > at:  # what lies before the run: stacked, as always
+                out += self._anneal_stack(models[at:start])
+            if stop > start:
+                out += self._anneal_shared(models[start:stop])
+            at = stop
+        return out
+
+    # ------------------------------------------------------------------ one run over one coupling matrix
+    def _anneal_shared(self, models: List[IsingModel]) -> List[AnnealingResult]:
+        J = models[0].dense_couplings().detach().cpu().numpy().astype(np.float32)
+        H = np.stack([m.external_fields.detach().cpu().numpy().astype(np.float32) for m in models])
+        s0 = np.stack([m.spins_int8() for m in models])  # [M, n]
+        self.last_description = None
+
+        def set_problem(eng):
+            if self.batch_config.stacked_fixed_point and self.annealer_config.fixed_point_fields:
+                eng.set_option("clf_fixed_point", 1)  # ([set] options: before the couplings)
+                eng.set_option("batch_fixed_point", 1)
+            eng.set_dense_shared(J, H, storage=self.annealer_config.coupling_storage)
+            self.last_description = eng.describe()  # names the kind: "... shared-J models=M ..."
+
+        return self._run(models, set_problem, s0)
 
     # ------------------------------------------------------------------ one stacked run
     def _anneal_stack(self, models: List[IsingModel]) -> List[AnnealingResult]:

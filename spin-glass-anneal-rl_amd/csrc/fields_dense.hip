@@ -229,6 +229,7 @@ hipError_t launch_fields_dense(const FieldsArgs &a, int mode, hipStream_t st) {
 // From the fields to the energies (and to the resident fields of the cached-field sweep):
 //   E_r = -1/2 fp32(sum_i Y_ri s_ri) - fp32(sum_i h_i s_ri)      (core/ising_model.py:161-168)
 //   F_ri = scale * (Y_ri + h_i)   as int16 | int32               (integer problems only)
+// (h: the one model's, or -- a.reps_per_model > 0 -- that of the replica's model: the MFMA pass knows no models)
 // One workgroup per replica; the energy's sums in fp64 in the per-replica kernels' order (sga_kernels.h,
 // energy_block_rows), each row's Y_ri rounded to fp32 as their row sums are: the same bits as theirs wherever the
 // row sums are exact.
@@ -241,9 +242,12 @@ __global__ void __launch_bounds__(256) fields_finish_kernel(const FieldsArgs a) 
     const int8_t *s = a.spins + (long long)r * a.sstride;
     int16_t *f16 = a.field_bits == 16 ? reinterpret_cast<int16_t *>(a.fields) + (long long)r * a.ldf : nullptr;
     int32_t *f32 = a.field_bits == 32 ? reinterpret_cast<int32_t *>(a.fields) + (long long)r * a.ldf : nullptr;
+    // one shared matrix under many field vectors: the h of this replica's model (workgroup-uniform)
+    const float *hv = a.h;
+    if (a.reps_per_model > 0) hv += (long long)((unsigned int)(a.replica_base + r) / (unsigned int)a.reps_per_model) * a.n;
     if (f16 || f32) {
         for (int i = tid; i < a.n; i += 256) {
-            const int v = (int)((float)a.field_scale * ((float)y[i] + a.h[i]));  // exact: integers / half-integers < 2^24
+            const int v = (int)((float)a.field_scale * ((float)y[i] + hv[i]));  // exact: integers / half-integers < 2^24
             if (f16) f16[i] = (int16_t)v;
             else f32[i] = v;
         }
@@ -256,7 +260,7 @@ __global__ void __launch_bounds__(256) fields_finish_kernel(const FieldsArgs a) 
     double et, ht;
     energy_canonical_sums(
         a.n, a.eblock, [&](int i) { return (double)(float)y[i] * (double)s[i]; },
-        [&](int i) { return (double)a.h[i] * (double)s[i]; }, ce, ch, et, ht);
+        [&](int i) { return (double)hv[i] * (double)s[i]; }, ce, ch, et, ht);
     if (tid == 0) a.energy[r] = -0.5 * (double)(float)et + (-(double)(float)ht);
 }
 

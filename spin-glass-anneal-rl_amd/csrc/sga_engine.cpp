@@ -16,6 +16,7 @@ sga_route_query route_query_of(const sga_engine *e) {
     q.kind = e->groups ? SGA_ROUTE_GROUPS : e->tsp ? SGA_ROUTE_TSP : (e->csr ? SGA_ROUTE_CSR : SGA_ROUTE_DENSE);
     q.n = e->n;
     q.n_models = e->n_models;
+    q.shared_j = e->shared_j ? 1 : 0;
     q.R_local = e->R;
     q.cus = e->cus;
     q.tune_waves = e->tune_waves;
@@ -66,7 +67,9 @@ bool fields_pass_applies(const sga_engine *e, int count) {
     // together (sga_set_spins: one; a shard: R_local).
     const long long mode = e->opt[OPT_BATCHED_ENERGY];
     if (mode == 0 || (mode == 1 && e->acc_canon)) return false;
-    return !e->csr && !e->implicit() && e->n_models == 1 && count >= 32 && e->J_packed;
+    // (one matrix for every replica: one model, or the models of sga_set_dense_shared -- the finish pass reads each
+    //  replica's own h)
+    return !e->csr && !e->implicit() && (e->n_models == 1 || e->shared_j) && count >= 32 && e->J_packed;
 }
 // The pass writes Y = S J^T for the replicas it is given into a scratch buffer ([tile][ldj] int32 | fp32) before
 // the finish kernel reduces it.  The scratch is bounded: replica sets whose Y would exceed the cap go
@@ -111,6 +114,8 @@ int fields_pass(sga_engine *e, int r0, int count, double *energy, void *fields) 
         f.field_bits = fields ? e->clf_bits : 0;
         f.field_scale = e->clf_scale;
         f.eblock = sga::energy_block_rows(e->n);
+        f.reps_per_model = e->shared_j ? e->Rg / e->n_models : 0;
+        f.replica_base = e->replica0 + r0 + (int)t0;
         HIPCHK(sga::launch_fields_dense(f, mode, e->stream));
         HIPCHK(sga::launch_fields_finish(f, mode == 0, e->stream));
     }
@@ -119,14 +124,16 @@ int fields_pass(sga_engine *e, int r0, int count, double *energy, void *fields) 
 
 // Row-shared windows (sweep_dense_rs.hip, option "row_shared"): the window W of the form for sweeps whose arguments are
 // the production ones (lean), 0 where today's row-per-proposal kernel runs.  The form needs what the look-ahead form
-// needs -- one dense model, integer J and h with exact fp32 sums (the accept table), Metropolis -- and J symmetric with a
-// zero diagonal (a flip's correction is read from the flipped site's row), |J| <= 255 (bit-planes of |J|).
+// needs -- one dense matrix, integer J and h with exact fp32 sums (the accept table), Metropolis -- and J symmetric with a
+// zero diagonal (a flip's correction is read from the flipped site's row), |J| <= 255 (bit-planes of |J|).  One matrix:
+// one model, or the models of sga_set_dense_shared, whose conditions are the batch's (table_m is over every h: one
+// accept table); a stacked batch has a row i per model and stays on the row-per-proposal kernel.
 // 1 = wherever it applies (W: option "row_shared_window", else the autotuner's, else 1024), 2 = where sga_autotune
 // measured it ahead (default).
 int row_shared_window(const sga_engine *e, bool lean) {
     const long long o = e->opt[OPT_ROW_SHARED];
     if (o == 0 || e->rs_suspend || !lean || e->rule != SGA_RULE_METROPOLIS || e->field_cache != SGA_FIELD_CACHE_OFF) return 0;
-    if (e->csr || e->implicit() || e->ragged || e->n_models != 1 || e->table_m <= 0 || e->acc64 || !e->consistent_dE) return 0;
+    if (e->csr || e->implicit() || e->ragged || (e->n_models != 1 && !e->shared_j) || e->table_m <= 0 || e->acc64 || !e->consistent_dE) return 0;
     if (e->opt[OPT_LOOK_AHEAD] == 0 || e->opt[OPT_FORCE_GENERAL] != 0 || !e->J_packed) return 0;
     if (sga::row_shared_planes(e->j_abs_max) == 0 || (long long)e->R * e->n >= (1ll << 31) || e->R >= (1 << 20)) return 0;
     if (o == 2) return e->rs_tuned_w;
@@ -256,7 +263,7 @@ int ensure_fields(sga_engine *e) {
         return fail(SGA_ERR_MEMORY, "no memory for the resident local fields of the cached-field sweep");
     }
     if (e->clf_fx_bits && e->n_models > 1) {  // option "batch_fixed_point": each replica over its own model's rows
-        HIPCHK(sga::launch_dense_fields_seed_fx_batch(e->J_packed, e->want_i8, e->ldj, (long long)e->n * e->ldj, e->spins,
+        HIPCHK(sga::launch_dense_fields_seed_fx_batch(e->J_packed, e->want_i8, e->ldj, model_stride_j(e), e->spins,
                                                       e->sstride, e->n, e->R, (uint32_t)e->replica0, e->Rg / e->n_models,
                                                       e->fields, e->ldf, e->clf_fx_bits, e->clf_fx_k, e->stream));
         e->fields_valid = true;
@@ -268,8 +275,10 @@ int ensure_fields(sga_engine *e) {
         e->fields_valid = true;
         return SGA_OK;
     }
-    if (e->n_models > 1) {  // many-model batches: exact integer sums per model, one launch (sweep_clf.hip)
-        HIPCHK(sga::launch_dense_fields_seed_batch(e->J_packed, e->want_i8, e->ldj, (long long)e->n * e->ldj, e->h, e->spins,
+    // many-model batches: exact integer sums per model, one launch (sweep_clf.hip).  One shared matrix holding 32
+    // replicas or more: the matrix-core pass below, J read once for all of them (integer sums: the same fields)
+    if (e->n_models > 1 && !(e->shared_j && e->R >= 32)) {
+        HIPCHK(sga::launch_dense_fields_seed_batch(e->J_packed, e->want_i8, e->ldj, model_stride_j(e), e->h, e->spins,
                                                    e->sstride, e->n, e->R, (uint32_t)e->replica0, e->Rg / e->n_models,
                                                    e->fields, e->ldf, e->clf_bits, e->clf_scale, e->stream));
         e->fields_valid = true;
@@ -347,7 +356,7 @@ int recompute_energy_range(sga_engine *e, int r0, int count) {
     a.R = count;
     a.reps_per_model = e->n_models > 1 ? e->Rg / e->n_models : 0;
     a.replica_base = e->replica0 + r0;
-    a.model_stride_j = (long long)e->n * e->ldj;
+    a.model_stride_j = model_stride_j(e);  // (0: one shared matrix)
     // the canonical order of the sums (sga_kernels.h): blocks of rows (TSP: of cities), a function of n alone
     const int units = e->tsp ? e->tsp_args.n_cities : e->n;
     a.block_rows = e->tsp ? (units + sga::ENERGY_MAX_BLOCKS - 1) / sga::ENERGY_MAX_BLOCKS : sga::energy_block_rows(units);
@@ -400,7 +409,7 @@ int ensure_packed(sga_engine *e) {
 extern "C" {
 
 const char *sga_last_error(void) { return g_last_error.c_str(); }
-int sga_version(void) { return 1500; }  // + sga_get_scan_summary; the dense and CSR setters refuse non-finite J / h  // 1400: + option "batch_fixed_point": fixed-point cached local fields for many-model dense batches (sweep_clf_fx.hip, MODELS)  // 1300: + options "ragged_field_cache" and "clf_fixed_point" together: fixed-point cached local fields for ragged CSR batches (sweep_clf_csr.hip)  // 1200: + sga_set_groups_csr (group couplings plus a stored sparse remainder, sweep_groups.hip)  // 1100: + option "ragged_field_cache" (cached local fields for ragged CSR batches, sweep_clf_csr.hip)  // 1000: + sga_set_groups (implicit cardinality-group couplings, sweep_groups.hip)  // 900: + cached local fields for many-model dense batches (sga_set_dense_batch)  // 800: + option "clf_fixed_point" over dense couplings (sweep_clf_fx.hip)  // 700: + option "clf_fixed_point" (cached fields of real-valued CSR couplings)  // 600: + sga_set_csr_batch / sga_get_batch_model (ragged CSR batches)  // round 5: + sga_explain_route / sga_get_route_query, sga_get_last_kernel, sga_get_autotune_table, ladder-local sga_exchange
+int sga_version(void) { return 1600; }  // + sga_set_dense_shared (one coupling matrix, many field vectors), sga_route_query.shared_j  // 1500: + sga_get_scan_summary; the dense and CSR setters refuse non-finite J / h  // 1400: + option "batch_fixed_point": fixed-point cached local fields for many-model dense batches (sweep_clf_fx.hip, MODELS)  // 1300: + options "ragged_field_cache" and "clf_fixed_point" together: fixed-point cached local fields for ragged CSR batches (sweep_clf_csr.hip)  // 1200: + sga_set_groups_csr (group couplings plus a stored sparse remainder, sweep_groups.hip)  // 1100: + option "ragged_field_cache" (cached local fields for ragged CSR batches, sweep_clf_csr.hip)  // 1000: + sga_set_groups (implicit cardinality-group couplings, sweep_groups.hip)  // 900: + cached local fields for many-model dense batches (sga_set_dense_batch)  // 800: + option "clf_fixed_point" over dense couplings (sweep_clf_fx.hip)  // 700: + option "clf_fixed_point" (cached fields of real-valued CSR couplings)  // 600: + sga_set_csr_batch / sga_get_batch_model (ragged CSR batches)  // round 5: + sga_explain_route / sga_get_route_query, sga_get_last_kernel, sga_get_autotune_table, ladder-local sga_exchange
 
 int sga_create(int device, sga_engine **out) {
     if (!out) return fail(SGA_ERR_INVALID, "out is NULL");
@@ -878,7 +887,7 @@ sga::SweepArgs base_args(const sga_engine *e, const SweepCall &c, const SweepPla
     if (a.csr_acc == sga::CSR_ACC_F32_TABLE && a.table_m == 0) a.csr_acc = sga::CSR_ACC_F32;
     a.no_best = p.exact_mode ? 1 : 0;
     a.reps_per_model = (e->n_models > 1 || e->ragged) ? e->Rg / e->n_models : 0;
-    a.model_stride_j = (long long)e->n * e->ldj;
+    a.model_stride_j = model_stride_j(e);  // (0: one shared matrix)
     if (e->ragged) a.ragged = e->ragged_at;
     a.seed_lo = (uint32_t)e->seed;
     a.seed_hi = (uint32_t)(e->seed >> 32);
@@ -1252,7 +1261,7 @@ static int point_op(sga_engine *e, int r, const int32_t *sites, int count, int o
         sga::PointArgs a{};
         const long long model = e->n_models > 1 ? (e->replica0 + r) / (e->Rg / e->n_models) : 0;
         a.J = e->J_packed;
-        a.model_offset_j = model * e->n * e->ldj;
+        a.model_offset_j = model * model_stride_j(e);  // (one shared matrix: 0; h and diag are per model)
         a.rowptr = e->rowptr64;
         a.cv = e->cv;
         a.h = e->h + model * e->n;

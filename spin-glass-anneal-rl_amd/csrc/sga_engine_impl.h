@@ -140,6 +140,9 @@ struct sga_engine {
     // problem
     int n = 0;
     int n_models = 1;  // dense batches: models stacked row-wise, replicas split evenly
+    // sga_set_dense_shared: the n_models models hold ONE coupling matrix (J_packed, J_bits: n rows) and differ in h alone
+    // ([n_models][n]; diag and row_nnz are repeated per model, so the kernels index them as they index a stacked batch's)
+    bool shared_j = false;
     // ragged CSR batches (sga_set_csr_batch): n_models CSR problems of any sizes concatenated row-wise, replicas split
     // evenly; n = the largest model's spins (the replica layout), n_rows = the rows of the concatenation
     bool ragged = false;
@@ -351,6 +354,7 @@ struct sga_engine {
         // the next problem's, whichever setter that is and whether or not it assigns the member itself
         // (tests/test_engine_reuse_host.py holds the struct's "// problem" section against this function)
         n_models = 1;
+        shared_j = false;
         csr = false;
         want_i8 = acc64 = acc_canon = false;
         waves_t2 = cpw_t2 = 0;
@@ -419,6 +423,8 @@ namespace sga_impl {
 inline int model_of(const sga_engine *e, int r) {
     return e->ragged && e->Rg > 0 ? (e->replica0 + r) / (e->Rg / e->n_models) : 0;
 }
+// elements between two models' coupling blocks as the kernels add them (SweepArgs::model_stride_j): 0 = one shared matrix
+inline long long model_stride_j(const sga_engine *e) { return e->shared_j ? 0 : (long long)e->n * e->ldj; }
 inline int spins_of(const sga_engine *e, int r) { return e->ragged ? e->model_n[(size_t)model_of(e, r)] : e->n; }
 
 inline int elems_per_chunk(bool i8) { return i8 ? 1024 : 256; }

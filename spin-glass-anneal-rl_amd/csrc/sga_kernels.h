@@ -58,7 +58,8 @@ struct SweepArgs {
     int n, sstride, R, n_sweeps;
     int site_mode, arith, rule;
     // many-model batches (dense): replica r belongs to model (replica0 + r) / reps_per_model;
-    // J / h / diag of model m start at m * model_stride_j / m * n elements (0 = one model)
+    // J / h / diag of model m start at m * model_stride_j / m * n elements (reps_per_model 0 = one model;
+    // model_stride_j 0 with reps_per_model > 0 = one shared matrix under many field vectors, sga_set_dense_shared)
     int reps_per_model;
     long long model_stride_j;
     int no_best;  // 1: leave best tracking to the host-driven pass (asymmetric / diagonal J)
@@ -186,13 +187,16 @@ struct FieldsArgs {
     const void *J;         // dense [n][ldj] int8 | float
     const int8_t *spins;   // [R][sstride]
     void *Y;               // [R][ldy] int32 (int8 J) | float: Y[r][i] = sum_j J[i][j] s[r][j]
-    const float *h;        // [n]
+    const float *h;        // [n]; many-model batches over one shared matrix: [n_models][n] (reps_per_model below)
     double *energy;        // [R] or null (finish pass)
     void *fields;          // [R][ldf] int16 | int32 or null (finish pass): field_scale * (Y + h)
     long long ldj, ldy, ldf;
     int n, R, sstride;
     int field_bits, field_scale;
     int eblock;  // energy_block_rows(n): the energies are summed in the per-replica kernels' order
+    // sga_set_dense_shared (finish pass only): replica r of this tile is global replica replica_base + r and reads the h
+    // of model (replica_base + r) / reps_per_model -- a tile may straddle models; 0 = one model
+    int reps_per_model, replica_base;
 };
 // mode 0: int8 J (i8 MFMA) | 1: fp32 J with exact fp32 sums (f32 MFMA) | 2: fp32 J, real valued (f64 MFMA)
 hipError_t launch_fields_dense(const FieldsArgs &a, int mode, hipStream_t st);
@@ -461,7 +465,8 @@ size_t sweep_dense_lds_bytes(long long ld, int table_m, bool acc64);
 // multiple of 1/2
 hipError_t launch_dense_row_nnz(const float *J, long long ld, int n, int *nnz, hipStream_t st);  // sparse matrices given dense
 hipError_t launch_dense_to_csr(const float *J, long long ld, int n, const int *rowptr, int *col, float *val, hipStream_t st);
+// (n_h > 1: a shared matrix -- `rows` = n rows, each against its n_h fields h[m * rows + i]; the words of the stack)
 hipError_t launch_dense_row_abs_max(const float *J, long long ldJ, const float *h, long long rows,
-                                    int n, unsigned int *out, hipStream_t st);
+                                    int n, unsigned int *out, hipStream_t st, int n_h = 1);
 
 }  // namespace sga

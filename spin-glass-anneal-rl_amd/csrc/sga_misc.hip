@@ -83,9 +83,11 @@ hipError_t launch_scan_values(const float *v, long long rows, long long cols, lo
 
 __global__ void __launch_bounds__(256) dense_row_abs_max_kernel(const float *__restrict__ J,
                                                                 long long ldJ,
-                                                                const float *__restrict__ h, int n,
+                                                                const float *__restrict__ h, int n, int n_h,
                                                                 unsigned int *out) {
-    // one workgroup per stacked row (gridDim.x = n_models * n), n columns each
+    // one workgroup per stacked row (gridDim.x = n_models * n), n columns each, against the row's one field (n_h = 1);
+    // a shared matrix (sga_set_dense_shared): gridDim.x = n rows, each against its n_h fields h[m][i] -- the words a
+    // stack of n_h copies of J would give, the row's sum formed once
     __shared__ double red[4];
     __shared__ int bad[4];
     const int i = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -111,21 +113,26 @@ __global__ void __launch_bounds__(256) dense_row_abs_max_kernel(const float *__r
     }
     __syncthreads();
     if (tid == 0) {
-        const float hi = h[i];
-        const float row = (float)((red[0] + red[1]) + (red[2] + red[3]) + (double)__builtin_fabsf(hi));
-        atomicMax(&out[0], __builtin_bit_cast(unsigned int, row));  // non-negative: bit order = value order
+        const double rowj = (red[0] + red[1]) + (red[2] + red[3]);
         const int jbits = bad[0] | bad[1] | bad[2] | bad[3];
         if (jbits & 1) atomicOr(&out[1], 1u);  // some J not an integer
-        if ((jbits & SCAN_NON_FINITE) || (__float_as_uint(hi) & 0x7F800000u) == 0x7F800000u)
-            atomicOr(&out[1], (unsigned int)SCAN_NON_FINITE);           // some J or h is NaN or +-Inf
-        if (hi != __builtin_rintf(hi)) atomicOr(&out[1], 2u);           // some h not an integer
-        if (2.0f * hi != __builtin_rintf(2.0f * hi)) atomicOr(&out[1], 4u);  // ... not even a multiple of 1/2
+        if (jbits & SCAN_NON_FINITE) atomicOr(&out[1], (unsigned int)SCAN_NON_FINITE);  // some J is NaN or +-Inf
+        for (int m = 0; m < n_h; ++m) {
+            const float hi = h[(long long)m * gridDim.x + i];
+            const float row = (float)(rowj + (double)__builtin_fabsf(hi));
+            atomicMax(&out[0], __builtin_bit_cast(unsigned int, row));  // non-negative: bit order = value order
+            if ((__float_as_uint(hi) & 0x7F800000u) == 0x7F800000u)
+                atomicOr(&out[1], (unsigned int)SCAN_NON_FINITE);           // some h is NaN or +-Inf
+            if (hi != __builtin_rintf(hi)) atomicOr(&out[1], 2u);           // some h not an integer
+            if (2.0f * hi != __builtin_rintf(2.0f * hi)) atomicOr(&out[1], 4u);  // ... not even a multiple of 1/2
+        }
     }
 }
 hipError_t launch_dense_row_abs_max(const float *J, long long ldJ, const float *h, long long rows,
-                                    int n, unsigned int *out, hipStream_t st) {
+                                    int n, unsigned int *out, hipStream_t st, int n_h) {
+    if (n_h < 1) return hipErrorInvalidValue;
     hipLaunchKernelGGL(dense_row_abs_max_kernel, dim3((unsigned)rows), dim3(256), 0, st, J, ldJ, h,
-                       n, out);
+                       n, n_h, out);
     return hipGetLastError();
 }
 

@@ -37,7 +37,7 @@ const char *const NON_FINITE_MSG = "non-finite value (NaN or +-Inf) in J or h";
 // layout(s): rows packed to 128 bytes, not padded to the kernel's whole chunks (2.4 % fewer bytes
 // per attempt at n = 10^4); lanes past a row's end re-read its first granule.
 int pack_dense(sga_engine *e, const float *src, long long ld_src) {
-    const long long rows = (long long)e->n_models * e->n;
+    const long long rows = e->shared_j ? e->n : (long long)e->n_models * e->n;  // (one shared matrix: its n rows)
     const long long elem = e->want_i8 ? 1 : 4;
     const long long ldj = ((long long)e->n * elem + 127) / 128 * 128 / elem;
     const size_t bytes = (size_t)rows * ldj * elem;
@@ -51,8 +51,17 @@ int pack_dense(sga_engine *e, const float *src, long long ld_src) {
         // it pulls through the cache hierarchy); the kernel masks the lanes past a row's end
         const long long row_bits = t2_row_bits(e->n);
         HIPCHK(hipMalloc(&e->J_bits, sizeof(unsigned int) * 2 * (size_t)e->n * (size_t)(row_bits / 32)));
-        HIPCHK(hipMalloc(&e->row_nnz, sizeof(float) * (size_t)e->n));
+        // (row_nnz is read as diag is, at model * n: a shared matrix repeats it per model)
+        HIPCHK(hipMalloc(&e->row_nnz, sizeof(float) * (size_t)e->n * (size_t)(e->shared_j ? e->n_models : 1)));
         HIPCHK(sga::launch_repack_tern2(src, ld_src, e->n, e->J_bits, row_bits, e->row_nnz, e->stream));
+    }
+    // one shared matrix: diag (and row_nnz) once more per model -- the kernels index them as a stacked batch's, no
+    // branch in their loops
+    for (int m = 1; e->shared_j && m < e->n_models; ++m) {
+        HIPCHK(hipMemcpyAsync(e->diag + (size_t)m * e->n, e->diag, sizeof(float) * (size_t)e->n, hipMemcpyDeviceToDevice, e->stream));
+        if (e->row_nnz)
+            HIPCHK(hipMemcpyAsync(e->row_nnz + (size_t)m * e->n, e->row_nnz, sizeof(float) * (size_t)e->n,
+                                  hipMemcpyDeviceToDevice, e->stream));
     }
     return SGA_OK;
 }
@@ -400,16 +409,13 @@ int route_sparse_dense(sga_engine *e, const float *src, long long ld_src, const 
     return rc;
 }
 
-}  // namespace
-
-extern "C" {
-
-int sga_set_dense(sga_engine *e, const float *J, int64_t ldJ, const float *h, int n, int storage) {
-    return sga_set_dense_batch(e, J, ldJ, h, n, 1, storage);
-}
-
-int sga_set_dense_batch(sga_engine *e, const float *J, int64_t ldJ, const float *h, int n,
-                        int n_models, int storage) {
+// sga_set_dense / sga_set_dense_batch (J: n_models matrices stacked row-wise) / sga_set_dense_shared (shared: J is ONE
+// matrix of n rows, h still [n_models][n]).  A shared problem is scanned, classified and held as the stack of n_models
+// copies of J would be -- the same eight scan words, the same batch-wide verdicts -- except that J is read, packed and
+// kept once, and that what needs the ROWS to be one matrix (bit-planes; row-shared windows and the matrix-core pass,
+// sga_engine.cpp) is open to it.
+int set_dense_common(sga_engine *e, const float *J, int64_t ldJ, const float *h, int n, int n_models, int storage,
+                     bool shared) {
     if (!e) return fail(SGA_ERR_INVALID, "engine is NULL");
     if (!J || !h || n <= 0 || ldJ < n || n_models <= 0)
         return fail(SGA_ERR_INVALID, "bad dense problem arguments");
@@ -425,7 +431,9 @@ int sga_set_dense_batch(sga_engine *e, const float *J, int64_t ldJ, const float 
     e->table_m = 0;
     e->n = n;
     e->n_models = n_models;
-    const long long rows = (long long)n_models * n;
+    e->shared_j = shared && n_models > 1;  // (one model: sga_set_dense in every respect)
+    const long long rows = (long long)n_models * n;            // rows of h and diag
+    const long long j_rows = e->shared_j ? (long long)n : rows;  // rows of J
     // A device matrix is scanned and packed where it lies; a host matrix is staged first.  Either
     // way nothing but the packed layout(s) stays resident (400 MB, not 800, at n = 10^4 fp32).
     const float *src = J;
@@ -435,9 +443,9 @@ int sga_set_dense_batch(sga_engine *e, const float *J, int64_t ldJ, const float 
         ~Staged() { dev_free(p); }
     } staged;
     if (!is_device_ptr(J)) {
-        HIPCHK(hipMalloc(&staged.p, sizeof(float) * (size_t)rows * n));
+        HIPCHK(hipMalloc(&staged.p, sizeof(float) * (size_t)j_rows * n));
         HIPCHK(hipMemcpy2DAsync(staged.p, sizeof(float) * (size_t)n, J, sizeof(float) * (size_t)ldJ,
-                                sizeof(float) * (size_t)n, (size_t)rows, hipMemcpyHostToDevice, e->stream));
+                                sizeof(float) * (size_t)n, (size_t)j_rows, hipMemcpyHostToDevice, e->stream));
         src = staged.p;
         ld_src = n;
     }
@@ -451,9 +459,10 @@ int sga_set_dense_batch(sga_engine *e, const float *J, int64_t ldJ, const float 
     unsigned int *uflags = reinterpret_cast<unsigned int *>(flags) + 2;
     int hflags[8] = {1, 1, 0, 1, 1, 0, 0, 0};  // ([7]: max |J_ij| as float bits, launch_dense_row_abs_max)
     HIPCHK(hipMemsetAsync(flags, 0, 8 * sizeof(int), e->stream));
-    HIPCHK(sga::launch_scan_values(src, rows, n, ld_src, flags, e->stream));
-    HIPCHK(sga::launch_dense_row_abs_max(src, ld_src, e->h, rows, n, uflags, e->stream));
-    HIPCHK(sga::launch_check_symmetric(src, ld_src, rows, n, flags + 4, e->stream));
+    // (a shared matrix: the J words from one pass over its n rows, the h-dependent ones over all n_models * n fields)
+    HIPCHK(sga::launch_scan_values(src, j_rows, n, ld_src, flags, e->stream));
+    HIPCHK(sga::launch_dense_row_abs_max(src, ld_src, e->h, j_rows, n, uflags, e->stream, e->shared_j ? n_models : 1));
+    HIPCHK(sga::launch_check_symmetric(src, ld_src, j_rows, n, flags + 4, e->stream));
     HIPCHK(hipMemcpyAsync(hflags, flags, sizeof(hflags), hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
     if (hflags[3] & sga::SCAN_NON_FINITE) {
@@ -462,7 +471,9 @@ int sga_set_dense_batch(sga_engine *e, const float *J, int64_t ldJ, const float 
     }
     e->scan_words.assign(hflags, hflags + 8);
     e->scan_per_model = 8;
-    const sga_classify::DenseClass c = sga_classify::classify_dense(hflags, n, n_models, storage, e->opt[OPT_FORCE_DENSE_CANON] != 0);
+    // (storage is a matter of the matrices held: a shared problem holds one)
+    const sga_classify::DenseClass c =
+        sga_classify::classify_dense(hflags, n, e->shared_j ? 1 : n_models, storage, e->opt[OPT_FORCE_DENSE_CANON] != 0);
     e->consistent_dE = c.consistent_dE;
     if ((storage == SGA_J_I8 && !c.fits_i8) || (storage == SGA_J_T2 && !c.ternary)) {
         e->free_problem();  // (no half-set problem: n, h and the scan words are this call's already)
@@ -516,6 +527,23 @@ int sga_set_dense_batch(sga_engine *e, const float *J, int64_t ldJ, const float 
     // the source (the caller's buffer, or the staging copy about to be released) is done with
     HIPCHK(hipStreamSynchronize(e->stream));
     return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sga_set_dense(sga_engine *e, const float *J, int64_t ldJ, const float *h, int n, int storage) {
+    return set_dense_common(e, J, ldJ, h, n, 1, storage, false);
+}
+
+int sga_set_dense_batch(sga_engine *e, const float *J, int64_t ldJ, const float *h, int n,
+                        int n_models, int storage) {
+    return set_dense_common(e, J, ldJ, h, n, n_models, storage, false);
+}
+
+int sga_set_dense_shared(sga_engine *e, const float *J, int64_t ldJ, const float *H, int n, int n_models, int storage) {
+    return set_dense_common(e, J, ldJ, H, n, n_models, storage, true);
 }
 
 int sga_set_csr(sga_engine *e, const int32_t *rowptr, const int32_t *colidx, const float *val,

@@ -679,10 +679,15 @@ std::string explain(const Query &q0) {
                       t2 ? "t2" : (i8 ? "i8" : "f32"), i8 ? "i32" : (q.acc == 0 ? "f32" : (q.acc == 2 ? "f64-canonical" : "f64-exact")),
                       W, C, streaming ? "(streaming)" : "", g.ld, la, t2 ? "sweep_dense_t2_kernel" : "sweep_dense_kernel");
         out = buf;
+        if (q.shared_j && q.n_models > 1) {  // sga_set_dense_shared: one matrix under n_models field vectors
+            std::snprintf(buf, sizeof(buf), " shared-J models=%d", q.n_models);
+            out += buf;
+        }
         // option "row_shared" = 1 forces the row-shared windows (sweep_dense_rs.hip) where the problem admits them:
-        // one model, integer J and h with exact fp32 sums, symmetric with a zero diagonal (clf_ok), Metropolis look-ahead
-        // allowed (the default 2 leaves the form to sga_autotune, which a query does not know about)
-        if (q.opt[OPT_ROW_SHARED] == 1 && q.field_cache == SGA_FIELD_CACHE_OFF && q.n_models == 1 && q.table_m > 0 &&
+        // one matrix (one model, or shared_j: the traits are then the batch's), integer J and h with exact fp32 sums,
+        // symmetric with a zero diagonal (clf_ok), Metropolis look-ahead allowed (the default 2 leaves the form to
+        // sga_autotune, which a query does not know about)
+        if (q.opt[OPT_ROW_SHARED] == 1 && q.field_cache == SGA_FIELD_CACHE_OFF && (q.n_models == 1 || q.shared_j) && q.table_m > 0 &&
             q.clf_ok && (q.acc == 0 || i8) && q.opt[OPT_LOOK_AHEAD] != 0 && q.opt[OPT_FORCE_GENERAL] == 0)
             out += " sweep=row-shared(W=1024)";
         q.sstride = (int)g.ld;

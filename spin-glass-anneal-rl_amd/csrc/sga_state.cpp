@@ -388,9 +388,9 @@ int sga_describe(sga_engine *e, char *buf, int buflen) {
                       e->big ? "lds-bits" : "lds-int8");
     else
         std::snprintf(tmp, sizeof(tmp),
-                      "dense n=%d models=%d storage=%s acc=%s R=%d waves_per_replica=%d "
+                      "dense n=%d %smodels=%d storage=%s acc=%s R=%d waves_per_replica=%d "
                       "chunks_per_wave=%d%s ld=%lld row_bytes=%lld table_m=%d look_ahead=%d",
-                      e->n, e->n_models, e->use_t2 ? "t2" : (e->want_i8 ? "i8" : "f32"),
+                      e->n, e->shared_j ? "shared-J " : "", e->n_models, e->use_t2 ? "t2" : (e->want_i8 ? "i8" : "f32"),
                       e->want_i8 ? "i32" : (e->acc64 ? (e->acc_canon ? "f64-canonical" : "f64-exact") : "f32"), e->R,
                       e->use_t2 ? e->waves_t2 : e->waves, e->use_t2 ? e->cpw_t2 : e->cpw,
                       (e->use_t2 ? e->cpw_t2 > sga::T2_MAX_CPW : e->cpw > sga::MAX_CPW) ? "(streaming)" : "", e->ld,
@@ -525,7 +525,8 @@ int sga_problem_checksum(sga_engine *e, uint64_t *out) {
         HIPCHK(sga::launch_checksum(e->rowptr64, 8ll * (rows + 1), d, e->stream));
         if (e->ragged) HIPCHK(sga::launch_checksum(e->d_models, 8ll * e->n_models, d, e->stream));  // the models' sizes
     } else {
-        HIPCHK(sga::launch_checksum(e->J_packed, (long long)e->n_models * e->n * e->ldj * (e->want_i8 ? 1 : 4), d,
+        // (sga_set_dense_shared: the one matrix once, every model's h below)
+        HIPCHK(sga::launch_checksum(e->J_packed, (long long)(e->shared_j ? 1 : e->n_models) * e->n * e->ldj * (e->want_i8 ? 1 : 4), d,
                                     e->stream));
     }
     HIPCHK(sga::launch_checksum(e->h, e->ragged ? 4ll * e->n_rows : 4ll * e->n * (e->implicit() ? 1 : e->n_models), d + 1, e->stream));

@@ -219,7 +219,7 @@ hipError_t launch_dense_fields_seed_fx_batch(const void *J, bool j_is_i8, long l
                                              int reps_per_model, void *D, long long ldf, int field_bits, int k, hipStream_t st) {
     const size_t lds = (size_t)CLFX_SEED_REPS * (size_t)((ldj + 31) / 32) * 4;
     if (lds > 160 * 1024 || (field_bits != 32 && field_bits != 64) || ldf < n || ldj < n || sstride < n || R <= 0 ||
-        reps_per_model <= 0 || (ldj * (j_is_i8 ? 1 : 4)) % 16 != 0 || model_stride_j < (long long)n * ldj || (j_is_i8 && k != 0))
+        reps_per_model <= 0 || (ldj * (j_is_i8 ? 1 : 4)) % 16 != 0 || (model_stride_j != 0 && model_stride_j < (long long)n * ldj) || (j_is_i8 && k != 0))  // (stride 0: one shared matrix)
         return hipErrorInvalidValue;
     // global groups [group0, group1] hold the local replicas [replica0, replica0 + R)
     const int gpm = (reps_per_model + CLFX_SEED_REPS - 1) / CLFX_SEED_REPS;
@@ -462,7 +462,7 @@ __global__ void __launch_bounds__(64 * CLF_MAX_WAVES) sweep_clf_fx_kernel(const 
 bool sweep_clf_fx_applies(const SweepArgs &a, bool j_is_i8) {
     return a.rule != SGA_RULE_WOLFF && a.fields && (a.field_bits == 32 || a.field_bits == 64) && a.ldf >= a.ldj &&
            a.ldf % 128 == 0 && a.sstride % 32 == 0 && a.sstride >= a.n && a.table_m == 0 && !(j_is_i8 && a.field_scale != 0) &&
-           a.reps_per_model >= 0 && (a.reps_per_model == 0 || a.model_stride_j >= (long long)a.n * a.ldj) &&
+           a.reps_per_model >= 0 && (a.reps_per_model == 0 || a.model_stride_j == 0 || a.model_stride_j >= (long long)a.n * a.ldj) &&
            sweep_clf_fx_lds_bytes(a.ldf, a.field_bits, a.sstride) <= 160 * 1024;
 }
 

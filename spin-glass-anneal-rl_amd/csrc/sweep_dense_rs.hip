@@ -18,6 +18,13 @@
 // J and h are integer valued with every partial sum below 2^24 (the look-ahead form's proof): the base sums and the
 // corrected fields are exactly the fp32 row sums of the one-update-at-a-time chain, the accept rule is the table
 // form's, and every decision, energy, spin and counter is bit-identical.  No field outlives its window.
+// Many field vectors over ONE matrix (sga_set_dense_shared, a.reps_per_model > 0): plan, fields, planes and corrections
+// know J and the replicas' spins only, so they run unchanged -- a (window, site) bucket holds the proposals of every
+// replica of every model, and the row is read once for all of them.  h enters in the chain alone: a wave resolves its
+// replica's model once and reads that model's h.  The bound above is then asked of the batch: the set-time scan takes
+// max (sum_j |J_ij| + |h_mi|) over every model m and site i (a.table_m, one accept table for the batch), so every
+// partial sum of every model stays below 2^24 with the batch-wide max of |h|, and each model walks the chain of a
+// one-model engine holding (J, h_m) -- whose own, smaller table_m tabulates the same values expf_det(-2 q / T).
 // The window plan -- which (replica, update) proposes which site -- is one counting sort per sweep, histogrammed in
 // LDS per (window, group of replicas): no atomic of it reaches memory.
 #include <type_traits>
@@ -369,6 +376,10 @@ __global__ void __launch_bounds__(64) rs_chain_kernel(const SweepArgs a, RowShar
     const double T = a.sched ? a.sched[k * a.sched_ss + r * a.sched_rs] : a.rep_temp[r];
     int8_t *srow = a.spins + (long long)r * a.sstride;
     const int *base = p.base + (long long)r * W;
+    // the h of this replica's model (one matrix, many field vectors); resolved once, wave-uniform
+    const float *hvec = a.h;
+    if (a.reps_per_model > 0)
+        hvec += (long long)__builtin_amdgcn_readfirstlane((int)((a.replica0 + (uint32_t)r) / (uint32_t)a.reps_per_model)) * n;
     int site[NB], s[NB];
     float f[NB], hh[NB], u[NB];
 #pragma unroll
@@ -380,7 +391,7 @@ __global__ void __launch_bounds__(64) rs_chain_kernel(const SweepArgs a, RowShar
         if (valid) rs_update(a, r, k, t0 + tw, site[b], ub);
         u[b] = (float)ub * 0x1.0p-24f;
         f[b] = valid ? (float)base[tw] : 0.0f;
-        hh[b] = a.h[site[b]];
+        hh[b] = hvec[site[b]];
         s[b] = srow[site[b]];
     }
     double E = a.energy[r];
@@ -534,6 +545,8 @@ hipError_t launch_rs_build_planes(const void *J, bool j_is_i8, long long ldj, in
 }
 
 hipError_t launch_sweep_dense_rs(const SweepArgs &a, const RowSharedPlan &p, bool j_is_i8, hipStream_t st) {
+    // (many models: only over one shared matrix -- the plan buckets proposals by site, whatever the replica's model)
+    if (a.reps_per_model < 0 || (a.reps_per_model > 0 && a.model_stride_j != 0)) return hipErrorInvalidValue;
     if (a.rep_list || a.R <= 0 || a.n <= 0 || (p.W != 256 && p.W != 512 && p.W != 1024) || (1 << p.log_w) != p.W)
         return hipErrorInvalidValue;
     if (p.log_rg < 0 || p.n_groups != (a.R + (1 << p.log_rg) - 1) >> p.log_rg || (p.jp && !p.jabs) || !p.tot)

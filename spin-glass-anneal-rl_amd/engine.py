@@ -288,6 +288,38 @@ class AnnealEngine:
         self._sizes = None
         self.n, self.R, self.n_models = n, 0, M
 
+    def set_dense_shared(self, J, H, storage: str = "auto"):
+        """One coupling matrix under many field vectors (sga_set_dense_shared): J [n, n], H [M, n] (numpy or torch, host
+        or device).  The engine behaves as after set_dense_batch on J tiled M times -- replicas split evenly over the M
+        models, one ladder per model -- but holds J once, serves storage="t2" and opens the row-shared windows and the
+        matrix-core energy pass to the batch."""
+        sel = {"auto": N.J_AUTO, "f32": N.J_F32, "i8": N.J_I8, "t2": N.J_T2}[storage]
+        if _is_tensor(J):
+            if J.dim() != 2 or J.shape[0] != J.shape[1]:
+                raise AnnealingError("shared couplings must be a square matrix [n, n]")
+            Jt = J.detach()
+            if Jt.dtype != torch.float32:
+                Jt = Jt.float()
+            if Jt.stride(1) != 1:
+                Jt = Jt.contiguous()
+            _producer_done(Jt)
+            n, ld, jp, keep = Jt.shape[0], Jt.stride(0), C.c_void_p(Jt.data_ptr()), Jt
+        else:
+            Ja = np.ascontiguousarray(J, dtype=np.float32)
+            if Ja.ndim != 2 or Ja.shape[0] != Ja.shape[1]:
+                raise AnnealingError("shared couplings must be a square matrix [n, n]")
+            n, ld, jp, keep = Ja.shape[0], Ja.shape[1], Ja.ctypes.data_as(C.c_void_p), Ja
+        if not _is_tensor(H):
+            H = np.asarray(H, dtype=np.float32)
+        if H.ndim != 2 or H.shape[1] != n or H.shape[0] < 1:
+            raise AnnealingError("shared-coupling fields must be [M, n]")
+        M = int(H.shape[0])
+        hp, hk = _buf(H, np.float32, "float32")
+        N.check(self._lib.sga_set_dense_shared(self._h, jp, int(ld), hp, int(n), M, sel), "sga_set_dense_shared")
+        del keep, hk
+        self._sizes = None
+        self.n, self.R, self.n_models = n, 0, M
+
     def set_csr(self, rowptr, colidx, val, h):
         """CSR couplings (both triangles).  int64 `rowptr` (numpy / torch) is passed through as
         64-bit extents -- required once nnz >= 2^31 -- anything else is taken as int32."""
