@@ -85,6 +85,31 @@ def one_graph_many_fields():
           f"{time.time() - t:.3f} s\n  engine: {bp.last_description}")
 
 
+def one_sparse_graph_many_fields(L=12, n_fields=8, n_replicas=4):
+    """A random-field scan over one 3-D +-J lattice: the CSR rows go to the engine once (AnnealEngine.set_csr_shared),
+    each model is a field vector; every model walks the chain a one-model engine would walk."""
+    from spin_glass_anneal_rl_amd import AnnealEngine
+    rs = np.random.RandomState(2)
+    idx = np.arange(L ** 3).reshape(L, L, L)
+    J = np.zeros((L ** 3, L ** 3), np.float32)
+    for ax in range(3):
+        a, b = idx.ravel(), np.roll(idx, -1, axis=ax).ravel()
+        J[a, b] = J[b, a] = rs.randint(0, 2, a.size) * 2.0 - 1.0
+    rowptr = np.concatenate([[0], np.cumsum((J != 0).sum(1))]).astype(np.int32)
+    colidx = np.concatenate([np.nonzero(r)[0] for r in J]).astype(np.int32)
+    val = J[J != 0].astype(np.float32)
+    H = np.stack([w * rs.choice([-1.0, 1.0], L ** 3) for w in range(n_fields)]).astype(np.float32)  # field strength 0, 1, 2, ...
+    with AnnealEngine(0) as e:
+        e.set_csr_shared(rowptr, colidx, val, H)
+        e.init_replicas(n_fields * n_replicas, seed=5)
+        e.set_ladder(np.tile(np.geomspace(3.0, 0.3, n_replicas), n_fields), n_ladders=n_fields)
+        for _ in range(20):
+            e.sweep(10)
+            e.exchange(count=False)
+        best = [min(e.best(m * n_replicas + j)[0] for j in range(n_replicas)) for m in range(n_fields)]
+        print(f"one lattice, {n_fields} field strengths: best energies {[round(b) for b in best]}\n  engine: {e.describe()}")
+
+
 def travelling_salesman(n_cities=12):
     rs = np.random.RandomState(0)
     xy = rs.rand(n_cities, 2)
@@ -180,6 +205,7 @@ if __name__ == "__main__":
     many_replicas()
     many_models()
     one_graph_many_fields()
+    one_sparse_graph_many_fields()
     travelling_salesman()
     travelling_salesman_without_storing_couplings()
     scheduling_without_storing_couplings()

@@ -80,7 +80,7 @@ typedef struct sga_engine sga_engine;
 int sga_create(int device, sga_engine **out);
 void sga_destroy(sga_engine *e);
 const char *sga_last_error(void);
-int sga_version(void);  /* 1600: sga_set_dense_shared (one coupling matrix, many field vectors; row-shared windows, bit-planes and the matrix-core pass for such batches), sga_route_query.shared_j; 1500: sga_get_scan_summary, and sga_set_dense / sga_set_dense_batch / sga_set_csr / sga_set_csr64 / sga_set_csr_batch refuse a NaN or +-Inf in J or h (SGA_ERR_INVALID, "non-finite"); 1400: option "batch_fixed_point" (fixed-point cached local fields for many-model dense batches); 1300: options "ragged_field_cache" and "clf_fixed_point" together (fixed-point cached local fields for ragged CSR batches); 1200: sga_set_groups_csr (group couplings plus a stored sparse remainder); 1100: option "ragged_field_cache" (cached local fields for ragged CSR batches); 1000: sga_set_groups */
+int sga_version(void);  /* 1700: sga_set_csr_shared (one set of CSR rows, many field vectors: every one-wave-per-replica CSR form for such batches), sga_route_query.shared_j on SGA_ROUTE_CSR queries; 1600: sga_set_dense_shared (one coupling matrix, many field vectors; row-shared windows, bit-planes and the matrix-core pass for such batches), sga_route_query.shared_j; 1500: sga_get_scan_summary, and sga_set_dense / sga_set_dense_batch / sga_set_csr / sga_set_csr64 / sga_set_csr_batch refuse a NaN or +-Inf in J or h (SGA_ERR_INVALID, "non-finite"); 1400: option "batch_fixed_point" (fixed-point cached local fields for many-model dense batches); 1300: options "ragged_field_cache" and "clf_fixed_point" together (fixed-point cached local fields for ragged CSR batches); 1200: sga_set_groups_csr (group couplings plus a stored sparse remainder); 1100: option "ragged_field_cache" (cached local fields for ragged CSR batches); 1000: sga_set_groups */
 /* Run on an existing HIP stream (e.g. torch.cuda.current_stream().cuda_stream); NULL = the
  * engine's own stream (default). */
 int sga_set_stream(sga_engine *e, void *hip_stream);
@@ -193,6 +193,38 @@ int sga_set_csr64(sga_engine *e, const int64_t *rowptr, const int32_t *colidx, c
  *   model (f64-canonical J, unsorted or duplicate rows, a row too long, fields wider than the bound). */
 int sga_set_csr_batch(sga_engine *e, int n_models, const int32_t *n_spins, const int64_t *rowptr,
                       const int32_t *colidx, const float *val, const float *h, int64_t nnz);
+/* ONE set of CSR rows under n_models field vectors (version >= 1700): rowptr / colidx / val as in sga_set_csr, H is
+ * [n_models][n] -- a random-field scan over one lattice, clamped sub-problems folded into h, one MaxCut or scheduling
+ * instance under many penalty or bias settings.  sga_set_csr_batch on the rows written n_models times stores the
+ * entries n_models times and runs the narrow one-update int8 form only; here the rows are checked, classified and
+ * packed ONCE, exactly as sga_set_csr does it (structure checks, duplicates add up, unsorted rows allowed, slots, tail
+ * pad), and every one-wave-per-replica CSR form is served: several updates per step (4 | 8, every row length it
+ * covers, int8 and bit spins), the narrow int8 and narrow bit-spin forms with every single-site rule, site mode and
+ * arithmetic, per-update traces and the pair look-ahead.
+ *   Replicas: global replica g belongs to model g / (R_global / n_models); R_global % n_models != 0 is SGA_ERR_INVALID at
+ *   sga_init_replicas; with a ladder pass n_ladders = n_models; sga_exchange_pairs takes a pair across models as on
+ *   sga_set_dense_shared; sharding through replica0 works, and a shard may begin in the middle of a model.  Model m
+ *   walks the chain of a one-model sga_set_csr engine holding (J, h_m) started at replica0 = m * (R_global / n_models),
+ *   bit for bit, in whatever form runs: spins, energies, traces, bests, acceptance counters, exchange decisions.
+ *   Batch-wide: the accumulation class comes from J alone; accept table, its scale and "covers" come from J and ALL of
+ *   H -- row bound max_i (sum_j |J_ij| + max_m |h_mi|), scale 2 as soon as any h_m has a half-integer, no table as soon
+ *   as any h_m is off the half-integers (an exact sum stays exact in a wider class, and a table entry stands for the
+ *   same dE at any scale: DESIGN.md 4.2d).
+ *   sga_get_scan_summary: model 0 only, the 11 CSR words with [2], [6] over all of H.  sga_problem_checksum: the layout
+ *   once, all of H, and n_models.  sga_describe: the one-model CSR line with "shared-J models=M"; sga_explain_route the
+ *   same from a query with kind = SGA_ROUTE_CSR, n_models = M, shared_j = 1.  Energies, sga_local_fields, sga_flip,
+ *   sga_update, export / import (into an engine with the same n_models only), sga_snapshot, stats and timing work.
+ *   SGA_ERR_UNSUPPORTED, each message starting "shared-coupling CSR batches": the one-replica-per-workgroup forms, whose
+ *   row records carry one field per row -- a problem that fits no one-wave-per-replica form, sga_set_tuning with
+ *   waves_per_replica > 1, SGA_CSR_STORAGE_PACKED --, sga_set_field_cache(ON) (AUTO streams), the Wolff rule,
+ *   sga_autotune, and a layout that needs 64-bit extents (there is no 64-bit variant).
+ *   A NaN or +-Inf in val or H: SGA_ERR_INVALID ("non-finite").  What the caller can get wrong -- extents, a column out
+ *   of range, a non-finite value -- is refused BEFORE the engine lets go of the problem it holds: after such a refusal
+ *   the previous problem and its replicas are in place.  (A device or memory failure later in the call leaves the engine
+ *   without a problem, as the other setters do.)
+ *   n_models = 1 is sga_set_csr: same kernels, same sga_describe line. */
+int sga_set_csr_shared(sga_engine *e, const int32_t *rowptr, const int32_t *colidx, const float *val,
+                       const float *H /* [n_models][n] */, int n, int64_t nnz, int n_models);
 /* model m of a ragged batch: its spins and, once replicas exist, its first global replica and replica count */
 int sga_get_batch_model(sga_engine *e, int m, int *n_spins, int *first_replica, int *n_replicas);
 
@@ -636,7 +668,7 @@ typedef struct sga_route_query {
     int32_t n_cities;     /* TSP */
     /* as laid out (0 = derive from the rest) */
     int32_t sstride;      /* spin stride of the replicas */
-    int32_t shared_j;     /* dense batches: 1 = one coupling matrix for every model (sga_set_dense_shared; version >= 1600) */
+    int32_t shared_j;     /* batches (n_models > 1): 1 = one coupling matrix for every model -- SGA_ROUTE_DENSE: sga_set_dense_shared (version >= 1600); SGA_ROUTE_CSR: sga_set_csr_shared (version >= 1700; 0 = a ragged batch) */
     int64_t ldj;          /* dense: row stride of the packed couplings in elements */
     int64_t opt[SGA_ROUTE_MAX_OPTS]; /* option values, index = sga_option_name order */
     /* sga_set_groups (version >= 1000) */

@@ -55,6 +55,7 @@ SYMBOLS = [
     ("sga_set_dense_batch", _i, [_p, _p, _i64, _p, _i, _i, _i]),
     ("sga_set_dense_shared", _i, [_p, _p, _i64, _p, _i, _i, _i]),
     ("sga_set_csr", _i, [_p, _p, _p, _p, _p, _i, _i64]),
+    ("sga_set_csr_shared", _i, [_p, _p, _p, _p, _p, _i, _i64, _i]),
     ("sga_set_csr64", _i, [_p, _p, _p, _p, _p, _i, _i64]),
     ("sga_set_csr_batch", _i, [_p, _i, _p, _p, _p, _p, _p, _i64]),
     ("sga_get_batch_model", _i, [_p, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),

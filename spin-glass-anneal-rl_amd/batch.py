@@ -48,6 +48,14 @@ the same graph under many bias vectors: a policy's proposals, sub-problems with 
 segment is annealed as `process_models_batch` would anneal it on its own (replicas numbered from the segment's first
 model), so a chunk that is one run gives the default path's results field for field but `total_time`.  All engine
 options above act on a shared run as on a stacked batch.
+
+The same switch acts on sparse chunks: a run of two or more CONSECUTIVE sparse models of one size whose coalesced COO
+indices and values are equal (`shared_sparse_runs`: the same tensor object, the same storage, or equal content) goes to
+ONE engine through `set_csr_shared` -- the entries are held once, and the several-updates-per-step and bit-spin CSR
+forms, closed to ragged batches, serve it; what lies between two runs stays on `set_csr_batch`.  Every segment's
+replicas keep the numbers they have in the chunk's one ragged engine (the segment's engine is a shard that starts at
+the segment's first replica), so every result field but `total_time` is the default path's.  A segment an engine
+refuses sends the whole chunk down the default path.
 """
 import time
 from dataclasses import dataclass
@@ -78,7 +86,7 @@ class BatchConfig:
     replicas_per_model: int = 1  # build-specific: independent restarts per model, best is kept
     ragged_field_cache: bool = False  # build-specific: sparse chunks serve field_cache "on" / "auto" on the ragged engine
     stacked_fixed_point: bool = False  # build-specific: stacked real-valued batches serve field_cache "on" / "auto" (fixed point)
-    shared_couplings: bool = False  # build-specific: runs of dense models with one coupling matrix go through set_dense_shared
+    shared_couplings: bool = False  # build-specific: runs of models with one coupling matrix go through set_dense_shared / set_csr_shared
 
     def __post_init__(self):
         if self.batch_size <= 0:
@@ -125,6 +133,41 @@ def shared_coupling_runs(models) -> List[tuple]:
     return runs
 
 
+def _same_sparse_couplings(a: torch.Tensor, b: torch.Tensor) -> bool:
+    if a is b:
+        return True
+    if not (a.is_sparse and b.is_sparse) or a.shape != b.shape:
+        return False
+    a, b = a.coalesce(), b.coalesce()
+    ia, ib, va, vb = a.indices(), b.indices(), a.values(), b.values()
+    if ia.shape != ib.shape or va.dtype != vb.dtype:
+        return False
+    if ia.device == ib.device and ia.data_ptr() == ib.data_ptr() and va.data_ptr() == vb.data_ptr():
+        return True  # one storage
+    if ia.device != ib.device:
+        ia, ib, va, vb = ia.cpu(), ib.cpu(), va.detach().cpu(), vb.detach().cpu()
+    return bool(torch.equal(ia, ib)) and bool(torch.equal(va, vb))
+
+
+def shared_sparse_runs(models) -> List[tuple]:
+    """[(start, stop), ...]: the maximal runs models[start:stop] of two or more CONSECUTIVE sparse models of equal
+    n_spins whose coalesced COO indices and values are equal -- the same tensor object, the same storage, or equal
+    content.  A dense model, another size or a differing J ends a run; a run of one is not shared.  Pure: no engine, no
+    GPU needed.  (`shared_coupling_runs` is the dense counterpart and keeps answering [] for sparse models.)"""
+    runs, start = [], 0
+    while start < len(models):
+        stop = start + 1
+        first = models[start]
+        if first.couplings.is_sparse:
+            while (stop < len(models) and models[stop].n_spins == first.n_spins and
+                   _same_sparse_couplings(first.couplings, models[stop].couplings)):
+                stop += 1
+        if stop - start >= 2:
+            runs.append((start, stop))
+        start = stop
+    return runs
+
+
 class BatchProcessor:
     def __init__(self, annealer_config: GPUAnnealerConfig, batch_config: Optional[BatchConfig] = None,
                  device_index: int = 0):
@@ -151,7 +194,7 @@ class BatchProcessor:
         for lo in range(0, len(sparse), bs):
             part = sparse[lo:lo + bs]
             t0 = time.time()
-            out = self._anneal_ragged([models[i] for i in part])
+            out = self._anneal_sparse([models[i] for i in part])
             if out is None:  # refused by the ragged engine: the stacked path, by size
                 for i in part:
                     by_size.setdefault(models[i].n_spins, []).append(i)
@@ -238,11 +281,58 @@ class BatchProcessor:
 
         return self._run(models, set_problem, s0)
 
+    # ------------------------------------------------------------------ a chunk of sparse models (any sizes)
+    def _anneal_sparse(self, models: List[IsingModel]) -> Optional[List[AnnealingResult]]:
+        runs = shared_sparse_runs(models) if self.batch_config.shared_couplings else []
+        if not runs:
+            return self._anneal_ragged(models)
+        out: List[AnnealingResult] = []
+        at = 0
+        for start, stop in runs + [(len(models), len(models))]:
+            seg = self._anneal_ragged(models[at:start], first=at) if start > at else []
+            if seg is not None and stop > start:
+                run = self._anneal_shared_csr(models[start:stop], first=start)
+                seg = None if run is None else seg + run
+            if seg is None:  # a segment refused: the chunk as the default path takes it
+                return self._anneal_ragged(models)
+            out += seg
+            at = stop
+        return out
+
+    def _unsupported_is_none(self, call):
+        try:
+            return call()
+        except AnnealingError as err:
+            if (getattr(err, "details", None) or {}).get("code") == N.ERR_UNSUPPORTED:
+                return None
+            raise
+
+    # ------------------------------------------------------------------ one run over one set of CSR rows
+    def _anneal_shared_csr(self, models: List[IsingModel], first: int) -> Optional[List[AnnealingResult]]:
+        """`first`: models of the chunk before this run.  The engine holds `first` all-zero field vectors in front of the
+        run's and is initialised as the shard that starts at the run's first replica: replica numbers, and with them
+        the random streams, are those of the chunk's one ragged engine.  (Zero fields change no batch-wide quantity.)"""
+        rowptr, colidx, val = coo_to_csr(models[0].couplings)
+        H = np.zeros((first + len(models), models[0].n_spins), np.float32)
+        for i, m in enumerate(models):
+            H[first + i] = m.external_fields.detach().cpu().numpy().astype(np.float32)
+        s0 = np.stack([m.spins_int8() for m in models])  # [M, n]
+        self.last_description = None
+
+        def set_problem(eng):
+            eng.set_csr_shared(rowptr, colidx, val, H)
+            self.last_description = eng.describe()  # names the kind: "csr n=... shared-J models=M ..."
+
+        return self._unsupported_is_none(lambda: self._run(models, set_problem, s0, first))
+
     # ------------------------------------------------------------------ one ragged run (sparse models, any sizes)
-    def _anneal_ragged(self, models: List[IsingModel]) -> Optional[List[AnnealingResult]]:
-        """None when the ragged engine refuses the chunk (SGA_ERR_UNSUPPORTED: diagonal / asymmetric J)."""
-        problems = [coo_to_csr(m.couplings) + (m.external_fields.detach().cpu().numpy().astype(np.float32),)
-                    for m in models]
+    def _anneal_ragged(self, models: List[IsingModel], first: int = 0) -> Optional[List[AnnealingResult]]:
+        """None when the ragged engine refuses the chunk (SGA_ERR_UNSUPPORTED: diagonal / asymmetric J).
+        `first` > 0 (a segment between two shared runs): that many one-spin models without couplings stand in front, and
+        the engine is the shard behind them -- the segment's replicas keep their numbers in the chunk."""
+        empty = (np.zeros(2, np.int32), np.zeros(0, np.int32), np.zeros(0, np.float32), np.zeros(1, np.float32))
+        problems = [empty] * first + [coo_to_csr(m.couplings) + (m.external_fields.detach().cpu().numpy().astype(np.float32),)
+                                      for m in models]
         n_max = max(m.n_spins for m in models)
         s0 = np.zeros((len(models), n_max), np.int8)  # [M, n_max], zero padded
         for i, m in enumerate(models):
@@ -254,14 +344,9 @@ class BatchProcessor:
                     eng.set_option("clf_fixed_point", 1)
             eng.set_csr_batch(problems)
 
-        try:
-            return self._run(models, set_problem, s0)
-        except AnnealingError as err:
-            if (getattr(err, "details", None) or {}).get("code") == N.ERR_UNSUPPORTED:
-                return None
-            raise
+        return self._unsupported_is_none(lambda: self._run(models, set_problem, s0, first))
 
-    def _run(self, models: List[IsingModel], set_problem, s0_models: np.ndarray) -> List[AnnealingResult]:
+    def _run(self, models: List[IsingModel], set_problem, s0_models: np.ndarray, first: int = 0) -> List[AnnealingResult]:
         cfg, k = self.annealer_config, self.batch_config.replicas_per_model
         M = len(models)
         t0 = time.time()
@@ -275,7 +360,9 @@ class BatchProcessor:
         with AnnealEngine(self.device_index) as eng:
             eng.set_field_cache(cfg.field_cache)  # (before the couplings, as GPUAnnealer.anneal)
             set_problem(eng)
-            eng.init_replicas(M * k, seed=fresh_seed(cfg.random_seed), s0=s0)
+            # (first > 0: the shard behind `first` models of the engine's batch, sparse segments only)
+            shard = dict(R_global=(first + M) * k, replica0=first * k) if first else {}
+            eng.init_replicas(M * k, seed=fresh_seed(cfg.random_seed), s0=s0, **shard)
             e0 = eng.energies().reshape(M, k).min(1)
             for m in range(M):
                 hist_e[m].append(float(e0[m]))

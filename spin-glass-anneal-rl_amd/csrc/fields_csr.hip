@@ -37,10 +37,14 @@ __global__ void __launch_bounds__(256) transpose_spin_bits_kernel(const int8_t *
 }
 
 // hs[r] = sum_i h_i s_ri in fp64, in the per-replica kernels' order (sga_kernels.h, energy_block_rows)
-__global__ void __launch_bounds__(256) field_dot_kernel(const float *__restrict__ h, const int8_t *__restrict__ spins,
-                                                        int sstride, int n, int eblock, double *__restrict__ hs) {
+// (reps_per_model > 0, sga_set_csr_shared: h is [n_models][n] and replica r reads its model's -- X = sum_i mv_i s_i above
+//  does not involve h, so the pass over the entries serves replicas of any models in one lane)
+__global__ void __launch_bounds__(256) field_dot_kernel(const float *__restrict__ h_all, const int8_t *__restrict__ spins,
+                                                        int sstride, int n, int eblock, int reps_per_model, int replica_base,
+                                                        double *__restrict__ hs) {
     __shared__ double ce[4 * ENERGY_MAX_BLOCKS], ch[4 * ENERGY_MAX_BLOCKS];
     const int r = blockIdx.x;
+    const float *h = h_all + (long long)(reps_per_model > 0 ? (replica_base + r) / reps_per_model : 0) * n;
     const int8_t *s = spins + (long long)r * sstride;
     double unused, acc;
     energy_canonical_sums(
@@ -110,13 +114,15 @@ size_t csr_energy_scratch_bytes(int n, int R, int groups) {
 
 // scratch: [n][RW] spin-bit words | [groups][32 RW] partial sums | [R] field dots
 hipError_t launch_energy_csr_all(const long long *rowptr, const int2 *cv, const float *h, const int8_t *spins, int sstride,
-                                 int n, int R, int groups, bool exact32, void *scratch, double *energy, hipStream_t st) {
+                                 int n, int R, int groups, bool exact32, void *scratch, double *energy, hipStream_t st,
+                                 int reps_per_model, int replica_base) {
     const int RW = (R + 31) / 32;
     unsigned int *sb = static_cast<unsigned int *>(scratch);
     double *partial = reinterpret_cast<double *>(sb + (((size_t)n * RW + 1) & ~(size_t)1));
     double *hs = partial + (size_t)groups * 32 * RW;
     hipLaunchKernelGGL(transpose_spin_bits_kernel, dim3((n + 255) / 256, RW), dim3(256), 0, st, spins, sstride, n, R, RW, sb);
-    hipLaunchKernelGGL(field_dot_kernel, dim3(R), dim3(256), 0, st, h, spins, sstride, n, energy_block_rows(n), hs);
+    hipLaunchKernelGGL(field_dot_kernel, dim3(R), dim3(256), 0, st, h, spins, sstride, n, energy_block_rows(n),
+                       reps_per_model, replica_base, hs);
     CsrEnergyArgs a{rowptr, cv, sb, partial, n, R, RW, groups};
     const long long threads = (long long)groups * RW;
     const dim3 grid((unsigned)((threads + 255) / 256));

@@ -124,6 +124,9 @@ int sga_autotune(sga_engine *e, double *best_ms_per_sweep) {
     if (e->R <= 0) return fail(SGA_ERR_INVALID, "no replicas (call sga_init_replicas)");
     if (best_ms_per_sweep) *best_ms_per_sweep = 0.0;
     if (e->ragged) return fail(SGA_ERR_UNSUPPORTED, "sga_autotune: ragged CSR batches have one form (nothing to tune)");
+    if (e->csr && e->shared_j)  // (its candidates are the one-replica-per-workgroup forms, which these batches do not run)
+        return fail(SGA_ERR_UNSUPPORTED, "shared-coupling CSR batches: sga_autotune is not served (they run the "
+                                         "one-wave-per-replica forms only)");
     if (e->groups)
         return fail(SGA_ERR_UNSUPPORTED, "sga_autotune: sga_set_groups problems run one form (sga_set_tuning picks its waves per replica)");
     if (e->tsp) return SGA_OK;

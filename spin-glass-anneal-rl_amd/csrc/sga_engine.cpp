@@ -323,7 +323,8 @@ int recompute_energy_range(sga_engine *e, int r0, int count) {
         if (e->csr_energy.reserve(sga::csr_energy_scratch_bytes(e->n, count, groups)) == hipSuccess) {
             const bool exact32 = e->csr_acc == sga::CSR_ACC_F32_TABLE || e->csr_acc == sga::CSR_ACC_F32;
             HIPCHK(sga::launch_energy_csr_all(e->rowptr64, e->cv, e->h, e->spins + (long long)r0 * e->sstride, e->sstride,
-                                              e->n, count, groups, exact32, e->csr_energy.ptr, e->energy + r0, e->stream));
+                                              e->n, count, groups, exact32, e->csr_energy.ptr, e->energy + r0, e->stream,
+                                              e->shared_j ? e->Rg / e->n_models : 0, e->replica0 + r0));
             return SGA_OK;
         }
         (void)hipGetLastError();  // no room for the transposed spin bits / partial sums: one pass per replica instead
@@ -409,7 +410,7 @@ int ensure_packed(sga_engine *e) {
 extern "C" {
 
 const char *sga_last_error(void) { return g_last_error.c_str(); }
-int sga_version(void) { return 1600; }  // + sga_set_dense_shared (one coupling matrix, many field vectors), sga_route_query.shared_j  // 1500: + sga_get_scan_summary; the dense and CSR setters refuse non-finite J / h  // 1400: + option "batch_fixed_point": fixed-point cached local fields for many-model dense batches (sweep_clf_fx.hip, MODELS)  // 1300: + options "ragged_field_cache" and "clf_fixed_point" together: fixed-point cached local fields for ragged CSR batches (sweep_clf_csr.hip)  // 1200: + sga_set_groups_csr (group couplings plus a stored sparse remainder, sweep_groups.hip)  // 1100: + option "ragged_field_cache" (cached local fields for ragged CSR batches, sweep_clf_csr.hip)  // 1000: + sga_set_groups (implicit cardinality-group couplings, sweep_groups.hip)  // 900: + cached local fields for many-model dense batches (sga_set_dense_batch)  // 800: + option "clf_fixed_point" over dense couplings (sweep_clf_fx.hip)  // 700: + option "clf_fixed_point" (cached fields of real-valued CSR couplings)  // 600: + sga_set_csr_batch / sga_get_batch_model (ragged CSR batches)  // round 5: + sga_explain_route / sga_get_route_query, sga_get_last_kernel, sga_get_autotune_table, ladder-local sga_exchange
+int sga_version(void) { return 1700; }  // + sga_set_csr_shared (one set of CSR rows, many field vectors)  // 1600: + sga_set_dense_shared (one coupling matrix, many field vectors), sga_route_query.shared_j  // 1500: + sga_get_scan_summary; the dense and CSR setters refuse non-finite J / h  // 1400: + option "batch_fixed_point": fixed-point cached local fields for many-model dense batches (sweep_clf_fx.hip, MODELS)  // 1300: + options "ragged_field_cache" and "clf_fixed_point" together: fixed-point cached local fields for ragged CSR batches (sweep_clf_csr.hip)  // 1200: + sga_set_groups_csr (group couplings plus a stored sparse remainder, sweep_groups.hip)  // 1100: + option "ragged_field_cache" (cached local fields for ragged CSR batches, sweep_clf_csr.hip)  // 1000: + sga_set_groups (implicit cardinality-group couplings, sweep_groups.hip)  // 900: + cached local fields for many-model dense batches (sga_set_dense_batch)  // 800: + option "clf_fixed_point" over dense couplings (sweep_clf_fx.hip)  // 700: + option "clf_fixed_point" (cached fields of real-valued CSR couplings)  // 600: + sga_set_csr_batch / sga_get_batch_model (ragged CSR batches)  // round 5: + sga_explain_route / sga_get_route_query, sga_get_last_kernel, sga_get_autotune_table, ladder-local sga_exchange
 
 int sga_create(int device, sga_engine **out) {
     if (!out) return fail(SGA_ERR_INVALID, "out is NULL");
@@ -523,6 +524,13 @@ int sga_set_csr_storage(sga_engine *e, int storage) {
     if (!e) return fail(SGA_ERR_INVALID, "engine is NULL");
     if (storage != SGA_CSR_STORAGE_AUTO && storage != SGA_CSR_STORAGE_F32 && storage != SGA_CSR_STORAGE_PACKED)
         return fail(SGA_ERR_INVALID, "bad CSR storage");
+    // (the problem held is one set of rows under many field vectors: refused here, the setting stays; set before such
+    //  a problem, sga_init_replicas refuses -- sga_route.cpp, csr_shared_form)
+    if (storage == SGA_CSR_STORAGE_PACKED && e->csr && e->shared_j) {
+        sga_route_query q = route_query_of(e);
+        q.storage = storage;
+        return fail(SGA_ERR_UNSUPPORTED, sga_route::csr_shared_form(q).error);
+    }
     e->csr_storage = storage;
     return SGA_OK;
 }
@@ -531,6 +539,11 @@ int sga_set_tuning(sga_engine *e, int waves_per_replica, int sweeps_per_launch) 
     if (!e) return fail(SGA_ERR_INVALID, "engine is NULL");
     if (waves_per_replica < 0 || waves_per_replica > sga::MAX_WAVES || sweeps_per_launch < 0)
         return fail(SGA_ERR_INVALID, "bad tuning values");
+    if (waves_per_replica > 1 && e->csr && e->shared_j) {  // (as sga_set_csr_storage)
+        sga_route_query q = route_query_of(e);
+        q.tune_waves = waves_per_replica;
+        return fail(SGA_ERR_UNSUPPORTED, sga_route::csr_shared_form(q).error);
+    }
     e->tune_waves = e->caller_tune_waves = waves_per_replica;
     e->tune_spl = sweeps_per_launch;
     return SGA_OK;
@@ -542,6 +555,11 @@ int sga_set_field_cache(sga_engine *e, int mode) {
         return fail(SGA_ERR_INVALID, "bad field-cache mode");
     if (mode == SGA_FIELD_CACHE_ON && e->ragged && e->opt[OPT_RAGGED_FIELD_CACHE] == 0)
         return fail(SGA_ERR_UNSUPPORTED, "cached local fields are not built for ragged CSR batches (AUTO runs the streaming form)");
+    if (mode == SGA_FIELD_CACHE_ON && e->csr && e->shared_j) {
+        sga_route_query q = route_query_of(e);
+        q.field_cache = mode;
+        return fail(SGA_ERR_UNSUPPORTED, sga_route::clf_refusal(q));
+    }
     if (mode != e->field_cache) {
         // what an earlier mode learnt about these replicas does not carry over: ON runs every replica on the cached-field
         // kernel (AUTO's per-replica routes would leave some on the row kernels for good), a failed allocation under
@@ -938,6 +956,8 @@ int plan_sweep(sga_engine *e, const SweepCall &c, SweepPlan &p) {
     const bool wolff = e->rule == SGA_RULE_WOLFF;
     if (wolff) {
         if (e->ragged) return fail(SGA_ERR_UNSUPPORTED, "the Wolff rule is not implemented for ragged CSR batches");
+        if (e->csr && e->shared_j)
+            return fail(SGA_ERR_UNSUPPORTED, "shared-coupling CSR batches: the Wolff rule is not implemented for them");
         if (e->tsp) return fail(SGA_ERR_UNSUPPORTED, "the Wolff rule is not implemented for sga_set_tsp problems");
         if (e->groups) return fail(SGA_ERR_UNSUPPORTED, "the Wolff rule is not implemented for sga_set_groups problems");
         if (sga::wolff_lds_bytes(e->n) > 160 * 1024 - 256)
@@ -1184,6 +1204,8 @@ int sga_set_update_rule(sga_engine *e, int rule) {
         return fail(SGA_ERR_UNSUPPORTED, "the Wolff rule is not implemented for sga_set_groups problems");
     if (rule == SGA_RULE_WOLFF && e->ragged)
         return fail(SGA_ERR_UNSUPPORTED, "the Wolff rule is not implemented for ragged CSR batches");
+    if (rule == SGA_RULE_WOLFF && e->csr && e->shared_j)
+        return fail(SGA_ERR_UNSUPPORTED, "shared-coupling CSR batches: the Wolff rule is not implemented for them");
     e->rule = rule;
     return SGA_OK;
 }
@@ -1265,7 +1287,7 @@ static int point_op(sga_engine *e, int r, const int32_t *sites, int count, int o
         a.rowptr = e->rowptr64;
         a.cv = e->cv;
         a.h = e->h + model * e->n;
-        a.diag = e->diag + model * e->n;
+        a.diag = e->diag + (e->csr ? 0 : model * e->n);  // (sga_set_csr_shared: the diagonal is J's, held once)
         if (e->ragged) {  // the model's rows (its columns are model-local)
             const int row0 = e->model_row0[(size_t)model_of(e, r)];
             a.model_offset_j = 0;

@@ -142,6 +142,8 @@ struct sga_engine {
     int n_models = 1;  // dense batches: models stacked row-wise, replicas split evenly
     // sga_set_dense_shared: the n_models models hold ONE coupling matrix (J_packed, J_bits: n rows) and differ in h alone
     // ([n_models][n]; diag and row_nnz are repeated per model, so the kernels index them as they index a stacked batch's)
+    // sga_set_csr_shared (csr && shared_j): ONE set of rows (rowptr, cv, diag: n rows) under n_models field vectors, h
+    // [n_models][n]; the kernels add model * n to h alone
     bool shared_j = false;
     // ragged CSR batches (sga_set_csr_batch): n_models CSR problems of any sizes concatenated row-wise, replicas split
     // evenly; n = the largest model's spins (the replica layout), n_rows = the rows of the concatenation

@@ -60,6 +60,8 @@ struct SweepArgs {
     // many-model batches (dense): replica r belongs to model (replica0 + r) / reps_per_model;
     // J / h / diag of model m start at m * model_stride_j / m * n elements (reps_per_model 0 = one model;
     // model_stride_j 0 with reps_per_model > 0 = one shared matrix under many field vectors, sga_set_dense_shared)
+    // CSR launches: reps_per_model > 0 together with ragged == 0 means one set of rows under many field vectors
+    // (sga_set_csr_shared): h of model m starts at m * n floats, rows and diag are the one model's; model_stride_j stays 0
     int reps_per_model;
     long long model_stride_j;
     int no_best;  // 1: leave best tracking to the host-driven pass (asymmetric / diagonal J)
@@ -262,8 +264,12 @@ struct CsrEnergyArgs {
 };
 // (h . s in the canonical order; X in group order, the same bits only where it is exact: sga_engine.cpp)
 size_t csr_energy_scratch_bytes(int n, int R, int groups);
+// (reps_per_model > 0: one set of rows under many field vectors, h [n_models][n] -- replica r of this pass is global
+//  replica replica_base + r and takes the h of model (replica_base + r) / reps_per_model; the pass over the entries is
+//  the same one, whatever the models of the 32 replicas a lane carries)
 hipError_t launch_energy_csr_all(const long long *rowptr, const int2 *cv, const float *h, const int8_t *spins, int sstride,
-                                 int n, int R, int groups, bool exact32, void *scratch, double *energy, hipStream_t st);
+                                 int n, int R, int groups, bool exact32, void *scratch, double *energy, hipStream_t st,
+                                 int reps_per_model = 0, int replica_base = 0);
 
 struct ExchangeArgs {
     const double *energies;   // [R_global] by global replica id
@@ -371,7 +377,7 @@ enum { CSR_ACC_F32_TABLE = 0,   // integer J and h, few distinct uphill moves: f
 hipError_t launch_csr_check_rowptr(const long long *rowptr, int n, long long nnz, int *flags,
                                    hipStream_t st);
 hipError_t launch_csr_scan(const long long *rowptr, const int32_t *colidx, const float *val,
-                           const float *h, int n, int *flags, hipStream_t st);
+                           const float *h, int n, int *flags, hipStream_t st, int n_h = 1);
 // sorted = rows strictly sorted by column (binary search); else linear scans of both rows
 hipError_t launch_csr_symmetry(const long long *rowptr, const int32_t *colidx, const float *val,
                                int n, bool sorted, int *flags, hipStream_t st);

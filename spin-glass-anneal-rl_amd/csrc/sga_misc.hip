@@ -395,8 +395,10 @@ hipError_t launch_csr_check_rowptr(const long long *rowptr, int n, long long nnz
 }
 
 // one wave per row (grid-stride): ranges, integrality, ordering, diagonal, sum of |entries|
+// (n_h > 1: one set of rows under n_h field vectors h[m][i], sga_set_csr_shared -- the words a batch of n_h copies of
+//  the rows would fold to, the row's sum formed once)
 __global__ void __launch_bounds__(256) csr_scan_kernel(const long long *rowptr, const int32_t *colidx,
-                                                       const float *val, const float *h, int n,
+                                                       const float *val, const float *h, int n, int n_h,
                                                        int *flags) {
     const int lane = threadIdx.x & 63;
     const int wave = (int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
@@ -427,14 +429,16 @@ __global__ void __launch_bounds__(256) csr_scan_kernel(const long long *rowptr, 
             if (j > beg && colidx[j - 1] >= c) unsorted = 1;
             acc += (double)fabsf(v);
         }
-        const float hi = h[i];
-        if (hi != rintf(hi)) non_int |= 2;
-        if (2.0f * hi != rintf(2.0f * hi)) non_int |= 4;
-        if ((__float_as_uint(hi) & 0x7F800000u) == 0x7F800000u) non_int |= SCAN_NON_FINITE;
         // an upper bound is all the table needs; fp32 rounds it up or down by < 1 ulp
         const double jsum = wave_sum(acc);
-        const float tot = (float)(jsum + (double)fabsf(hi));
-        row_max = fmaxf(row_max, tot);
+        for (int m = 0; m < n_h; ++m) {
+            const float hi = h[(long long)m * n + i];
+            if (hi != rintf(hi)) non_int |= 2;
+            if (2.0f * hi != rintf(2.0f * hi)) non_int |= 4;
+            if ((__float_as_uint(hi) & 0x7F800000u) == 0x7F800000u) non_int |= SCAN_NON_FINITE;
+            const float tot = (float)(jsum + (double)fabsf(hi));
+            row_max = fmaxf(row_max, tot);
+        }
         row_j_max = fmaxf(row_j_max, (float)jsum);  // sum_j |J_ij| alone: the range of the dynamic part of a field
     }
     if (bad_col) flags[CSR_BAD_COLUMN] = 1;
@@ -447,9 +451,10 @@ __global__ void __launch_bounds__(256) csr_scan_kernel(const long long *rowptr, 
     if (lane == 0) atomicMax(&flags[CSR_ROW_J_ABS_MAX], __float_as_int(row_j_max));
 }
 hipError_t launch_csr_scan(const long long *rowptr, const int32_t *colidx, const float *val,
-                           const float *h, int n, int *flags, hipStream_t st) {
+                           const float *h, int n, int *flags, hipStream_t st, int n_h) {
+    if (n_h < 1) return hipErrorInvalidValue;
     const int blocks = (int)std::min<long long>(((long long)n + 3) / 4, 256 * 32);
-    hipLaunchKernelGGL(csr_scan_kernel, dim3(blocks), dim3(256), 0, st, rowptr, colidx, val, h, n,
+    hipLaunchKernelGGL(csr_scan_kernel, dim3(blocks), dim3(256), 0, st, rowptr, colidx, val, h, n, n_h,
                        flags);
     return hipGetLastError();
 }
@@ -755,6 +760,8 @@ __global__ void __launch_bounds__(256) energy_csr_kernel(const EnergyArgs a) {
         __syncthreads();
     }
     const int b0 = blockIdx.y * a.blocks_per_slice, b1 = min(a.nblocks, b0 + a.blocks_per_slice);
+    // (one set of rows under many field vectors, sga_set_csr_shared: the replica's model's h, as the dense kernel above)
+    const float *hvec = a.h + (long long)(a.reps_per_model > 0 ? (a.replica_base + r) / a.reps_per_model : 0) * a.n;
     double e_tot = 0.0, h_tot = 0.0;
     for (int b = b0; b < b1; ++b) {
         const int row1 = min(a.n, (b + 1) * a.block_rows);
@@ -764,7 +771,7 @@ __global__ void __launch_bounds__(256) energy_csr_kernel(const EnergyArgs a) {
                                                      [&](int c) -> float { return (float)s[c]; });
             const double si = (double)s[i];
             e_acc += (double)mv_i * si;
-            h_acc += (double)a.h[i] * si;
+            h_acc += (double)hvec[i] * si;
         }
         energy_block_done(e_acc, h_acc, red, energy_partial(a, r, b), e_tot, h_tot);
     }
@@ -790,6 +797,7 @@ __global__ void __launch_bounds__(64 * ENERGY_BIG_WAVES) energy_csr_bits_kernel(
     constexpr int BPR = ENERGY_BIG_WAVES / 4;
     static_assert(BPR == ENERGY_BITS_BLOCKS_PER_PASS, "slices take whole passes (sga_engine.cpp)");
     const int b0 = blockIdx.y * a.blocks_per_slice, b1 = min(a.nblocks, b0 + a.blocks_per_slice);
+    const float *hvec = a.h + (long long)(a.reps_per_model > 0 ? (a.replica_base + r) / a.reps_per_model : 0) * a.n;
     double e_tot = 0.0, h_tot = 0.0;
     for (int bb = b0; bb < b1; bb += BPR) {
         const int b = bb + (w >> 2);
@@ -799,7 +807,7 @@ __global__ void __launch_bounds__(64 * ENERGY_BIG_WAVES) energy_csr_bits_kernel(
             const float mv_i = csr_row_sum_canonical(a.cv, a.rowptr[i], a.rowptr[i + 1], lane, spin_f);
             const double si = (double)spin_f(i);
             e_acc += (double)mv_i * si;
-            h_acc += (double)a.h[i] * si;
+            h_acc += (double)hvec[i] * si;
         }
         if (lane == 0) {
             red[w] = e_acc;

@@ -217,10 +217,15 @@ namespace {
 // same pass classifies the problem: integer valued (accept table, fp32-exact row sums),
 // symmetric with zero diagonal (dE of the rule == energy change).  Device arrays are read where
 // they lie, host arrays are staged; only the interleaved layout stays resident.
+//
+// n_models > 1 (sga_set_csr_shared): h is [n_models][n], ONE set of rows under n_models field vectors.  The structure is
+// checked, classified and packed once, exactly as for one model; the h-dependent scan words ([2], [6]) and with them the
+// accept table are taken over all of h -- an exact sum stays exact in a wider class, and a table entry stands for the
+// same dE at any scale.
 int set_csr_common(sga_engine *e, const void *rowptr, bool wide_extents, const int32_t *colidx,
-                          const float *val, const float *h, int n, int64_t nnz) {
+                          const float *val, const float *h, int n, int64_t nnz, int n_models = 1) {
     if (!e) return fail(SGA_ERR_INVALID, "engine is NULL");
-    if (!rowptr || !h || n <= 0 || nnz < 0 || (nnz > 0 && (!colidx || !val)))
+    if (!rowptr || !h || n <= 0 || nnz < 0 || (nnz > 0 && (!colidx || !val)) || n_models <= 0)
         return fail(SGA_ERR_INVALID, "bad CSR problem arguments");
     HIPCHK(hipSetDevice(e->device));
     HIPCHK(hipStreamSynchronize(e->stream));
@@ -230,7 +235,8 @@ int set_csr_common(sga_engine *e, const void *rowptr, bool wide_extents, const i
     e->csr = true;
     e->from_dense = false;
     e->n = n;
-    e->n_models = 1;
+    e->n_models = n_models;
+    e->shared_j = n_models > 1;  // (one model: sga_set_csr in every respect)
     e->nnz = nnz;
     const size_t np1 = (size_t)n + 1;
     if (!wide_extents && nnz >= (int64_t)INT32_MAX) {
@@ -260,9 +266,9 @@ int set_csr_common(sga_engine *e, const void *rowptr, bool wide_extents, const i
         HIPCHK(hipMemcpyAsync(e->val, val, sizeof(float) * nz, hipMemcpyHostToDevice, e->stream));
         vv = e->val;
     }
-    HIPCHK(hipMalloc(&e->h, sizeof(float) * (size_t)n));
-    HIPCHK(hipMemcpyAsync(e->h, h, sizeof(float) * (size_t)n, hipMemcpyDefault, e->stream));
-    HIPCHK(hipMalloc(&e->diag, sizeof(float) * (size_t)n));
+    HIPCHK(hipMalloc(&e->h, sizeof(float) * (size_t)n * (size_t)n_models));
+    HIPCHK(hipMemcpyAsync(e->h, h, sizeof(float) * (size_t)n * (size_t)n_models, hipMemcpyDefault, e->stream));
+    HIPCHK(hipMalloc(&e->diag, sizeof(float) * (size_t)n));  // (J's: once, whatever n_models)
 
     int *d_flags = e->d_flags;
     int flags[sga::CSR_FLAG_COUNT] = {0};
@@ -281,7 +287,7 @@ int set_csr_common(sga_engine *e, const void *rowptr, bool wide_extents, const i
     if (he != hipSuccess) return bail(SGA_ERR_DEVICE, hipGetErrorString(he));
     if (flags[sga::CSR_BAD_ROWPTR])
         return bail(SGA_ERR_INVALID, "CSR rowptr is not monotone or does not span [0, nnz]");
-    he = sga::launch_csr_scan(e->rowptr64, ci, vv, e->h, n, d_flags, e->stream);
+    he = sga::launch_csr_scan(e->rowptr64, ci, vv, e->h, n, d_flags, e->stream, n_models);
     if (he == hipSuccess) he = read_flags();
     if (he != hipSuccess) return bail(SGA_ERR_DEVICE, hipGetErrorString(he));
     if (flags[sga::CSR_BAD_COLUMN]) return bail(SGA_ERR_INVALID, "CSR column index out of range");
@@ -344,8 +350,67 @@ int set_csr_common(sga_engine *e, const void *rowptr, bool wide_extents, const i
     dev_free(src_ptr);
     dev_free(e->colidx);  // staging copies of host arrays (null when the caller's were device memory)
     dev_free(e->val);
+    // one wave per replica reads 32-bit extents: a layout beyond them is sga_set_csr64's, which has no shared variant
+    if (rc == SGA_OK && e->shared_j && !e->rowptr)
+        rc = fail(SGA_ERR_UNSUPPORTED, "shared-coupling CSR batches run one wave per replica (32-bit row extents): this "
+                                       "layout needs 64-bit extents");
     if (rc != SGA_OK) e->free_problem();
     return rc;
+}
+
+// sga_set_csr_shared: what the caller can get wrong -- extents, columns, non-finite values -- is looked at BEFORE the
+// engine lets go of the problem it holds, on staged copies that live for this call only (the two structure scans once
+// more, at set time; nothing of the engine but its flag words is written).  Past that point it is set_csr_common.
+int set_csr_shared(sga_engine *e, const int32_t *rowptr, const int32_t *colidx, const float *val, const float *H, int n,
+                   int64_t nnz, int n_models) {
+    if (!e) return fail(SGA_ERR_INVALID, "engine is NULL");
+    if (!rowptr || !H || n <= 0 || nnz < 0 || (nnz > 0 && (!colidx || !val)) || n_models <= 0)
+        return fail(SGA_ERR_INVALID, "bad CSR problem arguments");
+    if (nnz >= (int64_t)INT32_MAX)
+        return fail(SGA_ERR_UNSUPPORTED, "shared-coupling CSR batches take 32-bit row extents (nnz < 2^31)");
+    HIPCHK(hipSetDevice(e->device));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    struct Staged {
+        int32_t *rp = nullptr, *ci = nullptr;
+        long long *rp64 = nullptr;
+        float *v = nullptr, *h = nullptr;
+        ~Staged() { dev_free(rp), dev_free(ci), dev_free(rp64), dev_free(v), dev_free(h); }
+    } t;
+    const size_t np1 = (size_t)n + 1, nz = (size_t)std::max<int64_t>(nnz, 1), nh = (size_t)n * (size_t)n_models;
+    HIPCHK(hipMalloc(&t.rp, sizeof(int32_t) * np1));
+    HIPCHK(hipMalloc(&t.rp64, sizeof(long long) * np1));
+    HIPCHK(hipMemcpyAsync(t.rp, rowptr, sizeof(int32_t) * np1, hipMemcpyDefault, e->stream));
+    HIPCHK(sga::launch_widen_rowptr(t.rp, t.rp64, (long long)np1, e->stream));
+    const int32_t *ci = colidx;
+    const float *vv = val, *hh = H;
+    if (nnz > 0 && !is_device_ptr(colidx)) {
+        HIPCHK(hipMalloc(&t.ci, sizeof(int32_t) * nz));
+        HIPCHK(hipMemcpyAsync(t.ci, colidx, sizeof(int32_t) * nz, hipMemcpyHostToDevice, e->stream));
+        ci = t.ci;
+    }
+    if (nnz > 0 && !is_device_ptr(val)) {
+        HIPCHK(hipMalloc(&t.v, sizeof(float) * nz));
+        HIPCHK(hipMemcpyAsync(t.v, val, sizeof(float) * nz, hipMemcpyHostToDevice, e->stream));
+        vv = t.v;
+    }
+    if (!is_device_ptr(H)) {
+        HIPCHK(hipMalloc(&t.h, sizeof(float) * nh));
+        HIPCHK(hipMemcpyAsync(t.h, H, sizeof(float) * nh, hipMemcpyHostToDevice, e->stream));
+        hh = t.h;
+    }
+    int flags[sga::CSR_FLAG_COUNT] = {0};
+    HIPCHK(hipMemsetAsync(e->d_flags, 0, sizeof(flags), e->stream));
+    HIPCHK(sga::launch_csr_check_rowptr(t.rp64, n, nnz, e->d_flags, e->stream));
+    HIPCHK(hipMemcpyAsync(flags, e->d_flags, sizeof(flags), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    if (flags[sga::CSR_BAD_ROWPTR]) return fail(SGA_ERR_INVALID, "CSR rowptr is not monotone or does not span [0, nnz]");
+    HIPCHK(sga::launch_csr_scan(t.rp64, ci, vv, hh, n, e->d_flags, e->stream, n_models));
+    HIPCHK(hipMemcpyAsync(flags, e->d_flags, sizeof(flags), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    if (flags[sga::CSR_BAD_COLUMN]) return fail(SGA_ERR_INVALID, "CSR column index out of range");
+    if (flags[sga::CSR_NOT_INTEGRAL] & sga::SCAN_NON_FINITE) return fail(SGA_ERR_INVALID, NON_FINITE_MSG);
+    // (the staged copies are device memory: set_csr_common borrows them instead of staging again)
+    return set_csr_common(e, t.rp, false, ci, vv, hh, n, nnz, n_models);
 }
 
 // does the diagonal pack_dense extracted hold a non-zero?  (*out: 0 | 1)
@@ -549,6 +614,11 @@ int sga_set_dense_shared(sga_engine *e, const float *J, int64_t ldJ, const float
 int sga_set_csr(sga_engine *e, const int32_t *rowptr, const int32_t *colidx, const float *val,
                 const float *h, int n, int64_t nnz) {
     return set_csr_common(e, rowptr, false, colidx, val, h, n, nnz);
+}
+
+int sga_set_csr_shared(sga_engine *e, const int32_t *rowptr, const int32_t *colidx, const float *val, const float *H,
+                       int n, int64_t nnz, int n_models) {
+    return set_csr_shared(e, rowptr, colidx, val, H, n, nnz, n_models);
 }
 
 int sga_set_csr64(sga_engine *e, const int64_t *rowptr, const int32_t *colidx, const float *val,

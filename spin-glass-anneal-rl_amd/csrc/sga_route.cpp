@@ -170,7 +170,41 @@ CsrForm csr_ragged_form(const Query &q) {
     return f;
 }
 
+// a CSR query with n_models > 1: a ragged batch (sga_set_csr_batch), or one set of rows under n_models field vectors
+// (sga_set_csr_shared, shared_j)
+static bool csr_ragged(const Query &q) { return q.kind == SGA_ROUTE_CSR && q.n_models > 1 && !q.shared_j; }
+static bool csr_shared(const Query &q) { return q.kind == SGA_ROUTE_CSR && q.n_models > 1 && q.shared_j; }
+
+// One set of rows under n_models field vectors: the one-model decision among the one-wave-per-replica forms (int8
+// spins, or bit spins with several replicas per workgroup) -- updates per step, medium rows, bits and residency as for
+// one model.  The one-replica-per-workgroup forms read a row's h from rowinfo.w, which holds one model's: a problem
+// that fits no narrow form, tuning that asks for several waves and packed entries (a wide bit form's) are refused; so are
+// cached fields ON (not built for these batches; AUTO streams).  A long-row problem that one model would run wide
+// runs narrow here, as a ragged batch does.
+CsrForm csr_shared_form(const Query &q) {
+    Query one = q;
+    one.n_models = 1;
+    one.shared_j = 0;
+    one.tune_waves = 1;  // (one wave per replica: no wide int8 form, no one-replica-per-workgroup bit form by choice)
+    CsrForm f = csr_replica_form(one);
+    if (q.tune_waves > 1)
+        f.error = "shared-coupling CSR batches run one wave per replica (sga_set_tuning waves_per_replica > 1 picks a "
+                  "one-replica-per-workgroup form, whose row records carry one field)";
+    else if (q.storage == SGA_CSR_STORAGE_PACKED)
+        f.error = "shared-coupling CSR batches read (column, value) entries (packed storage is the one-replica-per-workgroup "
+                  "bit form's)";
+    else if (q.field_cache == SGA_FIELD_CACHE_ON)
+        f.error = "shared-coupling CSR batches: cached local fields are not built for them (SGA_FIELD_CACHE_AUTO runs the "
+                  "streaming forms)";
+    else if (f.error || f.waves != 1 || f.big_form == 1)
+        f.error = "shared-coupling CSR batches: the problem fits no one-wave-per-replica form (int8 spins of a replica beyond "
+                  "LDS, and long rows or 64-bit extents rule out the narrow bit form)";
+    f.needs_slots = f.wants_packed = false;
+    return f;
+}
+
 CsrForm csr_replica_form(const Query &q) {
+    if (csr_shared(q)) return csr_shared_form(q);
     if (q.n_models > 1) return csr_ragged_form(q);
     CsrForm f;
     const int R_local = q.R_local;
@@ -342,9 +376,12 @@ const char *clf_refusal(const Query &q) {
     if (q.kind == SGA_ROUTE_GROUPS)
         return "cached local fields: stored couplings only (sga_set_groups keeps the group sums resident instead; AUTO runs "
                "that form as it is)";
-    if (q.kind == SGA_ROUTE_CSR && q.n_models > 1 && q.opt[OPT_RAGGED_FIELD_CACHE] == 0)
+    if (csr_shared(q))
+        return "shared-coupling CSR batches: cached local fields are not built for them (SGA_FIELD_CACHE_AUTO runs the "
+               "streaming forms)";
+    if (csr_ragged(q) && q.opt[OPT_RAGGED_FIELD_CACHE] == 0)
         return "cached local fields: not built for ragged CSR batches (sga_set_csr_batch runs the streaming narrow form)";
-    if (q.kind == SGA_ROUTE_CSR && q.n_models > 1) {
+    if (csr_ragged(q)) {
         // option "ragged_field_cache": the int16 form of sweep_clf_csr.hip, each replica on its own model's rows; LDS is
         // laid out for the largest model (q.n), the table and the longest row are the batch's
         const long long ldf = ((long long)q.n + 127) / 128 * 128;
@@ -469,7 +506,7 @@ static double dense_fixed_point_theta(const Query &q, double t_upd) {
 double routing_theta(const Query &q) {
     const double kn = (double)q.n / 1000.0;
     // (ragged batches: q.n is the largest model, so nnz / n overstates the mean row; no row is longer than the longest)
-    const double deg = (q.kind == SGA_ROUTE_CSR && q.n_models > 1) ? std::min((double)q.nnz / (double)q.n, (double)q.max_row_len)
+    const double deg = csr_ragged(q) ? std::min((double)q.nnz / (double)q.n, (double)q.max_row_len)
                                                                      : (double)q.nnz / (double)q.n;
     const double t_upd = q.kind == SGA_ROUTE_CSR ? 0.20 + 0.0008 * deg  // (C4: 0.68, C2b as CSR: 0.36)
                          : q.storage == SGA_J_T2 ? 0.29 + 0.009 * kn
@@ -640,7 +677,7 @@ std::string explain(const Query &q0) {
                       t.waves, t.passes, (long long)q.opt[OPT_TSP_PARALLEL],
                       q.opt[OPT_TSP_PARALLEL] == 0 ? "sweep_tsp_kernel" : "sweep_tsp_par_kernel|sweep_tsp_kernel");
         out = buf;
-    } else if (q.kind == SGA_ROUTE_CSR && q.n_models > 1) {
+    } else if (csr_ragged(q)) {
         const CsrForm f = csr_ragged_form(q);
         if (f.error) return std::string("csr error=") + f.error;
         std::snprintf(buf, sizeof(buf),
@@ -666,6 +703,10 @@ std::string explain(const Query &q0) {
                       std::strcmp(fam, "rows") == 0 ? ups : ((ups == 1 || ups == 2) && !f.bits && f.waves == 1 ? ups : 0),
                       slotted_now ? 1 : 0, (f.wants_packed && q.packed_ok) ? "packed" : "cv", f.table_m, f.sstride);
         out = buf;
+        if (csr_shared(q)) {  // sga_set_csr_shared: one set of rows under n_models field vectors
+            std::snprintf(buf, sizeof(buf), " shared-J models=%d", q.n_models);
+            out += buf;
+        }
         q.sstride = f.sstride;
     } else {
         const DenseGeometry g = dense_geometry(q);
@@ -700,7 +741,7 @@ std::string explain(const Query &q0) {
         if (why) {
             out += q.field_cache == SGA_FIELD_CACHE_ON ? " cached=refused" : " cached=unavailable";
         } else if (q.field_cache == SGA_FIELD_CACHE_ON) {
-            if (q.kind == SGA_ROUTE_CSR && q.n_models > 1 && q.opt[OPT_CLF_FIXED_POINT] == 1 && (q.clf_bits == 32 || q.clf_bits == 64))
+            if (csr_ragged(q) && q.opt[OPT_CLF_FIXED_POINT] == 1 && (q.clf_bits == 32 || q.clf_bits == 64))
                 std::snprintf(buf, sizeof(buf), " cached=on(waves=%d fields=int%d fixed-point models=%d)", clf_csr_waves(q), q.clf_bits,
                               q.n_models);
             else if (q.kind == SGA_ROUTE_CSR && q.opt[OPT_CLF_FIXED_POINT] == 1 && (q.clf_bits == 32 || q.clf_bits == 64))
@@ -715,7 +756,7 @@ std::string explain(const Query &q0) {
                 std::snprintf(buf, sizeof(buf), " cached=on(waves=%d fields=int%d fixed-point)",
                               sga::sweep_clf_waves(dense_ldj(q), is_i8(q), std::max(q.R_local, 1), q.cus, (int)q.opt[OPT_CLF_WAVES]),
                               q.clf_bits);
-            else if (q.kind == SGA_ROUTE_CSR && q.n_models > 1)  // a ragged batch: waves by its longest row and largest model
+            else if (csr_ragged(q))  // a ragged batch: waves by its longest row and largest model
                 std::snprintf(buf, sizeof(buf), " cached=on(waves=%d models=%d)", clf_csr_waves(q), q.n_models);
             else if (q.kind == SGA_ROUTE_CSR) std::snprintf(buf, sizeof(buf), " cached=on(waves=%d)", clf_csr_waves(q));
             else if (q.n_models > 1)  // a many-model dense batch: batch-wide field width, each replica on its model's rows

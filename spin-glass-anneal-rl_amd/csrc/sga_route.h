@@ -120,6 +120,10 @@ int csr_replicas_per_block(const Query &q, const CsrForm &f);
 // ragged CSR batches (sga_set_csr_batch; a query with n_models > 1): the narrow one-update int8 form, or an error
 // naming the option that would pick another form
 CsrForm csr_ragged_form(const Query &q);
+// one set of rows under n_models field vectors (sga_set_csr_shared; a CSR query with n_models > 1 and shared_j): the
+// one-model decision restricted to one wave per replica (int8 spins, or bit spins with several replicas per workgroup),
+// or an error starting "shared-coupling CSR batches"
+CsrForm csr_shared_form(const Query &q);
 // the kernel family launch_sweep_csr takes for production arguments: "rows" | "narrow" | "narrow-bits" | "wide-bits" | "wide-bytes"
 const char *csr_kernel_family(const Query &q, const CsrForm &f, bool slotted_now);
 

@@ -206,6 +206,12 @@ struct StateHeader {
 };
 constexpr uint64_t STATE_MAGIC = 0x5347415354415445ull;  // "SGASTATE"
 constexpr int32_t STATE_VERSION = 2;
+// The blob of an sga_set_csr_shared engine is the one-model CSR blob; the header's version word carries the number of
+// field vectors in its upper half (n_models - 1: 0 for every other kind of problem, whose blobs are what they were), so
+// that a state goes back only into an engine with as many models.
+int32_t state_version_word(const sga_engine *e) {
+    return STATE_VERSION | (int32_t)((e->csr && e->shared_j ? (uint32_t)(e->n_models - 1) & 0x7FFFu : 0u) << 16);
+}
 
 uint64_t state_bytes(const sga_engine *e) {
     const uint64_t R = (uint64_t)e->R, Rg = (uint64_t)e->Rg, sb = R * (uint64_t)e->n;
@@ -225,7 +231,7 @@ int sga_export_state(sga_engine *e, void *buf, uint64_t capacity, uint64_t *need
     HIPCHK(hipSetDevice(e->device));
     HIPCHK(hipStreamSynchronize(e->stream));
     unsigned char *p = static_cast<unsigned char *>(buf);
-    StateHeader h{STATE_MAGIC, STATE_VERSION, e->n, e->R, e->Rg, e->replica0, e->n_ladders,
+    StateHeader h{STATE_MAGIC, state_version_word(e), e->n, e->R, e->Rg, e->replica0, e->n_ladders,
                   e->sweeps_done, e->rounds, e->seed, (int64_t)e->attempted};
     std::memcpy(p, &h, sizeof(h));
     p += sizeof(h);
@@ -262,7 +268,10 @@ int sga_import_state(sga_engine *e, const void *buf, uint64_t size) {
     StateHeader h;
     std::memcpy(&h, buf, sizeof(h));
     if (h.magic != STATE_MAGIC) return fail(SGA_ERR_INVALID, "not an engine state blob");
-    if (h.version != STATE_VERSION) return fail(SGA_ERR_INVALID, "state blob of another engine version");
+    if ((h.version & 0xFFFF) != STATE_VERSION) return fail(SGA_ERR_INVALID, "state blob of another engine version");
+    if (h.version != state_version_word(e))
+        return fail(SGA_ERR_INVALID, "state blob does not match this engine's problem (shared-coupling CSR batches: another "
+                                     "number of models)");
     if (h.n != e->n || h.R != e->R || h.Rg != e->Rg || h.replica0 != e->replica0 ||
         h.n_ladders != e->n_ladders)
         return fail(SGA_ERR_INVALID, "state blob does not match this engine's problem / replicas / ladder");
@@ -373,9 +382,9 @@ int sga_describe(sga_engine *e, char *buf, int buflen) {
                           ? "" : " sweep=streaming(no field cache for ragged batches)");
     else if (e->csr)
         std::snprintf(tmp, sizeof(tmp),
-                      "csr n=%d nnz=%lld R=%d waves_per_replica=%d replicas_per_block=%d sstride=%d "
+                      "csr n=%d %snnz=%lld R=%d waves_per_replica=%d replicas_per_block=%d sstride=%d "
                       "path=%s table_m=%d spins=%s",
-                      e->n, e->nnz, e->R, e->waves,
+                      e->n, e->shared_j ? ("shared-J models=" + std::to_string(e->n_models) + " ").c_str() : "", e->nnz, e->R, e->waves,
                       e->big_form == 2 ? sga::csr_bits_waves_per_block(e->sstride, e->table_m)
                                        : ((e->waves > 1 || e->big) ? 1 : sga::csr_waves_per_block(e->sstride, e->table_m)),
                       e->sstride,
@@ -534,6 +543,8 @@ int sga_problem_checksum(sga_engine *e, uint64_t *out) {
     HIPCHK(hipMemcpyAsync(host, d, sizeof(host), hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
     *out = host[0] ^ ((host[1] << 17) | (host[1] >> 47)) ^ ((uint64_t)(uint32_t)e->n << 32);
+    // (sga_set_csr_shared: the layout once, all of H above, and the number of models)
+    if (e->csr && e->shared_j) *out ^= (uint64_t)(uint32_t)e->n_models * 0x9E3779B97F4A7C15ull;
     return SGA_OK;
 }
 

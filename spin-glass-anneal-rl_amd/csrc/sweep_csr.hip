@@ -24,21 +24,23 @@ int csr_bits_waves_per_block(int sstride, int table_m) {  // narrow bit-spin for
     return wpb > CSR_WAVES_PER_BLOCK ? CSR_WAVES_PER_BLOCK : wpb;
 }
 
-template <bool BIG>
+// (SHARED: the builds for one set of rows under many field vectors, sga_set_csr_shared)
+template <int ACC, bool LEAN, bool BIG, bool SHARED>
+static constexpr auto narrow_kernel = sweep_csr_kernel<ACC, LEAN, false, BIG, 0, 8, false, false, SHARED>;
+template <bool BIG, bool SHARED = false>
 static hipError_t launch_csr_narrow(const SweepArgs &a, int waves, hipStream_t st) {
     const bool lean = csr_args_are_lean(a);
     void (*kern)(const SweepArgs) = nullptr;
     switch (csr_effective_acc(a, lean)) {
-        case CSR_ACC_F32_TABLE: kern = sweep_csr_kernel<CSR_ACC_F32_TABLE, true, false, BIG>; break;
+        case CSR_ACC_F32_TABLE: kern = narrow_kernel<CSR_ACC_F32_TABLE, true, BIG, SHARED>; break;
         case CSR_ACC_F32:
-            kern = lean ? sweep_csr_kernel<CSR_ACC_F32, true, false, BIG> : sweep_csr_kernel<CSR_ACC_F32, false, false, BIG>;
+            kern = lean ? narrow_kernel<CSR_ACC_F32, true, BIG, SHARED> : narrow_kernel<CSR_ACC_F32, false, BIG, SHARED>;
             break;
         case CSR_ACC_F64:
-            kern = lean ? sweep_csr_kernel<CSR_ACC_F64, true, false, BIG> : sweep_csr_kernel<CSR_ACC_F64, false, false, BIG>;
+            kern = lean ? narrow_kernel<CSR_ACC_F64, true, BIG, SHARED> : narrow_kernel<CSR_ACC_F64, false, BIG, SHARED>;
             break;
         default:
-            kern = lean ? sweep_csr_kernel<CSR_ACC_F64_CANON, true, false, BIG>
-                        : sweep_csr_kernel<CSR_ACC_F64_CANON, false, false, BIG>;
+            kern = lean ? narrow_kernel<CSR_ACC_F64_CANON, true, BIG, SHARED> : narrow_kernel<CSR_ACC_F64_CANON, false, BIG, SHARED>;
     }
     return launch_csr_kernel(kern, a, false, BIG, waves, st);
 }
@@ -57,6 +59,9 @@ hipError_t launch_sweep_csr(const SweepArgs &a0, int waves_per_replica, hipStrea
         a.csr_pair_ahead = 0;
         return launch_csr_ragged(a, wpb, st);
     }
+    // one set of rows under many field vectors (sga_set_csr_shared): the one-wave-per-replica forms only -- the wide
+    // forms read a row's h from rowinfo.w, which holds one model's
+    if (csr_args_are_shared(a0) && (waves_per_replica != 1 || a0.big == 1 || !a0.rowptr)) return hipErrorInvalidValue;
     // four | eight updates per step (sweep_csr_rows.hip): its own kernel; every other form reads 4 | 8 as "off"
     if (waves_per_replica == 1 && sweep_csr_rows_applies(a0)) {
         const int wpb = a0.big ? csr_bits_waves_per_block(a0.sstride, a0.table_m) : csr_waves_per_block(a0.sstride, a0.table_m);
@@ -71,7 +76,7 @@ hipError_t launch_sweep_csr(const SweepArgs &a0, int waves_per_replica, hipStrea
         if (waves_per_replica == 1 && a.rowptr && a.big == 2) {  // several replicas per workgroup
             const int wpb = csr_bits_waves_per_block(a.sstride, a.table_m);
             if (wpb < 1) return hipErrorInvalidValue;
-            return launch_csr_narrow<true>(a, wpb, st);
+            return csr_args_are_shared(a) ? launch_csr_narrow<true, true>(a, wpb, st) : launch_csr_narrow<true>(a, wpb, st);
         }
         if (!a.rowinfo) return hipErrorInvalidValue;  // wide forms read the slotted layout
         return launch_csr_wide_bits(a, waves_per_replica, a.csr_head, st);
@@ -83,7 +88,7 @@ hipError_t launch_sweep_csr(const SweepArgs &a0, int waves_per_replica, hipStrea
     }
     const int wpb = csr_waves_per_block(a.sstride, a.table_m);
     if (wpb < 1 || !a.rowptr) return hipErrorInvalidValue;
-    return launch_csr_narrow<false>(a, wpb, st);
+    return csr_args_are_shared(a) ? launch_csr_narrow<false, true>(a, wpb, st) : launch_csr_narrow<false>(a, wpb, st);
 }
 
 // ragged CSR batches: the narrow one-update int8 form (accept table, general and LEAN variants)

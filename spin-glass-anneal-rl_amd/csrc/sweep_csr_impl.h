@@ -84,10 +84,14 @@ constexpr int CSR_MAX_WIDE = 8;   // most waves one replica's row is dealt to (1
 //   * the table holds exp(float32(-dE / T)) at dE = 2 q / table_scale: with a larger scale or more entries, the entry
 //     a move looks up stands for the same dE, and a move beyond the table takes the exact expression -- either way
 //     the table decides exactly what metropolis_accept decides.
-template <int ACC, bool LEAN, bool WIDE, bool BIG, int NW = 0, int HD = 8, bool PK = false, bool RAGGED = false>
+//
+// SHARED = one set of rows under many field vectors (sga_set_csr_shared), narrow forms only: a build of its own, so that the
+// one-model builds -- at the SGPR limit -- stay what they were (see the h base below).
+template <int ACC, bool LEAN, bool WIDE, bool BIG, int NW = 0, int HD = 8, bool PK = false, bool RAGGED = false, bool SHARED = false>
 __global__ void __launch_bounds__(64 * (WIDE ? CSR_MAX_WIDE : CSR_WAVES_PER_BLOCK))
     sweep_csr_kernel(const SweepArgs a) {
     static_assert(!RAGGED || (!WIDE && !BIG && !PK), "ragged batches: the narrow int8 form");
+    static_assert(!SHARED || (!WIDE && !RAGGED && !PK), "shared-coupling batches: the narrow forms");
     constexpr bool FAST = ACC == CSR_ACC_F32_TABLE || ACC == CSR_ACC_F32;  // fp32 accumulation
     constexpr bool TABLE = ACC == CSR_ACC_F32_TABLE;
     constexpr bool CANON = ACC == CSR_ACC_F64_CANON;
@@ -125,6 +129,15 @@ __global__ void __launch_bounds__(64 * (WIDE ? CSR_MAX_WIDE : CSR_WAVES_PER_BLOC
         rowptr += model_row0;
     }
     const int n = RAGGED ? model_n : a.n;
+    // one set of rows under many field vectors (SHARED builds: a.reps_per_model > 0, a.ragged == 0): the replica's
+    // model's h, resolved here once -- a wave-uniform base held in SGPRs, so the scalar load of h[site] is the one-model
+    // build's instruction with another base.  Rows, diag and n are the one model's; the waves of a workgroup may belong
+    // to different models, and nothing in LDS is shared between waves.  (The wide forms carry h in rowinfo.w: refused.)
+    const float *hbase = a.h;
+    if constexpr (SHARED) {
+        const unsigned int m = __builtin_amdgcn_readfirstlane((a.replica0 + (uint32_t)r) / (uint32_t)a.reps_per_model);
+        hbase += (unsigned long long)m * (unsigned int)a.n;
+    }
     const int slots = WIDE ? 1 : nw;                    // replicas sharing this workgroup's LDS
     const int me = WIDE ? 0 : w;
     const int stride_lanes = WIDE ? 64 * nw : 64;       // entries between a lane's row elements
@@ -264,7 +277,7 @@ __global__ void __launch_bounds__(64 * (WIDE ? CSR_MAX_WIDE : CSR_WAVES_PER_BLOC
             o.end = sload_i(rowptr + us + 1);
             o.zrel = 0;
             o.rem = 0;
-            o.h = sload_f((RAGGED ? a.h + model_row0 : a.h) + us);
+            o.h = sload_f((RAGGED ? a.h + model_row0 : hbase) + us);
         }
         o.d = arith32 ? sload_f((RAGGED ? a.diag + model_row0 : a.diag) + us) : 0.0f;
         return o;
@@ -758,6 +771,8 @@ __global__ void __launch_bounds__(64 * (WIDE ? CSR_MAX_WIDE : CSR_WAVES_PER_BLOC
 inline size_t csr_lds_per_replica(int sstride, int table_m, bool big = false) {
     return (size_t)(big ? sstride / 8 : sstride) + sizeof(float) * (size_t)((table_m + 2) & ~1);
 }
+// one set of rows under many field vectors (sga_set_csr_shared), as SweepArgs spells it
+inline bool csr_args_are_shared(const SweepArgs &a) { return a.reps_per_model > 0 && a.ragged == 0; }
 template <typename K>
 inline hipError_t launch_csr_kernel(K kern, const SweepArgs &a, bool wide, bool big, int waves, hipStream_t st) {
     const int slots = wide ? 1 : waves;
@@ -766,8 +781,10 @@ inline hipError_t launch_csr_kernel(K kern, const SweepArgs &a, bool wide, bool 
     if (e != hipSuccess) return e;
     const int blocks = wide ? a.R : (a.R + waves - 1) / waves;
     hipLaunchKernelGGL(kern, dim3(blocks), dim3(64 * waves), lds, st, a);
-    note_sweep_kernel("sweep_csr_kernel<acc=%d, %s, %s spins> x %d %s", a.csr_acc, wide ? "one replica per workgroup" : "narrow",
-                      big ? "bit" : "int8", waves, wide ? "wave(s)" : "replica(s) per workgroup");
+    // (", shared": one set of rows under many field vectors, sga_set_csr_shared -- the same build, another h base)
+    note_sweep_kernel("sweep_csr_kernel<acc=%d, %s, %s spins%s> x %d %s", a.csr_acc, wide ? "one replica per workgroup" : "narrow",
+                      big ? "bit" : "int8", csr_args_are_shared(a) ? ", shared" : "", waves,
+                      wide ? "wave(s)" : "replica(s) per workgroup");
     return hipGetLastError();
 }
 // the accept table is a specialisation of the production (LEAN) builds

@@ -47,7 +47,10 @@ namespace sga {
 // then added in chain order.
 // MODE: 0 = accept table, moves beyond the table computed | 1 = REAL | 2 = accept table that holds EVERY move the problem can
 // propose (a.table_covers: C3, C4 -- the beyond-the-table test and its exp path are not compiled in)
-template <int G, int EPL, bool BIG, int MODE>
+// SHARED: one set of rows under many field vectors (sga_set_csr_shared) -- see the h base below.  A build of its own: the
+// kernel runs at the SGPR limit, and two more live scalars moved 70-80 lane spills into the one-model builds of eight
+// rows per step (the run-time test alone would have been free).
+template <int G, int EPL, bool BIG, int MODE, bool SHARED = false>
 __global__ void __launch_bounds__(64 * CSR_WAVES_PER_BLOCK) sweep_csr_rows_kernel(const SweepArgs a) {
     constexpr bool REAL = MODE == 1, COVERS = MODE == 2;
     constexpr int LPR = 64 / G;   // lanes per row
@@ -63,6 +66,14 @@ __global__ void __launch_bounds__(64 * CSR_WAVES_PER_BLOCK) sweep_csr_rows_kerne
     const int r = (int)blockIdx.x * nw + w;
     if (r >= a.R) return;  // wave-uniform; no barriers in this kernel
     const int n = a.n;
+    // one set of rows under many field vectors (SHARED builds: a.reps_per_model > 0): the replica's model's h, resolved
+    // once per wave -- a scalar base, used where the one-model build uses a.h (stage_extents); the waves of a workgroup
+    // may belong to different models, spins and accept table are per wave already
+    const unsigned char *hbase = reinterpret_cast<const unsigned char *>(a.h);
+    if constexpr (SHARED) {
+        const unsigned int m = __builtin_amdgcn_readfirstlane((a.replica0 + (uint32_t)r) / (uint32_t)a.reps_per_model);
+        hbase += ((unsigned long long)m * (unsigned int)n) << 2;
+    }
     // LDS as in the narrow form of sweep_csr_kernel: [nw] spin slices, then [nw] accept tables
     const long long sbytes = BIG ? a.sstride / 8 : a.sstride;  // LDS bytes of one replica's spins
     int8_t *s = reinterpret_cast<int8_t *>(smem) + (long long)w * sbytes;
@@ -153,7 +164,7 @@ __global__ void __launch_bounds__(64 * CSR_WAVES_PER_BLOCK) sweep_csr_rows_kerne
         const unsigned char *rp = reinterpret_cast<const unsigned char *>(a.rowptr);
         st.beg = *reinterpret_cast<const int *>(rp + off);
         st.end = *reinterpret_cast<const int *>(rp + off + 4);
-        st.h = *reinterpret_cast<const float *>(reinterpret_cast<const unsigned char *>(a.h) + off);
+        st.h = *reinterpret_cast<const float *>(hbase + off);
     };
     auto stage_heads = [&](Step &st) {
         // (256 zeroed entries follow the array -- CSR_TAIL_PAD, sga_engine.cpp: a row of the wave reaches up to
@@ -394,7 +405,7 @@ bool sweep_csr_rows_applies(const SweepArgs &a) {
     return a.csr_row_cap <= 64 || (a.csr_pair_ahead == 4 && rows_table_form(a));  // longer rows: integer problems, four per step
 }
 
-template <bool BIG, int MODE>
+template <bool BIG, int MODE, bool SHARED>
 static hipError_t launch_rows(const SweepArgs &a, int waves_per_block, hipStream_t st) {
     constexpr bool REAL = MODE == 1;
     const int cap = a.csr_row_cap;  // entries of the problem's longest row (<= 64)
@@ -403,31 +414,38 @@ static hipError_t launch_rows(const SweepArgs &a, int waves_per_block, hipStream
     if (a.csr_pair_ahead == 8) {  // rows of 8 lanes
         g = 8;
         epl = cap <= 8 ? 1 : cap <= 16 ? 2 : cap <= 32 ? 4 : 8;
-        kern = epl == 1 ? sweep_csr_rows_kernel<8, 1, BIG, MODE> : epl == 2 ? sweep_csr_rows_kernel<8, 2, BIG, MODE>
-             : epl == 4 ? sweep_csr_rows_kernel<8, 4, BIG, MODE> : sweep_csr_rows_kernel<8, 8, BIG, MODE>;
+        kern = epl == 1 ? sweep_csr_rows_kernel<8, 1, BIG, MODE, SHARED> : epl == 2 ? sweep_csr_rows_kernel<8, 2, BIG, MODE, SHARED>
+             : epl == 4 ? sweep_csr_rows_kernel<8, 4, BIG, MODE, SHARED> : sweep_csr_rows_kernel<8, 8, BIG, MODE, SHARED>;
     } else {                      // rows of 16 lanes
         epl = cap <= 16 ? 1 : cap <= 32 ? 2 : cap <= 64 ? 4 : cap <= 128 ? 8 : 16;
-        kern = epl == 1 ? sweep_csr_rows_kernel<4, 1, BIG, MODE> : epl == 2 ? sweep_csr_rows_kernel<4, 2, BIG, MODE>
-             : epl == 4 ? sweep_csr_rows_kernel<4, 4, BIG, MODE> : nullptr;
+        kern = epl == 1 ? sweep_csr_rows_kernel<4, 1, BIG, MODE, SHARED> : epl == 2 ? sweep_csr_rows_kernel<4, 2, BIG, MODE, SHARED>
+             : epl == 4 ? sweep_csr_rows_kernel<4, 4, BIG, MODE, SHARED> : nullptr;
         if constexpr (!REAL) {
-            if (epl == 8) kern = sweep_csr_rows_kernel<4, 8, BIG, MODE>;
-            if (epl == 16) kern = sweep_csr_rows_kernel<4, 16, BIG, MODE>;
+            if (epl == 8) kern = sweep_csr_rows_kernel<4, 8, BIG, MODE, SHARED>;
+            if (epl == 16) kern = sweep_csr_rows_kernel<4, 16, BIG, MODE, SHARED>;
         }
         if (!kern) return hipErrorInvalidValue;
     }
     const hipError_t e = launch_csr_kernel(kern, a, false, BIG, waves_per_block, st);
-    note_sweep_kernel("sweep_csr_rows_kernel<%d rows, %d entries per lane, %s spins, %s> x %d replica(s) per workgroup", g, epl,
-                      BIG ? "bit" : "int8", REAL ? "fp64 canonical sums" : "accept table", waves_per_block);
+    note_sweep_kernel("sweep_csr_rows_kernel<%d rows, %d entries per lane, %s spins, %s%s> x %d replica(s) per workgroup", g, epl,
+                      BIG ? "bit" : "int8", REAL ? "fp64 canonical sums" : "accept table", SHARED ? ", shared" : "",
+                      waves_per_block);
     return e;
 }
 
-hipError_t launch_sweep_csr_rows(const SweepArgs &a, int waves_per_block, hipStream_t st) {
+template <bool SHARED>
+static hipError_t launch_rows_mode(const SweepArgs &a, int waves_per_block, hipStream_t st) {
     // Everything but the accept-table class -- real-valued couplings, integer problems with larger sums -- runs the
     // fp64 builds (exact for integers too).  Table builds: with or without the beyond-the-table path (a.table_covers).
     const bool table = rows_table_form(a);
-    if (table && a.table_covers) return a.big ? launch_rows<true, 2>(a, waves_per_block, st) : launch_rows<false, 2>(a, waves_per_block, st);
-    if (a.big) return table ? launch_rows<true, 0>(a, waves_per_block, st) : launch_rows<true, 1>(a, waves_per_block, st);
-    return table ? launch_rows<false, 0>(a, waves_per_block, st) : launch_rows<false, 1>(a, waves_per_block, st);
+    if (table && a.table_covers)
+        return a.big ? launch_rows<true, 2, SHARED>(a, waves_per_block, st) : launch_rows<false, 2, SHARED>(a, waves_per_block, st);
+    if (a.big) return table ? launch_rows<true, 0, SHARED>(a, waves_per_block, st) : launch_rows<true, 1, SHARED>(a, waves_per_block, st);
+    return table ? launch_rows<false, 0, SHARED>(a, waves_per_block, st) : launch_rows<false, 1, SHARED>(a, waves_per_block, st);
+}
+
+hipError_t launch_sweep_csr_rows(const SweepArgs &a, int waves_per_block, hipStream_t st) {
+    return csr_args_are_shared(a) ? launch_rows_mode<true>(a, waves_per_block, st) : launch_rows_mode<false>(a, waves_per_block, st);
 }
 
 }  // namespace sga

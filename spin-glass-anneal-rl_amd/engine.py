@@ -339,6 +339,29 @@ class AnnealEngine:
         self.n, self.R, self.n_models = n, 0, 1
         self._sizes = None
 
+    def set_csr_shared(self, rowptr, colidx, val, H):
+        """One set of CSR rows under many field vectors (sga_set_csr_shared): rowptr [n + 1], colidx, val as in set_csr
+        (int32 extents), H [M, n] (numpy or torch, host or device).  Replicas are split evenly over the M models, one
+        ladder per model; the entries are held once and every one-wave-per-replica CSR form is served.  A refused input
+        (bad extents, a column out of range, a non-finite value) leaves the problem the engine held in place."""
+        rp, k1 = _buf(rowptr, np.int32, "int32")
+        ci, k2 = _buf(colidx, np.int32, "int32")
+        vp, k3 = _buf(val, np.float32, "float32")
+        n = (k1.numel() if _is_tensor(k1) else k1.size) - 1
+        nnz = k2.numel() if _is_tensor(k2) else k2.size
+        if k3 is not None and (k3.numel() if _is_tensor(k3) else k3.size) != nnz:
+            raise AnnealingError("CSR values must have one entry per column index")
+        if not _is_tensor(H):
+            H = np.asarray(H, dtype=np.float32)
+        if H.ndim != 2 or H.shape[1] != n or H.shape[0] < 1:
+            raise AnnealingError("shared-coupling fields must be [M, n]")
+        M = int(H.shape[0])
+        hp, k4 = _buf(H, np.float32, "float32")
+        N.check(self._lib.sga_set_csr_shared(self._h, rp, ci, vp, hp, int(n), int(nnz), M), "sga_set_csr_shared")
+        del k1, k2, k3, k4
+        self.n, self.R, self.n_models = n, 0, M
+        self._sizes = None
+
     def set_csr_batch(self, problems):
         """Many independent sparse models of any sizes in one engine (sga_set_csr_batch): `problems` is a list of
         (rowptr, colidx, val, h) with model-local columns.  Replicas are split evenly over the models (R a multiple of
