@@ -621,7 +621,8 @@ int sga_set_tuning(sga_engine *e, int waves_per_replica, int sweeps_per_launch);
  * it was measured on: the next sga_set_* call returns to the caller's own values -- what the caller last passed to
  * sga_set_tuning and sga_set_option("csr_updates_per_step"), or the defaults -- sga_get_option reads the caller's value
  * again and the table of sga_get_autotune_table is empty.  Dense problems under option "row_shared" = 2 also time the row-shared windows at W = 256, 512 and
- * 1024 on the winning geometry (table entries "row-shared:W<W>") and keep the fastest where it beats the fastest
+ * 1024 on the winning geometry, each after 16 untimed sweeps at that window from the saved state (the form's time depends on
+ * the acceptance, which falls steeply in the first sweeps of a run), over at least 16 timed sweeps (table entries "row-shared:W<W>") and keep the fastest where it beats the fastest
  * geometry by more than 1 %; *best_ms_per_sweep is the fastest GEOMETRY's figure either way.  No-op for sga_set_tsp problems.
  * (No reference counterpart: the reference has no launch geometry.) */
 int sga_autotune(sga_engine *e, double *best_ms_per_sweep);

@@ -115,6 +115,12 @@ static int autotune_csr(sga_engine *e, double *best_ms_per_sweep) {
     return SGA_OK;
 }
 
+// Untimed sweeps ahead of each row-shared window trial.  A run that starts from random spins accepts a large share of
+// its proposals in its first sweep (C2a: 29 % over the whole ladder) and a small one a dozen sweeps later (1.2 %), near
+// where it then stays for thousands of sweeps: DESIGN.md 7 has C2a's acceptance per sweep for sweeps 1 ... 30.  The
+// burn-in is the first sweep after which it changes by less than 10 % per sweep (12), rounded up to a power of two.
+constexpr int RS_TRIAL_BURN_IN = 16;
+
 // Measured choice of the dense launch geometry.  Every candidate (waves per replica) runs the
 // real sweep kernel on the real replicas for a trial; the chain does not depend on the geometry,
 // and spins / energies / best states / counters are put back afterwards, so the run continues
@@ -264,10 +270,12 @@ int sga_autotune(sga_engine *e, double *best_ms_per_sweep) {
                 best_w = w;
                 break;
             }
-    // Row-shared windows (sweep_dense_rs.hip, option "row_shared" = 2): W = 256, 512, 1024 timed on the winner's layout
-    // the same way, appended to the table as "row-shared:W<W>"; the form is kept only where it beats the fastest
-    // geometry by more than the same 1 % (ties go to the row-per-proposal kernel).  *best_ms_per_sweep stays the
-    // fastest geometry's figure.
+    // Row-shared windows (sweep_dense_rs.hip, option "row_shared" = 2): W = 256, 512, 1024 timed on the winner's layout,
+    // appended to the table as "row-shared:W<W>"; the form is kept only where it beats the fastest geometry by more
+    // than the same 1 % (ties go to the row-per-proposal kernel).  *best_ms_per_sweep stays the fastest geometry's
+    // figure.  Unlike a geometry's, the time of this form depends on the acceptance -- every accept of a window costs
+    // corrections in every later block, the more the longer the window -- so each W is timed after RS_TRIAL_BURN_IN
+    // sweeps at that W from the saved state (layout() puts the state back before each trial and after the last).
     e->rs_suspend = false;
     if (rc == SGA_OK && best_w >= 0 && e->opt[OPT_ROW_SHARED] == 2) {
         double best_rs = 1e300;
@@ -277,11 +285,13 @@ int sga_autotune(sga_engine *e, double *best_ms_per_sweep) {
             if (row_shared_window(e, true) != W) break;  // (the problem does not admit the form)
             rc = layout(best_w);
             if (rc != SGA_OK) break;
-            double t1 = 0.0, t = 0.0;
-            rc = timed(1, t1);
+            // burn-in at this W (untimed), then at least as many timed sweeps: the trial runs in the regime the run is in
+            double tb = 0.0, t = 0.0;
+            rc = timed(RS_TRIAL_BURN_IN, tb);
             if (rc != SGA_OK) break;
             if (std::strncmp(sga::last_sweep_kernel(), "sweep_dense_rs", 14) != 0) break;  // (its scratch was not to be had)
-            const int k = t1 > 0.0 ? (int)std::min(64.0, std::max(1.0, std::ceil(2.0 / t1))) : 1;
+            const int k = tb > 0.0 ? (int)std::min(64.0, std::max((double)RS_TRIAL_BURN_IN, std::ceil(2.0 * RS_TRIAL_BURN_IN / tb)))
+                                   : RS_TRIAL_BURN_IN;
             rc = timed(k, t);
             if (rc != SGA_OK) break;
             char item[64];
