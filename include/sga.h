@@ -586,6 +586,14 @@ int sga_set_field_cache(sga_engine *e, int mode);
  *                           replica that proposes it, the chain then walked per replica with exact corrections for the
  *                           window's earlier accepts.  Same chain.  0 = never, 1 = wherever it applies (W: option
  *                           "row_shared_window"), 2 = where sga_autotune measured it ahead of every geometry by more than 1 % [sweep; SGA_ROW_SHARED]
+ *   "row_shared_grid"       0 (default) | 1   (version >= 1800) opens the row-shared windows to dense problems the integer form
+ *                           does not take: every J_ij a multiple of 2^-k (k <= 30, integer J: k = 0) with 2^k |J_ij| <= 255
+ *                           and 2^k max_i (sum_j |J_ij| + |h_i|) < 2^24, J symmetric with a zero diagonal and not all zero, h
+ *                           ANY finite fp32 (quarter-valued QUBO encodings, integer J beside a real-valued h).  The planes hold
+ *                           2^k J, the chain decides with the row kernels' general rule: same chain.  Acts where "row_shared"
+ *                           does (field cache off; 1 forces the form, 2 lets sga_autotune time it); a shared-coupling batch
+ *                           qualifies as a whole (k, planes and the bound over the batch).  0: nothing changes
+ *                                                                                          [sweep; SGA_ROW_SHARED_GRID]
  *   "row_shared_window"     0 (default) | 256 | 512 | 1024 (other values: rounded down): W under "row_shared" = 1 (0: the
  *                           autotuner's, else 1024)                                      [sweep; SGA_ROW_SHARED_WINDOW]
  *   "ragged_field_cache"    0 (default) | 1   ragged CSR batches (sga_set_csr_batch): the int16 cached-field sweep of
@@ -678,7 +686,8 @@ typedef struct sga_route_query {
     /* sga_set_groups_csr (version >= 1200): the stored remainder, 0 = none */
     int64_t rest_nnz;     /* entries */
     int32_t rest_max_row; /* entries of the longest row */
-    int32_t reserved2_;
+    int32_t rs_grid;      /* dense (version >= 1800): 0 = the set-time scan gave no grid verdict for the row-shared windows
+                             (option "row_shared_grid"), else 1 + k: J on the grid 2^-k */
 } sga_route_query;
 /* zeroes *q and fills the option defaults (the environment is NOT consulted), cus = 256, n_models = 1 */
 int sga_route_query_init(sga_route_query *q);

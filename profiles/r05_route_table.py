@@ -22,9 +22,10 @@ import spin_glass_anneal_rl_amd as sg  # noqa: E402
 from spin_glass_anneal_rl_amd import _native as N  # noqa: E402
 
 # (n_groups / group_max, rest_nnz / rest_max_row: appended for sga_set_groups / sga_set_groups_csr queries, 0 for every
-# problem of this table -- dense, CSR, TSP; shared_j: in the place of reserved_ for sga_set_dense_shared, 0 likewise)
+# problem of this table -- dense, CSR, TSP; shared_j: in the place of reserved_ for sga_set_dense_shared, 0 likewise;
+# rs_grid: in the place of reserved2_, the grid verdict of option "row_shared_grid" -- no recorded answer depends on it)
 FIELDS = [f for f, _ in N.RouteQuery._fields_
-          if f not in ("opt", "reserved_", "shared_j", "n_groups", "group_max", "rest_nnz", "rest_max_row", "reserved2_")]
+          if f not in ("opt", "reserved_", "shared_j", "n_groups", "group_max", "rest_nnz", "rest_max_row", "reserved2_", "rs_grid")]
 
 
 def query_dict(q):

@@ -35,7 +35,7 @@ class RouteQuery(C.Structure):
                [(k, C.c_int32) for k in ("slotted", "rowptr32", "packed_ok", "n_cities", "sstride", "shared_j")] + \
                [("ldj", C.c_int64), ("opt", C.c_int64 * ROUTE_MAX_OPTS)] + \
                [("n_groups", C.c_int32), ("group_max", C.c_int32)] + \
-               [("rest_nnz", C.c_int64), ("rest_max_row", C.c_int32), ("reserved2_", C.c_int32)]
+               [("rest_nnz", C.c_int64), ("rest_max_row", C.c_int32), ("rs_grid", C.c_int32)]
 
 
 # every symbol include/sga.h declares: (name, restype, argtypes)

@@ -222,6 +222,7 @@ DenseClass classify_dense(const int hflags[8], int n, int n_models, int storage,
     // batch qualifies as a whole: the scans above run over all stacked rows, so scale, field width, accept table and
     // max |J| are batch-wide -- a field kept at scale 2 or as int32 because ANOTHER model needs it is still exact
     c.row_abs_max = m;
+    c.j_max = jm;
     c.j_abs_max = (int)std::min(std::ceil((double)jm), 16777216.0);
     c.clf_scale = (c.nonint & 2u) ? 2 : 1;
     c.clf_problem = (c.nonint & 5u) == 0u && (double)m * c.clf_scale < 16777216.0 && c.consistent_dE;
@@ -255,6 +256,36 @@ FxVerdict dense_fixed_point(const DenseClass &c, int n_models, const std::functi
     q.canonical = c.acc_canon;
     q.consistent_dE = c.consistent_dE;
     return fixed_point_verdict(q, diagonal);
+}
+
+// Every J_ij is an integer multiple of 2^-k (k = minus the exponent of the lowest set bit of any J, clamped at 0 as
+// dense_fixed_point clamps it), so the planes of 2^k J are integer planes; a row sum is 2^-k times an integer D with
+// |D| <= 2^k max_i sum_j |J_ij| < 2^24 (row_abs_max, which includes |h_i|, bounds that maximum from above; fx_bound
+// allows for its fp32 rounding), so every partial sum is exact in fp32 in any order and fp32(2^-k D) is the row
+// kernels' dot.  h stays outside the sums: any finite fp32 value.  The planes follow sga::row_shared_planes
+// (sweep_dense_rs.hip) on the scaled maximum -- 1 | 3 | 8 for up to 1 | 7 | 255 -- written out here: this file calls no
+// kernel header.
+RsGridVerdict row_shared_grid(const DenseClass &c) {
+    RsGridVerdict v;
+    const int k = c.span.any ? std::max(0, -c.span.lo) : 0;
+    const double scaled = k <= RS_GRID_MAX_K ? std::ldexp((double)c.j_max, k) : 0.0;
+    if (c.table_m > 0 && !c.acc64)
+        v.why = "row-shared windows (grid): an integer problem, the integer form of the windows serves it";
+    else if (!c.consistent_dE)
+        v.why = "row-shared windows (grid): J must be symmetric with a zero diagonal";
+    else if (!c.span.any)
+        v.why = "row-shared windows (grid): J is all zero";
+    else if (k > RS_GRID_MAX_K)
+        v.why = "row-shared windows (grid): the couplings need a grid finer than 2^-30";
+    else if (!(scaled <= 255.0))
+        v.why = "row-shared windows (grid): 2^k max |J_ij| exceeds 255 (bit-planes of |2^k J|)";
+    else if (!(fx_bound(c.row_abs_max, k) < 16777216.0))
+        v.why = "row-shared windows (grid): 2^k max_i (sum_j |J_ij| + |h_i|) is not below 2^24";
+    else if (c.acc_canon)
+        v.why = "row-shared windows (grid): the couplings need the canonical fp64 summation order";
+    else
+        v.k = k, v.planes = scaled <= 1.0 ? 1 : scaled <= 7.0 ? 3 : 8;
+    return v;
 }
 
 TspClass classify_tsp(const BitSpan &span, bool integral, double worst_row, int n_cities) {

@@ -86,6 +86,7 @@ struct DenseClass {
     unsigned nonint = 0;  // bit 0: some J, bit 1: some h not an integer, bit 2: some h not a multiple of 1/2
     int table_m = 0, clf_scale = 1, clf_bits = 16, j_abs_max = 0;
     float row_abs_max = 0.0f;
+    float j_max = 0.0f;   // max |J_ij| as the scan wrote it (word [7]; j_abs_max is its ceiling)
     BitSpan span;
 };
 // hflags: the eight words of launch_scan_values / launch_dense_row_abs_max / launch_check_symmetric
@@ -94,6 +95,16 @@ DenseClass classify_dense(const int hflags[8], int n, int n_models, int storage,
 const char *dense_clf_why(const DenseClass &c, const std::function<bool()> &diagonal);
 // batch_allowed (option "batch_fixed_point"): a many-model batch gets the one-model verdict over its stacked scan
 FxVerdict dense_fixed_point(const DenseClass &c, int n_models, const std::function<bool()> &diagonal, bool batch_allowed = false);
+
+// Row-shared windows on a binary grid (option "row_shared_grid", sweep_dense_rs.hip): the dense problems the integer
+// form of the windows does not take -- J on a grid 2^-k whose scaled values 2^k J_ij are integers of at most 255, every
+// scaled row sum below 2^24 -- under any finite fp32 h.  A shared-coupling batch hands in the batch's words.
+constexpr int RS_GRID_MAX_K = 30;  // a declared limit (2^k is formed as an int and as a float)
+struct RsGridVerdict {
+    int k = 0, planes = 0;      // the grid 2^-k and the magnitude planes of |2^k J| (1 | 3 | 8) where the form applies
+    const char *why = nullptr;  // else the first condition that fails
+};
+RsGridVerdict row_shared_grid(const DenseClass &c);
 
 // ---- implicit couplings --------------------------------------------------------------------------------------------------
 struct TspClass {

@@ -50,6 +50,7 @@ sga_route_query route_query_of(const sga_engine *e) {
     q.group_max = e->groups ? e->g_max_size : 0;
     q.rest_nnz = e->groups ? e->group_args.rest.nnz : 0;
     q.rest_max_row = e->groups ? e->group_args.rest.max_row : 0;
+    q.rs_grid = (!e->csr && !e->implicit() && e->rs_grid_planes > 0) ? 1 + e->rs_grid_k : 0;
     q.sstride = e->sstride;
     q.ldj = e->ldj;
     for (int i = 0; i < OPT_COUNT; ++i) q.opt[i] = e->opt[i];
@@ -130,12 +131,24 @@ int fields_pass(sga_engine *e, int r0, int count, double *energy, void *fields) 
 // accept table); a stacked batch has a row i per model and stays on the row-per-proposal kernel.
 // 1 = wherever it applies (W: option "row_shared_window", else the autotuner's, else 1024), 2 = where sga_autotune
 // measured it ahead (default).
+// Option "row_shared_grid" = 1 opens the form to the problems the integer form does not take and the set-time verdict
+// admits (sga_classify.cpp, row_shared_grid: J on a grid 2^-k, |2^k J| <= 255, scaled row sums below 2^24, any h) under
+// the same remaining conditions; the chain then decides with the row kernels' general rule instead of the table's.
+int row_shared_form_planes(const sga_engine *e, int *grid) {
+    *grid = 0;
+    if (e->table_m > 0 && !e->acc64) return sga::row_shared_planes(e->j_abs_max);
+    if (e->opt[OPT_ROW_SHARED_GRID] != 1 || e->rs_grid_planes == 0) return 0;
+    *grid = 1 + e->rs_grid_k;
+    return e->rs_grid_planes;
+}
+
 int row_shared_window(const sga_engine *e, bool lean) {
     const long long o = e->opt[OPT_ROW_SHARED];
+    int grid = 0;
     if (o == 0 || e->rs_suspend || !lean || e->rule != SGA_RULE_METROPOLIS || e->field_cache != SGA_FIELD_CACHE_OFF) return 0;
-    if (e->csr || e->implicit() || e->ragged || (e->n_models != 1 && !e->shared_j) || e->table_m <= 0 || e->acc64 || !e->consistent_dE) return 0;
+    if (e->csr || e->implicit() || e->ragged || (e->n_models != 1 && !e->shared_j) || !e->consistent_dE) return 0;
     if (e->opt[OPT_LOOK_AHEAD] == 0 || e->opt[OPT_FORCE_GENERAL] != 0 || !e->J_packed) return 0;
-    if (sga::row_shared_planes(e->j_abs_max) == 0 || (long long)e->R * e->n >= (1ll << 31) || e->R >= (1 << 20)) return 0;
+    if (row_shared_form_planes(e, &grid) == 0 || (long long)e->R * e->n >= (1ll << 31) || e->R >= (1 << 20)) return 0;
     if (o == 2) return e->rs_tuned_w;
     const long long fw = e->opt[OPT_ROW_SHARED_WINDOW];  // (option "row_shared_window": W for option 1)
     return fw >= 1024 ? 1024 : fw >= 512 ? 512 : fw >= 256 ? 256 : (e->rs_tuned_w > 0 ? e->rs_tuned_w : 1024);
@@ -144,10 +157,12 @@ int row_shared_window(const sga_engine *e, bool lean) {
 // the form's scratch for W and, where the problem gets them, its resident bit-planes of J: false (and the
 // row-per-proposal kernel runs) if either cannot be had
 static bool ensure_row_shared(sga_engine *e, int W, hipStream_t st) {
-    if (e->rs.cnt && e->rs.W == W && e->rs_R == e->R && e->rs_n == e->n) return true;
+    int grid = 0;
+    const int planes = row_shared_form_planes(e, &grid);
+    if (e->rs.cnt && e->rs.W == W && e->rs_R == e->R && e->rs_n == e->n && e->rs_grid == grid) return true;
     e->free_row_shared();
     const size_t n = (size_t)e->n, R = (size_t)e->R, nwin = (n + (size_t)W - 1) / (size_t)W;
-    const int nw32 = sga::row_shared_nw32(e->n), planes = sga::row_shared_planes(e->j_abs_max);
+    const int nw32 = sga::row_shared_nw32(e->n);
     const int log_rg = sga::row_shared_log_group(e->n, W);
     const size_t groups = (R + ((size_t)1 << log_rg) - 1) >> log_rg;
     hipError_t he = hipSuccess;
@@ -155,7 +170,8 @@ static bool ensure_row_shared(sga_engine *e, int W, hipStream_t st) {
         he = hipMalloc(&e->rs_jp, sga::row_shared_plane_bytes(e->n, planes));
         if (he == hipSuccess) he = hipMalloc(&e->rs_jabs, sizeof(int) * n);
         if (he == hipSuccess)
-            he = sga::launch_rs_build_planes(e->J_packed, e->want_i8, e->ldj, e->n, planes, e->rs_jp, e->rs_jabs, st);
+            he = sga::launch_rs_build_planes(e->J_packed, e->want_i8, e->ldj, e->n, planes, grid ? grid - 1 : 0, e->rs_jp,
+                                             e->rs_jabs, st);
         if (he != hipSuccess) {
             dev_free(e->rs_jp);
             dev_free(e->rs_jabs);
@@ -178,6 +194,7 @@ static bool ensure_row_shared(sga_engine *e, int W, hipStream_t st) {
     e->rs.log_w = lw;
     e->rs.nw32 = nw32;
     e->rs.planes = planes;
+    e->rs_grid = grid;
     e->rs.jp = e->rs_jp;
     e->rs.jabs = e->rs_jabs;
     e->rs.log_rg = log_rg;
@@ -410,7 +427,7 @@ int ensure_packed(sga_engine *e) {
 extern "C" {
 
 const char *sga_last_error(void) { return g_last_error.c_str(); }
-int sga_version(void) { return 1700; }  // + sga_set_csr_shared (one set of CSR rows, many field vectors)  // 1600: + sga_set_dense_shared (one coupling matrix, many field vectors), sga_route_query.shared_j  // 1500: + sga_get_scan_summary; the dense and CSR setters refuse non-finite J / h  // 1400: + option "batch_fixed_point": fixed-point cached local fields for many-model dense batches (sweep_clf_fx.hip, MODELS)  // 1300: + options "ragged_field_cache" and "clf_fixed_point" together: fixed-point cached local fields for ragged CSR batches (sweep_clf_csr.hip)  // 1200: + sga_set_groups_csr (group couplings plus a stored sparse remainder, sweep_groups.hip)  // 1100: + option "ragged_field_cache" (cached local fields for ragged CSR batches, sweep_clf_csr.hip)  // 1000: + sga_set_groups (implicit cardinality-group couplings, sweep_groups.hip)  // 900: + cached local fields for many-model dense batches (sga_set_dense_batch)  // 800: + option "clf_fixed_point" over dense couplings (sweep_clf_fx.hip)  // 700: + option "clf_fixed_point" (cached fields of real-valued CSR couplings)  // 600: + sga_set_csr_batch / sga_get_batch_model (ragged CSR batches)  // round 5: + sga_explain_route / sga_get_route_query, sga_get_last_kernel, sga_get_autotune_table, ladder-local sga_exchange
+int sga_version(void) { return 1800; }  // + option "row_shared_grid": row-shared windows for dense J on a binary grid under any h (sweep_dense_rs.hip, GRID), sga_route_query.rs_grid  // 1700: + sga_set_csr_shared (one set of CSR rows, many field vectors)  // 1600: + sga_set_dense_shared (one coupling matrix, many field vectors), sga_route_query.shared_j  // 1500: + sga_get_scan_summary; the dense and CSR setters refuse non-finite J / h  // 1400: + option "batch_fixed_point": fixed-point cached local fields for many-model dense batches (sweep_clf_fx.hip, MODELS)  // 1300: + options "ragged_field_cache" and "clf_fixed_point" together: fixed-point cached local fields for ragged CSR batches (sweep_clf_csr.hip)  // 1200: + sga_set_groups_csr (group couplings plus a stored sparse remainder, sweep_groups.hip)  // 1100: + option "ragged_field_cache" (cached local fields for ragged CSR batches, sweep_clf_csr.hip)  // 1000: + sga_set_groups (implicit cardinality-group couplings, sweep_groups.hip)  // 900: + cached local fields for many-model dense batches (sga_set_dense_batch)  // 800: + option "clf_fixed_point" over dense couplings (sweep_clf_fx.hip)  // 700: + option "clf_fixed_point" (cached fields of real-valued CSR couplings)  // 600: + sga_set_csr_batch / sga_get_batch_model (ragged CSR batches)  // round 5: + sga_explain_route / sga_get_route_query, sga_get_last_kernel, sga_get_autotune_table, ladder-local sga_exchange
 
 int sga_create(int device, sga_engine **out) {
     if (!out) return fail(SGA_ERR_INVALID, "out is NULL");
@@ -1096,7 +1113,7 @@ hipError_t launch_sweep(sga_engine *e, const SweepPlan &p, sga::SweepArgs a, hip
     if (e->groups) return sga::launch_sweep_groups(a, e->group_args, e->waves, st);
     if (e->tsp) return sga::launch_sweep_tsp(a, e->tsp_args, e->tsp_waves, e->tsp_passes, st);
     if (e->csr) return sga::launch_sweep_csr(a, e->waves, st);
-    if (p.rs_w) return sga::launch_sweep_dense_rs(a, e->rs, e->want_i8, st);
+    if (p.rs_w) return sga::launch_sweep_dense_rs(a, e->rs, e->want_i8, st, e->rs_grid);
     return launch_dense_rows(e, a, st);
 }
 

@@ -244,10 +244,14 @@ struct sga_engine {
     // rs_jp / rs_jabs: the resident bit-planes of J_packed and sum_j |J_ij| per row (RowSharedPlan::jp, jabs), built by
     // the form's first sweep of a problem.  They belong to the problem, not to W or the replicas: free_problem -- the
     // one place J_packed is replaced -- drops them, window and replica changes keep them.
+    // rs_grid_planes / rs_grid_k: the set-time verdict of the grid form (option "row_shared_grid", sga_classify.cpp:
+    // row_shared_grid) -- planes of |2^k J| (0: no verdict) and k; a shared-coupling batch: over the batch's words.
     int rs_tuned_w = 0;
+    int rs_grid_planes = 0, rs_grid_k = 0;
     bool rs_suspend = false;
     sga::RowSharedPlan rs{};
     int rs_R = 0, rs_n = 0;
+    int rs_grid = 0;  // what rs was prepared for: 0 the integer form, else 1 + k (launch_sweep_dense_rs)
     unsigned long long *rs_jp = nullptr;
     int *rs_jabs = nullptr;
     void free_row_shared() {
@@ -259,6 +263,7 @@ struct sga_engine {
         dev_free(rs.bits);
         rs = sga::RowSharedPlan{};
         rs_R = rs_n = 0;
+        rs_grid = 0;
     }
     int csr_acc = sga::CSR_ACC_F64_CANON;  // CSR: how the sweep kernels form a row sum (set time)
     // what the set-time scans wrote, as read back by the setter (sga_get_scan_summary): dense the eight words of
@@ -352,6 +357,8 @@ struct sga_engine {
         dev_free(rs_jp);
         dev_free(rs_jabs);
         rs_tuned_w = 0;
+        rs_grid_planes = 0;
+        rs_grid_k = 0;
         // every other problem-scoped member back to its declared default: what one problem's setter computed is never
         // the next problem's, whichever setter that is and whether or not it assigns the member itself
         // (tests/test_engine_reuse_host.py holds the struct's "// problem" section against this function)
@@ -448,6 +455,8 @@ int ensure_fields(sga_engine *e);
 int recompute_energy_range(sga_engine *e, int r0, int count);
 int ensure_packed(sga_engine *e);
 int row_shared_window(const sga_engine *e, bool lean);
+// magnitude planes of the row-shared form that serves the problem (0: none); *grid: 0 the integer form, else 1 + k
+int row_shared_form_planes(const sga_engine *e, int *grid);
 // ---- sga_problem.cpp
 bool csr_rows_medium(const sga_engine *e);
 int csr_updates_per_step(const sga_engine *e);

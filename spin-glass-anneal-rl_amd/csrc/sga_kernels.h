@@ -433,6 +433,13 @@ struct RowSharedPlan {
     int W, log_w, nw32, planes;  // planes: magnitude bit-planes of |J| (1 | 3 | 8)
     int log_rg, n_groups;        // replicas per group of the plan (a power of two), groups
 };
+// What the GRID instantiations take instead (option "row_shared_grid"): the planes hold 2^k J, the chain works in real
+// units and decides with the row kernels' general rule.  A type of its own, so that the kernels of the integer form
+// keep their arguments byte for byte.
+struct RowSharedGridPlan {
+    RowSharedPlan p;
+    int k;
+};
 int row_shared_planes(int j_abs_max);  // 0: |J| beyond 255, the form does not apply
 inline int row_shared_nw32(int n) { return 8 * ((n + 255) / 256); }
 inline int row_shared_scan_chunks(int n) { return (n + 1023) / 1024; }  // workgroups of the scan per window
@@ -451,12 +458,14 @@ inline int row_shared_log_group(int n, int W) {
     while ((1 << l) < nwin) ++l;
     return l;
 }
-// one pass over J: jp and jabs of every row (the first time the form is prepared for a problem)
-hipError_t launch_rs_build_planes(const void *J, bool j_is_i8, long long ldj, int n, int planes, unsigned long long *jp,
-                                  int *jabs, hipStream_t st);
+// one pass over J: jp and jabs of every row (the first time the form is prepared for a problem); grid_k: the planes
+// and jabs are those of 2^k J (fp32 rows; 0: of J itself)
+hipError_t launch_rs_build_planes(const void *J, bool j_is_i8, long long ldj, int n, int planes, int grid_k,
+                                  unsigned long long *jp, int *jabs, hipStream_t st);
 // a.n_sweeps sweeps: spins -> bits, then per sweep the plan, per window fields + chain, best tracking.  Production
 // arguments only (Philox sites, Metropolis with the accept table, fp64 rule, no per-update traces, all replicas).
-hipError_t launch_sweep_dense_rs(const SweepArgs &a, const RowSharedPlan &p, bool j_is_i8, hipStream_t st);
+// grid: 0 the integer form; else 1 + k, the GRID instantiations (J on the grid 2^-k, any h: the general fp64 rule).
+hipError_t launch_sweep_dense_rs(const SweepArgs &a, const RowSharedPlan &p, bool j_is_i8, hipStream_t st, int grid = 0);
 
 // operator-form PT exchange (cuda_kernels.py:415-443): decide sequentially, then permute rows
 hipError_t launch_op_exchange(float *spins, float *tmp_rows, float *energies, const float *temps,

@@ -731,6 +731,14 @@ std::string explain(const Query &q0) {
         if (q.opt[OPT_ROW_SHARED] == 1 && q.field_cache == SGA_FIELD_CACHE_OFF && (q.n_models == 1 || q.shared_j) && q.table_m > 0 &&
             q.clf_ok && (q.acc == 0 || i8) && q.opt[OPT_LOOK_AHEAD] != 0 && q.opt[OPT_FORCE_GENERAL] == 0)
             out += " sweep=row-shared(W=1024)";
+        // option "row_shared_grid" = 1 beside it: the problems the integer form does not take whose J lies on a binary
+        // grid (rs_grid = 1 + k: the set-time verdict of sga_classify.cpp, row_shared_grid), under the same conditions
+        else if (q.opt[OPT_ROW_SHARED] == 1 && q.opt[OPT_ROW_SHARED_GRID] == 1 && q.rs_grid > 0 &&
+                 q.field_cache == SGA_FIELD_CACHE_OFF && (q.n_models == 1 || q.shared_j) && q.clf_ok &&
+                 q.opt[OPT_LOOK_AHEAD] != 0 && q.opt[OPT_FORCE_GENERAL] == 0) {
+            std::snprintf(buf, sizeof(buf), " sweep=row-shared(W=1024 grid=2^-%d)", q.rs_grid - 1);
+            out += buf;
+        }
         q.sstride = (int)g.ld;
     }
     // what sga_set_field_cache would run

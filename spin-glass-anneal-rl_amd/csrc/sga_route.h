@@ -30,8 +30,8 @@ enum Opt {
     OPT_LOOK_AHEAD, OPT_CLF_WAVES, OPT_SPARSE_ROUTE, OPT_BATCHED_ENERGY, OPT_FORCE_GENERAL, OPT_CSR_UPDATES_PER_STEP,
     OPT_TSP_PARALLEL, OPT_FORCE_CSR_BITS, OPT_CSR_BITS, OPT_CSR_SLOTS, OPT_HALF_TABLE, OPT_FORCE_CSR_ACC,
     OPT_FORCE_DENSE_CANON, OPT_ZERO_SLOT_EVERY, OPT_REPLICA_ROUTING, OPT_FIELDS_SCRATCH_MB, OPT_CLF_BATCHED,
-    OPT_CLF_TAIL_WAVES, OPT_CLF_FIXED_POINT, OPT_ROW_SHARED, OPT_ROW_SHARED_WINDOW, OPT_BATCH_FIXED_POINT,
-    OPT_RAGGED_FIELD_CACHE, OPT_COUNT
+    OPT_CLF_TAIL_WAVES, OPT_CLF_FIXED_POINT, OPT_ROW_SHARED, OPT_ROW_SHARED_GRID, OPT_ROW_SHARED_WINDOW,
+    OPT_BATCH_FIXED_POINT, OPT_RAGGED_FIELD_CACHE, OPT_COUNT
 };
 struct OptDef {
     const char *key;
@@ -62,9 +62,10 @@ constexpr OptDef OPT_DEFS[OPT_COUNT] = {
     {"clf_tail_waves", "SGA_NO_CLF_TAIL_WAVES", 1, 0, 1, 0, 1, 0},
     {"clf_fixed_point", nullptr, 0, 0, 0, 0, 1, 2},
     {"row_shared", "SGA_ROW_SHARED", 0, 0, 2, 0, 2, 0},
+    {"row_shared_grid", "SGA_ROW_SHARED_GRID", 0, 0, 0, 0, 1, 0},
     {"row_shared_window", "SGA_ROW_SHARED_WINDOW", 0, 0, 0, 0, 1024, 0},
-    // ("ragged_field_cache" stays the last entry; every option before "batch_fixed_point" keeps its index, and queries name
-    //  options by key -- _native.route_query, tests/golden/route_table.json -- never by number)
+    // ("ragged_field_cache" stays the last entry and the list ends row_shared_window, batch_fixed_point, ragged_field_cache;
+    //  queries name options by key -- _native.route_query, tests/golden/route_table.json -- never by number)
     {"batch_fixed_point", "SGA_BATCH_FIXED_POINT", 0, 0, 0, 0, 1, 2},
     {"ragged_field_cache", nullptr, 0, 0, 0, 0, 1, 2},
 };

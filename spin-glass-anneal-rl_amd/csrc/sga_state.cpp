@@ -412,8 +412,13 @@ int sga_describe(sga_engine *e, char *buf, int buflen) {
     if (!e->csr && !e->implicit() && e->field_cache == SGA_FIELD_CACHE_OFF) {  // production sweeps in row-shared windows
         const int rw = row_shared_window(e, true);
         if (rw > 0) {
-            const int pl = sga::row_shared_planes(e->j_abs_max);
-            std::snprintf(tmp + std::strlen(tmp), sizeof(tmp) - std::strlen(tmp), " sweep=row-shared(W=%d planes=%d)", rw, pl);
+            int grid = 0;
+            const int pl = row_shared_form_planes(e, &grid);
+            if (grid)  // option "row_shared_grid": J on the grid 2^-k, the planes are those of 2^k J
+                std::snprintf(tmp + std::strlen(tmp), sizeof(tmp) - std::strlen(tmp), " sweep=row-shared(W=%d planes=%d grid=2^-%d)", rw,
+                              pl, grid - 1);
+            else
+                std::snprintf(tmp + std::strlen(tmp), sizeof(tmp) - std::strlen(tmp), " sweep=row-shared(W=%d planes=%d)", rw, pl);
             if (sga::row_shared_resident(e->want_i8, pl))  // (the bytes the form's first sweep adds, once per problem)
                 std::snprintf(tmp + std::strlen(tmp), sizeof(tmp) - std::strlen(tmp), " rs_fields=resident-planes(%zuB)",
                               sga::row_shared_plane_bytes(e->n, pl));

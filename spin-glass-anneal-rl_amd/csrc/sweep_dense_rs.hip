@@ -27,11 +27,40 @@
 // one-model engine holding (J, h_m) -- whose own, smaller table_m tabulates the same values expf_det(-2 q / T).
 // The window plan -- which (replica, update) proposes which site -- is one counting sort per sweep, histogrammed in
 // LDS per (window, group of replicas): no atomic of it reaches memory.
+//
+// GRID (option "row_shared_grid", RowSharedGridPlan::k): J on a binary grid, any finite fp32 h -- the problems
+// with table_m == 0 that sga_classify.cpp's row_shared_grid admits.  Every J_ij is an integer multiple of 2^-k (k <=
+// 30), |2^k J_ij| <= 255 and B = 2^k max_i sum_j |J_ij| < 2^24.  The planes and jabs are those of the integers 2^k J_ij
+// (the scaling is a power-of-two multiply of a value below 2^8: exact), so plan, fields and base are the integer
+// form's: base = D = 2^k sum_j J_ij s_j against the window-start spins, an integer with |D| <= B.  Proof that the chain
+// is the row kernels':
+//   * f = ldexpf((float)D, -k) is exact (|D| < 2^24, and the exponent stays far inside fp32's range: k <= 30).  A
+//     correction -2 J[i_a][i_t] s_a is an integer multiple of 2^-k (read as the fp32 J itself, or decoded from one
+//     magnitude plane as +-2^-k), and the corrected field is 2^-k times the row sum of 2^k J against the spins as they
+//     then stand, again at most B in magnitude.  So every partial sum of the corrected field, in ANY order of the
+//     corrections, is 2^-k times an integer below 2^24 (an intermediate state is a spin state too): exact in fp32.
+//   * The row kernel's dot for the same spins is the fp32 rounding of the exact row sum -- accumulated in fp64 where
+//     the class is f64-exact (every partial sum a multiple of 2^-k below 2^24 / 2^k: exact), in fp32 for integer J
+//     with sums below 2^24, in int32 for int8 rows -- and that sum is representable, so dot == the corrected field.
+//   * field = (double)dot + (double)h and dE = 2 s field are then formed by metropolis_accept (sweep_common.h) on the
+//     row kernels' own arguments: the same decision -- T = 0, T = inf and the 104 T cut-off with it -- and the same
+//     dE, and E += dE runs in chain order.  h never enters a sum that has to be exact.
+// A shared-coupling batch: k, the planes and the bound are the batch's (one J; the bound's word takes the largest
+// |h| of any model), each wave reads its model's h.  The non-GRID instantiations are the integer form's, unchanged:
+// the GRID ones take a plan type of their own (RowSharedGridPlan), so not even an argument offset moves in the others.
 #include <type_traits>
 
 #include "sweep_common.h"
 
 namespace sga {
+
+// the plan argument of an instantiation, and its parts
+template <bool GRID>
+using RsPlanArg = typename std::conditional<GRID, RowSharedGridPlan, RowSharedPlan>::type;
+__device__ __forceinline__ const RowSharedPlan &rs_plan(const RowSharedPlan &p) { return p; }
+__device__ __forceinline__ const RowSharedPlan &rs_plan(const RowSharedGridPlan &g) { return g.p; }
+__device__ __forceinline__ int rs_grid_k(const RowSharedPlan &) { return 0; }
+__device__ __forceinline__ int rs_grid_k(const RowSharedGridPlan &g) { return g.k; }
 
 // Spin and coupling bits share one layout: element j = 256 g + 4 l + q sits in bit l of 64-bit word 4 g + q (a lane
 // that loads four consecutive elements contributes one bit to each of four ballots).
@@ -167,8 +196,9 @@ __global__ void __launch_bounds__(256) rs_pack_kernel(const SweepArgs a, RowShar
 // ---- a row of J as bit-planes ------------------------------------------------------------------------------------
 // PL magnitude planes: |J| < 2^PL.  planes: [PL + 1][nw = 4 nseg] 64-bit words (sign plane first), in LDS or in the
 // resident copy; every word is written.  Called by a workgroup of four waves; returns this lane's share of sum |J_ij|.
-template <typename JE, int PL>
-__device__ __forceinline__ int rs_row_to_planes(const JE *row, int n, unsigned long long *planes, int lane, int wv) {
+// GRID: the planes of 2^gk J (fp32 rows on the grid 2^-gk: every scaled element an integer, the multiply exact).
+template <typename JE, int PL, bool GRID>
+__device__ __forceinline__ int rs_row_to_planes(const JE *row, int n, unsigned long long *planes, int lane, int wv, int gk) {
     const int nseg = (n + 255) >> 8, nw = 4 * nseg;
     int absum = 0;
     // four segments per wave in flight, then their ballots
@@ -179,7 +209,8 @@ __device__ __forceinline__ int rs_row_to_planes(const JE *row, int n, unsigned l
             const int e = 256 * (g0 + 4 * s) + 4 * lane;  // e < n <= ldj, e % 4 == 0: the 4-element load stays in the row
             if (g0 + 4 * s < nseg && e < n) {
                 if constexpr (std::is_same<JE, float>::value) {
-                    const float4 x = *reinterpret_cast<const float4 *>(row + e);
+                    float4 x = *reinterpret_cast<const float4 *>(row + e);
+                    if constexpr (GRID) x.x = ldexpf(x.x, gk), x.y = ldexpf(x.y, gk), x.z = ldexpf(x.z, gk), x.w = ldexpf(x.w, gk);
                     v[s][0] = (int)x.x, v[s][1] = (int)x.y, v[s][2] = (int)x.z, v[s][3] = (int)x.w;
                 } else {
                     const int x = *reinterpret_cast<const int *>(row + e);
@@ -223,7 +254,20 @@ __global__ void __launch_bounds__(256) rs_planes_kernel(const JE *J, long long l
     __shared__ int csum[4];
     const int i = blockIdx.x, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int nw = 4 * ((n + 255) >> 8);
-    int absum = rs_row_to_planes<JE, PL>(J + (long long)i * ldj, n, jp + (long long)i * (PL + 1) * nw, lane, wv);
+    int absum = rs_row_to_planes<JE, PL, false>(J + (long long)i * ldj, n, jp + (long long)i * (PL + 1) * nw, lane, wv, 0);
+    absum = wave_sum(absum);
+    if (lane == 0) csum[wv] = absum;
+    __syncthreads();
+    if (threadIdx.x == 0) jabs[i] = csum[0] + csum[1] + csum[2] + csum[3];
+}
+// GRID: the planes and jabs of 2^gk J (fp32 rows)
+template <int PL>
+__global__ void __launch_bounds__(256) rs_planes_grid_kernel(const float *J, long long ldj, int n, unsigned long long *jp, int *jabs,
+                                                             int gk) {
+    __shared__ int csum[4];
+    const int i = blockIdx.x, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int nw = 4 * ((n + 255) >> 8);
+    int absum = rs_row_to_planes<float, PL, true>(J + (long long)i * ldj, n, jp + (long long)i * (PL + 1) * nw, lane, wv, gk);
     absum = wave_sum(absum);
     if (lane == 0) csum[wv] = absum;
     __syncthreads();
@@ -274,8 +318,9 @@ __global__ void __launch_bounds__(256) rs_fields_planes_kernel(const SweepArgs a
 
 // ---- fields by on-chip conversion (int8 rows with 8 magnitude planes): one workgroup (4 waves) per proposed site -------
 // LDS: [PL + 1][4 nseg] 64-bit words (sign plane first).
-template <typename JE, int PL>
-__global__ void __launch_bounds__(256) rs_fields_kernel(const SweepArgs a, RowSharedPlan p, int win) {
+template <typename JE, int PL, bool GRID>
+__global__ void __launch_bounds__(256) rs_fields_kernel(const SweepArgs a, const RsPlanArg<GRID> pg, int win) {
+    const RowSharedPlan &p = rs_plan(pg);
     const int i = blockIdx.x, n = a.n;
     const int *off = p.off + (long long)win * (n + 1);
     const int lo = off[i], hi = off[i + 1];
@@ -285,7 +330,7 @@ __global__ void __launch_bounds__(256) rs_fields_kernel(const SweepArgs a, RowSh
     const int nseg = (n + 255) >> 8, nw = 4 * nseg;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const JE *row = reinterpret_cast<const JE *>(a.J) + (long long)i * a.ldj;
-    int absum = rs_row_to_planes<JE, PL>(row, n, planes, lane, wv);
+    int absum = rs_row_to_planes<JE, PL, GRID>(row, n, planes, lane, wv, rs_grid_k(pg));
     absum = wave_sum(absum);
     if (lane == 0) csum[wv] = absum;
     __syncthreads();
@@ -348,9 +393,10 @@ __device__ __forceinline__ void rs_coupling_load(RsRaw<JE, BITS> &raw, const Swe
         raw.v = *reinterpret_cast<const JE *>(row + voff);
     }
 }
+// unit: the value of one magnitude bit (1, GRID: 2^-k); rows of J itself are in real units already
 template <typename JE, bool BITS>
-__device__ __forceinline__ float rs_coupling(const RsRaw<JE, BITS> &raw, unsigned int bit) {
-    if constexpr (BITS) return (raw.v.y & bit) ? ((raw.v.x & bit) ? -1.0f : 1.0f) : 0.0f;
+__device__ __forceinline__ float rs_coupling(const RsRaw<JE, BITS> &raw, unsigned int bit, float unit) {
+    if constexpr (BITS) return (raw.v.y & bit) ? ((raw.v.x & bit) ? -unit : unit) : 0.0f;
     else return (float)raw.v;
 }
 
@@ -367,8 +413,21 @@ constexpr int RS_CHAIN_U = 8;  // earlier accepts applied to a block per wait
 // the next candidate.  A candidate that stopped accepting is skipped; a lane that was not fetched and accepts first
 // starts a new round.  One memory round trip per round, not per accept; the sums are integers below 2^24, so the
 // order of the corrections does not matter.
-template <typename JE, int NB, bool BITS>
-__global__ void __launch_bounds__(64) rs_chain_kernel(const SweepArgs a, RowSharedPlan p, int k, int win) {
+// GRID: the fields are held in real units (2^-k times those integers: as exact, in any order), and the decision and
+// dE are metropolis_accept's, the row kernels' general rule (the proof at the top of the file).
+template <bool GRID>
+__device__ __forceinline__ bool rs_decide(int cs, float cf, float chh, float cu, double T, int table_m) {
+    if constexpr (GRID) {
+        double dE;
+        return metropolis_accept(SGA_RULE_METROPOLIS, SGA_ARITH_F64, cf, cs, chh, 0.0f, T, cu, dE);
+    } else {
+        return rs_accept((float)cs * (cf + chh), cu, T, table_m);
+    }
+}
+
+template <typename JE, int NB, bool BITS, bool GRID>
+__global__ void __launch_bounds__(64) rs_chain_kernel(const SweepArgs a, const RsPlanArg<GRID> pg, int k, int win) {
+    const RowSharedPlan &p = rs_plan(pg);
     constexpr int W = 64 * NB, K = RS_CHAIN_K, U = RS_CHAIN_U;
     __shared__ uint32_t alist[W + U];  // the window's accepts in chain order: site | (spin before the flip < 0) << 31
     const int r = blockIdx.x, lane = threadIdx.x, n = a.n;
@@ -380,6 +439,7 @@ __global__ void __launch_bounds__(64) rs_chain_kernel(const SweepArgs a, RowShar
     const float *hvec = a.h;
     if (a.reps_per_model > 0)
         hvec += (long long)__builtin_amdgcn_readfirstlane((int)((a.replica0 + (uint32_t)r) / (uint32_t)a.reps_per_model)) * n;
+    const float unit = GRID ? ldexpf(1.0f, -rs_grid_k(pg)) : 1.0f;  // 2^-k
     int site[NB], s[NB];
     float f[NB], hh[NB], u[NB];
 #pragma unroll
@@ -391,6 +451,7 @@ __global__ void __launch_bounds__(64) rs_chain_kernel(const SweepArgs a, RowShar
         if (valid) rs_update(a, r, k, t0 + tw, site[b], ub);
         u[b] = (float)ub * 0x1.0p-24f;
         f[b] = valid ? (float)base[tw] : 0.0f;
+        if constexpr (GRID) f[b] = ldexpf(f[b], -rs_grid_k(pg));  // 2^-k D, exact
         hh[b] = hvec[site[b]];
         s[b] = srow[site[b]];
     }
@@ -429,12 +490,12 @@ __global__ void __launch_bounds__(64) rs_chain_kernel(const SweepArgs a, RowShar
 #pragma unroll
             for (int j = 0; j < U; ++j) {
                 if (k0 + j < nA) {
-                    cf -= rs_coupling<JE, BITS>(x[j], bit) * ((e[j] >> 31) ? -2.0f : 2.0f);
+                    cf -= rs_coupling<JE, BITS>(x[j], bit, unit) * ((e[j] >> 31) ? -2.0f : 2.0f);
                     if (csite == (int)(e[j] & 0x7fffffffu)) cs = -cs;
                 }
             }
         }
-        bool acc = cvalid && rs_accept((float)cs * (cf + chh), cu, T, a.table_m);
+        bool acc = cvalid && rs_decide<GRID>(cs, cf, chh, cu, T, a.table_m);
         unsigned long long m = ballot64(acc);  // accepting lanes among the undecided ones
         while (m) {
             int cl[K];
@@ -457,8 +518,12 @@ __global__ void __launch_bounds__(64) rs_chain_kernel(const SweepArgs a, RowShar
                 if (fl < cl[j]) break;      // not fetched (or the candidates are used up): the next round
                 if (fl > cl[j]) continue;   // candidate j accepts no longer
                 const int sa = read_lane(csite, fl), ss = read_lane(cs, fl);
-                const float fk = (float)ss * (read_lane(cf, fl) + read_lane(chh, fl));
-                E += (double)(2.0f * fk);
+                if constexpr (GRID) {  // metropolis_accept's dE, formed as it forms it
+                    E += 2.0 * (double)ss * ((double)read_lane(cf, fl) + (double)read_lane(chh, fl));
+                } else {
+                    const float fk = (float)ss * (read_lane(cf, fl) + read_lane(chh, fl));
+                    E += (double)(2.0f * fk);
+                }
                 if (lane == 0) {
                     srow[sa] = (int8_t)(-ss);
                     int aw;
@@ -468,9 +533,9 @@ __global__ void __launch_bounds__(64) rs_chain_kernel(const SweepArgs a, RowShar
                     alist[nA] = (uint32_t)sa | (ss < 0 ? 0x80000000u : 0u);
                 }
                 ++nA;
-                cf -= rs_coupling<JE, BITS>(x[j], bit) * (2.0f * (float)ss);
+                cf -= rs_coupling<JE, BITS>(x[j], bit, unit) * (2.0f * (float)ss);
                 if (csite == sa) cs = -cs;
-                acc = cvalid && rs_accept((float)cs * (cf + chh), cu, T, a.table_m);
+                acc = cvalid && rs_decide<GRID>(cs, cf, chh, cu, T, a.table_m);
                 m = ballot64(acc) & (~1ull << fl);
             }
         }
@@ -482,8 +547,8 @@ __global__ void __launch_bounds__(64) rs_chain_kernel(const SweepArgs a, RowShar
     }
 }
 
-template <typename Kern>
-static hipError_t rs_launch_fields(Kern kern, size_t lds, const SweepArgs &a, const RowSharedPlan &p, int win, hipStream_t st) {
+template <typename Kern, typename Plan>
+static hipError_t rs_launch_fields(Kern kern, size_t lds, const SweepArgs &a, const Plan &p, int win, hipStream_t st) {
     hipError_t e = ensure_lds_limit(reinterpret_cast<const void *>(kern), lds);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(kern, dim3(a.n), dim3(256), lds, st, a, p, win);
@@ -491,7 +556,7 @@ static hipError_t rs_launch_fields(Kern kern, size_t lds, const SweepArgs &a, co
 }
 
 template <typename JE>
-static hipError_t rs_fields(const SweepArgs &a, const RowSharedPlan &p, int win, hipStream_t st) {
+static hipError_t rs_fields(const SweepArgs &a, const RowSharedPlan &p, int grid, int win, hipStream_t st) {
     const size_t lds = (size_t)(p.planes + 1) * (p.nw32 / 2) * 8;
     if (p.jp) {
         switch (p.planes) {
@@ -501,23 +566,39 @@ static hipError_t rs_fields(const SweepArgs &a, const RowSharedPlan &p, int win,
             default: return hipErrorInvalidValue;
         }
     }
+    if constexpr (std::is_same<JE, float>::value) {  // (int8 rows are integers: k = 0, the planes are the integer form's)
+        if (grid > 1) {
+            const RowSharedGridPlan g{p, grid - 1};
+            switch (p.planes) {
+                case 1: return rs_launch_fields(rs_fields_kernel<JE, 1, true>, lds, a, g, win, st);
+                case 3: return rs_launch_fields(rs_fields_kernel<JE, 3, true>, lds, a, g, win, st);
+                case 8: return rs_launch_fields(rs_fields_kernel<JE, 8, true>, lds, a, g, win, st);
+                default: return hipErrorInvalidValue;
+            }
+        }
+    }
     switch (p.planes) {
-        case 1: return rs_launch_fields(rs_fields_kernel<JE, 1>, lds, a, p, win, st);
-        case 3: return rs_launch_fields(rs_fields_kernel<JE, 3>, lds, a, p, win, st);
-        case 8: return rs_launch_fields(rs_fields_kernel<JE, 8>, lds, a, p, win, st);
+        case 1: return rs_launch_fields(rs_fields_kernel<JE, 1, false>, lds, a, p, win, st);
+        case 3: return rs_launch_fields(rs_fields_kernel<JE, 3, false>, lds, a, p, win, st);
+        case 8: return rs_launch_fields(rs_fields_kernel<JE, 8, false>, lds, a, p, win, st);
         default: return hipErrorInvalidValue;
     }
 }
 
-template <typename JE, bool BITS>
-static hipError_t rs_chain(const SweepArgs &a, const RowSharedPlan &p, int k, int win, hipStream_t st) {
-    switch (p.W) {
-        case 256: hipLaunchKernelGGL((rs_chain_kernel<JE, 4, BITS>), dim3(a.R), dim3(64), 0, st, a, p, k, win); break;
-        case 512: hipLaunchKernelGGL((rs_chain_kernel<JE, 8, BITS>), dim3(a.R), dim3(64), 0, st, a, p, k, win); break;
-        case 1024: hipLaunchKernelGGL((rs_chain_kernel<JE, 16, BITS>), dim3(a.R), dim3(64), 0, st, a, p, k, win); break;
+template <typename JE, bool BITS, bool GRID>
+static hipError_t rs_chain_launch(const SweepArgs &a, const RsPlanArg<GRID> &p, int W, int k, int win, hipStream_t st) {
+    switch (W) {
+        case 256: hipLaunchKernelGGL((rs_chain_kernel<JE, 4, BITS, GRID>), dim3(a.R), dim3(64), 0, st, a, p, k, win); break;
+        case 512: hipLaunchKernelGGL((rs_chain_kernel<JE, 8, BITS, GRID>), dim3(a.R), dim3(64), 0, st, a, p, k, win); break;
+        case 1024: hipLaunchKernelGGL((rs_chain_kernel<JE, 16, BITS, GRID>), dim3(a.R), dim3(64), 0, st, a, p, k, win); break;
         default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
+}
+template <typename JE, bool BITS>
+static hipError_t rs_chain(const SweepArgs &a, const RowSharedPlan &p, int grid, int k, int win, hipStream_t st) {
+    if (grid) return rs_chain_launch<JE, BITS, true>(a, RowSharedGridPlan{p, grid - 1}, p.W, k, win, st);
+    return rs_chain_launch<JE, BITS, false>(a, p, p.W, k, win, st);
 }
 
 int row_shared_planes(int j_abs_max) {
@@ -536,21 +617,34 @@ static hipError_t rs_build_planes(const void *J, long long ldj, int n, int plane
     }
     return hipGetLastError();
 }
-
-hipError_t launch_rs_build_planes(const void *J, bool j_is_i8, long long ldj, int n, int planes, unsigned long long *jp,
-                                  int *jabs, hipStream_t st) {
-    if (!J || !jp || !jabs || n <= 0) return hipErrorInvalidValue;
-    return j_is_i8 ? rs_build_planes<int8_t>(J, ldj, n, planes, jp, jabs, st)
-                   : rs_build_planes<float>(J, ldj, n, planes, jp, jabs, st);
+static hipError_t rs_build_planes_grid(const void *J, long long ldj, int n, int planes, int gk, unsigned long long *jp, int *jabs,
+                                       hipStream_t st) {
+    const float *Jt = reinterpret_cast<const float *>(J);
+    switch (planes) {
+        case 1: hipLaunchKernelGGL((rs_planes_grid_kernel<1>), dim3(n), dim3(256), 0, st, Jt, ldj, n, jp, jabs, gk); break;
+        case 3: hipLaunchKernelGGL((rs_planes_grid_kernel<3>), dim3(n), dim3(256), 0, st, Jt, ldj, n, jp, jabs, gk); break;
+        case 8: hipLaunchKernelGGL((rs_planes_grid_kernel<8>), dim3(n), dim3(256), 0, st, Jt, ldj, n, jp, jabs, gk); break;
+        default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
 }
 
-hipError_t launch_sweep_dense_rs(const SweepArgs &a, const RowSharedPlan &p, bool j_is_i8, hipStream_t st) {
+hipError_t launch_rs_build_planes(const void *J, bool j_is_i8, long long ldj, int n, int planes, int grid_k,
+                                  unsigned long long *jp, int *jabs, hipStream_t st) {
+    if (!J || !jp || !jabs || n <= 0 || grid_k < 0 || grid_k > 30 || (j_is_i8 && grid_k != 0)) return hipErrorInvalidValue;
+    if (j_is_i8) return rs_build_planes<int8_t>(J, ldj, n, planes, jp, jabs, st);
+    return grid_k ? rs_build_planes_grid(J, ldj, n, planes, grid_k, jp, jabs, st)
+                  : rs_build_planes<float>(J, ldj, n, planes, jp, jabs, st);
+}
+
+hipError_t launch_sweep_dense_rs(const SweepArgs &a, const RowSharedPlan &p, bool j_is_i8, hipStream_t st, int grid) {
     // (many models: only over one shared matrix -- the plan buckets proposals by site, whatever the replica's model)
     if (a.reps_per_model < 0 || (a.reps_per_model > 0 && a.model_stride_j != 0)) return hipErrorInvalidValue;
     if (a.rep_list || a.R <= 0 || a.n <= 0 || (p.W != 256 && p.W != 512 && p.W != 1024) || (1 << p.log_w) != p.W)
         return hipErrorInvalidValue;
     if (p.log_rg < 0 || p.n_groups != (a.R + (1 << p.log_rg) - 1) >> p.log_rg || (p.jp && !p.jabs) || !p.tot)
         return hipErrorInvalidValue;
+    if (grid < 0 || grid > 31 || (j_is_i8 && grid > 1)) return hipErrorInvalidValue;  // (int8 rows: k = 0)
     const int nwin = (a.n + p.W - 1) / p.W;
     const dim3 pgrid(p.n_groups, nwin, (a.n + RS_PLAN_TILE - 1) / RS_PLAN_TILE);
     const size_t plds = sizeof(int) * (size_t)(a.n < RS_PLAN_TILE ? a.n : RS_PLAN_TILE);
@@ -565,18 +659,21 @@ hipError_t launch_sweep_dense_rs(const SweepArgs &a, const RowSharedPlan &p, boo
         hipLaunchKernelGGL(rs_plan_kernel<true>, pgrid, dim3(256), plds, st, a, p, k);
         e = hipGetLastError();
         for (int w = 0; w < nwin && e == hipSuccess; ++w) {
-            e = j_is_i8 ? rs_fields<int8_t>(a, p, w, st) : rs_fields<float>(a, p, w, st);
+            e = j_is_i8 ? rs_fields<int8_t>(a, p, grid, w, st) : rs_fields<float>(a, p, grid, w, st);
             if (e != hipSuccess) break;
             if (chain_bits)
-                e = j_is_i8 ? rs_chain<int8_t, true>(a, p, k, w, st) : rs_chain<float, true>(a, p, k, w, st);
+                e = j_is_i8 ? rs_chain<int8_t, true>(a, p, grid, k, w, st) : rs_chain<float, true>(a, p, grid, k, w, st);
             else
-                e = j_is_i8 ? rs_chain<int8_t, false>(a, p, k, w, st) : rs_chain<float, false>(a, p, k, w, st);
+                e = j_is_i8 ? rs_chain<int8_t, false>(a, p, grid, k, w, st) : rs_chain<float, false>(a, p, grid, k, w, st);
         }
         // sweep boundary: best tracking (annealing/gpu_annealer.py:151-153), the energy is in a.energy
         if (e == hipSuccess && !a.no_best)
             e = launch_update_best(a.energy, a.spins, a.best_energy, a.best_spins, a.sstride, a.R, st);
     }
-    if (e == hipSuccess)
+    if (e == hipSuccess && grid)
+        note_sweep_kernel("sweep_dense_rs<%s, planes=%d, W=%d, grid=2^-%d> (row-shared windows: plan, fields from %s, chain)",
+                          j_is_i8 ? "int8_t" : "float", p.planes, p.W, grid - 1, p.jp ? "resident bit-planes" : "on-chip conversion");
+    else if (e == hipSuccess)
         note_sweep_kernel("sweep_dense_rs<%s, planes=%d, W=%d> (row-shared windows: plan, fields from %s, chain)",
                           j_is_i8 ? "int8_t" : "float", p.planes, p.W, p.jp ? "resident bit-planes" : "on-chip conversion");
     return e;

@@ -49,6 +49,10 @@ class GPUAnnealerConfig:
     #                                       the same chain bit for bit as "off" (one row read per proposal)
     fixed_point_fields: bool = False      # engine option "clf_fixed_point": the field cache also serves real-valued
     #                                       sparse and dense couplings (exact int32 | int64 fixed-point fields; same chain)
+    row_shared_grid: bool = False         # engine option "row_shared_grid": the row-shared windows also serve dense J on a
+    #                                       binary grid 2^-k under any h (quarter-valued QUBO encodings, integer J beside a
+    #                                       real-valued h; same chain).  Acts with field_cache="off", where the autotuner picks
+    #                                       the form or option "row_shared" = 1 forces it
     device_index: Optional[int] = None
 
     def __post_init__(self):
@@ -106,6 +110,8 @@ class GPUAnnealer:
             eng.set_field_cache(cfg.field_cache)  # (before the couplings: "on" keeps a sparse matrix dense)
             if cfg.fixed_point_fields:
                 eng.set_option("clf_fixed_point", 1)  # (read when the couplings are set)
+            if cfg.row_shared_grid:
+                eng.set_option("row_shared_grid", 1)  # (read at every sweep; acts with field_cache="off")
             model.load_into(eng, storage=cfg.coupling_storage)
             eng.set_update_rule(rule)
             eng.init_replicas(1, seed=fresh_seed(cfg.random_seed), s0=model.spins_int8()[None, :])

@@ -119,6 +119,8 @@ class MultiGPUAnnealer:
         eng.set_field_cache(self.annealer_config.field_cache)
         if self.annealer_config.fixed_point_fields:  # (real-valued sparse and dense couplings: exact fixed-point fields)
             eng.set_option("clf_fixed_point", 1)  # (read when the couplings are set)
+        if self.annealer_config.row_shared_grid:  # (row-shared windows for dense J on a binary grid, any h)
+            eng.set_option("row_shared_grid", 1)
         model.load_into(eng, storage=self.annealer_config.coupling_storage)
         return eng
 

@@ -49,6 +49,9 @@ class ParallelTemperingConfig:
     coupling_storage: str = "auto"
     field_cache: str = "auto"             # resident local fields where the problem allows (identical chain)
     fixed_point_fields: bool = False      # ... real-valued sparse and dense couplings too (option "clf_fixed_point")
+    row_shared_grid: bool = False         # option "row_shared_grid": row-shared windows for dense J on a binary grid 2^-k
+    #                                       under any h (same chain); acts with field_cache="off", where autotune picks the
+    #                                       form or option "row_shared" = 1 forces it
     device_index: Optional[int] = None
     autotune: Optional[bool] = None       # measured launch geometry (None: for long runs only)
 
@@ -94,6 +97,8 @@ class ParallelTempering:
             eng.set_field_cache(cfg.field_cache)  # (before the couplings: "on" keeps a sparse matrix dense)
             if cfg.fixed_point_fields:
                 eng.set_option("clf_fixed_point", 1)  # (read when the couplings are set)
+            if cfg.row_shared_grid:
+                eng.set_option("row_shared_grid", 1)  # (read at every sweep; acts with field_cache="off")
             model.load_into(eng, storage=cfg.coupling_storage)
             eng.set_update_rule(rule)
             eng.init_replicas(R, seed=fresh_seed(cfg.random_seed),
