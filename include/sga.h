@@ -80,7 +80,7 @@ typedef struct sga_engine sga_engine;
 int sga_create(int device, sga_engine **out);
 void sga_destroy(sga_engine *e);
 const char *sga_last_error(void);
-int sga_version(void);  /* 1700: sga_set_csr_shared (one set of CSR rows, many field vectors: every one-wave-per-replica CSR form for such batches), sga_route_query.shared_j on SGA_ROUTE_CSR queries; 1600: sga_set_dense_shared (one coupling matrix, many field vectors; row-shared windows, bit-planes and the matrix-core pass for such batches), sga_route_query.shared_j; 1500: sga_get_scan_summary, and sga_set_dense / sga_set_dense_batch / sga_set_csr / sga_set_csr64 / sga_set_csr_batch refuse a NaN or +-Inf in J or h (SGA_ERR_INVALID, "non-finite"); 1400: option "batch_fixed_point" (fixed-point cached local fields for many-model dense batches); 1300: options "ragged_field_cache" and "clf_fixed_point" together (fixed-point cached local fields for ragged CSR batches); 1200: sga_set_groups_csr (group couplings plus a stored sparse remainder); 1100: option "ragged_field_cache" (cached local fields for ragged CSR batches); 1000: sga_set_groups */
+int sga_version(void);  /* 1900: options "row_shared_fields" and "row_shared_tile_sites" (row-shared fields in tiles of sites, sign-only rows); 1800: option "row_shared_grid", sga_route_query.rs_grid; 1700: sga_set_csr_shared (one set of CSR rows, many field vectors: every one-wave-per-replica CSR form for such batches), sga_route_query.shared_j on SGA_ROUTE_CSR queries; 1600: sga_set_dense_shared (one coupling matrix, many field vectors; row-shared windows, bit-planes and the matrix-core pass for such batches), sga_route_query.shared_j; 1500: sga_get_scan_summary, and sga_set_dense / sga_set_dense_batch / sga_set_csr / sga_set_csr64 / sga_set_csr_batch refuse a NaN or +-Inf in J or h (SGA_ERR_INVALID, "non-finite"); 1400: option "batch_fixed_point" (fixed-point cached local fields for many-model dense batches); 1300: options "ragged_field_cache" and "clf_fixed_point" together (fixed-point cached local fields for ragged CSR batches); 1200: sga_set_groups_csr (group couplings plus a stored sparse remainder); 1100: option "ragged_field_cache" (cached local fields for ragged CSR batches); 1000: sga_set_groups */
 /* Run on an existing HIP stream (e.g. torch.cuda.current_stream().cuda_stream); NULL = the
  * engine's own stream (default). */
 int sga_set_stream(sga_engine *e, void *hip_stream);
@@ -594,6 +594,18 @@ int sga_set_field_cache(sga_engine *e, int mode);
  *                           does (field cache off; 1 forces the form, 2 lets sga_autotune time it); a shared-coupling batch
  *                           qualifies as a whole (k, planes and the bound over the batch).  0: nothing changes
  *                                                                                          [sweep; SGA_ROW_SHARED_GRID]
+ *   "row_shared_fields"     0 | 1 | 2 (default)   (version >= 1900) the fields kernel of the row-shared windows over resident
+ *                           bit-planes: 0 = one workgroup per proposed site; 1 | 2 = one workgroup per tile of S consecutive
+ *                           sites, the tile's plane rows in LDS and its entries grouped by replica, so that a replica's spin
+ *                           bits are read once per tile instead of once per proposal; where every off-diagonal |J_ij| (grid
+ *                           form: |2^k J_ij|) is 1 the rows are their sign planes alone ("sign-only").  1: wherever the kernel
+ *                           can run; 2: where it was measured to win -- sign-only rows, 7936 < n <= 16384 (a replica's spin
+ *                           bits of 1 KB or more, within the kernel's registers).  The per-site kernel
+ *                           still runs where R exceeds 4096 (the kernel's replica counters), two rows' planes do not fit the
+ *                           tile image, or the runtime refuses the LDS: sga_describe says which (rs_tiles=...).  Same chain
+ *                                                                                        [sweep; SGA_ROW_SHARED_FIELDS]
+ *   "row_shared_tile_sites" 0 (default) = S by the library's rule, else S, 2 ... 4096 (tests, A/B runs)
+ *                                                                                    [sweep; SGA_ROW_SHARED_TILE_SITES]
  *   "row_shared_window"     0 (default) | 256 | 512 | 1024 (other values: rounded down): W under "row_shared" = 1 (0: the
  *                           autotuner's, else 1024)                                      [sweep; SGA_ROW_SHARED_WINDOW]
  *   "ragged_field_cache"    0 (default) | 1   ragged CSR batches (sga_set_csr_batch): the int16 cached-field sweep of

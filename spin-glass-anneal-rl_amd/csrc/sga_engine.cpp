@@ -154,6 +154,25 @@ int row_shared_window(const sga_engine *e, bool lean) {
     return fw >= 1024 ? 1024 : fw >= 512 ? 512 : fw >= 256 ? 256 : (e->rs_tuned_w > 0 ? e->rs_tuned_w : 1024);
 }
 
+// The fields kernel of the row-shared windows over resident planes, by option "row_shared_fields": the tile size S and
+// whether the rows are sign-only, or S = 0 and the reason where the per-site kernel runs.  Option 2 takes the tiles only
+// in the configuration measured to win.  Known once the planes exist (rs_ones is found with them).
+sga::RowSharedTiles row_shared_tiles(const sga_engine *e, const char **why) {
+    sga::RowSharedTiles t{};
+    const char *dummy;
+    if (!why) why = &dummy;
+    *why = nullptr;
+    int grid = 0;
+    const int planes = row_shared_form_planes(e, &grid);
+    if (e->opt[OPT_ROW_SHARED_FIELDS] == 0) return (*why = "option row_shared_fields = 0"), t;
+    if (!e->rs_jp) return (*why = "no resident bit-planes"), t;
+    if (e->rs_tiles_refused) return (*why = "the tile kernel's LDS request was refused"), t;
+    if (e->opt[OPT_ROW_SHARED_FIELDS] == 2 && (*why = sga::row_shared_tiles_not_default(e->n, planes, e->rs_ones))) return t;
+    t.S = sga::row_shared_tile_sites(e->n, planes, e->rs_ones, e->R, e->cus, (int)e->opt[OPT_ROW_SHARED_TILE_SITES], why);
+    t.ones = t.S > 0 && e->rs_ones;
+    return t;
+}
+
 // the form's scratch for W and, where the problem gets them, its resident bit-planes of J: false (and the
 // row-per-proposal kernel runs) if either cannot be had
 static bool ensure_row_shared(sga_engine *e, int W, hipStream_t st) {
@@ -172,6 +191,15 @@ static bool ensure_row_shared(sga_engine *e, int W, hipStream_t st) {
         if (he == hipSuccess)
             he = sga::launch_rs_build_planes(e->J_packed, e->want_i8, e->ldj, e->n, planes, grid ? grid - 1 : 0, e->rs_jp,
                                              e->rs_jabs, st);
+        // sign-only rows: one magnitude plane and sum_j |J_ij| = n - 1 in every row -- every off-diagonal |J_ij| (grid
+        // form: |2^k J_ij|) is 1, the magnitude plane says nothing the diagonal's place does not (rs_fields_tiles_kernel)
+        e->rs_ones = false;
+        if (he == hipSuccess && planes == 1) {
+            std::vector<int> jabs(n);
+            he = hipMemcpyAsync(jabs.data(), e->rs_jabs, sizeof(int) * n, hipMemcpyDeviceToHost, st);
+            if (he == hipSuccess) he = hipStreamSynchronize(st);
+            e->rs_ones = he == hipSuccess && std::all_of(jabs.begin(), jabs.end(), [&](int v) { return v == (int)n - 1; });
+        }
         if (he != hipSuccess) {
             dev_free(e->rs_jp);
             dev_free(e->rs_jabs);
@@ -427,7 +455,7 @@ int ensure_packed(sga_engine *e) {
 extern "C" {
 
 const char *sga_last_error(void) { return g_last_error.c_str(); }
-int sga_version(void) { return 1800; }  // + option "row_shared_grid": row-shared windows for dense J on a binary grid under any h (sweep_dense_rs.hip, GRID), sga_route_query.rs_grid  // 1700: + sga_set_csr_shared (one set of CSR rows, many field vectors)  // 1600: + sga_set_dense_shared (one coupling matrix, many field vectors), sga_route_query.shared_j  // 1500: + sga_get_scan_summary; the dense and CSR setters refuse non-finite J / h  // 1400: + option "batch_fixed_point": fixed-point cached local fields for many-model dense batches (sweep_clf_fx.hip, MODELS)  // 1300: + options "ragged_field_cache" and "clf_fixed_point" together: fixed-point cached local fields for ragged CSR batches (sweep_clf_csr.hip)  // 1200: + sga_set_groups_csr (group couplings plus a stored sparse remainder, sweep_groups.hip)  // 1100: + option "ragged_field_cache" (cached local fields for ragged CSR batches, sweep_clf_csr.hip)  // 1000: + sga_set_groups (implicit cardinality-group couplings, sweep_groups.hip)  // 900: + cached local fields for many-model dense batches (sga_set_dense_batch)  // 800: + option "clf_fixed_point" over dense couplings (sweep_clf_fx.hip)  // 700: + option "clf_fixed_point" (cached fields of real-valued CSR couplings)  // 600: + sga_set_csr_batch / sga_get_batch_model (ragged CSR batches)  // round 5: + sga_explain_route / sga_get_route_query, sga_get_last_kernel, sga_get_autotune_table, ladder-local sga_exchange
+int sga_version(void) { return 1900; }  // + options "row_shared_fields", "row_shared_tile_sites": the row-shared fields in tiles of sites, sign-only rows (sweep_dense_rs.hip, rs_fields_tiles_kernel)  // 1800: + option "row_shared_grid": row-shared windows for dense J on a binary grid under any h (sweep_dense_rs.hip, GRID), sga_route_query.rs_grid  // 1700: + sga_set_csr_shared (one set of CSR rows, many field vectors)  // 1600: + sga_set_dense_shared (one coupling matrix, many field vectors), sga_route_query.shared_j  // 1500: + sga_get_scan_summary; the dense and CSR setters refuse non-finite J / h  // 1400: + option "batch_fixed_point": fixed-point cached local fields for many-model dense batches (sweep_clf_fx.hip, MODELS)  // 1300: + options "ragged_field_cache" and "clf_fixed_point" together: fixed-point cached local fields for ragged CSR batches (sweep_clf_csr.hip)  // 1200: + sga_set_groups_csr (group couplings plus a stored sparse remainder, sweep_groups.hip)  // 1100: + option "ragged_field_cache" (cached local fields for ragged CSR batches, sweep_clf_csr.hip)  // 1000: + sga_set_groups (implicit cardinality-group couplings, sweep_groups.hip)  // 900: + cached local fields for many-model dense batches (sga_set_dense_batch)  // 800: + option "clf_fixed_point" over dense couplings (sweep_clf_fx.hip)  // 700: + option "clf_fixed_point" (cached fields of real-valued CSR couplings)  // 600: + sga_set_csr_batch / sga_get_batch_model (ragged CSR batches)  // round 5: + sga_explain_route / sga_get_route_query, sga_get_last_kernel, sga_get_autotune_table, ladder-local sga_exchange
 
 int sga_create(int device, sga_engine **out) {
     if (!out) return fail(SGA_ERR_INVALID, "out is NULL");
@@ -813,6 +841,7 @@ struct SweepPlan {  // what holds for every launch of a call
     int n_clf = 0;              // ... the replicas on it,
     bool mixed = false;         // ... and the others beside them on the row kernels, second stream
     int rs_w = 0;               // row-shared window (0: not this form)
+    sga::RowSharedTiles rs_tiles{};  // its fields kernel: tiles of S sites (S = 0: one workgroup per site)
 };
 
 // The policy's look at the acceptance counters (sga_route.cpp, look): one read-back and synchronise when a look is due,
@@ -1053,6 +1082,17 @@ int plan_sweep(sga_engine *e, const SweepCall &c, SweepPlan &p) {
         const bool lean_call = c.site_mode == SGA_SITE_RANDOM && c.arith == SGA_ARITH_F64 && !c.acc.ptr && !c.dE.ptr;
         p.rs_w = row_shared_window(e, lean_call);
         if (p.rs_w && !ensure_row_shared(e, p.rs_w, e->stream)) p.rs_w = 0;
+        if (p.rs_w) {  // the fields in tiles: the kernel's LDS is asked for here, a refusal leaves the per-site kernel
+            p.rs_tiles = row_shared_tiles(e, nullptr);
+            if (p.rs_tiles.S > 0 &&
+                sga::row_shared_tiles_prepare(e->rs.planes, p.rs_tiles.ones != 0,
+                                              sga::row_shared_tile_lds(e->n, e->rs.planes, p.rs_tiles.ones != 0, p.rs_tiles.S, e->R)) !=
+                    hipSuccess) {
+                (void)hipGetLastError();
+                e->rs_tiles_refused = true;
+                p.rs_tiles = sga::RowSharedTiles{};
+            }
+        }
     }
     return SGA_OK;
 }
@@ -1113,7 +1153,7 @@ hipError_t launch_sweep(sga_engine *e, const SweepPlan &p, sga::SweepArgs a, hip
     if (e->groups) return sga::launch_sweep_groups(a, e->group_args, e->waves, st);
     if (e->tsp) return sga::launch_sweep_tsp(a, e->tsp_args, e->tsp_waves, e->tsp_passes, st);
     if (e->csr) return sga::launch_sweep_csr(a, e->waves, st);
-    if (p.rs_w) return sga::launch_sweep_dense_rs(a, e->rs, e->want_i8, st, e->rs_grid);
+    if (p.rs_w) return sga::launch_sweep_dense_rs(a, e->rs, e->want_i8, st, e->rs_grid, p.rs_tiles);
     return launch_dense_rows(e, a, st);
 }
 

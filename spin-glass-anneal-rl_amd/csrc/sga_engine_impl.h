@@ -254,6 +254,9 @@ struct sga_engine {
     int rs_grid = 0;  // what rs was prepared for: 0 the integer form, else 1 + k (launch_sweep_dense_rs)
     unsigned long long *rs_jp = nullptr;
     int *rs_jabs = nullptr;
+    // rs_ones: found with the planes -- every off-diagonal |J_ij| (grid form: |2^k J_ij|) is 1, the fields kernel reads
+    // sign planes only; rs_tiles_refused: the runtime refused the tile kernel's LDS for this problem (per-site kernel)
+    bool rs_ones = false, rs_tiles_refused = false;
     void free_row_shared() {
         dev_free(rs.cnt);
         dev_free(rs.off);
@@ -356,6 +359,8 @@ struct sga_engine {
         free_row_shared();
         dev_free(rs_jp);
         dev_free(rs_jabs);
+        rs_ones = false;
+        rs_tiles_refused = false;
         rs_tuned_w = 0;
         rs_grid_planes = 0;
         rs_grid_k = 0;
@@ -457,6 +462,8 @@ int ensure_packed(sga_engine *e);
 int row_shared_window(const sga_engine *e, bool lean);
 // magnitude planes of the row-shared form that serves the problem (0: none); *grid: 0 the integer form, else 1 + k
 int row_shared_form_planes(const sga_engine *e, int *grid);
+// the tiles of its fields kernel (option "row_shared_fields"); S = 0: the per-site kernel, *why the reason
+sga::RowSharedTiles row_shared_tiles(const sga_engine *e, const char **why);
 // ---- sga_problem.cpp
 bool csr_rows_medium(const sga_engine *e);
 int csr_updates_per_step(const sga_engine *e);

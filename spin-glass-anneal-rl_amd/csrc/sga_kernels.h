@@ -458,6 +458,68 @@ inline int row_shared_log_group(int n, int W) {
     while ((1 << l) < nwin) ++l;
     return l;
 }
+// Fields from the resident planes in tiles (rs_fields_tiles_kernel, option "row_shared_fields"): one workgroup per
+// (window, tile of S consecutive sites) holds the tile's plane rows in LDS and walks its entries grouped by replica.
+// S == 0: the per-site kernel.  ones: every off-diagonal |J_ij| (GRID: |2^k J_ij|) is 1 -- the rows are their sign
+// planes alone ("sign-only").  A type of its own beside the plan, so that the other kernels keep their arguments.
+struct RowSharedTiles {
+    int S = 0;
+    int ones = 0;
+};
+constexpr int RS_TILE_THREADS = 1024;        // workgroup of the tile kernel
+constexpr int RS_TILE_ENTRIES = 6144;        // its entry buffer: a longer range goes through in chunks of this many
+constexpr int RS_TILE_MAX_REPLICAS = 4096;   // its replica counters (one LDS word per replica of the launch)
+constexpr int RS_TILE_MAX_SITES = 4096;      // (a site's index in the tile is kept in 16 bits)
+constexpr size_t RS_TILE_LDS_BUDGET = 160 * 1024 - 256;
+// Option "row_shared_fields" = 2 takes the tiles only where a replica's spin bits are at least this many bytes (n > 7936):
+// what a tile saves is bits per entry, what it costs -- the sort -- is per entry whatever n.  Measured at 1024 replicas,
+// W = 1024: 1280 B (n = 10 000) 67.5 -> 57.0 us per window, 256 B (n = 2000) 30.7 -> 34.3 us; the straight line between
+// the two crosses at about 520 B, and the default asks for twice that.
+constexpr int RS_TILE_MIN_BITS_BYTES = 1024;
+// 16-byte words of a replica's spin bits that a lane of the tile kernel keeps in registers (a quarter wave holds 256 bytes
+// per word: n <= 16384 beside one magnitude plane); longer vectors, and eight planes, stream the bits per entry
+constexpr int row_shared_tile_register_words(int planes) { return planes == 1 ? 8 : planes == 3 ? 4 : 0; }
+// Option "row_shared_fields" = 2: null where the tiles are the default -- the one configuration measured to win, sign-only
+// rows with the bits in registers from RS_TILE_MIN_BITS_BYTES (7936 < n <= 16384) -- else why the per-site kernel runs.
+// General planes measured slower or level in tiles; option 1 takes the tiles wherever they can run.
+inline const char *row_shared_tiles_not_default(int n, int planes, bool ones) {
+    const int bytes = 4 * row_shared_nw32(n);
+    if (!ones) return "rows not sign-only; row_shared_fields = 1 forces the tiles";
+    if (bytes < RS_TILE_MIN_BITS_BYTES) return "spin bits under 1 KB per replica: the per-site kernel is faster";
+    if (bytes > 256 * row_shared_tile_register_words(planes))
+        return "spin bits beyond the kernel's registers; row_shared_fields = 1 forces the tiles";
+    return nullptr;
+}
+// dynamic LDS of the tile kernel: [S][rows per site][nw32 / 4] 16-byte words of planes, the sorted entries (32-bit
+// entry, 16-bit site in the tile), R counters, S + 1 offsets, S row constants, one total per wave
+inline size_t row_shared_tile_lds(int n, int planes, bool ones, int S, int R) {
+    const size_t row = (size_t)(ones ? 1 : planes + 1) * (size_t)row_shared_nw32(n) * 4;
+    return (size_t)S * row + (size_t)RS_TILE_ENTRIES * 6 + 4 * ((size_t)R + 2 * (size_t)S + 1 + RS_TILE_THREADS / 64);
+}
+// The tile size for a problem and replica count, 0 where the per-site kernel serves (why: the reason).  forced > 0:
+// option "row_shared_tile_sites".  The rule: S = ceil(n / (m cus)) for the smallest m whose image fits LDS, at least 2
+// -- ceil(n / S) tiles then fill m rounds of one workgroup per CU almost whole.
+inline int row_shared_tile_sites(int n, int planes, bool ones, int R, int cus, int forced, const char **why) {
+    const char *dummy;
+    if (!why) why = &dummy;
+    *why = nullptr;
+    if (planes <= 0 || n <= 0) return (*why = "no resident bit-planes"), 0;
+    if (R > RS_TILE_MAX_REPLICAS) return (*why = "more replicas than the tile kernel's 4096 LDS counters"), 0;
+    if (row_shared_tile_lds(n, planes, ones, 2, R) > RS_TILE_LDS_BUDGET) return (*why = "two rows' planes do not fit the tile image in LDS"), 0;
+    if (forced > 0) {
+        const int S = forced < 2 ? 2 : forced > RS_TILE_MAX_SITES ? RS_TILE_MAX_SITES : forced;
+        if (row_shared_tile_lds(n, planes, ones, S, R) > RS_TILE_LDS_BUDGET) return (*why = "the forced tile does not fit LDS"), 0;
+        return S;
+    }
+    if (cus <= 0) cus = 256;
+    for (long long m = 1;; ++m) {
+        long long S = ((long long)n + m * cus - 1) / (m * cus);
+        if (S < 2) S = 2;
+        if (S <= RS_TILE_MAX_SITES && row_shared_tile_lds(n, planes, ones, (int)S, R) <= RS_TILE_LDS_BUDGET) return (int)S;
+    }
+}
+// asks the runtime for the tile kernel's LDS (once per instantiation and size): an error where it is refused
+hipError_t row_shared_tiles_prepare(int planes, bool ones, size_t lds_bytes);
 // one pass over J: jp and jabs of every row (the first time the form is prepared for a problem); grid_k: the planes
 // and jabs are those of 2^k J (fp32 rows; 0: of J itself)
 hipError_t launch_rs_build_planes(const void *J, bool j_is_i8, long long ldj, int n, int planes, int grid_k,
@@ -465,7 +527,9 @@ hipError_t launch_rs_build_planes(const void *J, bool j_is_i8, long long ldj, in
 // a.n_sweeps sweeps: spins -> bits, then per sweep the plan, per window fields + chain, best tracking.  Production
 // arguments only (Philox sites, Metropolis with the accept table, fp64 rule, no per-update traces, all replicas).
 // grid: 0 the integer form; else 1 + k, the GRID instantiations (J on the grid 2^-k, any h: the general fp64 rule).
-hipError_t launch_sweep_dense_rs(const SweepArgs &a, const RowSharedPlan &p, bool j_is_i8, hipStream_t st, int grid = 0);
+// tiles.S > 0 (with resident planes): the fields by rs_fields_tiles_kernel in tiles of S sites.
+hipError_t launch_sweep_dense_rs(const SweepArgs &a, const RowSharedPlan &p, bool j_is_i8, hipStream_t st, int grid = 0,
+                                 RowSharedTiles tiles = RowSharedTiles{});
 
 // operator-form PT exchange (cuda_kernels.py:415-443): decide sequentially, then permute rows
 hipError_t launch_op_exchange(float *spins, float *tmp_rows, float *energies, const float *temps,

@@ -30,8 +30,8 @@ enum Opt {
     OPT_LOOK_AHEAD, OPT_CLF_WAVES, OPT_SPARSE_ROUTE, OPT_BATCHED_ENERGY, OPT_FORCE_GENERAL, OPT_CSR_UPDATES_PER_STEP,
     OPT_TSP_PARALLEL, OPT_FORCE_CSR_BITS, OPT_CSR_BITS, OPT_CSR_SLOTS, OPT_HALF_TABLE, OPT_FORCE_CSR_ACC,
     OPT_FORCE_DENSE_CANON, OPT_ZERO_SLOT_EVERY, OPT_REPLICA_ROUTING, OPT_FIELDS_SCRATCH_MB, OPT_CLF_BATCHED,
-    OPT_CLF_TAIL_WAVES, OPT_CLF_FIXED_POINT, OPT_ROW_SHARED, OPT_ROW_SHARED_GRID, OPT_ROW_SHARED_WINDOW,
-    OPT_BATCH_FIXED_POINT, OPT_RAGGED_FIELD_CACHE, OPT_COUNT
+    OPT_CLF_TAIL_WAVES, OPT_CLF_FIXED_POINT, OPT_ROW_SHARED, OPT_ROW_SHARED_GRID, OPT_ROW_SHARED_FIELDS,
+    OPT_ROW_SHARED_TILE_SITES, OPT_ROW_SHARED_WINDOW, OPT_BATCH_FIXED_POINT, OPT_RAGGED_FIELD_CACHE, OPT_COUNT
 };
 struct OptDef {
     const char *key;
@@ -63,6 +63,8 @@ constexpr OptDef OPT_DEFS[OPT_COUNT] = {
     {"clf_fixed_point", nullptr, 0, 0, 0, 0, 1, 2},
     {"row_shared", "SGA_ROW_SHARED", 0, 0, 2, 0, 2, 0},
     {"row_shared_grid", "SGA_ROW_SHARED_GRID", 0, 0, 0, 0, 1, 0},
+    {"row_shared_fields", "SGA_ROW_SHARED_FIELDS", 0, 0, 2, 0, 2, 0},
+    {"row_shared_tile_sites", "SGA_ROW_SHARED_TILE_SITES", 0, 0, 0, 0, 4096, 0},
     {"row_shared_window", "SGA_ROW_SHARED_WINDOW", 0, 0, 0, 0, 1024, 0},
     // ("ragged_field_cache" stays the last entry and the list ends row_shared_window, batch_fixed_point, ragged_field_cache;
     //  queries name options by key -- _native.route_query, tests/golden/route_table.json -- never by number)

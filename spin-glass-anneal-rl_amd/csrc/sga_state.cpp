@@ -424,6 +424,15 @@ int sga_describe(sga_engine *e, char *buf, int buflen) {
                               sga::row_shared_plane_bytes(e->n, pl));
             else
                 std::strncat(tmp, " rs_fields=on-chip-conversion", sizeof(tmp) - std::strlen(tmp) - 1);
+            if (e->rs_jp) {  // (the planes exist: whether the rows are sign-only is known) option "row_shared_fields"
+                const char *why = nullptr;
+                const sga::RowSharedTiles t = row_shared_tiles(e, &why);
+                if (t.S > 0)
+                    std::snprintf(tmp + std::strlen(tmp), sizeof(tmp) - std::strlen(tmp), " rs_tiles=%d-sites%s", t.S,
+                                  t.ones ? "(sign-only)" : "");
+                else
+                    std::snprintf(tmp + std::strlen(tmp), sizeof(tmp) - std::strlen(tmp), " rs_tiles=no(%s)", why ? why : "-");
+            }
         }
     }
     if (e->csr && !e->ragged && csr_updates_per_step(e) >= 4 && e->waves <= 1 && (e->big_form == 0 || e->big_form == 2) && e->rowptr)

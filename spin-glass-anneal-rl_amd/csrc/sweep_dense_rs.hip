@@ -8,7 +8,10 @@
 //     base(r, t) = sum_j J_ij s_j -- a full row sum of n terms per proposal.  The planes of the whole matrix are made
 //     once per problem and stay in HBM (rs_planes_kernel, RowSharedPlan::jp): J does not change between two
 //     sga_set_* calls, and a plane row is (planes + 1) / 32 of the fp32 row.  Only int8 rows with 8 magnitude planes,
-//     whose planes would outweigh J, are converted on chip per window (rs_fields_kernel);
+//     whose planes would outweigh J, are converted on chip per window (rs_fields_kernel).  Over resident planes and
+//     long rows the same sums are formed per TILE of consecutive sites, so that a replica's spin bits are read once per
+//     tile, not once per proposal, and from sign planes alone where every |J_ij| is 1 (rs_fields_tiles_kernel; option
+//     "row_shared_fields");
 //   * chain: one wave per replica holds the W pending fields, one per (lane, block of 64 updates), and walks the
 //     blocks in order.  A block first takes the corrections -2 J[i_a][i_t] s_a (J symmetric: read from row i_a) of
 //     every accept the window has made so far, its spins negated where the site repeats; then its 64 updates are
@@ -48,6 +51,7 @@
 // A shared-coupling batch: k, the planes and the bound are the batch's (one J; the bound's word takes the largest
 // |h| of any model), each wave reads its model's h.  The non-GRID instantiations are the integer form's, unchanged:
 // the GRID ones take a plan type of their own (RowSharedGridPlan), so not even an argument offset moves in the others.
+#include <cstdio>
 #include <type_traits>
 
 #include "sweep_common.h"
@@ -316,6 +320,189 @@ __global__ void __launch_bounds__(256) rs_fields_planes_kernel(const SweepArgs a
     }
 }
 
+// ---- fields from the resident planes in tiles: one workgroup (16 waves) per tile of S consecutive sites ---------------
+// The per-site kernel reads a replica's spin bits from L2 once per ENTRY; a replica proposes about W S / n sites of a
+// tile inside a window, so a workgroup that owns the tile needs them once per replica.  The tile's entries are the
+// contiguous range off[tile0] ... off[tile0 + ns] of the plan (unchanged).  The plane rows of its proposed sites go to
+// LDS (rows nobody proposes are not read), and the entries are grouped by replica with a counting sort in LDS (key
+// ent >> log_w, the site's index in the tile carried beside the entry; no atomic reaches memory; a range longer than
+// the entry buffer goes through in chunks, each sorted on its own).  Then the per-site kernel's inner loop, in sorted
+// order: the entries of a replica sit in adjacent quarter waves and passes, so their spin-bit loads merge or hit L1.
+// The order inside a replica's run is whatever the LDS atomics make it; every entry names its own base slot.
+// ONES (every off-diagonal |J_ij| is 1: the magnitude plane is all ones but for the diagonal and the pad): the rows
+// are their sign planes alone.  sum_j |J_ij| [sign_ij != spin_j] = popcount(sign ^ spin) - spin_i, as the diagonal's sign
+// bit is 0 (its term is the spin bit itself, and the magnitude plane would have masked it) and the pad bits are 0 in
+// both; base = C - 2 acc as before.
+// 16 bytes of a row against 16 bytes of spin bits: sum_b 2^b popcount(plane_b & (sign ^ spin)); ONES: popcount(sign ^ spin)
+template <int PL, bool ONES>
+__device__ __forceinline__ int rs_tile_word(const ulonglong2 sv, const ulonglong2 *row, int nw2, int c) {
+    const ulonglong2 sg = row[c];
+    const unsigned long long x0w = sv.x ^ sg.x, x1w = sv.y ^ sg.y;
+    if constexpr (ONES) {
+        return __popcll(x0w) + __popcll(x1w);
+    } else {
+        int acc = 0;
+#pragma unroll
+        for (int b = 0; b < PL; ++b) {
+            const ulonglong2 pb = row[(1 + b) * nw2 + c];
+            acc += (__popcll(pb.x & x0w) + __popcll(pb.y & x1w)) << b;
+        }
+        return acc;
+    }
+}
+
+// The inner loop of the tile kernel over one sorted chunk.  A quarter wave takes a contiguous piece of the chunk -- the
+// four pieces of a wave are equally long, so no quarter wave idles -- and keeps the spin bits of the piece's current
+// replica in registers, NK words of 16 bytes per lane (NK = ceil(nw2 / 16), chosen wave-uniformly by the caller, so the
+// loads of a replica and the LDS reads of an entry are NK independent instructions without a branch between them; the
+// lanes of the last, partial group read word 0 and drop the sum): the bits are read once per replica and piece, about
+// once per replica and tile.  NK = 0: longer rows stream the bits per entry, as the per-site kernel
+// does (from L1 now, a replica's entries being adjacent).
+struct RsTileChunk {
+    const int *sent;
+    const unsigned short *sls;
+    const int *sjabs;
+    const ulonglong2 *prow, *bits;
+    int *base;
+    int cn, nw2, rw2, log_w, W, nwaves;
+};
+template <int PL, bool ONES, int NK>
+__device__ __forceinline__ void rs_tile_pieces(const RsTileChunk &ch, int wv, int sub, int l16) {
+    const int L = (ch.cn + 4 * ch.nwaves - 1) / (4 * ch.nwaves), x1 = (4 * wv + sub) * L, wmask = (1 << ch.log_w) - 1;
+    constexpr int NR = NK > 0 ? NK : 1;
+    const int clast = l16 + 16 * (NR - 1);
+    const bool vlast = clast < ch.nw2;
+    const int cl = vlast ? clast : 0;
+    ulonglong2 sv[NR];
+#pragma unroll
+    for (int k = 0; k < NR; ++k) sv[k] = make_ulonglong2(0ull, 0ull);
+    int rcur = -1;
+    for (int t = 0; t < L; ++t) {  // wave-uniform bounds: the DPP steps run with every lane on
+        const int x = x1 + t;
+        const bool live = x < ch.cn;
+        const int e = ch.sent[live ? x : 0], lsd = ch.sls[live ? x : 0], ls = lsd & 0x7fff, r = e >> ch.log_w;
+        const ulonglong2 *s = ch.bits + (long long)r * ch.nw2;
+        const ulonglong2 *row = ch.prow + ls * ch.rw2;
+        int acc = 0;
+        if constexpr (NK > 0) {
+            if (live && r != rcur) {  // a new run
+                rcur = r;
+#pragma unroll
+                for (int k = 0; k < NK - 1; ++k) sv[k] = s[l16 + 16 * k];
+                sv[NK - 1] = s[cl];
+            }
+#pragma unroll
+            for (int k = 0; k < NK - 1; ++k) acc += rs_tile_word<PL, ONES>(sv[k], row, ch.nw2, l16 + 16 * k);
+            const int last = rs_tile_word<PL, ONES>(sv[NK - 1], row, ch.nw2, cl);
+            acc += vlast ? last : 0;
+        } else {
+            for (int c = l16; c < ch.nw2; c += 16) acc += rs_tile_word<PL, ONES>(s[c], row, ch.nw2, c);
+        }
+        acc += dpp_move<DPP_QUAD_XOR1>(acc);
+        acc += dpp_move<DPP_QUAD_XOR2>(acc);
+        acc += dpp_move<DPP_ROW_HALF_MIRROR>(acc);
+        acc += dpp_move<DPP_ROW_MIRROR>(acc);
+        // ONES, the diagonal: its sign bit is 0, so the xor held the replica's own spin bit at site i (lsd >> 15)
+        if (live && l16 == 0) ch.base[(long long)r * ch.W + (e & wmask)] = ch.sjabs[ls] - 2 * (acc - (lsd >> 15));
+    }
+}
+
+template <int PL, bool ONES>
+__global__ void __launch_bounds__(RS_TILE_THREADS) rs_fields_tiles_kernel(const SweepArgs a, RowSharedPlan p, int S, int win) {
+    constexpr int RP = ONES ? 1 : PL + 1, T = RS_TILE_THREADS, NW = T / 64;
+    const int n = a.n, R = a.R, tile0 = blockIdx.x * S, ns = min(S, n - tile0);
+    const int *off = p.off + (long long)win * (n + 1) + tile0;
+    const int lo = off[0], hi = off[ns];
+    if (lo == hi) return;  // nobody proposes a site of this tile in this window
+    extern __shared__ ulonglong2 prow[];  // [S][RP][nw / 2], then the arrays below (row_shared_tile_lds)
+    const int nw2 = p.nw32 >> 2, rw2 = RP * nw2;
+    int *sent = reinterpret_cast<int *>(prow + (size_t)S * rw2);  // [RS_TILE_ENTRIES] the chunk's entries by replica
+    int *cnt = sent + RS_TILE_ENTRIES;                            // [R] entries per replica, then the cursors
+    int *soff = cnt + R;                                          // [S + 1] first entry of each site of the tile
+    int *sjabs = soff + S + 1;                                    // [S] sum_j |J_ij|
+    int *wtot = sjabs + S;                                        // [NW] the scan's wave totals
+    unsigned short *sls = reinterpret_cast<unsigned short *>(wtot + NW);  // [RS_TILE_ENTRIES] site - tile0 of sent[.] (15 bits)
+    const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6), sub = lane >> 4, l16 = lane & 15;
+    for (int s = tid; s <= ns; s += T) soff[s] = off[s];
+    for (int s = tid; s < ns; s += T) sjabs[s] = p.jabs[tile0 + s];
+    __syncthreads();
+    for (int s = wv; s < ns; s += NW) {  // a wave per row
+        if (soff[s] == soff[s + 1]) continue;
+        const ulonglong2 *src = reinterpret_cast<const ulonglong2 *>(p.jp) + (long long)(tile0 + s) * (PL + 1) * nw2;
+        for (int c = lane; c < rw2; c += 64) prow[s * rw2 + c] = src[c];  // (ONES: the sign plane, the first)
+    }
+    const ulonglong2 *bits = reinterpret_cast<const ulonglong2 *>(p.bits);
+    const int per = (R + T - 1) / T;  // counters per thread in the scan
+    for (int c0 = lo; c0 < hi; c0 += RS_TILE_ENTRIES) {
+        const int cn = min(RS_TILE_ENTRIES, hi - c0);
+        const int *ent = p.ent + c0;
+        for (int r = tid; r < R; r += T) cnt[r] = 0;
+        __syncthreads();  // (and the rows; and the last chunk's readers of sent are two barriers ahead of its writers)
+        for (int x = tid; x < cn; x += T) atomicAdd(&cnt[ent[x] >> p.log_w], 1);
+        __syncthreads();
+        {  // exclusive scan of cnt: thread t owns counters [t per, (t + 1) per)
+            const int r0 = tid * per;
+            int sum = 0;
+            for (int j = 0; j < per; ++j)
+                if (r0 + j < R) sum += cnt[r0 + j];
+            int inc = sum;
+#pragma unroll
+            for (int d = 1; d < 64; d <<= 1) {
+                const int t = __shfl_up(inc, d);
+                if (lane >= d) inc += t;
+            }
+            if (lane == 63) wtot[wv] = inc;
+            __syncthreads();
+            int run = inc - sum;
+            for (int w = 0; w < wv; ++w) run += wtot[w];
+            for (int j = 0; j < per; ++j)
+                if (r0 + j < R) {
+                    const int c = cnt[r0 + j];
+                    cnt[r0 + j] = run;
+                    run += c;
+                }
+        }
+        __syncthreads();
+        for (int x = tid; x < cn; x += T) {
+            const int e = ent[x], g = c0 + x;
+            int sl = 0, sh = ns;  // soff[sl] <= g < soff[sh]: the entry's site is the last s with soff[s] <= g
+            while (sh - sl > 1) {
+                const int mid = (sl + sh) >> 1;
+                if (soff[mid] <= g) sl = mid;
+                else sh = mid;
+            }
+            if constexpr (ONES) {  // the replica's own spin bit at the site rides in bit 15 (these loads overlap across the workgroup)
+                int w32;
+                unsigned int bit;
+                rs_bit_of(tile0 + sl, w32, bit);
+                if (p.bits[(long long)(e >> p.log_w) * p.nw32 + w32] & bit) sl |= 0x8000;
+            }
+            const int pos = atomicAdd(&cnt[e >> p.log_w], 1);
+            sent[pos] = e;
+            sls[pos] = (unsigned short)sl;
+        }
+        __syncthreads();
+        // the sorted chunk, a contiguous piece per quarter wave: the spin bits in registers up to NKMAX words of 16 bytes
+        // per lane (one magnitude plane: n <= 16384), streamed per entry beyond
+        const RsTileChunk ch{sent, sls, sjabs, prow, bits, p.base, cn, nw2, rw2, p.log_w, p.W, NW};
+        // (the register budget of 1024 threads: 8 words per lane beside one magnitude plane, 4 beside three; eight
+        //  magnitude planes -- nine LDS reads per word of spin bits -- always stream)
+        constexpr int NKMAX = row_shared_tile_register_words(PL);
+        const int nk = (nw2 + 15) >> 4;
+        switch (nk <= NKMAX ? nk : 0) {
+            case 1: rs_tile_pieces<PL, ONES, NKMAX >= 1 ? 1 : 0>(ch, wv, sub, l16); break;
+            case 2: rs_tile_pieces<PL, ONES, NKMAX >= 2 ? 2 : 0>(ch, wv, sub, l16); break;
+            case 3: rs_tile_pieces<PL, ONES, NKMAX >= 3 ? 3 : 0>(ch, wv, sub, l16); break;
+            case 4: rs_tile_pieces<PL, ONES, NKMAX >= 4 ? 4 : 0>(ch, wv, sub, l16); break;
+            case 5: rs_tile_pieces<PL, ONES, NKMAX >= 5 ? 5 : 0>(ch, wv, sub, l16); break;
+            case 6: rs_tile_pieces<PL, ONES, NKMAX >= 6 ? 6 : 0>(ch, wv, sub, l16); break;
+            case 7: rs_tile_pieces<PL, ONES, NKMAX >= 7 ? 7 : 0>(ch, wv, sub, l16); break;
+            case 8: rs_tile_pieces<PL, ONES, NKMAX >= 8 ? 8 : 0>(ch, wv, sub, l16); break;
+            default: rs_tile_pieces<PL, ONES, 0>(ch, wv, sub, l16); break;
+        }
+    }
+}
+
 // ---- fields by on-chip conversion (int8 rows with 8 magnitude planes): one workgroup (4 waves) per proposed site -------
 // LDS: [PL + 1][4 nseg] 64-bit words (sign plane first).
 template <typename JE, int PL, bool GRID>
@@ -555,9 +742,45 @@ static hipError_t rs_launch_fields(Kern kern, size_t lds, const SweepArgs &a, co
     return hipGetLastError();
 }
 
+// the tile kernel's instantiation for (planes, ones); null: none
+static const void *rs_tiles_kernel_of(int planes, bool ones) {
+    if (ones) return planes == 1 ? reinterpret_cast<const void *>(rs_fields_tiles_kernel<1, true>) : nullptr;
+    switch (planes) {
+        case 1: return reinterpret_cast<const void *>(rs_fields_tiles_kernel<1, false>);
+        case 3: return reinterpret_cast<const void *>(rs_fields_tiles_kernel<3, false>);
+        case 8: return reinterpret_cast<const void *>(rs_fields_tiles_kernel<8, false>);
+        default: return nullptr;
+    }
+}
+hipError_t row_shared_tiles_prepare(int planes, bool ones, size_t lds_bytes) {
+    const void *kern = rs_tiles_kernel_of(planes, ones);
+    if (!kern || lds_bytes > RS_TILE_LDS_BUDGET) return hipErrorInvalidValue;
+    return ensure_lds_limit(kern, lds_bytes);
+}
+template <typename Kern>
+static hipError_t rs_launch_tiles(Kern kern, const SweepArgs &a, const RowSharedPlan &p, const RowSharedTiles &t, int win,
+                                  hipStream_t st) {
+    const size_t lds = row_shared_tile_lds(a.n, p.planes, t.ones != 0, t.S, a.R);
+    hipError_t e = ensure_lds_limit(reinterpret_cast<const void *>(kern), lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(kern, dim3((a.n + t.S - 1) / t.S), dim3(RS_TILE_THREADS), lds, st, a, p, t.S, win);
+    return hipGetLastError();
+}
+static hipError_t rs_fields_tiles(const SweepArgs &a, const RowSharedPlan &p, const RowSharedTiles &t, int win, hipStream_t st) {
+    if (t.ones) return rs_launch_tiles(rs_fields_tiles_kernel<1, true>, a, p, t, win, st);
+    switch (p.planes) {
+        case 1: return rs_launch_tiles(rs_fields_tiles_kernel<1, false>, a, p, t, win, st);
+        case 3: return rs_launch_tiles(rs_fields_tiles_kernel<3, false>, a, p, t, win, st);
+        case 8: return rs_launch_tiles(rs_fields_tiles_kernel<8, false>, a, p, t, win, st);
+        default: return hipErrorInvalidValue;
+    }
+}
+
 template <typename JE>
-static hipError_t rs_fields(const SweepArgs &a, const RowSharedPlan &p, int grid, int win, hipStream_t st) {
+static hipError_t rs_fields(const SweepArgs &a, const RowSharedPlan &p, int grid, const RowSharedTiles &tiles, int win,
+                            hipStream_t st) {
     const size_t lds = (size_t)(p.planes + 1) * (p.nw32 / 2) * 8;
+    if (p.jp && tiles.S > 0) return rs_fields_tiles(a, p, tiles, win, st);
     if (p.jp) {
         switch (p.planes) {
             case 1: return rs_launch_fields(rs_fields_planes_kernel<1>, lds, a, p, win, st);
@@ -637,7 +860,13 @@ hipError_t launch_rs_build_planes(const void *J, bool j_is_i8, long long ldj, in
                   : rs_build_planes<float>(J, ldj, n, planes, jp, jabs, st);
 }
 
-hipError_t launch_sweep_dense_rs(const SweepArgs &a, const RowSharedPlan &p, bool j_is_i8, hipStream_t st, int grid) {
+hipError_t launch_sweep_dense_rs(const SweepArgs &a, const RowSharedPlan &p, bool j_is_i8, hipStream_t st, int grid,
+                                 RowSharedTiles tiles) {
+    // the tile kernel: resident planes, the image and the replica counters within LDS (the host rule saw to it), sign-only
+    // rows only where the planes are one magnitude plane
+    if (tiles.S > 0 && (!p.jp || tiles.S > RS_TILE_MAX_SITES || a.R > RS_TILE_MAX_REPLICAS || (tiles.ones && p.planes != 1) ||
+                        row_shared_tile_lds(a.n, p.planes, tiles.ones != 0, tiles.S, a.R) > RS_TILE_LDS_BUDGET))
+        return hipErrorInvalidValue;
     // (many models: only over one shared matrix -- the plan buckets proposals by site, whatever the replica's model)
     if (a.reps_per_model < 0 || (a.reps_per_model > 0 && a.model_stride_j != 0)) return hipErrorInvalidValue;
     if (a.rep_list || a.R <= 0 || a.n <= 0 || (p.W != 256 && p.W != 512 && p.W != 1024) || (1 << p.log_w) != p.W)
@@ -659,7 +888,7 @@ hipError_t launch_sweep_dense_rs(const SweepArgs &a, const RowSharedPlan &p, boo
         hipLaunchKernelGGL(rs_plan_kernel<true>, pgrid, dim3(256), plds, st, a, p, k);
         e = hipGetLastError();
         for (int w = 0; w < nwin && e == hipSuccess; ++w) {
-            e = j_is_i8 ? rs_fields<int8_t>(a, p, grid, w, st) : rs_fields<float>(a, p, grid, w, st);
+            e = j_is_i8 ? rs_fields<int8_t>(a, p, grid, tiles, w, st) : rs_fields<float>(a, p, grid, tiles, w, st);
             if (e != hipSuccess) break;
             if (chain_bits)
                 e = j_is_i8 ? rs_chain<int8_t, true>(a, p, grid, k, w, st) : rs_chain<float, true>(a, p, grid, k, w, st);
@@ -670,12 +899,14 @@ hipError_t launch_sweep_dense_rs(const SweepArgs &a, const RowSharedPlan &p, boo
         if (e == hipSuccess && !a.no_best)
             e = launch_update_best(a.energy, a.spins, a.best_energy, a.best_spins, a.sstride, a.R, st);
     }
-    if (e == hipSuccess && grid)
-        note_sweep_kernel("sweep_dense_rs<%s, planes=%d, W=%d, grid=2^-%d> (row-shared windows: plan, fields from %s, chain)",
-                          j_is_i8 ? "int8_t" : "float", p.planes, p.W, grid - 1, p.jp ? "resident bit-planes" : "on-chip conversion");
-    else if (e == hipSuccess)
-        note_sweep_kernel("sweep_dense_rs<%s, planes=%d, W=%d> (row-shared windows: plan, fields from %s, chain)",
-                          j_is_i8 ? "int8_t" : "float", p.planes, p.W, p.jp ? "resident bit-planes" : "on-chip conversion");
+    if (e == hipSuccess) {
+        // (the words "fields from resident bit-planes" / "on-chip conversion" are read by tests and bench.py)
+        char gs[24] = "", ts[64] = "";
+        if (grid) std::snprintf(gs, sizeof(gs), ", grid=2^-%d", grid - 1);
+        if (p.jp && tiles.S > 0) std::snprintf(ts, sizeof(ts), " in tiles of %d sites%s", tiles.S, tiles.ones ? ", sign-only" : "");
+        note_sweep_kernel("sweep_dense_rs<%s, planes=%d, W=%d%s> (row-shared windows: plan, fields from %s%s, chain)",
+                          j_is_i8 ? "int8_t" : "float", p.planes, p.W, gs, p.jp ? "resident bit-planes" : "on-chip conversion", ts);
+    }
     return e;
 }
 

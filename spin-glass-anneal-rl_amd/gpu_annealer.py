@@ -53,6 +53,9 @@ class GPUAnnealerConfig:
     #                                       binary grid 2^-k under any h (quarter-valued QUBO encodings, integer J beside a
     #                                       real-valued h; same chain).  Acts with field_cache="off", where the autotuner picks
     #                                       the form or option "row_shared" = 1 forces it
+    row_shared_fields: int = 2            # engine option "row_shared_fields": the fields kernel of those windows over
+    #                                       resident bit-planes -- 0 per proposed site, 1 per tile of sites wherever it can
+    #                                       run, 2 where it was measured to win (same chain)
     device_index: Optional[int] = None
 
     def __post_init__(self):
@@ -112,6 +115,8 @@ class GPUAnnealer:
                 eng.set_option("clf_fixed_point", 1)  # (read when the couplings are set)
             if cfg.row_shared_grid:
                 eng.set_option("row_shared_grid", 1)  # (read at every sweep; acts with field_cache="off")
+            if cfg.row_shared_fields != 2:
+                eng.set_option("row_shared_fields", cfg.row_shared_fields)  # (read at every sweep)
             model.load_into(eng, storage=cfg.coupling_storage)
             eng.set_update_rule(rule)
             eng.init_replicas(1, seed=fresh_seed(cfg.random_seed), s0=model.spins_int8()[None, :])

@@ -121,6 +121,8 @@ class MultiGPUAnnealer:
             eng.set_option("clf_fixed_point", 1)  # (read when the couplings are set)
         if self.annealer_config.row_shared_grid:  # (row-shared windows for dense J on a binary grid, any h)
             eng.set_option("row_shared_grid", 1)
+        if self.annealer_config.row_shared_fields != 2:  # (the fields kernel of the row-shared windows: 0 per site, 1 tiles)
+            eng.set_option("row_shared_fields", self.annealer_config.row_shared_fields)
         model.load_into(eng, storage=self.annealer_config.coupling_storage)
         return eng
 

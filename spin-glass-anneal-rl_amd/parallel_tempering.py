@@ -52,6 +52,9 @@ class ParallelTemperingConfig:
     row_shared_grid: bool = False         # option "row_shared_grid": row-shared windows for dense J on a binary grid 2^-k
     #                                       under any h (same chain); acts with field_cache="off", where autotune picks the
     #                                       form or option "row_shared" = 1 forces it
+    row_shared_fields: int = 2            # option "row_shared_fields": the fields kernel of those windows over resident
+    #                                       bit-planes -- 0 per proposed site, 1 per tile of sites wherever it can run, 2 where
+    #                                       it was measured to win (same chain)
     device_index: Optional[int] = None
     autotune: Optional[bool] = None       # measured launch geometry (None: for long runs only)
 
@@ -99,6 +102,8 @@ class ParallelTempering:
                 eng.set_option("clf_fixed_point", 1)  # (read when the couplings are set)
             if cfg.row_shared_grid:
                 eng.set_option("row_shared_grid", 1)  # (read at every sweep; acts with field_cache="off")
+            if cfg.row_shared_fields != 2:
+                eng.set_option("row_shared_fields", cfg.row_shared_fields)  # (read at every sweep)
             model.load_into(eng, storage=cfg.coupling_storage)
             eng.set_update_rule(rule)
             eng.init_replicas(R, seed=fresh_seed(cfg.random_seed),
