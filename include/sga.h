@@ -80,7 +80,7 @@ typedef struct sga_engine sga_engine;
 int sga_create(int device, sga_engine **out);
 void sga_destroy(sga_engine *e);
 const char *sga_last_error(void);
-int sga_version(void);  /* 1900: options "row_shared_fields" and "row_shared_tile_sites" (row-shared fields in tiles of sites, sign-only rows); 1800: option "row_shared_grid", sga_route_query.rs_grid; 1700: sga_set_csr_shared (one set of CSR rows, many field vectors: every one-wave-per-replica CSR form for such batches), sga_route_query.shared_j on SGA_ROUTE_CSR queries; 1600: sga_set_dense_shared (one coupling matrix, many field vectors; row-shared windows, bit-planes and the matrix-core pass for such batches), sga_route_query.shared_j; 1500: sga_get_scan_summary, and sga_set_dense / sga_set_dense_batch / sga_set_csr / sga_set_csr64 / sga_set_csr_batch refuse a NaN or +-Inf in J or h (SGA_ERR_INVALID, "non-finite"); 1400: option "batch_fixed_point" (fixed-point cached local fields for many-model dense batches); 1300: options "ragged_field_cache" and "clf_fixed_point" together (fixed-point cached local fields for ragged CSR batches); 1200: sga_set_groups_csr (group couplings plus a stored sparse remainder); 1100: option "ragged_field_cache" (cached local fields for ragged CSR batches); 1000: sga_set_groups */
+int sga_version(void);  /* 2000: the row-shared windows (option "row_shared") serve SGA_RULE_GLAUBER and SGA_RULE_HEAT_BATH too ("rule=glauber" / "rule=heat-bath" in sga_describe and sga_get_last_kernel; the window sga_autotune picks holds for the rule it was timed under); 1900: options "row_shared_fields" and "row_shared_tile_sites" (row-shared fields in tiles of sites, sign-only rows); 1800: option "row_shared_grid", sga_route_query.rs_grid; 1700: sga_set_csr_shared (one set of CSR rows, many field vectors: every one-wave-per-replica CSR form for such batches), sga_route_query.shared_j on SGA_ROUTE_CSR queries; 1600: sga_set_dense_shared (one coupling matrix, many field vectors; row-shared windows, bit-planes and the matrix-core pass for such batches), sga_route_query.shared_j; 1500: sga_get_scan_summary, and sga_set_dense / sga_set_dense_batch / sga_set_csr / sga_set_csr64 / sga_set_csr_batch refuse a NaN or +-Inf in J or h (SGA_ERR_INVALID, "non-finite"); 1400: option "batch_fixed_point" (fixed-point cached local fields for many-model dense batches); 1300: options "ragged_field_cache" and "clf_fixed_point" together (fixed-point cached local fields for ragged CSR batches); 1200: sga_set_groups_csr (group couplings plus a stored sparse remainder); 1100: option "ragged_field_cache" (cached local fields for ragged CSR batches); 1000: sga_set_groups */
 /* Run on an existing HIP stream (e.g. torch.cuda.current_stream().cuda_stream); NULL = the
  * engine's own stream (default). */
 int sga_set_stream(sga_engine *e, void *hip_stream);
@@ -125,8 +125,9 @@ int sga_set_dense_batch(sga_engine *e, const float *J, int64_t ldJ, const float 
  *   4. The forms that need the ROWS to be the same for every replica open up: bit-plane storage (SGA_J_AUTO resolves
  *      as for one model -- bit-planes for ternary J from n = 4096, else int8, else fp32 -- and SGA_J_T2 is served),
  *      row-shared windows (option "row_shared"; integer J and EVERY h with exact fp32 sums -- one accept table for
- *      the batch --, symmetric J with a zero diagonal, |J| <= 255, Metropolis, production arguments, field cache
- *      OFF: a proposed row is read once for every replica of every model that proposes it) and the matrix-core
+ *      the batch --, symmetric J with a zero diagonal, |J| <= 255, production arguments, field cache OFF: a proposed
+ *      row is read once for every replica of every model that proposes it; Metropolis decides with the accept table,
+ *      Glauber and heat bath with the row kernels' general rule, Wolff is never served) and the matrix-core
  *      energy / field pass (J leaves HBM once for all replicas).  Cached fields ON / AUTO behave as on the stacked
  *      batch: batch-wide scale, field width and table; the fixed-point form behind "clf_fixed_point" +
  *      "batch_fixed_point".  AUTO's break-evens are the stacked batch's (not measured for shared batches).
@@ -584,8 +585,16 @@ int sga_set_field_cache(sga_engine *e, int mode);
  *                           "row-shared windows" (csrc/sweep_dense_rs.hip) -- each sweep cut into windows of W updates per
  *                           replica, each proposed row read ONCE per window and dotted with the window-start spins of every
  *                           replica that proposes it, the chain then walked per replica with exact corrections for the
- *                           window's earlier accepts.  Same chain.  0 = never, 1 = wherever it applies (W: option
- *                           "row_shared_window"), 2 = where sga_autotune measured it ahead of every geometry by more than 1 % [sweep; SGA_ROW_SHARED]
+ *                           window's earlier accepts.  Same chain.  The rule: SGA_RULE_METROPOLIS decides with the accept
+ *                           table; SGA_RULE_GLAUBER and SGA_RULE_HEAT_BATH (version >= 2000) decide with the row kernels'
+ *                           general fp64 rule on the same exact fields -- sga_describe and sga_get_last_kernel then say
+ *                           "rule=glauber" / "rule=heat-bath" --; SGA_RULE_WOLFF is never served.  0 = never, 1 = wherever
+ *                           it applies (W: option "row_shared_window"), 2 = where sga_autotune measured it ahead of every
+ *                           geometry by more than 1 %, under the rule the engine had when it measured: after
+ *                           sga_set_update_rule to another rule the row-per-proposal kernel runs until sga_autotune is
+ *                           called again.  Measured at n = 10^4, 1024 replicas (profiles/row_shared_rules.json): +-1 J,
+ *                           integer h 21.8 -> 1.22 ms per sweep under Glauber, 22.1 -> 1.21 under heat bath; J = +-1/4
+ *                           with "row_shared_grid" 57.8 -> 1.90 and 57.9 -> 1.86                    [sweep; SGA_ROW_SHARED]
  *   "row_shared_grid"       0 (default) | 1   (version >= 1800) opens the row-shared windows to dense problems the integer form
  *                           does not take: every J_ij a multiple of 2^-k (k <= 30, integer J: k = 0) with 2^k |J_ij| <= 255
  *                           and 2^k max_i (sum_j |J_ij| + |h_i|) < 2^24, J symmetric with a zero diagonal and not all zero, h
@@ -643,7 +652,9 @@ int sga_set_tuning(sga_engine *e, int waves_per_replica, int sweeps_per_launch);
  * again and the table of sga_get_autotune_table is empty.  Dense problems under option "row_shared" = 2 also time the row-shared windows at W = 256, 512 and
  * 1024 on the winning geometry, each after 16 untimed sweeps at that window from the saved state (the form's time depends on
  * the acceptance, which falls steeply in the first sweeps of a run), over at least 16 timed sweeps (table entries "row-shared:W<W>") and keep the fastest where it beats the fastest
- * geometry by more than 1 %; *best_ms_per_sweep is the fastest GEOMETRY's figure either way.  No-op for sga_set_tsp problems.
+ * geometry by more than 1 %; *best_ms_per_sweep is the fastest GEOMETRY's figure either way.  The trials sweep under the engine's update
+ * rule (Metropolis, Glauber or heat bath; version >= 2000) and the window kept holds for that rule only: after sga_set_update_rule to another rule the
+ * row-per-proposal kernel runs until sga_autotune is called again.  No-op for sga_set_tsp problems.
  * (No reference counterpart: the reference has no launch geometry.) */
 int sga_autotune(sga_engine *e, double *best_ms_per_sweep);
 /* What the last sga_autotune of this engine measured: "candidate=ms per sweep;..." (dense: "<waves>x<chunks per wave>",
@@ -707,7 +718,9 @@ int sga_route_query_init(sga_route_query *q);
  * "csr form=rows|narrow|narrow-bits|wide-bits|wide-bytes spins=... waves=... updates_per_step=..." | "tsp waves=... passes=..." |
  * "groups n_groups=... sums=int16|int32 waves=... kernel=sweep_groups_kernel|sweep_groups_general_kernel"
  * (with a stored remainder, rest_nnz > 0: " rest_nnz=... rest_max_row=..." behind it)
- * followed by " cached=..." (what sga_set_field_cache would run).  Pure: no device needed. */
+ * followed by " cached=..." (what sga_set_field_cache would run).  Pure: no device needed.
+ * A query does not carry the update rule: the line is the SGA_RULE_METROPOLIS answer (" sweep=row-shared(...)" under
+ * option "row_shared" = 1 included); sga_describe and sga_get_last_kernel name the rule an engine sweeps under. */
 int sga_explain_route(const sga_route_query *q, char *buf, int buflen);
 /* the query the engine itself would pose for its current problem / replicas / options */
 int sga_get_route_query(sga_engine *e, sga_route_query *out);

@@ -184,6 +184,7 @@ int sga_autotune(sga_engine *e, double *best_ms_per_sweep) {
     e->field_cache = SGA_FIELD_CACHE_OFF;
     e->rs_suspend = true;  // (the geometry trials time the row-per-proposal kernel, whatever option "row_shared" says)
     e->rs_tuned_w = 0;
+    e->rs_tuned_rule = SGA_RULE_METROPOLIS;
 
     // lay the replicas out for `waves` (0 = heuristic) and put the saved state back
     auto layout = [&](int waves) -> int {
@@ -282,6 +283,7 @@ int sga_autotune(sga_engine *e, double *best_ms_per_sweep) {
         int pick = 0;
         for (int W : {256, 512, 1024}) {
             e->rs_tuned_w = W;
+            e->rs_tuned_rule = e->rule;  // (timed() sweeps under the engine's rule: the pick is that rule's)
             if (row_shared_window(e, true) != W) break;  // (the problem does not admit the form)
             rc = layout(best_w);
             if (rc != SGA_OK) break;
@@ -300,7 +302,10 @@ int sga_autotune(sga_engine *e, double *best_ms_per_sweep) {
             if (t / k < best_rs) best_rs = t / k, pick = W;
         }
         e->rs_tuned_w = (rc == SGA_OK && pick > 0 && best_rs < best * 0.99) ? pick : 0;
-        if (!e->rs_tuned_w) e->free_row_shared();
+        if (!e->rs_tuned_w) {
+            e->rs_tuned_rule = SGA_RULE_METROPOLIS;
+            e->free_row_shared();
+        }
     }
     // leave with the winner (or the caller's setting if something failed) and the saved state
     e->timing = was_timing;

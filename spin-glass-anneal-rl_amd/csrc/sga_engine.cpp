@@ -125,12 +125,15 @@ int fields_pass(sga_engine *e, int r0, int count, double *energy, void *fields) 
 
 // Row-shared windows (sweep_dense_rs.hip, option "row_shared"): the window W of the form for sweeps whose arguments are
 // the production ones (lean), 0 where today's row-per-proposal kernel runs.  The form needs what the look-ahead form
-// needs -- one dense matrix, integer J and h with exact fp32 sums (the accept table), Metropolis -- and J symmetric with a
-// zero diagonal (a flip's correction is read from the flipped site's row), |J| <= 255 (bit-planes of |J|).  One matrix:
+// needs -- one dense matrix, integer J and h with exact fp32 sums (the accept table) -- and J symmetric with a
+// zero diagonal (a flip's correction is read from the flipped site's row), |J| <= 255 (bit-planes of |J|).  The rule:
+// Metropolis decides with the accept table, Glauber and heat bath with the row kernels' general rule on the same exact
+// fields (lean then implies SGA_ARITH_F64: sga_sweep refuses them fp32), Wolff is never served.  One matrix:
 // one model, or the models of sga_set_dense_shared, whose conditions are the batch's (table_m is over every h: one
 // accept table); a stacked batch has a row i per model and stays on the row-per-proposal kernel.
 // 1 = wherever it applies (W: option "row_shared_window", else the autotuner's, else 1024), 2 = where sga_autotune
-// measured it ahead (default).
+// measured it ahead (default).  The autotuner's W counts only while the engine's rule is the one it was timed under
+// (rs_tuned_rule): the form's time follows the flip rate, and Glauber's is not Metropolis'.
 // Option "row_shared_grid" = 1 opens the form to the problems the integer form does not take and the set-time verdict
 // admits (sga_classify.cpp, row_shared_grid: J on a grid 2^-k, |2^k J| <= 255, scaled row sums below 2^24, any h) under
 // the same remaining conditions; the chain then decides with the row kernels' general rule instead of the table's.
@@ -145,13 +148,14 @@ int row_shared_form_planes(const sga_engine *e, int *grid) {
 int row_shared_window(const sga_engine *e, bool lean) {
     const long long o = e->opt[OPT_ROW_SHARED];
     int grid = 0;
-    if (o == 0 || e->rs_suspend || !lean || e->rule != SGA_RULE_METROPOLIS || e->field_cache != SGA_FIELD_CACHE_OFF) return 0;
+    if (o == 0 || e->rs_suspend || !lean || e->rule == SGA_RULE_WOLFF || e->field_cache != SGA_FIELD_CACHE_OFF) return 0;
     if (e->csr || e->implicit() || e->ragged || (e->n_models != 1 && !e->shared_j) || !e->consistent_dE) return 0;
     if (e->opt[OPT_LOOK_AHEAD] == 0 || e->opt[OPT_FORCE_GENERAL] != 0 || !e->J_packed) return 0;
     if (row_shared_form_planes(e, &grid) == 0 || (long long)e->R * e->n >= (1ll << 31) || e->R >= (1 << 20)) return 0;
-    if (o == 2) return e->rs_tuned_w;
+    const int tuned = e->rule == e->rs_tuned_rule ? e->rs_tuned_w : 0;  // the autotuner's pick belongs to the rule it timed
+    if (o == 2) return tuned;
     const long long fw = e->opt[OPT_ROW_SHARED_WINDOW];  // (option "row_shared_window": W for option 1)
-    return fw >= 1024 ? 1024 : fw >= 512 ? 512 : fw >= 256 ? 256 : (e->rs_tuned_w > 0 ? e->rs_tuned_w : 1024);
+    return fw >= 1024 ? 1024 : fw >= 512 ? 512 : fw >= 256 ? 256 : (tuned > 0 ? tuned : 1024);
 }
 
 // The fields kernel of the row-shared windows over resident planes, by option "row_shared_fields": the tile size S and
@@ -455,7 +459,7 @@ int ensure_packed(sga_engine *e) {
 extern "C" {
 
 const char *sga_last_error(void) { return g_last_error.c_str(); }
-int sga_version(void) { return 1900; }  // + options "row_shared_fields", "row_shared_tile_sites": the row-shared fields in tiles of sites, sign-only rows (sweep_dense_rs.hip, rs_fields_tiles_kernel)  // 1800: + option "row_shared_grid": row-shared windows for dense J on a binary grid under any h (sweep_dense_rs.hip, GRID), sga_route_query.rs_grid  // 1700: + sga_set_csr_shared (one set of CSR rows, many field vectors)  // 1600: + sga_set_dense_shared (one coupling matrix, many field vectors), sga_route_query.shared_j  // 1500: + sga_get_scan_summary; the dense and CSR setters refuse non-finite J / h  // 1400: + option "batch_fixed_point": fixed-point cached local fields for many-model dense batches (sweep_clf_fx.hip, MODELS)  // 1300: + options "ragged_field_cache" and "clf_fixed_point" together: fixed-point cached local fields for ragged CSR batches (sweep_clf_csr.hip)  // 1200: + sga_set_groups_csr (group couplings plus a stored sparse remainder, sweep_groups.hip)  // 1100: + option "ragged_field_cache" (cached local fields for ragged CSR batches, sweep_clf_csr.hip)  // 1000: + sga_set_groups (implicit cardinality-group couplings, sweep_groups.hip)  // 900: + cached local fields for many-model dense batches (sga_set_dense_batch)  // 800: + option "clf_fixed_point" over dense couplings (sweep_clf_fx.hip)  // 700: + option "clf_fixed_point" (cached fields of real-valued CSR couplings)  // 600: + sga_set_csr_batch / sga_get_batch_model (ragged CSR batches)  // round 5: + sga_explain_route / sga_get_route_query, sga_get_last_kernel, sga_get_autotune_table, ladder-local sga_exchange
+int sga_version(void) { return 2000; }  // + row-shared windows under SGA_RULE_GLAUBER and SGA_RULE_HEAT_BATH (sweep_dense_rs.hip, ANYRULE; "rule=..." in sga_describe and sga_get_last_kernel), the autotuner's window kept per rule  // 1900: + options "row_shared_fields", "row_shared_tile_sites": the row-shared fields in tiles of sites, sign-only rows (sweep_dense_rs.hip, rs_fields_tiles_kernel)  // 1800: + option "row_shared_grid": row-shared windows for dense J on a binary grid under any h (sweep_dense_rs.hip, GRID), sga_route_query.rs_grid  // 1700: + sga_set_csr_shared (one set of CSR rows, many field vectors)  // 1600: + sga_set_dense_shared (one coupling matrix, many field vectors), sga_route_query.shared_j  // 1500: + sga_get_scan_summary; the dense and CSR setters refuse non-finite J / h  // 1400: + option "batch_fixed_point": fixed-point cached local fields for many-model dense batches (sweep_clf_fx.hip, MODELS)  // 1300: + options "ragged_field_cache" and "clf_fixed_point" together: fixed-point cached local fields for ragged CSR batches (sweep_clf_csr.hip)  // 1200: + sga_set_groups_csr (group couplings plus a stored sparse remainder, sweep_groups.hip)  // 1100: + option "ragged_field_cache" (cached local fields for ragged CSR batches, sweep_clf_csr.hip)  // 1000: + sga_set_groups (implicit cardinality-group couplings, sweep_groups.hip)  // 900: + cached local fields for many-model dense batches (sga_set_dense_batch)  // 800: + option "clf_fixed_point" over dense couplings (sweep_clf_fx.hip)  // 700: + option "clf_fixed_point" (cached fields of real-valued CSR couplings)  // 600: + sga_set_csr_batch / sga_get_batch_model (ragged CSR batches)  // round 5: + sga_explain_route / sga_get_route_query, sga_get_last_kernel, sga_get_autotune_table, ladder-local sga_exchange
 
 int sga_create(int device, sga_engine **out) {
     if (!out) return fail(SGA_ERR_INVALID, "out is NULL");

@@ -239,14 +239,15 @@ struct sga_engine {
     hipStream_t aux_stream = nullptr;   // the second launch of a mixed sweep
     hipEvent_t fork_ev = nullptr, join_ev = nullptr;
     char last_kernel[512] = {0};        // the instantiation this engine's last sweep launch ran (sga_get_last_kernel)
-    // row-shared windows (sweep_dense_rs.hip, option "row_shared"): the window the autotuner picked (0: none), the
+    // row-shared windows (sweep_dense_rs.hip, option "row_shared"): the window the autotuner picked (0: none) and the
+    // update rule it was measured under (the form's time follows the flip rate: the pick holds for that rule only), the
     // plan / field scratch and what it was sized for; rs_suspend keeps the form out of the autotuner's geometry trials.
     // rs_jp / rs_jabs: the resident bit-planes of J_packed and sum_j |J_ij| per row (RowSharedPlan::jp, jabs), built by
     // the form's first sweep of a problem.  They belong to the problem, not to W or the replicas: free_problem -- the
     // one place J_packed is replaced -- drops them, window and replica changes keep them.
     // rs_grid_planes / rs_grid_k: the set-time verdict of the grid form (option "row_shared_grid", sga_classify.cpp:
     // row_shared_grid) -- planes of |2^k J| (0: no verdict) and k; a shared-coupling batch: over the batch's words.
-    int rs_tuned_w = 0;
+    int rs_tuned_w = 0, rs_tuned_rule = SGA_RULE_METROPOLIS;
     int rs_grid_planes = 0, rs_grid_k = 0;
     bool rs_suspend = false;
     sga::RowSharedPlan rs{};
@@ -362,6 +363,7 @@ struct sga_engine {
         rs_ones = false;
         rs_tiles_refused = false;
         rs_tuned_w = 0;
+        rs_tuned_rule = SGA_RULE_METROPOLIS;
         rs_grid_planes = 0;
         rs_grid_k = 0;
         // every other problem-scoped member back to its declared default: what one problem's setter computed is never
@@ -426,6 +428,7 @@ struct sga_engine {
         dev_free(d_rep_lists);
         free_row_shared();
         rs_tuned_w = 0;
+        rs_tuned_rule = SGA_RULE_METROPOLIS;
         R = Rg = 0;
         n_ladders = 0;
     }

@@ -525,7 +525,9 @@ hipError_t row_shared_tiles_prepare(int planes, bool ones, size_t lds_bytes);
 hipError_t launch_rs_build_planes(const void *J, bool j_is_i8, long long ldj, int n, int planes, int grid_k,
                                   unsigned long long *jp, int *jabs, hipStream_t st);
 // a.n_sweeps sweeps: spins -> bits, then per sweep the plan, per window fields + chain, best tracking.  Production
-// arguments only (Philox sites, Metropolis with the accept table, fp64 rule, no per-update traces, all replicas).
+// arguments only (Philox sites, fp64 rule, no per-update traces, all replicas).  a.rule: Metropolis decides with the
+// accept table; Glauber and heat bath with the row kernels' general rule (the ANYRULE instantiations, "rule=glauber" /
+// "rule=heat-bath" in the kernel note); Wolff is an error.
 // grid: 0 the integer form; else 1 + k, the GRID instantiations (J on the grid 2^-k, any h: the general fp64 rule).
 // tiles.S > 0 (with resident planes): the fields by rs_fields_tiles_kernel in tiles of S sites.
 hipError_t launch_sweep_dense_rs(const SweepArgs &a, const RowSharedPlan &p, bool j_is_i8, hipStream_t st, int grid = 0,

@@ -414,11 +414,13 @@ int sga_describe(sga_engine *e, char *buf, int buflen) {
         if (rw > 0) {
             int grid = 0;
             const int pl = row_shared_form_planes(e, &grid);
+            // (Metropolis lines name no rule; Glauber and heat bath decide with the general rule: " rule=...")
+            const char *rule = e->rule == SGA_RULE_GLAUBER ? " rule=glauber" : e->rule == SGA_RULE_HEAT_BATH ? " rule=heat-bath" : "";
             if (grid)  // option "row_shared_grid": J on the grid 2^-k, the planes are those of 2^k J
-                std::snprintf(tmp + std::strlen(tmp), sizeof(tmp) - std::strlen(tmp), " sweep=row-shared(W=%d planes=%d grid=2^-%d)", rw,
-                              pl, grid - 1);
+                std::snprintf(tmp + std::strlen(tmp), sizeof(tmp) - std::strlen(tmp), " sweep=row-shared(W=%d planes=%d grid=2^-%d%s)", rw,
+                              pl, grid - 1, rule);
             else
-                std::snprintf(tmp + std::strlen(tmp), sizeof(tmp) - std::strlen(tmp), " sweep=row-shared(W=%d planes=%d)", rw, pl);
+                std::snprintf(tmp + std::strlen(tmp), sizeof(tmp) - std::strlen(tmp), " sweep=row-shared(W=%d planes=%d%s)", rw, pl, rule);
             if (sga::row_shared_resident(e->want_i8, pl))  // (the bytes the form's first sweep adds, once per problem)
                 std::snprintf(tmp + std::strlen(tmp), sizeof(tmp) - std::strlen(tmp), " rs_fields=resident-planes(%zuB)",
                               sga::row_shared_plane_bytes(e->n, pl));

@@ -1,5 +1,6 @@
 // sweep_dense_rs.hip -- "row-shared windows": the dense Metropolis sweep of integer problems with ONE read of a
-// coupling row per proposed site and window, instead of one per proposal.
+// coupling row per proposed site and window, instead of one per proposal; the Glauber and heat-bath
+// rules walk the same windows (ANYRULE, below).
 //
 // The sites and uniforms come from the counter RNG (the stream of fetch_pair / PairSource), so every replica's
 // proposals are known ahead of the chain.  A sweep is cut into windows of W updates per replica; each window runs
@@ -51,7 +52,23 @@
 // A shared-coupling batch: k, the planes and the bound are the batch's (one J; the bound's word takes the largest
 // |h| of any model), each wave reads its model's h.  The non-GRID instantiations are the integer form's, unchanged:
 // the GRID ones take a plan type of their own (RowSharedGridPlan), so not even an argument offset moves in the others.
+//
+// ANYRULE (a.rule is SGA_RULE_GLAUBER or SGA_RULE_HEAT_BATH): nothing above the chain knows the rule -- every rule takes
+// one (site, u) pair per update from the same stream coordinates, so plan, fields, planes and corrections are
+// unchanged -- and the chain's block logic needs the decision to be a pure function of (field, spin, u, T) only: the
+// first lane that flips is the chain's next flip, every lane before it stays against fields that hold all earlier flips,
+// and "flip iff new_spin != s_i" is such a function exactly as "accept" is.  The decision is metropolis_accept(a.rule,
+// SGA_ARITH_F64, ...), the row kernels' own (sweep_dense_impl.h), in the integer and the GRID form alike.  Integer form:
+// the field stays the exact integer-valued fp32 it is above (every partial sum of the corrected field an integer below
+// 2^24, in any order), which is the row kernel's dot for the same spins, so field = (double)dot + (double)h is the row
+// kernel's value; GRID: the proof above does not mention the rule.  dE = 2 s field is formed as metropolis_accept
+// forms it and E += dE runs in chain order (heat bath too: only the per-update record is negated there, and the form
+// keeps none).  Glauber's x = (float)(-2.0 * field / T) keeps its fp64 divide per lane and heat bath's
+// x = (float)((-2.0 * (1.0 / T)) * field) its operation sequence (the factor is wave-uniform: formed once, the same
+// operations): T = 0, T = inf and a zero field give the row kernels' +-inf, NaN and -+0 and their decisions.
+// With ANYRULE off an instantiation is the Metropolis code, unchanged.
 #include <cstdio>
+#include <cstring>
 #include <type_traits>
 
 #include "sweep_common.h"
@@ -602,6 +619,7 @@ constexpr int RS_CHAIN_U = 8;  // earlier accepts applied to a block per wait
 // order of the corrections does not matter.
 // GRID: the fields are held in real units (2^-k times those integers: as exact, in any order), and the decision and
 // dE are metropolis_accept's, the row kernels' general rule (the proof at the top of the file).
+// ANYRULE: "accept" reads "flip" -- Glauber and heat bath by the same general rule, in either form of the fields.
 template <bool GRID>
 __device__ __forceinline__ bool rs_decide(int cs, float cf, float chh, float cu, double T, int table_m) {
     if constexpr (GRID) {
@@ -611,8 +629,19 @@ __device__ __forceinline__ bool rs_decide(int cs, float cf, float chh, float cu,
         return rs_accept((float)cs * (cf + chh), cu, T, table_m);
     }
 }
+// ANYRULE: Glauber / heat bath (rule: a.rule, wave-uniform at run time) by the row kernels' general rule, in the integer
+// form (cf the exact integer-valued field) and the GRID form alike; true: the spin flips.  Off: rs_decide, as it was.
+template <bool GRID, bool ANYRULE>
+__device__ __forceinline__ bool rs_decide_rule(int rule, int cs, float cf, float chh, float cu, double T, int table_m) {
+    if constexpr (ANYRULE) {
+        double dE;
+        return metropolis_accept(rule, SGA_ARITH_F64, cf, cs, chh, 0.0f, T, cu, dE);
+    } else {
+        return rs_decide<GRID>(cs, cf, chh, cu, T, table_m);
+    }
+}
 
-template <typename JE, int NB, bool BITS, bool GRID>
+template <typename JE, int NB, bool BITS, bool GRID, bool ANYRULE = false>
 __global__ void __launch_bounds__(64) rs_chain_kernel(const SweepArgs a, const RsPlanArg<GRID> pg, int k, int win) {
     const RowSharedPlan &p = rs_plan(pg);
     constexpr int W = 64 * NB, K = RS_CHAIN_K, U = RS_CHAIN_U;
@@ -682,7 +711,7 @@ __global__ void __launch_bounds__(64) rs_chain_kernel(const SweepArgs a, const R
                 }
             }
         }
-        bool acc = cvalid && rs_decide<GRID>(cs, cf, chh, cu, T, a.table_m);
+        bool acc = cvalid && rs_decide_rule<GRID, ANYRULE>(a.rule, cs, cf, chh, cu, T, a.table_m);
         unsigned long long m = ballot64(acc);  // accepting lanes among the undecided ones
         while (m) {
             int cl[K];
@@ -705,7 +734,7 @@ __global__ void __launch_bounds__(64) rs_chain_kernel(const SweepArgs a, const R
                 if (fl < cl[j]) break;      // not fetched (or the candidates are used up): the next round
                 if (fl > cl[j]) continue;   // candidate j accepts no longer
                 const int sa = read_lane(csite, fl), ss = read_lane(cs, fl);
-                if constexpr (GRID) {  // metropolis_accept's dE, formed as it forms it
+                if constexpr (GRID || ANYRULE) {  // metropolis_accept's dE, formed as it forms it
                     E += 2.0 * (double)ss * ((double)read_lane(cf, fl) + (double)read_lane(chh, fl));
                 } else {
                     const float fk = (float)ss * (read_lane(cf, fl) + read_lane(chh, fl));
@@ -722,7 +751,7 @@ __global__ void __launch_bounds__(64) rs_chain_kernel(const SweepArgs a, const R
                 ++nA;
                 cf -= rs_coupling<JE, BITS>(x[j], bit, unit) * (2.0f * (float)ss);
                 if (csite == sa) cs = -cs;
-                acc = cvalid && rs_decide<GRID>(cs, cf, chh, cu, T, a.table_m);
+                acc = cvalid && rs_decide_rule<GRID, ANYRULE>(a.rule, cs, cf, chh, cu, T, a.table_m);
                 m = ballot64(acc) & (~1ull << fl);
             }
         }
@@ -808,20 +837,25 @@ static hipError_t rs_fields(const SweepArgs &a, const RowSharedPlan &p, int grid
     }
 }
 
-template <typename JE, bool BITS, bool GRID>
+template <typename JE, bool BITS, bool GRID, bool ANYRULE>
 static hipError_t rs_chain_launch(const SweepArgs &a, const RsPlanArg<GRID> &p, int W, int k, int win, hipStream_t st) {
     switch (W) {
-        case 256: hipLaunchKernelGGL((rs_chain_kernel<JE, 4, BITS, GRID>), dim3(a.R), dim3(64), 0, st, a, p, k, win); break;
-        case 512: hipLaunchKernelGGL((rs_chain_kernel<JE, 8, BITS, GRID>), dim3(a.R), dim3(64), 0, st, a, p, k, win); break;
-        case 1024: hipLaunchKernelGGL((rs_chain_kernel<JE, 16, BITS, GRID>), dim3(a.R), dim3(64), 0, st, a, p, k, win); break;
+        case 256: hipLaunchKernelGGL((rs_chain_kernel<JE, 4, BITS, GRID, ANYRULE>), dim3(a.R), dim3(64), 0, st, a, p, k, win); break;
+        case 512: hipLaunchKernelGGL((rs_chain_kernel<JE, 8, BITS, GRID, ANYRULE>), dim3(a.R), dim3(64), 0, st, a, p, k, win); break;
+        case 1024: hipLaunchKernelGGL((rs_chain_kernel<JE, 16, BITS, GRID, ANYRULE>), dim3(a.R), dim3(64), 0, st, a, p, k, win); break;
         default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
 }
+// (Glauber / heat bath: the ANYRULE instantiations; the rule itself stays a run-time value in them)
 template <typename JE, bool BITS>
 static hipError_t rs_chain(const SweepArgs &a, const RowSharedPlan &p, int grid, int k, int win, hipStream_t st) {
-    if (grid) return rs_chain_launch<JE, BITS, true>(a, RowSharedGridPlan{p, grid - 1}, p.W, k, win, st);
-    return rs_chain_launch<JE, BITS, false>(a, p, p.W, k, win, st);
+    if (a.rule != SGA_RULE_METROPOLIS) {
+        if (grid) return rs_chain_launch<JE, BITS, true, true>(a, RowSharedGridPlan{p, grid - 1}, p.W, k, win, st);
+        return rs_chain_launch<JE, BITS, false, true>(a, p, p.W, k, win, st);
+    }
+    if (grid) return rs_chain_launch<JE, BITS, true, false>(a, RowSharedGridPlan{p, grid - 1}, p.W, k, win, st);
+    return rs_chain_launch<JE, BITS, false, false>(a, p, p.W, k, win, st);
 }
 
 int row_shared_planes(int j_abs_max) {
@@ -874,6 +908,9 @@ hipError_t launch_sweep_dense_rs(const SweepArgs &a, const RowSharedPlan &p, boo
     if (p.log_rg < 0 || p.n_groups != (a.R + (1 << p.log_rg) - 1) >> p.log_rg || (p.jp && !p.jabs) || !p.tot)
         return hipErrorInvalidValue;
     if (grid < 0 || grid > 31 || (j_is_i8 && grid > 1)) return hipErrorInvalidValue;  // (int8 rows: k = 0)
+    // the single-site rules; Glauber and heat bath decide in fp64 only (sga_sweep refuses them fp32 arithmetic)
+    if (a.rule != SGA_RULE_METROPOLIS && a.rule != SGA_RULE_GLAUBER && a.rule != SGA_RULE_HEAT_BATH) return hipErrorInvalidValue;
+    if (a.rule != SGA_RULE_METROPOLIS && a.arith != SGA_ARITH_F64) return hipErrorInvalidValue;
     const int nwin = (a.n + p.W - 1) / p.W;
     const dim3 pgrid(p.n_groups, nwin, (a.n + RS_PLAN_TILE - 1) / RS_PLAN_TILE);
     const size_t plds = sizeof(int) * (size_t)(a.n < RS_PLAN_TILE ? a.n : RS_PLAN_TILE);
@@ -901,8 +938,10 @@ hipError_t launch_sweep_dense_rs(const SweepArgs &a, const RowSharedPlan &p, boo
     }
     if (e == hipSuccess) {
         // (the words "fields from resident bit-planes" / "on-chip conversion" are read by tests and bench.py)
-        char gs[24] = "", ts[64] = "";
+        char gs[48] = "", ts[64] = "";
         if (grid) std::snprintf(gs, sizeof(gs), ", grid=2^-%d", grid - 1);
+        if (a.rule != SGA_RULE_METROPOLIS)  // (Metropolis strings stay as they were)
+            std::snprintf(gs + std::strlen(gs), sizeof(gs) - std::strlen(gs), ", rule=%s", a.rule == SGA_RULE_GLAUBER ? "glauber" : "heat-bath");
         if (p.jp && tiles.S > 0) std::snprintf(ts, sizeof(ts), " in tiles of %d sites%s", tiles.S, tiles.ones ? ", sign-only" : "");
         note_sweep_kernel("sweep_dense_rs<%s, planes=%d, W=%d%s> (row-shared windows: plan, fields from %s%s, chain)",
                           j_is_i8 ? "int8_t" : "float", p.planes, p.W, gs, p.jp ? "resident bit-planes" : "on-chip conversion", ts);

@@ -52,7 +52,8 @@ class GPUAnnealerConfig:
     row_shared_grid: bool = False         # engine option "row_shared_grid": the row-shared windows also serve dense J on a
     #                                       binary grid 2^-k under any h (quarter-valued QUBO encodings, integer J beside a
     #                                       real-valued h; same chain).  Acts with field_cache="off", where the autotuner picks
-    #                                       the form or option "row_shared" = 1 forces it
+    #                                       the form or option "row_shared" = 1 forces it, under the Metropolis, Glauber
+    #                                       and heat-bath rules (the autotuner's pick is the rule's it was timed under)
     row_shared_fields: int = 2            # engine option "row_shared_fields": the fields kernel of those windows over
     #                                       resident bit-planes -- 0 per proposed site, 1 per tile of sites wherever it can
     #                                       run, 2 where it was measured to win (same chain)

@@ -51,7 +51,8 @@ class ParallelTemperingConfig:
     fixed_point_fields: bool = False      # ... real-valued sparse and dense couplings too (option "clf_fixed_point")
     row_shared_grid: bool = False         # option "row_shared_grid": row-shared windows for dense J on a binary grid 2^-k
     #                                       under any h (same chain); acts with field_cache="off", where autotune picks the
-    #                                       form or option "row_shared" = 1 forces it
+    #                                       form or option "row_shared" = 1 forces it, under the Metropolis, Glauber and
+    #                                       heat-bath rules (the autotuner's pick is the rule's it was timed under)
     row_shared_fields: int = 2            # option "row_shared_fields": the fields kernel of those windows over resident
     #                                       bit-planes -- 0 per proposed site, 1 per tile of sites wherever it can run, 2 where
     #                                       it was measured to win (same chain)
