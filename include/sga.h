@@ -80,7 +80,7 @@ typedef struct sga_engine sga_engine;
 int sga_create(int device, sga_engine **out);
 void sga_destroy(sga_engine *e);
 const char *sga_last_error(void);
-int sga_version(void);  /* 2000: the row-shared windows (option "row_shared") serve SGA_RULE_GLAUBER and SGA_RULE_HEAT_BATH too ("rule=glauber" / "rule=heat-bath" in sga_describe and sga_get_last_kernel; the window sga_autotune picks holds for the rule it was timed under); 1900: options "row_shared_fields" and "row_shared_tile_sites" (row-shared fields in tiles of sites, sign-only rows); 1800: option "row_shared_grid", sga_route_query.rs_grid; 1700: sga_set_csr_shared (one set of CSR rows, many field vectors: every one-wave-per-replica CSR form for such batches), sga_route_query.shared_j on SGA_ROUTE_CSR queries; 1600: sga_set_dense_shared (one coupling matrix, many field vectors; row-shared windows, bit-planes and the matrix-core pass for such batches), sga_route_query.shared_j; 1500: sga_get_scan_summary, and sga_set_dense / sga_set_dense_batch / sga_set_csr / sga_set_csr64 / sga_set_csr_batch refuse a NaN or +-Inf in J or h (SGA_ERR_INVALID, "non-finite"); 1400: option "batch_fixed_point" (fixed-point cached local fields for many-model dense batches); 1300: options "ragged_field_cache" and "clf_fixed_point" together (fixed-point cached local fields for ragged CSR batches); 1200: sga_set_groups_csr (group couplings plus a stored sparse remainder); 1100: option "ragged_field_cache" (cached local fields for ragged CSR batches); 1000: sga_set_groups */
+int sga_version(void);  /* 2100: sga_set_sequential_windows / sga_get_sequential_windows (SGA_SITE_SEQUENTIAL sweeps in windows, the fields of every replica on the matrix cores; csrc/sweep_dense_seq.hip); 2000: the row-shared windows (option "row_shared") serve SGA_RULE_GLAUBER and SGA_RULE_HEAT_BATH too ("rule=glauber" / "rule=heat-bath" in sga_describe and sga_get_last_kernel; the window sga_autotune picks holds for the rule it was timed under); 1900: options "row_shared_fields" and "row_shared_tile_sites" (row-shared fields in tiles of sites, sign-only rows); 1800: option "row_shared_grid", sga_route_query.rs_grid; 1700: sga_set_csr_shared (one set of CSR rows, many field vectors: every one-wave-per-replica CSR form for such batches), sga_route_query.shared_j on SGA_ROUTE_CSR queries; 1600: sga_set_dense_shared (one coupling matrix, many field vectors; row-shared windows, bit-planes and the matrix-core pass for such batches), sga_route_query.shared_j; 1500: sga_get_scan_summary, and sga_set_dense / sga_set_dense_batch / sga_set_csr / sga_set_csr64 / sga_set_csr_batch refuse a NaN or +-Inf in J or h (SGA_ERR_INVALID, "non-finite"); 1400: option "batch_fixed_point" (fixed-point cached local fields for many-model dense batches); 1300: options "ragged_field_cache" and "clf_fixed_point" together (fixed-point cached local fields for ragged CSR batches); 1200: sga_set_groups_csr (group couplings plus a stored sparse remainder); 1100: option "ragged_field_cache" (cached local fields for ragged CSR batches); 1000: sga_set_groups */
 /* Run on an existing HIP stream (e.g. torch.cuda.current_stream().cuda_stream); NULL = the
  * engine's own stream (default). */
 int sga_set_stream(sga_engine *e, void *hip_stream);
@@ -523,6 +523,28 @@ int sga_set_csr_storage(sga_engine *e, int storage);
 #define SGA_FIELD_CACHE_ON 1
 #define SGA_FIELD_CACHE_AUTO 2
 int sga_set_field_cache(sga_engine *e, int mode);
+
+/* Sequential windows (version >= 2100; csrc/sweep_dense_seq.hip): SGA_SITE_SEQUENTIAL sweeps of many replicas with ONE
+ * read of each coupling row per sweep.
+ * W = 0 (default): off, nothing changes.  W = 256 | 512 | 1024: on, wherever the form applies.
+ * Any other value: SGA_ERR_INVALID.  Read at every sga_sweep; kept across sga_set_* calls, as sga_set_field_cache is.
+ * In typewriter order every replica proposes the same W sites inside a window of W consecutive updates: the
+ * window-start row sums of all replicas are one (W x n) . (n x R) product on the matrix cores (int8 cores for int8
+ * rows and for fp32 rows with |2^k J_ij| <= 127, else the fp32 cores), and one wave per replica then walks the window's
+ * chain, correcting the fields for the window's earlier accepts from the accepted sites' rows.  The chain, energies,
+ * counters and bests are the row-per-proposal kernel's, bit for bit.
+ * The form runs where all of these hold, otherwise that call runs today's kernel: site_mode == SGA_SITE_SEQUENTIAL
+ * (uniforms from Philox or replay_u), no accept_trace / dE_trace (energy_trace is served), Metropolis in either
+ * arithmetic or Glauber / heat bath (never Wolff), field cache OFF, J symmetric with a zero diagonal, option
+ * "force_general" = 0, one dense matrix (one model or sga_set_dense_shared; not a stacked batch, CSR, TSP or groups),
+ * R n < 2^31, and a problem class in which the product is exact: J and h integer valued with every partial sum below
+ * 2^24 (the accept table's class), or -- under option "row_shared_grid" = 1 -- J on a binary grid 2^-k with scaled sums
+ * below 2^24 and any finite h (integer J beside a half-integer or real h is k = 0).  Option "row_shared" does not gate
+ * it.  sga_describe shows " sweep=seq-windows(W=...)" while the setting is on and the problem qualifies,
+ * sga_get_last_kernel names sweep_dense_seq<...>; sga_explain_route keeps its random-site answer (a query carries the
+ * site mode no more than the rule).  The setting is not part of sga_export_state. */
+int sga_set_sequential_windows(sga_engine *e, int W);
+int sga_get_sequential_windows(sga_engine *e, int *W);
 /* Form-selection options of ONE engine -- the A/B switches of the measurements and what the parity tests use to
  * force a kernel form -- by name.  None changes a result: every form walks the same chain.  The
  * environment is read once, in sga_create, for the defaults (variable in brackets); afterwards only these calls

@@ -158,6 +158,79 @@ int row_shared_window(const sga_engine *e, bool lean) {
     return fw >= 1024 ? 1024 : fw >= 512 ? 512 : fw >= 256 ? 256 : (tuned > 0 ? tuned : 1024);
 }
 
+// Sequential windows (sweep_dense_seq.hip, sga_set_sequential_windows): the form as a SGA_SITE_SEQUENTIAL sweep without
+// per-update traces would run it, W = 0 where the row-per-proposal kernel runs.  One dense matrix (one model, or the
+// models of sga_set_dense_shared), symmetric with a zero diagonal, cache off, a single-site rule, and a problem class in
+// which the product is exact: the integer class of the look-ahead form (the accept table's), or -- option
+// "row_shared_grid" = 1 -- the set-time grid verdict (J on 2^-k, scaled sums below 2^24, any finite h; integer J beside
+// a half-integer or real h is k = 0).  Option "row_shared" does not gate it: that one governs the random-site windows.
+// The product: int8 rows on the int8 matrix cores; fp32 rows too where every |2^k J_ij| <= 127 (through a resident int8
+// copy, ensure_seq_j8) -- j_abs_max for integer J, 3 magnitude planes (|2^k J| <= 7) for the grid -- else the fp32 cores.
+// The mode returned for fp32 rows is the class's; the sweep moves mode 0 to mode 1 where the copy cannot be had.
+sga::SeqWindows sequential_windows(const sga_engine *e) {
+    sga::SeqWindows q{};
+    if (e->seq_w <= 0 || e->rule == SGA_RULE_WOLFF || e->field_cache != SGA_FIELD_CACHE_OFF) return q;
+    if (e->csr || e->implicit() || e->ragged || (e->n_models != 1 && !e->shared_j) || !e->consistent_dE) return q;
+    if (e->opt[OPT_FORCE_GENERAL] != 0 || !e->J_packed || e->n <= 0) return q;
+    int jmax;
+    if (e->table_m > 0 && !e->acc64) {
+        jmax = e->j_abs_max;
+    } else if (e->opt[OPT_ROW_SHARED_GRID] == 1 && e->rs_grid_planes > 0) {
+        q.grid = 1 + e->rs_grid_k;
+        jmax = e->rs_grid_planes <= 3 ? 7 : 255;
+    } else {
+        return q;
+    }
+    if (e->want_i8 && q.grid > 1) return q;  // (int8 rows are integers)
+    if ((long long)e->R * e->n >= (1ll << 31)) return q;
+    // the product's 16-byte loads walk whole steps of 32 columns: inside the (zero-padded) strides of both operands
+    const long long kpad = ((long long)e->n + 31) / 32 * 32;
+    if (e->ldj < kpad || (e->R > 0 && (e->sstride % 16 != 0 || e->sstride < kpad))) return q;
+    q.mode = (e->want_i8 || jmax <= 127) ? 0 : 1;
+    q.W = e->seq_w;
+    return q;
+}
+
+// fp32 rows that the int8 matrix cores can take: their resident int8 copy, made once per problem -- the product reads a
+// quarter of the bytes and converts nothing (measured against conversion in registers, DESIGN.md 7: 1.23 -> 0.65 ms of
+// product per sweep at n = 10^4, 1024 replicas).  Where the n^2 bytes cannot be had the fp32 matrix cores take the rows
+// (exact all the same).
+static void ensure_seq_j8(sga_engine *e, sga::SeqWindows &q, hipStream_t st) {
+    if (q.mode != 0 || e->want_i8) return;
+    const long long ld8 = sga::seq_i8_stride(e->n);
+    if (!e->seq_j8 && !e->seq_j8_refused) {
+        hipError_t he = hipMalloc(&e->seq_j8, (size_t)e->n * (size_t)ld8);
+        if (he == hipSuccess)
+            he = sga::launch_seq_build_i8(static_cast<const float *>(e->J_packed), e->ldj, e->n, q.grid ? q.grid - 1 : 0, e->seq_j8, ld8, st);
+        if (he != hipSuccess) {
+            (void)hipGetLastError();
+            dev_free(e->seq_j8);
+            e->seq_j8_refused = true;
+        }
+    }
+    if (!e->seq_j8) {
+        q.mode = 1;
+        return;
+    }
+    q.j8 = e->seq_j8;
+    q.ld8 = ld8;
+}
+
+// its scratch, base[R][W]: made by the form's first sweep, kept until the replicas go; false (and the row-per-proposal
+// kernel runs) if it cannot be had
+static bool ensure_seq_base(sga_engine *e, int W) {
+    if (e->seq_base && e->seq_base_w >= W) return true;
+    dev_free(e->seq_base);
+    e->seq_base_w = 0;
+    if (hipMalloc(&e->seq_base, sizeof(int) * (size_t)e->R * (size_t)W) != hipSuccess) {
+        (void)hipGetLastError();
+        e->seq_base = nullptr;
+        return false;
+    }
+    e->seq_base_w = W;
+    return true;
+}
+
 // The fields kernel of the row-shared windows over resident planes, by option "row_shared_fields": the tile size S and
 // whether the rows are sign-only, or S = 0 and the reason where the per-site kernel runs.  Option 2 takes the tiles only
 // in the configuration measured to win.  Known once the planes exist (rs_ones is found with them).
@@ -459,7 +532,7 @@ int ensure_packed(sga_engine *e) {
 extern "C" {
 
 const char *sga_last_error(void) { return g_last_error.c_str(); }
-int sga_version(void) { return 2000; }  // + row-shared windows under SGA_RULE_GLAUBER and SGA_RULE_HEAT_BATH (sweep_dense_rs.hip, ANYRULE; "rule=..." in sga_describe and sga_get_last_kernel), the autotuner's window kept per rule  // 1900: + options "row_shared_fields", "row_shared_tile_sites": the row-shared fields in tiles of sites, sign-only rows (sweep_dense_rs.hip, rs_fields_tiles_kernel)  // 1800: + option "row_shared_grid": row-shared windows for dense J on a binary grid under any h (sweep_dense_rs.hip, GRID), sga_route_query.rs_grid  // 1700: + sga_set_csr_shared (one set of CSR rows, many field vectors)  // 1600: + sga_set_dense_shared (one coupling matrix, many field vectors), sga_route_query.shared_j  // 1500: + sga_get_scan_summary; the dense and CSR setters refuse non-finite J / h  // 1400: + option "batch_fixed_point": fixed-point cached local fields for many-model dense batches (sweep_clf_fx.hip, MODELS)  // 1300: + options "ragged_field_cache" and "clf_fixed_point" together: fixed-point cached local fields for ragged CSR batches (sweep_clf_csr.hip)  // 1200: + sga_set_groups_csr (group couplings plus a stored sparse remainder, sweep_groups.hip)  // 1100: + option "ragged_field_cache" (cached local fields for ragged CSR batches, sweep_clf_csr.hip)  // 1000: + sga_set_groups (implicit cardinality-group couplings, sweep_groups.hip)  // 900: + cached local fields for many-model dense batches (sga_set_dense_batch)  // 800: + option "clf_fixed_point" over dense couplings (sweep_clf_fx.hip)  // 700: + option "clf_fixed_point" (cached fields of real-valued CSR couplings)  // 600: + sga_set_csr_batch / sga_get_batch_model (ragged CSR batches)  // round 5: + sga_explain_route / sga_get_route_query, sga_get_last_kernel, sga_get_autotune_table, ladder-local sga_exchange
+int sga_version(void) { return 2100; }  // + sga_set_sequential_windows / sga_get_sequential_windows: SGA_SITE_SEQUENTIAL sweeps in windows, the window-start fields of every replica on the matrix cores (sweep_dense_seq.hip; " sweep=seq-windows(W=...)" in sga_describe)  // 2000: + row-shared windows under SGA_RULE_GLAUBER and SGA_RULE_HEAT_BATH (sweep_dense_rs.hip, ANYRULE; "rule=..." in sga_describe and sga_get_last_kernel), the autotuner's window kept per rule  // 1900: + options "row_shared_fields", "row_shared_tile_sites": the row-shared fields in tiles of sites, sign-only rows (sweep_dense_rs.hip, rs_fields_tiles_kernel)  // 1800: + option "row_shared_grid": row-shared windows for dense J on a binary grid under any h (sweep_dense_rs.hip, GRID), sga_route_query.rs_grid  // 1700: + sga_set_csr_shared (one set of CSR rows, many field vectors)  // 1600: + sga_set_dense_shared (one coupling matrix, many field vectors), sga_route_query.shared_j  // 1500: + sga_get_scan_summary; the dense and CSR setters refuse non-finite J / h  // 1400: + option "batch_fixed_point": fixed-point cached local fields for many-model dense batches (sweep_clf_fx.hip, MODELS)  // 1300: + options "ragged_field_cache" and "clf_fixed_point" together: fixed-point cached local fields for ragged CSR batches (sweep_clf_csr.hip)  // 1200: + sga_set_groups_csr (group couplings plus a stored sparse remainder, sweep_groups.hip)  // 1100: + option "ragged_field_cache" (cached local fields for ragged CSR batches, sweep_clf_csr.hip)  // 1000: + sga_set_groups (implicit cardinality-group couplings, sweep_groups.hip)  // 900: + cached local fields for many-model dense batches (sga_set_dense_batch)  // 800: + option "clf_fixed_point" over dense couplings (sweep_clf_fx.hip)  // 700: + option "clf_fixed_point" (cached fields of real-valued CSR couplings)  // 600: + sga_set_csr_batch / sga_get_batch_model (ragged CSR batches)  // round 5: + sga_explain_route / sga_get_route_query, sga_get_last_kernel, sga_get_autotune_table, ladder-local sga_exchange
 
 int sga_create(int device, sga_engine **out) {
     if (!out) return fail(SGA_ERR_INVALID, "out is NULL");
@@ -617,6 +690,20 @@ int sga_set_field_cache(sga_engine *e, int mode) {
         e->fields_valid = false;
     }
     e->field_cache = mode;
+    return SGA_OK;
+}
+
+int sga_set_sequential_windows(sga_engine *e, int W) {
+    if (!e) return fail(SGA_ERR_INVALID, "engine is NULL");
+    if (W != 0 && W != 256 && W != 512 && W != 1024)
+        return fail(SGA_ERR_INVALID, "sequential windows: W must be 0 (off), 256, 512 or 1024");
+    e->seq_w = W;
+    return SGA_OK;
+}
+
+int sga_get_sequential_windows(sga_engine *e, int *W) {
+    if (!e || !W) return fail(SGA_ERR_INVALID, "engine or output is NULL");
+    *W = e->seq_w;
     return SGA_OK;
 }
 
@@ -846,6 +933,7 @@ struct SweepPlan {  // what holds for every launch of a call
     bool mixed = false;         // ... and the others beside them on the row kernels, second stream
     int rs_w = 0;               // row-shared window (0: not this form)
     sga::RowSharedTiles rs_tiles{};  // its fields kernel: tiles of S sites (S = 0: one workgroup per site)
+    sga::SeqWindows seq{};      // sequential windows (W = 0: not this form)
 };
 
 // The policy's look at the acceptance counters (sga_route.cpp, look): one read-back and synchronise when a look is due,
@@ -1097,6 +1185,13 @@ int plan_sweep(sga_engine *e, const SweepCall &c, SweepPlan &p) {
                 p.rs_tiles = sga::RowSharedTiles{};
             }
         }
+        // sequential windows (sweep_dense_seq.hip, sga_set_sequential_windows): one read of each coupling row per sweep
+        if (c.site_mode == SGA_SITE_SEQUENTIAL && !c.acc.ptr && !c.dE.ptr) {
+            p.seq = sequential_windows(e);
+            if (p.seq.W && !ensure_seq_base(e, p.seq.W)) p.seq.W = 0;
+            p.seq.base = e->seq_base;
+            if (p.seq.W) ensure_seq_j8(e, p.seq, e->stream);
+        }
     }
     return SGA_OK;
 }
@@ -1157,6 +1252,7 @@ hipError_t launch_sweep(sga_engine *e, const SweepPlan &p, sga::SweepArgs a, hip
     if (e->groups) return sga::launch_sweep_groups(a, e->group_args, e->waves, st);
     if (e->tsp) return sga::launch_sweep_tsp(a, e->tsp_args, e->tsp_waves, e->tsp_passes, st);
     if (e->csr) return sga::launch_sweep_csr(a, e->waves, st);
+    if (p.seq.W) return sga::launch_sweep_dense_seq(a, p.seq, e->want_i8, e->cus, st);
     if (p.rs_w) return sga::launch_sweep_dense_rs(a, e->rs, e->want_i8, st, e->rs_grid, p.rs_tiles);
     return launch_dense_rows(e, a, st);
 }

@@ -134,6 +134,9 @@ struct sga_engine {
     // and opt[] for the problem it measured; free_problem() -- every setter -- goes back to these.
     int caller_tune_waves = 0;
     long long caller_csr_ups = -1;
+    // sga_set_sequential_windows: W of the sequential windows (sweep_dense_seq.hip; 0: off).  The caller's choice for
+    // every later problem, read at every sga_sweep; not part of sga_export_state.
+    int seq_w = 0;
     hipStream_t own_stream = nullptr;
     hipStream_t stream = nullptr;
 
@@ -255,6 +258,11 @@ struct sga_engine {
     int rs_grid = 0;  // what rs was prepared for: 0 the integer form, else 1 + k (launch_sweep_dense_rs)
     unsigned long long *rs_jp = nullptr;
     int *rs_jabs = nullptr;
+    // sequential windows (sweep_dense_seq.hip): the resident int8 copy of fp32 rows with |2^k J| <= 127, [n][seq_i8_stride(n)],
+    // made by the form's first sweep of a problem (SeqWindows::j8); refused: its allocation failed, the product runs on
+    // the fp32 matrix cores
+    int8_t *seq_j8 = nullptr;
+    bool seq_j8_refused = false;
     // rs_ones: found with the planes -- every off-diagonal |J_ij| (grid form: |2^k J_ij|) is 1, the fields kernel reads
     // sign planes only; rs_tiles_refused: the runtime refused the tile kernel's LDS for this problem (per-site kernel)
     bool rs_ones = false, rs_tiles_refused = false;
@@ -285,6 +293,8 @@ struct sga_engine {
     unsigned long long *n_acc = nullptr;
     long long attempted = 0;  // per replica
     uint32_t sweeps_done = 0, rounds = 0;
+    int *seq_base = nullptr;  // [R][seq_base_w] scratch of the sequential windows, made by their first sweep
+    int seq_base_w = 0;
 
     // ladder
     int n_ladders = 0;
@@ -360,6 +370,8 @@ struct sga_engine {
         free_row_shared();
         dev_free(rs_jp);
         dev_free(rs_jabs);
+        dev_free(seq_j8);
+        seq_j8_refused = false;
         rs_ones = false;
         rs_tiles_refused = false;
         rs_tuned_w = 0;
@@ -427,6 +439,8 @@ struct sga_engine {
         routing.reset();
         dev_free(d_rep_lists);
         free_row_shared();
+        dev_free(seq_base);
+        seq_base_w = 0;
         rs_tuned_w = 0;
         rs_tuned_rule = SGA_RULE_METROPOLIS;
         R = Rg = 0;
@@ -467,6 +481,9 @@ int row_shared_window(const sga_engine *e, bool lean);
 int row_shared_form_planes(const sga_engine *e, int *grid);
 // the tiles of its fields kernel (option "row_shared_fields"); S = 0: the per-site kernel, *why the reason
 sga::RowSharedTiles row_shared_tiles(const sga_engine *e, const char **why);
+// the sequential windows (sga_set_sequential_windows) as a sequential, untraced sweep of this engine would run them:
+// W = 0 where the row-per-proposal kernel runs (base is left null: the scratch is the sweep's)
+sga::SeqWindows sequential_windows(const sga_engine *e);
 // ---- sga_problem.cpp
 bool csr_rows_medium(const sga_engine *e);
 int csr_updates_per_step(const sga_engine *e);

@@ -533,6 +533,27 @@ hipError_t launch_rs_build_planes(const void *J, bool j_is_i8, long long ldj, in
 hipError_t launch_sweep_dense_rs(const SweepArgs &a, const RowSharedPlan &p, bool j_is_i8, hipStream_t st, int grid = 0,
                                  RowSharedTiles tiles = RowSharedTiles{});
 
+// Sequential windows (sweep_dense_seq.hip, sga_set_sequential_windows): SGA_SITE_SEQUENTIAL sweeps in windows of W
+// consecutive sites -- per window one product on the matrix cores (the window-start row sums of every replica), then
+// one chain wave per replica.  One dense symmetric matrix with a zero diagonal whose row sums are exact (the integer
+// class, or J on the grid 2^-k).
+struct SeqWindows {
+    int *base = nullptr;  // [R][W] 2^k sum_j J[t0 + w][j] s_r[j] against the window-start spins (owned by the engine)
+    int W = 0;            // 256 | 512 | 1024 (0: not this form)
+    int grid = 0;         // 0: the integer form; else 1 + k, J on the grid 2^-k
+    int mode = 0;         // the product: 0 on the int8 matrix cores (int8 rows, or the resident int8 copy j8 of fp32 rows
+                          // with every |2^k J| <= 127) | 1 fp32 rows on the fp32 matrix cores
+    const int8_t *j8 = nullptr;  // fp32 rows, mode 0: [n][ld8] 2^k J as int8, zero padded (made once per problem, owned by the engine)
+    long long ld8 = 0;
+};
+inline long long seq_i8_stride(int n) { return ((long long)n + 127) / 128 * 128; }
+// the resident int8 copy of fp32 rows with every |2^k J_ij| <= 127: out[i][j] = (int8)(2^k J_ij), pads zero
+hipError_t launch_seq_build_i8(const float *J, long long ldj, int n, int grid_k, int8_t *out, long long ld8, hipStream_t st);
+// a.n_sweeps sequential sweeps (a.site_mode == SGA_SITE_SEQUENTIAL, Philox or replayed uniforms, no per-update traces,
+// all replicas): per sweep and window product + chain, then best tracking.  Any single-site rule and arithmetic: the
+// decision is metropolis_accept's.  cus: compute units (the K split of the product).
+hipError_t launch_sweep_dense_seq(const SweepArgs &a, const SeqWindows &sq, bool j_is_i8, int cus, hipStream_t st);
+
 // operator-form PT exchange (cuda_kernels.py:415-443): decide sequentially, then permute rows
 hipError_t launch_op_exchange(float *spins, float *tmp_rows, float *energies, const float *temps,
                               const float *u, int32_t *src_of_pos, int *n_accepted,

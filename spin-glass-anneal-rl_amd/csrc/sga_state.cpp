@@ -437,6 +437,8 @@ int sga_describe(sga_engine *e, char *buf, int buflen) {
             }
         }
     }
+    if (const sga::SeqWindows sq = sequential_windows(e); sq.W > 0)  // sga_set_sequential_windows: SGA_SITE_SEQUENTIAL sweeps
+        std::snprintf(tmp + std::strlen(tmp), sizeof(tmp) - std::strlen(tmp), " sweep=seq-windows(W=%d)", sq.W);
     if (e->csr && !e->ragged && csr_updates_per_step(e) >= 4 && e->waves <= 1 && (e->big_form == 0 || e->big_form == 2) && e->rowptr)
         std::snprintf(tmp + std::strlen(tmp), sizeof(tmp) - std::strlen(tmp), " updates_per_step=%d", csr_updates_per_step(e));
     if (e->csr && e->from_dense) std::strncat(tmp, " source=dense-matrix(sparse)", sizeof(tmp) - std::strlen(tmp) - 1);

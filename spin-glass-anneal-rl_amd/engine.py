@@ -207,6 +207,18 @@ class AnnealEngine:
         code = {"off": 0, False: 0, "on": 1, True: 1, "auto": 2}[mode]
         N.check(self._lib.sga_set_field_cache(self._h, code), "sga_set_field_cache")
 
+    def set_sequential_windows(self, W: int = 1024):
+        """Sequential windows (sga_set_sequential_windows): SITE_SEQUENTIAL sweeps of many replicas read each coupling
+        row once per sweep -- W = 256 | 512 | 1024 consecutive sites per window, 0 = off (default).  Acts with
+        set_field_cache("off") on one dense symmetric matrix whose row sums are exact (integer J and h, or option
+        "row_shared_grid" = 1 and J on a grid 2^-k); every other call runs the kernel it had.  Identical chains."""
+        N.check(self._lib.sga_set_sequential_windows(self._h, int(W)), "sga_set_sequential_windows")
+
+    def sequential_windows(self) -> int:
+        w = C.c_int(0)
+        N.check(self._lib.sga_get_sequential_windows(self._h, C.byref(w)), "sga_get_sequential_windows")
+        return int(w.value)
+
     def autotune(self) -> float:
         """Time every feasible waves-per-replica on the current replicas and keep the fastest
         (dense problems; results are unaffected).  Returns the best kernel ms per sweep."""

@@ -56,8 +56,17 @@ class ParallelTemperingConfig:
     row_shared_fields: int = 2            # option "row_shared_fields": the fields kernel of those windows over resident
     #                                       bit-planes -- 0 per proposed site, 1 per tile of sites wherever it can run, 2 where
     #                                       it was measured to win (same chain)
+    site_order: str = "random"            # "random" | "sequential": typewriter sweeps, site t at update t (SITE_SEQUENTIAL)
+    sequential_window: int = 1024         # sequential order: W of the sequential windows (set_sequential_windows; 0 = off) --
+    #                                       one read of each coupling row per sweep for all replicas (same chain).  The form
+    #                                       acts with field_cache="off"; under "auto" / "on" the cached-field kernels serve
+    #                                       sequential sweeps as before
     device_index: Optional[int] = None
     autotune: Optional[bool] = None       # measured launch geometry (None: for long runs only)
+
+    def __post_init__(self):
+        if self.site_order not in ("random", "sequential"):
+            raise ConfigurationError("site_order must be 'random' or 'sequential'")
 
 
 class ParallelTempering:
@@ -87,6 +96,7 @@ class ParallelTempering:
         if cfg.exchange_method not in ("nearest_neighbor", "all_pairs"):
             raise ValueError(f"Unknown exchange method: {cfg.exchange_method}")  # reference :212
         all_pairs = cfg.exchange_method == "all_pairs"
+        site_mode = N.SITE_RANDOM if cfg.site_order == "random" else N.SITE_SEQUENTIAL  # (the _replay hook: SITE_REPLAY)
         # all_pairs: the gate `np.random.rand() < 0.1` of the reference (:222-232) only selects which
         # pairs are attempted; it is drawn on the host (seeded), the attempts run on the engine
         gate_rng = np.random.RandomState(fresh_seed(cfg.random_seed) & 0x7FFFFFFF)
@@ -105,6 +115,8 @@ class ParallelTempering:
                 eng.set_option("row_shared_grid", 1)  # (read at every sweep; acts with field_cache="off")
             if cfg.row_shared_fields != 2:
                 eng.set_option("row_shared_fields", cfg.row_shared_fields)  # (read at every sweep)
+            if cfg.site_order == "sequential":
+                eng.set_sequential_windows(cfg.sequential_window)  # (read at every sweep; acts with field_cache="off")
             model.load_into(eng, storage=cfg.coupling_storage)
             eng.set_update_rule(rule)
             eng.init_replicas(R, seed=fresh_seed(cfg.random_seed),
@@ -122,7 +134,7 @@ class ParallelTempering:
                     stop += 1
                 count = stop - sweep + 1
                 if _replay is None:
-                    eng.sweep(count)
+                    eng.sweep(count, site_mode=site_mode)
                 else:
                     inv = np.argsort(slot_to_rep)
                     site = _replay["site"][sweep:stop + 1][:, inv].transpose(1, 0, 2).reshape(R, -1)

@@ -17,6 +17,7 @@ from typing import Optional, Sequence, Union
 import numpy as np
 import torch
 
+from . import _native as N
 from .engine import AnnealEngine
 from .exceptions import ConfigurationError
 from .gpu_annealer import fresh_seed
@@ -51,12 +52,20 @@ class SpinGlassScheduler:
                beta_max: float = 10.0, exchange_interval: int = 10, n_ladders: int = 1,
                coupling_storage: str = "auto", record_interval: int = 10,
                autotune: Optional[bool] = None, field_cache: str = "auto",
-               fixed_point_fields: bool = False) -> AnnealingResult:
+               fixed_point_fields: bool = False, site_order: str = "random",
+               sequential_window: int = 1024) -> AnnealingResult:
         """field_cache: "auto" keeps every replica's local fields resident where the problem allows it
         (dense integer-valued symmetric couplings) so that a coupling row is read only when a proposal is
         accepted -- the chain, and with it the result, is the one "off" (a row per proposal) gives.
         fixed_point_fields: the cache also serves real-valued sparse and dense couplings, as exact fixed-point fields
-        (engine option "clf_fixed_point"); the same chain again."""
+        (engine option "clf_fixed_point"); the same chain again.
+        site_order: "random" (default) | "sequential" -- typewriter sweeps, site t at update t (the reference's GPU path).
+        sequential_window: their sequential windows (AnnealEngine.set_sequential_windows; 0 = off): one read of each
+        coupling row per sweep for all replicas.  The form acts with field_cache="off"; under "auto" / "on" the
+        cached-field kernels serve sequential sweeps as before.  The same chain either way."""
+        if site_order not in ("random", "sequential"):
+            raise ConfigurationError("site_order must be 'random' or 'sequential'")
+        site_mode = N.SITE_RANDOM if site_order == "random" else N.SITE_SEQUENTIAL
         if n_replicas < 1 or n_sweeps < 1 or n_replicas % n_ladders:
             raise ConfigurationError("bad replica / sweep / ladder counts")
         t0 = time.time()
@@ -74,6 +83,8 @@ class SpinGlassScheduler:
             eng.set_field_cache(field_cache)  # (before the couplings: "on" keeps a sparse matrix dense)
             if fixed_point_fields:
                 eng.set_option("clf_fixed_point", 1)  # (read when the couplings are set)
+            if site_order == "sequential":
+                eng.set_sequential_windows(sequential_window)  # (read at every sweep; acts with field_cache="off")
             ising_model.load_into(eng, storage=coupling_storage)
             eng.init_replicas(n_replicas, seed=fresh_seed(self.random_seed))
             eng.set_ladder(temps, n_ladders)
@@ -81,7 +92,7 @@ class SpinGlassScheduler:
             done = 0
             while done < n_sweeps:
                 step = min(exchange_interval, n_sweeps - done)
-                eng.sweep(step)
+                eng.sweep(step, site_mode=site_mode)
                 done += step
                 if L > 1 and done < n_sweeps:
                     eng.exchange(count=False)  # enqueue only: no host round trip per round
