@@ -1,5 +1,6 @@
 """Instances that sit exactly at the limits of the exact-integer sweep forms' number ranges, and a group-sum reference
-that never materialises J (test infrastructure of tests/test_range_edges_host.py and tests/test_range_edges_gpu.py).
+that never materialises J (test infrastructure of tests/test_range_edges_host.py and tests/test_range_edges_gpu.py; the
+window section at the end: of tests/test_window_range_edges_host.py and tests/test_window_range_edges_gpu.py).
 
 Saturating instances: a gauge xi in {+-1}^n, J_ij = a_ij xi_i xi_j with integer a_ij = a_ji >= 0 and a zero diagonal,
 h_i = b_i xi_i with b_i >= 0.  In state s = xi every s_i F_i equals its row's bound sum_j a_ij + b_i; row 0's bound is
@@ -224,20 +225,25 @@ def temperatures(R, unit):
     return np.asarray([[0.0, unit / 8.0, unit / 2.0, 2.0 * unit, INF][r % 5] for r in range(R)])
 
 
-def proposals(J, h, s0, temps, n_sweeps, seed):
+def proposals(J, h, s0, temps, n_sweeps, seed, replay_u=None):
     """The oracle's traced run from s0 plus the dE of EVERY proposal (the oracle traces 0 for a refused one): the chain
     is followed along the oracle's accept trace with the exact fields F = J s + h (integers and halves: exact in fp64).
-    Returns (oracle result, proposed dE [R, n_sweeps * n], final spins)."""
+    `replay_u` [R, n_sweeps * n]: the sequential order on these recorded uniforms (update t proposes site t) instead of
+    the Philox stream's random sites.  Returns (oracle result, proposed dE [R, n_sweeps * n], final spins)."""
     n, R = J.shape[0], s0.shape[0]
     s = s0.copy()
-    ref = oracle.sweeps(oracle.Problem(J=J, h=h), s, temps, n_sweeps, seed=seed, trace=True)
+    if replay_u is None:
+        ref = oracle.sweeps(oracle.Problem(J=J, h=h), s, temps, n_sweeps, seed=seed, trace=True)
+    else:
+        ref = oracle.sweeps(oracle.Problem(J=J, h=h), s, temps, n_sweeps, site_mode=oracle.SITE_SEQUENTIAL, replay_u=replay_u,
+                            seed=seed, trace=True)
     J64, out = J.astype(np.float64), np.zeros((R, n_sweeps * n))
     for r in range(R):
         v = s0[r].astype(np.float64)
         F = J64 @ v + h
         for k in range(n_sweeps):
             for t in range(n):
-                i = oracle.stream_site(seed, r, k, t, n)
+                i = oracle.stream_site(seed, r, k, t, n) if replay_u is None else t
                 out[r, k * n + t] = 2.0 * v[i] * F[i]
                 if ref["accept_trace"][r, k * n + t]:
                     assert out[r, k * n + t] == ref["dE_trace"][r, k * n + t]
@@ -509,5 +515,141 @@ def flat_reference(J, h, s0, temps, n_sweeps, seed, trace=False):
     prob = oracle.Problem(J=J, h=h)
     s = s0.copy()
     out = oracle.sweeps(prob, s, temps, n_sweeps, seed=seed, trace=trace, n_threads=8)
+    out["spins"], out["scratch"] = s, oracle.energy(prob, s)
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the window forms (tests/test_window_range_edges_{host,gpu}.py): sequential windows (csrc/sweep_dense_seq.hip) and
+# row-shared windows on a binary grid (sga_classify::row_shared_grid, csrc/sweep_dense_rs.hip)
+# ---------------------------------------------------------------------------------------------------------------------
+def product_saturating_dense(L, n, reverse=False):
+    """Integer J in the gauge, h = 0, sum_j |J_0j| == L exactly (the deficit of the construction goes on a[0, n - 1], as
+    in fixed_point_dense): at s = +-xi the window-start product of row 0 is +-L itself and every partial sum along the
+    row rises monotonically to it.  `reverse`: J[::-1, ::-1] with xi reversed -- the limit row is site n - 1, the last
+    update of the last window, whose field has taken the corrections of every accept before it.  Returns (J, h, xi)."""
+    xi = gauge(n)
+    a = _couplings(row_bounds(L, n))
+    a[0, n - 1] += L - a[0].sum()
+    a[n - 1, 0] = a[0, n - 1]
+    rs = a.sum(1)
+    assert rs[0] == L and (rs[1:] < L).all() and a.max() < (1 << 24) and (a + np.eye(n, dtype=np.int64) > 0).all()
+    J = (a * np.outer(xi, xi)).astype(np.float32)
+    assert np.array_equal(J.astype(np.float64), a * np.outer(xi, xi))
+    if reverse:
+        J, xi = np.ascontiguousarray(J[::-1, ::-1]), xi[::-1]
+    return J, np.zeros(n, np.float32), np.ascontiguousarray(xi).astype(np.int8)
+
+
+def grid_flat(amp, k, M, n=300):
+    """Couplings on the grid 2^-k under a field that carries the bound: J_ij = a_ij 2^-k xi_i xi_j with a_ij = amp off
+    the diagonal, h_i = xi_i (row_bounds(M, n)_i - sum_j a_ij) 2^-k, so that s_i F_i = row_bounds_i 2^-k at s = xi and
+    row 0 has 2^k (sum_j |J_0j| + |h_0|) == M exactly.  The set-time scan takes k from the lowest set bit of any J: where
+    amp is even ONE coupling (sites 1, 2) is amp - 1, or the scan would find the coarser grid of amp's trailing zeros and
+    a scaled maximum below amp (the twins are the code's: its k, its 2^k max |J|).  Returns (J, h, xi)."""
+    xi = gauge(n)
+    a = np.full((n, n), amp, np.int64)
+    np.fill_diagonal(a, 0)
+    if amp % 2 == 0:
+        a[1, 2] = a[2, 1] = amp - 1
+    t = row_bounds(M, n)
+    b = t - a.sum(1)  # (negative where the couplings alone exceed the row's bound: the gauge property holds all the same)
+    unit = 2.0 ** -k
+    J = (a * np.outer(xi, xi) * unit).astype(np.float32)
+    h = (b * xi * unit).astype(np.float32)
+    assert np.array_equal(J.astype(np.float64) * 2.0 ** k, a * np.outer(xi, xi))  # the intended integers, exactly
+    assert np.array_equal(h.astype(np.float64) * 2.0 ** k, b * xi)
+    assert (a % 2).any() and a.max() == amp
+    rows = (np.abs(J).astype(np.float64).sum(1) + np.abs(h)) * 2.0 ** k
+    assert rows[0] == M and (rows[1:] < M).all() and b[0] > 0
+    return J, h, xi.astype(np.int8)
+
+
+def grid_verdict(J, h):
+    """sga_classify::row_shared_grid as written (a host mirror of its conditions on these instances -- symmetric, zero
+    diagonal, no canonical-order class; tests/test_window_range_edges_host.py holds it against the compiled classifier):
+    (k, planes), planes = 0 where the verdict refuses."""
+    from scan_reference import bit_span
+    m = float(np.float32((np.abs(J).astype(np.float64).sum(1) + np.abs(h)).max()))
+    integer = bool((J == np.rint(J)).all() and (h == np.rint(h)).all())
+    if integer and 1.0 <= m < 16777216.0:
+        return 0, 0  # the integer form's
+    k = max(0, -bit_span(J)[1])
+    scaled = float(np.abs(J).max()) * 2.0 ** k
+    if k > 30 or scaled > 255.0 or not np.ldexp(m, k) * (1.0 + 2.0 ** -20) < 16777216.0:
+        return 0, 0
+    return k, 1 if scaled <= 1.0 else 3 if scaled <= 7.0 else 8
+
+
+P24_IN, P24_OUT = (1 << 24) - 1, 1 << 24          # the integer class: m < 2^24 (acc f32, table_m > 0)
+GB_IN, GB_OUT = (1 << 24) - 16, (1 << 24) - 15    # fx_bound: (2^24 - 16)(1 + 2^-20) = 2^24 - 2^-16 < 2^24 <= the next one
+# name -> (L, n, reverse): product_saturating_dense
+PRODUCT = {
+    "p24_in_n67": (P24_IN, 67, False), "p24_out_n67": (P24_OUT, 67, False),
+    "p24_in_n579": (P24_IN, 579, False), "p24_out_n579": (P24_OUT, 579, False),
+    "p24_in_n579_reversed": (P24_IN, 579, True),
+}
+# name -> (amp, k, M, planes the verdict gives (0: refused), the sequential product's matrix cores): grid_flat, n = 300
+GRID = {
+    "bound_in": (7, 3, GB_IN, 3, "i8"), "bound_out": (7, 3, GB_OUT, 0, None),
+    "amp1": (1, 3, 1 << 20, 1, "i8"), "amp2": (2, 3, 1 << 20, 3, "i8"),
+    "amp7": (7, 3, 1 << 20, 3, "i8"), "amp8": (8, 3, 1 << 20, 8, "f32"),
+    "amp255": (255, 3, 1 << 20, 8, "f32"), "amp256": (256, 3, 1 << 20, 0, None),
+    "k30_amp7": (7, 30, GB_IN, 3, "i8"), "k31_amp7": (7, 31, GB_IN, 0, None),
+    "k30_amp255": (255, 30, GB_IN, 8, "f32"), "k31_amp255": (255, 31, GB_IN, 0, None),
+}
+FLAT = {"flat127": None, "flat127_spike128": 128}   # flat_dense(127, 131, spike): the int8 copy's |m| <= 127
+WINDOW_SEQ = list(PRODUCT) + ["i24_in", "i24_out"] + list(FLAT) + list(GRID)
+WINDOW_RANDOM = list(GRID)
+# Seeds at which every instance meets the input conditions of tests/test_window_range_edges_host.py.  Sequential order:
+# the seed of the random start spins and of the recorded uniforms; random sites: the Philox seed too -- at 218 replica 2
+# proposes site 0 in its first update, before anything has moved that field.
+WINDOW_SEED_SEQ, WINDOW_SEED_RANDOM = 44, 218
+
+
+def recorded_u(R, n_sweeps, n, seed):
+    """One array of uniforms for the engine and the oracle alike (sequential order: update t of sweep k is site t)."""
+    return np.random.RandomState(seed).rand(R, n_sweeps * n).astype(np.float32)
+
+
+@functools.lru_cache(maxsize=None)
+def window_case(name, order="seq"):
+    """The named instance with its start spins, temperatures and, in sequential order, its recorded uniforms "u"."""
+    limit_row = 0
+    if name in PRODUCT:
+        L, n, reverse = PRODUCT[name]
+        J, h, xi = product_saturating_dense(L, n, reverse)
+        scale, limit_row = 1, n - 1 if reverse else 0
+    elif name in DENSE:
+        L, scale, jmax, n = DENSE[name]
+        J, h, xi = saturating_dense(L, scale, jmax, n)
+    elif name in FLAT:
+        J, h, xi = flat_dense(127, 131, FLAT[name])
+        L, scale = int((np.abs(J).astype(np.float64).sum(1) + np.abs(h)).max()), 1
+    else:
+        amp, k, M = GRID[name][:3]
+        J, h, xi = grid_flat(amp, k, M)
+        L, scale = M, 2.0 ** k
+    seed = WINDOW_SEED_SEQ if order == "seq" else WINDOW_SEED_RANDOM
+    s0 = start_spins(xi[::-1] if limit_row else xi, R_MAIN, seed)
+    if limit_row:  # the mirror image of the forward instance's start: replica 2 has the limit row flipped
+        s0 = np.ascontiguousarray(s0[:, ::-1])
+    c = dict(J=J, h=h, xi=xi, L=L, scale=scale, seed=seed, s0=s0, temps=temperatures(R_MAIN, L / scale), sweeps=SWEEPS,
+             limit_row=limit_row, order=order)
+    if order == "seq":
+        c["u"] = recorded_u(R_MAIN, SWEEPS, J.shape[0], seed)
+    return c
+
+
+@functools.lru_cache(maxsize=None)
+def window_reference(name, order="seq", rule=0, arith=None):
+    """oracle.sweeps of the named instance in the given order; 'spins' the final state, 'scratch' its from-scratch
+    energies."""
+    c = window_case(name, order)
+    prob = oracle.Problem(J=c["J"], h=c["h"])
+    s = c["s0"].copy()
+    kw = dict(site_mode=oracle.SITE_SEQUENTIAL, replay_u=c["u"]) if order == "seq" else {}
+    out = oracle.sweeps(prob, s, c["temps"], c["sweeps"], seed=c["seed"], rule=rule,
+                        arith=oracle.ARITH_F64 if arith is None else arith, n_threads=5, **kw)
     out["spins"], out["scratch"] = s, oracle.energy(prob, s)
     return out
