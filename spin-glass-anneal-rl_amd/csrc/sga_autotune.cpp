@@ -146,7 +146,7 @@ int sga_autotune(sga_engine *e, double *best_ms_per_sweep) {
     double *en = nullptr, *ben = nullptr;
     unsigned long long *acc = nullptr;
     auto release = [&]() {
-        e->rs_suspend = false;
+        e->win.suspend = false;
         dev_free(spins_c);
         dev_free(best_c);
         dev_free(en);
@@ -182,9 +182,9 @@ int sga_autotune(sga_engine *e, double *best_ms_per_sweep) {
     e->tune_table.clear();
     const int user_cache = e->field_cache;  // the geometry belongs to the row-per-proposal kernels
     e->field_cache = SGA_FIELD_CACHE_OFF;
-    e->rs_suspend = true;  // (the geometry trials time the row-per-proposal kernel, whatever option "row_shared" says)
-    e->rs_tuned_w = 0;
-    e->rs_tuned_rule = SGA_RULE_METROPOLIS;
+    e->win.suspend = true;  // (the geometry trials time the row-per-proposal kernel, whatever option "row_shared" says)
+    e->win.tuned_w = 0;
+    e->win.tuned_rule = SGA_RULE_METROPOLIS;
 
     // lay the replicas out for `waves` (0 = heuristic) and put the saved state back
     auto layout = [&](int waves) -> int {
@@ -277,13 +277,13 @@ int sga_autotune(sga_engine *e, double *best_ms_per_sweep) {
     // figure.  Unlike a geometry's, the time of this form depends on the acceptance -- every accept of a window costs
     // corrections in every later block, the more the longer the window -- so each W is timed after RS_TRIAL_BURN_IN
     // sweeps at that W from the saved state (layout() puts the state back before each trial and after the last).
-    e->rs_suspend = false;
+    e->win.suspend = false;
     if (rc == SGA_OK && best_w >= 0 && e->opt[OPT_ROW_SHARED] == 2) {
         double best_rs = 1e300;
         int pick = 0;
         for (int W : {256, 512, 1024}) {
-            e->rs_tuned_w = W;
-            e->rs_tuned_rule = e->rule;  // (timed() sweeps under the engine's rule: the pick is that rule's)
+            e->win.tuned_w = W;
+            e->win.tuned_rule = e->rule;  // (timed() sweeps under the engine's rule: the pick is that rule's)
             if (row_shared_window(e, true) != W) break;  // (the problem does not admit the form)
             rc = layout(best_w);
             if (rc != SGA_OK) break;
@@ -301,9 +301,9 @@ int sga_autotune(sga_engine *e, double *best_ms_per_sweep) {
             e->tune_table += item;
             if (t / k < best_rs) best_rs = t / k, pick = W;
         }
-        e->rs_tuned_w = (rc == SGA_OK && pick > 0 && best_rs < best * 0.99) ? pick : 0;
-        if (!e->rs_tuned_w) {
-            e->rs_tuned_rule = SGA_RULE_METROPOLIS;
+        e->win.tuned_w = (rc == SGA_OK && pick > 0 && best_rs < best * 0.99) ? pick : 0;
+        if (!e->win.tuned_w) {
+            e->win.tuned_rule = SGA_RULE_METROPOLIS;
             e->free_row_shared();
         }
     }

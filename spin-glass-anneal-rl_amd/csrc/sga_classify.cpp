@@ -263,7 +263,7 @@ FxVerdict dense_fixed_point(const DenseClass &c, int n_models, const std::functi
 // |D| <= 2^k max_i sum_j |J_ij| < 2^24 (row_abs_max, which includes |h_i|, bounds that maximum from above; fx_bound
 // allows for its fp32 rounding), so every partial sum is exact in fp32 in any order and fp32(2^-k D) is the row
 // kernels' dot.  h stays outside the sums: any finite fp32 value.  The planes follow sga::row_shared_planes
-// (sweep_dense_rs.hip) on the scaled maximum -- 1 | 3 | 8 for up to 1 | 7 | 255 -- written out here: this file calls no
+// (sga_kernels.h) on the scaled maximum -- 1 | 3 | 8 for up to 1 | 7 | 255 -- written out here: this file calls no
 // kernel header.
 RsGridVerdict row_shared_grid(const DenseClass &c) {
     RsGridVerdict v;

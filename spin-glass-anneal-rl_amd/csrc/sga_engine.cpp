@@ -2,7 +2,7 @@
 // (packed couplings, replica spins / energies / bests, ladder state), picks the launch
 // geometry, and drives the HIP kernels.  No torch, no exceptions across the ABI.
 // (problem set-up: sga_problem.cpp; autotune: sga_autotune.cpp; state access / describe: sga_state.cpp; form selection:
-// sga_route.cpp; shared internals: sga_engine_impl.h)
+// sga_route.cpp; the window forms' admission, state and scratch: sga_windows.cpp; shared internals: sga_engine_impl.h)
 #include "sga_engine_impl.h"
 
 #include <cmath>
@@ -50,7 +50,7 @@ sga_route_query route_query_of(const sga_engine *e) {
     q.group_max = e->groups ? e->g_max_size : 0;
     q.rest_nnz = e->groups ? e->group_args.rest.nnz : 0;
     q.rest_max_row = e->groups ? e->group_args.rest.max_row : 0;
-    q.rs_grid = (!e->csr && !e->implicit() && e->rs_grid_planes > 0) ? 1 + e->rs_grid_k : 0;
+    q.rs_grid = (!e->csr && !e->implicit() && e->win.grid_planes > 0) ? 1 + e->win.grid_k : 0;
     q.sstride = e->sstride;
     q.ldj = e->ldj;
     for (int i = 0; i < OPT_COUNT; ++i) q.opt[i] = e->opt[i];
@@ -121,192 +121,6 @@ int fields_pass(sga_engine *e, int r0, int count, double *energy, void *fields) 
         HIPCHK(sga::launch_fields_finish(f, mode == 0, e->stream));
     }
     return SGA_OK;
-}
-
-// Row-shared windows (sweep_dense_rs.hip, option "row_shared"): the window W of the form for sweeps whose arguments are
-// the production ones (lean), 0 where today's row-per-proposal kernel runs.  The form needs what the look-ahead form
-// needs -- one dense matrix, integer J and h with exact fp32 sums (the accept table) -- and J symmetric with a
-// zero diagonal (a flip's correction is read from the flipped site's row), |J| <= 255 (bit-planes of |J|).  The rule:
-// Metropolis decides with the accept table, Glauber and heat bath with the row kernels' general rule on the same exact
-// fields (lean then implies SGA_ARITH_F64: sga_sweep refuses them fp32), Wolff is never served.  One matrix:
-// one model, or the models of sga_set_dense_shared, whose conditions are the batch's (table_m is over every h: one
-// accept table); a stacked batch has a row i per model and stays on the row-per-proposal kernel.
-// 1 = wherever it applies (W: option "row_shared_window", else the autotuner's, else 1024), 2 = where sga_autotune
-// measured it ahead (default).  The autotuner's W counts only while the engine's rule is the one it was timed under
-// (rs_tuned_rule): the form's time follows the flip rate, and Glauber's is not Metropolis'.
-// Option "row_shared_grid" = 1 opens the form to the problems the integer form does not take and the set-time verdict
-// admits (sga_classify.cpp, row_shared_grid: J on a grid 2^-k, |2^k J| <= 255, scaled row sums below 2^24, any h) under
-// the same remaining conditions; the chain then decides with the row kernels' general rule instead of the table's.
-int row_shared_form_planes(const sga_engine *e, int *grid) {
-    *grid = 0;
-    if (e->table_m > 0 && !e->acc64) return sga::row_shared_planes(e->j_abs_max);
-    if (e->opt[OPT_ROW_SHARED_GRID] != 1 || e->rs_grid_planes == 0) return 0;
-    *grid = 1 + e->rs_grid_k;
-    return e->rs_grid_planes;
-}
-
-int row_shared_window(const sga_engine *e, bool lean) {
-    const long long o = e->opt[OPT_ROW_SHARED];
-    int grid = 0;
-    if (o == 0 || e->rs_suspend || !lean || e->rule == SGA_RULE_WOLFF || e->field_cache != SGA_FIELD_CACHE_OFF) return 0;
-    if (e->csr || e->implicit() || e->ragged || (e->n_models != 1 && !e->shared_j) || !e->consistent_dE) return 0;
-    if (e->opt[OPT_LOOK_AHEAD] == 0 || e->opt[OPT_FORCE_GENERAL] != 0 || !e->J_packed) return 0;
-    if (row_shared_form_planes(e, &grid) == 0 || (long long)e->R * e->n >= (1ll << 31) || e->R >= (1 << 20)) return 0;
-    const int tuned = e->rule == e->rs_tuned_rule ? e->rs_tuned_w : 0;  // the autotuner's pick belongs to the rule it timed
-    if (o == 2) return tuned;
-    const long long fw = e->opt[OPT_ROW_SHARED_WINDOW];  // (option "row_shared_window": W for option 1)
-    return fw >= 1024 ? 1024 : fw >= 512 ? 512 : fw >= 256 ? 256 : (tuned > 0 ? tuned : 1024);
-}
-
-// Sequential windows (sweep_dense_seq.hip, sga_set_sequential_windows): the form as a SGA_SITE_SEQUENTIAL sweep without
-// per-update traces would run it, W = 0 where the row-per-proposal kernel runs.  One dense matrix (one model, or the
-// models of sga_set_dense_shared), symmetric with a zero diagonal, cache off, a single-site rule, and a problem class in
-// which the product is exact: the integer class of the look-ahead form (the accept table's), or -- option
-// "row_shared_grid" = 1 -- the set-time grid verdict (J on 2^-k, scaled sums below 2^24, any finite h; integer J beside
-// a half-integer or real h is k = 0).  Option "row_shared" does not gate it: that one governs the random-site windows.
-// The product: int8 rows on the int8 matrix cores; fp32 rows too where every |2^k J_ij| <= 127 (through a resident int8
-// copy, ensure_seq_j8) -- j_abs_max for integer J, 3 magnitude planes (|2^k J| <= 7) for the grid -- else the fp32 cores.
-// The mode returned for fp32 rows is the class's; the sweep moves mode 0 to mode 1 where the copy cannot be had.
-sga::SeqWindows sequential_windows(const sga_engine *e) {
-    sga::SeqWindows q{};
-    if (e->seq_w <= 0 || e->rule == SGA_RULE_WOLFF || e->field_cache != SGA_FIELD_CACHE_OFF) return q;
-    if (e->csr || e->implicit() || e->ragged || (e->n_models != 1 && !e->shared_j) || !e->consistent_dE) return q;
-    if (e->opt[OPT_FORCE_GENERAL] != 0 || !e->J_packed || e->n <= 0) return q;
-    int jmax;
-    if (e->table_m > 0 && !e->acc64) {
-        jmax = e->j_abs_max;
-    } else if (e->opt[OPT_ROW_SHARED_GRID] == 1 && e->rs_grid_planes > 0) {
-        q.grid = 1 + e->rs_grid_k;
-        jmax = e->rs_grid_planes <= 3 ? 7 : 255;
-    } else {
-        return q;
-    }
-    if (e->want_i8 && q.grid > 1) return q;  // (int8 rows are integers)
-    if ((long long)e->R * e->n >= (1ll << 31)) return q;
-    // the product's 16-byte loads walk whole steps of 32 columns: inside the (zero-padded) strides of both operands
-    const long long kpad = ((long long)e->n + 31) / 32 * 32;
-    if (e->ldj < kpad || (e->R > 0 && (e->sstride % 16 != 0 || e->sstride < kpad))) return q;
-    q.mode = (e->want_i8 || jmax <= 127) ? 0 : 1;
-    q.W = e->seq_w;
-    return q;
-}
-
-// fp32 rows that the int8 matrix cores can take: their resident int8 copy, made once per problem -- the product reads a
-// quarter of the bytes and converts nothing (measured against conversion in registers, DESIGN.md 7: 1.23 -> 0.65 ms of
-// product per sweep at n = 10^4, 1024 replicas).  Where the n^2 bytes cannot be had the fp32 matrix cores take the rows
-// (exact all the same).
-static void ensure_seq_j8(sga_engine *e, sga::SeqWindows &q, hipStream_t st) {
-    if (q.mode != 0 || e->want_i8) return;
-    const long long ld8 = sga::seq_i8_stride(e->n);
-    if (!e->seq_j8 && !e->seq_j8_refused) {
-        hipError_t he = hipMalloc(&e->seq_j8, (size_t)e->n * (size_t)ld8);
-        if (he == hipSuccess)
-            he = sga::launch_seq_build_i8(static_cast<const float *>(e->J_packed), e->ldj, e->n, q.grid ? q.grid - 1 : 0, e->seq_j8, ld8, st);
-        if (he != hipSuccess) {
-            (void)hipGetLastError();
-            dev_free(e->seq_j8);
-            e->seq_j8_refused = true;
-        }
-    }
-    if (!e->seq_j8) {
-        q.mode = 1;
-        return;
-    }
-    q.j8 = e->seq_j8;
-    q.ld8 = ld8;
-}
-
-// its scratch, base[R][W]: made by the form's first sweep, kept until the replicas go; false (and the row-per-proposal
-// kernel runs) if it cannot be had
-static bool ensure_seq_base(sga_engine *e, int W) {
-    if (e->seq_base && e->seq_base_w >= W) return true;
-    dev_free(e->seq_base);
-    e->seq_base_w = 0;
-    if (hipMalloc(&e->seq_base, sizeof(int) * (size_t)e->R * (size_t)W) != hipSuccess) {
-        (void)hipGetLastError();
-        e->seq_base = nullptr;
-        return false;
-    }
-    e->seq_base_w = W;
-    return true;
-}
-
-// The fields kernel of the row-shared windows over resident planes, by option "row_shared_fields": the tile size S and
-// whether the rows are sign-only, or S = 0 and the reason where the per-site kernel runs.  Option 2 takes the tiles only
-// in the configuration measured to win.  Known once the planes exist (rs_ones is found with them).
-sga::RowSharedTiles row_shared_tiles(const sga_engine *e, const char **why) {
-    sga::RowSharedTiles t{};
-    const char *dummy;
-    if (!why) why = &dummy;
-    *why = nullptr;
-    int grid = 0;
-    const int planes = row_shared_form_planes(e, &grid);
-    if (e->opt[OPT_ROW_SHARED_FIELDS] == 0) return (*why = "option row_shared_fields = 0"), t;
-    if (!e->rs_jp) return (*why = "no resident bit-planes"), t;
-    if (e->rs_tiles_refused) return (*why = "the tile kernel's LDS request was refused"), t;
-    if (e->opt[OPT_ROW_SHARED_FIELDS] == 2 && (*why = sga::row_shared_tiles_not_default(e->n, planes, e->rs_ones))) return t;
-    t.S = sga::row_shared_tile_sites(e->n, planes, e->rs_ones, e->R, e->cus, (int)e->opt[OPT_ROW_SHARED_TILE_SITES], why);
-    t.ones = t.S > 0 && e->rs_ones;
-    return t;
-}
-
-// the form's scratch for W and, where the problem gets them, its resident bit-planes of J: false (and the
-// row-per-proposal kernel runs) if either cannot be had
-static bool ensure_row_shared(sga_engine *e, int W, hipStream_t st) {
-    int grid = 0;
-    const int planes = row_shared_form_planes(e, &grid);
-    if (e->rs.cnt && e->rs.W == W && e->rs_R == e->R && e->rs_n == e->n && e->rs_grid == grid) return true;
-    e->free_row_shared();
-    const size_t n = (size_t)e->n, R = (size_t)e->R, nwin = (n + (size_t)W - 1) / (size_t)W;
-    const int nw32 = sga::row_shared_nw32(e->n);
-    const int log_rg = sga::row_shared_log_group(e->n, W);
-    const size_t groups = (R + ((size_t)1 << log_rg) - 1) >> log_rg;
-    hipError_t he = hipSuccess;
-    if (!e->rs_jp && sga::row_shared_resident(e->want_i8, planes)) {  // once per problem
-        he = hipMalloc(&e->rs_jp, sga::row_shared_plane_bytes(e->n, planes));
-        if (he == hipSuccess) he = hipMalloc(&e->rs_jabs, sizeof(int) * n);
-        if (he == hipSuccess)
-            he = sga::launch_rs_build_planes(e->J_packed, e->want_i8, e->ldj, e->n, planes, grid ? grid - 1 : 0, e->rs_jp,
-                                             e->rs_jabs, st);
-        // sign-only rows: one magnitude plane and sum_j |J_ij| = n - 1 in every row -- every off-diagonal |J_ij| (grid
-        // form: |2^k J_ij|) is 1, the magnitude plane says nothing the diagonal's place does not (rs_fields_tiles_kernel)
-        e->rs_ones = false;
-        if (he == hipSuccess && planes == 1) {
-            std::vector<int> jabs(n);
-            he = hipMemcpyAsync(jabs.data(), e->rs_jabs, sizeof(int) * n, hipMemcpyDeviceToHost, st);
-            if (he == hipSuccess) he = hipStreamSynchronize(st);
-            e->rs_ones = he == hipSuccess && std::all_of(jabs.begin(), jabs.end(), [&](int v) { return v == (int)n - 1; });
-        }
-        if (he != hipSuccess) {
-            dev_free(e->rs_jp);
-            dev_free(e->rs_jabs);
-        }
-    }
-    if (he == hipSuccess) he = hipMalloc(&e->rs.cnt, sizeof(int) * nwin * groups * n);
-    if (he == hipSuccess) he = hipMalloc(&e->rs.off, sizeof(int) * nwin * (n + 1));
-    if (he == hipSuccess) he = hipMalloc(&e->rs.tot, sizeof(int) * nwin * (size_t)sga::row_shared_scan_chunks(e->n));
-    if (he == hipSuccess) he = hipMalloc(&e->rs.ent, sizeof(int) * R * n);
-    if (he == hipSuccess) he = hipMalloc(&e->rs.base, sizeof(int) * R * (size_t)W);
-    if (he == hipSuccess) he = hipMalloc(&e->rs.bits, sizeof(uint32_t) * R * (size_t)nw32);
-    if (he != hipSuccess) {
-        (void)hipGetLastError();
-        e->free_row_shared();
-        return false;
-    }
-    int lw = 0;
-    while ((1 << lw) < W) ++lw;
-    e->rs.W = W;
-    e->rs.log_w = lw;
-    e->rs.nw32 = nw32;
-    e->rs.planes = planes;
-    e->rs_grid = grid;
-    e->rs.jp = e->rs_jp;
-    e->rs.jabs = e->rs_jabs;
-    e->rs.log_rg = log_rg;
-    e->rs.n_groups = (int)groups;
-    e->rs_R = e->R;
-    e->rs_n = e->n;
-    return true;
 }
 
 // The cached-local-field sweep serves this problem / these replicas?  why: the reason when it does not
@@ -532,7 +346,33 @@ int ensure_packed(sga_engine *e) {
 extern "C" {
 
 const char *sga_last_error(void) { return g_last_error.c_str(); }
-int sga_version(void) { return 2100; }  // + sga_set_sequential_windows / sga_get_sequential_windows: SGA_SITE_SEQUENTIAL sweeps in windows, the window-start fields of every replica on the matrix cores (sweep_dense_seq.hip; " sweep=seq-windows(W=...)" in sga_describe)  // 2000: + row-shared windows under SGA_RULE_GLAUBER and SGA_RULE_HEAT_BATH (sweep_dense_rs.hip, ANYRULE; "rule=..." in sga_describe and sga_get_last_kernel), the autotuner's window kept per rule  // 1900: + options "row_shared_fields", "row_shared_tile_sites": the row-shared fields in tiles of sites, sign-only rows (sweep_dense_rs.hip, rs_fields_tiles_kernel)  // 1800: + option "row_shared_grid": row-shared windows for dense J on a binary grid under any h (sweep_dense_rs.hip, GRID), sga_route_query.rs_grid  // 1700: + sga_set_csr_shared (one set of CSR rows, many field vectors)  // 1600: + sga_set_dense_shared (one coupling matrix, many field vectors), sga_route_query.shared_j  // 1500: + sga_get_scan_summary; the dense and CSR setters refuse non-finite J / h  // 1400: + option "batch_fixed_point": fixed-point cached local fields for many-model dense batches (sweep_clf_fx.hip, MODELS)  // 1300: + options "ragged_field_cache" and "clf_fixed_point" together: fixed-point cached local fields for ragged CSR batches (sweep_clf_csr.hip)  // 1200: + sga_set_groups_csr (group couplings plus a stored sparse remainder, sweep_groups.hip)  // 1100: + option "ragged_field_cache" (cached local fields for ragged CSR batches, sweep_clf_csr.hip)  // 1000: + sga_set_groups (implicit cardinality-group couplings, sweep_groups.hip)  // 900: + cached local fields for many-model dense batches (sga_set_dense_batch)  // 800: + option "clf_fixed_point" over dense couplings (sweep_clf_fx.hip)  // 700: + option "clf_fixed_point" (cached fields of real-valued CSR couplings)  // 600: + sga_set_csr_batch / sga_get_batch_model (ragged CSR batches)  // round 5: + sga_explain_route / sga_get_route_query, sga_get_last_kernel, sga_get_autotune_table, ladder-local sga_exchange
+// The ABI version, one line per step:
+//   2100:    + sga_set_sequential_windows / sga_get_sequential_windows: SGA_SITE_SEQUENTIAL sweeps in windows, the
+//            window-start fields of every replica on the matrix cores (sweep_dense_seq.hip; " sweep=seq-windows(W=...)"
+//            in sga_describe)
+//   2000:    + row-shared windows under SGA_RULE_GLAUBER and SGA_RULE_HEAT_BATH (sweep_dense_rs.hip, ANYRULE;
+//            "rule=..." in sga_describe and sga_get_last_kernel), the autotuner's window kept per rule
+//   1900:    + options "row_shared_fields", "row_shared_tile_sites": the row-shared fields in tiles of sites, sign-only
+//            rows (sweep_dense_rs.hip, rs_fields_tiles_kernel)
+//   1800:    + option "row_shared_grid": row-shared windows for dense J on a binary grid under any h
+//            (sweep_dense_rs.hip, GRID), sga_route_query.rs_grid
+//   1700:    + sga_set_csr_shared (one set of CSR rows, many field vectors)
+//   1600:    + sga_set_dense_shared (one coupling matrix, many field vectors), sga_route_query.shared_j
+//   1500:    + sga_get_scan_summary; the dense and CSR setters refuse non-finite J / h
+//   1400:    + option "batch_fixed_point": fixed-point cached local fields for many-model dense batches
+//            (sweep_clf_fx.hip, MODELS)
+//   1300:    + options "ragged_field_cache" and "clf_fixed_point" together: fixed-point cached local fields for ragged
+//            CSR batches (sweep_clf_csr.hip)
+//   1200:    + sga_set_groups_csr (group couplings plus a stored sparse remainder, sweep_groups.hip)
+//   1100:    + option "ragged_field_cache" (cached local fields for ragged CSR batches, sweep_clf_csr.hip)
+//   1000:    + sga_set_groups (implicit cardinality-group couplings, sweep_groups.hip)
+//   900:     + cached local fields for many-model dense batches (sga_set_dense_batch)
+//   800:     + option "clf_fixed_point" over dense couplings (sweep_clf_fx.hip)
+//   700:     + option "clf_fixed_point" (cached fields of real-valued CSR couplings)
+//   600:     + sga_set_csr_batch / sga_get_batch_model (ragged CSR batches)
+//   round 5: + sga_explain_route / sga_get_route_query, sga_get_last_kernel, sga_get_autotune_table, ladder-local
+//            sga_exchange
+int sga_version(void) { return 2100; }
 
 int sga_create(int device, sga_engine **out) {
     if (!out) return fail(SGA_ERR_INVALID, "out is NULL");
@@ -697,13 +537,13 @@ int sga_set_sequential_windows(sga_engine *e, int W) {
     if (!e) return fail(SGA_ERR_INVALID, "engine is NULL");
     if (W != 0 && W != 256 && W != 512 && W != 1024)
         return fail(SGA_ERR_INVALID, "sequential windows: W must be 0 (off), 256, 512 or 1024");
-    e->seq_w = W;
+    e->win.seq_w = W;
     return SGA_OK;
 }
 
 int sga_get_sequential_windows(sga_engine *e, int *W) {
     if (!e || !W) return fail(SGA_ERR_INVALID, "engine or output is NULL");
-    *W = e->seq_w;
+    *W = e->win.seq_w;
     return SGA_OK;
 }
 
@@ -1169,29 +1009,12 @@ int plan_sweep(sga_engine *e, const SweepCall &c, SweepPlan &p) {
             e->fields_valid = false;
         }
     }
-    // row-shared windows (sweep_dense_rs.hip): one coupling-row read per proposed site and window
+    // the window forms (sga_windows.cpp): row-shared windows for production arguments, sequential windows for sequential
+    // sweeps, neither with per-update traces; a form whose scratch cannot be had leaves the row-per-proposal kernel
     if (!clf && !p.exact_mode) {  // (exact_mode: the Wolff rule too)
-        const bool lean_call = c.site_mode == SGA_SITE_RANDOM && c.arith == SGA_ARITH_F64 && !c.acc.ptr && !c.dE.ptr;
-        p.rs_w = row_shared_window(e, lean_call);
-        if (p.rs_w && !ensure_row_shared(e, p.rs_w, e->stream)) p.rs_w = 0;
-        if (p.rs_w) {  // the fields in tiles: the kernel's LDS is asked for here, a refusal leaves the per-site kernel
-            p.rs_tiles = row_shared_tiles(e, nullptr);
-            if (p.rs_tiles.S > 0 &&
-                sga::row_shared_tiles_prepare(e->rs.planes, p.rs_tiles.ones != 0,
-                                              sga::row_shared_tile_lds(e->n, e->rs.planes, p.rs_tiles.ones != 0, p.rs_tiles.S, e->R)) !=
-                    hipSuccess) {
-                (void)hipGetLastError();
-                e->rs_tiles_refused = true;
-                p.rs_tiles = sga::RowSharedTiles{};
-            }
-        }
-        // sequential windows (sweep_dense_seq.hip, sga_set_sequential_windows): one read of each coupling row per sweep
-        if (c.site_mode == SGA_SITE_SEQUENTIAL && !c.acc.ptr && !c.dE.ptr) {
-            p.seq = sequential_windows(e);
-            if (p.seq.W && !ensure_seq_base(e, p.seq.W)) p.seq.W = 0;
-            p.seq.base = e->seq_base;
-            if (p.seq.W) ensure_seq_j8(e, p.seq, e->stream);
-        }
+        const bool untraced = !c.acc.ptr && !c.dE.ptr;
+        plan_windows(e, untraced && c.site_mode == SGA_SITE_RANDOM && c.arith == SGA_ARITH_F64,
+                     untraced && c.site_mode == SGA_SITE_SEQUENTIAL, p.rs_w, p.rs_tiles, p.seq);
     }
     return SGA_OK;
 }
@@ -1253,7 +1076,7 @@ hipError_t launch_sweep(sga_engine *e, const SweepPlan &p, sga::SweepArgs a, hip
     if (e->tsp) return sga::launch_sweep_tsp(a, e->tsp_args, e->tsp_waves, e->tsp_passes, st);
     if (e->csr) return sga::launch_sweep_csr(a, e->waves, st);
     if (p.seq.W) return sga::launch_sweep_dense_seq(a, p.seq, e->want_i8, e->cus, st);
-    if (p.rs_w) return sga::launch_sweep_dense_rs(a, e->rs, e->want_i8, st, e->rs_grid, p.rs_tiles);
+    if (p.rs_w) return sga::launch_sweep_dense_rs(a, e->win.rs, e->want_i8, st, e->win.rs_grid, p.rs_tiles);
     return launch_dense_rows(e, a, st);
 }
 

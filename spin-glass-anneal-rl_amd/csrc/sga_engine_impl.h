@@ -8,6 +8,8 @@
 //                     modes' sweep-time policy over the acceptance counters (no HIP calls)
 //   sga_classify.cpp  WHICH arithmetic a problem admits: accumulation class, accept table, cached-field eligibility and
 //                     the refusal reasons, pure functions of the set-time scan summaries (no HIP calls)
+//   sga_windows.cpp   the window forms of the dense sweep (row-shared, its tiles, sequential): admission as pure functions
+//                     of WindowTraits, the forms' state by lifetime (WindowState), their scratch and per-call plan
 #ifndef SGA_ENGINE_IMPL_H
 #define SGA_ENGINE_IMPL_H
 #include <hip/hip_runtime.h>
@@ -22,6 +24,7 @@
 #include "sga.h"
 #include "sga_kernels.h"
 #include "sga_route.h"
+#include "sga_windows.h"
 
 namespace sga_impl {
 
@@ -39,6 +42,7 @@ void dev_free(T *&p) {
     if (p) (void)hipFree(p);
     p = nullptr;
 }
+inline void dev_release(void *p) { (void)hipFree(p); }  // (what WindowState's resets hand their buffers to)
 
 inline bool is_device_ptr(const void *p) {
     if (!p) return false;
@@ -134,9 +138,6 @@ struct sga_engine {
     // and opt[] for the problem it measured; free_problem() -- every setter -- goes back to these.
     int caller_tune_waves = 0;
     long long caller_csr_ups = -1;
-    // sga_set_sequential_windows: W of the sequential windows (sweep_dense_seq.hip; 0: off).  The caller's choice for
-    // every later problem, read at every sga_sweep; not part of sga_export_state.
-    int seq_w = 0;
     hipStream_t own_stream = nullptr;
     hipStream_t stream = nullptr;
 
@@ -242,41 +243,10 @@ struct sga_engine {
     hipStream_t aux_stream = nullptr;   // the second launch of a mixed sweep
     hipEvent_t fork_ev = nullptr, join_ev = nullptr;
     char last_kernel[512] = {0};        // the instantiation this engine's last sweep launch ran (sga_get_last_kernel)
-    // row-shared windows (sweep_dense_rs.hip, option "row_shared"): the window the autotuner picked (0: none) and the
-    // update rule it was measured under (the form's time follows the flip rate: the pick holds for that rule only), the
-    // plan / field scratch and what it was sized for; rs_suspend keeps the form out of the autotuner's geometry trials.
-    // rs_jp / rs_jabs: the resident bit-planes of J_packed and sum_j |J_ij| per row (RowSharedPlan::jp, jabs), built by
-    // the form's first sweep of a problem.  They belong to the problem, not to W or the replicas: free_problem -- the
-    // one place J_packed is replaced -- drops them, window and replica changes keep them.
-    // rs_grid_planes / rs_grid_k: the set-time verdict of the grid form (option "row_shared_grid", sga_classify.cpp:
-    // row_shared_grid) -- planes of |2^k J| (0: no verdict) and k; a shared-coupling batch: over the batch's words.
-    int rs_tuned_w = 0, rs_tuned_rule = SGA_RULE_METROPOLIS;
-    int rs_grid_planes = 0, rs_grid_k = 0;
-    bool rs_suspend = false;
-    sga::RowSharedPlan rs{};
-    int rs_R = 0, rs_n = 0;
-    int rs_grid = 0;  // what rs was prepared for: 0 the integer form, else 1 + k (launch_sweep_dense_rs)
-    unsigned long long *rs_jp = nullptr;
-    int *rs_jabs = nullptr;
-    // sequential windows (sweep_dense_seq.hip): the resident int8 copy of fp32 rows with |2^k J| <= 127, [n][seq_i8_stride(n)],
-    // made by the form's first sweep of a problem (SeqWindows::j8); refused: its allocation failed, the product runs on
-    // the fp32 matrix cores
-    int8_t *seq_j8 = nullptr;
-    bool seq_j8_refused = false;
-    // rs_ones: found with the planes -- every off-diagonal |J_ij| (grid form: |2^k J_ij|) is 1, the fields kernel reads
-    // sign planes only; rs_tiles_refused: the runtime refused the tile kernel's LDS for this problem (per-site kernel)
-    bool rs_ones = false, rs_tiles_refused = false;
-    void free_row_shared() {
-        dev_free(rs.cnt);
-        dev_free(rs.off);
-        dev_free(rs.tot);
-        dev_free(rs.ent);
-        dev_free(rs.base);
-        dev_free(rs.bits);
-        rs = sga::RowSharedPlan{};
-        rs_R = rs_n = 0;
-        rs_grid = 0;
-    }
+    // the window forms (row-shared windows, their tiles, sequential windows): everything they keep between sweeps, ordered
+    // by lifetime (sga_windows.h); the three resets below drop what the next plan, replica set and problem each must not see
+    sga_windows::WindowState win;
+    void free_row_shared() { win.next_plan(dev_release); }
     int csr_acc = sga::CSR_ACC_F64_CANON;  // CSR: how the sweep kernels form a row sum (set time)
     // what the set-time scans wrote, as read back by the setter (sga_get_scan_summary): dense the eight words of
     // classify_dense, CSR the CSR_* words and the longest row per model; empty: none kept (implicit couplings)
@@ -293,8 +263,6 @@ struct sga_engine {
     unsigned long long *n_acc = nullptr;
     long long attempted = 0;  // per replica
     uint32_t sweeps_done = 0, rounds = 0;
-    int *seq_base = nullptr;  // [R][seq_base_w] scratch of the sequential windows, made by their first sweep
-    int seq_base_w = 0;
 
     // ladder
     int n_ladders = 0;
@@ -367,17 +335,7 @@ struct sga_engine {
         scan_per_model = 0;
         n = 0;
         ld = 0;
-        free_row_shared();
-        dev_free(rs_jp);
-        dev_free(rs_jabs);
-        dev_free(seq_j8);
-        seq_j8_refused = false;
-        rs_ones = false;
-        rs_tiles_refused = false;
-        rs_tuned_w = 0;
-        rs_tuned_rule = SGA_RULE_METROPOLIS;
-        rs_grid_planes = 0;
-        rs_grid_k = 0;
+        win.next_problem(dev_release);
         // every other problem-scoped member back to its declared default: what one problem's setter computed is never
         // the next problem's, whichever setter that is and whether or not it assigns the member itself
         // (tests/test_engine_reuse_host.py holds the struct's "// problem" section against this function)
@@ -438,11 +396,7 @@ struct sga_engine {
         ybuf_bytes = 0;
         routing.reset();
         dev_free(d_rep_lists);
-        free_row_shared();
-        dev_free(seq_base);
-        seq_base_w = 0;
-        rs_tuned_w = 0;
-        rs_tuned_rule = SGA_RULE_METROPOLIS;
+        win.next_replicas(dev_release);
         R = Rg = 0;
         n_ladders = 0;
     }
@@ -476,6 +430,9 @@ bool clf_active(const sga_engine *e);
 int ensure_fields(sga_engine *e);
 int recompute_energy_range(sga_engine *e, int r0, int count);
 int ensure_packed(sga_engine *e);
+// ---- sga_windows.cpp: each of the four a line over the pure half (sga_windows.h), asked of window_traits_of(e)
+sga_windows::WindowTraits window_traits_of(const sga_engine *e);
+// W of the row-shared windows for a sweep whose arguments are the production ones (lean), 0: the row-per-proposal kernel
 int row_shared_window(const sga_engine *e, bool lean);
 // magnitude planes of the row-shared form that serves the problem (0: none); *grid: 0 the integer form, else 1 + k
 int row_shared_form_planes(const sga_engine *e, int *grid);
@@ -484,6 +441,11 @@ sga::RowSharedTiles row_shared_tiles(const sga_engine *e, const char **why);
 // the sequential windows (sga_set_sequential_windows) as a sequential, untraced sweep of this engine would run them:
 // W = 0 where the row-per-proposal kernel runs (base is left null: the scratch is the sweep's)
 sga::SeqWindows sequential_windows(const sga_engine *e);
+// The window forms of one sga_sweep call off the cached fields and the exact mode: rs_w, rs_tiles and seq as the launches
+// take them.  In this order: the row-shared scratch (and, once per problem, the planes), the tile kernel's LDS request,
+// the sequential scratch and int8 copy.  Every failure leaves the row-per-proposal kernel; a refused LDS request and a
+// failed int8 copy are remembered for the problem.
+void plan_windows(sga_engine *e, bool lean_call, bool sequential_call, int &rs_w, sga::RowSharedTiles &rs_tiles, sga::SeqWindows &seq);
 // ---- sga_problem.cpp
 bool csr_rows_medium(const sga_engine *e);
 int csr_updates_per_step(const sga_engine *e);

@@ -440,7 +440,8 @@ struct RowSharedGridPlan {
     RowSharedPlan p;
     int k;
 };
-int row_shared_planes(int j_abs_max);  // 0: |J| beyond 255, the form does not apply
+// magnitude bit-planes of |J| for an integer bound on it; 0: |J| beyond 255, the form does not apply
+inline int row_shared_planes(int j_abs_max) { return j_abs_max <= 1 ? 1 : j_abs_max <= 7 ? 3 : j_abs_max <= 255 ? 8 : 0; }
 inline int row_shared_nw32(int n) { return 8 * ((n + 255) / 256); }
 inline int row_shared_scan_chunks(int n) { return (n + 1023) / 1024; }  // workgroups of the scan per window
 // Resident planes exist where they take at most half the bytes of J: fp32 rows always ((planes + 1) / 32 of J), int8

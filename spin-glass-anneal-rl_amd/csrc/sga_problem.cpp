@@ -570,8 +570,8 @@ int set_dense_common(sga_engine *e, const float *J, int64_t ldJ, const float *h,
     // option says now); a shared-coupling batch: the words, hence k, planes and the bound, are the batch's
     {
         const sga_classify::RsGridVerdict g = sga_classify::row_shared_grid(c);
-        e->rs_grid_planes = g.why ? 0 : g.planes;
-        e->rs_grid_k = g.why ? 0 : g.k;
+        e->win.grid_planes = g.why ? 0 : g.planes;
+        e->win.grid_k = g.why ? 0 : g.k;
     }
     // The problems the integer cached-field form does not take: which of its conditions failed, and with option
     // "clf_fixed_point" the fixed-point form's verdict (sga_classify.cpp).  After the packing: the diagonal it extracts

@@ -10,6 +10,7 @@
 #include <cstdio>
 
 #include "sga_kernels.h"
+#include "sga_windows.h"
 
 namespace sga_route {
 
@@ -652,6 +653,38 @@ bool look(ReplicaRouting &s, const LookInput &in, const std::function<const unsi
     return back;
 }
 
+// ---- the window forms' admission rules over a query (sga_windows.h) ------------------------------------------------------
+sga_windows::WindowTraits window_traits_of_query(const Query &q) {
+    sga_windows::WindowTraits t;
+    t.dense = q.kind == SGA_ROUTE_DENSE;
+    t.n_models = q.n_models;
+    t.shared_j = q.shared_j != 0;
+    t.n = q.n;
+    t.ldj = q.ldj;
+    t.sstride = q.sstride;
+    t.want_i8 = is_i8(q);
+    t.acc64 = q.acc != 0 && !t.want_i8;  // (int8 rows sum in int32 whatever q.acc says)
+    t.table_m = q.table_m;
+    t.grid_planes = q.rs_grid > 0 ? 1 : 0;  // assumed: a query carries k alone -- some verdict, the fewest planes
+    t.grid_k = q.rs_grid > 0 ? q.rs_grid - 1 : 0;
+    t.field_cache = q.field_cache;
+    t.cus = q.cus;
+    t.row_shared = q.opt[sga_impl::OPT_ROW_SHARED];
+    t.row_shared_grid = q.opt[sga_impl::OPT_ROW_SHARED_GRID];
+    t.row_shared_fields = q.opt[sga_impl::OPT_ROW_SHARED_FIELDS];
+    t.row_shared_tile_sites = q.opt[sga_impl::OPT_ROW_SHARED_TILE_SITES];
+    t.look_ahead = q.opt[sga_impl::OPT_LOOK_AHEAD];
+    t.force_general = q.opt[sga_impl::OPT_FORCE_GENERAL];
+    t.consistent_dE = q.clf_ok != 0;  // assumed: the cached-field verdict stands in for "symmetric, zero diagonal"
+    t.j_abs_max = 1;                  // assumed: |J| within the planes' range (a query carries no maximum)
+    t.R = 0;                          // assumed: the replica bounds are met (R n < 2^31, R < 2^20)
+    t.packed = true;                  // assumed: the couplings are set
+    t.rule = SGA_RULE_METROPOLIS;     // assumed: a query carries no rule
+    t.row_shared_window = 0;          // assumed: the default window -- with no tuned pick (tuned_w = 0), option 1 gives
+                                      // W = 1024 and option 2 no window
+    return t;
+}
+
 // ---- the whole chain of decisions as one line ----------------------------------------------------------------------------
 std::string explain(const Query &q0) {
     Query q = q0;
@@ -724,19 +757,15 @@ std::string explain(const Query &q0) {
             std::snprintf(buf, sizeof(buf), " shared-J models=%d", q.n_models);
             out += buf;
         }
-        // option "row_shared" = 1 forces the row-shared windows (sweep_dense_rs.hip) where the problem admits them:
-        // one matrix (one model, or shared_j: the traits are then the batch's), integer J and h with exact fp32 sums,
-        // symmetric with a zero diagonal (clf_ok), Metropolis look-ahead allowed (the default 2 leaves the form to
-        // sga_autotune, which a query does not know about)
-        if (q.opt[OPT_ROW_SHARED] == 1 && q.field_cache == SGA_FIELD_CACHE_OFF && (q.n_models == 1 || q.shared_j) && q.table_m > 0 &&
-            q.clf_ok && (q.acc == 0 || i8) && q.opt[OPT_LOOK_AHEAD] != 0 && q.opt[OPT_FORCE_GENERAL] == 0)
-            out += " sweep=row-shared(W=1024)";
-        // option "row_shared_grid" = 1 beside it: the problems the integer form does not take whose J lies on a binary
-        // grid (rs_grid = 1 + k: the set-time verdict of sga_classify.cpp, row_shared_grid), under the same conditions
-        else if (q.opt[OPT_ROW_SHARED] == 1 && q.opt[OPT_ROW_SHARED_GRID] == 1 && q.rs_grid > 0 &&
-                 q.field_cache == SGA_FIELD_CACHE_OFF && (q.n_models == 1 || q.shared_j) && q.clf_ok &&
-                 q.opt[OPT_LOOK_AHEAD] != 0 && q.opt[OPT_FORCE_GENERAL] == 0) {
-            std::snprintf(buf, sizeof(buf), " sweep=row-shared(W=1024 grid=2^-%d)", q.rs_grid - 1);
+        // option "row_shared" = 1 forces the row-shared windows (sweep_dense_rs.hip) where the problem admits them, in the
+        // integer class or -- option "row_shared_grid" = 1 -- on the binary grid of the set-time verdict (rs_grid = 1 + k);
+        // the default 2 leaves the form to sga_autotune, which a query does not know about
+        const sga_windows::WindowTraits wt = window_traits_of_query(q);
+        if (const int w = sga_windows::row_shared_w(wt, true)) {
+            if (const int grid = sga_windows::form_class(wt).grid)
+                std::snprintf(buf, sizeof(buf), " sweep=row-shared(W=%d grid=2^-%d)", w, grid - 1);
+            else
+                std::snprintf(buf, sizeof(buf), " sweep=row-shared(W=%d)", w);
             out += buf;
         }
         q.sstride = (int)g.ld;

@@ -81,6 +81,10 @@ static_assert(OPT_COUNT <= SGA_ROUTE_MAX_OPTS, "sga_route_query::opt holds every
 
 }  // namespace sga_impl
 
+namespace sga_windows {
+struct WindowTraits;  // sga_windows.h
+}
+
 namespace sga_route {
 
 using Query = sga_route_query;
@@ -197,6 +201,10 @@ struct LookInput {
 // acceptance counters now (nullptr: the read failed, nothing moves), and the routes, hot / wide, the marks and the
 // interval move.  True: somebody returns from the row kernels, the resident fields are to be seeded anew.
 bool look(ReplicaRouting &s, const LookInput &in, const std::function<const unsigned long long *()> &read_counters);
+
+// A dense query as the traits the window forms' admission rules read (sga_windows.h); what a query does not carry is
+// assumed there, line by line.  explain() prints " sweep=row-shared(...)" from it.
+sga_windows::WindowTraits window_traits_of_query(const Query &q);
 
 std::string explain(const Query &q);
 

@@ -426,7 +426,7 @@ int sga_describe(sga_engine *e, char *buf, int buflen) {
                               sga::row_shared_plane_bytes(e->n, pl));
             else
                 std::strncat(tmp, " rs_fields=on-chip-conversion", sizeof(tmp) - std::strlen(tmp) - 1);
-            if (e->rs_jp) {  // (the planes exist: whether the rows are sign-only is known) option "row_shared_fields"
+            if (e->win.jp) {  // (the planes exist: whether the rows are sign-only is known) option "row_shared_fields"
                 const char *why = nullptr;
                 const sga::RowSharedTiles t = row_shared_tiles(e, &why);
                 if (t.S > 0)

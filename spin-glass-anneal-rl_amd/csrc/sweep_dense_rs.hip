@@ -858,10 +858,6 @@ static hipError_t rs_chain(const SweepArgs &a, const RowSharedPlan &p, int grid,
     return rs_chain_launch<JE, BITS, false, false>(a, p, p.W, k, win, st);
 }
 
-int row_shared_planes(int j_abs_max) {
-    return j_abs_max <= 1 ? 1 : j_abs_max <= 7 ? 3 : j_abs_max <= 255 ? 8 : 0;
-}
-
 template <typename JE>
 static hipError_t rs_build_planes(const void *J, long long ldj, int n, int planes, unsigned long long *jp, int *jabs,
                                   hipStream_t st) {
