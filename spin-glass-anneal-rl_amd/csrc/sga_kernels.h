@@ -425,6 +425,9 @@ struct RowSharedPlan {
     int *off;        // [n_windows][n + 1] first entry of each (window, site)
     int *tot;        // [n_windows][row_shared_scan_chunks(n)] proposals per (window, chunk of 1024 sites): the scan's carries
     int *ent;        // [R n] (replica << log_w | update in window), grouped by (window, site)
+                     // The tile kernel's plan (rs_tile_plan_kernel) in the same two arrays: ent grouped by (window, slice
+                     // of replicas, tile, replica), site in tile | replica in slice << 12 | update in window << 17; cnt
+                     // as 16-bit words [n_windows][tiles][slices], the first entry of each run inside its slice
     int *base;       // [R][W] row sums against the window-start spins
     uint32_t *bits;  // [R][nw32] window-start spins, 1 = down (the layout of sweep_dense_rs.hip)
     const unsigned long long *jp;  // [n][planes + 1][nw32 / 2] sign plane and magnitude planes of every row of J in the
@@ -518,6 +521,47 @@ inline int row_shared_tile_sites(int n, int planes, bool ones, int R, int cus, i
         if (S < 2) S = 2;
         if (S <= RS_TILE_MAX_SITES && row_shared_tile_lds(n, planes, ones, (int)S, R) <= RS_TILE_LDS_BUDGET) return (int)S;
     }
+}
+// The plan of the tile kernel (rs_tile_plan_kernel): a workgroup owns a slice -- one window, rg consecutive replicas -- and
+// sorts its rg W entries in LDS by (tile, replica); it asks for rg W words of staging, a counter per (tile of its pass,
+// replica), and RS_TILE_PLAN_EXTRA words.  The first entry of every (window, tile, slice) run goes, 16 bits wide (at most
+// 32 W), where the by-site plan keeps its counts: ceil(n / S) ceil(R / rg) values per window must fit the n ceil(R / 2^
+// row_shared_log_group) words the engine allocates there.  rg: a power of two, at most 32 (5 bits of the entry word), 0
+// where no geometry serves; tiles: the tiles a workgroup covers in one pass -- fewer than ceil(n / S) where the tiles
+// are covered in ranges, every range walking the slice's Philox blocks again (a third grid dimension).
+struct RowSharedTilePlan {
+    int rg = 0;
+    int tiles = 0;
+};
+constexpr int RS_TILE_PLAN_THREADS = 1024;      // workgroup of the plan
+constexpr int RS_TILE_PLAN_EXTRA = 32;          // words beside staging and counters: the scan's wave totals, two sums
+constexpr size_t RS_TILE_PLAN_LDS = 80 * 1024;  // what the rule asks for: two workgroups per CU
+inline size_t row_shared_tile_plan_lds(int W, int rg, int tiles) {
+    return 4 * ((size_t)rg * (size_t)W + (size_t)rg * (size_t)tiles + RS_TILE_PLAN_EXTRA);
+}
+inline bool row_shared_tile_plan_runs_fit(int n, int W, int S, int R, int rg) {
+    const long long ntiles = (n + S - 1) / S, slices = (R + rg - 1) / rg;
+    const long long groups = ((long long)R + (1ll << row_shared_log_group(n, W)) - 1) >> row_shared_log_group(n, W);
+    return 2 * ntiles * slices <= 4 * groups * (long long)n;
+}
+// The rule: the largest rg whose staging and counters for ALL tiles fit RS_TILE_PLAN_LDS (and whose run starts fit);
+// else tile ranges with the smallest rg whose run starts fit -- the fewest ranges, so the fewest walks of the Philox
+// blocks -- in RS_TILE_PLAN_LDS, and last in the tile kernel's own budget (32 replicas of W = 1024 stage 128 KB).
+inline RowSharedTilePlan row_shared_tile_plan(int n, int W, int S, int R) {
+    RowSharedTilePlan t;
+    if (n <= 0 || S <= 0 || R <= 0 || W <= 0) return t;
+    const int ntiles = (n + S - 1) / S;
+    for (int rg = 32; rg >= 1; rg >>= 1)
+        if (row_shared_tile_plan_lds(W, rg, ntiles) <= RS_TILE_PLAN_LDS && row_shared_tile_plan_runs_fit(n, W, S, R, rg))
+            return (t.rg = rg), (t.tiles = ntiles), t;
+    const size_t budgets[2] = {RS_TILE_PLAN_LDS, RS_TILE_LDS_BUDGET};
+    for (const size_t budget : budgets)
+        for (int rg = 1; rg <= 32; rg <<= 1) {
+            if (row_shared_tile_plan_lds(W, rg, 1) > budget || !row_shared_tile_plan_runs_fit(n, W, S, R, rg)) continue;
+            const size_t per_pass = (budget / 4 - RS_TILE_PLAN_EXTRA - (size_t)rg * (size_t)W) / (size_t)rg;
+            return (t.rg = rg), (t.tiles = per_pass < (size_t)ntiles ? (int)per_pass : ntiles), t;
+        }
+    return t;
 }
 // asks the runtime for the tile kernel's LDS (once per instantiation and size): an error where it is refused
 hipError_t row_shared_tiles_prepare(int planes, bool ones, size_t lds_bytes);

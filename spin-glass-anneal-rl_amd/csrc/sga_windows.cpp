@@ -238,6 +238,9 @@ void plan_windows(sga_engine *e, bool lean_call, bool sequential_call, int &rs_w
     if (rs_w) {  // the fields in tiles: the kernel's LDS is asked for here, a refusal leaves the per-site kernel
         rs_tiles = row_shared_tiles(e, nullptr);
         const int planes = e->win.rs.planes;
+        // (the tile plan's run starts live in the by-site plan's counts: where they cannot -- many replicas over more
+        //  than 32 windows in tiles of a few sites -- the per-site kernel and its plan run)
+        if (rs_tiles.S > 0 && sga::row_shared_tile_plan(e->n, rs_w, rs_tiles.S, e->R).rg == 0) rs_tiles = sga::RowSharedTiles{};
         if (rs_tiles.S > 0 &&
             sga::row_shared_tiles_prepare(planes, rs_tiles.ones != 0,
                                           sga::row_shared_tile_lds(e->n, planes, rs_tiles.ones != 0, rs_tiles.S, e->R)) != hipSuccess) {

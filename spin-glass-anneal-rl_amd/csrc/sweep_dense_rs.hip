@@ -214,6 +214,118 @@ __global__ void __launch_bounds__(256) rs_pack_kernel(const SweepArgs a, RowShar
     }
 }
 
+// ---- the tile kernel's plan: the sweep's pairs sorted by (window, slice of rg replicas, tile, replica) ----------------
+// The tile kernel needs the entries of its S sites grouped by replica, and no order by site: so a workgroup owns one slice
+// (window w, replicas r0 .. r0 + rg), sorts the slice's entries in LDS by (tile, replica in the slice) -- a counting sort:
+// count per key while the Philox blocks are walked, the sites kept in registers; scan; place -- and writes the sorted
+// slice out in one piece, consecutive lanes to consecutive words, at its fixed place R t0 + r0 nt of ent[] (the regions
+// tile ent[] exactly).  One launch per sweep, no atomic and no partial line of entries reaches memory.  The entries of a
+// (slice, tile) pair are a contiguous run, ordered by replica; the run's first entry (relative to the slice, 16 bits)
+// goes to runs[w][tile][slice], in the by-site plan's cnt allocation (row_shared_tile_plan_runs_fit), so that a tile reads
+// the bounds of its runs over all slices as two contiguous rows (the last tile's runs end with their slices).
+// The entry word: site - tile S (12 bits: S <= RS_TILE_MAX_SITES) | replica - r0 (5 bits) << 12 | update in the window
+// << 17; the reader knows the slice from the run it reads.  The order inside a (tile, replica) bucket is whatever the LDS
+// atomics make it; every entry names its own base slot.
+// blockIdx.z: the range of tpp tiles this workgroup sorts (row_shared_tile_plan: one range wherever the counters of all
+// tiles fit); a range walks all of the slice's blocks, counts the entries of earlier tiles -- its place in the slice --
+// and drops those of later ones.
+constexpr int RS_TILE_PLAN_PAIRS = 32 * 1024 / 2 / RS_TILE_PLAN_THREADS;  // Philox blocks per thread: rg W <= 32 * 1024
+
+// site / S without a divide: mul = ceil(2^32 / S), S >= 2; the product's high word is the quotient or one above it
+__device__ __forceinline__ int rs_tile_of(int site, int S, unsigned int mul, int &ls) {
+    int tile = (int)__umulhi((unsigned int)site, mul);
+    ls = site - tile * S;
+    if (ls < 0) --tile, ls += S;
+    return tile;
+}
+
+__global__ void __launch_bounds__(RS_TILE_PLAN_THREADS) rs_tile_plan_kernel(const SweepArgs a, RowSharedPlan p, int k, int S,
+                                                                           int log_trg, int tpp) {
+    constexpr int T = RS_TILE_PLAN_THREADS, NP = RS_TILE_PLAN_PAIRS;
+    extern __shared__ int stage[];  // [rg W] the sorted entries, [tpp rg] counters then cursors, RS_TILE_PLAN_EXTRA words
+    const int sl = blockIdx.x, w = blockIdx.y, n = a.n, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int rg = 1 << log_trg, r0 = sl << log_trg, nr = min(rg, a.R - r0);
+    const int t0 = w << p.log_w, nt = min(p.W, n - t0);  // t0 is even: one Philox block serves updates 2 b, 2 b + 1
+    const int ntiles = (n + S - 1) / S, tl0 = blockIdx.z * tpp, ntl = min(tpp, ntiles - tl0), ncnt = ntl << log_trg;
+    int *cnt = stage + (rg << p.log_w), *wtot = cnt + (tpp << log_trg), *sums = wtot + T / 64;  // sums: [0] earlier tiles, [1] ours
+    const unsigned int mul = 0xffffffffu / (unsigned int)S + 1u;
+    for (int c = tid; c < ncnt; c += T) cnt[c] = 0;
+    if (tid < 2) sums[tid] = 0;
+    __syncthreads();
+    const int lhalf = p.log_w - 1, hmask = (1 << lhalf) - 1, np = nr << lhalf;
+    int site[2 * NP];  // the sites of this thread's updates that fall into the range; -1: none
+    int below = 0;
+#pragma unroll
+    for (int j = 0; j < NP; ++j) {
+        const int x = tid + j * T, rr = x >> lhalf, b = x & hmask;
+        site[2 * j] = site[2 * j + 1] = -1;
+        if (x < np && 2 * b < nt) {
+            const u32x4 q = philox4x32_10((uint32_t)((t0 >> 1) + b), a.sweep0 + (uint32_t)k, a.replica0 + (uint32_t)(r0 + rr),
+                                          DOMAIN_SWEEP, a.seed_lo, a.seed_hi);
+            const int sA = (int)word_to_site(q.x, (uint32_t)n), sB = 2 * b + 1 < nt ? (int)word_to_site(q.z, (uint32_t)n) : -1;
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const int s = h ? sB : sA;
+                if (s < 0) continue;
+                int ls;
+                const int tl = rs_tile_of(s, S, mul, ls) - tl0;
+                if (tl < 0) ++below;
+                else if (tl < ntl) {
+                    atomicAdd(&cnt[(tl << log_trg) + rr], 1);
+                    site[2 * j + h] = s;
+                }
+            }
+        }
+    }
+    if (tl0 > 0) {  // (workgroup-uniform)
+        below = wave_sum(below);
+        if (lane == 0 && below) atomicAdd(&sums[0], below);
+    }
+    __syncthreads();
+    below = sums[0];
+    {  // exclusive scan of cnt in (tile, replica) order: thread t owns counters [t per, (t + 1) per)
+        const int per = (ncnt + T - 1) / T, c0 = tid * per;
+        int sum = 0;
+        for (int j = 0; j < per; ++j)
+            if (c0 + j < ncnt) sum += cnt[c0 + j];
+        int inc = sum;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const int t = __shfl_up(inc, d);
+            if (lane >= d) inc += t;
+        }
+        if (lane == 63) wtot[wv] = inc;
+        __syncthreads();
+        int run = inc - sum;
+        for (int x = 0; x < wv; ++x) run += wtot[x];
+        unsigned short *runs = reinterpret_cast<unsigned short *>(p.cnt) + ((long long)w * ntiles + tl0) * gridDim.x + sl;
+        for (int j = 0; j < per; ++j)
+            if (c0 + j < ncnt) {
+                const int c = cnt[c0 + j];
+                cnt[c0 + j] = run;
+                if (((c0 + j) & (rg - 1)) == 0) runs[(long long)((c0 + j) >> log_trg) * gridDim.x] = (unsigned short)(below + run);
+                run += c;
+            }
+        if (tid == T - 1) sums[1] = run;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < NP; ++j) {
+        const int x = tid + j * T, rr = x >> lhalf, b = x & hmask;
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const int s = site[2 * j + h];
+            if (s < 0) continue;
+            int ls;
+            const int tl = rs_tile_of(s, S, mul, ls) - tl0;
+            stage[atomicAdd(&cnt[(tl << log_trg) + rr], 1)] = ls | (rr << 12) | ((2 * b + h) << 17);
+        }
+    }
+    __syncthreads();
+    int *dst = p.ent + (long long)a.R * t0 + (long long)r0 * nt + below;
+    for (int i = tid, m = sums[1]; i < m; i += T) dst[i] = stage[i];
+}
+
 // ---- a row of J as bit-planes ------------------------------------------------------------------------------------
 // PL magnitude planes: |J| < 2^PL.  planes: [PL + 1][nw = 4 nseg] 64-bit words (sign plane first), in LDS or in the
 // resident copy; every word is written.  Called by a workgroup of four waves; returns this lane's share of sum |J_ij|.
@@ -340,12 +452,12 @@ __global__ void __launch_bounds__(256) rs_fields_planes_kernel(const SweepArgs a
 // ---- fields from the resident planes in tiles: one workgroup (16 waves) per tile of S consecutive sites ---------------
 // The per-site kernel reads a replica's spin bits from L2 once per ENTRY; a replica proposes about W S / n sites of a
 // tile inside a window, so a workgroup that owns the tile needs them once per replica.  The tile's entries are the
-// contiguous range off[tile0] ... off[tile0 + ns] of the plan (unchanged).  The plane rows of its proposed sites go to
-// LDS (rows nobody proposes are not read), and the entries are grouped by replica with a counting sort in LDS (key
-// ent >> log_w, the site's index in the tile carried beside the entry; no atomic reaches memory; a range longer than
-// the entry buffer goes through in chunks, each sorted on its own).  Then the per-site kernel's inner loop, in sorted
-// order: the entries of a replica sit in adjacent quarter waves and passes, so their spin-bit loads merge or hit L1.
-// The order inside a replica's run is whatever the LDS atomics make it; every entry names its own base slot.
+// concatenation, in slice order, of its runs in the tile plan (rs_tile_plan_kernel): grouped by replica as they stand,
+// each carrying its site's index in the tile, so the kernel sorts nothing -- a prefix over the runs' lengths, then a
+// coalesced copy to LDS (a range longer than the entry buffer goes through in chunks: successive ranges of the
+// concatenation, cut wherever they fall).  The plane rows of the tile go to LDS beside the copy.
+// Then the per-site kernel's inner loop: the entries of a replica sit in adjacent quarter waves and passes, so their
+// spin-bit loads merge or hit L1.  The order inside a replica's run is the plan's; every entry names its own base slot.
 // ONES (every off-diagonal |J_ij| is 1: the magnitude plane is all ones but for the diagonal and the pad): the rows
 // are their sign planes alone.  sum_j |J_ij| [sign_ij != spin_j] = popcount(sign ^ spin) - spin_i, as the diagonal's sign
 // bit is 0 (its term is the spin bit itself, and the magnitude plane would have masked it) and the pad bits are 0 in
@@ -425,78 +537,90 @@ __device__ __forceinline__ void rs_tile_pieces(const RsTileChunk &ch, int wv, in
 }
 
 template <int PL, bool ONES>
-__global__ void __launch_bounds__(RS_TILE_THREADS) rs_fields_tiles_kernel(const SweepArgs a, RowSharedPlan p, int S, int win) {
+__global__ void __launch_bounds__(RS_TILE_THREADS) rs_fields_tiles_kernel(const SweepArgs a, RowSharedPlan p, int S, int log_trg,
+                                                                         int win) {
     constexpr int RP = ONES ? 1 : PL + 1, T = RS_TILE_THREADS, NW = T / 64;
     const int n = a.n, R = a.R, tile0 = blockIdx.x * S, ns = min(S, n - tile0);
-    const int *off = p.off + (long long)win * (n + 1) + tile0;
-    const int lo = off[0], hi = off[ns];
-    if (lo == hi) return;  // nobody proposes a site of this tile in this window
     extern __shared__ ulonglong2 prow[];  // [S][RP][nw / 2], then the arrays below (row_shared_tile_lds)
     const int nw2 = p.nw32 >> 2, rw2 = RP * nw2;
     int *sent = reinterpret_cast<int *>(prow + (size_t)S * rw2);  // [RS_TILE_ENTRIES] the chunk's entries by replica
-    int *cnt = sent + RS_TILE_ENTRIES;                            // [R] entries per replica, then the cursors
-    int *soff = cnt + R;                                          // [S + 1] first entry of each site of the tile
-    int *sjabs = soff + S + 1;                                    // [S] sum_j |J_ij|
+    int *spre = sent + RS_TILE_ENTRIES;                           // [R] entries of the tile before each slice's run (slices <= R)
+    int *sjabs = spre + R + S + 1;                                // [S] sum_j |J_ij| (behind S + 1 words the by-site plan's offsets took)                                    // [S] sum_j |J_ij|
     int *wtot = sjabs + S;                                        // [NW] the scan's wave totals
     unsigned short *sls = reinterpret_cast<unsigned short *>(wtot + NW);  // [RS_TILE_ENTRIES] site - tile0 of sent[.] (15 bits)
     const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6), sub = lane >> 4, l16 = lane & 15;
-    for (int s = tid; s <= ns; s += T) soff[s] = off[s];
+    // the tile's runs, one per slice (rs_tile_plan_kernel): run s is run0[s] ... run1[s] of the slice's region of ent[]
+    const int nsl = (R + (1 << log_trg) - 1) >> log_trg, t0 = win << p.log_w, nt = min(p.W, n - t0);
+    const bool last = blockIdx.x + 1 == gridDim.x;
+    const unsigned short *run0 = reinterpret_cast<const unsigned short *>(p.cnt) + ((long long)win * gridDim.x + blockIdx.x) * nsl;
+    const unsigned short *run1 = run0 + nsl;  // (the last tile's runs end where their slices end)
+    int total;
+    {  // spre: the exclusive prefix of the runs' lengths, thread t owns slices [t per, (t + 1) per)
+        const int per = (nsl + T - 1) / T, s0 = tid * per;
+        int sum = 0;
+        for (int j = 0; j < per; ++j)
+            if (s0 + j < nsl) sum += (last ? min(1 << log_trg, R - ((s0 + j) << log_trg)) * nt : (int)run1[s0 + j]) - (int)run0[s0 + j];
+        int inc = sum;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const int t = __shfl_up(inc, d);
+            if (lane >= d) inc += t;
+        }
+        if (lane == 63) wtot[wv] = inc;
+        __syncthreads();
+        int run = inc - sum;
+        total = 0;
+        for (int w = 0; w < NW; ++w) {
+            if (w < wv) run += wtot[w];
+            total += wtot[w];
+        }
+        if (total == 0) return;  // nobody proposes a site of this tile in this window (workgroup-uniform)
+        for (int j = 0; j < per; ++j)
+            if (s0 + j < nsl) {
+                spre[s0 + j] = run;
+                run += (last ? min(1 << log_trg, R - ((s0 + j) << log_trg)) * nt : (int)run1[s0 + j]) - (int)run0[s0 + j];
+            }
+    }
+    // The plane rows of the whole tile, beside the copy below.  (Reading only the rows somebody proposes was measured
+    // against this at 8 replicas, where most rows of a tile go unproposed: the rows come from L2, and marking them during
+    // the copy puts their loads behind it and a barrier more -- slower)
     for (int s = tid; s < ns; s += T) sjabs[s] = p.jabs[tile0 + s];
-    __syncthreads();
     for (int s = wv; s < ns; s += NW) {  // a wave per row
-        if (soff[s] == soff[s + 1]) continue;
         const ulonglong2 *src = reinterpret_cast<const ulonglong2 *>(p.jp) + (long long)(tile0 + s) * (PL + 1) * nw2;
         for (int c = lane; c < rw2; c += 64) prow[s * rw2 + c] = src[c];  // (ONES: the sign plane, the first)
     }
     const ulonglong2 *bits = reinterpret_cast<const ulonglong2 *>(p.bits);
-    const int per = (R + T - 1) / T;  // counters per thread in the scan
-    for (int c0 = lo; c0 < hi; c0 += RS_TILE_ENTRIES) {
-        const int cn = min(RS_TILE_ENTRIES, hi - c0);
-        const int *ent = p.ent + c0;
-        for (int r = tid; r < R; r += T) cnt[r] = 0;
-        __syncthreads();  // (and the rows; and the last chunk's readers of sent are two barriers ahead of its writers)
-        for (int x = tid; x < cn; x += T) atomicAdd(&cnt[ent[x] >> p.log_w], 1);
-        __syncthreads();
-        {  // exclusive scan of cnt: thread t owns counters [t per, (t + 1) per)
-            const int r0 = tid * per;
-            int sum = 0;
-            for (int j = 0; j < per; ++j)
-                if (r0 + j < R) sum += cnt[r0 + j];
-            int inc = sum;
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) {
-                const int t = __shfl_up(inc, d);
-                if (lane >= d) inc += t;
-            }
-            if (lane == 63) wtot[wv] = inc;
-            __syncthreads();
-            int run = inc - sum;
-            for (int w = 0; w < wv; ++w) run += wtot[w];
-            for (int j = 0; j < per; ++j)
-                if (r0 + j < R) {
-                    const int c = cnt[r0 + j];
-                    cnt[r0 + j] = run;
-                    run += c;
+    const int *went = p.ent + (long long)R * t0;  // the window's entries
+    for (int c0 = 0; c0 < total; c0 += RS_TILE_ENTRIES) {
+        const int cn = min(RS_TILE_ENTRIES, total - c0);
+        __syncthreads();  // (spre; and the last chunk's readers of sent are ahead of its writers)
+        // The chunk is entries c0 ... c0 + cn of the runs' concatenation in slice order -- slices are ascending, disjoint
+        // replica ranges and a run is ordered by replica, so it is grouped by replica as it stands: a wave per run copies
+        // what the chunk holds of it, consecutive lanes consecutive entries.  A wave takes runs wv, wv + NW, ...: it reads
+        // the bounds of 64 of them at once, a lane each, so that a run costs one trip to memory, not two in a row.
+        for (int sb = wv; sb < nsl; sb += 64 * NW) {
+            const int sm = sb + NW * lane;
+            int st = 0, b0 = 0, b1 = 0;
+            if (sm < nsl) st = run0[sm], b0 = spre[sm], b1 = sm + 1 < nsl ? spre[sm + 1] : total;
+            const int nrun = min(64, (nsl - sb + NW - 1) / NW);
+            for (int i = 0; i < nrun; ++i) {
+                const int B0 = read_lane(b0, i), x0 = max(B0, c0), x1 = min(read_lane(b1, i), c0 + cn);
+                if (x0 >= x1) continue;  // (wave-uniform)
+                const int rs0 = (sb + NW * i) << log_trg;
+                const int *src = went + (long long)rs0 * nt + read_lane(st, i) - B0;  // entry g of the concatenation, b0 <= g < b1
+                for (int g = x0 + lane; g < x1; g += 64) {
+                    const int v = src[g], r = rs0 + ((v >> 12) & 31);
+                    int ls = v & 0xfff;
+                    if constexpr (ONES) {  // the replica's own spin bit at the site rides in bit 15 (these loads overlap across the workgroup)
+                        int w32;
+                        unsigned int bit;
+                        rs_bit_of(tile0 + ls, w32, bit);
+                        if (p.bits[(long long)r * p.nw32 + w32] & bit) ls |= 0x8000;
+                    }
+                    sent[g - c0] = (r << p.log_w) | (v >> 17);
+                    sls[g - c0] = (unsigned short)ls;
                 }
-        }
-        __syncthreads();
-        for (int x = tid; x < cn; x += T) {
-            const int e = ent[x], g = c0 + x;
-            int sl = 0, sh = ns;  // soff[sl] <= g < soff[sh]: the entry's site is the last s with soff[s] <= g
-            while (sh - sl > 1) {
-                const int mid = (sl + sh) >> 1;
-                if (soff[mid] <= g) sl = mid;
-                else sh = mid;
             }
-            if constexpr (ONES) {  // the replica's own spin bit at the site rides in bit 15 (these loads overlap across the workgroup)
-                int w32;
-                unsigned int bit;
-                rs_bit_of(tile0 + sl, w32, bit);
-                if (p.bits[(long long)(e >> p.log_w) * p.nw32 + w32] & bit) sl |= 0x8000;
-            }
-            const int pos = atomicAdd(&cnt[e >> p.log_w], 1);
-            sent[pos] = e;
-            sls[pos] = (unsigned short)sl;
         }
         __syncthreads();
         // the sorted chunk, a contiguous piece per quarter wave: the spin bits in registers up to NKMAX words of 16 bytes
@@ -787,29 +911,30 @@ hipError_t row_shared_tiles_prepare(int planes, bool ones, size_t lds_bytes) {
     return ensure_lds_limit(kern, lds_bytes);
 }
 template <typename Kern>
-static hipError_t rs_launch_tiles(Kern kern, const SweepArgs &a, const RowSharedPlan &p, const RowSharedTiles &t, int win,
-                                  hipStream_t st) {
+static hipError_t rs_launch_tiles(Kern kern, const SweepArgs &a, const RowSharedPlan &p, const RowSharedTiles &t, int log_trg,
+                                  int win, hipStream_t st) {
     const size_t lds = row_shared_tile_lds(a.n, p.planes, t.ones != 0, t.S, a.R);
     hipError_t e = ensure_lds_limit(reinterpret_cast<const void *>(kern), lds);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3((a.n + t.S - 1) / t.S), dim3(RS_TILE_THREADS), lds, st, a, p, t.S, win);
+    hipLaunchKernelGGL(kern, dim3((a.n + t.S - 1) / t.S), dim3(RS_TILE_THREADS), lds, st, a, p, t.S, log_trg, win);
     return hipGetLastError();
 }
-static hipError_t rs_fields_tiles(const SweepArgs &a, const RowSharedPlan &p, const RowSharedTiles &t, int win, hipStream_t st) {
-    if (t.ones) return rs_launch_tiles(rs_fields_tiles_kernel<1, true>, a, p, t, win, st);
+static hipError_t rs_fields_tiles(const SweepArgs &a, const RowSharedPlan &p, const RowSharedTiles &t, int log_trg, int win,
+                                  hipStream_t st) {
+    if (t.ones) return rs_launch_tiles(rs_fields_tiles_kernel<1, true>, a, p, t, log_trg, win, st);
     switch (p.planes) {
-        case 1: return rs_launch_tiles(rs_fields_tiles_kernel<1, false>, a, p, t, win, st);
-        case 3: return rs_launch_tiles(rs_fields_tiles_kernel<3, false>, a, p, t, win, st);
-        case 8: return rs_launch_tiles(rs_fields_tiles_kernel<8, false>, a, p, t, win, st);
+        case 1: return rs_launch_tiles(rs_fields_tiles_kernel<1, false>, a, p, t, log_trg, win, st);
+        case 3: return rs_launch_tiles(rs_fields_tiles_kernel<3, false>, a, p, t, log_trg, win, st);
+        case 8: return rs_launch_tiles(rs_fields_tiles_kernel<8, false>, a, p, t, log_trg, win, st);
         default: return hipErrorInvalidValue;
     }
 }
 
 template <typename JE>
-static hipError_t rs_fields(const SweepArgs &a, const RowSharedPlan &p, int grid, const RowSharedTiles &tiles, int win,
+static hipError_t rs_fields(const SweepArgs &a, const RowSharedPlan &p, int grid, const RowSharedTiles &tiles, int log_trg, int win,
                             hipStream_t st) {
     const size_t lds = (size_t)(p.planes + 1) * (p.nw32 / 2) * 8;
-    if (p.jp && tiles.S > 0) return rs_fields_tiles(a, p, tiles, win, st);
+    if (p.jp && tiles.S > 0) return rs_fields_tiles(a, p, tiles, log_trg, win, st);
     if (p.jp) {
         switch (p.planes) {
             case 1: return rs_launch_fields(rs_fields_planes_kernel<1>, lds, a, p, win, st);
@@ -912,16 +1037,35 @@ hipError_t launch_sweep_dense_rs(const SweepArgs &a, const RowSharedPlan &p, boo
     const size_t plds = sizeof(int) * (size_t)(a.n < RS_PLAN_TILE ? a.n : RS_PLAN_TILE);
     const dim3 sgrid(row_shared_scan_chunks(a.n), nwin);
     const bool chain_bits = p.jp && p.planes == 1;
+    // the tile kernel takes its entries by (slice, tile, replica): one launch of the plan (row_shared_tile_plan)
+    const bool by_tile = p.jp && tiles.S > 0;
+    RowSharedTilePlan tp;
+    size_t tlds = 0;
+    int log_trg = 0;
+    if (by_tile) {
+        tp = row_shared_tile_plan(a.n, p.W, tiles.S, a.R);
+        if (tp.rg <= 0) return hipErrorInvalidValue;
+        while ((1 << log_trg) < tp.rg) ++log_trg;
+        tlds = row_shared_tile_plan_lds(p.W, tp.rg, tp.tiles);
+        const hipError_t le = ensure_lds_limit(reinterpret_cast<const void *>(rs_tile_plan_kernel), tlds);
+        if (le != hipSuccess) return le;
+    }
+    const int ntiles = by_tile ? (a.n + tiles.S - 1) / tiles.S : 0;
+    const dim3 tgrid(by_tile ? (a.R + tp.rg - 1) / tp.rg : 1, nwin, by_tile ? (ntiles + tp.tiles - 1) / tp.tiles : 1);
     hipLaunchKernelGGL(rs_pack_kernel, dim3(a.R), dim3(256), 0, st, a, p);
     hipError_t e = hipGetLastError();
     for (int k = 0; k < a.n_sweeps && e == hipSuccess; ++k) {
-        hipLaunchKernelGGL(rs_plan_kernel<false>, pgrid, dim3(256), plds, st, a, p, k);
-        hipLaunchKernelGGL(rs_scan_totals_kernel, sgrid, dim3(RS_SCAN_CHUNK), 0, st, a, p);
-        hipLaunchKernelGGL(rs_scan_kernel, sgrid, dim3(RS_SCAN_CHUNK), 0, st, a, p);
-        hipLaunchKernelGGL(rs_plan_kernel<true>, pgrid, dim3(256), plds, st, a, p, k);
+        if (by_tile) {
+            hipLaunchKernelGGL(rs_tile_plan_kernel, tgrid, dim3(RS_TILE_PLAN_THREADS), tlds, st, a, p, k, tiles.S, log_trg, tp.tiles);
+        } else {
+            hipLaunchKernelGGL(rs_plan_kernel<false>, pgrid, dim3(256), plds, st, a, p, k);
+            hipLaunchKernelGGL(rs_scan_totals_kernel, sgrid, dim3(RS_SCAN_CHUNK), 0, st, a, p);
+            hipLaunchKernelGGL(rs_scan_kernel, sgrid, dim3(RS_SCAN_CHUNK), 0, st, a, p);
+            hipLaunchKernelGGL(rs_plan_kernel<true>, pgrid, dim3(256), plds, st, a, p, k);
+        }
         e = hipGetLastError();
         for (int w = 0; w < nwin && e == hipSuccess; ++w) {
-            e = j_is_i8 ? rs_fields<int8_t>(a, p, grid, tiles, w, st) : rs_fields<float>(a, p, grid, tiles, w, st);
+            e = j_is_i8 ? rs_fields<int8_t>(a, p, grid, tiles, log_trg, w, st) : rs_fields<float>(a, p, grid, tiles, log_trg, w, st);
             if (e != hipSuccess) break;
             if (chain_bits)
                 e = j_is_i8 ? rs_chain<int8_t, true>(a, p, grid, k, w, st) : rs_chain<float, true>(a, p, grid, k, w, st);
