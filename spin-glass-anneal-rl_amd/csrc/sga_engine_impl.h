@@ -10,6 +10,11 @@
 //                     the refusal reasons, pure functions of the set-time scan summaries (no HIP calls)
 //   sga_windows.cpp   the window forms of the dense sweep (row-shared, its tiles, sequential): admission as pure functions
 //                     of WindowTraits, the forms' state by lifetime (WindowState), their scratch and per-call plan
+// The engine record is split by lifetime.  sga_engine derives from ProblemState (what the next sga_set_* must not see)
+// and ReplicaState (what the next sga_init_replicas must not see), so every member is still e->member; what survives
+// both stays in sga_engine itself.  A sub-record's defaults stand once, in its declaration: its reset releases the
+// device buffers it owns -- the one list there is -- and assigns a fresh record.  tests/c_abi/engine_record.cpp runs
+// the resets over a filled engine without a GPU.
 #ifndef SGA_ENGINE_IMPL_H
 #define SGA_ENGINE_IMPL_H
 #include <hip/hip_runtime.h>
@@ -19,6 +24,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <string>
 #include <vector>
 #include "sga.h"
@@ -42,7 +48,13 @@ void dev_free(T *&p) {
     if (p) (void)hipFree(p);
     p = nullptr;
 }
-inline void dev_release(void *p) { (void)hipFree(p); }  // (what WindowState's resets hand their buffers to)
+// What a reset hands the device buffers it drops to: the engine hipFree, tests/c_abi/engine_record.cpp a recorder.
+using Release = sga_windows::WindowState::Release;
+inline void dev_release(void *p) { (void)hipFree(p); }
+inline void release_all(std::initializer_list<void *> owned, Release release) {
+    for (void *p : owned)
+        if (p) release(p);
+}
 
 inline bool is_device_ptr(const void *p) {
     if (!p) return false;
@@ -121,27 +133,9 @@ struct DevOut {
     }
 };
 
-
-}  // namespace sga_impl
-
-using namespace sga_impl;
-
-struct sga_engine {
-    int device = 0;
-    int cus = 256;  // compute units of the device
-    long long opt[OPT_COUNT];  // sga_set_option values (defaults: OPT_DEFS, the environment read once in sga_create)
-    // an option latched at sga_set_* (bit 2) / sga_init_replicas (bit 1) changed afterwards: the next sweep says so
-    // instead of silently running the form the old value chose
-    int opt_stale = 0;
-    const char *opt_stale_key = nullptr;
-    // The caller's own sga_set_tuning waves and option "csr_updates_per_step".  sga_autotune writes its pick into tune_waves
-    // and opt[] for the problem it measured; free_problem() -- every setter -- goes back to these.
-    int caller_tune_waves = 0;
-    long long caller_csr_ups = -1;
-    hipStream_t own_stream = nullptr;
-    hipStream_t stream = nullptr;
-
-    // problem
+// ---- the problem: what a setter (sga_set_*) computes and allocates.  None of it is the next problem's, whichever setter
+// that is and whether or not it assigns the member itself: sga_engine::free_problem() -- every setter -- resets the record.
+struct ProblemState {
     int n = 0;
     int n_models = 1;  // dense batches: models stacked row-wise, replicas split evenly
     // sga_set_dense_shared: the n_models models hold ONE coupling matrix (J_packed, J_bits: n rows) and differ in h alone
@@ -154,19 +148,16 @@ struct sga_engine {
     bool ragged = false;
     int n_rows = 0;
     std::vector<int> model_n, model_row0;
-    int2 *d_models = nullptr;  // [n_models] {first row, spins}: what the ragged kernels read (inside h's allocation,
-    int ragged_at = 0;         // ragged_at floats in: SweepArgs::ragged)
+    int2 *d_models = nullptr;  // [n_models] {first row, spins}: what the ragged kernels read -- a view inside h's
+    int ragged_at = 0;         // allocation, never released; ragged_at floats in: SweepArgs::ragged
     bool csr = false;
     bool want_i8 = false, acc64 = false;
     bool acc_canon = false;  // acc64 and the fp64 row sum is not provably exact: canonical summation order
     bool use_t2 = false;           // ternary J as two bit-planes for the production sweeps
     unsigned int *J_bits = nullptr;  // [2][n][ld/32]
     float *row_nnz = nullptr;        // [n]
-    int waves_t2 = 0, cpw_t2 = 0;    // bit-plane geometry (waves/cpw then describe the int8 fallback)
     void *J_packed = nullptr;  // [n][ldj] float | int8
-    long long ld = 0;   // spins per replica (whole chunks)
     long long ldj = 0;  // row stride of J_packed: n rounded up to 128 bytes
-    int waves = 0, cpw = 0;
     int32_t *rowptr = nullptr, *colidx = nullptr;  // rowptr: only while the layout has < 2^31 entries
     long long *rowptr64 = nullptr;                  // always (energy / single-site kernels)
     int4 *rowinfo = nullptr;     // slotted layout, per row: first slot, slots, offset of a zero slot, h (wide sweep forms)
@@ -174,13 +165,9 @@ struct sga_engine {
     bool csr_sorted = false;     // rows strictly sorted by column: no duplicate entries
     uint32_t *cvp = nullptr;     // slotted layout with packed entries (24-bit column | int8 value << 24), on demand
     bool cvp_tried = false;      // packing was attempted for this problem (values may not fit)
-    int csr_storage = SGA_CSR_STORAGE_AUTO;         // what the caller asked for ...
-    int csr_storage_latched = SGA_CSR_STORAGE_AUTO; // ... and what the current replicas were laid out for
     int table_scale = 1;         // CSR accept table: entry q stands for dE = 2 q / table_scale
     long long layout_entries = 0;  // entries of the layout the kernels read (nnz + padding)
     long long max_row_len = 0;     // entries of the longest row
-    bool big = false;  // CSR sweeps with bit spins in LDS (decided per replica set)
-    int big_form = 0;  // 0 int8 spins | 1 bits, one replica per workgroup, 64-bit extents | 2 bits, narrow
     float *val = nullptr;   // colidx / val: only while the structure is being checked
     int2 *cv = nullptr;     // [nnz] interleaved (column, value bits): what the kernels read
     long long nnz = 0;
@@ -189,7 +176,6 @@ struct sga_engine {
     bool tsp = false, tsp_exact = true;
     float *nd4 = nullptr, *nd4t = nullptr;
     sga::TspArgs tsp_args{};
-    int tsp_waves = 0, tsp_passes = 0;
     // couplings as a sum of complete graphs on groups, never stored (sga_set_groups): site -> group table, group -> members
     bool groups = false;
     int *g_gptr = nullptr, *g_members = nullptr;
@@ -204,13 +190,9 @@ struct sga_engine {
     bool implicit() const { return tsp || groups; }  // structured couplings, none stored
     double *epart = nullptr;  // per-slice energy sums (few replicas)
     size_t epart_bytes = 0;
-    int tune_waves = 0, tune_spl = 0;
     std::string tune_table;  // what the last sga_autotune measured: "candidate=ms per sweep;..." (sga_get_autotune_table)
-    int rule = SGA_RULE_METROPOLIS;
     bool consistent_dE = true;  // J symmetric with zero diagonal: dE of the rule == energy change
-    int table_m = 0;  // integer problems: largest possible |dE| / 2 (0 = not integer / too big)
     // cached-local-field sweep (sweep_clf_impl.h)
-    int field_cache = SGA_FIELD_CACHE_OFF;  // what the caller asked for
     bool from_dense = false;  // CSR problem built from a sparse matrix handed over dense (sga_set_dense, SGA_J_AUTO)
     bool clf_problem = false;  // dense (one model or a batch, over all stacked rows), J integer valued, h in multiples of 1/2, symmetric, zero diagonal, sums < 2^24
     float row_abs_max = 0.0f;  // max_i(sum_j |J_ij| + |h_i|)
@@ -231,8 +213,49 @@ struct sga_engine {
     float csr_row_abs_max = 0.0f;  // CSR: max_i (sum_j |J_ij| + |h_i|): no |fk| of a move exceeds it
     int *hq = nullptr;           // [n] table_scale * h_i as integers (built with the first cached sweep)
     int clf_scale = 1, clf_bits = 16;
+    long long ldf = 0;  // row stride of ReplicaState::fields
+    int csr_acc = sga::CSR_ACC_F64_CANON;  // CSR: how the sweep kernels form a row sum (set time)
+    // what the set-time scans wrote, as read back by the setter (sga_get_scan_summary): dense the eight words of
+    // classify_dense, CSR the CSR_* words and the longest row per model; empty: none kept (implicit couplings)
+    std::vector<int32_t> scan_words;
+    int scan_per_model = 0;  // words per model (dense: the one stacked scan)
+    bool csr_x_exact = false;  // CSR: the fp64 sum X = sum_i mv_i s_i of an energy is exact in any order (set time)
+    // Latched per replica set: sga_init_replicas writes these for the replicas it lays out, and they stay -- through
+    // free_replicas(), for sga_describe and sga_get_route_query -- until the next problem.
+    long long ld = 0;   // spins per replica (whole chunks)
+    int waves = 0, cpw = 0;
+    int waves_t2 = 0, cpw_t2 = 0;    // bit-plane geometry (waves/cpw then describe the int8 fallback)
+    bool big = false;  // CSR sweeps with bit spins in LDS
+    int big_form = 0;  // 0 int8 spins | 1 bits, one replica per workgroup, 64-bit extents | 2 bits, narrow
+    int table_m = 0;  // integer problems: largest possible |dE| / 2 (0 = not integer / too big)
+    int tsp_waves = 0, tsp_passes = 0;
+    int csr_storage_latched = SGA_CSR_STORAGE_AUTO;  // what the current replicas were laid out for (asked: csr_storage)
+
+    void reset(Release release) {
+        release_all({J_packed, J_bits, row_nnz, rowptr, rowptr64, rowinfo, cvp, colidx, val, cv, h, diag, nd4, nd4t, hq, g_gptr,
+                     g_members, g_gent, g_member_ptr, g_coeff, g_rptr, g_rent, epart},
+                    release);
+        *this = ProblemState{};
+    }
+};
+
+// ---- the replicas: what sga_init_replicas, the ladder and the sweeps keep per replica set.  sga_engine::free_replicas()
+// -- every setter before free_problem(), sga_init_replicas itself -- resets the record.
+struct ReplicaState {
+    int R = 0, Rg = 0;
+    int8_t *spins = nullptr, *best_spins = nullptr;
+    double *energy = nullptr, *best_energy = nullptr, *rep_temp = nullptr;
+    unsigned long long *n_acc = nullptr;
+    // ladder
+    int n_ladders = 0;
+    double *slot_temps = nullptr;
+    int32_t *slot_to_rep = nullptr;
+    long long *ex_attempts = nullptr, *ex_accepts = nullptr;
+    float *wolff_u = nullptr;        // recorded uniforms of the Wolff rule [R][wolff_cap] (parity tests)
+    long long *wolff_cursor = nullptr;  // [R]
+    long long wolff_cap = 0;
+    // cached-local-field sweep
     void *fields = nullptr;    // [R][ldf] int16 | int32: clf_scale * (J s + h), valid while fields_valid
-    long long ldf = 0;
     bool fields_valid = false;
     void *ybuf = nullptr;      // [count][ldj] int32 | float: scratch of the all-replica field pass
     size_t ybuf_bytes = 0;
@@ -240,165 +263,81 @@ struct sga_engine {
     // counters): which replicas run on which kernel family, and in which form of the cached one (sga_route.cpp, look)
     sga_route::ReplicaRouting routing;
     int *d_rep_lists = nullptr;         // [2][R]: the cached-field kernel's replicas, then the row kernels'
+
+    void reset(Release release) {
+        release_all({spins, best_spins, energy, best_energy, rep_temp, n_acc, slot_temps, slot_to_rep, ex_attempts, ex_accepts,
+                     wolff_u, wolff_cursor, fields, ybuf, d_rep_lists},
+                    release);
+        *this = ReplicaState{};
+    }
+};
+
+}  // namespace sga_impl
+
+using namespace sga_impl;
+
+// What no reset touches stays here, grouped by why it survives.
+struct sga_engine : ProblemState, ReplicaState {
+    // -- the caller's choices: they hold for every later problem (include/sga.h)
+    long long opt[OPT_COUNT];  // sga_set_option values (defaults: OPT_DEFS, the environment read once in sga_create)
+    // an option latched at sga_set_* (bit 2) / sga_init_replicas (bit 1) changed afterwards: the next sweep says so
+    // instead of silently running the form the old value chose
+    int opt_stale = 0;
+    const char *opt_stale_key = nullptr;
+    // The caller's own sga_set_tuning waves and option "csr_updates_per_step".  sga_autotune writes its pick into tune_waves
+    // and opt[] for the problem it measured; free_problem() -- every setter -- goes back to these.
+    int caller_tune_waves = 0;
+    long long caller_csr_ups = -1;
+    int tune_waves = 0, tune_spl = 0;
+    int csr_storage = SGA_CSR_STORAGE_AUTO;  // sga_set_csr_storage (laid out for: csr_storage_latched)
+    int field_cache = SGA_FIELD_CACHE_OFF;   // sga_set_field_cache
+    int rule = SGA_RULE_METROPOLIS;          // sga_set_update_rule
+
+    // -- as long as the engine: made in sga_create or on first use, released in sga_destroy
+    int device = 0;
+    int cus = 256;  // compute units of the device
+    hipStream_t own_stream = nullptr;
+    hipStream_t stream = nullptr;
     hipStream_t aux_stream = nullptr;   // the second launch of a mixed sweep
     hipEvent_t fork_ev = nullptr, join_ev = nullptr;
     char last_kernel[512] = {0};        // the instantiation this engine's last sweep launch ran (sga_get_last_kernel)
-    // the window forms (row-shared windows, their tiles, sequential windows): everything they keep between sweeps, ordered
-    // by lifetime (sga_windows.h); the three resets below drop what the next plan, replica set and problem each must not see
-    sga_windows::WindowState win;
-    void free_row_shared() { win.next_plan(dev_release); }
-    int csr_acc = sga::CSR_ACC_F64_CANON;  // CSR: how the sweep kernels form a row sum (set time)
-    // what the set-time scans wrote, as read back by the setter (sga_get_scan_summary): dense the eight words of
-    // classify_dense, CSR the CSR_* words and the longest row per model; empty: none kept (implicit couplings)
-    std::vector<int32_t> scan_words;
-    int scan_per_model = 0;  // words per model (dense: the one stacked scan)
-    bool csr_x_exact = false;  // CSR: the fp64 sum X = sum_i mv_i s_i of an energy is exact in any order (set time)
-
-    // replicas
-    int R = 0, Rg = 0, replica0 = 0;
-    uint64_t seed = 0;
-    int sstride = 0;
-    int8_t *spins = nullptr, *best_spins = nullptr;
-    double *energy = nullptr, *best_energy = nullptr, *rep_temp = nullptr;
-    unsigned long long *n_acc = nullptr;
-    long long attempted = 0;  // per replica
-    uint32_t sweeps_done = 0, rounds = 0;
-
-    // ladder
-    int n_ladders = 0;
-    double *slot_temps = nullptr;
-    int32_t *slot_to_rep = nullptr;
-    long long *ex_attempts = nullptr, *ex_accepts = nullptr;
     int *d_count = nullptr;
-    float *wolff_u = nullptr;        // recorded uniforms of the Wolff rule [R][wolff_cap] (parity tests)
-    long long *wolff_cursor = nullptr;  // [R]
-    long long wolff_cap = 0;
     int *d_flags = nullptr;  // [16] value / structure scan results of the set_* calls (one per engine)
-
     // staging slots: 0 sched, 1 replay sites, 2 replay u, 3 energy trace, 4 accept trace,
     // 5 dE trace, 6 exchange energies, 7 exchange start, 8 exchange u
     Scratch scratch[9];
     Scratch point_sites, point_out;  // single-site operators
     Scratch csr_energy;              // transposed spin bits + partial sums of the all-replica CSR energy pass
-
     // timing
     bool timing = false;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
     int64_t launches = 0;
     double total_ms = 0.0;
 
-    void free_problem() {
-        dev_free(J_packed);
-        dev_free(J_bits);
-        dev_free(row_nnz);
-        use_t2 = false;
-        dev_free(rowptr);
-        dev_free(rowptr64);
-        dev_free(rowinfo);
-        dev_free(cvp);
-        cvp_tried = false;
-        slotted = false;
-        dev_free(colidx);
-        dev_free(val);
-        dev_free(cv);
-        dev_free(h);
-        dev_free(diag);
-        dev_free(nd4);
-        dev_free(nd4t);
-        dev_free(hq);
-        clf_csr_problem = false;
-        clf_ragged_why.clear();
-        clf_fx_bits = 0;
-        clf_fx_k = 0;
-        clf_fx_why = nullptr;
-        tsp = false;
-        dev_free(g_gptr);
-        dev_free(g_members);
-        dev_free(g_gent);
-        dev_free(g_member_ptr);
-        dev_free(g_coeff);
-        dev_free(g_rptr);
-        dev_free(g_rent);
-        groups = false;
-        group_args = sga::GroupArgs{};
-        dev_free(epart);
-        epart_bytes = 0;
-        clf_problem = false;
-        clf_why = nullptr;
-        d_models = nullptr;  // (part of h)
-        ragged_at = 0;
-        ragged = false;
-        n_rows = 0;
-        model_n.clear();
-        model_row0.clear();
-        scan_words.clear();
-        scan_per_model = 0;
-        n = 0;
-        ld = 0;
-        win.next_problem(dev_release);
-        // every other problem-scoped member back to its declared default: what one problem's setter computed is never
-        // the next problem's, whichever setter that is and whether or not it assigns the member itself
-        // (tests/test_engine_reuse_host.py holds the struct's "// problem" section against this function)
-        n_models = 1;
-        shared_j = false;
-        csr = false;
-        want_i8 = acc64 = acc_canon = false;
-        waves_t2 = cpw_t2 = 0;
-        ldj = 0;
-        waves = cpw = 0;
-        csr_sorted = false;
-        csr_storage_latched = SGA_CSR_STORAGE_AUTO;
-        table_scale = 1;
-        layout_entries = 0;
-        max_row_len = 0;
-        big = false;
-        big_form = 0;
-        nnz = 0;
-        tsp_exact = true;
-        tsp_args = sga::TspArgs{};
-        tsp_waves = tsp_passes = 0;
-        g_memberships = 0;
-        g_max_size = g_kmax = g_exp = 0;
-        consistent_dE = true;
-        table_m = 0;
-        from_dense = false;
-        row_abs_max = 0.0f;
-        j_abs_max = 0;
-        row_j_abs_max = 0.0f;
-        csr_row_abs_max = 0.0f;
-        clf_scale = 1;
-        clf_bits = 16;
-        ldf = 0;
-        csr_acc = sga::CSR_ACC_F64_CANON;
-        csr_x_exact = false;
+    // -- the window forms (row-shared windows, their tiles, sequential windows): everything they keep between sweeps, ordered
+    // by lifetime (sga_windows.h).  It holds the caller's seq_w and the autotuner's suspend beside what its own three resets
+    // drop for the next plan, replica set and problem: never assigned wholesale.
+    sga_windows::WindowState win;
+    void free_row_shared() { win.next_plan(dev_release); }
+
+    // -- the random stream's coordinates and the counters: sga_set_seed and sga_get_sweep_counter work on an engine without
+    // replicas, and sga_init_replicas (or an import of state) overwrites what it means to
+    int replica0 = 0;
+    uint64_t seed = 0;
+    int sstride = 0;
+    long long attempted = 0;  // per replica
+    uint32_t sweeps_done = 0, rounds = 0;
+
+    void free_problem(Release release = dev_release) {
+        ProblemState::reset(release);
+        win.next_problem(release);
         // sga_autotune's pick ends with the problem it was measured on (include/sga.h)
         tune_waves = caller_tune_waves;
         opt[OPT_CSR_UPDATES_PER_STEP] = caller_csr_ups;
-        tune_table.clear();
     }
-    void free_replicas() {
-        dev_free(spins);
-        dev_free(best_spins);
-        dev_free(energy);
-        dev_free(best_energy);
-        dev_free(rep_temp);
-        dev_free(n_acc);
-        dev_free(slot_temps);
-        dev_free(slot_to_rep);
-        dev_free(ex_attempts);
-        dev_free(ex_accepts);
-        dev_free(wolff_u);
-        dev_free(wolff_cursor);
-        wolff_cap = 0;
-        dev_free(fields);
-        fields_valid = false;
-        dev_free(ybuf);
-        ybuf_bytes = 0;
-        routing.reset();
-        dev_free(d_rep_lists);
-        win.next_replicas(dev_release);
-        R = Rg = 0;
-        n_ladders = 0;
+    void free_replicas(Release release = dev_release) {
+        ReplicaState::reset(release);
+        win.next_replicas(release);
     }
 };
 

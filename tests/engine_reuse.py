@@ -1,8 +1,9 @@
 """One engine, many problems: stations, walks and the comparison (test infrastructure; imports without a GPU).
 
 The C ABI lets one engine take any number of problems, and the long-lived callers (IsingModel._engine,
-CUDAKernelManager._engine) do exactly that.  What one problem leaves behind for the next is hand-maintained in
-csrc/sga_engine_impl.h (free_problem), so the tests walk ONE engine through problems of every kind and compare every
+CUDAKernelManager._engine) do exactly that.  What one problem leaves behind for the next is decided by where a member
+is declared in csrc/sga_engine_impl.h (ProblemState and ReplicaState are reset whole by free_problem / free_replicas,
+what stays in sga_engine survives), so the tests walk ONE engine through problems of every kind and compare every
 visit with a FRESH engine given the same settings and the same calls.  Same code, same inputs: everything is equal, no
 tolerance.  So that "fresh and re-used are wrong alike" cannot pass, a station's last visit in a walk is also held
 against the CPU oracle.

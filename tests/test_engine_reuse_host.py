@@ -1,15 +1,19 @@
-"""The engine-reuse walks without a GPU: what they cover, whether the comparison can fail, and whether free_problem()
-in csrc/sga_engine_impl.h resets every problem-scoped member of the engine record."""
+"""The engine-reuse walks without a GPU: what they cover, whether the comparison can fail, and whether the two resets
+of the engine record in csrc/sga_engine_impl.h (free_problem, free_replicas) drop every member of the sub-record they
+stand for, release every buffer it owns once, and leave the rest of the engine alone (tests/c_abi/engine_record.cpp)."""
 import os
 import re
+import subprocess
 
 import numpy as np
 import pytest
 
 import engine_reuse as er
+from test_window_forms_host import HIPCC, HOST
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 IMPL = os.path.join(ROOT, "spin-glass-anneal-rl_amd", "csrc", "sga_engine_impl.h")
+PROGRAM = os.path.join(ROOT, "tests", "c_abi", "engine_record.cpp")
 
 
 # ----------------------------------------------------------------------------- coverage
@@ -103,24 +107,22 @@ def test_assert_same_engine_tells_a_negative_zero_and_a_missing_key():
         er.assert_same_engine(_state(), b, "keys")
 
 
-# ----------------------------------------------------------------------------- the engine record against free_problem()
-# Members of the "// problem" section that are NOT the problem's, each with the reason it may survive a setter.
-# The caller's own settings persist by contract (include/sga.h):
-PERSIST = {
-    "csr_storage": "sga_set_csr_storage: the caller's choice for every later CSR problem",
-    "field_cache": "sga_set_field_cache: the caller's choice for every later problem",
-    "rule": "sga_set_update_rule: the caller's choice for every later problem",
-    "tune_spl": "sga_set_tuning's sweeps per launch (sga_autotune puts the caller's value back itself)",
-}
-# ... these live as long as the engine:
-ENGINE_LIFETIME = {
-    "aux_stream": "the second stream of a mixed launch, created once, destroyed in sga_destroy",
-    "fork_ev": "event of the mixed launch, created once, destroyed in sga_destroy",
-    "join_ev": "event of the mixed launch, created once, destroyed in sga_destroy",
-    "last_kernel": "what this engine's last sweep launched: a record of the past, not a trait of the problem",
-}
-# ... and these belong to the replicas: free_replicas(), which every setter calls first, must assign them
-REPLICA_SCOPED = ("fields", "fields_valid", "ybuf", "ybuf_bytes", "routing", "d_rep_lists")
+# ----------------------------------------------------------------------------- the engine record against its two resets
+# sga_engine derives from ProblemState and ReplicaState; each resets by releasing the buffers it owns and assigning a fresh
+# record.  tests/c_abi/engine_record.cpp runs free_replicas() / free_problem() over a filled engine (sentinels, no device
+# memory) and prints what came back to its default, what kept its value and what was released.  The declarations are read
+# here only for their member names: a member added later that the program does not cover fails below.
+REPLICA = ("spins best_spins energy best_energy rep_temp n_acc slot_temps slot_to_rep ex_attempts ex_accepts wolff_u wolff_cursor "
+           "wolff_cap fields fields_valid ybuf ybuf_bytes routing d_rep_lists R Rg n_ladders").split()
+# what sga_init_replicas writes and only the next problem resets
+LATCHED = "waves cpw ld waves_t2 cpw_t2 big big_form table_m tsp_waves tsp_passes csr_storage_latched".split()
+# what no reset may touch: the caller's choices, what lives as long as the engine, the window state's own two, the
+# random stream's coordinates and the counters
+SURVIVE = ("opt opt_stale opt_stale_key caller_tune_waves caller_csr_ups csr_storage field_cache rule tune_waves tune_spl "
+           "own_stream stream aux_stream fork_ev join_ev last_kernel d_count d_flags scratch point_sites point_out csr_energy "
+           "timing events launches total_ms win.seq_w win.suspend replica0 seed sstride attempted sweeps_done rounds").split()
+# free_problem() puts the caller's own values back over the autotuner's pick: these two hold neither their value nor a default
+CALLERS = ["opt", "tune_waves"]
 
 
 def _braces(text, at):
@@ -139,8 +141,9 @@ def _body(text, signature):
     return text[open_:_braces(text, open_)]
 
 
-def _members(section):
-    """Names of the data members declared in a piece of the struct (comments, member functions and initialisers dropped)."""
+def _members(section, owned_pointers=False):
+    """Names of the data members declared in a piece of a struct (comments, member functions and initialisers dropped).
+    owned_pointers: only those declared with a '*' to something not const (const char *: a string literal, not a buffer)."""
     s = re.sub(r"//[^\n]*", "", section)
     s = re.sub(r"\{\s*0?\s*\}", "", s)  # value initialisers: tsp_args{}, last_kernel[512] = {0}
     while "{" in s:  # what is left in braces is a member function's body: drop the function
@@ -156,59 +159,113 @@ def _members(section):
             part = part.split("=")[0].strip()
             m = re.search(r"([A-Za-z_]\w*)\s*(\[[^\]]*\])?$", part)
             assert m, (decl, part)
-            names.append(m.group(1))
+            if not owned_pointers or ("*" in part and not decl.startswith("const ")):
+                names.append(m.group(1))
     return names
 
 
-def _assigned(body, name, text):
-    # (win: the window forms' state resets itself by lifetime, next_problem / next_replicas -- member by member in
-    #  tests/test_window_forms_host.py::test_what_each_reset_drops)
-    pat = (rf"\b{name}\b(\[[^\]]*\])?\s*=(?!=)|dev_free\({name}\)|\b{name}\.(clear|reset|assign|next_\w+)\(")
-    if re.search(pat, body):
-        return True
-    # members reset through a helper the body calls (free_row_shared())
-    return any(re.search(pat, _body(text, f"void {fn}()")) for fn in re.findall(r"\b(free_\w+)\(\)", body)
-               if f"void {fn}()" in text and fn not in ("free_problem", "free_replicas"))
+def _declared(struct, **kw):
+    """Member names of `struct ProblemState {` | `struct ReplicaState {` | `struct sga_engine :` as declared."""
+    return _members(_body(open(IMPL).read(), f"struct {struct}")[1:-1], **kw)
 
 
-def _record():
-    text = open(IMPL).read()
-    struct = _body(text, "struct sga_engine {")
-    begin, end = struct.index("    // problem\n"), struct.index("    // replicas\n")
-    return text, _members(struct[begin:end])
+def _run(exe, *args):
+    """The program's report: key -> the names behind it"""
+    run = subprocess.run([exe, *args], capture_output=True, text=True)
+    assert run.returncode == 0 and not run.stderr, run.stderr[-2000:]
+    return {key: names.split() for key, names in (ln.split(":", 1) for ln in run.stdout.splitlines())}, run.stdout
+
+
+@pytest.fixture(scope="module")
+def record(tmp_path_factory):
+    exe = str(tmp_path_factory.mktemp("engine_record") / "engine_record")
+    subprocess.run([HIPCC] + HOST + [PROGRAM, "-o", exe], check=True, capture_output=True)
+    return exe
 
 
 def test_the_parser_reads_the_section():
-    _, members = _record()
-    for name in ("n", "n_models", "model_row0", "d_models", "J_bits", "table_scale", "tsp_args", "g_exp", "tune_table", "win",
-                 "scan_words", "csr_x_exact", "last_kernel", "clf_ragged_why", "cpw_t2", "nd4t", "rowptr64"):
-        assert name in members, name
-    assert "implicit" not in members and "free_row_shared" not in members and len(members) == len(set(members)) > 90
-    assert _members("int a = 0, *b = nullptr;  // x\n std::vector<int> c, d; void f() { a = 1; }\n char e[8] = {0}; T g{};") == \
-        ["a", "b", "c", "d", "e", "g"]
+    problem, replica, engine = _declared("ProblemState {"), _declared("ReplicaState {"), _declared("sga_engine :")
+    for name in ("n", "n_models", "model_row0", "d_models", "J_bits", "table_scale", "tsp_args", "g_exp", "tune_table",
+                 "scan_words", "csr_x_exact", "clf_ragged_why", "cpw_t2", "nd4t", "rowptr64", "group_args", "epart_bytes"):
+        assert name in problem, name
+    for name in ("win", "last_kernel", "opt", "scratch", "events", "join_ev", "rounds", "csr_energy"):
+        assert name in engine, name
+    everything = problem + replica + engine
+    assert not {"implicit", "reset", "free_row_shared", "free_problem", "free_replicas", "release"} & set(everything)
+    assert len(everything) == len(set(everything)) and len(problem) > 80 and len(replica) == 22 and len(engine) > 30
+    toy = "int a = 0, *b = nullptr;  // x\n std::vector<int> c, d; void f() { a = 1; }\n char e[8] = {0}; T g{}; const char *w = nullptr; void *p;"
+    assert _members(toy) == ["a", "b", "c", "d", "e", "g", "w", "p"] and _members(toy, owned_pointers=True) == ["b", "p"]
+    assert "clf_why" not in _declared("ProblemState {", owned_pointers=True) and "d_models" in _declared("ProblemState {", owned_pointers=True)
 
 
-def test_free_problem_resets_every_problem_scoped_member():
-    """Every member declared in the struct's "// problem" section is assigned in free_problem() -- or is on one of the
-    short lists above, with its reason.  A member added later without either fails here."""
-    text, members = _record()
-    body = _body(text, "void free_problem()")
-    replicas = _body(text, "void free_replicas()")
-    listed = set(PERSIST) | set(ENGINE_LIFETIME) | set(REPLICA_SCOPED)
-    assert listed <= set(members), ("listed, but no longer a member of the section", listed - set(members))
-    assert all(len(r) > 20 for r in list(PERSIST.values()) + list(ENGINE_LIFETIME.values()))
-    missing = [m for m in members if m not in listed and not _assigned(body, m, text)]
-    assert not missing, ("problem-scoped members that free_problem() does not reset", missing)
-    missing = [m for m in REPLICA_SCOPED if not _assigned(replicas, m, text)]
-    assert not missing, ("replica-scoped members that free_replicas() does not reset", missing)
-    # the autotuner's pick ends with its problem: free_problem() goes back to the caller's own values
-    assert re.search(r"tune_waves\s*=\s*caller_tune_waves", body) and re.search(r"opt\[OPT_CSR_UPDATES_PER_STEP\]\s*=\s*caller_csr_ups", body)
+def test_the_program_covers_exactly_the_declared_members(record):
+    out, _ = _run(record)
+    assert sorted(out["members.problem"]) == sorted(_declared("ProblemState {"))
+    assert sorted(out["members.replica"]) == sorted(_declared("ReplicaState {")) == sorted(REPLICA)
+    # (win resets itself by lifetime -- tests/test_window_forms_host.py::test_what_each_reset_drops; here its two members that
+    #  no reset touches stand for it)
+    own = sorted(set(_declared("sga_engine :")) - {"win"} | {"win.seq_w", "win.suspend"})
+    assert sorted(out["members.engine"]) == own and set(SURVIVE) <= set(own)
+    assert set(LATCHED) <= set(out["members.problem"])
+    assert out["members.unfilled"] == []  # every member was given a value that is not its default
 
 
-def test_the_check_would_notice_a_member_left_out():
-    text, members = _record()
-    body = _body(text, "void free_problem()")
-    for gone in ("table_scale = 1;", "from_dense = false;", "dev_free(g_rent);", "model_n.clear();"):
-        assert gone in body, gone
-        name = re.search(r"[a-z_]\w*(?=\)| =|\.)", gone.replace("dev_free(", "")).group(0)
-        assert _assigned(body, name, text) and not _assigned(body.replace(gone, ""), name, text), name
+def _owned(struct):
+    return [m for m in _declared(struct, owned_pointers=True) if m != "d_models"]  # (a view into h's allocation)
+
+
+def test_free_problem_resets_every_problem_scoped_member(record):
+    """Every ProblemState member is back at its declared default after free_problem(), every buffer the record owns went
+    to the release function once, the replicas and the rest of the engine kept their values -- but for tune_waves and
+    option "csr_updates_per_step", which are the caller's own again."""
+    out, _ = _run(record)
+    f = "free_problem"
+    assert out[f + ".problem.reset"] == out["members.problem"] and not out[f + ".problem.kept"] and not out[f + ".problem.neither"]
+    assert out[f + ".replica.kept"] == out["members.replica"] and not out[f + ".replica.reset"] and not out[f + ".replica.neither"]
+    assert sorted(out[f + ".released"]) == sorted(_owned("ProblemState {")) and len(out[f + ".released"]) == 23
+    assert "d_models" not in out[f + ".released"] and "d_models" in out[f + ".problem.reset"]
+    assert out[f + ".engine.kept"] == [m for m in out["members.engine"] if m not in CALLERS] and not out[f + ".engine.reset"]
+    assert out[f + ".engine.neither"] == CALLERS
+    assert out[f + ".caller"] == ["tune_waves=caller's", "csr_updates_per_step=caller's", "other_options=kept"]
+    assert set(SURVIVE) - set(CALLERS) <= set(out[f + ".engine.kept"])
+
+
+def test_free_replicas_resets_every_replica_scoped_member_and_nothing_else(record):
+    out, _ = _run(record)
+    f = "free_replicas"
+    assert out[f + ".replica.reset"] == out["members.replica"] and not out[f + ".replica.kept"] and not out[f + ".replica.neither"]
+    assert out[f + ".problem.kept"] == out["members.problem"] and not out[f + ".problem.reset"] and not out[f + ".problem.neither"]
+    assert sorted(out[f + ".released"]) == sorted(_owned("ReplicaState {")) and len(out[f + ".released"]) == 15
+    assert out[f + ".engine.kept"] == out["members.engine"] and not out[f + ".engine.reset"] and not out[f + ".engine.neither"]
+    assert out[f + ".caller"] == ["tune_waves=kept", "csr_updates_per_step=kept", "other_options=kept"]
+
+
+def test_both_resets_release_every_owned_buffer_exactly_once(record):
+    """free_replicas() then free_problem(), as every setter and sga_destroy call them."""
+    out, _ = _run(record)
+    assert out["both.released"] == out["free_replicas.released"] + out["free_problem.released"]
+    assert len(out["both.released"]) == len(set(out["both.released"])) == 38 and "?" not in out["both.released"]
+    assert out["both.problem.reset"] == out["members.problem"] and out["both.replica.reset"] == out["members.replica"]
+    assert out["both.engine.kept"] == out["free_problem.engine.kept"] and out["both.engine.neither"] == CALLERS
+    assert not out["both.engine.reset"] and set(SURVIVE) - set(CALLERS) <= set(out["both.engine.kept"])
+
+
+def test_the_check_would_notice_a_member_left_out(record):
+    """Mode "selfcheck" puts one value member and one buffer back to their filled values after the resets: the report
+    names exactly those two as kept."""
+    out, _ = _run(record, "selfcheck")
+    for f in ("free_problem", "both"):
+        assert out[f + ".problem.kept"] == ["table_scale", "g_rent"] and not out[f + ".problem.neither"]
+        assert out[f + ".problem.reset"] == [m for m in out["members.problem"] if m not in ("table_scale", "g_rent")]
+    assert out["free_replicas.problem.kept"] == out["members.problem"]
+
+
+def test_the_record_under_the_sanitizers(record, tmp_path):
+    """The same stand-alone program built with the address and undefined-behaviour sanitizers: the same report, no finding."""
+    exe = str(tmp_path / "engine_record_san")
+    san = ["-g", "-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=undefined"]
+    subprocess.run([HIPCC] + HOST + san + [PROGRAM, "-o", exe], check=True, capture_output=True)
+    for mode in ((), ("selfcheck",)):
+        assert _run(exe, *mode)[1] == _run(record, *mode)[1]
+
+
