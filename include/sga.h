@@ -80,7 +80,7 @@ typedef struct sga_engine sga_engine;
 int sga_create(int device, sga_engine **out);
 void sga_destroy(sga_engine *e);
 const char *sga_last_error(void);
-int sga_version(void);  /* 2200: the row-shared fields in tiles take a plan of their own, one launch per sweep (csrc/sweep_dense_rs.hip, rs_tile_plan_kernel; no change of interface or results); 2100: sga_set_sequential_windows / sga_get_sequential_windows (SGA_SITE_SEQUENTIAL sweeps in windows, the fields of every replica on the matrix cores; csrc/sweep_dense_seq.hip); 2000: the row-shared windows (option "row_shared") serve SGA_RULE_GLAUBER and SGA_RULE_HEAT_BATH too ("rule=glauber" / "rule=heat-bath" in sga_describe and sga_get_last_kernel; the window sga_autotune picks holds for the rule it was timed under); 1900: options "row_shared_fields" and "row_shared_tile_sites" (row-shared fields in tiles of sites, sign-only rows); 1800: option "row_shared_grid", sga_route_query.rs_grid; 1700: sga_set_csr_shared (one set of CSR rows, many field vectors: every one-wave-per-replica CSR form for such batches), sga_route_query.shared_j on SGA_ROUTE_CSR queries; 1600: sga_set_dense_shared (one coupling matrix, many field vectors; row-shared windows, bit-planes and the matrix-core pass for such batches), sga_route_query.shared_j; 1500: sga_get_scan_summary, and sga_set_dense / sga_set_dense_batch / sga_set_csr / sga_set_csr64 / sga_set_csr_batch refuse a NaN or +-Inf in J or h (SGA_ERR_INVALID, "non-finite"); 1400: option "batch_fixed_point" (fixed-point cached local fields for many-model dense batches); 1300: options "ragged_field_cache" and "clf_fixed_point" together (fixed-point cached local fields for ragged CSR batches); 1200: sga_set_groups_csr (group couplings plus a stored sparse remainder); 1100: option "ragged_field_cache" (cached local fields for ragged CSR batches); 1000: sga_set_groups */
+int sga_version(void);  /* 2300: sga_get_magnetizations / sga_get_overlaps / sga_get_overlaps_with (replica observables on the device: the exact integer product of int8 spin rows on the matrix cores, csrc/observables.hip; read only, no engine state); 2200: the row-shared fields in tiles take a plan of their own, one launch per sweep (csrc/sweep_dense_rs.hip, rs_tile_plan_kernel; no change of interface or results); 2100: sga_set_sequential_windows / sga_get_sequential_windows (SGA_SITE_SEQUENTIAL sweeps in windows, the fields of every replica on the matrix cores; csrc/sweep_dense_seq.hip); 2000: the row-shared windows (option "row_shared") serve SGA_RULE_GLAUBER and SGA_RULE_HEAT_BATH too ("rule=glauber" / "rule=heat-bath" in sga_describe and sga_get_last_kernel; the window sga_autotune picks holds for the rule it was timed under); 1900: options "row_shared_fields" and "row_shared_tile_sites" (row-shared fields in tiles of sites, sign-only rows); 1800: option "row_shared_grid", sga_route_query.rs_grid; 1700: sga_set_csr_shared (one set of CSR rows, many field vectors: every one-wave-per-replica CSR form for such batches), sga_route_query.shared_j on SGA_ROUTE_CSR queries; 1600: sga_set_dense_shared (one coupling matrix, many field vectors; row-shared windows, bit-planes and the matrix-core pass for such batches), sga_route_query.shared_j; 1500: sga_get_scan_summary, and sga_set_dense / sga_set_dense_batch / sga_set_csr / sga_set_csr64 / sga_set_csr_batch refuse a NaN or +-Inf in J or h (SGA_ERR_INVALID, "non-finite"); 1400: option "batch_fixed_point" (fixed-point cached local fields for many-model dense batches); 1300: options "ragged_field_cache" and "clf_fixed_point" together (fixed-point cached local fields for ragged CSR batches); 1200: sga_set_groups_csr (group couplings plus a stored sparse remainder); 1100: option "ragged_field_cache" (cached local fields for ragged CSR batches); 1000: sga_set_groups */
 /* Run on an existing HIP stream (e.g. torch.cuda.current_stream().cuda_stream); NULL = the
  * engine's own stream (default). */
 int sga_set_stream(sga_engine *e, void *hip_stream);
@@ -411,6 +411,43 @@ int sga_get_energies(sga_engine *e, double *out /* [R_local] */);
  * stream: an RCCL all-gather of the energies followed by sga_exchange needs no host synchronisation). */
 int sga_get_energies_async(sga_engine *e, double *out_device /* [R_local] */);
 int sga_get_temperatures(sga_engine *e, double *out /* [R_local] */);
+
+/* ---- replica observables (version >= 2300; csrc/observables.hip) -------------------------------------------------
+ * How the replicas relate to each other, computed where the spins are: one exact integer product Q = A B^T, A the local
+ * replicas' int8 spins [R_local][n] and B a set of int8 configurations [C][n], on the int8 matrix cores (both operands
+ * read straight from their row-major rows, the K range split over workgroups, partial sums joined by int32 atomics:
+ * exact in any order, bit for bit the integer product).  B = A: the overlap matrix n q_ab; B = the best configurations:
+ * distances between solutions, d = (n - Q) / 2; B = rows of the caller's: overlaps against an outside state (a planted
+ * solution, another rank's spins); one row of ones: the magnetisations.
+ *   Pointers: out and cfg may be host or device pointers, as everywhere in this header.  cfg holds int8 values,
+ *   normally +-1; a 0 leaves a site out; nothing is checked, the result is the plain dot product.
+ *   Stream order: the work is enqueued on the engine's stream behind whatever sweep was enqueued before it.  A host out:
+ *   the call returns after the copy has landed; a device out: it returns at once, as sga_get_energies_async does.
+ *   Sites are 0 ... n - 1 of the spin rows; what a row holds past n never enters a sum.
+ *   Ragged batches (sga_set_csr_batch): rows are zero past n_m, so a magnetisation is over the model's own n_m sites and
+ *   a pair of replicas inside a model gets its model's overlap.  A pair ACROSS models gets the dot over the shorter
+ *   model's sites: a number without a meaning, computed and not refused.  cfg rows are [n_max].
+ *   Every kind of problem is served (the spins in HBM are int8 rows for all of them): one dense model, stacked and
+ *   shared batches, CSR with int8 or bit spins in LDS, ragged batches, sga_set_tsp, sga_set_groups with or without a
+ *   remainder.  Sharded engines answer for their local replicas; overlaps across ranks are an all-gather of the spins
+ *   followed by sga_get_overlaps_with.  Range: n <= ~1.3 10^6 spins, so |Q| < 2^31 for every int8 cfg.
+ *   SGA_ERR_INVALID, before anything is enqueued: a NULL engine or out; no problem or no replicas; which outside
+ *   {0, 1}; count < 0, or cfg NULL with count > 0 (count = 0 is a no-op); ld < n; ldq < R_local (sga_get_overlaps) or
+ *   ldq < count (sga_get_overlaps_with).
+ *   Read only: no replica state, cached field, counter, best, window plan or sga_get_last_kernel text changes, and the
+ *   engine keeps no state for these calls (scratch: the staging slots of the single-site operators).  A run with these
+ *   calls interleaved walks the same chain as one without them.
+ * (Reference: core/spin_dynamics.py:90-92, magnetization_history = sum_i s_i per sweep; it has no overlaps.) */
+#define SGA_SPINS_CURRENT 0   /* the replicas' spins, as sga_get_spins returns them   */
+#define SGA_SPINS_BEST    1   /* the best configurations, as sga_get_best returns them */
+/* out[r] = sum_i s_r[i], local replica r (ragged batches: over the model's own n_m sites) */
+int sga_get_magnetizations(sga_engine *e, int which, int32_t *out /* [R_local] */);
+/* out[a * ldq + b] = sum_i A_a[i] B_b[i] over all local replicas a, b; A = which_a, B = which_b */
+int sga_get_overlaps(sga_engine *e, int which_a, int which_b, int32_t *out, int64_t ldq /* >= R_local */);
+/* out[a * ldq + c] = sum_i A_a[i] cfg[c * ld + i] : the local replicas against caller-supplied configurations */
+int sga_get_overlaps_with(sga_engine *e, int which, const int8_t *cfg, int64_t ld /* >= n */, int count,
+                          int32_t *out, int64_t ldq /* >= count */);
+
 int sga_get_spins(sga_engine *e, int r, int8_t *out /* [n]; r<0: all, [R_local][n] */);
 int sga_set_spins(sga_engine *e, int r, const int8_t *s /* recomputes that energy */);
 /* r >= 0: best (energy, spins) seen by local replica r at sweep ends; r < 0: the best over

@@ -17,6 +17,7 @@ J_AUTO, J_F32, J_I8, J_T2 = 0, 1, 2, 3
 SITE_RANDOM, SITE_SEQUENTIAL, SITE_REPLAY = 0, 1, 2
 ARITH_F64, ARITH_F32 = 0, 1
 RULE_METROPOLIS, RULE_GLAUBER, RULE_HEAT_BATH, RULE_WOLFF = 0, 1, 2, 3
+SPINS_CURRENT, SPINS_BEST = 0, 1
 
 _p, _i, _i64, _u64, _u32, _d = C.c_void_p, C.c_int, C.c_int64, C.c_uint64, C.c_uint32, C.c_double
 
@@ -78,6 +79,9 @@ SYMBOLS = [
     ("sga_get_energies", _i, [_p, _p]),
     ("sga_get_energies_async", _i, [_p, _p]),
     ("sga_get_temperatures", _i, [_p, _p]),
+    ("sga_get_magnetizations", _i, [_p, _i, _p]),
+    ("sga_get_overlaps", _i, [_p, _i, _i, _p, _i64]),
+    ("sga_get_overlaps_with", _i, [_p, _i, _p, _i64, _i, _p, _i64]),
     ("sga_get_spins", _i, [_p, _i, _p]),
     ("sga_set_spins", _i, [_p, _i, _p]),
     ("sga_get_best", _i, [_p, _i, C.POINTER(_d), _p, C.POINTER(_i)]),

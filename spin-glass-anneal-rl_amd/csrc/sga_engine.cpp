@@ -347,6 +347,8 @@ extern "C" {
 
 const char *sga_last_error(void) { return g_last_error.c_str(); }
 // The ABI version, one line per step:
+//   2300:    + sga_get_magnetizations / sga_get_overlaps / sga_get_overlaps_with: replica observables as one exact int8
+//            product on the matrix cores (observables.hip); read only, no engine state
 //   2200:    the row-shared fields in tiles take a plan of their own, sorted by (slice of replicas, tile, replica) in one
 //            launch (sweep_dense_rs.hip, rs_tile_plan_kernel); results and interface unchanged
 //   2100:    + sga_set_sequential_windows / sga_get_sequential_windows: SGA_SITE_SEQUENTIAL sweeps in windows, the
@@ -374,7 +376,7 @@ const char *sga_last_error(void) { return g_last_error.c_str(); }
 //   600:     + sga_set_csr_batch / sga_get_batch_model (ragged CSR batches)
 //   round 5: + sga_explain_route / sga_get_route_query, sga_get_last_kernel, sga_get_autotune_table, ladder-local
 //            sga_exchange
-int sga_version(void) { return 2200; }
+int sga_version(void) { return 2300; }
 
 int sga_create(int device, sga_engine **out) {
     if (!out) return fail(SGA_ERR_INVALID, "out is NULL");

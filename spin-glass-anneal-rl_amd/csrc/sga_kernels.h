@@ -599,6 +599,48 @@ hipError_t launch_seq_build_i8(const float *J, long long ldj, int n, int grid_k,
 // decision is metropolis_accept's.  cus: compute units (the K split of the product).
 hipError_t launch_sweep_dense_seq(const SweepArgs &a, const SeqWindows &sq, bool j_is_i8, int cus, hipStream_t st);
 
+// Replica observables (observables.hip; sga_get_magnetizations / sga_get_overlaps / sga_get_overlaps_with): the exact
+// integer product Q = A B^T of two sets of row-major int8 rows over sites 0 ... n - 1, on the int8 matrix cores.  A
+// workgroup takes one tile of OBS_TILE rows of A x OBS_TILE rows of B over one K range; the ranges' partial sums meet
+// in int32 atomics (exact in any order).  The geometry is a pure function of (n, rows_a, rows_b, cus): no device call.
+constexpr int OBS_TILE = 128;    // rows of A, and of B, per workgroup (2 x 2 waves of 64 x 64, as sweep_dense_seq.hip)
+constexpr int OBS_K_GRAIN = 128; // a K range is a multiple of this (four K steps of 32 columns, loaded together)
+constexpr int OBS_K_MIN = 512;   // no K range shorter than this: below it a split buys less than its atomics cost
+struct ObservablesPlan {
+    int tiles_m = 0, tiles_n = 0;  // tiles over the rows of A and of B
+    int ksplit = 0;                // K ranges (1: plain stores, no zeroing of the result)
+    int kchunk = 0;                // columns per K range; range s is [s kchunk, min(n, (s + 1) kchunk))
+};
+// The rule: about two workgroups per compute unit, as far as ranges of at least OBS_K_MIN columns allow.
+inline ObservablesPlan observables_plan(int n, int rows_a, int rows_b, int cus) {
+    ObservablesPlan p;
+    if (n <= 0 || rows_a <= 0 || rows_b <= 0) return p;
+    p.tiles_m = (rows_a + OBS_TILE - 1) / OBS_TILE;
+    p.tiles_n = (rows_b + OBS_TILE - 1) / OBS_TILE;
+    const long long tiles = (long long)p.tiles_m * p.tiles_n;
+    const long long want = (2ll * (cus > 0 ? cus : 1) + tiles - 1) / tiles;
+    const long long most = ((long long)n + OBS_K_MIN - 1) / OBS_K_MIN;
+    const long long s = want < most ? want : most;  // (>= 1)
+    const long long per = ((long long)n + s - 1) / s;
+    p.kchunk = (int)((per + OBS_K_GRAIN - 1) / OBS_K_GRAIN * OBS_K_GRAIN);
+    p.ksplit = (int)(((long long)n + p.kchunk - 1) / p.kchunk);
+    return p;
+}
+struct ObservablesArgs {
+    const int8_t *A;  // [rows_a][lda]
+    const int8_t *B;  // [rows_b][ldb]
+    int *out;         // out[a * ldq + b]; zeroed by the caller where plan.ksplit > 1
+    long long lda, ldb, ldq;
+    int rows_a, rows_b, n;
+    int symmetric;    // A and B are the same rows: only the tiles with a <= b are computed, both halves written
+    ObservablesPlan plan;
+};
+// Rows whose base and stride are multiples of 16 bytes are read 16 bytes per lane; any other operand byte by byte.
+// Columns k >= n never enter the sums, whatever the rows hold there.
+hipError_t launch_observables_product(const ObservablesArgs &a, hipStream_t st);
+// out[r] = sum_{i < n} S[r][i]: one workgroup per row
+hipError_t launch_observables_row_sums(const int8_t *S, long long ld, int n, int R, int *out, hipStream_t st);
+
 // operator-form PT exchange (cuda_kernels.py:415-443): decide sequentially, then permute rows
 hipError_t launch_op_exchange(float *spins, float *tmp_rows, float *energies, const float *temps,
                               const float *u, int32_t *src_of_pos, int *n_accepted,

@@ -582,6 +582,99 @@ int sga_get_energies_async(sga_engine *e, double *out_device) {
     return SGA_OK;
 }
 
+// ---- replica observables (observables.hip) --------------------------------------------------
+// Read only, and no state of their own: the result of a host `out` goes through the point_out slot, a host `cfg`
+// through point_sites (both grow-only, so the steady-state call allocates nothing), and nothing else of the engine is
+// written -- not the spins, fields, counters, bests, window plan or last_kernel.
+namespace {
+const int8_t *observed_rows(const sga_engine *e, int which) { return which == SGA_SPINS_BEST ? e->best_spins : e->spins; }
+bool observed_which(int which) { return which == SGA_SPINS_CURRENT || which == SGA_SPINS_BEST; }
+const char *observables_ready(const sga_engine *e) {
+    if (e->n <= 0) return "no couplings set";
+    if (e->R <= 0 || !e->spins || !e->best_spins) return "no replicas";
+    return nullptr;
+}
+
+// out[a * ldq + b] = sum_{i < n} A_a[i] B_b[i], A the local replicas' rows; B on the device.  Every argument is checked
+// by the caller; the work goes on the engine's stream, and a host `out` is waited for.
+int observables_product(sga_engine *e, const int8_t *A, const int8_t *B, long long ldb, int rows_b, bool symmetric,
+                        int32_t *out, int64_t ldq) {
+    sga::ObservablesArgs a{};
+    a.A = A, a.B = B;
+    a.lda = e->sstride, a.ldb = ldb;
+    a.rows_a = e->R, a.rows_b = rows_b, a.n = e->n;
+    a.symmetric = symmetric ? 1 : 0;
+    a.plan = sga::observables_plan(e->n, e->R, rows_b, e->cus);
+    const bool on_device = is_device_ptr(out);
+    if (on_device) {
+        a.out = out, a.ldq = ldq;
+    } else {
+        HIPCHK(e->point_out.reserve((size_t)e->R * (size_t)rows_b * sizeof(int32_t)));
+        a.out = static_cast<int *>(e->point_out.ptr), a.ldq = rows_b;
+    }
+    if (a.plan.ksplit > 1)  // the K ranges add into the result
+        HIPCHK(hipMemset2DAsync(a.out, (size_t)a.ldq * sizeof(int32_t), 0, (size_t)rows_b * sizeof(int32_t), (size_t)e->R, e->stream));
+    HIPCHK(sga::launch_observables_product(a, e->stream));
+    if (!on_device) {
+        HIPCHK(hipMemcpy2DAsync(out, (size_t)ldq * sizeof(int32_t), a.out, (size_t)rows_b * sizeof(int32_t),
+                                (size_t)rows_b * sizeof(int32_t), (size_t)e->R, hipMemcpyDeviceToHost, e->stream));
+        HIPCHK(hipStreamSynchronize(e->stream));
+    }
+    return SGA_OK;
+}
+}  // namespace
+
+int sga_get_magnetizations(sga_engine *e, int which, int32_t *out) {
+    if (!e || !out) return fail(SGA_ERR_INVALID, "NULL argument");
+    if (const char *why = observables_ready(e)) return fail(SGA_ERR_INVALID, why);
+    if (!observed_which(which)) return fail(SGA_ERR_INVALID, "which must be SGA_SPINS_CURRENT or SGA_SPINS_BEST");
+    HIPCHK(hipSetDevice(e->device));
+    const bool on_device = is_device_ptr(out);
+    int *d = out;
+    if (!on_device) {
+        HIPCHK(e->point_out.reserve((size_t)e->R * sizeof(int32_t)));
+        d = static_cast<int *>(e->point_out.ptr);
+    }
+    HIPCHK(sga::launch_observables_row_sums(observed_rows(e, which), e->sstride, e->n, e->R, d, e->stream));
+    if (!on_device) {
+        HIPCHK(hipMemcpyAsync(out, d, (size_t)e->R * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
+        HIPCHK(hipStreamSynchronize(e->stream));
+    }
+    return SGA_OK;
+}
+
+int sga_get_overlaps(sga_engine *e, int which_a, int which_b, int32_t *out, int64_t ldq) {
+    if (!e || !out) return fail(SGA_ERR_INVALID, "NULL argument");
+    if (const char *why = observables_ready(e)) return fail(SGA_ERR_INVALID, why);
+    if (!observed_which(which_a) || !observed_which(which_b))
+        return fail(SGA_ERR_INVALID, "which_a / which_b must be SGA_SPINS_CURRENT or SGA_SPINS_BEST");
+    if (ldq < e->R) return fail(SGA_ERR_INVALID, "ldq is smaller than the number of local replicas");
+    HIPCHK(hipSetDevice(e->device));
+    return observables_product(e, observed_rows(e, which_a), observed_rows(e, which_b), e->sstride, e->R, which_a == which_b, out, ldq);
+}
+
+int sga_get_overlaps_with(sga_engine *e, int which, const int8_t *cfg, int64_t ld, int count, int32_t *out, int64_t ldq) {
+    if (!e || !out) return fail(SGA_ERR_INVALID, "NULL argument");
+    if (const char *why = observables_ready(e)) return fail(SGA_ERR_INVALID, why);
+    if (!observed_which(which)) return fail(SGA_ERR_INVALID, "which must be SGA_SPINS_CURRENT or SGA_SPINS_BEST");
+    if (count < 0) return fail(SGA_ERR_INVALID, "count is negative");
+    if (count > 0 && !cfg) return fail(SGA_ERR_INVALID, "cfg is NULL");
+    if (ld < e->n) return fail(SGA_ERR_INVALID, "ld is smaller than n");
+    if (ldq < count) return fail(SGA_ERR_INVALID, "ldq is smaller than count");
+    if (count == 0) return SGA_OK;
+    HIPCHK(hipSetDevice(e->device));
+    const int8_t *B = cfg;
+    long long ldb = ld;
+    if (!is_device_ptr(cfg)) {  // staged with rows 16 bytes apart: the product's wide loads (the pad is masked, not read as data)
+        ldb = ((long long)e->n + 15) / 16 * 16;
+        HIPCHK(e->point_sites.reserve((size_t)count * (size_t)ldb));
+        HIPCHK(hipMemcpy2DAsync(e->point_sites.ptr, (size_t)ldb, cfg, (size_t)ld, (size_t)e->n, (size_t)count, hipMemcpyHostToDevice,
+                                e->stream));
+        B = static_cast<const int8_t *>(e->point_sites.ptr);
+    }
+    return observables_product(e, observed_rows(e, which), B, ldb, count, false, out, ldq);
+}
+
 int sga_get_route_query(sga_engine *e, sga_route_query *out) {
     if (!e || !out) return fail(SGA_ERR_INVALID, "NULL argument");
     if (e->n <= 0) return fail(SGA_ERR_INVALID, "no couplings set");

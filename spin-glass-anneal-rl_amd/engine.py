@@ -673,6 +673,112 @@ class AnnealEngine:
                 "sga_get_slot_map")
         return out
 
+    # ------------------------------------------------------------------ replica observables
+    # One exact integer product on the matrix cores (csrc/observables.hip): read only, stream ordered behind the sweeps.
+    _WHICH = {"current": N.SPINS_CURRENT, "best": N.SPINS_BEST, N.SPINS_CURRENT: N.SPINS_CURRENT, N.SPINS_BEST: N.SPINS_BEST}
+
+    def _which(self, which) -> int:
+        if isinstance(which, (str, int)) and which in self._WHICH:
+            return self._WHICH[which]
+        raise AnnealingError(f'which must be "current" or "best", not {which!r}')
+
+    def _observable_out(self, out, cols: int):
+        """(pointer, ldq, result, device?) for an [R, cols] int32 result: a fresh numpy array, or the caller's CUDA
+        tensor (rows may be strided: ldq = out.stride(0)) -- ordered as _buf(..., ordered=True) orders an input."""
+        if out is None:
+            res = np.zeros((self.R, cols), np.int32)
+            return res.ctypes.data_as(C.c_void_p), cols, res, False
+        if not _is_tensor(out) or not out.is_cuda or out.dtype != torch.int32 or tuple(out.shape) != (self.R, cols):
+            raise AnnealingError(f"out must be an int32 CUDA tensor of shape [{self.R}, {cols}]")
+        ldq = int(out.stride(0)) if self.R > 1 else cols  # (one row: its stride is never used)
+        if (cols > 1 and out.stride(1) != 1) or ldq < cols:
+            raise AnnealingError("out must have unit column stride and rows that do not overlap")
+        if not self.shares_torch_stream():
+            _producer_done(out)
+        return C.c_void_p(out.data_ptr()), ldq, out, True
+
+    def _observable_done(self, device: bool):
+        """A device result is only enqueued (as sga_get_energies_async): torch work on another stream waits here."""
+        if device and not self.shares_torch_stream():
+            N.check(self._lib.sga_snapshot(self._h, None, None, None), "sga_snapshot")  # nothing asked for: the stream's wait
+
+    def magnetizations(self, which="current") -> np.ndarray:
+        """int32 [R]: sum_i s_r[i] of every local replica (sga_get_magnetizations; ragged batches: over the model's own
+        sites).  which: "current" | "best"."""
+        w = self._which(which)
+        out = np.zeros(self.R, np.int32)
+        N.check(self._lib.sga_get_magnetizations(self._h, w, out.ctypes.data_as(C.c_void_p)), "sga_get_magnetizations")
+        return out
+
+    def overlaps(self, which_a="current", which_b=None, out=None):
+        """int32 [R, R]: Q[a, b] = sum_i A_a[i] B_b[i] over the local replicas (sga_get_overlaps), A = which_a and B =
+        which_b ("current" | "best"; which_b None: which_a) -- n times the overlap q_ab.  out: an optional int32 CUDA
+        tensor [R, R] (rows may be strided) that receives the result on the device; with shares_torch_stream() the call
+        is only enqueued.  Ragged batches: a pair across models is the dot over the shorter model's sites, meaningless."""
+        wa = self._which(which_a)
+        wb = wa if which_b is None else self._which(which_b)
+        ptr, ldq, res, dev = self._observable_out(out, self.R)
+        N.check(self._lib.sga_get_overlaps(self._h, wa, wb, ptr, ldq), "sga_get_overlaps")
+        self._observable_done(dev)
+        return res
+
+    def overlaps_with(self, configs, which="current", out=None):
+        """int32 [R, C]: the local replicas against C configurations of the caller's (sga_get_overlaps_with): configs a
+        numpy or torch int8 array [C, n] (a device tensor is read in place, rows may be strided), normally +-1, a 0
+        leaves a site out.  One row of ones gives the magnetisations.  out: as in overlaps()."""
+        w = self._which(which)
+        if _is_tensor(configs):
+            t = configs.detach()
+            if t.dim() != 2 or t.shape[1] != self.n:
+                raise AnnealingError("configs must be [C, n] int8")
+            if t.dtype != torch.int8:
+                t = t.to(torch.int8)
+            if (self.n > 1 and t.stride(1) != 1) or (t.shape[0] > 1 and t.stride(0) < self.n):
+                t = t.contiguous()  # (anything else: rows of a wider tensor pass as they lie, ld = stride(0))
+            if not (t.is_cuda and self.shares_torch_stream()):
+                _producer_done(t)
+            count, ld, cp, keep = int(t.shape[0]), (int(t.stride(0)) if t.shape[0] > 1 else self.n), C.c_void_p(t.data_ptr()), t
+        else:
+            a = np.asarray(configs)
+            if a.ndim != 2 or a.shape[1] != self.n:
+                raise AnnealingError("configs must be [C, n] int8")
+            if a.dtype != np.int8 or a.strides[1] != 1 or a.strides[0] < self.n:  # (rows of a wider array pass as they lie)
+                a = np.ascontiguousarray(a, dtype=np.int8)
+            count, ld, cp, keep = int(a.shape[0]), (int(a.strides[0]) if a.shape[0] > 1 else self.n), C.c_void_p(a.ctypes.data), a
+        ptr, ldq, res, dev = self._observable_out(out, count)
+        N.check(self._lib.sga_get_overlaps_with(self._h, w, cp, ld, count, ptr, ldq), "sga_get_overlaps_with")
+        self._observable_done(dev)
+        if dev:
+            self._pending = (keep, res)  # a converted device operand stays alive while the kernel is queued
+        return res
+
+    def hamming(self, which_a="current", which_b=None) -> np.ndarray:
+        """int32 [R, R]: Hamming distances (n_r - Q) / 2 between the configurations of overlaps(which_a, which_b), n_r the
+        ROW replica's model size on ragged engines (a pair across models is meaningless there)."""
+        Q = self.overlaps(which_a, which_b)
+        n_r = np.asarray([self._replica_n(r) for r in range(self.R)], np.int32)
+        return ((n_r[:, None] - Q) // 2).astype(np.int32)
+
+    def distinct_best(self, k: int, min_hamming: int = 1, up_to_global_flip: bool = False):
+        """Up to k best configurations that are genuinely different: [(replica, energy, spins)].  The replicas are walked
+        by best energy ascending (ties by replica index); one is kept when its best configuration is at least
+        min_hamming away from every one kept so far -- with up_to_global_flip the distance is (n - |Q|) / 2, for h = 0
+        where s and -s are one solution.  Batch engines: distances inside one model only (another model's solutions
+        never exclude one).  Costs one overlaps("best", "best"), the best energies (read replica by replica: sga_get_best
+        has no bulk form) and one best(r) read per configuration returned."""
+        Q = self.overlaps("best", "best").astype(np.int64)
+        energy = np.asarray([self.best(r, with_spins=False)[0] for r in range(self.R)]) if self.R else np.zeros(0)
+        model = [(self.replica0 + r) // max(self.R_global // max(self.n_models, 1), 1) for r in range(self.R)]
+        kept = []
+        for r in sorted(range(self.R), key=lambda i: (energy[i], i)):
+            if len(kept) >= int(k):
+                break
+            n_r = self._replica_n(r)
+            q = np.abs(Q[r]) if up_to_global_flip else Q[r]
+            if all(model[j] != model[r] or (n_r - q[j]) // 2 >= int(min_hamming) for j in kept):
+                kept.append(r)
+        return [(r, float(energy[r]), self.best(r)[1]) for r in kept]
+
     def route_query(self):
         """The query the engine itself poses to the form selection (sga_get_route_query)."""
         q = N.RouteQuery()

@@ -190,6 +190,8 @@ class ParallelTempering:
             self.exchange_attempts = att[:R - 1].astype(np.float64)
             self.exchange_accepts = acc[:R - 1].astype(np.float64)
             self.final_spins = eng.spins()[slot_to_rep]
+            # the final overlap matrix, formed where the spins are (sga_get_overlaps), in slot order like final_spins
+            self._final_overlaps = eng.overlaps()[np.ix_(slot_to_rep, slot_to_rep)].astype(np.float64) / n
         self.slot_acceptance = acc_slot / np.maximum(att_slot, 1)
         total_time = time.time() - t_start
         return AnnealingResult(
@@ -203,6 +205,14 @@ class ParallelTempering:
     def _event(self, sweep: int) -> bool:
         c = self.config
         return (sweep % c.exchange_interval == 0 and sweep > 0) or sweep % c.record_interval == 0
+
+    def replica_overlaps(self) -> np.ndarray:
+        """q_ab = (1/n) sum_i s_i^a s_i^b of the final configurations as float64 [R, R], in slot (temperature) order:
+        entry [i, j] relates the replicas that ended at temperatures[i] and temperatures[j].  After run()."""
+        q = getattr(self, "_final_overlaps", None)
+        if q is None:
+            raise ConfigurationError("replica_overlaps() needs a finished run()")
+        return q.copy()
 
     def get_exchange_rates(self) -> np.ndarray:
         with np.errstate(divide="ignore", invalid="ignore"):
