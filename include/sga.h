@@ -582,6 +582,22 @@ int sga_set_field_cache(sga_engine *e, int mode);
  * site mode no more than the rule).  The setting is not part of sga_export_state. */
 int sga_set_sequential_windows(sga_engine *e, int W);
 int sga_get_sequential_windows(sga_engine *e, int *W);
+/* Replica groups (version >= 2400; csrc/sweep_dense_rs.hip): replicas are independent inside a sweep, so the row-shared
+ * sweep over the tile plan (its fields in tiles of sites, option "row_shared_fields") cuts them into contiguous groups
+ * and runs each group's whole sweep -- plan, fields and chain per window, best tracking -- on a stream of its own: one
+ * group's chain runs beside another's fields.  Every group is forked from the engine's stream when a launch starts and
+ * joined into it before the launch returns, so whatever follows on that stream sees all replicas done.  No result
+ * changes: a replica's chain is the one-group chain, bit for bit.
+ * g = 0 (default): the count is the rule's -- two groups where each gets at least 256 replicas, else one (four measured
+ * slower than two and are only ever forced).
+ * g = 1 | 2 | 4: that count wherever the form admits groups (fewer where R gives fewer ranges: every inner boundary is a
+ * multiple of 32).  Any other value: SGA_ERR_INVALID.  Read at every sga_sweep; kept across sga_set_* calls; not part of
+ * sga_export_state.  One group runs wherever the tile plan does not (the per-site fields kernel, the sequential windows,
+ * every other sweep form) and while an energy trace is asked for.  sga_describe and sga_get_last_kernel end in
+ * " groups=G" where more than one group runs -- at one they are what they were -- and sga_describe in " groups=no(why)"
+ * where g > 1 was asked for and one runs. */
+int sga_set_replica_groups(sga_engine *e, int g);
+int sga_get_replica_groups(sga_engine *e, int *g);
 /* Form-selection options of ONE engine -- the A/B switches of the measurements and what the parity tests use to
  * force a kernel form -- by name.  None changes a result: every form walks the same chain.  The
  * environment is read once, in sga_create, for the defaults (variable in brackets); afterwards only these calls

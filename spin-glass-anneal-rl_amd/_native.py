@@ -105,6 +105,8 @@ SYMBOLS = [
     ("sga_set_field_cache", _i, [_p, _i]),
     ("sga_set_sequential_windows", _i, [_p, _i]),
     ("sga_get_sequential_windows", _i, [_p, C.POINTER(_i)]),
+    ("sga_set_replica_groups", _i, [_p, _i]),
+    ("sga_get_replica_groups", _i, [_p, C.POINTER(_i)]),
     ("sga_set_option", _i, [_p, C.c_char_p, _i64]),
     ("sga_get_option", _i, [_p, C.c_char_p, C.POINTER(_i64)]),
     ("sga_option_name", _i, [_i, C.c_char_p, _i]),

@@ -347,6 +347,9 @@ extern "C" {
 
 const char *sga_last_error(void) { return g_last_error.c_str(); }
 // The ABI version, one line per step:
+//   2400:    + sga_set_replica_groups / sga_get_replica_groups: the row-shared sweep over the tile plan runs contiguous
+//            groups of replicas as pipelines of their own, a stream each (sweep_dense_rs.hip; " groups=G" behind
+//            sga_describe and sga_get_last_kernel where more than one runs); results unchanged
 //   2300:    + sga_get_magnetizations / sga_get_overlaps / sga_get_overlaps_with: replica observables as one exact int8
 //            product on the matrix cores (observables.hip); read only, no engine state
 //   2200:    the row-shared fields in tiles take a plan of their own, sorted by (slice of replicas, tile, replica) in one
@@ -376,7 +379,7 @@ const char *sga_last_error(void) { return g_last_error.c_str(); }
 //   600:     + sga_set_csr_batch / sga_get_batch_model (ragged CSR batches)
 //   round 5: + sga_explain_route / sga_get_route_query, sga_get_last_kernel, sga_get_autotune_table, ladder-local
 //            sga_exchange
-int sga_version(void) { return 2300; }
+int sga_version(void) { return 2400; }
 
 int sga_create(int device, sga_engine **out) {
     if (!out) return fail(SGA_ERR_INVALID, "out is NULL");
@@ -441,6 +444,11 @@ void sga_destroy(sga_engine *e) {
     if (e->fork_ev) (void)hipEventDestroy(e->fork_ev);
     if (e->join_ev) (void)hipEventDestroy(e->join_ev);
     if (e->aux_stream) (void)hipStreamDestroy(e->aux_stream);
+    if (e->win.run.fork) (void)hipEventDestroy(e->win.run.fork);
+    for (int g = 0; g < sga::RS_MAX_GROUPS - 1; ++g) {  // the replica groups' (sga_windows.cpp, ensure_group_run)
+        if (e->win.run.join[g]) (void)hipEventDestroy(e->win.run.join[g]);
+        if (e->win.run.stream[g]) (void)hipStreamDestroy(e->win.run.stream[g]);
+    }
     if (e->own_stream) (void)hipStreamDestroy(e->own_stream);
     delete e;
 }
@@ -542,6 +550,20 @@ int sga_set_sequential_windows(sga_engine *e, int W) {
     if (W != 0 && W != 256 && W != 512 && W != 1024)
         return fail(SGA_ERR_INVALID, "sequential windows: W must be 0 (off), 256, 512 or 1024");
     e->win.seq_w = W;
+    return SGA_OK;
+}
+
+int sga_set_replica_groups(sga_engine *e, int g) {
+    if (!e) return fail(SGA_ERR_INVALID, "engine is NULL");
+    if (g != 0 && g != 1 && g != 2 && g != 4)
+        return fail(SGA_ERR_INVALID, "replica groups: g must be 0 (the rule's choice), 1, 2 or 4");
+    e->win.groups = g;
+    return SGA_OK;
+}
+
+int sga_get_replica_groups(sga_engine *e, int *g) {
+    if (!e || !g) return fail(SGA_ERR_INVALID, "engine or output is NULL");
+    *g = e->win.groups;
     return SGA_OK;
 }
 
@@ -777,6 +799,7 @@ struct SweepPlan {  // what holds for every launch of a call
     bool mixed = false;         // ... and the others beside them on the row kernels, second stream
     int rs_w = 0;               // row-shared window (0: not this form)
     sga::RowSharedTiles rs_tiles{};  // its fields kernel: tiles of S sites (S = 0: one workgroup per site)
+    int rs_groups = 1;          // its replica groups, a stream each (1: every launch on the engine's stream)
     sga::SeqWindows seq{};      // sequential windows (W = 0: not this form)
 };
 
@@ -1018,7 +1041,7 @@ int plan_sweep(sga_engine *e, const SweepCall &c, SweepPlan &p) {
     if (!clf && !p.exact_mode) {  // (exact_mode: the Wolff rule too)
         const bool untraced = !c.acc.ptr && !c.dE.ptr;
         plan_windows(e, untraced && c.site_mode == SGA_SITE_RANDOM && c.arith == SGA_ARITH_F64,
-                     untraced && c.site_mode == SGA_SITE_SEQUENTIAL, p.rs_w, p.rs_tiles, p.seq);
+                     untraced && c.site_mode == SGA_SITE_SEQUENTIAL, c.etrace.ptr != nullptr, p.rs_w, p.rs_tiles, p.rs_groups, p.seq);
     }
     return SGA_OK;
 }
@@ -1080,7 +1103,10 @@ hipError_t launch_sweep(sga_engine *e, const SweepPlan &p, sga::SweepArgs a, hip
     if (e->tsp) return sga::launch_sweep_tsp(a, e->tsp_args, e->tsp_waves, e->tsp_passes, st);
     if (e->csr) return sga::launch_sweep_csr(a, e->waves, st);
     if (p.seq.W) return sga::launch_sweep_dense_seq(a, p.seq, e->want_i8, e->cus, st);
-    if (p.rs_w) return sga::launch_sweep_dense_rs(a, e->win.rs, e->want_i8, st, e->win.rs_grid, p.rs_tiles);
+    if (p.rs_w) {
+        e->win.run.G = p.rs_groups;
+        return sga::launch_sweep_dense_rs(a, e->win.rs, e->want_i8, st, e->win.rs_grid, p.rs_tiles, p.rs_groups > 1 ? &e->win.run : nullptr);
+    }
     return launch_dense_rows(e, a, st);
 }
 

@@ -377,6 +377,9 @@ int row_shared_window(const sga_engine *e, bool lean);
 int row_shared_form_planes(const sga_engine *e, int *grid);
 // the tiles of its fields kernel (option "row_shared_fields"); S = 0: the per-site kernel, *why the reason
 sga::RowSharedTiles row_shared_tiles(const sga_engine *e, const char **why);
+// the replica groups of a row-shared sweep of window rs_w over `tiles` (sga_set_replica_groups, or the rule's count); one
+// wherever the form admits none, *why the reason where more were asked for
+int replica_groups(const sga_engine *e, int rs_w, const sga::RowSharedTiles &tiles, bool energy_trace, const char **why);
 // the sequential windows (sga_set_sequential_windows) as a sequential, untraced sweep of this engine would run them:
 // W = 0 where the row-per-proposal kernel runs (base is left null: the scratch is the sweep's)
 sga::SeqWindows sequential_windows(const sga_engine *e);
@@ -384,7 +387,9 @@ sga::SeqWindows sequential_windows(const sga_engine *e);
 // take them.  In this order: the row-shared scratch (and, once per problem, the planes), the tile kernel's LDS request,
 // the sequential scratch and int8 copy.  Every failure leaves the row-per-proposal kernel; a refused LDS request and a
 // failed int8 copy are remembered for the problem.
-void plan_windows(sga_engine *e, bool lean_call, bool sequential_call, int &rs_w, sga::RowSharedTiles &rs_tiles, sga::SeqWindows &seq);
+// rs_groups: the replica groups the row-shared launch runs (their streams and events made here, once per engine).
+void plan_windows(sga_engine *e, bool lean_call, bool sequential_call, bool energy_trace, int &rs_w, sga::RowSharedTiles &rs_tiles,
+                  int &rs_groups, sga::SeqWindows &seq);
 // ---- sga_problem.cpp
 bool csr_rows_medium(const sga_engine *e);
 int csr_updates_per_step(const sga_engine *e);

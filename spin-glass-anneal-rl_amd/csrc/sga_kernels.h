@@ -563,6 +563,89 @@ inline RowSharedTilePlan row_shared_tile_plan(int n, int W, int S, int R) {
         }
     return t;
 }
+// Replica groups (launch_sweep_dense_rs over the tile plan): replicas are independent inside a sweep, so contiguous ranges
+// of them run the whole sweep -- plan, (fields, chain) per window, best tracking -- as engines of their own on streams of
+// their own: the chain of one group fills the SIMD slots beside the fields of another, no kernel waits on another group,
+// and a replica's chain is the one-group chain (every launch of a group takes the group's own SweepArgs and plan view;
+// the device code knows nothing of groups).  The rule: (R, G asked for) -> at most G ascending, disjoint, non-empty ranges
+// [begin[g], begin[g + 1]) that cover [0, R); every inner boundary is a multiple of 32, the largest slice of the tile
+// plan, so that no slice straddles two groups.  R <= 32: one group.
+constexpr int RS_MAX_GROUPS = 4;  // with the caller's stream: within the four hardware queues a process gets by default
+struct RowSharedGroups {
+    int G = 1;
+    int begin[RS_MAX_GROUPS + 1] = {0, 0, 0, 0, 0};
+};
+inline RowSharedGroups row_shared_groups(int R, int G) {
+    RowSharedGroups g;
+    g.begin[1] = R > 0 ? R : 0;
+    if (R <= 32 || G <= 1) return g;
+    const int slices = (R + 31) / 32;
+    g.G = G > RS_MAX_GROUPS ? RS_MAX_GROUPS : G;
+    if (g.G > slices) g.G = slices;
+    for (int i = 1; i < g.G; ++i) g.begin[i] = 32 * (int)((long long)slices * i / g.G);
+    g.begin[g.G] = R;
+    return g;
+}
+// What a group's view of the plan's scratch starts at, in elements of each array (RowSharedPlan): ent, base and bits are
+// per replica; cnt is carved by the by-site plan's own unit, n words per window and group of 2^row_shared_log_group
+// replicas -- the share a one-group engine of R_g replicas would have allocated, inside which row_shared_tile_plan finds
+// room for its run starts (row_shared_tile_plan_runs_fit asks exactly that of R_g).
+struct RowSharedGroupView {
+    long long cnt = 0, ent = 0, base = 0, bits = 0;
+    int n_groups = 0;  // plan groups of the view: ceil(R_g / 2^log_rg)
+};
+inline RowSharedGroupView row_shared_group_view(int n, int W, const RowSharedGroups &g, int i) {
+    const int l = row_shared_log_group(n, W);
+    const long long nwin = (n + W - 1) / W;
+    RowSharedGroupView v;
+    long long before = 0;
+    for (int j = 0; j < i; ++j) before += ((long long)(g.begin[j + 1] - g.begin[j]) + (1ll << l) - 1) >> l;
+    v.cnt = nwin * before * n;
+    v.ent = (long long)g.begin[i] * n;
+    v.base = (long long)g.begin[i] * W;
+    v.bits = (long long)g.begin[i] * row_shared_nw32(n);
+    v.n_groups = (int)(((long long)(g.begin[i + 1] - g.begin[i]) + (1ll << l) - 1) >> l);
+    return v;
+}
+// Whether G groups can run: every group's tile plan exists for its R_g (its run starts inside its share of cnt), and the
+// shares together stay inside the allocation of the R replicas (beyond 32 windows a plan group is more than 32 replicas
+// and the shares of ranges cut at multiples of 32 may round up past it).  Else: one group.
+inline bool row_shared_groups_fit(int n, int W, int S, int R, const RowSharedGroups &g) {
+    if (g.G <= 1) return true;
+    if (n <= 0 || W <= 0 || S <= 0) return false;
+    const int l = row_shared_log_group(n, W);
+    long long shares = 0;
+    for (int i = 0; i < g.G; ++i) {
+        const int Rg = g.begin[i + 1] - g.begin[i];
+        if (Rg <= 0 || row_shared_tile_plan(n, W, S, Rg).rg <= 0) return false;
+        shares += ((long long)Rg + (1ll << l) - 1) >> l;
+    }
+    return shares <= (((long long)R + (1ll << l) - 1) >> l);
+}
+// The default count: the largest of RS_DEFAULT_MAX_GROUPS, ..., 2, 1 that leaves every group at least RS_GROUP_MIN_REPLICAS
+// replicas.  Both from measurements at n = 10 000, W = 1024 over 64 ... 2048 replicas: two groups win from
+// 2 x 256 replicas and are level at 2 x 128; below, the tile kernel's fixed cost per launch -- a tile's rows, the prefix
+// over the runs -- outweighs what the overlap saves.  Four groups lost to two at every count measured (groups of 16 to 512
+// replicas): a CU holds one workgroup of the tile kernel (its LDS), so the fields launches of the groups queue behind each
+// other and every chain waits for its own; four stay behind the setter.
+constexpr int RS_GROUP_MIN_REPLICAS = 256;
+constexpr int RS_DEFAULT_MAX_GROUPS = 2;
+inline int row_shared_default_groups(int R) {
+    for (int G = RS_DEFAULT_MAX_GROUPS; G > 1; G >>= 1) {
+        const RowSharedGroups g = row_shared_groups(R, G);
+        bool ok = g.G == G;
+        for (int i = 0; i < g.G; ++i) ok = ok && g.begin[i + 1] - g.begin[i] >= RS_GROUP_MIN_REPLICAS;
+        if (ok) return G;
+    }
+    return 1;
+}
+// The streams and events of a grouped launch (the engine's: made once, destroyed with it): group 0 runs on the launch's
+// stream, group g > 0 on stream[g - 1]; one fork at the start of the call, one join per group at its end.
+struct RowSharedGroupRun {
+    int G = 1;  // groups asked of row_shared_groups (the launch refuses a count that does not fit)
+    hipStream_t stream[RS_MAX_GROUPS - 1] = {nullptr, nullptr, nullptr};
+    hipEvent_t fork = nullptr, join[RS_MAX_GROUPS - 1] = {nullptr, nullptr, nullptr};
+};
 // asks the runtime for the tile kernel's LDS (once per instantiation and size): an error where it is refused
 hipError_t row_shared_tiles_prepare(int planes, bool ones, size_t lds_bytes);
 // one pass over J: jp and jabs of every row (the first time the form is prepared for a problem); grid_k: the planes
@@ -575,8 +658,11 @@ hipError_t launch_rs_build_planes(const void *J, bool j_is_i8, long long ldj, in
 // "rule=heat-bath" in the kernel note); Wolff is an error.
 // grid: 0 the integer form; else 1 + k, the GRID instantiations (J on the grid 2^-k, any h: the general fp64 rule).
 // tiles.S > 0 (with resident planes): the fields by rs_fields_tiles_kernel in tiles of S sites.
+// run with G > 1: the replicas in row_shared_groups(a.R, G), a stream each, forked from st at the start and joined into
+// it at the end (over the tile plan, without an energy trace, where row_shared_groups_fit: anything else is an error;
+// " groups=G" behind the kernel note).  Null or G = 1: every launch on st, as ever.
 hipError_t launch_sweep_dense_rs(const SweepArgs &a, const RowSharedPlan &p, bool j_is_i8, hipStream_t st, int grid = 0,
-                                 RowSharedTiles tiles = RowSharedTiles{});
+                                 RowSharedTiles tiles = RowSharedTiles{}, const RowSharedGroupRun *run = nullptr);
 
 // Sequential windows (sweep_dense_seq.hip, sga_set_sequential_windows): SGA_SITE_SEQUENTIAL sweeps in windows of W
 // consecutive sites -- per window one product on the matrix cores (the window-start row sums of every replica), then

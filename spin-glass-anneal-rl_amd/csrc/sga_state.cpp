@@ -521,6 +521,20 @@ int sga_describe(sga_engine *e, char *buf, int buflen) {
             std::snprintf(tmp + std::strlen(tmp), sizeof(tmp) - std::strlen(tmp), " cached-batch(models=%d scale=%d)", e->n_models,
                           e->clf_scale);
     }
+    // Replica groups of the row-shared sweep (sga_set_replica_groups), behind everything else: the count where more than one
+    // runs; where the caller asked for more and the form admits none, why.  One group by the rule: the line as it was.
+    if (e->R > 0) {
+        int rw = 0;
+        sga::RowSharedTiles t{};
+        if (!e->csr && !e->implicit() && e->field_cache == SGA_FIELD_CACHE_OFF && (rw = row_shared_window(e, true)) > 0 && e->win.jp) {
+            t = row_shared_tiles(e, nullptr);
+            if (t.S > 0 && sga::row_shared_tile_plan(e->n, rw, t.S, e->R).rg == 0) t = sga::RowSharedTiles{};  // (as plan_windows)
+        }
+        const char *why = nullptr;
+        const int G = replica_groups(e, rw, t, false, &why);
+        if (G > 1) std::snprintf(tmp + std::strlen(tmp), sizeof(tmp) - std::strlen(tmp), " groups=%d", G);
+        else if (why && e->win.groups > 1) std::snprintf(tmp + std::strlen(tmp), sizeof(tmp) - std::strlen(tmp), " groups=no(%s)", why);
+    }
     std::snprintf(buf, (size_t)buflen, "%s", tmp);
     return SGA_OK;
 }

@@ -76,6 +76,21 @@ sga::RowSharedTiles tiles(const WindowTraits &t, const char **why) {
     return s;
 }
 
+int groups(const WindowTraits &t, int rs_w, const sga::RowSharedTiles &tiles, bool energy_trace, const char **why) {
+    const char *dummy;
+    if (!why) why = &dummy;
+    *why = nullptr;
+    const int asked = t.groups > 0 ? t.groups : sga::row_shared_default_groups(t.R);
+    if (asked <= 1) return 1;
+    if (rs_w <= 0) return (*why = "not the row-shared windows"), 1;
+    if (tiles.S <= 0) return (*why = "the per-site fields kernel: its plan orders the entries across all replicas"), 1;
+    if (energy_trace) return (*why = "an energy trace, strided by all replicas"), 1;
+    const sga::RowSharedGroups g = sga::row_shared_groups(t.R, asked);
+    if (g.G <= 1) return (*why = "32 replicas or fewer"), 1;
+    if (!sga::row_shared_groups_fit(t.n, rs_w, tiles.S, t.R, g)) return (*why = "a group's tile plan does not fit its share of the scratch"), 1;
+    return g.G;
+}
+
 }  // namespace sga_windows
 
 #ifndef SGA_WINDOWS_PURE
@@ -119,6 +134,7 @@ sga_windows::WindowTraits window_traits_of(const sga_engine *e) {
     t.planes_resident = e->win.jp != nullptr;
     t.ones = e->win.ones;
     t.tiles_refused = e->win.tiles_refused;
+    t.groups = e->win.groups;
     return t;
 }
 
@@ -129,6 +145,23 @@ int row_shared_form_planes(const sga_engine *e, int *grid) {
 }
 sga::RowSharedTiles row_shared_tiles(const sga_engine *e, const char **why) { return sga_windows::tiles(window_traits_of(e), why); }
 sga::SeqWindows sequential_windows(const sga_engine *e) { return sga_windows::sequential(window_traits_of(e)); }
+int replica_groups(const sga_engine *e, int rs_w, const sga::RowSharedTiles &tiles, bool energy_trace, const char **why) {
+    return sga_windows::groups(window_traits_of(e), rs_w, tiles, energy_trace, why);
+}
+
+// the streams and events of G replica groups: made once, kept as long as the engine; false (and one group runs) if one
+// cannot be had
+static bool ensure_group_run(sga_engine *e, int G) {
+    sga::RowSharedGroupRun &run = e->win.run;
+    hipError_t he = hipSuccess;
+    if (!run.fork) he = hipEventCreateWithFlags(&run.fork, hipEventDisableTiming);
+    for (int g = 0; g + 1 < G && he == hipSuccess; ++g) {
+        if (!run.stream[g]) he = hipStreamCreateWithFlags(&run.stream[g], hipStreamNonBlocking);
+        if (he == hipSuccess && !run.join[g]) he = hipEventCreateWithFlags(&run.join[g], hipEventDisableTiming);
+    }
+    if (he != hipSuccess) (void)hipGetLastError();
+    return he == hipSuccess;
+}
 
 // fp32 rows that the int8 matrix cores can take: their resident int8 copy, made once per problem -- the product reads a
 // quarter of the bytes and converts nothing (measured against conversion in registers, DESIGN.md 7: 1.23 -> 0.65 ms of
@@ -231,7 +264,9 @@ static bool ensure_row_shared(sga_engine *e, int W, hipStream_t st) {
     return true;
 }
 
-void plan_windows(sga_engine *e, bool lean_call, bool sequential_call, int &rs_w, sga::RowSharedTiles &rs_tiles, sga::SeqWindows &seq) {
+void plan_windows(sga_engine *e, bool lean_call, bool sequential_call, bool energy_trace, int &rs_w, sga::RowSharedTiles &rs_tiles,
+                  int &rs_groups, sga::SeqWindows &seq) {
+    rs_groups = 1;
     // row-shared windows (sweep_dense_rs.hip): one coupling-row read per proposed site and window
     rs_w = row_shared_window(e, lean_call);
     if (rs_w && !ensure_row_shared(e, rs_w, e->stream)) rs_w = 0;
@@ -248,6 +283,9 @@ void plan_windows(sga_engine *e, bool lean_call, bool sequential_call, int &rs_w
             e->win.tiles_refused = true;
             rs_tiles = sga::RowSharedTiles{};
         }
+        // replica groups, a stream each (over the tile plan only)
+        rs_groups = replica_groups(e, rs_w, rs_tiles, energy_trace, nullptr);
+        if (rs_groups > 1 && !ensure_group_run(e, rs_groups)) rs_groups = 1;
     }
     // sequential windows (sweep_dense_seq.hip, sga_set_sequential_windows): one read of each coupling row per sweep
     if (sequential_call) {

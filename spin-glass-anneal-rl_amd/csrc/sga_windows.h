@@ -37,6 +37,7 @@ struct WindowTraits {
     int seq_w = 0;
     // the tiles: resident planes exist, every off-diagonal |2^k J_ij| is 1, the runtime refused the tile kernel's LDS
     bool planes_resident = false, ones = false, tiles_refused = false;
+    int groups = 0;  // sga_set_replica_groups: 0 the rule's choice, 1 | 2 | 4 forced
 };
 
 // The class of exact products a problem falls in.  why: null, or why there is none.
@@ -74,6 +75,13 @@ sga::SeqWindows sequential(const WindowTraits &t);
 // whether the rows are sign-only, or S = 0 and the reason where the per-site kernel runs.  Option 2 takes the tiles only
 // in the configuration measured to win.  Known once the planes exist (ones is found with them).
 sga::RowSharedTiles tiles(const WindowTraits &t, const char **why);
+// Replica groups of a row-shared sweep of window rs_w whose fields kernel is `tiles` (sga_kernels.h, row_shared_groups):
+// the count the launch runs.  One wherever the tile plan does not run (the per-site kernels' plan orders its entries across
+// all replicas; the sequential windows and every other form have no groups either) and under an energy trace (its stride
+// is the call's R).  t.groups = 0: row_shared_default_groups; 1 | 2 | 4: that count, or as many ranges as R gives.  A count
+// whose carve of the plan's scratch does not fit is one group.  why: null, or why a count above one was asked for (by the
+// caller or the rule) and one group runs.
+int groups(const WindowTraits &t, int rs_w, const sga::RowSharedTiles &tiles, bool energy_trace, const char **why);
 
 // ---- the forms' state in an engine, by lifetime -------------------------------------------------------------------------
 // Every pointer is device memory the engine allocated; a reset hands what it drops to `release` (the engine: hipFree;
@@ -84,6 +92,10 @@ struct WindowState {
     int seq_w = 0;         // sga_set_sequential_windows: W of the sequential windows (0: off), read at every sga_sweep;
                            // not part of sga_export_state
     bool suspend = false;  // true only inside sga_autotune: its geometry trials time the row-per-proposal kernel
+    int groups = 0;        // sga_set_replica_groups: 0 the rule's choice, 1 | 2 | 4 forced; not part of sga_export_state
+    // -- as long as the engine: the streams and events of the replica groups, made by the first grouped sweep, destroyed
+    // by sga_destroy (run.G is set per call)
+    sga::RowSharedGroupRun run{};
     // -- per problem: dropped by next_problem() alone; a change of W or of the replicas keeps them
     int grid_planes = 0, grid_k = 0;     // the set-time grid verdict: planes of |2^k J| (0: no verdict) and k; a
                                          // shared-coupling batch: over the batch's words

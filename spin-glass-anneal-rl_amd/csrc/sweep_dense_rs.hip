@@ -703,16 +703,22 @@ __device__ __forceinline__ bool rs_accept(float fk, float u, double T, int table
 // rs_coupling_load issues the loads and rs_coupling decodes the float the row of J holds.  BITS: from the resident
 // planes of row sa (one magnitude plane: two bits give nonzero ? (sign ? -1 : +1) : 0), (w32, bit) = rs_bit_of(site)
 // -- a 40 KB fp32 row gathered at W sites costs about a cache line per lane, its plane row is 2.5 KB in all.
-template <typename JE, bool BITS>
+// ONES (with BITS): the problem is flagged sign-only -- every off-diagonal |J| is one unit -- so the magnitude word is
+// known without a load: off the diagonal the coupling is +-unit by the sign bit, and on it (J_aa = 0) the two sites are
+// the same, the very test the chain makes to negate a repeated site's spin.  Half the gathers per correction and candidate.
+template <typename JE, bool BITS, bool ONES = false>
 struct RsRaw {
-    typename std::conditional<BITS, uint2, JE>::type v;
+    typename std::conditional<BITS, typename std::conditional<ONES, uint32_t, uint2>::type, JE>::type v;
 };
 // voff: the lane's byte offset in the row (BITS: of the 32-bit word of rs_bit_of(site) in a plane; else of J[.][site]),
 // unsigned and 32 bits wide beside a wave-uniform row address
-template <typename JE, bool BITS>
-__device__ __forceinline__ void rs_coupling_load(RsRaw<JE, BITS> &raw, const SweepArgs &a, const RowSharedPlan &p, int sa,
+template <typename JE, bool BITS, bool ONES>
+__device__ __forceinline__ void rs_coupling_load(RsRaw<JE, BITS, ONES> &raw, const SweepArgs &a, const RowSharedPlan &p, int sa,
                                                  unsigned int voff) {
-    if constexpr (BITS) {
+    if constexpr (BITS && ONES) {
+        const char *sgn = reinterpret_cast<const char *>(p.jp) + (long long)sa * (8ll * p.nw32);
+        raw.v = *reinterpret_cast<const uint32_t *>(sgn + voff);
+    } else if constexpr (BITS) {
         const char *sgn = reinterpret_cast<const char *>(p.jp) + (long long)sa * (8ll * p.nw32);
         const char *mag = sgn + 4ll * p.nw32;
         raw.v = make_uint2(*reinterpret_cast<const uint32_t *>(sgn + voff), *reinterpret_cast<const uint32_t *>(mag + voff));
@@ -727,7 +733,20 @@ __device__ __forceinline__ float rs_coupling(const RsRaw<JE, BITS> &raw, unsigne
     if constexpr (BITS) return (raw.v.y & bit) ? ((raw.v.x & bit) ? -unit : unit) : 0.0f;
     else return (float)raw.v;
 }
+// ONES; same: the two sites are one -- the diagonal, whose coupling is 0
+template <typename JE>
+__device__ __forceinline__ float rs_coupling(const RsRaw<JE, true, true> &raw, unsigned int bit, float unit, bool same) {
+    return same ? 0.0f : ((raw.v & bit) ? -unit : unit);
+}
 
+// Wave priority of the chain for its lifetime (s_setprio, 0 ... 3): beside another replica group's fields kernel a chain
+// wave shares its SIMD with VALU-saturated waves, and its serial stretches -- a decision of 64 lanes, the selects of the
+// current block -- wait for issue slots.  0: no instruction is emitted, the kernel is what it was.  The value is the
+// measured one; -DSGA_RS_CHAIN_PRIO=0 builds the other side of the A/B.
+#ifndef SGA_RS_CHAIN_PRIO
+#define SGA_RS_CHAIN_PRIO 3
+#endif
+constexpr int RS_CHAIN_PRIO = SGA_RS_CHAIN_PRIO;
 constexpr int RS_CHAIN_K = 4;  // candidates fetched per round (measured among 4, 8, 16)
 constexpr int RS_CHAIN_U = 8;  // earlier accepts applied to a block per wait
 
@@ -765,9 +784,10 @@ __device__ __forceinline__ bool rs_decide_rule(int rule, int cs, float cf, float
     }
 }
 
-template <typename JE, int NB, bool BITS, bool GRID, bool ANYRULE = false>
+template <typename JE, int NB, bool BITS, bool GRID, bool ANYRULE = false, bool ONES = false>
 __global__ void __launch_bounds__(64) rs_chain_kernel(const SweepArgs a, const RsPlanArg<GRID> pg, int k, int win) {
     const RowSharedPlan &p = rs_plan(pg);
+    if constexpr (RS_CHAIN_PRIO > 0) __builtin_amdgcn_s_setprio(RS_CHAIN_PRIO);
     constexpr int W = 64 * NB, K = RS_CHAIN_K, U = RS_CHAIN_U;
     __shared__ uint32_t alist[W + U];  // the window's accepts in chain order: site | (spin before the flip < 0) << 31
     const int r = blockIdx.x, lane = threadIdx.x, n = a.n;
@@ -816,22 +836,28 @@ __global__ void __launch_bounds__(64) rs_chain_kernel(const SweepArgs a, const R
         __syncthreads();
         for (int k0 = 0; k0 < nA; k0 += U) {
             uint32_t e[U];
-            RsRaw<JE, BITS> x[U];
+            RsRaw<JE, BITS, ONES> x[U];
 #pragma unroll
             for (int j = 0; j < U; ++j) e[j] = alist[k0 + j];  // (past nA: in the array, unused)
 #pragma unroll
             for (int j = 0; j < U; ++j) {
-                x[j] = RsRaw<JE, BITS>{};
+                x[j] = RsRaw<JE, BITS, ONES>{};
                 if (k0 + j < nA) {  // wave-uniform, here and below
                     e[j] = (uint32_t)__builtin_amdgcn_readfirstlane((int)e[j]);
-                    rs_coupling_load<JE, BITS>(x[j], a, p, (int)(e[j] & 0x7fffffffu), voff);
+                    rs_coupling_load<JE, BITS, ONES>(x[j], a, p, (int)(e[j] & 0x7fffffffu), voff);
                 }
             }
 #pragma unroll
             for (int j = 0; j < U; ++j) {
                 if (k0 + j < nA) {
-                    cf -= rs_coupling<JE, BITS>(x[j], bit, unit) * ((e[j] >> 31) ? -2.0f : 2.0f);
-                    if (csite == (int)(e[j] & 0x7fffffffu)) cs = -cs;
+                    if constexpr (ONES) {
+                        const bool same = csite == (int)(e[j] & 0x7fffffffu);
+                        cf -= rs_coupling<JE>(x[j], bit, unit, same) * ((e[j] >> 31) ? -2.0f : 2.0f);
+                        if (same) cs = -cs;
+                    } else {
+                        cf -= rs_coupling<JE, BITS>(x[j], bit, unit) * ((e[j] >> 31) ? -2.0f : 2.0f);
+                        if (csite == (int)(e[j] & 0x7fffffffu)) cs = -cs;
+                    }
                 }
             }
         }
@@ -839,7 +865,7 @@ __global__ void __launch_bounds__(64) rs_chain_kernel(const SweepArgs a, const R
         unsigned long long m = ballot64(acc);  // accepting lanes among the undecided ones
         while (m) {
             int cl[K];
-            RsRaw<JE, BITS> x[K];
+            RsRaw<JE, BITS, ONES> x[K];
             unsigned long long rest = m;
 #pragma unroll
             for (int j = 0; j < K; ++j) {
@@ -848,8 +874,8 @@ __global__ void __launch_bounds__(64) rs_chain_kernel(const SweepArgs a, const R
             }
 #pragma unroll
             for (int j = 0; j < K; ++j) {
-                x[j] = RsRaw<JE, BITS>{};
-                if (cl[j] < 64) rs_coupling_load<JE, BITS>(x[j], a, p, read_lane(csite, cl[j]), voff);  // wave-uniform
+                x[j] = RsRaw<JE, BITS, ONES>{};
+                if (cl[j] < 64) rs_coupling_load<JE, BITS, ONES>(x[j], a, p, read_lane(csite, cl[j]), voff);  // wave-uniform
             }
 #pragma unroll
             for (int j = 0; j < K; ++j) {
@@ -873,7 +899,8 @@ __global__ void __launch_bounds__(64) rs_chain_kernel(const SweepArgs a, const R
                     alist[nA] = (uint32_t)sa | (ss < 0 ? 0x80000000u : 0u);
                 }
                 ++nA;
-                cf -= rs_coupling<JE, BITS>(x[j], bit, unit) * (2.0f * (float)ss);
+                if constexpr (ONES) cf -= rs_coupling<JE>(x[j], bit, unit, csite == sa) * (2.0f * (float)ss);
+                else cf -= rs_coupling<JE, BITS>(x[j], bit, unit) * (2.0f * (float)ss);
                 if (csite == sa) cs = -cs;
                 acc = cvalid && rs_decide_rule<GRID, ANYRULE>(a.rule, cs, cf, chh, cu, T, a.table_m);
                 m = ballot64(acc) & (~1ull << fl);
@@ -962,25 +989,26 @@ static hipError_t rs_fields(const SweepArgs &a, const RowSharedPlan &p, int grid
     }
 }
 
-template <typename JE, bool BITS, bool GRID, bool ANYRULE>
+template <typename JE, bool BITS, bool GRID, bool ANYRULE, bool ONES>
 static hipError_t rs_chain_launch(const SweepArgs &a, const RsPlanArg<GRID> &p, int W, int k, int win, hipStream_t st) {
     switch (W) {
-        case 256: hipLaunchKernelGGL((rs_chain_kernel<JE, 4, BITS, GRID, ANYRULE>), dim3(a.R), dim3(64), 0, st, a, p, k, win); break;
-        case 512: hipLaunchKernelGGL((rs_chain_kernel<JE, 8, BITS, GRID, ANYRULE>), dim3(a.R), dim3(64), 0, st, a, p, k, win); break;
-        case 1024: hipLaunchKernelGGL((rs_chain_kernel<JE, 16, BITS, GRID, ANYRULE>), dim3(a.R), dim3(64), 0, st, a, p, k, win); break;
+        case 256: hipLaunchKernelGGL((rs_chain_kernel<JE, 4, BITS, GRID, ANYRULE, ONES>), dim3(a.R), dim3(64), 0, st, a, p, k, win); break;
+        case 512: hipLaunchKernelGGL((rs_chain_kernel<JE, 8, BITS, GRID, ANYRULE, ONES>), dim3(a.R), dim3(64), 0, st, a, p, k, win); break;
+        case 1024: hipLaunchKernelGGL((rs_chain_kernel<JE, 16, BITS, GRID, ANYRULE, ONES>), dim3(a.R), dim3(64), 0, st, a, p, k, win); break;
         default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
 }
 // (Glauber / heat bath: the ANYRULE instantiations; the rule itself stays a run-time value in them)
-template <typename JE, bool BITS>
+// ONES: the rows are sign-only (RowSharedTiles::ones, known where the tile kernel runs): the BITS chain gathers sign words alone
+template <typename JE, bool BITS, bool ONES = false>
 static hipError_t rs_chain(const SweepArgs &a, const RowSharedPlan &p, int grid, int k, int win, hipStream_t st) {
     if (a.rule != SGA_RULE_METROPOLIS) {
-        if (grid) return rs_chain_launch<JE, BITS, true, true>(a, RowSharedGridPlan{p, grid - 1}, p.W, k, win, st);
-        return rs_chain_launch<JE, BITS, false, true>(a, p, p.W, k, win, st);
+        if (grid) return rs_chain_launch<JE, BITS, true, true, ONES>(a, RowSharedGridPlan{p, grid - 1}, p.W, k, win, st);
+        return rs_chain_launch<JE, BITS, false, true, ONES>(a, p, p.W, k, win, st);
     }
-    if (grid) return rs_chain_launch<JE, BITS, true, false>(a, RowSharedGridPlan{p, grid - 1}, p.W, k, win, st);
-    return rs_chain_launch<JE, BITS, false, false>(a, p, p.W, k, win, st);
+    if (grid) return rs_chain_launch<JE, BITS, true, false, ONES>(a, RowSharedGridPlan{p, grid - 1}, p.W, k, win, st);
+    return rs_chain_launch<JE, BITS, false, false, ONES>(a, p, p.W, k, win, st);
 }
 
 template <typename JE>
@@ -1015,8 +1043,43 @@ hipError_t launch_rs_build_planes(const void *J, bool j_is_i8, long long ldj, in
                   : rs_build_planes<float>(J, ldj, n, planes, jp, jabs, st);
 }
 
+// One replica group of a launch: the group's own arguments and plan view (a one-group launch: the call's), its stream and
+// the geometry of its plan launches.
+struct RsGroupLaunch {
+    SweepArgs a;
+    RowSharedPlan p;
+    hipStream_t st = nullptr;
+    RowSharedTilePlan tp;
+    size_t tlds = 0;
+    int log_trg = 0;
+    dim3 pgrid, tgrid;
+};
+
+// replicas [r0, r1) of the call as an engine of their own: every per-replica pointer advanced, the plan's scratch carved
+// (row_shared_group_view); Philox streams and the model of a shared-coupling batch go through replica0 + r
+static void rs_group_args(const SweepArgs &a, const RowSharedPlan &p, const RowSharedGroups &g, int i, SweepArgs &ag, RowSharedPlan &pg) {
+    const int r0 = g.begin[i];
+    const RowSharedGroupView v = row_shared_group_view(a.n, p.W, g, i);
+    ag = a;
+    ag.R = g.begin[i + 1] - r0;
+    ag.replica0 = a.replica0 + (uint32_t)r0;
+    ag.spins = a.spins + (long long)r0 * a.sstride;
+    ag.energy = a.energy + r0;
+    ag.best_energy = a.best_energy ? a.best_energy + r0 : nullptr;
+    ag.best_spins = a.best_spins ? a.best_spins + (long long)r0 * a.sstride : nullptr;
+    ag.n_accepted = a.n_accepted + r0;
+    ag.rep_temp = a.rep_temp ? a.rep_temp + r0 : nullptr;
+    ag.sched = a.sched ? a.sched + (long long)r0 * a.sched_rs : nullptr;
+    pg = p;
+    pg.cnt = p.cnt + v.cnt;
+    pg.ent = p.ent + v.ent;
+    pg.base = p.base + v.base;
+    pg.bits = p.bits + v.bits;
+    pg.n_groups = v.n_groups;
+}
+
 hipError_t launch_sweep_dense_rs(const SweepArgs &a, const RowSharedPlan &p, bool j_is_i8, hipStream_t st, int grid,
-                                 RowSharedTiles tiles) {
+                                 RowSharedTiles tiles, const RowSharedGroupRun *run) {
     // the tile kernel: resident planes, the image and the replica counters within LDS (the host rule saw to it), sign-only
     // rows only where the planes are one magnitude plane
     if (tiles.S > 0 && (!p.jp || tiles.S > RS_TILE_MAX_SITES || a.R > RS_TILE_MAX_REPLICAS || (tiles.ones && p.planes != 1) ||
@@ -1033,58 +1096,106 @@ hipError_t launch_sweep_dense_rs(const SweepArgs &a, const RowSharedPlan &p, boo
     if (a.rule != SGA_RULE_METROPOLIS && a.rule != SGA_RULE_GLAUBER && a.rule != SGA_RULE_HEAT_BATH) return hipErrorInvalidValue;
     if (a.rule != SGA_RULE_METROPOLIS && a.arith != SGA_ARITH_F64) return hipErrorInvalidValue;
     const int nwin = (a.n + p.W - 1) / p.W;
-    const dim3 pgrid(p.n_groups, nwin, (a.n + RS_PLAN_TILE - 1) / RS_PLAN_TILE);
     const size_t plds = sizeof(int) * (size_t)(a.n < RS_PLAN_TILE ? a.n : RS_PLAN_TILE);
     const dim3 sgrid(row_shared_scan_chunks(a.n), nwin);
     const bool chain_bits = p.jp && p.planes == 1;
     // the tile kernel takes its entries by (slice, tile, replica): one launch of the plan (row_shared_tile_plan)
     const bool by_tile = p.jp && tiles.S > 0;
-    RowSharedTilePlan tp;
-    size_t tlds = 0;
-    int log_trg = 0;
-    if (by_tile) {
-        tp = row_shared_tile_plan(a.n, p.W, tiles.S, a.R);
-        if (tp.rg <= 0) return hipErrorInvalidValue;
-        while ((1 << log_trg) < tp.rg) ++log_trg;
-        tlds = row_shared_tile_plan_lds(p.W, tp.rg, tp.tiles);
-        const hipError_t le = ensure_lds_limit(reinterpret_cast<const void *>(rs_tile_plan_kernel), tlds);
-        if (le != hipSuccess) return le;
-    }
+    const bool chain_ones = chain_bits && by_tile && tiles.ones;  // sign-only rows (the flag travels with the tiles): sign words alone
     const int ntiles = by_tile ? (a.n + tiles.S - 1) / tiles.S : 0;
-    const dim3 tgrid(by_tile ? (a.R + tp.rg - 1) / tp.rg : 1, nwin, by_tile ? (ntiles + tp.tiles - 1) / tp.tiles : 1);
-    hipLaunchKernelGGL(rs_pack_kernel, dim3(a.R), dim3(256), 0, st, a, p);
-    hipError_t e = hipGetLastError();
-    for (int k = 0; k < a.n_sweeps && e == hipSuccess; ++k) {
-        if (by_tile) {
-            hipLaunchKernelGGL(rs_tile_plan_kernel, tgrid, dim3(RS_TILE_PLAN_THREADS), tlds, st, a, p, k, tiles.S, log_trg, tp.tiles);
+    // Replica groups: only over the tile plan (the by-site plan orders its entries across all replicas), only without an
+    // energy trace (its stride is the call's R), and only in a geometry the pure rule admits; the caller asked the same rule.
+    const RowSharedGroups groups = row_shared_groups(a.R, run ? run->G : 1);
+    const int G = groups.G;
+    if (run && run->G > 1 && (G != run->G || !by_tile || a.energy_trace || !run->fork || !row_shared_groups_fit(a.n, p.W, tiles.S, a.R, groups)))
+        return hipErrorInvalidValue;
+    RsGroupLaunch gl[RS_MAX_GROUPS];
+    for (int g = 0; g < G; ++g) {
+        RsGroupLaunch &q = gl[g];
+        if (G > 1) {
+            rs_group_args(a, p, groups, g, q.a, q.p);
+            q.st = g ? run->stream[g - 1] : st;
+            if (g && (!q.st || !run->join[g - 1])) return hipErrorInvalidValue;
         } else {
-            hipLaunchKernelGGL(rs_plan_kernel<false>, pgrid, dim3(256), plds, st, a, p, k);
-            hipLaunchKernelGGL(rs_scan_totals_kernel, sgrid, dim3(RS_SCAN_CHUNK), 0, st, a, p);
-            hipLaunchKernelGGL(rs_scan_kernel, sgrid, dim3(RS_SCAN_CHUNK), 0, st, a, p);
-            hipLaunchKernelGGL(rs_plan_kernel<true>, pgrid, dim3(256), plds, st, a, p, k);
+            q.a = a, q.p = p, q.st = st;
         }
+        q.pgrid = dim3(q.p.n_groups, nwin, (a.n + RS_PLAN_TILE - 1) / RS_PLAN_TILE);
+        if (by_tile) {
+            q.tp = row_shared_tile_plan(a.n, p.W, tiles.S, q.a.R);
+            if (q.tp.rg <= 0) return hipErrorInvalidValue;
+            while ((1 << q.log_trg) < q.tp.rg) ++q.log_trg;
+            q.tlds = row_shared_tile_plan_lds(p.W, q.tp.rg, q.tp.tiles);
+            const hipError_t le = ensure_lds_limit(reinterpret_cast<const void *>(rs_tile_plan_kernel), q.tlds);
+            if (le != hipSuccess) return le;
+        }
+        q.tgrid = dim3(by_tile ? (q.a.R + q.tp.rg - 1) / q.tp.rg : 1, nwin, by_tile ? (ntiles + q.tp.tiles - 1) / q.tp.tiles : 1);
+    }
+    hipError_t e = hipSuccess;
+    if (G > 1) {  // fork: every group's stream behind what the call's stream holds
+        e = hipEventRecord(run->fork, st);
+        for (int g = 1; g < G && e == hipSuccess; ++g) e = hipStreamWaitEvent(gl[g].st, run->fork, 0);
+        if (e != hipSuccess) return e;
+    }
+    // The groups' launches are issued turn by turn -- every group's plan, then window by window every group's fields and
+    // chain -- so that no stream runs dry while the host fills another; inside a stream the order is the one-group order,
+    // and nothing orders two groups against each other before the join: a group runs ahead across sweep boundaries.
+    for (int g = 0; g < G && e == hipSuccess; ++g) {
+        hipLaunchKernelGGL(rs_pack_kernel, dim3(gl[g].a.R), dim3(256), 0, gl[g].st, gl[g].a, gl[g].p);
         e = hipGetLastError();
+    }
+    for (int k = 0; k < a.n_sweeps && e == hipSuccess; ++k) {
+        for (int g = 0; g < G && e == hipSuccess; ++g) {
+            const RsGroupLaunch &q = gl[g];
+            if (by_tile) {
+                hipLaunchKernelGGL(rs_tile_plan_kernel, q.tgrid, dim3(RS_TILE_PLAN_THREADS), q.tlds, q.st, q.a, q.p, k, tiles.S, q.log_trg,
+                                   q.tp.tiles);
+            } else {
+                hipLaunchKernelGGL(rs_plan_kernel<false>, q.pgrid, dim3(256), plds, q.st, q.a, q.p, k);
+                hipLaunchKernelGGL(rs_scan_totals_kernel, sgrid, dim3(RS_SCAN_CHUNK), 0, q.st, q.a, q.p);
+                hipLaunchKernelGGL(rs_scan_kernel, sgrid, dim3(RS_SCAN_CHUNK), 0, q.st, q.a, q.p);
+                hipLaunchKernelGGL(rs_plan_kernel<true>, q.pgrid, dim3(256), plds, q.st, q.a, q.p, k);
+            }
+            e = hipGetLastError();
+        }
         for (int w = 0; w < nwin && e == hipSuccess; ++w) {
-            e = j_is_i8 ? rs_fields<int8_t>(a, p, grid, tiles, log_trg, w, st) : rs_fields<float>(a, p, grid, tiles, log_trg, w, st);
-            if (e != hipSuccess) break;
-            if (chain_bits)
-                e = j_is_i8 ? rs_chain<int8_t, true>(a, p, grid, k, w, st) : rs_chain<float, true>(a, p, grid, k, w, st);
-            else
-                e = j_is_i8 ? rs_chain<int8_t, false>(a, p, grid, k, w, st) : rs_chain<float, false>(a, p, grid, k, w, st);
+            for (int g = 0; g < G && e == hipSuccess; ++g) {
+                const RsGroupLaunch &q = gl[g];
+                e = j_is_i8 ? rs_fields<int8_t>(q.a, q.p, grid, tiles, q.log_trg, w, q.st)
+                            : rs_fields<float>(q.a, q.p, grid, tiles, q.log_trg, w, q.st);
+                if (e != hipSuccess) break;
+                if (chain_ones)
+                    e = j_is_i8 ? rs_chain<int8_t, true, true>(q.a, q.p, grid, k, w, q.st) : rs_chain<float, true, true>(q.a, q.p, grid, k, w, q.st);
+                else if (chain_bits)
+                    e = j_is_i8 ? rs_chain<int8_t, true>(q.a, q.p, grid, k, w, q.st) : rs_chain<float, true>(q.a, q.p, grid, k, w, q.st);
+                else
+                    e = j_is_i8 ? rs_chain<int8_t, false>(q.a, q.p, grid, k, w, q.st) : rs_chain<float, false>(q.a, q.p, grid, k, w, q.st);
+            }
         }
         // sweep boundary: best tracking (annealing/gpu_annealer.py:151-153), the energy is in a.energy
-        if (e == hipSuccess && !a.no_best)
-            e = launch_update_best(a.energy, a.spins, a.best_energy, a.best_spins, a.sstride, a.R, st);
+        for (int g = 0; g < G && e == hipSuccess && !a.no_best; ++g) {
+            const RsGroupLaunch &q = gl[g];
+            e = launch_update_best(q.a.energy, q.a.spins, q.a.best_energy, q.a.best_spins, q.a.sstride, q.a.R, q.st);
+        }
+    }
+    if (G > 1) {  // join, whatever happened in between: nothing else uses the call's stream before every group is done
+        hipError_t je = hipSuccess;
+        for (int g = 1; g < G; ++g) {
+            hipError_t x = hipEventRecord(run->join[g - 1], gl[g].st);
+            if (x == hipSuccess) x = hipStreamWaitEvent(st, run->join[g - 1], 0);
+            if (x != hipSuccess) (void)hipStreamSynchronize(gl[g].st), je = x;
+        }
+        if (e == hipSuccess) e = je;
     }
     if (e == hipSuccess) {
         // (the words "fields from resident bit-planes" / "on-chip conversion" are read by tests and bench.py)
-        char gs[48] = "", ts[64] = "";
+        char gs[48] = "", ts[64] = "", rg[24] = "";
         if (grid) std::snprintf(gs, sizeof(gs), ", grid=2^-%d", grid - 1);
         if (a.rule != SGA_RULE_METROPOLIS)  // (Metropolis strings stay as they were)
             std::snprintf(gs + std::strlen(gs), sizeof(gs) - std::strlen(gs), ", rule=%s", a.rule == SGA_RULE_GLAUBER ? "glauber" : "heat-bath");
         if (p.jp && tiles.S > 0) std::snprintf(ts, sizeof(ts), " in tiles of %d sites%s", tiles.S, tiles.ones ? ", sign-only" : "");
-        note_sweep_kernel("sweep_dense_rs<%s, planes=%d, W=%d%s> (row-shared windows: plan, fields from %s%s, chain)",
-                          j_is_i8 ? "int8_t" : "float", p.planes, p.W, gs, p.jp ? "resident bit-planes" : "on-chip conversion", ts);
+        if (G > 1) std::snprintf(rg, sizeof(rg), " groups=%d", G);  // (one group: the string stays as it was)
+        note_sweep_kernel("sweep_dense_rs<%s, planes=%d, W=%d%s> (row-shared windows: plan, fields from %s%s, chain)%s",
+                          j_is_i8 ? "int8_t" : "float", p.planes, p.W, gs, p.jp ? "resident bit-planes" : "on-chip conversion", ts, rg);
     }
     return e;
 }

@@ -219,6 +219,17 @@ class AnnealEngine:
         N.check(self._lib.sga_get_sequential_windows(self._h, C.byref(w)), "sga_get_sequential_windows")
         return int(w.value)
 
+    def set_replica_groups(self, g: int = 0):
+        """Replica groups (sga_set_replica_groups): the row-shared sweep over the tile plan runs contiguous groups of
+        replicas as pipelines of their own, a stream each, joined before the sweep returns -- 0 = the rule's count
+        (default), 1 | 2 | 4 = that many where the form admits groups.  Identical chains."""
+        N.check(self._lib.sga_set_replica_groups(self._h, int(g)), "sga_set_replica_groups")
+
+    def replica_groups(self) -> int:
+        g = C.c_int(0)
+        N.check(self._lib.sga_get_replica_groups(self._h, C.byref(g)), "sga_get_replica_groups")
+        return int(g.value)
+
     def autotune(self) -> float:
         """Time every feasible waves-per-replica on the current replicas and keep the fastest
         (dense problems; results are unaffected).  Returns the best kernel ms per sweep."""
