@@ -110,6 +110,26 @@ def one_sparse_graph_many_fields(L=12, n_fields=8, n_replicas=4):
         print(f"one lattice, {n_fields} field strengths: best energies {[round(b) for b in best]}\n  engine: {e.describe()}")
 
 
+def frustrated_lattice_with_cluster_moves(L=10):
+    """Parallel tempering on a 3-D +-J lattice with isoenergetic cluster moves: two copies of the ladder run side by side,
+    and after every exchange round the copies trade, slot by slot, the connected component of differing sites around
+    one drawn site (AnnealEngine.cluster_move_ladders) -- rejection free, E_a + E_b conserved, sparse couplings only."""
+    rs = np.random.RandomState(4)
+    idx = np.arange(L ** 3).reshape(L, L, L)
+    J = np.zeros((L ** 3, L ** 3), np.float32)
+    for ax in range(3):
+        a, b = idx.ravel(), np.roll(idx, -1, axis=ax).ravel()
+        J[a, b] = J[b, a] = rs.randint(0, 2, a.size) * 2.0 - 1.0
+    model = IsingModel(IsingModelConfig(n_spins=L ** 3, use_sparse=True))
+    model.set_couplings_from_matrix(torch.from_numpy(J))
+    cfg = ParallelTemperingConfig(n_replicas=16, n_sweeps=500, temp_min=0.2, temp_max=3.0, exchange_interval=10, random_seed=42,
+                                  n_copies=2, cluster_moves=True, cluster_temp_max=1.2)
+    pt = ParallelTempering(cfg)
+    result = pt.run(model)
+    print(f"PT + cluster moves, {L}^3 +-J lattice: best energy {result.best_energy:.1f}; {pt.cluster_moves_flipped} of "
+          f"{pt.cluster_moves_made} moves flipped {pt.cluster_sites_flipped} sites, largest cluster {pt.cluster_size_max}")
+
+
 def travelling_salesman(n_cities=12):
     rs = np.random.RandomState(0)
     xy = rs.rand(n_cities, 2)
@@ -206,6 +226,7 @@ if __name__ == "__main__":
     many_models()
     one_graph_many_fields()
     one_sparse_graph_many_fields()
+    frustrated_lattice_with_cluster_moves()
     travelling_salesman()
     travelling_salesman_without_storing_couplings()
     scheduling_without_storing_couplings()

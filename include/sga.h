@@ -80,7 +80,7 @@ typedef struct sga_engine sga_engine;
 int sga_create(int device, sga_engine **out);
 void sga_destroy(sga_engine *e);
 const char *sga_last_error(void);
-int sga_version(void);  /* 2300: sga_get_magnetizations / sga_get_overlaps / sga_get_overlaps_with (replica observables on the device: the exact integer product of int8 spin rows on the matrix cores, csrc/observables.hip; read only, no engine state); 2200: the row-shared fields in tiles take a plan of their own, one launch per sweep (csrc/sweep_dense_rs.hip, rs_tile_plan_kernel; no change of interface or results); 2100: sga_set_sequential_windows / sga_get_sequential_windows (SGA_SITE_SEQUENTIAL sweeps in windows, the fields of every replica on the matrix cores; csrc/sweep_dense_seq.hip); 2000: the row-shared windows (option "row_shared") serve SGA_RULE_GLAUBER and SGA_RULE_HEAT_BATH too ("rule=glauber" / "rule=heat-bath" in sga_describe and sga_get_last_kernel; the window sga_autotune picks holds for the rule it was timed under); 1900: options "row_shared_fields" and "row_shared_tile_sites" (row-shared fields in tiles of sites, sign-only rows); 1800: option "row_shared_grid", sga_route_query.rs_grid; 1700: sga_set_csr_shared (one set of CSR rows, many field vectors: every one-wave-per-replica CSR form for such batches), sga_route_query.shared_j on SGA_ROUTE_CSR queries; 1600: sga_set_dense_shared (one coupling matrix, many field vectors; row-shared windows, bit-planes and the matrix-core pass for such batches), sga_route_query.shared_j; 1500: sga_get_scan_summary, and sga_set_dense / sga_set_dense_batch / sga_set_csr / sga_set_csr64 / sga_set_csr_batch refuse a NaN or +-Inf in J or h (SGA_ERR_INVALID, "non-finite"); 1400: option "batch_fixed_point" (fixed-point cached local fields for many-model dense batches); 1300: options "ragged_field_cache" and "clf_fixed_point" together (fixed-point cached local fields for ragged CSR batches); 1200: sga_set_groups_csr (group couplings plus a stored sparse remainder); 1100: option "ragged_field_cache" (cached local fields for ragged CSR batches); 1000: sga_set_groups */
+int sga_version(void);  /* 2500: sga_cluster_move_pairs / sga_cluster_move_ladders (isoenergetic cluster moves between replica copies on sparse couplings, csrc/cluster_moves.hip; no engine state, no option); 2400: sga_set_replica_groups / sga_get_replica_groups; 2300: sga_get_magnetizations / sga_get_overlaps / sga_get_overlaps_with (replica observables on the device: the exact integer product of int8 spin rows on the matrix cores, csrc/observables.hip; read only, no engine state); 2200: the row-shared fields in tiles take a plan of their own, one launch per sweep (csrc/sweep_dense_rs.hip, rs_tile_plan_kernel; no change of interface or results); 2100: sga_set_sequential_windows / sga_get_sequential_windows (SGA_SITE_SEQUENTIAL sweeps in windows, the fields of every replica on the matrix cores; csrc/sweep_dense_seq.hip); 2000: the row-shared windows (option "row_shared") serve SGA_RULE_GLAUBER and SGA_RULE_HEAT_BATH too ("rule=glauber" / "rule=heat-bath" in sga_describe and sga_get_last_kernel; the window sga_autotune picks holds for the rule it was timed under); 1900: options "row_shared_fields" and "row_shared_tile_sites" (row-shared fields in tiles of sites, sign-only rows); 1800: option "row_shared_grid", sga_route_query.rs_grid; 1700: sga_set_csr_shared (one set of CSR rows, many field vectors: every one-wave-per-replica CSR form for such batches), sga_route_query.shared_j on SGA_ROUTE_CSR queries; 1600: sga_set_dense_shared (one coupling matrix, many field vectors; row-shared windows, bit-planes and the matrix-core pass for such batches), sga_route_query.shared_j; 1500: sga_get_scan_summary, and sga_set_dense / sga_set_dense_batch / sga_set_csr / sga_set_csr64 / sga_set_csr_batch refuse a NaN or +-Inf in J or h (SGA_ERR_INVALID, "non-finite"); 1400: option "batch_fixed_point" (fixed-point cached local fields for many-model dense batches); 1300: options "ragged_field_cache" and "clf_fixed_point" together (fixed-point cached local fields for ragged CSR batches); 1200: sga_set_groups_csr (group couplings plus a stored sparse remainder); 1100: option "ragged_field_cache" (cached local fields for ragged CSR batches); 1000: sga_set_groups */
 /* Run on an existing HIP stream (e.g. torch.cuda.current_stream().cuda_stream); NULL = the
  * engine's own stream (default). */
 int sga_set_stream(sga_engine *e, void *hip_stream);
@@ -394,6 +394,45 @@ int sga_exchange(sga_engine *e, const double *energies_global, const int32_t *st
  * u: [count] doubles or NULL (Philox, domain 1); energies_global as in sga_exchange. */
 int sga_exchange_pairs(sga_engine *e, const double *energies_global, const int32_t *pairs,
                        const double *u, int count, int *n_accepted);
+
+/* ---- isoenergetic cluster moves (version >= 2500; csrc/cluster_moves.hip) ------------------------------------------
+ * The cluster move of parallel tempering on frustrated sparse couplings (Houdayer 2001; Zhu, Ochoa and Katzgraber 2015)
+ * between two replicas a, b of ONE Hamiltonian: the sites where the two differ; one of them drawn uniformly; the
+ * connected component of differing sites around it, connected through stored non-zero couplings (an entry whose value
+ * is +-0 connects nothing); that component flipped in both replicas.  On the component the move swaps the two
+ * configurations and every coupling that leaves it ends on a site where the replicas agree, so E_a + E_b is conserved
+ * exactly for any J and h: the move is rejection free.  Identical replicas: nothing happens (size 0).
+ *   EQUAL TEMPERATURES WITHIN A PAIR ARE THE CALLER'S RESPONSIBILITY: only there is the move a valid Monte-Carlo step.
+ *   The pair form does not look at temperatures; the ladder form pairs equal slot indices of two ladders, which hold
+ *   equal temperatures where the ladders were set up with the same temperatures (sga_set_ladder of a tiled ladder).
+ *   The draw: Philox4x32-10, key = the engine's seed, counter (0, round, min(global id of a, global id of b), 5),
+ *   global id = replica0 + local index; with count = the number of differing sites the seed site is the
+ *   ((word 0 * count) >> 32)-th of them in index order.  round is the caller's: no counter of the engine moves.
+ *   Served: one-model CSR problems (sga_set_csr, sga_set_csr64, a sparse matrix that sga_set_dense kept as CSR) and
+ *   sga_set_csr_shared, where both replicas of a pair must lie under the same field vector (SGA_ERR_INVALID otherwise).
+ *   SGA_ERR_UNSUPPORTED, with the reason in sga_last_error: dense couplings (every differing site is connected to every
+ *   other: the component is always all of them, the move a plain exchange of the two replicas), sga_set_tsp, sga_set_groups
+ *   and sga_set_groups_csr (no stored rows to walk), ragged batches, n beyond what the kernel's bitmaps hold in LDS
+ *   (n / 2 bytes of the 160 KiB: n <= 327 040).
+ *   SGA_ERR_INVALID: a NULL engine or pair list; no problem or no replicas; count < 0; an index outside [0, R_local); a
+ *   replica named twice, or a == b; the ladder form: no ladder, an odd n_ladders, R_local != R_global, a slot range not
+ *   inside [0, slots).  count == 0 and an empty slot range are no-ops.  Every refusal happens before anything is
+ *   enqueued or changed.
+ *   After the call, enqueued on the engine's stream behind earlier sweeps: the spins of the replicas whose cluster was
+ *   not empty are flipped there; their tracked energies are what sga_recompute_energies would store, bit for bit; the
+ *   best of each follows where the new energy is lower (the step a sweep's end runs); their accept counters grow by
+ *   the cluster's size (as under SGA_RULE_WOLFF); the cached local fields are seeded again by the next sweep (as after
+ *   sga_set_spins).  Every other replica, the temperatures, the slot map, the exchange statistics and the sweep / round
+ *   counters are unchanged.  Cost beside the move itself: one from-scratch energy pass over the local replicas.
+ *   sizes: the clusters' sizes, host or device, or NULL.  A device buffer: the call returns at once; a host buffer:
+ *   after the copy has landed. */
+/* pairs: host [count][2] int32 LOCAL replica indices, every replica at most once, a != b */
+int sga_cluster_move_pairs(sga_engine *e, const int32_t *pairs, int count, uint32_t round,
+                           int32_t *sizes /* [count], host or device, or NULL */);
+/* ladders 2c and 2c+1, slots slot_lo <= s < slot_hi: the replicas that hold slot s of both, read
+ * from the slot map ON THE DEVICE (no host round trip); needs an even n_ladders and R_local == R_global */
+int sga_cluster_move_ladders(sga_engine *e, int slot_lo, int slot_hi, uint32_t round,
+                             int32_t *sizes /* [n_ladders/2][slot_hi - slot_lo] or NULL */);
 
 /* Stateless operator form of CUDAKernelManager.parallel_tempering_exchange_optimized
  * (annealing/cuda_kernels.py:326-369, fallback :415-443): sequential adjacent pairs, fp32,

@@ -727,6 +727,53 @@ hipError_t launch_observables_product(const ObservablesArgs &a, hipStream_t st);
 // out[r] = sum_{i < n} S[r][i]: one workgroup per row
 hipError_t launch_observables_row_sums(const int8_t *S, long long ld, int n, int R, int *out, hipStream_t st);
 
+// Isoenergetic cluster moves between two replicas of one sparse Hamiltonian (cluster_moves.hip; sga_cluster_move_pairs /
+// sga_cluster_move_ladders; Houdayer 2001, Zhu, Ochoa and Katzgraber 2015): one workgroup of 256 threads per pair.  The
+// sites where the two replicas differ, the cluster, and the two frontiers of a level-synchronous breadth-first search
+// are bitmaps of ceil(n / 32) words in LDS; the connected component of differing sites around one drawn site is flipped
+// in both replicas.  Rows are walked from rowptr64[i] to rowptr64[i + 1] of cv; an entry whose value is +-0 (padding,
+// a stored zero) connects nothing.
+constexpr int CLUSTER_THREADS = 256;
+constexpr size_t CLUSTER_LDS_BUDGET = 160 * 1024 - 256;  // what the other kernels allow themselves
+constexpr size_t CLUSTER_LDS_FIXED = 64;                 // wave sums and prefixes, the level's flag
+inline size_t cluster_lds_bytes(long long n) { return 16 * (size_t)((n + 31) / 32) + CLUSTER_LDS_FIXED; }
+// the largest n the bitmaps hold: 327 040 sites
+constexpr long long CLUSTER_MAX_N = (long long)((CLUSTER_LDS_BUDGET - CLUSTER_LDS_FIXED) / 16) * 32;
+// The pair list of sga_cluster_move_pairs, checked on the host before anything is enqueued: nullptr, or what is wrong
+// with it.  reps_per_model > 0 (sga_set_csr_shared): both replicas of a pair under one field vector.  seen: R bytes.
+inline const char *cluster_pairs_check(const int32_t *pairs, int count, int R, int replica0, int reps_per_model,
+                                       unsigned char *seen) {
+    for (int r = 0; r < R; ++r) seen[r] = 0;
+    for (int k = 0; k < count; ++k) {
+        const int a = pairs[2 * k], b = pairs[2 * k + 1];
+        if (a < 0 || a >= R || b < 0 || b >= R) return "replica index out of range";
+        if (a == b) return "a pair names one replica twice (a == b)";
+        if (seen[a] || seen[b]) return "a replica is named in more than one pair";
+        seen[a] = seen[b] = 1;
+        if (reps_per_model > 0 && (replica0 + a) / reps_per_model != (replica0 + b) / reps_per_model)
+            return "shared-coupling CSR batch: a pair joins replicas of two models (their field vectors differ)";
+    }
+    return nullptr;
+}
+struct ClusterArgs {
+    int8_t *spins;                   // [R][sstride], sstride a multiple of 16
+    const long long *rowptr64;       // [n + 1]
+    const int2 *cv;                  // (column, value bits)
+    unsigned long long *n_accepted;  // [R]: both replicas' counters grow by the cluster's size
+    const int32_t *pairs;            // pair form: [count][2] local replicas
+    const int32_t *slot_to_rep;      // ladder form (pairs == null): the slot map, [n_ladders][L] global ids
+    int L, slot_lo, n_slots;         // ... pair p: ladders 2 (p / n_slots) and 2 (p / n_slots) + 1, slot slot_lo + p % n_slots
+    int *sizes;                      // [count] cluster sizes, or null
+    int *touched;                    // [R], zeroed by the caller: 1 where a replica's spins changed
+    int n, sstride, R, count;
+    uint32_t replica0, seed_lo, seed_hi, round;
+};
+hipError_t launch_cluster_moves(const ClusterArgs &a, hipStream_t st);
+// After the energies were formed again: an untouched replica gets its saved energy back; a touched one's best follows
+// where the new energy is lower (launch_update_best's step).
+hipError_t launch_cluster_finish(const int *touched, const double *saved_energy, double *energy, const int8_t *spins,
+                                 double *best_energy, int8_t *best_spins, int sstride, int R, hipStream_t st);
+
 // operator-form PT exchange (cuda_kernels.py:415-443): decide sequentially, then permute rows
 hipError_t launch_op_exchange(float *spins, float *tmp_rows, float *energies, const float *temps,
                               const float *u, int32_t *src_of_pos, int *n_accepted,

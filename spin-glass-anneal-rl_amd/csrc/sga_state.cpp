@@ -689,6 +689,111 @@ int sga_get_overlaps_with(sga_engine *e, int which, const int8_t *cfg, int64_t l
     return observables_product(e, observed_rows(e, which), B, ldb, count, false, out, ldq);
 }
 
+// ---- isoenergetic cluster moves (cluster_moves.hip) ------------------------------------------
+// No state of their own: a host pair list is staged in scratch slot 7 (as sga_exchange_pairs stages its list), the
+// energies before the move and the touched flags lie in slot 6, a host `sizes` goes through point_out.
+namespace {
+// nullptr where the engine's problem is one the move serves, else why not; *code: the error to return
+const char *cluster_refusal(const sga_engine *e, int *code) {
+    *code = SGA_ERR_INVALID;
+    if (e->n <= 0) return "no couplings set";
+    if (e->R <= 0 || !e->spins) return "no replicas";
+    *code = SGA_ERR_UNSUPPORTED;
+    if (e->tsp) return "cluster moves are not implemented for sga_set_tsp problems (no stored rows to walk)";
+    if (e->groups) return "cluster moves are not implemented for sga_set_groups / sga_set_groups_csr problems (no stored rows to walk)";
+    if (e->ragged) return "cluster moves are not implemented for ragged CSR batches";
+    if (!e->csr || !e->rowptr64 || !e->cv)
+        return "cluster moves need sparse (CSR) couplings: on dense couplings the component is always every differing site";
+    if (e->n > sga::CLUSTER_MAX_N) return "cluster moves: the bitmaps of n sites do not fit LDS (n / 2 bytes of 160 KiB)";
+    return nullptr;
+}
+
+// The move over `count` pairs (a.pairs or a.slot_to_rep set by the caller), the energies and the bests behind it.
+int cluster_move_run(sga_engine *e, sga::ClusterArgs a, int count, uint32_t round, int32_t *sizes) {
+    hipStream_t st = e->stream;
+    const size_t R = (size_t)e->R;
+    HIPCHK(e->scratch[6].reserve(R * (sizeof(double) + sizeof(int))));
+    double *saved = static_cast<double *>(e->scratch[6].ptr);
+    int *touched = reinterpret_cast<int *>(saved + R);
+    const bool sizes_on_device = sizes && is_device_ptr(sizes);
+    if (sizes && !sizes_on_device) HIPCHK(e->point_out.reserve((size_t)count * sizeof(int32_t)));
+    HIPCHK(hipMemcpyAsync(saved, e->energy, R * sizeof(double), hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipMemsetAsync(touched, 0, R * sizeof(int), st));
+    a.spins = e->spins;
+    a.rowptr64 = e->rowptr64;
+    a.cv = e->cv;
+    a.n_accepted = e->n_acc;
+    a.sizes = !sizes ? nullptr : sizes_on_device ? sizes : static_cast<int *>(e->point_out.ptr);
+    a.touched = touched;
+    a.n = e->n;
+    a.sstride = e->sstride;
+    a.R = e->R;
+    a.count = count;
+    a.replica0 = (uint32_t)e->replica0;
+    a.seed_lo = (uint32_t)e->seed;
+    a.seed_hi = (uint32_t)(e->seed >> 32);
+    a.round = round;
+    HIPCHK(sga::launch_cluster_moves(a, st));
+    e->fields_valid = false;
+    // the whole range, as sga_recompute_energies forms it: the same pass, so the same bits; the replicas whose spins did
+    // not change get their energies back
+    int rc = recompute_energy_range(e, 0, e->R);
+    if (rc != SGA_OK) return rc;
+    HIPCHK(sga::launch_cluster_finish(touched, saved, e->energy, e->spins, e->best_energy, e->best_spins, e->sstride, e->R, st));
+    if (sizes && !sizes_on_device) {
+        HIPCHK(hipMemcpyAsync(sizes, a.sizes, (size_t)count * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+    }
+    return SGA_OK;
+}
+}  // namespace
+
+int sga_cluster_move_pairs(sga_engine *e, const int32_t *pairs, int count, uint32_t round, int32_t *sizes) {
+    if (!e || !pairs) return fail(SGA_ERR_INVALID, "NULL argument");
+    int code = SGA_OK;
+    if (const char *why = cluster_refusal(e, &code)) return fail(code, why);
+    if (count < 0) return fail(SGA_ERR_INVALID, "count is negative");
+    if (is_device_ptr(pairs)) return fail(SGA_ERR_INVALID, "pairs must be a host buffer");
+    std::vector<unsigned char> seen((size_t)e->R);
+    const int reps_per_model = e->shared_j && e->n_models > 1 ? e->Rg / e->n_models : 0;
+    if (const char *why = sga::cluster_pairs_check(pairs, count, e->R, e->replica0, reps_per_model, seen.data()))
+        return fail(SGA_ERR_INVALID, why);
+    if (count == 0) return SGA_OK;
+    HIPCHK(hipSetDevice(e->device));
+    // (a pageable host list: the copy has left the caller's buffer when the call returns)
+    HIPCHK(e->scratch[7].reserve((size_t)2 * count * sizeof(int32_t)));
+    HIPCHK(hipMemcpyAsync(e->scratch[7].ptr, pairs, (size_t)2 * count * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
+    sga::ClusterArgs a{};
+    a.pairs = static_cast<const int32_t *>(e->scratch[7].ptr);
+    return cluster_move_run(e, a, count, round, sizes);
+}
+
+int sga_cluster_move_ladders(sga_engine *e, int slot_lo, int slot_hi, uint32_t round, int32_t *sizes) {
+    if (!e) return fail(SGA_ERR_INVALID, "engine is NULL");
+    int code = SGA_OK;
+    if (const char *why = cluster_refusal(e, &code)) return fail(code, why);
+    if (e->n_ladders <= 0 || !e->slot_to_rep) return fail(SGA_ERR_INVALID, "no ladder (call sga_set_ladder)");
+    if (e->n_ladders % 2 != 0) return fail(SGA_ERR_INVALID, "cluster moves between ladders need an even number of ladders");
+    if (e->R != e->Rg) return fail(SGA_ERR_INVALID, "cluster moves between ladders need every replica on this rank (R_local == R_global)");
+    const int L = e->Rg / e->n_ladders;
+    if (slot_lo < 0 || slot_hi > L || slot_lo > slot_hi) return fail(SGA_ERR_INVALID, "slot range outside [0, slots)");
+    if (e->shared_j && e->n_models > 1) {  // a ladder's slots hold its own L replicas: both ladders under one field vector
+        const int reps = e->Rg / e->n_models;
+        for (int c = 0; c < e->n_ladders / 2; ++c)
+            if ((2 * c * L) / reps != ((2 * c + 2) * L - 1) / reps)
+                return fail(SGA_ERR_INVALID, "shared-coupling CSR batch: ladders " + std::to_string(2 * c) + " and " +
+                                                 std::to_string(2 * c + 1) + " lie under two models (their field vectors differ)");
+    }
+    if (slot_lo == slot_hi) return SGA_OK;
+    HIPCHK(hipSetDevice(e->device));
+    sga::ClusterArgs a{};
+    a.slot_to_rep = e->slot_to_rep;
+    a.L = L;
+    a.slot_lo = slot_lo;
+    a.n_slots = slot_hi - slot_lo;
+    return cluster_move_run(e, a, (e->n_ladders / 2) * a.n_slots, round, sizes);
+}
+
 int sga_get_route_query(sga_engine *e, sga_route_query *out) {
     if (!e || !out) return fail(SGA_ERR_INVALID, "NULL argument");
     if (e->n <= 0) return fail(SGA_ERR_INVALID, "no couplings set");

@@ -134,6 +134,13 @@ __device__ __forceinline__ u32x4 sweep_block(const SweepArgs &a, int r, int k, u
     return philox4x32_10(b, a.sweep0 + (uint32_t)k, a.replica0 + (uint32_t)r, DOMAIN_SWEEP, a.seed_lo, a.seed_hi);
 }
 
+// The one draw of an isoenergetic cluster move between global replicas ga and gb in exchange round `round`: word 0 of
+// block 0 at (round, min(ga, gb), DOMAIN_CLUSTER); the seed site is the __umulhi(word, count)-th differing site.
+__device__ __forceinline__ uint32_t cluster_seed_word(uint32_t round, uint32_t ga, uint32_t gb, uint32_t seed_lo,
+                                                      uint32_t seed_hi) {
+    return philox4x32_10(0u, round, ga < gb ? ga : gb, DOMAIN_CLUSTER, seed_lo, seed_hi).x;
+}
+
 // The accept rule.  dot = fp32 coupling dot product J[site,:].s (already rounded to fp32),
 // si = s[site] (+-1).  Returns true if the spin flips; dE receives the energy change of the
 // flip.

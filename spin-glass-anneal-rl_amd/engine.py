@@ -606,6 +606,56 @@ class AnnealEngine:
                                              C.byref(out)), "sga_exchange_pairs")
         return int(out.value)
 
+    # ------------------------------------------------------------------ isoenergetic cluster moves
+    # csrc/cluster_moves.hip: between two replicas of one sparse Hamiltonian AT EQUAL TEMPERATURES (the caller's to see
+    # to), the connected component of differing sites around one drawn site is flipped in both; E_a + E_b is conserved.
+    def _cluster_sizes(self, sizes, count: int):
+        """(pointer, result, device?) of a cluster call's sizes: True a fresh int32 numpy array, False / None nothing, an
+        int32 CUDA tensor of `count` entries the caller's buffer (the call is then only enqueued)."""
+        if sizes is None or sizes is False:
+            return None, None, False
+        if sizes is True:
+            res = np.zeros(count, np.int32)
+            return res.ctypes.data_as(C.c_void_p), res, False
+        if not _is_tensor(sizes) or not sizes.is_cuda or sizes.dtype != torch.int32 or sizes.numel() != count or \
+                not sizes.is_contiguous():
+            raise AnnealingError(f"sizes must be True, False or a contiguous int32 CUDA tensor of {count} entries")
+        if not self.shares_torch_stream():
+            _producer_done(sizes)
+        return C.c_void_p(sizes.data_ptr()), sizes, True
+
+    def cluster_move_pairs(self, pairs, round: Optional[int] = None, sizes=True):
+        """One isoenergetic cluster move per pair (a, b) of LOCAL replica indices (sga_cluster_move_pairs): every replica
+        at most once, a != b; CSR couplings only.  round: the draw's coordinate, None = the engine's exchange-round
+        counter (counters()[1]).  Returns the clusters' sizes, int32 [count] (sizes=False: None; a CUDA tensor: filled
+        on the device, the call only enqueued)."""
+        pr = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+        rnd = self.counters()[1] if round is None else int(round)
+        ptr, res, dev = self._cluster_sizes(sizes, len(pr))
+        N.check(self._lib.sga_cluster_move_pairs(self._h, pr.ctypes.data_as(C.c_void_p), len(pr), rnd & 0xFFFFFFFF, ptr),
+                "sga_cluster_move_pairs")
+        self._observable_done(dev)
+        self._pending = (pr, res)  # the pair list and a device result stay alive while the work is queued
+        return res
+
+    def cluster_move_ladders(self, slot_lo: int = 0, slot_hi: Optional[int] = None, round: Optional[int] = None, sizes=True):
+        """One isoenergetic cluster move per slot slot_lo <= s < slot_hi (None: every slot) and pair of ladders 2c, 2c + 1,
+        between the replicas that hold slot s of both now -- read from the slot map on the device, no host round trip
+        (sga_cluster_move_ladders; an even n_ladders, every replica local).  Returns the sizes as int32
+        [n_ladders / 2, slot_hi - slot_lo] (sizes=False: None; a CUDA tensor of as many entries: filled on the device)."""
+        if self.n_ladders <= 0:
+            raise AnnealingError("no ladder (call set_ladder)")
+        L = self.R_global // self.n_ladders
+        lo, hi = int(slot_lo), L if slot_hi is None else int(slot_hi)
+        rnd = self.counters()[1] if round is None else int(round)
+        count = (self.n_ladders // 2) * max(hi - lo, 0)
+        ptr, res, dev = self._cluster_sizes(sizes, count)
+        N.check(self._lib.sga_cluster_move_ladders(self._h, lo, hi, rnd & 0xFFFFFFFF, ptr), "sga_cluster_move_ladders")
+        self._observable_done(dev)
+        if res is not None and not dev:
+            res = res.reshape(self.n_ladders // 2, max(hi - lo, 0))
+        return res
+
     # ------------------------------------------------------------------ state access
     def energies(self) -> np.ndarray:
         out = np.zeros(self.R, np.float64)

@@ -63,10 +63,25 @@ class ParallelTemperingConfig:
     #                                       sequential sweeps as before
     device_index: Optional[int] = None
     autotune: Optional[bool] = None       # measured launch geometry (None: for long runs only)
+    n_copies: int = 1                     # identical ladders run side by side (n_copies * n_replicas engine replicas), each
+    #                                       exchanged on its own; histories and exchange statistics are copy 0's, the best is
+    #                                       taken over all copies
+    cluster_moves: bool = False           # isoenergetic cluster moves between copies 2c and 2c + 1 at equal slots after every
+    #                                       exchange round (AnnealEngine.cluster_move_ladders; sparse couplings, an even n_copies)
+    cluster_temp_max: Optional[float] = None  # ... only in the slots whose temperature is at or below this (None: all)
 
     def __post_init__(self):
         if self.site_order not in ("random", "sequential"):
             raise ConfigurationError("site_order must be 'random' or 'sequential'")
+        self.check_copies()
+
+    def check_copies(self):
+        if int(self.n_copies) != self.n_copies or self.n_copies < 1:
+            raise ConfigurationError("n_copies must be a positive integer")
+        if self.cluster_moves and (self.n_copies < 2 or self.n_copies % 2 != 0):
+            raise ConfigurationError("cluster_moves needs an even n_copies >= 2 (the moves act between two copies of the ladder)")
+        if self.n_copies > 1 and self.exchange_method == "all_pairs":
+            raise ConfigurationError('n_copies > 1 is not implemented for exchange_method="all_pairs"')
 
 
 class ParallelTempering:
@@ -75,6 +90,7 @@ class ParallelTempering:
             raise ConfigurationError("parallel tempering needs at least 2 replicas")
         if config.exchange_interval <= 0 or config.record_interval <= 0 or config.n_sweeps <= 0:
             raise ConfigurationError("intervals and n_sweeps must be positive")
+        config.check_copies()
         self.config = config
         self.temperatures = temperature_ladder(config.n_replicas, config.temp_min,
                                                config.temp_max, config.temp_distribution)
@@ -84,6 +100,8 @@ class ParallelTempering:
         self.energy_histories: List[List[float]] = [[] for _ in range(R)]
         self.temp_histories: List[List[float]] = [[] for _ in range(R)]
         self.slot_acceptance = np.zeros(R)
+        # isoenergetic cluster moves of the last run(): moves made, those that flipped anything, sites flipped, largest cluster
+        self.cluster_moves_made = self.cluster_moves_flipped = self.cluster_sites_flipped = self.cluster_size_max = 0
         self.device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
         self.use_cuda = self.device.type == "cuda"
 
@@ -93,6 +111,7 @@ class ParallelTempering:
         recorded from the reference, replacing every Philox draw."""
         rule = rule_code(update_rule)
         cfg = self.config
+        cfg.check_copies()
         if cfg.exchange_method not in ("nearest_neighbor", "all_pairs"):
             raise ValueError(f"Unknown exchange method: {cfg.exchange_method}")  # reference :212
         all_pairs = cfg.exchange_method == "all_pairs"
@@ -102,8 +121,16 @@ class ParallelTempering:
         gate_rng = np.random.RandomState(fresh_seed(cfg.random_seed) & 0x7FFFFFFF)
         pair_list = [(i, j) for i in range(cfg.n_replicas - 1) for j in range(i + 1, cfg.n_replicas)]
         t_start = time.time()
-        R, n = cfg.n_replicas, model.n_spins
+        R, n, C = cfg.n_replicas, model.n_spins, int(cfg.n_copies)
         temps = np.asarray(self.temperatures, np.float64)
+        if C > 1 and _replay is not None:
+            raise ConfigurationError("the replay hook drives one ladder (n_copies = 1)")
+        # the slots the cluster moves act in: the ladder is monotone (index 0 the hottest), so they are one range
+        cl_lo, cl_hi = 0, R
+        if cfg.cluster_moves and cfg.cluster_temp_max is not None:
+            cold = np.nonzero(temps <= cfg.cluster_temp_max)[0]
+            cl_lo, cl_hi = (int(cold.min()), int(cold.max()) + 1) if cold.size else (0, 0)
+        self.cluster_moves_made = self.cluster_moves_flipped = self.cluster_sites_flipped = self.cluster_size_max = 0
         dev_idx = cfg.device_index if cfg.device_index is not None else _device_index(model.device)
         best_energy, best_configuration = float("inf"), None
         acc_slot, att_slot = np.zeros(R, np.int64), np.zeros(R, np.int64)
@@ -119,9 +146,14 @@ class ParallelTempering:
                 eng.set_sequential_windows(cfg.sequential_window)  # (read at every sweep; acts with field_cache="off")
             model.load_into(eng, storage=cfg.coupling_storage)
             eng.set_update_rule(rule)
-            eng.init_replicas(R, seed=fresh_seed(cfg.random_seed),
+            eng.init_replicas(C * R, seed=fresh_seed(cfg.random_seed),
                               s0=None if _replay is None else _replay["s0"])
-            eng.set_ladder(temps, 1)
+            eng.set_ladder(np.tile(temps, C) if C > 1 else temps, C)
+            if cfg.cluster_moves:  # an empty range moves nothing: what the engine refuses, it refuses here
+                try:
+                    eng.cluster_move_ladders(0, 0, round=0, sizes=False)
+                except AnnealingError as exc:
+                    raise ConfigurationError(f"cluster_moves: {exc.message}") from exc
             eng.maybe_autotune(cfg.n_sweeps, cfg.autotune)
             slot_to_rep = np.arange(R, dtype=np.int32)
             acc_prev = np.zeros(R, np.int64)
@@ -167,9 +199,17 @@ class ParallelTempering:
                         eng.exchange(start=[start], u=uu, count=False)
                         ucur += npairs
                     rnd += 1
+                if exchange_now and cfg.cluster_moves and cl_hi > cl_lo:
+                    # round: the engine's exchange-round counter, just advanced by the exchange
+                    sz = eng.cluster_move_ladders(cl_lo, cl_hi)
+                    self.cluster_moves_made += int(sz.size)
+                    self.cluster_moves_flipped += int(np.count_nonzero(sz))
+                    self.cluster_sites_flipped += int(sz.sum())
+                    self.cluster_size_max = max(self.cluster_size_max, int(sz.max()))
                 # one synchronisation per event: energies (an exchange moves labels, not energies),
                 # acceptance counters, ladder permutation
-                en_rep, acc_now, new_map = eng.snapshot()
+                en_rep, acc_now, full_map = eng.snapshot()
+                acc_now, new_map = acc_now[:R], full_map[:R]  # copy 0: ladder 0 holds replicas 0 ... R - 1
                 # per-slot acceptance bookkeeping (the reference's SpinDynamics stay with slots):
                 # these sweeps ran under the permutation in force BEFORE the exchange
                 acc_slot += (acc_now - acc_prev)[slot_to_rep]
@@ -181,10 +221,12 @@ class ParallelTempering:
                     for i in range(R):
                         self.energy_histories[i].append(float(en[i]))
                         self.temp_histories[i].append(float(temps[i]))
+                    if C > 1:  # the best over all copies
+                        en = en_rep[full_map]
                     i_best = int(np.argmin(en))
                     if en[i_best] < best_energy:
                         best_energy = float(en[i_best])
-                        best_configuration = eng.spins(int(slot_to_rep[i_best]))
+                        best_configuration = eng.spins(int(full_map[i_best]))
                 sweep = stop + 1
             att, acc = eng.exchange_stats()
             self.exchange_attempts = att[:R - 1].astype(np.float64)
