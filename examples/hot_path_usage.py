@@ -17,7 +17,8 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from spin_glass_anneal_rl_amd import (GPUAnnealer, GPUAnnealerConfig, IsingModel, IsingModelConfig,  # noqa: E402
-                                      ParallelTempering, ParallelTemperingConfig, SpinGlassScheduler)
+                                      ParallelTempering, ParallelTemperingConfig, PopulationAnnealing,
+                                      PopulationAnnealingConfig, SpinGlassScheduler)
 from spin_glass_anneal_rl_amd import encoders  # noqa: E402
 
 
@@ -130,6 +131,27 @@ def frustrated_lattice_with_cluster_moves(L=10):
           f"{pt.cluster_moves_made} moves flipped {pt.cluster_sites_flipped} sites, largest cluster {pt.cluster_size_max}")
 
 
+def frustrated_lattice_by_population_annealing(L=8):
+    """Population annealing on a 3-D +-J lattice: 4 independent populations of 1024 replicas cooled together from beta = 0
+    to 2, every replica copied or culled by its weight at each step (AnnealEngine.resample, on the device).  The run yields
+    the free energy -- the spread over the populations is its error bar -- and the surviving families say whether the
+    population equilibrated."""
+    rs = np.random.RandomState(4)
+    idx = np.arange(L ** 3).reshape(L, L, L)
+    J = np.zeros((L ** 3, L ** 3), np.float32)
+    for ax in range(3):
+        a, b = idx.ravel(), np.roll(idx, -1, axis=ax).ravel()
+        J[a, b] = J[b, a] = rs.randint(0, 2, a.size) * 2.0 - 1.0
+    model = IsingModel(IsingModelConfig(n_spins=L ** 3, use_sparse=True))
+    model.set_couplings_from_matrix(torch.from_numpy(J))
+    pa = PopulationAnnealing(PopulationAnnealingConfig(population_size=1024, n_populations=4, beta_max=2.0, n_steps=40,
+                                                       sweeps_per_step=5, random_seed=42))
+    result = pa.run(model)
+    f, err = pa.free_energy.mean() / L ** 3, pa.free_energy.std(ddof=1) / 2.0 / L ** 3
+    print(f"population annealing, {L}^3 +-J lattice: best energy {result.best_energy:.1f}; free energy per spin at beta = 2: "
+          f"{f:.4f} +- {err:.4f}; families left {pa.family_counts.tolist()} of 1024, rho_t {np.round(pa.rho_t, 1).tolist()}")
+
+
 def travelling_salesman(n_cities=12):
     rs = np.random.RandomState(0)
     xy = rs.rand(n_cities, 2)
@@ -227,6 +249,7 @@ if __name__ == "__main__":
     one_graph_many_fields()
     one_sparse_graph_many_fields()
     frustrated_lattice_with_cluster_moves()
+    frustrated_lattice_by_population_annealing()
     travelling_salesman()
     travelling_salesman_without_storing_couplings()
     scheduling_without_storing_couplings()

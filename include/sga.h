@@ -434,6 +434,44 @@ int sga_cluster_move_pairs(sga_engine *e, const int32_t *pairs, int count, uint3
 int sga_cluster_move_ladders(sga_engine *e, int slot_lo, int slot_hi, uint32_t round,
                              int32_t *sizes /* [n_ladders/2][slot_hi - slot_lo] or NULL */);
 
+/* ---- population annealing: the resampling step (version >= 2600; csrc/resample.hip) --------------------------------
+ * Population annealing (Hukushima and Iba 2003; Machta 2010; Wang, Machta and Katzgraber 2015) cools a population of
+ * replicas together; between two temperatures every replica is copied or culled in proportion to exp(-(beta' - beta) E).
+ * This call is that step, on the device and exact in integers, so that it is a function of the tracked energies, dbeta,
+ * the engine's seed and `round` alone.  The local replicas are cut into n_populations contiguous blocks of
+ * N = R_local / n_populations members; for population p with members r = 0 ... N - 1:
+ *   x_r = (-dbeta[p]) * E_r (one fp64 product), x_max = max_r x_r, W_r = (uint64)(exp(x_r - x_max) * 2^40), exp the
+ *   deterministic fp64 exp of the sweeps' accept rule; the product is exact, the cast truncates, exp(0) is exactly 1, so
+ *   S = sum W_r >= 2^40, and N <= 2^23 keeps S < 2^64.  C_r = W_0 + ... + W_r.
+ *   The draw: Philox4x32-10, key = the engine's seed, counter (0, round, replica0 / N + p, 6): U = (word 0 << 32) | word 1,
+ *   the offset o = (U * S) >> 64, 0 <= o < S.
+ *   Systematic resampling: child k = 0 ... N - 1 sits at t_k = k S + o and its parent is the r with
+ *   N C_{r-1} <= t_k < N C_r (128-bit integer compares).  n_r, the children of r, is the floor or the ceiling of
+ *   N W_r / S, and sum n_r = N.
+ *   Placement: every r with n_r >= 1 keeps its slot; the slots with n_r == 0, in ascending order, receive the surplus
+ *   copies in ascending order (parent r repeated n_r - 1 times, ascending in r).  A source is never a destination.
+ *   The relative weight lost to the truncation of W_r is below N * 2^-40.
+ *   dbeta: host [n_populations], finite.  round is the caller's: no counter of the engine moves.
+ *   parents: [R_local] the LOCAL index of every slot's parent (d itself where the slot is not overwritten); shift:
+ *   [n_populations] x_max; weight_sum: [n_populations] S.  ln Q_p = shift[p] + ln(weight_sum[p] / (N * 2^40)) is the
+ *   free-energy increment of the step; the logarithm is the caller's, so both outputs are exact.  Each of the three is a
+ *   host or a device buffer or NULL.  The work is enqueued on the engine's stream behind earlier sweeps; with device
+ *   outputs only the call returns at once, with a host output after its copy has landed.
+ *   After the call, an overwritten slot holds its parent's spins and tracked energy (the parent's bits: no energy pass
+ *   runs); its best becomes the parent's current state where the parent's energy is below the slot's best, else it is
+ *   kept (the best over all replicas is never lost); its accept counter is unchanged.  The cached local fields are seeded
+ *   again by the next sweep (as after sga_set_spins).  Every surviving slot, the temperatures (the new ones are the
+ *   caller's to set), the slot map, the exchange statistics, the sweep / round counters and the Wolff cursors are unchanged.
+ *   Served: every kind of problem.  Batches (sga_set_dense_batch, sga_set_dense_shared, sga_set_csr_batch,
+ *   sga_set_csr_shared) where no population spans two models; shards where replica0 and R_local are multiples of N.
+ *   SGA_ERR_INVALID, before anything is enqueued or changed: a NULL engine or dbeta; no problem or no replicas;
+ *   n_populations < 1 or not a divisor of R_local; N > 2^23; a dbeta that is NaN or infinite; a device dbeta; a
+ *   population across two models; a shard boundary inside a population. */
+int sga_resample(sga_engine *e, int n_populations, const double *dbeta /* host [n_populations] */, uint32_t round,
+                 int32_t *parents   /* [R_local] local indices, host or device, or NULL */,
+                 double *shift      /* [n_populations] x_max, host or device, or NULL */,
+                 uint64_t *weight_sum /* [n_populations] S, host or device, or NULL */);
+
 /* Stateless operator form of CUDAKernelManager.parallel_tempering_exchange_optimized
  * (annealing/cuda_kernels.py:326-369, fallback :415-443): sequential adjacent pairs, fp32,
  * p = exp((1/T[i+1] - 1/T[i]) * (E[i] - E[i+1])), accepted pairs swap spin rows and energies

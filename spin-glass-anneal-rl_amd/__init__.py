@@ -16,6 +16,7 @@ from .spin_dynamics import SpinDynamics, UpdateRule
 from .energy_computer import ComputeMode, EnergyComputer, EnergyStats
 from .gpu_annealer import GPUAnnealer, GPUAnnealerConfig
 from .parallel_tempering import ParallelTempering, ParallelTemperingConfig
+from .population_annealing import PopulationAnnealing, PopulationAnnealingConfig
 from .kernel_manager import CUDAKernelManager, GPUMemoryOptimizer, HIPKernelManager
 from .scheduler import SpinGlassScheduler
 from .sharded import LocalShardedTempering, ShardedTempering
@@ -30,6 +31,7 @@ __all__ = [
     "ScheduleType", "ScheduleConfig", "TemperatureScheduler", "temperature_ladder",
     "AnnealingResult", "IsingModel", "IsingModelConfig", "SpinDynamics", "UpdateRule",
     "GPUAnnealer", "GPUAnnealerConfig", "ParallelTempering", "ParallelTemperingConfig",
+    "PopulationAnnealing", "PopulationAnnealingConfig",
     "HIPKernelManager", "CUDAKernelManager", "GPUMemoryOptimizer", "SpinGlassScheduler",
     "ShardedTempering", "LocalShardedTempering", "MultiGPUAnnealer", "MultiGPUConfig", "LoadBalancer",
     "encoders", "IsingBuilder", "BatchConfig", "BatchProcessor", "EnergyComputer", "ComputeMode",

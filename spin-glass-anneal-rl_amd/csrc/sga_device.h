@@ -37,6 +37,8 @@ __device__ __forceinline__ u32x4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_
 constexpr uint32_t DOMAIN_SWEEP = 0, DOMAIN_EXCHANGE = 1, DOMAIN_INIT = 2;
 // the seed site of an isoenergetic cluster move (cluster_moves.hip): domain word 5 (the Wolff rule's always ends in 3)
 constexpr uint32_t DOMAIN_CLUSTER = DOMAIN_EXCHANGE | (1u << 2);
+// the offset of a population-annealing resampling step (resample.hip): domain word 6
+constexpr uint32_t DOMAIN_RESAMPLE = DOMAIN_INIT | (1u << 2);
 
 __device__ __forceinline__ uint32_t word_to_site(uint32_t w, uint32_t n) { return __umulhi(w, n); }
 __device__ __forceinline__ float word_to_u(uint32_t w) { return (float)(w >> 8) * 0x1.0p-24f; }

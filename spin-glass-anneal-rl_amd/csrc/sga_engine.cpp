@@ -347,6 +347,8 @@ extern "C" {
 
 const char *sga_last_error(void) { return g_last_error.c_str(); }
 // The ABI version, one line per step:
+//   2600:    + sga_resample: the resampling step of population annealing, planned and copied on the device, exact in
+//            integers (resample.hip; host side in sga_state.cpp); no engine state, no option
 //   2500:    + sga_cluster_move_pairs / sga_cluster_move_ladders: isoenergetic cluster moves between two replicas of one
 //            sparse Hamiltonian (cluster_moves.hip; host side in sga_state.cpp); no engine state, no option
 //   2400:    + sga_set_replica_groups / sga_get_replica_groups: the row-shared sweep over the tile plan runs contiguous
@@ -381,7 +383,7 @@ const char *sga_last_error(void) { return g_last_error.c_str(); }
 //   600:     + sga_set_csr_batch / sga_get_batch_model (ragged CSR batches)
 //   round 5: + sga_explain_route / sga_get_route_query, sga_get_last_kernel, sga_get_autotune_table, ladder-local
 //            sga_exchange
-int sga_version(void) { return 2500; }
+int sga_version(void) { return 2600; }
 
 int sga_create(int device, sga_engine **out) {
     if (!out) return fail(SGA_ERR_INVALID, "out is NULL");

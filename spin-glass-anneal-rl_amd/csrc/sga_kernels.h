@@ -774,6 +774,79 @@ hipError_t launch_cluster_moves(const ClusterArgs &a, hipStream_t st);
 hipError_t launch_cluster_finish(const int *touched, const double *saved_energy, double *energy, const int8_t *spins,
                                  double *best_energy, int8_t *best_spins, int sstride, int R, hipStream_t st);
 
+// Population annealing's resampling step (resample.hip; sga_resample; Hukushima and Iba 2003, Machta 2010): the local
+// replicas in n_pop contiguous populations of N members, each copied or culled in proportion to exp(-dbeta E), exact in
+// integers.  For population p with members r = 0 ... N - 1:
+//   x_r = (-dbeta[p]) * E_r (one fp64 product), x_max = max_r x_r, W_r = (uint64)(exp_det(x_r - x_max) * 2^40) (the product
+//   exact, the cast truncating; exp_det(0) == 1, so S = sum W_r >= 2^40; N <= 2^23 keeps S < 2^64), C_r = W_0 + ... + W_r;
+//   one draw U of 64 bits (sweep_common.h, resample_draw), the offset o = (U * S) >> 64 < S;
+//   child k = 0 ... N - 1 sits at t_k = k S + o, its parent is the r with N C_{r-1} <= t_k < N C_r (128-bit compares), so
+//   n_r, the children of r, is the floor or the ceiling of N W_r / S and sum n_r = N;
+//   every r with n_r >= 1 keeps its slot; the slots with n_r == 0, ascending, receive the surplus list -- parent r repeated
+//   n_r - 1 times, ascending in r.  A source is never a destination: the copy runs in place.
+// The relative weight the truncation loses is below N * 2^-40.
+constexpr int RESAMPLE_THREADS = 256;
+constexpr int RESAMPLE_MAX_MEMBERS = 1 << 23;
+constexpr int RESAMPLE_COPY_BYTES = 16384;  // of a spin row per workgroup of the copy kernel: 256 threads x 4 x 16 bytes
+// sga_resample's arguments, checked on the host before anything is enqueued: nullptr, or what is wrong with them.
+// R local replicas of Rg, the first the global replica0; n_models > 1: Rg / n_models consecutive replicas per model.
+inline const char *resample_check(int n_populations, const double *dbeta, int R, int Rg, int replica0, int n_models) {
+    if (!dbeta) return "dbeta is NULL";
+    if (R <= 0) return "no replicas";
+    if (n_populations < 1) return "n_populations must be at least 1";
+    if (R % n_populations != 0) return "n_populations does not divide the number of local replicas";
+    const int N = R / n_populations;
+    if (N > RESAMPLE_MAX_MEMBERS) return "a population holds more than 2^23 members (the weight sum would leave 64 bits)";
+    for (int p = 0; p < n_populations; ++p)
+        if (!(dbeta[p] - dbeta[p] == 0.0)) return "dbeta must be finite";  // (NaN and +-inf fail alike)
+    if (replica0 % N != 0) return "a shard boundary lies inside a population (replica0 must be a multiple of the population size)";
+    if (n_models > 1 && Rg > 0) {
+        const long long reps = Rg / n_models;
+        for (int p = 0; p < n_populations; ++p) {
+            const long long first = (long long)replica0 + (long long)p * N;
+            if (reps <= 0 || first / reps != (first + N - 1) / reps) return "a population lies across two models";
+        }
+    }
+    return nullptr;
+}
+// bytes of the plan's scratch for R replicas in n_pop populations, and where its arrays lie in it (each 16-byte aligned)
+struct ResampleScratch {
+    size_t c, f, sp, parent, take, shift, sum, dbeta, bytes;
+};
+inline ResampleScratch resample_scratch(long long R, long long n_pop) {
+    auto up = [](size_t v) { return (v + 15) / 16 * 16; };
+    ResampleScratch s{};
+    s.c = 0;
+    s.f = s.c + up((size_t)R * 8);
+    s.sp = s.f + up((size_t)R * 4);
+    s.parent = s.sp + up((size_t)R * 4);
+    s.take = s.parent + up((size_t)R * 4);
+    s.shift = s.take + up((size_t)R * 4);
+    s.sum = s.shift + up((size_t)n_pop * 8);
+    s.dbeta = s.sum + up((size_t)n_pop * 8);
+    s.bytes = s.dbeta + up((size_t)n_pop * 8);
+    return s;
+}
+struct ResampleArgs {
+    const double *energy;       // [R] tracked energies
+    const double *best_energy;  // [R]
+    const double *dbeta;        // [n_pop], on the device
+    unsigned long long *C;      // [R] scratch: W_r, then the inclusive sums C_r
+    int *F;                     // [R] scratch: children of members 0 ... r of r's population
+    int *SP;                    // [R] scratch: surplus copies of members 0 ... r
+    int32_t *parent;            // [R] out: LOCAL replica index of every slot's parent (d itself where it is not overwritten)
+    int *take_best;             // [R] out: 1 where slot d is overwritten and its parent's energy is below d's best
+    double *shift;              // [n_pop] out: x_max
+    unsigned long long *sum;    // [n_pop] out: S
+    int N, n_pop;
+    uint32_t gpop0, seed_lo, seed_hi, round;  // gpop0 = replica0 / N: the global index of population 0
+};
+hipError_t launch_resample_plan(const ResampleArgs &a, hipStream_t st);
+// For every slot d with parent[d] != d: the parent's spin row, its tracked energy (the bits), and, where take_best[d], the
+// parent's state as d's best.  In place: no source row is a destination.
+hipError_t launch_resample_copy(const int32_t *parent, const int *take_best, int8_t *spins, double *energy, int8_t *best_spins,
+                                double *best_energy, int sstride, int R, hipStream_t st);
+
 // operator-form PT exchange (cuda_kernels.py:415-443): decide sequentially, then permute rows
 hipError_t launch_op_exchange(float *spins, float *tmp_rows, float *energies, const float *temps,
                               const float *u, int32_t *src_of_pos, int *n_accepted,

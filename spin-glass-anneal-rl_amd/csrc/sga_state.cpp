@@ -794,6 +794,63 @@ int sga_cluster_move_ladders(sga_engine *e, int slot_lo, int slot_hi, uint32_t r
     return cluster_move_run(e, a, (e->n_ladders / 2) * a.n_slots, round, sizes);
 }
 
+// ---- population annealing: the resampling step (resample.hip) ---------------------------------
+// No state of its own: the plan's arrays (sga_kernels.h, resample_scratch) lie in scratch slot 6 with the staged dbeta
+// behind them, the outputs leave from there; the two kernels follow each other on the engine's stream.
+int sga_resample(sga_engine *e, int n_populations, const double *dbeta, uint32_t round, int32_t *parents, double *shift,
+                 uint64_t *weight_sum) {
+    if (!e || !dbeta) return fail(SGA_ERR_INVALID, "NULL argument");
+    if (e->n <= 0) return fail(SGA_ERR_INVALID, "no couplings set");
+    if (e->R <= 0 || !e->spins || !e->best_spins) return fail(SGA_ERR_INVALID, "no replicas");
+    if (is_device_ptr(dbeta)) return fail(SGA_ERR_INVALID, "dbeta must be a host buffer");
+    if (const char *why = sga::resample_check(n_populations, dbeta, e->R, e->Rg, e->replica0, e->n_models))
+        return fail(SGA_ERR_INVALID, std::string("sga_resample: ") + why);
+    HIPCHK(hipSetDevice(e->device));
+    hipStream_t st = e->stream;
+    const int R = e->R, P = n_populations, N = R / P;
+    const sga::ResampleScratch lay = sga::resample_scratch(R, P);
+    HIPCHK(e->scratch[6].reserve(lay.bytes));
+    unsigned char *s = static_cast<unsigned char *>(e->scratch[6].ptr);
+    sga::ResampleArgs a{};
+    a.energy = e->energy;
+    a.best_energy = e->best_energy;
+    a.C = reinterpret_cast<unsigned long long *>(s + lay.c);
+    a.F = reinterpret_cast<int *>(s + lay.f);
+    a.SP = reinterpret_cast<int *>(s + lay.sp);
+    a.parent = reinterpret_cast<int32_t *>(s + lay.parent);
+    a.take_best = reinterpret_cast<int *>(s + lay.take);
+    a.shift = reinterpret_cast<double *>(s + lay.shift);
+    a.sum = reinterpret_cast<unsigned long long *>(s + lay.sum);
+    double *d_dbeta = reinterpret_cast<double *>(s + lay.dbeta);
+    // (a pageable host array: the copy has left the caller's buffer when the call returns)
+    HIPCHK(hipMemcpyAsync(d_dbeta, dbeta, (size_t)P * sizeof(double), hipMemcpyHostToDevice, st));
+    a.dbeta = d_dbeta;
+    a.N = N;
+    a.n_pop = P;
+    a.gpop0 = (uint32_t)(e->replica0 / N);
+    a.seed_lo = (uint32_t)e->seed;
+    a.seed_hi = (uint32_t)(e->seed >> 32);
+    a.round = round;
+    HIPCHK(sga::launch_resample_plan(a, st));
+    HIPCHK(sga::launch_resample_copy(a.parent, a.take_best, e->spins, e->energy, e->best_spins, e->best_energy, e->sstride, R, st));
+    e->fields_valid = false;  // (as after sga_set_spins: the next sweep seeds the cached fields again)
+    bool wait = false;
+    if (parents) {
+        HIPCHK(hipMemcpyAsync(parents, a.parent, (size_t)R * sizeof(int32_t), hipMemcpyDefault, st));
+        wait = wait || !is_device_ptr(parents);
+    }
+    if (shift) {
+        HIPCHK(hipMemcpyAsync(shift, a.shift, (size_t)P * sizeof(double), hipMemcpyDefault, st));
+        wait = wait || !is_device_ptr(shift);
+    }
+    if (weight_sum) {
+        HIPCHK(hipMemcpyAsync(weight_sum, a.sum, (size_t)P * sizeof(uint64_t), hipMemcpyDefault, st));
+        wait = wait || !is_device_ptr(weight_sum);
+    }
+    if (wait) HIPCHK(hipStreamSynchronize(st));
+    return SGA_OK;
+}
+
 int sga_get_route_query(sga_engine *e, sga_route_query *out) {
     if (!e || !out) return fail(SGA_ERR_INVALID, "NULL argument");
     if (e->n <= 0) return fail(SGA_ERR_INVALID, "no couplings set");

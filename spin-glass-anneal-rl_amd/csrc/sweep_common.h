@@ -141,6 +141,13 @@ __device__ __forceinline__ uint32_t cluster_seed_word(uint32_t round, uint32_t g
     return philox4x32_10(0u, round, ga < gb ? ga : gb, DOMAIN_CLUSTER, seed_lo, seed_hi).x;
 }
 
+// The one draw of a resampling step (sga_resample) of the population with global index gpop in round `round`: words 0
+// and 1 of block 0 at (round, gpop, DOMAIN_RESAMPLE) as U = (word 0 << 32) | word 1; the offset is (U * S) >> 64.
+__device__ __forceinline__ uint64_t resample_draw(uint32_t round, uint32_t gpop, uint32_t seed_lo, uint32_t seed_hi) {
+    const u32x4 w = philox4x32_10(0u, round, gpop, DOMAIN_RESAMPLE, seed_lo, seed_hi);
+    return ((uint64_t)w.x << 32) | (uint64_t)w.y;
+}
+
 // The accept rule.  dot = fp32 coupling dot product J[site,:].s (already rounded to fp32),
 // si = s[site] (+-1).  Returns true if the spin flips; dE receives the energy change of the
 // flip.

@@ -64,6 +64,12 @@ def _host_array(x, dtype, what):
     return np.ascontiguousarray(a, dtype=dtype)
 
 
+def resample_log_q(shift, weight_sum, members: int) -> np.ndarray:
+    """ln Q_p = shift[p] + ln(weight_sum[p] / (members * 2^40)) of sga_resample's two exact outputs, float64."""
+    w = np.asarray(weight_sum, np.uint64).astype(np.float64)
+    return np.asarray(shift, np.float64) + np.log(w / (float(members) * 2.0 ** 40))
+
+
 def concat_csr_batch(problems):
     """[(rowptr, colidx, val, h), ...] (numpy or torch, model-local columns) -> the one concatenated CSR of
     sga_set_csr_batch: (n_spins int32 [M], rowptr int64 [sum n + 1], colidx int32, val float32, h float32).
@@ -655,6 +661,46 @@ class AnnealEngine:
         if res is not None and not dev:
             res = res.reshape(self.n_ladders // 2, max(hi - lo, 0))
         return res
+
+    # ------------------------------------------------------------------ population annealing
+    def resample(self, dbeta, n_populations: int = 1, round: Optional[int] = None, parents=True):
+        """The resampling step of population annealing (sga_resample, csrc/resample.hip): the local replicas in
+        n_populations contiguous populations, every member copied or culled in proportion to exp(-dbeta E), planned and
+        copied on the device, exact in integers.  dbeta: a number or one per population.  round: the draw's coordinate,
+        None = the engine's exchange-round counter (counters()[1]).  Returns (parents, log_q): parents int32 [R], the
+        local index of every slot's parent (parents=False: None), and log_q float64 [n_populations], the free-energy
+        increments ln Q_p of the step.  With an int32 CUDA tensor of R entries for `parents` the call is only enqueued:
+        the tensor is filled on the device and log_q comes back as a CUDA tensor."""
+        P = int(n_populations)
+        try:
+            db = np.ascontiguousarray(np.broadcast_to(np.asarray(dbeta, np.float64), (max(P, 0),)))
+        except ValueError:
+            raise AnnealingError("dbeta must be a number or hold one entry per population") from None
+        rnd = self.counters()[1] if round is None else int(round)
+        N_ = self.R // P if P > 0 and self.R % P == 0 else 0
+        on_device = _is_tensor(parents)
+        if on_device:
+            if not parents.is_cuda or parents.dtype != torch.int32 or parents.numel() != self.R or not parents.is_contiguous():
+                raise AnnealingError(f"parents must be True, False or a contiguous int32 CUDA tensor of {self.R} entries")
+            shift = torch.zeros(max(P, 1), dtype=torch.float64, device=parents.device)
+            wsum = torch.zeros(max(P, 1), dtype=torch.int64, device=parents.device)
+            if not self.shares_torch_stream():
+                _producer_done(parents)
+            pp, sp, wp = C.c_void_p(parents.data_ptr()), C.c_void_p(shift.data_ptr()), C.c_void_p(wsum.data_ptr())
+            res = parents
+        else:
+            res = np.zeros(self.R, np.int32) if parents else None
+            shift, wsum = np.zeros(max(P, 1), np.float64), np.zeros(max(P, 1), np.uint64)
+            pp = None if res is None else res.ctypes.data_as(C.c_void_p)
+            sp, wp = shift.ctypes.data_as(C.c_void_p), wsum.ctypes.data_as(C.c_void_p)
+        N.check(self._lib.sga_resample(self._h, P, db.ctypes.data_as(C.c_void_p), rnd & 0xFFFFFFFF, pp, sp, wp), "sga_resample")
+        if on_device:
+            self._observable_done(True)
+            self._pending = (res, shift, wsum)
+            w = wsum.to(torch.float64)
+            w = torch.where(w < 0, w + 2.0 ** 64, w)  # (S up to 2^63 as an unsigned word)
+            return res, shift + torch.log(w / (N_ * 2.0 ** 40))
+        return res, resample_log_q(shift, wsum, N_)
 
     # ------------------------------------------------------------------ state access
     def energies(self) -> np.ndarray:
