@@ -114,7 +114,9 @@ def one_sparse_graph_many_fields(L=12, n_fields=8, n_replicas=4):
 def frustrated_lattice_with_cluster_moves(L=10):
     """Parallel tempering on a 3-D +-J lattice with isoenergetic cluster moves: two copies of the ladder run side by side,
     and after every exchange round the copies trade, slot by slot, the connected component of differing sites around
-    one drawn site (AnnealEngine.cluster_move_ladders) -- rejection free, E_a + E_b conserved, sparse couplings only."""
+    one drawn site (AnnealEngine.cluster_move_ladders) -- rejection free, E_a + E_b conserved, sparse couplings only.
+    measure_overlaps: after each of those rounds, from sweep 100 on, the spin and link overlap between the copies goes
+    into histograms per temperature that stay on the device (AnnealEngine.accumulate_ladder_overlaps)."""
     rs = np.random.RandomState(4)
     idx = np.arange(L ** 3).reshape(L, L, L)
     J = np.zeros((L ** 3, L ** 3), np.float32)
@@ -124,11 +126,16 @@ def frustrated_lattice_with_cluster_moves(L=10):
     model = IsingModel(IsingModelConfig(n_spins=L ** 3, use_sparse=True))
     model.set_couplings_from_matrix(torch.from_numpy(J))
     cfg = ParallelTemperingConfig(n_replicas=16, n_sweeps=500, temp_min=0.2, temp_max=3.0, exchange_interval=10, random_seed=42,
-                                  n_copies=2, cluster_moves=True, cluster_temp_max=1.2)
+                                  n_copies=2, cluster_moves=True, cluster_temp_max=1.2,
+                                  measure_overlaps=True, measure_after=100, overlap_bins=64)
     pt = ParallelTempering(cfg)
     result = pt.run(model)
     print(f"PT + cluster moves, {L}^3 +-J lattice: best energy {result.best_energy:.1f}; {pt.cluster_moves_flipped} of "
           f"{pt.cluster_moves_made} moves flipped {pt.cluster_sites_flipped} sites, largest cluster {pt.cluster_size_max}")
+    st = pt.overlap_statistics
+    print(f"  overlaps between the copies over {pt.overlap_rounds_measured} rounds, coldest / hottest temperature: <q^2> "
+          f"{st.moments()[0][-1]:.3f} / {st.moments()[0][0]:.3f}, Binder {st.binder()[-1]:.2f} / {st.binder()[0]:.2f}, "
+          f"link overlap {st.link_overlap()[-1]:.3f} / {st.link_overlap()[0]:.3f}")
 
 
 def frustrated_lattice_by_population_annealing(L=8):

@@ -80,7 +80,7 @@ typedef struct sga_engine sga_engine;
 int sga_create(int device, sga_engine **out);
 void sga_destroy(sga_engine *e);
 const char *sga_last_error(void);
-int sga_version(void);  /* 2500: sga_cluster_move_pairs / sga_cluster_move_ladders (isoenergetic cluster moves between replica copies on sparse couplings, csrc/cluster_moves.hip; no engine state, no option); 2400: sga_set_replica_groups / sga_get_replica_groups; 2300: sga_get_magnetizations / sga_get_overlaps / sga_get_overlaps_with (replica observables on the device: the exact integer product of int8 spin rows on the matrix cores, csrc/observables.hip; read only, no engine state); 2200: the row-shared fields in tiles take a plan of their own, one launch per sweep (csrc/sweep_dense_rs.hip, rs_tile_plan_kernel; no change of interface or results); 2100: sga_set_sequential_windows / sga_get_sequential_windows (SGA_SITE_SEQUENTIAL sweeps in windows, the fields of every replica on the matrix cores; csrc/sweep_dense_seq.hip); 2000: the row-shared windows (option "row_shared") serve SGA_RULE_GLAUBER and SGA_RULE_HEAT_BATH too ("rule=glauber" / "rule=heat-bath" in sga_describe and sga_get_last_kernel; the window sga_autotune picks holds for the rule it was timed under); 1900: options "row_shared_fields" and "row_shared_tile_sites" (row-shared fields in tiles of sites, sign-only rows); 1800: option "row_shared_grid", sga_route_query.rs_grid; 1700: sga_set_csr_shared (one set of CSR rows, many field vectors: every one-wave-per-replica CSR form for such batches), sga_route_query.shared_j on SGA_ROUTE_CSR queries; 1600: sga_set_dense_shared (one coupling matrix, many field vectors; row-shared windows, bit-planes and the matrix-core pass for such batches), sga_route_query.shared_j; 1500: sga_get_scan_summary, and sga_set_dense / sga_set_dense_batch / sga_set_csr / sga_set_csr64 / sga_set_csr_batch refuse a NaN or +-Inf in J or h (SGA_ERR_INVALID, "non-finite"); 1400: option "batch_fixed_point" (fixed-point cached local fields for many-model dense batches); 1300: options "ragged_field_cache" and "clf_fixed_point" together (fixed-point cached local fields for ragged CSR batches); 1200: sga_set_groups_csr (group couplings plus a stored sparse remainder); 1100: option "ragged_field_cache" (cached local fields for ragged CSR batches); 1000: sga_set_groups */
+int sga_version(void);  /* 2700: sga_get_link_count / sga_get_pair_overlaps / sga_accumulate_ladder_overlaps (spin and link overlaps between pairs of replicas, histogrammed per temperature on the device, csrc/pair_overlaps.hip; read only, no engine state, no option); 2600: sga_resample (the resampling step of population annealing, csrc/resample.hip); 2500: sga_cluster_move_pairs / sga_cluster_move_ladders (isoenergetic cluster moves between replica copies on sparse couplings, csrc/cluster_moves.hip; no engine state, no option); 2400: sga_set_replica_groups / sga_get_replica_groups; 2300: sga_get_magnetizations / sga_get_overlaps / sga_get_overlaps_with (replica observables on the device: the exact integer product of int8 spin rows on the matrix cores, csrc/observables.hip; read only, no engine state); 2200: the row-shared fields in tiles take a plan of their own, one launch per sweep (csrc/sweep_dense_rs.hip, rs_tile_plan_kernel; no change of interface or results); 2100: sga_set_sequential_windows / sga_get_sequential_windows (SGA_SITE_SEQUENTIAL sweeps in windows, the fields of every replica on the matrix cores; csrc/sweep_dense_seq.hip); 2000: the row-shared windows (option "row_shared") serve SGA_RULE_GLAUBER and SGA_RULE_HEAT_BATH too ("rule=glauber" / "rule=heat-bath" in sga_describe and sga_get_last_kernel; the window sga_autotune picks holds for the rule it was timed under); 1900: options "row_shared_fields" and "row_shared_tile_sites" (row-shared fields in tiles of sites, sign-only rows); 1800: option "row_shared_grid", sga_route_query.rs_grid; 1700: sga_set_csr_shared (one set of CSR rows, many field vectors: every one-wave-per-replica CSR form for such batches), sga_route_query.shared_j on SGA_ROUTE_CSR queries; 1600: sga_set_dense_shared (one coupling matrix, many field vectors; row-shared windows, bit-planes and the matrix-core pass for such batches), sga_route_query.shared_j; 1500: sga_get_scan_summary, and sga_set_dense / sga_set_dense_batch / sga_set_csr / sga_set_csr64 / sga_set_csr_batch refuse a NaN or +-Inf in J or h (SGA_ERR_INVALID, "non-finite"); 1400: option "batch_fixed_point" (fixed-point cached local fields for many-model dense batches); 1300: options "ragged_field_cache" and "clf_fixed_point" together (fixed-point cached local fields for ragged CSR batches); 1200: sga_set_groups_csr (group couplings plus a stored sparse remainder); 1100: option "ragged_field_cache" (cached local fields for ragged CSR batches); 1000: sga_set_groups */
 /* Run on an existing HIP stream (e.g. torch.cuda.current_stream().cuda_stream); NULL = the
  * engine's own stream (default). */
 int sga_set_stream(sga_engine *e, void *hip_stream);
@@ -471,6 +471,54 @@ int sga_resample(sga_engine *e, int n_populations, const double *dbeta /* host [
                  int32_t *parents   /* [R_local] local indices, host or device, or NULL */,
                  double *shift      /* [n_populations] x_max, host or device, or NULL */,
                  uint64_t *weight_sum /* [n_populations] S, host or device, or NULL */);
+
+/* ---- spin and link overlaps between pairs of replicas (version >= 2700; csrc/pair_overlaps.hip) ----------------------
+ * What a sampler with two copies of a ladder measures per temperature -- P(q), <q^2>, the Binder ratio, the link overlap
+ * q_l -- as exact integer counts formed where the spins are.  For a pair (a, b) of local replicas let
+ * x_i = [s_a[i] != s_b[i]] for the sites i < n:
+ *   d = sum_i x_i, the distance: n q_ab = n - 2 d (int32).
+ *   A LINK is an entry (i, j) of the engine's packed rows whose value is not +-0, with j != i and 0 <= j < n: the entries
+ *   the isoenergetic cluster move connects through.  Padding of long-row layouts and stored zeros are none; a stored
+ *   diagonal entry is none; both triangles count as they are stored (a symmetric matrix has every bond twice).  Packing
+ *   keeps every input entry as it came ("duplicates add up" in a row sum, they are not merged): a duplicate (i, j) is
+ *   TWO links.  L = the number of links, a constant of the problem (sga_get_link_count; int64: a graph may hold more
+ *   than 2^31 entries).
+ *   b = the number of links with x_i != x_j, the broken links: L q_l = L - 2 b (int64).
+ *   The pair form takes any list of pairs: the call only reads, so a replica may stand in many pairs, and a == b is a
+ *   pair (d = b = 0).  dist and broken: host or device, one of them may be NULL.
+ *   The ladder form takes the pairs of sga_cluster_move_ladders: ladders 2c and 2c + 1, slots slot_lo <= s < slot_hi, the
+ *   replicas that hold them read from the slot map ON THE DEVICE; it needs an even n_ladders and R_local == R_global.
+ *   The cell of pair c and slot s is k = c (slot_hi - slot_lo) + (s - slot_lo); the call adds exactly 1 to
+ *   hist_q[k bins_q + min(d >> q_shift, bins_q - 1)] and, where hist_l is given, to
+ *   hist_l[k bins_l + min(b >> l_shift, bins_l - 1)].  The clamp keeps the store inside the cell for any bin count; the
+ *   exact layout is shift 0 with n + 1 (L + 1) bins.  The histograms are the CALLER'S DEVICE BUFFERS, [cells][bins]
+ *   uint64, zeroed by the caller once: the engine keeps nothing between calls and never zeroes them; one workgroup owns
+ *   one cell per launch, so the count is a plain load / add / store, deterministic.
+ *   Served -- d: every kind of problem (ragged batches: rows are zero past a model's own sites and never differ there).
+ *   b, hist_l and sga_get_link_count: the problems the cluster move serves -- one-model CSR (sga_set_csr, sga_set_csr64,
+ *   a sparse matrix that sga_set_dense kept as CSR) and sga_set_csr_shared, where a pair under two field vectors is
+ *   served too (the graph is one).  SGA_ERR_UNSUPPORTED, with the reason in sga_last_error: a non-NULL broken or hist_l,
+ *   or sga_get_link_count, on dense couplings, sga_set_tsp, sga_set_groups / sga_set_groups_csr or ragged batches; links
+ *   with n beyond the kernel's bitmap of differing sites in LDS (n / 8 bytes of the 160 KiB: n <= 1 308 160).  Without
+ *   links no bitmap is built and no bound on n applies.
+ *   SGA_ERR_INVALID: a NULL engine; no problem or no replicas; which outside {SGA_SPINS_CURRENT, SGA_SPINS_BEST};
+ *   count < 0, or a NULL pair list with count > 0; a pair list on the device; an index outside [0, R_local); dist and
+ *   broken both NULL; a NULL n_links; bins < 1; a shift outside [0, 31]; a NULL or host hist_q, a host hist_l; no ladder,
+ *   an odd n_ladders, R_local != R_global, a slot range not inside [0, slots).  count == 0 and an empty slot range are
+ *   no-ops.  Every refusal happens before anything is enqueued or written.
+ *   Read only: no spin, energy, best, counter, cached field, window plan, slot map or sga_get_last_kernel changes, and a
+ *   run with these calls between its sweeps walks the same chain.  The work is enqueued on the engine's stream behind
+ *   earlier sweeps; with device outputs the call returns at once, with a host output after its copy has landed. */
+int sga_get_link_count(sga_engine *e, int64_t *n_links /* host or device */);
+/* pairs: host [count][2] int32 LOCAL replica indices */
+int sga_get_pair_overlaps(sga_engine *e, int which /* SGA_SPINS_CURRENT | SGA_SPINS_BEST */,
+                          const int32_t *pairs /* host [count][2], LOCAL indices */, int count,
+                          int32_t *dist /* [count], host or device, or NULL */,
+                          int64_t *broken /* [count], host or device, or NULL */);
+/* the CURRENT spins; hist_q [n_ladders/2][slot_hi - slot_lo][bins_q], hist_l [...][bins_l]: device, uint64 */
+int sga_accumulate_ladder_overlaps(sga_engine *e, int slot_lo, int slot_hi,
+                                   uint64_t *hist_q, int bins_q, int q_shift,
+                                   uint64_t *hist_l /* or NULL */, int bins_l, int l_shift);
 
 /* Stateless operator form of CUDAKernelManager.parallel_tempering_exchange_optimized
  * (annealing/cuda_kernels.py:326-369, fallback :415-443): sequential adjacent pairs, fp32,

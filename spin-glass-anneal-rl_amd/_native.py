@@ -78,6 +78,9 @@ SYMBOLS = [
     ("sga_cluster_move_pairs", _i, [_p, _p, _i, _u32, _p]),
     ("sga_cluster_move_ladders", _i, [_p, _i, _i, _u32, _p]),
     ("sga_resample", _i, [_p, _i, _p, _u32, _p, _p, _p]),
+    ("sga_get_link_count", _i, [_p, _p]),
+    ("sga_get_pair_overlaps", _i, [_p, _i, _p, _i, _p, _p]),
+    ("sga_accumulate_ladder_overlaps", _i, [_p, _i, _i, _p, _i, _i, _p, _i, _i]),
     ("sga_op_pt_exchange", _i, [_i, _p, _p, _p, _p, _u64, _u32, _i, _i, C.POINTER(_i)]),
     ("sga_get_energies", _i, [_p, _p]),
     ("sga_get_energies_async", _i, [_p, _p]),

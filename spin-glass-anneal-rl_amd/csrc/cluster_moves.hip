@@ -21,17 +21,6 @@ namespace {
 
 constexpr int CLUSTER_GROUP = 16;  // lanes that share one row
 
-// bit q of the result: the sign bits (bit 7) of byte q of the four dwords differ between x and y, i.e. s_a != s_b
-__device__ __forceinline__ unsigned int diff_bits16(const int4 x, const int4 y) {
-    const unsigned int d[4] = {(unsigned)(x.x ^ y.x), (unsigned)(x.y ^ y.y), (unsigned)(x.z ^ y.z), (unsigned)(x.w ^ y.w)};
-    unsigned int b = 0;
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-        b |= ((d[q] >> 7) & 1u) << (4 * q) | ((d[q] >> 15) & 1u) << (4 * q + 1) | ((d[q] >> 23) & 1u) << (4 * q + 2) |
-             ((d[q] >> 31) & 1u) << (4 * q + 3);
-    return b;
-}
-
 // the sum of v over the workgroup's 256 threads, in every thread (red: 4 ints of LDS; two barriers)
 __device__ __forceinline__ int block_sum(int v, int *red) {
     const int w = wave_sum(v);

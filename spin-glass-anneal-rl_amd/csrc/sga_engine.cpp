@@ -347,6 +347,9 @@ extern "C" {
 
 const char *sga_last_error(void) { return g_last_error.c_str(); }
 // The ABI version, one line per step:
+//   2700:    + sga_get_link_count / sga_get_pair_overlaps / sga_accumulate_ladder_overlaps: spin and link overlaps between
+//            pairs of replicas, the pairs of two ladders read from the slot map and histogrammed on the device
+//            (pair_overlaps.hip; host side in sga_state.cpp); read only, no engine state, no option
 //   2600:    + sga_resample: the resampling step of population annealing, planned and copied on the device, exact in
 //            integers (resample.hip; host side in sga_state.cpp); no engine state, no option
 //   2500:    + sga_cluster_move_pairs / sga_cluster_move_ladders: isoenergetic cluster moves between two replicas of one
@@ -383,7 +386,7 @@ const char *sga_last_error(void) { return g_last_error.c_str(); }
 //   600:     + sga_set_csr_batch / sga_get_batch_model (ragged CSR batches)
 //   round 5: + sga_explain_route / sga_get_route_query, sga_get_last_kernel, sga_get_autotune_table, ladder-local
 //            sga_exchange
-int sga_version(void) { return 2600; }
+int sga_version(void) { return 2700; }
 
 int sga_create(int device, sga_engine **out) {
     if (!out) return fail(SGA_ERR_INVALID, "out is NULL");

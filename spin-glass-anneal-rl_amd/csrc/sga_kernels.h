@@ -847,6 +847,64 @@ hipError_t launch_resample_plan(const ResampleArgs &a, hipStream_t st);
 hipError_t launch_resample_copy(const int32_t *parent, const int *take_best, int8_t *spins, double *energy, int8_t *best_spins,
                                 double *best_energy, int sstride, int R, hipStream_t st);
 
+// Spin and link overlaps between pairs of replicas (pair_overlaps.hip; sga_get_pair_overlaps /
+// sga_accumulate_ladder_overlaps / sga_get_link_count): one workgroup of 256 threads per pair.  d = the sites where the
+// two replicas differ; with links asked for the diff words also go to a bitmap of ceil(n / 32) words in LDS, and groups
+// of lanes walk the rows of cv counting the links (the entries cluster_moves_kernel follows: value not +-0, j != i,
+// 0 <= j < n) whose two ends differ in x -- the broken links b.  Read only.
+constexpr int PAIR_OVERLAP_THREADS = 256;
+constexpr size_t PAIR_OVERLAP_LDS_FIXED = 64;  // wave sums of d (4 ints) and of b (4 64-bit words), in front of the bitmap
+// the kernel's LDS: without links the fixed part alone
+inline size_t pair_overlap_lds_bytes(long long n, bool links) {
+    return PAIR_OVERLAP_LDS_FIXED + (links ? 4 * (size_t)((n + 31) / 32) : 0);
+}
+// the largest n whose diff bitmap (n / 8 bytes) fits the budget the cluster move allows itself: 1 308 160 sites
+constexpr long long PAIR_OVERLAP_MAX_N = (long long)((CLUSTER_LDS_BUDGET - PAIR_OVERLAP_LDS_FIXED) / 4) * 32;
+// Lanes that share one row, as log2: the smallest power of two that holds the layout's mean row (entries / n), from 1
+// (a lane a row) to 64 (a wave a row).  A degree-6 lattice gets 8 lanes, a slotted layout of long rows a whole wave; a
+// hub among short rows is walked by its few lanes in more steps.
+inline int pair_overlap_group_log2(long long entries, long long n) {
+    int g = 0;
+    while (g < 6 && (long long)(1 << g) * n < entries) ++g;
+    return g;
+}
+// The pair list of sga_get_pair_overlaps, checked on the host before anything is enqueued: nullptr, or what is wrong
+// with it.  The call only reads: a replica may stand in many pairs, and a == b is a pair (d = b = 0).
+inline const char *pair_overlap_pairs_check(const int32_t *pairs, int count, int R) {
+    if (count < 0) return "count is negative";
+    if (count > 0 && !pairs) return "pairs is NULL";
+    for (int k = 0; k < 2 * count; ++k)
+        if (pairs[k] < 0 || pairs[k] >= R) return "replica index out of range";
+    return nullptr;
+}
+// The histogram arguments of sga_accumulate_ladder_overlaps (whether the buffers lie on the device is the caller's look)
+inline const char *pair_overlap_hist_check(bool have_q, int bins_q, int q_shift, bool have_l, int bins_l, int l_shift) {
+    if (!have_q) return "hist_q is NULL";
+    if (bins_q < 1 || (have_l && bins_l < 1)) return "a histogram needs at least one bin";
+    if (q_shift < 0 || q_shift > 31 || (have_l && (l_shift < 0 || l_shift > 31))) return "a bin shift lies outside [0, 31]";
+    return nullptr;
+}
+struct PairOverlapArgs {
+    const int8_t *spins;         // [R][sstride] the observed rows (current or best), sstride a multiple of 16
+    const long long *rowptr64;   // [n + 1], links only
+    const int2 *cv;              // (column, value bits), links only
+    const int32_t *pairs;        // pair form: [count][2] local replicas
+    const int32_t *slot_to_rep;  // ladder form (pairs == null): the slot map, [n_ladders][L] global ids
+    int L, slot_lo, n_slots;     // ... pair p: ladders 2 (p / n_slots) and 2 (p / n_slots) + 1, slot slot_lo + p % n_slots
+    int32_t *dist;               // pair form: [count] d, or null
+    long long *broken;           // pair form: [count] b, or null
+    unsigned long long *hist_q;  // ladder form: [count][bins_q], cell p bin min(d >> q_shift, bins_q - 1) grows by one
+    unsigned long long *hist_l;  // ... [count][bins_l] of b, or null
+    int bins_q, q_shift, bins_l, l_shift;
+    int links;                   // b is asked for: the bitmap and the walk
+    int group_log2;              // lanes to a row
+    int n, sstride, R, count, replica0;
+};
+hipError_t launch_pair_overlaps(const PairOverlapArgs &a, hipStream_t st);
+// *out += the number of links of the layout (out zeroed by the caller, on the device)
+hipError_t launch_link_count(const long long *rowptr64, const int2 *cv, int n, int group_log2, unsigned long long *out,
+                             hipStream_t st);
+
 // operator-form PT exchange (cuda_kernels.py:415-443): decide sequentially, then permute rows
 hipError_t launch_op_exchange(float *spins, float *tmp_rows, float *energies, const float *temps,
                               const float *u, int32_t *src_of_pos, int *n_accepted,

@@ -851,6 +851,104 @@ int sga_resample(sga_engine *e, int n_populations, const double *dbeta, uint32_t
     return SGA_OK;
 }
 
+// ---- spin and link overlaps between pairs of replicas (pair_overlaps.hip) ----------------------
+// Read only, under the rule of the replica observables above: a host pair list is staged in point_sites, host results
+// leave through point_out (both grow-only), and nothing else of the engine is written.
+namespace {
+// nullptr where the engine's stored rows are ones the link walk serves (the cluster move's problems; the graph of
+// sga_set_csr_shared is one, whatever the field vectors), else why not
+const char *links_refusal(const sga_engine *e) {
+    if (e->tsp) return "link overlaps are not implemented for sga_set_tsp problems (no stored rows to walk)";
+    if (e->groups) return "link overlaps are not implemented for sga_set_groups / sga_set_groups_csr problems (no stored rows to walk)";
+    if (e->ragged) return "link overlaps are not implemented for ragged CSR batches";
+    if (!e->csr || !e->rowptr64 || !e->cv) return "link overlaps need sparse (CSR) couplings: dense couplings have no stored links";
+    if (e->n > sga::PAIR_OVERLAP_MAX_N) return "link overlaps: the bitmap of n differing sites does not fit LDS (n / 8 bytes of 160 KiB)";
+    return nullptr;
+}
+int link_group_log2(const sga_engine *e) { return sga::pair_overlap_group_log2(e->layout_entries, e->n); }
+}  // namespace
+
+int sga_get_link_count(sga_engine *e, int64_t *n_links) {
+    if (!e || !n_links) return fail(SGA_ERR_INVALID, "NULL argument");
+    if (const char *why = observables_ready(e)) return fail(SGA_ERR_INVALID, why);
+    if (const char *why = links_refusal(e)) return fail(SGA_ERR_UNSUPPORTED, why);
+    HIPCHK(hipSetDevice(e->device));
+    HIPCHK(e->point_out.reserve(sizeof(unsigned long long)));
+    unsigned long long *d = static_cast<unsigned long long *>(e->point_out.ptr);
+    HIPCHK(hipMemsetAsync(d, 0, sizeof(unsigned long long), e->stream));
+    HIPCHK(sga::launch_link_count(e->rowptr64, e->cv, e->n, link_group_log2(e), d, e->stream));
+    HIPCHK(hipMemcpyAsync(n_links, d, sizeof(int64_t), hipMemcpyDefault, e->stream));
+    if (!is_device_ptr(n_links)) HIPCHK(hipStreamSynchronize(e->stream));
+    return SGA_OK;
+}
+
+int sga_get_pair_overlaps(sga_engine *e, int which, const int32_t *pairs, int count, int32_t *dist, int64_t *broken) {
+    if (!e) return fail(SGA_ERR_INVALID, "engine is NULL");
+    if (const char *why = observables_ready(e)) return fail(SGA_ERR_INVALID, why);
+    if (!observed_which(which)) return fail(SGA_ERR_INVALID, "which must be SGA_SPINS_CURRENT or SGA_SPINS_BEST");
+    if (!dist && !broken) return fail(SGA_ERR_INVALID, "dist and broken are both NULL");
+    if (pairs && is_device_ptr(pairs)) return fail(SGA_ERR_INVALID, "pairs must be a host buffer");
+    if (const char *why = sga::pair_overlap_pairs_check(pairs, count, e->R)) return fail(SGA_ERR_INVALID, why);
+    if (broken)
+        if (const char *why = links_refusal(e)) return fail(SGA_ERR_UNSUPPORTED, why);
+    if (count == 0) return SGA_OK;
+    HIPCHK(hipSetDevice(e->device));
+    hipStream_t st = e->stream;
+    const size_t cnt = (size_t)count;
+    // (a pageable host list: the copy has left the caller's buffer when the call returns)
+    HIPCHK(e->point_sites.reserve(2 * cnt * sizeof(int32_t)));
+    HIPCHK(hipMemcpyAsync(e->point_sites.ptr, pairs, 2 * cnt * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    const bool dist_host = dist && !is_device_ptr(dist), broken_host = broken && !is_device_ptr(broken);
+    // host results: [count] int64 b, then [count] int32 d
+    if (dist_host || broken_host) HIPCHK(e->point_out.reserve(cnt * (sizeof(int64_t) + sizeof(int32_t))));
+    long long *stage_b = static_cast<long long *>(e->point_out.ptr);
+    int32_t *stage_d = reinterpret_cast<int32_t *>(stage_b + cnt);
+    sga::PairOverlapArgs a{};
+    a.spins = observed_rows(e, which);
+    a.pairs = static_cast<const int32_t *>(e->point_sites.ptr);
+    a.dist = dist_host ? stage_d : dist;
+    a.broken = broken_host ? stage_b : reinterpret_cast<long long *>(broken);
+    a.links = broken ? 1 : 0;
+    if (a.links) a.rowptr64 = e->rowptr64, a.cv = e->cv, a.group_log2 = link_group_log2(e);
+    a.n = e->n, a.sstride = e->sstride, a.R = e->R, a.count = count, a.replica0 = e->replica0;
+    HIPCHK(sga::launch_pair_overlaps(a, st));
+    if (dist_host) HIPCHK(hipMemcpyAsync(dist, stage_d, cnt * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    if (broken_host) HIPCHK(hipMemcpyAsync(broken, stage_b, cnt * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    if (dist_host || broken_host) HIPCHK(hipStreamSynchronize(st));
+    return SGA_OK;
+}
+
+int sga_accumulate_ladder_overlaps(sga_engine *e, int slot_lo, int slot_hi, uint64_t *hist_q, int bins_q, int q_shift,
+                                   uint64_t *hist_l, int bins_l, int l_shift) {
+    if (!e) return fail(SGA_ERR_INVALID, "engine is NULL");
+    if (const char *why = observables_ready(e)) return fail(SGA_ERR_INVALID, why);
+    if (const char *why = sga::pair_overlap_hist_check(hist_q != nullptr, bins_q, q_shift, hist_l != nullptr, bins_l, l_shift))
+        return fail(SGA_ERR_INVALID, why);
+    if (!is_device_ptr(hist_q) || (hist_l && !is_device_ptr(hist_l)))
+        return fail(SGA_ERR_INVALID, "the histograms must be device buffers (they stay on the device for the whole run)");
+    if (e->n_ladders <= 0 || !e->slot_to_rep) return fail(SGA_ERR_INVALID, "no ladder (call sga_set_ladder)");
+    if (e->n_ladders % 2 != 0) return fail(SGA_ERR_INVALID, "overlaps between ladders need an even number of ladders");
+    if (e->R != e->Rg) return fail(SGA_ERR_INVALID, "overlaps between ladders need every replica on this rank (R_local == R_global)");
+    const int L = e->Rg / e->n_ladders;
+    if (slot_lo < 0 || slot_hi > L || slot_lo > slot_hi) return fail(SGA_ERR_INVALID, "slot range outside [0, slots)");
+    if (hist_l)
+        if (const char *why = links_refusal(e)) return fail(SGA_ERR_UNSUPPORTED, why);
+    if (slot_lo == slot_hi) return SGA_OK;
+    HIPCHK(hipSetDevice(e->device));
+    sga::PairOverlapArgs a{};
+    a.spins = e->spins;
+    a.slot_to_rep = e->slot_to_rep;
+    a.L = L, a.slot_lo = slot_lo, a.n_slots = slot_hi - slot_lo;
+    a.hist_q = reinterpret_cast<unsigned long long *>(hist_q);
+    a.hist_l = reinterpret_cast<unsigned long long *>(hist_l);
+    a.bins_q = bins_q, a.q_shift = q_shift, a.bins_l = hist_l ? bins_l : 1, a.l_shift = hist_l ? l_shift : 0;
+    a.links = hist_l ? 1 : 0;
+    if (a.links) a.rowptr64 = e->rowptr64, a.cv = e->cv, a.group_log2 = link_group_log2(e);
+    a.n = e->n, a.sstride = e->sstride, a.R = e->R, a.count = (e->n_ladders / 2) * a.n_slots, a.replica0 = e->replica0;
+    HIPCHK(sga::launch_pair_overlaps(a, e->stream));
+    return SGA_OK;
+}
+
 int sga_get_route_query(sga_engine *e, sga_route_query *out) {
     if (!e || !out) return fail(SGA_ERR_INVALID, "NULL argument");
     if (e->n <= 0) return fail(SGA_ERR_INVALID, "no couplings set");

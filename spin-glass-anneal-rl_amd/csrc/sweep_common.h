@@ -141,6 +141,18 @@ __device__ __forceinline__ uint32_t cluster_seed_word(uint32_t round, uint32_t g
     return philox4x32_10(0u, round, ga < gb ? ga : gb, DOMAIN_CLUSTER, seed_lo, seed_hi).x;
 }
 
+// Where two replicas differ, 16 sites a load (cluster_moves.hip, pair_overlaps.hip): bit q of the result is set where the
+// sign bits (bit 7) of byte q of the four dwords differ between x and y, i.e. s_a != s_b
+__device__ __forceinline__ unsigned int diff_bits16(const int4 x, const int4 y) {
+    const unsigned int d[4] = {(unsigned)(x.x ^ y.x), (unsigned)(x.y ^ y.y), (unsigned)(x.z ^ y.z), (unsigned)(x.w ^ y.w)};
+    unsigned int b = 0;
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+        b |= ((d[q] >> 7) & 1u) << (4 * q) | ((d[q] >> 15) & 1u) << (4 * q + 1) | ((d[q] >> 23) & 1u) << (4 * q + 2) |
+             ((d[q] >> 31) & 1u) << (4 * q + 3);
+    return b;
+}
+
 // The one draw of a resampling step (sga_resample) of the population with global index gpop in round `round`: words 0
 // and 1 of block 0 at (round, gpop, DOMAIN_RESAMPLE) as U = (word 0 << 32) | word 1; the offset is (U * S) >> 64.
 __device__ __forceinline__ uint64_t resample_draw(uint32_t round, uint32_t gpop, uint32_t seed_lo, uint32_t seed_hi) {

@@ -859,6 +859,77 @@ class AnnealEngine:
             self._pending = (keep, res)  # a converted device operand stays alive while the kernel is queued
         return res
 
+    # ------------------------------------------------------------------ spin and link overlaps between pairs
+    # csrc/pair_overlaps.hip: exact integer counts per pair -- d differing sites (n q = n - 2 d), b broken links
+    # (L q_l = L - 2 b) over the stored rows -- read only, stream ordered behind the sweeps.
+    def link_count(self) -> int:
+        """L: the links of the stored rows (sga_get_link_count) -- entries with a value that is not +-0, j != i, both
+        triangles as stored.  Sparse (CSR) couplings only."""
+        out = np.zeros(1, np.int64)
+        N.check(self._lib.sga_get_link_count(self._h, out.ctypes.data_as(C.c_void_p)), "sga_get_link_count")
+        return int(out[0])
+
+    def _pair_out(self, out, count: int, dtype, what):
+        """(pointer, result, device?) of one output of pair_overlaps: None a fresh numpy array, else the caller's
+        contiguous CUDA tensor of `count` entries (ordered as overlaps(out=) orders its tensor)."""
+        if out is None:
+            res = np.zeros(count, np.int32 if dtype == "int32" else np.int64)
+            return res.ctypes.data_as(C.c_void_p), res, False
+        if not _is_tensor(out) or not out.is_cuda or out.dtype != getattr(torch, dtype) or out.numel() != count or \
+                not out.is_contiguous():
+            raise AnnealingError(f"{what} must be a contiguous {dtype} CUDA tensor of {count} entries")
+        if not self.shares_torch_stream():
+            _producer_done(out)
+        return C.c_void_p(out.data_ptr()), out, True
+
+    def pair_overlaps(self, pairs, which="current", links=True, dist=None, broken=None):
+        """(dist int32 [count], broken int64 [count] | None) of the pairs (a, b) of LOCAL replica indices
+        (sga_get_pair_overlaps): dist the sites where the two differ, broken the links whose two ends differ in that
+        (links=False: None, and every kind of problem is served).  Any list: a replica may stand in many pairs, a == b
+        gives zeros.  which: "current" | "best".  dist / broken: optional CUDA tensors (int32 / int64, `count` entries)
+        that receive the results on the device; with shares_torch_stream() the call is then only enqueued."""
+        w = self._which(which)
+        pr = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+        dp, dres, ddev = self._pair_out(dist, len(pr), "int32", "dist")
+        bp, bres, bdev = (None, None, False)
+        if links:
+            bp, bres, bdev = self._pair_out(broken, len(pr), "int64", "broken")
+        elif broken is not None:
+            raise AnnealingError("broken was given with links=False")
+        N.check(self._lib.sga_get_pair_overlaps(self._h, w, pr.ctypes.data_as(C.c_void_p), len(pr), dp, bp), "sga_get_pair_overlaps")
+        self._observable_done(ddev or bdev)
+        if ddev or bdev:
+            self._pending = (pr, dres, bres)  # device results stay alive while the work is queued
+        return dres, bres
+
+    def _hist(self, hist, cells, what):
+        if not _is_tensor(hist) or not hist.is_cuda or hist.dtype not in (torch.int64, getattr(torch, "uint64", torch.int64)) or \
+                hist.dim() != 3 or tuple(hist.shape[:2]) != cells or not hist.is_contiguous():
+            raise AnnealingError(f"{what} must be a contiguous uint64 or int64 CUDA tensor of shape [{cells[0]}, {cells[1]}, bins]")
+        if not self.shares_torch_stream():
+            _producer_done(hist)
+        return C.c_void_p(hist.data_ptr()), int(hist.shape[2])
+
+    def accumulate_ladder_overlaps(self, hist_q, hist_l=None, slot_lo: int = 0, slot_hi: Optional[int] = None,
+                                   q_shift: int = 0, l_shift: int = 0):
+        """One count per slot slot_lo <= s < slot_hi (None: every slot) and pair of ladders 2c, 2c + 1 into the caller's
+        histograms on the device (sga_accumulate_ladder_overlaps): between the replicas that hold slot s of both now --
+        read from the slot map on the device -- bin min(d >> q_shift, bins - 1) of hist_q[c, s - slot_lo] grows by one,
+        and, where hist_l is given (sparse couplings), bin min(b >> l_shift, bins - 1) of hist_l[c, s - slot_lo].
+        hist_q, hist_l: uint64 or int64 CUDA tensors [n_ladders / 2, slot_hi - slot_lo, bins], zeroed by the caller once;
+        the exact layout is shift 0 with n + 1 (link_count() + 1) bins.  Only enqueued: nothing comes back."""
+        if self.n_ladders <= 0:
+            raise AnnealingError("no ladder (call set_ladder)")
+        L = self.R_global // self.n_ladders
+        lo, hi = int(slot_lo), L if slot_hi is None else int(slot_hi)
+        cells = (self.n_ladders // 2, max(hi - lo, 0))
+        qp, bins_q = self._hist(hist_q, cells, "hist_q")
+        lp, bins_l = (None, 0) if hist_l is None else self._hist(hist_l, cells, "hist_l")
+        N.check(self._lib.sga_accumulate_ladder_overlaps(self._h, lo, hi, qp, bins_q, int(q_shift), lp, bins_l, int(l_shift)),
+                "sga_accumulate_ladder_overlaps")
+        self._observable_done(True)
+        self._pending = (hist_q, hist_l)
+
     def hamming(self, which_a="current", which_b=None) -> np.ndarray:
         """int32 [R, R]: Hamming distances (n_r - Q) / 2 between the configurations of overlaps(which_a, which_b), n_r the
         ROW replica's model size on ragged engines (a pair across models is meaningless there)."""

@@ -69,6 +69,14 @@ class ParallelTemperingConfig:
     cluster_moves: bool = False           # isoenergetic cluster moves between copies 2c and 2c + 1 at equal slots after every
     #                                       exchange round (AnnealEngine.cluster_move_ladders; sparse couplings, an even n_copies)
     cluster_temp_max: Optional[float] = None  # ... only in the slots whose temperature is at or below this (None: all)
+    measure_overlaps: bool = False        # histogram, per temperature, the spin overlap and (sparse couplings) the link overlap
+    #                                       between copies 2c and 2c + 1 on the device (AnnealEngine.accumulate_ladder_overlaps;
+    #                                       an even n_copies), after the exchange round and its cluster moves; read once at the
+    #                                       end into ParallelTempering.overlap_statistics.  Off: the run issues no such call
+    measure_after: int = 0                # ... only in exchange rounds with at least this many sweeps behind them
+    measure_interval: int = 1             # ... in every measure_interval-th of those rounds, the first one included
+    overlap_bins: Optional[int] = None    # ... None: exact, a bin per value (n + 1, links + 1); else the smallest power-of-two
+    #                                       bin width that needs at most this many bins
 
     def __post_init__(self):
         if self.site_order not in ("random", "sequential"):
@@ -82,6 +90,79 @@ class ParallelTemperingConfig:
             raise ConfigurationError("cluster_moves needs an even n_copies >= 2 (the moves act between two copies of the ladder)")
         if self.n_copies > 1 and self.exchange_method == "all_pairs":
             raise ConfigurationError('n_copies > 1 is not implemented for exchange_method="all_pairs"')
+        if self.measure_overlaps and (self.n_copies < 2 or self.n_copies % 2 != 0):
+            raise ConfigurationError("measure_overlaps needs an even n_copies >= 2 (the overlaps are taken between two copies of the ladder)")
+        if int(self.measure_after) != self.measure_after or self.measure_after < 0:
+            raise ConfigurationError("measure_after must be a non-negative number of sweeps")
+        if int(self.measure_interval) != self.measure_interval or self.measure_interval < 1:
+            raise ConfigurationError("measure_interval must be a positive number of exchange rounds")
+        if self.overlap_bins is not None and (int(self.overlap_bins) != self.overlap_bins or self.overlap_bins < 1):
+            raise ConfigurationError("overlap_bins must be None or a positive integer")
+
+
+def bin_shift(largest: int, max_bins: Optional[int]) -> int:
+    """The smallest shift s in [0, 31] with (largest >> s) + 1 <= max_bins (None: 0, a bin per value); 31 where none is
+    (the last bin then takes the rest: the engine clamps)."""
+    if max_bins is None:
+        return 0
+    return next((s for s in range(32) if (int(largest) >> s) + 1 <= max_bins), 31)
+
+
+@dataclass
+class OverlapStatistics:
+    """Histograms of the overlaps between two copies of a ladder, per temperature, as accumulate_ladder_overlaps left them:
+    hist_q[c, s, k] counts the measurements of copy pair c at temperatures[s] whose distance d (differing sites; q = 1 -
+    2 d / n) fell into bin k = min(d >> q_shift, bins - 1); hist_l the same for the broken links b (q_l = 1 - 2 b /
+    n_links), None where the couplings are not sparse.  Everything here is plain numpy on the host."""
+    temperatures: np.ndarray
+    n: int
+    n_links: Optional[int]
+    hist_q: np.ndarray
+    q_shift: int = 0
+    hist_l: Optional[np.ndarray] = None
+    l_shift: int = 0
+
+    @staticmethod
+    def _centres(bins: int, shift: int, largest: int) -> np.ndarray:
+        """1 - 2 c_k / largest, c_k the middle of the values bin k holds: [k << shift, (k + 1) << shift) cut at `largest`,
+        the last bin up to `largest` (the clamp)."""
+        k = np.arange(bins, dtype=np.float64)
+        lo = np.minimum(k * 2.0 ** shift, float(largest))
+        hi = np.minimum((k + 1.0) * 2.0 ** shift - 1.0, float(largest))
+        hi[-1] = max(float(largest), lo[-1])
+        return 1.0 - (lo + hi) / max(float(largest), 1.0)
+
+    def q_values(self) -> np.ndarray:
+        """The overlap q at the centre of every bin of hist_q (exact where q_shift == 0)."""
+        return self._centres(self.hist_q.shape[-1], self.q_shift, self.n)
+
+    def link_values(self) -> np.ndarray:
+        """The link overlap q_l at the centre of every bin of hist_l."""
+        if self.hist_l is None:
+            raise ConfigurationError("no link overlaps were measured (the couplings are not sparse)")
+        return self._centres(self.hist_l.shape[-1], self.l_shift, self.n_links)
+
+    @staticmethod
+    def _mean(hist, values) -> np.ndarray:
+        w = np.asarray(hist, np.float64).sum(axis=0)  # over the copy pairs: [slots, bins]
+        total = w.sum(axis=1)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return (w * values).sum(axis=1) / total
+
+    def moments(self):
+        """(<q^2>, <q^4>) per temperature, over all copy pairs (NaN where nothing was measured)."""
+        q = self.q_values()
+        return self._mean(self.hist_q, q ** 2), self._mean(self.hist_q, q ** 4)
+
+    def binder(self) -> np.ndarray:
+        """The Binder ratio (3 - <q^4> / <q^2>^2) / 2 per temperature."""
+        q2, q4 = self.moments()
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return 0.5 * (3.0 - q4 / q2 ** 2)
+
+    def link_overlap(self) -> np.ndarray:
+        """<q_l> per temperature, over all copy pairs."""
+        return self._mean(self.hist_l, self.link_values())
 
 
 class ParallelTempering:
@@ -102,6 +183,9 @@ class ParallelTempering:
         self.slot_acceptance = np.zeros(R)
         # isoenergetic cluster moves of the last run(): moves made, those that flipped anything, sites flipped, largest cluster
         self.cluster_moves_made = self.cluster_moves_flipped = self.cluster_sites_flipped = self.cluster_size_max = 0
+        # measure_overlaps: the histograms of the last run() (OverlapStatistics) and the exchange rounds that were measured
+        self.overlap_statistics: Optional[OverlapStatistics] = None
+        self.overlap_rounds_measured = 0
         self.device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
         self.use_cuda = self.device.type == "cuda"
 
@@ -154,6 +238,23 @@ class ParallelTempering:
                     eng.cluster_move_ladders(0, 0, round=0, sizes=False)
                 except AnnealingError as exc:
                     raise ConfigurationError(f"cluster_moves: {exc.message}") from exc
+            hist_q = hist_l = None
+            self.overlap_statistics, self.overlap_rounds_measured, eligible = None, 0, 0
+            if cfg.measure_overlaps:  # the histograms stay on the device for the whole run
+                try:
+                    n_links = eng.link_count()
+                except AnnealingError as exc:  # dense and implicit couplings: the spin part only
+                    if exc.details.get("code") != N.ERR_UNSUPPORTED:
+                        raise
+                    n_links = None
+                q_shift = bin_shift(n, cfg.overlap_bins)
+                hdev = torch.device("cuda", dev_idx)
+                hist_q = torch.zeros((C // 2, R, (n >> q_shift) + 1), dtype=torch.int64, device=hdev)
+                l_shift = 0
+                if n_links is not None:
+                    l_shift = bin_shift(n_links, cfg.overlap_bins)
+                    hist_l = torch.zeros((C // 2, R, min((n_links >> l_shift) + 1, cfg.overlap_bins or n_links + 1)),
+                                         dtype=torch.int64, device=hdev)
             eng.maybe_autotune(cfg.n_sweeps, cfg.autotune)
             slot_to_rep = np.arange(R, dtype=np.int32)
             acc_prev = np.zeros(R, np.int64)
@@ -206,6 +307,11 @@ class ParallelTempering:
                     self.cluster_moves_flipped += int(np.count_nonzero(sz))
                     self.cluster_sites_flipped += int(sz.sum())
                     self.cluster_size_max = max(self.cluster_size_max, int(sz.max()))
+                if exchange_now and hist_q is not None and stop + 1 >= cfg.measure_after:
+                    if eligible % cfg.measure_interval == 0:
+                        eng.accumulate_ladder_overlaps(hist_q, hist_l, q_shift=q_shift, l_shift=l_shift)
+                        self.overlap_rounds_measured += 1
+                    eligible += 1
                 # one synchronisation per event: energies (an exchange moves labels, not energies),
                 # acceptance counters, ladder permutation
                 en_rep, acc_now, full_map = eng.snapshot()
@@ -234,6 +340,10 @@ class ParallelTempering:
             self.final_spins = eng.spins()[slot_to_rep]
             # the final overlap matrix, formed where the spins are (sga_get_overlaps), in slot order like final_spins
             self._final_overlaps = eng.overlaps()[np.ix_(slot_to_rep, slot_to_rep)].astype(np.float64) / n
+            if hist_q is not None:  # (the reads above waited for the engine's stream)
+                self.overlap_statistics = OverlapStatistics(
+                    temperatures=temps.copy(), n=int(n), n_links=n_links, hist_q=hist_q.cpu().numpy(), q_shift=q_shift,
+                    hist_l=None if hist_l is None else hist_l.cpu().numpy(), l_shift=l_shift)
         self.slot_acceptance = acc_slot / np.maximum(att_slot, 1)
         total_time = time.time() - t_start
         return AnnealingResult(
