@@ -462,6 +462,29 @@ inline int row_shared_log_group(int n, int W) {
     while ((1 << l) < nwin) ++l;
     return l;
 }
+// The chain's accept table (rs_chain_kernel, integer Metropolis form): a wave tabulates ptab[q] = expf_det((float)(
+// -(double)(2 q) / T)), q = 1 ... Q, once per window and decides u < ptab[q] from LDS.  Q = min(table_m,
+// RS_ACCEPT_TABLE_MAX, zero_from(T)), zero_from(T) = floor(52 T) + 2 where 0 <= 52 T < RS_ACCEPT_TABLE_MAX and no bound
+// otherwise (T < 0, inf, NaN).  Where Q == zero_from(T) every q > Q is decided "false" without an entry:
+//   * fl(52 T) >= k whenever 52 T >= k for an integer k (k is an fp64 number, rounding is monotone), so floor(fl(52 T))
+//     >= floor(52 T) and q >= floor(52 T) + 3 > 52 T + 2, that is 2 q > 104 T + 4;
+//   * T > 0: the quotient -(2 q) / T < -104 - 4 / T < -104; -104 is an fp64 and an fp32 number, so neither the rounding
+//     of the divide nor the conversion to fp32 (both monotone) lifts the argument above -104, and expf_det returns 0
+//     below -103.972084; no uniform u >= 0 is below 0.  (q > table_m: rs_accept's cut-off 2 q > fl(104 T) holds by the
+//     margin of 4 against a rounding error of 104 T 2^-53, T < 20 -- false as well.)
+//   * T = 0: zero_from = 2, the quotient is -inf for every q >= 1, expf_det(-inf) = 0: false, as the entries 1 and 2 are.
+// Elsewhere (Q at the cap, or cut by table_m) a q > Q takes rs_accept's own per-lane evaluation.
+constexpr int RS_ACCEPT_TABLE_MAX = 1023;  // entries 0 ... 1023: 4 KB of floats per chain wave
+__host__ __device__ inline int rs_accept_table_zero_from(double T) {
+    const double x = 52.0 * T;
+    return (x >= 0.0 && x < (double)RS_ACCEPT_TABLE_MAX) ? (int)x + 2 : 0x7fffffff;  // ((int)x: floor, x >= 0)
+}
+__host__ __device__ inline int rs_accept_table_entries(double T, int table_m) {
+    const int z = rs_accept_table_zero_from(T);
+    int Q = table_m < RS_ACCEPT_TABLE_MAX ? table_m : RS_ACCEPT_TABLE_MAX;
+    if (Q < 0) Q = 0;
+    return z < Q ? z : Q;
+}
 // Fields from the resident planes in tiles (rs_fields_tiles_kernel, option "row_shared_fields"): one workgroup per
 // (window, tile of S consecutive sites) holds the tile's plane rows in LDS and walks its entries grouped by replica.
 // S == 0: the per-site kernel.  ones: every off-diagonal |J_ij| (GRID: |2^k J_ij|) is 1 -- the rows are their sign

@@ -749,6 +749,24 @@ __device__ __forceinline__ float rs_coupling(const RsRaw<JE, true, true> &raw, u
 constexpr int RS_CHAIN_PRIO = SGA_RS_CHAIN_PRIO;
 constexpr int RS_CHAIN_K = 4;  // candidates fetched per round (measured among 4, 8, 16)
 constexpr int RS_CHAIN_U = 8;  // earlier accepts applied to a block per wait
+// The accept probabilities of the integer Metropolis form from a table the wave fills once per window (DESIGN.md 7,
+// "Chain: accept table"); -DSGA_RS_CHAIN_TABLE=0 builds the other side of the A/B, rs_accept per lane at every decision.
+#ifndef SGA_RS_CHAIN_TABLE
+#define SGA_RS_CHAIN_TABLE 1
+#endif
+constexpr bool RS_CHAIN_TABLE = SGA_RS_CHAIN_TABLE != 0;
+
+// The decision of the integer Metropolis form from the wave's table (sga_kernels.h: rs_accept_table_entries, with the
+// argument for "false beyond Q"): ptab[q] holds rs_accept's own expression for q = 1 ... Q, so u < ptab[q] is its
+// decision bit for bit; zero_tail: Q == rs_accept_table_zero_from(T).  A q beyond a table that does not end in zeros is
+// evaluated by rs_accept itself, in a branch the wave takes only when one of its lanes needs it.
+__device__ __forceinline__ bool rs_accept_tabled(const float *ptab, int Q, bool zero_tail, float fk, float u, double T, int table_m) {
+    if (fk <= 0.0f) return true;
+    const int q = (int)fk;
+    if (q <= Q) return u < ptab[q];
+    if (zero_tail) return false;
+    return rs_accept(fk, u, T, table_m);
+}
 
 // The blocks of the window (64 updates, one per lane) are walked in order.  A block is touched when it becomes
 // current: first it takes the corrections of every accept made so far in the window -- field -= 2 J[i_a][site] s_a
@@ -789,7 +807,9 @@ __global__ void __launch_bounds__(64) rs_chain_kernel(const SweepArgs a, const R
     const RowSharedPlan &p = rs_plan(pg);
     if constexpr (RS_CHAIN_PRIO > 0) __builtin_amdgcn_s_setprio(RS_CHAIN_PRIO);
     constexpr int W = 64 * NB, K = RS_CHAIN_K, U = RS_CHAIN_U;
+    constexpr bool TABLE = RS_CHAIN_TABLE && !GRID && !ANYRULE;
     __shared__ uint32_t alist[W + U];  // the window's accepts in chain order: site | (spin before the flip < 0) << 31
+    __shared__ float ptab[TABLE ? RS_ACCEPT_TABLE_MAX + 1 : 1];  // TABLE: the accept probabilities of this wave's T
     const int r = blockIdx.x, lane = threadIdx.x, n = a.n;
     const int t0 = win * W, cnt = min(W, n - t0);
     const double T = a.sched ? a.sched[k * a.sched_ss + r * a.sched_rs] : a.rep_temp[r];
@@ -815,9 +835,22 @@ __global__ void __launch_bounds__(64) rs_chain_kernel(const SweepArgs a, const R
         hh[b] = hvec[site[b]];
         s[b] = srow[site[b]];
     }
+    // The accept table of this wave's T, filled behind the loads above (nothing has waited for them yet): rs_accept's
+    // expression for q = 1 ... Q, Q / 64 entries per lane (entry 0 is never read: fk <= 0 accepts).
+    int Q = 0;
+    bool zero_tail = false;
+    if constexpr (TABLE) {
+        Q = __builtin_amdgcn_readfirstlane(rs_accept_table_entries(T, a.table_m));
+        zero_tail = Q == __builtin_amdgcn_readfirstlane(rs_accept_table_zero_from(T));
+        for (int q = lane; q <= Q; q += 64) ptab[q] = expf_det((float)(-(double)(2 * q) / T));
+    }
     double E = a.energy[r];
     int nA = 0;  // accepts of this window so far
     const int nblk = (cnt + 63) >> 6;
+    auto decide = [&](int cs, float cf, float chh, float cu) {
+        if constexpr (TABLE) return rs_accept_tabled(ptab, Q, zero_tail, (float)cs * (cf + chh), cu, T, a.table_m);
+        else return rs_decide_rule<GRID, ANYRULE>(a.rule, cs, cf, chh, cu, T, a.table_m);
+    };
     for (int cb = 0; cb < nblk; ++cb) {
         int csite = 0, cs = 0;
         float cf = 0.0f, chh = 0.0f, cu = 0.0f;
@@ -861,7 +894,7 @@ __global__ void __launch_bounds__(64) rs_chain_kernel(const SweepArgs a, const R
                 }
             }
         }
-        bool acc = cvalid && rs_decide_rule<GRID, ANYRULE>(a.rule, cs, cf, chh, cu, T, a.table_m);
+        bool acc = cvalid && decide(cs, cf, chh, cu);
         unsigned long long m = ballot64(acc);  // accepting lanes among the undecided ones
         while (m) {
             int cl[K];
@@ -902,7 +935,7 @@ __global__ void __launch_bounds__(64) rs_chain_kernel(const SweepArgs a, const R
                 if constexpr (ONES) cf -= rs_coupling<JE>(x[j], bit, unit, csite == sa) * (2.0f * (float)ss);
                 else cf -= rs_coupling<JE, BITS>(x[j], bit, unit) * (2.0f * (float)ss);
                 if (csite == sa) cs = -cs;
-                acc = cvalid && rs_decide_rule<GRID, ANYRULE>(a.rule, cs, cf, chh, cu, T, a.table_m);
+                acc = cvalid && decide(cs, cf, chh, cu);
                 m = ballot64(acc) & (~1ull << fl);
             }
         }
