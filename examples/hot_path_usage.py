@@ -138,6 +138,30 @@ def frustrated_lattice_with_cluster_moves(L=10):
           f"link overlap {st.link_overlap()[-1]:.3f} / {st.link_overlap()[0]:.3f}")
 
 
+def frustrated_lattice_correlation_length(L=8):
+    """The finite-size correlation length xi_L / L of a 3-D +-J lattice per temperature, the quantity whose crossing locates
+    T_c: two copies of the ladder, and after every exchange round from sweep 200 on the overlap between the copies resolved
+    by the lattice's planes goes, with its second moments, into sums that stay on the device
+    (AnnealEngine.accumulate_ladder_class_overlaps with the class maps of encoders.lattice_planes)."""
+    rs = np.random.RandomState(4)
+    idx = np.arange(L ** 3).reshape(L, L, L)
+    J = np.zeros((L ** 3, L ** 3), np.float32)
+    for ax in range(3):
+        a, b = idx.ravel(), np.roll(idx, -1, axis=ax).ravel()
+        J[a, b] = J[b, a] = rs.randint(0, 2, a.size) * 2.0 - 1.0
+    model = IsingModel(IsingModelConfig(n_spins=L ** 3, use_sparse=True))
+    model.set_couplings_from_matrix(torch.from_numpy(J))
+    cfg = ParallelTemperingConfig(n_replicas=12, n_sweeps=1000, temp_min=0.6, temp_max=2.4, exchange_interval=10, random_seed=42,
+                                  n_copies=2, measure_class_overlaps=True, overlap_classes=encoders.lattice_planes((L, L, L)),
+                                  measure_after=200)
+    pt = ParallelTempering(cfg)
+    pt.run(model)
+    st = pt.class_overlap_statistics
+    print(f"PT, {L}^3 +-J lattice, plane overlaps over {st.measurements} rounds: xi_L / L per temperature")
+    for T, xi in zip(st.temperatures, st.correlation_length() / L):
+        print(f"  T = {T:.3f}  xi_L / L = {xi:.3f}")
+
+
 def frustrated_lattice_by_population_annealing(L=8):
     """Population annealing on a 3-D +-J lattice: 4 independent populations of 1024 replicas cooled together from beta = 0
     to 2, every replica copied or culled by its weight at each step (AnnealEngine.resample, on the device).  The run yields
@@ -256,6 +280,7 @@ if __name__ == "__main__":
     one_graph_many_fields()
     one_sparse_graph_many_fields()
     frustrated_lattice_with_cluster_moves()
+    frustrated_lattice_correlation_length()
     frustrated_lattice_by_population_annealing()
     travelling_salesman()
     travelling_salesman_without_storing_couplings()

@@ -80,7 +80,7 @@ typedef struct sga_engine sga_engine;
 int sga_create(int device, sga_engine **out);
 void sga_destroy(sga_engine *e);
 const char *sga_last_error(void);
-int sga_version(void);  /* 2700: sga_get_link_count / sga_get_pair_overlaps / sga_accumulate_ladder_overlaps (spin and link overlaps between pairs of replicas, histogrammed per temperature on the device, csrc/pair_overlaps.hip; read only, no engine state, no option); 2600: sga_resample (the resampling step of population annealing, csrc/resample.hip); 2500: sga_cluster_move_pairs / sga_cluster_move_ladders (isoenergetic cluster moves between replica copies on sparse couplings, csrc/cluster_moves.hip; no engine state, no option); 2400: sga_set_replica_groups / sga_get_replica_groups; 2300: sga_get_magnetizations / sga_get_overlaps / sga_get_overlaps_with (replica observables on the device: the exact integer product of int8 spin rows on the matrix cores, csrc/observables.hip; read only, no engine state); 2200: the row-shared fields in tiles take a plan of their own, one launch per sweep (csrc/sweep_dense_rs.hip, rs_tile_plan_kernel; no change of interface or results); 2100: sga_set_sequential_windows / sga_get_sequential_windows (SGA_SITE_SEQUENTIAL sweeps in windows, the fields of every replica on the matrix cores; csrc/sweep_dense_seq.hip); 2000: the row-shared windows (option "row_shared") serve SGA_RULE_GLAUBER and SGA_RULE_HEAT_BATH too ("rule=glauber" / "rule=heat-bath" in sga_describe and sga_get_last_kernel; the window sga_autotune picks holds for the rule it was timed under); 1900: options "row_shared_fields" and "row_shared_tile_sites" (row-shared fields in tiles of sites, sign-only rows); 1800: option "row_shared_grid", sga_route_query.rs_grid; 1700: sga_set_csr_shared (one set of CSR rows, many field vectors: every one-wave-per-replica CSR form for such batches), sga_route_query.shared_j on SGA_ROUTE_CSR queries; 1600: sga_set_dense_shared (one coupling matrix, many field vectors; row-shared windows, bit-planes and the matrix-core pass for such batches), sga_route_query.shared_j; 1500: sga_get_scan_summary, and sga_set_dense / sga_set_dense_batch / sga_set_csr / sga_set_csr64 / sga_set_csr_batch refuse a NaN or +-Inf in J or h (SGA_ERR_INVALID, "non-finite"); 1400: option "batch_fixed_point" (fixed-point cached local fields for many-model dense batches); 1300: options "ragged_field_cache" and "clf_fixed_point" together (fixed-point cached local fields for ragged CSR batches); 1200: sga_set_groups_csr (group couplings plus a stored sparse remainder); 1100: option "ragged_field_cache" (cached local fields for ragged CSR batches); 1000: sga_set_groups */
+int sga_version(void);  /* 2800: sga_get_class_overlaps / sga_accumulate_ladder_class_overlaps (the overlap between two replicas resolved by a class of sites, first and second moments per temperature summed on the device, csrc/class_overlaps.hip; read only, no engine state, no option); 2700: sga_get_link_count / sga_get_pair_overlaps / sga_accumulate_ladder_overlaps (spin and link overlaps between pairs of replicas, histogrammed per temperature on the device, csrc/pair_overlaps.hip; read only, no engine state, no option); 2600: sga_resample (the resampling step of population annealing, csrc/resample.hip); 2500: sga_cluster_move_pairs / sga_cluster_move_ladders (isoenergetic cluster moves between replica copies on sparse couplings, csrc/cluster_moves.hip; no engine state, no option); 2400: sga_set_replica_groups / sga_get_replica_groups; 2300: sga_get_magnetizations / sga_get_overlaps / sga_get_overlaps_with (replica observables on the device: the exact integer product of int8 spin rows on the matrix cores, csrc/observables.hip; read only, no engine state); 2200: the row-shared fields in tiles take a plan of their own, one launch per sweep (csrc/sweep_dense_rs.hip, rs_tile_plan_kernel; no change of interface or results); 2100: sga_set_sequential_windows / sga_get_sequential_windows (SGA_SITE_SEQUENTIAL sweeps in windows, the fields of every replica on the matrix cores; csrc/sweep_dense_seq.hip); 2000: the row-shared windows (option "row_shared") serve SGA_RULE_GLAUBER and SGA_RULE_HEAT_BATH too ("rule=glauber" / "rule=heat-bath" in sga_describe and sga_get_last_kernel; the window sga_autotune picks holds for the rule it was timed under); 1900: options "row_shared_fields" and "row_shared_tile_sites" (row-shared fields in tiles of sites, sign-only rows); 1800: option "row_shared_grid", sga_route_query.rs_grid; 1700: sga_set_csr_shared (one set of CSR rows, many field vectors: every one-wave-per-replica CSR form for such batches), sga_route_query.shared_j on SGA_ROUTE_CSR queries; 1600: sga_set_dense_shared (one coupling matrix, many field vectors; row-shared windows, bit-planes and the matrix-core pass for such batches), sga_route_query.shared_j; 1500: sga_get_scan_summary, and sga_set_dense / sga_set_dense_batch / sga_set_csr / sga_set_csr64 / sga_set_csr_batch refuse a NaN or +-Inf in J or h (SGA_ERR_INVALID, "non-finite"); 1400: option "batch_fixed_point" (fixed-point cached local fields for many-model dense batches); 1300: options "ragged_field_cache" and "clf_fixed_point" together (fixed-point cached local fields for ragged CSR batches); 1200: sga_set_groups_csr (group couplings plus a stored sparse remainder); 1100: option "ragged_field_cache" (cached local fields for ragged CSR batches); 1000: sga_set_groups */
 /* Run on an existing HIP stream (e.g. torch.cuda.current_stream().cuda_stream); NULL = the
  * engine's own stream (default). */
 int sga_set_stream(sga_engine *e, void *hip_stream);
@@ -519,6 +519,53 @@ int sga_get_pair_overlaps(sga_engine *e, int which /* SGA_SPINS_CURRENT | SGA_SP
 int sga_accumulate_ladder_overlaps(sga_engine *e, int slot_lo, int slot_hi,
                                    uint64_t *hist_q, int bins_q, int q_shift,
                                    uint64_t *hist_l /* or NULL */, int bins_l, int l_shift);
+
+/* ---- class-resolved overlaps between pairs of replicas (version >= 2800; csrc/class_overlaps.hip) --------------------
+ * The overlap between two replicas resolved by a CLASS of sites -- the planes of a lattice, sublattices, layers,
+ * communities, the machines of a scheduling instance -- as exact integer counts formed where the spins are: what the
+ * wave-vector-dependent spin-glass susceptibility chi_SG(k) and the correlation length xi_L / L are made of.
+ *   A CLASS MAP is classes[m][i]: int32, n_maps rows with leading dimension ld >= n, values in [0, n_classes).  A site
+ *   whose value lies outside that range, negative included, belongs to NO class in that map: that is how callers mask
+ *   sites, and the kernel tests the range and never trusts it, so a map the host never saw cannot index out of bounds.
+ *   For a pair (a, b) of local replicas let x_i = [s_a[i] != s_b[i]] for the sites i < n:
+ *   D[m][c] = sum_{i : classes[m][i] = c} x_i (int32).  With N_c the size of the class, the class overlap is
+ *   Q_c = N_c - 2 D_c; where a map gives every site a class, sum_c D[m][c] = d of sga_get_pair_overlaps.
+ *   The pair form takes `which` and a host pair list under the rules of sga_get_pair_overlaps: any list, a replica may
+ *   stand in many pairs, a == b is a pair and gives all zeros.  classes: a host or a device buffer; a HOST MAP IS
+ *   STAGED ON EVERY CALL (4 n_maps n bytes over the bus) -- a run keeps its map on the device.  dist:
+ *   [count][n_maps][n_classes] int32, host or device; a device output returns at once, a host output after its copy has
+ *   landed.
+ *   The ladder form takes the pairs of sga_accumulate_ladder_overlaps: ladders 2c and 2c + 1, slots
+ *   slot_lo <= s < slot_hi, the replicas that hold them read from the slot map ON THE DEVICE; it needs an even
+ *   n_ladders and R_local == R_global.  The cell of pair c and slot s is k = c (slot_hi - slot_lo) + (s - slot_lo).
+ *   Each call adds D[m][c] to sum1[k][m][c] and, where sum2 is not NULL, D[m][c] D[m][c'] to sum2[k][m][c][c'], the full
+ *   C x C matrix for every c, c'.  classes, sum1 and sum2 are the CALLER'S DEVICE BUFFERS, the sums uint64, zeroed by
+ *   the caller once: the engine keeps nothing between calls and never zeroes them; one workgroup owns one cell per
+ *   launch, so the update is a plain 64-bit load / add / store, deterministic, no atomics on global memory.  The caller
+ *   counts its own calls: each adds one measurement to every cell of the range.  From these sums every second moment
+ *   follows in exact integers, <Q_c Q_c'> = N_c N_c' - 2 N_c <D_c'> - 2 N_c' <D_c> + 4 <D_c D_c'>, and any wave vector
+ *   afterwards on the host.  Overflow is the caller's to respect: measurements (max_c N_c)^2 < 2^64.
+ *   Served: every kind of problem, as d of sga_get_pair_overlaps -- only the int8 spin rows are read; n is the engine's
+ *   row length in sites (ragged batches: rows are zero past a model's own sites and never differ there).
+ *   The kernel (one workgroup of 256 threads per pair) keeps a counter per (m, c) in LDS, a copy for each of its four
+ *   waves where n_maps n_classes <= 10 224, one copy up to 40 896: 4 bytes x copies x n_maps n_classes of LDS.
+ *   SGA_ERR_UNSUPPORTED, with the reason in sga_last_error: n_maps n_classes > 40 896.
+ *   SGA_ERR_INVALID: a NULL engine, classes or output; no problem or no replicas; which outside {SGA_SPINS_CURRENT,
+ *   SGA_SPINS_BEST}; every pair-list error of sga_get_pair_overlaps; n_maps < 1, n_classes < 1 or ld < n; a host sum1,
+ *   sum2 or classes in the ladder form; no ladder, an odd n_ladders, R_local != R_global, a slot range not inside
+ *   [0, slots).  count == 0 and an empty slot range are no-ops.  Every refusal happens before anything is enqueued or
+ *   written.
+ *   Read only: no spin, energy, best, counter, cached field, window plan, slot map or sga_get_last_kernel changes, and a
+ *   run with these calls between its sweeps walks the same chain.  The work is enqueued on the engine's stream behind
+ *   earlier sweeps. */
+int sga_get_class_overlaps(sga_engine *e, int which /* SGA_SPINS_CURRENT | SGA_SPINS_BEST */,
+                           const int32_t *pairs /* host [count][2], LOCAL indices */, int count,
+                           const int32_t *classes /* [n_maps][ld], host or device */, int64_t ld, int n_maps, int n_classes,
+                           int32_t *dist /* [count][n_maps][n_classes], host or device */);
+/* the CURRENT spins; sum1 [n_ladders/2][slot_hi - slot_lo][n_maps][n_classes], sum2 [...][n_classes][n_classes]: device, uint64 */
+int sga_accumulate_ladder_class_overlaps(sga_engine *e, int slot_lo, int slot_hi,
+                                         const int32_t *classes /* [n_maps][ld], device */, int64_t ld, int n_maps, int n_classes,
+                                         uint64_t *sum1, uint64_t *sum2 /* or NULL */);
 
 /* Stateless operator form of CUDAKernelManager.parallel_tempering_exchange_optimized
  * (annealing/cuda_kernels.py:326-369, fallback :415-443): sequential adjacent pairs, fp32,

@@ -15,7 +15,7 @@ from .ising_model import IsingModel, IsingModelConfig
 from .spin_dynamics import SpinDynamics, UpdateRule
 from .energy_computer import ComputeMode, EnergyComputer, EnergyStats
 from .gpu_annealer import GPUAnnealer, GPUAnnealerConfig
-from .parallel_tempering import OverlapStatistics, ParallelTempering, ParallelTemperingConfig
+from .parallel_tempering import ClassOverlapStatistics, OverlapStatistics, ParallelTempering, ParallelTemperingConfig
 from .population_annealing import PopulationAnnealing, PopulationAnnealingConfig
 from .kernel_manager import CUDAKernelManager, GPUMemoryOptimizer, HIPKernelManager
 from .scheduler import SpinGlassScheduler
@@ -30,7 +30,7 @@ __all__ = [
     "DeviceError", "ModelError", "ValidationError", "ConfigurationError", "ResourceError",
     "ScheduleType", "ScheduleConfig", "TemperatureScheduler", "temperature_ladder",
     "AnnealingResult", "IsingModel", "IsingModelConfig", "SpinDynamics", "UpdateRule",
-    "GPUAnnealer", "GPUAnnealerConfig", "ParallelTempering", "ParallelTemperingConfig", "OverlapStatistics",
+    "GPUAnnealer", "GPUAnnealerConfig", "ParallelTempering", "ParallelTemperingConfig", "OverlapStatistics", "ClassOverlapStatistics",
     "PopulationAnnealing", "PopulationAnnealingConfig",
     "HIPKernelManager", "CUDAKernelManager", "GPUMemoryOptimizer", "SpinGlassScheduler",
     "ShardedTempering", "LocalShardedTempering", "MultiGPUAnnealer", "MultiGPUConfig", "LoadBalancer",

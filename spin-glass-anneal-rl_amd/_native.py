@@ -81,6 +81,8 @@ SYMBOLS = [
     ("sga_get_link_count", _i, [_p, _p]),
     ("sga_get_pair_overlaps", _i, [_p, _i, _p, _i, _p, _p]),
     ("sga_accumulate_ladder_overlaps", _i, [_p, _i, _i, _p, _i, _i, _p, _i, _i]),
+    ("sga_get_class_overlaps", _i, [_p, _i, _p, _i, _p, _i64, _i, _i, _p]),
+    ("sga_accumulate_ladder_class_overlaps", _i, [_p, _i, _i, _p, _i64, _i, _i, _p, _p]),
     ("sga_op_pt_exchange", _i, [_i, _p, _p, _p, _p, _u64, _u32, _i, _i, C.POINTER(_i)]),
     ("sga_get_energies", _i, [_p, _p]),
     ("sga_get_energies_async", _i, [_p, _p]),

@@ -347,6 +347,10 @@ extern "C" {
 
 const char *sga_last_error(void) { return g_last_error.c_str(); }
 // The ABI version, one line per step:
+//   2800:    + sga_get_class_overlaps / sga_accumulate_ladder_class_overlaps: the overlap between two replicas resolved
+//            by a class of sites (planes of a lattice, sublattices, communities), the pairs of two ladders read from the
+//            slot map and summed into the caller's first and second moments on the device (class_overlaps.hip; host
+//            side in sga_state.cpp); read only, no engine state, no option
 //   2700:    + sga_get_link_count / sga_get_pair_overlaps / sga_accumulate_ladder_overlaps: spin and link overlaps between
 //            pairs of replicas, the pairs of two ladders read from the slot map and histogrammed on the device
 //            (pair_overlaps.hip; host side in sga_state.cpp); read only, no engine state, no option
@@ -386,7 +390,7 @@ const char *sga_last_error(void) { return g_last_error.c_str(); }
 //   600:     + sga_set_csr_batch / sga_get_batch_model (ragged CSR batches)
 //   round 5: + sga_explain_route / sga_get_route_query, sga_get_last_kernel, sga_get_autotune_table, ladder-local
 //            sga_exchange
-int sga_version(void) { return 2700; }
+int sga_version(void) { return 2800; }
 
 int sga_create(int device, sga_engine **out) {
     if (!out) return fail(SGA_ERR_INVALID, "out is NULL");

@@ -928,6 +928,55 @@ hipError_t launch_pair_overlaps(const PairOverlapArgs &a, hipStream_t st);
 hipError_t launch_link_count(const long long *rowptr64, const int2 *cv, int n, int group_log2, unsigned long long *out,
                              hipStream_t st);
 
+// Class-resolved overlaps between pairs of replicas (class_overlaps.hip; sga_get_class_overlaps /
+// sga_accumulate_ladder_class_overlaps): one workgroup of 256 threads per pair, a lane a site, and per map m a counter
+// cnt[m C + c] in LDS for D[m][c] = the differing sites of class c.  Read only.
+//   copies: every one of the workgroup's four waves counts into a copy of its own where four copies fit the budget
+//           (M C <= CLASS_OVERLAP_MAX_MC_4 = 10 224), else all four share one copy;
+//   LDS:    4 bytes x copies x M C, nothing else;
+//   bound:  M C <= CLASS_OVERLAP_MAX_MC = 40 896, one copy filling CLUSTER_LDS_BUDGET.
+constexpr int CLASS_OVERLAP_THREADS = 256;
+#ifndef SGA_CLASS_OVERLAP_MAX_COPIES  // (a measurement build passes 1: profiles/class_overlaps_timing.py)
+#define SGA_CLASS_OVERLAP_MAX_COPIES 4
+#endif
+constexpr long long CLASS_OVERLAP_MAX_MC = (long long)(CLUSTER_LDS_BUDGET / 4);
+constexpr long long CLASS_OVERLAP_MAX_MC_4 = (long long)(CLUSTER_LDS_BUDGET / 16);
+inline int class_overlap_copies(long long mc) {
+    return SGA_CLASS_OVERLAP_MAX_COPIES >= 4 && mc <= CLASS_OVERLAP_MAX_MC_4 ? 4 : 1;
+}
+inline size_t class_overlap_lds_bytes(long long mc) { return 4 * (size_t)class_overlap_copies(mc) * (size_t)mc; }
+// The class-map arguments of both calls, checked on the host before anything is enqueued: nullptr, or what is wrong
+// (SGA_ERR_INVALID).  n: the engine's row length in sites.
+inline const char *class_overlap_args_check(bool have_classes, bool have_out, int n_maps, int n_classes, long long ld, long long n) {
+    if (!have_classes) return "classes is NULL";
+    if (!have_out) return "the output is NULL";
+    if (n_maps < 1) return "n_maps must be at least 1";
+    if (n_classes < 1) return "n_classes must be at least 1";
+    if (ld < n) return "ld is smaller than n";
+    return nullptr;
+}
+// ... and what is not served (SGA_ERR_UNSUPPORTED): more counters than LDS holds
+inline const char *class_overlap_unsupported(int n_maps, int n_classes) {
+    if ((long long)n_maps * (long long)n_classes > CLASS_OVERLAP_MAX_MC)
+        return "class overlaps: n_maps * n_classes counters do not fit LDS (at most 40896)";
+    return nullptr;
+}
+struct ClassOverlapArgs {
+    const int8_t *spins;         // [R][sstride] the observed rows (current or best)
+    const int32_t *pairs;        // pair form: [count][2] local replicas
+    const int32_t *slot_to_rep;  // ladder form (pairs == null): the slot map, [n_ladders][L] global ids
+    int L, slot_lo, n_slots;     // ... pair p: ladders 2 (p / n_slots) and 2 (p / n_slots) + 1, slot slot_lo + p % n_slots
+    const int32_t *classes;      // [n_maps][ld]; a value outside [0, n_classes) is no class
+    long long ld;
+    int n_maps, n_classes;
+    int vec_classes;             // set by the launcher: classes is 16-byte aligned and ld a multiple of 4 (int4 loads)
+    int32_t *dist;               // pair form: [count][n_maps][n_classes] D
+    unsigned long long *sum1;    // ladder form: [count][n_maps][n_classes], += D[m][c]
+    unsigned long long *sum2;    // ... [count][n_maps][n_classes][n_classes], += D[m][c] D[m][c'], or null
+    int n, sstride, R, count, replica0;
+};
+hipError_t launch_class_overlaps(const ClassOverlapArgs &a, hipStream_t st);
+
 // operator-form PT exchange (cuda_kernels.py:415-443): decide sequentially, then permute rows
 hipError_t launch_op_exchange(float *spins, float *tmp_rows, float *energies, const float *temps,
                               const float *u, int32_t *src_of_pos, int *n_accepted,

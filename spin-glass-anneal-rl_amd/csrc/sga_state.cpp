@@ -949,6 +949,78 @@ int sga_accumulate_ladder_overlaps(sga_engine *e, int slot_lo, int slot_hi, uint
     return SGA_OK;
 }
 
+// ---- class-resolved overlaps between pairs of replicas (class_overlaps.hip) -------------------
+// Read only, under the same rule: a host pair list and behind it a host class map are staged in point_sites, a host
+// result leaves through point_out (both grow-only), and nothing else of the engine is written.
+int sga_get_class_overlaps(sga_engine *e, int which, const int32_t *pairs, int count, const int32_t *classes, int64_t ld,
+                           int n_maps, int n_classes, int32_t *dist) {
+    if (!e) return fail(SGA_ERR_INVALID, "engine is NULL");
+    if (const char *why = observables_ready(e)) return fail(SGA_ERR_INVALID, why);
+    if (!observed_which(which)) return fail(SGA_ERR_INVALID, "which must be SGA_SPINS_CURRENT or SGA_SPINS_BEST");
+    if (pairs && is_device_ptr(pairs)) return fail(SGA_ERR_INVALID, "pairs must be a host buffer");
+    if (const char *why = sga::pair_overlap_pairs_check(pairs, count, e->R)) return fail(SGA_ERR_INVALID, why);
+    if (const char *why = sga::class_overlap_args_check(classes != nullptr, dist != nullptr, n_maps, n_classes, ld, e->n))
+        return fail(SGA_ERR_INVALID, why);
+    if (const char *why = sga::class_overlap_unsupported(n_maps, n_classes)) return fail(SGA_ERR_UNSUPPORTED, why);
+    if (count == 0) return SGA_OK;
+    HIPCHK(hipSetDevice(e->device));
+    hipStream_t st = e->stream;
+    const size_t cnt = (size_t)count, mc = (size_t)n_maps * (size_t)n_classes, n = (size_t)e->n;
+    const bool map_host = !is_device_ptr(classes), dist_host = !is_device_ptr(dist);
+    // the pair list, then a host map packed to ld = n rounded up to 4 (pageable host buffers: the copies have left them on return)
+    const size_t pair_bytes = (2 * cnt * sizeof(int32_t) + 15) / 16 * 16;
+    const size_t ld4 = (n + 3) / 4 * 4;  // (rows of the staged map start 16-byte aligned: the kernel loads int4)
+    HIPCHK(e->point_sites.reserve(pair_bytes + (map_host ? (size_t)n_maps * ld4 * sizeof(int32_t) : 0)));
+    unsigned char *stage = static_cast<unsigned char *>(e->point_sites.ptr);
+    HIPCHK(hipMemcpyAsync(stage, pairs, 2 * cnt * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    if (map_host)
+        HIPCHK(hipMemcpy2DAsync(stage + pair_bytes, ld4 * sizeof(int32_t), classes, (size_t)ld * sizeof(int32_t), n * sizeof(int32_t),
+                                (size_t)n_maps, hipMemcpyHostToDevice, st));
+    if (dist_host) HIPCHK(e->point_out.reserve(cnt * mc * sizeof(int32_t)));
+    sga::ClassOverlapArgs a{};
+    a.spins = observed_rows(e, which);
+    a.pairs = reinterpret_cast<const int32_t *>(stage);
+    a.classes = map_host ? reinterpret_cast<const int32_t *>(stage + pair_bytes) : classes;
+    a.ld = map_host ? (long long)ld4 : (long long)ld;
+    a.n_maps = n_maps, a.n_classes = n_classes;
+    a.dist = dist_host ? static_cast<int32_t *>(e->point_out.ptr) : dist;
+    a.n = e->n, a.sstride = e->sstride, a.R = e->R, a.count = count, a.replica0 = e->replica0;
+    HIPCHK(sga::launch_class_overlaps(a, st));
+    if (dist_host) {
+        HIPCHK(hipMemcpyAsync(dist, a.dist, cnt * mc * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+    }
+    return SGA_OK;
+}
+
+int sga_accumulate_ladder_class_overlaps(sga_engine *e, int slot_lo, int slot_hi, const int32_t *classes, int64_t ld, int n_maps,
+                                         int n_classes, uint64_t *sum1, uint64_t *sum2) {
+    if (!e) return fail(SGA_ERR_INVALID, "engine is NULL");
+    if (const char *why = observables_ready(e)) return fail(SGA_ERR_INVALID, why);
+    if (const char *why = sga::class_overlap_args_check(classes != nullptr, sum1 != nullptr, n_maps, n_classes, ld, e->n))
+        return fail(SGA_ERR_INVALID, why);
+    if (!is_device_ptr(classes) || !is_device_ptr(sum1) || (sum2 && !is_device_ptr(sum2)))
+        return fail(SGA_ERR_INVALID, "classes, sum1 and sum2 must be device buffers (they stay on the device for the whole run)");
+    if (e->n_ladders <= 0 || !e->slot_to_rep) return fail(SGA_ERR_INVALID, "no ladder (call sga_set_ladder)");
+    if (e->n_ladders % 2 != 0) return fail(SGA_ERR_INVALID, "overlaps between ladders need an even number of ladders");
+    if (e->R != e->Rg) return fail(SGA_ERR_INVALID, "overlaps between ladders need every replica on this rank (R_local == R_global)");
+    const int L = e->Rg / e->n_ladders;
+    if (slot_lo < 0 || slot_hi > L || slot_lo > slot_hi) return fail(SGA_ERR_INVALID, "slot range outside [0, slots)");
+    if (const char *why = sga::class_overlap_unsupported(n_maps, n_classes)) return fail(SGA_ERR_UNSUPPORTED, why);
+    if (slot_lo == slot_hi) return SGA_OK;
+    HIPCHK(hipSetDevice(e->device));
+    sga::ClassOverlapArgs a{};
+    a.spins = e->spins;
+    a.slot_to_rep = e->slot_to_rep;
+    a.L = L, a.slot_lo = slot_lo, a.n_slots = slot_hi - slot_lo;
+    a.classes = classes, a.ld = (long long)ld, a.n_maps = n_maps, a.n_classes = n_classes;
+    a.sum1 = reinterpret_cast<unsigned long long *>(sum1);
+    a.sum2 = reinterpret_cast<unsigned long long *>(sum2);
+    a.n = e->n, a.sstride = e->sstride, a.R = e->R, a.count = (e->n_ladders / 2) * a.n_slots, a.replica0 = e->replica0;
+    HIPCHK(sga::launch_class_overlaps(a, e->stream));
+    return SGA_OK;
+}
+
 int sga_get_route_query(sga_engine *e, sga_route_query *out) {
     if (!e || !out) return fail(SGA_ERR_INVALID, "NULL argument");
     if (e->n <= 0) return fail(SGA_ERR_INVALID, "no couplings set");

@@ -491,3 +491,15 @@ def scheduling_groups_rest(durations: Sequence[float], n_agents: int, time_horiz
     b = scheduling_ising(durations, n_agents, time_horizon, time_discretization, due_dates, priorities, objective,
                          penalty_weights, precedence_pairs=precedence_pairs)
     return (b.n,) + b.group_rest_structure()
+
+
+def lattice_planes(shape: Sequence[int]) -> np.ndarray:
+    """The class maps of a row-major lattice's planes, int32 [len(shape), prod(shape)]: map a holds the coordinate of site
+    i along axis a, i.e. the planes perpendicular to axis a are its classes (site index i = ravel of the coordinates, the
+    last axis the fastest).  With AnnealEngine.class_overlaps / ParallelTemperingConfig(overlap_classes=...) these give
+    the plane overlaps Q_c from which the susceptibility chi_SG(k) along every axis and the correlation length follow;
+    n_classes = max(shape) serves all maps at once (a shorter axis leaves its last classes empty)."""
+    shape = tuple(int(v) for v in shape)
+    if not shape or min(shape) < 1:
+        raise ValueError("shape must hold positive extents")
+    return np.stack([c.reshape(-1) for c in np.indices(shape)]).astype(np.int32)

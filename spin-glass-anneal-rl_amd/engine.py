@@ -930,6 +930,82 @@ class AnnealEngine:
         self._observable_done(True)
         self._pending = (hist_q, hist_l)
 
+    # ------------------------------------------------------------------ class-resolved overlaps between pairs
+    # csrc/class_overlaps.hip: per pair and class map, D[m][c] = the differing sites of class c (Q_c = N_c - 2 D_c) as
+    # exact integer counts -- read only, stream ordered behind the sweeps.
+    def _class_map(self, classes, device_only: bool):
+        """(pointer, ld, n_maps, keepalive) of a class map: a numpy array or an int32 CUDA tensor [n_maps, n], or [n]."""
+        if _is_tensor(classes) and classes.is_cuda:
+            t = classes.reshape(1, -1) if classes.dim() == 1 else classes
+            if t.dtype != torch.int32 or t.dim() != 2 or t.shape[1] < self.n or t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) < self.n):
+                raise AnnealingError(f"classes must be an int32 CUDA tensor [n_maps, n] or [n] with n = {self.n}, rows contiguous")
+            if not self.shares_torch_stream():
+                _producer_done(t)
+            return C.c_void_p(t.data_ptr()), int(t.stride(0)) if t.shape[0] > 1 else int(t.shape[1]), int(t.shape[0]), t
+        if device_only:
+            raise AnnealingError("classes must be an int32 CUDA tensor (the map stays on the device for the whole run)")
+        a = np.asarray(classes.cpu() if _is_tensor(classes) else classes)
+        a = np.ascontiguousarray(a.reshape(1, -1) if a.ndim == 1 else a, dtype=np.int32)
+        if a.ndim != 2 or a.shape[1] < self.n:
+            raise AnnealingError(f"classes must be an array [n_maps, n] or [n] with n = {self.n}")
+        return a.ctypes.data_as(C.c_void_p), int(a.shape[1]), int(a.shape[0]), a
+
+    def class_overlaps(self, pairs, classes, n_classes: int, which="current", out=None):
+        """int32 [count, n_maps, n_classes]: D[p, m, c], the sites of class c in map m where the two replicas of pair p
+        differ (sga_get_class_overlaps); the class overlap is Q_c = N_c - 2 D_c.  pairs: (a, b) of LOCAL replica indices,
+        any list, a == b gives zeros.  classes: a numpy array or an int32 CUDA tensor [n_maps, n], or [n]; a value outside
+        [0, n_classes) puts the site in no class.  A numpy map is staged on every call: a run keeps its map on the
+        device.  which: "current" | "best".  out: an optional contiguous int32 CUDA tensor of that shape that receives the
+        result on the device; with shares_torch_stream() the call is then only enqueued."""
+        w = self._which(which)
+        pr = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+        cp, ld, n_maps, keep = self._class_map(classes, False)
+        shape = (len(pr), n_maps, int(n_classes))
+        if out is None:
+            res = np.zeros((len(pr), n_maps, max(int(n_classes), 0)), np.int32)
+            op, dev = res.ctypes.data_as(C.c_void_p), False
+        else:
+            if not _is_tensor(out) or not out.is_cuda or out.dtype != torch.int32 or tuple(out.shape) != shape or not out.is_contiguous():
+                raise AnnealingError(f"out must be a contiguous int32 CUDA tensor of shape {list(shape)}")
+            if not self.shares_torch_stream():
+                _producer_done(out)
+            res, op, dev = out, C.c_void_p(out.data_ptr()), True
+        N.check(self._lib.sga_get_class_overlaps(self._h, w, pr.ctypes.data_as(C.c_void_p), len(pr), cp, ld, n_maps, int(n_classes), op),
+                "sga_get_class_overlaps")
+        self._observable_done(dev)
+        if dev:
+            self._pending = (pr, keep, res)  # operands and a device result stay alive while the work is queued
+        return res
+
+    def _class_sums(self, t, shape, what):
+        if not _is_tensor(t) or not t.is_cuda or t.dtype not in (torch.int64, getattr(torch, "uint64", torch.int64)) or \
+                tuple(t.shape) != shape or not t.is_contiguous():
+            raise AnnealingError(f"{what} must be a contiguous uint64 or int64 CUDA tensor of shape {list(shape)}")
+        if not self.shares_torch_stream():
+            _producer_done(t)
+        return C.c_void_p(t.data_ptr())
+
+    def accumulate_ladder_class_overlaps(self, classes, n_classes: int, sum1, sum2=None, slot_lo: int = 0,
+                                         slot_hi: Optional[int] = None):
+        """One measurement per slot slot_lo <= s < slot_hi (None: every slot) and pair of ladders 2p, 2p + 1 into the
+        caller's sums on the device (sga_accumulate_ladder_class_overlaps): between the replicas that hold slot s of both
+        now -- read from the slot map on the device -- D[m, c] is added to sum1[p, s - slot_lo, m, c] and, where sum2 is
+        given, D[m, c] D[m, c'] to sum2[p, s - slot_lo, m, c, c'].  classes: an int32 CUDA tensor [n_maps, n] or [n];
+        sum1, sum2: uint64 or int64 CUDA tensors [n_ladders / 2, slot_hi - slot_lo, n_maps, n_classes(, n_classes)],
+        zeroed by the caller once.  The caller counts its calls.  Only enqueued: nothing comes back."""
+        if self.n_ladders <= 0:
+            raise AnnealingError("no ladder (call set_ladder)")
+        L = self.R_global // self.n_ladders
+        lo, hi = int(slot_lo), L if slot_hi is None else int(slot_hi)
+        cp, ld, n_maps, keep = self._class_map(classes, True)
+        cells = (self.n_ladders // 2, max(hi - lo, 0), n_maps, int(n_classes))
+        p1 = self._class_sums(sum1, cells, "sum1")
+        p2 = None if sum2 is None else self._class_sums(sum2, cells + (int(n_classes),), "sum2")
+        N.check(self._lib.sga_accumulate_ladder_class_overlaps(self._h, lo, hi, cp, ld, n_maps, int(n_classes), p1, p2),
+                "sga_accumulate_ladder_class_overlaps")
+        self._observable_done(True)
+        self._pending = (keep, sum1, sum2)
+
     def hamming(self, which_a="current", which_b=None) -> np.ndarray:
         """int32 [R, R]: Hamming distances (n_r - Q) / 2 between the configurations of overlaps(which_a, which_b), n_r the
         ROW replica's model size on ragged engines (a pair across models is meaningless there)."""

@@ -77,6 +77,13 @@ class ParallelTemperingConfig:
     measure_interval: int = 1             # ... in every measure_interval-th of those rounds, the first one included
     overlap_bins: Optional[int] = None    # ... None: exact, a bin per value (n + 1, links + 1); else the smallest power-of-two
     #                                       bin width that needs at most this many bins
+    measure_class_overlaps: bool = False  # sum, per temperature, the overlap between copies 2c and 2c + 1 resolved by the classes
+    #                                       of overlap_classes and its second moments on the device
+    #                                       (AnnealEngine.accumulate_ladder_class_overlaps; an even n_copies), in the rounds
+    #                                       measure_overlaps would measure (measure_after, measure_interval); read once at the end
+    #                                       into ParallelTempering.class_overlap_statistics.  Off: the run issues no such call
+    overlap_classes: Optional[np.ndarray] = None  # ... the class maps, int [n_maps, n] or [n] (encoders.lattice_planes for the
+    #                                       planes of a lattice); a negative value puts a site in no class
 
     def __post_init__(self):
         if self.site_order not in ("random", "sequential"):
@@ -98,6 +105,18 @@ class ParallelTemperingConfig:
             raise ConfigurationError("measure_interval must be a positive number of exchange rounds")
         if self.overlap_bins is not None and (int(self.overlap_bins) != self.overlap_bins or self.overlap_bins < 1):
             raise ConfigurationError("overlap_bins must be None or a positive integer")
+        if self.measure_class_overlaps:
+            if self.n_copies < 2 or self.n_copies % 2 != 0:
+                raise ConfigurationError("measure_class_overlaps needs an even n_copies >= 2 (the overlaps are taken between two copies of the ladder)")
+            if self.overlap_classes is None:
+                raise ConfigurationError("measure_class_overlaps needs overlap_classes, the class maps [n_maps, n]")
+            cl = np.asarray(self.overlap_classes)
+            if cl.ndim not in (1, 2) or cl.size == 0 or not np.issubdtype(cl.dtype, np.integer):
+                raise ConfigurationError("overlap_classes must be an integer array [n_maps, n] or [n]")
+            if cl.max() < 0:
+                raise ConfigurationError("overlap_classes puts no site in any class")
+            if cl.max() >= 2 ** 31 or cl.min() < -2 ** 31:
+                raise ConfigurationError("overlap_classes must hold 32-bit values")
 
 
 def bin_shift(largest: int, max_bins: Optional[int]) -> int:
@@ -165,6 +184,82 @@ class OverlapStatistics:
         return self._mean(self.hist_l, self.link_values())
 
 
+@dataclass
+class ClassOverlapStatistics:
+    """First and second moments of the class-resolved overlaps between two copies of a ladder, per temperature, as
+    accumulate_ladder_class_overlaps left them.  For copy pair p, temperatures[s] and class map m, with D_c the sites of
+    class c where the two copies differ (the class overlap is Q_c = N_c - 2 D_c): sum1[p, s, m, c] is the sum of D_c over
+    the measurements, sum2[p, s, m, c, c'] the sum of D_c D_c' (None where it was not taken).  class_sizes[m, c] = N_c.
+    Everything here is plain numpy on the host.
+
+    susceptibility(k) and correlation_length() read the class index as a coordinate: they are meaningful only where the
+    classes are the planes of a periodic lattice (encoders.lattice_planes), every map one axis."""
+    temperatures: np.ndarray
+    class_sizes: np.ndarray
+    measurements: int
+    sum1: np.ndarray
+    sum2: Optional[np.ndarray] = None
+
+    def class_correlations(self) -> np.ndarray:
+        """<Q_c Q_c'> per copy pair, temperature and map, float64 [pairs, slots, n_maps, C, C], from
+        N_c N_c' - 2 N_c <D_c'> - 2 N_c' <D_c> + 4 <D_c D_c'>: formed in exact integers as T N_c N_c' - 2 N_c S1_c' -
+        2 N_c' S1_c + 4 S2_cc' (T measurements) before the one division by T.  NaN where nothing was measured."""
+        if self.sum2 is None:
+            raise ConfigurationError("no second moments were measured (sum2 is None)")
+        T = int(self.measurements)
+        N_ = [[int(v) for v in row] for row in np.asarray(self.class_sizes)]
+        s1, s2 = np.asarray(self.sum1), np.asarray(self.sum2)
+        out = np.full(s2.shape, np.nan, np.float64)
+        if T <= 0:
+            return out
+        for idx in np.ndindex(*s2.shape[:3]):
+            Nm = np.asarray(N_[idx[2]], dtype=object)
+            a = np.asarray([int(v) for v in s1[idx]], dtype=object)
+            b = np.asarray([[int(v) for v in row] for row in s2[idx]], dtype=object)
+            num = T * np.outer(Nm, Nm) - 2 * np.outer(Nm, a) - 2 * np.outer(a, Nm) + 4 * b  # Python integers: exact
+            out[idx] = (num / T).astype(np.float64)
+        return out
+
+    def susceptibility(self, k: float) -> np.ndarray:
+        """chi(k) = (1 / n) sum_{c, c'} <Q_c Q_c'> cos(k (c - c')) per temperature, averaged over the maps and the copy
+        pairs; n = the sites of a map, sum_c N_c."""
+        qq = self.class_correlations()
+        c = np.arange(qq.shape[-1], dtype=np.float64)
+        w = np.cos(float(k) * (c[:, None] - c[None, :]))
+        n_sites = np.asarray(self.class_sizes, np.float64).sum(axis=1)  # [n_maps]
+        chi = (qq * w).sum(axis=(3, 4)) / n_sites[None, None, :]
+        return chi.mean(axis=(0, 2))
+
+    def correlation_length(self) -> np.ndarray:
+        """xi = sqrt(chi(0) / chi(k_min) - 1) / (2 sin(k_min / 2)) per temperature, k_min = 2 pi / C: the finite-size
+        correlation length whose ratio xi / L crosses at T_c.  NaN where nothing was measured or the radicand is negative
+        or undefined (chi(k_min) = chi(0) = 0); +inf where chi(k_min) = 0 < chi(0), zero meaning |chi(k_min)| <= 1e-12 chi(0).  Meaningful only where the
+        classes are the planes of a periodic lattice."""
+        C = self.sum1.shape[-1]
+        k_min = 2.0 * np.pi / C
+        chi0, chik = self.susceptibility(0.0), self.susceptibility(k_min)
+        zero = np.abs(chik) <= 1e-12 * np.abs(chi0)  # chi(k_min) = 0 up to the rounding of the cosine sum
+        with np.errstate(divide="ignore", invalid="ignore"):
+            rad = np.where(zero, np.where(chi0 > 0, np.inf, np.nan), chi0 / np.where(zero, 1.0, chik) - 1.0)
+            return np.sqrt(np.where(rad >= 0, rad, np.nan)) / (2.0 * np.sin(k_min / 2.0))
+
+
+def planned_measurements(n_sweeps: int, exchange_interval: int, measure_after: int, measure_interval: int) -> int:
+    """The exchange rounds a run measures in: those behind sweeps s = exchange_interval, 2 exchange_interval ... < n_sweeps
+    with s + 1 >= measure_after, every measure_interval-th of them, the first one included."""
+    last = (n_sweeps - 1) // exchange_interval                       # s = k exchange_interval, 1 <= k <= last
+    first = max(1, -(-(measure_after - 1) // exchange_interval))      # ... and k exchange_interval + 1 >= measure_after
+    eligible = max(0, last - first + 1)
+    return -(-eligible // measure_interval)
+
+
+def class_sizes(classes: np.ndarray, n_classes: int) -> np.ndarray:
+    """N[m, c]: the sites of class c in map m (values outside [0, n_classes) are no class), int64 [n_maps, n_classes]."""
+    cl = np.asarray(classes)
+    cl = cl.reshape(1, -1) if cl.ndim == 1 else cl
+    return np.stack([np.bincount(row[(row >= 0) & (row < n_classes)], minlength=n_classes) for row in cl]).astype(np.int64)
+
+
 class ParallelTempering:
     def __init__(self, config: ParallelTemperingConfig):
         if config.n_replicas < 2:
@@ -186,6 +281,8 @@ class ParallelTempering:
         # measure_overlaps: the histograms of the last run() (OverlapStatistics) and the exchange rounds that were measured
         self.overlap_statistics: Optional[OverlapStatistics] = None
         self.overlap_rounds_measured = 0
+        # measure_class_overlaps: the sums of the last run() (ClassOverlapStatistics)
+        self.class_overlap_statistics: Optional[ClassOverlapStatistics] = None
         self.device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
         self.use_cuda = self.device.type == "cuda"
 
@@ -207,6 +304,8 @@ class ParallelTempering:
         t_start = time.time()
         R, n, C = cfg.n_replicas, model.n_spins, int(cfg.n_copies)
         temps = np.asarray(self.temperatures, np.float64)
+        self.class_overlap_statistics = None
+        class_plan = self.class_overlap_plan(n) if cfg.measure_class_overlaps else None  # (refused before the device is touched)
         if C > 1 and _replay is not None:
             raise ConfigurationError("the replay hook drives one ladder (n_copies = 1)")
         # the slots the cluster moves act in: the ladder is monotone (index 0 the hottest), so they are one range
@@ -255,6 +354,13 @@ class ParallelTempering:
                     l_shift = bin_shift(n_links, cfg.overlap_bins)
                     hist_l = torch.zeros((C // 2, R, min((n_links >> l_shift) + 1, cfg.overlap_bins or n_links + 1)),
                                          dtype=torch.int64, device=hdev)
+            cls_map = cls_sum1 = cls_sum2 = None
+            cls_measured = 0
+            if class_plan is not None:  # the map and the sums stay on the device for the whole run
+                cdev = torch.device("cuda", dev_idx)
+                cls_map = torch.from_numpy(class_plan[0]).to(cdev)
+                cls_sum1 = torch.zeros((C // 2, R) + class_plan[0].shape[:1] + (class_plan[1],), dtype=torch.int64, device=cdev)
+                cls_sum2 = torch.zeros(tuple(cls_sum1.shape) + (class_plan[1],), dtype=torch.int64, device=cdev)
             eng.maybe_autotune(cfg.n_sweeps, cfg.autotune)
             slot_to_rep = np.arange(R, dtype=np.int32)
             acc_prev = np.zeros(R, np.int64)
@@ -312,6 +418,10 @@ class ParallelTempering:
                         eng.accumulate_ladder_overlaps(hist_q, hist_l, q_shift=q_shift, l_shift=l_shift)
                         self.overlap_rounds_measured += 1
                     eligible += 1
+                if exchange_now and cls_map is not None and stop + 1 >= cfg.measure_after:
+                    if cls_measured % cfg.measure_interval == 0:
+                        eng.accumulate_ladder_class_overlaps(cls_map, class_plan[1], cls_sum1, cls_sum2)
+                    cls_measured += 1
                 # one synchronisation per event: energies (an exchange moves labels, not energies),
                 # acceptance counters, ladder permutation
                 en_rep, acc_now, full_map = eng.snapshot()
@@ -344,6 +454,10 @@ class ParallelTempering:
                 self.overlap_statistics = OverlapStatistics(
                     temperatures=temps.copy(), n=int(n), n_links=n_links, hist_q=hist_q.cpu().numpy(), q_shift=q_shift,
                     hist_l=None if hist_l is None else hist_l.cpu().numpy(), l_shift=l_shift)
+            if cls_map is not None:
+                self.class_overlap_statistics = ClassOverlapStatistics(
+                    temperatures=temps.copy(), class_sizes=class_plan[2], measurements=-(-cls_measured // cfg.measure_interval),
+                    sum1=cls_sum1.cpu().numpy().view(np.uint64), sum2=cls_sum2.cpu().numpy().view(np.uint64))
         self.slot_acceptance = acc_slot / np.maximum(att_slot, 1)
         total_time = time.time() - t_start
         return AnnealingResult(
@@ -353,6 +467,24 @@ class ParallelTempering:
             acceptance_rate_history=[float(x) for x in self.slot_acceptance],
             total_time=total_time, n_sweeps=cfg.n_sweeps, algorithm="parallel_tempering",
             device=f"cuda:{dev_idx}", random_seed=cfg.random_seed)
+
+    def class_overlap_plan(self, n: int):
+        """(class maps int32 [n_maps, n], n_classes, class sizes, planned measurements) of measure_class_overlaps for a
+        model of n spins; ConfigurationError where the maps do not fit the model, or where the sums could overflow:
+        measurements x max N_c^2 must stay below 2^63."""
+        cfg = self.config
+        cfg.check_copies()
+        cl = np.asarray(cfg.overlap_classes)
+        cl = np.ascontiguousarray(cl.reshape(1, -1) if cl.ndim == 1 else cl, dtype=np.int32)
+        if cl.shape[1] != n:
+            raise ConfigurationError(f"overlap_classes has {cl.shape[1]} sites, the model has {n}")
+        n_classes = int(cl.max()) + 1
+        sizes = class_sizes(cl, n_classes)
+        planned = planned_measurements(cfg.n_sweeps, cfg.exchange_interval, cfg.measure_after, cfg.measure_interval)
+        if planned * int(sizes.max()) ** 2 >= 2 ** 63:
+            raise ConfigurationError(f"measure_class_overlaps: {planned} measurements of classes of up to {int(sizes.max())} sites "
+                                     "could overflow the 64-bit sums (measurements x max N_c^2 must stay below 2^63)")
+        return cl, n_classes, sizes, planned
 
     def _event(self, sweep: int) -> bool:
         c = self.config
