@@ -80,7 +80,7 @@ typedef struct sga_engine sga_engine;
 int sga_create(int device, sga_engine **out);
 void sga_destroy(sga_engine *e);
 const char *sga_last_error(void);
-int sga_version(void);  /* 2800: sga_get_class_overlaps / sga_accumulate_ladder_class_overlaps (the overlap between two replicas resolved by a class of sites, first and second moments per temperature summed on the device, csrc/class_overlaps.hip; read only, no engine state, no option); 2700: sga_get_link_count / sga_get_pair_overlaps / sga_accumulate_ladder_overlaps (spin and link overlaps between pairs of replicas, histogrammed per temperature on the device, csrc/pair_overlaps.hip; read only, no engine state, no option); 2600: sga_resample (the resampling step of population annealing, csrc/resample.hip); 2500: sga_cluster_move_pairs / sga_cluster_move_ladders (isoenergetic cluster moves between replica copies on sparse couplings, csrc/cluster_moves.hip; no engine state, no option); 2400: sga_set_replica_groups / sga_get_replica_groups; 2300: sga_get_magnetizations / sga_get_overlaps / sga_get_overlaps_with (replica observables on the device: the exact integer product of int8 spin rows on the matrix cores, csrc/observables.hip; read only, no engine state); 2200: the row-shared fields in tiles take a plan of their own, one launch per sweep (csrc/sweep_dense_rs.hip, rs_tile_plan_kernel; no change of interface or results); 2100: sga_set_sequential_windows / sga_get_sequential_windows (SGA_SITE_SEQUENTIAL sweeps in windows, the fields of every replica on the matrix cores; csrc/sweep_dense_seq.hip); 2000: the row-shared windows (option "row_shared") serve SGA_RULE_GLAUBER and SGA_RULE_HEAT_BATH too ("rule=glauber" / "rule=heat-bath" in sga_describe and sga_get_last_kernel; the window sga_autotune picks holds for the rule it was timed under); 1900: options "row_shared_fields" and "row_shared_tile_sites" (row-shared fields in tiles of sites, sign-only rows); 1800: option "row_shared_grid", sga_route_query.rs_grid; 1700: sga_set_csr_shared (one set of CSR rows, many field vectors: every one-wave-per-replica CSR form for such batches), sga_route_query.shared_j on SGA_ROUTE_CSR queries; 1600: sga_set_dense_shared (one coupling matrix, many field vectors; row-shared windows, bit-planes and the matrix-core pass for such batches), sga_route_query.shared_j; 1500: sga_get_scan_summary, and sga_set_dense / sga_set_dense_batch / sga_set_csr / sga_set_csr64 / sga_set_csr_batch refuse a NaN or +-Inf in J or h (SGA_ERR_INVALID, "non-finite"); 1400: option "batch_fixed_point" (fixed-point cached local fields for many-model dense batches); 1300: options "ragged_field_cache" and "clf_fixed_point" together (fixed-point cached local fields for ragged CSR batches); 1200: sga_set_groups_csr (group couplings plus a stored sparse remainder); 1100: option "ragged_field_cache" (cached local fields for ragged CSR batches); 1000: sga_set_groups */
+int sga_version(void);  /* 2900: sga_sweep_transverse (simulated quantum annealing: the Trotter slices of one instance coupled in the CSR sweep, two half-sweeps per sweep, csrc/sweep_transverse.hip; no option, no engine member); 2800: sga_get_class_overlaps / sga_accumulate_ladder_class_overlaps (the overlap between two replicas resolved by a class of sites, first and second moments per temperature summed on the device, csrc/class_overlaps.hip; read only, no engine state, no option); 2700: sga_get_link_count / sga_get_pair_overlaps / sga_accumulate_ladder_overlaps (spin and link overlaps between pairs of replicas, histogrammed per temperature on the device, csrc/pair_overlaps.hip; read only, no engine state, no option); 2600: sga_resample (the resampling step of population annealing, csrc/resample.hip); 2500: sga_cluster_move_pairs / sga_cluster_move_ladders (isoenergetic cluster moves between replica copies on sparse couplings, csrc/cluster_moves.hip; no engine state, no option); 2400: sga_set_replica_groups / sga_get_replica_groups; 2300: sga_get_magnetizations / sga_get_overlaps / sga_get_overlaps_with (replica observables on the device: the exact integer product of int8 spin rows on the matrix cores, csrc/observables.hip; read only, no engine state); 2200: the row-shared fields in tiles take a plan of their own, one launch per sweep (csrc/sweep_dense_rs.hip, rs_tile_plan_kernel; no change of interface or results); 2100: sga_set_sequential_windows / sga_get_sequential_windows (SGA_SITE_SEQUENTIAL sweeps in windows, the fields of every replica on the matrix cores; csrc/sweep_dense_seq.hip); 2000: the row-shared windows (option "row_shared") serve SGA_RULE_GLAUBER and SGA_RULE_HEAT_BATH too ("rule=glauber" / "rule=heat-bath" in sga_describe and sga_get_last_kernel; the window sga_autotune picks holds for the rule it was timed under); 1900: options "row_shared_fields" and "row_shared_tile_sites" (row-shared fields in tiles of sites, sign-only rows); 1800: option "row_shared_grid", sga_route_query.rs_grid; 1700: sga_set_csr_shared (one set of CSR rows, many field vectors: every one-wave-per-replica CSR form for such batches), sga_route_query.shared_j on SGA_ROUTE_CSR queries; 1600: sga_set_dense_shared (one coupling matrix, many field vectors; row-shared windows, bit-planes and the matrix-core pass for such batches), sga_route_query.shared_j; 1500: sga_get_scan_summary, and sga_set_dense / sga_set_dense_batch / sga_set_csr / sga_set_csr64 / sga_set_csr_batch refuse a NaN or +-Inf in J or h (SGA_ERR_INVALID, "non-finite"); 1400: option "batch_fixed_point" (fixed-point cached local fields for many-model dense batches); 1300: options "ragged_field_cache" and "clf_fixed_point" together (fixed-point cached local fields for ragged CSR batches); 1200: sga_set_groups_csr (group couplings plus a stored sparse remainder); 1100: option "ragged_field_cache" (cached local fields for ragged CSR batches); 1000: sga_set_groups */
 /* Run on an existing HIP stream (e.g. torch.cuda.current_stream().cuda_stream); NULL = the
  * engine's own stream (default). */
 int sga_set_stream(sga_engine *e, void *hip_stream);
@@ -566,6 +566,48 @@ int sga_get_class_overlaps(sga_engine *e, int which /* SGA_SPINS_CURRENT | SGA_S
 int sga_accumulate_ladder_class_overlaps(sga_engine *e, int slot_lo, int slot_hi,
                                          const int32_t *classes /* [n_maps][ld], device */, int64_t ld, int n_maps, int n_classes,
                                          uint64_t *sum1, uint64_t *sum2 /* or NULL */);
+
+/* ---- simulated quantum annealing: Trotter slices coupled in the sweep (version >= 2900; csrc/sweep_transverse.hip) ---
+ * Path-integral Monte Carlo of the transverse-field Ising model: P replicas -- the Trotter slices of ONE instance -- each
+ * sweep under a field that depends on the spins of the two neighbouring slices.
+ *   The local replicas are cut into G = R_local / P contiguous groups of P = n_slices slices; each group is one instance
+ *   of the quantum problem.  replica0 % P == 0, so groups lie whole on a rank and no collective is needed.  The slice
+ *   index of local replica r is p = (replica0 + r) % P, its neighbours are the slices p +- 1 mod P of its group (P = 2:
+ *   both neighbours are the same slice, counted twice).
+ *   Sweep kk of the call is two half-sweeps, enqueued on the engine's stream: half-sweep A moves the slices with even p
+ *   while the odd ones stand still, half-sweep B the odd ones.  P is even, so a moving slice never has a moving neighbour.
+ *   Within a half-sweep every moving slice r performs the n updates t = 0 ... n-1 of sga_sweep's production stream in
+ *   SGA_SITE_RANDOM mode: site and u from Philox counter (t >> 1, sweeps_done + kk, replica0 + r, 0) -- domain 0, no new
+ *   domain word.  The update at site i:
+ *     a     = s_up[i] + s_dn[i] in {-2, 0, 2}, the neighbour slices as they stand at the start of the half-sweep;
+ *     h_eff = h_i + k (float)a in fp32, k = k_perp[kk][g] (the product is exact: the sum rounds once, an FMA gives the
+ *             same bits);
+ *     the decision is the engine's Metropolis rule in `arith` on (fp32 row sum of J s, s_i, h_eff, T_r, u): what
+ *             sga_update decides for a problem whose field at i is h_eff, T = 0 and T = inf included;
+ *     on accept the spin flips, the accept counter grows by one and the tracked energy moves by the CLASSICAL dE -- the
+ *             dE the same rule computes with h_i in place of h_eff, what sga_flip would report: the tracked energy stays
+ *             the slice's classical energy -1/2 s J s - h s (sga_recompute_energies gives the same value).
+ *   After both half-sweeps of a sweep every slice's best follows where its energy is lower (the step a sweep's end runs).
+ *   sweeps_done grows by n_sweeps at the end of the call; the cached local fields are marked for re-seeding, as after
+ *   sga_set_spins.  Temperatures, the slot map, exchange statistics, round counters and Wolff cursors do not move.
+ *   By construction: with k = 0 everywhere the call is sga_sweep(n_sweeps, SGA_SITE_RANDOM, arith) bit for bit (spins,
+ *   energies, bests, counters), and a call of 2 sweeps equals two calls of 1 sweep.
+ *   Equal temperatures within a group are the caller's responsibility, as with the cluster move.  So is the physical
+ *   mapping: at temperature T and transverse field Gamma each slice runs at P T with
+ *   k_perp = -(P T / 2) ln tanh(Gamma / (P T)) in classical energy units.  Any finite k_perp, negative values included.
+ *   k_perp is a HOST array, copied to the device once per call (it has left the caller's buffer on return).
+ *   Served: one-model CSR problems (sga_set_csr, sga_set_csr64, a sparse matrix that sga_set_dense kept as CSR) whose
+ *   set-time class has an exact fp32 integer row sum in any order (integer J; any fp32 h), symmetric with a zero
+ *   diagonal, under SGA_RULE_METROPOLIS, a slice's int8 spins within LDS (n <= ~163 000).
+ *   SGA_ERR_UNSUPPORTED, with the reason in sga_last_error: dense couplings, sga_set_tsp, sga_set_groups /
+ *   sga_set_groups_csr, batches (ragged and shared), the other CSR classes (real-valued J needs the canonical order),
+ *   rules other than Metropolis, asymmetric J or a non-zero diagonal.
+ *   SGA_ERR_INVALID, before anything is enqueued or changed: a NULL engine or k_perp, a device k_perp; no problem or no
+ *   replicas; n_sweeps < 0; a bad arith; P odd, P < 2, P not a divisor of R_local, replica0 % P != 0; a NaN or infinite
+ *   k_perp.  Argument errors are reported before the problem's kind is looked at.  n_sweeps == 0 is a no-op.
+ *   The launches (two per sweep, built per arithmetic) show in sga_get_last_kernel; sga_enable_timing does not bracket them. */
+int sga_sweep_transverse(sga_engine *e, int n_sweeps, int n_slices, int arith /* SGA_ARITH_* */,
+                         const float *k_perp /* host [n_sweeps][R_local / n_slices] */);
 
 /* Stateless operator form of CUDAKernelManager.parallel_tempering_exchange_optimized
  * (annealing/cuda_kernels.py:326-369, fallback :415-443): sequential adjacent pairs, fp32,

@@ -17,6 +17,9 @@ from .energy_computer import ComputeMode, EnergyComputer, EnergyStats
 from .gpu_annealer import GPUAnnealer, GPUAnnealerConfig
 from .parallel_tempering import ClassOverlapStatistics, OverlapStatistics, ParallelTempering, ParallelTemperingConfig
 from .population_annealing import PopulationAnnealing, PopulationAnnealingConfig
+from . import quantum
+from .quantum import (QuantumFluctuations, SimulatedQuantumAnnealing, SimulatedQuantumAnnealingConfig, TransverseField,
+                      transverse_coupling)
 from .kernel_manager import CUDAKernelManager, GPUMemoryOptimizer, HIPKernelManager
 from .scheduler import SpinGlassScheduler
 from .sharded import LocalShardedTempering, ShardedTempering
@@ -32,6 +35,8 @@ __all__ = [
     "AnnealingResult", "IsingModel", "IsingModelConfig", "SpinDynamics", "UpdateRule",
     "GPUAnnealer", "GPUAnnealerConfig", "ParallelTempering", "ParallelTemperingConfig", "OverlapStatistics", "ClassOverlapStatistics",
     "PopulationAnnealing", "PopulationAnnealingConfig",
+    "quantum", "QuantumFluctuations", "SimulatedQuantumAnnealing", "SimulatedQuantumAnnealingConfig", "TransverseField",
+    "transverse_coupling",
     "HIPKernelManager", "CUDAKernelManager", "GPUMemoryOptimizer", "SpinGlassScheduler",
     "ShardedTempering", "LocalShardedTempering", "MultiGPUAnnealer", "MultiGPUConfig", "LoadBalancer",
     "encoders", "IsingBuilder", "BatchConfig", "BatchProcessor", "EnergyComputer", "ComputeMode",

@@ -347,6 +347,9 @@ extern "C" {
 
 const char *sga_last_error(void) { return g_last_error.c_str(); }
 // The ABI version, one line per step:
+//   2900:    + sga_sweep_transverse: simulated quantum annealing, the Trotter slices of one instance coupled in the CSR
+//            sweep -- two half-sweeps per sweep, the moving slices under h + k (s_up + s_dn) (sweep_transverse.hip; the
+//            admission rule in sga_kernels.h); no option, no engine member
 //   2800:    + sga_get_class_overlaps / sga_accumulate_ladder_class_overlaps: the overlap between two replicas resolved
 //            by a class of sites (planes of a lattice, sublattices, communities), the pairs of two ladders read from the
 //            slot map and summed into the caller's first and second moments on the device (class_overlaps.hip; host
@@ -390,7 +393,7 @@ const char *sga_last_error(void) { return g_last_error.c_str(); }
 //   600:     + sga_set_csr_batch / sga_get_batch_model (ragged CSR batches)
 //   round 5: + sga_explain_route / sga_get_route_query, sga_get_last_kernel, sga_get_autotune_table, ladder-local
 //            sga_exchange
-int sga_version(void) { return 2800; }
+int sga_version(void) { return 2900; }
 
 int sga_create(int device, sga_engine **out) {
     if (!out) return fail(SGA_ERR_INVALID, "out is NULL");
@@ -1213,6 +1216,78 @@ int sga_sweep(sga_engine *e, int n_sweeps, int site_mode, int arith, const doubl
     e->sweeps_done += (uint32_t)n_sweeps;
     e->attempted += (long long)n_sweeps * e->n;
     return c.finish(e->stream);
+}
+
+// ---- simulated quantum annealing: Trotter slices coupled in the sweep (sweep_transverse.hip) ----------------------
+// No state of its own: k_perp is staged in scratch slot 0 (where sga_sweep stages a schedule), and per sweep two
+// launches follow each other on the engine's stream, the even slices' half-sweep and the odd ones'.
+int sga_sweep_transverse(sga_engine *e, int n_sweeps, int n_slices, int arith, const float *k_perp) {
+    sga::TransverseProblem tp;
+    if (e) {
+        tp.n = e->n, tp.R_local = e->spins ? e->R : 0, tp.replica0 = e->replica0, tp.sstride = e->sstride;
+        tp.csr = e->csr, tp.tsp = e->tsp, tp.groups = e->groups, tp.ragged = e->ragged, tp.n_models = e->n_models;
+        tp.csr_acc = e->csr_acc;
+        tp.metropolis = e->rule == SGA_RULE_METROPOLIS;
+        tp.consistent_dE = e->consistent_dE;
+    }
+    if (k_perp && is_device_ptr(k_perp)) return fail(SGA_ERR_INVALID, "k_perp must be a host buffer");
+    bool invalid = true;
+    if (const char *why = sga::transverse_check(e != nullptr, tp, n_sweeps, n_slices, arith == SGA_ARITH_F64 || arith == SGA_ARITH_F32,
+                                                k_perp, &invalid))
+        return fail(invalid ? SGA_ERR_INVALID : SGA_ERR_UNSUPPORTED, why);
+    if (n_sweeps == 0) return SGA_OK;
+    if (e->opt_stale)
+        return fail(SGA_ERR_INVALID, std::string("option \"") + (e->opt_stale_key ? e->opt_stale_key : "?") +
+                                         "\" changed after it was read: set the couplings and initialise the replicas again");
+    if (!e->rowptr64 || !e->cv || !e->h || !e->best_spins) return fail(SGA_ERR_INVALID, "no couplings set");
+    HIPCHK(hipSetDevice(e->device));
+    hipStream_t st = e->stream;
+    const int G = e->R / n_slices;
+    // (a pageable host array: the copy has left the caller's buffer when the call returns)
+    HIPCHK(e->scratch[0].reserve((size_t)n_sweeps * (size_t)G * sizeof(float)));
+    float *d_k = static_cast<float *>(e->scratch[0].ptr);
+    HIPCHK(hipMemcpyAsync(d_k, k_perp, (size_t)n_sweeps * (size_t)G * sizeof(float), hipMemcpyHostToDevice, st));
+    sga::SweepArgs a{};
+    a.rowptr64 = e->rowptr64;
+    a.cv = e->cv;
+    a.h = e->h;
+    a.diag = e->diag;
+    a.spins = e->spins;
+    a.energy = e->energy;
+    a.best_energy = e->best_energy;
+    a.best_spins = e->best_spins;
+    a.n_accepted = e->n_acc;
+    a.rep_temp = e->rep_temp;
+    a.n = e->n;
+    a.sstride = e->sstride;
+    a.R = e->R;
+    a.n_sweeps = 1;
+    a.site_mode = SGA_SITE_RANDOM;
+    a.arith = arith;
+    a.rule = SGA_RULE_METROPOLIS;
+    a.csr_acc = e->csr_acc;
+    a.seed_lo = (uint32_t)e->seed;
+    a.seed_hi = (uint32_t)(e->seed >> 32);
+    a.replica0 = (uint32_t)e->replica0;
+    float *h_eff = nullptr;
+#if defined(SGA_TRANSVERSE_PREPASS) && SGA_TRANSVERSE_PREPASS  // (measurement builds: sweep_transverse.hip)
+    HIPCHK(e->scratch[1].reserve((size_t)e->R * (size_t)e->n * sizeof(float)));
+    h_eff = static_cast<float *>(e->scratch[1].ptr);
+#endif
+    e->fields_valid = false;  // (as after sga_set_spins: the next sweep seeds the cached fields again)
+    for (int kk = 0; kk < n_sweeps; ++kk) {
+        a.sweep0 = e->sweeps_done + (uint32_t)kk;
+        for (int parity = 0; parity < 2; ++parity) {
+            const sga::TransverseArgs t{d_k + (size_t)kk * (size_t)G, n_slices, parity, G * (n_slices / 2), h_eff};
+            const hipError_t le = sga::launch_sweep_transverse(a, t, st);
+            if (le != hipSuccess) (void)hipStreamSynchronize(st);
+            HIPCHK(le);
+        }
+    }
+    std::snprintf(e->last_kernel, sizeof(e->last_kernel), "%s", sga::last_sweep_kernel());
+    e->sweeps_done += (uint32_t)n_sweeps;
+    e->attempted += (long long)n_sweeps * e->n;
+    return SGA_OK;
 }
 
 int sga_set_update_rule(sga_engine *e, int rule) {

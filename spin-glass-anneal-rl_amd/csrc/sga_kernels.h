@@ -977,6 +977,66 @@ struct ClassOverlapArgs {
 };
 hipError_t launch_class_overlaps(const ClassOverlapArgs &a, hipStream_t st);
 
+// Simulated quantum annealing: Trotter slices coupled in the CSR sweep (sweep_transverse.hip; sga_sweep_transverse).
+// The local replicas are G = R_local / P contiguous groups of P slices; a launch is one HALF-SWEEP: the slices of one
+// parity each perform the n updates of sga_sweep's production stream under the field h_i + k (s_up[i] + s_dn[i]), the
+// other parity stands still and is only read.  One wave per moving slice, its int8 spins in LDS (sstride bytes a wave).
+constexpr size_t TRANSVERSE_LDS_BUDGET = 160 * 1024 - 256;
+inline int transverse_waves_per_block(int sstride) {  // 0: a slice's spins do not fit
+    if (sstride <= 0) return 0;
+    const size_t wpb = TRANSVERSE_LDS_BUDGET / (size_t)sstride;
+    return wpb > (size_t)CSR_WAVES_PER_BLOCK ? CSR_WAVES_PER_BLOCK : (int)wpb;
+}
+// What of an engine the admission rule reads.
+struct TransverseProblem {
+    int n = 0, R_local = 0, replica0 = 0, sstride = 0;
+    int csr = 0, tsp = 0, groups = 0, ragged = 0, n_models = 1;
+    int csr_acc = CSR_ACC_F64_CANON;
+    int metropolis = 1;     // the engine's rule is SGA_RULE_METROPOLIS
+    int consistent_dE = 1;  // J symmetric with zero diagonal: the rule's dE is the energy change
+};
+// The admission rule of sga_sweep_transverse, a pure function: nullptr where the call is served, else why not, with
+// *invalid = true for SGA_ERR_INVALID and false for SGA_ERR_UNSUPPORTED.  Every argument error comes first, so that a
+// wrong call is told so whatever the problem; k_perp: the caller's HOST array [n_sweeps][R_local / n_slices].
+inline const char *transverse_check(bool have_engine, const TransverseProblem &p, int n_sweeps, int n_slices, bool arith_ok,
+                                    const float *k_perp, bool *invalid) {
+    *invalid = true;
+    if (!have_engine) return "engine is NULL";
+    if (!k_perp) return "k_perp is NULL";
+    if (p.n <= 0) return "no couplings set";
+    if (p.R_local <= 0) return "no replicas (call sga_init_replicas)";
+    if (n_sweeps < 0) return "n_sweeps < 0";
+    if (!arith_ok) return "bad arith";
+    if (n_slices < 2) return "n_slices must be at least 2";
+    if (n_slices % 2 != 0) return "n_slices must be even (a moving slice never has a moving neighbour)";
+    if (p.R_local % n_slices != 0) return "n_slices must divide the number of local replicas";
+    if (p.replica0 % n_slices != 0) return "replica0 must be a multiple of n_slices (groups lie whole on a rank)";
+    const long long count = (long long)n_sweeps * (p.R_local / n_slices);
+    for (long long i = 0; i < count; ++i)
+        if (!(k_perp[i] - k_perp[i] == 0.0f)) return "k_perp holds a NaN or an infinite value";
+    *invalid = false;
+    if (p.tsp) return "transverse sweeps are not implemented for sga_set_tsp problems";
+    if (p.groups) return "transverse sweeps are not implemented for sga_set_groups / sga_set_groups_csr problems";
+    if (p.ragged) return "transverse sweeps are not implemented for ragged CSR batches";
+    if (p.n_models > 1) return "transverse sweeps are not implemented for many-model batches (shared or stacked)";
+    if (!p.csr) return "transverse sweeps need sparse (CSR) couplings: dense couplings are not served";
+    if (p.csr_acc != CSR_ACC_F32_TABLE && p.csr_acc != CSR_ACC_F32)
+        return "transverse sweeps need integer couplings with exact fp32 row sums (real-valued J needs the canonical order)";
+    if (!p.metropolis) return "transverse sweeps are implemented for the Metropolis rule only";
+    if (!p.consistent_dE) return "transverse sweeps need symmetric couplings with a zero diagonal";
+    if (transverse_waves_per_block(p.sstride) < 1) return "transverse sweeps: a slice's int8 spins do not fit LDS";
+    return nullptr;
+}
+struct TransverseArgs {
+    const float *k_perp;  // device [G]: this sweep's coupling per group
+    int n_slices;         // P
+    int parity;           // the slices p with p % 2 == parity move
+    int moving;           // G P / 2 waves
+    float *h_eff;         // measurement builds with -DSGA_TRANSVERSE_PREPASS=1 only: scratch [R][n]; null otherwise
+};
+// a: the arguments of one production sweep (n_sweeps = 1, sweep0 = the sweep's counter); reads a.rowptr64 / a.cv
+hipError_t launch_sweep_transverse(const SweepArgs &a, const TransverseArgs &t, hipStream_t st);
+
 // operator-form PT exchange (cuda_kernels.py:415-443): decide sequentially, then permute rows
 hipError_t launch_op_exchange(float *spins, float *tmp_rows, float *energies, const float *temps,
                               const float *u, int32_t *src_of_pos, int *n_accepted,

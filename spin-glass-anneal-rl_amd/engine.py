@@ -70,6 +70,20 @@ def resample_log_q(shift, weight_sum, members: int) -> np.ndarray:
     return np.asarray(shift, np.float64) + np.log(w / (float(members) * 2.0 ** 40))
 
 
+def transverse_k_perp(k_perp, n_sweeps: int, n_groups: int) -> np.ndarray:
+    """k_perp as sga_sweep_transverse takes it, float32 [n_sweeps, n_groups], from a scalar, [n_sweeps] (one value per
+    sweep, shared by the groups) or [n_sweeps, n_groups].  Shapes only: the values are the engine's to judge."""
+    n_sweeps, G = max(int(n_sweeps), 0), int(n_groups)
+    k = np.asarray(k_perp, dtype=np.float32)
+    if k.ndim == 0:
+        k = np.full((n_sweeps, G), k, np.float32)
+    elif k.shape == (n_sweeps,):
+        k = np.repeat(k[:, None], G, axis=1)
+    elif k.shape != (n_sweeps, G):
+        raise AnnealingError("k_perp must be a scalar, [n_sweeps] or [n_sweeps, R / n_slices]")
+    return np.ascontiguousarray(k, dtype=np.float32)
+
+
 def concat_csr_batch(problems):
     """[(rowptr, colidx, val, h), ...] (numpy or torch, model-local columns) -> the one concatenated CSR of
     sga_set_csr_batch: (n_spins int32 [M], rowptr int64 [sum n + 1], colidx int32, val float32, h float32).
@@ -547,6 +561,19 @@ class AnnealEngine:
         N.check(self._lib.sga_sweep(self._h, n_sweeps, int(site_mode), int(arith), sp, ss, rs, rsp,
                                     rup, ptr(et), ptr(at), ptr(dt)), "sga_sweep")
         return {"energy_trace": et, "accept_trace": at, "dE_trace": dt}
+
+    # ------------------------------------------------------------------ simulated quantum annealing
+    def sweep_transverse(self, n_sweeps: int, n_slices: int, k_perp, arith: int = N.ARITH_F64):
+        """n_sweeps sweeps of the replicas as R / n_slices groups of n_slices Trotter slices (sga_sweep_transverse): per
+        sweep the even slices move under h + k (s_up + s_dn), then the odd ones; the tracked energies stay classical.
+        k_perp: a scalar, [n_sweeps] or [n_sweeps, R / n_slices] (see quantum.transverse_coupling).  A problem the step
+        does not serve raises AnnealingError with the engine's reason."""
+        P = int(n_slices)
+        # (a P the engine will refuse: any well-formed array, so that the refusal and its reason are the engine's)
+        G = self.R // P if P >= 1 and self.R > 0 and self.R % P == 0 else 1
+        k = transverse_k_perp(k_perp, n_sweeps, G)
+        N.check(self._lib.sga_sweep_transverse(self._h, int(n_sweeps), int(n_slices), int(arith), k.ctypes.data_as(C.c_void_p)),
+                "sga_sweep_transverse")
 
     # single-site operators (the reference's per-spin API)
     def local_fields(self, r: int, sites) -> np.ndarray:
