@@ -755,6 +755,32 @@ constexpr int RS_CHAIN_U = 8;  // earlier accepts applied to a block per wait
 #define SGA_RS_CHAIN_TABLE 1
 #endif
 constexpr bool RS_CHAIN_TABLE = SGA_RS_CHAIN_TABLE != 0;
+// The prologue without a load under a lane condition ("Staged prologue"): the window's base slots are
+// loaded raw for every lane (base is [R][W]), the gathers of h and spin follow their block's site, the accept table is
+// filled, and the conversions of the base slots -- the first values that wait -- come last, so the compiler counts vmcnt
+// down instead of draining it once per block.  -DSGA_RS_CHAIN_STAGED=0: base[tw] loaded and converted per block under
+// the lane's condition, as it was.
+#ifndef SGA_RS_CHAIN_STAGED
+#define SGA_RS_CHAIN_STAGED 1
+#endif
+constexpr bool RS_CHAIN_STAGED = SGA_RS_CHAIN_STAGED != 0;
+// The current block's values read from register vectors with the wave-uniform block index (NB = 16: indexed register
+// moves; NB = 4, 8: the compiler's own select chain).  -DSGA_RS_CHAIN_INDEXED=0: arrays and one select over every block.
+#ifndef SGA_RS_CHAIN_INDEXED
+#define SGA_RS_CHAIN_INDEXED 1
+#endif
+constexpr bool RS_CHAIN_INDEXED = SGA_RS_CHAIN_INDEXED != 0;
+
+// NB values of a lane, one per block of the window: written with constant indices
+template <typename T, int NB>
+struct RsBlockRegs {
+#if SGA_RS_CHAIN_INDEXED
+    typedef T V __attribute__((ext_vector_type(NB)));
+    V v;
+#else
+    T v[NB];
+#endif
+};
 
 // The decision of the integer Metropolis form from the wave's table (sga_kernels.h: rs_accept_table_entries, with the
 // argument for "false beyond Q"): ptab[q] holds rs_accept's own expression for q = 1 ... Q, so u < ptab[q] is its
@@ -820,29 +846,48 @@ __global__ void __launch_bounds__(64) rs_chain_kernel(const SweepArgs a, const R
     if (a.reps_per_model > 0)
         hvec += (long long)__builtin_amdgcn_readfirstlane((int)((a.replica0 + (uint32_t)r) / (uint32_t)a.reps_per_model)) * n;
     const float unit = GRID ? ldexpf(1.0f, -rs_grid_k(pg)) : 1.0f;  // 2^-k
-    int site[NB], s[NB];
-    float f[NB], hh[NB], u[NB];
+    RsBlockRegs<int, NB> site, s;
+    RsBlockRegs<float, NB> f, hh, u;
+    // the window's base slots, raw (base is [R][W]: a slot past cnt is in the array, its value unused)
+    int braw[NB];
+    if constexpr (RS_CHAIN_STAGED) {
+#pragma unroll
+        for (int b = 0; b < NB; ++b) braw[b] = base[64 * b + lane];
+    }
+    // sites, uniforms and the gathers of h and spin; a lane past cnt keeps site 0 and u 0
 #pragma unroll
     for (int b = 0; b < NB; ++b) {
         const int tw = 64 * b + lane;
         const bool valid = tw < cnt;
         uint32_t ub = 0;
-        site[b] = 0;
-        if (valid) rs_update(a, r, k, t0 + tw, site[b], ub);
-        u[b] = (float)ub * 0x1.0p-24f;
-        f[b] = valid ? (float)base[tw] : 0.0f;
-        if constexpr (GRID) f[b] = ldexpf(f[b], -rs_grid_k(pg));  // 2^-k D, exact
-        hh[b] = hvec[site[b]];
-        s[b] = srow[site[b]];
+        int sb = 0;
+        if (valid) rs_update(a, r, k, t0 + tw, sb, ub);
+        site.v[b] = sb;
+        u.v[b] = (float)ub * 0x1.0p-24f;
+        if constexpr (!RS_CHAIN_STAGED) {
+            f.v[b] = valid ? (float)base[tw] : 0.0f;
+            if constexpr (GRID) f.v[b] = ldexpf(f.v[b], -rs_grid_k(pg));  // 2^-k D, exact
+        }
+        hh.v[b] = hvec[sb];
+        s.v[b] = srow[sb];
     }
-    // The accept table of this wave's T, filled behind the loads above (nothing has waited for them yet): rs_accept's
-    // expression for q = 1 ... Q, Q / 64 entries per lane (entry 0 is never read: fk <= 0 accepts).
+    // The accept table of this wave's T, filled behind the loads above: rs_accept's expression for
+    // q = 1 ... Q, Q / 64 entries per lane (entry 0 is never read: fk <= 0 accepts).
     int Q = 0;
     bool zero_tail = false;
     if constexpr (TABLE) {
         Q = __builtin_amdgcn_readfirstlane(rs_accept_table_entries(T, a.table_m));
         zero_tail = Q == __builtin_amdgcn_readfirstlane(rs_accept_table_zero_from(T));
         for (int q = lane; q <= Q; q += 64) ptab[q] = expf_det((float)(-(double)(2 * q) / T));
+    }
+    // the fields from the base slots -- the first values that wait
+    if constexpr (RS_CHAIN_STAGED) {
+#pragma unroll
+        for (int b = 0; b < NB; ++b) {
+            float fb = 64 * b + lane < cnt ? (float)braw[b] : 0.0f;
+            if constexpr (GRID) fb = ldexpf(fb, -rs_grid_k(pg));  // 2^-k D, exact
+            f.v[b] = fb;
+        }
     }
     double E = a.energy[r];
     int nA = 0;  // accepts of this window so far
@@ -854,9 +899,13 @@ __global__ void __launch_bounds__(64) rs_chain_kernel(const SweepArgs a, const R
     for (int cb = 0; cb < nblk; ++cb) {
         int csite = 0, cs = 0;
         float cf = 0.0f, chh = 0.0f, cu = 0.0f;
+        if constexpr (RS_CHAIN_INDEXED) {
+            csite = site.v[cb], cs = s.v[cb], cf = f.v[cb], chh = hh.v[cb], cu = u.v[cb];
+        } else {
 #pragma unroll
-        for (int b = 0; b < NB; ++b)
-            if (b == cb) csite = site[b], cs = s[b], cf = f[b], chh = hh[b], cu = u[b];
+            for (int b = 0; b < NB; ++b)
+                if (b == cb) csite = site.v[b], cs = s.v[b], cf = f.v[b], chh = hh.v[b], cu = u.v[b];
+        }
         const bool cvalid = 64 * cb + lane < cnt;
         unsigned int voff = (unsigned int)csite * (unsigned int)sizeof(JE), bit = 0;
         if constexpr (BITS) {
