@@ -201,6 +201,11 @@ def frustrated_lattice_by_simulated_quantum_annealing(L=8):
                                            initial_field_strength=3.0)
     sqa = quantum_annealer.simulated_quantum_anneal(model, n_trotter_slices=32, quantum_monte_carlo=True)
     pimc = quantum_annealer.path_integral_mc(model, imaginary_time_slices=64, quantum_temperature=0.1)
+    # towards Gamma = 0.01 the slices freeze into copies; world-line cluster updates (AnnealEngine.worldline_clusters) after
+    # every transverse sweep keep them moving
+    with_clusters = QuantumFluctuations(base_annealer=annealer, transverse_field_schedule="linear_decrease",
+                                        initial_field_strength=3.0, worldline_clusters=True)
+    sqa_clusters = with_clusters.simulated_quantum_anneal(model, n_trotter_slices=32)
     print(f"SQA, {L}^3 +-J lattice, 32 slices: best energy {sqa.best_energy:.1f} in {sqa.total_time:.3f} s; "
           f"PIMC at Gamma = 3, 64 slices: best energy {pimc.best_energy:.1f}")
 

@@ -80,7 +80,7 @@ typedef struct sga_engine sga_engine;
 int sga_create(int device, sga_engine **out);
 void sga_destroy(sga_engine *e);
 const char *sga_last_error(void);
-int sga_version(void);  /* 2900: sga_sweep_transverse (simulated quantum annealing: the Trotter slices of one instance coupled in the CSR sweep, two half-sweeps per sweep, csrc/sweep_transverse.hip; no option, no engine member); 2800: sga_get_class_overlaps / sga_accumulate_ladder_class_overlaps (the overlap between two replicas resolved by a class of sites, first and second moments per temperature summed on the device, csrc/class_overlaps.hip; read only, no engine state, no option); 2700: sga_get_link_count / sga_get_pair_overlaps / sga_accumulate_ladder_overlaps (spin and link overlaps between pairs of replicas, histogrammed per temperature on the device, csrc/pair_overlaps.hip; read only, no engine state, no option); 2600: sga_resample (the resampling step of population annealing, csrc/resample.hip); 2500: sga_cluster_move_pairs / sga_cluster_move_ladders (isoenergetic cluster moves between replica copies on sparse couplings, csrc/cluster_moves.hip; no engine state, no option); 2400: sga_set_replica_groups / sga_get_replica_groups; 2300: sga_get_magnetizations / sga_get_overlaps / sga_get_overlaps_with (replica observables on the device: the exact integer product of int8 spin rows on the matrix cores, csrc/observables.hip; read only, no engine state); 2200: the row-shared fields in tiles take a plan of their own, one launch per sweep (csrc/sweep_dense_rs.hip, rs_tile_plan_kernel; no change of interface or results); 2100: sga_set_sequential_windows / sga_get_sequential_windows (SGA_SITE_SEQUENTIAL sweeps in windows, the fields of every replica on the matrix cores; csrc/sweep_dense_seq.hip); 2000: the row-shared windows (option "row_shared") serve SGA_RULE_GLAUBER and SGA_RULE_HEAT_BATH too ("rule=glauber" / "rule=heat-bath" in sga_describe and sga_get_last_kernel; the window sga_autotune picks holds for the rule it was timed under); 1900: options "row_shared_fields" and "row_shared_tile_sites" (row-shared fields in tiles of sites, sign-only rows); 1800: option "row_shared_grid", sga_route_query.rs_grid; 1700: sga_set_csr_shared (one set of CSR rows, many field vectors: every one-wave-per-replica CSR form for such batches), sga_route_query.shared_j on SGA_ROUTE_CSR queries; 1600: sga_set_dense_shared (one coupling matrix, many field vectors; row-shared windows, bit-planes and the matrix-core pass for such batches), sga_route_query.shared_j; 1500: sga_get_scan_summary, and sga_set_dense / sga_set_dense_batch / sga_set_csr / sga_set_csr64 / sga_set_csr_batch refuse a NaN or +-Inf in J or h (SGA_ERR_INVALID, "non-finite"); 1400: option "batch_fixed_point" (fixed-point cached local fields for many-model dense batches); 1300: options "ragged_field_cache" and "clf_fixed_point" together (fixed-point cached local fields for ragged CSR batches); 1200: sga_set_groups_csr (group couplings plus a stored sparse remainder); 1100: option "ragged_field_cache" (cached local fields for ragged CSR batches); 1000: sga_set_groups */
+int sga_version(void);  /* 3000: sga_worldline_clusters (simulated quantum annealing: Swendsen-Wang clusters along imaginary time at one site, flipped under the classical field, one launch per call, csrc/worldline_clusters.hip; domain word 4; no option, no engine member); 2900: sga_sweep_transverse (simulated quantum annealing: the Trotter slices of one instance coupled in the CSR sweep, two half-sweeps per sweep, csrc/sweep_transverse.hip; no option, no engine member); 2800: sga_get_class_overlaps / sga_accumulate_ladder_class_overlaps (the overlap between two replicas resolved by a class of sites, first and second moments per temperature summed on the device, csrc/class_overlaps.hip; read only, no engine state, no option); 2700: sga_get_link_count / sga_get_pair_overlaps / sga_accumulate_ladder_overlaps (spin and link overlaps between pairs of replicas, histogrammed per temperature on the device, csrc/pair_overlaps.hip; read only, no engine state, no option); 2600: sga_resample (the resampling step of population annealing, csrc/resample.hip); 2500: sga_cluster_move_pairs / sga_cluster_move_ladders (isoenergetic cluster moves between replica copies on sparse couplings, csrc/cluster_moves.hip; no engine state, no option); 2400: sga_set_replica_groups / sga_get_replica_groups; 2300: sga_get_magnetizations / sga_get_overlaps / sga_get_overlaps_with (replica observables on the device: the exact integer product of int8 spin rows on the matrix cores, csrc/observables.hip; read only, no engine state); 2200: the row-shared fields in tiles take a plan of their own, one launch per sweep (csrc/sweep_dense_rs.hip, rs_tile_plan_kernel; no change of interface or results); 2100: sga_set_sequential_windows / sga_get_sequential_windows (SGA_SITE_SEQUENTIAL sweeps in windows, the fields of every replica on the matrix cores; csrc/sweep_dense_seq.hip); 2000: the row-shared windows (option "row_shared") serve SGA_RULE_GLAUBER and SGA_RULE_HEAT_BATH too ("rule=glauber" / "rule=heat-bath" in sga_describe and sga_get_last_kernel; the window sga_autotune picks holds for the rule it was timed under); 1900: options "row_shared_fields" and "row_shared_tile_sites" (row-shared fields in tiles of sites, sign-only rows); 1800: option "row_shared_grid", sga_route_query.rs_grid; 1700: sga_set_csr_shared (one set of CSR rows, many field vectors: every one-wave-per-replica CSR form for such batches), sga_route_query.shared_j on SGA_ROUTE_CSR queries; 1600: sga_set_dense_shared (one coupling matrix, many field vectors; row-shared windows, bit-planes and the matrix-core pass for such batches), sga_route_query.shared_j; 1500: sga_get_scan_summary, and sga_set_dense / sga_set_dense_batch / sga_set_csr / sga_set_csr64 / sga_set_csr_batch refuse a NaN or +-Inf in J or h (SGA_ERR_INVALID, "non-finite"); 1400: option "batch_fixed_point" (fixed-point cached local fields for many-model dense batches); 1300: options "ragged_field_cache" and "clf_fixed_point" together (fixed-point cached local fields for ragged CSR batches); 1200: sga_set_groups_csr (group couplings plus a stored sparse remainder); 1100: option "ragged_field_cache" (cached local fields for ragged CSR batches); 1000: sga_set_groups */
 /* Run on an existing HIP stream (e.g. torch.cuda.current_stream().cuda_stream); NULL = the
  * engine's own stream (default). */
 int sga_set_stream(sga_engine *e, void *hip_stream);
@@ -608,6 +608,58 @@ int sga_accumulate_ladder_class_overlaps(sga_engine *e, int slot_lo, int slot_hi
  *   The launches (two per sweep, built per arithmetic) show in sga_get_last_kernel; sga_enable_timing does not bracket them. */
 int sga_sweep_transverse(sga_engine *e, int n_sweeps, int n_slices, int arith /* SGA_ARITH_* */,
                          const float *k_perp /* host [n_sweeps][R_local / n_slices] */);
+
+/* ---- world-line cluster updates for simulated quantum annealing (version >= 3000; csrc/worldline_clusters.hip) --------
+ * Swendsen-Wang clusters along the imaginary-time direction at one site, flipped under the classical field (Rieger and
+ * Kawashima 1999; Heim et al. 2015): what keeps simulated quantum annealing ergodic at small Gamma, where k_perp freezes
+ * the slices of sga_sweep_transverse into identical copies.
+ *   Groups.  Those of sga_sweep_transverse: G = R_local / P contiguous groups of P = n_slices slices, replica0 % P == 0.
+ *   Slice p of group g is local replica g P + p with global id q_p = replica0 + g P + p.  T_g is the temperature of
+ *   local replica g P; equal temperatures within a group are the caller's responsibility, as there.  2 <= P <= 64; P
+ *   need not be even.
+ *   Threshold.  thr = (uint32_t)floor(p_bond[kk][g] * 16777216.0), formed on the host in double; p = 1 gives 2^24: every
+ *   bond between equal spins is active.
+ *   Order.  For sweep kk = 0 ... n_sweeps-1 the sites go in typewriter order i = 0 ... n-1; at each site all of the
+ *   following is decided from the spins as they stand when the site is reached.
+ *     1. Draws.  Each slice p takes ONE Philox block at counter (i, (uint32_t)(round + kk), q_p, 4), the engine's 64-bit
+ *        seed as key.  Domain word 4 is DOMAIN_WORLDLINE = sweep | 1 << 2 (in use besides: 0, 1, 2, 5, 6; every Wolff
+ *        word ends in bits 11).  Word 0 decides the bond from slice p to slice (p+1) mod P:
+ *          b_p = (s_p[i] == s_{p+1}[i]) && ((w0 >> 8) < thr).
+ *        Word 1 gives u_p = (w1 >> 8) 2^-24 as fp32.  For P = 2 the two bonds join the same pair and both are drawn:
+ *        the doubled coupling the transverse sweep uses there.
+ *     2. Segments.  Slice p is a head iff b_{(p-1) mod P} is false.  With no head the whole ring is one segment with
+ *        head 0; otherwise each head f owns f, f+1, ... cyclically up to the slice before the next head.
+ *     3. Decision per segment with head f, size m and common spin sigma = s_f[i]:
+ *          A   = sum over the segment of dot_p, dot_p = sum_j J_ij s_p[j]: an exact integer, |A| < 2^30 by the admitted
+ *                class, accumulated in int32;
+ *          Phi = (double)A + (double)m * (double)h_i (the product is exact, the sum rounds once);
+ *          dE  = 2 sigma Phi;
+ *          flip iff dE <= 0 or (double)u_f < (double)expf((float)(-dE / T_g)): the fp64 Metropolis rule of the oracle
+ *          (metropolis_core, SGO_ARITH_F64); T = 0 and T = inf behave as that expression does.  There is no `arith`
+ *          argument: only this rule is built, whatever sga_set_update_rule says.
+ *     4. On a flip every slice of the segment takes -sigma at site i, and its tracked energy moves by
+ *        2 sigma ((double)dot_p + (double)h_i) -- what sga_flip reports: the tracked energies stay classical and equal
+ *        sga_recompute_energies.
+ *   After the n sites of a sweep every slice's best follows where its energy is lower (the step a sweep's end runs).
+ *   What does not move: sweeps_done, the exchange round counters, accept counters, temperatures, the slot map, exchange
+ *   statistics and Wolff cursors.  `round` is the caller's, as with sga_cluster_move_pairs.  The cached local fields are
+ *   marked for re-seeding, as after sga_set_spins.
+ *   By construction a call of 2 sweeps at `round` equals a call of 1 at `round` followed by a call of 1 at `round + 1`;
+ *   n_sweeps == 0 is a no-op.
+ *   With p_bond = 1 - exp(-2 k_perp / T_g) one site update satisfies detailed balance against exp(-H_eff / T_g), H_eff
+ *   the effective energy of the transverse sweep at k_perp.
+ *   p_bond is a HOST array (it has left the caller's buffer on return); stats, where given, is a HOST array the call adds
+ *   to and waits for: per group the segments formed, the segments flipped and the slice spins flipped.
+ *   SGA_ERR_INVALID, first and with the engine unchanged: a NULL engine or p_bond, a device p_bond or stats; no problem or
+ *   no replicas; n_sweeps < 0; P < 2, P > 64, P not a divisor of R_local, replica0 % P != 0; a p_bond that is NaN or
+ *   outside [0, 1].
+ *   SGA_ERR_UNSUPPORTED, with the reason in sga_last_error: everything sga_sweep_transverse refuses, for the same reasons,
+ *   except the update rule, which this call ignores; and a group's spin words beyond LDS (one word of 4 bytes per site
+ *   for P <= 32, of 8 bytes beyond: n <= ~40 000 and ~20 000).
+ *   The launch (one per call) shows in sga_get_last_kernel; sga_enable_timing does not bracket it. */
+int sga_worldline_clusters(sga_engine *e, int n_sweeps, int n_slices, uint32_t round,
+                           const double *p_bond /* host [n_sweeps][R_local / n_slices], each in [0, 1] */,
+                           int64_t *stats       /* host [R_local / n_slices][3] or NULL: += segments formed, segments flipped, slice spins flipped */);
 
 /* Stateless operator form of CUDAKernelManager.parallel_tempering_exchange_optimized
  * (annealing/cuda_kernels.py:326-369, fallback :415-443): sequential adjacent pairs, fp32,

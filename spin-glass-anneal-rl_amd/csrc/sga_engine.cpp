@@ -347,6 +347,10 @@ extern "C" {
 
 const char *sga_last_error(void) { return g_last_error.c_str(); }
 // The ABI version, one line per step:
+//   3000:    + sga_worldline_clusters: Swendsen-Wang clusters along imaginary time at one site, flipped under the classical
+//            field -- what keeps simulated quantum annealing ergodic at small Gamma; one launch per call, one wave per
+//            group of slices, a coupling row read once for all slices of a site (worldline_clusters.hip; the admission
+//            rule in sga_kernels.h); domain word 4; no option, no engine member
 //   2900:    + sga_sweep_transverse: simulated quantum annealing, the Trotter slices of one instance coupled in the CSR
 //            sweep -- two half-sweeps per sweep, the moving slices under h + k (s_up + s_dn) (sweep_transverse.hip; the
 //            admission rule in sga_kernels.h); no option, no engine member
@@ -393,7 +397,7 @@ const char *sga_last_error(void) { return g_last_error.c_str(); }
 //   600:     + sga_set_csr_batch / sga_get_batch_model (ragged CSR batches)
 //   round 5: + sga_explain_route / sga_get_route_query, sga_get_last_kernel, sga_get_autotune_table, ladder-local
 //            sga_exchange
-int sga_version(void) { return 2900; }
+int sga_version(void) { return 3000; }
 
 int sga_create(int device, sga_engine **out) {
     if (!out) return fail(SGA_ERR_INVALID, "out is NULL");
@@ -1287,6 +1291,74 @@ int sga_sweep_transverse(sga_engine *e, int n_sweeps, int n_slices, int arith, c
     std::snprintf(e->last_kernel, sizeof(e->last_kernel), "%s", sga::last_sweep_kernel());
     e->sweeps_done += (uint32_t)n_sweeps;
     e->attempted += (long long)n_sweeps * e->n;
+    return SGA_OK;
+}
+
+// ---- world-line cluster updates along imaginary time (worldline_clusters.hip) --------------------------------------
+// No state of its own: the thresholds floor(p_bond 2^24), formed here in double, are staged in scratch slot 0 with the
+// group counts behind them; one launch serves the whole call.
+int sga_worldline_clusters(sga_engine *e, int n_sweeps, int n_slices, uint32_t round, const double *p_bond, int64_t *stats) {
+    sga::TransverseProblem tp;
+    if (e) {
+        tp.n = e->n, tp.R_local = e->spins ? e->R : 0, tp.replica0 = e->replica0, tp.sstride = e->sstride;
+        tp.csr = e->csr, tp.tsp = e->tsp, tp.groups = e->groups, tp.ragged = e->ragged, tp.n_models = e->n_models;
+        tp.csr_acc = e->csr_acc;
+        tp.consistent_dE = e->consistent_dE;
+    }
+    if (p_bond && is_device_ptr(p_bond)) return fail(SGA_ERR_INVALID, "p_bond must be a host buffer");
+    if (stats && is_device_ptr(stats)) return fail(SGA_ERR_INVALID, "stats must be a host buffer");
+    bool invalid = true;
+    if (const char *why = sga::worldline_check(e != nullptr, tp, n_sweeps, n_slices, p_bond, &invalid))
+        return fail(invalid ? SGA_ERR_INVALID : SGA_ERR_UNSUPPORTED, why);
+    if (n_sweeps == 0) return SGA_OK;
+    if (e->opt_stale)
+        return fail(SGA_ERR_INVALID, std::string("option \"") + (e->opt_stale_key ? e->opt_stale_key : "?") +
+                                         "\" changed after it was read: set the couplings and initialise the replicas again");
+    if (!e->rowptr64 || !e->cv || !e->h || !e->best_spins) return fail(SGA_ERR_INVALID, "no couplings set");
+    HIPCHK(hipSetDevice(e->device));
+    hipStream_t st = e->stream;
+    const int G = e->R / n_slices;
+    const size_t count = (size_t)n_sweeps * (size_t)G;
+    std::vector<uint32_t> thr(count);
+    for (size_t i = 0; i < count; ++i) thr[i] = sga::worldline_threshold(p_bond[i]);
+    const size_t thr_bytes = (count * sizeof(uint32_t) + 7) / 8 * 8, stats_bytes = (size_t)G * 3 * sizeof(long long);
+    HIPCHK(e->scratch[0].reserve(thr_bytes + stats_bytes));
+    unsigned char *base = static_cast<unsigned char *>(e->scratch[0].ptr);
+    // (a pageable host array: the copy has left the buffer when the call returns)
+    HIPCHK(hipMemcpyAsync(base, thr.data(), count * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    sga::SweepArgs a{};
+    a.rowptr64 = e->rowptr64;
+    a.cv = e->cv;
+    a.h = e->h;
+    a.spins = e->spins;
+    a.energy = e->energy;
+    a.best_energy = e->best_energy;
+    a.best_spins = e->best_spins;
+    a.rep_temp = e->rep_temp;
+    a.n = e->n;
+    a.sstride = e->sstride;
+    a.R = e->R;
+    a.csr_acc = e->csr_acc;
+    a.seed_lo = (uint32_t)e->seed;
+    a.seed_hi = (uint32_t)(e->seed >> 32);
+    a.replica0 = (uint32_t)e->replica0;
+    sga::WorldlineArgs w{};
+    w.thr = reinterpret_cast<const uint32_t *>(base);
+    w.stats = stats ? reinterpret_cast<long long *>(base + thr_bytes) : nullptr;
+    w.n_slices = n_slices;
+    w.n_sweeps = n_sweeps;
+    w.round = round;
+    e->fields_valid = false;  // (as after sga_set_spins: the next sweep seeds the cached fields again)
+    const hipError_t le = sga::launch_worldline_clusters(a, w, st);
+    if (le != hipSuccess) (void)hipStreamSynchronize(st);
+    HIPCHK(le);
+    std::snprintf(e->last_kernel, sizeof(e->last_kernel), "%s", sga::last_sweep_kernel());
+    if (stats) {
+        std::vector<long long> got((size_t)G * 3);
+        HIPCHK(hipMemcpyAsync(got.data(), w.stats, stats_bytes, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        for (size_t i = 0; i < got.size(); ++i) stats[i] += (int64_t)got[i];
+    }
     return SGA_OK;
 }
 

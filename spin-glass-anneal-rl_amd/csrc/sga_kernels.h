@@ -1037,6 +1037,64 @@ struct TransverseArgs {
 // a: the arguments of one production sweep (n_sweeps = 1, sweep0 = the sweep's counter); reads a.rowptr64 / a.cv
 hipError_t launch_sweep_transverse(const SweepArgs &a, const TransverseArgs &t, hipStream_t st);
 
+// World-line cluster updates along imaginary time (worldline_clusters.hip; sga_worldline_clusters).  The groups are those
+// of the transverse sweep.  One wave per group, lane p = slice p; the group's spins as one word per site in LDS, bit p =
+// [s_p[i] < 0]: uint32_t for P <= 32, uint64_t beyond.  The budget is the transverse sweep's; behind the words lie 64
+// int32 accumulators of the segment sums.
+constexpr int WORLDLINE_MAX_SLICES = 64;
+constexpr size_t WORLDLINE_ACC_BYTES = 64 * sizeof(int32_t);
+inline int worldline_word_bytes(int n_slices) { return n_slices <= 32 ? 4 : 8; }
+// the words of a group: n rounded up to the 4 sites of a dword of int8 spins (the transposes move 4 sites a step)
+inline size_t worldline_lds_bytes(int n, int n_slices) {
+    return (((size_t)(n > 0 ? n : 0) + 3) / 4) * 4 * (size_t)worldline_word_bytes(n_slices) + WORLDLINE_ACC_BYTES;
+}
+inline int worldline_max_sites(int n_slices) {  // the largest n a group of n_slices slices is served at
+    return (int)((TRANSVERSE_LDS_BUDGET - WORLDLINE_ACC_BYTES) / (size_t)worldline_word_bytes(n_slices) / 4 * 4);
+}
+// The admission rule of sga_worldline_clusters, a pure function as transverse_check is: nullptr where the call is
+// served, else why not, *invalid = true for SGA_ERR_INVALID and false for SGA_ERR_UNSUPPORTED.  Argument errors come
+// first; p_bond: the caller's HOST array [n_sweeps][R_local / n_slices].  The engine's rule is not looked at: the call
+// brings its own.
+inline const char *worldline_check(bool have_engine, const TransverseProblem &p, int n_sweeps, int n_slices, const double *p_bond,
+                                   bool *invalid) {
+    *invalid = true;
+    if (!have_engine) return "engine is NULL";
+    if (!p_bond) return "p_bond is NULL";
+    if (p.n <= 0) return "no couplings set";
+    if (p.R_local <= 0) return "no replicas (call sga_init_replicas)";
+    if (n_sweeps < 0) return "n_sweeps < 0";
+    if (n_slices < 2) return "n_slices must be at least 2";
+    if (n_slices > WORLDLINE_MAX_SLICES) return "n_slices must be at most 64 (one lane of a wave per slice)";
+    if (p.R_local % n_slices != 0) return "n_slices must divide the number of local replicas";
+    if (p.replica0 % n_slices != 0) return "replica0 must be a multiple of n_slices (groups lie whole on a rank)";
+    const long long count = (long long)n_sweeps * (p.R_local / n_slices);
+    for (long long i = 0; i < count; ++i)
+        if (!(p_bond[i] >= 0.0 && p_bond[i] <= 1.0)) return "p_bond holds a NaN or a value outside [0, 1]";
+    *invalid = false;
+    if (p.tsp) return "world-line clusters are not implemented for sga_set_tsp problems";
+    if (p.groups) return "world-line clusters are not implemented for sga_set_groups / sga_set_groups_csr problems";
+    if (p.ragged) return "world-line clusters are not implemented for ragged CSR batches";
+    if (p.n_models > 1) return "world-line clusters are not implemented for many-model batches (shared or stacked)";
+    if (!p.csr) return "world-line clusters need sparse (CSR) couplings: dense couplings are not served";
+    if (p.csr_acc != CSR_ACC_F32_TABLE && p.csr_acc != CSR_ACC_F32)
+        return "world-line clusters need integer couplings with exact fp32 row sums (real-valued J needs the canonical order)";
+    if (!p.consistent_dE) return "world-line clusters need symmetric couplings with a zero diagonal";
+    if (transverse_waves_per_block(p.sstride) < 1) return "world-line clusters: a slice's int8 spins do not fit LDS";
+    if (p.n > worldline_max_sites(n_slices)) return "world-line clusters: a group's spin words do not fit LDS";
+    return nullptr;
+}
+// the threshold a bond's 24 random bits are held against: floor(p 2^24) in double, p = 1 -> 2^24 (every bond active)
+inline uint32_t worldline_threshold(double p_bond) { return (uint32_t)(long long)(p_bond * 16777216.0); }
+struct WorldlineArgs {
+    const uint32_t *thr;  // device [n_sweeps][G]
+    long long *stats;     // device [G][3], zeroed: segments formed, segments flipped, slice spins flipped (or null)
+    int n_slices;         // P
+    int n_sweeps;
+    uint32_t round;       // sweep kk draws at round + kk
+};
+// a: the engine's CSR view, replica state and seed (a.n_sweeps, a.sweep0 unused); one launch serves the whole call
+hipError_t launch_worldline_clusters(const SweepArgs &a, const WorldlineArgs &w, hipStream_t st);
+
 // operator-form PT exchange (cuda_kernels.py:415-443): decide sequentially, then permute rows
 hipError_t launch_op_exchange(float *spins, float *tmp_rows, float *energies, const float *temps,
                               const float *u, int32_t *src_of_pos, int *n_accepted,

@@ -160,6 +160,14 @@ __device__ __forceinline__ uint64_t resample_draw(uint32_t round, uint32_t gpop,
     return ((uint64_t)w.x << 32) | (uint64_t)w.y;
 }
 
+// The draws of a world-line cluster sweep (worldline_clusters.hip) of the slice with global id q at site i in round
+// `round`: block i at (round, q, DOMAIN_WORLDLINE) -- domain word 4 = sweep | 1 << 2 (in use besides: 0, 1, 2, 5, 6; every
+// Wolff word ends in bits 11).  Word 0: the bond towards the next slice; word 1: the uniform of a segment this slice heads.
+constexpr uint32_t DOMAIN_WORLDLINE = DOMAIN_SWEEP | (1u << 2);
+__device__ __forceinline__ u32x4 worldline_block(uint32_t site, uint32_t round, uint32_t q, uint32_t seed_lo, uint32_t seed_hi) {
+    return philox4x32_10(site, round, q, DOMAIN_WORLDLINE, seed_lo, seed_hi);
+}
+
 // The accept rule.  dot = fp32 coupling dot product J[site,:].s (already rounded to fp32),
 // si = s[site] (+-1).  Returns true if the spin flips; dE receives the energy change of the
 // flip.

@@ -84,6 +84,20 @@ def transverse_k_perp(k_perp, n_sweeps: int, n_groups: int) -> np.ndarray:
     return np.ascontiguousarray(k, dtype=np.float32)
 
 
+def worldline_p_bond(p_bond, n_sweeps: int, n_groups: int) -> np.ndarray:
+    """p_bond as sga_worldline_clusters takes it, float64 [n_sweeps, n_groups], from a scalar, [n_sweeps] (one value per
+    sweep, shared by the groups) or [n_sweeps, n_groups].  Shapes only: the values are the engine's to judge."""
+    n_sweeps, G = max(int(n_sweeps), 0), int(n_groups)
+    b = np.asarray(p_bond, dtype=np.float64)
+    if b.ndim == 0:
+        b = np.full((n_sweeps, G), b, np.float64)
+    elif b.shape == (n_sweeps,):
+        b = np.repeat(b[:, None], G, axis=1)
+    elif b.shape != (n_sweeps, G):
+        raise AnnealingError("p_bond must be a scalar, [n_sweeps] or [n_sweeps, R / n_slices]")
+    return np.ascontiguousarray(b, dtype=np.float64)
+
+
 def concat_csr_batch(problems):
     """[(rowptr, colidx, val, h), ...] (numpy or torch, model-local columns) -> the one concatenated CSR of
     sga_set_csr_batch: (n_spins int32 [M], rowptr int64 [sum n + 1], colidx int32, val float32, h float32).
@@ -574,6 +588,24 @@ class AnnealEngine:
         k = transverse_k_perp(k_perp, n_sweeps, G)
         N.check(self._lib.sga_sweep_transverse(self._h, int(n_sweeps), int(n_slices), int(arith), k.ctypes.data_as(C.c_void_p)),
                 "sga_sweep_transverse")
+
+    def worldline_clusters(self, n_sweeps: int, n_slices: int, p_bond, round: Optional[int] = None, stats: bool = False):
+        """n_sweeps sweeps of world-line cluster updates over the replicas as R / n_slices groups of n_slices Trotter
+        slices (sga_worldline_clusters): per site the slices are cut into segments by bonds drawn with p_bond between equal
+        neighbouring slices (see quantum.bond_probability), and each segment flips as one under the classical field; the
+        tracked energies stay classical.  p_bond: a scalar, [n_sweeps] or [n_sweeps, R / n_slices].  round: the draws'
+        coordinate, None = the engine's sweeps_done (counters()[0]); sweep kk draws at round + kk.  stats=True returns
+        int64 [R / n_slices, 3]: segments formed, segments flipped, slice spins flipped.  A problem the step does not
+        serve raises AnnealingError with the engine's reason."""
+        P = int(n_slices)
+        # (a P the engine will refuse: any well-formed array, so that the refusal and its reason are the engine's)
+        G = self.R // P if P >= 1 and self.R > 0 and self.R % P == 0 else 1
+        b = worldline_p_bond(p_bond, n_sweeps, G)
+        rnd = self.counters()[0] if round is None else int(round)
+        out = np.zeros((G, 3), np.int64) if stats else None
+        N.check(self._lib.sga_worldline_clusters(self._h, int(n_sweeps), P, rnd & 0xFFFFFFFF, b.ctypes.data_as(C.c_void_p),
+                                                 out.ctypes.data_as(C.c_void_p) if stats else None), "sga_worldline_clusters")
+        return out
 
     # single-site operators (the reference's per-spin API)
     def local_fields(self, r: int, sites) -> np.ndarray:

@@ -8,6 +8,13 @@ h + k_perp (s_up + s_dn), then the odd ones, with no host round trip; the tracke
 energies, so the best over all slices is a solution of the classical problem.  overlaps() between slices works as for
 any replicas.
 
+At small Gamma k_perp grows without bound and a single-slice flip against two equal neighbours is never accepted: the
+slices freeze into identical copies.  AnnealEngine.worldline_clusters (sga_worldline_clusters) is the move that keeps
+the method ergodic there: at each site the ring of slices is cut into segments by bonds drawn with probability
+bond_probability(k_perp, P T) between equal neighbouring slices, and each segment flips as one under the classical
+field (Rieger and Kawashima 1999; Heim et al. 2015).  SimulatedQuantumAnnealingConfig(worldline_clusters=True) follows
+every cluster_interval-th transverse sweep with one such sweep.
+
 The step serves one-model sparse (CSR) problems with integer couplings under the Metropolis rule; any other problem
 raises AnnealingError with the engine's reason -- there is no classical fallback.
 """
@@ -42,6 +49,20 @@ def transverse_coupling(gamma, temperature: float, n_slices: int):
         k = -0.5 * pt * np.log(np.tanh(g / pt))
     k = np.where(k == 0.0, 0.0, k)  # (tanh rounds to 1 for a large Gamma: +0, not -0)
     return float(k) if k.ndim == 0 else k
+
+
+def bond_probability(k_perp, slice_temperature: float):
+    """p_bond = 1 - exp(-2 k_perp / T) = -expm1(-2 k / T) in float64: the probability of a bond between two equal spins
+    of neighbouring slices that run at temperature T (= P times the quantum temperature) under the coupling k_perp.  With
+    it one site update of AnnealEngine.worldline_clusters satisfies detailed balance against exp(-H_eff / T).  k_perp:
+    a scalar or an array; a negative one has no such clusters (an antiferromagnetic time coupling)."""
+    if not np.isfinite(slice_temperature) or slice_temperature <= 0:
+        raise ConfigurationError("slice_temperature must be positive and finite")
+    k = np.asarray(k_perp, np.float64)
+    if np.any(np.isnan(k)) or np.any(k < 0):
+        raise ConfigurationError("k_perp must not be negative: an antiferromagnetic time coupling has no such clusters")
+    b = -np.expm1(-2.0 * k / float(slice_temperature))
+    return float(b) if b.ndim == 0 else b
 
 
 @dataclass
@@ -85,12 +106,14 @@ class SimulatedQuantumAnnealingConfig:
     seed: Optional[int] = None
     measure_interval: int = 1             # sweeps per engine call; the histories hold one record per call
     device_index: Optional[int] = None
+    worldline_clusters: bool = False      # follow transverse sweeps with world-line cluster sweeps (sga_worldline_clusters)
+    cluster_interval: int = 1             # ... every cluster_interval-th of them
 
     def __post_init__(self):
         self.check()
 
     def check(self):
-        for name in ("n_slices", "n_instances", "n_sweeps", "measure_interval"):
+        for name in ("n_slices", "n_instances", "n_sweeps", "measure_interval", "cluster_interval"):
             v = getattr(self, name)
             if isinstance(v, bool) or int(v) != v or v < 1:
                 raise ConfigurationError(f"{name} must be a positive integer")
@@ -100,6 +123,10 @@ class SimulatedQuantumAnnealingConfig:
             raise ConfigurationError("temperature must be positive and finite")
         if not isinstance(self.transverse_field, TransverseField):
             raise ConfigurationError("transverse_field must be a TransverseField")
+        if not isinstance(self.worldline_clusters, (bool, np.bool_)):
+            raise ConfigurationError("worldline_clusters must be True or False")
+        if self.worldline_clusters and self.n_slices > 64:
+            raise ConfigurationError("world-line clusters serve at most 64 slices (one lane of a wave per slice)")
 
     def couplings(self) -> np.ndarray:
         """float32 [n_sweeps]: k_perp per sweep."""
@@ -116,12 +143,37 @@ class SimulatedQuantumAnnealing:
         self.config = config
         self.final_energies = None   # float64 [n_instances, n_slices]: the slices' classical energies at the end
         self.slice_overlaps = None   # int32 [R, R] of run(measure_overlaps=True): s_a . s_b between the final slices
+        self.cluster_statistics = None  # int64 [3] of a run with world-line clusters: segments formed, segments flipped,
+        #                                 slice spins flipped, summed over the run
         self.device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
         self.use_cuda = self.device.type == "cuda"
 
-    def run(self, model: IsingModel, measure_overlaps: bool = False) -> AnnealingResult:
+    def _sweeps(self, eng, k0: int, ns: int, k, clusters: bool):
+        """Transverse sweeps k0 ... k0 + ns - 1; with clusters, every cluster_interval-th one (counted over the run) is
+        followed by one cluster sweep at its k_perp, drawn at round = the sweep's index."""
+        cfg = self.config
+        P = int(cfg.n_slices)
+        if not clusters:
+            eng.sweep_transverse(ns, P, k[k0:k0 + ns])
+            return
+        every, slice_T = int(cfg.cluster_interval), P * float(cfg.temperature)
+        t = k0
+        while t < k0 + ns:
+            stop = min(((t // every) + 1) * every, k0 + ns)  # the sweeps up to and with the next one that is followed
+            eng.sweep_transverse(stop - t, P, k[t:stop])
+            if stop % every == 0:
+                self.cluster_statistics += eng.worldline_clusters(1, P, bond_probability(float(k[stop - 1]), slice_T),
+                                                                  round=stop - 1, stats=True).sum(axis=0)
+            t = stop
+
+    def run(self, model: IsingModel, measure_overlaps: bool = False, worldline_clusters: Optional[bool] = None) -> AnnealingResult:
+        """worldline_clusters: None = the configuration's; False is the transverse sweeps alone."""
         cfg = self.config
         cfg.check()
+        clusters = bool(cfg.worldline_clusters if worldline_clusters is None else worldline_clusters)
+        if clusters and cfg.n_slices > 64:
+            raise ConfigurationError("world-line clusters serve at most 64 slices (one lane of a wave per slice)")
+        self.cluster_statistics = np.zeros(3, np.int64) if clusters else None
         P, G, n = int(cfg.n_slices), int(cfg.n_instances), model.n_spins
         R = P * G
         k = cfg.couplings()
@@ -137,7 +189,7 @@ class SimulatedQuantumAnnealing:
             acc_prev = np.zeros(R, np.int64)
             for k0 in range(0, int(cfg.n_sweeps), step):
                 ns = min(step, int(cfg.n_sweeps) - k0)
-                eng.sweep_transverse(ns, P, k[k0:k0 + ns])
+                self._sweeps(eng, k0, ns, k, clusters)
                 en, acc, _ = eng.snapshot(slots=False)
                 energy_history.append(float(en.min()))       # the lowest classical energy over the slices now
                 temp_history.append(float(gam[k0 + ns - 1]))  # (the transverse field: T is constant)
@@ -164,9 +216,10 @@ class QuantumFluctuations:
     number of sweeps, the temperature (its final one) and the seed; the schedule gives Gamma."""
 
     def __init__(self, base_annealer=None, transverse_field_schedule: str = "linear_decrease", initial_field_strength: float = 5.0,
-                 final_field_strength: float = 0.01, n_instances: int = 1):
+                 final_field_strength: float = 0.01, n_instances: int = 1, worldline_clusters: bool = False):
         self.base_annealer = base_annealer
         self.n_instances = int(n_instances)
+        self.worldline_clusters = bool(worldline_clusters)
         self.field = TransverseField(transverse_field_schedule, float(initial_field_strength),
                                      min(float(final_field_strength), float(initial_field_strength)))
         self.last = None  # the SimulatedQuantumAnnealing of the last call (final_energies, slice_overlaps)
@@ -180,7 +233,7 @@ class QuantumFluctuations:
         cfg = SimulatedQuantumAnnealingConfig(
             n_slices=int(P), n_instances=self.n_instances, temperature=float(T), n_sweeps=int(self._base("n_sweeps", 1000)),
             transverse_field=tf, seed=self._base("random_seed", None), measure_interval=int(self._base("record_interval", 10)),
-            device_index=self._base("device_index", None))
+            device_index=self._base("device_index", None), worldline_clusters=self.worldline_clusters)
         self.last = SimulatedQuantumAnnealing(cfg)
         return self.last.run(model)
 
