@@ -495,6 +495,26 @@ struct RsTileChunk {
     int *base;
     int cn, nw2, rw2, log_w, W, nwaves;
 };
+// The entry loop's addresses as unsigned 32-bit byte offsets beside wave-uniform base pointers (the chain's voff): a
+// replica's spin bits at r * 16 nw2 of bits, the entry's slot at 4 e of base (W = 2^log_w, so r W + t is the entry word
+// itself), the site's row at ls * 16 rw2 of the LDS image -- 24-bit multiplies; and the next pass's entry read one pass
+// ahead.  -DSGA_RS_TILES_LEAN=0: 64-bit pointers formed per entry, the entry read where it is used, as it was.  The bounds (launch_sweep_dense_rs refuses anything beyond them): r < 4096 =
+// RS_TILE_MAX_REPLICAS, 16 nw2 < 2^18 (two rows fit LDS) -- bits spans R * 16 nw2 < 2^30 bytes; base spans 4 R W <= 2^24
+// bytes (W <= 1024); ls < 2^12 and 16 rw2 < 2^18, their product inside LDS.
+#ifndef SGA_RS_TILES_LEAN
+#define SGA_RS_TILES_LEAN 1
+#endif
+constexpr bool RS_TILES_LEAN = SGA_RS_TILES_LEAN != 0;
+// The tile kernel's prologue with every independent load issued before the first wait ("Tile prologue"):
+// the run bounds read once and kept across the barrier, the row constants and plane rows loaded at kernel entry and
+// stored to LDS behind the prefix, the entries copied flat -- four dependent trips to memory before the first popcount
+// (bounds with rows; entries; own spin bits; the first replica's bits), whatever S and the number of runs.
+// -DSGA_RS_TILES_PROLOGUE=0: a wave per row and per run, each load behind its own wait, as it was.
+#ifndef SGA_RS_TILES_PROLOGUE
+#define SGA_RS_TILES_PROLOGUE 1
+#endif
+constexpr bool RS_TILES_PROLOGUE = SGA_RS_TILES_PROLOGUE != 0;
+
 template <int PL, bool ONES, int NK>
 __device__ __forceinline__ void rs_tile_pieces(const RsTileChunk &ch, int wv, int sub, int l16) {
     const int L = (ch.cn + 4 * ch.nwaves - 1) / (4 * ch.nwaves), x1 = (4 * wv + sub) * L, wmask = (1 << ch.log_w) - 1;
@@ -506,6 +526,51 @@ __device__ __forceinline__ void rs_tile_pieces(const RsTileChunk &ch, int wv, in
 #pragma unroll
     for (int k = 0; k < NR; ++k) sv[k] = make_ulonglong2(0ull, 0ull);
     int rcur = -1;
+    if constexpr (RS_TILES_LEAN) {
+        const char *bitsb = reinterpret_cast<const char *>(ch.bits), *prowb = reinterpret_cast<const char *>(ch.prow);
+        char *baseb = reinterpret_cast<char *>(ch.base);
+        const unsigned int rowb = 16u * (unsigned int)ch.nw2, lrowb = 16u * (unsigned int)ch.rw2;
+        const unsigned int o16 = 16u * (unsigned int)l16, ocl = 16u * (unsigned int)cl;
+        // (the entry of the next pass is read from LDS under this one's work: one LDS round trip less on every pass's path)
+        bool live_n = x1 < ch.cn;
+        unsigned int e_n = (unsigned int)ch.sent[live_n ? x1 : 0], lsd_n = ch.sls[live_n ? x1 : 0];
+        for (int t = 0; t < L; ++t) {  // wave-uniform bounds: the DPP steps run with every lane on
+            const bool live = live_n;
+            const unsigned int e = e_n, lsd = lsd_n, ls = lsd & 0x7fffu;
+            const int xn = x1 + t + 1;
+            live_n = xn < ch.cn;
+            e_n = (unsigned int)ch.sent[live_n ? xn : 0], lsd_n = ch.sls[live_n ? xn : 0];
+            const int r = (int)(e >> ch.log_w);
+            const unsigned int bo = __umul24((unsigned int)r, rowb);  // < 2^30: R <= 4096, 16 nw2 < 2^18
+            const ulonglong2 *row = reinterpret_cast<const ulonglong2 *>(prowb + __umul24(ls, lrowb));
+            int acc = 0;
+            if constexpr (NK > 0) {
+                if (live && r != rcur) {  // a new run
+                    rcur = r;
+                    const char *s = bitsb + (size_t)(bo + o16);
+#pragma unroll
+                    for (int k = 0; k < NK - 1; ++k) sv[k] = *reinterpret_cast<const ulonglong2 *>(s + 256 * k);
+                    sv[NK - 1] = *reinterpret_cast<const ulonglong2 *>(bitsb + (size_t)(bo + ocl));
+                }
+#pragma unroll
+                for (int k = 0; k < NK - 1; ++k) acc += rs_tile_word<PL, ONES>(sv[k], row, ch.nw2, l16 + 16 * k);
+                const int last = rs_tile_word<PL, ONES>(sv[NK - 1], row, ch.nw2, cl);
+                acc += vlast ? last : 0;
+            } else {
+                for (int c = l16; c < ch.nw2; c += 16)
+                    acc += rs_tile_word<PL, ONES>(*reinterpret_cast<const ulonglong2 *>(bitsb + (size_t)(bo + 16u * (unsigned int)c)), row,
+                                                  ch.nw2, c);
+            }
+            acc += dpp_move<DPP_QUAD_XOR1>(acc);
+            acc += dpp_move<DPP_QUAD_XOR2>(acc);
+            acc += dpp_move<DPP_ROW_HALF_MIRROR>(acc);
+            acc += dpp_move<DPP_ROW_MIRROR>(acc);
+            // ONES, the diagonal: its sign bit is 0, so the xor held the replica's own spin bit at site i (lsd >> 15)
+            if (live && l16 == 0)  // 4 e < 2^24: e < R W <= 4096 * 1024
+                *reinterpret_cast<int *>(baseb + (size_t)(e << 2)) = ch.sjabs[ls] - 2 * (acc - (int)(lsd >> 15));
+        }
+        return;
+    }
     for (int t = 0; t < L; ++t) {  // wave-uniform bounds: the DPP steps run with every lane on
         const int x = x1 + t;
         const bool live = x < ch.cn;
@@ -555,11 +620,57 @@ __global__ void __launch_bounds__(RS_TILE_THREADS) rs_fields_tiles_kernel(const 
     const unsigned short *run0 = reinterpret_cast<const unsigned short *>(p.cnt) + ((long long)win * gridDim.x + blockIdx.x) * nsl;
     const unsigned short *run1 = run0 + nsl;  // (the last tile's runs end where their slices end)
     int total;
+    // PROLOGUE: what the loads below fill, kept in registers until the prefix is known (the stores follow the barrier)
+    constexpr int NJB = RS_TILE_MAX_SITES / T;                                                     // jabs words per thread
+    constexpr int NPW = (int)((RS_TILE_LDS_BUDGET - 6 * RS_TILE_ENTRIES) / 16 + T - 1) / T;        // 16-byte plane words per thread
+    constexpr int NEN = RS_TILE_ENTRIES / T;                                                       // entries of a chunk per thread
+    const int npw = ns * rw2;  // the image's words: S rw2 16 <= RS_TILE_LDS_BUDGET less the entry buffer, so npw <= NPW T
+    // the run starts less the prefix, beside spre where the words are free (a slice of one replica and R > S + 1: not)
+    const bool have_sd = 2 * nsl <= R + S + 1;
+    int *sd = spre + nsl;
+    int st1 = 0, jb[NJB], li[NPW];
+    ulonglong2 pw[NPW];
     {  // spre: the exclusive prefix of the runs' lengths, thread t owns slices [t per, (t + 1) per)
         const int per = (nsl + T - 1) / T, s0 = tid * per;
         int sum = 0;
-        for (int j = 0; j < per; ++j)
-            if (s0 + j < nsl) sum += (last ? min(1 << log_trg, R - ((s0 + j) << log_trg)) * nt : (int)run1[s0 + j]) - (int)run0[s0 + j];
+        int en1 = 0;
+        if (RS_TILES_PROLOGUE && per == 1) {  // the bounds once, every lane a valid address; then everything else the tile reads
+            const unsigned short *end1 = last ? run0 : run1;
+            const int s1 = min(tid, nsl - 1);
+            st1 = run0[s1];
+            en1 = end1[s1];
+        }
+        if constexpr (RS_TILES_PROLOGUE) {
+            // The tile's row constants and plane rows: addresses of the block index alone, the image's words dealt flat to the
+            // threads (word c is word c % rw2 of row c / rw2), all of a thread's loads in flight beside the bounds -- the guards
+            // are wave-uniform and the lanes past the end read the last word.
+#pragma unroll
+            for (int j = 0; j < NJB; ++j) {
+                jb[j] = 0;
+                if (j * T < ns) jb[j] = p.jabs[tile0 + min(tid + j * T, ns - 1)];
+            }
+            const ulonglong2 *jp2 = reinterpret_cast<const ulonglong2 *>(p.jp) + (long long)tile0 * (PL + 1) * nw2;
+            const unsigned int mul = 0xffffffffu / (unsigned int)rw2 + 1u;  // (rw2 >= 2: nw2 is even)
+#pragma unroll
+            for (int j = 0; j < NPW; ++j) {
+                pw[j] = make_ulonglong2(0ull, 0ull);
+                li[j] = -1;
+                if (j * T < npw) {
+                    const int c = tid + j * T;
+                    int col;
+                    const int s = rs_tile_of(min(c, npw - 1), rw2, mul, col);
+                    pw[j] = jp2[(long long)s * ((PL + 1) * nw2) + col];  // (ONES: the sign plane, the first)
+                    li[j] = c < npw ? c : -1;
+                }
+            }
+        }
+        if (RS_TILES_PROLOGUE && per == 1) {
+            const int len = (last ? min(1 << log_trg, R - (tid << log_trg)) * nt : en1) - st1;
+            sum = tid < nsl ? len : 0;
+        } else {
+            for (int j = 0; j < per; ++j)
+                if (s0 + j < nsl) sum += (last ? min(1 << log_trg, R - ((s0 + j) << log_trg)) * nt : (int)run1[s0 + j]) - (int)run0[s0 + j];
+        }
         int inc = sum;
 #pragma unroll
         for (int d = 1; d < 64; d <<= 1) {
@@ -575,50 +686,126 @@ __global__ void __launch_bounds__(RS_TILE_THREADS) rs_fields_tiles_kernel(const 
             total += wtot[w];
         }
         if (total == 0) return;  // nobody proposes a site of this tile in this window (workgroup-uniform)
-        for (int j = 0; j < per; ++j)
-            if (s0 + j < nsl) {
-                spre[s0 + j] = run;
-                run += (last ? min(1 << log_trg, R - ((s0 + j) << log_trg)) * nt : (int)run1[s0 + j]) - (int)run0[s0 + j];
+        if (RS_TILES_PROLOGUE && per == 1) {
+            if (tid < nsl) {
+                spre[tid] = run;
+                if (have_sd) sd[tid] = st1 - run;
             }
+        } else {
+            for (int j = 0; j < per; ++j)
+                if (s0 + j < nsl) {
+                    const int b = run0[s0 + j];
+                    spre[s0 + j] = run;
+                    if (RS_TILES_PROLOGUE && have_sd) sd[s0 + j] = b - run;
+                    run += (last ? min(1 << log_trg, R - ((s0 + j) << log_trg)) * nt : (int)run1[s0 + j]) - b;
+                }
+        }
     }
     // The plane rows of the whole tile, beside the copy below.  (Reading only the rows somebody proposes was measured
     // against this at 8 replicas, where most rows of a tile go unproposed: the rows come from L2, and marking them during
     // the copy puts their loads behind it and a barrier more -- slower)
-    for (int s = tid; s < ns; s += T) sjabs[s] = p.jabs[tile0 + s];
-    for (int s = wv; s < ns; s += NW) {  // a wave per row
-        const ulonglong2 *src = reinterpret_cast<const ulonglong2 *>(p.jp) + (long long)(tile0 + s) * (PL + 1) * nw2;
-        for (int c = lane; c < rw2; c += 64) prow[s * rw2 + c] = src[c];  // (ONES: the sign plane, the first)
+    if constexpr (RS_TILES_PROLOGUE) {
+#pragma unroll
+        for (int j = 0; j < NJB; ++j)
+            if (j * T < ns && tid + j * T < ns) sjabs[tid + j * T] = jb[j];
+#pragma unroll
+        for (int j = 0; j < NPW; ++j)
+            if (j * T < npw && li[j] >= 0) prow[li[j]] = pw[j];
+    } else {
+        for (int s = tid; s < ns; s += T) sjabs[s] = p.jabs[tile0 + s];
+        for (int s = wv; s < ns; s += NW) {  // a wave per row
+            const ulonglong2 *src = reinterpret_cast<const ulonglong2 *>(p.jp) + (long long)(tile0 + s) * (PL + 1) * nw2;
+            for (int c = lane; c < rw2; c += 64) prow[s * rw2 + c] = src[c];  // (ONES: the sign plane, the first)
+        }
     }
     const ulonglong2 *bits = reinterpret_cast<const ulonglong2 *>(p.bits);
     const int *went = p.ent + (long long)R * t0;  // the window's entries
+    const int btop = nsl > 1 ? 1 << (31 - __clz(nsl - 1)) : 0;  // the bisection's first step: the highest bit of nsl - 1
     for (int c0 = 0; c0 < total; c0 += RS_TILE_ENTRIES) {
         const int cn = min(RS_TILE_ENTRIES, total - c0);
         __syncthreads();  // (spre; and the last chunk's readers of sent are ahead of its writers)
-        // The chunk is entries c0 ... c0 + cn of the runs' concatenation in slice order -- slices are ascending, disjoint
-        // replica ranges and a run is ordered by replica, so it is grouped by replica as it stands: a wave per run copies
-        // what the chunk holds of it, consecutive lanes consecutive entries.  A wave takes runs wv, wv + NW, ...: it reads
-        // the bounds of 64 of them at once, a lane each, so that a run costs one trip to memory, not two in a row.
-        for (int sb = wv; sb < nsl; sb += 64 * NW) {
-            const int sm = sb + NW * lane;
-            int st = 0, b0 = 0, b1 = 0;
-            if (sm < nsl) st = run0[sm], b0 = spre[sm], b1 = sm + 1 < nsl ? spre[sm + 1] : total;
-            const int nrun = min(64, (nsl - sb + NW - 1) / NW);
-            for (int i = 0; i < nrun; ++i) {
-                const int B0 = read_lane(b0, i), x0 = max(B0, c0), x1 = min(read_lane(b1, i), c0 + cn);
-                if (x0 >= x1) continue;  // (wave-uniform)
-                const int rs0 = (sb + NW * i) << log_trg;
-                const int *src = went + (long long)rs0 * nt + read_lane(st, i) - B0;  // entry g of the concatenation, b0 <= g < b1
-                for (int g = x0 + lane; g < x1; g += 64) {
-                    const int v = src[g], r = rs0 + ((v >> 12) & 31);
-                    int ls = v & 0xfff;
-                    if constexpr (ONES) {  // the replica's own spin bit at the site rides in bit 15 (these loads overlap across the workgroup)
+        if constexpr (RS_TILES_PROLOGUE) {
+            // The chunk is entries c0 ... c0 + cn of the runs' concatenation in slice order -- slices are ascending, disjoint
+            // replica ranges and a run is ordered by replica, so it is grouped by replica as it stands.  Flat: thread t takes
+            // entries c0 + t + j T and finds the run of each -- the last slice whose prefix is not beyond the entry (empty
+            // runs share their prefix with the run behind them) -- by bisecting spre[] in LDS, every step a read of all its
+            // entries.  Then the stages, each issued for all of a thread's entries before the next one's first wait: the
+            // entry words; ONES: the replica's own spin bit at the site; the LDS stores.  The guards are wave-uniform, and
+            // a lane past the chunk's end reads the chunk's last entry and stores nothing.
+            int g[NEN], sl[NEN], v[NEN];
+            unsigned int ob[NEN];
+#pragma unroll
+            for (int j = 0; j < NEN; ++j) g[j] = min(c0 + tid + j * T, c0 + cn - 1), sl[j] = 0;
+            for (int b = btop; b; b >>= 1) {
+#pragma unroll
+                for (int j = 0; j < NEN; ++j) {
+                    const int m = sl[j] + b;
+                    if (spre[min(m, nsl - 1)] <= g[j] && m < nsl) sl[j] = m;
+                }
+            }
+            const int w0 = c0 + 64 * wv;  // the wave's first entry of round 0
+#pragma unroll
+            for (int j = 0; j < NEN; ++j) {
+                v[j] = 0;
+                if (w0 + j * T < c0 + cn) {
+                    const int d = have_sd ? sd[sl[j]] : (int)run0[sl[j]] - spre[sl[j]];
+                    v[j] = went[((sl[j] << log_trg) * nt + d) + g[j]];  // (inside the window's R nt entries)
+                }
+            }
+            if constexpr (ONES) {  // the replica's own spin bit at the site rides in bit 15
+#pragma unroll
+                for (int j = 0; j < NEN; ++j) {
+                    ob[j] = 0u;
+                    if (w0 + j * T < c0 + cn) {
+                        int w32;
+                        unsigned int bit;
+                        rs_bit_of(tile0 + (v[j] & 0xfff), w32, bit);
+                        const int r = (sl[j] << log_trg) + ((v[j] >> 12) & 31);
+                        ob[j] = p.bits[(long long)r * p.nw32 + w32];  // (the word as loaded: masking it here would wait here)
+                    }
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < NEN; ++j)
+                if (w0 + j * T < c0 + cn && c0 + tid + j * T < c0 + cn) {
+                    const int r = (sl[j] << log_trg) + ((v[j] >> 12) & 31);
+                    int ls = v[j] & 0xfff;
+                    if constexpr (ONES) {
                         int w32;
                         unsigned int bit;
                         rs_bit_of(tile0 + ls, w32, bit);
-                        if (p.bits[(long long)r * p.nw32 + w32] & bit) ls |= 0x8000;
+                        if (ob[j] & bit) ls |= 0x8000;
                     }
-                    sent[g - c0] = (r << p.log_w) | (v >> 17);
-                    sls[g - c0] = (unsigned short)ls;
+                    sent[tid + j * T] = (r << p.log_w) | (v[j] >> 17);
+                    sls[tid + j * T] = (unsigned short)ls;
+                }
+        } else {
+            // The chunk is entries c0 ... c0 + cn of the runs' concatenation in slice order -- slices are ascending, disjoint
+            // replica ranges and a run is ordered by replica, so it is grouped by replica as it stands: a wave per run copies
+            // what the chunk holds of it, consecutive lanes consecutive entries.  A wave takes runs wv, wv + NW, ...: it reads
+            // the bounds of 64 of them at once, a lane each, so that a run costs one trip to memory, not two in a row.
+            for (int sb = wv; sb < nsl; sb += 64 * NW) {
+                const int sm = sb + NW * lane;
+                int st = 0, b0 = 0, b1 = 0;
+                if (sm < nsl) st = run0[sm], b0 = spre[sm], b1 = sm + 1 < nsl ? spre[sm + 1] : total;
+                const int nrun = min(64, (nsl - sb + NW - 1) / NW);
+                for (int i = 0; i < nrun; ++i) {
+                    const int B0 = read_lane(b0, i), x0 = max(B0, c0), x1 = min(read_lane(b1, i), c0 + cn);
+                    if (x0 >= x1) continue;  // (wave-uniform)
+                    const int rs0 = (sb + NW * i) << log_trg;
+                    const int *src = went + (long long)rs0 * nt + read_lane(st, i) - B0;  // entry g of the concatenation, b0 <= g < b1
+                    for (int g = x0 + lane; g < x1; g += 64) {
+                        const int v = src[g], r = rs0 + ((v >> 12) & 31);
+                        int ls = v & 0xfff;
+                        if constexpr (ONES) {  // the replica's own spin bit at the site rides in bit 15 (these loads overlap across the workgroup)
+                            int w32;
+                            unsigned int bit;
+                            rs_bit_of(tile0 + ls, w32, bit);
+                            if (p.bits[(long long)r * p.nw32 + w32] & bit) ls |= 0x8000;
+                        }
+                        sent[g - c0] = (r << p.log_w) | (v >> 17);
+                        sls[g - c0] = (unsigned short)ls;
+                    }
                 }
             }
         }
@@ -1167,6 +1354,8 @@ hipError_t launch_sweep_dense_rs(const SweepArgs &a, const RowSharedPlan &p, boo
     if (tiles.S > 0 && (!p.jp || tiles.S > RS_TILE_MAX_SITES || a.R > RS_TILE_MAX_REPLICAS || (tiles.ones && p.planes != 1) ||
                         row_shared_tile_lds(a.n, p.planes, tiles.ones != 0, tiles.S, a.R) > RS_TILE_LDS_BUDGET))
         return hipErrorInvalidValue;
+    // (its entry loop's 32-bit byte offsets: a group's spin bits within 2^30 bytes, a replica's within 2^18; base is 4 R W <= 2^24)
+    if (tiles.S > 0 && (4ll * p.nw32 >= (1ll << 18) || 4ll * p.nw32 * a.R > (1ll << 30))) return hipErrorInvalidValue;
     // (many models: only over one shared matrix -- the plan buckets proposals by site, whatever the replica's model)
     if (a.reps_per_model < 0 || (a.reps_per_model > 0 && a.model_stride_j != 0)) return hipErrorInvalidValue;
     if (a.rep_list || a.R <= 0 || a.n <= 0 || (p.W != 256 && p.W != 512 && p.W != 1024) || (1 << p.log_w) != p.W)
