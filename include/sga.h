@@ -80,7 +80,7 @@ typedef struct sga_engine sga_engine;
 int sga_create(int device, sga_engine **out);
 void sga_destroy(sga_engine *e);
 const char *sga_last_error(void);
-int sga_version(void);  /* 3000: sga_worldline_clusters (simulated quantum annealing: Swendsen-Wang clusters along imaginary time at one site, flipped under the classical field, one launch per call, csrc/worldline_clusters.hip; domain word 4; no option, no engine member); 2900: sga_sweep_transverse (simulated quantum annealing: the Trotter slices of one instance coupled in the CSR sweep, two half-sweeps per sweep, csrc/sweep_transverse.hip; no option, no engine member); 2800: sga_get_class_overlaps / sga_accumulate_ladder_class_overlaps (the overlap between two replicas resolved by a class of sites, first and second moments per temperature summed on the device, csrc/class_overlaps.hip; read only, no engine state, no option); 2700: sga_get_link_count / sga_get_pair_overlaps / sga_accumulate_ladder_overlaps (spin and link overlaps between pairs of replicas, histogrammed per temperature on the device, csrc/pair_overlaps.hip; read only, no engine state, no option); 2600: sga_resample (the resampling step of population annealing, csrc/resample.hip); 2500: sga_cluster_move_pairs / sga_cluster_move_ladders (isoenergetic cluster moves between replica copies on sparse couplings, csrc/cluster_moves.hip; no engine state, no option); 2400: sga_set_replica_groups / sga_get_replica_groups; 2300: sga_get_magnetizations / sga_get_overlaps / sga_get_overlaps_with (replica observables on the device: the exact integer product of int8 spin rows on the matrix cores, csrc/observables.hip; read only, no engine state); 2200: the row-shared fields in tiles take a plan of their own, one launch per sweep (csrc/sweep_dense_rs.hip, rs_tile_plan_kernel; no change of interface or results); 2100: sga_set_sequential_windows / sga_get_sequential_windows (SGA_SITE_SEQUENTIAL sweeps in windows, the fields of every replica on the matrix cores; csrc/sweep_dense_seq.hip); 2000: the row-shared windows (option "row_shared") serve SGA_RULE_GLAUBER and SGA_RULE_HEAT_BATH too ("rule=glauber" / "rule=heat-bath" in sga_describe and sga_get_last_kernel; the window sga_autotune picks holds for the rule it was timed under); 1900: options "row_shared_fields" and "row_shared_tile_sites" (row-shared fields in tiles of sites, sign-only rows); 1800: option "row_shared_grid", sga_route_query.rs_grid; 1700: sga_set_csr_shared (one set of CSR rows, many field vectors: every one-wave-per-replica CSR form for such batches), sga_route_query.shared_j on SGA_ROUTE_CSR queries; 1600: sga_set_dense_shared (one coupling matrix, many field vectors; row-shared windows, bit-planes and the matrix-core pass for such batches), sga_route_query.shared_j; 1500: sga_get_scan_summary, and sga_set_dense / sga_set_dense_batch / sga_set_csr / sga_set_csr64 / sga_set_csr_batch refuse a NaN or +-Inf in J or h (SGA_ERR_INVALID, "non-finite"); 1400: option "batch_fixed_point" (fixed-point cached local fields for many-model dense batches); 1300: options "ragged_field_cache" and "clf_fixed_point" together (fixed-point cached local fields for ragged CSR batches); 1200: sga_set_groups_csr (group couplings plus a stored sparse remainder); 1100: option "ragged_field_cache" (cached local fields for ragged CSR batches); 1000: sga_set_groups */
+int sga_version(void);  /* 3100: sga_sweep_transverse_dense (simulated quantum annealing on dense couplings: the step of sga_sweep_transverse carried by the cached local fields, a coupling row read on accept only, csrc/sweep_transverse_clf.hip; no option, no engine member); 3000: sga_worldline_clusters (simulated quantum annealing: Swendsen-Wang clusters along imaginary time at one site, flipped under the classical field, one launch per call, csrc/worldline_clusters.hip; domain word 4; no option, no engine member); 2900: sga_sweep_transverse (simulated quantum annealing: the Trotter slices of one instance coupled in the CSR sweep, two half-sweeps per sweep, csrc/sweep_transverse.hip; no option, no engine member); 2800: sga_get_class_overlaps / sga_accumulate_ladder_class_overlaps (the overlap between two replicas resolved by a class of sites, first and second moments per temperature summed on the device, csrc/class_overlaps.hip; read only, no engine state, no option); 2700: sga_get_link_count / sga_get_pair_overlaps / sga_accumulate_ladder_overlaps (spin and link overlaps between pairs of replicas, histogrammed per temperature on the device, csrc/pair_overlaps.hip; read only, no engine state, no option); 2600: sga_resample (the resampling step of population annealing, csrc/resample.hip); 2500: sga_cluster_move_pairs / sga_cluster_move_ladders (isoenergetic cluster moves between replica copies on sparse couplings, csrc/cluster_moves.hip; no engine state, no option); 2400: sga_set_replica_groups / sga_get_replica_groups; 2300: sga_get_magnetizations / sga_get_overlaps / sga_get_overlaps_with (replica observables on the device: the exact integer product of int8 spin rows on the matrix cores, csrc/observables.hip; read only, no engine state); 2200: the row-shared fields in tiles take a plan of their own, one launch per sweep (csrc/sweep_dense_rs.hip, rs_tile_plan_kernel; no change of interface or results); 2100: sga_set_sequential_windows / sga_get_sequential_windows (SGA_SITE_SEQUENTIAL sweeps in windows, the fields of every replica on the matrix cores; csrc/sweep_dense_seq.hip); 2000: the row-shared windows (option "row_shared") serve SGA_RULE_GLAUBER and SGA_RULE_HEAT_BATH too ("rule=glauber" / "rule=heat-bath" in sga_describe and sga_get_last_kernel; the window sga_autotune picks holds for the rule it was timed under); 1900: options "row_shared_fields" and "row_shared_tile_sites" (row-shared fields in tiles of sites, sign-only rows); 1800: option "row_shared_grid", sga_route_query.rs_grid; 1700: sga_set_csr_shared (one set of CSR rows, many field vectors: every one-wave-per-replica CSR form for such batches), sga_route_query.shared_j on SGA_ROUTE_CSR queries; 1600: sga_set_dense_shared (one coupling matrix, many field vectors; row-shared windows, bit-planes and the matrix-core pass for such batches), sga_route_query.shared_j; 1500: sga_get_scan_summary, and sga_set_dense / sga_set_dense_batch / sga_set_csr / sga_set_csr64 / sga_set_csr_batch refuse a NaN or +-Inf in J or h (SGA_ERR_INVALID, "non-finite"); 1400: option "batch_fixed_point" (fixed-point cached local fields for many-model dense batches); 1300: options "ragged_field_cache" and "clf_fixed_point" together (fixed-point cached local fields for ragged CSR batches); 1200: sga_set_groups_csr (group couplings plus a stored sparse remainder); 1100: option "ragged_field_cache" (cached local fields for ragged CSR batches); 1000: sga_set_groups */
 /* Run on an existing HIP stream (e.g. torch.cuda.current_stream().cuda_stream); NULL = the
  * engine's own stream (default). */
 int sga_set_stream(sga_engine *e, void *hip_stream);
@@ -608,6 +608,34 @@ int sga_accumulate_ladder_class_overlaps(sga_engine *e, int slot_lo, int slot_hi
  *   The launches (two per sweep, built per arithmetic) show in sga_get_last_kernel; sga_enable_timing does not bracket them. */
 int sga_sweep_transverse(sga_engine *e, int n_sweeps, int n_slices, int arith /* SGA_ARITH_* */,
                          const float *k_perp /* host [n_sweeps][R_local / n_slices] */);
+
+/* ---- simulated quantum annealing on dense couplings (version >= 3100; csrc/sweep_transverse_clf.hip) ------------------
+ * The step of sga_sweep_transverse, word for word -- groups, half-sweeps, the production stream, h_eff = h_i + k (float)a
+ * in fp32, the Metropolis rule in `arith`, the classical dE on accept, bests after the sweep, counters -- on ONE dense
+ * matrix, in the form of the cached-local-field sweep: a moving slice keeps F = scale (J s + h) in LDS and reads a
+ * coupling row only when a proposal is accepted.  The rule sees the exact integer row sum dot_i = (F_i - scale h_i) /
+ * scale and h_eff: (double)dot + (double)h_eff under SGA_ARITH_F64, that sum rounded to fp32 once under SGA_ARITH_F32.
+ *   By construction: with k = 0 everywhere the call is sga_sweep(n_sweeps, SGA_SITE_RANDOM, arith) bit for bit, a call of 2
+ *   sweeps equals two calls of 1, and the same integer couplings held as CSR under sga_sweep_transverse give the same chain.
+ *   Fields.  The call seeds the resident fields where they are not valid (the pass the cached sga_sweep uses) and keeps
+ *   them valid: every launch writes the moving slices' fields back, and a cached sga_sweep after it goes on without
+ *   seeding.  (Under SGA_FIELD_CACHE_AUTO, which routes replica by replica, the call seeds them every time.)  The field
+ *   cache mode itself is not looked at: the call is its own opt-in.
+ *   Served: one dense model (sga_set_dense) that the integer cached-field form admits -- integer symmetric J with a zero
+ *   diagonal, h in multiples of 1/2, row bound below 2^24; int8 and fp32 rows, int16 and int32 fields -- under
+ *   SGA_RULE_METROPOLIS, with a slice's fields, spin bits, two rows of neighbour bits and decision slots within LDS
+ *   (163 584 bytes): 2.375 n + 512 bytes with int16 fields, 4.375 n + 512 with int32 fields, rows padded to 128 elements:
+ *   n <= 68 608 and n <= 37 248.  Option "clf_waves" sets the waves per slice; 0 leaves the cached sweep's choice, taken
+ *   over the R_local / 2 workgroups of a launch.
+ *   SGA_ERR_INVALID, first and with the engine unchanged: exactly what sga_sweep_transverse reports so, in the same words.
+ *   SGA_ERR_UNSUPPORTED, with the reason in sga_last_error: sga_set_tsp, sga_set_groups / sga_set_groups_csr, batches
+ *   (ragged, shared and stacked), CSR engines -- a sparse matrix that sga_set_dense kept as CSR included: they are
+ *   sga_sweep_transverse's --, a dense problem the integer cached-field form does not take (real-valued J, a non-zero
+ *   diagonal, asymmetric J, a bound of 2^24 or more: the set-time scan's reason), rules other than Metropolis, a slice
+ *   beyond LDS.  World-line clusters on dense couplings are not served.
+ *   The launches (two per sweep) show in sga_get_last_kernel; sga_enable_timing does not bracket them. */
+int sga_sweep_transverse_dense(sga_engine *e, int n_sweeps, int n_slices, int arith /* SGA_ARITH_* */,
+                               const float *k_perp /* host [n_sweeps][R_local / n_slices] */);
 
 /* ---- world-line cluster updates for simulated quantum annealing (version >= 3000; csrc/worldline_clusters.hip) --------
  * Swendsen-Wang clusters along the imaginary-time direction at one site, flipped under the classical field (Rieger and

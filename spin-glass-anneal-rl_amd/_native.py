@@ -68,6 +68,7 @@ SYMBOLS = [
     ("sga_set_ladder", _i, [_p, _p, _i]),
     ("sga_sweep", _i, [_p, _i, _i, _i, _p, _i64, _i64, _p, _p, _p, _p, _p]),
     ("sga_sweep_transverse", _i, [_p, _i, _i, _i, _p]),
+    ("sga_sweep_transverse_dense", _i, [_p, _i, _i, _i, _p]),
     ("sga_worldline_clusters", _i, [_p, _i, _i, _u32, _p, _p]),
     ("sga_local_fields", _i, [_p, _i, _p, _i, _p]),
     ("sga_flip", _i, [_p, _i, _i, C.POINTER(_d)]),

@@ -347,6 +347,9 @@ extern "C" {
 
 const char *sga_last_error(void) { return g_last_error.c_str(); }
 // The ABI version, one line per step:
+//   3100:    + sga_sweep_transverse_dense: the step of sga_sweep_transverse on dense couplings, carried by the cached local
+//            fields -- one workgroup per moving slice, a coupling row read on accept only, the fields kept valid
+//            (sweep_transverse_clf.hip; the admission rule in sga_kernels.h); no option, no engine member
 //   3000:    + sga_worldline_clusters: Swendsen-Wang clusters along imaginary time at one site, flipped under the classical
 //            field -- what keeps simulated quantum annealing ergodic at small Gamma; one launch per call, one wave per
 //            group of slices, a coupling row read once for all slices of a site (worldline_clusters.hip; the admission
@@ -397,7 +400,7 @@ const char *sga_last_error(void) { return g_last_error.c_str(); }
 //   600:     + sga_set_csr_batch / sga_get_batch_model (ragged CSR batches)
 //   round 5: + sga_explain_route / sga_get_route_query, sga_get_last_kernel, sga_get_autotune_table, ladder-local
 //            sga_exchange
-int sga_version(void) { return 3000; }
+int sga_version(void) { return 3100; }
 
 int sga_create(int device, sga_engine **out) {
     if (!out) return fail(SGA_ERR_INVALID, "out is NULL");
@@ -1285,6 +1288,88 @@ int sga_sweep_transverse(sga_engine *e, int n_sweeps, int n_slices, int arith, c
             const sga::TransverseArgs t{d_k + (size_t)kk * (size_t)G, n_slices, parity, G * (n_slices / 2), h_eff};
             const hipError_t le = sga::launch_sweep_transverse(a, t, st);
             if (le != hipSuccess) (void)hipStreamSynchronize(st);
+            HIPCHK(le);
+        }
+    }
+    std::snprintf(e->last_kernel, sizeof(e->last_kernel), "%s", sga::last_sweep_kernel());
+    e->sweeps_done += (uint32_t)n_sweeps;
+    e->attempted += (long long)n_sweeps * e->n;
+    return SGA_OK;
+}
+
+// ---- simulated quantum annealing on dense couplings, carried by the cached local fields (sweep_transverse_clf.hip) --
+// The step of sga_sweep_transverse over the resident fields of the dense cached-field sweep: seeded through
+// ensure_fields where they are not valid, written back by every launch for the slices that moved -- they stay valid.
+int sga_sweep_transverse_dense(sga_engine *e, int n_sweeps, int n_slices, int arith, const float *k_perp) {
+    sga::TransverseDenseProblem tp;
+    if (e) {
+        tp.n = e->n, tp.R_local = e->spins ? e->R : 0, tp.replica0 = e->replica0, tp.sstride = e->sstride;
+        tp.csr = e->csr, tp.tsp = e->tsp, tp.groups = e->groups, tp.ragged = e->ragged, tp.n_models = e->n_models;
+        tp.clf_problem = (!e->csr && !e->implicit() && e->clf_problem && !e->clf_fx_bits) ? 1 : 0;
+        tp.clf_why = e->clf_why;
+        tp.field_bits = e->clf_bits;
+        tp.ldf = (e->ldj + 127) / 128 * 128;  // (as ensure_fields lays the rows out)
+        tp.metropolis = e->rule == SGA_RULE_METROPOLIS;
+    }
+    if (k_perp && is_device_ptr(k_perp)) return fail(SGA_ERR_INVALID, "k_perp must be a host buffer");
+    bool invalid = true;
+    if (const char *why = sga::transverse_dense_check(e != nullptr, tp, n_sweeps, n_slices,
+                                                      arith == SGA_ARITH_F64 || arith == SGA_ARITH_F32, k_perp, &invalid))
+        return fail(invalid ? SGA_ERR_INVALID : SGA_ERR_UNSUPPORTED, why);
+    if (n_sweeps == 0) return SGA_OK;
+    if (e->opt_stale)
+        return fail(SGA_ERR_INVALID, std::string("option \"") + (e->opt_stale_key ? e->opt_stale_key : "?") +
+                                         "\" changed after it was read: set the couplings and initialise the replicas again");
+    if (!e->J_packed || !e->h || !e->best_spins) return fail(SGA_ERR_INVALID, "no couplings set");
+    HIPCHK(hipSetDevice(e->device));
+    hipStream_t st = e->stream;
+    {
+        // (SGA_FIELD_CACHE_AUTO routes replica by replica: the fields of a replica on the row kernels are stale while
+        //  fields_valid stands for the others -- this call reads every slice's, so under AUTO it seeds them itself)
+        if (e->field_cache == SGA_FIELD_CACHE_AUTO) e->fields_valid = false;
+        const int rc = ensure_fields(e);
+        if (rc != SGA_OK) return rc;
+    }
+    const int G = e->R / n_slices, moving = G * (n_slices / 2);
+    // (a pageable host array: the copy has left the caller's buffer when the call returns)
+    HIPCHK(e->scratch[0].reserve((size_t)n_sweeps * (size_t)G * sizeof(float)));
+    float *d_k = static_cast<float *>(e->scratch[0].ptr);
+    HIPCHK(hipMemcpyAsync(d_k, k_perp, (size_t)n_sweeps * (size_t)G * sizeof(float), hipMemcpyHostToDevice, st));
+    sga::SweepArgs a{};
+    a.J = e->J_packed;
+    a.h = e->h;
+    a.spins = e->spins;
+    a.energy = e->energy;
+    a.best_energy = e->best_energy;
+    a.best_spins = e->best_spins;
+    a.n_accepted = e->n_acc;
+    a.rep_temp = e->rep_temp;
+    a.ldj = e->ldj;
+    a.n = e->n;
+    a.sstride = e->sstride;
+    a.R = e->R;
+    a.n_sweeps = 1;
+    a.site_mode = SGA_SITE_RANDOM;
+    a.arith = arith;
+    a.rule = SGA_RULE_METROPOLIS;
+    a.fields = e->fields;
+    a.ldf = e->ldf;
+    a.field_bits = e->clf_bits;
+    a.field_scale = e->clf_scale;
+    a.seed_lo = (uint32_t)e->seed;
+    a.seed_hi = (uint32_t)(e->seed >> 32);
+    a.replica0 = (uint32_t)e->replica0;
+    // waves per slice: option "clf_waves", else the cached-field sweep's choice over the workgroups of a launch, R / 2
+    const int waves = sga::sweep_clf_waves(e->ldj, e->want_i8, moving, e->cus, (int)e->opt[OPT_CLF_WAVES]);
+    for (int kk = 0; kk < n_sweeps; ++kk) {
+        a.sweep0 = e->sweeps_done + (uint32_t)kk;
+        for (int parity = 0; parity < 2; ++parity) {
+            const sga::TransverseDenseArgs t{d_k + (size_t)kk * (size_t)G, n_slices, parity, moving};
+            const hipError_t le = sga::launch_sweep_transverse_dense(a, t, e->want_i8, waves, st);
+            if (le != hipSuccess) {
+                (void)hipStreamSynchronize(st);
+                e->fields_valid = false;  // (a launch that did not go out: nothing is known about the sweep's state)
+            }
             HIPCHK(le);
         }
     }

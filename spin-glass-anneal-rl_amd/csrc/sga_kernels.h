@@ -1037,6 +1037,70 @@ struct TransverseArgs {
 // a: the arguments of one production sweep (n_sweeps = 1, sweep0 = the sweep's counter); reads a.rowptr64 / a.cv
 hipError_t launch_sweep_transverse(const SweepArgs &a, const TransverseArgs &t, hipStream_t st);
 
+// Simulated quantum annealing on DENSE couplings, carried by the cached local fields (sweep_transverse_clf.hip;
+// sga_sweep_transverse_dense).  The step and the groups are sga_sweep_transverse's; the form is the cached-field sweep's:
+// one workgroup per moving slice, LDS = fields [ldf] int16 | int32, the slice's spin bits, the two neighbour slices'
+// spin bits (n / 4 bytes), the decision slots.
+constexpr size_t TRANSVERSE_DENSE_SLOT_BYTES = 2 * 8 * 8 * sizeof(int);  // [2][CLF_MAX_WAVES][CLF_SLOT_INTS]
+__host__ __device__ constexpr long long transverse_dense_bits_bytes(int sstride) { return (sstride / 8 + 15) & ~15; }
+inline size_t transverse_dense_lds_bytes(long long ldf, int fbytes, int sstride) {
+    return (size_t)((ldf * fbytes + 15) & ~15ll) + 3 * (size_t)transverse_dense_bits_bytes(sstride) + TRANSVERSE_DENSE_SLOT_BYTES;
+}
+// What of an engine the admission rule reads.
+struct TransverseDenseProblem {
+    int n = 0, R_local = 0, replica0 = 0, sstride = 0;
+    int csr = 0, tsp = 0, groups = 0, ragged = 0, n_models = 1;
+    int clf_problem = 0;            // the one-model integer cached-field form admits the problem (set-time scan)
+    const char *clf_why = nullptr;  // ... where it does not: which condition failed
+    int field_bits = 16;            // 16 | 32: the width of the resident fields
+    long long ldf = 0;              // elements of a replica's field row
+    int metropolis = 1;             // the engine's rule is SGA_RULE_METROPOLIS
+};
+// The admission rule of sga_sweep_transverse_dense, a pure function as transverse_check is: nullptr where the call is
+// served, else why not, *invalid = true for SGA_ERR_INVALID and false for SGA_ERR_UNSUPPORTED.  The argument errors are
+// transverse_check's, in its words and its order, and come first.  The bound on n (include/sga.h) is the last test: the
+// fields, three rows of spin bits and the slots within TRANSVERSE_LDS_BUDGET -- 2.375 n bytes with int16 fields, 4.375 n
+// with int32 fields, plus padding and 512 bytes of slots.
+inline const char *transverse_dense_check(bool have_engine, const TransverseDenseProblem &p, int n_sweeps, int n_slices, bool arith_ok,
+                                          const float *k_perp, bool *invalid) {
+    *invalid = true;
+    if (!have_engine) return "engine is NULL";
+    if (!k_perp) return "k_perp is NULL";
+    if (p.n <= 0) return "no couplings set";
+    if (p.R_local <= 0) return "no replicas (call sga_init_replicas)";
+    if (n_sweeps < 0) return "n_sweeps < 0";
+    if (!arith_ok) return "bad arith";
+    if (n_slices < 2) return "n_slices must be at least 2";
+    if (n_slices % 2 != 0) return "n_slices must be even (a moving slice never has a moving neighbour)";
+    if (p.R_local % n_slices != 0) return "n_slices must divide the number of local replicas";
+    if (p.replica0 % n_slices != 0) return "replica0 must be a multiple of n_slices (groups lie whole on a rank)";
+    const long long count = (long long)n_sweeps * (p.R_local / n_slices);
+    for (long long i = 0; i < count; ++i)
+        if (!(k_perp[i] - k_perp[i] == 0.0f)) return "k_perp holds a NaN or an infinite value";
+    *invalid = false;
+    if (p.tsp) return "dense transverse sweeps are not implemented for sga_set_tsp problems";
+    if (p.groups) return "dense transverse sweeps are not implemented for sga_set_groups / sga_set_groups_csr problems";
+    if (p.ragged) return "dense transverse sweeps are not implemented for ragged CSR batches";
+    if (p.n_models > 1) return "dense transverse sweeps are not implemented for many-model batches (shared or stacked)";
+    if (p.csr) return "dense transverse sweeps need dense rows: the engine holds sparse (CSR) couplings, which sga_sweep_transverse serves";
+    if (!p.clf_problem)
+        return p.clf_why ? p.clf_why : "dense transverse sweeps need the integer cached-field form (integer symmetric J, zero diagonal)";
+    if (!p.metropolis) return "dense transverse sweeps are implemented for the Metropolis rule only";
+    if ((p.field_bits != 16 && p.field_bits != 32) || p.sstride <= 0 || p.ldf <= 0 ||
+        transverse_dense_lds_bytes(p.ldf, p.field_bits / 8, p.sstride) > TRANSVERSE_LDS_BUDGET)
+        return "dense transverse sweeps: a slice's fields, spin bits and neighbour bits do not fit LDS";
+    return nullptr;
+}
+struct TransverseDenseArgs {
+    const float *k_perp;  // device [G]: this sweep's coupling per group
+    int n_slices;         // P
+    int parity;           // the slices p with p % 2 == parity move
+    int moving;           // G P / 2 workgroups
+};
+// a: the arguments of one production sweep (n_sweeps = 1, sweep0 = the sweep's counter) with the resident fields (fields,
+// ldf, field_bits, field_scale) and the dense rows (J, ldj); the launch reads and writes the moving slices' fields
+hipError_t launch_sweep_transverse_dense(const SweepArgs &a, const TransverseDenseArgs &t, bool j_is_i8, int waves, hipStream_t st);
+
 // World-line cluster updates along imaginary time (worldline_clusters.hip; sga_worldline_clusters).  The groups are those
 // of the transverse sweep.  One wave per group, lane p = slice p; the group's spins as one word per site in LDS, bit p =
 // [s_p[i] < 0]: uint32_t for P <= 32, uint64_t beyond.  The budget is the transverse sweep's; behind the words lie 64

@@ -589,6 +589,19 @@ class AnnealEngine:
         N.check(self._lib.sga_sweep_transverse(self._h, int(n_sweeps), int(n_slices), int(arith), k.ctypes.data_as(C.c_void_p)),
                 "sga_sweep_transverse")
 
+    def sweep_transverse_dense(self, n_sweeps: int, n_slices: int, k_perp, arith: int = N.ARITH_F64):
+        """sweep_transverse on one dense matrix (sga_sweep_transverse_dense): the same step, carried by the cached local
+        fields -- a moving slice keeps its fields in LDS and reads a coupling row only on accept; the fields are seeded
+        where they are not valid and stay valid for a cached sweep() after it.  k_perp as in sweep_transverse.  Serves
+        integer symmetric J with a zero diagonal and h in multiples of 1/2 (set_dense); any other problem raises
+        AnnealingError with the engine's reason."""
+        P = int(n_slices)
+        # (a P the engine will refuse: any well-formed array, so that the refusal and its reason are the engine's)
+        G = self.R // P if P >= 1 and self.R > 0 and self.R % P == 0 else 1
+        k = transverse_k_perp(k_perp, n_sweeps, G)
+        N.check(self._lib.sga_sweep_transverse_dense(self._h, int(n_sweeps), int(n_slices), int(arith), k.ctypes.data_as(C.c_void_p)),
+                "sga_sweep_transverse_dense")
+
     def worldline_clusters(self, n_sweeps: int, n_slices: int, p_bond, round: Optional[int] = None, stats: bool = False):
         """n_sweeps sweeps of world-line cluster updates over the replicas as R / n_slices groups of n_slices Trotter
         slices (sga_worldline_clusters): per site the slices are cut into segments by bonds drawn with p_bond between equal

@@ -17,6 +17,12 @@ every cluster_interval-th transverse sweep with one such sweep.
 
 The step serves one-model sparse (CSR) problems with integer couplings under the Metropolis rule; any other problem
 raises AnnealingError with the engine's reason -- there is no classical fallback.
+
+Dense couplings (SK glasses, number partitioning, dense QUBO encodings) are an opt-in:
+SimulatedQuantumAnnealingConfig(dense_couplings=True) hands the model to the engine as one dense matrix with the field
+cache on and sweeps through AnnealEngine.sweep_transverse_dense (sga_sweep_transverse_dense) -- the same step, a slice's
+local fields resident in LDS and a coupling row read on accept only.  It serves integer symmetric J with a zero diagonal
+and h in multiples of 1/2; world-line clusters are not served there.
 """
 import time
 from dataclasses import dataclass, field
@@ -27,7 +33,7 @@ import torch
 
 from . import _native as N
 from .engine import AnnealEngine
-from .exceptions import ConfigurationError
+from .exceptions import AnnealingError, ConfigurationError
 from .gpu_annealer import fresh_seed
 from .ising_model import IsingModel, _device_index
 from .result import AnnealingResult
@@ -108,6 +114,8 @@ class SimulatedQuantumAnnealingConfig:
     device_index: Optional[int] = None
     worldline_clusters: bool = False      # follow transverse sweeps with world-line cluster sweeps (sga_worldline_clusters)
     cluster_interval: int = 1             # ... every cluster_interval-th of them
+    dense_couplings: bool = False         # hand the model over as one dense matrix, field cache on, and sweep through
+    #                                       sga_sweep_transverse_dense (False: the model's own form, CSR rows served only)
 
     def __post_init__(self):
         self.check()
@@ -127,6 +135,8 @@ class SimulatedQuantumAnnealingConfig:
             raise ConfigurationError("worldline_clusters must be True or False")
         if self.worldline_clusters and self.n_slices > 64:
             raise ConfigurationError("world-line clusters serve at most 64 slices (one lane of a wave per slice)")
+        if not isinstance(self.dense_couplings, (bool, np.bool_)):
+            raise ConfigurationError("dense_couplings must be True or False")
 
     def couplings(self) -> np.ndarray:
         """float32 [n_sweeps]: k_perp per sweep."""
@@ -148,11 +158,15 @@ class SimulatedQuantumAnnealing:
         self.device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
         self.use_cuda = self.device.type == "cuda"
 
-    def _sweeps(self, eng, k0: int, ns: int, k, clusters: bool):
+    def _sweeps(self, eng, k0: int, ns: int, k, clusters: bool, dense: bool = False):
         """Transverse sweeps k0 ... k0 + ns - 1; with clusters, every cluster_interval-th one (counted over the run) is
-        followed by one cluster sweep at its k_perp, drawn at round = the sweep's index."""
+        followed by one cluster sweep at its k_perp, drawn at round = the sweep's index.  dense: the engine holds dense
+        rows, the sweeps are sweep_transverse_dense's (never with clusters)."""
         cfg = self.config
         P = int(cfg.n_slices)
+        if dense:
+            eng.sweep_transverse_dense(ns, P, k[k0:k0 + ns])
+            return
         if not clusters:
             eng.sweep_transverse(ns, P, k[k0:k0 + ns])
             return
@@ -173,6 +187,9 @@ class SimulatedQuantumAnnealing:
         clusters = bool(cfg.worldline_clusters if worldline_clusters is None else worldline_clusters)
         if clusters and cfg.n_slices > 64:
             raise ConfigurationError("world-line clusters serve at most 64 slices (one lane of a wave per slice)")
+        if cfg.dense_couplings and clusters:
+            raise AnnealingError("world-line clusters are not served on dense couplings: sga_worldline_clusters reads CSR rows "
+                                 "(run with dense_couplings=False on a sparse model, or without worldline_clusters)")
         self.cluster_statistics = np.zeros(3, np.int64) if clusters else None
         P, G, n = int(cfg.n_slices), int(cfg.n_instances), model.n_spins
         R = P * G
@@ -183,13 +200,22 @@ class SimulatedQuantumAnnealing:
         energy_history, temp_history, acc_history = [], [], []
         step = int(cfg.measure_interval)
         with AnnealEngine(dev_idx) as eng:
-            model.load_into(eng)
+            dense = False
+            if cfg.dense_couplings:
+                # one dense matrix with the field cache on: the rows stay dense (the sparse route is taken with the cache
+                # off or left to the engine only); should the engine hold CSR rows all the same, they are sweep_transverse's
+                eng.set_field_cache("on")
+                J = model.couplings.to_dense() if model.couplings.is_sparse else model.couplings
+                eng.set_dense(J, model.external_fields)
+                dense = eng.route_query().kind != N.ROUTE_CSR
+            else:
+                model.load_into(eng)
             eng.init_replicas(R, seed=fresh_seed(cfg.seed))
             eng.set_temperatures(P * float(cfg.temperature))
             acc_prev = np.zeros(R, np.int64)
             for k0 in range(0, int(cfg.n_sweeps), step):
                 ns = min(step, int(cfg.n_sweeps) - k0)
-                self._sweeps(eng, k0, ns, k, clusters)
+                self._sweeps(eng, k0, ns, k, clusters, dense)
                 en, acc, _ = eng.snapshot(slots=False)
                 energy_history.append(float(en.min()))       # the lowest classical energy over the slices now
                 temp_history.append(float(gam[k0 + ns - 1]))  # (the transverse field: T is constant)
@@ -216,10 +242,12 @@ class QuantumFluctuations:
     number of sweeps, the temperature (its final one) and the seed; the schedule gives Gamma."""
 
     def __init__(self, base_annealer=None, transverse_field_schedule: str = "linear_decrease", initial_field_strength: float = 5.0,
-                 final_field_strength: float = 0.01, n_instances: int = 1, worldline_clusters: bool = False):
+                 final_field_strength: float = 0.01, n_instances: int = 1, worldline_clusters: bool = False,
+                 dense_couplings: bool = False):
         self.base_annealer = base_annealer
         self.n_instances = int(n_instances)
         self.worldline_clusters = bool(worldline_clusters)
+        self.dense_couplings = bool(dense_couplings)
         self.field = TransverseField(transverse_field_schedule, float(initial_field_strength),
                                      min(float(final_field_strength), float(initial_field_strength)))
         self.last = None  # the SimulatedQuantumAnnealing of the last call (final_energies, slice_overlaps)
@@ -233,7 +261,8 @@ class QuantumFluctuations:
         cfg = SimulatedQuantumAnnealingConfig(
             n_slices=int(P), n_instances=self.n_instances, temperature=float(T), n_sweeps=int(self._base("n_sweeps", 1000)),
             transverse_field=tf, seed=self._base("random_seed", None), measure_interval=int(self._base("record_interval", 10)),
-            device_index=self._base("device_index", None), worldline_clusters=self.worldline_clusters)
+            device_index=self._base("device_index", None), worldline_clusters=self.worldline_clusters,
+            dense_couplings=self.dense_couplings)
         self.last = SimulatedQuantumAnnealing(cfg)
         return self.last.run(model)
 
