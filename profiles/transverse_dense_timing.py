@@ -18,8 +18,10 @@ at P T = 80 (`--slice-temperature 80 --gammas 80 2.7`), the hotter schedule.  Fi
                         proposal passes), set_dense_shared with one model per slice, init_replicas(s0 = the spins),
                         set_temperatures, sweep(1); twice for a sweep
 `--clf-waves W` times the new sweep alone under option clf_waves = W (keys ..._wavesW): the waves per slice.
+`--ab LABEL`: transverse_dense_ms alone, of the library in use (SGA_LIBRARY_PATH), appended as one round under
+doc["ab_rounds"][LABEL][key] (profiles/ab_rounds.py); nothing else of the file changes.
 usage: transverse_dense_timing.py [--reps 20] [--warmup 3] [--presweeps 50] [--n 10000] [--storage i8|f32|both]
-                                  [--slice-temperature 30] [--gammas MID END] [--clf-waves W] [--out FILE] [--no-write]"""
+                                  [--slice-temperature 30] [--gammas MID END] [--clf-waves W] [--ab LABEL] [--out FILE] [--no-write]"""
 import argparse
 import json
 import os
@@ -76,7 +78,8 @@ def measure(J, storage, point, gamma, G, P, a):
         res["transverse_dense_ms"] = event_ms(torch, lambda: e.sweep_transverse_dense(1, P, k), a.warmup, a.reps)
         res["hottest_acceptance"] = float((e.stats()[0] - acc0).max()) / float((a.warmup + a.reps) * n)
         res["transverse_dense_kernel"] = e.last_kernel()
-        if a.clf_waves:  # (the waves per slice: the new sweep alone)
+        if a.clf_waves or a.ab:  # (the waves per slice, a round of an A/B: the new sweep alone)
+            res["library"] = os.path.basename(sg._native.library_path())
             return res
         res["describe"] = e.describe()
         # (a) the classical cached-field sweep, from the state the presweeps left
@@ -135,6 +138,7 @@ if __name__ == "__main__":
     ap.add_argument("--gammas", type=float, nargs=2, default=[30.0, 1.0], metavar=("MID", "END"))
     ap.add_argument("--storage", default="both", choices=["i8", "f32", "both"])
     ap.add_argument("--clf-waves", type=int, default=0, help="option clf_waves: transverse_dense_ms alone, key suffix _wavesN")
+    ap.add_argument("--ab", default="", metavar="LABEL")
     ap.add_argument("--no-write", action="store_true")
     ap.add_argument("--out", default=OUT)
     a = ap.parse_args()
@@ -152,8 +156,13 @@ if __name__ == "__main__":
             key = "T%g_%s_%s" % (a.slice_temperature, storage, point)  # (runs at several slice temperatures share the file)
             if a.clf_waves:
                 key += "_waves%d" % a.clf_waves
-            doc[key] = measure(J, storage, point, gamma, a.instances, a.slices, a)
-            print(json.dumps({key: doc[key]}, indent=1), flush=True)
+            got = measure(J, storage, point, gamma, a.instances, a.slices, a)
+            print(json.dumps({key: got}, indent=1), flush=True)
+            if a.ab:
+                import ab_rounds
+                ab_rounds.append(doc, a.ab, key, {"transverse_dense_ms": got["transverse_dense_ms"]}, got["library"])
+            else:
+                doc[key] = got
     if not a.no_write:
         with open(a.out, "w") as f:
             json.dump(doc, f, indent=1)

@@ -20,10 +20,11 @@ Figures per shape, median [min, max] ms of `--reps` (20) calls after `--warmup` 
                        (h + k (s_up + s_dn) for the moving slices; a standing slice is given T = 0 and a field 10^6 s that no
                        proposal passes), set_csr_shared with one model per slice, init_replicas(s0 = the spins), set_temperatures,
                        sweep(1); twice for a sweep
-`--variant NAME` stores transverse_ms and transverse_8_ms of a library given in SGA_LIBRARY_PATH whose sweep_transverse.hip and
-sga_engine.cpp were compiled with -DSGA_TRANSVERSE_PREPASS=1 (h_eff from a pre-kernel, one float gather) under
-doc[shape]["variants"][NAME].
-usage: transverse_timing.py [--reps 20] [--warmup 3] [--presweeps 50] [--shape lattice_22|c3|both] [--variant NAME] [--out FILE] [--no-write]"""
+doc[shape]["variants"] holds the figures of a build that is no longer there (h_eff from a pre-kernel: DESIGN.md 4.9); it is
+carried over as it stands.
+`--ab LABEL`: transverse_ms and transverse_8_ms alone, of the library in use (SGA_LIBRARY_PATH), appended as one round under
+doc["ab_rounds"][LABEL][shape] (profiles/ab_rounds.py); nothing else of the file changes.
+usage: transverse_timing.py [--reps 20] [--warmup 3] [--presweeps 50] [--shape lattice_22|c3|both] [--ab LABEL] [--out FILE] [--no-write]"""
 import argparse
 import json
 import os
@@ -81,9 +82,9 @@ def measure(name, graph, G, P, a):
         out = {"transverse_ms": event_ms(torch, lambda: e.sweep_transverse(1, P, k), a.warmup, a.reps),
                "transverse_8_ms": [t / 8 for t in event_ms(torch, lambda: e.sweep_transverse(8, P, k), a.warmup, a.reps)],
                "transverse_kernel": e.last_kernel()}
-        if a.variant:
-            out["library"] = os.path.basename(sg._native.library_path())
-            return {"variants": {a.variant: out}}
+        if a.ab:
+            return {"figures": {key: out[key] for key in ("transverse_ms", "transverse_8_ms")},
+                    "library": os.path.basename(sg._native.library_path())}
         res.update(out)
         res["describe"] = e.describe()
         res["sweep_default_ms"] = event_ms(torch, lambda: e.sweep(1), a.warmup, a.reps)
@@ -128,7 +129,7 @@ if __name__ == "__main__":
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--presweeps", type=int, default=50)
     ap.add_argument("--shape", default="both", choices=["lattice_22", "c3", "both"])
-    ap.add_argument("--variant", default="")
+    ap.add_argument("--ab", default="", metavar="LABEL")
     ap.add_argument("--no-write", action="store_true")
     ap.add_argument("--out", default=OUT)
     a = ap.parse_args()
@@ -148,8 +149,9 @@ if __name__ == "__main__":
         shapes["c3"] = (bench.make_sparse_instance(10000, 16, 3), 16, 64)
     for name, (graph, G, P) in shapes.items():
         got = measure(name, graph, G, P, a)
-        if a.variant:
-            doc.setdefault(name, {}).setdefault("variants", {}).update(got["variants"])
+        if a.ab:
+            import ab_rounds
+            ab_rounds.append(doc, a.ab, name, got["figures"], got["library"])
         else:
             got["variants"] = doc.get(name, {}).get("variants", {})
             doc[name] = got

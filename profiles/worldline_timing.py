@@ -18,8 +18,11 @@ and from the counts of the timed calls: the mean segment length (P n / segments 
 `--anneal SWEEPS`: the residual energy of SimulatedQuantumAnnealing.run on the lattice, 32 slices x 4 instances, Gamma 3 ->
 0.01 linearly, with and without the clusters at equal transverse sweeps over the same `--seeds` (4) seeds: the best energy
 per site of each run.
+`--ab LABEL`: clusters_ms, clusters_8_ms and transverse_ms per Gamma alone (no host route), of the library in use
+(SGA_LIBRARY_PATH), appended as one round under doc["ab_rounds"][LABEL][shape] (profiles/ab_rounds.py); nothing else of the
+file changes.
 usage: worldline_timing.py [--reps 20] [--warmup 3] [--presweeps 50] [--shape lattice_22|c3|both] [--anneal 0] [--seeds 4]
-                           [--no-host-route] [--out FILE] [--no-write]"""
+                           [--no-host-route] [--ab LABEL] [--out FILE] [--no-write]"""
 import argparse
 import json
 import os
@@ -111,7 +114,7 @@ def measure(name, graph, G, P, a):
             out["segments_flipped_share"] = float(st[1]) / float(st[0])
             out["spins_flipped_share"] = float(st[2]) / (4.0 * R * n)
             out["clusters_over_transverse"] = out["clusters_ms"][0] / out["transverse_ms"][0]
-            if not a.no_host_route:
+            if not a.no_host_route and not a.ab:
                 rnd = 1000
                 S0 = e.spins()
                 e.worldline_clusters(1, P, pb, round=rnd)
@@ -130,6 +133,7 @@ def measure(name, graph, G, P, a):
                 out["host_route_spins_differing"] = int(np.count_nonzero(S != want))
                 out["host_route_over_clusters"] = out["host_route_ms"] / out["clusters_ms"][0]
             res["gamma_%g" % gamma] = out
+        res["library"] = os.path.basename(sg._native.library_path())
     return res
 
 
@@ -172,6 +176,7 @@ if __name__ == "__main__":
     ap.add_argument("--anneal", type=int, default=0)
     ap.add_argument("--seeds", type=int, default=4)
     ap.add_argument("--no-host-route", action="store_true")
+    ap.add_argument("--ab", default="", metavar="LABEL")
     ap.add_argument("--no-write", action="store_true")
     ap.add_argument("--out", default=OUT)
     a = ap.parse_args()
@@ -190,7 +195,15 @@ if __name__ == "__main__":
         import bench
         shapes["c3"] = (bench.make_sparse_instance(10000, 16, 3), 16, 64)
     for name, (graph, G, P) in shapes.items():
-        doc[name] = measure(name, graph, G, P, a)
+        got = measure(name, graph, G, P, a)
+        if a.ab:
+            import ab_rounds
+            figures = {"gamma_%g_%s" % (gamma, key): got["gamma_%g" % gamma][key] for gamma in GAMMAS
+                       for key in ("clusters_ms", "clusters_8_ms", "transverse_ms")}
+            ab_rounds.append(doc, a.ab, name, figures, got["library"])
+        else:
+            del got["library"]
+            doc[name] = got
     if a.anneal > 0:
         doc["residual_energy_lattice_22"] = anneal(lattice(22, 1), a)
     print(json.dumps(doc, indent=1))

@@ -1225,228 +1225,6 @@ int sga_sweep(sga_engine *e, int n_sweeps, int site_mode, int arith, const doubl
     return c.finish(e->stream);
 }
 
-// ---- simulated quantum annealing: Trotter slices coupled in the sweep (sweep_transverse.hip) ----------------------
-// No state of its own: k_perp is staged in scratch slot 0 (where sga_sweep stages a schedule), and per sweep two
-// launches follow each other on the engine's stream, the even slices' half-sweep and the odd ones'.
-int sga_sweep_transverse(sga_engine *e, int n_sweeps, int n_slices, int arith, const float *k_perp) {
-    sga::TransverseProblem tp;
-    if (e) {
-        tp.n = e->n, tp.R_local = e->spins ? e->R : 0, tp.replica0 = e->replica0, tp.sstride = e->sstride;
-        tp.csr = e->csr, tp.tsp = e->tsp, tp.groups = e->groups, tp.ragged = e->ragged, tp.n_models = e->n_models;
-        tp.csr_acc = e->csr_acc;
-        tp.metropolis = e->rule == SGA_RULE_METROPOLIS;
-        tp.consistent_dE = e->consistent_dE;
-    }
-    if (k_perp && is_device_ptr(k_perp)) return fail(SGA_ERR_INVALID, "k_perp must be a host buffer");
-    bool invalid = true;
-    if (const char *why = sga::transverse_check(e != nullptr, tp, n_sweeps, n_slices, arith == SGA_ARITH_F64 || arith == SGA_ARITH_F32,
-                                                k_perp, &invalid))
-        return fail(invalid ? SGA_ERR_INVALID : SGA_ERR_UNSUPPORTED, why);
-    if (n_sweeps == 0) return SGA_OK;
-    if (e->opt_stale)
-        return fail(SGA_ERR_INVALID, std::string("option \"") + (e->opt_stale_key ? e->opt_stale_key : "?") +
-                                         "\" changed after it was read: set the couplings and initialise the replicas again");
-    if (!e->rowptr64 || !e->cv || !e->h || !e->best_spins) return fail(SGA_ERR_INVALID, "no couplings set");
-    HIPCHK(hipSetDevice(e->device));
-    hipStream_t st = e->stream;
-    const int G = e->R / n_slices;
-    // (a pageable host array: the copy has left the caller's buffer when the call returns)
-    HIPCHK(e->scratch[0].reserve((size_t)n_sweeps * (size_t)G * sizeof(float)));
-    float *d_k = static_cast<float *>(e->scratch[0].ptr);
-    HIPCHK(hipMemcpyAsync(d_k, k_perp, (size_t)n_sweeps * (size_t)G * sizeof(float), hipMemcpyHostToDevice, st));
-    sga::SweepArgs a{};
-    a.rowptr64 = e->rowptr64;
-    a.cv = e->cv;
-    a.h = e->h;
-    a.diag = e->diag;
-    a.spins = e->spins;
-    a.energy = e->energy;
-    a.best_energy = e->best_energy;
-    a.best_spins = e->best_spins;
-    a.n_accepted = e->n_acc;
-    a.rep_temp = e->rep_temp;
-    a.n = e->n;
-    a.sstride = e->sstride;
-    a.R = e->R;
-    a.n_sweeps = 1;
-    a.site_mode = SGA_SITE_RANDOM;
-    a.arith = arith;
-    a.rule = SGA_RULE_METROPOLIS;
-    a.csr_acc = e->csr_acc;
-    a.seed_lo = (uint32_t)e->seed;
-    a.seed_hi = (uint32_t)(e->seed >> 32);
-    a.replica0 = (uint32_t)e->replica0;
-    float *h_eff = nullptr;
-#if defined(SGA_TRANSVERSE_PREPASS) && SGA_TRANSVERSE_PREPASS  // (measurement builds: sweep_transverse.hip)
-    HIPCHK(e->scratch[1].reserve((size_t)e->R * (size_t)e->n * sizeof(float)));
-    h_eff = static_cast<float *>(e->scratch[1].ptr);
-#endif
-    e->fields_valid = false;  // (as after sga_set_spins: the next sweep seeds the cached fields again)
-    for (int kk = 0; kk < n_sweeps; ++kk) {
-        a.sweep0 = e->sweeps_done + (uint32_t)kk;
-        for (int parity = 0; parity < 2; ++parity) {
-            const sga::TransverseArgs t{d_k + (size_t)kk * (size_t)G, n_slices, parity, G * (n_slices / 2), h_eff};
-            const hipError_t le = sga::launch_sweep_transverse(a, t, st);
-            if (le != hipSuccess) (void)hipStreamSynchronize(st);
-            HIPCHK(le);
-        }
-    }
-    std::snprintf(e->last_kernel, sizeof(e->last_kernel), "%s", sga::last_sweep_kernel());
-    e->sweeps_done += (uint32_t)n_sweeps;
-    e->attempted += (long long)n_sweeps * e->n;
-    return SGA_OK;
-}
-
-// ---- simulated quantum annealing on dense couplings, carried by the cached local fields (sweep_transverse_clf.hip) --
-// The step of sga_sweep_transverse over the resident fields of the dense cached-field sweep: seeded through
-// ensure_fields where they are not valid, written back by every launch for the slices that moved -- they stay valid.
-int sga_sweep_transverse_dense(sga_engine *e, int n_sweeps, int n_slices, int arith, const float *k_perp) {
-    sga::TransverseDenseProblem tp;
-    if (e) {
-        tp.n = e->n, tp.R_local = e->spins ? e->R : 0, tp.replica0 = e->replica0, tp.sstride = e->sstride;
-        tp.csr = e->csr, tp.tsp = e->tsp, tp.groups = e->groups, tp.ragged = e->ragged, tp.n_models = e->n_models;
-        tp.clf_problem = (!e->csr && !e->implicit() && e->clf_problem && !e->clf_fx_bits) ? 1 : 0;
-        tp.clf_why = e->clf_why;
-        tp.field_bits = e->clf_bits;
-        tp.ldf = (e->ldj + 127) / 128 * 128;  // (as ensure_fields lays the rows out)
-        tp.metropolis = e->rule == SGA_RULE_METROPOLIS;
-    }
-    if (k_perp && is_device_ptr(k_perp)) return fail(SGA_ERR_INVALID, "k_perp must be a host buffer");
-    bool invalid = true;
-    if (const char *why = sga::transverse_dense_check(e != nullptr, tp, n_sweeps, n_slices,
-                                                      arith == SGA_ARITH_F64 || arith == SGA_ARITH_F32, k_perp, &invalid))
-        return fail(invalid ? SGA_ERR_INVALID : SGA_ERR_UNSUPPORTED, why);
-    if (n_sweeps == 0) return SGA_OK;
-    if (e->opt_stale)
-        return fail(SGA_ERR_INVALID, std::string("option \"") + (e->opt_stale_key ? e->opt_stale_key : "?") +
-                                         "\" changed after it was read: set the couplings and initialise the replicas again");
-    if (!e->J_packed || !e->h || !e->best_spins) return fail(SGA_ERR_INVALID, "no couplings set");
-    HIPCHK(hipSetDevice(e->device));
-    hipStream_t st = e->stream;
-    {
-        // (SGA_FIELD_CACHE_AUTO routes replica by replica: the fields of a replica on the row kernels are stale while
-        //  fields_valid stands for the others -- this call reads every slice's, so under AUTO it seeds them itself)
-        if (e->field_cache == SGA_FIELD_CACHE_AUTO) e->fields_valid = false;
-        const int rc = ensure_fields(e);
-        if (rc != SGA_OK) return rc;
-    }
-    const int G = e->R / n_slices, moving = G * (n_slices / 2);
-    // (a pageable host array: the copy has left the caller's buffer when the call returns)
-    HIPCHK(e->scratch[0].reserve((size_t)n_sweeps * (size_t)G * sizeof(float)));
-    float *d_k = static_cast<float *>(e->scratch[0].ptr);
-    HIPCHK(hipMemcpyAsync(d_k, k_perp, (size_t)n_sweeps * (size_t)G * sizeof(float), hipMemcpyHostToDevice, st));
-    sga::SweepArgs a{};
-    a.J = e->J_packed;
-    a.h = e->h;
-    a.spins = e->spins;
-    a.energy = e->energy;
-    a.best_energy = e->best_energy;
-    a.best_spins = e->best_spins;
-    a.n_accepted = e->n_acc;
-    a.rep_temp = e->rep_temp;
-    a.ldj = e->ldj;
-    a.n = e->n;
-    a.sstride = e->sstride;
-    a.R = e->R;
-    a.n_sweeps = 1;
-    a.site_mode = SGA_SITE_RANDOM;
-    a.arith = arith;
-    a.rule = SGA_RULE_METROPOLIS;
-    a.fields = e->fields;
-    a.ldf = e->ldf;
-    a.field_bits = e->clf_bits;
-    a.field_scale = e->clf_scale;
-    a.seed_lo = (uint32_t)e->seed;
-    a.seed_hi = (uint32_t)(e->seed >> 32);
-    a.replica0 = (uint32_t)e->replica0;
-    // waves per slice: option "clf_waves", else the cached-field sweep's choice over the workgroups of a launch, R / 2
-    const int waves = sga::sweep_clf_waves(e->ldj, e->want_i8, moving, e->cus, (int)e->opt[OPT_CLF_WAVES]);
-    for (int kk = 0; kk < n_sweeps; ++kk) {
-        a.sweep0 = e->sweeps_done + (uint32_t)kk;
-        for (int parity = 0; parity < 2; ++parity) {
-            const sga::TransverseDenseArgs t{d_k + (size_t)kk * (size_t)G, n_slices, parity, moving};
-            const hipError_t le = sga::launch_sweep_transverse_dense(a, t, e->want_i8, waves, st);
-            if (le != hipSuccess) {
-                (void)hipStreamSynchronize(st);
-                e->fields_valid = false;  // (a launch that did not go out: nothing is known about the sweep's state)
-            }
-            HIPCHK(le);
-        }
-    }
-    std::snprintf(e->last_kernel, sizeof(e->last_kernel), "%s", sga::last_sweep_kernel());
-    e->sweeps_done += (uint32_t)n_sweeps;
-    e->attempted += (long long)n_sweeps * e->n;
-    return SGA_OK;
-}
-
-// ---- world-line cluster updates along imaginary time (worldline_clusters.hip) --------------------------------------
-// No state of its own: the thresholds floor(p_bond 2^24), formed here in double, are staged in scratch slot 0 with the
-// group counts behind them; one launch serves the whole call.
-int sga_worldline_clusters(sga_engine *e, int n_sweeps, int n_slices, uint32_t round, const double *p_bond, int64_t *stats) {
-    sga::TransverseProblem tp;
-    if (e) {
-        tp.n = e->n, tp.R_local = e->spins ? e->R : 0, tp.replica0 = e->replica0, tp.sstride = e->sstride;
-        tp.csr = e->csr, tp.tsp = e->tsp, tp.groups = e->groups, tp.ragged = e->ragged, tp.n_models = e->n_models;
-        tp.csr_acc = e->csr_acc;
-        tp.consistent_dE = e->consistent_dE;
-    }
-    if (p_bond && is_device_ptr(p_bond)) return fail(SGA_ERR_INVALID, "p_bond must be a host buffer");
-    if (stats && is_device_ptr(stats)) return fail(SGA_ERR_INVALID, "stats must be a host buffer");
-    bool invalid = true;
-    if (const char *why = sga::worldline_check(e != nullptr, tp, n_sweeps, n_slices, p_bond, &invalid))
-        return fail(invalid ? SGA_ERR_INVALID : SGA_ERR_UNSUPPORTED, why);
-    if (n_sweeps == 0) return SGA_OK;
-    if (e->opt_stale)
-        return fail(SGA_ERR_INVALID, std::string("option \"") + (e->opt_stale_key ? e->opt_stale_key : "?") +
-                                         "\" changed after it was read: set the couplings and initialise the replicas again");
-    if (!e->rowptr64 || !e->cv || !e->h || !e->best_spins) return fail(SGA_ERR_INVALID, "no couplings set");
-    HIPCHK(hipSetDevice(e->device));
-    hipStream_t st = e->stream;
-    const int G = e->R / n_slices;
-    const size_t count = (size_t)n_sweeps * (size_t)G;
-    std::vector<uint32_t> thr(count);
-    for (size_t i = 0; i < count; ++i) thr[i] = sga::worldline_threshold(p_bond[i]);
-    const size_t thr_bytes = (count * sizeof(uint32_t) + 7) / 8 * 8, stats_bytes = (size_t)G * 3 * sizeof(long long);
-    HIPCHK(e->scratch[0].reserve(thr_bytes + stats_bytes));
-    unsigned char *base = static_cast<unsigned char *>(e->scratch[0].ptr);
-    // (a pageable host array: the copy has left the buffer when the call returns)
-    HIPCHK(hipMemcpyAsync(base, thr.data(), count * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    sga::SweepArgs a{};
-    a.rowptr64 = e->rowptr64;
-    a.cv = e->cv;
-    a.h = e->h;
-    a.spins = e->spins;
-    a.energy = e->energy;
-    a.best_energy = e->best_energy;
-    a.best_spins = e->best_spins;
-    a.rep_temp = e->rep_temp;
-    a.n = e->n;
-    a.sstride = e->sstride;
-    a.R = e->R;
-    a.csr_acc = e->csr_acc;
-    a.seed_lo = (uint32_t)e->seed;
-    a.seed_hi = (uint32_t)(e->seed >> 32);
-    a.replica0 = (uint32_t)e->replica0;
-    sga::WorldlineArgs w{};
-    w.thr = reinterpret_cast<const uint32_t *>(base);
-    w.stats = stats ? reinterpret_cast<long long *>(base + thr_bytes) : nullptr;
-    w.n_slices = n_slices;
-    w.n_sweeps = n_sweeps;
-    w.round = round;
-    e->fields_valid = false;  // (as after sga_set_spins: the next sweep seeds the cached fields again)
-    const hipError_t le = sga::launch_worldline_clusters(a, w, st);
-    if (le != hipSuccess) (void)hipStreamSynchronize(st);
-    HIPCHK(le);
-    std::snprintf(e->last_kernel, sizeof(e->last_kernel), "%s", sga::last_sweep_kernel());
-    if (stats) {
-        std::vector<long long> got((size_t)G * 3);
-        HIPCHK(hipMemcpyAsync(got.data(), w.stats, stats_bytes, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        for (size_t i = 0; i < got.size(); ++i) stats[i] += (int64_t)got[i];
-    }
-    return SGA_OK;
-}
-
 int sga_set_update_rule(sga_engine *e, int rule) {
     if (!e) return fail(SGA_ERR_INVALID, "engine is NULL");
     if (rule < SGA_RULE_METROPOLIS || rule > SGA_RULE_WOLFF)

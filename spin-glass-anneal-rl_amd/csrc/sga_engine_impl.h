@@ -10,6 +10,8 @@
 //                     the refusal reasons, pure functions of the set-time scan summaries (no HIP calls)
 //   sga_windows.cpp   the window forms of the dense sweep (row-shared, its tiles, sequential): admission as pure functions
 //                     of WindowTraits, the forms' state by lifetime (WindowState), their scratch and per-call plan
+//   sga_quantum.cpp   simulated quantum annealing: the two transverse sweeps and the world-line clusters over the pure half
+//                     (sga_quantum.h: slice geometry, admission rules)
 // The engine record is split by lifetime.  sga_engine derives from ProblemState (what the next sga_set_* must not see)
 // and ReplicaState (what the next sga_init_replicas must not see), so every member is still e->member; what survives
 // both stays in sga_engine itself.  A sub-record's defaults stand once, in its declaration: its reset releases the
@@ -29,6 +31,7 @@
 #include <vector>
 #include "sga.h"
 #include "sga_kernels.h"
+#include "sga_quantum.h"
 #include "sga_route.h"
 #include "sga_windows.h"
 

@@ -977,188 +977,6 @@ struct ClassOverlapArgs {
 };
 hipError_t launch_class_overlaps(const ClassOverlapArgs &a, hipStream_t st);
 
-// Simulated quantum annealing: Trotter slices coupled in the CSR sweep (sweep_transverse.hip; sga_sweep_transverse).
-// The local replicas are G = R_local / P contiguous groups of P slices; a launch is one HALF-SWEEP: the slices of one
-// parity each perform the n updates of sga_sweep's production stream under the field h_i + k (s_up[i] + s_dn[i]), the
-// other parity stands still and is only read.  One wave per moving slice, its int8 spins in LDS (sstride bytes a wave).
-constexpr size_t TRANSVERSE_LDS_BUDGET = 160 * 1024 - 256;
-inline int transverse_waves_per_block(int sstride) {  // 0: a slice's spins do not fit
-    if (sstride <= 0) return 0;
-    const size_t wpb = TRANSVERSE_LDS_BUDGET / (size_t)sstride;
-    return wpb > (size_t)CSR_WAVES_PER_BLOCK ? CSR_WAVES_PER_BLOCK : (int)wpb;
-}
-// What of an engine the admission rule reads.
-struct TransverseProblem {
-    int n = 0, R_local = 0, replica0 = 0, sstride = 0;
-    int csr = 0, tsp = 0, groups = 0, ragged = 0, n_models = 1;
-    int csr_acc = CSR_ACC_F64_CANON;
-    int metropolis = 1;     // the engine's rule is SGA_RULE_METROPOLIS
-    int consistent_dE = 1;  // J symmetric with zero diagonal: the rule's dE is the energy change
-};
-// The admission rule of sga_sweep_transverse, a pure function: nullptr where the call is served, else why not, with
-// *invalid = true for SGA_ERR_INVALID and false for SGA_ERR_UNSUPPORTED.  Every argument error comes first, so that a
-// wrong call is told so whatever the problem; k_perp: the caller's HOST array [n_sweeps][R_local / n_slices].
-inline const char *transverse_check(bool have_engine, const TransverseProblem &p, int n_sweeps, int n_slices, bool arith_ok,
-                                    const float *k_perp, bool *invalid) {
-    *invalid = true;
-    if (!have_engine) return "engine is NULL";
-    if (!k_perp) return "k_perp is NULL";
-    if (p.n <= 0) return "no couplings set";
-    if (p.R_local <= 0) return "no replicas (call sga_init_replicas)";
-    if (n_sweeps < 0) return "n_sweeps < 0";
-    if (!arith_ok) return "bad arith";
-    if (n_slices < 2) return "n_slices must be at least 2";
-    if (n_slices % 2 != 0) return "n_slices must be even (a moving slice never has a moving neighbour)";
-    if (p.R_local % n_slices != 0) return "n_slices must divide the number of local replicas";
-    if (p.replica0 % n_slices != 0) return "replica0 must be a multiple of n_slices (groups lie whole on a rank)";
-    const long long count = (long long)n_sweeps * (p.R_local / n_slices);
-    for (long long i = 0; i < count; ++i)
-        if (!(k_perp[i] - k_perp[i] == 0.0f)) return "k_perp holds a NaN or an infinite value";
-    *invalid = false;
-    if (p.tsp) return "transverse sweeps are not implemented for sga_set_tsp problems";
-    if (p.groups) return "transverse sweeps are not implemented for sga_set_groups / sga_set_groups_csr problems";
-    if (p.ragged) return "transverse sweeps are not implemented for ragged CSR batches";
-    if (p.n_models > 1) return "transverse sweeps are not implemented for many-model batches (shared or stacked)";
-    if (!p.csr) return "transverse sweeps need sparse (CSR) couplings: dense couplings are not served";
-    if (p.csr_acc != CSR_ACC_F32_TABLE && p.csr_acc != CSR_ACC_F32)
-        return "transverse sweeps need integer couplings with exact fp32 row sums (real-valued J needs the canonical order)";
-    if (!p.metropolis) return "transverse sweeps are implemented for the Metropolis rule only";
-    if (!p.consistent_dE) return "transverse sweeps need symmetric couplings with a zero diagonal";
-    if (transverse_waves_per_block(p.sstride) < 1) return "transverse sweeps: a slice's int8 spins do not fit LDS";
-    return nullptr;
-}
-struct TransverseArgs {
-    const float *k_perp;  // device [G]: this sweep's coupling per group
-    int n_slices;         // P
-    int parity;           // the slices p with p % 2 == parity move
-    int moving;           // G P / 2 waves
-    float *h_eff;         // measurement builds with -DSGA_TRANSVERSE_PREPASS=1 only: scratch [R][n]; null otherwise
-};
-// a: the arguments of one production sweep (n_sweeps = 1, sweep0 = the sweep's counter); reads a.rowptr64 / a.cv
-hipError_t launch_sweep_transverse(const SweepArgs &a, const TransverseArgs &t, hipStream_t st);
-
-// Simulated quantum annealing on DENSE couplings, carried by the cached local fields (sweep_transverse_clf.hip;
-// sga_sweep_transverse_dense).  The step and the groups are sga_sweep_transverse's; the form is the cached-field sweep's:
-// one workgroup per moving slice, LDS = fields [ldf] int16 | int32, the slice's spin bits, the two neighbour slices'
-// spin bits (n / 4 bytes), the decision slots.
-constexpr size_t TRANSVERSE_DENSE_SLOT_BYTES = 2 * 8 * 8 * sizeof(int);  // [2][CLF_MAX_WAVES][CLF_SLOT_INTS]
-__host__ __device__ constexpr long long transverse_dense_bits_bytes(int sstride) { return (sstride / 8 + 15) & ~15; }
-inline size_t transverse_dense_lds_bytes(long long ldf, int fbytes, int sstride) {
-    return (size_t)((ldf * fbytes + 15) & ~15ll) + 3 * (size_t)transverse_dense_bits_bytes(sstride) + TRANSVERSE_DENSE_SLOT_BYTES;
-}
-// What of an engine the admission rule reads.
-struct TransverseDenseProblem {
-    int n = 0, R_local = 0, replica0 = 0, sstride = 0;
-    int csr = 0, tsp = 0, groups = 0, ragged = 0, n_models = 1;
-    int clf_problem = 0;            // the one-model integer cached-field form admits the problem (set-time scan)
-    const char *clf_why = nullptr;  // ... where it does not: which condition failed
-    int field_bits = 16;            // 16 | 32: the width of the resident fields
-    long long ldf = 0;              // elements of a replica's field row
-    int metropolis = 1;             // the engine's rule is SGA_RULE_METROPOLIS
-};
-// The admission rule of sga_sweep_transverse_dense, a pure function as transverse_check is: nullptr where the call is
-// served, else why not, *invalid = true for SGA_ERR_INVALID and false for SGA_ERR_UNSUPPORTED.  The argument errors are
-// transverse_check's, in its words and its order, and come first.  The bound on n (include/sga.h) is the last test: the
-// fields, three rows of spin bits and the slots within TRANSVERSE_LDS_BUDGET -- 2.375 n bytes with int16 fields, 4.375 n
-// with int32 fields, plus padding and 512 bytes of slots.
-inline const char *transverse_dense_check(bool have_engine, const TransverseDenseProblem &p, int n_sweeps, int n_slices, bool arith_ok,
-                                          const float *k_perp, bool *invalid) {
-    *invalid = true;
-    if (!have_engine) return "engine is NULL";
-    if (!k_perp) return "k_perp is NULL";
-    if (p.n <= 0) return "no couplings set";
-    if (p.R_local <= 0) return "no replicas (call sga_init_replicas)";
-    if (n_sweeps < 0) return "n_sweeps < 0";
-    if (!arith_ok) return "bad arith";
-    if (n_slices < 2) return "n_slices must be at least 2";
-    if (n_slices % 2 != 0) return "n_slices must be even (a moving slice never has a moving neighbour)";
-    if (p.R_local % n_slices != 0) return "n_slices must divide the number of local replicas";
-    if (p.replica0 % n_slices != 0) return "replica0 must be a multiple of n_slices (groups lie whole on a rank)";
-    const long long count = (long long)n_sweeps * (p.R_local / n_slices);
-    for (long long i = 0; i < count; ++i)
-        if (!(k_perp[i] - k_perp[i] == 0.0f)) return "k_perp holds a NaN or an infinite value";
-    *invalid = false;
-    if (p.tsp) return "dense transverse sweeps are not implemented for sga_set_tsp problems";
-    if (p.groups) return "dense transverse sweeps are not implemented for sga_set_groups / sga_set_groups_csr problems";
-    if (p.ragged) return "dense transverse sweeps are not implemented for ragged CSR batches";
-    if (p.n_models > 1) return "dense transverse sweeps are not implemented for many-model batches (shared or stacked)";
-    if (p.csr) return "dense transverse sweeps need dense rows: the engine holds sparse (CSR) couplings, which sga_sweep_transverse serves";
-    if (!p.clf_problem)
-        return p.clf_why ? p.clf_why : "dense transverse sweeps need the integer cached-field form (integer symmetric J, zero diagonal)";
-    if (!p.metropolis) return "dense transverse sweeps are implemented for the Metropolis rule only";
-    if ((p.field_bits != 16 && p.field_bits != 32) || p.sstride <= 0 || p.ldf <= 0 ||
-        transverse_dense_lds_bytes(p.ldf, p.field_bits / 8, p.sstride) > TRANSVERSE_LDS_BUDGET)
-        return "dense transverse sweeps: a slice's fields, spin bits and neighbour bits do not fit LDS";
-    return nullptr;
-}
-struct TransverseDenseArgs {
-    const float *k_perp;  // device [G]: this sweep's coupling per group
-    int n_slices;         // P
-    int parity;           // the slices p with p % 2 == parity move
-    int moving;           // G P / 2 workgroups
-};
-// a: the arguments of one production sweep (n_sweeps = 1, sweep0 = the sweep's counter) with the resident fields (fields,
-// ldf, field_bits, field_scale) and the dense rows (J, ldj); the launch reads and writes the moving slices' fields
-hipError_t launch_sweep_transverse_dense(const SweepArgs &a, const TransverseDenseArgs &t, bool j_is_i8, int waves, hipStream_t st);
-
-// World-line cluster updates along imaginary time (worldline_clusters.hip; sga_worldline_clusters).  The groups are those
-// of the transverse sweep.  One wave per group, lane p = slice p; the group's spins as one word per site in LDS, bit p =
-// [s_p[i] < 0]: uint32_t for P <= 32, uint64_t beyond.  The budget is the transverse sweep's; behind the words lie 64
-// int32 accumulators of the segment sums.
-constexpr int WORLDLINE_MAX_SLICES = 64;
-constexpr size_t WORLDLINE_ACC_BYTES = 64 * sizeof(int32_t);
-inline int worldline_word_bytes(int n_slices) { return n_slices <= 32 ? 4 : 8; }
-// the words of a group: n rounded up to the 4 sites of a dword of int8 spins (the transposes move 4 sites a step)
-inline size_t worldline_lds_bytes(int n, int n_slices) {
-    return (((size_t)(n > 0 ? n : 0) + 3) / 4) * 4 * (size_t)worldline_word_bytes(n_slices) + WORLDLINE_ACC_BYTES;
-}
-inline int worldline_max_sites(int n_slices) {  // the largest n a group of n_slices slices is served at
-    return (int)((TRANSVERSE_LDS_BUDGET - WORLDLINE_ACC_BYTES) / (size_t)worldline_word_bytes(n_slices) / 4 * 4);
-}
-// The admission rule of sga_worldline_clusters, a pure function as transverse_check is: nullptr where the call is
-// served, else why not, *invalid = true for SGA_ERR_INVALID and false for SGA_ERR_UNSUPPORTED.  Argument errors come
-// first; p_bond: the caller's HOST array [n_sweeps][R_local / n_slices].  The engine's rule is not looked at: the call
-// brings its own.
-inline const char *worldline_check(bool have_engine, const TransverseProblem &p, int n_sweeps, int n_slices, const double *p_bond,
-                                   bool *invalid) {
-    *invalid = true;
-    if (!have_engine) return "engine is NULL";
-    if (!p_bond) return "p_bond is NULL";
-    if (p.n <= 0) return "no couplings set";
-    if (p.R_local <= 0) return "no replicas (call sga_init_replicas)";
-    if (n_sweeps < 0) return "n_sweeps < 0";
-    if (n_slices < 2) return "n_slices must be at least 2";
-    if (n_slices > WORLDLINE_MAX_SLICES) return "n_slices must be at most 64 (one lane of a wave per slice)";
-    if (p.R_local % n_slices != 0) return "n_slices must divide the number of local replicas";
-    if (p.replica0 % n_slices != 0) return "replica0 must be a multiple of n_slices (groups lie whole on a rank)";
-    const long long count = (long long)n_sweeps * (p.R_local / n_slices);
-    for (long long i = 0; i < count; ++i)
-        if (!(p_bond[i] >= 0.0 && p_bond[i] <= 1.0)) return "p_bond holds a NaN or a value outside [0, 1]";
-    *invalid = false;
-    if (p.tsp) return "world-line clusters are not implemented for sga_set_tsp problems";
-    if (p.groups) return "world-line clusters are not implemented for sga_set_groups / sga_set_groups_csr problems";
-    if (p.ragged) return "world-line clusters are not implemented for ragged CSR batches";
-    if (p.n_models > 1) return "world-line clusters are not implemented for many-model batches (shared or stacked)";
-    if (!p.csr) return "world-line clusters need sparse (CSR) couplings: dense couplings are not served";
-    if (p.csr_acc != CSR_ACC_F32_TABLE && p.csr_acc != CSR_ACC_F32)
-        return "world-line clusters need integer couplings with exact fp32 row sums (real-valued J needs the canonical order)";
-    if (!p.consistent_dE) return "world-line clusters need symmetric couplings with a zero diagonal";
-    if (transverse_waves_per_block(p.sstride) < 1) return "world-line clusters: a slice's int8 spins do not fit LDS";
-    if (p.n > worldline_max_sites(n_slices)) return "world-line clusters: a group's spin words do not fit LDS";
-    return nullptr;
-}
-// the threshold a bond's 24 random bits are held against: floor(p 2^24) in double, p = 1 -> 2^24 (every bond active)
-inline uint32_t worldline_threshold(double p_bond) { return (uint32_t)(long long)(p_bond * 16777216.0); }
-struct WorldlineArgs {
-    const uint32_t *thr;  // device [n_sweeps][G]
-    long long *stats;     // device [G][3], zeroed: segments formed, segments flipped, slice spins flipped (or null)
-    int n_slices;         // P
-    int n_sweeps;
-    uint32_t round;       // sweep kk draws at round + kk
-};
-// a: the engine's CSR view, replica state and seed (a.n_sweeps, a.sweep0 unused); one launch serves the whole call
-hipError_t launch_worldline_clusters(const SweepArgs &a, const WorldlineArgs &w, hipStream_t st);
-
 // operator-form PT exchange (cuda_kernels.py:415-443): decide sequentially, then permute rows
 hipError_t launch_op_exchange(float *spins, float *tmp_rows, float *energies, const float *temps,
                               const float *u, int32_t *src_of_pos, int *n_accepted,

@@ -1,0 +1,163 @@
+// sga_quantum.cpp -- simulated quantum annealing, the engine half (the pure half: sga_quantum.h): sga_sweep_transverse,
+// sga_sweep_transverse_dense and sga_worldline_clusters.  None keeps state of its own: the caller's host array is staged in
+// scratch slot 0 (where sga_sweep stages a schedule).  A sweep is two launches on the engine's stream, the even slices'
+// half-sweep and the odd ones'; one launch serves a whole clusters call.
+#include "sga_engine_impl.h"
+
+namespace {
+
+// What of an engine the admission rules read (no engine: the defaults, the rules say so first).
+sga::TrotterProblem trotter_problem_of(const sga_engine *e) {
+    sga::TrotterProblem p;
+    if (!e) return p;
+    p.n = e->n, p.R_local = e->spins ? e->R : 0, p.replica0 = e->replica0, p.sstride = e->sstride;
+    p.csr = e->csr, p.tsp = e->tsp, p.groups = e->groups, p.ragged = e->ragged, p.n_models = e->n_models;
+    p.metropolis = e->rule == SGA_RULE_METROPOLIS;
+    p.csr_acc = e->csr_acc;
+    p.consistent_dE = e->consistent_dE;
+    p.clf_problem = (!e->csr && !e->implicit() && e->clf_problem && !e->clf_fx_bits) ? 1 : 0;
+    p.clf_why = e->clf_why;
+    p.field_bits = e->clf_bits;
+    p.ldf = (e->ldj + 127) / 128 * 128;  // (as ensure_fields lays the rows out)
+    return p;
+}
+
+int refuse_device_ptr(const void *p, const char *name) {
+    return p && is_device_ptr(p) ? fail(SGA_ERR_INVALID, std::string(name) + " must be a host buffer") : SGA_OK;
+}
+
+// From the admission rule's answer to the device: run = true where the call goes on, else the returned code is the call's.
+int begin_call(sga_engine *e, const char *why, bool invalid, int n_sweeps, bool &run) {
+    run = false;
+    if (why) return fail(invalid ? SGA_ERR_INVALID : SGA_ERR_UNSUPPORTED, why);
+    if (n_sweeps == 0) return SGA_OK;
+    if (e->opt_stale)
+        return fail(SGA_ERR_INVALID, std::string("option \"") + (e->opt_stale_key ? e->opt_stale_key : "?") +
+                                         "\" changed after it was read: set the couplings and initialise the replicas again");
+    if ((e->csr ? !e->rowptr64 || !e->cv : !e->J_packed) || !e->h || !e->best_spins) return fail(SGA_ERR_INVALID, "no couplings set");
+    HIPCHK(hipSetDevice(e->device));
+    run = true;
+    return SGA_OK;
+}
+
+// The caller's host array into scratch slot 0, base; `behind` further bytes are reserved after it, 8-byte aligned, at
+// *behind_at.  (A pageable host array: the copy has left the buffer when the call returns.)
+int stage(sga_engine *e, const void *host, size_t bytes, unsigned char *&base, size_t behind = 0, unsigned char **behind_at = nullptr) {
+    const size_t padded = (bytes + 7) / 8 * 8;
+    HIPCHK(e->scratch[0].reserve(padded + behind));
+    base = static_cast<unsigned char *>(e->scratch[0].ptr);
+    if (behind_at) *behind_at = base + padded;
+    HIPCHK(hipMemcpyAsync(base, host, bytes, hipMemcpyHostToDevice, e->stream));
+    return SGA_OK;
+}
+
+// What every launch reads of the replicas and the random stream; the caller adds its view of the couplings.
+sga::SweepArgs replica_args_of(const sga_engine *e) {
+    sga::SweepArgs a{};
+    a.h = e->h, a.spins = e->spins, a.best_spins = e->best_spins;
+    a.energy = e->energy, a.best_energy = e->best_energy, a.rep_temp = e->rep_temp;
+    a.n = e->n, a.sstride = e->sstride, a.R = e->R;
+    a.seed_lo = (uint32_t)e->seed, a.seed_hi = (uint32_t)(e->seed >> 32), a.replica0 = (uint32_t)e->replica0;
+    return a;
+}
+
+// The n_sweeps sweeps of either sweep call: k_perp staged, then per sweep the two half-sweeps through `launch`.
+template <typename Launch>
+int run_half_sweeps(sga_engine *e, sga::SweepArgs a, int n_sweeps, int n_slices, int arith, const float *k_perp, Launch launch) {
+    const int G = e->R / n_slices;
+    unsigned char *d_k = nullptr;
+    const int rc = stage(e, k_perp, (size_t)n_sweeps * (size_t)G * sizeof(float), d_k);
+    if (rc != SGA_OK) return rc;
+    a.n_accepted = e->n_acc;
+    a.n_sweeps = 1, a.site_mode = SGA_SITE_RANDOM, a.arith = arith, a.rule = SGA_RULE_METROPOLIS;
+    for (int kk = 0; kk < n_sweeps; ++kk) {
+        a.sweep0 = e->sweeps_done + (uint32_t)kk;
+        for (int parity = 0; parity < 2; ++parity) {
+            const sga::TrotterLaunch t{reinterpret_cast<const float *>(d_k) + (size_t)kk * (size_t)G, n_slices, parity, G * (n_slices / 2)};
+            const hipError_t le = launch(a, t);
+            if (le != hipSuccess) {
+                (void)hipStreamSynchronize(e->stream);
+                e->fields_valid = false;  // (a launch that did not go out: nothing is known about the sweep's state)
+            }
+            HIPCHK(le);
+        }
+    }
+    std::snprintf(e->last_kernel, sizeof(e->last_kernel), "%s", sga::last_sweep_kernel());
+    e->sweeps_done += (uint32_t)n_sweeps;
+    e->attempted += (long long)n_sweeps * e->n;
+    return SGA_OK;
+}
+
+bool arith_ok(int arith) { return arith == SGA_ARITH_F64 || arith == SGA_ARITH_F32; }
+
+}  // namespace
+
+int sga_sweep_transverse(sga_engine *e, int n_sweeps, int n_slices, int arith, const float *k_perp) {
+    if (const int rc = refuse_device_ptr(k_perp, "k_perp")) return rc;
+    bool invalid = true, run = false;
+    const char *why = sga::transverse_check(e != nullptr, trotter_problem_of(e), n_sweeps, n_slices, arith_ok(arith), k_perp, &invalid);
+    const int rc = begin_call(e, why, invalid, n_sweeps, run);
+    if (!run) return rc;
+    sga::SweepArgs a = replica_args_of(e);
+    a.rowptr64 = e->rowptr64, a.cv = e->cv, a.diag = e->diag, a.csr_acc = e->csr_acc;
+    e->fields_valid = false;  // (as after sga_set_spins: the next sweep seeds the cached fields again)
+    return run_half_sweeps(e, a, n_sweeps, n_slices, arith, k_perp,
+                           [&](const sga::SweepArgs &s, const sga::TrotterLaunch &t) { return sga::launch_sweep_transverse(s, t, e->stream); });
+}
+
+// The resident fields of the dense cached-field sweep carry the step: seeded through ensure_fields where they are not
+// valid, written back by every launch for the slices that moved -- they stay valid.
+int sga_sweep_transverse_dense(sga_engine *e, int n_sweeps, int n_slices, int arith, const float *k_perp) {
+    if (const int rc = refuse_device_ptr(k_perp, "k_perp")) return rc;
+    bool invalid = true, run = false;
+    const char *why = sga::transverse_dense_check(e != nullptr, trotter_problem_of(e), n_sweeps, n_slices, arith_ok(arith), k_perp, &invalid);
+    int rc = begin_call(e, why, invalid, n_sweeps, run);
+    if (!run) return rc;
+    // (SGA_FIELD_CACHE_AUTO routes replica by replica: the fields of a replica on the row kernels are stale while
+    //  fields_valid stands for the others -- this call reads every slice's, so under AUTO it seeds them itself)
+    if (e->field_cache == SGA_FIELD_CACHE_AUTO) e->fields_valid = false;
+    rc = ensure_fields(e);
+    if (rc != SGA_OK) return rc;
+    sga::SweepArgs a = replica_args_of(e);
+    a.J = e->J_packed, a.ldj = e->ldj;
+    a.fields = e->fields, a.ldf = e->ldf, a.field_bits = e->clf_bits, a.field_scale = e->clf_scale;
+    // waves per slice: option "clf_waves", else the cached-field sweep's choice over the workgroups of a launch, R / 2
+    const int waves = sga::sweep_clf_waves(e->ldj, e->want_i8, e->R / 2, e->cus, (int)e->opt[OPT_CLF_WAVES]);
+    return run_half_sweeps(e, a, n_sweeps, n_slices, arith, k_perp, [&](const sga::SweepArgs &s, const sga::TrotterLaunch &t) {
+        return sga::launch_sweep_transverse_dense(s, t, e->want_i8, waves, e->stream);
+    });
+}
+
+// The thresholds floor(p_bond 2^24), formed here in double, are staged with the group counts behind them.
+int sga_worldline_clusters(sga_engine *e, int n_sweeps, int n_slices, uint32_t round, const double *p_bond, int64_t *stats) {
+    if (const int rc = refuse_device_ptr(p_bond, "p_bond")) return rc;
+    if (const int rc = refuse_device_ptr(stats, "stats")) return rc;
+    bool invalid = true, run = false;
+    const char *why = sga::worldline_check(e != nullptr, trotter_problem_of(e), n_sweeps, n_slices, p_bond, &invalid);
+    int rc = begin_call(e, why, invalid, n_sweeps, run);
+    if (!run) return rc;
+    hipStream_t st = e->stream;
+    const int G = e->R / n_slices;
+    std::vector<uint32_t> thr((size_t)n_sweeps * (size_t)G);
+    for (size_t i = 0; i < thr.size(); ++i) thr[i] = sga::worldline_threshold(p_bond[i]);
+    const size_t stats_bytes = (size_t)G * 3 * sizeof(long long);
+    unsigned char *base = nullptr, *d_stats = nullptr;
+    rc = stage(e, thr.data(), thr.size() * sizeof(uint32_t), base, stats_bytes, &d_stats);
+    if (rc != SGA_OK) return rc;
+    sga::SweepArgs a = replica_args_of(e);
+    a.rowptr64 = e->rowptr64, a.cv = e->cv, a.csr_acc = e->csr_acc;
+    const sga::WorldlineArgs w{reinterpret_cast<const uint32_t *>(base), stats ? reinterpret_cast<long long *>(d_stats) : nullptr,
+                               n_slices, n_sweeps, round};
+    e->fields_valid = false;  // (as after sga_set_spins: the next sweep seeds the cached fields again)
+    const hipError_t le = sga::launch_worldline_clusters(a, w, st);
+    if (le != hipSuccess) (void)hipStreamSynchronize(st);
+    HIPCHK(le);
+    std::snprintf(e->last_kernel, sizeof(e->last_kernel), "%s", sga::last_sweep_kernel());
+    if (stats) {
+        std::vector<long long> got((size_t)G * 3);
+        HIPCHK(hipMemcpyAsync(got.data(), w.stats, stats_bytes, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        for (size_t i = 0; i < got.size(); ++i) stats[i] += (int64_t)got[i];
+    }
+    return SGA_OK;
+}

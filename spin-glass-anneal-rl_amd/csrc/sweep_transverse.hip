@@ -21,46 +21,17 @@
 // on the 22^3 lattice, 8.51 against 8.22 on C3's graph -- slower, its index arithmetic and 12 spilled SGPRs costing more than
 // the divide and the exp of the uphill proposals.  Every proposal takes metropolis_accept.
 //
-// SGA_TRANSVERSE_PREPASS (a measurement build passes 1: profiles/transverse_timing.py --variant): instead of the two
-// neighbour bytes, a kernel before each half-sweep writes h_eff[r][i] for the moving slices into t.h_eff and the sweep
-// gathers one float.  Measured level with the byte loads on the 22^3 lattice (8.54 against 8.56 ms per sweep) and slower on
-// C3's graph (8.99 against 8.22), at R n floats of scratch and a third launch per half-sweep: the default
-// reads the bytes.
+// A pre-kernel variant (build macro SGA_TRANSVERSE_PREPASS) was measured and then removed: instead of the two neighbour
+// bytes, a kernel before each half-sweep wrote h_eff[r][i] for the moving slices and the sweep gathered one float.  Level
+// with the byte loads on the 22^3 lattice (8.54 against 8.56 ms per sweep) and slower on C3's graph (8.99 against 8.22), at
+// R n floats of scratch and a third launch per half-sweep.  The figures are kept in DESIGN.md 4.9 and under "variants" in
+// profiles/transverse.json.
+#include "sga_quantum.h"
 #include "sweep_common.h"
-
-#ifndef SGA_TRANSVERSE_PREPASS
-#define SGA_TRANSVERSE_PREPASS 0
-#endif
 
 namespace sga {
 
 namespace {
-
-// the moving slice of wave-uniform index m: its local replica and its two neighbours' rows
-struct SliceOf {
-    int g, r, up, dn;
-};
-__device__ __forceinline__ SliceOf slice_of(int m, int P, int parity) {
-    const int half = P >> 1;
-    SliceOf o;
-    o.g = m / half;
-    const int p = 2 * (m - o.g * half) + parity;
-    o.r = o.g * P + p;  // (replica0 % P == 0: p is the global slice index too)
-    o.up = o.g * P + (p + 1 == P ? 0 : p + 1);
-    o.dn = o.g * P + (p == 0 ? P - 1 : p - 1);
-    return o;
-}
-
-#if SGA_TRANSVERSE_PREPASS
-// h_eff[r][i] = h_i + k_g (s_up[i] + s_dn[i]) for the moving slices: one workgroup per slice
-__global__ void __launch_bounds__(256) transverse_fields_kernel(const SweepArgs a, const TransverseArgs q) {
-    const SliceOf sl = slice_of((int)blockIdx.x, q.n_slices, q.parity);
-    const int8_t *up = a.spins + (long long)sl.up * a.sstride, *dn = a.spins + (long long)sl.dn * a.sstride;
-    const float kp = q.k_perp[sl.g];
-    float *out = q.h_eff + (long long)sl.r * a.n;
-    for (int i = threadIdx.x; i < a.n; i += blockDim.x) out[i] = a.h[i] + kp * (float)((int)up[i] + (int)dn[i]);
-}
-#endif
 
 // dE of the rule for a flip of s_i under field h_site, as metropolis_accept forms it (Metropolis rule)
 __device__ __forceinline__ double rule_dE(int arith, float dot, int si, float h_site, float diag_site) {
@@ -71,7 +42,7 @@ __device__ __forceinline__ double rule_dE(int arith, float dot, int si, float h_
 }
 
 template <bool F32>  // SGA_ARITH_F32 (the rule in fp32, J_ii subtracted)
-__global__ void __launch_bounds__(64 * CSR_WAVES_PER_BLOCK) sweep_transverse_kernel(const SweepArgs a, const TransverseArgs q) {
+__global__ void __launch_bounds__(64 * CSR_WAVES_PER_BLOCK) sweep_transverse_kernel(const SweepArgs a, const TrotterLaunch q) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -79,15 +50,11 @@ __global__ void __launch_bounds__(64 * CSR_WAVES_PER_BLOCK) sweep_transverse_ker
     const int nw = blockDim.x >> 6;
     const int m = (int)blockIdx.x * nw + w;  // moving slice of this wave
     if (m >= q.moving) return;               // wave-uniform; no barriers
-    const SliceOf sl = slice_of(m, q.n_slices, q.parity);
+    const MovingSlice sl = moving_slice(m, q.n_slices, q.parity);
     const int r = sl.r;
-#if SGA_TRANSVERSE_PREPASS
-    const float *heff = q.h_eff + (long long)r * a.n;
-#else
     const int8_t *up = a.spins + (long long)sl.up * a.sstride;
     const int8_t *dn = a.spins + (long long)sl.dn * a.sstride;
     const float kp = *(const __attribute__((address_space(4))) float *)(q.k_perp + sl.g);
-#endif
     const int n = a.n;
     constexpr int arith = F32 ? SGA_ARITH_F32 : SGA_ARITH_F64;
     constexpr bool arith32 = F32;
@@ -108,11 +75,7 @@ __global__ void __launch_bounds__(64 * CSR_WAVES_PER_BLOCK) sweep_transverse_ker
         long long beg;
         int len;
         float h, d;
-#if SGA_TRANSVERSE_PREPASS
-        float h_eff;
-#else
         int nb;  // s_up[site] + s_dn[site]
-#endif
     };
     struct Head {  // the row's first 64 entries, one per lane: requested one update ahead, once the extent is back
         const int2 *row;
@@ -125,11 +88,7 @@ __global__ void __launch_bounds__(64 * CSR_WAVES_PER_BLOCK) sweep_transverse_ker
         o.len = (int)(sload_ll(a.rowptr64 + us + 1) - o.beg);
         o.h = sload_f(a.h + us);
         o.d = arith32 ? sload_f(a.diag + us) : 0.0f;
-#if SGA_TRANSVERSE_PREPASS
-        o.h_eff = heff[us];
-#else
         o.nb = (int)up[us] + (int)dn[us];
-#endif
         return o;
     };
     auto load_head = [&](const Extent &x) {
@@ -148,11 +107,7 @@ __global__ void __launch_bounds__(64 * CSR_WAVES_PER_BLOCK) sweep_transverse_ker
             acc += (lane < x.len - c0 ? __int_as_float(ent.y) : 0.0f) * (float)s[ent.x];
         }
         const float dot = wave_sum(acc);
-#if SGA_TRANSVERSE_PREPASS
-        const float h_eff = x.h_eff;
-#else
         const float h_eff = x.h + kp * (float)x.nb;  // the product is exact: one rounding
-#endif
         double dE_eff;
         const bool flip = metropolis_accept(SGA_RULE_METROPOLIS, arith, dot, si, h_eff, x.d, T, u, dE_eff);
         if (flip) {
@@ -220,7 +175,7 @@ __global__ void __launch_bounds__(64 * CSR_WAVES_PER_BLOCK) sweep_transverse_ker
 
 }  // namespace
 
-hipError_t launch_sweep_transverse(const SweepArgs &a, const TransverseArgs &t, hipStream_t st) {
+hipError_t launch_sweep_transverse(const SweepArgs &a, const TrotterLaunch &t, hipStream_t st) {
     const int waves = transverse_waves_per_block(a.sstride);
     if (waves < 1 || !a.rowptr64 || !a.cv || !a.h || !a.spins || !t.k_perp || t.n_slices < 2 || (t.n_slices & 1) ||
         a.R % t.n_slices != 0 || t.moving != a.R / 2 || a.sstride % 16 != 0 || (a.arith == SGA_ARITH_F32 && !a.diag))
@@ -231,14 +186,9 @@ hipError_t launch_sweep_transverse(const SweepArgs &a, const TransverseArgs &t, 
     const auto kern = a.arith == SGA_ARITH_F32 ? sweep_transverse_kernel<true> : sweep_transverse_kernel<false>;
     hipError_t e = ensure_lds_limit(reinterpret_cast<const void *>(kern), lds);
     if (e != hipSuccess) return e;
-#if SGA_TRANSVERSE_PREPASS
-    if (!t.h_eff) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(transverse_fields_kernel, dim3(t.moving), dim3(256), 0, st, a, t);
-#endif
     hipLaunchKernelGGL(kern, dim3((t.moving + waves - 1) / waves), dim3(64 * waves), lds, st, a, t);
-    note_sweep_kernel("sweep_transverse_kernel<%s, %d slices, parity %d%s> x %d slice(s) per workgroup",
-                      a.arith == SGA_ARITH_F32 ? "f32 rule" : "f64 rule", t.n_slices, t.parity,
-                      SGA_TRANSVERSE_PREPASS ? ", h_eff from a pre-kernel" : "", waves);
+    note_sweep_kernel("sweep_transverse_kernel<%s, %d slices, parity %d> x %d slice(s) per workgroup",
+                      a.arith == SGA_ARITH_F32 ? "f32 rule" : "f64 rule", t.n_slices, t.parity, waves);
     return hipGetLastError();
 }
 

@@ -21,29 +21,15 @@
 // On accept the tracked energy moves by the classical dE (h_i in place of h_eff), formed once for the accepted candidate.
 //
 // Not here: several accepts per round (sweep_clfb_impl.h) and the eight-wave tail logic of the classical sweep.
+#include "sga_quantum.h"
 #include "sweep_clf_impl.h"
 
 namespace sga {
 
 namespace {
 
-// the moving slice of workgroup m: its local replica and its two neighbours' rows (as in sweep_transverse.hip)
-struct DenseSliceOf {
-    int g, r, up, dn;
-};
-__device__ __forceinline__ DenseSliceOf dense_slice_of(int m, int P, int parity) {
-    const int half = P >> 1;
-    DenseSliceOf o;
-    o.g = m / half;
-    const int p = 2 * (m - o.g * half) + parity;
-    o.r = o.g * P + p;  // (replica0 % P == 0: p is the global slice index too)
-    o.up = o.g * P + (p + 1 == P ? 0 : p + 1);
-    o.dn = o.g * P + (p == 0 ? P - 1 : p - 1);
-    return o;
-}
-
 template <typename JT, typename FT, bool F32, int CLF_BATCH, bool TAIL>
-__global__ void __launch_bounds__(64 * CLF_MAX_WAVES) sweep_transverse_clf_kernel(const SweepArgs a, const TransverseDenseArgs q) {
+__global__ void __launch_bounds__(64 * CLF_MAX_WAVES) sweep_transverse_clf_kernel(const SweepArgs a, const TrotterLaunch q) {
     constexpr int EPL = 16 / (int)sizeof(JT), EPC = 64 * EPL;  // elements per lane / per 1-KiB chunk
     constexpr int FB = (int)sizeof(FT);
     constexpr int arith = F32 ? SGA_ARITH_F32 : SGA_ARITH_F64;
@@ -58,7 +44,7 @@ __global__ void __launch_bounds__(64 * CLF_MAX_WAVES) sweep_transverse_clf_kerne
     const int tid = threadIdx.x, lane = tid & 63;
     const int W = (int)(blockDim.x >> 6);
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const DenseSliceOf sl = dense_slice_of((int)blockIdx.x, q.n_slices, q.parity);
+    const MovingSlice sl = moving_slice((int)blockIdx.x, q.n_slices, q.parity);
     const int r = sl.r, n = a.n;
     const int sc = a.field_scale, sh = sc >> 1;  // scale 1 | 2: the division is a shift by 0 | 1
     const float kp = q.k_perp[sl.g];
@@ -311,13 +297,13 @@ __global__ void __launch_bounds__(64 * CLF_MAX_WAVES) sweep_transverse_clf_kerne
 }
 
 template <typename JT, typename FT, bool F32>
-hipError_t launch_tclf(const SweepArgs &a, const TransverseDenseArgs &t, int waves, hipStream_t st) {
+hipError_t launch_tclf(const SweepArgs &a, const TrotterLaunch &t, int waves, hipStream_t st) {
     const size_t lds = transverse_dense_lds_bytes(a.ldf, (int)sizeof(FT), a.sstride);
     if (lds > TRANSVERSE_LDS_BUDGET) return hipErrorInvalidValue;
     const int batch = sweep_clf_batch(a.ldj, sizeof(JT) == 1, waves);
     const int epc = sizeof(JT) == 1 ? 1024 : 256;
     const bool tail = (int)((a.ldj + epc - 1) / epc) > batch * waves;  // (never with 3 chunks per wave)
-    void (*kern)(const SweepArgs, const TransverseDenseArgs) =
+    void (*kern)(const SweepArgs, const TrotterLaunch) =
         batch == 3 ? sweep_transverse_clf_kernel<JT, FT, F32, 3, false>
         : tail     ? sweep_transverse_clf_kernel<JT, FT, F32, CLF_BATCH_MAX, true>
                    : sweep_transverse_clf_kernel<JT, FT, F32, CLF_BATCH_MAX, false>;
@@ -332,7 +318,7 @@ hipError_t launch_tclf(const SweepArgs &a, const TransverseDenseArgs &t, int wav
 
 }  // namespace
 
-hipError_t launch_sweep_transverse_dense(const SweepArgs &a, const TransverseDenseArgs &t, bool j_is_i8, int waves, hipStream_t st) {
+hipError_t launch_sweep_transverse_dense(const SweepArgs &a, const TrotterLaunch &t, bool j_is_i8, int waves, hipStream_t st) {
     if (waves < 1 || waves > CLF_MAX_WAVES || !a.J || !a.h || !a.spins || !a.best_spins || !a.fields || !t.k_perp ||
         (a.field_bits != 16 && a.field_bits != 32) || (a.field_scale != 1 && a.field_scale != 2) ||
         (a.ldf * (a.field_bits / 8)) % 16 != 0 || a.sstride % 32 != 0 || a.sstride < a.n || a.ldf < a.ldj || a.ldj < a.n ||

@@ -19,6 +19,7 @@
 // patched in.
 // The decision is the oracle's fp64 Metropolis rule on Phi = A + m h_i, taken on the head's lane with the head's uniform.
 // No load under a lane condition (lanes >= P run along on clamped indices and add zeros), no scratch.
+#include "sga_quantum.h"
 #include "sweep_common.h"
 
 namespace sga {
@@ -54,15 +55,15 @@ __global__ void __launch_bounds__(64) worldline_clusters_kernel(const SweepArgs 
     int *acc = reinterpret_cast<int *>(smem + (size_t)n4 * 4 * sizeof(Word));
     const bool mine = lane < P;
     const int p = mine ? lane : P - 1;  // lanes >= P run along on slice P - 1 and store nothing
-    const int r = g * P + p;
-    const int pn = p + 1 == P ? 0 : p + 1;
+    const int r = slice_row(g, P, p);
+    const int pn = ring_next(p, P);
     const unsigned long long ring = P == 64 ? ~0ull : (1ull << P) - 1ull;
 
     // the int8 rows -> words, 4 sites (one dword of each row) a step
     for (int c = lane; c < n4; c += 64) {
         Word w[4] = {0, 0, 0, 0};
         for (int pp = 0; pp < P; ++pp) {
-            const uint32_t d = reinterpret_cast<const uint32_t *>(a.spins + (long long)(g * P + pp) * a.sstride)[c];
+            const uint32_t d = reinterpret_cast<const uint32_t *>(a.spins + (long long)slice_row(g, P, pp) * a.sstride)[c];
 #pragma unroll
             for (int k = 0; k < 4; ++k) w[k] |= (Word)((d >> (8 * k + 7)) & 1u) << pp;
         }
@@ -174,7 +175,7 @@ __global__ void __launch_bounds__(64) worldline_clusters_kernel(const SweepArgs 
         while (todo) {  // wave-uniform
             const int pp = __builtin_ctzll(todo);
             todo &= todo - 1;
-            uint32_t *dst = reinterpret_cast<uint32_t *>(a.best_spins + (long long)(g * P + pp) * a.sstride);
+            uint32_t *dst = reinterpret_cast<uint32_t *>(a.best_spins + (long long)slice_row(g, P, pp) * a.sstride);
             for (int c = lane; c < n4; c += 64) {
                 const Word w[4] = {s[4 * c], s[4 * c + 1], s[4 * c + 2], s[4 * c + 3]};
                 dst[c] = spin_dword(w, pp, 4 * c, n);
@@ -185,7 +186,7 @@ __global__ void __launch_bounds__(64) worldline_clusters_kernel(const SweepArgs 
     for (int c = lane; c < n4; c += 64) {
         const Word w[4] = {s[4 * c], s[4 * c + 1], s[4 * c + 2], s[4 * c + 3]};
         for (int pp = 0; pp < P; ++pp)
-            reinterpret_cast<uint32_t *>(a.spins + (long long)(g * P + pp) * a.sstride)[c] = spin_dword(w, pp, 4 * c, n);
+            reinterpret_cast<uint32_t *>(a.spins + (long long)slice_row(g, P, pp) * a.sstride)[c] = spin_dword(w, pp, 4 * c, n);
     }
     if (mine) {
         a.energy[r] = E;

@@ -577,14 +577,17 @@ class AnnealEngine:
         return {"energy_trace": et, "accept_trace": at, "dE_trace": dt}
 
     # ------------------------------------------------------------------ simulated quantum annealing
+    def _trotter_groups(self, P: int) -> int:
+        """R / P groups of P slices -- for a P the engine will refuse, 1: any well-formed array then does, so that the
+        refusal and its reason are the engine's."""
+        return self.R // P if P >= 1 and self.R > 0 and self.R % P == 0 else 1
+
     def sweep_transverse(self, n_sweeps: int, n_slices: int, k_perp, arith: int = N.ARITH_F64):
         """n_sweeps sweeps of the replicas as R / n_slices groups of n_slices Trotter slices (sga_sweep_transverse): per
         sweep the even slices move under h + k (s_up + s_dn), then the odd ones; the tracked energies stay classical.
         k_perp: a scalar, [n_sweeps] or [n_sweeps, R / n_slices] (see quantum.transverse_coupling).  A problem the step
         does not serve raises AnnealingError with the engine's reason."""
-        P = int(n_slices)
-        # (a P the engine will refuse: any well-formed array, so that the refusal and its reason are the engine's)
-        G = self.R // P if P >= 1 and self.R > 0 and self.R % P == 0 else 1
+        G = self._trotter_groups(int(n_slices))
         k = transverse_k_perp(k_perp, n_sweeps, G)
         N.check(self._lib.sga_sweep_transverse(self._h, int(n_sweeps), int(n_slices), int(arith), k.ctypes.data_as(C.c_void_p)),
                 "sga_sweep_transverse")
@@ -595,9 +598,7 @@ class AnnealEngine:
         where they are not valid and stay valid for a cached sweep() after it.  k_perp as in sweep_transverse.  Serves
         integer symmetric J with a zero diagonal and h in multiples of 1/2 (set_dense); any other problem raises
         AnnealingError with the engine's reason."""
-        P = int(n_slices)
-        # (a P the engine will refuse: any well-formed array, so that the refusal and its reason are the engine's)
-        G = self.R // P if P >= 1 and self.R > 0 and self.R % P == 0 else 1
+        G = self._trotter_groups(int(n_slices))
         k = transverse_k_perp(k_perp, n_sweeps, G)
         N.check(self._lib.sga_sweep_transverse_dense(self._h, int(n_sweeps), int(n_slices), int(arith), k.ctypes.data_as(C.c_void_p)),
                 "sga_sweep_transverse_dense")
@@ -611,8 +612,7 @@ class AnnealEngine:
         int64 [R / n_slices, 3]: segments formed, segments flipped, slice spins flipped.  A problem the step does not
         serve raises AnnealingError with the engine's reason."""
         P = int(n_slices)
-        # (a P the engine will refuse: any well-formed array, so that the refusal and its reason are the engine's)
-        G = self.R // P if P >= 1 and self.R > 0 and self.R % P == 0 else 1
+        G = self._trotter_groups(P)
         b = worldline_p_bond(p_bond, n_sweeps, G)
         rnd = self.counters()[0] if round is None else int(round)
         out = np.zeros((G, 3), np.int64) if stats else None

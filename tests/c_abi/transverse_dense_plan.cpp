@@ -1,4 +1,4 @@
-// transverse_dense_plan.cpp -- the admission rule of sga_sweep_transverse_dense (sga_kernels.h: transverse_dense_check,
+// transverse_dense_plan.cpp -- the admission rule of sga_sweep_transverse_dense (sga_quantum.h: transverse_dense_check,
 // transverse_dense_lds_bytes), pure host arithmetic: no device call.
 //   transverse_dense_plan lds ldf fbytes sstride      the LDS budget, then the bytes a slice of that shape takes
 //   transverse_dense_plan check have_engine have_k n R_local replica0 sstride csr tsp groups ragged n_models clf_problem
@@ -11,7 +11,7 @@
 #include <cstring>
 #include <vector>
 
-#include "sga_kernels.h"
+#include "sga_quantum.h"
 
 int main(int argc, char **argv) {
     if (argc == 5 && !std::strcmp(argv[1], "lds")) {
@@ -21,7 +21,7 @@ int main(int argc, char **argv) {
     }
     if (argc >= 22 && !std::strcmp(argv[1], "check")) {
         auto I = [&](int i) { return std::atoi(argv[i]); };
-        sga::TransverseDenseProblem p;
+        sga::TrotterProblem p;
         p.n = I(4), p.R_local = I(5), p.replica0 = I(6), p.sstride = I(7);
         p.csr = I(8), p.tsp = I(9), p.groups = I(10), p.ragged = I(11), p.n_models = I(12);
         p.clf_problem = I(13);

@@ -1,6 +1,8 @@
-// transverse_plan.cpp -- the admission rule of sga_sweep_transverse (sga_kernels.h: transverse_check,
+// transverse_plan.cpp -- the admission rule of sga_sweep_transverse (sga_quantum.h: transverse_check,
 // transverse_waves_per_block), pure host arithmetic: no device call.
 //   transverse_plan waves sstride...   the LDS budget, then the waves per workgroup of each spin stride
+//   transverse_plan slices P parity    the slice geometry of a half-sweep (moving_slice): per moving index m of three groups
+//                                      of P slices, "g r up dn" -- its group, its row and its two neighbours' rows
 //   transverse_plan check have_engine have_k n R_local replica0 sstride csr tsp groups ragged n_models csr_acc metropolis
 //                         consistent_dE n_sweeps n_slices arith_ok k...
 //                                      "ok", "invalid: <why>" or "unsupported: <why>"; k: the values of k_perp, the last
@@ -11,7 +13,7 @@
 #include <cstring>
 #include <vector>
 
-#include "sga_kernels.h"
+#include "sga_quantum.h"
 
 int main(int argc, char **argv) {
     if (argc >= 2 && !std::strcmp(argv[1], "waves")) {
@@ -19,9 +21,17 @@ int main(int argc, char **argv) {
         for (int a = 2; a < argc; ++a) std::printf("%d\n", sga::transverse_waves_per_block(std::atoi(argv[a])));
         return 0;
     }
+    if (argc == 4 && !std::strcmp(argv[1], "slices")) {
+        const int P = std::atoi(argv[2]), parity = std::atoi(argv[3]);
+        for (int m = 0; m < 3 * (P / 2); ++m) {  // three groups
+            const sga::MovingSlice s = sga::moving_slice(m, P, parity);
+            std::printf("%d %d %d %d\n", s.g, s.r, s.up, s.dn);
+        }
+        return 0;
+    }
     if (argc >= 20 && !std::strcmp(argv[1], "check")) {
         auto I = [&](int i) { return std::atoi(argv[i]); };
-        sga::TransverseProblem p;
+        sga::TrotterProblem p;
         p.n = I(4), p.R_local = I(5), p.replica0 = I(6), p.sstride = I(7);
         p.csr = I(8), p.tsp = I(9), p.groups = I(10), p.ragged = I(11), p.n_models = I(12);
         p.csr_acc = I(13), p.metropolis = I(14), p.consistent_dE = I(15);

@@ -1,4 +1,4 @@
-// worldline_plan.cpp -- the admission rule of sga_worldline_clusters (sga_kernels.h: worldline_check,
+// worldline_plan.cpp -- the admission rule of sga_worldline_clusters (sga_quantum.h: worldline_check,
 // worldline_max_sites, worldline_lds_bytes, worldline_threshold), pure host arithmetic: no device call.
 //   worldline_plan sites P...          the LDS budget, then per P: word bytes, the largest n served, the LDS bytes at that n
 //   worldline_plan thr p...            the threshold of each bond probability
@@ -11,7 +11,7 @@
 #include <cstring>
 #include <vector>
 
-#include "sga_kernels.h"
+#include "sga_quantum.h"
 
 int main(int argc, char **argv) {
     if (argc >= 2 && !std::strcmp(argv[1], "sites")) {
@@ -28,7 +28,7 @@ int main(int argc, char **argv) {
     }
     if (argc >= 18 && !std::strcmp(argv[1], "check")) {
         auto I = [&](int i) { return std::atoi(argv[i]); };
-        sga::TransverseProblem p;
+        sga::TrotterProblem p;
         p.n = I(4), p.R_local = I(5), p.replica0 = I(6), p.sstride = I(7);
         p.csr = I(8), p.tsp = I(9), p.groups = I(10), p.ragged = I(11), p.n_models = I(12);
         p.csr_acc = I(13), p.metropolis = I(14), p.consistent_dE = I(15);
