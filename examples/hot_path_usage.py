@@ -223,6 +223,14 @@ def sk_glass_by_simulated_quantum_annealing(n=1024):
     sqa = quantum_annealer.simulated_quantum_anneal(model, n_trotter_slices=32, quantum_monte_carlo=True)
     print(f"SQA, dense +-1 couplings on {n} spins, 4 instances x 32 slices: best energy {sqa.best_energy:.1f} "
           f"({sqa.best_energy / n ** 1.5:.4f} n^1.5) in {sqa.total_time:.3f} s")
+    # the cluster move beside the dense sweep (AnnealEngine.worldline_clusters_dense): decided on the same cached fields,
+    # which stay valid between the two calls -- a coupling row is read only where a segment of slices flips
+    with_clusters = QuantumFluctuations(base_annealer=annealer, transverse_field_schedule="linear_decrease",
+                                        initial_field_strength=3.0 * np.sqrt(n), final_field_strength=0.05,
+                                        n_instances=4, dense_couplings=True, dense_worldline_clusters=True)
+    sqa_c = with_clusters.simulated_quantum_anneal(model, n_trotter_slices=32)
+    print(f"   with world-line clusters after every sweep: best energy {sqa_c.best_energy:.1f} in {sqa_c.total_time:.3f} s; "
+          f"segments formed / flipped, slice spins flipped: {with_clusters.last.cluster_statistics.tolist()}")
 
 
 def travelling_salesman(n_cities=12):

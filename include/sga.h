@@ -80,7 +80,7 @@ typedef struct sga_engine sga_engine;
 int sga_create(int device, sga_engine **out);
 void sga_destroy(sga_engine *e);
 const char *sga_last_error(void);
-int sga_version(void);  /* 3100: sga_sweep_transverse_dense (simulated quantum annealing on dense couplings: the step of sga_sweep_transverse carried by the cached local fields, a coupling row read on accept only, csrc/sweep_transverse_clf.hip; no option, no engine member); 3000: sga_worldline_clusters (simulated quantum annealing: Swendsen-Wang clusters along imaginary time at one site, flipped under the classical field, one launch per call, csrc/worldline_clusters.hip; domain word 4; no option, no engine member); 2900: sga_sweep_transverse (simulated quantum annealing: the Trotter slices of one instance coupled in the CSR sweep, two half-sweeps per sweep, csrc/sweep_transverse.hip; no option, no engine member); 2800: sga_get_class_overlaps / sga_accumulate_ladder_class_overlaps (the overlap between two replicas resolved by a class of sites, first and second moments per temperature summed on the device, csrc/class_overlaps.hip; read only, no engine state, no option); 2700: sga_get_link_count / sga_get_pair_overlaps / sga_accumulate_ladder_overlaps (spin and link overlaps between pairs of replicas, histogrammed per temperature on the device, csrc/pair_overlaps.hip; read only, no engine state, no option); 2600: sga_resample (the resampling step of population annealing, csrc/resample.hip); 2500: sga_cluster_move_pairs / sga_cluster_move_ladders (isoenergetic cluster moves between replica copies on sparse couplings, csrc/cluster_moves.hip; no engine state, no option); 2400: sga_set_replica_groups / sga_get_replica_groups; 2300: sga_get_magnetizations / sga_get_overlaps / sga_get_overlaps_with (replica observables on the device: the exact integer product of int8 spin rows on the matrix cores, csrc/observables.hip; read only, no engine state); 2200: the row-shared fields in tiles take a plan of their own, one launch per sweep (csrc/sweep_dense_rs.hip, rs_tile_plan_kernel; no change of interface or results); 2100: sga_set_sequential_windows / sga_get_sequential_windows (SGA_SITE_SEQUENTIAL sweeps in windows, the fields of every replica on the matrix cores; csrc/sweep_dense_seq.hip); 2000: the row-shared windows (option "row_shared") serve SGA_RULE_GLAUBER and SGA_RULE_HEAT_BATH too ("rule=glauber" / "rule=heat-bath" in sga_describe and sga_get_last_kernel; the window sga_autotune picks holds for the rule it was timed under); 1900: options "row_shared_fields" and "row_shared_tile_sites" (row-shared fields in tiles of sites, sign-only rows); 1800: option "row_shared_grid", sga_route_query.rs_grid; 1700: sga_set_csr_shared (one set of CSR rows, many field vectors: every one-wave-per-replica CSR form for such batches), sga_route_query.shared_j on SGA_ROUTE_CSR queries; 1600: sga_set_dense_shared (one coupling matrix, many field vectors; row-shared windows, bit-planes and the matrix-core pass for such batches), sga_route_query.shared_j; 1500: sga_get_scan_summary, and sga_set_dense / sga_set_dense_batch / sga_set_csr / sga_set_csr64 / sga_set_csr_batch refuse a NaN or +-Inf in J or h (SGA_ERR_INVALID, "non-finite"); 1400: option "batch_fixed_point" (fixed-point cached local fields for many-model dense batches); 1300: options "ragged_field_cache" and "clf_fixed_point" together (fixed-point cached local fields for ragged CSR batches); 1200: sga_set_groups_csr (group couplings plus a stored sparse remainder); 1100: option "ragged_field_cache" (cached local fields for ragged CSR batches); 1000: sga_set_groups */
+int sga_version(void);  /* 3200: sga_worldline_clusters_dense (world-line cluster updates on dense couplings: the step of sga_worldline_clusters decided on the resident fields of every slice, a coupling row read only where a segment flips, the fields kept valid, csrc/worldline_clusters_dense.hip; no option, no engine member); 3100: sga_sweep_transverse_dense (simulated quantum annealing on dense couplings: the step of sga_sweep_transverse carried by the cached local fields, a coupling row read on accept only, csrc/sweep_transverse_clf.hip; no option, no engine member); 3000: sga_worldline_clusters (simulated quantum annealing: Swendsen-Wang clusters along imaginary time at one site, flipped under the classical field, one launch per call, csrc/worldline_clusters.hip; domain word 4; no option, no engine member); 2900: sga_sweep_transverse (simulated quantum annealing: the Trotter slices of one instance coupled in the CSR sweep, two half-sweeps per sweep, csrc/sweep_transverse.hip; no option, no engine member); 2800: sga_get_class_overlaps / sga_accumulate_ladder_class_overlaps (the overlap between two replicas resolved by a class of sites, first and second moments per temperature summed on the device, csrc/class_overlaps.hip; read only, no engine state, no option); 2700: sga_get_link_count / sga_get_pair_overlaps / sga_accumulate_ladder_overlaps (spin and link overlaps between pairs of replicas, histogrammed per temperature on the device, csrc/pair_overlaps.hip; read only, no engine state, no option); 2600: sga_resample (the resampling step of population annealing, csrc/resample.hip); 2500: sga_cluster_move_pairs / sga_cluster_move_ladders (isoenergetic cluster moves between replica copies on sparse couplings, csrc/cluster_moves.hip; no engine state, no option); 2400: sga_set_replica_groups / sga_get_replica_groups; 2300: sga_get_magnetizations / sga_get_overlaps / sga_get_overlaps_with (replica observables on the device: the exact integer product of int8 spin rows on the matrix cores, csrc/observables.hip; read only, no engine state); 2200: the row-shared fields in tiles take a plan of their own, one launch per sweep (csrc/sweep_dense_rs.hip, rs_tile_plan_kernel; no change of interface or results); 2100: sga_set_sequential_windows / sga_get_sequential_windows (SGA_SITE_SEQUENTIAL sweeps in windows, the fields of every replica on the matrix cores; csrc/sweep_dense_seq.hip); 2000: the row-shared windows (option "row_shared") serve SGA_RULE_GLAUBER and SGA_RULE_HEAT_BATH too ("rule=glauber" / "rule=heat-bath" in sga_describe and sga_get_last_kernel; the window sga_autotune picks holds for the rule it was timed under); 1900: options "row_shared_fields" and "row_shared_tile_sites" (row-shared fields in tiles of sites, sign-only rows); 1800: option "row_shared_grid", sga_route_query.rs_grid; 1700: sga_set_csr_shared (one set of CSR rows, many field vectors: every one-wave-per-replica CSR form for such batches), sga_route_query.shared_j on SGA_ROUTE_CSR queries; 1600: sga_set_dense_shared (one coupling matrix, many field vectors; row-shared windows, bit-planes and the matrix-core pass for such batches), sga_route_query.shared_j; 1500: sga_get_scan_summary, and sga_set_dense / sga_set_dense_batch / sga_set_csr / sga_set_csr64 / sga_set_csr_batch refuse a NaN or +-Inf in J or h (SGA_ERR_INVALID, "non-finite"); 1400: option "batch_fixed_point" (fixed-point cached local fields for many-model dense batches); 1300: options "ragged_field_cache" and "clf_fixed_point" together (fixed-point cached local fields for ragged CSR batches); 1200: sga_set_groups_csr (group couplings plus a stored sparse remainder); 1100: option "ragged_field_cache" (cached local fields for ragged CSR batches); 1000: sga_set_groups */
 /* Run on an existing HIP stream (e.g. torch.cuda.current_stream().cuda_stream); NULL = the
  * engine's own stream (default). */
 int sga_set_stream(sga_engine *e, void *hip_stream);
@@ -632,7 +632,7 @@ int sga_sweep_transverse(sga_engine *e, int n_sweeps, int n_slices, int arith /*
  *   (ragged, shared and stacked), CSR engines -- a sparse matrix that sga_set_dense kept as CSR included: they are
  *   sga_sweep_transverse's --, a dense problem the integer cached-field form does not take (real-valued J, a non-zero
  *   diagonal, asymmetric J, a bound of 2^24 or more: the set-time scan's reason), rules other than Metropolis, a slice
- *   beyond LDS.  World-line clusters on dense couplings are not served.
+ *   beyond LDS.  World-line clusters on dense couplings are sga_worldline_clusters_dense's.
  *   The launches (two per sweep) show in sga_get_last_kernel; sga_enable_timing does not bracket them. */
 int sga_sweep_transverse_dense(sga_engine *e, int n_sweeps, int n_slices, int arith /* SGA_ARITH_* */,
                                const float *k_perp /* host [n_sweeps][R_local / n_slices] */);
@@ -688,6 +688,36 @@ int sga_sweep_transverse_dense(sga_engine *e, int n_sweeps, int n_slices, int ar
 int sga_worldline_clusters(sga_engine *e, int n_sweeps, int n_slices, uint32_t round,
                            const double *p_bond /* host [n_sweeps][R_local / n_slices], each in [0, 1] */,
                            int64_t *stats       /* host [R_local / n_slices][3] or NULL: += segments formed, segments flipped, slice spins flipped */);
+
+/* ---- world-line cluster updates on dense couplings (version >= 3200; csrc/worldline_clusters_dense.hip) ----------------
+ * The step of sga_worldline_clusters, word for word as stated above -- groups, 2 <= P <= 64, thresholds, typewriter order,
+ * one Philox block per slice and site at (i, round + kk, q_p, 4), segments from the bonds, A in int32, the fp64 Metropolis
+ * rule with the head's uniform at T_g whatever the engine's rule, the tracked energy of a flipped slice moved by
+ * 2 sigma ((double)dot_p + (double)h_i), bests after the n sites of each sweep, 2 sweeps at `round` = 1 + 1, n_sweeps == 0 a
+ * no-op, no counter, temperature, slot map or statistic moved -- on ONE dense matrix.  The row sum is read from the resident
+ * fields F = scale (J s + h) of the cached-local-field sweep, dot_p = (F_p[i] - scale h_i) / scale, an exact integer: a
+ * coupling row is read only for a site where a segment flips.  By construction the same integer couplings held as CSR
+ * under sga_worldline_clusters walk the same chain bit for bit.
+ *   The differences:
+ *   Fields.  The cached local fields are NOT marked for re-seeding.  The call seeds them where they are not valid (the pass
+ *   the cached sga_sweep uses; under SGA_FIELD_CACHE_AUTO every time, as sga_sweep_transverse_dense does), updates them for
+ *   every flip and leaves them valid: sga_sweep_transverse_dense, this call, sga_sweep_transverse_dense run without seeding
+ *   in between.  A launch that did not go out leaves them marked for re-seeding.  The field cache mode itself is not
+ *   looked at: the call is its own opt-in.
+ *   Served: one dense model (sga_set_dense) that the integer cached-field form admits -- integer symmetric J with a zero
+ *   diagonal, h in multiples of 1/2, row bound below 2^24 (so |dot| < 2^24 and |A| < 2^30 at P = 64); int8 and fp32 rows,
+ *   int16 and int32 fields.  The kernel keeps nothing of size n in LDS (the fields stay in HBM / L2): no bound on n beyond
+ *   the memory of the fields.  Option "clf_waves" sets the waves per group; 0 leaves one wave per 1-KiB chunk of a row,
+ *   eight at the most.
+ *   SGA_ERR_INVALID, first and with the engine unchanged: exactly what sga_worldline_clusters reports so, in the same words.
+ *   SGA_ERR_UNSUPPORTED, with the reason in sga_last_error: sga_set_tsp, sga_set_groups / sga_set_groups_csr, batches
+ *   (ragged, shared and stacked), CSR engines -- a sparse matrix that sga_set_dense kept as CSR included: they are
+ *   sga_worldline_clusters' --, a dense problem the integer cached-field form does not take (the set-time scan's reason),
+ *   fields of another width (the fixed-point forms).  The update rule is not looked at.
+ *   The launch (one per call) shows in sga_get_last_kernel; sga_enable_timing does not bracket it. */
+int sga_worldline_clusters_dense(sga_engine *e, int n_sweeps, int n_slices, uint32_t round,
+                                 const double *p_bond /* host [n_sweeps][R_local / n_slices], each in [0, 1] */,
+                                 int64_t *stats       /* host [R_local / n_slices][3] or NULL: += as sga_worldline_clusters */);
 
 /* Stateless operator form of CUDAKernelManager.parallel_tempering_exchange_optimized
  * (annealing/cuda_kernels.py:326-369, fallback :415-443): sequential adjacent pairs, fp32,

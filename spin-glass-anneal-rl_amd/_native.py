@@ -70,6 +70,7 @@ SYMBOLS = [
     ("sga_sweep_transverse", _i, [_p, _i, _i, _i, _p]),
     ("sga_sweep_transverse_dense", _i, [_p, _i, _i, _i, _p]),
     ("sga_worldline_clusters", _i, [_p, _i, _i, _u32, _p, _p]),
+    ("sga_worldline_clusters_dense", _i, [_p, _i, _i, _u32, _p, _p]),
     ("sga_local_fields", _i, [_p, _i, _p, _i, _p]),
     ("sga_flip", _i, [_p, _i, _i, C.POINTER(_d)]),
     ("sga_update", _i, [_p, _i, _i, _d, C.c_float, _i, C.POINTER(_i), C.POINTER(_d)]),

@@ -347,6 +347,10 @@ extern "C" {
 
 const char *sga_last_error(void) { return g_last_error.c_str(); }
 // The ABI version, one line per step:
+//   3200:    + sga_worldline_clusters_dense: the step of sga_worldline_clusters on dense couplings, decided on the resident
+//            fields of every slice -- one workgroup per group, blocks of sites decided in registers, a coupling row read
+//            only where a segment flips, the fields kept valid (worldline_clusters_dense.hip; the admission rule in
+//            sga_quantum.h); no option, no engine member
 //   3100:    + sga_sweep_transverse_dense: the step of sga_sweep_transverse on dense couplings, carried by the cached local
 //            fields -- one workgroup per moving slice, a coupling row read on accept only, the fields kept valid
 //            (sweep_transverse_clf.hip; the admission rule in sga_kernels.h); no option, no engine member
@@ -400,7 +404,7 @@ const char *sga_last_error(void) { return g_last_error.c_str(); }
 //   600:     + sga_set_csr_batch / sga_get_batch_model (ragged CSR batches)
 //   round 5: + sga_explain_route / sga_get_route_query, sga_get_last_kernel, sga_get_autotune_table, ladder-local
 //            sga_exchange
-int sga_version(void) { return 3100; }
+int sga_version(void) { return 3200; }
 
 int sga_create(int device, sga_engine **out) {
     if (!out) return fail(SGA_ERR_INVALID, "out is NULL");

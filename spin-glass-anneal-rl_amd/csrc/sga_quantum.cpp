@@ -1,5 +1,5 @@
 // sga_quantum.cpp -- simulated quantum annealing, the engine half (the pure half: sga_quantum.h): sga_sweep_transverse,
-// sga_sweep_transverse_dense and sga_worldline_clusters.  None keeps state of its own: the caller's host array is staged in
+// sga_sweep_transverse_dense, sga_worldline_clusters and sga_worldline_clusters_dense.  None keeps state of its own: the caller's host array is staged in
 // scratch slot 0 (where sga_sweep stages a schedule).  A sweep is two launches on the engine's stream, the even slices'
 // half-sweep and the odd ones'; one launch serves a whole clusters call.
 #include "sga_engine_impl.h"
@@ -151,6 +151,49 @@ int sga_worldline_clusters(sga_engine *e, int n_sweeps, int n_slices, uint32_t r
     e->fields_valid = false;  // (as after sga_set_spins: the next sweep seeds the cached fields again)
     const hipError_t le = sga::launch_worldline_clusters(a, w, st);
     if (le != hipSuccess) (void)hipStreamSynchronize(st);
+    HIPCHK(le);
+    std::snprintf(e->last_kernel, sizeof(e->last_kernel), "%s", sga::last_sweep_kernel());
+    if (stats) {
+        std::vector<long long> got((size_t)G * 3);
+        HIPCHK(hipMemcpyAsync(got.data(), w.stats, stats_bytes, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        for (size_t i = 0; i < got.size(); ++i) stats[i] += (int64_t)got[i];
+    }
+    return SGA_OK;
+}
+
+// The step of sga_worldline_clusters on the dense rows, decided on the resident fields of every slice: seeded through
+// ensure_fields where they are not valid, updated by the launch for every flip -- they stay valid.
+int sga_worldline_clusters_dense(sga_engine *e, int n_sweeps, int n_slices, uint32_t round, const double *p_bond, int64_t *stats) {
+    if (const int rc = refuse_device_ptr(p_bond, "p_bond")) return rc;
+    if (const int rc = refuse_device_ptr(stats, "stats")) return rc;
+    bool invalid = true, run = false;
+    const char *why = sga::worldline_dense_check(e != nullptr, trotter_problem_of(e), n_sweeps, n_slices, p_bond, &invalid);
+    int rc = begin_call(e, why, invalid, n_sweeps, run);
+    if (!run) return rc;
+    // (SGA_FIELD_CACHE_AUTO: some replicas' fields may be stale while fields_valid stands, as in sga_sweep_transverse_dense)
+    if (e->field_cache == SGA_FIELD_CACHE_AUTO) e->fields_valid = false;
+    rc = ensure_fields(e);
+    if (rc != SGA_OK) return rc;
+    hipStream_t st = e->stream;
+    const int G = e->R / n_slices;
+    std::vector<uint32_t> thr((size_t)n_sweeps * (size_t)G);
+    for (size_t i = 0; i < thr.size(); ++i) thr[i] = sga::worldline_threshold(p_bond[i]);
+    const size_t stats_bytes = (size_t)G * 3 * sizeof(long long);
+    unsigned char *base = nullptr, *d_stats = nullptr;
+    rc = stage(e, thr.data(), thr.size() * sizeof(uint32_t), base, stats_bytes, &d_stats);
+    if (rc != SGA_OK) return rc;
+    sga::SweepArgs a = replica_args_of(e);
+    a.J = e->J_packed, a.ldj = e->ldj;
+    a.fields = e->fields, a.ldf = e->ldf, a.field_bits = e->clf_bits, a.field_scale = e->clf_scale;
+    const sga::WorldlineArgs w{reinterpret_cast<const uint32_t *>(base), stats ? reinterpret_cast<long long *>(d_stats) : nullptr,
+                               n_slices, n_sweeps, round};
+    const int waves = sga::worldline_dense_waves(e->ldj, e->want_i8, (int)e->opt[OPT_CLF_WAVES]);
+    const hipError_t le = sga::launch_worldline_clusters_dense(a, w, e->want_i8, waves, st);
+    if (le != hipSuccess) {
+        (void)hipStreamSynchronize(st);
+        e->fields_valid = false;  // (a launch that did not go out: nothing is known about the fields)
+    }
     HIPCHK(le);
     std::snprintf(e->last_kernel, sizeof(e->last_kernel), "%s", sga::last_sweep_kernel());
     if (stats) {

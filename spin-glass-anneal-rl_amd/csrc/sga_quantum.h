@@ -1,8 +1,9 @@
-// sga_quantum.h -- simulated quantum annealing: the Trotter-slice geometry and the admission rules of its three calls,
-// sga_sweep_transverse (sweep_transverse.hip), sga_sweep_transverse_dense (sweep_transverse_clf.hip) and
-// sga_worldline_clusters (worldline_clusters.hip).  The pure half: no sga_engine and no HIP call, so tests/c_abi/
-// transverse_plan.cpp, transverse_dense_plan.cpp and worldline_plan.cpp pin it on the CPU.  The engine half is
-// sga_quantum.cpp: it reads an engine into a TrotterProblem and runs the calls.
+// sga_quantum.h -- simulated quantum annealing: the Trotter-slice geometry and the admission rules of its four calls,
+// sga_sweep_transverse (sweep_transverse.hip), sga_sweep_transverse_dense (sweep_transverse_clf.hip),
+// sga_worldline_clusters (worldline_clusters.hip) and sga_worldline_clusters_dense (worldline_clusters_dense.hip).  The pure
+// half: no sga_engine and no HIP call, so tests/c_abi/transverse_plan.cpp, transverse_dense_plan.cpp, worldline_plan.cpp and
+// worldline_dense_plan.cpp pin it on the CPU.  The engine half is sga_quantum.cpp: it reads an engine into a TrotterProblem
+// and runs the calls.
 //
 // The local replicas are G = R_local / P contiguous groups of P slices, slice p of group g in row g P + p; replica0 is a
 // multiple of P, so p is the global slice index too.  The slices of a group form a ring.
@@ -79,7 +80,7 @@ struct TrotterProblem {
     int field_bits = 16;            // 16 | 32: the width of the resident fields
     long long ldf = 0;              // elements of a replica's field row
 };
-// The argument errors of a call (SGA_ERR_INVALID), the same ladder for all three: they come first, so that a wrong call is
+// The argument errors of a call (SGA_ERR_INVALID), the same ladder for all four: they come first, so that a wrong call is
 // told so whatever the problem.  What differs between the calls comes in: the text for a NULL array, whether arith was
 // acceptable (a call without one: true), the call's own rule on n_slices as its verdict, and the test of a value.
 // values: the caller's HOST array [n_sweeps][R_local / n_slices].
@@ -123,7 +124,7 @@ inline const char *trotter_kind_refused(const TrotterProblem &p, const char *wha
     return text;
 }
 
-// The three admission rules, pure functions: nullptr where the call is served, else why not, with *invalid = true for
+// The four admission rules, pure functions: nullptr where the call is served, else why not, with *invalid = true for
 // SGA_ERR_INVALID and false for SGA_ERR_UNSUPPORTED.  The argument errors, the kinds, then what the call's own kernel asks.
 inline const char *transverse_check(bool have_engine, const TrotterProblem &p, int n_sweeps, int n_slices, bool arith_ok,
                                     const float *k_perp, bool *invalid) {
@@ -156,14 +157,15 @@ inline const char *transverse_dense_check(bool have_engine, const TrotterProblem
     return nullptr;
 }
 // (p_bond in [0, 1]; at most one lane of a wave per slice; the engine's rule is not looked at)
+inline const char *worldline_argument_error(bool have_engine, const TrotterProblem &p, int n_sweeps, int n_slices, const double *p_bond) {
+    return trotter_argument_error(have_engine, p, n_sweeps, n_slices, p_bond, "p_bond is NULL", true,
+                                  n_slices > WORLDLINE_MAX_SLICES ? "n_slices must be at most 64 (one lane of a wave per slice)" : nullptr,
+                                  [](double b) { return b >= 0.0 && b <= 1.0; }, "p_bond holds a NaN or a value outside [0, 1]");
+}
 inline const char *worldline_check(bool have_engine, const TrotterProblem &p, int n_sweeps, int n_slices, const double *p_bond,
                                    bool *invalid) {
     *invalid = true;
-    if (const char *why = trotter_argument_error(
-            have_engine, p, n_sweeps, n_slices, p_bond, "p_bond is NULL", true,
-            n_slices > WORLDLINE_MAX_SLICES ? "n_slices must be at most 64 (one lane of a wave per slice)" : nullptr,
-            [](double b) { return b >= 0.0 && b <= 1.0; }, "p_bond holds a NaN or a value outside [0, 1]"))
-        return why;
+    if (const char *why = worldline_argument_error(have_engine, p, n_sweeps, n_slices, p_bond)) return why;
     *invalid = false;
     if (const char *why = trotter_kind_refused(p, "world-line clusters")) return why;
     if (!p.csr) return "world-line clusters need sparse (CSR) couplings: dense couplings are not served";
@@ -172,6 +174,19 @@ inline const char *worldline_check(bool have_engine, const TrotterProblem &p, in
     if (!p.consistent_dE) return "world-line clusters need symmetric couplings with a zero diagonal";
     if (transverse_waves_per_block(p.sstride) < 1) return "world-line clusters: a slice's int8 spins do not fit LDS";
     if (p.n > worldline_max_sites(n_slices)) return "world-line clusters: a group's spin words do not fit LDS";
+    return nullptr;
+}
+// (the argument ladder of worldline_check; the rule is not looked at; the kernel keeps nothing of size n in LDS: no bound on n)
+inline const char *worldline_dense_check(bool have_engine, const TrotterProblem &p, int n_sweeps, int n_slices, const double *p_bond,
+                                         bool *invalid) {
+    *invalid = true;
+    if (const char *why = worldline_argument_error(have_engine, p, n_sweeps, n_slices, p_bond)) return why;
+    *invalid = false;
+    if (const char *why = trotter_kind_refused(p, "dense world-line clusters")) return why;
+    if (p.csr) return "dense world-line clusters need dense rows: the engine holds sparse (CSR) couplings, which sga_worldline_clusters serves";
+    if (!p.clf_problem)
+        return p.clf_why ? p.clf_why : "dense world-line clusters need the integer cached-field form (integer symmetric J, zero diagonal)";
+    if (p.field_bits != 16 && p.field_bits != 32) return "dense world-line clusters: the resident fields are neither int16 nor int32";
     return nullptr;
 }
 
@@ -197,6 +212,10 @@ struct WorldlineArgs {
 };
 // a: the engine's CSR view, replica state and seed (a.n_sweeps, a.sweep0 unused); one launch serves the whole call
 hipError_t launch_worldline_clusters(const SweepArgs &a, const WorldlineArgs &w, hipStream_t st);
+// ... on the dense rows (J, ldj) and the resident fields (fields, ldf, field_bits, field_scale) of every slice, which the
+// launch reads and writes: they stay valid.  waves per group: worldline_dense_waves (forced: option "clf_waves", 0 = none)
+int worldline_dense_waves(long long ldj, bool j_is_i8, int forced);
+hipError_t launch_worldline_clusters_dense(const SweepArgs &a, const WorldlineArgs &w, bool j_is_i8, int waves, hipStream_t st);
 
 }  // namespace sga
 

@@ -620,6 +620,22 @@ class AnnealEngine:
                                                  out.ctypes.data_as(C.c_void_p) if stats else None), "sga_worldline_clusters")
         return out
 
+    def worldline_clusters_dense(self, n_sweeps: int, n_slices: int, p_bond, round: Optional[int] = None, stats: bool = False):
+        """worldline_clusters on one dense matrix (sga_worldline_clusters_dense): the same step, decided on the cached local
+        fields of every slice -- a coupling row is read only where a segment flips, and the fields are seeded where they
+        are not valid and stay valid: sweep_transverse_dense, this call, sweep_transverse_dense run without seeding in
+        between.  Arguments and the returned statistics as in worldline_clusters.  Serves what sweep_transverse_dense
+        serves, whatever the update rule; any other problem raises AnnealingError with the engine's reason."""
+        P = int(n_slices)
+        G = self._trotter_groups(P)
+        b = worldline_p_bond(p_bond, n_sweeps, G)
+        rnd = self.counters()[0] if round is None else int(round)
+        out = np.zeros((G, 3), np.int64) if stats else None
+        N.check(self._lib.sga_worldline_clusters_dense(self._h, int(n_sweeps), P, rnd & 0xFFFFFFFF, b.ctypes.data_as(C.c_void_p),
+                                                       out.ctypes.data_as(C.c_void_p) if stats else None),
+                "sga_worldline_clusters_dense")
+        return out
+
     # single-site operators (the reference's per-spin API)
     def local_fields(self, r: int, sites) -> np.ndarray:
         idx = np.ascontiguousarray(np.atleast_1d(sites), dtype=np.int32)

@@ -22,7 +22,9 @@ Dense couplings (SK glasses, number partitioning, dense QUBO encodings) are an o
 SimulatedQuantumAnnealingConfig(dense_couplings=True) hands the model to the engine as one dense matrix with the field
 cache on and sweeps through AnnealEngine.sweep_transverse_dense (sga_sweep_transverse_dense) -- the same step, a slice's
 local fields resident in LDS and a coupling row read on accept only.  It serves integer symmetric J with a zero diagonal
-and h in multiples of 1/2; world-line clusters are not served there.
+and h in multiples of 1/2.  The cluster move beside it is a flag of its own, dense_worldline_clusters=True: every
+cluster_interval-th dense sweep is followed by AnnealEngine.worldline_clusters_dense (sga_worldline_clusters_dense), the
+same cluster step decided on the same cached fields, which stay valid between the two calls.
 """
 import time
 from dataclasses import dataclass, field
@@ -116,6 +118,8 @@ class SimulatedQuantumAnnealingConfig:
     cluster_interval: int = 1             # ... every cluster_interval-th of them
     dense_couplings: bool = False         # hand the model over as one dense matrix, field cache on, and sweep through
     #                                       sga_sweep_transverse_dense (False: the model's own form, CSR rows served only)
+    dense_worldline_clusters: bool = False  # with dense_couplings: follow every cluster_interval-th dense sweep with one
+    #                                         cluster sweep on the cached fields (sga_worldline_clusters_dense)
 
     def __post_init__(self):
         self.check()
@@ -137,6 +141,17 @@ class SimulatedQuantumAnnealingConfig:
             raise ConfigurationError("world-line clusters serve at most 64 slices (one lane of a wave per slice)")
         if not isinstance(self.dense_couplings, (bool, np.bool_)):
             raise ConfigurationError("dense_couplings must be True or False")
+        if not isinstance(self.dense_worldline_clusters, (bool, np.bool_)):
+            raise ConfigurationError("dense_worldline_clusters must be True or False")
+        if self.dense_worldline_clusters:
+            self.check_dense_clusters()
+
+    def check_dense_clusters(self):
+        """What dense_worldline_clusters asks of the rest of the configuration."""
+        if not self.dense_couplings:
+            raise ConfigurationError("dense_worldline_clusters needs dense_couplings=True (sparse models: worldline_clusters)")
+        if self.n_slices > 64:
+            raise ConfigurationError("world-line clusters serve at most 64 slices (one lane of a wave per slice)")
 
     def couplings(self) -> np.ndarray:
         """float32 [n_sweeps]: k_perp per sweep."""
@@ -161,35 +176,41 @@ class SimulatedQuantumAnnealing:
     def _sweeps(self, eng, k0: int, ns: int, k, clusters: bool, dense: bool = False):
         """Transverse sweeps k0 ... k0 + ns - 1; with clusters, every cluster_interval-th one (counted over the run) is
         followed by one cluster sweep at its k_perp, drawn at round = the sweep's index.  dense: the engine holds dense
-        rows, the sweeps are sweep_transverse_dense's (never with clusters)."""
+        rows, the sweeps are sweep_transverse_dense's and the cluster sweeps worldline_clusters_dense's."""
         cfg = self.config
         P = int(cfg.n_slices)
-        if dense:
-            eng.sweep_transverse_dense(ns, P, k[k0:k0 + ns])
-            return
+        sweep = eng.sweep_transverse_dense if dense else eng.sweep_transverse
         if not clusters:
-            eng.sweep_transverse(ns, P, k[k0:k0 + ns])
+            sweep(ns, P, k[k0:k0 + ns])
             return
+        move = eng.worldline_clusters_dense if dense else eng.worldline_clusters
         every, slice_T = int(cfg.cluster_interval), P * float(cfg.temperature)
         t = k0
         while t < k0 + ns:
             stop = min(((t // every) + 1) * every, k0 + ns)  # the sweeps up to and with the next one that is followed
-            eng.sweep_transverse(stop - t, P, k[t:stop])
+            sweep(stop - t, P, k[t:stop])
             if stop % every == 0:
-                self.cluster_statistics += eng.worldline_clusters(1, P, bond_probability(float(k[stop - 1]), slice_T),
-                                                                  round=stop - 1, stats=True).sum(axis=0)
+                self.cluster_statistics += move(1, P, bond_probability(float(k[stop - 1]), slice_T), round=stop - 1,
+                                                stats=True).sum(axis=0)
             t = stop
 
-    def run(self, model: IsingModel, measure_overlaps: bool = False, worldline_clusters: Optional[bool] = None) -> AnnealingResult:
-        """worldline_clusters: None = the configuration's; False is the transverse sweeps alone."""
+    def run(self, model: IsingModel, measure_overlaps: bool = False, worldline_clusters: Optional[bool] = None,
+            dense_worldline_clusters: Optional[bool] = None) -> AnnealingResult:
+        """worldline_clusters: None = the configuration's; False is the transverse sweeps alone.  dense_worldline_clusters
+        likewise: the cluster move of a run with dense_couplings=True."""
         cfg = self.config
         cfg.check()
         clusters = bool(cfg.worldline_clusters if worldline_clusters is None else worldline_clusters)
+        dense_clusters = bool(cfg.dense_worldline_clusters if dense_worldline_clusters is None else dense_worldline_clusters)
         if clusters and cfg.n_slices > 64:
             raise ConfigurationError("world-line clusters serve at most 64 slices (one lane of a wave per slice)")
         if cfg.dense_couplings and clusters:
             raise AnnealingError("world-line clusters are not served on dense couplings: sga_worldline_clusters reads CSR rows "
-                                 "(run with dense_couplings=False on a sparse model, or without worldline_clusters)")
+                                 "(run with dense_worldline_clusters=True, which decides the move on the cached fields, with "
+                                 "dense_couplings=False on a sparse model, or without worldline_clusters)")
+        if dense_clusters:
+            cfg.check_dense_clusters()
+            clusters = True  # (from here on: a cluster sweep follows, by whichever call the engine's rows are served)
         self.cluster_statistics = np.zeros(3, np.int64) if clusters else None
         P, G, n = int(cfg.n_slices), int(cfg.n_instances), model.n_spins
         R = P * G
@@ -243,11 +264,12 @@ class QuantumFluctuations:
 
     def __init__(self, base_annealer=None, transverse_field_schedule: str = "linear_decrease", initial_field_strength: float = 5.0,
                  final_field_strength: float = 0.01, n_instances: int = 1, worldline_clusters: bool = False,
-                 dense_couplings: bool = False):
+                 dense_couplings: bool = False, dense_worldline_clusters: bool = False):
         self.base_annealer = base_annealer
         self.n_instances = int(n_instances)
         self.worldline_clusters = bool(worldline_clusters)
         self.dense_couplings = bool(dense_couplings)
+        self.dense_worldline_clusters = bool(dense_worldline_clusters)
         self.field = TransverseField(transverse_field_schedule, float(initial_field_strength),
                                      min(float(final_field_strength), float(initial_field_strength)))
         self.last = None  # the SimulatedQuantumAnnealing of the last call (final_energies, slice_overlaps)
@@ -262,7 +284,7 @@ class QuantumFluctuations:
             n_slices=int(P), n_instances=self.n_instances, temperature=float(T), n_sweeps=int(self._base("n_sweeps", 1000)),
             transverse_field=tf, seed=self._base("random_seed", None), measure_interval=int(self._base("record_interval", 10)),
             device_index=self._base("device_index", None), worldline_clusters=self.worldline_clusters,
-            dense_couplings=self.dense_couplings)
+            dense_couplings=self.dense_couplings, dense_worldline_clusters=self.dense_worldline_clusters)
         self.last = SimulatedQuantumAnnealing(cfg)
         return self.last.run(model)
 
