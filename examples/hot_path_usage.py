@@ -208,6 +208,15 @@ def frustrated_lattice_by_simulated_quantum_annealing(L=8):
     sqa_clusters = with_clusters.simulated_quantum_anneal(model, n_trotter_slices=32)
     print(f"SQA, {L}^3 +-J lattice, 32 slices: best energy {sqa.best_energy:.1f} in {sqa.total_time:.3f} s; "
           f"PIMC at Gamma = 3, 64 slices: best energy {pimc.best_energy:.1f}")
+    # equilibrium path-integral Monte Carlo on a ladder of transverse fields: 8 instances at 0.93 ... 1.07 Gamma, an exchange
+    # between neighbouring instances after every 5th sweep (AnnealEngine.exchange_transverse, decided on the device on the
+    # broken time links of AnnealEngine.time_links); <sigma^x> of every instance comes from the same counts
+    ladder = QuantumFluctuations(base_annealer=annealer, transverse_field_schedule="constant", initial_field_strength=1.0,
+                                 n_instances=8, field_ladder=np.geomspace(0.93, 1.07, 8).tolist(), field_exchange_interval=5)
+    pt = ladder.path_integral_mc(model, imaginary_time_slices=32, quantum_temperature=0.05)
+    attempts, accepts = ladder.last.field_exchange_statistics
+    print(f"   PIMC on a ladder of 8 fields: best energy {pt.best_energy:.1f}; exchanges accepted per pair "
+          f"{np.round(accepts / np.maximum(attempts, 1), 2).tolist()}; <sigma^x> {np.round(ladder.last.transverse_magnetization, 3).tolist()}")
 
 
 def sk_glass_by_simulated_quantum_annealing(n=1024):

@@ -80,7 +80,7 @@ typedef struct sga_engine sga_engine;
 int sga_create(int device, sga_engine **out);
 void sga_destroy(sga_engine *e);
 const char *sga_last_error(void);
-int sga_version(void);  /* 3200: sga_worldline_clusters_dense (world-line cluster updates on dense couplings: the step of sga_worldline_clusters decided on the resident fields of every slice, a coupling row read only where a segment flips, the fields kept valid, csrc/worldline_clusters_dense.hip; no option, no engine member); 3100: sga_sweep_transverse_dense (simulated quantum annealing on dense couplings: the step of sga_sweep_transverse carried by the cached local fields, a coupling row read on accept only, csrc/sweep_transverse_clf.hip; no option, no engine member); 3000: sga_worldline_clusters (simulated quantum annealing: Swendsen-Wang clusters along imaginary time at one site, flipped under the classical field, one launch per call, csrc/worldline_clusters.hip; domain word 4; no option, no engine member); 2900: sga_sweep_transverse (simulated quantum annealing: the Trotter slices of one instance coupled in the CSR sweep, two half-sweeps per sweep, csrc/sweep_transverse.hip; no option, no engine member); 2800: sga_get_class_overlaps / sga_accumulate_ladder_class_overlaps (the overlap between two replicas resolved by a class of sites, first and second moments per temperature summed on the device, csrc/class_overlaps.hip; read only, no engine state, no option); 2700: sga_get_link_count / sga_get_pair_overlaps / sga_accumulate_ladder_overlaps (spin and link overlaps between pairs of replicas, histogrammed per temperature on the device, csrc/pair_overlaps.hip; read only, no engine state, no option); 2600: sga_resample (the resampling step of population annealing, csrc/resample.hip); 2500: sga_cluster_move_pairs / sga_cluster_move_ladders (isoenergetic cluster moves between replica copies on sparse couplings, csrc/cluster_moves.hip; no engine state, no option); 2400: sga_set_replica_groups / sga_get_replica_groups; 2300: sga_get_magnetizations / sga_get_overlaps / sga_get_overlaps_with (replica observables on the device: the exact integer product of int8 spin rows on the matrix cores, csrc/observables.hip; read only, no engine state); 2200: the row-shared fields in tiles take a plan of their own, one launch per sweep (csrc/sweep_dense_rs.hip, rs_tile_plan_kernel; no change of interface or results); 2100: sga_set_sequential_windows / sga_get_sequential_windows (SGA_SITE_SEQUENTIAL sweeps in windows, the fields of every replica on the matrix cores; csrc/sweep_dense_seq.hip); 2000: the row-shared windows (option "row_shared") serve SGA_RULE_GLAUBER and SGA_RULE_HEAT_BATH too ("rule=glauber" / "rule=heat-bath" in sga_describe and sga_get_last_kernel; the window sga_autotune picks holds for the rule it was timed under); 1900: options "row_shared_fields" and "row_shared_tile_sites" (row-shared fields in tiles of sites, sign-only rows); 1800: option "row_shared_grid", sga_route_query.rs_grid; 1700: sga_set_csr_shared (one set of CSR rows, many field vectors: every one-wave-per-replica CSR form for such batches), sga_route_query.shared_j on SGA_ROUTE_CSR queries; 1600: sga_set_dense_shared (one coupling matrix, many field vectors; row-shared windows, bit-planes and the matrix-core pass for such batches), sga_route_query.shared_j; 1500: sga_get_scan_summary, and sga_set_dense / sga_set_dense_batch / sga_set_csr / sga_set_csr64 / sga_set_csr_batch refuse a NaN or +-Inf in J or h (SGA_ERR_INVALID, "non-finite"); 1400: option "batch_fixed_point" (fixed-point cached local fields for many-model dense batches); 1300: options "ragged_field_cache" and "clf_fixed_point" together (fixed-point cached local fields for ragged CSR batches); 1200: sga_set_groups_csr (group couplings plus a stored sparse remainder); 1100: option "ragged_field_cache" (cached local fields for ragged CSR batches); 1000: sga_set_groups */
+int sga_version(void);  /* 3300: sga_get_time_links / sga_exchange_transverse (simulated quantum annealing: the broken time links of every Trotter group counted on the device, and one round of replica exchange between neighbouring groups along the transverse field decided on those counts, csrc/trotter_exchange.hip; domain word 8; no option, no engine member); 3200: sga_worldline_clusters_dense (world-line cluster updates on dense couplings: the step of sga_worldline_clusters decided on the resident fields of every slice, a coupling row read only where a segment flips, the fields kept valid, csrc/worldline_clusters_dense.hip; no option, no engine member); 3100: sga_sweep_transverse_dense (simulated quantum annealing on dense couplings: the step of sga_sweep_transverse carried by the cached local fields, a coupling row read on accept only, csrc/sweep_transverse_clf.hip; no option, no engine member); 3000: sga_worldline_clusters (simulated quantum annealing: Swendsen-Wang clusters along imaginary time at one site, flipped under the classical field, one launch per call, csrc/worldline_clusters.hip; domain word 4; no option, no engine member); 2900: sga_sweep_transverse (simulated quantum annealing: the Trotter slices of one instance coupled in the CSR sweep, two half-sweeps per sweep, csrc/sweep_transverse.hip; no option, no engine member); 2800: sga_get_class_overlaps / sga_accumulate_ladder_class_overlaps (the overlap between two replicas resolved by a class of sites, first and second moments per temperature summed on the device, csrc/class_overlaps.hip; read only, no engine state, no option); 2700: sga_get_link_count / sga_get_pair_overlaps / sga_accumulate_ladder_overlaps (spin and link overlaps between pairs of replicas, histogrammed per temperature on the device, csrc/pair_overlaps.hip; read only, no engine state, no option); 2600: sga_resample (the resampling step of population annealing, csrc/resample.hip); 2500: sga_cluster_move_pairs / sga_cluster_move_ladders (isoenergetic cluster moves between replica copies on sparse couplings, csrc/cluster_moves.hip; no engine state, no option); 2400: sga_set_replica_groups / sga_get_replica_groups; 2300: sga_get_magnetizations / sga_get_overlaps / sga_get_overlaps_with (replica observables on the device: the exact integer product of int8 spin rows on the matrix cores, csrc/observables.hip; read only, no engine state); 2200: the row-shared fields in tiles take a plan of their own, one launch per sweep (csrc/sweep_dense_rs.hip, rs_tile_plan_kernel; no change of interface or results); 2100: sga_set_sequential_windows / sga_get_sequential_windows (SGA_SITE_SEQUENTIAL sweeps in windows, the fields of every replica on the matrix cores; csrc/sweep_dense_seq.hip); 2000: the row-shared windows (option "row_shared") serve SGA_RULE_GLAUBER and SGA_RULE_HEAT_BATH too ("rule=glauber" / "rule=heat-bath" in sga_describe and sga_get_last_kernel; the window sga_autotune picks holds for the rule it was timed under); 1900: options "row_shared_fields" and "row_shared_tile_sites" (row-shared fields in tiles of sites, sign-only rows); 1800: option "row_shared_grid", sga_route_query.rs_grid; 1700: sga_set_csr_shared (one set of CSR rows, many field vectors: every one-wave-per-replica CSR form for such batches), sga_route_query.shared_j on SGA_ROUTE_CSR queries; 1600: sga_set_dense_shared (one coupling matrix, many field vectors; row-shared windows, bit-planes and the matrix-core pass for such batches), sga_route_query.shared_j; 1500: sga_get_scan_summary, and sga_set_dense / sga_set_dense_batch / sga_set_csr / sga_set_csr64 / sga_set_csr_batch refuse a NaN or +-Inf in J or h (SGA_ERR_INVALID, "non-finite"); 1400: option "batch_fixed_point" (fixed-point cached local fields for many-model dense batches); 1300: options "ragged_field_cache" and "clf_fixed_point" together (fixed-point cached local fields for ragged CSR batches); 1200: sga_set_groups_csr (group couplings plus a stored sparse remainder); 1100: option "ragged_field_cache" (cached local fields for ragged CSR batches); 1000: sga_set_groups */
 /* Run on an existing HIP stream (e.g. torch.cuda.current_stream().cuda_stream); NULL = the
  * engine's own stream (default). */
 int sga_set_stream(sga_engine *e, void *hip_stream);
@@ -718,6 +718,56 @@ int sga_worldline_clusters(sga_engine *e, int n_sweeps, int n_slices, uint32_t r
 int sga_worldline_clusters_dense(sga_engine *e, int n_sweeps, int n_slices, uint32_t round,
                                  const double *p_bond /* host [n_sweeps][R_local / n_slices], each in [0, 1] */,
                                  int64_t *stats       /* host [R_local / n_slices][3] or NULL: += as sga_worldline_clusters */);
+
+/* ---- time links and the exchange along the transverse field (version >= 3300; csrc/trotter_exchange.hip) ------------------
+ * Groups as in sga_sweep_transverse: G = R_local / n_slices groups of P = n_slices slices, slice p of group g in row g P + p,
+ * the slices of a group a ring.  The BROKEN TIME LINKS of group g over the current spins are
+ *   B_g = sum_{p < P} sum_{i < n} [ s_{gP+p}[i] != s_{gP+next(p)}[i] ],   next(p) = p + 1 == P ? 0 : p + 1,
+ * so with P = 2 both links of the ring count and a differing site gives 2, as the sweep counts its neighbour twice; B is
+ * even and lies in [0, n P].  B is all of a configuration that the quantum side reads: <sigma^x> and the quantum energy
+ * estimator are functions of it (quantum.transverse_magnetization, quantum.quantum_energy), and so is the acceptance ratio
+ * of an exchange between two groups at different transverse fields.
+ *
+ * sga_get_time_links writes B into links [G] (int64, host or device).  Read only: no engine state moves.  Enqueued on the
+ * engine's stream behind earlier sweeps; a device buffer returns at once, a host buffer after the copy has landed.
+ *   SGA_ERR_INVALID, in this order: engine NULL, "links is NULL", no couplings, no replicas, n_slices < 2, n_slices not
+ *   dividing R_local, replica0 not a multiple of n_slices.  Any P >= 2 is served, odd ones included, with no upper bound.
+ *   SGA_ERR_UNSUPPORTED: sga_set_tsp, sga_set_groups / sga_set_groups_csr, batches (ragged, shared and stacked).  Everything
+ *   else is served -- dense rows in any storage, CSR rows of any class, whatever the rule: no coupling is read.
+ *
+ * sga_exchange_transverse runs ONE nearest-neighbour exchange round along the group index.  For every lower group a with
+ * a % 2 == parity and b = a + 1 < G, in fp64, every operation a single one:
+ *   beta_g = 1.0 / T[gP]                       (the temperature of the group's slice 0; equal T within a group is the
+ *                                               caller's responsibility, as for the sweeps)
+ *   E_g = energy[gP+0] + ... + energy[gP+P-1]  (the tracked energies, left to right)
+ *   t1  = (beta_a - beta_b) * (E_a - E_b)
+ *   c   = beta_a * (double)k_a - beta_b * (double)k_b
+ *   t2  = (2.0 * c) * (double)(B_a - B_b)
+ *   x   = t1 + t2;   prob = !(x < 0.0) ? 1.0 : exp(x)   (the deterministic exp of the accept rules)
+ *   u   = ((w0 >> 5) * 2^26 + (w1 >> 6)) * 2^-53, (w0, w1, ., .) = Philox4x32-10(counter (0, round, a, 8), key = seed)
+ *   the groups swap iff u < prob
+ * -- the ratio w(a at b's parameters) w(b at a's) / (w(a) w(b)) of the weights exp(-beta H_eff), H_eff = E - k (n P - 2 B).
+ * Domain word 8 = sweep | 2 << 2 is no other draw's.  The counter holds the group index: the call needs every group on
+ * this rank.  A pair where either T is not positive and finite is left alone.  `round` is the caller's: no counter of the
+ * engine moves.
+ *   On a swap slice p of a and slice p of b trade their spin rows (all sstride bytes) and their tracked energies (the
+ * bits).  Where the cached local fields are valid they trade their resident field rows too, and the fields STAY VALID (F
+ * depends on neither k nor T): sga_sweep_transverse_dense, this call, sga_sweep_transverse_dense run without seeding in
+ * between.  Where the fields are not valid nothing is done to them; under SGA_FIELD_CACHE_AUTO, where the mark stands for
+ * some replicas only, they are marked for re-seeding instead.  Then every slice's best follows where its energy is lower
+ * (the step at a sweep's end).  Accept counters, temperatures, slot map, exchange statistics, sweep and round counters and
+ * Wolff cursors do not move.
+ *   accepted [G] (int32: 1 for both groups of a swapped pair, else 0) and links [G] (int64: B BEFORE the exchange) are host
+ * or device buffers or NULL.  G = 1, or a parity that leaves no pair, is a no-op with the outputs still filled.
+ *   SGA_ERR_INVALID, first and with nothing enqueued or changed: the ladder above with "k_perp is NULL" and "k_perp holds a
+ *   NaN or an infinite value" over the G values, then "parity must be 0 or 1", then "exchanges between groups need every
+ *   group on this rank (R_local == R_global)"; k_perp on the device.  SGA_ERR_UNSUPPORTED: the kinds above.
+ *   Four launches on the engine's stream with no host round trip between them (the counts, the decision, the swap, the
+ *   bests); both calls show in sga_get_last_kernel (time_links_kernel, trotter_exchange_kernel). */
+int sga_get_time_links(sga_engine *e, int n_slices, int64_t *links /* host or device [R_local / n_slices] */);
+int sga_exchange_transverse(sga_engine *e, int n_slices, const float *k_perp /* host [R_local / n_slices] */, int parity,
+                            uint32_t round, int32_t *accepted /* host or device [R_local / n_slices], or NULL */,
+                            int64_t *links /* host or device [R_local / n_slices], or NULL */);
 
 /* Stateless operator form of CUDAKernelManager.parallel_tempering_exchange_optimized
  * (annealing/cuda_kernels.py:326-369, fallback :415-443): sequential adjacent pairs, fp32,

@@ -19,7 +19,7 @@ from .parallel_tempering import ClassOverlapStatistics, OverlapStatistics, Paral
 from .population_annealing import PopulationAnnealing, PopulationAnnealingConfig
 from . import quantum
 from .quantum import (QuantumFluctuations, SimulatedQuantumAnnealing, SimulatedQuantumAnnealingConfig, TransverseField,
-                      bond_probability, transverse_coupling)
+                      bond_probability, quantum_energy, transverse_coupling, transverse_magnetization)
 from .kernel_manager import CUDAKernelManager, GPUMemoryOptimizer, HIPKernelManager
 from .scheduler import SpinGlassScheduler
 from .sharded import LocalShardedTempering, ShardedTempering
@@ -36,7 +36,7 @@ __all__ = [
     "GPUAnnealer", "GPUAnnealerConfig", "ParallelTempering", "ParallelTemperingConfig", "OverlapStatistics", "ClassOverlapStatistics",
     "PopulationAnnealing", "PopulationAnnealingConfig",
     "quantum", "QuantumFluctuations", "SimulatedQuantumAnnealing", "SimulatedQuantumAnnealingConfig", "TransverseField",
-    "transverse_coupling", "bond_probability",
+    "transverse_coupling", "bond_probability", "transverse_magnetization", "quantum_energy",
     "HIPKernelManager", "CUDAKernelManager", "GPUMemoryOptimizer", "SpinGlassScheduler",
     "ShardedTempering", "LocalShardedTempering", "MultiGPUAnnealer", "MultiGPUConfig", "LoadBalancer",
     "encoders", "IsingBuilder", "BatchConfig", "BatchProcessor", "EnergyComputer", "ComputeMode",

@@ -71,6 +71,8 @@ SYMBOLS = [
     ("sga_sweep_transverse_dense", _i, [_p, _i, _i, _i, _p]),
     ("sga_worldline_clusters", _i, [_p, _i, _i, _u32, _p, _p]),
     ("sga_worldline_clusters_dense", _i, [_p, _i, _i, _u32, _p, _p]),
+    ("sga_get_time_links", _i, [_p, _i, _p]),
+    ("sga_exchange_transverse", _i, [_p, _i, _p, _i, _u32, _p, _p]),
     ("sga_local_fields", _i, [_p, _i, _p, _i, _p]),
     ("sga_flip", _i, [_p, _i, _i, C.POINTER(_d)]),
     ("sga_update", _i, [_p, _i, _i, _d, C.c_float, _i, C.POINTER(_i), C.POINTER(_d)]),

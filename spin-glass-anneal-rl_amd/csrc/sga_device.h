@@ -39,6 +39,9 @@ constexpr uint32_t DOMAIN_SWEEP = 0, DOMAIN_EXCHANGE = 1, DOMAIN_INIT = 2;
 constexpr uint32_t DOMAIN_CLUSTER = DOMAIN_EXCHANGE | (1u << 2);
 // the offset of a population-annealing resampling step (resample.hip): domain word 6
 constexpr uint32_t DOMAIN_RESAMPLE = DOMAIN_INIT | (1u << 2);
+// the uniform of an exchange between Trotter groups along the transverse field (trotter_exchange.hip): domain word 8
+// (word 4 = sweep | 1 << 2 is the world-line clusters', sweep_common.h)
+constexpr uint32_t DOMAIN_TROTTER_EXCHANGE = DOMAIN_SWEEP | (2u << 2);
 
 __device__ __forceinline__ uint32_t word_to_site(uint32_t w, uint32_t n) { return __umulhi(w, n); }
 __device__ __forceinline__ float word_to_u(uint32_t w) { return (float)(w >> 8) * 0x1.0p-24f; }

@@ -347,6 +347,11 @@ extern "C" {
 
 const char *sga_last_error(void) { return g_last_error.c_str(); }
 // The ABI version, one line per step:
+//   3300:    + sga_get_time_links / sga_exchange_transverse: the broken time links of every Trotter group counted on the device
+//            (a grid of site chunks x groups, 16-byte loads, one integer atomic per workgroup) and one round of replica
+//            exchange between neighbouring groups along the transverse field -- counts, decision, swap of spin rows,
+//            energies and valid field rows, bests (trotter_exchange.hip; the admission rules in sga_quantum.h; domain
+//            word 8); no option, no engine member
 //   3200:    + sga_worldline_clusters_dense: the step of sga_worldline_clusters on dense couplings, decided on the resident
 //            fields of every slice -- one workgroup per group, blocks of sites decided in registers, a coupling row read
 //            only where a segment flips, the fields kept valid (worldline_clusters_dense.hip; the admission rule in
@@ -404,7 +409,7 @@ const char *sga_last_error(void) { return g_last_error.c_str(); }
 //   600:     + sga_set_csr_batch / sga_get_batch_model (ragged CSR batches)
 //   round 5: + sga_explain_route / sga_get_route_query, sga_get_last_kernel, sga_get_autotune_table, ladder-local
 //            sga_exchange
-int sga_version(void) { return 3200; }
+int sga_version(void) { return 3300; }
 
 int sga_create(int device, sga_engine **out) {
     if (!out) return fail(SGA_ERR_INVALID, "out is NULL");

@@ -1,5 +1,6 @@
 // sga_quantum.cpp -- simulated quantum annealing, the engine half (the pure half: sga_quantum.h): sga_sweep_transverse,
-// sga_sweep_transverse_dense, sga_worldline_clusters and sga_worldline_clusters_dense.  None keeps state of its own: the caller's host array is staged in
+// sga_sweep_transverse_dense, sga_worldline_clusters, sga_worldline_clusters_dense, sga_get_time_links and
+// sga_exchange_transverse.  None keeps state of its own: the caller's host array is staged in
 // scratch slot 0 (where sga_sweep stages a schedule).  A sweep is two launches on the engine's stream, the even slices'
 // half-sweep and the odd ones'; one launch serves a whole clusters call.
 #include "sga_engine_impl.h"
@@ -19,7 +20,14 @@ sga::TrotterProblem trotter_problem_of(const sga_engine *e) {
     p.clf_why = e->clf_why;
     p.field_bits = e->clf_bits;
     p.ldf = (e->ldj + 127) / 128 * 128;  // (as ensure_fields lays the rows out)
+    p.R_global = e->Rg;
     return p;
+}
+
+// The bytes of a replica's resident field row, whichever form seeded it (ensure_fields): ldf is a multiple of 128.
+long long field_row_bytes_of(const sga_engine *e) {
+    const int bits = e->clf_fx_bits ? e->clf_fx_bits : e->csr ? 16 : e->clf_bits;
+    return e->ldf * (long long)(bits / 8);
 }
 
 int refuse_device_ptr(const void *p, const char *name) {
@@ -202,5 +210,74 @@ int sga_worldline_clusters_dense(sga_engine *e, int n_sweeps, int n_slices, uint
         HIPCHK(hipStreamSynchronize(st));
         for (size_t i = 0; i < got.size(); ++i) stats[i] += (int64_t)got[i];
     }
+    return SGA_OK;
+}
+
+// ---- the exchange between groups along the transverse field (trotter_exchange.hip) ----------------------------------------
+// Read only: the counts go into the caller's device buffer, or through scratch slot 0 onto the host.
+int sga_get_time_links(sga_engine *e, int n_slices, int64_t *links) {
+    bool invalid = true;
+    if (const char *why = sga::time_links_check(e != nullptr, trotter_problem_of(e), n_slices, links, &invalid))
+        return fail(invalid ? SGA_ERR_INVALID : SGA_ERR_UNSUPPORTED, why);
+    HIPCHK(hipSetDevice(e->device));
+    hipStream_t st = e->stream;
+    const size_t bytes = (size_t)(e->R / n_slices) * sizeof(int64_t);
+    const bool on_device = is_device_ptr(links);
+    if (!on_device) HIPCHK(e->scratch[0].reserve(bytes));
+    long long *d_links = on_device ? reinterpret_cast<long long *>(links) : static_cast<long long *>(e->scratch[0].ptr);
+    HIPCHK(hipMemsetAsync(d_links, 0, bytes, st));
+    HIPCHK(sga::launch_time_links(e->spins, e->sstride, e->R, n_slices, d_links, st));
+    std::snprintf(e->last_kernel, sizeof(e->last_kernel), "%s", sga::last_sweep_kernel());
+    if (!on_device) {
+        HIPCHK(hipMemcpyAsync(links, d_links, bytes, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+    }
+    return SGA_OK;
+}
+
+// k_perp is staged in scratch slot 0 with the counts and the flags behind it; the counts, the decision, the swap and the
+// bests' step follow each other on the engine's stream.  The resident fields are traded with the spins where they are
+// valid, and stay valid -- under SGA_FIELD_CACHE_AUTO, where fields_valid stands for some replicas only, they are marked
+// for re-seeding instead.
+int sga_exchange_transverse(sga_engine *e, int n_slices, const float *k_perp, int parity, uint32_t round, int32_t *accepted, int64_t *links) {
+    if (const int rc = refuse_device_ptr(k_perp, "k_perp")) return rc;
+    bool invalid = true;
+    if (const char *why = sga::exchange_check(e != nullptr, trotter_problem_of(e), n_slices, k_perp, parity, &invalid))
+        return fail(invalid ? SGA_ERR_INVALID : SGA_ERR_UNSUPPORTED, why);
+    if (!e->best_spins || !e->energy || !e->best_energy || !e->rep_temp) return fail(SGA_ERR_INVALID, "no replicas (call sga_init_replicas)");
+    HIPCHK(hipSetDevice(e->device));
+    hipStream_t st = e->stream;
+    const size_t G = (size_t)(e->R / n_slices);
+    unsigned char *d_k = nullptr, *behind = nullptr;
+    const int rc = stage(e, k_perp, G * sizeof(float), d_k, G * (sizeof(int64_t) + sizeof(int32_t)), &behind);
+    if (rc != SGA_OK) return rc;
+    long long *d_links = reinterpret_cast<long long *>(behind);
+    int *d_flags = reinterpret_cast<int *>(behind + G * sizeof(int64_t));
+    if (e->field_cache == SGA_FIELD_CACHE_AUTO) e->fields_valid = false;
+    const bool trade_fields = e->fields_valid && e->fields;
+    const sga::SweepArgs a = replica_args_of(e);
+    const sga::TrotterExchangeArgs x{reinterpret_cast<const float *>(d_k), d_links, d_flags, n_slices, parity, round,
+                                     trade_fields ? e->fields : nullptr, trade_fields ? field_row_bytes_of(e) : 0};
+    HIPCHK(hipMemsetAsync(d_links, 0, G * sizeof(int64_t), st));
+    HIPCHK(sga::launch_time_links(e->spins, e->sstride, e->R, n_slices, d_links, st));
+    HIPCHK(sga::launch_trotter_exchange_decide(a, x, st));
+    hipError_t le = sga::launch_trotter_exchange_swap(a, x, st);
+    std::snprintf(e->last_kernel, sizeof(e->last_kernel), "%s", sga::last_sweep_kernel());
+    if (le == hipSuccess) le = sga::launch_update_best(e->energy, e->spins, e->best_energy, e->best_spins, e->sstride, e->R, st);
+    if (le != hipSuccess) {
+        (void)hipStreamSynchronize(st);
+        e->fields_valid = false;  // (a launch that did not go out: nothing is known about which rows were traded)
+    }
+    HIPCHK(le);
+    bool wait = false;
+    if (accepted) {
+        HIPCHK(hipMemcpyAsync(accepted, d_flags, G * sizeof(int32_t), hipMemcpyDefault, st));
+        wait = wait || !is_device_ptr(accepted);
+    }
+    if (links) {
+        HIPCHK(hipMemcpyAsync(links, d_links, G * sizeof(int64_t), hipMemcpyDefault, st));
+        wait = wait || !is_device_ptr(links);
+    }
+    if (wait) HIPCHK(hipStreamSynchronize(st));
     return SGA_OK;
 }

@@ -1,9 +1,10 @@
-// sga_quantum.h -- simulated quantum annealing: the Trotter-slice geometry and the admission rules of its four calls,
+// sga_quantum.h -- simulated quantum annealing: the Trotter-slice geometry and the admission rules of its calls,
 // sga_sweep_transverse (sweep_transverse.hip), sga_sweep_transverse_dense (sweep_transverse_clf.hip),
-// sga_worldline_clusters (worldline_clusters.hip) and sga_worldline_clusters_dense (worldline_clusters_dense.hip).  The pure
-// half: no sga_engine and no HIP call, so tests/c_abi/transverse_plan.cpp, transverse_dense_plan.cpp, worldline_plan.cpp and
-// worldline_dense_plan.cpp pin it on the CPU.  The engine half is sga_quantum.cpp: it reads an engine into a TrotterProblem
-// and runs the calls.
+// sga_worldline_clusters (worldline_clusters.hip), sga_worldline_clusters_dense (worldline_clusters_dense.hip),
+// sga_get_time_links and sga_exchange_transverse (trotter_exchange.hip).  The pure half: no sga_engine and no HIP call, so
+// tests/c_abi/transverse_plan.cpp, transverse_dense_plan.cpp, worldline_plan.cpp, worldline_dense_plan.cpp and
+// trotter_exchange_plan.cpp pin it on the CPU.  The engine half is sga_quantum.cpp: it reads an engine into a
+// TrotterProblem and runs the calls.
 //
 // The local replicas are G = R_local / P contiguous groups of P slices, slice p of group g in row g P + p; replica0 is a
 // multiple of P, so p is the global slice index too.  The slices of a group form a ring.
@@ -79,6 +80,8 @@ struct TrotterProblem {
     const char *clf_why = nullptr;  // ... where it does not: which condition failed
     int field_bits = 16;            // 16 | 32: the width of the resident fields
     long long ldf = 0;              // elements of a replica's field row
+    // the exchange between groups
+    int R_global = 0;  // the replicas of every rank
 };
 // The argument errors of a call (SGA_ERR_INVALID), the same ladder for all four: they come first, so that a wrong call is
 // told so whatever the problem.  What differs between the calls comes in: the text for a NULL array, whether arith was
@@ -124,7 +127,7 @@ inline const char *trotter_kind_refused(const TrotterProblem &p, const char *wha
     return text;
 }
 
-// The four admission rules, pure functions: nullptr where the call is served, else why not, with *invalid = true for
+// The admission rules, pure functions: nullptr where the call is served, else why not, with *invalid = true for
 // SGA_ERR_INVALID and false for SGA_ERR_UNSUPPORTED.  The argument errors, the kinds, then what the call's own kernel asks.
 inline const char *transverse_check(bool have_engine, const TrotterProblem &p, int n_sweeps, int n_slices, bool arith_ok,
                                     const float *k_perp, bool *invalid) {
@@ -190,6 +193,29 @@ inline const char *worldline_dense_check(bool have_engine, const TrotterProblem 
     return nullptr;
 }
 
+// The broken time links of every group: the ladder with any P >= 2, odd ones included, and no value to read; then the
+// kinds.  No coupling is read: dense rows in any storage, CSR rows of any class and every rule are served.
+inline const char *time_links_check(bool have_engine, const TrotterProblem &p, int n_slices, const int64_t *links, bool *invalid) {
+    *invalid = true;
+    if (const char *why = trotter_argument_error(have_engine, p, 0, n_slices, links, "links is NULL", true, nullptr,
+                                                 [](int64_t) { return true; }, nullptr))
+        return why;
+    *invalid = false;
+    return trotter_kind_refused(p, "time links");
+}
+// One exchange round between neighbouring groups: the ladder over the G values of k_perp (one row), the parity, every
+// group on this rank; then the kinds.
+inline const char *exchange_check(bool have_engine, const TrotterProblem &p, int n_slices, const float *k_perp, int parity, bool *invalid) {
+    *invalid = true;
+    if (const char *why = trotter_argument_error(have_engine, p, 1, n_slices, k_perp, "k_perp is NULL", true, nullptr,
+                                                 [](float k) { return k - k == 0.0f; }, "k_perp holds a NaN or an infinite value"))
+        return why;
+    if (parity != 0 && parity != 1) return "parity must be 0 or 1";
+    if (p.R_local != p.R_global) return "exchanges between groups need every group on this rank (R_local == R_global)";
+    *invalid = false;
+    return trotter_kind_refused(p, "transverse-field exchanges");
+}
+
 // ---- the launches -----------------------------------------------------------------------------------------------------------
 // One half-sweep of either sweep.
 struct TrotterLaunch {
@@ -216,6 +242,26 @@ hipError_t launch_worldline_clusters(const SweepArgs &a, const WorldlineArgs &w,
 // launch reads and writes: they stay valid.  waves per group: worldline_dense_waves (forced: option "clf_waves", 0 = none)
 int worldline_dense_waves(long long ldj, bool j_is_i8, int forced);
 hipError_t launch_worldline_clusters_dense(const SweepArgs &a, const WorldlineArgs &w, bool j_is_i8, int waves, hipStream_t st);
+
+// The exchange between groups along the transverse field (trotter_exchange.hip).
+constexpr int TIME_LINKS_CHUNK_SITES = 64 * 16;  // the sites of one workgroup of the count: one wave, 16 bytes a lane
+// links[g] += the broken time links of group g, links [R / n_slices] ZEROED by the caller (device); spins [R][sstride]
+// int8 with a zero pad, sstride a multiple of 16.  Exact integer atomics: the same in any order.
+hipError_t launch_time_links(const int8_t *spins, int sstride, int R, int n_slices, long long *links, hipStream_t st);
+struct TrotterExchangeArgs {
+    const float *k_perp;     // device [G]
+    const long long *links;  // device [G]: B of every group, as launch_time_links left it
+    int *flags;              // device [G]: 1 for both groups of a swapped pair, else 0 (the decision writes every entry)
+    int n_slices;            // P
+    int parity;              // the pairs (a, a + 1) with a % 2 == parity
+    uint32_t round;
+    void *fields;            // the resident field rows, traded with the spins -- or null: not valid, left alone
+    long long field_row_bytes;  // a multiple of 16
+};
+// a: the replica state and the seed (a.spins, a.energy, a.rep_temp, a.sstride, a.R, a.seed_lo, a.seed_hi).  The decision
+// reads the energies the swap overwrites: two launches.
+hipError_t launch_trotter_exchange_decide(const SweepArgs &a, const TrotterExchangeArgs &x, hipStream_t st);
+hipError_t launch_trotter_exchange_swap(const SweepArgs &a, const TrotterExchangeArgs &x, hipStream_t st);
 
 }  // namespace sga
 

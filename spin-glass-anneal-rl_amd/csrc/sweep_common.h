@@ -161,11 +161,19 @@ __device__ __forceinline__ uint64_t resample_draw(uint32_t round, uint32_t gpop,
 }
 
 // The draws of a world-line cluster sweep (worldline_clusters.hip) of the slice with global id q at site i in round
-// `round`: block i at (round, q, DOMAIN_WORLDLINE) -- domain word 4 = sweep | 1 << 2 (in use besides: 0, 1, 2, 5, 6; every
-// Wolff word ends in bits 11).  Word 0: the bond towards the next slice; word 1: the uniform of a segment this slice heads.
+// `round`: block i at (round, q, DOMAIN_WORLDLINE) -- domain word 4 = sweep | 1 << 2 (in use besides: 0, 1, 2, 5, 6 and 8,
+// DOMAIN_TROTTER_EXCHANGE of sga_device.h; every Wolff word ends in bits 11).  Word 0: the bond towards the next slice; word 1: the uniform of a segment this slice heads.
 constexpr uint32_t DOMAIN_WORLDLINE = DOMAIN_SWEEP | (1u << 2);
 __device__ __forceinline__ u32x4 worldline_block(uint32_t site, uint32_t round, uint32_t q, uint32_t seed_lo, uint32_t seed_hi) {
     return philox4x32_10(site, round, q, DOMAIN_WORLDLINE, seed_lo, seed_hi);
+}
+
+// The uniform of an exchange between the Trotter groups a and a + 1 along the transverse field (trotter_exchange.hip) in
+// round `round`: words 0 and 1 of block 0 at (round, a, DOMAIN_TROTTER_EXCHANGE), 53 bits.  a is the group's index: the
+// call asks for every group on one rank.
+__device__ __forceinline__ double trotter_exchange_u(uint32_t round, uint32_t a, uint32_t seed_lo, uint32_t seed_hi) {
+    const u32x4 w = philox4x32_10(0u, round, a, DOMAIN_TROTTER_EXCHANGE, seed_lo, seed_hi);
+    return words_to_u53(w.x, w.y);
 }
 
 // The accept rule.  dot = fp32 coupling dot product J[site,:].s (already rounded to fp32),

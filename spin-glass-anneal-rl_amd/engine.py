@@ -636,6 +636,46 @@ class AnnealEngine:
                 "sga_worldline_clusters_dense")
         return out
 
+    def time_links(self, n_slices: int, out=None):
+        """int64 [R / n_slices]: the broken time links B_g of every group of n_slices Trotter slices (sga_get_time_links):
+        the sites at which neighbouring slices of the ring differ, summed over the ring (n_slices = 2: a differing site
+        counts 2).  All that quantum.transverse_magnetization and quantum.quantum_energy read of the spins.  Read only;
+        any n_slices >= 2 that divides R.  out: an optional contiguous int64 CUDA tensor [R / n_slices] that receives the
+        counts on the device, under the conventions of overlaps(out=): with shares_torch_stream() the call is only
+        enqueued."""
+        P = int(n_slices)
+        G = self._trotter_groups(P)
+        ptr, res, dev = self._pair_out(out, G, "int64", "out")
+        N.check(self._lib.sga_get_time_links(self._h, P, ptr), "sga_get_time_links")
+        self._observable_done(dev)
+        if dev:
+            self._pending = (res,)  # a device result stays alive while the work is queued
+        return res
+
+    def exchange_transverse(self, n_slices: int, k_perp, parity: Optional[int] = None, round: Optional[int] = None):
+        """One round of replica exchange between neighbouring groups of n_slices Trotter slices along the transverse
+        field (sga_exchange_transverse): the pairs (a, a + 1) with a % 2 == parity swap with probability
+        min(1, exp[(beta_a - beta_b)(E_a - E_b) + 2 (beta_a k_a - beta_b k_b)(B_a - B_b)]) -- whole groups trade spin
+        rows, tracked energies and, where they are valid, cached local fields, which stay valid.  k_perp: a scalar or
+        [R / n_slices], the couplings the groups run at.  round: None = counters()[0]; parity: None = round & 1.  No
+        counter, temperature or statistic of the engine moves.  Returns (accepted int32 [G], links int64 [G]): 1 for
+        both groups of a swapped pair, and B of every group before the exchange."""
+        P = int(n_slices)
+        G = self._trotter_groups(P)
+        k = np.asarray(k_perp, dtype=np.float32)
+        if k.ndim == 0:
+            k = np.full(G, k, np.float32)
+        elif k.shape != (G,):
+            raise AnnealingError("k_perp must be a scalar or [R / n_slices]")
+        k = np.ascontiguousarray(k, dtype=np.float32)
+        rnd = self.counters()[0] if round is None else int(round)
+        par = (rnd & 1) if parity is None else int(parity)
+        accepted, links = np.zeros(G, np.int32), np.zeros(G, np.int64)
+        N.check(self._lib.sga_exchange_transverse(self._h, P, k.ctypes.data_as(C.c_void_p), par, rnd & 0xFFFFFFFF,
+                                                  accepted.ctypes.data_as(C.c_void_p), links.ctypes.data_as(C.c_void_p)),
+                "sga_exchange_transverse")
+        return accepted, links
+
     # single-site operators (the reference's per-spin API)
     def local_fields(self, r: int, sites) -> np.ndarray:
         idx = np.ascontiguousarray(np.atleast_1d(sites), dtype=np.int32)

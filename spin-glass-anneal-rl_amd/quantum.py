@@ -25,10 +25,17 @@ local fields resident in LDS and a coupling row read on accept only.  It serves 
 and h in multiples of 1/2.  The cluster move beside it is a flag of its own, dense_worldline_clusters=True: every
 cluster_interval-th dense sweep is followed by AnnealEngine.worldline_clusters_dense (sga_worldline_clusters_dense), the
 same cluster step decided on the same cached fields, which stay valid between the two calls.
+
+The quantum side of a run is a function of one integer per instance, the number B of broken time links
+(AnnealEngine.time_links, sga_get_time_links): transverse_magnetization gives <sigma^x> and quantum_energy the energy
+estimator of H.  The same count decides the replica exchange along Gamma (quantum parallel tempering):
+SimulatedQuantumAnnealingConfig(field_ladder=[c_0, ...], field_exchange_interval=m) runs instance g at c_g Gamma(t) and
+follows every m-th sweep with one round of AnnealEngine.exchange_transverse (sga_exchange_transverse) between neighbouring
+instances, whole instances trading places on the device.
 """
 import time
 from dataclasses import dataclass, field
-from typing import Optional
+from typing import Optional, Sequence
 
 import numpy as np
 import torch
@@ -71,6 +78,26 @@ def bond_probability(k_perp, slice_temperature: float):
         raise ConfigurationError("k_perp must not be negative: an antiferromagnetic time coupling has no such clusters")
     b = -np.expm1(-2.0 * k / float(slice_temperature))
     return float(b) if b.ndim == 0 else b
+
+
+def transverse_magnetization(links, n_spins, n_slices, gamma, temperature):
+    """<sigma^x> per site of a path-integral configuration with B = links broken time links out of n P:
+    [(n P - B) tanh(a) + B / tanh(a)] / (n P), a = Gamma / (P T), in float64 -- tanh(a) for identical slices, 1 / tanh(a)
+    with every link broken.  Arrays broadcast against each other."""
+    B = np.asarray(links, np.float64)
+    nP = np.asarray(n_spins, np.float64) * np.asarray(n_slices, np.float64)
+    t = np.tanh(np.asarray(gamma, np.float64) / (np.asarray(n_slices, np.float64) * np.asarray(temperature, np.float64)))
+    m = ((nP - B) * t + B / t) / nP
+    return float(m) if m.ndim == 0 else m
+
+
+def quantum_energy(slice_energies, links, n_spins, n_slices, gamma, temperature):
+    """The estimator of <H> = <H_classical> - Gamma sum_i <sigma^x_i>: the mean over the slices of the classical energies
+    slice_energies [G, P] (or [P]) minus Gamma n transverse_magnetization(links, ...), float64 [G] (or a scalar)."""
+    E = np.asarray(slice_energies, np.float64).mean(axis=-1)
+    q = E - np.asarray(gamma, np.float64) * np.asarray(n_spins, np.float64) * \
+        transverse_magnetization(links, n_spins, n_slices, gamma, temperature)
+    return float(q) if np.ndim(q) == 0 else q
 
 
 @dataclass
@@ -120,6 +147,9 @@ class SimulatedQuantumAnnealingConfig:
     #                                       sga_sweep_transverse_dense (False: the model's own form, CSR rows served only)
     dense_worldline_clusters: bool = False  # with dense_couplings: follow every cluster_interval-th dense sweep with one
     #                                         cluster sweep on the cached fields (sga_worldline_clusters_dense)
+    field_ladder: Optional[Sequence[float]] = None  # multipliers c_g, one per instance: instance g runs at c_g Gamma(t)
+    field_exchange_interval: int = 0      # m > 0: every m-th sweep, counted over the run, is followed by one round of
+    #                                       replica exchange between neighbouring instances (sga_exchange_transverse)
 
     def __post_init__(self):
         self.check()
@@ -145,6 +175,17 @@ class SimulatedQuantumAnnealingConfig:
             raise ConfigurationError("dense_worldline_clusters must be True or False")
         if self.dense_worldline_clusters:
             self.check_dense_clusters()
+        if self.field_ladder is not None:
+            c = np.asarray(self.field_ladder, np.float64)
+            if c.ndim != 1 or c.size != int(self.n_instances):
+                raise ConfigurationError("field_ladder must hold one multiplier per instance (n_instances values)")
+            if not np.all(np.isfinite(c)) or np.any(c <= 0):
+                raise ConfigurationError("field_ladder must hold positive finite multipliers")
+        m = self.field_exchange_interval
+        if isinstance(m, (bool, np.bool_)) or not isinstance(m, (int, np.integer)) or m < 0:
+            raise ConfigurationError("field_exchange_interval must be a non-negative integer (0: no exchange)")
+        if m > 0 and self.n_instances < 2:
+            raise ConfigurationError("field_exchange_interval needs n_instances >= 2 (an exchange is between two instances)")
 
     def check_dense_clusters(self):
         """What dense_worldline_clusters asks of the rest of the configuration."""
@@ -161,6 +202,16 @@ class SimulatedQuantumAnnealingConfig:
             raise ConfigurationError("the schedule gives an infinite k_perp (a transverse field too close to 0)")
         return k32
 
+    def couplings_by_instance(self) -> np.ndarray:
+        """float32 [n_sweeps, n_instances]: k_perp per sweep and instance, instance g at field_ladder[g] Gamma(t) (no
+        ladder: every column is couplings())."""
+        c = np.ones(int(self.n_instances)) if self.field_ladder is None else np.asarray(self.field_ladder, np.float64)
+        g = self.transverse_field.gammas(self.n_sweeps)[:, None] * c[None, :]
+        k32 = np.asarray(transverse_coupling(g, self.temperature, self.n_slices), np.float64).astype(np.float32)
+        if not np.all(np.isfinite(k32)):
+            raise ConfigurationError("the schedule gives an infinite k_perp (a transverse field too close to 0)")
+        return k32
+
 
 class SimulatedQuantumAnnealing:
     def __init__(self, config: SimulatedQuantumAnnealingConfig):
@@ -170,28 +221,48 @@ class SimulatedQuantumAnnealing:
         self.slice_overlaps = None   # int32 [R, R] of run(measure_overlaps=True): s_a . s_b between the final slices
         self.cluster_statistics = None  # int64 [3] of a run with world-line clusters: segments formed, segments flipped,
         #                                 slice spins flipped, summed over the run
+        self.time_links = None       # int64 [n_instances]: the broken time links of every instance at the end
+        self.transverse_magnetization = None  # float64 [n_instances]: <sigma^x> per site at the end, from time_links
+        self.field_exchange_statistics = None  # of a run with field_exchange_interval > 0: (attempts, accepts), int64
+        #                                        [n_instances - 1] each, per pair of neighbouring instances
         self.device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
         self.use_cuda = self.device.type == "cuda"
 
     def _sweeps(self, eng, k0: int, ns: int, k, clusters: bool, dense: bool = False):
         """Transverse sweeps k0 ... k0 + ns - 1; with clusters, every cluster_interval-th one (counted over the run) is
         followed by one cluster sweep at its k_perp, drawn at round = the sweep's index.  dense: the engine holds dense
-        rows, the sweeps are sweep_transverse_dense's and the cluster sweeps worldline_clusters_dense's."""
+        rows, the sweeps are sweep_transverse_dense's and the cluster sweeps worldline_clusters_dense's.  k: [n_sweeps],
+        or [n_sweeps, G] with a field ladder.  With field_exchange_interval = m > 0 every m-th sweep (counted over the
+        run) is followed -- after its cluster sweep, if one is due -- by one exchange round at its row of k, round = the
+        sweep's index, the parity alternating from 0 with the exchanges of the run."""
         cfg = self.config
         P = int(cfg.n_slices)
         sweep = eng.sweep_transverse_dense if dense else eng.sweep_transverse
-        if not clusters:
+        m = int(cfg.field_exchange_interval)
+        if not clusters and m == 0:
             sweep(ns, P, k[k0:k0 + ns])
             return
         move = eng.worldline_clusters_dense if dense else eng.worldline_clusters
         every, slice_T = int(cfg.cluster_interval), P * float(cfg.temperature)
         t = k0
         while t < k0 + ns:
-            stop = min(((t // every) + 1) * every, k0 + ns)  # the sweeps up to and with the next one that is followed
+            stop = k0 + ns  # the sweeps up to and with the next one that is followed
+            if clusters:
+                stop = min(stop, ((t // every) + 1) * every)
+            if m:
+                stop = min(stop, ((t // m) + 1) * m)
             sweep(stop - t, P, k[t:stop])
-            if stop % every == 0:
-                self.cluster_statistics += move(1, P, bond_probability(float(k[stop - 1]), slice_T), round=stop - 1,
-                                                stats=True).sum(axis=0)
+            if clusters and stop % every == 0:
+                row = k[stop - 1]
+                b = bond_probability(float(row), slice_T) if np.ndim(row) == 0 else bond_probability(row, slice_T)[None, :]
+                self.cluster_statistics += move(1, P, b, round=stop - 1, stats=True).sum(axis=0)
+            if m and stop % m == 0:
+                parity = (stop // m - 1) & 1
+                accepted, _ = eng.exchange_transverse(P, k[stop - 1], parity=parity, round=stop - 1)
+                attempts, accepts = self.field_exchange_statistics
+                lower = np.arange(parity, len(attempts), 2)  # the lower instance of every pair of this round
+                attempts[lower] += 1
+                accepts[lower] += accepted[lower]
             t = stop
 
     def run(self, model: IsingModel, measure_overlaps: bool = False, worldline_clusters: Optional[bool] = None,
@@ -214,8 +285,9 @@ class SimulatedQuantumAnnealing:
         self.cluster_statistics = np.zeros(3, np.int64) if clusters else None
         P, G, n = int(cfg.n_slices), int(cfg.n_instances), model.n_spins
         R = P * G
-        k = cfg.couplings()
+        k = cfg.couplings() if cfg.field_ladder is None else cfg.couplings_by_instance()
         gam = cfg.transverse_field.gammas(cfg.n_sweeps)
+        self.field_exchange_statistics = (np.zeros(G - 1, np.int64), np.zeros(G - 1, np.int64)) if cfg.field_exchange_interval else None
         dev_idx = cfg.device_index if cfg.device_index is not None else _device_index(model.device)
         t_start = time.time()
         energy_history, temp_history, acc_history = [], [], []
@@ -243,6 +315,10 @@ class SimulatedQuantumAnnealing:
                 acc_history.append(float((acc - acc_prev).sum()) / float(R * n * ns))
                 acc_prev = acc
             self.final_energies = eng.energies().reshape(G, P)
+            self.time_links = eng.time_links(P)
+            ladder = 1.0 if cfg.field_ladder is None else np.asarray(cfg.field_ladder, np.float64)
+            self.transverse_magnetization = np.asarray(transverse_magnetization(
+                self.time_links, n, P, ladder * float(gam[-1]), float(cfg.temperature)), np.float64)
             if measure_overlaps:
                 self.slice_overlaps = eng.overlaps()
             best_energy, best_configuration, _ = eng.best()
@@ -264,12 +340,15 @@ class QuantumFluctuations:
 
     def __init__(self, base_annealer=None, transverse_field_schedule: str = "linear_decrease", initial_field_strength: float = 5.0,
                  final_field_strength: float = 0.01, n_instances: int = 1, worldline_clusters: bool = False,
-                 dense_couplings: bool = False, dense_worldline_clusters: bool = False):
+                 dense_couplings: bool = False, dense_worldline_clusters: bool = False,
+                 field_ladder: Optional[Sequence[float]] = None, field_exchange_interval: int = 0):
         self.base_annealer = base_annealer
         self.n_instances = int(n_instances)
         self.worldline_clusters = bool(worldline_clusters)
         self.dense_couplings = bool(dense_couplings)
         self.dense_worldline_clusters = bool(dense_worldline_clusters)
+        self.field_ladder = None if field_ladder is None else tuple(float(c) for c in field_ladder)
+        self.field_exchange_interval = field_exchange_interval
         self.field = TransverseField(transverse_field_schedule, float(initial_field_strength),
                                      min(float(final_field_strength), float(initial_field_strength)))
         self.last = None  # the SimulatedQuantumAnnealing of the last call (final_energies, slice_overlaps)
@@ -284,7 +363,8 @@ class QuantumFluctuations:
             n_slices=int(P), n_instances=self.n_instances, temperature=float(T), n_sweeps=int(self._base("n_sweeps", 1000)),
             transverse_field=tf, seed=self._base("random_seed", None), measure_interval=int(self._base("record_interval", 10)),
             device_index=self._base("device_index", None), worldline_clusters=self.worldline_clusters,
-            dense_couplings=self.dense_couplings, dense_worldline_clusters=self.dense_worldline_clusters)
+            dense_couplings=self.dense_couplings, dense_worldline_clusters=self.dense_worldline_clusters,
+            field_ladder=self.field_ladder, field_exchange_interval=self.field_exchange_interval)
         self.last = SimulatedQuantumAnnealing(cfg)
         return self.last.run(model)
 
