@@ -1,4 +1,5 @@
-"""A/B rounds of a timing script (transverse_timing.py, transverse_dense_timing.py, worldline_timing.py --ab LABEL): one
+"""A/B rounds of a timing script (the scripts that take --ab LABEL: the simulated-quantum-annealing ones and those of the
+replica measurements and moves): one
 run times one library -- the tree's, or the one SGA_LIBRARY_PATH names -- and appends its figures as a round under
 doc["ab_rounds"][LABEL][cell]; two libraries alternate in one session by alternating runs.  Nothing else of the file is
 touched.  doc["ab_rounds"]["summary"][cell][figure][LABEL] is rewritten with every round: the median of the rounds'

@@ -23,6 +23,8 @@ Figures per shape, median [min, max] ms of `--reps` (20) calls after `--warmup` 
 class_overlaps.hip was compiled with -DSGA_CLASS_OVERLAP_SHORTCUT=0 | 1 (the ballot shortcut) and
 -DSGA_CLASS_OVERLAP_MAX_COPIES=1 | 4 (the copies of the counters) and linked with the other objects as they are; the
 committed file holds all four as shortcut<S>_copies<K>.
+`--ab LABEL`: ladder_sum12_ms, ladder_sum1_ms and pair_form_host_ms (the pair form of --host-pairs pairs, map and result on the host) alone, of the library in use (SGA_LIBRARY_PATH), appended as one round under
+doc["ab_rounds"][LABEL][shape] (profiles/ab_rounds.py); nothing else of the file changes.
 usage: class_overlaps_timing.py [--reps 20] [--warmup 3] [--shape lattice_22|c3|both] [--variant NAME] [--out FILE] [--no-write]"""
 import argparse
 import json
@@ -96,6 +98,11 @@ def measure(name, graph, classes, n_classes, slots, presweeps, a):
         zmap = torch.zeros((1, n), dtype=torch.int32, device="cuda")
         z1 = torch.zeros((1, slots, 1, 1), dtype=torch.int64, device="cuda")
         one_class = event_ms(torch, lambda: e.accumulate_ladder_class_overlaps(zmap, 1, z1), a.warmup, a.reps)
+        if a.ab:  # the two ladder calls, and the pair form with its result on the host
+            pairs = np.stack([sm[:slots], sm[slots:]], axis=1)[:a.host_pairs]
+            figures = {"ladder_sum12_ms": ladder12, "ladder_sum1_ms": ladder1,
+                       "pair_form_host_ms": host_ms(lambda: e.class_overlaps(pairs, classes, n_classes), a.warmup, a.reps)}
+            return {"figures": figures, "library": res["library"]}
         if a.variant:
             return {"ladder_sum12_ms": ladder12, "ladder_sum1_ms": ladder1, "one_class_sum1_ms": one_class, "library": res["library"]}
         res["ladder_sum12_ms"], res["ladder_sum1_ms"], res["one_class_sum1_ms"] = ladder12, ladder1, one_class
@@ -126,6 +133,7 @@ if __name__ == "__main__":
     ap.add_argument("--host-pairs", type=int, default=32)
     ap.add_argument("--shape", default="both", choices=["lattice_22", "c3", "both"])
     ap.add_argument("--variant", default=None)
+    ap.add_argument("--ab", default="", metavar="LABEL")
     ap.add_argument("--no-write", action="store_true")
     ap.add_argument("--out", default=OUT)
     a = ap.parse_args()
@@ -138,7 +146,10 @@ if __name__ == "__main__":
             doc = json.load(f)
 
     def keep(shape, res):
-        if a.variant:
+        if a.ab:
+            import ab_rounds
+            ab_rounds.append(doc, a.ab, shape, res["figures"], res["library"])
+        elif a.variant:
             doc.setdefault(shape, {}).setdefault("variants", {})[a.variant] = res
         else:
             res["variants"] = doc.get(shape, {}).get("variants", {})

@@ -19,6 +19,8 @@ Figures, on ONE engine that runs on torch's stream so that torch events bracket 
 --c3 runs the other measurement: ms per sweep of bench.py's C3 graph (n = 10^4, degree ~32, 4096 replicas), 16 timed
 sweeps after 16, kernel time from enable_timing, in a process of its own per run, this library and --baseline-lib (the
 parent commit's build, through SGA_LIBRARY_PATH) alternating, three runs each: the one-model line must not move.
+`--ab LABEL`: cluster_all_ms and cluster_all_host_sizes_ms (the sizes on the host) alone, of the library in use (SGA_LIBRARY_PATH), appended as one round under
+doc["ab_rounds"][LABEL]["lattice_22"] (profiles/ab_rounds.py); nothing else of the file changes.
 usage: cluster_moves_timing.py [--reps 20] [--warmup 3] [--c3 --baseline-lib build/libsga_parent.so] [--no-write]"""
 import argparse
 import json
@@ -110,14 +112,19 @@ def main_cluster(a):
         for _ in range(120):
             e.sweep(10)
             e.exchange(count=False)
-        res["describe"] = e.describe()
-        res["sweep_ms"] = event_ms(torch, lambda: e.sweep(1), a.warmup, a.reps)
-        res["energy_pass_ms"] = event_ms(torch, e.recompute_energies, a.warmup, a.reps)
         rnd = [100]
 
         def call(lo, hi, out):
             rnd[0] += 1
             e.cluster_move_ladders(lo, hi, round=rnd[0], sizes=out)
+        if a.ab:  # the move of all slots with its sizes left on the device, and with the sizes on the host
+            out_all = torch.zeros(SLOTS, dtype=torch.int32, device="cuda")
+            figures = {"cluster_all_ms": event_ms(torch, lambda: call(0, SLOTS, out_all), a.warmup, a.reps),
+                       "cluster_all_host_sizes_ms": event_ms(torch, lambda: call(0, SLOTS, True), a.warmup, a.reps)}
+            return {"figures": figures, "library": os.path.basename(sg._native.library_path())}
+        res["describe"] = e.describe()
+        res["sweep_ms"] = event_ms(torch, lambda: e.sweep(1), a.warmup, a.reps)
+        res["energy_pass_ms"] = event_ms(torch, e.recompute_energies, a.warmup, a.reps)
         # one call of all slots held against the host reference on some of its pairs, and its sizes
         sm, S = e.slot_map(), e.spins()
         pairs = [(int(sm[s]), int(sm[SLOTS + s])) for s in range(SLOTS)]
@@ -206,6 +213,7 @@ if __name__ == "__main__":
     ap.add_argument("--c3", action="store_true")
     ap.add_argument("--c3-worker", action="store_true")
     ap.add_argument("--baseline-lib", default=os.path.join(ROOT, "build", "libsga_parent.so"))
+    ap.add_argument("--ab", default="", metavar="LABEL")
     ap.add_argument("--no-write", action="store_true")
     ap.add_argument("--out", default=OUT)
     a = ap.parse_args()
@@ -218,6 +226,10 @@ if __name__ == "__main__":
             doc = json.load(f)
     if a.c3:
         doc["c3_one_model_line"] = main_c3(a)
+    elif a.ab:
+        import ab_rounds
+        got = main_cluster(a)
+        ab_rounds.append(doc, a.ab, "lattice_22", got["figures"], got["library"])
     else:
         doc["lattice_22"] = main_cluster(a)
     print(json.dumps(doc, indent=1))

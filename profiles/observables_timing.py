@@ -18,7 +18,9 @@ that ends in a synchronisation, on ONE engine in ONE process:
   c_spins_torch_f32_ms      e.spins(), the array moved back onto the device with torch, a float32 matmul, waited for
 The three routes must agree: the device result is compared with (c) in full and with (b) on its rows.
 Each shape runs in a process of its own under a time limit; after a failed shape nothing more is started.
-usage: observables_timing.py [--reps 20] [--warmup 3] [--shapes c2a,c3,c5_1000] [--no-write]"""
+`--ab LABEL`: overlaps_ms, overlaps_device_out_ms and magnetizations_ms alone, of the library in use (SGA_LIBRARY_PATH), appended as one round under
+doc["ab_rounds"][LABEL][shape] (profiles/ab_rounds.py); nothing else of the file changes.
+usage: observables_timing.py [--reps 20] [--warmup 3] [--shapes c2a,c3,c5_1000] [--ab LABEL] [--no-write]"""
 import argparse
 import json
 import os
@@ -31,6 +33,7 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "profiles"))
 OUT = os.path.join(ROOT, "profiles", "observables.json")
 SHAPES = {"c2a": (10000, 1024), "c3": (10000, 4096), "c5_1000": (1000 * 1000, 256)}
 B_MACS = 4e9  # multiply-adds of the int32 numpy product that is actually timed
@@ -68,7 +71,7 @@ def median_ms(fn, warmup, reps):
     return float(np.median(times)), float(min(times)), float(max(times))
 
 
-def worker(shape, warmup, reps):
+def worker(shape, warmup, reps, ab=False):
     import torch
     import spin_glass_anneal_rl_amd as sg
     torch.zeros(1, device="cuda")
@@ -89,6 +92,10 @@ def worker(shape, warmup, reps):
             torch.cuda.synchronize()
             return Q
 
+        if ab:
+            calls = (("overlaps_ms", e.overlaps), ("overlaps_device_out_ms", device_out), ("magnetizations_ms", e.magnetizations))
+            return {"figures": {key: list(median_ms(fn, warmup, reps)) for key, fn in calls},
+                    "library": os.path.basename(sg._native.library_path())}
         for key, fn in (("overlaps_ms", e.overlaps), ("overlaps_device_out_ms", device_out),
                         ("magnetizations_ms", e.magnetizations), ("a_spins_ms", e.spins), ("c_spins_torch_f32_ms", via_torch)):
             res[key], res[key + "_min"], res[key + "_max"] = median_ms(fn, warmup, reps)
@@ -113,7 +120,7 @@ def worker(shape, warmup, reps):
 
 
 def plan_of(n, R, cus=256):
-    """observables_plan (csrc/sga_kernels.h), restated: tests/test_observables_host.py pins it."""
+    """observables_plan (csrc/sga_replicas.h), restated: tests/test_observables_host.py pins it."""
     tiles = -(-R // 128)
     s = min(-(-2 * cus // (tiles * tiles)), -(-n // 512))
     per = -(-n // s)
@@ -127,6 +134,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--shapes", default=",".join(SHAPES))
     ap.add_argument("--limit", type=int, default=400, help="seconds a shape's process may take")
+    ap.add_argument("--ab", default="", metavar="LABEL")
     ap.add_argument("--no-write", action="store_true")
     ap.add_argument("--worker")
     ap.add_argument("--out")
@@ -134,7 +142,7 @@ def main():
     if a.reps < 20 and not a.no_write:
         sys.exit("a written result is a median of at least 20 (use --no-write for a shorter trial)")
     if a.worker:
-        res = worker(a.worker, a.warmup, a.reps)
+        res = worker(a.worker, a.warmup, a.reps, bool(a.ab))
         with open(a.out, "w") as f:
             json.dump(res, f)
         return
@@ -143,18 +151,29 @@ def main():
     out = {"device": torch.cuda.get_device_name(0), "library_version": int(sg._native.lib().sga_version()),
            "note": "ms per call: median of `reps` host-clocked calls after `warmup`, each ending in a synchronisation; "
                    "b = a + the int32 numpy product timed on b_rows_timed replicas against all, scaled by R / b_rows_timed"}
+    rounds = []
     fd, tmp = tempfile.mkstemp(suffix=".json")
     os.close(fd)
     for shape in a.shapes.split(","):
         cmd = [sys.executable, os.path.abspath(__file__), "--worker", shape, "--out", tmp, "--reps", str(a.reps), "--warmup",
-               str(a.warmup)] + (["--no-write"] if a.no_write else [])
+               str(a.warmup)] + (["--no-write"] if a.no_write else []) + (["--ab", a.ab] if a.ab else [])
         proc = subprocess.run(cmd, timeout=a.limit)
         if proc.returncode != 0:  # (nothing more is started on the device after a failed shape)
             sys.exit(f"shape {shape} failed with status {proc.returncode}")
         with open(tmp) as f:
             out[shape] = json.load(f)
+        if a.ab:
+            rounds.append((shape, out.pop(shape)))
+            continue
         print(f"{shape}: " + json.dumps({k: round(v, 3) for k, v in out[shape].items() if k.endswith("_ms")}), flush=True)
     os.remove(tmp)
+    if a.ab:  # the rounds alone, into the file as it stands
+        import ab_rounds
+        with open(OUT) as f:
+            out = json.load(f)
+        for shape, got in rounds:
+            ab_rounds.append(out, a.ab, shape, got["figures"], got["library"])
+            print(f"{shape} [{a.ab}]: " + json.dumps({k: round(v[0], 3) for k, v in got["figures"].items()}), flush=True)
     if not a.no_write:
         with open(OUT, "w") as f:
             json.dump(out, f, indent=1)

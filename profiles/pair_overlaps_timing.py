@@ -16,6 +16,8 @@ Figures per shape, median [min, max] ms of `--reps` (20) calls after `--warmup` 
   host_route_ms        what a user did before: spins() and slot_map() (host clocked), then per pair a numpy count over
                        the stored entries, timed on the first `--host-pairs` (32) pairs and scaled to all slots; the counts
                        are compared with one device call's histograms through tests/overlap_reference.py
+`--ab LABEL`: ladder_links_ms, ladder_spins_ms, link_count_ms and pairs_host_ms (the pair form of --host-pairs pairs, results on the host) alone, of the library in use (SGA_LIBRARY_PATH), appended as one round under
+doc["ab_rounds"][LABEL][shape] (profiles/ab_rounds.py); nothing else of the file changes.
 usage: pair_overlaps_timing.py [--reps 20] [--warmup 3] [--shape lattice_22|c3|both] [--out FILE] [--no-write]"""
 import argparse
 import json
@@ -87,6 +89,13 @@ def measure(name, graph, slots, presweeps, a):
         t_pair = (time.perf_counter() - t0) * 1e3 / max(a.host_pairs, 1)
         for s, (d, b) in enumerate(counted):
             assert got_q[s, d >> qs] == 1 and got_q[s].sum() == 1 and got_l[s, b >> ls] == 1 and got_l[s].sum() == 1, s
+        if a.ab:  # the device calls, and the two whose results land on the host
+            pairs = np.stack([sm[:slots], sm[slots:]], axis=1)[:a.host_pairs]
+            figures = {"ladder_links_ms": event_ms(torch, lambda: e.accumulate_ladder_overlaps(hq, hl, q_shift=qs, l_shift=ls), a.warmup, a.reps),
+                       "ladder_spins_ms": event_ms(torch, lambda: e.accumulate_ladder_overlaps(hq, q_shift=qs), a.warmup, a.reps),
+                       "link_count_ms": host_ms(e.link_count, a.warmup, a.reps),
+                       "pairs_host_ms": host_ms(lambda: e.pair_overlaps(pairs), a.warmup, a.reps)}
+            return {"figures": figures, "library": os.path.basename(sg._native.library_path())}
         res["host_route_ms"] = {"spins_copy": t_spins, "slot_map": t_map, "per_pair": t_pair, "pairs_timed": a.host_pairs,
                                 "all_slots_scaled": t_spins + t_map + t_pair * slots}
         res["spins_ms"] = host_ms(e.spins, 1, 5)
@@ -109,6 +118,7 @@ if __name__ == "__main__":
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--host-pairs", type=int, default=32)
     ap.add_argument("--shape", default="both", choices=["lattice_22", "c3", "both"])
+    ap.add_argument("--ab", default="", metavar="LABEL")
     ap.add_argument("--no-write", action="store_true")
     ap.add_argument("--out", default=OUT)
     a = ap.parse_args()
@@ -119,12 +129,19 @@ if __name__ == "__main__":
     if os.path.exists(a.out):
         with open(a.out) as f:
             doc = json.load(f)
+    def keep(shape, got):
+        if a.ab:
+            import ab_rounds
+            ab_rounds.append(doc, a.ab, shape, got["figures"], got["library"])
+        else:
+            doc[shape] = got
+
     if a.shape in ("lattice_22", "both"):
         from cluster_moves_timing import lattice
-        doc["lattice_22"] = measure("lattice_22", lattice(22, 1), 512, 1200, a)
+        keep("lattice_22", measure("lattice_22", lattice(22, 1), 512, 1200, a))
     if a.shape in ("c3", "both"):
         import bench
-        doc["c3"] = measure("c3", bench.make_sparse_instance(10000, 16, 3), 2048, 200, a)
+        keep("c3", measure("c3", bench.make_sparse_instance(10000, 16, 3), 2048, 200, a))
     print(json.dumps(doc, indent=1))
     if not a.no_write:
         with open(a.out, "w") as f:

@@ -17,6 +17,8 @@ spread the energies again, so every call does about the same work (the achieved 
   reseed              field cache ON: the first sweep after a call (the cached fields are seeded again) and a later one
   host_route_ms       what a user did before: energies(), a numpy plan, spins(), one set_spins() per overwritten slot --
                       the set_spins() part timed on the first `--host-slots` (64) of them and scaled
+`--ab LABEL`: resample_device_ms and resample_host_ms per cell alone, of the library in use (SGA_LIBRARY_PATH), appended as one round under
+doc["ab_rounds"][LABEL][cell] (profiles/ab_rounds.py); nothing else of the file changes.
 usage: resample_timing.py [--reps 20] [--warmup 3] [--no-write]      (the driver; --cell INSTANCE:SHARE runs one cell)"""
 import argparse
 import ctypes as C
@@ -141,6 +143,10 @@ def cell(instance, share, a):
             if rnd[0]:
                 shares.append(float((par_d.cpu().numpy() == np.arange(R)).mean()))
             e.sweep(2)
+        if a.ab:  # the call with its results left on the device, and with them on the host
+            figures = {"resample_device_ms": event_ms(torch, lambda: call(db[0], True), a.warmup, a.reps, between=lambda: e.sweep(2)),
+                       "resample_host_ms": event_ms(torch, lambda: call(db[0], False), a.warmup, a.reps, between=lambda: e.sweep(2))}
+            return {"figures": figures, "library": os.path.basename(N.library_path())}
         res["sweep_ms"] = event_ms(torch, lambda: e.sweep(1), a.warmup, a.reps)
         res["resample_device_ms"] = event_ms(torch, lambda: call(db[0], True), a.warmup, a.reps, between=spread)
         spread()
@@ -203,6 +209,7 @@ if __name__ == "__main__":
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--host-slots", type=int, default=64)
     ap.add_argument("--cell", default=None)
+    ap.add_argument("--ab", default="", metavar="LABEL")
     ap.add_argument("--no-write", action="store_true")
     ap.add_argument("--out", default=OUT)
     a = ap.parse_args()
@@ -211,12 +218,22 @@ if __name__ == "__main__":
         print(json.dumps(cell(inst, float(share), a)))
         sys.exit(0)
     doc = {}
+    if a.ab and os.path.exists(a.out):  # the rounds alone, into the file as it stands
+        with open(a.out) as f:
+            doc = json.load(f)
     for inst, share in CELLS:
         p = subprocess.run([sys.executable, os.path.abspath(__file__), "--cell", f"{inst}:{share}", "--reps", str(a.reps), "--warmup",
-                            str(a.warmup), "--host-slots", str(a.host_slots)], capture_output=True, text=True, timeout=420)
+                            str(a.warmup), "--host-slots", str(a.host_slots)] + (["--ab", a.ab] if a.ab else []),
+                           capture_output=True, text=True, timeout=420)
         if p.returncode != 0:  # nothing more is started after a failed cell
             sys.exit(f"cell {inst}:{share} failed: rc={p.returncode}\n{p.stderr[-3000:]}")
-        doc[f"{inst}_survive_{share}"] = json.loads(p.stdout.strip().splitlines()[-1])
+        got = json.loads(p.stdout.strip().splitlines()[-1])
+        if a.ab:
+            import ab_rounds
+            ab_rounds.append(doc, a.ab, f"{inst}_survive_{share}", got["figures"], got["library"])
+            print(f"{inst}:{share} [{a.ab}]: " + json.dumps(got["figures"]), flush=True)
+            continue
+        doc[f"{inst}_survive_{share}"] = got
         print(json.dumps(doc[f"{inst}_survive_{share}"], indent=1), flush=True)
     if not a.no_write:
         with open(a.out, "w") as f:

@@ -30,6 +30,8 @@ again): single calls, `--reps` times each.
 setting), T = 0.05, 8 instances x 32 slices on the geometric ladder `--ladder LO HI` (0.5 2), with
 field_exchange_interval 5 and without, `--seeds` (4) seeds: the acceptance per pair, the best energy per site of each run
 (key physics_lattice_22_<LO>_<HI>).
+`--ab LABEL`: time_links_device_ms, time_links_host_ms and exchange_ms alone, of the library in use (SGA_LIBRARY_PATH), appended as one round under
+doc["ab_rounds"][LABEL][shape] (profiles/ab_rounds.py); nothing else of the file changes.
 usage: trotter_exchange_timing.py [--reps 20] [--warmup 3] [--presweeps 50] [--host-reps 3] [--shape lattice_22|dense_i8|both]
                                   [--physics 0] [--ladder 0.5 2] [--seeds 4] [--out FILE] [--no-write]"""
 import argparse
@@ -99,6 +101,15 @@ def measure(name, make_engine, sweep_name, slice_T, gamma, a):
         res["time_links_host_ms"] = event_ms(torch, lambda: e.time_links(P), a.warmup, a.reps)
         B = e.time_links(P)
         res["links_share"] = [float(B.min()) / (n * P), float(B.max()) / (n * P)]
+        if a.ab:  # the count with its result on the device and on the host, and the exchange (results on the host)
+            rnd = [1000]
+
+            def exchange_round():
+                rnd[0] += 1
+                e.exchange_transverse(P, k, parity=rnd[0] & 1, round=rnd[0])
+            figures = {key: res[key] for key in ("time_links_device_ms", "time_links_host_ms")}
+            figures["exchange_ms"] = event_ms(torch, exchange_round, a.warmup, a.reps)
+            return {"figures": figures, "library": os.path.basename(sg._native.library_path())}
         res["spin_bytes"] = R * sstride
         res["count_gb_per_s"] = R * sstride / (res["time_links_device_ms"][0] * 1e-3) / 1e9
         res["transverse_ms"] = event_ms(torch, lambda: sweep(1, P, k[None, :]), a.warmup, a.reps)
@@ -188,6 +199,7 @@ if __name__ == "__main__":
     ap.add_argument("--physics", type=int, default=0)
     ap.add_argument("--seeds", type=int, default=4)
     ap.add_argument("--ladder", type=float, nargs=2, default=[0.5, 2.0], metavar=("LO", "HI"))
+    ap.add_argument("--ab", default="", metavar="LABEL")
     ap.add_argument("--no-write", action="store_true")
     ap.add_argument("--out", default=OUT)
     a = ap.parse_args()
@@ -198,8 +210,16 @@ if __name__ == "__main__":
     if os.path.exists(a.out):
         with open(a.out) as f:
             doc = json.load(f)
-    from spin_glass_anneal_rl_amd.engine import probe_read_bandwidth
-    doc["read_probe_gb_per_s"] = probe_read_bandwidth(0)
+    if not a.ab:
+        from spin_glass_anneal_rl_amd.engine import probe_read_bandwidth
+        doc["read_probe_gb_per_s"] = probe_read_bandwidth(0)
+
+    def keep(shape, got):
+        if a.ab:
+            import ab_rounds
+            ab_rounds.append(doc, a.ab, shape, got["figures"], got["library"])
+        else:
+            doc[shape] = got
 
     def lattice_engine(sg, torch):
         from cluster_moves_timing import lattice
@@ -221,9 +241,9 @@ if __name__ == "__main__":
         return e
 
     if a.shape in ("lattice_22", "both"):
-        doc["lattice_22"] = measure("lattice_22", lattice_engine, "sweep_transverse", P * 0.05, 1.0, a)
+        keep("lattice_22", measure("lattice_22", lattice_engine, "sweep_transverse", P * 0.05, 1.0, a))
     if a.shape in ("dense_i8", "both"):
-        doc["dense_i8"] = measure("dense_i8", dense_engine, "sweep_transverse_dense", 30.0, 30.0, a)
+        keep("dense_i8", measure("dense_i8", dense_engine, "sweep_transverse_dense", 30.0, 30.0, a))
     if a.physics:
         doc["physics_lattice_22_%g_%g" % tuple(a.ladder)] = physics(a)
     print(json.dumps(doc, indent=1))

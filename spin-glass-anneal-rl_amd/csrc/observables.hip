@@ -25,7 +25,7 @@
 // measured at n = 10^4, R = 1024: 0.142 -> 0.087 ms per call).
 //
 // No Philox call: nothing here draws a random number.
-#include "sga_kernels.h"
+#include "sga_replicas.h"
 
 namespace sga {
 

@@ -1,5 +1,5 @@
 // resample.hip -- the resampling step of population annealing (Hukushima and Iba 2003; Machta 2010; Wang, Machta and
-// Katzgraber 2015): sga_resample.  The rule stands in sga_kernels.h (ResampleArgs): weights as 40-bit fixed point, one
+// Katzgraber 2015): sga_resample.  The rule stands in sga_replicas.h (ResampleArgs): weights as 40-bit fixed point, one
 // 64-bit draw per population (sweep_common.h, resample_draw), systematic resampling in 128-bit integer compares,
 // survivors keep their slots.  Integer sums are exact in any order, so the plan is a function of the energies, dbeta,
 // the seed and the round alone, whatever the launch shape.
@@ -11,7 +11,7 @@
 //      most), so n_r = F_r - F_{r-1}, and the thread's count of n_r == 0;
 //   C  SP_r = the surplus copies of members 0 ... r = F_r - (r + 1) + Z_r, and the rank of every slot without a child;
 //   D  (members strided) the j-th slot without a child takes the j-th entry of the surplus list: the smallest r with
-//      SP_r > j, a search over SP[]; with it the flag of the best (sga_kernels.h, take_best).
+//      SP_r > j, a search over SP[]; with it the flag of the best (sga_replicas.h, take_best).
 // Copy kernel: a workgroup per overwritten slot and 16 KiB of its row, 16 bytes a lane and access; the first of a slot
 // also moves the energy and the best energy.  It reads parent[] and take_best[] only, which it never writes.
 #include "sweep_common.h"

@@ -369,14 +369,14 @@ const char *sga_last_error(void) { return g_last_error.c_str(); }
 //   2800:    + sga_get_class_overlaps / sga_accumulate_ladder_class_overlaps: the overlap between two replicas resolved
 //            by a class of sites (planes of a lattice, sublattices, communities), the pairs of two ladders read from the
 //            slot map and summed into the caller's first and second moments on the device (class_overlaps.hip; host
-//            side in sga_state.cpp); read only, no engine state, no option
+//            side in sga_replicas.cpp); read only, no engine state, no option
 //   2700:    + sga_get_link_count / sga_get_pair_overlaps / sga_accumulate_ladder_overlaps: spin and link overlaps between
 //            pairs of replicas, the pairs of two ladders read from the slot map and histogrammed on the device
-//            (pair_overlaps.hip; host side in sga_state.cpp); read only, no engine state, no option
+//            (pair_overlaps.hip; host side in sga_replicas.cpp); read only, no engine state, no option
 //   2600:    + sga_resample: the resampling step of population annealing, planned and copied on the device, exact in
-//            integers (resample.hip; host side in sga_state.cpp); no engine state, no option
+//            integers (resample.hip; host side in sga_replicas.cpp); no engine state, no option
 //   2500:    + sga_cluster_move_pairs / sga_cluster_move_ladders: isoenergetic cluster moves between two replicas of one
-//            sparse Hamiltonian (cluster_moves.hip; host side in sga_state.cpp); no engine state, no option
+//            sparse Hamiltonian (cluster_moves.hip; host side in sga_replicas.cpp); no engine state, no option
 //   2400:    + sga_set_replica_groups / sga_get_replica_groups: the row-shared sweep over the tile plan runs contiguous
 //            groups of replicas as pipelines of their own, a stream each (sweep_dense_rs.hip; " groups=G" behind
 //            sga_describe and sga_get_last_kernel where more than one runs); results unchanged

@@ -3,15 +3,17 @@
 //   sga_engine.cpp    handle, options, replicas, ladder, sweeps, single-site operators, exchange
 //   sga_problem.cpp   sga_set_dense / sga_set_csr / sga_set_tsp: scans, packing, CSR layouts
 //   sga_autotune.cpp  sga_autotune (measured launch geometry / sweep form)
-//   sga_state.cpp     state access, checkpoint / resume, timing, sga_describe, checksum
+//   sga_state.cpp     state access, checkpoint / resume, timing, sga_describe, checksum, route query
+//   sga_replicas.cpp  measurements and moves over the replicas: observables, cluster moves, resampling, pair and class
+//                     overlaps over the pure half (sga_replicas.h: plans, argument records, the checks of the lists)
 //   sga_route.cpp     WHICH form runs: pure functions of the problem's traits and the options, and the cached-field
 //                     modes' sweep-time policy over the acceptance counters (no HIP calls)
 //   sga_classify.cpp  WHICH arithmetic a problem admits: accumulation class, accept table, cached-field eligibility and
 //                     the refusal reasons, pure functions of the set-time scan summaries (no HIP calls)
 //   sga_windows.cpp   the window forms of the dense sweep (row-shared, its tiles, sequential): admission as pure functions
 //                     of WindowTraits, the forms' state by lifetime (WindowState), their scratch and per-call plan
-//   sga_quantum.cpp   simulated quantum annealing: the two transverse sweeps and the world-line clusters over the pure half
-//                     (sga_quantum.h: slice geometry, admission rules)
+//   sga_quantum.cpp   simulated quantum annealing: the two transverse sweeps, the world-line clusters and the exchange along
+//                     the transverse field over the pure half (sga_quantum.h: slice geometry, admission rules)
 // The engine record is split by lifetime.  sga_engine derives from ProblemState (what the next sga_set_* must not see)
 // and ReplicaState (what the next sga_init_replicas must not see), so every member is still e->member; what survives
 // both stays in sga_engine itself.  A sub-record's defaults stand once, in its declaration: its reset releases the
@@ -32,6 +34,7 @@
 #include "sga.h"
 #include "sga_kernels.h"
 #include "sga_quantum.h"
+#include "sga_replicas.h"
 #include "sga_route.h"
 #include "sga_windows.h"
 
@@ -94,6 +97,20 @@ struct Scratch {
     }
 };
 
+// A caller's HOST array into a scratch slot, `at` bytes from its base: the slot grows to `total` bytes (what lies in front
+// of the copy and behind it is the caller's to lay out), one copy on `st`.  src_pitch > 0: `rows` rows of `bytes` bytes,
+// taken src_pitch bytes apart and laid down dst_pitch apart.  (Pageable: the copy has left the buffer on return.)
+inline int stage_host(Scratch &slot, size_t total, size_t at, const void *host, size_t bytes, hipStream_t st, size_t rows = 1,
+                      size_t src_pitch = 0, size_t dst_pitch = 0) {
+    HIPCHK(slot.reserve(total));
+    unsigned char *dst = static_cast<unsigned char *>(slot.ptr) + at;
+    if (src_pitch)
+        HIPCHK(hipMemcpy2DAsync(dst, dst_pitch, host, src_pitch, bytes, rows, hipMemcpyHostToDevice, st));
+    else
+        HIPCHK(hipMemcpyAsync(dst, host, bytes, hipMemcpyHostToDevice, st));
+    return SGA_OK;
+}
+
 // A read-only view of a user buffer on the device: borrowed if it already lives there,
 // otherwise staged into a scratch slot.
 template <typename T>
@@ -106,35 +123,78 @@ struct DevIn {
             ptr = user;
             return SGA_OK;
         }
-        HIPCHK(slot.reserve(count * sizeof(T)));
-        HIPCHK(hipMemcpyAsync(slot.ptr, user, count * sizeof(T), hipMemcpyHostToDevice, st));
+        if (const int rc = stage_host(slot, count * sizeof(T), 0, user, count * sizeof(T), st)) return rc;
         ptr = static_cast<const T *>(slot.ptr);
         staged = true;
         return SGA_OK;
     }
 };
 
-// A device scratch buffer whose contents are copied to a user buffer (host or device).
+template <typename T>
+inline T *slot_at(const Scratch &slot, size_t at = 0) { return reinterpret_cast<T *>(static_cast<unsigned char *>(slot.ptr) + at); }
+inline int refuse_device_ptr(const void *p, const char *name) {
+    return p && is_device_ptr(p) ? fail(SGA_ERR_INVALID, std::string(name) + " must be a host buffer") : SGA_OK;
+}
+
+// A result on its way to a user buffer, on the host or on the device.  ptr is what the kernels write (null: not asked
+// for); deliver() queues the copies of a call's results and waits once where one lands on the host.  It is placed by
+//   init    always through the slot, zero filled (the traces of sga_sweep, which waits itself)
+//   direct  the caller's own buffer where that lies on the device, else the slot (or a place in one the caller reserved)
+//   staged  a place in a slot whatever the caller's buffer is -- and whether or not it is asked for: the kernels write it
+// rows > 0: a 2-D result, `rows` rows of `count` elements, the caller's `pitch` elements apart and the slot's packed.
+// sum_on_host (the caller has refused a device buffer): the copy lands in `landed`, deliver() adds it to the caller's array.
 template <typename T>
 struct DevOut {
-    T *ptr = nullptr;
-    T *user = nullptr;
-    size_t count = 0;
+    T *ptr = nullptr, *user = nullptr;
+    size_t count = 0, rows = 0, pitch = 0;
+    bool host = false;    // the caller's buffer is known to lie on the host: the copy is waited for
+    bool copied = false;  // ptr is not the caller's buffer
+    bool summed = false;
+    std::vector<T> landed;
+    DevOut() = default;
+    DevOut(T *user_, size_t count_, size_t rows_ = 0, size_t pitch_ = 0, bool sum_on_host = false)
+        : user(user_), count(count_), rows(rows_), pitch(pitch_), host(user_ && (sum_on_host || !is_device_ptr(user_))),
+          summed(user_ && sum_on_host) {}
+    size_t bytes() const { return (rows ? rows : 1) * count * sizeof(T); }
+    size_t ld() const { return copied ? count : pitch; }  // of ptr, in elements (2-D)
     int init(Scratch &slot, T *user_, size_t count_, hipStream_t st) {
-        user = user_;
-        count = count_;
+        user = user_, count = count_;
         if (!user || count == 0) return SGA_OK;
         HIPCHK(slot.reserve(count * sizeof(T)));
-        ptr = static_cast<T *>(slot.ptr);
+        staged(slot.ptr);
         HIPCHK(hipMemsetAsync(ptr, 0, count * sizeof(T), st));
         return SGA_OK;
     }
-    int flush(hipStream_t st) {
-        if (!ptr) return SGA_OK;
-        HIPCHK(hipMemcpyAsync(user, ptr, count * sizeof(T), hipMemcpyDefault, st));
+    void direct(void *where) { copied = host, ptr = host ? static_cast<T *>(where) : user; }
+    int direct(Scratch &slot) {
+        if (host) HIPCHK(slot.reserve(bytes()));
+        direct(slot.ptr);
         return SGA_OK;
     }
+    void staged(void *where) { ptr = static_cast<T *>(where), copied = user != nullptr; }
+    int flush(hipStream_t st) {
+        if (!copied) return SGA_OK;
+        const hipMemcpyKind kind = host ? hipMemcpyDeviceToHost : hipMemcpyDefault;
+        if (summed) landed.resize(count);
+        T *to = summed ? landed.data() : user;
+        if (rows)
+            HIPCHK(hipMemcpy2DAsync(to, pitch * sizeof(T), ptr, count * sizeof(T), count * sizeof(T), rows, kind, st));
+        else
+            HIPCHK(hipMemcpyAsync(to, ptr, count * sizeof(T), kind, st));
+        return SGA_OK;
+    }
+    void land() { for (size_t i = 0; i < landed.size(); ++i) user[i] += landed[i]; }
 };
+// The end of a call: the copies of its results in the order given, at most one wait, then the sums on the host.
+template <typename... Outs>
+int deliver(hipStream_t st, Outs &...outs) {
+    int rc = SGA_OK;
+    ((rc = rc != SGA_OK ? rc : outs.flush(st)), ...);
+    if (rc != SGA_OK) return rc;
+    if (((outs.copied && outs.host) || ...)) HIPCHK(hipStreamSynchronize(st));
+    (outs.land(), ...);
+    return SGA_OK;
+}
 
 // ---- the problem: what a setter (sga_set_*) computes and allocates.  None of it is the next problem's, whichever setter
 // that is and whether or not it assigns the member itself: sga_engine::free_problem() -- every setter -- resets the record.
@@ -353,6 +413,14 @@ inline int model_of(const sga_engine *e, int r) {
 // elements between two models' coupling blocks as the kernels add them (SweepArgs::model_stride_j): 0 = one shared matrix
 inline long long model_stride_j(const sga_engine *e) { return e->shared_j ? 0 : (long long)e->n * e->ldj; }
 inline int spins_of(const sga_engine *e, int r) { return e->ragged ? e->model_n[(size_t)model_of(e, r)] : e->n; }
+// The replica geometry and the random stream's seed into an argument record that carries them (ClusterArgs, ResampleArgs,
+// PairOverlapArgs, ClassOverlapArgs, SweepArgs: the members keep their places, a record without seed takes no seed_into).
+template <typename Args>
+inline void geometry_into(Args &a, const sga_engine *e) {
+    a.n = e->n, a.sstride = e->sstride, a.R = e->R, a.replica0 = static_cast<decltype(a.replica0)>(e->replica0);
+}
+template <typename Args>
+inline void seed_into(Args &a, const sga_engine *e) { a.seed_lo = (uint32_t)e->seed, a.seed_hi = (uint32_t)(e->seed >> 32); }
 
 inline int elems_per_chunk(bool i8) { return i8 ? 1024 : 256; }
 // Zeroed (column 0, value 0) entries behind the CSR entry array.  The sweep kernels load a row's entries without

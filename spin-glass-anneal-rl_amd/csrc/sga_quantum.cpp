@@ -1,8 +1,9 @@
 // sga_quantum.cpp -- simulated quantum annealing, the engine half (the pure half: sga_quantum.h): sga_sweep_transverse,
 // sga_sweep_transverse_dense, sga_worldline_clusters, sga_worldline_clusters_dense, sga_get_time_links and
-// sga_exchange_transverse.  None keeps state of its own: the caller's host array is staged in
-// scratch slot 0 (where sga_sweep stages a schedule).  A sweep is two launches on the engine's stream, the even slices'
-// half-sweep and the odd ones'; one launch serves a whole clusters call.
+// sga_exchange_transverse.  None keeps state of its own: the caller's host array is staged in scratch slot 0 (where
+// sga_sweep stages a schedule) by stage_host, results leave through DevOut / deliver (sga_engine_impl.h), as those of the
+// replica calls of sga_replicas.cpp do.  A sweep is two launches on the engine's stream, the even slices' half-sweep and
+// the odd ones'; one launch serves a whole clusters call.
 #include "sga_engine_impl.h"
 
 namespace {
@@ -30,10 +31,6 @@ long long field_row_bytes_of(const sga_engine *e) {
     return e->ldf * (long long)(bits / 8);
 }
 
-int refuse_device_ptr(const void *p, const char *name) {
-    return p && is_device_ptr(p) ? fail(SGA_ERR_INVALID, std::string(name) + " must be a host buffer") : SGA_OK;
-}
-
 // From the admission rule's answer to the device: run = true where the call goes on, else the returned code is the call's.
 int begin_call(sga_engine *e, const char *why, bool invalid, int n_sweeps, bool &run) {
     run = false;
@@ -48,14 +45,20 @@ int begin_call(sga_engine *e, const char *why, bool invalid, int n_sweeps, bool 
     return SGA_OK;
 }
 
-// The caller's host array into scratch slot 0, base; `behind` further bytes are reserved after it, 8-byte aligned, at
-// *behind_at.  (A pageable host array: the copy has left the buffer when the call returns.)
-int stage(sga_engine *e, const void *host, size_t bytes, unsigned char *&base, size_t behind = 0, unsigned char **behind_at = nullptr) {
+// The caller's host array at the base of scratch slot 0, `behind` bytes reserved after it, 8-byte aligned, at *behind_at.
+int stage(sga_engine *e, const void *host, size_t bytes, size_t behind = 0, size_t *behind_at = nullptr) {
     const size_t padded = (bytes + 7) / 8 * 8;
-    HIPCHK(e->scratch[0].reserve(padded + behind));
-    base = static_cast<unsigned char *>(e->scratch[0].ptr);
-    if (behind_at) *behind_at = base + padded;
-    HIPCHK(hipMemcpyAsync(base, host, bytes, hipMemcpyHostToDevice, e->stream));
+    if (behind_at) *behind_at = padded;
+    return stage_host(e->scratch[0], padded + behind, 0, host, bytes, e->stream);
+}
+
+// A launch that did not go out: nothing is known about the sweep's state, the fields, or which rows were traded.
+int launched(sga_engine *e, hipError_t le) {
+    if (le != hipSuccess) {
+        (void)hipStreamSynchronize(e->stream);
+        e->fields_valid = false;
+    }
+    HIPCHK(le);
     return SGA_OK;
 }
 
@@ -64,8 +67,8 @@ sga::SweepArgs replica_args_of(const sga_engine *e) {
     sga::SweepArgs a{};
     a.h = e->h, a.spins = e->spins, a.best_spins = e->best_spins;
     a.energy = e->energy, a.best_energy = e->best_energy, a.rep_temp = e->rep_temp;
-    a.n = e->n, a.sstride = e->sstride, a.R = e->R;
-    a.seed_lo = (uint32_t)e->seed, a.seed_hi = (uint32_t)(e->seed >> 32), a.replica0 = (uint32_t)e->replica0;
+    geometry_into(a, e);
+    seed_into(a, e);
     return a;
 }
 
@@ -73,21 +76,16 @@ sga::SweepArgs replica_args_of(const sga_engine *e) {
 template <typename Launch>
 int run_half_sweeps(sga_engine *e, sga::SweepArgs a, int n_sweeps, int n_slices, int arith, const float *k_perp, Launch launch) {
     const int G = e->R / n_slices;
-    unsigned char *d_k = nullptr;
-    const int rc = stage(e, k_perp, (size_t)n_sweeps * (size_t)G * sizeof(float), d_k);
+    const int rc = stage(e, k_perp, (size_t)n_sweeps * (size_t)G * sizeof(float));
     if (rc != SGA_OK) return rc;
+    const float *d_k = slot_at<const float>(e->scratch[0]);
     a.n_accepted = e->n_acc;
     a.n_sweeps = 1, a.site_mode = SGA_SITE_RANDOM, a.arith = arith, a.rule = SGA_RULE_METROPOLIS;
     for (int kk = 0; kk < n_sweeps; ++kk) {
         a.sweep0 = e->sweeps_done + (uint32_t)kk;
         for (int parity = 0; parity < 2; ++parity) {
-            const sga::TrotterLaunch t{reinterpret_cast<const float *>(d_k) + (size_t)kk * (size_t)G, n_slices, parity, G * (n_slices / 2)};
-            const hipError_t le = launch(a, t);
-            if (le != hipSuccess) {
-                (void)hipStreamSynchronize(e->stream);
-                e->fields_valid = false;  // (a launch that did not go out: nothing is known about the sweep's state)
-            }
-            HIPCHK(le);
+            const sga::TrotterLaunch t{d_k + (size_t)kk * (size_t)G, n_slices, parity, G * (n_slices / 2)};
+            if (const int rc = launched(e, launch(a, t))) return rc;
         }
     }
     std::snprintf(e->last_kernel, sizeof(e->last_kernel), "%s", sga::last_sweep_kernel());
@@ -136,81 +134,66 @@ int sga_sweep_transverse_dense(sga_engine *e, int n_sweeps, int n_slices, int ar
     });
 }
 
-// The thresholds floor(p_bond 2^24), formed here in double, are staged with the group counts behind them.
-int sga_worldline_clusters(sga_engine *e, int n_sweeps, int n_slices, uint32_t round, const double *p_bond, int64_t *stats) {
+namespace {
+
+// Either world-line call: the thresholds floor(p_bond 2^24), formed here in double, are staged with the group counts
+// behind them; one launch; the counts are added to the caller's.  What differs comes in: the admission rule, whether the
+// step is decided on the resident fields (on_fields), the call's view of the couplings and its launch.
+template <typename Check, typename View, typename Launch>
+int worldline_call(sga_engine *e, int n_sweeps, int n_slices, uint32_t round, const double *p_bond, int64_t *stats, Check check,
+                   bool on_fields, View view, Launch launch) {
     if (const int rc = refuse_device_ptr(p_bond, "p_bond")) return rc;
     if (const int rc = refuse_device_ptr(stats, "stats")) return rc;
     bool invalid = true, run = false;
-    const char *why = sga::worldline_check(e != nullptr, trotter_problem_of(e), n_sweeps, n_slices, p_bond, &invalid);
+    const char *why = check(e != nullptr, trotter_problem_of(e), n_sweeps, n_slices, p_bond, &invalid);
     int rc = begin_call(e, why, invalid, n_sweeps, run);
     if (!run) return rc;
+    if (on_fields) {
+        // (SGA_FIELD_CACHE_AUTO: some replicas' fields may be stale while fields_valid stands, as in sga_sweep_transverse_dense)
+        if (e->field_cache == SGA_FIELD_CACHE_AUTO) e->fields_valid = false;
+        rc = ensure_fields(e);
+        if (rc != SGA_OK) return rc;
+    }
     hipStream_t st = e->stream;
     const int G = e->R / n_slices;
     std::vector<uint32_t> thr((size_t)n_sweeps * (size_t)G);
     for (size_t i = 0; i < thr.size(); ++i) thr[i] = sga::worldline_threshold(p_bond[i]);
-    const size_t stats_bytes = (size_t)G * 3 * sizeof(long long);
-    unsigned char *base = nullptr, *d_stats = nullptr;
-    rc = stage(e, thr.data(), thr.size() * sizeof(uint32_t), base, stats_bytes, &d_stats);
+    DevOut<int64_t> counts(stats, (size_t)G * 3, 0, 0, true);  // (a device buffer was refused above: added up on the host)
+    size_t counts_at = 0;
+    rc = stage(e, thr.data(), thr.size() * sizeof(uint32_t), counts.bytes(), &counts_at);
     if (rc != SGA_OK) return rc;
+    if (stats) counts.staged(slot_at<void>(e->scratch[0], counts_at));
     sga::SweepArgs a = replica_args_of(e);
-    a.rowptr64 = e->rowptr64, a.cv = e->cv, a.csr_acc = e->csr_acc;
-    const sga::WorldlineArgs w{reinterpret_cast<const uint32_t *>(base), stats ? reinterpret_cast<long long *>(d_stats) : nullptr,
-                               n_slices, n_sweeps, round};
-    e->fields_valid = false;  // (as after sga_set_spins: the next sweep seeds the cached fields again)
-    const hipError_t le = sga::launch_worldline_clusters(a, w, st);
-    if (le != hipSuccess) (void)hipStreamSynchronize(st);
-    HIPCHK(le);
+    view(a);
+    const sga::WorldlineArgs w{slot_at<const uint32_t>(e->scratch[0]), reinterpret_cast<long long *>(counts.ptr), n_slices, n_sweeps, round};
+    // (the sparse step leaves the fields behind, as sga_set_spins does; the dense one keeps them valid unless its launch fails)
+    if (!on_fields) e->fields_valid = false;
+    if ((rc = launched(e, launch(a, w, st))) != SGA_OK) return rc;
     std::snprintf(e->last_kernel, sizeof(e->last_kernel), "%s", sga::last_sweep_kernel());
-    if (stats) {
-        std::vector<long long> got((size_t)G * 3);
-        HIPCHK(hipMemcpyAsync(got.data(), w.stats, stats_bytes, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        for (size_t i = 0; i < got.size(); ++i) stats[i] += (int64_t)got[i];
-    }
-    return SGA_OK;
+    return deliver(st, counts);
+}
+
+}  // namespace
+
+int sga_worldline_clusters(sga_engine *e, int n_sweeps, int n_slices, uint32_t round, const double *p_bond, int64_t *stats) {
+    return worldline_call(
+        e, n_sweeps, n_slices, round, p_bond, stats, sga::worldline_check, false,
+        [&](sga::SweepArgs &a) { a.rowptr64 = e->rowptr64, a.cv = e->cv, a.csr_acc = e->csr_acc; },
+        [&](const sga::SweepArgs &a, const sga::WorldlineArgs &w, hipStream_t st) { return sga::launch_worldline_clusters(a, w, st); });
 }
 
 // The step of sga_worldline_clusters on the dense rows, decided on the resident fields of every slice: seeded through
 // ensure_fields where they are not valid, updated by the launch for every flip -- they stay valid.
 int sga_worldline_clusters_dense(sga_engine *e, int n_sweeps, int n_slices, uint32_t round, const double *p_bond, int64_t *stats) {
-    if (const int rc = refuse_device_ptr(p_bond, "p_bond")) return rc;
-    if (const int rc = refuse_device_ptr(stats, "stats")) return rc;
-    bool invalid = true, run = false;
-    const char *why = sga::worldline_dense_check(e != nullptr, trotter_problem_of(e), n_sweeps, n_slices, p_bond, &invalid);
-    int rc = begin_call(e, why, invalid, n_sweeps, run);
-    if (!run) return rc;
-    // (SGA_FIELD_CACHE_AUTO: some replicas' fields may be stale while fields_valid stands, as in sga_sweep_transverse_dense)
-    if (e->field_cache == SGA_FIELD_CACHE_AUTO) e->fields_valid = false;
-    rc = ensure_fields(e);
-    if (rc != SGA_OK) return rc;
-    hipStream_t st = e->stream;
-    const int G = e->R / n_slices;
-    std::vector<uint32_t> thr((size_t)n_sweeps * (size_t)G);
-    for (size_t i = 0; i < thr.size(); ++i) thr[i] = sga::worldline_threshold(p_bond[i]);
-    const size_t stats_bytes = (size_t)G * 3 * sizeof(long long);
-    unsigned char *base = nullptr, *d_stats = nullptr;
-    rc = stage(e, thr.data(), thr.size() * sizeof(uint32_t), base, stats_bytes, &d_stats);
-    if (rc != SGA_OK) return rc;
-    sga::SweepArgs a = replica_args_of(e);
-    a.J = e->J_packed, a.ldj = e->ldj;
-    a.fields = e->fields, a.ldf = e->ldf, a.field_bits = e->clf_bits, a.field_scale = e->clf_scale;
-    const sga::WorldlineArgs w{reinterpret_cast<const uint32_t *>(base), stats ? reinterpret_cast<long long *>(d_stats) : nullptr,
-                               n_slices, n_sweeps, round};
-    const int waves = sga::worldline_dense_waves(e->ldj, e->want_i8, (int)e->opt[OPT_CLF_WAVES]);
-    const hipError_t le = sga::launch_worldline_clusters_dense(a, w, e->want_i8, waves, st);
-    if (le != hipSuccess) {
-        (void)hipStreamSynchronize(st);
-        e->fields_valid = false;  // (a launch that did not go out: nothing is known about the fields)
-    }
-    HIPCHK(le);
-    std::snprintf(e->last_kernel, sizeof(e->last_kernel), "%s", sga::last_sweep_kernel());
-    if (stats) {
-        std::vector<long long> got((size_t)G * 3);
-        HIPCHK(hipMemcpyAsync(got.data(), w.stats, stats_bytes, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        for (size_t i = 0; i < got.size(); ++i) stats[i] += (int64_t)got[i];
-    }
-    return SGA_OK;
+    return worldline_call(
+        e, n_sweeps, n_slices, round, p_bond, stats, sga::worldline_dense_check, true,
+        [&](sga::SweepArgs &a) {
+            a.J = e->J_packed, a.ldj = e->ldj;
+            a.fields = e->fields, a.ldf = e->ldf, a.field_bits = e->clf_bits, a.field_scale = e->clf_scale;
+        },
+        [&](const sga::SweepArgs &a, const sga::WorldlineArgs &w, hipStream_t st) {
+            return sga::launch_worldline_clusters_dense(a, w, e->want_i8, sga::worldline_dense_waves(e->ldj, e->want_i8, (int)e->opt[OPT_CLF_WAVES]), st);
+        });
 }
 
 // ---- the exchange between groups along the transverse field (trotter_exchange.hip) ----------------------------------------
@@ -221,18 +204,12 @@ int sga_get_time_links(sga_engine *e, int n_slices, int64_t *links) {
         return fail(invalid ? SGA_ERR_INVALID : SGA_ERR_UNSUPPORTED, why);
     HIPCHK(hipSetDevice(e->device));
     hipStream_t st = e->stream;
-    const size_t bytes = (size_t)(e->R / n_slices) * sizeof(int64_t);
-    const bool on_device = is_device_ptr(links);
-    if (!on_device) HIPCHK(e->scratch[0].reserve(bytes));
-    long long *d_links = on_device ? reinterpret_cast<long long *>(links) : static_cast<long long *>(e->scratch[0].ptr);
-    HIPCHK(hipMemsetAsync(d_links, 0, bytes, st));
-    HIPCHK(sga::launch_time_links(e->spins, e->sstride, e->R, n_slices, d_links, st));
+    DevOut<int64_t> out(links, (size_t)(e->R / n_slices));
+    if (const int rc = out.direct(e->scratch[0])) return rc;
+    HIPCHK(hipMemsetAsync(out.ptr, 0, out.bytes(), st));
+    HIPCHK(sga::launch_time_links(e->spins, e->sstride, e->R, n_slices, reinterpret_cast<long long *>(out.ptr), st));
     std::snprintf(e->last_kernel, sizeof(e->last_kernel), "%s", sga::last_sweep_kernel());
-    if (!on_device) {
-        HIPCHK(hipMemcpyAsync(links, d_links, bytes, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-    }
-    return SGA_OK;
+    return deliver(st, out);
 }
 
 // k_perp is staged in scratch slot 0 with the counts and the flags behind it; the counts, the decision, the swap and the
@@ -248,15 +225,17 @@ int sga_exchange_transverse(sga_engine *e, int n_slices, const float *k_perp, in
     HIPCHK(hipSetDevice(e->device));
     hipStream_t st = e->stream;
     const size_t G = (size_t)(e->R / n_slices);
-    unsigned char *d_k = nullptr, *behind = nullptr;
-    const int rc = stage(e, k_perp, G * sizeof(float), d_k, G * (sizeof(int64_t) + sizeof(int32_t)), &behind);
-    if (rc != SGA_OK) return rc;
-    long long *d_links = reinterpret_cast<long long *>(behind);
-    int *d_flags = reinterpret_cast<int *>(behind + G * sizeof(int64_t));
+    size_t behind = 0;
+    if (const int rc = stage(e, k_perp, G * sizeof(float), G * (sizeof(int64_t) + sizeof(int32_t)), &behind)) return rc;
+    DevOut<int32_t> out_accepted(accepted, G);
+    DevOut<int64_t> out_links(links, G);
+    out_links.staged(slot_at<void>(e->scratch[0], behind));
+    out_accepted.staged(slot_at<void>(e->scratch[0], behind + G * sizeof(int64_t)));
+    long long *d_links = reinterpret_cast<long long *>(out_links.ptr);
     if (e->field_cache == SGA_FIELD_CACHE_AUTO) e->fields_valid = false;
     const bool trade_fields = e->fields_valid && e->fields;
     const sga::SweepArgs a = replica_args_of(e);
-    const sga::TrotterExchangeArgs x{reinterpret_cast<const float *>(d_k), d_links, d_flags, n_slices, parity, round,
+    const sga::TrotterExchangeArgs x{slot_at<const float>(e->scratch[0]), d_links, out_accepted.ptr, n_slices, parity, round,
                                      trade_fields ? e->fields : nullptr, trade_fields ? field_row_bytes_of(e) : 0};
     HIPCHK(hipMemsetAsync(d_links, 0, G * sizeof(int64_t), st));
     HIPCHK(sga::launch_time_links(e->spins, e->sstride, e->R, n_slices, d_links, st));
@@ -264,20 +243,6 @@ int sga_exchange_transverse(sga_engine *e, int n_slices, const float *k_perp, in
     hipError_t le = sga::launch_trotter_exchange_swap(a, x, st);
     std::snprintf(e->last_kernel, sizeof(e->last_kernel), "%s", sga::last_sweep_kernel());
     if (le == hipSuccess) le = sga::launch_update_best(e->energy, e->spins, e->best_energy, e->best_spins, e->sstride, e->R, st);
-    if (le != hipSuccess) {
-        (void)hipStreamSynchronize(st);
-        e->fields_valid = false;  // (a launch that did not go out: nothing is known about which rows were traded)
-    }
-    HIPCHK(le);
-    bool wait = false;
-    if (accepted) {
-        HIPCHK(hipMemcpyAsync(accepted, d_flags, G * sizeof(int32_t), hipMemcpyDefault, st));
-        wait = wait || !is_device_ptr(accepted);
-    }
-    if (links) {
-        HIPCHK(hipMemcpyAsync(links, d_links, G * sizeof(int64_t), hipMemcpyDefault, st));
-        wait = wait || !is_device_ptr(links);
-    }
-    if (wait) HIPCHK(hipStreamSynchronize(st));
-    return SGA_OK;
+    if (const int rc = launched(e, le)) return rc;
+    return deliver(st, out_accepted, out_links);
 }

@@ -1,5 +1,5 @@
-// sga_state.cpp -- state access, checkpoint / resume, measurement and description entry points of the C ABI
-// (include/sga.h): nothing here launches a sweep.
+// sga_state.cpp -- state access, checkpoint / resume, timing, description, checksum and route query entry points of the
+// C ABI (include/sga.h): nothing here launches a sweep.  (The measurements and moves over the replicas: sga_replicas.cpp.)
 #include "sga_engine_impl.h"
 
 extern "C" {
@@ -593,431 +593,6 @@ int sga_get_energies_async(sga_engine *e, double *out_device) {
     if (!is_device_ptr(out_device)) return fail(SGA_ERR_INVALID, "sga_get_energies_async needs a device buffer");
     HIPCHK(hipSetDevice(e->device));
     HIPCHK(hipMemcpyAsync(out_device, e->energy, sizeof(double) * e->R, hipMemcpyDeviceToDevice, e->stream));
-    return SGA_OK;
-}
-
-// ---- replica observables (observables.hip) --------------------------------------------------
-// Read only, and no state of their own: the result of a host `out` goes through the point_out slot, a host `cfg`
-// through point_sites (both grow-only, so the steady-state call allocates nothing), and nothing else of the engine is
-// written -- not the spins, fields, counters, bests, window plan or last_kernel.
-namespace {
-const int8_t *observed_rows(const sga_engine *e, int which) { return which == SGA_SPINS_BEST ? e->best_spins : e->spins; }
-bool observed_which(int which) { return which == SGA_SPINS_CURRENT || which == SGA_SPINS_BEST; }
-const char *observables_ready(const sga_engine *e) {
-    if (e->n <= 0) return "no couplings set";
-    if (e->R <= 0 || !e->spins || !e->best_spins) return "no replicas";
-    return nullptr;
-}
-
-// out[a * ldq + b] = sum_{i < n} A_a[i] B_b[i], A the local replicas' rows; B on the device.  Every argument is checked
-// by the caller; the work goes on the engine's stream, and a host `out` is waited for.
-int observables_product(sga_engine *e, const int8_t *A, const int8_t *B, long long ldb, int rows_b, bool symmetric,
-                        int32_t *out, int64_t ldq) {
-    sga::ObservablesArgs a{};
-    a.A = A, a.B = B;
-    a.lda = e->sstride, a.ldb = ldb;
-    a.rows_a = e->R, a.rows_b = rows_b, a.n = e->n;
-    a.symmetric = symmetric ? 1 : 0;
-    a.plan = sga::observables_plan(e->n, e->R, rows_b, e->cus);
-    const bool on_device = is_device_ptr(out);
-    if (on_device) {
-        a.out = out, a.ldq = ldq;
-    } else {
-        HIPCHK(e->point_out.reserve((size_t)e->R * (size_t)rows_b * sizeof(int32_t)));
-        a.out = static_cast<int *>(e->point_out.ptr), a.ldq = rows_b;
-    }
-    if (a.plan.ksplit > 1)  // the K ranges add into the result
-        HIPCHK(hipMemset2DAsync(a.out, (size_t)a.ldq * sizeof(int32_t), 0, (size_t)rows_b * sizeof(int32_t), (size_t)e->R, e->stream));
-    HIPCHK(sga::launch_observables_product(a, e->stream));
-    if (!on_device) {
-        HIPCHK(hipMemcpy2DAsync(out, (size_t)ldq * sizeof(int32_t), a.out, (size_t)rows_b * sizeof(int32_t),
-                                (size_t)rows_b * sizeof(int32_t), (size_t)e->R, hipMemcpyDeviceToHost, e->stream));
-        HIPCHK(hipStreamSynchronize(e->stream));
-    }
-    return SGA_OK;
-}
-}  // namespace
-
-int sga_get_magnetizations(sga_engine *e, int which, int32_t *out) {
-    if (!e || !out) return fail(SGA_ERR_INVALID, "NULL argument");
-    if (const char *why = observables_ready(e)) return fail(SGA_ERR_INVALID, why);
-    if (!observed_which(which)) return fail(SGA_ERR_INVALID, "which must be SGA_SPINS_CURRENT or SGA_SPINS_BEST");
-    HIPCHK(hipSetDevice(e->device));
-    const bool on_device = is_device_ptr(out);
-    int *d = out;
-    if (!on_device) {
-        HIPCHK(e->point_out.reserve((size_t)e->R * sizeof(int32_t)));
-        d = static_cast<int *>(e->point_out.ptr);
-    }
-    HIPCHK(sga::launch_observables_row_sums(observed_rows(e, which), e->sstride, e->n, e->R, d, e->stream));
-    if (!on_device) {
-        HIPCHK(hipMemcpyAsync(out, d, (size_t)e->R * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
-        HIPCHK(hipStreamSynchronize(e->stream));
-    }
-    return SGA_OK;
-}
-
-int sga_get_overlaps(sga_engine *e, int which_a, int which_b, int32_t *out, int64_t ldq) {
-    if (!e || !out) return fail(SGA_ERR_INVALID, "NULL argument");
-    if (const char *why = observables_ready(e)) return fail(SGA_ERR_INVALID, why);
-    if (!observed_which(which_a) || !observed_which(which_b))
-        return fail(SGA_ERR_INVALID, "which_a / which_b must be SGA_SPINS_CURRENT or SGA_SPINS_BEST");
-    if (ldq < e->R) return fail(SGA_ERR_INVALID, "ldq is smaller than the number of local replicas");
-    HIPCHK(hipSetDevice(e->device));
-    return observables_product(e, observed_rows(e, which_a), observed_rows(e, which_b), e->sstride, e->R, which_a == which_b, out, ldq);
-}
-
-int sga_get_overlaps_with(sga_engine *e, int which, const int8_t *cfg, int64_t ld, int count, int32_t *out, int64_t ldq) {
-    if (!e || !out) return fail(SGA_ERR_INVALID, "NULL argument");
-    if (const char *why = observables_ready(e)) return fail(SGA_ERR_INVALID, why);
-    if (!observed_which(which)) return fail(SGA_ERR_INVALID, "which must be SGA_SPINS_CURRENT or SGA_SPINS_BEST");
-    if (count < 0) return fail(SGA_ERR_INVALID, "count is negative");
-    if (count > 0 && !cfg) return fail(SGA_ERR_INVALID, "cfg is NULL");
-    if (ld < e->n) return fail(SGA_ERR_INVALID, "ld is smaller than n");
-    if (ldq < count) return fail(SGA_ERR_INVALID, "ldq is smaller than count");
-    if (count == 0) return SGA_OK;
-    HIPCHK(hipSetDevice(e->device));
-    const int8_t *B = cfg;
-    long long ldb = ld;
-    if (!is_device_ptr(cfg)) {  // staged with rows 16 bytes apart: the product's wide loads (the pad is masked, not read as data)
-        ldb = ((long long)e->n + 15) / 16 * 16;
-        HIPCHK(e->point_sites.reserve((size_t)count * (size_t)ldb));
-        HIPCHK(hipMemcpy2DAsync(e->point_sites.ptr, (size_t)ldb, cfg, (size_t)ld, (size_t)e->n, (size_t)count, hipMemcpyHostToDevice,
-                                e->stream));
-        B = static_cast<const int8_t *>(e->point_sites.ptr);
-    }
-    return observables_product(e, observed_rows(e, which), B, ldb, count, false, out, ldq);
-}
-
-// ---- isoenergetic cluster moves (cluster_moves.hip) ------------------------------------------
-// No state of their own: a host pair list is staged in scratch slot 7 (as sga_exchange_pairs stages its list), the
-// energies before the move and the touched flags lie in slot 6, a host `sizes` goes through point_out.
-namespace {
-// nullptr where the engine's problem is one the move serves, else why not; *code: the error to return
-const char *cluster_refusal(const sga_engine *e, int *code) {
-    *code = SGA_ERR_INVALID;
-    if (e->n <= 0) return "no couplings set";
-    if (e->R <= 0 || !e->spins) return "no replicas";
-    *code = SGA_ERR_UNSUPPORTED;
-    if (e->tsp) return "cluster moves are not implemented for sga_set_tsp problems (no stored rows to walk)";
-    if (e->groups) return "cluster moves are not implemented for sga_set_groups / sga_set_groups_csr problems (no stored rows to walk)";
-    if (e->ragged) return "cluster moves are not implemented for ragged CSR batches";
-    if (!e->csr || !e->rowptr64 || !e->cv)
-        return "cluster moves need sparse (CSR) couplings: on dense couplings the component is always every differing site";
-    if (e->n > sga::CLUSTER_MAX_N) return "cluster moves: the bitmaps of n sites do not fit LDS (n / 2 bytes of 160 KiB)";
-    return nullptr;
-}
-
-// The move over `count` pairs (a.pairs or a.slot_to_rep set by the caller), the energies and the bests behind it.
-int cluster_move_run(sga_engine *e, sga::ClusterArgs a, int count, uint32_t round, int32_t *sizes) {
-    hipStream_t st = e->stream;
-    const size_t R = (size_t)e->R;
-    HIPCHK(e->scratch[6].reserve(R * (sizeof(double) + sizeof(int))));
-    double *saved = static_cast<double *>(e->scratch[6].ptr);
-    int *touched = reinterpret_cast<int *>(saved + R);
-    const bool sizes_on_device = sizes && is_device_ptr(sizes);
-    if (sizes && !sizes_on_device) HIPCHK(e->point_out.reserve((size_t)count * sizeof(int32_t)));
-    HIPCHK(hipMemcpyAsync(saved, e->energy, R * sizeof(double), hipMemcpyDeviceToDevice, st));
-    HIPCHK(hipMemsetAsync(touched, 0, R * sizeof(int), st));
-    a.spins = e->spins;
-    a.rowptr64 = e->rowptr64;
-    a.cv = e->cv;
-    a.n_accepted = e->n_acc;
-    a.sizes = !sizes ? nullptr : sizes_on_device ? sizes : static_cast<int *>(e->point_out.ptr);
-    a.touched = touched;
-    a.n = e->n;
-    a.sstride = e->sstride;
-    a.R = e->R;
-    a.count = count;
-    a.replica0 = (uint32_t)e->replica0;
-    a.seed_lo = (uint32_t)e->seed;
-    a.seed_hi = (uint32_t)(e->seed >> 32);
-    a.round = round;
-    HIPCHK(sga::launch_cluster_moves(a, st));
-    e->fields_valid = false;
-    // the whole range, as sga_recompute_energies forms it: the same pass, so the same bits; the replicas whose spins did
-    // not change get their energies back
-    int rc = recompute_energy_range(e, 0, e->R);
-    if (rc != SGA_OK) return rc;
-    HIPCHK(sga::launch_cluster_finish(touched, saved, e->energy, e->spins, e->best_energy, e->best_spins, e->sstride, e->R, st));
-    if (sizes && !sizes_on_device) {
-        HIPCHK(hipMemcpyAsync(sizes, a.sizes, (size_t)count * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-    }
-    return SGA_OK;
-}
-}  // namespace
-
-int sga_cluster_move_pairs(sga_engine *e, const int32_t *pairs, int count, uint32_t round, int32_t *sizes) {
-    if (!e || !pairs) return fail(SGA_ERR_INVALID, "NULL argument");
-    int code = SGA_OK;
-    if (const char *why = cluster_refusal(e, &code)) return fail(code, why);
-    if (count < 0) return fail(SGA_ERR_INVALID, "count is negative");
-    if (is_device_ptr(pairs)) return fail(SGA_ERR_INVALID, "pairs must be a host buffer");
-    std::vector<unsigned char> seen((size_t)e->R);
-    const int reps_per_model = e->shared_j && e->n_models > 1 ? e->Rg / e->n_models : 0;
-    if (const char *why = sga::cluster_pairs_check(pairs, count, e->R, e->replica0, reps_per_model, seen.data()))
-        return fail(SGA_ERR_INVALID, why);
-    if (count == 0) return SGA_OK;
-    HIPCHK(hipSetDevice(e->device));
-    // (a pageable host list: the copy has left the caller's buffer when the call returns)
-    HIPCHK(e->scratch[7].reserve((size_t)2 * count * sizeof(int32_t)));
-    HIPCHK(hipMemcpyAsync(e->scratch[7].ptr, pairs, (size_t)2 * count * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
-    sga::ClusterArgs a{};
-    a.pairs = static_cast<const int32_t *>(e->scratch[7].ptr);
-    return cluster_move_run(e, a, count, round, sizes);
-}
-
-int sga_cluster_move_ladders(sga_engine *e, int slot_lo, int slot_hi, uint32_t round, int32_t *sizes) {
-    if (!e) return fail(SGA_ERR_INVALID, "engine is NULL");
-    int code = SGA_OK;
-    if (const char *why = cluster_refusal(e, &code)) return fail(code, why);
-    if (e->n_ladders <= 0 || !e->slot_to_rep) return fail(SGA_ERR_INVALID, "no ladder (call sga_set_ladder)");
-    if (e->n_ladders % 2 != 0) return fail(SGA_ERR_INVALID, "cluster moves between ladders need an even number of ladders");
-    if (e->R != e->Rg) return fail(SGA_ERR_INVALID, "cluster moves between ladders need every replica on this rank (R_local == R_global)");
-    const int L = e->Rg / e->n_ladders;
-    if (slot_lo < 0 || slot_hi > L || slot_lo > slot_hi) return fail(SGA_ERR_INVALID, "slot range outside [0, slots)");
-    if (e->shared_j && e->n_models > 1) {  // a ladder's slots hold its own L replicas: both ladders under one field vector
-        const int reps = e->Rg / e->n_models;
-        for (int c = 0; c < e->n_ladders / 2; ++c)
-            if ((2 * c * L) / reps != ((2 * c + 2) * L - 1) / reps)
-                return fail(SGA_ERR_INVALID, "shared-coupling CSR batch: ladders " + std::to_string(2 * c) + " and " +
-                                                 std::to_string(2 * c + 1) + " lie under two models (their field vectors differ)");
-    }
-    if (slot_lo == slot_hi) return SGA_OK;
-    HIPCHK(hipSetDevice(e->device));
-    sga::ClusterArgs a{};
-    a.slot_to_rep = e->slot_to_rep;
-    a.L = L;
-    a.slot_lo = slot_lo;
-    a.n_slots = slot_hi - slot_lo;
-    return cluster_move_run(e, a, (e->n_ladders / 2) * a.n_slots, round, sizes);
-}
-
-// ---- population annealing: the resampling step (resample.hip) ---------------------------------
-// No state of its own: the plan's arrays (sga_kernels.h, resample_scratch) lie in scratch slot 6 with the staged dbeta
-// behind them, the outputs leave from there; the two kernels follow each other on the engine's stream.
-int sga_resample(sga_engine *e, int n_populations, const double *dbeta, uint32_t round, int32_t *parents, double *shift,
-                 uint64_t *weight_sum) {
-    if (!e || !dbeta) return fail(SGA_ERR_INVALID, "NULL argument");
-    if (e->n <= 0) return fail(SGA_ERR_INVALID, "no couplings set");
-    if (e->R <= 0 || !e->spins || !e->best_spins) return fail(SGA_ERR_INVALID, "no replicas");
-    if (is_device_ptr(dbeta)) return fail(SGA_ERR_INVALID, "dbeta must be a host buffer");
-    if (const char *why = sga::resample_check(n_populations, dbeta, e->R, e->Rg, e->replica0, e->n_models))
-        return fail(SGA_ERR_INVALID, std::string("sga_resample: ") + why);
-    HIPCHK(hipSetDevice(e->device));
-    hipStream_t st = e->stream;
-    const int R = e->R, P = n_populations, N = R / P;
-    const sga::ResampleScratch lay = sga::resample_scratch(R, P);
-    HIPCHK(e->scratch[6].reserve(lay.bytes));
-    unsigned char *s = static_cast<unsigned char *>(e->scratch[6].ptr);
-    sga::ResampleArgs a{};
-    a.energy = e->energy;
-    a.best_energy = e->best_energy;
-    a.C = reinterpret_cast<unsigned long long *>(s + lay.c);
-    a.F = reinterpret_cast<int *>(s + lay.f);
-    a.SP = reinterpret_cast<int *>(s + lay.sp);
-    a.parent = reinterpret_cast<int32_t *>(s + lay.parent);
-    a.take_best = reinterpret_cast<int *>(s + lay.take);
-    a.shift = reinterpret_cast<double *>(s + lay.shift);
-    a.sum = reinterpret_cast<unsigned long long *>(s + lay.sum);
-    double *d_dbeta = reinterpret_cast<double *>(s + lay.dbeta);
-    // (a pageable host array: the copy has left the caller's buffer when the call returns)
-    HIPCHK(hipMemcpyAsync(d_dbeta, dbeta, (size_t)P * sizeof(double), hipMemcpyHostToDevice, st));
-    a.dbeta = d_dbeta;
-    a.N = N;
-    a.n_pop = P;
-    a.gpop0 = (uint32_t)(e->replica0 / N);
-    a.seed_lo = (uint32_t)e->seed;
-    a.seed_hi = (uint32_t)(e->seed >> 32);
-    a.round = round;
-    HIPCHK(sga::launch_resample_plan(a, st));
-    HIPCHK(sga::launch_resample_copy(a.parent, a.take_best, e->spins, e->energy, e->best_spins, e->best_energy, e->sstride, R, st));
-    e->fields_valid = false;  // (as after sga_set_spins: the next sweep seeds the cached fields again)
-    bool wait = false;
-    if (parents) {
-        HIPCHK(hipMemcpyAsync(parents, a.parent, (size_t)R * sizeof(int32_t), hipMemcpyDefault, st));
-        wait = wait || !is_device_ptr(parents);
-    }
-    if (shift) {
-        HIPCHK(hipMemcpyAsync(shift, a.shift, (size_t)P * sizeof(double), hipMemcpyDefault, st));
-        wait = wait || !is_device_ptr(shift);
-    }
-    if (weight_sum) {
-        HIPCHK(hipMemcpyAsync(weight_sum, a.sum, (size_t)P * sizeof(uint64_t), hipMemcpyDefault, st));
-        wait = wait || !is_device_ptr(weight_sum);
-    }
-    if (wait) HIPCHK(hipStreamSynchronize(st));
-    return SGA_OK;
-}
-
-// ---- spin and link overlaps between pairs of replicas (pair_overlaps.hip) ----------------------
-// Read only, under the rule of the replica observables above: a host pair list is staged in point_sites, host results
-// leave through point_out (both grow-only), and nothing else of the engine is written.
-namespace {
-// nullptr where the engine's stored rows are ones the link walk serves (the cluster move's problems; the graph of
-// sga_set_csr_shared is one, whatever the field vectors), else why not
-const char *links_refusal(const sga_engine *e) {
-    if (e->tsp) return "link overlaps are not implemented for sga_set_tsp problems (no stored rows to walk)";
-    if (e->groups) return "link overlaps are not implemented for sga_set_groups / sga_set_groups_csr problems (no stored rows to walk)";
-    if (e->ragged) return "link overlaps are not implemented for ragged CSR batches";
-    if (!e->csr || !e->rowptr64 || !e->cv) return "link overlaps need sparse (CSR) couplings: dense couplings have no stored links";
-    if (e->n > sga::PAIR_OVERLAP_MAX_N) return "link overlaps: the bitmap of n differing sites does not fit LDS (n / 8 bytes of 160 KiB)";
-    return nullptr;
-}
-int link_group_log2(const sga_engine *e) { return sga::pair_overlap_group_log2(e->layout_entries, e->n); }
-}  // namespace
-
-int sga_get_link_count(sga_engine *e, int64_t *n_links) {
-    if (!e || !n_links) return fail(SGA_ERR_INVALID, "NULL argument");
-    if (const char *why = observables_ready(e)) return fail(SGA_ERR_INVALID, why);
-    if (const char *why = links_refusal(e)) return fail(SGA_ERR_UNSUPPORTED, why);
-    HIPCHK(hipSetDevice(e->device));
-    HIPCHK(e->point_out.reserve(sizeof(unsigned long long)));
-    unsigned long long *d = static_cast<unsigned long long *>(e->point_out.ptr);
-    HIPCHK(hipMemsetAsync(d, 0, sizeof(unsigned long long), e->stream));
-    HIPCHK(sga::launch_link_count(e->rowptr64, e->cv, e->n, link_group_log2(e), d, e->stream));
-    HIPCHK(hipMemcpyAsync(n_links, d, sizeof(int64_t), hipMemcpyDefault, e->stream));
-    if (!is_device_ptr(n_links)) HIPCHK(hipStreamSynchronize(e->stream));
-    return SGA_OK;
-}
-
-int sga_get_pair_overlaps(sga_engine *e, int which, const int32_t *pairs, int count, int32_t *dist, int64_t *broken) {
-    if (!e) return fail(SGA_ERR_INVALID, "engine is NULL");
-    if (const char *why = observables_ready(e)) return fail(SGA_ERR_INVALID, why);
-    if (!observed_which(which)) return fail(SGA_ERR_INVALID, "which must be SGA_SPINS_CURRENT or SGA_SPINS_BEST");
-    if (!dist && !broken) return fail(SGA_ERR_INVALID, "dist and broken are both NULL");
-    if (pairs && is_device_ptr(pairs)) return fail(SGA_ERR_INVALID, "pairs must be a host buffer");
-    if (const char *why = sga::pair_overlap_pairs_check(pairs, count, e->R)) return fail(SGA_ERR_INVALID, why);
-    if (broken)
-        if (const char *why = links_refusal(e)) return fail(SGA_ERR_UNSUPPORTED, why);
-    if (count == 0) return SGA_OK;
-    HIPCHK(hipSetDevice(e->device));
-    hipStream_t st = e->stream;
-    const size_t cnt = (size_t)count;
-    // (a pageable host list: the copy has left the caller's buffer when the call returns)
-    HIPCHK(e->point_sites.reserve(2 * cnt * sizeof(int32_t)));
-    HIPCHK(hipMemcpyAsync(e->point_sites.ptr, pairs, 2 * cnt * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    const bool dist_host = dist && !is_device_ptr(dist), broken_host = broken && !is_device_ptr(broken);
-    // host results: [count] int64 b, then [count] int32 d
-    if (dist_host || broken_host) HIPCHK(e->point_out.reserve(cnt * (sizeof(int64_t) + sizeof(int32_t))));
-    long long *stage_b = static_cast<long long *>(e->point_out.ptr);
-    int32_t *stage_d = reinterpret_cast<int32_t *>(stage_b + cnt);
-    sga::PairOverlapArgs a{};
-    a.spins = observed_rows(e, which);
-    a.pairs = static_cast<const int32_t *>(e->point_sites.ptr);
-    a.dist = dist_host ? stage_d : dist;
-    a.broken = broken_host ? stage_b : reinterpret_cast<long long *>(broken);
-    a.links = broken ? 1 : 0;
-    if (a.links) a.rowptr64 = e->rowptr64, a.cv = e->cv, a.group_log2 = link_group_log2(e);
-    a.n = e->n, a.sstride = e->sstride, a.R = e->R, a.count = count, a.replica0 = e->replica0;
-    HIPCHK(sga::launch_pair_overlaps(a, st));
-    if (dist_host) HIPCHK(hipMemcpyAsync(dist, stage_d, cnt * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    if (broken_host) HIPCHK(hipMemcpyAsync(broken, stage_b, cnt * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-    if (dist_host || broken_host) HIPCHK(hipStreamSynchronize(st));
-    return SGA_OK;
-}
-
-int sga_accumulate_ladder_overlaps(sga_engine *e, int slot_lo, int slot_hi, uint64_t *hist_q, int bins_q, int q_shift,
-                                   uint64_t *hist_l, int bins_l, int l_shift) {
-    if (!e) return fail(SGA_ERR_INVALID, "engine is NULL");
-    if (const char *why = observables_ready(e)) return fail(SGA_ERR_INVALID, why);
-    if (const char *why = sga::pair_overlap_hist_check(hist_q != nullptr, bins_q, q_shift, hist_l != nullptr, bins_l, l_shift))
-        return fail(SGA_ERR_INVALID, why);
-    if (!is_device_ptr(hist_q) || (hist_l && !is_device_ptr(hist_l)))
-        return fail(SGA_ERR_INVALID, "the histograms must be device buffers (they stay on the device for the whole run)");
-    if (e->n_ladders <= 0 || !e->slot_to_rep) return fail(SGA_ERR_INVALID, "no ladder (call sga_set_ladder)");
-    if (e->n_ladders % 2 != 0) return fail(SGA_ERR_INVALID, "overlaps between ladders need an even number of ladders");
-    if (e->R != e->Rg) return fail(SGA_ERR_INVALID, "overlaps between ladders need every replica on this rank (R_local == R_global)");
-    const int L = e->Rg / e->n_ladders;
-    if (slot_lo < 0 || slot_hi > L || slot_lo > slot_hi) return fail(SGA_ERR_INVALID, "slot range outside [0, slots)");
-    if (hist_l)
-        if (const char *why = links_refusal(e)) return fail(SGA_ERR_UNSUPPORTED, why);
-    if (slot_lo == slot_hi) return SGA_OK;
-    HIPCHK(hipSetDevice(e->device));
-    sga::PairOverlapArgs a{};
-    a.spins = e->spins;
-    a.slot_to_rep = e->slot_to_rep;
-    a.L = L, a.slot_lo = slot_lo, a.n_slots = slot_hi - slot_lo;
-    a.hist_q = reinterpret_cast<unsigned long long *>(hist_q);
-    a.hist_l = reinterpret_cast<unsigned long long *>(hist_l);
-    a.bins_q = bins_q, a.q_shift = q_shift, a.bins_l = hist_l ? bins_l : 1, a.l_shift = hist_l ? l_shift : 0;
-    a.links = hist_l ? 1 : 0;
-    if (a.links) a.rowptr64 = e->rowptr64, a.cv = e->cv, a.group_log2 = link_group_log2(e);
-    a.n = e->n, a.sstride = e->sstride, a.R = e->R, a.count = (e->n_ladders / 2) * a.n_slots, a.replica0 = e->replica0;
-    HIPCHK(sga::launch_pair_overlaps(a, e->stream));
-    return SGA_OK;
-}
-
-// ---- class-resolved overlaps between pairs of replicas (class_overlaps.hip) -------------------
-// Read only, under the same rule: a host pair list and behind it a host class map are staged in point_sites, a host
-// result leaves through point_out (both grow-only), and nothing else of the engine is written.
-int sga_get_class_overlaps(sga_engine *e, int which, const int32_t *pairs, int count, const int32_t *classes, int64_t ld,
-                           int n_maps, int n_classes, int32_t *dist) {
-    if (!e) return fail(SGA_ERR_INVALID, "engine is NULL");
-    if (const char *why = observables_ready(e)) return fail(SGA_ERR_INVALID, why);
-    if (!observed_which(which)) return fail(SGA_ERR_INVALID, "which must be SGA_SPINS_CURRENT or SGA_SPINS_BEST");
-    if (pairs && is_device_ptr(pairs)) return fail(SGA_ERR_INVALID, "pairs must be a host buffer");
-    if (const char *why = sga::pair_overlap_pairs_check(pairs, count, e->R)) return fail(SGA_ERR_INVALID, why);
-    if (const char *why = sga::class_overlap_args_check(classes != nullptr, dist != nullptr, n_maps, n_classes, ld, e->n))
-        return fail(SGA_ERR_INVALID, why);
-    if (const char *why = sga::class_overlap_unsupported(n_maps, n_classes)) return fail(SGA_ERR_UNSUPPORTED, why);
-    if (count == 0) return SGA_OK;
-    HIPCHK(hipSetDevice(e->device));
-    hipStream_t st = e->stream;
-    const size_t cnt = (size_t)count, mc = (size_t)n_maps * (size_t)n_classes, n = (size_t)e->n;
-    const bool map_host = !is_device_ptr(classes), dist_host = !is_device_ptr(dist);
-    // the pair list, then a host map packed to ld = n rounded up to 4 (pageable host buffers: the copies have left them on return)
-    const size_t pair_bytes = (2 * cnt * sizeof(int32_t) + 15) / 16 * 16;
-    const size_t ld4 = (n + 3) / 4 * 4;  // (rows of the staged map start 16-byte aligned: the kernel loads int4)
-    HIPCHK(e->point_sites.reserve(pair_bytes + (map_host ? (size_t)n_maps * ld4 * sizeof(int32_t) : 0)));
-    unsigned char *stage = static_cast<unsigned char *>(e->point_sites.ptr);
-    HIPCHK(hipMemcpyAsync(stage, pairs, 2 * cnt * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    if (map_host)
-        HIPCHK(hipMemcpy2DAsync(stage + pair_bytes, ld4 * sizeof(int32_t), classes, (size_t)ld * sizeof(int32_t), n * sizeof(int32_t),
-                                (size_t)n_maps, hipMemcpyHostToDevice, st));
-    if (dist_host) HIPCHK(e->point_out.reserve(cnt * mc * sizeof(int32_t)));
-    sga::ClassOverlapArgs a{};
-    a.spins = observed_rows(e, which);
-    a.pairs = reinterpret_cast<const int32_t *>(stage);
-    a.classes = map_host ? reinterpret_cast<const int32_t *>(stage + pair_bytes) : classes;
-    a.ld = map_host ? (long long)ld4 : (long long)ld;
-    a.n_maps = n_maps, a.n_classes = n_classes;
-    a.dist = dist_host ? static_cast<int32_t *>(e->point_out.ptr) : dist;
-    a.n = e->n, a.sstride = e->sstride, a.R = e->R, a.count = count, a.replica0 = e->replica0;
-    HIPCHK(sga::launch_class_overlaps(a, st));
-    if (dist_host) {
-        HIPCHK(hipMemcpyAsync(dist, a.dist, cnt * mc * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-    }
-    return SGA_OK;
-}
-
-int sga_accumulate_ladder_class_overlaps(sga_engine *e, int slot_lo, int slot_hi, const int32_t *classes, int64_t ld, int n_maps,
-                                         int n_classes, uint64_t *sum1, uint64_t *sum2) {
-    if (!e) return fail(SGA_ERR_INVALID, "engine is NULL");
-    if (const char *why = observables_ready(e)) return fail(SGA_ERR_INVALID, why);
-    if (const char *why = sga::class_overlap_args_check(classes != nullptr, sum1 != nullptr, n_maps, n_classes, ld, e->n))
-        return fail(SGA_ERR_INVALID, why);
-    if (!is_device_ptr(classes) || !is_device_ptr(sum1) || (sum2 && !is_device_ptr(sum2)))
-        return fail(SGA_ERR_INVALID, "classes, sum1 and sum2 must be device buffers (they stay on the device for the whole run)");
-    if (e->n_ladders <= 0 || !e->slot_to_rep) return fail(SGA_ERR_INVALID, "no ladder (call sga_set_ladder)");
-    if (e->n_ladders % 2 != 0) return fail(SGA_ERR_INVALID, "overlaps between ladders need an even number of ladders");
-    if (e->R != e->Rg) return fail(SGA_ERR_INVALID, "overlaps between ladders need every replica on this rank (R_local == R_global)");
-    const int L = e->Rg / e->n_ladders;
-    if (slot_lo < 0 || slot_hi > L || slot_lo > slot_hi) return fail(SGA_ERR_INVALID, "slot range outside [0, slots)");
-    if (const char *why = sga::class_overlap_unsupported(n_maps, n_classes)) return fail(SGA_ERR_UNSUPPORTED, why);
-    if (slot_lo == slot_hi) return SGA_OK;
-    HIPCHK(hipSetDevice(e->device));
-    sga::ClassOverlapArgs a{};
-    a.spins = e->spins;
-    a.slot_to_rep = e->slot_to_rep;
-    a.L = L, a.slot_lo = slot_lo, a.n_slots = slot_hi - slot_lo;
-    a.classes = classes, a.ld = (long long)ld, a.n_maps = n_maps, a.n_classes = n_classes;
-    a.sum1 = reinterpret_cast<unsigned long long *>(sum1);
-    a.sum2 = reinterpret_cast<unsigned long long *>(sum2);
-    a.n = e->n, a.sstride = e->sstride, a.R = e->R, a.count = (e->n_ladders / 2) * a.n_slots, a.replica0 = e->replica0;
-    HIPCHK(sga::launch_class_overlaps(a, e->stream));
     return SGA_OK;
 }
 

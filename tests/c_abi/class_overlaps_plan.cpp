@@ -10,7 +10,7 @@
 #include <cstdlib>
 #include <cstring>
 
-#include "sga_kernels.h"
+#include "sga_replicas.h"
 
 int main(int argc, char **argv) {
     if (argc >= 2 && !std::strcmp(argv[1], "lds")) {

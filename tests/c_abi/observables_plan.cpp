@@ -4,7 +4,7 @@
 #include <cstdio>
 #include <cstdlib>
 
-#include "sga_kernels.h"
+#include "sga_replicas.h"
 
 int main(int argc, char **argv) {
     std::printf("tile=%d grain=%d kmin=%d\n", sga::OBS_TILE, sga::OBS_K_GRAIN, sga::OBS_K_MIN);

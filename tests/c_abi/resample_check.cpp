@@ -8,7 +8,7 @@
 #include <cstring>
 #include <vector>
 
-#include "sga_kernels.h"
+#include "sga_replicas.h"
 
 int main(int argc, char **argv) {
     if (argc >= 7 && !std::strcmp(argv[1], "check")) {

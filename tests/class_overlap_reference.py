@@ -52,10 +52,10 @@ def accumulate(sum1, sum2, slot_to_rep, L, S, classes, n_classes, slot_lo=0, slo
 
 
 def copies(mc):
-    """sga_kernels.h, class_overlap_copies: a copy of the counters for each of the four waves where four fit."""
+    """sga_replicas.h, class_overlap_copies: a copy of the counters for each of the four waves where four fit."""
     return 4 if mc <= MAX_MC_4 else 1
 
 
 def lds_bytes(mc):
-    """sga_kernels.h, class_overlap_lds_bytes: the counters, 4 bytes each, nothing else."""
+    """sga_replicas.h, class_overlap_lds_bytes: the counters, 4 bytes each, nothing else."""
     return 4 * copies(mc) * mc

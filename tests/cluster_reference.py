@@ -70,5 +70,5 @@ def move(rowptr, colidx, val, s_a, s_b, seed, round_, gid):
 
 
 def cluster_lds_bytes(n):
-    """sga_kernels.h, cluster_lds_bytes: four bitmaps of ceil(n / 32) words and 64 bytes beside them."""
+    """sga_replicas.h, cluster_lds_bytes: four bitmaps of ceil(n / 32) words and 64 bytes beside them."""
     return 16 * ((n + 31) // 32) + 64

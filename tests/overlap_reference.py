@@ -47,5 +47,5 @@ def accumulate(hist_q, hist_l, slot_to_rep, L, graph, S, slot_lo=0, slot_hi=None
 
 
 def lds_bytes(n, with_links):
-    """sga_kernels.h, pair_overlap_lds_bytes: 64 bytes, and with links a bitmap of ceil(n / 32) words behind them."""
+    """sga_replicas.h, pair_overlap_lds_bytes: 64 bytes, and with links a bitmap of ceil(n / 32) words behind them."""
     return 64 + (4 * ((n + 31) // 32) if with_links else 0)
