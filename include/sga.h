@@ -80,7 +80,7 @@ typedef struct sga_engine sga_engine;
 int sga_create(int device, sga_engine **out);
 void sga_destroy(sga_engine *e);
 const char *sga_last_error(void);
-int sga_version(void);  /* 3300: sga_get_time_links / sga_exchange_transverse (simulated quantum annealing: the broken time links of every Trotter group counted on the device, and one round of replica exchange between neighbouring groups along the transverse field decided on those counts, csrc/trotter_exchange.hip; domain word 8; no option, no engine member); 3200: sga_worldline_clusters_dense (world-line cluster updates on dense couplings: the step of sga_worldline_clusters decided on the resident fields of every slice, a coupling row read only where a segment flips, the fields kept valid, csrc/worldline_clusters_dense.hip; no option, no engine member); 3100: sga_sweep_transverse_dense (simulated quantum annealing on dense couplings: the step of sga_sweep_transverse carried by the cached local fields, a coupling row read on accept only, csrc/sweep_transverse_clf.hip; no option, no engine member); 3000: sga_worldline_clusters (simulated quantum annealing: Swendsen-Wang clusters along imaginary time at one site, flipped under the classical field, one launch per call, csrc/worldline_clusters.hip; domain word 4; no option, no engine member); 2900: sga_sweep_transverse (simulated quantum annealing: the Trotter slices of one instance coupled in the CSR sweep, two half-sweeps per sweep, csrc/sweep_transverse.hip; no option, no engine member); 2800: sga_get_class_overlaps / sga_accumulate_ladder_class_overlaps (the overlap between two replicas resolved by a class of sites, first and second moments per temperature summed on the device, csrc/class_overlaps.hip; read only, no engine state, no option); 2700: sga_get_link_count / sga_get_pair_overlaps / sga_accumulate_ladder_overlaps (spin and link overlaps between pairs of replicas, histogrammed per temperature on the device, csrc/pair_overlaps.hip; read only, no engine state, no option); 2600: sga_resample (the resampling step of population annealing, csrc/resample.hip); 2500: sga_cluster_move_pairs / sga_cluster_move_ladders (isoenergetic cluster moves between replica copies on sparse couplings, csrc/cluster_moves.hip; no engine state, no option); 2400: sga_set_replica_groups / sga_get_replica_groups; 2300: sga_get_magnetizations / sga_get_overlaps / sga_get_overlaps_with (replica observables on the device: the exact integer product of int8 spin rows on the matrix cores, csrc/observables.hip; read only, no engine state); 2200: the row-shared fields in tiles take a plan of their own, one launch per sweep (csrc/sweep_dense_rs.hip, rs_tile_plan_kernel; no change of interface or results); 2100: sga_set_sequential_windows / sga_get_sequential_windows (SGA_SITE_SEQUENTIAL sweeps in windows, the fields of every replica on the matrix cores; csrc/sweep_dense_seq.hip); 2000: the row-shared windows (option "row_shared") serve SGA_RULE_GLAUBER and SGA_RULE_HEAT_BATH too ("rule=glauber" / "rule=heat-bath" in sga_describe and sga_get_last_kernel; the window sga_autotune picks holds for the rule it was timed under); 1900: options "row_shared_fields" and "row_shared_tile_sites" (row-shared fields in tiles of sites, sign-only rows); 1800: option "row_shared_grid", sga_route_query.rs_grid; 1700: sga_set_csr_shared (one set of CSR rows, many field vectors: every one-wave-per-replica CSR form for such batches), sga_route_query.shared_j on SGA_ROUTE_CSR queries; 1600: sga_set_dense_shared (one coupling matrix, many field vectors; row-shared windows, bit-planes and the matrix-core pass for such batches), sga_route_query.shared_j; 1500: sga_get_scan_summary, and sga_set_dense / sga_set_dense_batch / sga_set_csr / sga_set_csr64 / sga_set_csr_batch refuse a NaN or +-Inf in J or h (SGA_ERR_INVALID, "non-finite"); 1400: option "batch_fixed_point" (fixed-point cached local fields for many-model dense batches); 1300: options "ragged_field_cache" and "clf_fixed_point" together (fixed-point cached local fields for ragged CSR batches); 1200: sga_set_groups_csr (group couplings plus a stored sparse remainder); 1100: option "ragged_field_cache" (cached local fields for ragged CSR batches); 1000: sga_set_groups */
+int sga_version(void);  /* 3400: sga_sweep_transverse_dense serves real-valued dense couplings too, on the fixed-point cached fields of option "clf_fixed_point" (D = 2^k J s as exact int32 | int64, any fp32 h; csrc/sweep_transverse_fx.hip; no new entry point, no new option); 3300: sga_get_time_links / sga_exchange_transverse (simulated quantum annealing: the broken time links of every Trotter group counted on the device, and one round of replica exchange between neighbouring groups along the transverse field decided on those counts, csrc/trotter_exchange.hip; domain word 8; no option, no engine member); 3200: sga_worldline_clusters_dense (world-line cluster updates on dense couplings: the step of sga_worldline_clusters decided on the resident fields of every slice, a coupling row read only where a segment flips, the fields kept valid, csrc/worldline_clusters_dense.hip; no option, no engine member); 3100: sga_sweep_transverse_dense (simulated quantum annealing on dense couplings: the step of sga_sweep_transverse carried by the cached local fields, a coupling row read on accept only, csrc/sweep_transverse_clf.hip; no option, no engine member); 3000: sga_worldline_clusters (simulated quantum annealing: Swendsen-Wang clusters along imaginary time at one site, flipped under the classical field, one launch per call, csrc/worldline_clusters.hip; domain word 4; no option, no engine member); 2900: sga_sweep_transverse (simulated quantum annealing: the Trotter slices of one instance coupled in the CSR sweep, two half-sweeps per sweep, csrc/sweep_transverse.hip; no option, no engine member); 2800: sga_get_class_overlaps / sga_accumulate_ladder_class_overlaps (the overlap between two replicas resolved by a class of sites, first and second moments per temperature summed on the device, csrc/class_overlaps.hip; read only, no engine state, no option); 2700: sga_get_link_count / sga_get_pair_overlaps / sga_accumulate_ladder_overlaps (spin and link overlaps between pairs of replicas, histogrammed per temperature on the device, csrc/pair_overlaps.hip; read only, no engine state, no option); 2600: sga_resample (the resampling step of population annealing, csrc/resample.hip); 2500: sga_cluster_move_pairs / sga_cluster_move_ladders (isoenergetic cluster moves between replica copies on sparse couplings, csrc/cluster_moves.hip; no engine state, no option); 2400: sga_set_replica_groups / sga_get_replica_groups; 2300: sga_get_magnetizations / sga_get_overlaps / sga_get_overlaps_with (replica observables on the device: the exact integer product of int8 spin rows on the matrix cores, csrc/observables.hip; read only, no engine state); 2200: the row-shared fields in tiles take a plan of their own, one launch per sweep (csrc/sweep_dense_rs.hip, rs_tile_plan_kernel; no change of interface or results); 2100: sga_set_sequential_windows / sga_get_sequential_windows (SGA_SITE_SEQUENTIAL sweeps in windows, the fields of every replica on the matrix cores; csrc/sweep_dense_seq.hip); 2000: the row-shared windows (option "row_shared") serve SGA_RULE_GLAUBER and SGA_RULE_HEAT_BATH too ("rule=glauber" / "rule=heat-bath" in sga_describe and sga_get_last_kernel; the window sga_autotune picks holds for the rule it was timed under); 1900: options "row_shared_fields" and "row_shared_tile_sites" (row-shared fields in tiles of sites, sign-only rows); 1800: option "row_shared_grid", sga_route_query.rs_grid; 1700: sga_set_csr_shared (one set of CSR rows, many field vectors: every one-wave-per-replica CSR form for such batches), sga_route_query.shared_j on SGA_ROUTE_CSR queries; 1600: sga_set_dense_shared (one coupling matrix, many field vectors; row-shared windows, bit-planes and the matrix-core pass for such batches), sga_route_query.shared_j; 1500: sga_get_scan_summary, and sga_set_dense / sga_set_dense_batch / sga_set_csr / sga_set_csr64 / sga_set_csr_batch refuse a NaN or +-Inf in J or h (SGA_ERR_INVALID, "non-finite"); 1400: option "batch_fixed_point" (fixed-point cached local fields for many-model dense batches); 1300: options "ragged_field_cache" and "clf_fixed_point" together (fixed-point cached local fields for ragged CSR batches); 1200: sga_set_groups_csr (group couplings plus a stored sparse remainder); 1100: option "ragged_field_cache" (cached local fields for ragged CSR batches); 1000: sga_set_groups */
 /* Run on an existing HIP stream (e.g. torch.cuda.current_stream().cuda_stream); NULL = the
  * engine's own stream (default). */
 int sga_set_stream(sga_engine *e, void *hip_stream);
@@ -609,7 +609,7 @@ int sga_accumulate_ladder_class_overlaps(sga_engine *e, int slot_lo, int slot_hi
 int sga_sweep_transverse(sga_engine *e, int n_sweeps, int n_slices, int arith /* SGA_ARITH_* */,
                          const float *k_perp /* host [n_sweeps][R_local / n_slices] */);
 
-/* ---- simulated quantum annealing on dense couplings (version >= 3100; csrc/sweep_transverse_clf.hip) ------------------
+/* ---- simulated quantum annealing on dense couplings (version >= 3100; csrc/sweep_transverse_clf.hip, _fx.hip) ----------
  * The step of sga_sweep_transverse, word for word -- groups, half-sweeps, the production stream, h_eff = h_i + k (float)a
  * in fp32, the Metropolis rule in `arith`, the classical dE on accept, bests after the sweep, counters -- on ONE dense
  * matrix, in the form of the cached-local-field sweep: a moving slice keeps F = scale (J s + h) in LDS and reads a
@@ -627,12 +627,24 @@ int sga_sweep_transverse(sga_engine *e, int n_sweeps, int n_slices, int arith /*
  *   (163 584 bytes): 2.375 n + 512 bytes with int16 fields, 4.375 n + 512 with int32 fields, rows padded to 128 elements:
  *   n <= 68 608 and n <= 37 248.  Option "clf_waves" sets the waves per slice; 0 leaves the cached sweep's choice, taken
  *   over the R_local / 2 workgroups of a launch.
+ *   Fixed-point fields (version >= 3400; csrc/sweep_transverse_fx.hip).  With option "clf_fixed_point" = 1 set before
+ *   sga_set_dense, a dense model the integer form does not take is served on the fixed-point cached fields instead: J in
+ *   one of the exact accumulation classes (integer J; J on a binary grid 2^-k, such as half- and quarter-valued penalty
+ *   encodings), symmetric with a zero diagonal, ANY fp32 h.  D = 2^k J s is kept exactly as int32 | int64 in LDS, h is
+ *   never folded in; the rule sees dot = fp32(2^-k D_i) -- the row kernels' dot, one rounding of the exact row sum --
+ *   and h_eff: metropolis on (dot, s_i, h_eff) in `arith`, exactly the classical fixed-point sweep's call with h_eff in
+ *   place of h_i; on accept E moves by that call's dE for h_i.  Everything said above holds: k = 0 is sga_sweep bit for
+ *   bit, the fields stay valid for the cached sga_sweep and are traded by sga_exchange_transverse.  LDS: 4.375 n + 512
+ *   bytes with int32 fields (n <= 37 248), 8.375 n + 512 with int64 fields (n <= 19 456).  A problem the integer form
+ *   takes keeps the integer kernel whatever the option says; with the option at 0 nothing changes.
  *   SGA_ERR_INVALID, first and with the engine unchanged: exactly what sga_sweep_transverse reports so, in the same words.
  *   SGA_ERR_UNSUPPORTED, with the reason in sga_last_error: sga_set_tsp, sga_set_groups / sga_set_groups_csr, batches
  *   (ragged, shared and stacked), CSR engines -- a sparse matrix that sga_set_dense kept as CSR included: they are
  *   sga_sweep_transverse's --, a dense problem the integer cached-field form does not take (real-valued J, a non-zero
- *   diagonal, asymmetric J, a bound of 2^24 or more: the set-time scan's reason), rules other than Metropolis, a slice
- *   beyond LDS.  World-line clusters on dense couplings are sga_worldline_clusters_dense's.
+ *   diagonal, asymmetric J, a bound of 2^24 or more: the set-time scan's reason) unless the fixed-point form serves it,
+ *   and under option "clf_fixed_point" a problem that form refuses too (J that needs the canonical fp64 order, asymmetric
+ *   J, a diagonal, fields wider than int64: the fixed-point verdict's reason), rules other than Metropolis, a slice beyond
+ *   LDS.  World-line clusters on dense couplings are sga_worldline_clusters_dense's; it does not serve fixed-point fields.
  *   The launches (two per sweep) show in sga_get_last_kernel; sga_enable_timing does not bracket them. */
 int sga_sweep_transverse_dense(sga_engine *e, int n_sweeps, int n_slices, int arith /* SGA_ARITH_* */,
                                const float *k_perp /* host [n_sweeps][R_local / n_slices] */);

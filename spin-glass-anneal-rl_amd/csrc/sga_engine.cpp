@@ -347,6 +347,9 @@ extern "C" {
 
 const char *sga_last_error(void) { return g_last_error.c_str(); }
 // The ABI version, one line per step:
+//   3400:    sga_sweep_transverse_dense serves real-valued dense couplings on the fixed-point cached fields of option
+//            "clf_fixed_point" (sweep_transverse_fx.hip: D = 2^k J s as exact int32 | int64, any fp32 h; the admission in
+//            sga_quantum.h, TrotterProblem::fx_bits); no new entry point, no new option, no engine member
 //   3300:    + sga_get_time_links / sga_exchange_transverse: the broken time links of every Trotter group counted on the device
 //            (a grid of site chunks x groups, 16-byte loads, one integer atomic per workgroup) and one round of replica
 //            exchange between neighbouring groups along the transverse field -- counts, decision, swap of spin rows,
@@ -409,7 +412,7 @@ const char *sga_last_error(void) { return g_last_error.c_str(); }
 //   600:     + sga_set_csr_batch / sga_get_batch_model (ragged CSR batches)
 //   round 5: + sga_explain_route / sga_get_route_query, sga_get_last_kernel, sga_get_autotune_table, ladder-local
 //            sga_exchange
-int sga_version(void) { return 3300; }
+int sga_version(void) { return 3400; }
 
 int sga_create(int device, sga_engine **out) {
     if (!out) return fail(SGA_ERR_INVALID, "out is NULL");

@@ -21,6 +21,8 @@ sga::TrotterProblem trotter_problem_of(const sga_engine *e) {
     p.clf_why = e->clf_why;
     p.field_bits = e->clf_bits;
     p.ldf = (e->ldj + 127) / 128 * 128;  // (as ensure_fields lays the rows out)
+    // (option "clf_fixed_point", read when the couplings were set: the verdict on a dense problem the integer form refused)
+    if (!e->csr && !e->implicit() && !e->clf_problem) p.fx_bits = e->clf_fx_bits, p.fx_why = e->clf_fx_why;
     p.R_global = e->Rg;
     return p;
 }
@@ -126,11 +128,15 @@ int sga_sweep_transverse_dense(sga_engine *e, int n_sweeps, int n_slices, int ar
     if (rc != SGA_OK) return rc;
     sga::SweepArgs a = replica_args_of(e);
     a.J = e->J_packed, a.ldj = e->ldj;
-    a.fields = e->fields, a.ldf = e->ldf, a.field_bits = e->clf_bits, a.field_scale = e->clf_scale;
+    // (fixed-point fields, option "clf_fixed_point": D = 2^k J s as int32 | int64, seeded by dense_fields_seed_fx_kernel)
+    const bool fx = e->clf_fx_bits != 0;
+    a.fields = e->fields, a.ldf = e->ldf;
+    a.field_bits = fx ? e->clf_fx_bits : e->clf_bits, a.field_scale = fx ? e->clf_fx_k : e->clf_scale;
     // waves per slice: option "clf_waves", else the cached-field sweep's choice over the workgroups of a launch, R / 2
     const int waves = sga::sweep_clf_waves(e->ldj, e->want_i8, e->R / 2, e->cus, (int)e->opt[OPT_CLF_WAVES]);
     return run_half_sweeps(e, a, n_sweeps, n_slices, arith, k_perp, [&](const sga::SweepArgs &s, const sga::TrotterLaunch &t) {
-        return sga::launch_sweep_transverse_dense(s, t, e->want_i8, waves, e->stream);
+        return fx ? sga::launch_sweep_transverse_dense_fx(s, t, e->want_i8, waves, e->stream)
+                  : sga::launch_sweep_transverse_dense(s, t, e->want_i8, waves, e->stream);
     });
 }
 

@@ -1,9 +1,9 @@
 // sga_quantum.h -- simulated quantum annealing: the Trotter-slice geometry and the admission rules of its calls,
-// sga_sweep_transverse (sweep_transverse.hip), sga_sweep_transverse_dense (sweep_transverse_clf.hip),
+// sga_sweep_transverse (sweep_transverse.hip), sga_sweep_transverse_dense (sweep_transverse_clf.hip, sweep_transverse_fx.hip),
 // sga_worldline_clusters (worldline_clusters.hip), sga_worldline_clusters_dense (worldline_clusters_dense.hip),
 // sga_get_time_links and sga_exchange_transverse (trotter_exchange.hip).  The pure half: no sga_engine and no HIP call, so
-// tests/c_abi/transverse_plan.cpp, transverse_dense_plan.cpp, worldline_plan.cpp, worldline_dense_plan.cpp and
-// trotter_exchange_plan.cpp pin it on the CPU.  The engine half is sga_quantum.cpp: it reads an engine into a
+// tests/c_abi/transverse_plan.cpp, transverse_dense_plan.cpp, transverse_fx_plan.cpp, worldline_plan.cpp,
+// worldline_dense_plan.cpp and trotter_exchange_plan.cpp pin it on the CPU.  The engine half is sga_quantum.cpp: it reads an engine into a
 // TrotterProblem and runs the calls.
 //
 // The local replicas are G = R_local / P contiguous groups of P slices, slice p of group g in row g P + p; replica0 is a
@@ -45,7 +45,8 @@ inline int transverse_waves_per_block(int sstride) {  // 0: a slice's spins do n
 }
 // The dense sweep: one workgroup per moving slice, LDS = fields [ldf] int16 | int32, the slice's spin bits, the two
 // neighbour slices' spin bits (n / 4 bytes), the decision slots -- 2.375 n bytes with int16 fields, 4.375 n with int32
-// fields, plus padding and 512 bytes of slots.
+// fields, plus padding and 512 bytes of slots.  On fixed-point fields (sweep_transverse_fx.hip) they are int32 | int64:
+// 4.375 n | 8.375 n.
 constexpr size_t TRANSVERSE_DENSE_SLOT_BYTES = 2 * 8 * 8 * sizeof(int);  // [2][CLF_MAX_WAVES][CLF_SLOT_INTS]
 __host__ __device__ constexpr long long transverse_dense_bits_bytes(int sstride) { return (sstride / 8 + 15) & ~15; }
 inline size_t transverse_dense_lds_bytes(long long ldf, int fbytes, int sstride) {
@@ -80,6 +81,9 @@ struct TrotterProblem {
     const char *clf_why = nullptr;  // ... where it does not: which condition failed
     int field_bits = 16;            // 16 | 32: the width of the resident fields
     long long ldf = 0;              // elements of a replica's field row
+    // ... on fixed-point fields (option "clf_fixed_point": the dense problems clf_problem does not take)
+    int fx_bits = 0;               // 32 | 64: the fixed-point form admits the problem, D = 2^k J s in that width; 0: it does not
+    const char *fx_why = nullptr;  // the fixed-point verdict's refusal, where the option is on and it refused
     // the exchange between groups
     int R_global = 0;  // the replicas of every rank
 };
@@ -151,11 +155,15 @@ inline const char *transverse_dense_check(bool have_engine, const TrotterProblem
     *invalid = false;
     if (const char *why = trotter_kind_refused(p, "dense transverse sweeps")) return why;
     if (p.csr) return "dense transverse sweeps need dense rows: the engine holds sparse (CSR) couplings, which sga_sweep_transverse serves";
-    if (!p.clf_problem)
+    const bool fx = !p.clf_problem && (p.fx_bits == 32 || p.fx_bits == 64);  // (the integer form keeps what it takes)
+    if (!p.clf_problem && !fx) {
+        if (p.fx_why) return p.fx_why;  // (option "clf_fixed_point" is on and its verdict refused the problem)
         return p.clf_why ? p.clf_why : "dense transverse sweeps need the integer cached-field form (integer symmetric J, zero diagonal)";
+    }
     if (!p.metropolis) return "dense transverse sweeps are implemented for the Metropolis rule only";
-    if ((p.field_bits != 16 && p.field_bits != 32) || p.sstride <= 0 || p.ldf <= 0 ||
-        transverse_dense_lds_bytes(p.ldf, p.field_bits / 8, p.sstride) > TRANSVERSE_LDS_BUDGET)
+    const int bits = fx ? p.fx_bits : p.field_bits;  // the width of the fields the launch keeps in LDS
+    if ((!fx && bits != 16 && bits != 32) || p.sstride <= 0 || p.ldf <= 0 ||
+        transverse_dense_lds_bytes(p.ldf, bits / 8, p.sstride) > TRANSVERSE_LDS_BUDGET)
         return "dense transverse sweeps: a slice's fields, spin bits and neighbour bits do not fit LDS";
     return nullptr;
 }
@@ -229,6 +237,9 @@ hipError_t launch_sweep_transverse(const SweepArgs &a, const TrotterLaunch &t, h
 // ... with the resident fields (fields, ldf, field_bits, field_scale) and the dense rows (J, ldj); the launch reads and
 // writes the moving slices' fields
 hipError_t launch_sweep_transverse_dense(const SweepArgs &a, const TrotterLaunch &t, bool j_is_i8, int waves, hipStream_t st);
+// ... on fixed-point fields (sweep_transverse_fx.hip): a.fields = D = 2^k J s, a.field_bits = 32 | 64, a.field_scale = k >= 0;
+// fp32 rows, or int8 rows (integer J, k = 0, int32 fields)
+hipError_t launch_sweep_transverse_dense_fx(const SweepArgs &a, const TrotterLaunch &t, bool j_is_i8, int waves, hipStream_t st);
 struct WorldlineArgs {
     const uint32_t *thr;  // device [n_sweeps][G]
     long long *stats;     // device [G][3], zeroed: segments formed, segments flipped, slice spins flipped (or null)

@@ -596,8 +596,9 @@ class AnnealEngine:
         """sweep_transverse on one dense matrix (sga_sweep_transverse_dense): the same step, carried by the cached local
         fields -- a moving slice keeps its fields in LDS and reads a coupling row only on accept; the fields are seeded
         where they are not valid and stay valid for a cached sweep() after it.  k_perp as in sweep_transverse.  Serves
-        integer symmetric J with a zero diagonal and h in multiples of 1/2 (set_dense); any other problem raises
-        AnnealingError with the engine's reason."""
+        integer symmetric J with a zero diagonal and h in multiples of 1/2 (set_dense); with option "clf_fixed_point" = 1
+        set before set_dense also real-valued symmetric J on a binary grid with a zero diagonal and any h, on exact
+        fixed-point fields (int32 | int64).  Any other problem raises AnnealingError with the engine's reason."""
         G = self._trotter_groups(int(n_slices))
         k = transverse_k_perp(k_perp, n_sweeps, G)
         N.check(self._lib.sga_sweep_transverse_dense(self._h, int(n_sweeps), int(n_slices), int(arith), k.ctypes.data_as(C.c_void_p)),

@@ -22,7 +22,9 @@ Dense couplings (SK glasses, number partitioning, dense QUBO encodings) are an o
 SimulatedQuantumAnnealingConfig(dense_couplings=True) hands the model to the engine as one dense matrix with the field
 cache on and sweeps through AnnealEngine.sweep_transverse_dense (sga_sweep_transverse_dense) -- the same step, a slice's
 local fields resident in LDS and a coupling row read on accept only.  It serves integer symmetric J with a zero diagonal
-and h in multiples of 1/2.  The cluster move beside it is a flag of its own, dense_worldline_clusters=True: every
+and h in multiples of 1/2; with fixed_point_fields=True beside it (engine option "clf_fixed_point") also real-valued J on
+a binary grid -- a QUBO's Q / 4, quarter-valued penalty encodings -- and any h, the fields kept as exact fixed point
+(int32 | int64).  The cluster move beside it is a flag of its own, dense_worldline_clusters=True: every
 cluster_interval-th dense sweep is followed by AnnealEngine.worldline_clusters_dense (sga_worldline_clusters_dense), the
 same cluster step decided on the same cached fields, which stay valid between the two calls.
 
@@ -150,6 +152,9 @@ class SimulatedQuantumAnnealingConfig:
     field_ladder: Optional[Sequence[float]] = None  # multipliers c_g, one per instance: instance g runs at c_g Gamma(t)
     field_exchange_interval: int = 0      # m > 0: every m-th sweep, counted over the run, is followed by one round of
     #                                       replica exchange between neighbouring instances (sga_exchange_transverse)
+    fixed_point_fields: bool = False      # with dense_couplings: engine option "clf_fixed_point" -- dense models the integer
+    #                                       cached-field form does not take (real-valued J on a binary grid, any h) are
+    #                                       swept on exact fixed-point fields; the cluster move does not serve those
 
     def __post_init__(self):
         self.check()
@@ -175,6 +180,11 @@ class SimulatedQuantumAnnealingConfig:
             raise ConfigurationError("dense_worldline_clusters must be True or False")
         if self.dense_worldline_clusters:
             self.check_dense_clusters()
+        if not isinstance(self.fixed_point_fields, (bool, np.bool_)):
+            raise ConfigurationError("fixed_point_fields must be True or False")
+        if self.fixed_point_fields and not self.dense_couplings:
+            raise ConfigurationError("fixed_point_fields needs dense_couplings=True (the transverse sweep on sparse rows keeps "
+                                     "no cached fields)")
         if self.field_ladder is not None:
             c = np.asarray(self.field_ladder, np.float64)
             if c.ndim != 1 or c.size != int(self.n_instances):
@@ -298,9 +308,17 @@ class SimulatedQuantumAnnealing:
                 # one dense matrix with the field cache on: the rows stay dense (the sparse route is taken with the cache
                 # off or left to the engine only); should the engine hold CSR rows all the same, they are sweep_transverse's
                 eng.set_field_cache("on")
+                if cfg.fixed_point_fields:
+                    eng.set_option("clf_fixed_point", 1)  # (read when the couplings are set)
                 J = model.couplings.to_dense() if model.couplings.is_sparse else model.couplings
                 eng.set_dense(J, model.external_fields)
-                dense = eng.route_query().kind != N.ROUTE_CSR
+                rq = eng.route_query()
+                dense = rq.kind != N.ROUTE_CSR
+                if cfg.fixed_point_fields and dense_clusters and dense and not rq.clf_ok and rq.clf_bits in (32, 64):
+                    raise AnnealingError("dense world-line clusters are not served on fixed-point fields: the model landed on "
+                                         "the fixed-point cached fields (int%d), and sga_worldline_clusters_dense decides its "
+                                         "segments on the integer form's fields only (run without dense_worldline_clusters, or "
+                                         "with integer J and h in multiples of 1/2)" % rq.clf_bits)
             else:
                 model.load_into(eng)
             eng.init_replicas(R, seed=fresh_seed(cfg.seed))
@@ -341,12 +359,14 @@ class QuantumFluctuations:
     def __init__(self, base_annealer=None, transverse_field_schedule: str = "linear_decrease", initial_field_strength: float = 5.0,
                  final_field_strength: float = 0.01, n_instances: int = 1, worldline_clusters: bool = False,
                  dense_couplings: bool = False, dense_worldline_clusters: bool = False,
-                 field_ladder: Optional[Sequence[float]] = None, field_exchange_interval: int = 0):
+                 field_ladder: Optional[Sequence[float]] = None, field_exchange_interval: int = 0,
+                 fixed_point_fields: bool = False):
         self.base_annealer = base_annealer
         self.n_instances = int(n_instances)
         self.worldline_clusters = bool(worldline_clusters)
         self.dense_couplings = bool(dense_couplings)
         self.dense_worldline_clusters = bool(dense_worldline_clusters)
+        self.fixed_point_fields = bool(fixed_point_fields)
         self.field_ladder = None if field_ladder is None else tuple(float(c) for c in field_ladder)
         self.field_exchange_interval = field_exchange_interval
         self.field = TransverseField(transverse_field_schedule, float(initial_field_strength),
@@ -364,7 +384,7 @@ class QuantumFluctuations:
             transverse_field=tf, seed=self._base("random_seed", None), measure_interval=int(self._base("record_interval", 10)),
             device_index=self._base("device_index", None), worldline_clusters=self.worldline_clusters,
             dense_couplings=self.dense_couplings, dense_worldline_clusters=self.dense_worldline_clusters,
-            field_ladder=self.field_ladder, field_exchange_interval=self.field_exchange_interval)
+            fixed_point_fields=self.fixed_point_fields, field_ladder=self.field_ladder, field_exchange_interval=self.field_exchange_interval)
         self.last = SimulatedQuantumAnnealing(cfg)
         return self.last.run(model)
 
